@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: LQR solves/sec at (nx=12, nu=4, N=256, batch=1024 per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python bench.py --nx 64 --nu 16 --horizon 512 --batch 256        # BASELINE config 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -29,6 +29,7 @@ Prints ONE JSON line on rank 0 (contract in the task description) with:
                   number of steps: lqr_prob_256.json x 1 (latency, error against the fixture's `soln`),
                   (12,4,1024) x 512 (one GPU's shard of config 4), (64,16,512) x 256 (config 5).
   gather       -- N>1: throughput including the all_gather of every shard's solutions.
+  dump_outputs -- with --dump-outputs DIR: where rank 0's solutions of the last timed step were written (DIR/*.npy).
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own N ranks: this
 process -- before it imports torch or touches a GPU in any way -- runs `python -m torch.distributed.run
@@ -410,6 +411,27 @@ def transfer_legs(rslqr_amd, bs, n, m, N, batch, seed0, steps):
     return out, end_to_end, sol
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname, sol, n, m, N, seed0):
+    """--dump-outputs: the solutions [batch, nvars] (fp64) of the last timed step as DIR/solutions.npy, for comparing
+    two builds output for output (the inputs are the seeded synthetic family, identical from run to run). Above
+    DUMP_MAX_BYTES a fixed sample of whole problems (rows drawn with seed 0, in increasing order) is written instead,
+    with their indices in DIR/solutions_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    batch = sol.shape[0]
+    rows = np.arange(batch)
+    if sol.nbytes > DUMP_MAX_BYTES:
+        keep = max(1, DUMP_MAX_BYTES // (sol.itemsize * sol.shape[1] + 8))
+        rows = np.sort(np.random.default_rng(0).choice(batch, size=min(keep, batch), replace=False))
+        np.save(os.path.join(dirname, "solutions_rows.npy"), rows.astype(np.float64))
+        sol = sol[rows]
+    np.save(os.path.join(dirname, "solutions.npy"), np.ascontiguousarray(sol, dtype=np.float64))
+    return {"dir": dirname, "solutions": list(sol.shape), "sampled": bool(rows.size < batch),
+            "problem_seeds": [int(seed0), int(seed0 + batch - 1)], "workload": [n, m, N, batch]}
+
+
 def launch_ranks(gpus):
     """--gpus N > 1 outside a launcher: start N fresh rank processes (one per GPU) with torch.distributed.run and
     exit with their status. Nothing in this process has touched the GPU (no torch import, no HIP call)."""
@@ -776,7 +798,8 @@ def time_mode(rslqr_amd, n, m, N, batch, device, seed0, flags, steps, rhs_only=F
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default: 100, or 10 where one step is a (64,16,512)-sized solve)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--spin-up-ms", type=float, default=60.0,
                     help="untimed full solves before the warm-up steps until the device has been under load this long (0: none)")
@@ -794,7 +817,13 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="N=1: skip the legs of the other BASELINE configurations")
     ap.add_argument("--config4-batch", type=int, default=512,
                     help="N>1: problems per GPU of the (12,4,1024) leg (512 x 8 GPUs = BASELINE config 4; 0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's solutions of the last timed step to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 10 if rf.model_b_flops(args.nx, args.nu, args.horizon) > 2e9 else 100  # (64,16,512): ~50 ms per step
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.transfer_leg:
         # Child of the N = 1 run (below): the transfer / end-to-end legs in a process of their own that never imports
@@ -854,8 +883,6 @@ def main():
     n, m, N, batch = args.nx, args.nu, args.horizon, args.batch
     steps = args.steps
     big = rf.model_b_flops(n, m, N) > 2e9
-    if big and args.steps == 100:
-        steps = 10  # (64,16,512) x 256: ~50 ms per step
     bs = rslqr_amd.BatchSolver(n, m, N, batch, device=local_rank, flags=args.flags)
     seed0 = sharding.shard_seed0(rank, batch)  # global problem g has seed 1 + g
 
@@ -884,6 +911,10 @@ def main():
     # Timed region: the product path as shipped (launch sequence replayed as a hipGraph).
     elapsed = sharding.timed_region(bs, steps, args.warmup, barrier)
     log("rank %d: %d steps in %.3f s" % (rank, steps, elapsed))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back, copied down before any later solve replaces it
+        dumped = dump_outputs(args.dump_outputs, bs.solutions(), n, m, N, seed0)
     fails = bs.cholesky_failures()
     schedule = bs.schedule()
     # The same K steps strictly stream-ordered (pipeline depth 1: a step starts when the previous one has
@@ -1015,6 +1046,8 @@ def main():
             "transfers": transfers,
             "end_to_end": end_to_end,
         }
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         if gather:
             g_el, g_bad = red[3], red[4]
             result["gather"] = {

@@ -4,6 +4,7 @@ Only tests/, bench.py's cpu_baseline leg and __graft_entry__.smoke() may import 
 Oracle / Reference classes (they are the *checkers*, never the product path).
 """
 import ctypes as C
+import hashlib
 import json
 import os
 import subprocess
@@ -173,6 +174,13 @@ def split_block(fact, prob, k, level):
     st = b[n * n: 2 * n * n].reshape(n, n).T
     inp = b[2 * n * n:].reshape(n, m).T
     return lam, st, inp
+
+
+def digest(a):
+    """Content digest of a float64 array: equal digests = the same values bit for bit, except that -0.0 is read
+    as 0.0 (as np.array_equal does). What tests/golden/reference_trace.json stores of the reference's arrays."""
+    a = np.ascontiguousarray(a, dtype=np.float64) + 0.0
+    return hashlib.sha256(a.tobytes()).hexdigest()
 
 
 def have_reference():
