@@ -43,6 +43,7 @@ static inline ndlqr::Dims apply_dims(const NdlqrHipCtx* c, const ndlqr::Dims& d)
 template <int NX, int NU, bool STRICT, bool KEEP>
 static SmallPlan plan_small(const NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
+  const BufferSet& s = c->set[c->cur];
   SmallPlan p;
   // fast mode without KEEP: solution by back-substitution from the separator records (backsub_small
   // resolves K + 4 separators of NX rows in one 256-thread workgroup)
@@ -53,11 +54,11 @@ static SmallPlan plan_small(const NdlqrHipCtx* c) {
   p.rowbcast = false;
   p.compact = false;
   if constexpr (!STRICT && !KEEP && ndlqr::P1OnMatrixCores<NX, NU>::value) {
-    if (p.lean && c->red) {
+    if (p.lean && s.red) {
       p.reduced = true;
       // tree schedule for small batches (at most half a resident round of bottom wavefronts): three
       // launches instead of K + 1; measured cross-over at batch x N / 4 ~ 4096 wavefronts
-      p.tree = c->tree_cnt && (c->tree == 1 || (c->tree < 0 && (size_t)d.batch * (d.N >> 2) <= 2048));
+      p.tree = s.tree_cnt && (c->tree == 1 || (c->tree < 0 && (size_t)d.batch * (d.N >> 2) <= 2048));
       // compact level-0 records (L of S-bar only) and the two-launch back-substitution: the tree schedule keeps the
       // one-kernel back-substitution; rb_backsub's thread roles need 8 (2 nx + nu) <= 256 (and rb_backsub_top's sweep
       // array, N / 8 multipliers, has to fit the LDS of its one workgroup per problem). With KEEP_RECORDS (round 4): the
@@ -84,6 +85,7 @@ static SmallPlan plan_small(const NdlqrHipCtx* c) {
 template <int NX, int NU, bool STRICT, bool KEEP>
 static int launch_small(NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   using Sh = ndlqr::SchurShape<NX, NU>;
   constexpr int JB = kBottomLevels;
   const SmallPlan plan = plan_small<NX, NU, STRICT, KEEP>(c);
@@ -106,8 +108,8 @@ static int launch_small(NdlqrHipCtx* c) {
         bool launched = false;
         if constexpr (NX <= 16 && NX + NU <= 16) {
           if (plan.rowbcast) {  // one separator per DPP row, four per wavefront
-            hipLaunchKernelGGL((ndlqr::rb_bottom<NX, NU>), dim3(d.N >> 4, d.batch), dim3(64), 0, c->stream, d, c->AB,
-                               c->QR, c->rhs, c->red, c->rec, c->info);
+            hipLaunchKernelGGL((ndlqr::rb_bottom<NX, NU>), dim3(d.N >> 4, d.batch), dim3(64), 0, s.stream, d, c->AB,
+                               c->QR, s.rhs, s.red, s.rec, c->info);
             launched = true;
           }
         }
@@ -121,17 +123,17 @@ static int launch_small(NdlqrHipCtx* c) {
         if (fuse2) c->schedule = "reduced-fused2";
         if (launched) {
         } else if (fuse2) {
-          hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU>), dim3(d.N >> 3, d.batch), dim3(128), 0, c->stream, d,
-                             c->AB, c->QR, c->rhs, c->red, c->rec, c->info);
+          hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream, d,
+                             c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
         } else if (tree)
-          hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, c->stream,
-                             d, c->AB, c->QR, c->rhs, c->red, c->rec, c->F, c->info, store_l, c->tree_cnt, 0);
+          hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
+                             d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, s.tree_cnt, 0);
         else if (compact)
-          hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, c->stream,
-                             d, c->AB, c->QR, c->rhs, c->red, c->rec, c->F, c->info, store_l, nullptr, 1);
+          hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
+                             d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, nullptr, 1);
         else
-          hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false>), dim3(d.N >> 2, d.batch), dim3(64), 0, c->stream,
-                             d, c->AB, c->QR, c->rhs, c->red, c->rec, c->F, c->info, store_l, nullptr, 0);
+          hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
+                             d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, nullptr, 0);
       }
       // upper levels: one launch per level while a level has more than four separators per problem, then the
       // last three levels in one launch (reduced_top_mc; NDLQR_NO_TOP=1: a launch per level to the root)
@@ -139,8 +141,8 @@ static int launch_small(NdlqrHipCtx* c) {
       const int ltop = (d.K >= 5 && !c->no_top) ? d.K - top_levels : d.K;
       for (int l = fuse2 ? 3 : 2; l < ltop && !tree; ++l) {
         ScopedSlot t(c, SLOT_UPPER);
-        hipLaunchKernelGGL((ndlqr::reduced_level_mc<NX, NU>), dim3(d.N >> (l + 1), d.batch), dim3(64), 0, c->stream,
-                           d, l, c->AB, c->QR, c->rhs, c->red, c->rec, c->F, c->info, store_l);
+        hipLaunchKernelGGL((ndlqr::reduced_level_mc<NX, NU>), dim3(d.N >> (l + 1), d.batch), dim3(64), 0, s.stream,
+                           d, l, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l);
       }
       // ... which also runs the top-down sweep over the records of level >= 3 when the back-substitution is the
       // two-launch form and its array fits the workgroup's LDS
@@ -149,8 +151,8 @@ static int launch_small(NdlqrHipCtx* c) {
       if (!tree && ltop < d.K) {
         ScopedSlot t(c, SLOT_TOP);  // (a profile slot of its own: one kernel name per slot, like rocprofv3's per-kernel averages)
         const int l0 = (fuse2 && ltop < 3) ? 3 : ltop;  // (level 2 went with the bottom launch)
-        hipLaunchKernelGGL((ndlqr::reduced_top_mc<NX, NU>), dim3(d.batch), dim3(256), 0, c->stream, d, l0, c->AB,
-                           c->QR, c->rhs, c->red, c->rec, c->F, c->info, store_l, top_sweeps ? c->ytop : (double*)nullptr);
+        hipLaunchKernelGGL((ndlqr::reduced_top_mc<NX, NU>), dim3(d.batch), dim3(256), 0, s.stream, d, l0, c->AB,
+                           c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, top_sweeps ? s.ytop : (double*)nullptr);
       }
       ScopedSlot t(c, SLOT_APPLY);
       if (compact) {
@@ -159,14 +161,14 @@ static int launch_small(NdlqrHipCtx* c) {
           if (top_lds > 64 * 1024)  // (beyond the default limit of dynamic LDS: horizons of 8192 knots at 12 states)
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ndlqr::rb_backsub_top<NX>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)top_lds);
-          hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), top_lds, c->stream, d, c->rec, c->ytop);
+          hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), top_lds, s.stream, d, s.rec, s.ytop);
         }
         // (an MPC step that asked for nothing but a knot range -- NDLQR_SOLN_ONLY -- runs the workgroups of that range)
-        hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, c->stream,
-                           apply_dims(c, d), c->AB, c->QR, c->rhs, c->rec, c->ytop, c->z);
+        hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream,
+                           apply_dims(c, d), c->AB, c->QR, s.rhs, s.rec, s.ytop, s.z);
       } else {
-        hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, c->stream, apply_dims(c, d), c->AB,
-                           c->QR, c->rhs, c->rec, c->z);
+        hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream, apply_dims(c, d), c->AB,
+                           c->QR, s.rhs, s.rec, s.z);
       }
       return NDLQR_OK;
     }
@@ -175,24 +177,24 @@ static int launch_small(NdlqrHipCtx* c) {
   {
     ScopedSlot t(c, SLOT_BOTTOM);
     hipLaunchKernelGGL((ndlqr::bottom_small<NX, NU, STRICT, KEEP, JB>), dim3(d.N >> JB, d.batch), dim3(32 << JB), 0,
-                       c->stream, d, c->AB, c->QR, c->rhs, c->F, c->z, c->info, c->rec, lean ? 1 : 0,
+                       s.stream, d, c->AB, c->QR, s.rhs, c->F, s.z, c->info, s.rec, lean ? 1 : 0,
                        ((lean || (KEEP && !STRICT)) ? 1 : 0) | (store_l ? 2 : 0));
   }
   for (int l = JB; l < d.K; ++l) {  // separator + boundary update of a level in one launch
     ScopedSlot t(c, SLOT_UPPER);
     hipLaunchKernelGGL((ndlqr::level_small<NX, NU, STRICT, KEEP>), dim3(d.N >> (l + 1), d.batch), dim3(64), 0,
-                       c->stream, d, l, c->AB, c->F, c->z, c->rec, c->info, store_l);
+                       s.stream, d, l, c->AB, c->F, s.z, s.rec, c->info, store_l);
   }
   ScopedSlot t(c, SLOT_APPLY);
   if (lean) {
     if constexpr (!STRICT && !KEEP)
-      hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, c->stream, apply_dims(c, d), c->AB,
-                         c->QR, c->rhs, c->rec, c->z);
+      hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream, apply_dims(c, d), c->AB,
+                         c->QR, s.rhs, s.rec, s.z);
     return NDLQR_OK;
   }
   const size_t lds = sizeof(double) * (size_t)(d.K - JB) * Sh::REC;
   hipLaunchKernelGGL((ndlqr::apply_small<NX, NU, STRICT, KEEP>), dim3(d.N / Sh::KPB, d.batch), dim3(256), lds,
-                     c->stream, d, JB, c->F, c->z, c->rec);
+                     s.stream, d, JB, c->F, s.z, s.rec);
   return NDLQR_OK;
 }
 
@@ -201,15 +203,16 @@ static int launch_small(NdlqrHipCtx* c) {
 template <int NX, int NU>
 static void launch_rhs_records(NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value && 8 * (2 * NX + NU) <= 256) {
     if (c->rec_compact) {
       // the compact records of the default schedule (round 4): forward pass over the separators with the right-hand-side
-      // column alone, then the back-substitution of a full solve. c->red (the accumulator slots, idle here) holds what
+      // column alone, then the back-substitution of a full solve. s.red (the accumulator slots, idle here) holds what
       // the eight-knot blocks push to the separators between them: [batch][N / 8][2][NX].
       {
         ScopedSlot t(c, SLOT_SEP);
-        hipLaunchKernelGGL((ndlqr::rb_forward<NX, NU>), dim3(d.N / 8, d.batch), dim3(256), 0, c->stream, d, c->AB, c->QR,
-                           c->rhs, c->rec, c->red);
+        hipLaunchKernelGGL((ndlqr::rb_forward<NX, NU>), dim3(d.N / 8, d.batch), dim3(256), 0, s.stream, d, c->AB, c->QR,
+                           s.rhs, s.rec, s.red);
       }
       {
         ScopedSlot t(c, SLOT_UPPER);
@@ -217,30 +220,30 @@ static void launch_rhs_records(NdlqrHipCtx* c) {
         if (lds > 64 * 1024)
           (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ndlqr::rb_forward_top<NX, NU>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU>), dim3(d.batch), dim3(256), lds, c->stream, d, c->AB, c->QR,
-                           c->rhs, c->rec, (const double*)c->red, c->ytop);
+        hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU>), dim3(d.batch), dim3(256), lds, s.stream, d, c->AB, c->QR,
+                           s.rhs, s.rec, (const double*)s.red, s.ytop);
       }
       ScopedSlot t(c, SLOT_APPLY);
-      hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, c->stream,
-                         apply_dims(c, d), c->AB, c->QR, c->rhs, c->rec, c->ytop, c->z);
+      hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream,
+                         apply_dims(c, d), c->AB, c->QR, s.rhs, s.rec, s.ytop, s.z);
       return;
     }
   }
   {
     ScopedSlot t(c, SLOT_SEP);
-    hipLaunchKernelGGL((ndlqr::rhs_forward_small<NX, NU>), dim3(d.N / 8, d.batch), dim3(64), 0, c->stream, d, c->AB,
-                       c->QR, c->rhs, c->F, c->rec, c->z);
+    hipLaunchKernelGGL((ndlqr::rhs_forward_small<NX, NU>), dim3(d.N / 8, d.batch), dim3(64), 0, s.stream, d, c->AB,
+                       c->QR, s.rhs, c->F, s.rec, s.z);
   }
   if (d.K > 3) {
     ScopedSlot t(c, SLOT_UPPER);
     const size_t lds = sizeof(double) * (size_t)(d.N / 8) * NX;
-    hipLaunchKernelGGL((ndlqr::rhs_forward_upper<NX, NU>), dim3(d.batch), dim3(512), lds, c->stream, d, c->AB, c->QR,
-                       c->rhs, c->F, c->rec, c->z);
+    hipLaunchKernelGGL((ndlqr::rhs_forward_upper<NX, NU>), dim3(d.batch), dim3(512), lds, s.stream, d, c->AB, c->QR,
+                       s.rhs, c->F, s.rec, s.z);
   }
   {
     ScopedSlot t(c, SLOT_APPLY);
-    hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, c->stream, apply_dims(c, d), c->AB,
-                       c->QR, c->rhs, c->rec, c->z);
+    hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream, apply_dims(c, d), c->AB,
+                       c->QR, s.rhs, s.rec, s.z);
   }
 }
 
@@ -253,18 +256,19 @@ static bool launch_multi_rhs(NdlqrHipCtx* c, const int count, const double* rhs,
                              double* z) {
   if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value && 8 * (2 * NX + NU) <= 256) {
     const ndlqr::Dims& d = c->d;
+    BufferSet& s = c->set[c->cur];
     const size_t lds = sizeof(double) * 4 * (size_t)(d.N >> 3) * NX;
     if (lds > 160 * 1024) return false;
     if (lds > 64 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ndlqr::rb_forward_top<NX, NU, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ndlqr::rb_forward<NX, NU, true>), dim3(d.N / 8, count), dim3(256), 0, c->stream, d, c->AB, c->QR, rhs,
-                       c->rec, fsum, d.batch, zsep);
-    hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU, true>), dim3(count), dim3(256), lds, c->stream, d, c->AB, c->QR, rhs,
-                       c->rec, (const double*)fsum, ytop, d.batch, zsep);
+    hipLaunchKernelGGL((ndlqr::rb_forward<NX, NU, true>), dim3(d.N / 8, count), dim3(256), 0, s.stream, d, c->AB, c->QR, rhs,
+                       s.rec, fsum, d.batch, zsep);
+    hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU, true>), dim3(count), dim3(256), lds, s.stream, d, c->AB, c->QR, rhs,
+                       s.rec, (const double*)fsum, ytop, d.batch, zsep);
     // (a knot range alone: ndlqr_hip_solve_multi_rhs_slices)
-    hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, true>), dim3(apply_grid(c, d), count), dim3(256), 0, c->stream,
-                       apply_dims(c, d), c->AB, c->QR, rhs, (const double*)c->rec, (const double*)ytop, z, d.batch,
+    hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, true>), dim3(apply_grid(c, d), count), dim3(256), 0, s.stream,
+                       apply_dims(c, d), c->AB, c->QR, rhs, (const double*)s.rec, (const double*)ytop, z, d.batch,
                        (const double*)zsep);
     return true;
   } else {
@@ -284,6 +288,7 @@ static bool launch_multi_rhs(NdlqrHipCtx* c, const int count, const double* rhs,
 template <int NX, int NU>
 static int launch_time_shard(NdlqrHipCtx* c, const int phase, const int g, const int G) {
   ndlqr::Dims d = c->d;
+  BufferSet& bs = c->set[c->cur];
   int lg = 0;
   while ((1 << lg) < G) ++lg;
   if (G < 2 || (1 << lg) != G || g < 0 || g >= G) return NDLQR_ERR_INVALID;
@@ -291,7 +296,7 @@ static int launch_time_shard(NdlqrHipCtx* c, const int phase, const int g, const
     return NDLQR_ERR_INVALID;
   } else {
     const int ltop = d.K - lg;  // levels [0, ltop) lie inside a chunk
-    if (!c->red || !c->ytop || ltop < 4 || 8 * (2 * NX + NU) > 256 || (c->flags & ~NDLQR_FLAG_PROFILE)) return NDLQR_ERR_INVALID;
+    if (!bs.red || !bs.ytop || ltop < 4 || 8 * (2 * NX + NU) > 256 || (c->flags & ~NDLQR_FLAG_PROFILE)) return NDLQR_ERR_INVALID;
     const size_t top_lds = sizeof(double) * (size_t)(d.N >> 3) * NX;
     if (top_lds > 160 * 1024) return NDLQR_ERR_INVALID;  // (rb_backsub_top's sweep array has to fit one workgroup's LDS)
     if (top_lds > 64 * 1024)
@@ -302,40 +307,40 @@ static int launch_time_shard(NdlqrHipCtx* c, const int phase, const int g, const
       // whatever an earlier exchange left in the top slots goes: this rank's chunk writes its halves afresh
       for (int j = 1; j < G; ++j) {
         const int s = j * (d.N / G) - 1;
-        double* p = c->red + (size_t)(s >> 2) * SLOT;
+        double* p = bs.red + (size_t)(s >> 2) * SLOT;
         if (hipMemset2DAsync(p, sizeof(double) * (size_t)(d.N >> 2) * SLOT, 0, sizeof(double) * SLOT, (size_t)d.batch,
-                             c->stream) != hipSuccess)
+                             bs.stream) != hipSuccess)
           return NDLQR_ERR_NO_DEVICE;
       }
       {
         ScopedSlot t(c, SLOT_BOTTOM);
         const int cnt = (d.N >> 2) / G;
         d.xoff = g * cnt;
-        hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false, true>), dim3(cnt, d.batch), dim3(64), 0, c->stream, d,
-                           c->AB, c->QR, c->rhs, c->red, c->rec, c->F, c->info, 0, nullptr, 1);
+        hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false, true>), dim3(cnt, d.batch), dim3(64), 0, bs.stream, d,
+                           c->AB, c->QR, bs.rhs, bs.red, bs.rec, c->F, c->info, 0, nullptr, 1);
       }
       for (int l = 2; l < ltop; ++l) {
         ScopedSlot t(c, SLOT_UPPER);
         const int cnt = (d.N >> (l + 1)) / G;
         d.xoff = g * cnt;
-        hipLaunchKernelGGL((ndlqr::reduced_level_mc<NX, NU>), dim3(cnt, d.batch), dim3(64), 0, c->stream, d, l, c->AB,
-                           c->QR, c->rhs, c->red, c->rec, c->F, c->info, 0);
+        hipLaunchKernelGGL((ndlqr::reduced_level_mc<NX, NU>), dim3(cnt, d.batch), dim3(64), 0, bs.stream, d, l, c->AB,
+                           c->QR, bs.rhs, bs.red, bs.rec, c->F, c->info, 0);
       }
     } else {
       d.xoff = 0;
       for (int l = ltop; l < d.K; ++l) {
         ScopedSlot t(c, SLOT_TOP);
-        hipLaunchKernelGGL((ndlqr::reduced_level_mc<NX, NU>), dim3(d.N >> (l + 1), d.batch), dim3(64), 0, c->stream, d,
-                           l, c->AB, c->QR, c->rhs, c->red, c->rec, c->F, c->info, 0);
+        hipLaunchKernelGGL((ndlqr::reduced_level_mc<NX, NU>), dim3(d.N >> (l + 1), d.batch), dim3(64), 0, bs.stream, d,
+                           l, c->AB, c->QR, bs.rhs, bs.red, bs.rec, c->F, c->info, 0);
       }
       ScopedSlot t(c, SLOT_APPLY);
       // (the sweep runs over every separator of level >= 3; those of other chunks have no records here and resolve to
       //  garbage nobody reads: a separator depends on its ancestors only, which are in this chunk or among the top ones)
-      hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), top_lds, c->stream, d, c->rec, c->ytop);
+      hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), top_lds, bs.stream, d, bs.rec, bs.ytop);
       const int cnt = (d.N >> 3) / G;
       d.xoff = g * cnt;
-      hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(cnt, d.batch), dim3(256), 0, c->stream, d, c->AB, c->QR,
-                         c->rhs, c->rec, c->ytop, c->z);
+      hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(cnt, d.batch), dim3(256), 0, bs.stream, d, c->AB, c->QR,
+                         bs.rhs, bs.rec, bs.ytop, bs.z);
     }
     c->schedule = "reduced-time-shard";
     return NDLQR_OK;

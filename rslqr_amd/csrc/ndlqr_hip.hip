@@ -50,6 +50,29 @@ static size_t bytes_z(const ndlqr::Dims& d) { return sizeof(double) * (size_t)d.
 static size_t bytes_rec(const ndlqr::Dims& d) { return sizeof(double) * (size_t)d.batch * d.N * (2 * d.n * d.n + d.n); }
 static size_t bytes_F(const ndlqr::Dims& d) { return sizeof(double) * (size_t)d.batch * d.K * d.N * d.fb; }
 
+// What both buffer sets allocate alike, on the set's stream (created by the caller): events, records, solution, its copy of
+// the right-hand side, failure word; with `slots` (size-specialised shapes) the accumulator slots, the multipliers of the
+// top separators and the arrival counters (the runtime-sized schedule's slots: ensure_red_generic)
+static bool alloc_set(NdlqrHipCtx* c, BufferSet& s, bool slots) {
+  const ndlqr::Dims& d = c->d;
+  bool ok = hipEventCreate(&s.ev_start) == hipSuccess && hipEventCreate(&s.ev_stop) == hipSuccess &&
+            hipMalloc(&s.rec, bytes_rec(d)) == hipSuccess && hipMalloc(&s.z, bytes_z(d)) == hipSuccess &&
+            hipMalloc(&s.rhs, bytes_z(d)) == hipSuccess &&
+            hipHostMalloc((void**)&s.h_fail, sizeof(int), hipHostMallocDefault) == hipSuccess;
+  if (ok) *s.h_fail = 0;
+  if (ok && slots) {
+    // slot = DL | DR (packed lower triangles) | CA | CB | gL | gR, padded to whole 128-byte lines (RedSlot<NX>::SIZE)
+    const size_t slot_doubles = ((size_t)d.n * (d.n + 1) + 2 * (size_t)d.n * d.n + 2 * d.n + 15) / 16 * 16;
+    const size_t red_bytes = sizeof(double) * (size_t)d.batch * (d.N / 4) * slot_doubles;
+    const size_t cnt_bytes = sizeof(int) * (size_t)d.batch * (d.N / 4);
+    ok = hipMalloc(&s.red, red_bytes) == hipSuccess && hipMemsetAsync(s.red, 0, red_bytes, s.stream) == hipSuccess &&
+         hipMalloc(&s.ytop, sizeof(double) * (size_t)d.batch * (d.N / 8) * d.n) == hipSuccess &&
+         hipMalloc(&s.tree_cnt, cnt_bytes) == hipSuccess && hipMemsetAsync(s.tree_cnt, 0, cnt_bytes, s.stream) == hipSuccess;
+    if (ok) s.red_bytes = red_bytes;
+  }
+  return ok && hipMemsetAsync(s.z, 0, bytes_z(d), s.stream) == hipSuccess;
+}
+
 NdlqrHipCtx* ndlqr_hip_create(int nstates, int ninputs, int nhorizon, int batch, int device) {
   return ndlqr_hip_create_ex(nstates, ninputs, nhorizon, batch, device, 0u);
 }
@@ -104,98 +127,70 @@ NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int bat
   }
   set_dims(d, pn, pm);
   c->padded = pn != nstates || pm != ninputs;
-  c->pad_stage = nullptr; c->pad_stage_cap = 0;
-  c->device = device; c->flags = 0; c->stream = nullptr; c->own_stream = true;
-  c->red_bytes = 0;
-  c->AB = c->QR = c->rhs = c->F = c->z = c->rec = c->red = nullptr; c->info = nullptr; c->tree_cnt = nullptr;
-  c->pipeline = getenv("NDLQR_PIPELINE") ? atoi(getenv("NDLQR_PIPELINE")) : 2;
-  c->solve_count = 0; c->in_alt = false; c->z_latest = nullptr; c->stream_latest = nullptr; c->h_fail_other = nullptr;
-  c->state_dirty = false; c->fail_base = 0; c->ytop = nullptr; c->schedule = "none"; c->kkt_out = nullptr; c->xfer = nullptr; c->h_stage[0] = c->h_stage[1] = nullptr; c->ev_inputs = nullptr; c->ev_step[0] = c->ev_step[1] = nullptr; c->step_count = 0; c->h_fail = nullptr; c->rec_complete = false; c->graph_rec_complete = false; c->graph_schedule = "none"; c->rec_compact = false; c->graph_rec_compact = false;
-
-  c->tree = getenv("NDLQR_TREE") ? (atoi(getenv("NDLQR_TREE")) != 0 ? 1 : 0) : -1;  // -1: by batch size
-  c->rowbcast = getenv("NDLQR_ROWBCAST") ? (atoi(getenv("NDLQR_ROWBCAST")) != 0 ? 1 : 0) : -1;  // -1: by block size
-  c->fuse2 = getenv("NDLQR_FUSE2") ? (atoi(getenv("NDLQR_FUSE2")) != 0 ? 1 : 0) : -1;  // -1: by instance (launch_small)
+  c->device = device;
+  if (getenv("NDLQR_PIPELINE")) c->pipeline = atoi(getenv("NDLQR_PIPELINE"));
+  if (getenv("NDLQR_TREE")) c->tree = atoi(getenv("NDLQR_TREE")) != 0 ? 1 : 0;  // unset: by batch size
+  if (getenv("NDLQR_ROWBCAST")) c->rowbcast = atoi(getenv("NDLQR_ROWBCAST")) != 0 ? 1 : 0;  // unset: by block size
+  if (getenv("NDLQR_FUSE2")) c->fuse2 = atoi(getenv("NDLQR_FUSE2")) != 0 ? 1 : 0;  // unset: by instance (launch_small)
   c->no_mfma = getenv("NDLQR_NO_MFMA") != nullptr;
   c->no_top = getenv("NDLQR_NO_TOP") != nullptr;
-  c->top_levels = getenv("NDLQR_TOP_LEVELS") ? atoi(getenv("NDLQR_TOP_LEVELS")) : 3;
+  if (getenv("NDLQR_TOP_LEVELS")) c->top_levels = atoi(getenv("NDLQR_TOP_LEVELS"));
   if (c->top_levels < 3 || c->top_levels > 5) c->top_levels = 3;
-  c->sep_threads = getenv("NDLQR_SEP_THREADS") ? atoi(getenv("NDLQR_SEP_THREADS")) : 0;
-  c->timing_pending = false; c->last_ms = 0; c->last_failures = 0; c->fact_valid = false;
-  memset(c->rhs_latest, 0, sizeof(c->rhs_latest)); memset(c->rhs_gen, 0, sizeof(c->rhs_gen));
-  c->sel_knot0 = 0; c->sel_nknots = 0; c->sel_blocks = 7u; c->step_set[0] = c->step_set[1] = 0;
-  c->apply_blk0 = c->apply_nblk = 0; c->graph_apply = 0; c->z_partial = false; c->z_blk0 = c->z_nblk = 0;
-  c->h_io = nullptr; c->graph_staged = nullptr; c->graph_staged_flags = 0;
-  c->graph_exec = nullptr; c->graph_flags = 0; c->graph_stream = nullptr;
-  c->sep_scratch = nullptr;
-  c->multi_cap = 0;
-  c->multi_rhs = c->multi_z = c->multi_zsep = c->multi_fsum = c->multi_ytop = c->multi_in = c->multi_out = nullptr;
-  memset(c->slot_ms, 0, sizeof(c->slot_ms));
-  memset(c->slot_launches, 0, sizeof(c->slot_launches));
-  bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreate(&c->ev_start) == hipSuccess && hipEventCreate(&c->ev_stop) == hipSuccess &&
+  if (getenv("NDLQR_SEP_THREADS")) c->sep_threads = atoi(getenv("NDLQR_SEP_THREADS"));
+  BufferSet& s = c->set[0];
+  bool ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_inputs, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_step[0], hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_step[1], hipEventDisableTiming) == hipSuccess &&
             hipMalloc(&c->AB, bytes_AB(d)) == hipSuccess && hipMalloc(&c->QR, bytes_QR(d)) == hipSuccess &&
-            hipMalloc(&c->rhs, bytes_z(d)) == hipSuccess && hipMalloc(&c->z, bytes_z(d)) == hipSuccess &&
-            hipMalloc(&c->rec, bytes_rec(d)) == hipSuccess &&
             hipMalloc(&c->info, sizeof(int) * ((size_t)batch + 1)) == hipSuccess &&
-            hipHostMalloc((void**)&c->h_fail, sizeof(int), hipHostMallocDefault) == hipSuccess;
-  if (ok) *c->h_fail = 0;
-  if (ok && nhorizon >= 8 && has_small_instance(d.n, d.m)) {
-    // slot = DL | DR (packed lower triangles) | CA | CB | gL | gR, padded to whole 128-byte lines (RedSlot<NX>::SIZE)
-    const size_t slot_doubles = ((size_t)d.n * (d.n + 1) + 2 * (size_t)d.n * d.n + 2 * d.n + 15) / 16 * 16;
-    const size_t red_bytes = sizeof(double) * (size_t)batch * (nhorizon / 4) * slot_doubles;
-    ok = hipMalloc(&c->red, red_bytes) == hipSuccess && hipMemsetAsync(c->red, 0, red_bytes, c->stream) == hipSuccess;
-    if (ok) c->red_bytes = red_bytes;
-    ok = ok && hipMalloc(&c->ytop, sizeof(double) * (size_t)batch * (nhorizon / 8) * d.n) == hipSuccess;
-    const size_t cnt_bytes = sizeof(int) * (size_t)batch * (nhorizon / 4);
-    ok = ok && hipMalloc(&c->tree_cnt, cnt_bytes) == hipSuccess &&
-         hipMemsetAsync(c->tree_cnt, 0, cnt_bytes, c->stream) == hipSuccess;
-  }
+            alloc_set(c, s, nhorizon >= 8 && has_small_instance(d.n, d.m));
   if (ok && c->padded) {
-    hipLaunchKernelGGL(ndlqr::pad_fill_generic, dim3(d.N, d.batch), dim3(128), 0, c->stream, d, c->AB, c->QR, c->rhs);
+    hipLaunchKernelGGL(ndlqr::pad_fill_generic, dim3(d.N, d.batch), dim3(128), 0, s.stream, d, c->AB, c->QR, s.rhs);
     ok = hipGetLastError() == hipSuccess;
   }
-  if (ok) {
-    // (the factor array F is allocated by the first solve whose schedule touches it: ndlqr_hip_ensure_F)
-    ok = hipMemsetAsync(c->z, 0, bytes_z(d), c->stream) == hipSuccess &&
-         hipMemsetAsync(c->info, 0, sizeof(int) * ((size_t)batch + 1), c->stream) == hipSuccess &&
-         hipStreamSynchronize(c->stream) == hipSuccess;
-  }
+  // (the factor array F is allocated by the first solve whose schedule touches it: ndlqr_hip_ensure_F)
+  ok = ok && hipMemsetAsync(c->info, 0, sizeof(int) * ((size_t)batch + 1), s.stream) == hipSuccess &&
+       hipStreamSynchronize(s.stream) == hipSuccess;
   if (!ok) {
     fail("device allocation", hipGetLastError());
     ndlqr_hip_destroy(c);
     return nullptr;
   }
+  s.ready = true;
   return c;
 }
 
-static void free_alt(NdlqrHipCtx* c);  // two-deep solve pipeline, below
+// release buffer set i (the primary set's stream only where the context owns it)
+static void free_set(NdlqrHipCtx* c, int i) {
+  BufferSet& s = c->set[i];
+  if (s.stream) (void)hipStreamSynchronize(s.stream);
+  s.graph.reset();
+  (void)hipFree(s.rec); (void)hipFree(s.red); (void)hipFree(s.ytop); (void)hipFree(s.z); (void)hipFree(s.tree_cnt);
+  (void)hipFree(s.rhs); (void)hipFree(s.xfer);
+  if (s.h_fail) (void)hipHostFree(s.h_fail);
+  if (s.ev_start) (void)hipEventDestroy(s.ev_start);
+  if (s.ev_stop) (void)hipEventDestroy(s.ev_stop);
+  if (s.stream && (i == 1 || c->own_stream)) (void)hipStreamDestroy(s.stream);
+  s = BufferSet();
+}
 
 void ndlqr_hip_destroy(NdlqrHipCtx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  free_alt(c);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
-  if (c->graph_staged) (void)hipGraphExecDestroy(c->graph_staged);
+  for (int i = 1; i >= 0; --i) free_set(c, i);
+  c->staged.reset();
   if (c->h_io) (void)hipHostFree(c->h_io);
   for (auto& p : c->pending) { (void)hipEventDestroy(p.start); (void)hipEventDestroy(p.stop); }
   for (auto& ev : c->event_pool) (void)hipEventDestroy(ev);
-  (void)hipFree(c->AB); (void)hipFree(c->QR); (void)hipFree(c->rhs); (void)hipFree(c->F);
-  (void)hipFree(c->z); (void)hipFree(c->rec); (void)hipFree(c->red); (void)hipFree(c->tree_cnt); (void)hipFree(c->info);
+  (void)hipFree(c->AB); (void)hipFree(c->QR); (void)hipFree(c->F); (void)hipFree(c->info);
   (void)hipFree(c->sep_scratch);
   (void)hipFree(c->multi_rhs); (void)hipFree(c->multi_z); (void)hipFree(c->multi_zsep); (void)hipFree(c->multi_fsum);
   (void)hipFree(c->multi_ytop); (void)hipFree(c->multi_in); (void)hipFree(c->multi_out);
-  (void)hipFree(c->kkt_out); (void)hipFree(c->ytop); (void)hipFree(c->xfer); (void)hipFree(c->pad_stage);
+  (void)hipFree(c->kkt_out); (void)hipFree(c->pad_stage);
   for (double* h : c->h_stage) if (h) (void)hipHostFree(h);
   if (c->ev_inputs) (void)hipEventDestroy(c->ev_inputs);
   for (hipEvent_t ev : c->ev_step) if (ev) (void)hipEventDestroy(ev);
-  if (c->h_fail) (void)hipHostFree(c->h_fail);
-  if (c->ev_start) (void)hipEventDestroy(c->ev_start);
-  if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
-  if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -204,8 +199,7 @@ void ndlqr_hip_destroy(NdlqrHipCtx* c) {
 // the current buffer set holds the most recent solution -- all of it, or (a step with NDLQR_SOLN_ONLY) the knots of the
 // workgroups its back-substitution ran
 static void note_solution(NdlqrHipCtx* c) {
-  c->z_latest = c->z;
-  c->stream_latest = c->stream;
+  c->latest = c->cur;
   c->z_partial = c->apply_nblk > 0;
   c->z_blk0 = c->apply_blk0;
   c->z_nblk = c->apply_nblk;
@@ -215,7 +209,7 @@ static void note_solution(NdlqrHipCtx* c) {
 // have to be brought up to date first (copy_rhs_parts_generic: 62 us per 1024 x (12,4,256) in a loop that replaces the
 // problem every iteration).
 static void next_solve_on_current_set(NdlqrHipCtx* c) {
-  if (((c->solve_count & 1u) != 0) != c->in_alt) ++c->solve_count;
+  if ((c->solve_count & 1u) != (unsigned)c->cur) ++c->solve_count;
 }
 // consumers of the whole solution vector refuse a slice
 static int need_full_solution(const NdlqrHipCtx* c, const char* who) {
@@ -225,42 +219,11 @@ static int need_full_solution(const NdlqrHipCtx* c, const char* who) {
   return NDLQR_ERR_INVALID;
 }
 
-// exchange the context's per-solve buffers, stream, graph and events with the alternate set
-static void swap_slot(NdlqrHipCtx* c) {
-  NdlqrAltSlot& a = c->alt;
-  std::swap(c->rec, a.rec); std::swap(c->red, a.red); std::swap(c->red_bytes, a.red_bytes); std::swap(c->ytop, a.ytop); std::swap(c->z, a.z);
-  std::swap(c->rhs, a.rhs); std::swap(c->xfer, a.xfer);
-  std::swap(c->tree_cnt, a.tree_cnt); std::swap(c->h_fail, a.h_fail); std::swap(c->stream, a.stream);
-  std::swap(c->graph_exec, a.graph_exec); std::swap(c->graph_flags, a.graph_flags);
-  std::swap(c->graph_stream, a.graph_stream); std::swap(c->graph_rec_complete, a.graph_rec_complete);
-  std::swap(c->graph_rec_compact, a.graph_rec_compact);
-  std::swap(c->graph_schedule, a.graph_schedule); std::swap(c->graph_apply, a.graph_apply);
-  std::swap(c->ev_start, a.ev_start); std::swap(c->ev_stop, a.ev_stop);
-  c->in_alt = !c->in_alt;
-}
-
-static void free_alt(NdlqrHipCtx* c) {
-  if (c->in_alt) swap_slot(c);
-  NdlqrAltSlot& a = c->alt;
-  if (a.stream) (void)hipStreamSynchronize(a.stream);
-  if (a.graph_exec) (void)hipGraphExecDestroy(a.graph_exec);
-  (void)hipFree(a.rec); (void)hipFree(a.red); (void)hipFree(a.ytop); (void)hipFree(a.z); (void)hipFree(a.tree_cnt);
-  (void)hipFree(a.rhs); (void)hipFree(a.xfer);
-  if (a.h_fail) (void)hipHostFree(a.h_fail);
-  if (a.ev_start) (void)hipEventDestroy(a.ev_start);
-  if (a.ev_stop) (void)hipEventDestroy(a.ev_stop);
-  if (a.stream) (void)hipStreamDestroy(a.stream);
-  a = NdlqrAltSlot();
-}
-
 // allocate the alternate set on first use; false (and depth 1 from then on) when it does not fit
 static bool ensure_alt(NdlqrHipCtx* c) {
-  NdlqrAltSlot& a = c->alt;
+  BufferSet& a = c->set[1];
   if (a.ready) return true;
-  const ndlqr::Dims& d = c->d;
-  const size_t slot_doubles = ((size_t)d.n * (d.n + 1) + 2 * (size_t)d.n * d.n + 2 * d.n + 15) / 16 * 16;  // RedSlot<NX>::SIZE
-  const size_t red_bytes = sizeof(double) * (size_t)d.batch * (d.N / 4) * slot_doubles;
-  const size_t cnt_bytes = sizeof(int) * (size_t)d.batch * (d.N / 4);
+  const BufferSet& p = c->set[0];  // (current: the alternate set is not in use before it exists)
   // The second set's stream gets another priority than the first's: streams of one priority share a few hardware
   // queues round-robin with every other stream of the process, and two streams on ONE hardware queue run strictly one
   // after the other (measured: the step pipeline lost all its overlap in a process that had created other streams
@@ -269,39 +232,29 @@ static bool ensure_alt(NdlqrHipCtx* c) {
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
   const int alt_prio = getenv("NDLQR_ALT_PRIORITY") ? atoi(getenv("NDLQR_ALT_PRIORITY")) : prio_greatest;
   bool ok = hipStreamCreateWithPriority(&a.stream, hipStreamNonBlocking, alt_prio) == hipSuccess &&
-            hipEventCreate(&a.ev_start) == hipSuccess && hipEventCreate(&a.ev_stop) == hipSuccess &&
-            hipMalloc(&a.rec, bytes_rec(d)) == hipSuccess && hipMalloc(&a.z, bytes_z(d)) == hipSuccess &&
-            hipMalloc(&a.rhs, bytes_z(d)) == hipSuccess &&
-            hipHostMalloc((void**)&a.h_fail, sizeof(int), hipHostMallocDefault) == hipSuccess;
+            alloc_set(c, a, p.tree_cnt != nullptr);
   // this set's own copy of the right-hand side (a step of ndlqr_hip_step_async replaces the right-hand side of
   // ITS buffer set only; rhs_gen / rhs_make_current keep track of which copy is behind in what)
-  ok = ok && hipStreamSynchronize(c->stream) == hipSuccess &&
-       hipMemcpyAsync(a.rhs, c->rhs, bytes_z(d), hipMemcpyDeviceToDevice, a.stream) == hipSuccess;
-  if (ok && c->tree_cnt)  // size-specialised shapes (the runtime-sized schedule's slots: ensure_red_generic)
-    ok = hipMalloc(&a.red, red_bytes) == hipSuccess && hipMemsetAsync(a.red, 0, red_bytes, a.stream) == hipSuccess &&
-         ((a.red_bytes = red_bytes), true) &&
-         hipMalloc(&a.ytop, sizeof(double) * (size_t)d.batch * (d.N / 8) * d.n) == hipSuccess &&
-         hipMalloc(&a.tree_cnt, cnt_bytes) == hipSuccess && hipMemsetAsync(a.tree_cnt, 0, cnt_bytes, a.stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(a.z, 0, bytes_z(d), a.stream) == hipSuccess && hipStreamSynchronize(a.stream) == hipSuccess;
+  ok = ok && hipStreamSynchronize(p.stream) == hipSuccess &&
+       hipMemcpyAsync(a.rhs, p.rhs, bytes_z(c->d), hipMemcpyDeviceToDevice, a.stream) == hipSuccess &&
+       hipStreamSynchronize(a.stream) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    free_alt(c);
+    free_set(c, 1);
     c->pipeline = 1;
     return false;
   }
-  *a.h_fail = *c->h_fail;
+  *a.h_fail = *p.h_fail;
+  for (int q = 0; q < 4; ++q) a.rhs_gen[q] = p.rhs_gen[q];  // (the new set's copy of the right-hand side was taken from p)
   a.ready = true;
-  {  // (the new set's copy of the right-hand side was taken from the current one)
-    const int cur = c->in_alt ? 1 : 0;
-    for (int p = 0; p < 4; ++p) c->rhs_gen[1 - cur][p] = c->rhs_gen[cur][p];
-  }
   return true;
 }
 
-// every solve in flight on either slot has finished
+// every solve in flight on either set has finished
 static hipError_t sync_all(NdlqrHipCtx* c) {
-  hipError_t e = c->stream ? hipStreamSynchronize(c->stream) : hipSuccess;
-  if (c->alt.stream) { const hipError_t e2 = hipStreamSynchronize(c->alt.stream); if (e == hipSuccess) e = e2; }
+  hipError_t e = hipSuccess;
+  for (const BufferSet& s : c->set)
+    if (s.stream) { const hipError_t e2 = hipStreamSynchronize(s.stream); if (e == hipSuccess) e = e2; }
   return e;
 }
 
@@ -311,18 +264,18 @@ int ndlqr_hip_set_pipeline_depth(NdlqrHipCtx* c, int depth) {
   if (!c || depth < 1) return NDLQR_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
-  if (c->in_alt) {  // keep the latest solution where the single-slot code expects it
-    swap_slot(c);
+  if (c->cur != 0) {  // keep the latest solution where the single-set code expects it
+    c->cur = 0;
     {  // (the right-hand side the latest solution belongs to: after ndlqr_hip_step_async the two sets may differ)
       const int merr = rhs_make_current(c, 0xFu);
       if (merr) return merr;
-      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(hipStreamSynchronize(c->set[0].stream));
     }
-    if (c->alt.z && c->z_latest == c->alt.z) {
-      HIP_TRY(hipMemcpy(c->z, c->alt.z, bytes_z(c->d), hipMemcpyDeviceToDevice));
+    if (c->latest == 1) {
+      HIP_TRY(hipMemcpy(c->set[0].z, c->set[1].z, bytes_z(c->d), hipMemcpyDeviceToDevice));
       HIP_TRY(hipDeviceSynchronize());  // (a device-to-device copy on the null stream need not be finished on return;
                                         //  the solver's streams do not wait for the null stream)
-      c->z_latest = c->z;
+      c->latest = 0;
     }
   }
   c->pipeline = depth > 2 ? 2 : depth;
@@ -348,7 +301,7 @@ int ndlqr_hip_ensure_F(NdlqrHipCtx* c) {
   }
   // Structural zeros of F are never written by the kernels; zero once so that the factor
   // download matches the reference's calloc'ed array (src/nddata.c:34).
-  HIP_TRY(hipMemsetAsync(c->F, 0, bytes_F(c->d), c->stream));
+  HIP_TRY(hipMemsetAsync(c->F, 0, bytes_F(c->d), c->set[c->cur].stream));
   return NDLQR_OK;
 }
 
@@ -363,61 +316,63 @@ int ndlqr_hip_set_stream(NdlqrHipCtx* c, void* hip_stream) {
   if (!c) return NDLQR_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   {
-    const int perr = ndlqr_hip_set_pipeline_depth(c, c->pipeline);  // drains both slots, primary set current
+    const int perr = ndlqr_hip_set_pipeline_depth(c, c->pipeline);  // drains both sets, primary set current
     if (perr) return perr;
   }
-  if (c->own_stream && c->stream) HIP_TRY(hipStreamDestroy(c->stream));
+  BufferSet& s = c->set[0];
+  if (c->own_stream && s.stream) HIP_TRY(hipStreamDestroy(s.stream));
   if (hip_stream) {
-    c->stream = (hipStream_t)hip_stream;
+    s.stream = (hipStream_t)hip_stream;
     c->own_stream = false;
   } else {
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
     c->own_stream = true;
   }
   return NDLQR_OK;
 }
-void* ndlqr_hip_get_stream(NdlqrHipCtx* c) { return c ? (void*)c->stream : nullptr; }
+void* ndlqr_hip_get_stream(NdlqrHipCtx* c) { return c ? (void*)c->set[c->cur].stream : nullptr; }
 
 // The right-hand side exists once per buffer set of the pipeline (hip_context.hpp: rhs_latest / rhs_gen).
 // rhs_written_cur: the parts of `mask` of the CURRENT set's copy have just been (re)written.
 static void rhs_written_cur(NdlqrHipCtx* c, unsigned mask) {
-  const int cur = c->in_alt ? 1 : 0;
   for (int p = 0; p < 4; ++p)
-    if (mask & (1u << p)) c->rhs_gen[cur][p] = ++c->rhs_latest[p];
+    if (mask & (1u << p)) c->set[c->cur].rhs_gen[p] = ++c->rhs_latest[p];
 }
 // rhs_make_current: the current set's copy is brought up to date in the parts of `need` before a solve reads it. Only a
 // change of flow gets here with something to do (full MPC steps followed by x0-only steps, a plain solve behind steps,
 // the first solve on the other set after an upload): everything in flight is waited for, the stale parts are copied
 // from the other set on this set's stream, and the other set's stream waits for that copy before it may rewrite its own.
 static int rhs_make_current(NdlqrHipCtx* c, unsigned need) {
-  const int cur = c->in_alt ? 1 : 0;
+  BufferSet& s = c->set[c->cur];
+  const BufferSet& o = c->set[1 - c->cur];
   unsigned stale = 0;
   for (int p = 0; p < 4; ++p)
-    if ((need & (1u << p)) && c->rhs_gen[cur][p] < c->rhs_latest[p]) stale |= 1u << p;
-  if (!stale || !c->alt.rhs) return NDLQR_OK;
+    if ((need & (1u << p)) && s.rhs_gen[p] < c->rhs_latest[p]) stale |= 1u << p;
+  if (!stale || !o.rhs) return NDLQR_OK;
   HIP_TRY(sync_all(c));
-  hipLaunchKernelGGL(ndlqr::copy_rhs_parts_generic, dim3(c->d.N, c->d.batch), dim3(64), 0, c->stream, c->d, stale,
-                     (const double*)c->alt.rhs, c->rhs);
+  hipLaunchKernelGGL(ndlqr::copy_rhs_parts_generic, dim3(c->d.N, c->d.batch), dim3(64), 0, s.stream, c->d, stale,
+                     (const double*)o.rhs, s.rhs);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_inputs, c->stream));
-  if (c->alt.stream) HIP_TRY(hipStreamWaitEvent(c->alt.stream, c->ev_inputs, 0));
+  HIP_TRY(hipEventRecord(c->ev_inputs, s.stream));
+  if (o.stream) HIP_TRY(hipStreamWaitEvent(o.stream, c->ev_inputs, 0));
   for (int p = 0; p < 4; ++p)
-    if (stale & (1u << p)) c->rhs_gen[cur][p] = c->rhs_latest[p];
+    if (stale & (1u << p)) s.rhs_gen[p] = c->rhs_latest[p];
   return NDLQR_OK;
 }
 
 // the other buffer set's stream waits for everything enqueued on the current one so far
 static hipError_t other_stream_waits(NdlqrHipCtx* c) {
-  if (!c->alt.stream) return hipSuccess;
-  const hipError_t e = hipEventRecord(c->ev_inputs, c->stream);
-  return e != hipSuccess ? e : hipStreamWaitEvent(c->alt.stream, c->ev_inputs, 0);
+  const hipStream_t other = c->set[1 - c->cur].stream;
+  if (!other) return hipSuccess;
+  const hipError_t e = hipEventRecord(c->ev_inputs, c->set[c->cur].stream);
+  return e != hipSuccess ? e : hipStreamWaitEvent(other, c->ev_inputs, 0);
 }
 
 // staging of caller-layout data of a padded shape
 static int ensure_pad_stage(NdlqrHipCtx* c, size_t doubles) {
   if (doubles <= c->pad_stage_cap) return NDLQR_OK;
-  if (c->pad_stage) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->pad_stage); c->pad_stage = nullptr; c->pad_stage_cap = 0; }
-  if (c->graph_staged) { (void)hipGraphExecDestroy(c->graph_staged); c->graph_staged = nullptr; }  // (it holds the old address)
+  if (c->pad_stage) { HIP_TRY(hipStreamSynchronize(c->set[c->cur].stream)); (void)hipFree(c->pad_stage); c->pad_stage = nullptr; c->pad_stage_cap = 0; }
+  c->staged.reset();  // (it holds the old address)
   HIP_TRY(hipMalloc(&c->pad_stage, sizeof(double) * doubles));
   c->pad_stage_cap = doubles;
   return NDLQR_OK;
@@ -428,6 +383,7 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
   if (!c || !AB || !QR || !rhs || p0 < 0 || count <= 0 || p0 + count > c->d.batch) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
   HIP_TRY(hipSetDevice(c->device));
+  BufferSet& s = c->set[c->cur];
   HIP_TRY(sync_all(c));  // solves in flight on either slot still read the inputs
   {  // (a partial upload lands on a complete, current copy: the other set then takes the whole of it on its next use)
     const int merr = rhs_make_current(c, 0xFu);
@@ -439,13 +395,13 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
     const int serr = ensure_pad_stage(c, uAB + uQR + uz);
     if (serr) return serr;
     double* s0 = c->pad_stage;
-    HIP_TRY(hipMemcpyAsync(s0, AB, sizeof(double) * uAB, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(s0 + uAB, QR, sizeof(double) * uQR, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(s0 + uAB + uQR, rhs, sizeof(double) * uz, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(ndlqr::pad_inputs_generic, dim3(d.N, count), dim3(128), 0, c->stream, u, d, p0, s0, s0 + uAB,
-                       s0 + uAB + uQR, c->AB, c->QR, c->rhs);
+    HIP_TRY(hipMemcpyAsync(s0, AB, sizeof(double) * uAB, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s0 + uAB, QR, sizeof(double) * uQR, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s0 + uAB + uQR, rhs, sizeof(double) * uz, hipMemcpyHostToDevice, s.stream));
+    hipLaunchKernelGGL(ndlqr::pad_inputs_generic, dim3(d.N, count), dim3(128), 0, s.stream, u, d, p0, s0, s0 + uAB,
+                       s0 + uAB + uQR, c->AB, c->QR, s.rhs);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(s.stream));
     rhs_written_cur(c, 0xFu);
     next_solve_on_current_set(c);
     c->fact_valid = false;
@@ -453,10 +409,10 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
     return NDLQR_OK;
   }
   const size_t sAB = (size_t)d.N * d.n * d.w, sQR = (size_t)d.N * d.w, sz = (size_t)d.N * d.rows;
-  HIP_TRY(hipMemcpyAsync(c->AB + p0 * sAB, AB, sizeof(double) * sAB * count, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->QR + p0 * sQR, QR, sizeof(double) * sQR * count, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->rhs + p0 * sz, rhs, sizeof(double) * sz * count, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // the host staging buffers are reused by the caller
+  HIP_TRY(hipMemcpyAsync(c->AB + p0 * sAB, AB, sizeof(double) * sAB * count, hipMemcpyHostToDevice, s.stream));
+  HIP_TRY(hipMemcpyAsync(c->QR + p0 * sQR, QR, sizeof(double) * sQR * count, hipMemcpyHostToDevice, s.stream));
+  HIP_TRY(hipMemcpyAsync(s.rhs + p0 * sz, rhs, sizeof(double) * sz * count, hipMemcpyHostToDevice, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));  // the host staging buffers are reused by the caller
   rhs_written_cur(c, 0xFu);
   next_solve_on_current_set(c);
   c->fact_valid = false;  // new A, B, Q, R: a cached factorisation no longer matches the inputs
@@ -469,18 +425,19 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
                                const double* x0) {
   if (!c || !A || !B || !Q || !R || !q || !r || !d || !x0) return NDLQR_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
+  BufferSet& s = c->set[c->cur];
   HIP_TRY(sync_all(c));  // solves in flight on either slot still read the inputs
   // (eight knots per workgroup while a thread's eight loads -- the same entry of eight consecutive blocks -- stay within what
   //  the caches hold together: at (64,16) the strided reads of eight 40 KB blocks at once took 9.5 instead of 5 ms)
   if (c->d.N % 8 == 0 && c->du.n <= 16)
-    hipLaunchKernelGGL(ndlqr::pack_flat_generic<8>, dim3(c->d.N / 8, c->d.batch), dim3(128), 0, c->stream, c->du, c->d, A, B, Q,
-                       R, q, r, d, x0, c->AB, c->QR, c->rhs);
+    hipLaunchKernelGGL(ndlqr::pack_flat_generic<8>, dim3(c->d.N / 8, c->d.batch), dim3(128), 0, s.stream, c->du, c->d, A, B, Q,
+                       R, q, r, d, x0, c->AB, c->QR, s.rhs);
   else if (c->du.n > 16 && sizeof(double) * (size_t)(c->du.n | 1) * c->du.w <= 64 * 1024)  // through LDS, whole lines in and out
     hipLaunchKernelGGL(ndlqr::pack_flat_tiled, dim3(c->d.N, c->d.batch), dim3(256), sizeof(double) * (size_t)(c->du.n | 1) * c->du.w,
-                       c->stream, c->du, c->d, A, B, Q, R, q, r, d, x0, c->AB, c->QR, c->rhs);
+                       s.stream, c->du, c->d, A, B, Q, R, q, r, d, x0, c->AB, c->QR, s.rhs);
   else
-    hipLaunchKernelGGL(ndlqr::pack_flat_generic<1>, dim3(c->d.N, c->d.batch), dim3(128), 0, c->stream, c->du, c->d, A, B, Q, R,
-                       q, r, d, x0, c->AB, c->QR, c->rhs);
+    hipLaunchKernelGGL(ndlqr::pack_flat_generic<1>, dim3(c->d.N, c->d.batch), dim3(128), 0, s.stream, c->du, c->d, A, B, Q, R,
+                       q, r, d, x0, c->AB, c->QR, s.rhs);
   HIP_TRY(hipGetLastError());
   rhs_written_cur(c, 0xFu);        // (the whole batch: nothing of the older copies is needed any more)
   next_solve_on_current_set(c);
@@ -502,7 +459,7 @@ int ndlqr_hip_device_pointers(NdlqrHipCtx* c, void** out5) {
   if (ferr) return ferr;
   const int perr = ndlqr_hip_set_pipeline_depth(c, 1);  // the caller holds raw pointers: one buffer set from now on
   if (perr) return perr;
-  out5[0] = c->AB; out5[1] = c->QR; out5[2] = c->rhs; out5[3] = c->F; out5[4] = c->z;
+  out5[0] = c->AB; out5[1] = c->QR; out5[2] = c->set[0].rhs; out5[3] = c->F; out5[4] = c->set[0].z;
   return NDLQR_OK;
 }
 
@@ -555,28 +512,23 @@ static size_t bytes_red_generic(const ndlqr::Dims& d) {
 static int ensure_red_generic(NdlqrHipCtx* c) {
   if (c->d.N < 4) return NDLQR_OK;  // a single separator: no slots
   const size_t need = bytes_red_generic(c->d);
-  for (int which = 0; which < 2; ++which) {
-    double** slot = which == 0 ? &c->red : &c->alt.red;
-    size_t* have = which == 0 ? &c->red_bytes : &c->alt.red_bytes;
-    if (which == 1 && !c->alt.ready) continue;
-    if (*slot && *have >= need) continue;
+  for (BufferSet& s : c->set) {
+    if (!s.ready || (s.red && s.red_bytes >= need)) continue;
     // (a context of a size-specialised shape under NDLQR_FLAG_GENERIC comes with the smaller array of ITS schedule)
     HIP_TRY(sync_all(c));
-    if (*slot) { (void)hipFree(*slot); *slot = nullptr; *have = 0; }
-    // a launch sequence captured on this buffer set holds the old address
-    hipGraphExec_t* ge = which == 0 ? &c->graph_exec : &c->alt.graph_exec;
-    if (*ge) { (void)hipGraphExecDestroy(*ge); *ge = nullptr; }
-    if (hipMalloc(slot, need) != hipSuccess) {
-      *slot = nullptr;
+    if (s.red) { (void)hipFree(s.red); s.red = nullptr; s.red_bytes = 0; }
+    s.graph.reset();  // a launch sequence captured on this buffer set holds the old address
+    if (hipMalloc(&s.red, need) != hipSuccess) {
+      s.red = nullptr;
       (void)hipGetLastError();
       g_last_error = "accumulator slots of the separator-only schedule do not fit on the device";
       return NDLQR_ERR_INVALID;
     }
-    *have = need;
+    s.red_bytes = need;
     // (zeros for the size-specialised schedule, should the context go back to it. hipMemset runs on the null
     //  stream and may return before it is done; the solver's streams are non-blocking: wait here, or the
     //  level-0 launch races with it)
-    HIP_TRY(hipMemset(*slot, 0, need));
+    HIP_TRY(hipMemset(s.red, 0, need));
     HIP_TRY(hipDeviceSynchronize());
   }
   return NDLQR_OK;
@@ -587,6 +539,7 @@ static int ensure_red_generic(NdlqrHipCtx* c) {
 // multipliers and the states / inputs of every knot
 static void launch_backsub_reduced_generic(NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   ScopedSlot t(c, SLOT_APPLY);
   const size_t lds_m = sizeof(double) * ((size_t)d.n * (d.n + 1) / 2 + 2 * (size_t)d.n + 16);
   // (rows of CA | CB eight per wavefront. Four wavefronts per separator leave a CU a quarter full at small blocks: one up to
@@ -605,27 +558,28 @@ static void launch_backsub_reduced_generic(NdlqrHipCtx* c) {
     ndlqr::Dims dl = d;
     int cnt = d.N >> (l + 1);
     if (part) { dl.xoff = ka >> (l + 1); cnt = (kb >> (l + 1)) - dl.xoff + 1; }
-    hipLaunchKernelGGL(ndlqr::backsub_multipliers_compact, dim3(cnt, d.batch), dim3(thr_m), lds_m, c->stream, dl, l,
-                       c->red, c->rec, c->z);
+    hipLaunchKernelGGL(ndlqr::backsub_multipliers_compact, dim3(cnt, d.batch), dim3(thr_m), lds_m, s.stream, dl, l,
+                       s.red, s.rec, s.z);
   }
   const int thr = d.n <= 16 ? 64 : (d.n <= 32 ? 128 : 256);  // (its y_s step wants n <= threads)
   const size_t lds = sizeof(double) * ((size_t)d.n * (d.n + 1) / 2 + 5 * (size_t)d.n + 4 * (size_t)d.w + 2 * (size_t)d.rows + thr);
   ndlqr::Dims d0 = d;
   if (part) d0.xoff = k0 >> 1;
   hipLaunchKernelGGL(ndlqr::backsub_level0_states_generic, dim3(part ? (k1 >> 1) - (k0 >> 1) + 1 : d.N >> 1, d.batch), dim3(thr),
-                     lds, c->stream, d0, c->AB, c->QR, c->rhs, c->rec, c->z);
+                     lds, s.stream, d0, c->AB, c->QR, s.rhs, s.rec, s.z);
 }
 
 static int launch_reduced_generic(NdlqrHipCtx* c, const ReducedGenericPlan& p) {
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   c->schedule = p.keep ? "generic-reduced-records" : "generic-reduced";
   c->rec_complete = p.keep;  // records, slots and W of every separator stay: rhs-only re-solves (launch_rhs_reduced_generic)
   for (int l = 0; l < d.K; ++l) {
     ScopedSlot t(c, SLOT_SEP);
     const dim3 grid(d.N >> (l + 1), d.batch);
 #define NDLQR_LAUNCH_SEP2(NB_, NT_, L0_, PAD_)                                                                     \
-  hipLaunchKernelGGL((ndlqr::separator_reduced_mfma<NB_, NT_, L0_, PAD_>), grid, dim3(NT_), p.lds, c->stream, d, l, \
-                     c->AB, c->QR, c->rhs, c->red, c->rec, c->info)
+  hipLaunchKernelGGL((ndlqr::separator_reduced_mfma<NB_, NT_, L0_, PAD_>), grid, dim3(NT_), p.lds, s.stream, d, l, \
+                     c->AB, c->QR, s.rhs, s.red, s.rec, c->info)
 #define NDLQR_LAUNCH_SEP(NB_, NT_)                                          \
   do {                                                                      \
     if (l == 0 && p.pad) NDLQR_LAUNCH_SEP2(NB_, NT_, true, true);           \
@@ -673,12 +627,13 @@ static int launch_reduced_generic(NdlqrHipCtx* c, const ReducedGenericPlan& p) {
 // rhs-only re-solve on the records, slots and separator factors of a generic-reduced-records sweep
 static void launch_rhs_reduced_generic(NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   const int np = (d.n + 15) / 16 * 16;
   const size_t lds = sizeof(double) * (2 * (size_t)d.w + d.n + 3 * (size_t)np + 256 + (size_t)d.n * (d.n + 1) / 2);
   for (int l = 0; l < d.K; ++l) {
     ScopedSlot t(c, SLOT_SEP);
-    hipLaunchKernelGGL(ndlqr::rhs_reduced_generic, dim3(d.N >> (l + 1), d.batch), dim3(256), lds, c->stream, d, l, np,
-                       c->AB, c->QR, c->rhs, c->red, c->rec);
+    hipLaunchKernelGGL(ndlqr::rhs_reduced_generic, dim3(d.N >> (l + 1), d.batch), dim3(256), lds, s.stream, d, l, np,
+                       c->AB, c->QR, s.rhs, s.red, s.rec);
   }
   launch_backsub_reduced_generic(c);
 }
@@ -726,12 +681,13 @@ static GenericSepPlan plan_generic_sep(const NdlqrHipCtx* c, const bool strict) 
 template <bool STRICT>
 static int launch_generic(NdlqrHipCtx* c, bool lean) {
   const ndlqr::Dims& d = c->d;
-  double* rec = lean ? c->rec : nullptr;
+  BufferSet& s = c->set[c->cur];
+  double* rec = lean ? s.rec : nullptr;
   c->schedule = lean ? "generic-lean" : (STRICT ? "generic-strict" : "generic-keep");
   {
     ScopedSlot t(c, SLOT_LEAF);
-    hipLaunchKernelGGL((ndlqr::leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(128), 0, c->stream, d,
-                       c->AB, c->QR, c->rhs, c->F, c->z, c->info, lean ? 1 : 0);
+    hipLaunchKernelGGL((ndlqr::leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(128), 0, s.stream, d,
+                       c->AB, c->QR, s.rhs, c->F, s.z, c->info, lean ? 1 : 0);
   }
   // S (n x (n+1)) + right-hand-side panel (n x (2n+1)); on the matrix-core path the panel goes through
   // LDS in chunks of kSepChunkTiles column tiles (+ the inverses of the 16x16 diagonal blocks, pitch 17)
@@ -753,11 +709,11 @@ static int launch_generic(NdlqrHipCtx* c, bool lean) {
       ScopedSlot t(c, SLOT_SEP);
       if (p1mfma)
         hipLaunchKernelGGL((ndlqr::separator_mfma<kSepChunkTiles>), dim3(nsub, d.batch), dim3(sep_threads), lds,
-                           c->stream, d, l, c->AB, c->F, c->z, c->info, rec, sep_scratch,
+                           s.stream, d, l, c->AB, c->F, s.z, c->info, rec, sep_scratch,
                            (size_t)d.n * (d.n + 1) + (size_t)d.n * (2 * d.n + 1));
       else
         hipLaunchKernelGGL((ndlqr::separator_generic<STRICT>), dim3(nsub, d.batch), dim3(sep_threads), lds,
-                           c->stream, d, l, c->AB, c->F, c->z, c->info, rec, sep_scratch);
+                           s.stream, d, l, c->AB, c->F, s.z, c->info, rec, sep_scratch);
     }
     if (lean && l == d.K - 1) break;  // nothing above the root separator
     {
@@ -768,36 +724,36 @@ static int launch_generic(NdlqrHipCtx* c, bool lean) {
       const bool mfma = !STRICT && d.n % 16 == 0 && d.rows % 16 == 0 && d.n <= 64 && !c->no_mfma;
       const size_t flds = sizeof(double) * (size_t)d.n * (d.n + 16);
       if (mfma && d.n == 64)
-        hipLaunchKernelGGL((ndlqr::schur_mfma<4>), dim3(gx, d.batch), dim3(256), flds, c->stream, d, l, c->F, c->z, bnd,
+        hipLaunchKernelGGL((ndlqr::schur_mfma<4>), dim3(gx, d.batch), dim3(256), flds, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
       else if (mfma && d.n == 48)
-        hipLaunchKernelGGL((ndlqr::schur_mfma<3>), dim3(gx, d.batch), dim3(256), flds, c->stream, d, l, c->F, c->z, bnd,
+        hipLaunchKernelGGL((ndlqr::schur_mfma<3>), dim3(gx, d.batch), dim3(256), flds, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
       else if (mfma && d.n == 32)
-        hipLaunchKernelGGL((ndlqr::schur_mfma<2>), dim3(gx, d.batch), dim3(256), flds, c->stream, d, l, c->F, c->z, bnd,
+        hipLaunchKernelGGL((ndlqr::schur_mfma<2>), dim3(gx, d.batch), dim3(256), flds, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
       else if (mfma && d.n == 16)
-        hipLaunchKernelGGL((ndlqr::schur_mfma<1>), dim3(gx, d.batch), dim3(256), flds, c->stream, d, l, c->F, c->z, bnd,
+        hipLaunchKernelGGL((ndlqr::schur_mfma<1>), dim3(gx, d.batch), dim3(256), flds, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
       else if (!STRICT && d.n % 16 == 0 && d.n > 64 && !c->no_mfma)  // (runtime-sized matrix-core form: blocks beyond 64 states)
-        hipLaunchKernelGGL(ndlqr::schur_mfma_rt, dim3(gx, d.batch), dim3(256), 0, c->stream, d, l, c->F, c->z, bnd,
+        hipLaunchKernelGGL(ndlqr::schur_mfma_rt, dim3(gx, d.batch), dim3(256), 0, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
       else {
         const long work = (long)gx * d.rows * d.n;
         hipLaunchKernelGGL((ndlqr::schur_generic<STRICT>), dim3((unsigned)((work + 255) / 256), d.batch),
-                           dim3(256), 0, c->stream, d, l, c->F, c->z, bnd, (const double*)rec);
+                           dim3(256), 0, s.stream, d, l, c->F, s.z, bnd, (const double*)rec);
       }
     }
   }
   if (lean) {
     ScopedSlot t(c, SLOT_APPLY);
     for (int l = d.K - 1; l >= 0; --l) {
-      hipLaunchKernelGGL(ndlqr::backsub_multipliers_generic, dim3(d.N >> (l + 1), d.batch), dim3(64), 0, c->stream,
-                         d, l, c->rec, c->z);
+      hipLaunchKernelGGL(ndlqr::backsub_multipliers_generic, dim3(d.N >> (l + 1), d.batch), dim3(64), 0, s.stream,
+                         d, l, s.rec, s.z);
     }
     const int work = d.N * d.rows;
-    hipLaunchKernelGGL(ndlqr::backsub_states_generic, dim3((work + 255) / 256, d.batch), dim3(256), 0, c->stream, d,
-                       c->AB, c->QR, c->rhs, c->z);
+    hipLaunchKernelGGL(ndlqr::backsub_states_generic, dim3((work + 255) / 256, d.batch), dim3(256), 0, s.stream, d,
+                       c->AB, c->QR, s.rhs, s.z);
   }
   return NDLQR_OK;
 }
@@ -912,6 +868,7 @@ static bool records_kept_as_factors(const NdlqrHipCtx* c) {
 // Enqueue leaf/bottom + per-level + apply launches on the context's stream.
 static int enqueue_solve(NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   // (the failure counters are cumulative: no memset node; the host subtracts what it has seen)
   const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
   int err = NDLQR_OK;
@@ -927,12 +884,12 @@ static int enqueue_solve(NdlqrHipCtx* c) {
   }
   // the batch-wide failure count travels to pinned host memory behind the last kernel: the host
   // reads it after the stream synchronisation without another blocking copy
-  if (!err) HIP_TRY(hipMemcpyAsync(c->h_fail, c->info + d.batch, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (!err) HIP_TRY(hipMemcpyAsync(s.h_fail, c->info + d.batch, sizeof(int), hipMemcpyDeviceToHost, s.stream));
   return err;
 }
 
-// first half of a solve: allocations, recovery from a failed solve, choice of the buffer set (the context's
-// buffer / stream fields hold it on return). *pipelined_out: this solve runs on the two-deep pipeline.
+// first half of a solve: allocations, recovery from a failed solve, choice of the buffer set (c->cur on return).
+// *pipelined_out: this solve runs on the two-deep pipeline.
 static int prepare_solve(NdlqrHipCtx* c, bool* pipelined_out) {
   HIP_TRY(hipSetDevice(c->device));
   if (solve_needs_F(c)) {  // before any capture starts: allocation is not a stream operation
@@ -961,14 +918,13 @@ static int prepare_solve(NdlqrHipCtx* c, bool* pipelined_out) {
     // the previous solve did not launch or complete: its arrival counters may be odd and its failure
     // words meaningless -- start from zero (the kernels themselves leave both clean)
     (void)sync_all(c);
-    if (c->tree_cnt)
-      HIP_TRY(hipMemsetAsync(c->tree_cnt, 0, sizeof(int) * (size_t)c->d.batch * (c->d.N / 4), c->stream));
-    if (c->alt.tree_cnt)
-      HIP_TRY(hipMemsetAsync(c->alt.tree_cnt, 0, sizeof(int) * (size_t)c->d.batch * (c->d.N / 4), c->stream));
-    HIP_TRY(hipMemsetAsync(c->info, 0, sizeof(int) * ((size_t)c->d.batch + 1), c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *c->h_fail = 0;
-    if (c->alt.h_fail) *c->alt.h_fail = 0;
+    const hipStream_t st = c->set[c->cur].stream;
+    for (const BufferSet& s : c->set)
+      if (s.tree_cnt) HIP_TRY(hipMemsetAsync(s.tree_cnt, 0, sizeof(int) * (size_t)c->d.batch * (c->d.N / 4), st));
+    HIP_TRY(hipMemsetAsync(c->info, 0, sizeof(int) * ((size_t)c->d.batch + 1), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (const BufferSet& s : c->set)
+      if (s.h_fail) *s.h_fail = 0;
     c->fail_base = 0;
     c->state_dirty = false;
   }
@@ -978,57 +934,62 @@ static int prepare_solve(NdlqrHipCtx* c, bool* pipelined_out) {
   const bool pipelined = c->pipeline >= 2 && c->own_stream && !solve_needs_F(c) &&
                          !(c->flags & (NDLQR_FLAG_PROFILE | NDLQR_FLAG_KEEP_RECORDS | NDLQR_FLAG_KEEP_FACT));
   const bool want_alt = pipelined && (c->solve_count & 1u) && ensure_alt(c);
-  if (!pipelined && c->alt.stream) HIP_TRY(hipStreamSynchronize(c->in_alt ? c->stream : c->alt.stream));
+  if (!pipelined && c->set[1].stream) HIP_TRY(hipStreamSynchronize(c->set[1].stream));
   if (red_generic) {  // (after ensure_alt: both buffer sets get their slots)
     const int rerr = ensure_red_generic(c);
     if (rerr) return rerr;
   }
-  if (want_alt != c->in_alt) swap_slot(c);
+  c->cur = want_alt ? 1 : 0;
   ++c->solve_count;
   c->state_dirty = true;  // until this solve is known to have been enqueued completely
   if (pipelined_out) *pipelined_out = pipelined;
   return NDLQR_OK;
 }
 
-// second half: the launch sequence (replayed as a hipGraph) on the current buffer set's stream
-static int launch_solve(NdlqrHipCtx* c) {
-  int err = NDLQR_OK;
-  if (c->flags & NDLQR_FLAG_PROFILE) {
-    err = enqueue_solve(c);  // per-kernel events need eager launches
-  } else {
-    // The sequence is a fixed chain of up to 1 + 2K short launches: capture it once as a hipGraph
-    // and replay it (launch-bound single solves -- batch 1 -- gain the most).
-    const unsigned apply_key = ((unsigned)c->apply_blk0 << 16) | (unsigned)c->apply_nblk;  // (restricted back-substitution of a step)
-    const bool stale = !c->graph_exec || c->graph_flags != c->flags || c->graph_stream != c->stream || c->graph_apply != apply_key;
-    if (stale) {
-      if (c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-      hipGraph_t graph = nullptr;
-      HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-      err = enqueue_solve(c);
-      hipError_t e = hipStreamEndCapture(c->stream, &graph);
-      if (err) { if (graph) (void)hipGraphDestroy(graph); return err; }
-      if (e != hipSuccess) return fail("hipStreamEndCapture", e);
-      e = hipGraphInstantiate(&c->graph_exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) { c->graph_exec = nullptr; return fail("hipGraphInstantiate", e); }
-      c->graph_flags = c->flags;
-      c->graph_stream = c->stream;
-      c->graph_apply = apply_key;
-      c->graph_rec_complete = c->rec_complete;
-      c->graph_rec_compact = c->rec_compact;  // what the captured sequence leaves behind
-      c->graph_schedule = c->schedule;
-    }
-    HIP_TRY(hipGraphLaunch(c->graph_exec, c->stream));
-    c->rec_complete = c->graph_rec_complete;
-    c->rec_compact = c->graph_rec_compact;
-    c->schedule = c->graph_schedule;
+// The launch sequence `enqueue` issues on the current buffer set's stream, replayed as the hipGraph of `g`: a fixed chain
+// of short launches, captured once (launch-bound single solves -- batch 1 -- gain the most) and again whenever the key it
+// was captured under changes. The schedule bookkeeping is then what THIS chain's sequence leaves behind.
+static int replay_chain(NdlqrHipCtx* c, CapturedChain& g, int (*enqueue)(NdlqrHipCtx*)) {
+  const hipStream_t st = c->set[c->cur].stream;
+  const unsigned apply = ((unsigned)c->apply_blk0 << 16) | (unsigned)c->apply_nblk;  // (restricted back-substitution of a step)
+  if (!g.exec || g.flags != c->flags || g.stream != st || g.apply != apply) {
+    g.reset();
+    hipGraph_t graph = nullptr;
+    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int err = enqueue(c);
+    hipError_t e = hipStreamEndCapture(st, &graph);
+    if (err) { if (graph) (void)hipGraphDestroy(graph); return err; }
+    if (e != hipSuccess) return fail("hipStreamEndCapture", e);
+    e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) { g.exec = nullptr; return fail("hipGraphInstantiate", e); }
+    g.flags = c->flags;
+    g.stream = st;
+    g.apply = apply;
+    g.rec_complete = c->rec_complete;
+    g.rec_compact = c->rec_compact;
+    g.schedule = c->schedule;
   }
+  HIP_TRY(hipGraphLaunch(g.exec, st));
+  c->rec_complete = g.rec_complete;
+  c->rec_compact = g.rec_compact;
+  c->schedule = g.schedule;
+  return NDLQR_OK;
+}
+
+// a complete factor array is on the device with KEEP, and on the strict runtime-sized path
+static bool solve_leaves_factors(const NdlqrHipCtx* c) {
+  return (c->flags & NDLQR_FLAG_KEEP_FACT) != 0 || records_kept_as_factors(c) ||
+         ((c->flags & NDLQR_FLAG_GENERIC) && (c->flags & NDLQR_FLAG_STRICT_FP));
+}
+
+// second half: the launch sequence on the current buffer set's stream (per-kernel events need eager launches)
+static int launch_solve(NdlqrHipCtx* c) {
+  const int err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_solve(c) : replay_chain(c, c->set[c->cur].graph, enqueue_solve);
   if (err) return err;
   HIP_TRY(hipGetLastError());
   note_solution(c);
-  // a complete factor array is on the device with KEEP, and on the strict runtime-sized path
-  c->fact_valid = (c->flags & NDLQR_FLAG_KEEP_FACT) != 0 || records_kept_as_factors(c) ||
-                  ((c->flags & NDLQR_FLAG_GENERIC) && (c->flags & NDLQR_FLAG_STRICT_FP));
+  c->fact_valid = solve_leaves_factors(c);
   return NDLQR_OK;
 }
 
@@ -1036,12 +997,13 @@ int ndlqr_hip_solve_async(NdlqrHipCtx* c) {
   if (!c) return NDLQR_ERR_INVALID;
   int err = prepare_solve(c, nullptr);
   if (err) return err;
+  BufferSet& s = c->set[c->cur];
   err = rhs_make_current(c, 0xFu);  // (this buffer set's copy of the right-hand side may be behind: steps write one set)
   if (err) return err;
-  HIP_TRY(hipEventRecord(c->ev_start, c->stream));
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   err = launch_solve(c);
   if (err) return err;
-  HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   c->timing_pending = true;
   c->state_dirty = false;
   return NDLQR_OK;
@@ -1082,30 +1044,31 @@ int ndlqr_hip_staged_io(NdlqrHipCtx* c, double** AB, double** QR, double** rhs, 
 static int enqueue_staged(NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
+  BufferSet& s = c->set[c->cur];
   size_t oAB, oQR, orhs, oz;
   (void)staged_doubles(u, &oAB, &oQR, &orhs, &oz);
   const size_t nAB = oQR, nQR = orhs - oQR, nz = oz - orhs;
-  hipStream_t st = c->stream;
+  hipStream_t st = s.stream;
   if (c->padded) {
     double* s0 = c->pad_stage;
     HIP_TRY(hipMemcpyAsync(s0, c->h_io, sizeof(double) * (nAB + nQR + nz), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(ndlqr::pad_inputs_generic, dim3(d.N, d.batch), dim3(128), 0, st, u, d, 0, (const double*)s0,
-                       (const double*)(s0 + oQR), (const double*)(s0 + orhs), c->AB, c->QR, c->rhs);
+                       (const double*)(s0 + oQR), (const double*)(s0 + orhs), c->AB, c->QR, s.rhs);
     HIP_TRY(hipGetLastError());
   } else {
     HIP_TRY(hipMemcpyAsync(c->AB, c->h_io + oAB, sizeof(double) * nAB, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(c->QR, c->h_io + oQR, sizeof(double) * nQR, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->rhs, c->h_io + orhs, sizeof(double) * nz, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.rhs, c->h_io + orhs, sizeof(double) * nz, hipMemcpyHostToDevice, st));
   }
   const int err = enqueue_solve(c);
   if (err) return err;
   if (c->padded) {
-    hipLaunchKernelGGL(ndlqr::unpad_blocks_generic, dim3(d.N * d.batch), dim3(64), 0, st, u, d, (const double*)c->z,
+    hipLaunchKernelGGL(ndlqr::unpad_blocks_generic, dim3(d.N * d.batch), dim3(64), 0, st, u, d, (const double*)s.z,
                        c->pad_stage + oz);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_io + oz, c->pad_stage + oz, sizeof(double) * nz, hipMemcpyDeviceToHost, st));
   } else {
-    HIP_TRY(hipMemcpyAsync(c->h_io + oz, c->z, sizeof(double) * nz, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->h_io + oz, s.z, sizeof(double) * nz, hipMemcpyDeviceToHost, st));
   }
   return NDLQR_OK;
 }
@@ -1121,38 +1084,14 @@ int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
   rhs_written_cur(c, 0xFu);
   c->fact_valid = false;  // new A, B, Q, R: neither a cached factor array nor cached records match
   c->rec_complete = false;
-  HIP_TRY(hipEventRecord(c->ev_start, c->stream));
-  if (c->flags & NDLQR_FLAG_PROFILE) {
-    err = enqueue_staged(c);  // per-kernel events need eager launches
-    if (err) return err;
-  } else {
-    const bool stale = !c->graph_staged || c->graph_staged_flags != c->flags;
-    if (stale) {
-      if (c->graph_staged) { (void)hipGraphExecDestroy(c->graph_staged); c->graph_staged = nullptr; }
-      hipGraph_t graph = nullptr;
-      HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-      err = enqueue_staged(c);
-      hipError_t e = hipStreamEndCapture(c->stream, &graph);
-      if (err) { if (graph) (void)hipGraphDestroy(graph); return err; }
-      if (e != hipSuccess) return fail("hipStreamEndCapture", e);
-      e = hipGraphInstantiate(&c->graph_staged, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) { c->graph_staged = nullptr; return fail("hipGraphInstantiate", e); }
-      c->graph_staged_flags = c->flags;
-      c->graph_rec_complete = c->rec_complete;
-      c->graph_rec_compact = c->rec_compact;
-      c->graph_schedule = c->schedule;
-    }
-    HIP_TRY(hipGraphLaunch(c->graph_staged, c->stream));
-    c->rec_complete = c->graph_rec_complete;
-    c->rec_compact = c->graph_rec_compact;
-    c->schedule = c->graph_schedule;
-  }
+  BufferSet& s = c->set[c->cur];
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_staged(c) : replay_chain(c, c->staged, enqueue_staged);
+  if (err) return err;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   note_solution(c);
-  c->fact_valid = (c->flags & NDLQR_FLAG_KEEP_FACT) != 0 || records_kept_as_factors(c) ||
-                  ((c->flags & NDLQR_FLAG_GENERIC) && (c->flags & NDLQR_FLAG_STRICT_FP));
+  c->fact_valid = solve_leaves_factors(c);
   c->timing_pending = true;
   c->state_dirty = false;
   return ndlqr_hip_synchronize(c);
@@ -1177,17 +1116,18 @@ static int time_shard_copy_slots(NdlqrHipCtx* c, int G, double* buf, bool to_buf
   const SmallInstance* inst = time_shard_instance(c, G);
   if (!inst || !buf) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
+  BufferSet& b = c->set[c->cur];
   const size_t slot = (size_t)inst->slot();
   const size_t pitch_red = sizeof(double) * (size_t)(d.N >> 2) * slot, width = sizeof(double) * slot;
   HIP_TRY(hipSetDevice(c->device));
   for (int j = 1; j < G; ++j) {
     const int s = j * (d.N / G) - 1;
-    double* p = c->red + (size_t)(s >> 2) * slot;
+    double* p = b.red + (size_t)(s >> 2) * slot;
     double* q = buf + (size_t)(j - 1) * d.batch * slot;
-    if (to_buf) HIP_TRY(hipMemcpy2DAsync(q, width, p, pitch_red, width, (size_t)d.batch, hipMemcpyDefault, c->stream));
-    else HIP_TRY(hipMemcpy2DAsync(p, pitch_red, q, width, width, (size_t)d.batch, hipMemcpyDefault, c->stream));
+    if (to_buf) HIP_TRY(hipMemcpy2DAsync(q, width, p, pitch_red, width, (size_t)d.batch, hipMemcpyDefault, b.stream));
+    else HIP_TRY(hipMemcpy2DAsync(p, pitch_red, q, width, width, (size_t)d.batch, hipMemcpyDefault, b.stream));
   }
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(b.stream));
   return NDLQR_OK;
 }
 int ndlqr_hip_time_shard_export(NdlqrHipCtx* c, int G, double* buf) { return time_shard_copy_slots(c, G, buf, true); }
@@ -1205,13 +1145,13 @@ static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
   if (c->flags & ~NDLQR_FLAG_PROFILE) { g_last_error = "time-axis sharding runs the default fast mode only"; return NDLQR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
   if (phase == 0) {
-    if (c->pipeline != 1 || c->in_alt) {
+    if (c->pipeline != 1 || c->cur != 0) {
       const int perr = ndlqr_hip_set_pipeline_depth(c, 1);  // stream-ordered on the primary buffer set
       if (perr) return perr;
     }
     const int merr = rhs_make_current(c, 0xFu);
     if (merr) return merr;
-    HIP_TRY(hipEventRecord(c->ev_start, c->stream));
+    HIP_TRY(hipEventRecord(c->set[0].ev_start, c->set[0].stream));
   }
   const int err = inst->tshard(c, phase, g, G);
   if (err) {
@@ -1220,8 +1160,9 @@ static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
   }
   HIP_TRY(hipGetLastError());
   if (phase == 1) {
-    HIP_TRY(hipMemcpyAsync(c->h_fail, c->info + c->d.batch, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
+    BufferSet& s = c->set[c->cur];
+    HIP_TRY(hipMemcpyAsync(s.h_fail, c->info + c->d.batch, sizeof(int), hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
     c->timing_pending = true;
     note_solution(c);
     c->fact_valid = false;
@@ -1234,9 +1175,10 @@ int ndlqr_hip_time_shard_finish(NdlqrHipCtx* c, int g, int G) { return time_shar
 
 // transfer staging of the current buffer set: max(flat right-hand side, packed solutions) doubles
 static int ensure_xfer(NdlqrHipCtx* c) {
-  if (c->xfer) return NDLQR_OK;
+  BufferSet& s = c->set[c->cur];
+  if (s.xfer) return NDLQR_OK;
   const ndlqr::Dims& d = c->du;  // (caller-layout data: flat right-hand side going up, packed solutions coming down)
-  HIP_TRY(hipMalloc(&c->xfer, sizeof(double) * ((size_t)d.batch * d.N * d.rows + (size_t)d.batch * d.n)));
+  HIP_TRY(hipMalloc(&s.xfer, sizeof(double) * ((size_t)d.batch * d.N * d.rows + (size_t)d.batch * d.n)));
   return NDLQR_OK;
 }
 
@@ -1261,6 +1203,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   const ndlqr::Dims& d = c->d;
   int err = prepare_solve(c, nullptr);
   if (err) return err;
+  BufferSet& s = c->set[c->cur];
   err = ensure_xfer(c);  // (before anything is captured: allocation is not a stream operation)
   if (err) return err;
   // the parts of the right-hand side this step does not replace: this buffer set's copy of them may be behind the other's
@@ -1272,14 +1215,14 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   // those copies itself and blocks). Solutions: pack kernel, then ONE copy-engine transfer. With the two-deep
   // pipeline the transfers of one step run beside the kernels of the other set's step; otherwise (factor array /
   // records kept, caller-owned stream, depth 1) the steps are simply stream-ordered.
-  hipStream_t st = c->stream;
-  HIP_TRY(hipEventRecord(c->ev_start, st));
+  hipStream_t st = s.stream;
+  HIP_TRY(hipEventRecord(s.ev_start, st));
   const ndlqr::Dims& u = c->du;
   const size_t nq = (size_t)u.batch * u.N * u.n, nr = (size_t)u.batch * u.N * u.m, nx = (size_t)u.batch * u.n;
   const double* src[4] = {q, r, dd, x0};
   const size_t cnt[4] = {nq, nr, nq, nx};
   const double* view[4];
-  double* stage = c->xfer;
+  double* stage = s.xfer;
   for (int k = 0; k < 4; ++k) {
     view[k] = pinned_device_view(src[k], c->device);
     if (src[k] && !view[k]) {
@@ -1289,7 +1232,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
     stage += cnt[k];
   }
   hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic, dim3(512), dim3(256), 0, st, u, d, view[0], view[1], view[2],
-                     view[3], c->rhs);
+                     view[3], s.rhs);
   HIP_TRY(hipGetLastError());
   rhs_written_cur(c, written);
   // NDLQR_SOLN_ONLY: nothing but the selected knots is wanted -- the last launch of the back-substitution runs the
@@ -1314,7 +1257,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   //  full-record form of the small shapes -- tree schedule -- re-solves no faster than it factors and keeps factoring.)
   const bool generic_records = !pick_small(c) && c->d.n > 32;
   if ((c->flags & NDLQR_FLAG_KEEP_RECORDS) && !(c->flags & (NDLQR_FLAG_STRICT_FP | NDLQR_FLAG_KEEP_FACT)) && c->rec_complete &&
-      (c->rec_compact || generic_records) && !c->in_alt && try_launch_rhs_records(c)) {
+      (c->rec_compact || generic_records) && c->cur == 0 && try_launch_rhs_records(c)) {
     HIP_TRY(hipGetLastError());
     note_solution(c);
     c->schedule = generic_records ? "generic-reduced-records (re-solve)" : "reduced-compact-records (re-solve)";
@@ -1325,7 +1268,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   // (the staging has been consumed by the pack kernel: it now takes the packed solutions -- all of them, or the slice
   //  chosen with ndlqr_hip_set_step_selection)
   //  chosen with ndlqr_hip_set_step_selection); a `soln` in this device's memory is written by the pack kernel itself
-  double* packed = c->xfer;
+  double* packed = s.xfer;
   {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, soln) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->device) packed = soln;
@@ -1334,19 +1277,19 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   if (c->sel_nknots > 0) {
     const size_t width = ((c->sel_blocks & 1u) ? u.n : 0) + ((c->sel_blocks & 2u) ? u.n : 0) + ((c->sel_blocks & 4u) ? u.m : 0);
     hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(c->sel_nknots, d.batch), dim3(64), 0, st, u, d, c->sel_knot0,
-                       c->sel_nknots, c->sel_blocks & 7u, (const double*)c->z, packed);
+                       c->sel_nknots, c->sel_blocks & 7u, (const double*)s.z, packed);
     HIP_TRY(hipGetLastError());
     if (packed != soln)
       HIP_TRY(hipMemcpyAsync(soln, packed, sizeof(double) * width * c->sel_nknots * d.batch, hipMemcpyDefault, st));
   } else {
-    hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(u), d.batch), dim3(256), 0, st, u, d, c->z, packed);
+    hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(u), d.batch), dim3(256), 0, st, u, d, s.z, packed);
     HIP_TRY(hipGetLastError());
     const size_t nvars = (size_t)u.rows * u.N - u.m;
     if (packed != soln) HIP_TRY(hipMemcpyAsync(soln, packed, sizeof(double) * nvars * d.batch, hipMemcpyDefault, st));
   }
-  HIP_TRY(hipEventRecord(c->ev_stop, st));
+  HIP_TRY(hipEventRecord(s.ev_stop, st));
   HIP_TRY(hipEventRecord(c->ev_step[c->step_count & 1u], st));
-  c->step_set[c->step_count & 1u] = c->in_alt ? 1 : 0;
+  c->step_set[c->step_count & 1u] = c->cur;
   ++c->step_count;
   c->timing_pending = true;
   c->state_dirty = false;
@@ -1364,18 +1307,19 @@ int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   const ndlqr::Dims& u = c->du;
   int err = prepare_solve(c, nullptr);
   if (err) return err;
+  BufferSet& s = c->set[c->cur];
   err = ensure_xfer(c);
   if (err) return err;
   err = rhs_make_current(c, 0xFu);
   if (err) return err;
-  hipStream_t st = c->stream;
-  HIP_TRY(hipEventRecord(c->ev_start, st));
+  hipStream_t st = s.stream;
+  HIP_TRY(hipEventRecord(s.ev_start, st));
   c->apply_blk0 = knot0 >> 3;
   c->apply_nblk = ((knot0 + nknots - 1) >> 3) - c->apply_blk0 + 1;
   err = launch_solve(c);
   c->apply_blk0 = c->apply_nblk = 0;
   if (err) return err;
-  double* packed = c->xfer;
+  double* packed = s.xfer;
   {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, out) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->device) packed = out;
@@ -1383,10 +1327,10 @@ int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   }
   const size_t width = ((blocks & 1u) ? u.n : 0) + ((blocks & 2u) ? u.n : 0) + ((blocks & 4u) ? u.m : 0);
   hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(nknots, d.batch), dim3(64), 0, st, u, d, knot0, nknots, blocks & 7u,
-                     (const double*)c->z, packed);
+                     (const double*)s.z, packed);
   HIP_TRY(hipGetLastError());
   if (packed != out) HIP_TRY(hipMemcpyAsync(out, packed, sizeof(double) * width * nknots * d.batch, hipMemcpyDefault, st));
-  HIP_TRY(hipEventRecord(c->ev_stop, st));
+  HIP_TRY(hipEventRecord(s.ev_stop, st));
   c->timing_pending = true;
   c->state_dirty = false;
   return NDLQR_OK;
@@ -1401,8 +1345,7 @@ int ndlqr_hip_synchronize_previous(NdlqrHipCtx* c) {
   HIP_TRY(hipEventSynchronize(c->ev_step[slot]));
   // The failure word of that step's buffer set holds the cumulative count of non-positive pivots as of the end of its
   // solve: anything beyond what has been reported so far belongs to it (or to a step before it).
-  const bool cur_is_alt = c->in_alt;
-  const int* word = (c->step_set[slot] == (cur_is_alt ? 1 : 0)) ? c->h_fail : c->alt.h_fail;
+  const int* word = c->set[c->step_set[slot]].h_fail;
   if (word && *word > c->fail_base) {
     c->last_failures = *word - c->fail_base;
     c->fail_base = *word;
@@ -1429,6 +1372,7 @@ int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
     return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
+  BufferSet& s = c->set[c->cur];
   if (c->z_partial && (knot0 < 8 * c->z_blk0 || knot0 + nknots > 8 * (c->z_blk0 + c->z_nblk)))
     return need_full_solution(c, "ndlqr_hip_download_selection");
   HIP_TRY(hipSetDevice(c->device));
@@ -1436,11 +1380,11 @@ int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   const int xerr = ensure_xfer(c);
   if (xerr) return xerr;
   const size_t width = ((blocks & 1u) ? u.n : 0) + ((blocks & 2u) ? u.n : 0) + ((blocks & 4u) ? u.m : 0);
-  hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(nknots, d.batch), dim3(64), 0, c->stream, u, d, knot0, nknots,
-                     blocks, c->z_latest ? c->z_latest : (const double*)c->z, c->xfer);
+  hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(nknots, d.batch), dim3(64), 0, s.stream, u, d, knot0, nknots,
+                     blocks, (const double*)c->set[c->latest].z, s.xfer);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, c->xfer, sizeof(double) * width * nknots * d.batch, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(out, s.xfer, sizeof(double) * width * nknots * d.batch, hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }
 
@@ -1477,6 +1421,7 @@ int ndlqr_hip_copy(void* dst, const void* src, size_t bytes) {
 int ndlqr_hip_upload_rhs(NdlqrHipCtx* c, int p0, int count, const double* rhs) {
   if (!c || !rhs || p0 < 0 || count <= 0 || p0 + count > c->d.batch) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
   {
@@ -1488,14 +1433,14 @@ int ndlqr_hip_upload_rhs(NdlqrHipCtx* c, int p0, int count, const double* rhs) {
     const size_t uz = (size_t)c->du.N * c->du.rows * count;
     const int serr = ensure_pad_stage(c, uz);
     if (serr) return serr;
-    HIP_TRY(hipMemcpyAsync(c->pad_stage, rhs, sizeof(double) * uz, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(ndlqr::pad_inputs_generic, dim3(d.N, count), dim3(128), 0, c->stream, c->du, d, p0,
-                       (const double*)nullptr, (const double*)nullptr, (const double*)c->pad_stage, c->AB, c->QR, c->rhs);
+    HIP_TRY(hipMemcpyAsync(c->pad_stage, rhs, sizeof(double) * uz, hipMemcpyHostToDevice, s.stream));
+    hipLaunchKernelGGL(ndlqr::pad_inputs_generic, dim3(d.N, count), dim3(128), 0, s.stream, c->du, d, p0,
+                       (const double*)nullptr, (const double*)nullptr, (const double*)c->pad_stage, c->AB, c->QR, s.rhs);
     HIP_TRY(hipGetLastError());
   } else {
-    HIP_TRY(hipMemcpyAsync(c->rhs + p0 * sz, rhs, sizeof(double) * sz * count, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(s.rhs + p0 * sz, rhs, sizeof(double) * sz * count, hipMemcpyHostToDevice, s.stream));
   }
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
   rhs_written_cur(c, 0xFu);
   next_solve_on_current_set(c);
   return NDLQR_OK;
@@ -1504,10 +1449,11 @@ int ndlqr_hip_upload_rhs(NdlqrHipCtx* c, int p0, int count, const double* rhs) {
 template <bool STRICT>
 static void launch_rhs_sweep(NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   {
     ScopedSlot t(c, SLOT_LEAF);
-    hipLaunchKernelGGL((ndlqr::rhs_leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(64), 0, c->stream, d, c->QR,
-                       c->rhs, c->z);
+    hipLaunchKernelGGL((ndlqr::rhs_leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(64), 0, s.stream, d, c->QR,
+                       s.rhs, s.z);
   }
   for (int l = 0; l < d.K; ++l) {
     {
@@ -1515,13 +1461,13 @@ static void launch_rhs_sweep(NdlqrHipCtx* c) {
       const size_t lds_staged = sizeof(double) * ((size_t)d.n * (d.n + 1) + d.n);
       const int staged = lds_staged <= 160 * 1024 ? 1 : 0;
       hipLaunchKernelGGL((ndlqr::rhs_separator_generic<STRICT>), dim3(d.N >> (l + 1), d.batch), dim3(64),
-                         staged ? lds_staged : sizeof(double) * (size_t)d.n, c->stream, d, l, c->AB, c->F, c->z, staged);
+                         staged ? lds_staged : sizeof(double) * (size_t)d.n, s.stream, d, l, c->AB, c->F, s.z, staged);
     }
     {
       ScopedSlot t(c, SLOT_SCHUR);
       const int work = d.N * d.rows;
       hipLaunchKernelGGL((ndlqr::rhs_update_generic<STRICT>), dim3((work + 255) / 256, d.batch), dim3(256), 0,
-                         c->stream, d, l, c->F, c->z);
+                         s.stream, d, l, c->F, s.z);
     }
   }
 }
@@ -1555,12 +1501,13 @@ int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
   }
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
-  if (c->in_alt) swap_slot(c);  // cached records / factors live in the primary set
+  c->cur = 0;  // cached records / factors live in the primary set
+  BufferSet& s = c->set[0];
   {
     const int merr = rhs_make_current(c, 0xFu);
     if (merr) return merr;
   }
-  HIP_TRY(hipEventRecord(c->ev_start, c->stream));
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   if (!try_launch_rhs_records(c)) {
     if (!c->fact_valid) {  // records only, but this shape / horizon has no record-based re-solve
       g_last_error = "rhs-only solve: this configuration needs NDLQR_FLAG_KEEP_FACT";
@@ -1570,7 +1517,7 @@ int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
     if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c); else launch_rhs_sweep<false>(c);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   c->timing_pending = true;
   note_solution(c);
   return NDLQR_OK;
@@ -1593,7 +1540,8 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
   if (nknots < 0 || knot0 < 0 || knot0 + nknots > c->d.N || (nknots > 0 && (!(blocks & 7u) || (blocks & ~15u)))) return NDLQR_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
-  if (c->in_alt) swap_slot(c);
+  c->cur = 0;
+  BufferSet& st = c->set[0];
   const SmallInstance* inst = pick_small(c);
   if (!inst || !c->rec_complete || !c->rec_compact) {
     g_last_error = "multiple right-hand sides need the compact records of a solve with NDLQR_FLAG_KEEP_RECORDS on a "
@@ -1627,8 +1575,8 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
               hipMalloc(&c->multi_in, sizeof(double) * nin) == hipSuccess &&
               hipMalloc(&c->multi_out, sizeof(double) * cap * nvars) == hipSuccess;
     // (padded shapes: the pad entries of the right-hand side are zero and stay zero -- the pack kernel never touches them)
-    ok = ok && hipMemsetAsync(c->multi_rhs, 0, sizeof(double) * nz, c->stream) == hipSuccess &&
-         hipMemsetAsync(c->multi_z, 0, sizeof(double) * nz, c->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(c->multi_rhs, 0, sizeof(double) * nz, st.stream) == hipSuccess &&
+         hipMemsetAsync(c->multi_z, 0, sizeof(double) * nz, st.stream) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();
       g_last_error = "buffers of the multiple right-hand sides do not fit on the device";
@@ -1643,14 +1591,14 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
     uc.batch = dc.batch = (int)count;  // (the pack kernels index problems by their position alone)
     const size_t nq = count * u.N * u.n, nr = count * u.N * u.m, nx = count * u.n;
     double* in = c->multi_in;
-    HIP_TRY(hipMemcpyAsync(in, q + s0 * per_set * u.N * u.n, sizeof(double) * nq, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + nq, r + s0 * per_set * u.N * u.m, sizeof(double) * nr, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + nq + nr, dd + s0 * per_set * u.N * u.n, sizeof(double) * nq, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + 2 * nq + nr, x0 + s0 * per_set * u.n, sizeof(double) * nx, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic, dim3(512), dim3(256), 0, c->stream, uc, dc, (const double*)in,
+    HIP_TRY(hipMemcpyAsync(in, q + s0 * per_set * u.N * u.n, sizeof(double) * nq, hipMemcpyHostToDevice, st.stream));
+    HIP_TRY(hipMemcpyAsync(in + nq, r + s0 * per_set * u.N * u.m, sizeof(double) * nr, hipMemcpyHostToDevice, st.stream));
+    HIP_TRY(hipMemcpyAsync(in + nq + nr, dd + s0 * per_set * u.N * u.n, sizeof(double) * nq, hipMemcpyHostToDevice, st.stream));
+    HIP_TRY(hipMemcpyAsync(in + 2 * nq + nr, x0 + s0 * per_set * u.n, sizeof(double) * nx, hipMemcpyHostToDevice, st.stream));
+    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic, dim3(512), dim3(256), 0, st.stream, uc, dc, (const double*)in,
                        (const double*)(in + nq), (const double*)(in + nq + nr), (const double*)(in + 2 * nq + nr), c->multi_rhs);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_start, c->stream));
+    HIP_TRY(hipEventRecord(st.ev_start, st.stream));
     if (nknots > 0) { c->apply_blk0 = knot0 >> 3; c->apply_nblk = ((knot0 + nknots - 1) >> 3) - c->apply_blk0 + 1; }
     const bool launched = inst->multi(c, (int)count, c->multi_rhs, c->multi_zsep, c->multi_fsum, c->multi_ytop, c->multi_z);
     c->apply_blk0 = c->apply_nblk = 0;
@@ -1659,24 +1607,24 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
       return NDLQR_ERR_INVALID;
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
+    HIP_TRY(hipEventRecord(st.ev_stop, st.stream));
     if (nknots > 0) {
       const size_t width = ((blocks & 1u) ? u.n : 0) + ((blocks & 2u) ? u.n : 0) + ((blocks & 4u) ? u.m : 0);
-      hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(nknots, (unsigned)count), dim3(64), 0, c->stream, uc, dc, knot0,
+      hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(nknots, (unsigned)count), dim3(64), 0, st.stream, uc, dc, knot0,
                          nknots, blocks & 7u, (const double*)c->multi_z, c->multi_out);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpyAsync(soln + s0 * per_set * nknots * width, c->multi_out, sizeof(double) * count * nknots * width,
-                             hipMemcpyDeviceToHost, c->stream));
+                             hipMemcpyDeviceToHost, st.stream));
     } else {
-      hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(uc), (unsigned)count), dim3(256), 0, c->stream, uc, dc,
+      hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(uc), (unsigned)count), dim3(256), 0, st.stream, uc, dc,
                          (const double*)c->multi_z, c->multi_out);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpyAsync(soln + s0 * per_set * nvars, c->multi_out, sizeof(double) * count * nvars, hipMemcpyDeviceToHost,
-                             c->stream));
+                             st.stream));
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(st.stream));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->ev_start, c->ev_stop) == hipSuccess) total_ms += ms;
+    if (hipEventElapsedTime(&ms, st.ev_start, st.ev_stop) == hipSuccess) total_ms += ms;
   }
   c->last_ms = total_ms;
   c->timing_pending = false;
@@ -1701,12 +1649,13 @@ int ndlqr_hip_synchronize(NdlqrHipCtx* c) {
   }
   if (c->timing_pending) {
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    HIP_TRY(hipEventElapsedTime(&ms, c->set[c->cur].ev_start, c->set[c->cur].ev_stop));
     c->last_ms = ms;
     c->timing_pending = false;
     // info[batch] = cumulative batch-wide count of non-positive pivots: failures since the last synchronisation
-    int seen = *c->h_fail;  // the counter is cumulative: the larger of the two slots' copies is the newer one
-    if (c->alt.h_fail && *c->alt.h_fail > seen) seen = *c->alt.h_fail;
+    int seen = 0;  // the counter is cumulative: the larger of the two sets' copies is the newer one
+    for (const BufferSet& s : c->set)
+      if (s.h_fail && *s.h_fail > seen) seen = *s.h_fail;
     c->last_failures = seen - c->fail_base;
     c->fail_base = seen;
   }
@@ -1762,24 +1711,25 @@ int ndlqr_hip_download_solutions(NdlqrHipCtx* c, int p0, int count, double* soln
   if (!c || !soln || p0 < 0 || count <= 0 || p0 + count > c->d.batch) return NDLQR_ERR_INVALID;
   if (c->z_partial) return need_full_solution(c, "ndlqr_hip_download_solutions");
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
   const int xerr = ensure_xfer(c);
   if (xerr) return xerr;
-  const double* zl = c->z_latest ? c->z_latest : c->z;
+  const double* zl = c->set[c->latest].z;
   const size_t nvars = (size_t)c->du.rows * d.N - c->du.m, pitch = (size_t)d.rows * d.N;
-  hipStream_t st = c->stream;
-  hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(c->du), count), dim3(256), 0, st, c->du, d, zl + p0 * pitch, c->xfer);
+  hipStream_t st = s.stream;
+  hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(c->du), count), dim3(256), 0, st, c->du, d, zl + p0 * pitch, s.xfer);
   HIP_TRY(hipGetLastError());
   const size_t total = nvars * count;
   if (host_ptr_is_pinned(soln)) {
-    HIP_TRY(hipMemcpyAsync(soln, c->xfer, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(soln, s.xfer, sizeof(double) * total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return NDLQR_OK;
   }
   const size_t chunk = (8u << 20) / sizeof(double);
   if (total <= chunk / 8) {  // small: one synchronous copy (the runtime stages it)
-    HIP_TRY(hipMemcpyAsync(soln, c->xfer, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(soln, s.xfer, sizeof(double) * total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return NDLQR_OK;
   }
@@ -1791,7 +1741,7 @@ int ndlqr_hip_download_solutions(NdlqrHipCtx* c, int p0, int count, double* soln
   for (size_t i = 0; i <= nchunks && e == hipSuccess; ++i) {
     if (i < nchunks) {  // (buffer i & 1 held chunk i - 2, which the previous iteration copied out)
       const size_t off = i * chunk, len = total - off < chunk ? total - off : chunk;
-      e = hipMemcpyAsync(c->h_stage[i & 1], c->xfer + off, sizeof(double) * len, hipMemcpyDeviceToHost, st);
+      e = hipMemcpyAsync(c->h_stage[i & 1], s.xfer + off, sizeof(double) * len, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipEventRecord(done[i & 1], st);
     }
     if (i > 0 && e == hipSuccess) {
@@ -1817,7 +1767,7 @@ int ndlqr_hip_pack_solutions_device(NdlqrHipCtx* c, double* dst) {
   HIP_TRY(hipSetDevice(c->device));
   // on the stream of the latest solve: ordered behind it, asynchronous for the caller
   hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(c->du), d.batch), dim3(256), 0,
-                     c->stream_latest ? c->stream_latest : c->stream, c->du, d, c->z_latest ? c->z_latest : c->z, dst);
+                     c->set[c->latest].stream, c->du, d, c->set[c->latest].z, dst);
   HIP_TRY(hipGetLastError());
   return NDLQR_OK;
 }
@@ -1826,17 +1776,18 @@ int ndlqr_hip_kkt_residual(NdlqrHipCtx* c, double* res, double* bnorm) {
   if (!c || !res) return NDLQR_ERR_INVALID;
   if (c->z_partial) return need_full_solution(c, "ndlqr_hip_kkt_residual");
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
   if (!c->kkt_out) HIP_TRY(hipMalloc(&c->kkt_out, sizeof(double) * 2 * (size_t)d.batch));
   double* out = c->kkt_out;
   HIP_TRY(sync_all(c));
-  hipLaunchKernelGGL(ndlqr::kkt_residual_generic, dim3(d.batch), dim3(256), 0, c->stream, d, c->AB, c->QR, c->rhs,
-                     c->z_latest ? c->z_latest : c->z, out);
+  hipLaunchKernelGGL(ndlqr::kkt_residual_generic, dim3(d.batch), dim3(256), 0, s.stream, d, c->AB, c->QR, s.rhs,
+                     c->set[c->latest].z, out);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(res, out, sizeof(double) * d.batch, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(res, out, sizeof(double) * d.batch, hipMemcpyDeviceToHost, s.stream);
   if (e == hipSuccess && bnorm)
-    e = hipMemcpyAsync(bnorm, out + d.batch, sizeof(double) * d.batch, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    e = hipMemcpyAsync(bnorm, out + d.batch, sizeof(double) * d.batch, hipMemcpyDeviceToHost, s.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
   if (e != hipSuccess) return fail("ndlqr_hip_kkt_residual", e);
   return NDLQR_OK;
 }
@@ -1845,21 +1796,22 @@ int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
   if (!c || !z_full || p < 0 || p >= c->d.batch) return NDLQR_ERR_INVALID;
   if (c->z_partial) return need_full_solution(c, "ndlqr_hip_download_rhs_blocks");
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
   const size_t pitch = (size_t)d.rows * d.N;
   HIP_TRY(sync_all(c));
-  const double* zp = (c->z_latest ? c->z_latest : c->z) + p * pitch;
+  const double* zp = c->set[c->latest].z + p * pitch;
   if (c->padded) {
     const size_t upitch = (size_t)c->du.rows * d.N;
     const int serr = ensure_pad_stage(c, upitch);
     if (serr) return serr;
-    hipLaunchKernelGGL(ndlqr::unpad_blocks_generic, dim3(d.N), dim3(64), 0, c->stream, c->du, d, zp, c->pad_stage);
+    hipLaunchKernelGGL(ndlqr::unpad_blocks_generic, dim3(d.N), dim3(64), 0, s.stream, c->du, d, zp, c->pad_stage);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(z_full, c->pad_stage, sizeof(double) * upitch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(z_full, c->pad_stage, sizeof(double) * upitch, hipMemcpyDeviceToHost, s.stream));
   } else {
-    HIP_TRY(hipMemcpyAsync(z_full, zp, sizeof(double) * pitch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(z_full, zp, sizeof(double) * pitch, hipMemcpyDeviceToHost, s.stream));
   }
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }
 
@@ -1871,11 +1823,12 @@ int ndlqr_hip_download_factors(NdlqrHipCtx* c, int p, double* fact) {
     return NDLQR_ERR_INVALID;
   }
   const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
   const size_t count = (size_t)d.K * d.N * d.fb;
   std::vector<double> tmp(count);
-  HIP_TRY(hipMemcpyAsync(tmp.data(), c->F + p * count, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(tmp.data(), c->F + p * count, sizeof(double) * count, hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
   // device: [level][knot][row][col] row-major -> reference: block (k,level) at (k + N*level)*fb,
   // sub-blocks lambda (n x n), state (n x n), input (m x n), each column-major (src/nddata.c:40-53)
   // (a padded shape: the device blocks have np >= n columns and rows lambda [0, np), state [np, 2 np), input
@@ -2044,12 +1997,13 @@ int ndlqr_hip_trsv_lower(int n, int nrhs, const double* L, int ldl, double* B, i
 extern "C" long ndlqr_hip_debug_download(NdlqrHipCtx* c, int which, double* host, long count) {
   if (!c || !host) return -1;
   const ndlqr::Dims& d = c->d;
-  const double* src = which == 0 ? c->rec : c->red;
+  BufferSet& s = c->set[c->cur];
+  const double* src = which == 0 ? s.rec : s.red;
   const size_t slot_doubles = ((size_t)d.n * (d.n + 1) + 2 * (size_t)d.n * d.n + 2 * d.n + 15) / 16 * 16;  // RedSlot<NX>::SIZE
   const size_t have = which == 0 ? (size_t)d.batch * d.N * (2 * d.n * d.n + d.n) : (size_t)d.batch * (d.N / 4) * slot_doubles;
   if (!src) return -1;
   const size_t n = (size_t)count < have ? (size_t)count : have;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+  if (hipStreamSynchronize(s.stream) != hipSuccess) return -1;
   if (hipMemcpy(host, src, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return (long)n;
 }

@@ -837,6 +837,34 @@ def test_dropin_solve_flags(ndlqr, oracle):
         L.ndlqr_FreeNdLqrSolver(solver)
 
 
+def test_dropin_schedule_survives_factor_sync(ndlqr):
+    """The captured graph of ndlqr_Solve restores what ITS launch sequence leaves behind: the re-factorisation of
+    ndlqr_SyncFactorsToHost (KEEP_FACT, a graph of its own) does not leak into the schedule of the next drop-in solve."""
+    L = ndlqr.lib()
+    path = os.path.join(GOLDEN, "lqr_prob_256.json").encode()
+    pyprob, soln = load_json_problem(path.decode())
+    prob = L.ndlqr_ReadLQRProblemJSONFile(path)
+    solver = L.ndlqr_NewNdLqrSolver(pyprob.n, pyprob.m, pyprob.N)
+
+    def solve():  # (the solution overwrites the right-hand side in solver->soln: set it again every time)
+        assert L.ndlqr_InitializeWithLQRProblem(prob, solver) == 0
+        assert L.ndlqr_Solve(solver) == 0
+        x = np.zeros(soln.size)
+        L.ndlqr_CopySolution(solver, x.ctypes.data_as(C.POINTER(C.c_double)))
+        return x
+
+    solve()  # (profiled: eager launches)
+    x = solve()  # captures the staged graph
+    ctx = L.ndlqr_BatchDeviceContext(solver.contents.device_ctx)
+    schedule = L.ndlqr_hip_schedule(ctx)
+    assert L.ndlqr_SyncFactorsToHost(solver) == 0
+    x2 = solve()  # replays it
+    assert L.ndlqr_hip_schedule(ctx) == schedule
+    assert np.array_equal(x2, x)
+    L.ndlqr_FreeLQRProblem(prob)
+    L.ndlqr_FreeNdLqrSolver(solver)
+
+
 def test_dropin_solve_leaves_the_factorisation(ndlqr, oracle, monkeypatch):
     """ndlqr_SetFactorMirroring / NDLQR_SOLVE_MIRRORS_FACT=1: ndlqr_Solve ends like the reference's (src/solve.c:120-131),
     with the complete factorisation in solver->fact -- no ndlqr_SyncFactorsToHost; bit-identical in strict mode."""
