@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: LQR solves/sec at (nx=12, nu=4, N=256, batch=1024 per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python bench.py --nx 64 --nu 16 --horizon 512 --batch 256        # BASELINE config 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -11,7 +11,13 @@ resident in HBM. The batch axis is the sharding unit: every rank owns `--batch` 
 scaling), there is no data-path collective; torch.distributed (RCCL) carries the barriers, the
 max-over-ranks of the elapsed time and -- outside `value` -- the optional gather of the solutions.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with:
+Prints ONE JSON line on rank 0. A plain run does only what the headline figure needs: it sets up, spins up and
+warms up, times the K steps, writes --dump-outputs and prints `metric`, `value` (solves/s of the whole job),
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` and the description of the run (steps, per-rank times,
+workload, schedule), with
+  spin_up      -- untimed full solves before the W warm-up steps (one-time work of the first solves, clock ramp).
+  dump_outputs -- with --dump-outputs DIR: where rank 0's solutions of the last timed step were written (DIR/*.npy).
+With --full the benchmark goes on to measure and check everything else, and the line also carries:
   roofline     -- dominant kernel of the step: algorithmic bytes and useful flops of the IMPLEMENTED
                   schedule (rslqr_amd/roofline.py) / its HIP-event launch time
                   measured in this run, against 8 TB/s and 78.6 TFLOP/s fp64; the larger fraction
@@ -23,13 +29,14 @@ Prints ONE JSON line on rank 0 (contract in the task description) with:
   pipeline     -- depth of the solve pipeline behind `value` and the same steps strictly stream-ordered.
   transfers    -- H2D of the packed inputs and D2H of the solutions, timed separately (never in `value`).
   end_to_end   -- the MPC step of a drop-in caller: right-hand side up, factor + solve, solutions down, two in flight.
-  spin_up      -- untimed full solves before the W warm-up steps (one-time work of the first solves, clock ramp).
   modes        -- N=1: strict mode, KEEP_FACT and the rhs-only re-solve on the same workload.
   configs      -- N=1: the other single-GPU configurations of BASELINE.json, each timed the same way on a bounded
                   number of steps: lqr_prob_256.json x 1 (latency, error against the fixture's `soln`),
                   (12,4,1024) x 512 (one GPU's shard of config 4), (64,16,512) x 256 (config 5).
   gather       -- N>1: throughput including the all_gather of every shard's solutions.
-  dump_outputs -- with --dump-outputs DIR: where rank 0's solutions of the last timed step were written (DIR/*.npy).
+  device_ms_per_step, config.cholesky_failures, config.kkt_residual_rel_max -- per-solve device times and the checks
+                  of every problem of the shard.
+--no-cpu, --no-modes, --no-transfers, --no-configs, --no-gather and --config4-batch 0 leave legs out of a --full run.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own N ranks: this
 process -- before it imports torch or touches a GPU in any way -- runs `python -m torch.distributed.run
@@ -795,6 +802,30 @@ def time_mode(rslqr_amd, n, m, N, batch, device, seed0, flags, steps, rhs_only=F
         bs.close()
 
 
+def headline_line(args, world, ranks_seen, backend, schedule, elapsed_max, elapsed_per_rank, spin_steps, spin_ms):
+    """The result line of every run: the headline figure (the slowest rank's elapsed time over the K timed steps)
+    and the description of the run. --full adds its legs to it."""
+    n, m, N, batch, steps = args.nx, args.nu, args.horizon, args.batch, args.steps
+    value = batch * world * steps / elapsed_max
+    return {
+        "metric": "LQR solves/sec (nx=%d,nu=%d,N=%d,batch=%d per GPU)" % (n, m, N, batch),
+        "value": value, "unit": "solves/s", "n_gpus": world, "steps": steps,
+        "warmup": args.warmup, "ms_per_step": elapsed_max / steps * 1e3,
+        "ms_per_solve": 1e3 / value,
+        "elapsed_s_per_rank": elapsed_per_rank, "elapsed_minmax_s": [min(elapsed_per_rank), max(elapsed_per_rank)],
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic (seeded splitmix64 family of SURVEY.md 8d, time-varying A,B,Q,R)",
+        "config": {"workload": "nx=%d nu=%d N=%d batch=%d per GPU, fp64, factor+solve per step" % (n, m, N, batch),
+                   "parallelism": "batch-sharded x%d, no data-path collective" % world,
+                   "ranks_seen": ranks_seen, "backend": backend,
+                   "flags": args.flags, "schedule": schedule, "csrc_sha": csrc_sha()},
+        "spin_up": {"steps": spin_steps, "ms": spin_ms,
+                    "note": "untimed full solves before the W warm-up steps: one-time work of the first solves and "
+                            "the clock ramp of the device; --spin-up-ms 0 disables"},
+        "full": bool(args.full),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -808,15 +839,20 @@ def main():
     ap.add_argument("--horizon", type=int, default=256)
     ap.add_argument("--batch", type=int, default=1024, help="problems per GPU")
     ap.add_argument("--flags", type=int, default=0, help="NDLQR_FLAG_* bits (1 strict, 2 generic, 8 keep fact)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-modes", action="store_true", help="skip the strict / KEEP / rhs-only legs")
-    ap.add_argument("--no-gather", action="store_true", help="N>1: skip the solution-gather leg")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="problems in the CPU sample (0 = auto)")
-    ap.add_argument("--no-transfers", action="store_true", help="skip the transfer / end-to-end legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, measure and check everything else: roofline and per-kernel times, "
+                         "stream-ordered steps, per-solve device times, KKT residuals, transfers and the end-to-end MPC "
+                         "step, other modes and configurations, the CPU baseline, the N>1 gather")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the strict / KEEP / rhs-only legs")
+    ap.add_argument("--no-gather", action="store_true", help="--full, N>1: skip the solution-gather leg")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: problems in the CPU sample (0 = auto)")
+    ap.add_argument("--no-transfers", action="store_true", help="--full: skip the transfer / end-to-end legs")
     ap.add_argument("--transfer-leg", action="store_true", help=argparse.SUPPRESS)  # internal: child process of the N=1 run
-    ap.add_argument("--no-configs", action="store_true", help="N=1: skip the legs of the other BASELINE configurations")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="--full: skip the legs of the other BASELINE configurations")
     ap.add_argument("--config4-batch", type=int, default=512,
-                    help="N>1: problems per GPU of the (12,4,1024) leg (512 x 8 GPUs = BASELINE config 4; 0: skip)")
+                    help="--full, N>1: problems per GPU of the (12,4,1024) leg (512 x 8 GPUs = BASELINE config 4; 0: skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write rank 0's solutions of the last timed step to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
@@ -915,8 +951,25 @@ def main():
     if args.dump_outputs and rank == 0:
         # what the last timed step handed back, copied down before any later solve replaces it
         dumped = dump_outputs(args.dump_outputs, bs.solutions(), n, m, N, seed0)
-    fails = bs.cholesky_failures()
     schedule = bs.schedule()
+    tdev = "cuda" if backend == "nccl" else "cpu"
+    if not args.full:
+        # a plain run ends here: the headline figure is all it computes (everything else: --full)
+        elapsed_per_rank = sharding.all_over_ranks(elapsed, device=tdev) if distributed else [elapsed]
+        elapsed_max = sharding.max_over_ranks([elapsed], device=tdev)[0]
+        if rank == 0:
+            result = headline_line(args, world, ranks_seen, backend if distributed else None, schedule, elapsed_max,
+                                   elapsed_per_rank, spin_steps, spin_ms)
+            if dumped is not None:
+                result["dump_outputs"] = dumped
+            print(json.dumps(result), flush=True)
+        bs.close()
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    fails = bs.cholesky_failures()
     # The same K steps strictly stream-ordered (pipeline depth 1: a step starts when the previous one has
     # finished), next to the default two-deep pipeline of `value` (include/ndlqr_hip.h)
     depth = bs.pipeline_depth()
@@ -990,7 +1043,6 @@ def main():
         gather = {"steps": gsteps, "elapsed_s": g_elapsed, "own_shard_intact": gather_ok,
                   "bytes_per_rank_per_step": 8 * batch * bs.nvars}
 
-    tdev = "cuda" if backend == "nccl" else "cpu"
     elapsed_per_rank = sharding.all_over_ranks(elapsed, device=tdev) if distributed else [elapsed]
     red = [elapsed, float(fails), kkt_worst]
     if elapsed_ordered is not None:
@@ -1011,26 +1063,14 @@ def main():
 
     if rank == 0:
         total_solves = batch * world * steps
-        value = total_solves / elapsed_max
-        step_ms = elapsed_max / steps * 1e3
-        roofline = roofline_object(prof, steps, schedule, n, m, N, batch, args.flags, value / world)
-        result = {
-            "metric": "LQR solves/sec (nx=%d,nu=%d,N=%d,batch=%d per GPU)" % (n, m, N, batch),
-            "value": value, "unit": "solves/s", "n_gpus": world, "steps": steps,
-            "warmup": args.warmup, "ms_per_step": step_ms,
-            "ms_per_solve": 1e3 / value,
+        result = headline_line(args, world, ranks_seen, backend if distributed else None, schedule, elapsed_max,
+                               elapsed_per_rank, spin_steps, spin_ms)
+        value, step_ms = result["value"], result["ms_per_step"]
+        result["config"].update(cholesky_failures=fails_max, kkt_residual_rel_max=kkt_max)
+        result.update({
             "device_ms_per_step": {"median": dev_median, "min": dev_min, "reps": len(per_solve),
                                    "note": "rank 0, HIP events per solve, one solve in flight"},
-            "elapsed_s_per_rank": elapsed_per_rank, "elapsed_minmax_s": [min(elapsed_per_rank), max(elapsed_per_rank)],
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic (seeded splitmix64 family of SURVEY.md 8d, time-varying A,B,Q,R)",
-            "config": {"workload": "nx=%d nu=%d N=%d batch=%d per GPU, fp64, factor+solve per step"
-                                   % (n, m, N, batch),
-                       "parallelism": "batch-sharded x%d, no data-path collective" % world,
-                       "ranks_seen": ranks_seen, "backend": backend if distributed else None,
-                       "flags": args.flags, "schedule": schedule, "cholesky_failures": fails_max,
-                       "kkt_residual_rel_max": kkt_max, "csrc_sha": csrc_sha()},
-            "roofline": roofline,
+            "roofline": roofline_object(prof, steps, schedule, n, m, N, batch, args.flags, value / world),
             "kernel_ms_note": "second pass of the same %d steps with per-launch HIP events (eager "
                               "launches): %.3f ms/step vs %.3f ms/step in the timed, graph-replayed region"
                               % (steps, elapsed_profiled / steps * 1e3, step_ms),
@@ -1040,12 +1080,9 @@ def main():
                                  "starts when the previous one has finished",
                          "value_depth1": (total_solves / elapsed_ordered) if elapsed_ordered else None,
                          "ms_per_step_depth1": (elapsed_ordered / steps * 1e3) if elapsed_ordered else None},
-            "spin_up": {"steps": spin_steps, "ms": spin_ms,
-                        "note": "untimed full solves before the W warm-up steps: one-time work of the first solves and "
-                                "the clock ramp of the device; --spin-up-ms 0 disables"},
             "transfers": transfers,
             "end_to_end": end_to_end,
-        }
+        })
         if dumped is not None:
             result["dump_outputs"] = dumped
         if gather:

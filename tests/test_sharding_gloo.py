@@ -127,7 +127,7 @@ def test_bench_two_ranks_on_one_gpu():
     """bench.py's own N = 2 path end to end on the one GPU of the test box: two rank processes (launched by
     bench.py itself), both on device 0, gloo instead of RCCL (one GPU cannot host two RCCL ranks); the real
     BatchSolver, the shared timed regions, the gather leg."""
-    proc, lines = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--no-modes",
+    proc, lines = _run_bench(["--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--batch", "64", "--no-modes",
                               "--spin-up-ms", "5", "--cpu-sample", "4", "--config4-batch", "8"],
                              {"NDLQR_BENCH_SAME_DEVICE": "1", "NDLQR_BENCH_BACKEND": "gloo",
                               "NDLQR_BENCH_FORCE_CONFIG4": "1"}, 900)
@@ -167,7 +167,7 @@ def test_bench_rccl_path_one_rank():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
-           "--warmup", "1", "--batch", "64", "--no-cpu", "--no-modes", "--no-configs", "--no-transfers", "--spin-up-ms", "5"]
+           "--warmup", "1", "--batch", "64", "--full", "--no-cpu", "--no-modes", "--no-configs", "--no-transfers", "--spin-up-ms", "5"]
     proc = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [json.loads(l) for l in proc.stdout.splitlines() if l.startswith("{")]
@@ -177,3 +177,25 @@ def test_bench_rccl_path_one_rank():
     assert res["gather"]["every_rank_found_its_shard_intact"] is True
     assert "RCCL" in res["gather"]["collective"]
     assert res["config"]["kkt_residual_rel_max"] <= 1e-9
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain `bench.py --gpus 1` run stops after the timed steps and --dump-outputs: its line holds the headline
+    figure and the description of the run, and none of the legs that --full adds."""
+    proc, lines = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64", "--spin-up-ms", "5",
+                              "--dump-outputs", str(tmp_path)], {}, 600)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    assert len(lines) == 1, lines
+    res = lines[0]
+    assert res["value"] > 0 and res["unit"] == "solves/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+    assert res["metric"] == "LQR solves/sec (nx=12,nu=4,N=256,batch=64 per GPU)"
+    assert abs(res["ms_per_step"] - 64 / res["value"] * 1e3) <= 1e-9 * res["ms_per_step"]
+    assert res["full"] is False and res["steps"] == 3 and res["warmup"] == 1 and res["n_gpus"] == 1
+    for leg in ("roofline", "device_ms_per_step", "pipeline", "transfers", "end_to_end", "modes", "configs",
+                "cpu_baseline", "gather"):
+        assert leg not in res, leg
+    assert "kkt_residual_rel_max" not in res["config"] and "cholesky_failures" not in res["config"]
+    sol = np.load(tmp_path / "solutions.npy")
+    assert res["dump_outputs"]["solutions"] == list(sol.shape) and sol.shape[0] == 64
+    assert np.isfinite(sol).all()

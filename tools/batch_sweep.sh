@@ -3,7 +3,7 @@
 # run faster per problem? NDLQR_PIPELINE=1: one solve in flight, so a solve's own footprint is all that is live)
 export NDLQR_PIPELINE=1
 for b in 64 128 192 256 512 1024 2048; do
-python bench.py --no-cpu --no-modes --no-configs --no-transfers --steps 40 --batch $b 2>/dev/null | python -c "
+python bench.py --full --no-cpu --no-modes --no-configs --no-transfers --steps 40 --batch $b 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; ks=dict(r['kernels']); ks[r['kernel']]=r
 b=$b

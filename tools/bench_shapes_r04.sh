@@ -1,5 +1,5 @@
 # bench.py --no-cpu over the size-specialised and padded shapes x 1024 and a few runtime-sized ones (developer tool, GPU box)
-run() { python bench.py --no-cpu --no-modes --no-configs --no-transfers "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu --no-modes --no-configs --no-transfers "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; ks=dict(r['kernels']); ks[r['kernel']]=r
 print(d['config']['workload'], '|', d['config']['schedule'], '| %.0f solves/s, %.4f ms/step |' % (d['value'], d['ms_per_step']), {k: round(v['ms_per_step'],4) for k,v in ks.items()}, flush=True)"; }

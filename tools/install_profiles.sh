@@ -1,12 +1,13 @@
 #!/bin/bash
 # Developer tool: install the summaries of a profile round (tools/profile_round.sh + tools/sq_counters.sh, headline and config 5)
-# from gpurun_out/ into profiles/ under TAG, drop the set OLDTAG and rename its mentions in the documents.
+# from $TOOLS_OUT (default tools_out/) into profiles/ under TAG, drop the set OLDTAG and rename its mentions in the documents.
 #   bash tools/install_profiles.sh r04k r04j
 set -e
 tag=$1; old=$2
+out=${TOOLS_OUT:-tools_out}
 for s in "" _config5; do
-  for f in bench.json bench_under_rocprof.json kernel_stats.csv pmc.txt traffic.json issue.json; do cp gpurun_out/${tag}${s}_$f profiles/${tag}${s}_$f; done
-  cp gpurun_out/${tag}${s}_sq_summary.txt profiles/${tag}${s}_sq_counters.txt
+  for f in bench.json bench_under_rocprof.json kernel_stats.csv pmc.txt traffic.json issue.json; do cp $out/${tag}${s}_$f profiles/${tag}${s}_$f; done
+  cp $out/${tag}${s}_sq_summary.txt profiles/${tag}${s}_sq_counters.txt
 done
 if [ -n "$old" ]; then
   git rm -q profiles/${old}_* || true

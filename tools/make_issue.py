@@ -29,7 +29,8 @@ def main():
     tag = sys.argv[1]
     n, m, N, batch, flags = [int(v) for v in sys.argv[2:7]]
     acc = collections.defaultdict(lambda: collections.defaultdict(lambda: [0, 0.0]))  # kernel -> counter -> [launches, sum]
-    for f in sorted(glob.glob("gpurun_out/%s_sq_*/**/*counter_collection.csv" % tag, recursive=True)):
+    out = os.environ.get("TOOLS_OUT", "tools_out")  # where tools/sq_counters.sh put its passes
+    for f in sorted(glob.glob(os.path.join(out, "%s_sq_*/**/*counter_collection.csv" % tag), recursive=True)):
         for row in csv.DictReader(open(f)):
             c = acc[row["Kernel_Name"].split("(")[0]][row["Counter_Name"]]
             c[0] += 1

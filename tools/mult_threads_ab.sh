@@ -1,6 +1,6 @@
 #!/bin/bash
 # Developer tool (GPU box): workgroup size of backsub_multipliers_compact (NDLQR_MULT_THREADS=64 / 128 / 256) per block size
-run() { python bench.py --no-cpu --no-modes --no-configs --no-transfers "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu --no-modes --no-configs --no-transfers "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; ks=dict(r['kernels']); ks[r['kernel']]=r
 print('threads=$NDLQR_MULT_THREADS', d['config']['workload'][:34], '| %.0f solves/s, %.4f ms/step |' % (d['value'], d['ms_per_step']), {k: round(v['ms_per_step'],4) for k,v in ks.items()}, flush=True)"; }

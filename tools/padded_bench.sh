@@ -1,6 +1,6 @@
 # Developer tool (GPU box): block sizes without a size-specialised instance, zero-padded into the next instance
 # (default) against the runtime-sized kernels on their own block size (NDLQR_NO_PAD=1)
-run() { python bench.py --no-cpu --no-modes --no-configs --no-transfers --steps 20 "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu --no-modes --no-configs --no-transfers --steps 20 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; ks=dict(r['kernels']); ks[r['kernel']]=r
 print(d['config']['workload'], '|', d['config']['schedule'], '| %.0f solves/s, %.4f ms/step | kkt %.1e |' % (d['value'], d['ms_per_step'], d['config']['kkt_residual_rel_max']), {k: round(v['ms_per_step'],4) for k,v in ks.items()})"; }

@@ -1,6 +1,6 @@
 # developer tool (GPU box): block sizes without a size-specialised instance -- the separator-only schedule on the
 # matrix cores (zero-padded tiles where the block does not fill them) against the knot-based runtime-sized kernels
-run() { python bench.py --no-cpu --no-modes "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu --no-modes "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; ks=dict(r['kernels']); ks[r['kernel']]=r
 print('   %-16s %9.0f solves/s  %8.4f ms/step ' % (d['config']['schedule'], d['value'], d['ms_per_step']), {k: round(v['ms_per_step'],3) for k,v in ks.items()})"; }

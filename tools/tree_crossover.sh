@@ -1,6 +1,6 @@
 # developer tool (GPU box): tree schedule (one launch for the whole factorisation) against one launch per level,
 # by batch size -- where plan_small's threshold belongs
-run() { python bench.py --no-cpu --no-modes "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu --no-modes "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('   %-14s %8.0f solves/s  %.4f ms/step  depth1 %.4f ms' % (d['config']['schedule'], d['value'], d['ms_per_step'], d['pipeline']['ms_per_step_depth1']))"; }

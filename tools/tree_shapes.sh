@@ -1,4 +1,4 @@
-run() { python bench.py --no-cpu --no-modes "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu --no-modes "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print(d['config']['workload'], '|', d['config']['schedule'], '| %.0f solves/s, %.4f ms/step | depth1 %.4f ms' % (d['value'], d['ms_per_step'], d['pipeline']['ms_per_step_depth1']), 'device median %.4f' % d['device_ms_per_step']['median'])"; }
