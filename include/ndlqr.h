@@ -473,6 +473,34 @@ int ndlqr_BatchCholeskyFailures(NdLqrBatchSolver* bs);
  * data, evaluated on the device (batch doubles each; bnorm may be NULL). */
 int ndlqr_BatchKktResiduals(NdLqrBatchSolver* bs, double* res, double* bnorm);
 double ndlqr_BatchSolveTimeMs(const NdLqrBatchSolver* bs); /* HIP-event time of last solve */
+/* additive: adjoint solve and parameter gradients (differentiable MPC, system identification). For a loss L(z) of the
+ * resident solutions z and g = dL/dz ([batch][nvars], the packing of ndlqr_CopyBatchSolutions; host, pinned or the
+ * solver's device memory), ndlqr_SolveBatchAdjoint solves K w = g against the kept factorisation (K is symmetric) and
+ * ndlqr_BatchGradients assembles dL/d(A, B, Q, R, q, r, d, x0) from z and w on the device, in the flat layout of
+ * ndlqr_InitializeBatchFlat (A, B column-major; Q, R diagonals; zero for A, B, R, r, d of the last knot).
+ *   Reach: wherever ndlqr_SolveBatchRhsOnly works -- a solve with NDLQR_FLAG_KEEP_RECORDS (fast mode) or
+ *   NDLQR_FLAG_KEEP_FACT (any mode; with NDLQR_FLAG_STRICT_FP the gradients are bit-reproducible from z and w).
+ *   The primal state stays as it is: solutions, right-hand side, kept records and factors; a later
+ *   ndlqr_CopyBatchSolutions, ndlqr_BatchKktResiduals, ndlqr_SolveBatchRhsOnly or step behaves as if the adjoint had
+ *   never run. Any later solve, step or re-solve invalidates the adjoint, as does the upload of new inputs;
+ *   ndlqr_BatchGradients / ndlqr_CopyBatchAdjoint then return NDLQR_ERR_INVALID. So do all three after a step that
+ *   computed a slice alone (NDLQR_SOLN_ONLY), on a time-axis shard, and for device memory of another device.
+ *   Outputs of ndlqr_BatchGradients: NULL = not computed; host or pinned memory (staged through HBM, one copy each) or the
+ *   solver's device memory (written by the kernel). Bit o of sum_mask (NDLQR_GRAD_*): output o summed over the batch,
+ *   deterministically -- [N][...] ([n] for x0) instead of [batch][N][...]. All three calls block until their results are
+ *   complete; ndlqr_BatchSolveTimeMs then reports the device time of the adjoint solve / the gradient kernels. */
+#define NDLQR_GRAD_A 1u
+#define NDLQR_GRAD_B 2u
+#define NDLQR_GRAD_Q 4u
+#define NDLQR_GRAD_R 8u
+#define NDLQR_GRAD_q 16u
+#define NDLQR_GRAD_r 32u
+#define NDLQR_GRAD_d 64u
+#define NDLQR_GRAD_x0 128u
+int ndlqr_SolveBatchAdjoint(NdLqrBatchSolver* bs, const double* g);  /* K w = g against the kept factorisation */
+int ndlqr_CopyBatchAdjoint(NdLqrBatchSolver* bs, double* w);         /* [batch][nvars]; returns nvars */
+int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR,
+                         double* gq, double* gr, double* gd, double* gx0);
 void* ndlqr_BatchDeviceContext(NdLqrBatchSolver* bs);      /* NdlqrHipCtx* (ndlqr_hip.h) */
 
 /* Seeded synthetic problem generator (host, bit-reproducible). */

@@ -96,6 +96,13 @@ int ndlqr_hip_pipeline_depth(const NdlqrHipCtx* ctx);
 int ndlqr_hip_upload_rhs(NdlqrHipCtx* ctx, int p0, int count, const double* rhs);
 int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* ctx);
 double ndlqr_hip_last_solve_ms(NdlqrHipCtx* ctx); /* valid after synchronize */
+/* Adjoint solve and parameter gradients (ndlqr.h: ndlqr_SolveBatchAdjoint, ndlqr_BatchGradients). The adjoint K w = g is
+ * the re-solve of ndlqr_hip_solve_rhs_async (kept records, else the factor array) with g packed into an adjoint
+ * right-hand side, into an adjoint solution array of its own: [batch][N][2n+m] each, allocated on first use. Blocking. */
+int ndlqr_hip_solve_adjoint(NdlqrHipCtx* ctx, const double* g);
+int ndlqr_hip_download_adjoint(NdlqrHipCtx* ctx, double* w); /* [batch][nvars]: host, pinned or this device's memory */
+int ndlqr_hip_gradients(NdlqrHipCtx* ctx, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR, double* gq,
+                        double* gr, double* gd, double* gx0);
 /* Several right-hand sides per problem against one kept factorisation each (the reference's NdData holds a single
  * right-hand side, src/nddata.h:70-75): nrhs sets of right-hand sides for the whole batch, flat HOST arrays in the layout of
  * ndlqr_BatchSetRhsFlat with a leading [nrhs] -- q, d [nrhs][batch][N][n], r [nrhs][batch][N][m], x0 [nrhs][batch][n] --,

@@ -19,6 +19,9 @@ FLAG_PROFILE = 4
 FLAG_KEEP_FACT = 8
 FLAG_KEEP_RECORDS = 16
 SOLN_LAMBDA, SOLN_STATE, SOLN_INPUT, SOLN_ONLY = 1, 2, 4, 8
+# ndlqr_BatchGradients: bit o of sum_mask sums output o over the batch; GRAD_NAMES in the order of the bits / arguments
+GRAD_A, GRAD_B, GRAD_Q, GRAD_R, GRAD_q, GRAD_r, GRAD_d, GRAD_x0 = 1, 2, 4, 8, 16, 32, 64, 128
+GRAD_NAMES = ("A", "B", "Q", "R", "q", "r", "d", "x0")
 
 ERR_INVALID = -1
 ERR_NO_DEVICE = -2
@@ -251,6 +254,9 @@ def lib():
     proto("ndlqr_BatchCholeskyFailures", ci, vp)
     proto("ndlqr_BatchKktResiduals", ci, vp, dp, dp)
     proto("ndlqr_BatchSolveTimeMs", cd, vp)
+    proto("ndlqr_SolveBatchAdjoint", ci, vp, dp)
+    proto("ndlqr_CopyBatchAdjoint", ci, vp, dp)
+    proto("ndlqr_BatchGradients", ci, vp, C.c_uint, dp, dp, dp, dp, dp, dp, dp, dp)
     proto("ndlqr_BatchDeviceContext", vp, vp)
     # shim bits used by the benchmark
     proto("ndlqr_hip_set_stream", ci, vp, vp)
@@ -322,6 +328,18 @@ def device_count():
 
 def _ptr(a):
     return a.ctypes.data_as(dp)
+
+
+def _any_ptr(a, size):
+    """double* of a numpy array (float64, C-contiguous) or of device memory -- anything with `ptr` and `size` attributes,
+    such as a DeviceArray -- holding `size` doubles."""
+    if hasattr(a, "ptr"):
+        if a.size != size:
+            raise ValueError("expected %d doubles, got %d" % (size, a.size))
+        return C.cast(C.c_void_p(int(a.ptr)), dp)
+    if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags["C_CONTIGUOUS"] and a.size == size):
+        raise ValueError("expected a C-contiguous float64 array of %d doubles" % size)
+    return _ptr(a)
 
 
 def generate_synthetic(n, m, N, seed):
@@ -535,6 +553,50 @@ class BatchSolver:
         got = self.L.ndlqr_CopyBatchSolutions(self.h, _ptr(out))
         if got != self.nvars:
             raise RuntimeError("ndlqr_CopyBatchSolutions failed: %d" % got)
+        return out
+
+    # ---- adjoint solve and parameter gradients (include/ndlqr.h: ndlqr_SolveBatchAdjoint, ndlqr_BatchGradients)
+    def solve_adjoint(self, g):
+        """ndlqr_SolveBatchAdjoint: K w = g for g = dL/dz [batch, nvars] (numpy array or DeviceArray) against the
+        factorisation the last solve kept (FLAG_KEEP_RECORDS or FLAG_KEEP_FACT). Returns the C return code (0, or -1 when
+        there is no kept factorisation of the resident solution)."""
+        if not hasattr(g, "ptr"):
+            g = np.ascontiguousarray(g, dtype=np.float64)
+        return self.L.ndlqr_SolveBatchAdjoint(self.h, _any_ptr(g, self.batch * self.nvars))
+
+    def adjoint(self, out=None):
+        """ndlqr_CopyBatchAdjoint: the adjoint solution w [batch, nvars] into `out` (numpy array or DeviceArray)."""
+        if out is None:
+            out = np.zeros((self.batch, self.nvars))
+        got = self.L.ndlqr_CopyBatchAdjoint(self.h, _any_ptr(out, self.batch * self.nvars))
+        if got != self.nvars:
+            raise RuntimeError("ndlqr_CopyBatchAdjoint failed: %d (%s)" % (got, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def gradient_shape(self, name, summed=False):
+        """Shape of gradient `name` (GRAD_NAMES) in the flat layout, per problem or summed over the batch."""
+        n, m, N = self.n, self.m, self.N
+        per = dict(A=(N, n * n), B=(N, n * m), Q=(N, n), R=(N, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,))[name]
+        return per if summed else (self.batch,) + per
+
+    def gradients(self, sum_mask=0, out=None):
+        """ndlqr_BatchGradients: dict name -> dL/d(name) for the names of GRAD_NAMES, in the flat layout of
+        initialize_flat (A, B column-major per knot); those whose bit is in sum_mask (GRAD_*) summed over the batch.
+        `out`: dict of destinations (numpy arrays or DeviceArrays); only those names are computed. Default: numpy arrays
+        for all eight."""
+        if out is None:
+            out = {k: np.zeros(self.gradient_shape(k, bool(sum_mask & (1 << i)))) for i, k in enumerate(GRAD_NAMES)}
+        unknown = set(out) - set(GRAD_NAMES)
+        if unknown:
+            raise ValueError("unknown gradient names: %s" % sorted(unknown))
+        ptrs = []
+        for i, k in enumerate(GRAD_NAMES):
+            a = out.get(k)
+            ptrs.append(None if a is None else
+                        _any_ptr(a, int(np.prod(self.gradient_shape(k, bool(sum_mask & (1 << i)))))))
+        err = self.L.ndlqr_BatchGradients(self.h, sum_mask, *ptrs)
+        if err:
+            raise RuntimeError("ndlqr_BatchGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
 
     def solutions_to_device(self, device_ptr):

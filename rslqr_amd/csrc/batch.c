@@ -345,6 +345,20 @@ int ndlqr_CopyBatchSolutionsDevice(NdLqrBatchSolver* bs, double* dsoln) {
   int err = ndlqr_hip_pack_solutions_device(bs->ctx, dsoln);
   return err ? err : bs->nvars;
 }
+int ndlqr_SolveBatchAdjoint(NdLqrBatchSolver* bs, const double* g) {
+  if (!bs || !g) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_solve_adjoint(bs->ctx, g);
+}
+int ndlqr_CopyBatchAdjoint(NdLqrBatchSolver* bs, double* w) {
+  if (!bs || !w) return NDLQR_ERR_INVALID;
+  int err = ndlqr_hip_download_adjoint(bs->ctx, w);
+  return err ? err : bs->nvars;
+}
+int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR,
+                         double* gq, double* gr, double* gd, double* gx0) {
+  if (!bs) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_gradients(bs->ctx, sum_mask, gA, gB, gQ, gR, gq, gr, gd, gx0);
+}
 int ndlqr_CopyBatchFactors(NdLqrBatchSolver* bs, int p, double* fact) {
   if (!bs || !fact || p < 0 || p >= bs->batch) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_factors(bs->ctx, p, fact);

@@ -139,6 +139,16 @@ struct NdlqrHipCtx {
   double last_ms = 0;
   int last_failures = 0;
   bool fact_valid = false;  // the device holds a complete factorisation (last solve ran with KEEP_FACT)
+  // Adjoint solve and parameter gradients (ndlqr_hip_solve_adjoint / ndlqr_hip_gradients): the adjoint right-hand side
+  // and its solution w in buffers of their own, [batch][N][2n+m] (allocated on first use), so that the primal state stays
+  // as it is. soln_gen counts the resident solutions (note_solution); adj_gen is the one the adjoint belongs to (0: none).
+  double* adj_rhs = nullptr;
+  double* adj_z = nullptr;
+  double* adj_save = nullptr;    // right-hand-side columns of the kept records / slots, saved around the adjoint re-solve
+  double* grad_stage = nullptr;  // HBM staging of the host outputs / inputs and the partial batch sums (grown on demand)
+  size_t grad_stage_cap = 0;     // doubles
+  unsigned long long soln_gen = 0, adj_gen = 0;
+  bool inputs_replaced = false;  // new A, B, Q, R since the last solve
   // profile
   std::vector<PendingEvent> pending;
   std::vector<hipEvent_t> event_pool;

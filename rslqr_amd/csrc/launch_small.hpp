@@ -199,9 +199,9 @@ static int launch_small(NdlqrHipCtx* c) {
 }
 
 // Record-based re-solve (fast mode, specialised sizes): forward pass over the separators, then
-// the same back-substitution as the full solve. Returns false when the shape has no instance.
+// the same back-substitution as the full solve: right-hand side `rhs`, solution into `z`.
 template <int NX, int NU>
-static void launch_rhs_records(NdlqrHipCtx* c) {
+static void launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value && 8 * (2 * NX + NU) <= 256) {
@@ -212,7 +212,7 @@ static void launch_rhs_records(NdlqrHipCtx* c) {
       {
         ScopedSlot t(c, SLOT_SEP);
         hipLaunchKernelGGL((ndlqr::rb_forward<NX, NU>), dim3(d.N / 8, d.batch), dim3(256), 0, s.stream, d, c->AB, c->QR,
-                           s.rhs, s.rec, s.red);
+                           rhs, s.rec, s.red);
       }
       {
         ScopedSlot t(c, SLOT_UPPER);
@@ -221,29 +221,29 @@ static void launch_rhs_records(NdlqrHipCtx* c) {
           (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ndlqr::rb_forward_top<NX, NU>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU>), dim3(d.batch), dim3(256), lds, s.stream, d, c->AB, c->QR,
-                           s.rhs, s.rec, (const double*)s.red, s.ytop);
+                           rhs, s.rec, (const double*)s.red, s.ytop);
       }
       ScopedSlot t(c, SLOT_APPLY);
       hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream,
-                         apply_dims(c, d), c->AB, c->QR, s.rhs, s.rec, s.ytop, s.z);
+                         apply_dims(c, d), c->AB, c->QR, rhs, s.rec, s.ytop, z);
       return;
     }
   }
   {
     ScopedSlot t(c, SLOT_SEP);
     hipLaunchKernelGGL((ndlqr::rhs_forward_small<NX, NU>), dim3(d.N / 8, d.batch), dim3(64), 0, s.stream, d, c->AB,
-                       c->QR, s.rhs, c->F, s.rec, s.z);
+                       c->QR, rhs, c->F, s.rec, z);
   }
   if (d.K > 3) {
     ScopedSlot t(c, SLOT_UPPER);
     const size_t lds = sizeof(double) * (size_t)(d.N / 8) * NX;
     hipLaunchKernelGGL((ndlqr::rhs_forward_upper<NX, NU>), dim3(d.batch), dim3(512), lds, s.stream, d, c->AB, c->QR,
-                       s.rhs, c->F, s.rec, s.z);
+                       rhs, c->F, s.rec, z);
   }
   {
     ScopedSlot t(c, SLOT_APPLY);
     hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream, apply_dims(c, d), c->AB,
-                       c->QR, s.rhs, s.rec, s.z);
+                       c->QR, rhs, s.rec, z);
   }
 }
 

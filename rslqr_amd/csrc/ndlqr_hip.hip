@@ -11,6 +11,7 @@
 
 #include "hip_context.hpp"
 #include "kernels_generic.hpp"
+#include "kernels_grad.hpp"
 #include "kernels_mfma.hpp"
 #include "kernels_reduced_mfma.hpp"
 #ifdef NDLQR_SINGLE_TU  // developer builds (tools/segtime.py): every instance in this translation unit
@@ -188,6 +189,7 @@ void ndlqr_hip_destroy(NdlqrHipCtx* c) {
   (void)hipFree(c->multi_rhs); (void)hipFree(c->multi_z); (void)hipFree(c->multi_zsep); (void)hipFree(c->multi_fsum);
   (void)hipFree(c->multi_ytop); (void)hipFree(c->multi_in); (void)hipFree(c->multi_out);
   (void)hipFree(c->kkt_out); (void)hipFree(c->pad_stage);
+  (void)hipFree(c->adj_rhs); (void)hipFree(c->adj_z); (void)hipFree(c->adj_save); (void)hipFree(c->grad_stage);
   for (double* h : c->h_stage) if (h) (void)hipHostFree(h);
   if (c->ev_inputs) (void)hipEventDestroy(c->ev_inputs);
   for (hipEvent_t ev : c->ev_step) if (ev) (void)hipEventDestroy(ev);
@@ -199,6 +201,7 @@ void ndlqr_hip_destroy(NdlqrHipCtx* c) {
 // the current buffer set holds the most recent solution -- all of it, or (a step with NDLQR_SOLN_ONLY) the knots of the
 // workgroups its back-substitution ran
 static void note_solution(NdlqrHipCtx* c) {
+  ++c->soln_gen;  // (an adjoint of an earlier solution no longer applies)
   c->latest = c->cur;
   c->z_partial = c->apply_nblk > 0;
   c->z_blk0 = c->apply_blk0;
@@ -406,6 +409,7 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
     next_solve_on_current_set(c);
     c->fact_valid = false;
     c->rec_complete = false;
+    c->inputs_replaced = true;
     return NDLQR_OK;
   }
   const size_t sAB = (size_t)d.N * d.n * d.w, sQR = (size_t)d.N * d.w, sz = (size_t)d.N * d.rows;
@@ -417,6 +421,7 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
   next_solve_on_current_set(c);
   c->fact_valid = false;  // new A, B, Q, R: a cached factorisation no longer matches the inputs
   c->rec_complete = false;
+  c->inputs_replaced = true;
   return NDLQR_OK;
 }
 
@@ -444,6 +449,7 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
   HIP_TRY(other_stream_waits(c));  // the next solve may run on the other buffer set's stream
   c->fact_valid = false;  // new A, B, Q, R: neither a cached factor array nor cached records match
   c->rec_complete = false;
+  c->inputs_replaced = true;
   return NDLQR_OK;
 }
 
@@ -537,7 +543,7 @@ static int ensure_red_generic(NdlqrHipCtx* c) {
 // back-substitution of the runtime-sized separator-only schedule: its records are compact (the Cholesky factor and y~ instead of
 // f_a | f_bb | z_sep, the couplings come from the slots / the problem data), and one launch resolves the level-0
 // multipliers and the states / inputs of every knot
-static void launch_backsub_reduced_generic(NdlqrHipCtx* c) {
+static void launch_backsub_reduced_generic(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   ScopedSlot t(c, SLOT_APPLY);
@@ -559,14 +565,14 @@ static void launch_backsub_reduced_generic(NdlqrHipCtx* c) {
     int cnt = d.N >> (l + 1);
     if (part) { dl.xoff = ka >> (l + 1); cnt = (kb >> (l + 1)) - dl.xoff + 1; }
     hipLaunchKernelGGL(ndlqr::backsub_multipliers_compact, dim3(cnt, d.batch), dim3(thr_m), lds_m, s.stream, dl, l,
-                       s.red, s.rec, s.z);
+                       s.red, s.rec, z);
   }
   const int thr = d.n <= 16 ? 64 : (d.n <= 32 ? 128 : 256);  // (its y_s step wants n <= threads)
   const size_t lds = sizeof(double) * ((size_t)d.n * (d.n + 1) / 2 + 5 * (size_t)d.n + 4 * (size_t)d.w + 2 * (size_t)d.rows + thr);
   ndlqr::Dims d0 = d;
   if (part) d0.xoff = k0 >> 1;
   hipLaunchKernelGGL(ndlqr::backsub_level0_states_generic, dim3(part ? (k1 >> 1) - (k0 >> 1) + 1 : d.N >> 1, d.batch), dim3(thr),
-                     lds, s.stream, d0, c->AB, c->QR, s.rhs, s.rec, s.z);
+                     lds, s.stream, d0, c->AB, c->QR, rhs, s.rec, z);
 }
 
 static int launch_reduced_generic(NdlqrHipCtx* c, const ReducedGenericPlan& p) {
@@ -620,12 +626,13 @@ static int launch_reduced_generic(NdlqrHipCtx* c, const ReducedGenericPlan& p) {
 #undef NDLQR_LAUNCH_SEP2
 #undef NDLQR_LAUNCH_SEP
   }
-  launch_backsub_reduced_generic(c);
+  launch_backsub_reduced_generic(c, s.rhs, s.z);
   return NDLQR_OK;
 }
 
-// rhs-only re-solve on the records, slots and separator factors of a generic-reduced-records sweep
-static void launch_rhs_reduced_generic(NdlqrHipCtx* c) {
+// rhs-only re-solve on the records, slots and separator factors of a generic-reduced-records sweep: right-hand side
+// `rhs`, solution into `z` (the primal ones, or those of the adjoint solve)
+static void launch_rhs_reduced_generic(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   const int np = (d.n + 15) / 16 * 16;
@@ -633,9 +640,9 @@ static void launch_rhs_reduced_generic(NdlqrHipCtx* c) {
   for (int l = 0; l < d.K; ++l) {
     ScopedSlot t(c, SLOT_SEP);
     hipLaunchKernelGGL(ndlqr::rhs_reduced_generic, dim3(d.N >> (l + 1), d.batch), dim3(256), lds, s.stream, d, l, np,
-                       c->AB, c->QR, s.rhs, s.red, s.rec);
+                       c->AB, c->QR, rhs, s.red, s.rec);
   }
-  launch_backsub_reduced_generic(c);
+  launch_backsub_reduced_generic(c, rhs, z);
 }
 
 // The separator kernel of the knot-based runtime-sized schedules and where its S-bar (n x (n+1)) and right-hand-side panel
@@ -763,7 +770,7 @@ static int launch_generic(NdlqrHipCtx* c, bool lean) {
 #define NDLQR_SMALL_INSTANCE(NX_, NU_)                                              \
   int ndlqr_small_solve_##NX_##_##NU_(NdlqrHipCtx* c, bool strict, bool keep);       \
   int ndlqr_small_needs_F_##NX_##_##NU_(const NdlqrHipCtx* c, bool strict, bool keep); \
-  void ndlqr_small_rhs_##NX_##_##NU_(NdlqrHipCtx* c);                               \
+  void ndlqr_small_rhs_##NX_##_##NU_(NdlqrHipCtx* c, const double* rhs, double* z);                               \
   int ndlqr_small_kpb_##NX_##_##NU_(void);                                          \
   int ndlqr_small_tshard_##NX_##_##NU_(NdlqrHipCtx* c, int phase, int g, int G);      \
   int ndlqr_small_slot_##NX_##_##NU_(void);                                          \
@@ -775,7 +782,7 @@ struct SmallInstance {
   int nx, nu;
   int (*solve)(NdlqrHipCtx*, bool, bool);
   int (*needs_F)(const NdlqrHipCtx*, bool, bool);
-  void (*rhs)(NdlqrHipCtx*);
+  void (*rhs)(NdlqrHipCtx*, const double*, double*);
   int (*kpb)(void);
   int (*tshard)(NdlqrHipCtx*, int, int, int);
   int (*slot)(void);
@@ -791,7 +798,7 @@ struct SmallInstance {
     if (strict) return keep ? plan_small<NX_, NU_, true, true>(c).needs_F : plan_small<NX_, NU_, true, false>(c).needs_F; \
     return keep ? plan_small<NX_, NU_, false, true>(c).needs_F : plan_small<NX_, NU_, false, false>(c).needs_F;           \
   }                                                                                                 \
-  void ndlqr_small_rhs_##NX_##_##NU_(NdlqrHipCtx* c) { launch_rhs_records<NX_, NU_>(c); }           \
+  void ndlqr_small_rhs_##NX_##_##NU_(NdlqrHipCtx* c, const double* rhs, double* z) { launch_rhs_records<NX_, NU_>(c, rhs, z); } \
   int ndlqr_small_kpb_##NX_##_##NU_(void) { return ndlqr::SchurShape<NX_, NU_>::KPB; }              \
   int ndlqr_small_tshard_##NX_##_##NU_(NdlqrHipCtx* c, int phase, int g, int G) { return launch_time_shard<NX_, NU_>(c, phase, g, G); } \
   int ndlqr_small_slot_##NX_##_##NU_(void) { return (int)ndlqr::RedSlot<NX_>::SIZE; }              \
@@ -990,6 +997,7 @@ static int launch_solve(NdlqrHipCtx* c) {
   HIP_TRY(hipGetLastError());
   note_solution(c);
   c->fact_valid = solve_leaves_factors(c);
+  c->inputs_replaced = false;
   return NDLQR_OK;
 }
 
@@ -1092,6 +1100,7 @@ int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   note_solution(c);
   c->fact_valid = solve_leaves_factors(c);
+  c->inputs_replaced = false;
   c->timing_pending = true;
   c->state_dirty = false;
   return ndlqr_hip_synchronize(c);
@@ -1195,7 +1204,7 @@ static const double* pinned_device_view(const double* p, int device) {
   return static_cast<const double*>(dv);
 }
 
-static bool try_launch_rhs_records(NdlqrHipCtx* c);  // below
+static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z);  // below
 
 int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const double* dd, const double* x0,
                          double* soln) {
@@ -1257,7 +1266,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   //  full-record form of the small shapes -- tree schedule -- re-solves no faster than it factors and keeps factoring.)
   const bool generic_records = !pick_small(c) && c->d.n > 32;
   if ((c->flags & NDLQR_FLAG_KEEP_RECORDS) && !(c->flags & (NDLQR_FLAG_STRICT_FP | NDLQR_FLAG_KEEP_FACT)) && c->rec_complete &&
-      (c->rec_compact || generic_records) && c->cur == 0 && try_launch_rhs_records(c)) {
+      (c->rec_compact || generic_records) && c->cur == 0 && try_launch_rhs_records(c, s.rhs, s.z)) {
     HIP_TRY(hipGetLastError());
     note_solution(c);
     c->schedule = generic_records ? "generic-reduced-records (re-solve)" : "reduced-compact-records (re-solve)";
@@ -1446,14 +1455,15 @@ int ndlqr_hip_upload_rhs(NdlqrHipCtx* c, int p0, int count, const double* rhs) {
   return NDLQR_OK;
 }
 
+// the factor-array sweep of a re-solve: right-hand side `rhs`, solution into `z`
 template <bool STRICT>
-static void launch_rhs_sweep(NdlqrHipCtx* c) {
+static void launch_rhs_sweep(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   {
     ScopedSlot t(c, SLOT_LEAF);
     hipLaunchKernelGGL((ndlqr::rhs_leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(64), 0, s.stream, d, c->QR,
-                       s.rhs, s.z);
+                       rhs, z);
   }
   for (int l = 0; l < d.K; ++l) {
     {
@@ -1461,23 +1471,24 @@ static void launch_rhs_sweep(NdlqrHipCtx* c) {
       const size_t lds_staged = sizeof(double) * ((size_t)d.n * (d.n + 1) + d.n);
       const int staged = lds_staged <= 160 * 1024 ? 1 : 0;
       hipLaunchKernelGGL((ndlqr::rhs_separator_generic<STRICT>), dim3(d.N >> (l + 1), d.batch), dim3(64),
-                         staged ? lds_staged : sizeof(double) * (size_t)d.n, s.stream, d, l, c->AB, c->F, s.z, staged);
+                         staged ? lds_staged : sizeof(double) * (size_t)d.n, s.stream, d, l, c->AB, c->F, z, staged);
     }
     {
       ScopedSlot t(c, SLOT_SCHUR);
       const int work = d.N * d.rows;
       hipLaunchKernelGGL((ndlqr::rhs_update_generic<STRICT>), dim3((work + 255) / 256, d.batch), dim3(256), 0,
-                         s.stream, d, l, c->F, s.z);
+                         s.stream, d, l, c->F, z);
     }
   }
 }
 
-static bool try_launch_rhs_records(NdlqrHipCtx* c) {
+// the record-based re-solve where the kept records have one: right-hand side `rhs`, solution into `z`
+static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
   if (!c->rec_complete || (c->flags & NDLQR_FLAG_STRICT_FP)) return false;
   if (!pick_small(c)) {  // runtime-sized separator-only schedule: records + slots + W of every separator
     if (!plan_reduced_generic(c).ok) return false;
-    launch_rhs_reduced_generic(c);
+    launch_rhs_reduced_generic(c, rhs, z);
     return true;
   }
   if (c->flags & NDLQR_FLAG_GENERIC) return false;
@@ -1487,7 +1498,7 @@ static bool try_launch_rhs_records(NdlqrHipCtx* c) {
   //  separators of nx rows in one workgroup; the compact form -- rb_forward / rb_forward_top -- was checked by its plan)
   if (!c->rec_compact && (d.N < 8 || (size_t)(d.N / 8) * d.n * sizeof(double) > 60 * 1024 || (d.K + 4) * inst->nx > 256))
     return false;
-  inst->rhs(c);
+  inst->rhs(c, rhs, z);
   return true;
 }
 
@@ -1508,18 +1519,234 @@ int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
     if (merr) return merr;
   }
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  if (!try_launch_rhs_records(c)) {
+  if (!try_launch_rhs_records(c, s.rhs, s.z)) {
     if (!c->fact_valid) {  // records only, but this shape / horizon has no record-based re-solve
       g_last_error = "rhs-only solve: this configuration needs NDLQR_FLAG_KEEP_FACT";
       fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
       return NDLQR_ERR_INVALID;
     }
-    if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c); else launch_rhs_sweep<false>(c);
+    if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c, s.rhs, s.z); else launch_rhs_sweep<false>(c, s.rhs, s.z);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   c->timing_pending = true;
   note_solution(c);
+  return NDLQR_OK;
+}
+
+// ------------------------------------------------------------------------------ adjoint solve, parameter gradients
+
+// where `p` lives: 1 this device's memory (kernels take it as it is), 0 host memory, pinned or pageable (staged through
+// HBM), -1 another device's memory (refused: the caller has the wrong device, and a silent copy would hide it)
+static int locate(const void* p, int device) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (a.type == hipMemoryTypeDevice) return a.device == device ? 1 : -1;
+  return 0;
+}
+
+static int refuse(const std::string& msg) {
+  g_last_error = msg;
+  fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
+  return NDLQR_ERR_INVALID;
+}
+
+static int ensure_grad_stage(NdlqrHipCtx* c, size_t doubles) {
+  if (doubles <= c->grad_stage_cap) return NDLQR_OK;
+  (void)hipFree(c->grad_stage);
+  c->grad_stage = nullptr;
+  c->grad_stage_cap = 0;
+  HIP_TRY(hipMalloc(&c->grad_stage, sizeof(double) * doubles));
+  c->grad_stage_cap = doubles;
+  return NDLQR_OK;
+}
+
+// The re-solves of the kept records write what depends on the right-hand side into them (z_sep / y~: the last n entries
+// of every record) and, on the runtime-sized schedule, into the slots (gL | gR). Every re-solve recomputes those before
+// it reads them; the adjoint solve still leaves them as it found them: saved before, restored after (2 n doubles per
+// knot instead of the whole records).
+static hipError_t adjoint_scratch(NdlqrHipCtx* c, bool restore) {
+  const ndlqr::Dims& d = c->d;
+  const BufferSet& s = c->set[0];
+  const size_t col = sizeof(double) * d.n, rows = (size_t)d.batch * d.N;
+  double* save = c->adj_save;
+  double* rec_col = s.rec + 2 * (size_t)d.n * d.n;
+  const size_t rec_pitch = sizeof(double) * (2 * (size_t)d.n * d.n + d.n);
+  hipError_t e = restore ? hipMemcpy2DAsync(rec_col, rec_pitch, save, col, col, rows, hipMemcpyDeviceToDevice, s.stream)
+                         : hipMemcpy2DAsync(save, col, rec_col, rec_pitch, col, rows, hipMemcpyDeviceToDevice, s.stream);
+  if (e != hipSuccess || pick_small(c) || d.N < 4 || !s.red || s.red_bytes < bytes_red_generic(d)) return e;
+  double* slot_g = s.red + 4 * (size_t)d.n * d.n;
+  const size_t slot_pitch = sizeof(double) * (4 * (size_t)d.n * d.n + 2 * d.n), nslots = (size_t)d.batch * (d.N / 2);
+  save += rows * d.n;
+  return restore ? hipMemcpy2DAsync(slot_g, slot_pitch, save, 2 * col, 2 * col, nslots, hipMemcpyDeviceToDevice, s.stream)
+                 : hipMemcpy2DAsync(save, 2 * col, slot_g, slot_pitch, 2 * col, nslots, hipMemcpyDeviceToDevice, s.stream);
+}
+
+int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
+  if (!c || !g) return NDLQR_ERR_INVALID;
+  if (!c->fact_valid && !c->rec_complete)
+    return refuse("adjoint solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
+                  "factorisation) of the resident inputs");
+  if (c->z_partial) return need_full_solution(c, "ndlqr_hip_solve_adjoint");
+  if (!strcmp(c->schedule, "reduced-time-shard")) return refuse("adjoint solve: not available on a time-axis shard");
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  const int where = locate(g, c->device);
+  if (where < 0) return refuse("ndlqr_hip_solve_adjoint: g lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  c->cur = 0;  // cached records / factors live in the primary set
+  BufferSet& s = c->set[0];
+  const size_t nvars = (size_t)u.rows * u.N - u.m;
+  if (!c->adj_rhs) HIP_TRY(hipMalloc(&c->adj_rhs, bytes_z(d)));
+  if (!c->adj_save) HIP_TRY(hipMalloc(&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n));
+  if (!c->adj_z) {
+    HIP_TRY(hipMalloc(&c->adj_z, bytes_z(d)));
+    HIP_TRY(hipMemsetAsync(c->adj_z, 0, bytes_z(d), s.stream));  // (entries a re-solve does not write: the pad rows)
+  }
+  const double* gd = g;
+  if (where == 0) {
+    const int serr = ensure_grad_stage(c, nvars * d.batch);
+    if (serr) return serr;
+    HIP_TRY(hipMemcpyAsync(c->grad_stage, g, sizeof(double) * nvars * d.batch, hipMemcpyDefault, s.stream));
+    gd = c->grad_stage;
+  }
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, gd, c->adj_rhs);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(adjoint_scratch(c, false));
+  if (!try_launch_rhs_records(c, c->adj_rhs, c->adj_z)) {
+    if (!c->fact_valid)  // records only, but this shape / horizon has no record-based re-solve
+      return refuse("adjoint solve: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
+    if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c, c->adj_rhs, c->adj_z);
+    else launch_rhs_sweep<false>(c, c->adj_rhs, c->adj_z);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(adjoint_scratch(c, true));
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
+  c->adj_gen = c->soln_gen;
+  return NDLQR_OK;
+}
+
+// is there an adjoint of the resident solution of the resident inputs?
+static int need_adjoint(const NdlqrHipCtx* c, const char* who) {
+  if (c->z_partial) return need_full_solution(c, who);
+  if (c->adj_gen == 0 || c->adj_gen != c->soln_gen)
+    return refuse(std::string(who) + ": no adjoint of the resident solution (ndlqr_hip_solve_adjoint after the latest solve)");
+  if (c->inputs_replaced) return refuse(std::string(who) + ": the inputs were replaced after the factorisation");
+  return NDLQR_OK;
+}
+
+static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count, double* soln);  // below
+
+int ndlqr_hip_download_adjoint(NdlqrHipCtx* c, double* w) {
+  if (!c || !w) return NDLQR_ERR_INVALID;
+  const int aerr = need_adjoint(c, "ndlqr_hip_download_adjoint");
+  if (aerr) return aerr;
+  HIP_TRY(hipSetDevice(c->device));
+  const int where = locate(w, c->device);
+  if (where < 0) return refuse("ndlqr_hip_download_adjoint: w lies in the memory of another device than the solver's");
+  if (where == 0) return download_packed(c, c->adj_z, 0, c->d.batch, w);
+  const BufferSet& s = c->set[0];
+  HIP_TRY(sync_all(c));
+  hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(c->du), c->d.batch), dim3(256), 0,
+                     s.stream, c->du, c->d, (const double*)c->adj_z, w);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR, double* gq,
+                        double* gr, double* gd, double* gx0) {
+  if (!c || (sum_mask & ~0xFFu)) return NDLQR_ERR_INVALID;
+  const int aerr = need_adjoint(c, "ndlqr_hip_gradients");
+  if (aerr) return aerr;
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  double* user[ndlqr::GRAD_COUNT] = {gA, gB, gQ, gR, gq, gr, gd, gx0};
+  int where[ndlqr::GRAD_COUNT] = {};
+  size_t size[ndlqr::GRAD_COUNT] = {};
+  size_t stage = 0, total = 0;
+  ndlqr::GradOut out = {};
+  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) {
+    if (!user[o]) continue;
+    where[o] = locate(user[o], c->device);
+    if (where[o] < 0) return refuse("ndlqr_hip_gradients: an output lies in the memory of another device than the solver's");
+    const bool summed = (sum_mask >> o) & 1u;
+    const size_t per = o == ndlqr::GRAD_x0 ? (size_t)u.n : (size_t)u.N * ndlqr::grad_width(u, o);
+    size[o] = summed ? per : per * d.batch;
+    if (where[o] == 0) stage += size[o];
+    if (summed) { out.off[o] = total; total += per; }
+  }
+  out.sum = sum_mask;
+  out.total = total;
+  // chunk of knots per workgroup: the accumulators of its summed outputs and its z | w blocks within 48 KB of LDS where
+  // they fit (one knot of the batch-summed gA at 128 states is 128 KB)
+  int wsum = 0;
+  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o)
+    if (user[o] && ((sum_mask >> o) & 1u)) wsum += ndlqr::grad_width(u, o);
+  int KC = 8;
+  while (KC > 1 && (KC > d.N || sizeof(double) * ((size_t)KC * wsum + 2 * (size_t)(KC + 1) * d.rows) > 48 * 1024)) KC >>= 1;
+  const size_t lds = sizeof(double) * ((size_t)KC * wsum + 2 * (size_t)(KC + 1) * d.rows);
+  if (lds > 160 * 1024)
+    return refuse("ndlqr_hip_gradients: the batch sums of one knot of this block size exceed the LDS of a workgroup: "
+                  "sum fewer outputs at once, or sum the per-problem outputs");
+  const int nchunks = d.N / KC;
+  // problems per workgroup row: one without batch sums; with them, about 2048 workgroups in all (the split sums meet in
+  // a second, ordered pass)
+  int ppb = 1, nsplit = d.batch;
+  if (total > 0) {
+    nsplit = 2048 / nchunks;
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > d.batch) nsplit = d.batch;
+    while (nsplit > 1 && (size_t)nsplit * total > ((size_t)64 << 20)) nsplit >>= 1;  // partial sums within 512 MB
+    ppb = (d.batch + nsplit - 1) / nsplit;
+    nsplit = (d.batch + ppb - 1) / ppb;
+  }
+  const size_t npart = nsplit > 1 ? (size_t)nsplit * total : 0;
+  {
+    const int serr = ensure_grad_stage(c, stage + npart);
+    if (serr) return serr;
+  }
+  HIP_TRY(sync_all(c));
+  BufferSet& s = c->set[0];
+  double* at = c->grad_stage;
+  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) {
+    if (!user[o]) continue;
+    out.p[o] = where[o] == 1 ? user[o] : at;
+    if (where[o] == 0) at += size[o];
+  }
+  double* part = npart ? at : nullptr;
+  const double* z = c->set[c->latest].z;
+  const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
+  if (lds > 64 * 1024)  // (beyond the default limit of dynamic LDS)
+    HIP_TRY(hipFuncSetAttribute(strict ? reinterpret_cast<const void*>(&ndlqr::grad_assemble<true>)
+                                       : reinterpret_cast<const void*>(&ndlqr::grad_assemble<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  if (strict)
+    hipLaunchKernelGGL(ndlqr::grad_assemble<true>, dim3(nchunks, nsplit), dim3(256), lds, s.stream, u, d, KC, ppb, z,
+                       (const double*)c->adj_z, out, part);
+  else
+    hipLaunchKernelGGL(ndlqr::grad_assemble<false>, dim3(nchunks, nsplit), dim3(256), lds, s.stream, u, d, KC, ppb, z,
+                       (const double*)c->adj_z, out, part);
+  HIP_TRY(hipGetLastError());
+  if (part) {
+    hipLaunchKernelGGL(ndlqr::grad_sum_splits, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s.stream, out, nsplit,
+                       (const double*)part);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
+  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o)
+    if (user[o] && where[o] == 0)
+      HIP_TRY(hipMemcpyAsync(user[o], out.p[o], sizeof(double) * size[o], hipMemcpyDefault, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
   return NDLQR_OK;
 }
 
@@ -1710,13 +1937,17 @@ static bool host_ptr_is_pinned(const void* p) {
 int ndlqr_hip_download_solutions(NdlqrHipCtx* c, int p0, int count, double* soln) {
   if (!c || !soln || p0 < 0 || count <= 0 || p0 + count > c->d.batch) return NDLQR_ERR_INVALID;
   if (c->z_partial) return need_full_solution(c, "ndlqr_hip_download_solutions");
+  return download_packed(c, c->set[c->latest].z, p0, count, soln);
+}
+// ... of the blocks [batch][N][2n+m] at zsrc (the latest solution, or the adjoint solution)
+static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count, double* soln) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
   const int xerr = ensure_xfer(c);
   if (xerr) return xerr;
-  const double* zl = c->set[c->latest].z;
+  const double* zl = zsrc;
   const size_t nvars = (size_t)c->du.rows * d.N - c->du.m, pitch = (size_t)d.rows * d.N;
   hipStream_t st = s.stream;
   hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(c->du), count), dim3(256), 0, st, c->du, d, zl + p0 * pitch, s.xfer);

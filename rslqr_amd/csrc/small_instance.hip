@@ -3,7 +3,7 @@
 // -DNDLQR_INST_NU=<ninputs>; exports the two entry points ndlqr_hip.hip dispatches to:
 //   ndlqr_small_solve_<nx>_<nu>(ctx, strict, keep)   factor + solve launch sequence
 //   ndlqr_small_needs_F_<nx>_<nu>(ctx, strict, keep)  does that sequence touch the factor array?
-//   ndlqr_small_rhs_<nx>_<nu>(ctx)                      record-based right-hand-side re-solve
+//   ndlqr_small_rhs_<nx>_<nu>(ctx, rhs, z)              record-based right-hand-side re-solve of `rhs` into `z`
 //   ndlqr_small_kpb_<nx>_<nu>()                         knots per workgroup of its Schur kernels
 //   ndlqr_small_tshard_<nx>_<nu>(ctx, phase, g, G)      time-axis sharding: chunk g of G, phase 0 / 1 (launch_time_shard)
 //   ndlqr_small_slot_<nx>_<nu>()                        doubles per accumulator slot
@@ -32,7 +32,7 @@ int NDLQR_INST_NAME(ndlqr_small_needs_F_)(const NdlqrHipCtx* c, bool strict, boo
   return keep ? plan_small<NX, NU, false, true>(c).needs_F : plan_small<NX, NU, false, false>(c).needs_F;
 }
 
-void NDLQR_INST_NAME(ndlqr_small_rhs_)(NdlqrHipCtx* c) { launch_rhs_records<NX, NU>(c); }
+void NDLQR_INST_NAME(ndlqr_small_rhs_)(NdlqrHipCtx* c, const double* rhs, double* z) { launch_rhs_records<NX, NU>(c, rhs, z); }
 
 int NDLQR_INST_NAME(ndlqr_small_kpb_)(void) { return ndlqr::SchurShape<NX, NU>::KPB; }
 
