@@ -487,8 +487,9 @@ double ndlqr_BatchSolveTimeMs(const NdLqrBatchSolver* bs); /* HIP-event time of 
  *   computed a slice alone (NDLQR_SOLN_ONLY), on a time-axis shard, and for device memory of another device.
  *   Outputs of ndlqr_BatchGradients: NULL = not computed; host or pinned memory (staged through HBM, one copy each) or the
  *   solver's device memory (written by the kernel). Bit o of sum_mask (NDLQR_GRAD_*): output o summed over the batch,
- *   deterministically -- [N][...] ([n] for x0) instead of [batch][N][...]. All three calls block until their results are
- *   complete; ndlqr_BatchSolveTimeMs then reports the device time of the adjoint solve / the gradient kernels. */
+ *   deterministically -- [N][...] ([n] for x0) instead of [batch][N][...], at every block size the solver takes. The one
+ *   refusal by size: z and w of two knots beyond the LDS of a workgroup (2n+m > 5120). All three calls block until their
+ *   results are complete; ndlqr_BatchSolveTimeMs then reports the device time of the adjoint solve / the gradient kernels. */
 #define NDLQR_GRAD_A 1u
 #define NDLQR_GRAD_B 2u
 #define NDLQR_GRAD_Q 4u

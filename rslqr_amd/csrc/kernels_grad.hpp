@@ -57,14 +57,17 @@ __host__ __device__ inline int grad_width(const Dims& du, const int o) {
   }
 }
 
-// Per-problem gradients and / or batch sums of knots [k0, k0 + KC) of problems [p0, p1): grid (N / KC, nsplit), block 256,
-// dynamic LDS 2 (KC + 1) (2n+m) doubles of z | w (device blocks, + the lambda of the knot after the chunk) and the
-// accumulators of the summed outputs (KC x width each, n for x0 in the first chunk). Each workgroup takes its problems in
-// order and every thread owns the same accumulator entries throughout, so the sums are deterministic. Outputs are written
-// as contiguous runs of the flat layout: consecutive lanes, consecutive elements.
+// Per-problem gradients and / or batch sums of knots [k0, k0 + KC) of problems [p0, p1): grid (N / KC, nsplit, nslice),
+// block 256, dynamic LDS 2 (KC + 1) (2n+m) doubles of z | w (device blocks, + the lambda of the knot after the chunk) and
+// the accumulators of the summed outputs (KC x width each, n for x0 in the first chunk, one after the other in order of
+// the outputs). Slice blockIdx.z holds accumulator entries [z EC, z EC + EC) of that sequence (one slice, EC >= all of
+// them, where they fit the LDS; else the entries of one knot are spread over several workgroups), and slice 0 alone
+// writes the per-problem outputs. Each workgroup takes its problems in order and every thread owns the same accumulator
+// entries throughout, so the sums are deterministic. Outputs are written as contiguous runs of the flat layout:
+// consecutive lanes, consecutive elements.
 // STRICT: no contraction, gA / gB as t1 = a b, t2 = c e, s = t1 + t2, out = -s (numpy reproduces them bit for bit).
 template <bool STRICT>
-__global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int KC, const int ppb,
+__global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int KC, const int ppb, const int EC,
                                                      const double* __restrict__ z, const double* __restrict__ w,
                                                      GradOut out, double* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -75,6 +78,7 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
   double* ws = zs + (KC + 1) * rows;
   double* acc = ws + (KC + 1) * rows;
   const int tid = threadIdx.x;
+  const int s0 = blockIdx.z * EC, s1 = s0 + EC;  // this slice's accumulator entries: acc[j - s0] for j in [s0, s1)
   int aoff[GRAD_COUNT];
   {
     int a = 0;
@@ -82,7 +86,8 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
       aoff[o] = a;
       if (out.p[o] && (out.sum & (1u << o))) a += o == GRAD_x0 ? (k0 == 0 ? n : 0) : KC * grad_width(du, o);
     }
-    for (int e = tid; e < a; e += blockDim.x) acc[e] = 0.0;  // (each thread owns its entries: no barrier needed)
+    if (blockIdx.z > 0 && a <= s0) return;  // (a further slice with no entries in this chunk; uniform over the block)
+    for (int e = tid; e < (a < s1 ? a : s1) - s0; e += blockDim.x) acc[e] = 0.0;  // (the first barrier below orders these)
   }
   for (int p = p0; p < p1; ++p) {
     __syncthreads();  // the previous problem's blocks have been read
@@ -96,9 +101,11 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
       double* dst = out.p[o];
       if (!dst) continue;
       const bool summed = (out.sum & (1u << o)) != 0;
+      if (!summed && blockIdx.z > 0) continue;
       const int W = grad_width(du, o);
       const int E = o == GRAD_x0 ? (k0 == 0 ? n : 0) : KC * W;
-      for (int e = tid; e < E; e += blockDim.x) {
+      const int e0 = summed && s0 > aoff[o] ? s0 - aoff[o] : 0, e1 = summed && s1 - aoff[o] < E ? s1 - aoff[o] : E;
+      for (int e = e0 + tid; e < e1; e += blockDim.x) {
         const int kk = e / W, rr = e - kk * W, k = k0 + kk;
         const bool last = k == N - 1;
         const double* Z = zs + kk * rows;
@@ -127,7 +134,7 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
           case GRAD_d: v = last ? 0.0 : -Wv[rows + rr]; break;
           default: v = -Wv[rr]; break;  // x0: lambda of knot 0
         }
-        if (summed) acc[aoff[o] + e] += v;
+        if (summed) acc[aoff[o] + e - s0] += v;
         else dst[(o == GRAD_x0 ? (size_t)p * n : ((size_t)p * N + k0) * W) + e] = v;
       }
     }
@@ -136,9 +143,10 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
     if (!out.p[o] || !(out.sum & (1u << o))) continue;
     const int W = grad_width(du, o);
     const int E = o == GRAD_x0 ? (k0 == 0 ? n : 0) : KC * W;
+    const int e0 = s0 > aoff[o] ? s0 - aoff[o] : 0, e1 = s1 - aoff[o] < E ? s1 - aoff[o] : E;
     double* dst = part ? part + (size_t)blockIdx.y * out.total + out.off[o] : out.p[o];
     const size_t at = o == GRAD_x0 ? 0 : (size_t)k0 * W;
-    for (int e = tid; e < E; e += blockDim.x) dst[at + e] = acc[aoff[o] + e];
+    for (int e = e0 + tid; e < e1; e += blockDim.x) dst[at + e] = acc[aoff[o] + e - s0];
   }
 }
 

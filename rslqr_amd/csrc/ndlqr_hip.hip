@@ -1691,16 +1691,21 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
     if (user[o] && ((sum_mask >> o) & 1u)) wsum += ndlqr::grad_width(u, o);
   int KC = 8;
   while (KC > 1 && (KC > d.N || sizeof(double) * ((size_t)KC * wsum + 2 * (size_t)(KC + 1) * d.rows) > 48 * 1024)) KC >>= 1;
-  const size_t lds = sizeof(double) * ((size_t)KC * wsum + 2 * (size_t)(KC + 1) * d.rows);
-  if (lds > 160 * 1024)
-    return refuse("ndlqr_hip_gradients: the batch sums of one knot of this block size exceed the LDS of a workgroup: "
-                  "sum fewer outputs at once, or sum the per-problem outputs");
+  const size_t lds_max = 160 * 1024 / sizeof(double), zw = 2 * (size_t)(KC + 1) * d.rows, nacc = (size_t)KC * wsum;
+  if (zw >= lds_max)
+    return refuse("ndlqr_hip_gradients: z and w of two knots of this block size exceed the LDS of a workgroup");
+  // where the accumulators of one knot do not fit beside z | w (a batch-summed gA from about 139 states on), they are
+  // spread over nslice workgroups of EC entries each (a third grid dimension); one slice otherwise
+  int nslice = (int)((nacc + (lds_max - zw) - 1) / (lds_max - zw));
+  if (nslice < 1) nslice = 1;
+  const size_t EC = (nacc + nslice - 1) / nslice;
+  const size_t lds = sizeof(double) * (EC + zw);
   const int nchunks = d.N / KC;
   // problems per workgroup row: one without batch sums; with them, about 2048 workgroups in all (the split sums meet in
   // a second, ordered pass)
   int ppb = 1, nsplit = d.batch;
   if (total > 0) {
-    nsplit = 2048 / nchunks;
+    nsplit = 2048 / (nchunks * nslice);
     if (nsplit < 1) nsplit = 1;
     if (nsplit > d.batch) nsplit = d.batch;
     while (nsplit > 1 && (size_t)nsplit * total > ((size_t)64 << 20)) nsplit >>= 1;  // partial sums within 512 MB
@@ -1729,11 +1734,11 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   if (strict)
-    hipLaunchKernelGGL(ndlqr::grad_assemble<true>, dim3(nchunks, nsplit), dim3(256), lds, s.stream, u, d, KC, ppb, z,
-                       (const double*)c->adj_z, out, part);
+    hipLaunchKernelGGL(ndlqr::grad_assemble<true>, dim3(nchunks, nsplit, nslice), dim3(256), lds, s.stream, u, d, KC, ppb,
+                       (int)EC, z, (const double*)c->adj_z, out, part);
   else
-    hipLaunchKernelGGL(ndlqr::grad_assemble<false>, dim3(nchunks, nsplit), dim3(256), lds, s.stream, u, d, KC, ppb, z,
-                       (const double*)c->adj_z, out, part);
+    hipLaunchKernelGGL(ndlqr::grad_assemble<false>, dim3(nchunks, nsplit, nslice), dim3(256), lds, s.stream, u, d, KC, ppb,
+                       (int)EC, z, (const double*)c->adj_z, out, part);
   HIP_TRY(hipGetLastError());
   if (part) {
     hipLaunchKernelGGL(ndlqr::grad_sum_splits, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s.stream, out, nsplit,

@@ -309,3 +309,81 @@ def refined_solution(oracle, prob, iters=3):
                        (-r_lam[0]).astype(np.float64))
         z = z + oracle.solve(corr, 8)[0][: prob.nvars]
     return z.astype(np.float64)
+
+
+def kkt_direction_ld(prob, name, V, z, absolute=False):
+    """How the KKT residual r(z; theta) = b(theta) - K(theta) z of the problem changes when its argument `name` (one of
+    A, B, Q, R, q, r, d, x0, in the flat layout of Problem) moves by V: r(z; theta + V) - r(z; theta), exactly, since K
+    is affine in (A, B, Q, R) and b is linear in (q, r, d, x0). Extended precision (numpy longdouble), for z in the
+    reference's [lambda x u] order. absolute=True: |b(V)| + |K(V) - K(0)| |z| instead, the size of the terms.
+    Returns (r_lam [N, n], r_x [N, n], r_u [N, m]). Test infrastructure."""
+    ld = np.longdouble
+    n, m, N = prob.n, prob.m, prob.N
+    f = np.abs if absolute else (lambda a: a)
+    full = np.zeros(N * (2 * n + m), dtype=ld)
+    full[: z.size] = z
+    Z = f(full.reshape(N, 2 * n + m))
+    lam, x, u = Z[:, :n], Z[:, n:2 * n], Z[:, 2 * n:]
+    V = f(np.asarray(V, dtype=ld).reshape(getattr(prob, name).shape))
+    sg = 1 if absolute else -1
+    r_lam = np.zeros((N, n), dtype=ld)
+    r_x = np.zeros((N, n), dtype=ld)
+    r_u = np.zeros((N, m), dtype=ld)
+    if name == "x0":
+        r_lam[0] = sg * V
+    elif name == "q":
+        r_x[:] = sg * V
+    elif name == "r":
+        r_u[: N - 1] = sg * V[: N - 1]
+    elif name == "d":
+        r_lam[1:] = sg * V[: N - 1]
+    elif name == "Q":
+        r_x[:] = sg * V * x
+    elif name == "R":
+        r_u[: N - 1] = sg * V[: N - 1] * u[: N - 1]
+    elif name in ("A", "B"):
+        cols = n if name == "A" else m
+        M = V.reshape(N, cols, n).transpose(0, 2, 1)[: N - 1]  # column-major storage -> M[k][i, j], the last knot unused
+        col = x if name == "A" else u
+        tr = np.einsum("kij,ki->kj", M, lam[1:])   # M_k^T lambda_(k+1): rows of x_k (A) or u_k (B)
+        (r_x if name == "A" else r_u)[: N - 1] = sg * tr
+        r_lam[1:] = sg * np.einsum("kij,kj->ki", M, col[: N - 1])
+    else:
+        raise ValueError(name)
+    return r_lam, r_x, r_u
+
+
+def _dot_blocks(prob, w, parts):
+    n, m, N = prob.n, prob.m, prob.N
+    full = np.zeros(N * (2 * n + m), dtype=np.longdouble)
+    full[: w.size] = w
+    W = full.reshape(N, 2 * n + m)
+    return (W[:, :n] * parts[0]).sum() + (W[:, n:2 * n] * parts[1]).sum() + (W[:, 2 * n:] * parts[2]).sum()
+
+
+def gradient_direction_ld(prob, name, V, z, w):
+    """<dL/d(name), V> of a loss L of the solution z whose adjoint (K w = dL/dz) is w: w^T (r(z; theta + V) - r(z; theta))
+    from the KKT operator (no gradient formula, no step size), in extended precision. Returns (value, size): size =
+    sum |w| (|b(V)| + |K(V) - K(0)| |z|), the sum of the absolute values of the products -- what rounding is relative to."""
+    ld = np.longdouble
+    w = np.asarray(w, dtype=ld)
+    z = np.asarray(z, dtype=ld)
+    value = _dot_blocks(prob, w, kkt_direction_ld(prob, name, V, z))
+    size = _dot_blocks(prob, np.abs(w), kkt_direction_ld(prob, name, V, z, absolute=True))
+    return value, size
+
+
+def gradient_direction_bar(prob, name, V, z, w, z_true, w_true, ulps=16):
+    """(reference, bar) for <G, V> of gradients G computed from (z, w), where z_true, w_true are the solution and adjoint
+    taken as exact: the reference is gradient_direction_ld of the truths; the bar is an upper bound of what the errors of
+    z and w (entry by entry) and the rounding of the products can move it -- |w - w_true|^T |r_V|(z) +
+    |w_true|^T |K(V) - K(0)| |z - z_true| + ulps eps (size(z, w) + size(z_true, w_true))."""
+    ld = np.longdouble
+    ref, size_true = gradient_direction_ld(prob, name, V, z_true, w_true)
+    _, size = gradient_direction_ld(prob, name, V, z, w)
+    dw = np.abs(np.asarray(w, dtype=ld) - np.asarray(w_true, dtype=ld))
+    dz = np.abs(np.asarray(z, dtype=ld) - np.asarray(z_true, dtype=ld))
+    prop = _dot_blocks(prob, dw, kkt_direction_ld(prob, name, V, np.asarray(z, dtype=ld), absolute=True))
+    if name in ("A", "B", "Q", "R"):  # (the right-hand-side arguments do not multiply z)
+        prop += _dot_blocks(prob, np.abs(np.asarray(w_true, dtype=ld)), kkt_direction_ld(prob, name, V, dz, absolute=True))
+    return ref, prop + ulps * np.finfo(np.float64).eps * (size + size_true)

@@ -1,11 +1,14 @@
 """Adjoint solve and parameter gradients (ndlqr_SolveBatchAdjoint, ndlqr_BatchGradients, rslqr_amd.autograd) against the
 CPU oracle plus numpy: the adjoint K w = g is the oracle's solve of the adjoint problem (same A, B, Q, R; x0' = -g_lam0,
 q'_k = -g_xk, r'_k = -g_uk, d'_k = -g_lam(k+1)), the gradients are the outer-product formulas of kernels_grad.hpp
-evaluated by numpy on the oracle's z and w, and central differences of L = g . z through the oracle check the formulas."""
+evaluated by numpy on the oracle's z and w, and central differences of L = g . z through the oracle check the formulas.
+Independently of the formulas, every forward schedule and the gradient kernel's edges are checked against the KKT operator
+itself: <dL/dtheta, V> = w^T (r(z; theta + V) - r(z; theta)) in extended precision on the refined solution and adjoint
+(support.gradient_direction_bar)."""
 import numpy as np
 import pytest
 
-from support import Problem
+from support import Problem, gradient_direction_bar, refined_solution
 
 pytestmark = pytest.mark.gpu
 
@@ -66,6 +69,46 @@ def grad_formula(prob, z, w):
 def rel(a, b):
     nb = np.linalg.norm(b)
     return np.linalg.norm(a - b) / (nb if nb > 0 else 1.0)
+
+
+def directions(prob, seed):
+    """(argument, label, V): one random direction per argument over all of it, then one confined to knot 0, a middle
+    knot, knot N - 2 and the last knot (x0 has no knots: the whole of it once)."""
+    rng = np.random.default_rng(seed)
+    N = prob.N
+    out = []
+    for k in ARGS:
+        shape = getattr(prob, k).shape
+        out.append((k, "all", rng.standard_normal(shape)))
+        if k == "x0":
+            continue
+        for knot in sorted({0, N // 2, N - 2, N - 1}):
+            V = np.zeros(shape)
+            V[knot] = rng.standard_normal(shape[1:])
+            out.append((k, "knot %d" % knot, V))
+    return out
+
+
+def check_directions(prob, grads, z, w, z_true, w_true, seed):
+    """<G, V> of the gradients G (one problem, computed from z and w) against the KKT operator applied to the truths, for
+    every direction of directions(); the last knot of A, B, R, r, d exactly zero."""
+    for k, label, V in directions(prob, seed):
+        got = (np.asarray(grads[k], dtype=np.longdouble) * V).sum()
+        ref, bar = gradient_direction_bar(prob, k, V, z, w, z_true, w_true)
+        assert abs(got - ref) <= bar, (k, label, float(got), float(ref), float(bar))
+        if k in ("A", "B", "R", "r", "d"):
+            assert not np.any(grads[k][prob.N - 1]), (k, "last knot")
+
+
+def check_against_truth(oracle, prob, g, z, w, grads, seed):
+    """w against the refined adjoint (norm-wise, no worse than 10x the oracle's own error), then every direction."""
+    ap = adjoint_problem(prob, g)
+    z_true = refined_solution(oracle, prob)
+    w_true = refined_solution(oracle, ap)
+    w_oracle = oracle.solve(ap, 8)[0][: prob.nvars]
+    err_gpu, err_oracle = rel(w, w_true), rel(w_oracle, w_true)
+    assert err_gpu <= 10 * err_oracle + 1e-13, (err_gpu, err_oracle)
+    check_directions(prob, grads, z, w, z_true, w_true, seed)
 
 
 def references(oracle, probs, g):
@@ -487,3 +530,253 @@ def _case_refuses_bad_arguments(ndlqr):
     if torch.cuda.device_count() > 1:
         with pytest.raises(ValueError):
             lqr_solve(*[t[k].to("cuda:1") if k == "R" else t[k] for k in ARGS])
+
+
+# ------------------------------------------------------------------------------------------------ every forward schedule
+# Each schedule a solve can leave behind for an adjoint, named as ndlqr_hip_schedule reports it, with the checks of
+# check_against_truth (formula-free: the KKT operator on the refined solution and adjoint). A schedule not listed here has
+# no gradient case. KEEP_RECORDS: reduced-compact-records (level-per-launch, chosen by batch size alone and with
+# NDLQR_TREE=0), reduced-tree (full records, batch 1 and batch > 1), generic-reduced-records (runtime-sized records, also
+# at N = 2 and 4), generic-keep (records kept as factors beyond 128 states), knot-lean (an instance off the matrix cores,
+# (2,1)). KEEP_FACT:
+# generic-keep, knot-keep. STRICT_FP | KEEP_FACT: knot-strict, generic-strict. Padded buckets: (7,9), (11,3), (1,1).
+# (n, m, N, batch, flags, NDLQR_TREE, schedule, problems checked against the refined truth)
+SCHEDULE_CASES = [(12, 4, 64, 160, "records", None, "reduced-compact-records", (0, 159)),
+                  (12, 4, 64, 3, "records", "0", "reduced-compact-records", (1,)),
+                  (12, 4, 256, 1, "records", None, "reduced-tree", (0,)),
+                  (6, 3, 64, 3, "records", None, "reduced-tree", (0, 2)),
+                  (32, 8, 128, 1, "records", None, "generic-reduced-records", (0,)),
+                  (5, 2, 2, 3, "records", None, "generic-reduced-records", (0, 2)),
+                  (6, 3, 4, 2, "records", None, "generic-reduced-records", (1,)),
+                  (144, 16, 8, 1, "records", None, "generic-keep", (0,)),
+                  (7, 9, 16, 2, "records", "0", "reduced-compact-records", (1,)),
+                  (11, 3, 64, 2, "records", "0", "reduced-compact-records", (0,)),
+                  (1, 1, 16, 3, "records", None, "reduced-tree", (0, 2)),
+                  (2, 1, 64, 3, "records", None, "knot-lean", (1,)),
+                  (20, 6, 32, 2, "fact", None, "generic-keep", (1,)),
+                  (12, 4, 64, 2, "fact", None, "knot-keep", (0,)),
+                  (6, 3, 4, 2, "fact", None, "generic-keep", (0,)),
+                  (12, 4, 16, 2, "strict", None, "knot-strict", (1,)),
+                  (20, 6, 16, 2, "strict", None, "generic-strict", (0,))]
+SCHEDULE_FAMILIES = [(1.0, 1.0, 1.0), (1.3, 1e-3, 1.0), (1.0, 1.0, 1e-4)]
+_FLAGS = {"records": "FLAG_KEEP_RECORDS", "fact": "FLAG_KEEP_FACT", "strict": None}
+
+
+@pytest.mark.parametrize("n,m,N,batch,flags,tree,want,check", SCHEDULE_CASES,
+                         ids=["%s-%d.%d.%d.x%d" % (c[6], c[0], c[1], c[2], c[3]) for c in SCHEDULE_CASES])
+@pytest.mark.parametrize("a_scale,q_scale,r_scale", SCHEDULE_FAMILIES)
+def test_every_schedule_against_the_kkt_operator(ndlqr, oracle, monkeypatch, n, m, N, batch, flags, tree, want, check,
+                                                  a_scale, q_scale, r_scale):
+    if tree is not None:
+        monkeypatch.setenv("NDLQR_TREE", tree)
+    probs = [synth(ndlqr, n, m, N, 1500 + p, a_scale, q_scale, r_scale) for p in range(batch)]
+    fl = ndlqr.FLAG_STRICT_FP | ndlqr.FLAG_KEEP_FACT if flags == "strict" else getattr(ndlqr, _FLAGS[flags])
+    bs = ndlqr.BatchSolver(n, m, N, batch, flags=fl)
+    bs.initialize_flat(*stack(probs))
+    assert bs.solve() == 0
+    assert bs.schedule() == want, bs.schedule()
+    z = bs.solutions().copy()
+    g = np.random.default_rng(11).standard_normal((batch, bs.nvars))
+    assert bs.solve_adjoint(g) == 0
+    assert np.array_equal(bs.solutions(), z)
+    w = bs.adjoint()
+    grads = bs.gradients()
+    assert np.array_equal(bs.solutions(), z)
+    for p, prob in enumerate(probs):
+        wr = oracle.solve(adjoint_problem(prob, g[p]), 8)[0][: prob.nvars]
+        assert rel(w[p], wr) <= REL_TOL, (p, rel(w[p], wr))
+    for p in check:
+        check_against_truth(oracle, probs[p], g[p], z[p], w[p], {k: grads[k][p] for k in ARGS}, 20 + p)
+    bs.close()
+
+
+# ------------------------------------------------------------------------------------------------ gradient kernel edges
+
+def _ld_sum_bar(per):
+    """(sum over the batch in longdouble, batch eps sum |terms|) of per-problem outputs [batch, ...]."""
+    t = np.asarray(per, dtype=np.longdouble)
+    return t.sum(axis=0), per.shape[0] * np.finfo(np.float64).eps * np.abs(t).sum(axis=0)
+
+
+def _check_sums(full, per, keys):
+    for k in keys:
+        s, bar = _ld_sum_bar(per[k])
+        assert full[k].shape == per[k].shape[1:], k
+        assert (np.abs(full[k] - s) <= bar).all(), (k, float(np.abs(full[k] - s).max()))
+
+
+def _solved(ndlqr, n, m, N, batch, seed, flags=None):
+    probs = [synth(ndlqr, n, m, N, seed + p) for p in range(batch)]
+    bs = ndlqr.BatchSolver(n, m, N, batch, flags=ndlqr.FLAG_KEEP_RECORDS if flags is None else flags)
+    bs.initialize_flat(*stack(probs))
+    assert bs.solve() == 0
+    g = np.random.default_rng(seed).standard_normal((batch, bs.nvars))
+    assert bs.solve_adjoint(g) == 0
+    return bs, probs, g
+
+
+# (n, m, N, batch): beyond 64 KB of dynamic LDS at one knot per workgroup (96,16); one knot's summed gA beyond the LDS of
+# a workgroup (144,16), (150,10) padded, (256,32): its entries spread over several workgroups
+@pytest.mark.parametrize("n,m,N,batch", [(96, 16, 8, 3), (144, 16, 8, 3), (150, 10, 4, 2), (256, 32, 4, 2)])
+def test_batch_sums_of_large_blocks(ndlqr, n, m, N, batch):
+    bs, probs, g = _solved(ndlqr, n, m, N, batch, 1600)
+    per = bs.gradients()
+    full = bs.gradients(0xFF)
+    _check_sums(full, per, ARGS)
+    again = bs.gradients(0xFF)
+    for k in ARGS:
+        assert np.array_equal(full[k], again[k]), k
+    if n in (144, 256):  # every set of summed outputs with A or B in it; the rest per problem, as before
+        for mask in range(256):
+            if not mask & 3:
+                continue
+            got = bs.gradients(mask)
+            for i, k in enumerate(ARGS):
+                if mask & (1 << i):
+                    assert np.array_equal(got[k], full[k]), (mask, k)
+                else:
+                    assert np.array_equal(got[k], per[k]), (mask, k)
+    bs.close()
+
+
+@pytest.mark.parametrize("n,m,N,batch", [(12, 4, 256, 100), (144, 16, 64, 24), (6, 3, 16, 1)])
+def test_batch_sums_split_and_not_adjacent(ndlqr, n, m, N, batch):
+    """Batches split over several workgroup rows of several problems each (ppb > 1, nsplit > 1: (12,4,256) x 100 and the
+    sliced gA of (144,16,64) x 24), batch 1, and summed outputs that are not neighbours in GradOut order (the output
+    search of grad_sum_splits)."""
+    bs, probs, g = _solved(ndlqr, n, m, N, batch, 1700)
+    if n == 144:  # (gA alone: the per-problem arrays of all eight would be large)
+        per = bs.gradients(0, {"A": np.zeros((batch, N, n * n))})
+        full = bs.gradients(ndlqr.GRAD_A, {"A": np.zeros((N, n * n))})
+        _check_sums(full, per, ["A"])
+        again = bs.gradients(ndlqr.GRAD_A, {"A": np.zeros((N, n * n))})
+        assert np.array_equal(full["A"], again["A"])
+        bs.close()
+        return
+    per = bs.gradients()
+    for mask in (ndlqr.GRAD_B | ndlqr.GRAD_x0, ndlqr.GRAD_Q | ndlqr.GRAD_d, ndlqr.GRAD_A | ndlqr.GRAD_r,
+                 ndlqr.GRAD_R | ndlqr.GRAD_x0, ndlqr.GRAD_x0, ndlqr.GRAD_q):
+        got = bs.gradients(mask)
+        summed = [k for i, k in enumerate(ARGS) if mask & (1 << i)]
+        _check_sums(got, per, summed)
+        for k in ARGS:
+            if k not in summed:
+                assert np.array_equal(got[k], per[k]), (mask, k)
+        again = bs.gradients(mask)
+        for k in ARGS:
+            assert np.array_equal(got[k], again[k]), (mask, k)
+    bs.close()
+
+
+def test_strict_bit_exact_beyond_128_states(ndlqr):
+    """Strict mode at (144,16): every per-problem output bit for bit what numpy computes from the device's z and w, and
+    the batch sums (their entries spread over several workgroups) within the rounding of a sum."""
+    n, m, N, batch = 144, 16, 4, 2
+    bs, probs, g = _solved(ndlqr, n, m, N, batch, 1800, ndlqr.FLAG_STRICT_FP | ndlqr.FLAG_KEEP_FACT)
+    z, w = bs.solutions(), bs.adjoint()
+    per = bs.gradients()
+    for p, prob in enumerate(probs):
+        want = grad_formula(prob, z[p], w[p])
+        for k in ARGS:
+            assert np.array_equal(per[k][p], want[k]), (p, k)
+    _check_sums(bs.gradients(0xFF), per, ARGS)
+    bs.close()
+
+
+# ------------------------------------------------------------------------------------------------ lqr_solve edges
+
+@pytest.mark.parametrize("case", ["shared_alone", "partial_and_layouts", "horizons", "large_shared_A"])
+def test_torch_edges(case):
+    """lqr_solve against the dense torch reference: each argument shared alone; requires_grad on a subset; expanded
+    (stride-0), transposed and sliced A, B; a non-contiguous incoming gradient; batch 1, N = 2, N = 64; a shared A at
+    (144,16), whose batch-summed gA spreads over several workgroups."""
+    _run_case("_case_edges", case)
+
+
+def _leaves(ndlqr, n, m, N, batch, seed, shared=()):
+    """Leaf tensors of a problem (row-major A, B), the arguments in `shared` without the batch dimension."""
+    import torch
+    t = _torch_problem(ndlqr, n, m, N, batch, seed)
+    return {k: (v.detach()[0].clone() if k in shared else v.detach().clone()).requires_grad_(True) for k, v in t.items()}
+
+
+def _compare(args, leaves, n, m, N, batch, gz, backward_with=None):
+    """z and the leaves' gradients through lqr_solve(args) against the same through _dense_solve(args)."""
+    import torch
+    from rslqr_amd.autograd import lqr_solve
+    res = []
+    for fn in (lambda: lqr_solve(*[args[k] for k in ARGS]), lambda: _dense_solve(args, n, m, N, batch)):
+        for v in leaves.values():
+            v.grad = None
+        z = fn()
+        z.backward(gz)
+        res.append((z.detach(), {k: (None if v.grad is None else v.grad.clone()) for k, v in leaves.items()}))
+    (z, got), (zr, ref) = res
+    assert rel(z.cpu().numpy(), zr.cpu().numpy()) <= REL_TOL
+    for k in leaves:
+        if ref[k] is None:
+            assert got[k] is None, k
+            continue
+        assert got[k] is not None and got[k].shape == leaves[k].shape, k
+        assert rel(got[k].cpu().numpy(), ref[k].cpu().numpy()) <= 1e-8, k
+
+
+def _case_edges(ndlqr, case):
+    import torch
+    from rslqr_amd.autograd import lqr_solve
+    nv = lambda n, m, N: (2 * n + m) * N - m
+    if case == "shared_alone":
+        n, m, N, batch = 6, 3, 16, 3
+        gz = torch.randn((batch, nv(n, m, N)), dtype=torch.float64, device="cuda")
+        for k in ARGS:
+            leaves = _leaves(ndlqr, n, m, N, batch, 1900, shared=(k,))
+            _compare(leaves, leaves, n, m, N, batch, gz)
+    elif case == "partial_and_layouts":
+        n, m, N, batch = 6, 3, 16, 3
+        gz = torch.randn((batch, nv(n, m, N)), dtype=torch.float64, device="cuda")
+        # requires_grad on a subset: the others come back None
+        for subset in (("A",), ("B", "x0"), ("Q", "d", "r"), ("R", "q")):
+            leaves = _leaves(ndlqr, n, m, N, batch, 2000)
+            for k in ARGS:
+                if k not in subset:
+                    leaves[k].requires_grad_(False)
+            z = lqr_solve(*[leaves[k] for k in ARGS])
+            z.backward(gz)
+            for k in ARGS:
+                assert (leaves[k].grad is None) == (k not in subset), k
+            _compare(leaves, leaves, n, m, N, batch, gz)
+        # expanded (stride 0) A and B: one leaf each, broadcast by expand
+        leaves = _leaves(ndlqr, n, m, N, batch, 2100, shared=("A", "B"))
+        args = dict(leaves)
+        args["A"] = leaves["A"].expand(batch, N, n, n)
+        args["B"] = leaves["B"].expand(batch, N, n, m)
+        assert args["A"].stride(0) == 0
+        _compare(args, leaves, n, m, N, batch, gz)
+        # transposed A (a leaf that holds A^T: the argument is its transpose) and B sliced from a wider tensor
+        leaves = _leaves(ndlqr, n, m, N, batch, 2200)
+        leaves["AT"] = leaves.pop("A").detach().transpose(-1, -2).contiguous().requires_grad_(True)
+        leaves["Bw"] = torch.nn.functional.pad(leaves.pop("B").detach(), (0, 2)).requires_grad_(True)
+        args = {k: leaves[k] for k in ARGS if k in leaves}
+        args["A"] = leaves["AT"].transpose(-1, -2)
+        args["B"] = leaves["Bw"][..., :m]
+        assert not args["A"].is_contiguous() and not args["B"].is_contiguous()
+        _compare(args, leaves, n, m, N, batch, gz)
+        # an incoming gradient that is a column slice of a wider tensor
+        leaves = _leaves(ndlqr, n, m, N, batch, 2300)
+        wide = torch.randn((batch, nv(n, m, N) + 7), dtype=torch.float64, device="cuda")
+        gzs = wide[:, 3:3 + nv(n, m, N)]
+        assert not gzs.is_contiguous()
+        _compare(leaves, leaves, n, m, N, batch, gzs)
+    elif case == "horizons":
+        for n, m, N, batch, shared in ((6, 3, 16, 1, ()), (4, 2, 2, 3, ()), (4, 2, 2, 3, ("A", "B")),
+                                       (3, 2, 64, 2, ()), (3, 2, 64, 2, ("A", "Q"))):
+            gz = torch.randn((batch, nv(n, m, N)), dtype=torch.float64, device="cuda")
+            leaves = _leaves(ndlqr, n, m, N, batch, 2400, shared=shared)
+            _compare(leaves, leaves, n, m, N, batch, gz)
+    elif case == "large_shared_A":
+        n, m, N, batch = 144, 16, 4, 2
+        gz = torch.randn((batch, nv(n, m, N)), dtype=torch.float64, device="cuda")
+        leaves = _leaves(ndlqr, n, m, N, batch, 2500, shared=("A",))
+        _compare(leaves, leaves, n, m, N, batch, gz)
+    else:
+        raise ValueError(case)
