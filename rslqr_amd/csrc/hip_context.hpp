@@ -71,6 +71,22 @@ struct BufferSet {
   bool ready = false;      // allocated
 };
 
+// A slice of every solution: knots [knot0, knot0 + nknots), of each the blocks of `blocks` (NDLQR_SOLN_*), packed
+// [batch][nknots][width]. nknots == 0: the whole solution vectors, [batch][nvars].
+struct KnotSlice {
+  int knot0 = 0, nknots = 0;
+  unsigned blocks = 7u;
+  // a non-empty range of the N knots that names some block and sets no bit outside `allowed`
+  bool valid(int N, unsigned allowed) const {
+    return knot0 >= 0 && nknots > 0 && knot0 + nknots <= N && (blocks & 7u) && !(blocks & ~allowed);
+  }
+  size_t width(const ndlqr::Dims& u) const {
+    return ((blocks & 1u) ? u.n : 0) + ((blocks & 2u) ? u.n : 0) + ((blocks & 4u) ? u.m : 0);
+  }
+  // doubles per problem
+  size_t doubles(const ndlqr::Dims& u) const { return nknots > 0 ? width(u) * nknots : (size_t)u.rows * u.N - u.m; }
+};
+
 struct NdlqrHipCtx {
   ndlqr::Dims d = {};   // block sizes of the DEVICE layout (every kernel works on these)
   ndlqr::Dims du = {};  // the caller's block sizes: the same, or smaller when the problem runs zero-padded into the next
@@ -119,11 +135,10 @@ struct NdlqrHipCtx {
   // (uploads, device packing, an MPC step) writes the CURRENT set and bumps its generations; a solve or step that
   // lands on a set whose copy is behind in a part it does not replace copies that part over first (rhs_make_current).
   unsigned long long rhs_latest[4] = {};
-  // what an MPC step brings down (ndlqr_hip_set_step_selection): sel_nknots == 0: every solution, [batch][nvars]
-  int sel_knot0 = 0, sel_nknots = 0;
-  unsigned sel_blocks = 7u;  // NDLQR_SOLN_* bits; with NDLQR_SOLN_ONLY (8) a step computes nothing but the selected knots:
-  // the last launch of the back-substitution covers workgroups [apply_blk0, apply_blk0 + apply_nblk) of eight knots only
-  // (apply_nblk == 0: all; set by ndlqr_hip_step_async around its launches, honoured by the schedules that end in
+  KnotSlice sel;  // what an MPC step brings down (ndlqr_hip_set_step_selection)
+  // With NDLQR_SOLN_ONLY (8) in sel.blocks a step computes nothing but the selected knots: the last launch of the
+  // back-substitution covers workgroups [apply_blk0, apply_blk0 + apply_nblk) of eight knots only
+  // (apply_nblk == 0: all; set by ApplySlice around the launches of a step or a slice, honoured by the schedules that end in
   // rb_backsub, part of the key of the captured launch sequence), and z_partial says that the latest solution is such a
   // slice -- [z_blk0, z_blk0 + z_nblk) -- so that nothing else is handed out until the next complete solve
   int apply_blk0 = 0, apply_nblk = 0;

@@ -33,6 +33,22 @@ int ndlqr_hip_fail(const char* what, hipError_t e) {
   return NDLQR_ERR_NO_DEVICE;
 }
 static int fail(const char* what, hipError_t e) { return ndlqr_hip_fail(what, e); }
+// records the message for ndlqr_hip_last_error(), prints it, returns NDLQR_ERR_INVALID
+static int refuse(const std::string& msg) {
+  g_last_error = msg;
+  fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
+  return NDLQR_ERR_INVALID;
+}
+
+// Where a caller's array lives. A pointer the runtime does not know (an ordinary malloc'ed one is "invalid value" to older
+// runtimes) is pageable host memory.
+enum class Where { Pageable, Pinned, OwnDevice, OtherDevice };
+static Where where(const void* p, int device) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return Where::Pageable; }
+  if (a.type == hipMemoryTypeDevice) return a.device == device ? Where::OwnDevice : Where::OtherDevice;
+  return a.type == hipMemoryTypeHost ? Where::Pinned : Where::Pageable;
+}
 
 int ndlqr_hip_device_count(void) {
   int count = 0;
@@ -296,11 +312,9 @@ int ndlqr_hip_ensure_F(NdlqrHipCtx* c) {
   hipError_t e = hipMalloc(&c->F, bytes_F(c->d));
   if (e != hipSuccess) {
     c->F = nullptr;
-    g_last_error = "factor array does not fit on the device (" + std::to_string(bytes_F(c->d) >> 20) +
-                   " MiB): use the default fast mode without NDLQR_FLAG_KEEP_FACT, or a smaller batch";
-    fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
     (void)hipGetLastError();
-    return NDLQR_ERR_INVALID;
+    return refuse("factor array does not fit on the device (" + std::to_string(bytes_F(c->d) >> 20) +
+                  " MiB): use the default fast mode without NDLQR_FLAG_KEEP_FACT, or a smaller batch");
   }
   // Structural zeros of F are never written by the kernels; zero once so that the factor
   // download matches the reference's calloc'ed array (src/nddata.c:34).
@@ -371,6 +385,16 @@ static hipError_t other_stream_waits(NdlqrHipCtx* c) {
   return e != hipSuccess ? e : hipStreamWaitEvent(other, c->ev_inputs, 0);
 }
 
+// the current buffer set holds new A, B, Q, R and a whole new right-hand side: neither a cached factor array nor cached
+// records match them any more
+static void note_new_inputs(NdlqrHipCtx* c) {
+  rhs_written_cur(c, 0xFu);
+  next_solve_on_current_set(c);
+  c->fact_valid = false;
+  c->rec_complete = false;
+  c->inputs_replaced = true;
+}
+
 // staging of caller-layout data of a padded shape
 static int ensure_pad_stage(NdlqrHipCtx* c, size_t doubles) {
   if (doubles <= c->pad_stage_cap) return NDLQR_OK;
@@ -404,24 +428,14 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
     hipLaunchKernelGGL(ndlqr::pad_inputs_generic, dim3(d.N, count), dim3(128), 0, s.stream, u, d, p0, s0, s0 + uAB,
                        s0 + uAB + uQR, c->AB, c->QR, s.rhs);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    rhs_written_cur(c, 0xFu);
-    next_solve_on_current_set(c);
-    c->fact_valid = false;
-    c->rec_complete = false;
-    c->inputs_replaced = true;
-    return NDLQR_OK;
+  } else {
+    const size_t sAB = (size_t)d.N * d.n * d.w, sQR = (size_t)d.N * d.w, sz = (size_t)d.N * d.rows;
+    HIP_TRY(hipMemcpyAsync(c->AB + p0 * sAB, AB, sizeof(double) * sAB * count, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(c->QR + p0 * sQR, QR, sizeof(double) * sQR * count, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.rhs + p0 * sz, rhs, sizeof(double) * sz * count, hipMemcpyHostToDevice, s.stream));
   }
-  const size_t sAB = (size_t)d.N * d.n * d.w, sQR = (size_t)d.N * d.w, sz = (size_t)d.N * d.rows;
-  HIP_TRY(hipMemcpyAsync(c->AB + p0 * sAB, AB, sizeof(double) * sAB * count, hipMemcpyHostToDevice, s.stream));
-  HIP_TRY(hipMemcpyAsync(c->QR + p0 * sQR, QR, sizeof(double) * sQR * count, hipMemcpyHostToDevice, s.stream));
-  HIP_TRY(hipMemcpyAsync(s.rhs + p0 * sz, rhs, sizeof(double) * sz * count, hipMemcpyHostToDevice, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));  // the host staging buffers are reused by the caller
-  rhs_written_cur(c, 0xFu);
-  next_solve_on_current_set(c);
-  c->fact_valid = false;  // new A, B, Q, R: a cached factorisation no longer matches the inputs
-  c->rec_complete = false;
-  c->inputs_replaced = true;
+  note_new_inputs(c);
   return NDLQR_OK;
 }
 
@@ -444,23 +458,16 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
     hipLaunchKernelGGL(ndlqr::pack_flat_generic<1>, dim3(c->d.N, c->d.batch), dim3(128), 0, s.stream, c->du, c->d, A, B, Q, R,
                        q, r, d, x0, c->AB, c->QR, s.rhs);
   HIP_TRY(hipGetLastError());
-  rhs_written_cur(c, 0xFu);        // (the whole batch: nothing of the older copies is needed any more)
-  next_solve_on_current_set(c);
+  note_new_inputs(c);              // (the whole batch: nothing of the older copies is needed any more)
   HIP_TRY(other_stream_waits(c));  // the next solve may run on the other buffer set's stream
-  c->fact_valid = false;  // new A, B, Q, R: neither a cached factor array nor cached records match
-  c->rec_complete = false;
-  c->inputs_replaced = true;
   return NDLQR_OK;
 }
 
 int ndlqr_hip_device_pointers(NdlqrHipCtx* c, void** out5) {
   if (!c || !out5) return NDLQR_ERR_INVALID;
-  if (c->padded) {
-    g_last_error = "no raw device pointers for a block size that runs zero-padded (the arrays have another layout): "
-                   "use ndlqr_hip_pack_flat_device, or NDLQR_NO_PAD=1";
-    fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
-    return NDLQR_ERR_INVALID;
-  }
+  if (c->padded)
+    return refuse("no raw device pointers for a block size that runs zero-padded (the arrays have another layout): "
+                  "use ndlqr_hip_pack_flat_device, or NDLQR_NO_PAD=1");
   const int ferr = ndlqr_hip_ensure_F(c);  // the caller asks for the factor array: it has to exist
   if (ferr) return ferr;
   const int perr = ndlqr_hip_set_pipeline_depth(c, 1);  // the caller holds raw pointers: one buffer set from now on
@@ -914,10 +921,8 @@ static int prepare_solve(NdlqrHipCtx* c, bool* pipelined_out) {
       if (hipMalloc(&c->sep_scratch, bytes) != hipSuccess) {
         c->sep_scratch = nullptr;
         (void)hipGetLastError();
-        g_last_error = "global scratch of the large-block separator kernel does not fit on the device (" +
-                       std::to_string(bytes >> 20) + " MiB): use a smaller batch";
-        fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
-        return NDLQR_ERR_INVALID;
+        return refuse("global scratch of the large-block separator kernel does not fit on the device (" +
+                      std::to_string(bytes >> 20) + " MiB): use a smaller batch");
       }
     }
   }
@@ -1191,18 +1196,39 @@ static int ensure_xfer(NdlqrHipCtx* c) {
   return NDLQR_OK;
 }
 
-// address under which kernels of device `device` read `p` directly: pinned host memory (hipHostMalloc / hipHostRegister)
-// through its device-side view, memory of that device as it is; else (pageable memory, another device's) null
-static const double* pinned_device_view(const double* p, int device) {
-  if (!p) return nullptr;
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  if (a.type == hipMemoryTypeDevice) return a.device == device ? p : nullptr;
-  if (a.type != hipMemoryTypeHost) return nullptr;
-  void* dv = nullptr;
-  if (hipHostGetDevicePointer(&dv, const_cast<double*>(p), 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  return static_cast<const double*>(dv);
+// Packs the solutions of `count` problems from the blocks [count][N][2n+m] at z into dst: the whole vectors [count][nvars],
+// or the slice `sel` [count][nknots][width]. u: the caller's block sizes, d: the device layout.
+static hipError_t launch_pack(const ndlqr::Dims& u, const ndlqr::Dims& d, const KnotSlice& sel, const double* z, double* dst,
+                              hipStream_t st, unsigned count) {
+  if (sel.nknots > 0)
+    hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(sel.nknots, count), dim3(64), 0, st, u, d, sel.knot0, sel.nknots,
+                       sel.blocks & 7u, z, dst);
+  else
+    hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(u), count), dim3(256), 0, st, u, d, z,
+                       dst);
+  return hipGetLastError();
 }
+
+// ... into `dst`: packed in place where that is this device's memory (`own`), else packed into `stage` and copied out
+static int deliver(const ndlqr::Dims& u, const ndlqr::Dims& d, const KnotSlice& sel, const double* z, double* dst, bool own,
+                   double* stage, hipMemcpyKind kind, hipStream_t st, unsigned count) {
+  HIP_TRY(launch_pack(u, d, sel, z, own ? dst : stage, st, count));
+  if (!own) HIP_TRY(hipMemcpyAsync(dst, stage, sizeof(double) * sel.doubles(u) * count, kind, st));
+  return NDLQR_OK;
+}
+
+// While in scope, the last launch of the back-substitution runs only the workgroups (eight knots each) that hold the knots
+// of `sel` (launch_small.hpp: apply_grid / apply_dims; schedules without that launch compute everything); an empty slice,
+// or `on` false, leaves it whole.
+struct ApplySlice {
+  NdlqrHipCtx* c;
+  ApplySlice(NdlqrHipCtx* ctx, const KnotSlice& sel, bool on = true) : c(ctx) {
+    if (!on || sel.nknots <= 0) return;
+    c->apply_blk0 = sel.knot0 >> 3;
+    c->apply_nblk = ((sel.knot0 + sel.nknots - 1) >> 3) - c->apply_blk0 + 1;
+  }
+  ~ApplySlice() { c->apply_blk0 = c->apply_nblk = 0; }
+};
 
 static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z);  // below
 
@@ -1233,8 +1259,13 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   const double* view[4];
   double* stage = s.xfer;
   for (int k = 0; k < 4; ++k) {
-    view[k] = pinned_device_view(src[k], c->device);
-    if (src[k] && !view[k]) {
+    view[k] = src[k];  // null: a part this step does not replace; this device's memory: read as it is
+    const Where w = src[k] ? where(src[k], c->device) : Where::OwnDevice;
+    void* dv = nullptr;
+    if (w == Where::Pinned && hipHostGetDevicePointer(&dv, const_cast<double*>(src[k]), 0) == hipSuccess) {
+      view[k] = static_cast<const double*>(dv);  // the kernel reads it over the host link
+    } else if (w != Where::OwnDevice) {  // pageable, another device's, or pinned without a device-side view
+      if (w == Where::Pinned) (void)hipGetLastError();
       HIP_TRY(hipMemcpyAsync(stage, src[k], sizeof(double) * cnt[k], hipMemcpyDefault, st));
       view[k] = stage;
     }
@@ -1244,18 +1275,8 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
                      view[3], s.rhs);
   HIP_TRY(hipGetLastError());
   rhs_written_cur(c, written);
-  // NDLQR_SOLN_ONLY: nothing but the selected knots is wanted -- the last launch of the back-substitution runs the
-  // workgroups (eight knots each) that hold them (launch_small.hpp; schedules without that launch compute everything)
-  struct ApplyRange {
-    NdlqrHipCtx* c;
-    ApplyRange(NdlqrHipCtx* c_) : c(c_) {
-      if (c->sel_nknots > 0 && (c->sel_blocks & 8u)) {
-        c->apply_blk0 = c->sel_knot0 >> 3;
-        c->apply_nblk = ((c->sel_knot0 + c->sel_nknots - 1) >> 3) - c->apply_blk0 + 1;
-      }
-    }
-    ~ApplyRange() { c->apply_blk0 = c->apply_nblk = 0; }
-  } apply_range(c);
+  // NDLQR_SOLN_ONLY: nothing but the selected knots is wanted
+  const ApplySlice apply_slice(c, c->sel, (c->sel.blocks & NDLQR_SOLN_ONLY) != 0);
   // A step never changes A, B, Q, R. Under NDLQR_FLAG_KEEP_RECORDS the first step (or a solve before it) leaves the
   // compact records of the default schedule, and every further step is the right-hand-side re-solve on them (rb_forward,
   // rb_forward_top, rb_backsub: 0.46 instead of 0.59 ms per (12,4,256) x 1024) -- until new inputs are uploaded, which
@@ -1276,26 +1297,8 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   }
   // (the staging has been consumed by the pack kernel: it now takes the packed solutions -- all of them, or the slice
   //  chosen with ndlqr_hip_set_step_selection)
-  //  chosen with ndlqr_hip_set_step_selection); a `soln` in this device's memory is written by the pack kernel itself
-  double* packed = s.xfer;
-  {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, soln) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->device) packed = soln;
-    else (void)hipGetLastError();
-  }
-  if (c->sel_nknots > 0) {
-    const size_t width = ((c->sel_blocks & 1u) ? u.n : 0) + ((c->sel_blocks & 2u) ? u.n : 0) + ((c->sel_blocks & 4u) ? u.m : 0);
-    hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(c->sel_nknots, d.batch), dim3(64), 0, st, u, d, c->sel_knot0,
-                       c->sel_nknots, c->sel_blocks & 7u, (const double*)s.z, packed);
-    HIP_TRY(hipGetLastError());
-    if (packed != soln)
-      HIP_TRY(hipMemcpyAsync(soln, packed, sizeof(double) * width * c->sel_nknots * d.batch, hipMemcpyDefault, st));
-  } else {
-    hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(u), d.batch), dim3(256), 0, st, u, d, s.z, packed);
-    HIP_TRY(hipGetLastError());
-    const size_t nvars = (size_t)u.rows * u.N - u.m;
-    if (packed != soln) HIP_TRY(hipMemcpyAsync(soln, packed, sizeof(double) * nvars * d.batch, hipMemcpyDefault, st));
-  }
+  err = deliver(u, d, c->sel, s.z, soln, where(soln, c->device) == Where::OwnDevice, s.xfer, hipMemcpyDefault, st, d.batch);
+  if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   HIP_TRY(hipEventRecord(c->ev_step[c->step_count & 1u], st));
   c->step_set[c->step_count & 1u] = c->cur;
@@ -1310,10 +1313,9 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
 // solve of a loop that replaces A, B, Q, R as well (ndlqr_hip_pack_flat_device / uploads) and consumes u of knot 0.
 // Consecutive calls alternate between the buffer sets like ndlqr_hip_solve_async; complete after ndlqr_hip_synchronize.
 int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
-  if (!c || !out || knot0 < 0 || nknots <= 0 || knot0 + nknots > c->d.N || !(blocks & 7u) || (blocks & ~15u))
-    return NDLQR_ERR_INVALID;
+  const KnotSlice sel = {knot0, nknots, blocks};
+  if (!c || !out || !sel.valid(c->d.N, 15u)) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
   int err = prepare_solve(c, nullptr);
   if (err) return err;
   BufferSet& s = c->set[c->cur];
@@ -1323,22 +1325,11 @@ int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   if (err) return err;
   hipStream_t st = s.stream;
   HIP_TRY(hipEventRecord(s.ev_start, st));
-  c->apply_blk0 = knot0 >> 3;
-  c->apply_nblk = ((knot0 + nknots - 1) >> 3) - c->apply_blk0 + 1;
+  const ApplySlice apply_slice(c, sel);
   err = launch_solve(c);
-  c->apply_blk0 = c->apply_nblk = 0;
   if (err) return err;
-  double* packed = s.xfer;
-  {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, out) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->device) packed = out;
-    else (void)hipGetLastError();
-  }
-  const size_t width = ((blocks & 1u) ? u.n : 0) + ((blocks & 2u) ? u.n : 0) + ((blocks & 4u) ? u.m : 0);
-  hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(nknots, d.batch), dim3(64), 0, st, u, d, knot0, nknots, blocks & 7u,
-                     (const double*)s.z, packed);
-  HIP_TRY(hipGetLastError());
-  if (packed != out) HIP_TRY(hipMemcpyAsync(out, packed, sizeof(double) * width * nknots * d.batch, hipMemcpyDefault, st));
+  err = deliver(c->du, d, sel, s.z, out, where(out, c->device) == Where::OwnDevice, s.xfer, hipMemcpyDefault, st, d.batch);
+  if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   c->timing_pending = true;
   c->state_dirty = false;
@@ -1369,18 +1360,17 @@ int ndlqr_hip_synchronize_previous(NdlqrHipCtx* c) {
 // (src/solve.c:192-201); an MPC loop consumes u of knot 0.
 int ndlqr_hip_set_step_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks) {
   if (!c) return NDLQR_ERR_INVALID;
-  if (nknots == 0) { c->sel_knot0 = 0; c->sel_nknots = 0; c->sel_blocks = 7u; return NDLQR_OK; }
-  if (knot0 < 0 || nknots < 0 || knot0 + nknots > c->d.N || !(blocks & 7u) || (blocks & ~15u)) return NDLQR_ERR_INVALID;
-  c->sel_knot0 = knot0; c->sel_nknots = nknots; c->sel_blocks = blocks;
+  if (nknots == 0) { c->sel = KnotSlice(); return NDLQR_OK; }
+  const KnotSlice sel = {knot0, nknots, blocks};
+  if (!sel.valid(c->d.N, 15u)) return NDLQR_ERR_INVALID;
+  c->sel = sel;
   return NDLQR_OK;
 }
 
 // the same slice of the most recent solve, synchronously: out = [batch][nknots][width] doubles
 int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
-  if (!c || !out || knot0 < 0 || nknots <= 0 || knot0 + nknots > c->d.N || !(blocks & 7u) || (blocks & ~7u))
-    return NDLQR_ERR_INVALID;
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
+  const KnotSlice sel = {knot0, nknots, blocks};
+  if (!c || !out || !sel.valid(c->d.N, 7u)) return NDLQR_ERR_INVALID;
   BufferSet& s = c->set[c->cur];
   if (c->z_partial && (knot0 < 8 * c->z_blk0 || knot0 + nknots > 8 * (c->z_blk0 + c->z_nblk)))
     return need_full_solution(c, "ndlqr_hip_download_selection");
@@ -1388,11 +1378,9 @@ int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   HIP_TRY(sync_all(c));
   const int xerr = ensure_xfer(c);
   if (xerr) return xerr;
-  const size_t width = ((blocks & 1u) ? u.n : 0) + ((blocks & 2u) ? u.n : 0) + ((blocks & 4u) ? u.m : 0);
-  hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(nknots, d.batch), dim3(64), 0, s.stream, u, d, knot0, nknots,
-                     blocks, (const double*)c->set[c->latest].z, s.xfer);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, s.xfer, sizeof(double) * width * nknots * d.batch, hipMemcpyDeviceToHost, s.stream));
+  const int derr =
+      deliver(c->du, c->d, sel, c->set[c->latest].z, out, false, s.xfer, hipMemcpyDeviceToHost, s.stream, c->d.batch);
+  if (derr) return derr;
   HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }
@@ -1502,14 +1490,20 @@ static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z)
   return true;
 }
 
+// the re-solve on what the last factorisation kept: the records where they have one, else the factor array; refused with
+// `refusal` when there are records only and this shape / horizon has no record-based re-solve
+static int launch_resolve(NdlqrHipCtx* c, const double* rhs, double* z, const char* refusal) {
+  if (try_launch_rhs_records(c, rhs, z)) return NDLQR_OK;
+  if (!c->fact_valid) return refuse(refusal);
+  if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c, rhs, z); else launch_rhs_sweep<false>(c, rhs, z);
+  return NDLQR_OK;
+}
+
 int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
   if (!c) return NDLQR_ERR_INVALID;
-  if (!c->fact_valid && !c->rec_complete) {
-    g_last_error = "rhs-only solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or "
-                   "NDLQR_FLAG_KEEP_RECORDS (cached factorisation)";
-    fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
-    return NDLQR_ERR_INVALID;
-  }
+  if (!c->fact_valid && !c->rec_complete)
+    return refuse("rhs-only solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or "
+                  "NDLQR_FLAG_KEEP_RECORDS (cached factorisation)");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
   c->cur = 0;  // cached records / factors live in the primary set
@@ -1519,14 +1513,8 @@ int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
     if (merr) return merr;
   }
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  if (!try_launch_rhs_records(c, s.rhs, s.z)) {
-    if (!c->fact_valid) {  // records only, but this shape / horizon has no record-based re-solve
-      g_last_error = "rhs-only solve: this configuration needs NDLQR_FLAG_KEEP_FACT";
-      fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
-      return NDLQR_ERR_INVALID;
-    }
-    if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c, s.rhs, s.z); else launch_rhs_sweep<false>(c, s.rhs, s.z);
-  }
+  const int rerr = launch_resolve(c, s.rhs, s.z, "rhs-only solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
+  if (rerr) return rerr;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   c->timing_pending = true;
@@ -1535,21 +1523,8 @@ int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
 }
 
 // ------------------------------------------------------------------------------ adjoint solve, parameter gradients
-
-// where `p` lives: 1 this device's memory (kernels take it as it is), 0 host memory, pinned or pageable (staged through
-// HBM), -1 another device's memory (refused: the caller has the wrong device, and a silent copy would hide it)
-static int locate(const void* p, int device) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  if (a.type == hipMemoryTypeDevice) return a.device == device ? 1 : -1;
-  return 0;
-}
-
-static int refuse(const std::string& msg) {
-  g_last_error = msg;
-  fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
-  return NDLQR_ERR_INVALID;
-}
+// The caller's arrays: this device's memory is taken as it is, host memory (pinned or pageable) is staged through HBM, and
+// another device's memory is refused (the caller has the wrong device, and a silent copy would hide it).
 
 static int ensure_grad_stage(NdlqrHipCtx* c, size_t doubles) {
   if (doubles <= c->grad_stage_cap) return NDLQR_OK;
@@ -1592,8 +1567,8 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
-  const int where = locate(g, c->device);
-  if (where < 0) return refuse("ndlqr_hip_solve_adjoint: g lies in the memory of another device than the solver's");
+  const Where wg = where(g, c->device);
+  if (wg == Where::OtherDevice) return refuse("ndlqr_hip_solve_adjoint: g lies in the memory of another device than the solver's");
   HIP_TRY(sync_all(c));
   c->cur = 0;  // cached records / factors live in the primary set
   BufferSet& s = c->set[0];
@@ -1605,7 +1580,7 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
     HIP_TRY(hipMemsetAsync(c->adj_z, 0, bytes_z(d), s.stream));  // (entries a re-solve does not write: the pad rows)
   }
   const double* gd = g;
-  if (where == 0) {
+  if (wg != Where::OwnDevice) {
     const int serr = ensure_grad_stage(c, nvars * d.batch);
     if (serr) return serr;
     HIP_TRY(hipMemcpyAsync(c->grad_stage, g, sizeof(double) * nvars * d.batch, hipMemcpyDefault, s.stream));
@@ -1615,12 +1590,9 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, gd, c->adj_rhs);
   HIP_TRY(hipGetLastError());
   HIP_TRY(adjoint_scratch(c, false));
-  if (!try_launch_rhs_records(c, c->adj_rhs, c->adj_z)) {
-    if (!c->fact_valid)  // records only, but this shape / horizon has no record-based re-solve
-      return refuse("adjoint solve: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
-    if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c, c->adj_rhs, c->adj_z);
-    else launch_rhs_sweep<false>(c, c->adj_rhs, c->adj_z);
-  }
+  const int rerr = launch_resolve(c, c->adj_rhs, c->adj_z,
+                                  "adjoint solve: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
+  if (rerr) return rerr;
   HIP_TRY(hipGetLastError());
   HIP_TRY(adjoint_scratch(c, true));
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
@@ -1647,14 +1619,12 @@ int ndlqr_hip_download_adjoint(NdlqrHipCtx* c, double* w) {
   const int aerr = need_adjoint(c, "ndlqr_hip_download_adjoint");
   if (aerr) return aerr;
   HIP_TRY(hipSetDevice(c->device));
-  const int where = locate(w, c->device);
-  if (where < 0) return refuse("ndlqr_hip_download_adjoint: w lies in the memory of another device than the solver's");
-  if (where == 0) return download_packed(c, c->adj_z, 0, c->d.batch, w);
+  const Where ww = where(w, c->device);
+  if (ww == Where::OtherDevice) return refuse("ndlqr_hip_download_adjoint: w lies in the memory of another device than the solver's");
+  if (ww != Where::OwnDevice) return download_packed(c, c->adj_z, 0, c->d.batch, w);
   const BufferSet& s = c->set[0];
   HIP_TRY(sync_all(c));
-  hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(c->du), c->d.batch), dim3(256), 0,
-                     s.stream, c->du, c->d, (const double*)c->adj_z, w);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->adj_z, w, s.stream, c->d.batch));
   HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }
@@ -1668,18 +1638,19 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
   double* user[ndlqr::GRAD_COUNT] = {gA, gB, gQ, gR, gq, gr, gd, gx0};
-  int where[ndlqr::GRAD_COUNT] = {};
+  bool own[ndlqr::GRAD_COUNT] = {};  // this device's memory: written by the kernels as it is
   size_t size[ndlqr::GRAD_COUNT] = {};
   size_t stage = 0, total = 0;
   ndlqr::GradOut out = {};
   for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) {
     if (!user[o]) continue;
-    where[o] = locate(user[o], c->device);
-    if (where[o] < 0) return refuse("ndlqr_hip_gradients: an output lies in the memory of another device than the solver's");
+    const Where wo = where(user[o], c->device);
+    if (wo == Where::OtherDevice) return refuse("ndlqr_hip_gradients: an output lies in the memory of another device than the solver's");
     const bool summed = (sum_mask >> o) & 1u;
     const size_t per = o == ndlqr::GRAD_x0 ? (size_t)u.n : (size_t)u.N * ndlqr::grad_width(u, o);
     size[o] = summed ? per : per * d.batch;
-    if (where[o] == 0) stage += size[o];
+    own[o] = wo == Where::OwnDevice;
+    if (!own[o]) stage += size[o];
     if (summed) { out.off[o] = total; total += per; }
   }
   out.sum = sum_mask;
@@ -1722,8 +1693,8 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
   double* at = c->grad_stage;
   for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) {
     if (!user[o]) continue;
-    out.p[o] = where[o] == 1 ? user[o] : at;
-    if (where[o] == 0) at += size[o];
+    out.p[o] = own[o] ? user[o] : at;
+    if (!own[o]) at += size[o];
   }
   double* part = npart ? at : nullptr;
   const double* z = c->set[c->latest].z;
@@ -1747,7 +1718,7 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
   }
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   for (int o = 0; o < ndlqr::GRAD_COUNT; ++o)
-    if (user[o] && where[o] == 0)
+    if (user[o] && !own[o])
       HIP_TRY(hipMemcpyAsync(user[o], out.p[o], sizeof(double) * size[o], hipMemcpyDefault, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   float ms = 0.0f;
@@ -1767,20 +1738,17 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
 // [nrhs][batch][nknots][width] -- and only the workgroups of the last launch that hold them run (the rest of a vector is
 // never produced: nothing keeps these solutions on the device anyway)
 static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const double* r, const double* dd, const double* x0,
-                           int knot0, int nknots, unsigned blocks, double* soln) {
+                           const KnotSlice& sel, double* soln) {
   if (!c || nrhs <= 0 || !q || !r || !dd || !x0 || !soln) return NDLQR_ERR_INVALID;
-  if (nknots < 0 || knot0 < 0 || knot0 + nknots > c->d.N || (nknots > 0 && (!(blocks & 7u) || (blocks & ~15u)))) return NDLQR_ERR_INVALID;
+  if (sel.nknots > 0 && !sel.valid(c->d.N, 15u)) return NDLQR_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
   c->cur = 0;
   BufferSet& st = c->set[0];
   const SmallInstance* inst = pick_small(c);
-  if (!inst || !c->rec_complete || !c->rec_compact) {
-    g_last_error = "multiple right-hand sides need the compact records of a solve with NDLQR_FLAG_KEEP_RECORDS on a "
-                   "size-specialised shape (level-per-launch schedule: batch x N / 4 > 2048, or NDLQR_TREE=0)";
-    fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
-    return NDLQR_ERR_INVALID;
-  }
+  if (!inst || !c->rec_complete || !c->rec_compact)
+    return refuse("multiple right-hand sides need the compact records of a solve with NDLQR_FLAG_KEEP_RECORDS on a "
+                  "size-specialised shape (level-per-launch schedule: batch x N / 4 > 2048, or NDLQR_TREE=0)");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   const size_t nvars = (size_t)u.rows * u.N - u.m;
@@ -1831,29 +1799,16 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
                        (const double*)(in + nq), (const double*)(in + nq + nr), (const double*)(in + 2 * nq + nr), c->multi_rhs);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.ev_start, st.stream));
-    if (nknots > 0) { c->apply_blk0 = knot0 >> 3; c->apply_nblk = ((knot0 + nknots - 1) >> 3) - c->apply_blk0 + 1; }
-    const bool launched = inst->multi(c, (int)count, c->multi_rhs, c->multi_zsep, c->multi_fsum, c->multi_ytop, c->multi_z);
-    c->apply_blk0 = c->apply_nblk = 0;
-    if (!launched) {
+    const ApplySlice apply_slice(c, sel);
+    if (!inst->multi(c, (int)count, c->multi_rhs, c->multi_zsep, c->multi_fsum, c->multi_ytop, c->multi_z)) {
       g_last_error = "multiple right-hand sides: this shape / horizon has no such form";
       return NDLQR_ERR_INVALID;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.ev_stop, st.stream));
-    if (nknots > 0) {
-      const size_t width = ((blocks & 1u) ? u.n : 0) + ((blocks & 2u) ? u.n : 0) + ((blocks & 4u) ? u.m : 0);
-      hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(nknots, (unsigned)count), dim3(64), 0, st.stream, uc, dc, knot0,
-                         nknots, blocks & 7u, (const double*)c->multi_z, c->multi_out);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(soln + s0 * per_set * nknots * width, c->multi_out, sizeof(double) * count * nknots * width,
-                             hipMemcpyDeviceToHost, st.stream));
-    } else {
-      hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(uc), (unsigned)count), dim3(256), 0, st.stream, uc, dc,
-                         (const double*)c->multi_z, c->multi_out);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(soln + s0 * per_set * nvars, c->multi_out, sizeof(double) * count * nvars, hipMemcpyDeviceToHost,
-                             st.stream));
-    }
+    const int derr = deliver(uc, dc, sel, c->multi_z, soln + s0 * per_set * sel.doubles(u), false, c->multi_out,
+                             hipMemcpyDeviceToHost, st.stream, (unsigned)count);
+    if (derr) return derr;
     HIP_TRY(hipStreamSynchronize(st.stream));
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, st.ev_start, st.ev_stop) == hipSuccess) total_ms += ms;
@@ -1864,12 +1819,12 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
 }
 int ndlqr_hip_solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const double* r, const double* dd,
                               const double* x0, double* soln) {
-  return solve_multi_rhs(c, nrhs, q, r, dd, x0, 0, 0, 7u, soln);
+  return solve_multi_rhs(c, nrhs, q, r, dd, x0, KnotSlice(), soln);
 }
 int ndlqr_hip_solve_multi_rhs_slices(NdlqrHipCtx* c, int nrhs, const double* q, const double* r, const double* dd,
                                      const double* x0, int knot0, int nknots, unsigned blocks, double* out) {
   if (nknots <= 0) return NDLQR_ERR_INVALID;
-  return solve_multi_rhs(c, nrhs, q, r, dd, x0, knot0, nknots, blocks, out);
+  return solve_multi_rhs(c, nrhs, q, r, dd, x0, KnotSlice{knot0, nknots, blocks}, out);
 }
 
 int ndlqr_hip_synchronize(NdlqrHipCtx* c) {
@@ -1924,16 +1879,6 @@ int ndlqr_hip_profile_reset(NdlqrHipCtx* c) {
 
 // ------------------------------------------------------------------------------ downloads
 
-// is `p` pinned (hipHostMalloc / hipHostRegister) host memory?
-static bool host_ptr_is_pinned(const void* p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();  // an ordinary malloc'ed pointer is "invalid value" to older runtimes
-    return false;
-  }
-  return a.type == hipMemoryTypeHost;
-}
-
 // Solutions of problems [p0, p0 + count) as [count][nvars]: a pack kernel gathers them into the transfer staging
 // (the device layout carries the unused trailing input slot of every problem, src/solver.c:64), then ONE contiguous
 // copy brings them down -- straight into `soln` when that is pinned memory (ndlqr_hip_host_alloc), through two
@@ -1952,13 +1897,11 @@ static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count
   HIP_TRY(sync_all(c));
   const int xerr = ensure_xfer(c);
   if (xerr) return xerr;
-  const double* zl = zsrc;
   const size_t nvars = (size_t)c->du.rows * d.N - c->du.m, pitch = (size_t)d.rows * d.N;
   hipStream_t st = s.stream;
-  hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(c->du), count), dim3(256), 0, st, c->du, d, zl + p0 * pitch, s.xfer);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_pack(c->du, d, KnotSlice(), zsrc + p0 * pitch, s.xfer, st, count));
   const size_t total = nvars * count;
-  if (host_ptr_is_pinned(soln)) {
+  if (where(soln, c->device) == Where::Pinned) {
     HIP_TRY(hipMemcpyAsync(soln, s.xfer, sizeof(double) * total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return NDLQR_OK;
@@ -2002,9 +1945,7 @@ int ndlqr_hip_pack_solutions_device(NdlqrHipCtx* c, double* dst) {
   const ndlqr::Dims& d = c->d;
   HIP_TRY(hipSetDevice(c->device));
   // on the stream of the latest solve: ordered behind it, asynchronous for the caller
-  hipLaunchKernelGGL(ndlqr::pack_solutions_generic, dim3(ndlqr::pack_solutions_chunks(c->du), d.batch), dim3(256), 0,
-                     c->set[c->latest].stream, c->du, d, c->set[c->latest].z, dst);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_pack(c->du, d, KnotSlice(), c->set[c->latest].z, dst, c->set[c->latest].stream, d.batch));
   return NDLQR_OK;
 }
 
@@ -2053,11 +1994,7 @@ int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
 
 int ndlqr_hip_download_factors(NdlqrHipCtx* c, int p, double* fact) {
   if (!c || !fact || p < 0 || p >= c->d.batch) return NDLQR_ERR_INVALID;
-  if (!c->fact_valid) {
-    g_last_error = "factor download needs NDLQR_FLAG_KEEP_FACT set before the solve";
-    fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
-    return NDLQR_ERR_INVALID;
-  }
+  if (!c->fact_valid) return refuse("factor download needs NDLQR_FLAG_KEEP_FACT set before the solve");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
