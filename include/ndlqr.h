@@ -502,6 +502,49 @@ int ndlqr_SolveBatchAdjoint(NdLqrBatchSolver* bs, const double* g);  /* K w = g 
 int ndlqr_CopyBatchAdjoint(NdLqrBatchSolver* bs, double* w);         /* [batch][nvars]; returns nvars */
 int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR,
                          double* gq, double* gr, double* gd, double* gx0);
+/* additive: box-constrained batch solve (MPC with actuator and state limits). For every problem of the batch, the resident
+ * LQR problem plus the bounds xlo_k <= x_k <= xhi_k (k = 1 .. N-1) and ulo_k <= u_k <= uhi_k (k = 0 .. N-2), solved by
+ * scaled ADMM with over-relaxation and a fixed penalty rho (OSQP-style) on the kept factorisation:
+ *   ndlqr_BatchSetBounds: xlo, xhi [batch][N][n], ulo, uhi [batch][N][m] in the flat layout of ndlqr_InitializeBatchFlat
+ *   ([N][..], one set for every problem, with NDLQR_BOUNDS_SHARED); NULL = unbounded; entries may be +-INFINITY. Bounds on
+ *   x of knot 0 (x0 is fixed) and on u of the last knot (it has no input) are ignored. lo > hi (or NaN) for an entry that
+ *   is used: NDLQR_ERR_INVALID, and the previous bounds stay. Host, pinned or the solver's device memory.
+ *   ndlqr_SolveBatchBoxConstrained: factors Q + rho M_x, R + rho M_u (M: the bounded entries) once -- or not at all while rho,
+ *   the finite / infinite pattern of the bounds and A, B, Q, R are those of the previous constrained solve: an MPC loop of
+ *   ndlqr_BatchSetRhsFlat + this call pays only the iterations -- then iterates one right-hand-side re-solve and one
+ *   element-wise update kernel per iteration. iters[p], status[p] (each may be NULL; host or the solver's device memory):
+ *   iterations taken; 1 = converged, 2 = max_iter reached, the last iterate is returned (not an error; an infeasible
+ *   problem ends so -- there is no infeasibility certificate), 3 = the iterate is not finite (NaN or inf in the problem's
+ *   data): stopped, not a solution. A non-positive pivot of the shifted factorisation (Q or R <= 0 on an unbounded entry,
+ *   as ndlqr_SolveBatch refuses it) returns NDLQR_ERR_NOT_SPD before any iteration; after that, and after any other
+ *   error once the factorisation ran, the solution getters refuse until the next solve. A warm start keeps v, y of the
+ *   entries bounded now (y of the others is zeroed). Blocking. Converged when, over the bounded entries of the problem,
+ *       ||z - v||_inf <= eps_abs + eps_rel max(||z||_inf, ||v||_inf)   and   rho ||v - v_prev||_inf <= eps_abs + eps_rel ||rho y||_inf
+ *   (z: the re-solve, v: its projection onto the bounds, y: the scaled dual); a converged problem is frozen.
+ *   The resident solution becomes the constrained one: ndlqr_CopyBatchSolution(s), slices and the device pack hand back
+ *   [lambda, x, u] with x, u the projected iterate (the bounds hold exactly) and lambda from the last re-solve.
+ *   ndlqr_BatchKktResiduals keeps its meaning -- the unconstrained KKT system --, so after a constrained solve it measures
+ *   about ||mu||. The resident A, B, Q, R, q, r, d, x0 are unchanged, but the kept records / factors are those of the
+ *   shifted matrix: ndlqr_SolveBatchRhsOnly, the multi-rhs solves and the adjoint return NDLQR_ERR_INVALID until the next
+ *   ndlqr_SolveBatch. Reach: wherever a kept factorisation exists (NDLQR_FLAG_KEEP_RECORDS is or-ed in for its own
+ *   factorisation in fast mode, NDLQR_FLAG_KEEP_FACT in strict mode), padded shapes included; strict mode is
+ *   bit-reproducible (DESIGN.md section 3.9 gives the operation order).
+ *   ndlqr_CopyBatchBoundMultipliers: mu = rho y, mu_x [batch][N][n], mu_u [batch][N][m] (either may be NULL): >= 0 where the
+ *   upper bound is active, <= 0 at the lower one, 0 inside; z solves the unconstrained problem with q + mu_x, r + mu_u. */
+typedef struct {
+  double rho;       /* penalty; 0 -> 0.1 */
+  double alpha;     /* over-relaxation in (0, 2); 0 -> 1.6 */
+  double eps_abs;   /* 0 -> 1e-6 */
+  double eps_rel;   /* 0 -> 1e-6 */
+  int max_iter;     /* 0 -> 4000 */
+  int check_every;  /* host looks at the convergence count every this many iterations; 0 -> 10 */
+  int warm_start;   /* start from v, y of the previous constrained solve (same bounds pattern) */
+} NdLqrBoxSettings; /* zero-initialised = all defaults; NULL = all defaults */
+#define NDLQR_BOUNDS_SHARED 1u /* bounds arrays are [N][..], one set for every problem */
+int ndlqr_BatchSetBounds(NdLqrBatchSolver* bs, unsigned flags, const double* xlo, const double* xhi, const double* ulo,
+                         const double* uhi);
+int ndlqr_SolveBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status);
+int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u);
 void* ndlqr_BatchDeviceContext(NdLqrBatchSolver* bs);      /* NdlqrHipCtx* (ndlqr_hip.h) */
 
 /* Seeded synthetic problem generator (host, bit-reproducible). */

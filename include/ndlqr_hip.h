@@ -103,6 +103,18 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* ctx, const double* g);
 int ndlqr_hip_download_adjoint(NdlqrHipCtx* ctx, double* w); /* [batch][nvars]: host, pinned or this device's memory */
 int ndlqr_hip_gradients(NdlqrHipCtx* ctx, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR, double* gq,
                         double* gr, double* gd, double* gx0);
+/* Box-constrained solve by scaled ADMM on the kept factorisation (ndlqr.h: ndlqr_BatchSetBounds,
+ * ndlqr_SolveBatchBoxConstrained, ndlqr_CopyBatchBoundMultipliers). Bounds in the flat layout,
+ * [batch][N][n] / [batch][N][m], or [N][..] once for every problem when `shared`; NULL = unbounded; host, pinned or this
+ * device's memory. ndlqr_hip_solve_box takes the resolved settings (no zero defaults here) and blocks; iters / status
+ * [batch] may be NULL. Multipliers mu = rho y in the flat layout. ndlqr_hip_factor_count: factorisations launched by
+ * this context so far (tests: a constrained solve that reuses the remembered shifted factorisation launches none). */
+int ndlqr_hip_set_bounds(NdlqrHipCtx* ctx, int shared, const double* xlo, const double* xhi, const double* ulo,
+                         const double* uhi);
+int ndlqr_hip_solve_box(NdlqrHipCtx* ctx, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
+                        int check_every, int warm_start, int* iters, int* status);
+int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* ctx, double* mu_x, double* mu_u);
+unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* ctx);
 /* Several right-hand sides per problem against one kept factorisation each (the reference's NdData holds a single
  * right-hand side, src/nddata.h:70-75): nrhs sets of right-hand sides for the whole batch, flat HOST arrays in the layout of
  * ndlqr_BatchSetRhsFlat with a leading [nrhs] -- q, d [nrhs][batch][N][n], r [nrhs][batch][N][m], x0 [nrhs][batch][n] --,

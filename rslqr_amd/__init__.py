@@ -7,6 +7,7 @@ C API, plus a numpy-friendly ``BatchSolver``; ``rslqr_amd.autograd`` puts the so
 ``torch.autograd.Function`` (adjoint solve and parameter gradients on the device).
 """
 from .api import (  # noqa: F401
+    BOUNDS_SHARED,
     BatchSolver,
     DeviceArray,
     FLAG_GENERIC,
@@ -28,6 +29,7 @@ from .api import (  # noqa: F401
     Matrix,
     NdData,
     NdFactor,
+    NdLqrBoxSettings,
     NdLqrSolver,
     SOLN_INPUT,
     SOLN_ONLY,

@@ -111,6 +111,13 @@ class NdLqrSolver(C.Structure):
                 ("device_split", NdLqrProfile), ("mirror_fact", C.c_int)]
 
 
+class NdLqrBoxSettings(C.Structure):
+    _fields_ = [("rho", C.c_double), ("alpha", C.c_double), ("eps_abs", C.c_double), ("eps_rel", C.c_double),
+                ("max_iter", C.c_int), ("check_every", C.c_int), ("warm_start", C.c_int)]
+
+
+BOUNDS_SHARED = 1
+
 _LIB = None
 
 
@@ -258,6 +265,10 @@ def lib():
     proto("ndlqr_CopyBatchAdjoint", ci, vp, dp)
     proto("ndlqr_BatchGradients", ci, vp, C.c_uint, dp, dp, dp, dp, dp, dp, dp, dp)
     proto("ndlqr_BatchDeviceContext", vp, vp)
+    proto("ndlqr_BatchSetBounds", ci, vp, C.c_uint, dp, dp, dp, dp)
+    proto("ndlqr_SolveBatchBoxConstrained", ci, vp, C.POINTER(NdLqrBoxSettings), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_CopyBatchBoundMultipliers", ci, vp, dp, dp)
+    proto("ndlqr_hip_factor_count", C.c_ulonglong, vp)
     # shim bits used by the benchmark
     proto("ndlqr_hip_set_stream", ci, vp, vp)
     proto("ndlqr_hip_get_stream", vp, vp)
@@ -598,6 +609,58 @@ class BatchSolver:
         if err:
             raise RuntimeError("ndlqr_BatchGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
+
+    # ---- box-constrained solve (include/ndlqr.h: ndlqr_BatchSetBounds, ndlqr_SolveBatchBoxConstrained)
+    def set_bounds(self, xlo=None, xhi=None, ulo=None, uhi=None):
+        """ndlqr_BatchSetBounds. Each bound is None (unbounded), a numpy array of shape (n,) / (m,), (N, n) / (N, m) --
+        one set for every problem, sent as NDLQR_BOUNDS_SHARED -- or (batch, N, n) / (batch, N, m), or a DeviceArray of
+        batch * N * n (m) doubles. Entries may be +-inf. Raises on a refusal (lo > hi)."""
+        n, m, N, B = self.n, self.m, self.N, self.batch
+        given = [(a, k) for a, k in ((xlo, n), (xhi, n), (ulo, m), (uhi, m))]
+        host = [(a if a is None or hasattr(a, "ptr") else np.asarray(a, dtype=np.float64)) for a, _ in given]
+        shared = all(a is None or (not hasattr(a, "ptr") and a.ndim <= 2) for a in host)
+        ptrs, keep = [], []
+        for a, (_, k) in zip(host, given):
+            if a is not None and not hasattr(a, "ptr"):
+                if a.shape not in ((k,), (N, k), (B, N, k)):
+                    raise ValueError("bounds of shape %s: expected (%d,), (%d, %d) or (%d, %d, %d)" % (a.shape, k, N, k, B, N, k))
+                a = np.ascontiguousarray(np.broadcast_to(a, (N, k) if shared else (B, N, k)))
+                keep.append(a)
+            ptrs.append(None if a is None else _any_ptr(a, (1 if shared else B) * N * k))
+        err = self.L.ndlqr_BatchSetBounds(self.h, BOUNDS_SHARED if shared else 0, *ptrs)
+        if err:
+            raise RuntimeError("ndlqr_BatchSetBounds failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+
+    def solve_box(self, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0, warm_start=False):
+        """ndlqr_SolveBatchBoxConstrained (0 = the library's default for every setting). Returns (iters, status) as numpy
+        int arrays [batch]; status 1 = converged, 2 = max_iter reached. Raises on a nonzero return."""
+        st = NdLqrBoxSettings(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0)
+        iters = np.zeros(self.batch, dtype=np.int32)
+        status = np.zeros(self.batch, dtype=np.int32)
+        err = self.L.ndlqr_SolveBatchBoxConstrained(self.h, C.byref(st), iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                                    status.ctypes.data_as(C.POINTER(C.c_int)))
+        if err:
+            raise RuntimeError("ndlqr_SolveBatchBoxConstrained failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return iters, status
+
+    def bound_multipliers(self, mu_x=None, mu_u=None):
+        """ndlqr_CopyBatchBoundMultipliers: (mu_x [batch, N, n], mu_u [batch, N, m]) = rho y of the last constrained solve;
+        `mu_x`, `mu_u`: destinations (numpy arrays or DeviceArrays)."""
+        n, m, N, B = self.n, self.m, self.N, self.batch
+        if mu_x is None:
+            mu_x = np.zeros((B, N, n))
+        if mu_u is None:
+            mu_u = np.zeros((B, N, m))
+        err = self.L.ndlqr_CopyBatchBoundMultipliers(self.h, _any_ptr(mu_x, B * N * n), _any_ptr(mu_u, B * N * m))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchBoundMultipliers failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return mu_x, mu_u
+
+    def factor_count(self):
+        """factorisations this solver has launched (ndlqr_hip_factor_count; tests of the kept shifted factorisation)"""
+        return int(self.L.ndlqr_hip_factor_count(self.ctx))
 
     def solutions_to_device(self, device_ptr):
         """[batch][nvars] packed solutions into device memory (asynchronous on the solver's stream)."""

@@ -359,6 +359,28 @@ int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, do
   if (!bs) return NDLQR_ERR_INVALID;
   return ndlqr_hip_gradients(bs->ctx, sum_mask, gA, gB, gQ, gR, gq, gr, gd, gx0);
 }
+int ndlqr_BatchSetBounds(NdLqrBatchSolver* bs, unsigned flags, const double* xlo, const double* xhi, const double* ulo,
+                         const double* uhi) {
+  if (!bs || (flags & ~NDLQR_BOUNDS_SHARED)) return NDLQR_ERR_INVALID;
+  /* (lo <= hi is checked on the device, where the bounds may already live) */
+  return ndlqr_hip_set_bounds(bs->ctx, (flags & NDLQR_BOUNDS_SHARED) ? 1 : 0, xlo, xhi, ulo, uhi);
+}
+int ndlqr_SolveBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status) {
+  NdLqrBoxSettings z;
+  if (!bs) return NDLQR_ERR_INVALID;
+  memset(&z, 0, sizeof(z));
+  if (s) z = *s;
+  if (z.rho < 0.0 || z.alpha < 0.0 || z.alpha >= 2.0 || z.eps_abs < 0.0 || z.eps_rel < 0.0 || z.max_iter < 0 ||
+      z.check_every < 0)
+    return NDLQR_ERR_INVALID;
+  return ndlqr_hip_solve_box(bs->ctx, z.rho > 0.0 ? z.rho : 0.1, z.alpha > 0.0 ? z.alpha : 1.6, z.eps_abs > 0.0 ? z.eps_abs : 1e-6,
+                             z.eps_rel > 0.0 ? z.eps_rel : 1e-6, z.max_iter > 0 ? z.max_iter : 4000,
+                             z.check_every > 0 ? z.check_every : 10, z.warm_start != 0, iters, status);
+}
+int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u) {
+  if (!bs || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_bound_multipliers(bs->ctx, mu_x, mu_u);
+}
 int ndlqr_CopyBatchFactors(NdLqrBatchSolver* bs, int p, double* fact) {
   if (!bs || !fact || p < 0 || p >= bs->batch) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_factors(bs->ctx, p, fact);

@@ -143,6 +143,7 @@ struct NdlqrHipCtx {
   // slice -- [z_blk0, z_blk0 + z_nblk) -- so that nothing else is handed out until the next complete solve
   int apply_blk0 = 0, apply_nblk = 0;
   bool z_partial = false;
+  bool z_invalid = false;  // the resident solution is not one (a constrained solve failed after its factorisation)
   int z_blk0 = 0, z_nblk = 0;
   int step_set[2] = {};  // buffer set of the steps behind ev_step[0 / 1]
   // One-shot solve of a small batch from / into pinned host staging (ndlqr_hip_solve_staged; the drop-in ndlqr_Solve):
@@ -164,6 +165,25 @@ struct NdlqrHipCtx {
   size_t grad_stage_cap = 0;     // doubles
   unsigned long long soln_gen = 0, adj_gen = 0;
   bool inputs_replaced = false;  // new A, B, Q, R since the last solve
+  // Box-constrained solve by ADMM (ndlqr_hip_set_bounds / ndlqr_hip_solve_box, kernels_box.hpp; buffers allocated on first
+  // use). Bounds lo | hi in the device layout [batch][N][n+m] ([N][n+m] when shared: box_bstride 0) and their bounded
+  // pattern; v, y and two ADMM right-hand sides (ping-pong) and the re-solve's z; per problem status, iterations and
+  // residuals; box_word: running count | lo > hi | pattern changed. The shifted factorisation is remembered (box_fact)
+  // with what the plain API's state flags were after it, so that the next constrained solve may skip factoring.
+  double *box_lo = nullptr, *box_hi = nullptr, *box_v = nullptr, *box_y = nullptr, *box_z = nullptr, *box_qr_save = nullptr;
+  double* box_rhs[2] = {};
+  double* box_resid = nullptr;
+  unsigned char* box_mask = nullptr;
+  int *box_status = nullptr, *box_iters = nullptr, *box_word = nullptr;
+  int* h_box_word = nullptr;   // pinned
+  bool box_shared = false, box_have_bounds = false, box_have_vy = false;
+  size_t box_bstride = 0;      // doubles between the bounds of consecutive problems (0: shared)
+  bool box_fact = false;       // the kept records / factors are those of QR + rho M of the current bounds pattern
+  double box_rho = 0.0;
+  unsigned box_flags = 0;      // the flags of that factorisation
+  bool box_rec_complete = false, box_rec_compact = false, box_fact_valid = false;
+  const char* box_schedule = "none";
+  unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // profile
   std::vector<PendingEvent> pending;
   std::vector<hipEvent_t> event_pool;

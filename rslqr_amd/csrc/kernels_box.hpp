@@ -1,0 +1,241 @@
+// kernels_box.hpp -- internal: the box-constrained batch solve by scaled ADMM on the kept factorisation
+// (ndlqr_hip_set_bounds, ndlqr_hip_solve_box).
+//
+// The ADMM variables v (projected copy) and y (scaled dual) are shaped like the [x | u] part of every knot, in the device
+// layout [batch][N][n+m] of QR; so are the bounds lo, hi ([N][n+m] once when they are shared by every problem). An entry
+// is bounded (mask M = 1) when one of its bounds is finite; x of knot 0, u of the last knot and the pad entries of a
+// padded shape are never bounded. With rho and alpha fixed, one iteration is a re-solve with the right-hand side
+//     q~ = q + rho M (y - v)     (r~ likewise; x0 and d as resident)
+// against the factorisation of Q~ = Q + rho M_x, R~ = R + rho M_u, followed by box_update:
+//     zh = alpha z + (1 - alpha) v,   v+ = clip(zh + y, lo, hi),   y+ = (y + zh) - v+
+// STRICT: separate mul and add in exactly that order, 1 - alpha computed once on the host, q~ as t = y - v, t = rho t,
+// s = q + t, rhs = -s: numpy reproduces every value bit for bit. Unbounded entries are never touched by the update: their
+// right-hand side is the resident one (written once per solve), y stays 0, and v = z is filled in by box_finish.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kernels_common.hpp"
+
+namespace ndlqr {
+
+struct BoxParams {
+  double rho, alpha, oma;  // oma = 1 - alpha
+  double eps_abs, eps_rel;
+};
+
+__device__ __forceinline__ bool box_bounded(double lo, double hi) { return lo > -HUGE_VAL || hi < HUGE_VAL; }
+// max that keeps a NaN of either operand (fmax drops it): a NaN iterate must not look converged
+__device__ __forceinline__ double max_nan(double m, double a) { return (a > m || a != a) ? a : m; }
+
+// Bounds in the caller's layout -- xlo, xhi [P][N][n], ulo, uhi [P][N][m], P = batch or 1 (shared); nullptr: unbounded --
+// into the device layout lo, hi [P][N][n+m]. commit == 0: only check, *bad = 1 when lo > hi (or NaN) for an entry that is
+// used. commit == 1: write lo, hi, and the bounded pattern into mask, *changed = 1 where it differs from what mask held.
+//   grid (N, P), block 64.
+static __global__ void box_bounds(Dims du, Dims d, const double* __restrict__ xlo, const double* __restrict__ xhi,
+                                  const double* __restrict__ ulo, const double* __restrict__ uhi, int commit,
+                                  double* __restrict__ lo, double* __restrict__ hi, unsigned char* __restrict__ mask,
+                                  int* __restrict__ bad, int* __restrict__ changed) {
+  const int k = blockIdx.x, p = blockIdx.y;
+  const size_t xo = ((size_t)p * du.N + k) * du.n, uo = ((size_t)p * du.N + k) * du.m;
+  const size_t o = ((size_t)p * d.N + k) * d.w;
+  for (int j = threadIdx.x; j < d.w; j += blockDim.x) {
+    double l = -HUGE_VAL, h = HUGE_VAL;
+    if (j < d.n) {
+      if (j < du.n && k > 0) {
+        if (xlo) l = xlo[xo + j];
+        if (xhi) h = xhi[xo + j];
+      }
+    } else {
+      const int i = j - d.n;
+      if (i < du.m && k < d.N - 1) {
+        if (ulo) l = ulo[uo + i];
+        if (uhi) h = uhi[uo + i];
+      }
+    }
+    if (!commit) {
+      if (!(l <= h)) *bad = 1;
+      continue;
+    }
+    lo[o + j] = l;
+    hi[o + j] = h;
+    const unsigned char b = box_bounded(l, h) ? 1 : 0;
+    if (mask[o + j] != b) {
+      mask[o + j] = b;
+      *changed = 1;
+    }
+  }
+}
+
+// QR <- QR + rho M in place (the caller has saved QR). lo, hi of problem b at offset b * bstride.
+//   grid (N, batch), block 64.
+static __global__ void box_shift_qr(Dims d, double rho, const double* __restrict__ lo, const double* __restrict__ hi,
+                                    size_t bstride, double* __restrict__ QR) {
+  const int k = blockIdx.x, b = blockIdx.y;
+  const size_t ob = (size_t)b * bstride + (size_t)k * d.w, oq = ((size_t)b * d.N + k) * d.w;
+  for (int j = threadIdx.x; j < d.w; j += blockDim.x)
+    if (box_bounded(lo[ob + j], hi[ob + j])) QR[oq + j] = QR[oq + j] + rho;
+}
+
+// q~ of one bounded entry from the resident right-hand side entry res = -q
+template <bool STRICT>
+__device__ __forceinline__ double box_rhs_entry(double res, double v, double y, double rho) {
+  const double q = -res;
+  double t = y - v;
+  if constexpr (STRICT) {
+    t = rho * t;
+    return -(q + t);
+  } else {
+    return -fma(rho, t, q);
+  }
+}
+
+// Start of a solve: both ADMM right-hand sides from the resident one and v, y (zeroed first for a cold start; a warm
+// start zeroes y of the entries the current bounds leave unbounded, which may have been bounded in the previous solve).
+//   grid (N, batch), block 64.
+template <bool STRICT>
+__global__ void box_start(Dims d, double rho, int cold, const double* __restrict__ lo, const double* __restrict__ hi,
+                          size_t bstride, const double* __restrict__ res, double* __restrict__ v, double* __restrict__ y,
+                          double* __restrict__ rhs0, double* __restrict__ rhs1) {
+  const int k = blockIdx.x, b = blockIdx.y;
+  const size_t oz = ((size_t)b * d.N + k) * d.rows, ov = ((size_t)b * d.N + k) * d.w,
+               ob = (size_t)b * bstride + (size_t)k * d.w;
+  for (int r = threadIdx.x; r < d.rows; r += blockDim.x) {
+    double val = res[oz + r];
+    if (r >= d.n) {
+      const int j = r - d.n;
+      const bool bounded = box_bounded(lo[ob + j], hi[ob + j]);
+      if (cold) { v[ov + j] = 0.0; y[ov + j] = 0.0; }
+      else if (!bounded) y[ov + j] = 0.0;
+      if (bounded) val = box_rhs_entry<STRICT>(val, cold ? 0.0 : v[ov + j], cold ? 0.0 : y[ov + j], rho);
+    }
+    rhs0[oz + r] = val;
+    rhs1[oz + r] = val;
+  }
+}
+
+// One ADMM update of every running problem (status[b] == 0) after re-solve `it` (1-based): z [batch][N][2n+m] is the
+// re-solve's solution with the right-hand side rhs_cur; v, y are updated in place, the next right-hand side -- from the
+// resident one, res -- goes to rhs_next. Per problem, over its bounded entries: r_prim = max |z - v+|, r_dual = rho max |v+ - v|; converged when
+//     r_prim <= eps_abs + eps_rel max(max |z|, max |v+|)   and   r_dual <= eps_abs + eps_rel rho max |y+|.
+// A converged problem is frozen: status 1, and rhs_next takes a copy of rhs_cur, so later re-solves reproduce its z. A
+// problem whose maxima are not finite (NaN / inf in its iterate; the reductions keep a NaN) is frozen as status 3.
+// The running count drops by one with an ordinary global atomic. Max-reductions in LDS: deterministic.
+//   grid (batch), block 256.
+template <bool STRICT>
+__global__ __launch_bounds__(256) void box_update(Dims d, int it, BoxParams P, const double* __restrict__ z,
+                                                  const double* __restrict__ lo, const double* __restrict__ hi, size_t bstride,
+                                                  double* __restrict__ v, double* __restrict__ y, const double* __restrict__ res,
+                                                  const double* __restrict__ rhs_cur, double* __restrict__ rhs_next,
+                                                  int* __restrict__ status, int* __restrict__ iters,
+                                                  double* __restrict__ resid, int* __restrict__ running) {
+  __shared__ double red[5][256];
+  __shared__ int conv_s;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (status[b] != 0) return;  // frozen (uniform over the workgroup)
+  const int w = d.w, n = d.n, rows = d.rows;
+  const unsigned nw = (unsigned)(d.N * w);
+  const double* lb = lo + (size_t)b * bstride;
+  const double* hb = hi + (size_t)b * bstride;
+  double* vb = v + (size_t)b * nw;
+  double* yb = y + (size_t)b * nw;
+  const double* zb = z + (size_t)b * d.N * rows;
+  const double* rs = res + (size_t)b * d.N * rows;
+  const double* rc = rhs_cur + (size_t)b * d.N * rows;
+  double* rn = rhs_next + (size_t)b * d.N * rows;
+  double rp = 0.0, rd = 0.0, zm = 0.0, vm = 0.0, ym = 0.0;
+  for (unsigned e = tid; e < nw; e += blockDim.x) {
+    const double l = lb[e], h = hb[e];
+    if (!box_bounded(l, h)) continue;
+    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
+    const size_t oz = (size_t)k * rows + n + j;
+    const double zi = zb[oz], v0 = vb[e], y0 = yb[e];
+    double zh;
+    if constexpr (STRICT) {
+      const double a = P.alpha * zi;
+      const double c = P.oma * v0;
+      zh = a + c;
+    } else {
+      zh = fma(P.alpha, zi, P.oma * v0);
+    }
+    const double t = zh + y0;
+    const double vn = fmin(fmax(t, l), h);
+    const double yn = (y0 + zh) - vn;
+    vb[e] = vn;
+    yb[e] = yn;
+    rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, P.rho);
+    rp = max_nan(rp, fabs(zi - vn));
+    rd = max_nan(rd, fabs(vn - v0));
+    zm = max_nan(zm, fabs(zi));
+    vm = max_nan(vm, fabs(vn));
+    ym = max_nan(ym, fabs(yn));
+  }
+  red[0][tid] = rp; red[1][tid] = rd; red[2][tid] = zm; red[3][tid] = vm; red[4][tid] = ym;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s)
+      for (int q = 0; q < 5; ++q) red[q][tid] = max_nan(red[q][tid], red[q][tid + s]);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double r_prim = red[0][0], r_dual = P.rho * red[1][0];
+    const double tol_p = P.eps_abs + P.eps_rel * max_nan(red[2][0], red[3][0]);
+    const double tol_d = P.eps_abs + P.eps_rel * (P.rho * red[4][0]);
+    // a NaN or an infinity in z, v+ or y+ (from the problem data or a failed pivot) ends the problem as status 3
+    const bool finite = isfinite(r_prim) && isfinite(r_dual) && isfinite(red[2][0]) && isfinite(red[3][0]) &&
+                        isfinite(red[4][0]);
+    const int conv = finite && r_prim <= tol_p && r_dual <= tol_d;
+    iters[b] = it;
+    resid[2 * (size_t)b] = r_prim;
+    resid[2 * (size_t)b + 1] = r_dual;
+    if (conv || !finite) {
+      status[b] = conv ? 1 : 3;
+      atomicSub(running, 1);
+    }
+    conv_s = conv || !finite;
+  }
+  __syncthreads();
+  if (!conv_s) return;
+  for (unsigned e = tid; e < nw; e += blockDim.x) {  // frozen: the next right-hand side is the current one
+    if (!box_bounded(lb[e], hb[e])) continue;
+    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
+    const size_t oz = (size_t)k * rows + n + j;
+    rn[oz] = rc[oz];
+  }
+}
+
+// End of a solve: the resident solution blocks zs get lambda from the last re-solve z and x, u from v (bounded entries)
+// or z (unbounded ones, where v = z is stored too).
+//   grid (N, batch), block 64.
+static __global__ void box_finish(Dims d, const double* __restrict__ lo, const double* __restrict__ hi, size_t bstride,
+                                  const double* __restrict__ z, double* __restrict__ v, double* __restrict__ zs) {
+  const int k = blockIdx.x, b = blockIdx.y;
+  const size_t oz = ((size_t)b * d.N + k) * d.rows, ov = ((size_t)b * d.N + k) * d.w,
+               ob = (size_t)b * bstride + (size_t)k * d.w;
+  for (int r = threadIdx.x; r < d.rows; r += blockDim.x) {
+    double val = z[oz + r];
+    if (r >= d.n) {
+      const int j = r - d.n;
+      if (box_bounded(lo[ob + j], hi[ob + j])) val = v[ov + j];
+      else v[ov + j] = val;
+    }
+    zs[oz + r] = val;
+  }
+}
+
+// Multipliers mu = rho y into the caller's flat layout: mu_x [batch][N][n], mu_u [batch][N][m] (either may be nullptr).
+//   grid (N, batch), block 64.
+static __global__ void box_multipliers(Dims du, Dims d, double rho, const double* __restrict__ y, double* __restrict__ mu_x,
+                                       double* __restrict__ mu_u) {
+  const int k = blockIdx.x, b = blockIdx.y;
+  const size_t ov = ((size_t)b * d.N + k) * d.w;
+  for (int j = threadIdx.x; j < du.n + du.m; j += blockDim.x) {
+    if (j < du.n) {
+      if (mu_x) mu_x[((size_t)b * du.N + k) * du.n + j] = rho * y[ov + j];
+    } else if (mu_u) {
+      const int i = j - du.n;
+      mu_u[((size_t)b * du.N + k) * du.m + i] = rho * y[ov + d.n + i];
+    }
+  }
+}
+
+}  // namespace ndlqr

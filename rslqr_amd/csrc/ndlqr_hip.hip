@@ -11,6 +11,7 @@
 
 #include "hip_context.hpp"
 #include "kernels_generic.hpp"
+#include "kernels_box.hpp"
 #include "kernels_grad.hpp"
 #include "kernels_mfma.hpp"
 #include "kernels_reduced_mfma.hpp"
@@ -206,6 +207,10 @@ void ndlqr_hip_destroy(NdlqrHipCtx* c) {
   (void)hipFree(c->multi_ytop); (void)hipFree(c->multi_in); (void)hipFree(c->multi_out);
   (void)hipFree(c->kkt_out); (void)hipFree(c->pad_stage);
   (void)hipFree(c->adj_rhs); (void)hipFree(c->adj_z); (void)hipFree(c->adj_save); (void)hipFree(c->grad_stage);
+  (void)hipFree(c->box_lo); (void)hipFree(c->box_hi); (void)hipFree(c->box_v); (void)hipFree(c->box_y); (void)hipFree(c->box_z);
+  (void)hipFree(c->box_qr_save); (void)hipFree(c->box_rhs[0]); (void)hipFree(c->box_rhs[1]); (void)hipFree(c->box_resid);
+  (void)hipFree(c->box_mask); (void)hipFree(c->box_status); (void)hipFree(c->box_iters); (void)hipFree(c->box_word);
+  if (c->h_box_word) (void)hipHostFree(c->h_box_word);
   for (double* h : c->h_stage) if (h) (void)hipHostFree(h);
   if (c->ev_inputs) (void)hipEventDestroy(c->ev_inputs);
   for (hipEvent_t ev : c->ev_step) if (ev) (void)hipEventDestroy(ev);
@@ -220,6 +225,7 @@ static void note_solution(NdlqrHipCtx* c) {
   ++c->soln_gen;  // (an adjoint of an earlier solution no longer applies)
   c->latest = c->cur;
   c->z_partial = c->apply_nblk > 0;
+  c->z_invalid = false;
   c->z_blk0 = c->apply_blk0;
   c->z_nblk = c->apply_nblk;
 }
@@ -232,6 +238,8 @@ static void next_solve_on_current_set(NdlqrHipCtx* c) {
 }
 // consumers of the whole solution vector refuse a slice
 static int need_full_solution(const NdlqrHipCtx* c, const char* who) {
+  if (c->z_invalid)
+    return refuse(std::string(who) + ": the last constrained solve failed; there is no resident solution until the next solve");
   if (!c->z_partial) return NDLQR_OK;
   g_last_error = std::string(who) + ": the last step computed only knots " + std::to_string(8 * c->z_blk0) + " .. " +
                  std::to_string(8 * (c->z_blk0 + c->z_nblk) - 1) + " (NDLQR_SOLN_ONLY); run a solve or a step without it first";
@@ -393,6 +401,7 @@ static void note_new_inputs(NdlqrHipCtx* c) {
   c->fact_valid = false;
   c->rec_complete = false;
   c->inputs_replaced = true;
+  c->box_fact = false;
 }
 
 // staging of caller-layout data of a padded shape
@@ -1003,6 +1012,8 @@ static int launch_solve(NdlqrHipCtx* c) {
   note_solution(c);
   c->fact_valid = solve_leaves_factors(c);
   c->inputs_replaced = false;
+  c->box_fact = false;  // (the records / factors are those of the unshifted matrix now)
+  ++c->factor_count;
   return NDLQR_OK;
 }
 
@@ -1097,6 +1108,7 @@ int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
   rhs_written_cur(c, 0xFu);
   c->fact_valid = false;  // new A, B, Q, R: neither a cached factor array nor cached records match
   c->rec_complete = false;
+  c->box_fact = false;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_staged(c) : replay_chain(c, c->staged, enqueue_staged);
@@ -1150,6 +1162,7 @@ int ndlqr_hip_time_shard_import(NdlqrHipCtx* c, int G, const double* buf) {
 }
 
 static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
+  if (c) c->box_fact = false;  // (the phases overwrite the records)
   const SmallInstance* inst = time_shard_instance(c, G);
   if (!inst) {
     g_last_error = "time-axis sharding: needs a size-specialised block size with a matrix-core instance, G a power of two, "
@@ -1372,7 +1385,7 @@ int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   const KnotSlice sel = {knot0, nknots, blocks};
   if (!c || !out || !sel.valid(c->d.N, 7u)) return NDLQR_ERR_INVALID;
   BufferSet& s = c->set[c->cur];
-  if (c->z_partial && (knot0 < 8 * c->z_blk0 || knot0 + nknots > 8 * (c->z_blk0 + c->z_nblk)))
+  if (c->z_invalid || (c->z_partial && (knot0 < 8 * c->z_blk0 || knot0 + nknots > 8 * (c->z_blk0 + c->z_nblk))))
     return need_full_solution(c, "ndlqr_hip_download_selection");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
@@ -1562,7 +1575,7 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   if (!c->fact_valid && !c->rec_complete)
     return refuse("adjoint solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
                   "factorisation) of the resident inputs");
-  if (c->z_partial) return need_full_solution(c, "ndlqr_hip_solve_adjoint");
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_adjoint");
   if (!strcmp(c->schedule, "reduced-time-shard")) return refuse("adjoint solve: not available on a time-axis shard");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
@@ -1605,7 +1618,7 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
 
 // is there an adjoint of the resident solution of the resident inputs?
 static int need_adjoint(const NdlqrHipCtx* c, const char* who) {
-  if (c->z_partial) return need_full_solution(c, who);
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, who);
   if (c->adj_gen == 0 || c->adj_gen != c->soln_gen)
     return refuse(std::string(who) + ": no adjoint of the resident solution (ndlqr_hip_solve_adjoint after the latest solve)");
   if (c->inputs_replaced) return refuse(std::string(who) + ": the inputs were replaced after the factorisation");
@@ -1725,6 +1738,298 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
   if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
   return NDLQR_OK;
 }
+
+// ------------------------------------------------------------------------------ box-constrained solve (ADMM)
+// Scaled ADMM with a fixed penalty on the kept factorisation (kernels_box.hpp): QR is shifted by
+// rho M in place -- the pointers, and with them the captured launch chain of the primary set, stay valid, and every record
+// re-solve reads the shifted diagonal --, factored once (or not at all while the remembered shifted factorisation still
+// applies), and every iteration is one re-solve into box_z plus one box_update; the host reads the running count every
+// check_every iterations.
+
+template <typename T>
+static int box_alloc(T** p, size_t bytes) {
+  if (*p) return NDLQR_OK;
+  HIP_TRY(hipMalloc(p, bytes));
+  return NDLQR_OK;
+}
+static int fail_if(hipError_t e, const char* what) { return e == hipSuccess ? NDLQR_OK : fail(what, e); }
+
+// Bounds in the caller's layout, [P][N][n] and [P][N][m] with P = batch, or P = 1 (shared): this device's memory is read
+// as it is, host memory is staged through HBM. Checked (lo <= hi for every used entry) before anything is replaced.
+int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const double* xhi, const double* ulo,
+                         const double* uhi) {
+  if (!c) return NDLQR_ERR_INVALID;
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  const int P = shared ? 1 : d.batch;
+  const size_t nx = (size_t)P * u.N * u.n, nu = (size_t)P * u.N * u.m;
+  const double* src[4] = {xlo, xhi, ulo, uhi};
+  const size_t cnt[4] = {nx, nx, nu, nu};
+  Where w[4] = {Where::OwnDevice, Where::OwnDevice, Where::OwnDevice, Where::OwnDevice};
+  size_t stage = 0;
+  for (int k = 0; k < 4; ++k) {
+    if (!src[k]) continue;
+    w[k] = where(src[k], c->device);
+    if (w[k] == Where::OtherDevice) return refuse("ndlqr_hip_set_bounds: bounds lie in the memory of another device than the solver's");
+    if (w[k] != Where::OwnDevice) stage += cnt[k];
+  }
+  {
+    const int serr = ensure_grad_stage(c, stage);
+    if (serr) return serr;
+  }
+  const size_t nlo = sizeof(double) * (size_t)d.batch * d.N * d.w;  // (room for per-problem bounds, shared or not)
+  if (!c->box_mask) {
+    HIP_TRY(hipMalloc(&c->box_mask, (size_t)d.batch * d.N * d.w));
+    HIP_TRY(hipMemset(c->box_mask, 0, (size_t)d.batch * d.N * d.w));
+  }
+  int aerr = box_alloc(&c->box_lo, nlo);
+  if (!aerr) aerr = box_alloc(&c->box_hi, nlo);
+  if (!aerr) aerr = box_alloc(&c->box_word, 4 * sizeof(int));
+  if (aerr) return aerr;
+  if (!c->h_box_word) HIP_TRY(hipHostMalloc((void**)&c->h_box_word, 4 * sizeof(int), hipHostMallocDefault));
+  HIP_TRY(sync_all(c));  // (a solve in flight may still read the bounds)
+  BufferSet& s = c->set[0];
+  const double* view[4] = {};
+  double* at = c->grad_stage;
+  for (int k = 0; k < 4; ++k) {
+    if (!src[k]) continue;
+    view[k] = src[k];
+    if (w[k] != Where::OwnDevice) {
+      HIP_TRY(hipMemcpyAsync(at, src[k], sizeof(double) * cnt[k], hipMemcpyDefault, s.stream));
+      view[k] = at;
+      at += cnt[k];
+    }
+  }
+  HIP_TRY(hipMemsetAsync(c->box_word, 0, 4 * sizeof(int), s.stream));
+  hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 0,
+                     c->box_lo, c->box_hi, c->box_mask, c->box_word + 1, c->box_word + 2);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  if (c->h_box_word[1]) return refuse("ndlqr_hip_set_bounds: a lower bound exceeds its upper bound (or is NaN)");
+  // the pattern lives in mask per problem: shared bounds are compared against problem 0's row of it, so a change between
+  // shared and per-problem bounds always counts as a new pattern
+  hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 1,
+                     c->box_lo, c->box_hi, c->box_mask, c->box_word + 1, c->box_word + 2);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  if (c->h_box_word[2] || (bool)shared != c->box_shared || !c->box_have_bounds) c->box_fact = false;
+  c->box_shared = shared != 0;
+  c->box_bstride = shared ? 0 : (size_t)d.N * d.w;
+  c->box_have_bounds = true;
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
+                        int check_every, int warm_start, int* iters, int* status) {
+  if (!c || !(rho > 0.0) || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 ||
+      check_every < 1)
+    return NDLQR_ERR_INVALID;
+  if (!c->box_have_bounds) return refuse("ndlqr_hip_solve_box: no bounds (ndlqr_hip_set_bounds first)");
+  const ndlqr::Dims& d = c->d;
+  HIP_TRY(hipSetDevice(c->device));
+  for (const int* p : {iters, status})
+    if (p && where(p, c->device) == Where::OtherDevice)
+      return refuse("ndlqr_hip_solve_box: iters / status lie in the memory of another device than the solver's");
+  const size_t nz = bytes_z(d), nv = sizeof(double) * (size_t)d.batch * d.N * d.w;
+  if (!c->box_z) {
+    HIP_TRY(hipMalloc(&c->box_z, nz));
+    HIP_TRY(hipMemset(c->box_z, 0, nz));  // (entries a re-solve does not write: the pad rows)
+  }
+  int aerr = box_alloc(&c->box_v, nv);
+  if (!aerr) aerr = box_alloc(&c->box_y, nv);
+  if (!aerr) aerr = box_alloc(&c->box_qr_save, bytes_QR(d));
+  if (!aerr) aerr = box_alloc(&c->box_rhs[0], nz);
+  if (!aerr) aerr = box_alloc(&c->box_rhs[1], nz);
+  if (!aerr) aerr = box_alloc(&c->box_resid, sizeof(double) * 2 * (size_t)d.batch);
+  if (!aerr) aerr = box_alloc(&c->box_status, sizeof(int) * (size_t)d.batch);
+  if (!aerr) aerr = box_alloc(&c->box_iters, sizeof(int) * (size_t)d.batch);
+  if (aerr) return aerr;
+  // 1. everything idle, the primary set current with an up-to-date right-hand side
+  HIP_TRY(sync_all(c));
+  c->cur = 0;
+  {
+    const int merr = rhs_make_current(c, 0xFu);
+    if (merr) return merr;
+  }
+  BufferSet& s = c->set[0];
+  const hipStream_t st = s.stream;
+  const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
+  const unsigned user_flags = c->flags;
+  const unsigned box_flags = user_flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
+  const bool reuse = c->box_fact && c->box_rho == rho && c->box_flags == box_flags;
+  HIP_TRY(hipEventRecord(s.ev_start, st));
+  // 2. shift QR (restored on every exit below)
+  HIP_TRY(hipMemcpyAsync(c->box_qr_save, c->QR, bytes_QR(d), hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, (const double*)c->box_lo,
+                     (const double*)c->box_hi, c->box_bstride, c->QR);
+  int err = fail_if(hipGetLastError(), "box_shift_qr");
+  bool factored = false;  // the shifted matrix was factored in this call (the resident solution is then overwritten)
+  int not_spd = NDLQR_OK;
+  c->flags = box_flags;
+  // 3. factor the shifted matrix, unless the remembered factorisation applies
+  if (!err && reuse) {
+    c->rec_complete = c->box_rec_complete;
+    c->rec_compact = c->box_rec_compact;
+    c->fact_valid = c->box_fact_valid;
+    c->schedule = c->box_schedule;
+  } else if (!err) {
+    c->box_fact = false;
+    factored = true;
+    err = prepare_solve(c, nullptr);  // (KEEP_*: stream-ordered on the primary set)
+    if (!err) err = launch_solve(c);
+    if (!err) c->state_dirty = false;
+    if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (!err) {  // a non-positive pivot of the shifted factorisation (e.g. Q or R <= 0 on an unbounded entry): no iterations
+      int seen = 0;
+      for (const BufferSet& b : c->set)
+        if (b.h_fail && *b.h_fail > seen) seen = *b.h_fail;
+      c->last_failures = seen - c->fail_base;
+      c->fail_base = seen;
+      if (c->last_failures > 0) {
+        refuse("ndlqr_hip_solve_box: " + std::to_string(c->last_failures) + " non-positive pivot(s) in the factorisation of "
+               "Q + rho M, R + rho M");
+        err = not_spd = NDLQR_ERR_NOT_SPD;
+      }
+    }
+  }
+  // 4. the iterations
+  const double* lo = c->box_lo;
+  const double* hi = c->box_hi;
+  const size_t bs = c->box_bstride;
+  ndlqr::BoxParams P = {rho, alpha, 1.0 - alpha, eps_abs, eps_rel};
+  int done_iters = 0;
+  if (!err) {
+    const int cold = warm_start && c->box_have_vy ? 0 : 1;
+    if (strict)
+      hipLaunchKernelGGL(ndlqr::box_start<true>, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, cold, lo, hi, bs,
+                         (const double*)s.rhs, c->box_v, c->box_y, c->box_rhs[0], c->box_rhs[1]);
+    else
+      hipLaunchKernelGGL(ndlqr::box_start<false>, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, cold, lo, hi, bs,
+                         (const double*)s.rhs, c->box_v, c->box_y, c->box_rhs[0], c->box_rhs[1]);
+    err = fail_if(hipGetLastError(), "box_start");
+    c->box_have_vy = true;
+    c->h_box_word[0] = d.batch;
+    if (!err) err = fail_if(hipMemcpyAsync(c->box_word, c->h_box_word, sizeof(int), hipMemcpyHostToDevice, st), "box running count");
+    if (!err) err = fail_if(hipMemsetAsync(c->box_status, 0, sizeof(int) * (size_t)d.batch, st), "box status");
+  }
+  for (int it = 1; it <= max_iter && !err; ++it) {
+    const double* rc = c->box_rhs[(it - 1) & 1];
+    double* rn = c->box_rhs[it & 1];
+    err = launch_resolve(c, rc, c->box_z, "box-constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
+    if (err) break;
+    if (strict)
+      hipLaunchKernelGGL(ndlqr::box_update<true>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->box_z, lo, hi,
+                         bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_status, c->box_iters, c->box_resid,
+                         c->box_word);
+    else
+      hipLaunchKernelGGL(ndlqr::box_update<false>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->box_z, lo, hi,
+                         bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_status, c->box_iters, c->box_resid,
+                         c->box_word);
+    err = fail_if(hipGetLastError(), "box_update");
+    done_iters = it;
+    if (!err && (it % check_every == 0 || it == max_iter)) {
+      // 5. one word: how many problems still run
+      err = fail_if(hipMemcpyAsync(c->h_box_word, c->box_word, sizeof(int), hipMemcpyDeviceToHost, st), "box running count");
+      if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
+      if (!err && c->h_box_word[0] == 0) break;
+    }
+  }
+  // 6. deliver, restore QR, bookkeeping
+  if (!err && done_iters > 0) {
+    hipLaunchKernelGGL(ndlqr::box_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, lo, hi, bs, (const double*)c->box_z, c->box_v,
+                       s.z);
+    err = fail_if(hipGetLastError(), "box_finish");
+  }
+  const hipError_t re = hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(d), hipMemcpyDeviceToDevice, st);
+  if (!err && re != hipSuccess) err = fail("restoring QR", re);
+  c->flags = user_flags;
+  if (!err) {
+    c->box_fact = true;
+    c->box_rho = rho;
+    c->box_flags = box_flags;
+    c->box_rec_complete = c->rec_complete;
+    c->box_rec_compact = c->rec_compact;
+    c->box_fact_valid = c->fact_valid;
+    c->box_schedule = c->schedule;
+  } else {
+    c->box_fact = false;
+    c->box_have_vy = false;
+    if (!not_spd) c->state_dirty = true;  // (a failed launch; a non-positive pivot leaves the device state clean)
+    if (factored) c->z_invalid = true;    // (the factorisation solved the shifted matrix with the unshifted right-hand side)
+  }
+  // the kept records / factors belong to the shifted matrix: the plain re-solves refuse until the next solve
+  c->rec_complete = false;
+  c->fact_valid = false;
+  if (err) {
+    (void)hipStreamSynchronize(st);
+    return err;
+  }
+  note_solution(c);
+  HIP_TRY(hipEventRecord(s.ev_stop, st));
+  std::vector<int> h_it((size_t)d.batch), h_st((size_t)d.batch);
+  HIP_TRY(hipMemcpyAsync(h_it.data(), c->box_iters, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_st.data(), c->box_status, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
+  c->timing_pending = true;
+  const int serr = ndlqr_hip_synchronize(c);
+  if (serr) return serr;
+  for (int& v : h_st)
+    if (v == 0) v = 2;  // max_iter reached: the last iterate
+  int* user[2] = {iters, status};
+  const std::vector<int>* val[2] = {&h_it, &h_st};
+  for (int k = 0; k < 2; ++k) {  // (host or this device's memory)
+    if (!user[k]) continue;
+    if (where(user[k], c->device) == Where::OwnDevice)
+      HIP_TRY(hipMemcpy(user[k], val[k]->data(), sizeof(int) * (size_t)d.batch, hipMemcpyHostToDevice));
+    else
+      memcpy(user[k], val[k]->data(), sizeof(int) * (size_t)d.batch);
+  }
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* mu_u) {
+  if (!c || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
+  if (!c->box_have_vy || !c->box_y) return refuse("ndlqr_hip_download_bound_multipliers: no constrained solve yet");
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  double* user[2] = {mu_x, mu_u};
+  const size_t cnt[2] = {(size_t)u.batch * u.N * u.n, (size_t)u.batch * u.N * u.m};
+  bool own[2] = {};
+  size_t stage = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (!user[k]) continue;
+    const Where w = where(user[k], c->device);
+    if (w == Where::OtherDevice)
+      return refuse("ndlqr_hip_download_bound_multipliers: an output lies in the memory of another device than the solver's");
+    own[k] = w == Where::OwnDevice;
+    if (!own[k]) stage += cnt[k];
+  }
+  {
+    const int serr = ensure_grad_stage(c, stage);
+    if (serr) return serr;
+  }
+  HIP_TRY(sync_all(c));
+  const BufferSet& s = c->set[0];
+  double* out[2] = {};
+  double* at = c->grad_stage;
+  for (int k = 0; k < 2; ++k) {
+    if (!user[k]) continue;
+    out[k] = own[k] ? user[k] : at;
+    if (!own[k]) at += cnt[k];
+  }
+  hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, c->box_rho,
+                     (const double*)c->box_y, out[0], out[1]);
+  HIP_TRY(hipGetLastError());
+  for (int k = 0; k < 2; ++k)
+    if (user[k] && !own[k]) HIP_TRY(hipMemcpyAsync(user[k], out[k], sizeof(double) * cnt[k], hipMemcpyDefault, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
+}
+
+unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* c) { return c ? c->factor_count : 0; }
 
 // Several right-hand sides per problem against ONE kept factorisation each (SURVEY.md 8(f)-2 "multiple right-hand
 // sides"; the reference's NdData holds a single one, src/nddata.h:70-75): nrhs x batch right-hand sides, flat host arrays
@@ -1886,7 +2191,7 @@ int ndlqr_hip_profile_reset(NdlqrHipCtx* c) {
 // hipMemcpy2D into pageable memory this replaces ran at 5.4 GB/s.
 int ndlqr_hip_download_solutions(NdlqrHipCtx* c, int p0, int count, double* soln) {
   if (!c || !soln || p0 < 0 || count <= 0 || p0 + count > c->d.batch) return NDLQR_ERR_INVALID;
-  if (c->z_partial) return need_full_solution(c, "ndlqr_hip_download_solutions");
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_download_solutions");
   return download_packed(c, c->set[c->latest].z, p0, count, soln);
 }
 // ... of the blocks [batch][N][2n+m] at zsrc (the latest solution, or the adjoint solution)
@@ -1941,7 +2246,7 @@ int ndlqr_hip_factors_valid(const NdlqrHipCtx* c) { return c && c->fact_valid ? 
 
 int ndlqr_hip_pack_solutions_device(NdlqrHipCtx* c, double* dst) {
   if (!c || !dst) return NDLQR_ERR_INVALID;
-  if (c->z_partial) return need_full_solution(c, "ndlqr_hip_pack_solutions_device");
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_pack_solutions_device");
   const ndlqr::Dims& d = c->d;
   HIP_TRY(hipSetDevice(c->device));
   // on the stream of the latest solve: ordered behind it, asynchronous for the caller
@@ -1951,7 +2256,7 @@ int ndlqr_hip_pack_solutions_device(NdlqrHipCtx* c, double* dst) {
 
 int ndlqr_hip_kkt_residual(NdlqrHipCtx* c, double* res, double* bnorm) {
   if (!c || !res) return NDLQR_ERR_INVALID;
-  if (c->z_partial) return need_full_solution(c, "ndlqr_hip_kkt_residual");
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_kkt_residual");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
@@ -1971,7 +2276,7 @@ int ndlqr_hip_kkt_residual(NdlqrHipCtx* c, double* res, double* bnorm) {
 
 int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
   if (!c || !z_full || p < 0 || p >= c->d.batch) return NDLQR_ERR_INVALID;
-  if (c->z_partial) return need_full_solution(c, "ndlqr_hip_download_rhs_blocks");
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_download_rhs_blocks");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
