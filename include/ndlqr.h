@@ -545,6 +545,26 @@ int ndlqr_BatchSetBounds(NdLqrBatchSolver* bs, unsigned flags, const double* xlo
                          const double* uhi);
 int ndlqr_SolveBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status);
 int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u);
+/* additive: gradients through the box-constrained solve (differentiable MPC with actuator and state limits). After
+ * ndlqr_SolveBatchBoxConstrained, for a loss L(z*) of the constrained solutions and g = dL/dz* (as for
+ * ndlqr_SolveBatchAdjoint), ndlqr_SolveBatchBoxAdjoint solves the adjoint of the active-set system
+ *     K w + E_A' nu = g,   E_A w = 0
+ * (A: the bounded entries whose projected iterate lies exactly on a bound; E_A picks them) by the same ADMM on the
+ * forward's kept shifted factorisation -- same rho, cold start, nothing factored. The settings' rho and warm_start are
+ * ignored; alpha, eps_abs, eps_rel, max_iter and check_every (0: the defaults of the forward) apply, and iters / status
+ * report as for the forward. A problem whose forward ended as 3 is not iterated and reports 3. Afterwards
+ * ndlqr_CopyBatchAdjoint returns w and ndlqr_BatchGradients dL/d(A, B, Q, R, q, r, d, x0) at the constrained solution,
+ * as after ndlqr_SolveBatchAdjoint. ndlqr_BatchBoundGradients returns dL/dc_A = nu: entry i goes to dL/dhi_i when the
+ * forward's iterate sits on hi_i (lo_i == hi_i included), to dL/dlo_i when it sits on lo_i, 0 everywhere else; flat
+ * layout [batch][N][n] / [batch][N][m], or summed over the batch ([N][..], deterministic) with NDLQR_BOUNDS_SHARED; a
+ * NULL output is not computed; host, pinned or the solver's device memory. Where the active constraints are degenerate
+ * (their rows of the KKT system are linearly dependent), nu is not unique and the bound gradients are one of many.
+ *   Nothing of the forward changes: resident solution, v and y (the next warm start), mu, the remembered shifted
+ *   factorisation; ndlqr_SolveBatchAdjoint and the plain re-solves still refuse. The box adjoint returns
+ *   NDLQR_ERR_INVALID unless the resident solution is that of the latest constrained solve -- no solve, step, re-solve,
+ *   input upload or ndlqr_BatchSetBounds since --, and any later solve invalidates it (as the plain adjoint). Blocking. */
+int ndlqr_SolveBatchBoxAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrBoxSettings* s, int* iters, int* status);
+int ndlqr_BatchBoundGradients(NdLqrBatchSolver* bs, unsigned flags, double* gxlo, double* gxhi, double* gulo, double* guhi);
 void* ndlqr_BatchDeviceContext(NdLqrBatchSolver* bs);      /* NdlqrHipCtx* (ndlqr_hip.h) */
 
 /* Seeded synthetic problem generator (host, bit-reproducible). */

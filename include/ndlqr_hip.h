@@ -115,6 +115,14 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* ctx, double rho, double alpha, double eps_a
                         int check_every, int warm_start, int* iters, int* status);
 int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* ctx, double* mu_x, double* mu_u);
 unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* ctx);
+/* Gradients through the box-constrained solve (ndlqr.h: ndlqr_SolveBatchBoxAdjoint, ndlqr_BatchBoundGradients;
+ * DESIGN.md section 3.10). ndlqr_hip_solve_box_adjoint takes the resolved settings (the forward's rho, a cold start) and
+ * blocks; g as for ndlqr_hip_solve_adjoint, iters / status [batch] may be NULL. Afterwards ndlqr_hip_download_adjoint and
+ * ndlqr_hip_gradients read its w as they read a plain adjoint. ndlqr_hip_bound_gradients: dL/d(xlo, xhi, ulo, uhi) in the
+ * flat layout, per problem or (summed) over the batch, [N][n] / [N][m]; NULL = not computed. */
+int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* ctx, const double* g, double alpha, double eps_abs, double eps_rel, int max_iter,
+                                int check_every, int* iters, int* status);
+int ndlqr_hip_bound_gradients(NdlqrHipCtx* ctx, int summed, double* gxlo, double* gxhi, double* gulo, double* guhi);
 /* Several right-hand sides per problem against one kept factorisation each (the reference's NdData holds a single
  * right-hand side, src/nddata.h:70-75): nrhs sets of right-hand sides for the whole batch, flat HOST arrays in the layout of
  * ndlqr_BatchSetRhsFlat with a leading [nrhs] -- q, d [nrhs][batch][N][n], r [nrhs][batch][N][m], x0 [nrhs][batch][n] --,

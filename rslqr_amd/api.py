@@ -268,6 +268,8 @@ def lib():
     proto("ndlqr_BatchSetBounds", ci, vp, C.c_uint, dp, dp, dp, dp)
     proto("ndlqr_SolveBatchBoxConstrained", ci, vp, C.POINTER(NdLqrBoxSettings), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_CopyBatchBoundMultipliers", ci, vp, dp, dp)
+    proto("ndlqr_SolveBatchBoxAdjoint", ci, vp, dp, C.POINTER(NdLqrBoxSettings), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_BatchBoundGradients", ci, vp, C.c_uint, dp, dp, dp, dp)
     proto("ndlqr_hip_factor_count", C.c_ulonglong, vp)
     # shim bits used by the benchmark
     proto("ndlqr_hip_set_stream", ci, vp, vp)
@@ -657,6 +659,43 @@ class BatchSolver:
             raise RuntimeError("ndlqr_CopyBatchBoundMultipliers failed: %d (%s)"
                                % (err, self.L.ndlqr_hip_last_error().decode()))
         return mu_x, mu_u
+
+    # ---- gradients through the box-constrained solve (include/ndlqr.h: ndlqr_SolveBatchBoxAdjoint,
+    # ndlqr_BatchBoundGradients)
+    def solve_box_adjoint(self, g, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0):
+        """ndlqr_SolveBatchBoxAdjoint: the adjoint of the active-set system of the last constrained solve for g = dL/dz*
+        [batch, nvars] (numpy array or DeviceArray), on the forward's kept shifted factorisation (its rho, a cold start;
+        0 = the library's default for every setting). Returns (iters, status) as numpy int arrays [batch]; status 1 =
+        converged, 2 = max_iter reached, 3 = not finite (or the forward's was). Raises on a nonzero return. Afterwards
+        adjoint() and gradients() read its w."""
+        if not hasattr(g, "ptr"):
+            g = np.ascontiguousarray(g, dtype=np.float64)
+        st = NdLqrBoxSettings(0.0, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 0)
+        iters = np.zeros(self.batch, dtype=np.int32)
+        status = np.zeros(self.batch, dtype=np.int32)
+        err = self.L.ndlqr_SolveBatchBoxAdjoint(self.h, _any_ptr(g, self.batch * self.nvars), C.byref(st),
+                                                iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                                status.ctypes.data_as(C.POINTER(C.c_int)))
+        if err:
+            raise RuntimeError("ndlqr_SolveBatchBoxAdjoint failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return iters, status
+
+    def bound_gradients(self, summed=False, out=None):
+        """ndlqr_BatchBoundGradients: dict with keys xlo, xhi, ulo, uhi -> dL/d(bound) of the last box adjoint, [batch, N, n]
+        / [batch, N, m], or [N, n] / [N, m] summed over the batch (NDLQR_BOUNDS_SHARED). `out`: dict of destinations
+        (numpy arrays or DeviceArrays); only those keys are computed. Default: numpy arrays for all four."""
+        n, m, N, B = self.n, self.m, self.N, self.batch
+        shape = {k: ((N, w) if summed else (B, N, w)) for k, w in (("xlo", n), ("xhi", n), ("ulo", m), ("uhi", m))}
+        if out is None:
+            out = {k: np.zeros(sh) for k, sh in shape.items()}
+        unknown = set(out) - set(shape)
+        if unknown:
+            raise ValueError("unknown bound names: %s" % sorted(unknown))
+        ptrs = [None if out.get(k) is None else _any_ptr(out[k], int(np.prod(shape[k]))) for k in ("xlo", "xhi", "ulo", "uhi")]
+        err = self.L.ndlqr_BatchBoundGradients(self.h, BOUNDS_SHARED if summed else 0, *ptrs)
+        if err:
+            raise RuntimeError("ndlqr_BatchBoundGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
 
     def factor_count(self):
         """factorisations this solver has launched (ndlqr_hip_factor_count; tests of the kept shifted factorisation)"""

@@ -14,6 +14,9 @@ Streams: the library runs on streams of its own. Before it reads torch memory, t
 every call into the library returns only after its writes are complete. That is the whole contract: the tensors this
 module returns may be used on any stream at once.
 
+``lqr_solve_box`` adds bounds on x and u (ndlqr_SolveBatchBoxConstrained); its backward is the adjoint of the
+active-set system (ndlqr_SolveBatchBoxAdjoint) plus the gradients with respect to the bounds (ndlqr_BatchBoundGradients).
+
 Process start-up: torch ships its own HIP runtime next to the system one this library links. Initialise torch's device
 (any CUDA tensor) before the library's first device call in a process; the other order may leave torch without a device.
 """
@@ -164,4 +167,155 @@ def lqr_solve(A, B, Q, R, q, r, d, x0):
     return LqrSolve.apply(A, B, Q, R, q, r, d, x0)
 
 
-__all__ = ["LqrSolve", "lqr_solve", "split_solution"]
+# ------------------------------------------------------------------------------------------------ box-constrained
+# A cache of its own, so that lqr_solve and lqr_solve_box do not evict each other's solvers.
+_BOUNDS = ("xlo", "xhi", "ulo", "uhi")
+_box_cache = {}              # (n, m, N, b, device index) -> [BatchSolver, token of the forward it holds]
+
+
+def _check_bounds(bounds, dev, n, m, N, b):
+    """Each bound None, [N, n|m] (shared by every problem) or [b, N, n|m]; returns the per-bound shared flags."""
+    shared = []
+    for name, t in zip(_BOUNDS, bounds):
+        if t is None:
+            shared.append(None)
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("lqr_solve_box: %s must be a torch.Tensor or None" % name)
+        if t.dtype != torch.float64:
+            raise TypeError("lqr_solve_box: %s must be float64, got %s" % (name, t.dtype))
+        if t.device != dev:
+            raise ValueError("lqr_solve_box: %s must be on the problem's device %s, got %s" % (name, dev, t.device))
+        k = n if name[0] == "x" else m
+        if tuple(t.shape) == (N, k):
+            shared.append(True)
+        elif tuple(t.shape) == (b, N, k):
+            shared.append(False)
+        else:
+            raise ValueError("lqr_solve_box: %s must be [%d, %d] or [%d, %d, %d], got %s" % (name, N, k, b, N, k, tuple(t.shape)))
+    if all(s is None for s in shared):
+        raise ValueError("lqr_solve_box: no bounds given (use lqr_solve)")
+    return shared
+
+
+def _flat_bounds(bounds, bshared, b):
+    """(NDLQR_BOUNDS_SHARED when every given bound is shared, contiguous device copies): shared bounds are expanded to
+    the batch when others are per problem."""
+    all_shared = all(s is not False for s in bshared)
+    out = []
+    for t, sh in zip(bounds, bshared):
+        if t is None:
+            out.append(None)
+            continue
+        t = t.detach()
+        if sh and not all_shared:
+            t = t.unsqueeze(0).expand(b, *t.shape)
+        out.append(t.contiguous())
+    return all_shared, out
+
+
+def _solve_box(bs, flat, bflat, all_shared, settings, token, key):
+    """Factor + constrained solve (cold) of `flat` with the bounds `bflat` on the cached solver; it then holds `token`."""
+    from .api import BOUNDS_SHARED, _any_ptr
+    torch.cuda.current_stream(flat[0].device).synchronize()  # (the library reads torch memory on its own stream)
+    _box_cache[key][1] = None
+    bs.initialize_flat_device(*[t.data_ptr() for t in flat])
+    ptrs = [None if t is None else _any_ptr(_View(t), t.numel()) for t in bflat]
+    err = bs.L.ndlqr_BatchSetBounds(bs.h, BOUNDS_SHARED if all_shared else 0, *ptrs)
+    if err:
+        raise ValueError("lqr_solve_box: the bounds were refused (%s)" % bs.L.ndlqr_hip_last_error().decode())
+    rho, alpha, eps_abs, eps_rel, max_iter = settings
+    try:
+        _, status = bs.solve_box(rho=rho, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter)
+    except RuntimeError as e:
+        raise RuntimeError("lqr_solve_box: the constrained solve failed (%s)" % e) from None
+    bad = int((status != 1).sum())
+    if bad:
+        raise RuntimeError("lqr_solve_box: %d of %d problems did not converge (status %s): raise max_iter or change rho"
+                           % (bad, status.size, sorted(set(status.tolist()) - {1})))
+    _box_cache[key][1] = token
+
+
+class LqrSolveBox(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, settings, *args):
+        problem, bounds = args[:8], args[8:]
+        dev, n, m, N, b, shared = _check(problem)
+        bshared = _check_bounds(bounds, dev, n, m, N, b)
+        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
+        if key not in _box_cache:
+            _box_cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
+        bs = _box_cache[key][0]
+        flat = _flat(problem, n, m, N, b, shared)
+        all_shared, bflat = _flat_bounds(bounds, bshared, b)
+        token = next(_tokens)
+        _solve_box(bs, flat, bflat, all_shared, settings, token, key)
+        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
+        bs.solutions_to_device(z.data_ptr())
+        bs.synchronize()
+        ctx.key, ctx.token, ctx.flat, ctx.shared, ctx.dims = key, token, flat, shared, (n, m, N, b)
+        ctx.bflat, ctx.bshared, ctx.all_shared, ctx.settings = bflat, bshared, all_shared, settings
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        n, m, N, b = ctx.dims
+        bs = _box_cache[ctx.key][0]
+        if _box_cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's forward again
+            _solve_box(bs, ctx.flat, ctx.bflat, ctx.all_shared, ctx.settings, ctx.token, ctx.key)
+        gz = gz.detach().to(torch.float64).contiguous()
+        torch.cuda.current_stream(gz.device).synchronize()
+        _, alpha, eps_abs, eps_rel, max_iter = ctx.settings
+        _, status = bs.solve_box_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter)
+        bad = int((status != 1).sum())
+        if bad:
+            raise RuntimeError("lqr_solve_box backward: the adjoint of %d of %d problems did not converge (status %s)"
+                               % (bad, status.size, sorted(set(status.tolist()) - {1})))
+        need, need_b = ctx.needs_input_grad[1:9], ctx.needs_input_grad[9:]
+        mask = 0
+        out, views = {}, {}
+        for i, (name, sh, nd) in enumerate(zip(GRAD_NAMES, ctx.shared, need)):
+            if not nd:
+                continue
+            if sh:
+                mask |= 1 << i
+            out[name] = torch.empty(bs.gradient_shape(name, sh), dtype=torch.float64, device=gz.device)
+            views[name] = _View(out[name])
+        if views:
+            bs.gradients(mask, views)
+        grads = []
+        for name in GRAD_NAMES:
+            g = out.get(name)
+            if g is not None and name in ("A", "B"):  # flat column-major -> row-major math convention
+                cols = n if name == "A" else m
+                g = g.reshape(*g.shape[:-1], cols, n).transpose(-1, -2)
+            grads.append(g)
+        bout = {}
+        for name, t, nd in zip(_BOUNDS, ctx.bflat, need_b):
+            if nd and t is not None:
+                k = n if name[0] == "x" else m
+                bout[name] = torch.empty((N, k) if ctx.all_shared else (b, N, k), dtype=torch.float64, device=gz.device)
+        if bout:
+            bs.bound_gradients(ctx.all_shared, {k: _View(v) for k, v in bout.items()})
+        for name, sh in zip(_BOUNDS, ctx.bshared):
+            g = bout.get(name)
+            if g is not None and sh and not ctx.all_shared:  # a shared bound expanded to the batch: its gradient summed
+                g = g.sum(0)
+            grads.append(g)
+        return (None,) + tuple(grads)
+
+
+def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=None, *, rho=0.0, alpha=0.0, eps_abs=0.0,
+                  eps_rel=0.0, max_iter=0):
+    """z* [b, nvars] of the LQR problems of lqr_solve with xlo <= x_k <= xhi (k >= 1) and ulo <= u_k <= uhi, by the
+    box-constrained batch solve (ndlqr_SolveBatchBoxConstrained, cold start; 0 = the library's default for every
+    setting), differentiable in all twelve tensors: the backward is the adjoint of the active-set system
+    (ndlqr_SolveBatchBoxAdjoint) with the same settings. Bounds: None (unbounded), [N, n] / [N, m] shared by every problem
+    or [b, N, n] / [b, N, m]; entries may be +-inf. Raises RuntimeError when a problem's forward or adjoint iteration
+    does not converge (status != 1). The gradients hold where the active set is locally stable (strict
+    complementarity); at a degenerate active set the bound gradients are one of many."""
+    return LqrSolveBox.apply((float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter)),
+                             A, B, Q, R, q, r, d, x0, xlo, xhi, ulo, uhi)
+
+
+__all__ = ["LqrSolve", "LqrSolveBox", "lqr_solve", "lqr_solve_box", "split_solution"]

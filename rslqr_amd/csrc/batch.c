@@ -381,6 +381,22 @@ int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* 
   if (!bs || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_bound_multipliers(bs->ctx, mu_x, mu_u);
 }
+int ndlqr_SolveBatchBoxAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrBoxSettings* s, int* iters, int* status) {
+  NdLqrBoxSettings z;
+  if (!bs || !g) return NDLQR_ERR_INVALID;
+  memset(&z, 0, sizeof(z));
+  if (s) z = *s;
+  /* (rho and warm_start are the forward's: ignored here) */
+  if (z.alpha < 0.0 || z.alpha >= 2.0 || z.eps_abs < 0.0 || z.eps_rel < 0.0 || z.max_iter < 0 || z.check_every < 0)
+    return NDLQR_ERR_INVALID;
+  return ndlqr_hip_solve_box_adjoint(bs->ctx, g, z.alpha > 0.0 ? z.alpha : 1.6, z.eps_abs > 0.0 ? z.eps_abs : 1e-6,
+                                     z.eps_rel > 0.0 ? z.eps_rel : 1e-6, z.max_iter > 0 ? z.max_iter : 4000,
+                                     z.check_every > 0 ? z.check_every : 10, iters, status);
+}
+int ndlqr_BatchBoundGradients(NdLqrBatchSolver* bs, unsigned flags, double* gxlo, double* gxhi, double* gulo, double* guhi) {
+  if (!bs || (flags & ~NDLQR_BOUNDS_SHARED)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_bound_gradients(bs->ctx, (flags & NDLQR_BOUNDS_SHARED) ? 1 : 0, gxlo, gxhi, gulo, guhi);
+}
 int ndlqr_CopyBatchFactors(NdLqrBatchSolver* bs, int p, double* fact) {
   if (!bs || !fact || p < 0 || p >= bs->batch) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_factors(bs->ctx, p, fact);

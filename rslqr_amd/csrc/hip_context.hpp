@@ -183,6 +183,16 @@ struct NdlqrHipCtx {
   unsigned box_flags = 0;      // the flags of that factorisation
   bool box_rec_complete = false, box_rec_compact = false, box_fact_valid = false;
   const char* box_schedule = "none";
+  // Gradients through the box-constrained solve (ndlqr_hip_solve_box_adjoint / ndlqr_hip_bound_gradients,
+  // kernels_box_grad.hpp; allocated on first use). box_soln_gen: the solution generation the latest constrained solve
+  // left (0: none since the bounds were set); abox_gen: the one the box adjoint belongs to (0: none). The adjoint's own
+  // entry codes, v, y, ADMM right-hand sides (its resident one is adj_rhs, its solution adj_z), per problem status,
+  // iterations and residuals, and its running count: nothing of the forward's iteration state is touched.
+  unsigned long long box_soln_gen = 0, abox_gen = 0;
+  unsigned char* abox_code = nullptr;
+  double *abox_v = nullptr, *abox_y = nullptr, *abox_resid = nullptr;
+  double* abox_rhs[2] = {};
+  int *abox_status = nullptr, *abox_iters = nullptr, *abox_word = nullptr;
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // profile
   std::vector<PendingEvent> pending;

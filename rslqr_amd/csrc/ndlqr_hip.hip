@@ -12,6 +12,7 @@
 #include "hip_context.hpp"
 #include "kernels_generic.hpp"
 #include "kernels_box.hpp"
+#include "kernels_box_grad.hpp"
 #include "kernels_grad.hpp"
 #include "kernels_mfma.hpp"
 #include "kernels_reduced_mfma.hpp"
@@ -210,6 +211,9 @@ void ndlqr_hip_destroy(NdlqrHipCtx* c) {
   (void)hipFree(c->box_lo); (void)hipFree(c->box_hi); (void)hipFree(c->box_v); (void)hipFree(c->box_y); (void)hipFree(c->box_z);
   (void)hipFree(c->box_qr_save); (void)hipFree(c->box_rhs[0]); (void)hipFree(c->box_rhs[1]); (void)hipFree(c->box_resid);
   (void)hipFree(c->box_mask); (void)hipFree(c->box_status); (void)hipFree(c->box_iters); (void)hipFree(c->box_word);
+  (void)hipFree(c->abox_code); (void)hipFree(c->abox_v); (void)hipFree(c->abox_y); (void)hipFree(c->abox_resid);
+  (void)hipFree(c->abox_rhs[0]); (void)hipFree(c->abox_rhs[1]); (void)hipFree(c->abox_status); (void)hipFree(c->abox_iters);
+  (void)hipFree(c->abox_word);
   if (c->h_box_word) (void)hipHostFree(c->h_box_word);
   for (double* h : c->h_stage) if (h) (void)hipHostFree(h);
   if (c->ev_inputs) (void)hipEventDestroy(c->ev_inputs);
@@ -1816,6 +1820,7 @@ int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const do
   HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   if (c->h_box_word[2] || (bool)shared != c->box_shared || !c->box_have_bounds) c->box_fact = false;
+  c->box_soln_gen = 0;  // (a box adjoint needs the constrained solution of these bounds)
   c->box_shared = shared != 0;
   c->box_bstride = shared ? 0 : (size_t)d.N * d.w;
   c->box_have_bounds = true;
@@ -1968,6 +1973,7 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
     return err;
   }
   note_solution(c);
+  c->box_soln_gen = c->soln_gen;
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   std::vector<int> h_it((size_t)d.batch), h_st((size_t)d.batch);
   HIP_TRY(hipMemcpyAsync(h_it.data(), c->box_iters, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
@@ -2026,6 +2032,254 @@ int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* m
   for (int k = 0; k < 2; ++k)
     if (user[k] && !own[k]) HIP_TRY(hipMemcpyAsync(user[k], out[k], sizeof(double) * cnt[k], hipMemcpyDefault, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
+}
+
+// ------------------------------------------------------------------------------ gradients through the box-constrained solve
+// The adjoint of the active-set system (kernels_box_grad.hpp) by the ADMM of the forward on its
+// remembered shifted factorisation: QR shifted by the forward's rho on its bounded entries again (restored on every
+// exit), the kept records / factors taken as the forward left them -- nothing is factored --, every iteration one
+// re-solve into adj_z plus one box_adjoint_update. The right-hand-side columns of the kept records and slots are saved and
+// restored around it as for the plain adjoint, so the next warm-started forward finds everything as it was.
+
+int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, double eps_abs, double eps_rel, int max_iter,
+                                int check_every, int* iters, int* status) {
+  if (!c || !g || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 ||
+      check_every < 1)
+    return NDLQR_ERR_INVALID;
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_box_adjoint");
+  if (c->box_soln_gen == 0 || c->box_soln_gen != c->soln_gen || !c->box_fact || c->inputs_replaced)
+    return refuse("ndlqr_hip_solve_box_adjoint: the resident solution is not that of the latest constrained solve (a solve, "
+                  "step, re-solve, new inputs or new bounds came after it)");
+  if (!strcmp(c->box_schedule, "reduced-time-shard")) return refuse("ndlqr_hip_solve_box_adjoint: not available on a time-axis shard");
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  const Where wg = where(g, c->device);
+  if (wg == Where::OtherDevice) return refuse("ndlqr_hip_solve_box_adjoint: g lies in the memory of another device than the solver's");
+  for (const int* p : {iters, status})
+    if (p && where(p, c->device) == Where::OtherDevice)
+      return refuse("ndlqr_hip_solve_box_adjoint: iters / status lie in the memory of another device than the solver's");
+  const size_t nz = bytes_z(d), nv = sizeof(double) * (size_t)d.batch * d.N * d.w;
+  const size_t nvars = (size_t)u.rows * u.N - u.m;
+  if (!c->adj_z) {
+    HIP_TRY(hipMalloc(&c->adj_z, nz));
+    HIP_TRY(hipMemset(c->adj_z, 0, nz));  // (entries a re-solve does not write: the pad rows)
+  }
+  int aerr = box_alloc(&c->adj_rhs, nz);
+  if (!aerr) aerr = box_alloc(&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n);
+  if (!aerr) aerr = box_alloc(&c->abox_code, (size_t)d.batch * d.N * d.w);
+  if (!aerr) aerr = box_alloc(&c->abox_v, nv);
+  if (!aerr) aerr = box_alloc(&c->abox_y, nv);
+  if (!aerr) aerr = box_alloc(&c->abox_rhs[0], nz);
+  if (!aerr) aerr = box_alloc(&c->abox_rhs[1], nz);
+  if (!aerr) aerr = box_alloc(&c->abox_resid, sizeof(double) * 2 * (size_t)d.batch);
+  if (!aerr) aerr = box_alloc(&c->abox_status, sizeof(int) * (size_t)d.batch);
+  if (!aerr) aerr = box_alloc(&c->abox_iters, sizeof(int) * (size_t)d.batch);
+  if (!aerr) aerr = box_alloc(&c->abox_word, sizeof(int));
+  if (!aerr && wg != Where::OwnDevice) aerr = ensure_grad_stage(c, nvars * d.batch);
+  if (aerr) return aerr;
+  // 1. everything idle, the primary set current; g packed into the adjoint's resident right-hand side
+  HIP_TRY(sync_all(c));
+  c->cur = 0;
+  BufferSet& s = c->set[0];
+  const hipStream_t st = s.stream;
+  const double* gd = g;
+  if (wg != Where::OwnDevice) {
+    HIP_TRY(hipMemcpyAsync(c->grad_stage, g, sizeof(double) * nvars * d.batch, hipMemcpyDefault, st));
+    gd = c->grad_stage;
+  }
+  c->abox_gen = 0;
+  c->adj_gen = 0;
+  const bool strict = (c->box_flags & NDLQR_FLAG_STRICT_FP) != 0;
+  const unsigned user_flags = c->flags;
+  const double rho = c->box_rho;
+  const double* lo = c->box_lo;
+  const double* hi = c->box_hi;
+  const size_t bs = c->box_bstride;
+  HIP_TRY(hipEventRecord(s.ev_start, st));
+  hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, st, u, d, gd, c->adj_rhs);
+  int err = fail_if(hipGetLastError(), "adjoint_rhs_generic");
+  // 2. shift QR, take up the remembered shifted factorisation, save the right-hand-side columns of the records
+  if (!err) err = fail_if(hipMemcpyAsync(c->box_qr_save, c->QR, bytes_QR(d), hipMemcpyDeviceToDevice, st), "saving QR");
+  bool shifted = false;
+  if (!err) {
+    hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, lo, hi, bs, c->QR);
+    err = fail_if(hipGetLastError(), "box_shift_qr");
+    shifted = true;
+  }
+  c->flags = c->box_flags;
+  c->rec_complete = c->box_rec_complete;
+  c->rec_compact = c->box_rec_compact;
+  c->fact_valid = c->box_fact_valid;
+  c->schedule = c->box_schedule;
+  bool saved = false;
+  if (!err) {
+    err = fail_if(adjoint_scratch(c, false), "saving the record columns");
+    saved = !err;
+  }
+  // 3. codes, v = y = 0, right-hand sides, status
+  ndlqr::BoxParams P = {rho, alpha, 1.0 - alpha, eps_abs, eps_rel};
+  if (!err) err = fail_if(hipMemsetAsync(c->abox_word, 0, sizeof(int), st), "box adjoint running count");
+  if (!err) {
+    if (strict)
+      hipLaunchKernelGGL(ndlqr::box_adjoint_start<true>, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, lo, hi, bs,
+                         (const double*)c->box_v, (const int*)c->box_status, (const double*)c->adj_rhs, c->abox_code,
+                         c->abox_v, c->abox_y, c->abox_rhs[0], c->abox_rhs[1], c->abox_status, c->abox_iters, c->abox_word);
+    else
+      hipLaunchKernelGGL(ndlqr::box_adjoint_start<false>, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, lo, hi, bs,
+                         (const double*)c->box_v, (const int*)c->box_status, (const double*)c->adj_rhs, c->abox_code,
+                         c->abox_v, c->abox_y, c->abox_rhs[0], c->abox_rhs[1], c->abox_status, c->abox_iters, c->abox_word);
+    err = fail_if(hipGetLastError(), "box_adjoint_start");
+  }
+  // 4. the iterations (none when every problem's forward ended non-finite)
+  if (!err) {
+    err = fail_if(hipMemcpyAsync(&c->h_box_word[3], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st), "box adjoint running count");
+    if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
+  }
+  const bool any = !err && c->h_box_word[3] > 0;
+  for (int it = 1; it <= max_iter && any && !err; ++it) {
+    const double* rc = c->abox_rhs[(it - 1) & 1];
+    double* rn = c->abox_rhs[it & 1];
+    err = launch_resolve(c, rc, c->adj_z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
+    if (err) break;
+    if (strict)
+      hipLaunchKernelGGL(ndlqr::box_adjoint_update<true>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj_z,
+                         (const unsigned char*)c->abox_code, c->abox_v, c->abox_y, (const double*)c->adj_rhs, rc, rn,
+                         c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
+    else
+      hipLaunchKernelGGL(ndlqr::box_adjoint_update<false>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj_z,
+                         (const unsigned char*)c->abox_code, c->abox_v, c->abox_y, (const double*)c->adj_rhs, rc, rn,
+                         c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
+    err = fail_if(hipGetLastError(), "box_adjoint_update");
+    if (!err && (it % check_every == 0 || it == max_iter)) {
+      err = fail_if(hipMemcpyAsync(&c->h_box_word[3], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st), "box adjoint running count");
+      if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
+      if (!err && c->h_box_word[3] == 0) break;
+    }
+  }
+  if (!err && !any) {  // (no re-solve ran: a defined w all the same -- the re-solve of the packed g)
+    err = launch_resolve(c, c->abox_rhs[0], c->adj_z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
+    if (!err) err = fail_if(hipGetLastError(), "box adjoint re-solve");
+  }
+  // 5. w = [lambda, v], restore the record columns and QR, bookkeeping
+  if (!err) {
+    hipLaunchKernelGGL(ndlqr::box_adjoint_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, (const unsigned char*)c->abox_code,
+                       (const double*)c->abox_v, c->adj_z);
+    err = fail_if(hipGetLastError(), "box_adjoint_finish");
+  }
+  if (saved) {
+    const hipError_t re = adjoint_scratch(c, true);
+    if (!err && re != hipSuccess) err = fail("restoring the record columns", re);
+  }
+  if (shifted) {
+    const hipError_t re = hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(d), hipMemcpyDeviceToDevice, st);
+    if (!err && re != hipSuccess) err = fail("restoring QR", re);
+  }
+  c->flags = user_flags;
+  c->rec_complete = false;  // (as the constrained solve left them: the kept records / factors are the shifted ones)
+  c->fact_valid = false;
+  if (err) {
+    c->state_dirty = true;
+    (void)hipStreamSynchronize(st);
+    return err;
+  }
+  HIP_TRY(hipEventRecord(s.ev_stop, st));
+  std::vector<int> h_it((size_t)d.batch), h_st((size_t)d.batch);
+  HIP_TRY(hipMemcpyAsync(h_it.data(), c->abox_iters, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_st.data(), c->abox_status, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
+  c->adj_gen = c->soln_gen;
+  c->abox_gen = c->soln_gen;
+  for (int& v : h_st)
+    if (v == 0) v = 2;  // max_iter reached: the last iterate
+  int* user[2] = {iters, status};
+  const std::vector<int>* val[2] = {&h_it, &h_st};
+  for (int k = 0; k < 2; ++k) {  // (host or this device's memory)
+    if (!user[k]) continue;
+    if (where(user[k], c->device) == Where::OwnDevice)
+      HIP_TRY(hipMemcpy(user[k], val[k]->data(), sizeof(int) * (size_t)d.batch, hipMemcpyHostToDevice));
+    else
+      memcpy(user[k], val[k]->data(), sizeof(int) * (size_t)d.batch);
+  }
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* gxhi, double* gulo, double* guhi) {
+  if (!c) return NDLQR_ERR_INVALID;
+  const int aerr = need_adjoint(c, "ndlqr_hip_bound_gradients");
+  if (aerr) return aerr;
+  if (c->abox_gen != c->soln_gen)
+    return refuse("ndlqr_hip_bound_gradients: no box adjoint of the resident solution (ndlqr_hip_solve_box_adjoint after the "
+                  "latest constrained solve)");
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  double* user[4] = {gxlo, gxhi, gulo, guhi};
+  const size_t P = summed ? 1 : (size_t)d.batch;
+  const size_t cnt[4] = {P * u.N * u.n, P * u.N * u.n, P * u.N * u.m, P * u.N * u.m};
+  bool own[4] = {};
+  size_t stage = 0;
+  bool anyout = false;
+  for (int k = 0; k < 4; ++k) {
+    if (!user[k]) continue;
+    anyout = true;
+    const Where w = where(user[k], c->device);
+    if (w == Where::OtherDevice)
+      return refuse("ndlqr_hip_bound_gradients: an output lies in the memory of another device than the solver's");
+    own[k] = w == Where::OwnDevice;
+    if (!own[k]) stage += cnt[k];
+  }
+  if (!anyout) return NDLQR_OK;
+  // batch sums: entries of [N][n+m] one per thread, the batch split into about 2048 / ceil(entries / 256) runs of problems
+  // added in order, then the runs in order (grad_assemble's scheme: deterministic, no atomics)
+  const size_t E = (size_t)u.N * (u.n + u.m);
+  const unsigned nblk = (unsigned)((E + 255) / 256);
+  int nsplit = 1, ppb = d.batch;
+  if (summed) {
+    nsplit = (int)(2048 / nblk);
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > d.batch) nsplit = d.batch;
+    ppb = (d.batch + nsplit - 1) / nsplit;
+    nsplit = (d.batch + ppb - 1) / ppb;
+  }
+  const size_t npart = nsplit > 1 ? (size_t)nsplit * 2 * E : 0;
+  {
+    const int serr = ensure_grad_stage(c, stage + npart);
+    if (serr) return serr;
+  }
+  HIP_TRY(sync_all(c));
+  BufferSet& s = c->set[0];
+  ndlqr::BoundOut out = {};
+  double* at = c->grad_stage;
+  for (int k = 0; k < 4; ++k) {
+    if (!user[k]) continue;
+    out.p[k] = own[k] ? user[k] : at;
+    if (!own[k]) at += cnt[k];
+  }
+  double* part = npart ? at : nullptr;
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  if (!summed) {
+    hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, c->box_rho,
+                       (const unsigned char*)c->abox_code, (const double*)c->abox_y, out);
+    HIP_TRY(hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(ndlqr::box_bound_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d, c->box_rho, ppb,
+                       (const unsigned char*)c->abox_code, (const double*)c->abox_y, out, part);
+    HIP_TRY(hipGetLastError());
+    if (part) {
+      hipLaunchKernelGGL(ndlqr::box_bound_sum_splits, dim3(nblk), dim3(256), 0, s.stream, u, nsplit, (const double*)part, out);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
+  for (int k = 0; k < 4; ++k)
+    if (user[k] && !own[k]) HIP_TRY(hipMemcpyAsync(user[k], out.p[k], sizeof(double) * cnt[k], hipMemcpyDefault, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
   return NDLQR_OK;
 }
 
