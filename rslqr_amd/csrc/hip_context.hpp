@@ -102,6 +102,7 @@ struct NdlqrHipCtx {
   double* F = nullptr;  // complete factor array; allocated by the first solve whose schedule touches it (ndlqr_hip_ensure_F)
   int rowbcast = -1;  // bottom levels of the separator-only schedule on the row-broadcast core (rb_bottom): NDLQR_ROWBCAST=1 always, 0 never (bottom_reduced_mc), unset (-1): by block size
   int tree = -1;  // tree schedule (bottom_reduced_mc<TREE>: one launch for the whole factorisation, wavefronts climbing on arrival counters): NDLQR_TREE=1 always, 0 never, unset (-1): when all bottom wavefronts are resident at once (small batches: fewer launches win; large ones: a launch per level is faster)
+  int backsub_cols = -1;  // rb_backsub at nstates + ninputs <= 16: the body with [A | B] in registers (rb_backsub_cols, block 128) unless NDLQR_BACKSUB_COLS=0 asks for the LDS-staged one
   int fuse2 = -1;  // tree level 2 inside the bottom launch (bottom8_reduced_mc) instead of as a launch of its own: NDLQR_FUSE2=1 always, 0 never, unset (-1): where it measured faster -- the (12,4) instance (launch_small.hpp)
   BufferSet set[2];     // the two-deep solve pipeline: [0] the primary set, [1] the alternate (allocated on first use)
   int cur = 0;          // the set the next launches go to

@@ -518,7 +518,8 @@ __global__ __launch_bounds__(256) void rb_backsub_top(Dims d, const double* __re
   backsub_top_body<NX>(d, blockIdx.x, threadIdx.x, recs, ytop, ytop_lds);
 }
 
-//   rb_backsub: grid (N / 8, batch), block 256; N >= 8. A workgroup needs nothing of its neighbours' (the two multipliers
+//   rb_backsub: grid (N / 8, batch), block 256 for the body below, 128 for rb_backsub_cols (instances with NX + NU <= 16:
+//   launch_rb_backsub); N >= 8. A workgroup needs nothing of its neighbours' (the two multipliers
 //   next to its subtree come from `ytop`): a step that wants a knot range alone launches the workgroups of that range
 //   (Dims::xoff = the first one, a shorter grid: NDLQR_SOLN_ONLY, launch_small.hpp).
 // Everything the workgroup needs ([A | B] of its eight knots, its seven records, weights, right-hand
@@ -542,11 +543,12 @@ struct alignas(16) RbBacksubLds {
 
 // MULTI (several right-hand sides per problem, kernels below): grid.y counts right-hand sides, b % nprob is the problem whose
 // inputs and records are read, z_sep of the level-1 / 2 separators come from zsep[b][N][NX] instead of the records.
-template <int NX, int NU, bool MULTI = false>
-__global__ __launch_bounds__(256) void rb_backsub(Dims d, const double* __restrict__ AB, const double* __restrict__ QR,
+// (the body of the instances with NX + NU > 16, and of the others with NDLQR_BACKSUB_COLS=0; default there: rb_backsub_cols below)
+template <int NX, int NU, bool MULTI>
+__device__ __forceinline__ void rb_backsub_staged(const Dims& d, const double* __restrict__ AB, const double* __restrict__ QR,
                                                   const double* __restrict__ rhs, const double* __restrict__ recs,
                                                   const double* __restrict__ ytop, double* __restrict__ z,
-                                                  const int nprob = 0, const double* __restrict__ zsep = nullptr) {
+                                                  const int nprob, const double* __restrict__ zsep) {
   using Lds = RbBacksubLds<NX, NU>;
   constexpr int W = NX + NU, ROWS = 2 * NX + NU, NN = NX * NX, REC = 2 * NN + NX, KPB = 8, WP = Lds::WP;
   constexpr int R0 = Lds::R0;
@@ -764,6 +766,216 @@ __global__ __launch_bounds__(256) void rb_backsub(Dims d, const double* __restri
     out = (i == N - 1) ? rv : (rv - dot) * lds.qs[kn][rr - NX];
   }
   z[((size_t)b * N + i) * ROWS + rr] = out;
+}
+
+template <int NX>  // (below, with the re-solve that shares it)
+__device__ __forceinline__ double rb_llt_solve(double x, const double (&lrow)[NX], const double (&lcol)[NX], const double dinv);
+
+// 1 / x to the last bit or two: v_rcp_f64 (about 2^-24 relative) and two Newton steps, ten instructions where the
+// IEEE division sequence has about thirty.
+__device__ __forceinline__ double rb_rcp(const double x) {
+  double y = __builtin_amdgcn_rcp(x);
+  y = fma(fma(-x, y, 1.0), y, y);
+  return fma(fma(-x, y, 1.0), y, y);
+}
+
+// rb_backsub at NX + NU <= 16: [A | B] in registers, one 16-lane DPP row per knot, block 128.
+//   wavefront 0: the even knots first + 0, 2, 4, 6 in its rows 0..3, wavefront 1: the odd knots first + 1, 3, 5, 7.
+//   Lane (knot k, column c) holds column c of [A_k | B_k] (NX registers, loaded straight from global memory: the
+//   sixteen lanes of a row read one contiguous row of the matrix per load), 1 / [Q | R](c), and the two right-hand-side
+//   rows lambda(c), cost(c) of its knot: the products [A_k | B_k]' y_k and the solution rows x(c) / u(c), lambda(c) need
+//   nothing else but multipliers from LDS.
+//   Wavefront 1 resolves the separators of level 2 and 1 (rows of its lanes: first + 3 in row 1, then first + 1 and
+//   first + 5 in rows 0 and 2), dots its knots with their multipliers and leaves what knot s + 1 contributes to v(s)
+//   in lds.wv. Wavefront 0 then forms v = [A_s | B_s] z-hat: every lane multiplies its column by its z-hat(c), the
+//   products cross LDS once (lds.prod, in the bytes of the records of level 1 / 2, which are spent by then) and lane r
+//   adds up row r -- a transposed sum; fp64 DPP on gfx950 has row_newbcast alone, a butterfly of 32-bit moves and
+//   selects costs twice the instructions. The four substitutions run where the sums land. Three workgroup barriers.
+constexpr int kRbBacksubColsThreads = 128;
+
+template <int NX, int NU>
+struct alignas(16) RbBacksubColsLds {
+  static constexpr int NN = NX * NX, REC = 2 * NN + NX, R0 = NX * (NX + 1) / 2;
+  static constexpr int R0P = (R0 + 1) / 2 * 2, RECP = REC + (REC & 1);
+  static constexpr int TS = 17;  // row pitch of the products: odd, the sixteen lanes of a row read sixteen banks
+  double rec0[4][R0P];    // level-0 separators first + 0, 2, 4, 6: Cholesky factor of S-bar, packed lower triangle
+  union {
+    double rec1[3][RECP];  // separators first + 1, first + 3, first + 5: f_a | f_bb | z_sep
+    double prod[4][NX * TS];  // [even knot][row r][column c]: [A | B](r, c) z-hat(c)
+  };
+  double ys[9][NX];       // [0..6]: separators first .. first + 6; [7]: first - 1; [8]: first + 7
+  double wv[4][NX];       // z(s+1).lambda + (cost(s+1) - A_{s+1}' y_{s+1}) / Q_{s+1} of the four odd knots
+};
+
+// e / SZ for e < 4 SZ (which of up to four records a staged word belongs to): three compares instead of a multiply-high
+template <int SZ>
+__device__ __forceinline__ int rec_of(const int e) { return (e >= SZ) + (e >= 2 * SZ) + (e >= 3 * SZ); }
+
+template <int NX, int NU, bool MULTI>
+__device__ __forceinline__ void rb_backsub_cols(const Dims& d, const double* __restrict__ AB, const double* __restrict__ QR,
+                                                const double* __restrict__ rhs, const double* __restrict__ recs,
+                                                const double* __restrict__ ytop, double* __restrict__ z,
+                                                const int nprob, const double* __restrict__ zsep) {
+  using Lds = RbBacksubColsLds<NX, NU>;
+  constexpr int W = NX + NU, ROWS = 2 * NX + NU, NN = NX * NX, REC = 2 * NN + NX, KPB = 8, R0 = Lds::R0, TS = Lds::TS;
+  constexpr int NT = kRbBacksubColsThreads;  // two wavefronts (four measured slower at every instance: DESIGN.md section 7)
+  static_assert(W <= 16 && NT == 128 && 3 * NX <= NT, "thread roles fit the workgroup");
+  __shared__ Lds lds;
+  const int N = d.N, b = blockIdx.y, first = (blockIdx.x + d.xoff) * KPB;
+  const int bp = MULTI ? b % nprob : b;  // the problem whose inputs and records this right-hand side is solved against
+  const int t = threadIdx.x;
+  const int odd = t >> 6, j = (t >> 4) & 3, c = t & 15;
+  const int k = 2 * j + odd, i = first + k;     // this row's knot
+  const int cw = c < W ? c : W - 1, cx = c < NX ? c : NX - 1;
+
+  // ---- one round of loads: columns, weights and right-hand sides into registers, records into LDS
+  double a[NX];
+  const double* abk = AB + ((size_t)bp * N + i) * NX * W + cw;
+#pragma unroll
+  for (int r = 0; r < NX; ++r) a[r] = abk[r * W];
+  const double tq = QR[((size_t)bp * N + i) * W + cw];
+  const double* rk = rhs + ((size_t)b * N + i) * ROWS;
+  const double tl = rk[cx], tg = rk[NX + cw];
+  {
+    const double* rc0 = recs + ((size_t)bp * N + first) * REC;
+    constexpr bool WIDE = NX % 2 == 0 && R0 % 2 == 0;
+    constexpr int G = WIDE ? 2 : 1;                                             // doubles per record load
+    constexpr int N0 = 4 * R0 / G, I0 = (N0 + NT - 1) / NT, N1 = 3 * REC / G, I1 = (N1 + NT - 1) / NT;
+    double t0[I0][G], t1[I1][G];
+#pragma unroll
+    for (int it = 0; it < I0; ++it) {
+      const int e = t + NT * it, ec = e < N0 ? e : N0 - 1, q = rec_of<R0 / G>(ec), w_ = ec - q * (R0 / G);
+      const double* src = rc0 + (size_t)(2 * q) * REC + G * w_;
+      if constexpr (WIDE) { const double2 v = *reinterpret_cast<const double2*>(src); t0[it][0] = v.x; t0[it][1] = v.y; }
+      else t0[it][0] = *src;
+    }
+#pragma unroll
+    for (int it = 0; it < I1; ++it) {
+      const int e = t + NT * it, ec = e < N1 ? e : N1 - 1, q = rec_of<REC / G>(ec), w_ = ec - q * (REC / G);
+      const double* src = rc0 + (size_t)(2 * q + 1) * REC + G * w_;
+      if constexpr (WIDE) { const double2 v = *reinterpret_cast<const double2*>(src); t1[it][0] = v.x; t1[it][1] = v.y; }
+      else t1[it][0] = *src;
+    }
+    double tz = 0.0;
+    if constexpr (MULTI) {  // z_sep of separators first + 1, + 3, + 5 of THIS right-hand side
+      const int e = t < 3 * NX ? t : 3 * NX - 1, q = e / NX;
+      tz = zsep[((size_t)b * N + first + 2 * q + 1) * NX + (e - q * NX)];
+    }
+    double ty = 0.0;
+    if (t < 2 * NX) {  // the two multipliers next to the workgroup's subtree
+      const int sx = t < NX ? first - 1 : first + 7;
+      if (sx >= 0 && sx < N - 1) ty = ytop[((size_t)b * (N >> 3) + (sx >> 3)) * NX + (t < NX ? t : t - NX)];
+    }
+#pragma unroll
+    for (int it = 0; it < I0; ++it) {
+      const int e = t + NT * it, ec = e < N0 ? e : N0 - 1, q = rec_of<R0 / G>(ec), w_ = ec - q * (R0 / G);
+#pragma unroll
+      for (int h = 0; h < G; ++h) lds.rec0[q][G * w_ + h] = t0[it][h];
+    }
+#pragma unroll
+    for (int it = 0; it < I1; ++it) {
+      const int e = t + NT * it, ec = e < N1 ? e : N1 - 1, q = rec_of<REC / G>(ec), w_ = ec - q * (REC / G);
+      // (MULTI: the records carry the z_sep of whatever right-hand side was solved last; this one's come from zsep.
+      //  WIDE: 2 NN is even, no word holds both an entry of f_bb and one of z_sep)
+      if (!MULTI || G * w_ < 2 * NN) {
+#pragma unroll
+        for (int h = 0; h < G; ++h) lds.rec1[q][G * w_ + h] = t1[it][h];
+      }
+    }
+    if (t < 2 * NX) lds.ys[t < NX ? 7 : 8][t < NX ? t : t - NX] = ty;
+    if constexpr (MULTI) {
+      if (t < 3 * NX) lds.rec1[t / NX][2 * NN + t % NX] = tz;
+    }
+  }
+  const double qinv = rb_rcp(tq);  // 1 / [Q | R](c) of this lane's knot
+  __syncthreads();
+
+  double dot = 0.0;  // column c of [A_i | B_i] times y_i
+  auto ab_dot = [&](const double* y) {
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < NX; ++r) s = fma(a[r], y[r], s);
+    return s;
+  };
+  if (odd) {
+    // ---- wavefront 1: multipliers of the local separators of level 2, then 1
+    auto resolve = [&](const int q, const bool hasA, const int slotA, const bool hasB, const int slotB) {
+      const double* rc = lds.rec1[q >> 1];
+      double s = rc[2 * NN + c];
+      if (hasA) {
+#pragma unroll
+        for (int e = 0; e < NX; ++e) s = fma(-rc[c * NX + e], lds.ys[slotA][e], s);
+      }
+      if (hasB) {
+#pragma unroll
+        for (int e = 0; e < NX; ++e) s = fma(-rc[NN + c * NX + e], lds.ys[slotB][e], s);
+      }
+      lds.ys[q][c] = s;
+    };
+    const bool left = first > 0, right = first + KPB < N;
+    if (j == 1 && c < NX) resolve(3, left, 7, right, 8);
+    wave_lds_sync();
+    if (j == 0 && c < NX) resolve(1, left, 7, true, 3);
+    if (j == 2 && c < NX) resolve(5, true, 3, right, 8);
+    wave_lds_sync();
+    // ---- its knots' [A_i | B_i]' y_i (the last knot of the horizon has neither), and what they add to v(i - 1)
+    if (i < N - 1) dot = ab_dot(lds.ys[k < 7 ? k : 8]);
+    if (c < NX) lds.wv[j][c] = tl + (tg - dot) * qinv;
+  }
+  __syncthreads();
+  if (!odd) {
+    // ---- wavefront 0, level-0 separators: v = [A_s | B_s] z-hat(s) - r_a y_{s-1} - wv, then y = L^-T L^-1 v
+    const double ya = (i > 0 && c < NX) ? lds.ys[k > 0 ? k - 1 : 7][cx] : 0.0;
+    const double zh = (i == 0 && c < NX) ? -tl : (tg + ya) * qinv;  // z-hat(c) + what r_a y_{s-1} contributes through column c
+    if (c < W) {
+#pragma unroll
+      for (int r = 0; r < NX; ++r) lds.prod[j][r * TS + c] = a[r] * zh;
+    }
+    wave_lds_sync();
+    const double* pr = lds.prod[j] + cx * TS;
+    double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+    for (int m = 0; m + 1 < W; m += 2) { v0 += pr[m]; v1 += pr[m + 1]; }
+    if constexpr (W % 2) v0 += pr[W - 1];
+    double x = (v0 + v1) - lds.wv[j][cx];
+    // the four separators in the four DPP rows, row c of L per lane; both substitutions broadcast the freshly resolved
+    // entry inside the row. (All 64 lanes run it -- DPP needs them active --, lanes c >= NX idle.)
+    const double* Lp = lds.rec0[j];
+    const double dinv = rb_rcp(Lp[cx * (cx + 1) / 2 + cx]);
+    double lrow[NX], lcol[NX];
+#pragma unroll
+    for (int e = 0; e < NX; ++e) {
+      const double lo = Lp[cx * (cx + 1) / 2 + (e < cx ? e : cx)];                  // L(c, e), e < c
+      const double up = Lp[(e > cx ? e : cx) * ((e > cx ? e : cx) + 1) / 2 + cx];  // L(e, c), e > c
+      lrow[e] = (e < c && c < NX) ? lo : 0.0;
+      lcol[e] = (e > c && c < NX) ? up : 0.0;
+    }
+    x = rb_llt_solve<NX>(x, lrow, lcol, dinv);
+    if (c < NX) lds.ys[2 * j][c] = x;
+    wave_lds_sync();
+    dot = ab_dot(lds.ys[k]);  // (an even knot is never the last one)
+  }
+  __syncthreads();
+
+  // ---- solution rows: lambda(c), then x(c) / u(c)
+  const double yp = (i > 0 && c < NX) ? lds.ys[k > 0 ? k - 1 : 7][cx] : 0.0;  // y_{i-1}(c)
+  double* zi = z + ((size_t)b * N + i) * ROWS;
+  if (c < NX) {
+    zi[c] = (i == 0) ? fma(-tq, tl, -tg) + dot : yp;
+    zi[NX + c] = (i == 0) ? -tl : (tg - dot + yp) * qinv;
+  } else if (c < W) {
+    zi[NX + c] = (i == N - 1) ? tg : (tg - dot) * qinv;
+  }
+}
+
+// COLS: rb_backsub_cols (NX + NU <= 16 only), block kRbBacksubColsThreads; else rb_backsub_staged, block 256
+template <int NX, int NU, bool MULTI = false, bool COLS = false>
+__global__ __launch_bounds__(COLS ? kRbBacksubColsThreads : 256) void rb_backsub(
+    Dims d, const double* __restrict__ AB, const double* __restrict__ QR, const double* __restrict__ rhs,
+    const double* __restrict__ recs, const double* __restrict__ ytop, double* __restrict__ z, const int nprob = 0,
+    const double* __restrict__ zsep = nullptr) {
+  if constexpr (COLS) rb_backsub_cols<NX, NU, MULTI>(d, AB, QR, rhs, recs, ytop, z, nprob, zsep);
+  else rb_backsub_staged<NX, NU, MULTI>(d, AB, QR, rhs, recs, ytop, z, nprob, zsep);
 }
 
 // ------------------------------------------------------------------------------------- right-hand-side re-solve (round 4)

@@ -40,6 +40,21 @@ static inline ndlqr::Dims apply_dims(const NdlqrHipCtx* c, const ndlqr::Dims& d)
   return da;
 }
 
+// Last launch of the two-launch back-substitution. Instances with nstates + ninputs <= 16 have two bodies (DESIGN.md
+// section 3.4): the one that keeps [A | B] in registers -- the default: same-box A/B against the staged body at
+// (12,4), (10,4), (9,3), (8,4), (6,3) x 1024 and (12,4,1024) x 512, faster at each -- and,
+// with NDLQR_BACKSUB_COLS=0, the LDS-staged one that the larger instances run.
+template <int NX, int NU, bool MULTI, class... Args>
+static void launch_rb_backsub(const NdlqrHipCtx* c, const dim3 grid, hipStream_t stream, Args... args) {
+  if constexpr (NX + NU <= 16) {
+    if (c->backsub_cols != 0) {
+      hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, MULTI, true>), grid, dim3(ndlqr::kRbBacksubColsThreads), 0, stream, args...);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, MULTI, false>), grid, dim3(256), 0, stream, args...);
+}
+
 template <int NX, int NU, bool STRICT, bool KEEP>
 static SmallPlan plan_small(const NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
@@ -164,7 +179,7 @@ static int launch_small(NdlqrHipCtx* c) {
           hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), top_lds, s.stream, d, s.rec, s.ytop);
         }
         // (an MPC step that asked for nothing but a knot range -- NDLQR_SOLN_ONLY -- runs the workgroups of that range)
-        hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream,
+        launch_rb_backsub<NX, NU, false>(c, dim3(apply_grid(c, d), d.batch), s.stream,
                            apply_dims(c, d), c->AB, c->QR, s.rhs, s.rec, s.ytop, s.z);
       } else {
         hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream, apply_dims(c, d), c->AB,
@@ -224,7 +239,7 @@ static void launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
                            rhs, s.rec, (const double*)s.red, s.ytop);
       }
       ScopedSlot t(c, SLOT_APPLY);
-      hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream,
+      launch_rb_backsub<NX, NU, false>(c, dim3(apply_grid(c, d), d.batch), s.stream,
                          apply_dims(c, d), c->AB, c->QR, rhs, s.rec, s.ytop, z);
       return;
     }
@@ -267,7 +282,7 @@ static bool launch_multi_rhs(NdlqrHipCtx* c, const int count, const double* rhs,
     hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU, true>), dim3(count), dim3(256), lds, s.stream, d, c->AB, c->QR, rhs,
                        s.rec, (const double*)fsum, ytop, d.batch, zsep);
     // (a knot range alone: ndlqr_hip_solve_multi_rhs_slices)
-    hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, true>), dim3(apply_grid(c, d), count), dim3(256), 0, s.stream,
+    launch_rb_backsub<NX, NU, true>(c, dim3(apply_grid(c, d), count), s.stream,
                        apply_dims(c, d), c->AB, c->QR, rhs, (const double*)s.rec, (const double*)ytop, z, d.batch,
                        (const double*)zsep);
     return true;
@@ -339,7 +354,7 @@ static int launch_time_shard(NdlqrHipCtx* c, const int phase, const int g, const
       hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), top_lds, bs.stream, d, bs.rec, bs.ytop);
       const int cnt = (d.N >> 3) / G;
       d.xoff = g * cnt;
-      hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU>), dim3(cnt, d.batch), dim3(256), 0, bs.stream, d, c->AB, c->QR,
+      launch_rb_backsub<NX, NU, false>(c, dim3(cnt, d.batch), bs.stream, d, c->AB, c->QR,
                          bs.rhs, bs.rec, bs.ytop, bs.z);
     }
     c->schedule = "reduced-time-shard";

@@ -151,6 +151,7 @@ NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int bat
   if (getenv("NDLQR_TREE")) c->tree = atoi(getenv("NDLQR_TREE")) != 0 ? 1 : 0;  // unset: by batch size
   if (getenv("NDLQR_ROWBCAST")) c->rowbcast = atoi(getenv("NDLQR_ROWBCAST")) != 0 ? 1 : 0;  // unset: by block size
   if (getenv("NDLQR_FUSE2")) c->fuse2 = atoi(getenv("NDLQR_FUSE2")) != 0 ? 1 : 0;  // unset: by instance (launch_small)
+  if (getenv("NDLQR_BACKSUB_COLS")) c->backsub_cols = atoi(getenv("NDLQR_BACKSUB_COLS")) != 0 ? 1 : 0;
   c->no_mfma = getenv("NDLQR_NO_MFMA") != nullptr;
   c->no_top = getenv("NDLQR_NO_TOP") != nullptr;
   if (getenv("NDLQR_TOP_LEVELS")) c->top_levels = atoi(getenv("NDLQR_TOP_LEVELS"));
