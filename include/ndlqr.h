@@ -530,7 +530,17 @@ int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, do
  *   factorisation in fast mode, NDLQR_FLAG_KEEP_FACT in strict mode), padded shapes included; strict mode is
  *   bit-reproducible (DESIGN.md section 3.9 gives the operation order).
  *   ndlqr_CopyBatchBoundMultipliers: mu = rho y, mu_x [batch][N][n], mu_u [batch][N][m] (either may be NULL): >= 0 where the
- *   upper bound is active, <= 0 at the lower one, 0 inside; z solves the unconstrained problem with q + mu_x, r + mu_u. */
+ *   upper bound is active, <= 0 at the lower one, 0 inside; z solves the unconstrained problem with q + mu_x, r + mu_u.
+ *   Adaptive penalty (adapt_every > 0): rho is per problem, started at the settings' rho. At every
+ *   adapt_every-th iteration a running problem takes k = (ilogb(r_prim / s_prim) - ilogb(r_dual / s_dual)) / 2, clamped to
+ *   [-6, 6] (r: its residuals, s: the scales of the convergence test above), and for k != 0 moves to rho 2^k within
+ *   [rho_min, rho_max], y scaled so that mu = rho y stays; the batch is factored again in every round in which a problem
+ *   moved. With warm_start, while the remembered factorisation applies (same pattern, A, B, Q, R and flags), the solve
+ *   starts from the penalties the previous one ended with and factors nothing -- the settings' rho is ignored, an MPC
+ *   loop keeps what it learnt; otherwise every problem starts at the settings' rho. A fixed-rho solve reuses a
+ *   remembered factorisation only when all its penalties are that rho. iters and status keep their meaning.
+ *   adapt_every < 0 or rho_min > rho_max: NDLQR_ERR_INVALID. ndlqr_CopyBatchBoxPenalties: rho [batch] of the latest
+ *   constrained solve (host, pinned or the solver's device memory). */
 typedef struct {
   double rho;       /* penalty; 0 -> 0.1 */
   double alpha;     /* over-relaxation in (0, 2); 0 -> 1.6 */
@@ -539,19 +549,23 @@ typedef struct {
   int max_iter;     /* 0 -> 4000 */
   int check_every;  /* host looks at the convergence count every this many iterations; 0 -> 10 */
   int warm_start;   /* start from v, y of the previous constrained solve (same bounds pattern) */
+  int adapt_every;  /* per-problem adaptive penalty, considered every this many iterations; 0 -> fixed rho */
+  double rho_min;   /* clamp of the adaptive penalty; 0 -> 1e-6 */
+  double rho_max;   /* 0 -> 1e6 */
 } NdLqrBoxSettings; /* zero-initialised = all defaults; NULL = all defaults */
 #define NDLQR_BOUNDS_SHARED 1u /* bounds arrays are [N][..], one set for every problem */
 int ndlqr_BatchSetBounds(NdLqrBatchSolver* bs, unsigned flags, const double* xlo, const double* xhi, const double* ulo,
                          const double* uhi);
 int ndlqr_SolveBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status);
 int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u);
+int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho);
 /* additive: gradients through the box-constrained solve (differentiable MPC with actuator and state limits). After
  * ndlqr_SolveBatchBoxConstrained, for a loss L(z*) of the constrained solutions and g = dL/dz* (as for
  * ndlqr_SolveBatchAdjoint), ndlqr_SolveBatchBoxAdjoint solves the adjoint of the active-set system
  *     K w + E_A' nu = g,   E_A w = 0
  * (A: the bounded entries whose projected iterate lies exactly on a bound; E_A picks them) by the same ADMM on the
- * forward's kept shifted factorisation -- same rho, cold start, nothing factored. The settings' rho and warm_start are
- * ignored; alpha, eps_abs, eps_rel, max_iter and check_every (0: the defaults of the forward) apply, and iters / status
+ * forward's kept shifted factorisation -- the penalties the forward ended with, cold start, nothing factored, nothing
+ * adapted. The settings' rho, warm_start, adapt_every, rho_min and rho_max are ignored; alpha, eps_abs, eps_rel, max_iter and check_every (0: the defaults of the forward) apply, and iters / status
  * report as for the forward. A problem whose forward ended as 3 is not iterated and reports 3. Afterwards
  * ndlqr_CopyBatchAdjoint returns w and ndlqr_BatchGradients dL/d(A, B, Q, R, q, r, d, x0) at the constrained solution,
  * as after ndlqr_SolveBatchAdjoint. ndlqr_BatchBoundGradients returns dL/dc_A = nu: entry i goes to dL/dhi_i when the

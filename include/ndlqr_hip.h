@@ -107,16 +107,25 @@ int ndlqr_hip_gradients(NdlqrHipCtx* ctx, unsigned sum_mask, double* gA, double*
  * ndlqr_SolveBatchBoxConstrained, ndlqr_CopyBatchBoundMultipliers). Bounds in the flat layout,
  * [batch][N][n] / [batch][N][m], or [N][..] once for every problem when `shared`; NULL = unbounded; host, pinned or this
  * device's memory. ndlqr_hip_solve_box takes the resolved settings (no zero defaults here) and blocks; iters / status
- * [batch] may be NULL. Multipliers mu = rho y in the flat layout. ndlqr_hip_factor_count: factorisations launched by
+ * [batch] may be NULL. Multipliers mu = rho_p y in the flat layout (rho_p: the penalty of problem p). ndlqr_hip_factor_count: factorisations launched by
  * this context so far (tests: a constrained solve that reuses the remembered shifted factorisation launches none). */
 int ndlqr_hip_set_bounds(NdlqrHipCtx* ctx, int shared, const double* xlo, const double* xhi, const double* ulo,
                          const double* uhi);
 int ndlqr_hip_solve_box(NdlqrHipCtx* ctx, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
                         int check_every, int warm_start, int* iters, int* status);
+/* ndlqr_hip_solve_box_ex: the same with a per-problem adaptive penalty: adapt_every > 0 lets
+ * every running problem move its rho by a power of two at every adapt_every-th iteration, within [rho_min, rho_max]
+ * (resolved: 0 < rho_min <= rho_max), and the batch is factored again whenever one did; adapt_every == 0 is
+ * ndlqr_hip_solve_box. ndlqr_hip_download_box_penalties: rho [batch] of the latest constrained solve (host, pinned or
+ * this device's memory). */
+int ndlqr_hip_solve_box_ex(NdlqrHipCtx* ctx, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
+                           int check_every, int warm_start, int* iters, int* status, int adapt_every, double rho_min,
+                           double rho_max);
+int ndlqr_hip_download_box_penalties(NdlqrHipCtx* ctx, double* rho);
 int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* ctx, double* mu_x, double* mu_u);
 unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* ctx);
 /* Gradients through the box-constrained solve (ndlqr.h: ndlqr_SolveBatchBoxAdjoint, ndlqr_BatchBoundGradients;
- * DESIGN.md section 3.10). ndlqr_hip_solve_box_adjoint takes the resolved settings (the forward's rho, a cold start) and
+ * DESIGN.md section 3.10). ndlqr_hip_solve_box_adjoint takes the resolved settings (the forward's final penalties, a cold start) and
  * blocks; g as for ndlqr_hip_solve_adjoint, iters / status [batch] may be NULL. Afterwards ndlqr_hip_download_adjoint and
  * ndlqr_hip_gradients read its w as they read a plain adjoint. ndlqr_hip_bound_gradients: dL/d(xlo, xhi, ulo, uhi) in the
  * flat layout, per problem or (summed) over the batch, [N][n] / [N][m]; NULL = not computed. */

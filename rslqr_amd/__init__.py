@@ -30,6 +30,7 @@ from .api import (  # noqa: F401
     NdData,
     NdFactor,
     NdLqrBoxSettings,
+    NdLqrBoxSettingsFull,
     NdLqrSolver,
     SOLN_INPUT,
     SOLN_ONLY,

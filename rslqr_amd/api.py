@@ -112,8 +112,17 @@ class NdLqrSolver(C.Structure):
 
 
 class NdLqrBoxSettings(C.Structure):
+    """The seven fixed-penalty fields of the C NdLqrBoxSettings, at the size that struct had before the adaptive-penalty
+    fields were appended: kept for code that builds or inspects it. The library calls take NdLqrBoxSettingsFull (ctypes
+    refuses a pointer to this shorter struct: the C side reads all ten fields)."""
     _fields_ = [("rho", C.c_double), ("alpha", C.c_double), ("eps_abs", C.c_double), ("eps_rel", C.c_double),
                 ("max_iter", C.c_int), ("check_every", C.c_int), ("warm_start", C.c_int)]
+
+
+class NdLqrBoxSettingsFull(C.Structure):
+    """NdLqrBoxSettings of include/ndlqr.h as it is now: the seven fields above, then adapt_every, rho_min, rho_max
+    (positional construction with the first seven leaves those zero: the fixed penalty)."""
+    _fields_ = NdLqrBoxSettings._fields_ + [("adapt_every", C.c_int), ("rho_min", C.c_double), ("rho_max", C.c_double)]
 
 
 BOUNDS_SHARED = 1
@@ -266,9 +275,10 @@ def lib():
     proto("ndlqr_BatchGradients", ci, vp, C.c_uint, dp, dp, dp, dp, dp, dp, dp, dp)
     proto("ndlqr_BatchDeviceContext", vp, vp)
     proto("ndlqr_BatchSetBounds", ci, vp, C.c_uint, dp, dp, dp, dp)
-    proto("ndlqr_SolveBatchBoxConstrained", ci, vp, C.POINTER(NdLqrBoxSettings), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_SolveBatchBoxConstrained", ci, vp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_CopyBatchBoundMultipliers", ci, vp, dp, dp)
-    proto("ndlqr_SolveBatchBoxAdjoint", ci, vp, dp, C.POINTER(NdLqrBoxSettings), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_CopyBatchBoxPenalties", ci, vp, dp)
+    proto("ndlqr_SolveBatchBoxAdjoint", ci, vp, dp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_BatchBoundGradients", ci, vp, C.c_uint, dp, dp, dp, dp)
     proto("ndlqr_hip_factor_count", C.c_ulonglong, vp)
     # shim bits used by the benchmark
@@ -633,10 +643,14 @@ class BatchSolver:
         if err:
             raise RuntimeError("ndlqr_BatchSetBounds failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
 
-    def solve_box(self, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0, warm_start=False):
-        """ndlqr_SolveBatchBoxConstrained (0 = the library's default for every setting). Returns (iters, status) as numpy
-        int arrays [batch]; status 1 = converged, 2 = max_iter reached. Raises on a nonzero return."""
-        st = NdLqrBoxSettings(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0)
+    def solve_box(self, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0, warm_start=False,
+                  adapt_every=0, rho_min=0.0, rho_max=0.0):
+        """ndlqr_SolveBatchBoxConstrained (0 = the library's default for every setting). adapt_every > 0: the per-problem
+        adaptive penalty, considered every that many iterations and kept within [rho_min, rho_max]; 0: fixed rho. Returns
+        (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached. Raises on a nonzero
+        return."""
+        st = NdLqrBoxSettingsFull(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0,
+                                  int(adapt_every), rho_min, rho_max)
         iters = np.zeros(self.batch, dtype=np.int32)
         status = np.zeros(self.batch, dtype=np.int32)
         err = self.L.ndlqr_SolveBatchBoxConstrained(self.h, C.byref(st), iters.ctypes.data_as(C.POINTER(C.c_int)),
@@ -645,6 +659,16 @@ class BatchSolver:
             raise RuntimeError("ndlqr_SolveBatchBoxConstrained failed: %d (%s)"
                                % (err, self.L.ndlqr_hip_last_error().decode()))
         return iters, status
+
+    def box_penalties(self, rho=None):
+        """ndlqr_CopyBatchBoxPenalties: rho [batch] of the last constrained solve (what an adaptive solve ended with);
+        `rho`: destination (numpy array or DeviceArray)."""
+        if rho is None:
+            rho = np.zeros(self.batch)
+        err = self.L.ndlqr_CopyBatchBoxPenalties(self.h, _any_ptr(rho, self.batch))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchBoxPenalties failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return rho
 
     def bound_multipliers(self, mu_x=None, mu_u=None):
         """ndlqr_CopyBatchBoundMultipliers: (mu_x [batch, N, n], mu_u [batch, N, m]) = rho y of the last constrained solve;
@@ -664,13 +688,13 @@ class BatchSolver:
     # ndlqr_BatchBoundGradients)
     def solve_box_adjoint(self, g, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0):
         """ndlqr_SolveBatchBoxAdjoint: the adjoint of the active-set system of the last constrained solve for g = dL/dz*
-        [batch, nvars] (numpy array or DeviceArray), on the forward's kept shifted factorisation (its rho, a cold start;
+        [batch, nvars] (numpy array or DeviceArray), on the forward's kept shifted factorisation (its final penalties, a cold start;
         0 = the library's default for every setting). Returns (iters, status) as numpy int arrays [batch]; status 1 =
         converged, 2 = max_iter reached, 3 = not finite (or the forward's was). Raises on a nonzero return. Afterwards
         adjoint() and gradients() read its w."""
         if not hasattr(g, "ptr"):
             g = np.ascontiguousarray(g, dtype=np.float64)
-        st = NdLqrBoxSettings(0.0, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 0)
+        st = NdLqrBoxSettingsFull(0.0, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 0)
         iters = np.zeros(self.batch, dtype=np.int32)
         status = np.zeros(self.batch, dtype=np.int32)
         err = self.L.ndlqr_SolveBatchBoxAdjoint(self.h, _any_ptr(g, self.batch * self.nvars), C.byref(st),

@@ -367,15 +367,24 @@ int ndlqr_BatchSetBounds(NdLqrBatchSolver* bs, unsigned flags, const double* xlo
 }
 int ndlqr_SolveBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status) {
   NdLqrBoxSettings z;
+  double rho_min, rho_max;
   if (!bs) return NDLQR_ERR_INVALID;
   memset(&z, 0, sizeof(z));
   if (s) z = *s;
   if (z.rho < 0.0 || z.alpha < 0.0 || z.alpha >= 2.0 || z.eps_abs < 0.0 || z.eps_rel < 0.0 || z.max_iter < 0 ||
-      z.check_every < 0)
+      z.check_every < 0 || z.adapt_every < 0 || z.rho_min < 0.0 || z.rho_max < 0.0)
     return NDLQR_ERR_INVALID;
-  return ndlqr_hip_solve_box(bs->ctx, z.rho > 0.0 ? z.rho : 0.1, z.alpha > 0.0 ? z.alpha : 1.6, z.eps_abs > 0.0 ? z.eps_abs : 1e-6,
-                             z.eps_rel > 0.0 ? z.eps_rel : 1e-6, z.max_iter > 0 ? z.max_iter : 4000,
-                             z.check_every > 0 ? z.check_every : 10, z.warm_start != 0, iters, status);
+  rho_min = z.rho_min > 0.0 ? z.rho_min : 1e-6;
+  rho_max = z.rho_max > 0.0 ? z.rho_max : 1e6;
+  if (!(rho_min <= rho_max)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_solve_box_ex(bs->ctx, z.rho > 0.0 ? z.rho : 0.1, z.alpha > 0.0 ? z.alpha : 1.6,
+                                z.eps_abs > 0.0 ? z.eps_abs : 1e-6, z.eps_rel > 0.0 ? z.eps_rel : 1e-6,
+                                z.max_iter > 0 ? z.max_iter : 4000, z.check_every > 0 ? z.check_every : 10,
+                                z.warm_start != 0, iters, status, z.adapt_every, rho_min, rho_max);
+}
+int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho) {
+  if (!bs || !rho) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_box_penalties(bs->ctx, rho);
 }
 int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u) {
   if (!bs || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
@@ -386,7 +395,7 @@ int ndlqr_SolveBatchBoxAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLq
   if (!bs || !g) return NDLQR_ERR_INVALID;
   memset(&z, 0, sizeof(z));
   if (s) z = *s;
-  /* (rho and warm_start are the forward's: ignored here) */
+  /* (rho, warm_start and the adaptive-penalty fields are the forward's: ignored here) */
   if (z.alpha < 0.0 || z.alpha >= 2.0 || z.eps_abs < 0.0 || z.eps_rel < 0.0 || z.max_iter < 0 || z.check_every < 0)
     return NDLQR_ERR_INVALID;
   return ndlqr_hip_solve_box_adjoint(bs->ctx, g, z.alpha > 0.0 ? z.alpha : 1.6, z.eps_abs > 0.0 ? z.eps_abs : 1e-6,

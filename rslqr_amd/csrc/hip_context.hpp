@@ -169,18 +169,22 @@ struct NdlqrHipCtx {
   // Box-constrained solve by ADMM (ndlqr_hip_set_bounds / ndlqr_hip_solve_box, kernels_box.hpp; buffers allocated on first
   // use). Bounds lo | hi in the device layout [batch][N][n+m] ([N][n+m] when shared: box_bstride 0) and their bounded
   // pattern; v, y and two ADMM right-hand sides (ping-pong) and the re-solve's z; per problem status, iterations and
-  // residuals; box_word: running count | lo > hi | pattern changed. The shifted factorisation is remembered (box_fact)
-  // with what the plain API's state flags were after it, so that the next constrained solve may skip factoring.
+  // residuals; box_rho: the penalty of every problem [batch]; box_word: running count | problems whose penalty changed |
+  // lo > hi | pattern changed (h_box_word: the same four, then the box adjoint's running count). The shifted
+  // factorisation is remembered (box_fact) with its penalties -- box_rho, and box_rho_value when box_rho_uniform says
+  // they are all that one value -- and what the plain API's state flags were after it, so that the next constrained
+  // solve may skip factoring.
   double *box_lo = nullptr, *box_hi = nullptr, *box_v = nullptr, *box_y = nullptr, *box_z = nullptr, *box_qr_save = nullptr;
   double* box_rhs[2] = {};
-  double* box_resid = nullptr;
+  double *box_resid = nullptr, *box_rho = nullptr;
   unsigned char* box_mask = nullptr;
   int *box_status = nullptr, *box_iters = nullptr, *box_word = nullptr;
   int* h_box_word = nullptr;   // pinned
   bool box_shared = false, box_have_bounds = false, box_have_vy = false;
   size_t box_bstride = 0;      // doubles between the bounds of consecutive problems (0: shared)
   bool box_fact = false;       // the kept records / factors are those of QR + rho M of the current bounds pattern
-  double box_rho = 0.0;
+  bool box_rho_uniform = false;
+  double box_rho_value = 0.0;
   unsigned box_flags = 0;      // the flags of that factorisation
   bool box_rec_complete = false, box_rec_compact = false, box_fact_valid = false;
   const char* box_schedule = "none";

@@ -4,7 +4,9 @@
 // The ADMM variables v (projected copy) and y (scaled dual) are shaped like the [x | u] part of every knot, in the device
 // layout [batch][N][n+m] of QR; so are the bounds lo, hi ([N][n+m] once when they are shared by every problem). An entry
 // is bounded (mask M = 1) when one of its bounds is finite; x of knot 0, u of the last knot and the pad entries of a
-// padded shape are never bounded. With rho and alpha fixed, one iteration is a re-solve with the right-hand side
+// padded shape are never bounded. The penalty is per problem, rho[batch] (a fixed-penalty solve fills it with one value;
+// box_update may move it by powers of two: DESIGN.md section 3.11). With rho and alpha fixed, one iteration is a re-solve
+// with the right-hand side
 //     q~ = q + rho M (y - v)     (r~ likewise; x0 and d as resident)
 // against the factorisation of Q~ = Q + rho M_x, R~ = R + rho M_u, followed by box_update:
 //     zh = alpha z + (1 - alpha) v,   v+ = clip(zh + y, lo, hi),   y+ = (y + zh) - v+
@@ -19,8 +21,9 @@
 namespace ndlqr {
 
 struct BoxParams {
-  double rho, alpha, oma;  // oma = 1 - alpha
+  double alpha, oma;  // oma = 1 - alpha
   double eps_abs, eps_rel;
+  double rho_min, rho_max;  // clamp of the adaptive penalty (read only when box_update adapts)
 };
 
 __device__ __forceinline__ bool box_bounded(double lo, double hi) { return lo > -HUGE_VAL || hi < HUGE_VAL; }
@@ -66,11 +69,19 @@ static __global__ void box_bounds(Dims du, Dims d, const double* __restrict__ xl
   }
 }
 
-// QR <- QR + rho M in place (the caller has saved QR). lo, hi of problem b at offset b * bstride.
+// rho[b] = value for every problem.
+//   grid ceil(batch / 256), block 256.
+static __global__ void box_fill_rho(int batch, double value, double* __restrict__ rho) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < batch) rho[b] = value;
+}
+
+// QR <- QR + rho[b] M in place (the caller has saved QR). lo, hi of problem b at offset b * bstride.
 //   grid (N, batch), block 64.
-static __global__ void box_shift_qr(Dims d, double rho, const double* __restrict__ lo, const double* __restrict__ hi,
-                                    size_t bstride, double* __restrict__ QR) {
+static __global__ void box_shift_qr(Dims d, const double* __restrict__ rhov, const double* __restrict__ lo,
+                                    const double* __restrict__ hi, size_t bstride, double* __restrict__ QR) {
   const int k = blockIdx.x, b = blockIdx.y;
+  const double rho = rhov[b];
   const size_t ob = (size_t)b * bstride + (size_t)k * d.w, oq = ((size_t)b * d.N + k) * d.w;
   for (int j = threadIdx.x; j < d.w; j += blockDim.x)
     if (box_bounded(lo[ob + j], hi[ob + j])) QR[oq + j] = QR[oq + j] + rho;
@@ -93,10 +104,12 @@ __device__ __forceinline__ double box_rhs_entry(double res, double v, double y, 
 // start zeroes y of the entries the current bounds leave unbounded, which may have been bounded in the previous solve).
 //   grid (N, batch), block 64.
 template <bool STRICT>
-__global__ void box_start(Dims d, double rho, int cold, const double* __restrict__ lo, const double* __restrict__ hi,
-                          size_t bstride, const double* __restrict__ res, double* __restrict__ v, double* __restrict__ y,
-                          double* __restrict__ rhs0, double* __restrict__ rhs1) {
+__global__ void box_start(Dims d, const double* __restrict__ rhov, int cold, const double* __restrict__ lo,
+                          const double* __restrict__ hi, size_t bstride, const double* __restrict__ res,
+                          double* __restrict__ v, double* __restrict__ y, double* __restrict__ rhs0,
+                          double* __restrict__ rhs1) {
   const int k = blockIdx.x, b = blockIdx.y;
+  const double rho = rhov[b];
   const size_t oz = ((size_t)b * d.N + k) * d.rows, ov = ((size_t)b * d.N + k) * d.w,
                ob = (size_t)b * bstride + (size_t)k * d.w;
   for (int r = threadIdx.x; r < d.rows; r += blockDim.x) {
@@ -120,18 +133,29 @@ __global__ void box_start(Dims d, double rho, int cold, const double* __restrict
 // A converged problem is frozen: status 1, and rhs_next takes a copy of rhs_cur, so later re-solves reproduce its z. A
 // problem whose maxima are not finite (NaN / inf in its iterate; the reductions keep a NaN) is frozen as status 3.
 // The running count drops by one with an ordinary global atomic. Max-reductions in LDS: deterministic.
+// adapt != 0: a problem that keeps running may move its penalty by a power of two, decided by
+// thread 0 from the same maxima -- with sp = max(max |z|, max |v+|) and sd = rho max |y+|, all of r_prim, r_dual, sp, sd
+// finite and > 0:
+//     k = (ilogb(r_prim / sp) - ilogb(r_dual / sd)) / 2 (toward zero) clamped to [-6, 6],
+//     rho+ = ldexp(rho, k) clamped to [rho_min, rho_max];
+// when rho+ != rho: y <- y (rho / rho+) on the bounded entries (mu = rho y is kept), rho[b] = rho+, rhs_next rewritten
+// from rho+ and that y in a second pass, and running[1] counts the problem (the host refactors). Exact or correctly
+// rounded operations only: numpy reproduces the decision bit for bit. A frozen problem never changes its penalty.
 //   grid (batch), block 256.
 template <bool STRICT>
-__global__ __launch_bounds__(256) void box_update(Dims d, int it, BoxParams P, const double* __restrict__ z,
+__global__ __launch_bounds__(256) void box_update(Dims d, int it, int adapt, BoxParams P, const double* __restrict__ z,
                                                   const double* __restrict__ lo, const double* __restrict__ hi, size_t bstride,
                                                   double* __restrict__ v, double* __restrict__ y, const double* __restrict__ res,
                                                   const double* __restrict__ rhs_cur, double* __restrict__ rhs_next,
-                                                  int* __restrict__ status, int* __restrict__ iters,
-                                                  double* __restrict__ resid, int* __restrict__ running) {
+                                                  double* __restrict__ rhov, int* __restrict__ status,
+                                                  int* __restrict__ iters, double* __restrict__ resid,
+                                                  int* __restrict__ running) {
   __shared__ double red[5][256];
-  __shared__ int conv_s;
+  __shared__ double rho_s;  // the new penalty when conv_s == 2
+  __shared__ int conv_s;    // 0: goes on, 1: frozen, 2: goes on with a new penalty
   const int b = blockIdx.x, tid = threadIdx.x;
   if (status[b] != 0) return;  // frozen (uniform over the workgroup)
+  const double rho = rhov[b];
   const int w = d.w, n = d.n, rows = d.rows;
   const unsigned nw = (unsigned)(d.N * w);
   const double* lb = lo + (size_t)b * bstride;
@@ -162,7 +186,7 @@ __global__ __launch_bounds__(256) void box_update(Dims d, int it, BoxParams P, c
     const double yn = (y0 + zh) - vn;
     vb[e] = vn;
     yb[e] = yn;
-    rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, P.rho);
+    rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, rho);
     rp = max_nan(rp, fabs(zi - vn));
     rd = max_nan(rd, fabs(vn - v0));
     zm = max_nan(zm, fabs(zi));
@@ -177,9 +201,10 @@ __global__ __launch_bounds__(256) void box_update(Dims d, int it, BoxParams P, c
     __syncthreads();
   }
   if (tid == 0) {
-    const double r_prim = red[0][0], r_dual = P.rho * red[1][0];
-    const double tol_p = P.eps_abs + P.eps_rel * max_nan(red[2][0], red[3][0]);
-    const double tol_d = P.eps_abs + P.eps_rel * (P.rho * red[4][0]);
+    const double r_prim = red[0][0], r_dual = rho * red[1][0];
+    const double sp = max_nan(red[2][0], red[3][0]), sd = rho * red[4][0];
+    const double tol_p = P.eps_abs + P.eps_rel * sp;
+    const double tol_d = P.eps_abs + P.eps_rel * sd;
     // a NaN or an infinity in z, v+ or y+ (from the problem data or a failed pivot) ends the problem as status 3
     const bool finite = isfinite(r_prim) && isfinite(r_dual) && isfinite(red[2][0]) && isfinite(red[3][0]) &&
                         isfinite(red[4][0]);
@@ -191,10 +216,36 @@ __global__ __launch_bounds__(256) void box_update(Dims d, int it, BoxParams P, c
       status[b] = conv ? 1 : 3;
       atomicSub(running, 1);
     }
-    conv_s = conv || !finite;
+    int mode = conv || !finite;
+    if (adapt && !mode && isfinite(sd) && r_prim > 0.0 && r_dual > 0.0 && sp > 0.0 && sd > 0.0) {
+      int k = (ilogb(r_prim / sp) - ilogb(r_dual / sd)) / 2;
+      k = k < -6 ? -6 : k > 6 ? 6 : k;
+      if (k != 0) {
+        const double rho_next = fmin(fmax(ldexp(rho, k), P.rho_min), P.rho_max);
+        if (rho_next != rho) {
+          rho_s = rho_next;
+          rhov[b] = rho_next;
+          atomicAdd(running + 1, 1);
+          mode = 2;
+        }
+      }
+    }
+    conv_s = mode;
   }
   __syncthreads();
   if (!conv_s) return;
+  if (conv_s == 2) {  // a new penalty: y rescaled, the next right-hand side from it (same entry -> thread map as above)
+    const double rho_new = rho_s, s = rho / rho_new;
+    for (unsigned e = tid; e < nw; e += blockDim.x) {
+      if (!box_bounded(lb[e], hb[e])) continue;
+      const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
+      const size_t oz = (size_t)k * rows + n + j;
+      const double ys = yb[e] * s;
+      yb[e] = ys;
+      rn[oz] = box_rhs_entry<STRICT>(rs[oz], vb[e], ys, rho_new);
+    }
+    return;
+  }
   for (unsigned e = tid; e < nw; e += blockDim.x) {  // frozen: the next right-hand side is the current one
     if (!box_bounded(lb[e], hb[e])) continue;
     const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
@@ -222,11 +273,12 @@ static __global__ void box_finish(Dims d, const double* __restrict__ lo, const d
   }
 }
 
-// Multipliers mu = rho y into the caller's flat layout: mu_x [batch][N][n], mu_u [batch][N][m] (either may be nullptr).
+// Multipliers mu = rho[b] y into the caller's flat layout: mu_x [batch][N][n], mu_u [batch][N][m] (either may be nullptr).
 //   grid (N, batch), block 64.
-static __global__ void box_multipliers(Dims du, Dims d, double rho, const double* __restrict__ y, double* __restrict__ mu_x,
-                                       double* __restrict__ mu_u) {
+static __global__ void box_multipliers(Dims du, Dims d, const double* __restrict__ rhov, const double* __restrict__ y,
+                                       double* __restrict__ mu_x, double* __restrict__ mu_u) {
   const int k = blockIdx.x, b = blockIdx.y;
+  const double rho = rhov[b];
   const size_t ov = ((size_t)b * d.N + k) * d.w;
   for (int j = threadIdx.x; j < du.n + du.m; j += blockDim.x) {
     if (j < du.n) {

@@ -5,7 +5,7 @@
 // bound), the adjoint of a loss L(z*) with g = dL/dz* is the equality-constrained system
 //     K w + E_A' nu = g,   E_A w = 0,
 // solved as one more box-constrained problem by the ADMM of kernels_box.hpp on the forward's kept shifted factorisation
-// (same rho, same M): right-hand side g, lo = hi = 0 on A. The entries of M \ A carry the rho shift of that factorisation,
+// (same rho per problem, same M): right-hand side g, lo = hi = 0 on A. The entries of M \ A carry the rho shift of that factorisation,
 // so they stay in the splitting as free entries: bounded, but their clip is the identity (y stays 0). Every entry gets a
 // byte code from the forward's v once:
 //     BOX_UNBOUNDED 0   not in M: untouched by the iteration (right-hand side as packed, w = z)
@@ -31,12 +31,13 @@ enum : unsigned char { BOX_UNBOUNDED = 0, BOX_SPLIT = 1, BOX_AT_LO = 2, BOX_AT_H
 // where the forward ended as 3, else 0 and one more in the running count.
 //   grid (N, batch), block 64.
 template <bool STRICT>
-__global__ void box_adjoint_start(Dims d, double rho, const double* __restrict__ lo, const double* __restrict__ hi,
-                                  size_t bstride, const double* __restrict__ vf, const int* __restrict__ fstatus,
+__global__ void box_adjoint_start(Dims d, const double* __restrict__ rhov, const double* __restrict__ lo,
+                                  const double* __restrict__ hi, size_t bstride, const double* __restrict__ vf, const int* __restrict__ fstatus,
                                   const double* __restrict__ res, unsigned char* __restrict__ code, double* __restrict__ v,
                                   double* __restrict__ y, double* __restrict__ rhs0, double* __restrict__ rhs1,
                                   int* __restrict__ status, int* __restrict__ iters, int* __restrict__ running) {
   const int k = blockIdx.x, b = blockIdx.y;
+  const double rho = rhov[b];
   const size_t oz = ((size_t)b * d.N + k) * d.rows, ov = ((size_t)b * d.N + k) * d.w,
                ob = (size_t)b * bstride + (size_t)k * d.w;
   for (int r = threadIdx.x; r < d.rows; r += blockDim.x) {
@@ -70,12 +71,14 @@ __global__ __launch_bounds__(256) void box_adjoint_update(Dims d, int it, BoxPar
                                                           const unsigned char* __restrict__ code, double* __restrict__ v,
                                                           double* __restrict__ y, const double* __restrict__ res,
                                                           const double* __restrict__ rhs_cur, double* __restrict__ rhs_next,
-                                                          int* __restrict__ status, int* __restrict__ iters,
-                                                          double* __restrict__ resid, int* __restrict__ running) {
+                                                          const double* __restrict__ rhov, int* __restrict__ status,
+                                                          int* __restrict__ iters, double* __restrict__ resid,
+                                                          int* __restrict__ running) {
   __shared__ double red[5][256];
   __shared__ int conv_s;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (status[b] != 0) return;  // frozen (uniform over the workgroup)
+  const double rho = rhov[b];  // (the forward's final penalty of this problem: the adjoint does not adapt)
   const int w = d.w, n = d.n, rows = d.rows;
   const unsigned nw = (unsigned)(d.N * w);
   const unsigned char* cb = code + (size_t)b * nw;
@@ -107,7 +110,7 @@ __global__ __launch_bounds__(256) void box_adjoint_update(Dims d, int it, BoxPar
     const double yn = (y0 + zh) - vn;
     if (fixed) yb[e] = yn;
     else vb[e] = vn;  // (yn is +0 exactly: y of a split entry is never stored)
-    rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, P.rho);
+    rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, rho);
     rp = max_nan(rp, fabs(zi - vn));
     rd = max_nan(rd, fabs(vn - v0));
     zm = max_nan(zm, fabs(zi));
@@ -122,9 +125,9 @@ __global__ __launch_bounds__(256) void box_adjoint_update(Dims d, int it, BoxPar
     __syncthreads();
   }
   if (tid == 0) {
-    const double r_prim = red[0][0], r_dual = P.rho * red[1][0];
+    const double r_prim = red[0][0], r_dual = rho * red[1][0];
     const double tol_p = P.eps_abs + P.eps_rel * max_nan(red[2][0], red[3][0]);
-    const double tol_d = P.eps_abs + P.eps_rel * (P.rho * red[4][0]);
+    const double tol_d = P.eps_abs + P.eps_rel * (rho * red[4][0]);
     const bool finite = isfinite(r_prim) && isfinite(r_dual) && isfinite(red[2][0]) && isfinite(red[3][0]) &&
                         isfinite(red[4][0]);
     const int conv = finite && r_prim <= tol_p && r_dual <= tol_d;
@@ -164,8 +167,9 @@ struct BoundOut {
 };
 
 // nu of entry j (caller's block sizes: x then u) of knot k of problem b split onto its lower and upper bound
-__device__ __forceinline__ void bound_grad_entry(const Dims& du, const Dims& d, double rho, const unsigned char* code,
+__device__ __forceinline__ void bound_grad_entry(const Dims& du, const Dims& d, const double* rhov, const unsigned char* code,
                                                  const double* y, int b, int k, int j, double* glo, double* ghi) {
+  const double rho = rhov[b];
   const int jd = j < du.n ? j : d.n + (j - du.n);
   const size_t ov = ((size_t)b * d.N + k) * d.w + jd;
   const unsigned char c = code[ov];
@@ -189,7 +193,7 @@ __device__ __forceinline__ void bound_grad_put(const Dims& du, const BoundOut& o
 
 // Per-problem bound gradients in the caller's flat layout ([batch][N][n], [batch][N][m]).
 //   grid (N, batch), block 64.
-static __global__ void box_bound_grads(Dims du, Dims d, double rho, const unsigned char* __restrict__ code,
+static __global__ void box_bound_grads(Dims du, Dims d, const double* __restrict__ rho, const unsigned char* __restrict__ code,
                                        const double* __restrict__ y, BoundOut out) {
   const int k = blockIdx.x, b = blockIdx.y;
   for (int j = threadIdx.x; j < du.n + du.m; j += blockDim.x) {
@@ -203,7 +207,7 @@ static __global__ void box_bound_grads(Dims du, Dims d, double rho, const unsign
 // blockIdx.y in order. nsplit == 1 (part == nullptr): straight into the outputs ([N][n], [N][m]); else into
 // part[split][2][N (n+m)] (lower | upper), which box_bound_sum_splits adds up in order. Deterministic, no atomics.
 //   grid (ceil(N (n+m) / 256), nsplit), block 256.
-static __global__ __launch_bounds__(256) void box_bound_grads_sum(Dims du, Dims d, double rho, int ppb,
+static __global__ __launch_bounds__(256) void box_bound_grads_sum(Dims du, Dims d, const double* __restrict__ rho, int ppb,
                                                                   const unsigned char* __restrict__ code,
                                                                   const double* __restrict__ y, BoundOut out,
                                                                   double* __restrict__ part) {

@@ -211,6 +211,7 @@ void ndlqr_hip_destroy(NdlqrHipCtx* c) {
   (void)hipFree(c->adj_rhs); (void)hipFree(c->adj_z); (void)hipFree(c->adj_save); (void)hipFree(c->grad_stage);
   (void)hipFree(c->box_lo); (void)hipFree(c->box_hi); (void)hipFree(c->box_v); (void)hipFree(c->box_y); (void)hipFree(c->box_z);
   (void)hipFree(c->box_qr_save); (void)hipFree(c->box_rhs[0]); (void)hipFree(c->box_rhs[1]); (void)hipFree(c->box_resid);
+  (void)hipFree(c->box_rho);
   (void)hipFree(c->box_mask); (void)hipFree(c->box_status); (void)hipFree(c->box_iters); (void)hipFree(c->box_word);
   (void)hipFree(c->abox_code); (void)hipFree(c->abox_v); (void)hipFree(c->abox_y); (void)hipFree(c->abox_resid);
   (void)hipFree(c->abox_rhs[0]); (void)hipFree(c->abox_rhs[1]); (void)hipFree(c->abox_status); (void)hipFree(c->abox_iters);
@@ -1749,7 +1750,10 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
 // rho M in place -- the pointers, and with them the captured launch chain of the primary set, stay valid, and every record
 // re-solve reads the shifted diagonal --, factored once (or not at all while the remembered shifted factorisation still
 // applies), and every iteration is one re-solve into box_z plus one box_update; the host reads the running count every
-// check_every iterations.
+// check_every iterations. The penalty is a device vector, box_rho [batch]. With adapt_every > 0
+// box_update may move a problem's penalty at every adapt_every-th iteration; the host then reads the count of changed
+// problems next to the running count and, when it is not zero, restores QR, shifts it by the new vector and factors the
+// whole batch again -- one factorisation serves every problem that changed in that round.
 
 template <typename T>
 static int box_alloc(T** p, size_t bytes) {
@@ -1792,7 +1796,7 @@ int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const do
   if (!aerr) aerr = box_alloc(&c->box_hi, nlo);
   if (!aerr) aerr = box_alloc(&c->box_word, 4 * sizeof(int));
   if (aerr) return aerr;
-  if (!c->h_box_word) HIP_TRY(hipHostMalloc((void**)&c->h_box_word, 4 * sizeof(int), hipHostMallocDefault));
+  if (!c->h_box_word) HIP_TRY(hipHostMalloc((void**)&c->h_box_word, 5 * sizeof(int), hipHostMallocDefault));
   HIP_TRY(sync_all(c));  // (a solve in flight may still read the bounds)
   BufferSet& s = c->set[0];
   const double* view[4] = {};
@@ -1808,19 +1812,19 @@ int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const do
   }
   HIP_TRY(hipMemsetAsync(c->box_word, 0, 4 * sizeof(int), s.stream));
   hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 0,
-                     c->box_lo, c->box_hi, c->box_mask, c->box_word + 1, c->box_word + 2);
+                     c->box_lo, c->box_hi, c->box_mask, c->box_word + 2, c->box_word + 3);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
-  if (c->h_box_word[1]) return refuse("ndlqr_hip_set_bounds: a lower bound exceeds its upper bound (or is NaN)");
+  if (c->h_box_word[2]) return refuse("ndlqr_hip_set_bounds: a lower bound exceeds its upper bound (or is NaN)");
   // the pattern lives in mask per problem: shared bounds are compared against problem 0's row of it, so a change between
   // shared and per-problem bounds always counts as a new pattern
   hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 1,
-                     c->box_lo, c->box_hi, c->box_mask, c->box_word + 1, c->box_word + 2);
+                     c->box_lo, c->box_hi, c->box_mask, c->box_word + 2, c->box_word + 3);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
-  if (c->h_box_word[2] || (bool)shared != c->box_shared || !c->box_have_bounds) c->box_fact = false;
+  if (c->h_box_word[3] || (bool)shared != c->box_shared || !c->box_have_bounds) c->box_fact = false;
   c->box_soln_gen = 0;  // (a box adjoint needs the constrained solution of these bounds)
   c->box_shared = shared != 0;
   c->box_bstride = shared ? 0 : (size_t)d.N * d.w;
@@ -1830,8 +1834,38 @@ int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const do
 
 int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
                         int check_every, int warm_start, int* iters, int* status) {
+  return ndlqr_hip_solve_box_ex(c, rho, alpha, eps_abs, eps_rel, max_iter, check_every, warm_start, iters, status, 0, 1e-6,
+                                1e6);
+}
+
+// The shifted matrix factored on the primary set as a plain solve does it (the resident solution is overwritten), with
+// the pivot check: *not_spd = NDLQR_ERR_NOT_SPD, which is returned, when a pivot was not positive.
+static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd) {
+  c->box_fact = false;
+  int err = prepare_solve(c, nullptr);  // (KEEP_*: stream-ordered on the primary set)
+  if (!err) err = launch_solve(c);
+  if (!err) c->state_dirty = false;
+  if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (!err) {  // a non-positive pivot of the shifted factorisation (e.g. Q or R <= 0 on an unbounded entry): no iterations
+    int seen = 0;
+    for (const BufferSet& b : c->set)
+      if (b.h_fail && *b.h_fail > seen) seen = *b.h_fail;
+    c->last_failures = seen - c->fail_base;
+    c->fail_base = seen;
+    if (c->last_failures > 0) {
+      refuse("ndlqr_hip_solve_box: " + std::to_string(c->last_failures) + " non-positive pivot(s) in the factorisation of "
+             "Q + rho M, R + rho M");
+      err = *not_spd = NDLQR_ERR_NOT_SPD;
+    }
+  }
+  return err;
+}
+
+int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
+                           int check_every, int warm_start, int* iters, int* status, int adapt_every, double rho_min,
+                           double rho_max) {
   if (!c || !(rho > 0.0) || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 ||
-      check_every < 1)
+      check_every < 1 || adapt_every < 0 || (adapt_every > 0 && !(rho_min > 0.0 && rho_min <= rho_max)))
     return NDLQR_ERR_INVALID;
   if (!c->box_have_bounds) return refuse("ndlqr_hip_solve_box: no bounds (ndlqr_hip_set_bounds first)");
   const ndlqr::Dims& d = c->d;
@@ -1852,6 +1886,7 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
   if (!aerr) aerr = box_alloc(&c->box_resid, sizeof(double) * 2 * (size_t)d.batch);
   if (!aerr) aerr = box_alloc(&c->box_status, sizeof(int) * (size_t)d.batch);
   if (!aerr) aerr = box_alloc(&c->box_iters, sizeof(int) * (size_t)d.batch);
+  if (!aerr) aerr = box_alloc(&c->box_rho, sizeof(double) * (size_t)d.batch);
   if (aerr) return aerr;
   // 1. everything idle, the primary set current with an up-to-date right-hand side
   HIP_TRY(sync_all(c));
@@ -1865,12 +1900,23 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
   const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
   const unsigned user_flags = c->flags;
   const unsigned box_flags = user_flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
-  const bool reuse = c->box_fact && c->box_rho == rho && c->box_flags == box_flags;
+  // the remembered factorisation applies to an adaptive warm start whatever its penalties are (the settings' rho is
+  // ignored: an MPC loop keeps what it learnt); everywhere else only when they are all the settings' rho
+  const bool usable = c->box_fact && c->box_flags == box_flags;
+  const bool keep_rho = usable && adapt_every > 0 && warm_start;
+  const bool reuse = keep_rho || (usable && c->box_rho_uniform && c->box_rho_value == rho);
+  bool uniform = keep_rho ? c->box_rho_uniform : true;
+  const double uniform_value = keep_rho ? c->box_rho_value : rho;
   HIP_TRY(hipEventRecord(s.ev_start, st));
-  // 2. shift QR (restored on every exit below)
+  // 2. the penalties; shift QR (restored on every exit below)
+  if (!reuse) {
+    c->box_fact = false;  // (the remembered factorisation belongs to the penalties overwritten here)
+    hipLaunchKernelGGL(ndlqr::box_fill_rho, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, rho, c->box_rho);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipMemcpyAsync(c->box_qr_save, c->QR, bytes_QR(d), hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, (const double*)c->box_lo,
-                     (const double*)c->box_hi, c->box_bstride, c->QR);
+  hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)c->box_rho,
+                     (const double*)c->box_lo, (const double*)c->box_hi, c->box_bstride, c->QR);
   int err = fail_if(hipGetLastError(), "box_shift_qr");
   bool factored = false;  // the shifted matrix was factored in this call (the resident solution is then overwritten)
   int not_spd = NDLQR_OK;
@@ -1882,43 +1928,29 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
     c->fact_valid = c->box_fact_valid;
     c->schedule = c->box_schedule;
   } else if (!err) {
-    c->box_fact = false;
     factored = true;
-    err = prepare_solve(c, nullptr);  // (KEEP_*: stream-ordered on the primary set)
-    if (!err) err = launch_solve(c);
-    if (!err) c->state_dirty = false;
-    if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if (!err) {  // a non-positive pivot of the shifted factorisation (e.g. Q or R <= 0 on an unbounded entry): no iterations
-      int seen = 0;
-      for (const BufferSet& b : c->set)
-        if (b.h_fail && *b.h_fail > seen) seen = *b.h_fail;
-      c->last_failures = seen - c->fail_base;
-      c->fail_base = seen;
-      if (c->last_failures > 0) {
-        refuse("ndlqr_hip_solve_box: " + std::to_string(c->last_failures) + " non-positive pivot(s) in the factorisation of "
-               "Q + rho M, R + rho M");
-        err = not_spd = NDLQR_ERR_NOT_SPD;
-      }
-    }
+    err = box_factor(c, st, &not_spd);
   }
   // 4. the iterations
   const double* lo = c->box_lo;
   const double* hi = c->box_hi;
   const size_t bs = c->box_bstride;
-  ndlqr::BoxParams P = {rho, alpha, 1.0 - alpha, eps_abs, eps_rel};
+  ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, rho_min, rho_max};
+  const double* rhov = c->box_rho;
   int done_iters = 0;
   if (!err) {
     const int cold = warm_start && c->box_have_vy ? 0 : 1;
     if (strict)
-      hipLaunchKernelGGL(ndlqr::box_start<true>, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, cold, lo, hi, bs,
+      hipLaunchKernelGGL(ndlqr::box_start<true>, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, lo, hi, bs,
                          (const double*)s.rhs, c->box_v, c->box_y, c->box_rhs[0], c->box_rhs[1]);
     else
-      hipLaunchKernelGGL(ndlqr::box_start<false>, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, cold, lo, hi, bs,
+      hipLaunchKernelGGL(ndlqr::box_start<false>, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, lo, hi, bs,
                          (const double*)s.rhs, c->box_v, c->box_y, c->box_rhs[0], c->box_rhs[1]);
     err = fail_if(hipGetLastError(), "box_start");
     c->box_have_vy = true;
     c->h_box_word[0] = d.batch;
-    if (!err) err = fail_if(hipMemcpyAsync(c->box_word, c->h_box_word, sizeof(int), hipMemcpyHostToDevice, st), "box running count");
+    c->h_box_word[1] = 0;
+    if (!err) err = fail_if(hipMemcpyAsync(c->box_word, c->h_box_word, 2 * sizeof(int), hipMemcpyHostToDevice, st), "box running count");
     if (!err) err = fail_if(hipMemsetAsync(c->box_status, 0, sizeof(int) * (size_t)d.batch, st), "box status");
   }
   for (int it = 1; it <= max_iter && !err; ++it) {
@@ -1926,21 +1958,36 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
     double* rn = c->box_rhs[it & 1];
     err = launch_resolve(c, rc, c->box_z, "box-constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
     if (err) break;
+    const int adapt = adapt_every > 0 && it % adapt_every == 0 && it < max_iter;
     if (strict)
-      hipLaunchKernelGGL(ndlqr::box_update<true>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->box_z, lo, hi,
-                         bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_status, c->box_iters, c->box_resid,
-                         c->box_word);
+      hipLaunchKernelGGL(ndlqr::box_update<true>, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box_z,
+                         lo, hi, bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_rho, c->box_status,
+                         c->box_iters, c->box_resid, c->box_word);
     else
-      hipLaunchKernelGGL(ndlqr::box_update<false>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->box_z, lo, hi,
-                         bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_status, c->box_iters, c->box_resid,
-                         c->box_word);
+      hipLaunchKernelGGL(ndlqr::box_update<false>, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box_z,
+                         lo, hi, bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_rho, c->box_status,
+                         c->box_iters, c->box_resid, c->box_word);
     err = fail_if(hipGetLastError(), "box_update");
     done_iters = it;
-    if (!err && (it % check_every == 0 || it == max_iter)) {
-      // 5. one word: how many problems still run
-      err = fail_if(hipMemcpyAsync(c->h_box_word, c->box_word, sizeof(int), hipMemcpyDeviceToHost, st), "box running count");
+    if (!err && (it % check_every == 0 || it == max_iter || adapt)) {
+      // 5. one word: how many problems still run; after an adapting update also how many changed their penalty
+      err = fail_if(hipMemcpyAsync(c->h_box_word, c->box_word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st),
+                    "box running count");
       if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
       if (!err && c->h_box_word[0] == 0) break;
+      if (!err && adapt && c->h_box_word[1] != 0) {
+        // 5a. new penalties: the saved QR shifted by the new vector and factored as above (frozen problems keep their
+        // penalty: the same factors again, so their later re-solves reproduce their z)
+        uniform = false;
+        factored = true;
+        err = fail_if(hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(d), hipMemcpyDeviceToDevice, st), "restoring QR");
+        if (!err) {
+          hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, lo, hi, bs, c->QR);
+          err = fail_if(hipGetLastError(), "box_shift_qr");
+        }
+        if (!err) err = box_factor(c, st, &not_spd);
+        if (!err) err = fail_if(hipMemsetAsync(c->box_word + 1, 0, sizeof(int), st), "box changed count");
+      }
     }
   }
   // 6. deliver, restore QR, bookkeeping
@@ -1954,7 +2001,8 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
   c->flags = user_flags;
   if (!err) {
     c->box_fact = true;
-    c->box_rho = rho;
+    c->box_rho_uniform = uniform;
+    c->box_rho_value = uniform_value;
     c->box_flags = box_flags;
     c->box_rec_complete = c->rec_complete;
     c->box_rec_compact = c->rec_compact;
@@ -1996,6 +2044,17 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
   return NDLQR_OK;
 }
 
+int ndlqr_hip_download_box_penalties(NdlqrHipCtx* c, double* rho) {
+  if (!c || !rho) return NDLQR_ERR_INVALID;
+  if (!c->box_have_vy || !c->box_rho) return refuse("ndlqr_hip_download_box_penalties: no constrained solve yet");
+  HIP_TRY(hipSetDevice(c->device));
+  if (where(rho, c->device) == Where::OtherDevice)
+    return refuse("ndlqr_hip_download_box_penalties: the output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  HIP_TRY(hipMemcpy(rho, c->box_rho, sizeof(double) * (size_t)c->d.batch, hipMemcpyDefault));
+  return NDLQR_OK;
+}
+
 int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* mu_u) {
   if (!c || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
   if (!c->box_have_vy || !c->box_y) return refuse("ndlqr_hip_download_bound_multipliers: no constrained solve yet");
@@ -2027,7 +2086,7 @@ int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* m
     out[k] = own[k] ? user[k] : at;
     if (!own[k]) at += cnt[k];
   }
-  hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, c->box_rho,
+  hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box_rho,
                      (const double*)c->box_y, out[0], out[1]);
   HIP_TRY(hipGetLastError());
   for (int k = 0; k < 2; ++k)
@@ -2094,7 +2153,7 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
   c->adj_gen = 0;
   const bool strict = (c->box_flags & NDLQR_FLAG_STRICT_FP) != 0;
   const unsigned user_flags = c->flags;
-  const double rho = c->box_rho;
+  const double* rho = c->box_rho;  // (the forward's final penalties: those of the remembered factorisation)
   const double* lo = c->box_lo;
   const double* hi = c->box_hi;
   const size_t bs = c->box_bstride;
@@ -2120,7 +2179,7 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
     saved = !err;
   }
   // 3. codes, v = y = 0, right-hand sides, status
-  ndlqr::BoxParams P = {rho, alpha, 1.0 - alpha, eps_abs, eps_rel};
+  ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
   if (!err) err = fail_if(hipMemsetAsync(c->abox_word, 0, sizeof(int), st), "box adjoint running count");
   if (!err) {
     if (strict)
@@ -2135,10 +2194,10 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
   }
   // 4. the iterations (none when every problem's forward ended non-finite)
   if (!err) {
-    err = fail_if(hipMemcpyAsync(&c->h_box_word[3], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st), "box adjoint running count");
+    err = fail_if(hipMemcpyAsync(&c->h_box_word[4], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st), "box adjoint running count");
     if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
   }
-  const bool any = !err && c->h_box_word[3] > 0;
+  const bool any = !err && c->h_box_word[4] > 0;
   for (int it = 1; it <= max_iter && any && !err; ++it) {
     const double* rc = c->abox_rhs[(it - 1) & 1];
     double* rn = c->abox_rhs[it & 1];
@@ -2147,16 +2206,16 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
     if (strict)
       hipLaunchKernelGGL(ndlqr::box_adjoint_update<true>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj_z,
                          (const unsigned char*)c->abox_code, c->abox_v, c->abox_y, (const double*)c->adj_rhs, rc, rn,
-                         c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
+                         rho, c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
     else
       hipLaunchKernelGGL(ndlqr::box_adjoint_update<false>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj_z,
                          (const unsigned char*)c->abox_code, c->abox_v, c->abox_y, (const double*)c->adj_rhs, rc, rn,
-                         c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
+                         rho, c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
     err = fail_if(hipGetLastError(), "box_adjoint_update");
     if (!err && (it % check_every == 0 || it == max_iter)) {
-      err = fail_if(hipMemcpyAsync(&c->h_box_word[3], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st), "box adjoint running count");
+      err = fail_if(hipMemcpyAsync(&c->h_box_word[4], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st), "box adjoint running count");
       if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
-      if (!err && c->h_box_word[3] == 0) break;
+      if (!err && c->h_box_word[4] == 0) break;
     }
   }
   if (!err && !any) {  // (no re-solve ran: a defined w all the same -- the re-solve of the packed g)
@@ -2263,11 +2322,12 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
   double* part = npart ? at : nullptr;
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   if (!summed) {
-    hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, c->box_rho,
+    hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box_rho,
                        (const unsigned char*)c->abox_code, (const double*)c->abox_y, out);
     HIP_TRY(hipGetLastError());
   } else {
-    hipLaunchKernelGGL(ndlqr::box_bound_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d, c->box_rho, ppb,
+    hipLaunchKernelGGL(ndlqr::box_bound_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d,
+                       (const double*)c->box_rho, ppb,
                        (const unsigned char*)c->abox_code, (const double*)c->abox_y, out, part);
     HIP_TRY(hipGetLastError());
     if (part) {

@@ -12,7 +12,13 @@ The update kernel's algorithmic traffic per iteration: per bounded entry z, v, y
 v, y, the next right-hand side written (72 B; shared bounds are read from L2: 56 B of HBM traffic), per unbounded entry
 lo and hi read. Its own time comes from a rocprofv3 --kernel-trace --stats run of this script (box_update).
 
-    python tools/box_bench.py [--shape 12,4,256,1024] [--iters 200] [--reps 5] [--warmup 1]
+--adapt-every K adds the per-problem adaptive penalty: for both bounds configurations a cold
+fixed-penalty solve and a cold adaptive one (period K) of the same problems and bounds in this process, each after
+fresh inputs so that both pay their first factorisation -- iterations, problems not converged, factorisations and
+HIP-event time per constrained solve -- next to the time per iteration of adapt_every = 0, appended as JSON lines to
+--out (profiles/box_adaptive_bench.jsonl).
+
+    python tools/box_bench.py [--shape 12,4,256,1024] [--iters 200] [--reps 5] [--warmup 1] [--adapt-every 25]
 """
 import argparse
 import json
@@ -33,7 +39,21 @@ def median(fn, reps, warmup):
     return float(np.median([fn() for _ in range(reps)]))
 
 
-def run(n, m, N, batch, iters, reps, warmup):
+def cold_solve(bs, bounds, **kw):
+    """one cold constrained solve after fresh inputs (nothing remembered): its figures for the adaptive comparison"""
+    bs.initialize_synthetic(1)
+    bs.set_bounds(*bounds)
+    f0 = bs.factor_count()
+    it, st = bs.solve_box(max_iter=20000, **kw)
+    ms = bs.solve_ms()
+    pen = bs.box_penalties()
+    return {"iterations": {"min": int(it.min()), "median": float(np.median(it)), "max": int(it.max())},
+            "not_converged": int((st != 1).sum()), "factorisations": int(bs.factor_count() - f0),
+            "solve_ms": round(ms, 3), "ms_per_iteration_of_the_solve": round(ms / int(it.max()), 4),
+            "rho_min_max": [float(pen.min()), float(pen.max())]}
+
+
+def run(n, m, N, batch, iters, reps, warmup, adapt_every=0):
     bs = R.BatchSolver(n, m, N, batch, flags=R.FLAG_KEEP_RECORDS)
     bs.initialize_synthetic(1)
     assert bs.solve() == 0
@@ -89,6 +109,9 @@ def run(n, m, N, batch, iters, reps, warmup):
                     "iterations_to_1e-6": {"max": int(it.max()), "median": float(np.median(it)), "min": int(it.min())},
                     "converged": int((st == 1).sum()), "cold_solve_ms": round(cold_ms, 3), "iters_timed": iters,
                     "reps": reps})
+        if adapt_every > 0:
+            out[-1]["adaptive"] = {"adapt_every": adapt_every, "fixed": cold_solve(bs, b, rho=rho),
+                                   "adaptive": cold_solve(bs, b, rho=rho, adapt_every=adapt_every)}
     bs.close()
     return out
 
@@ -99,10 +122,18 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--adapt-every", type=int, default=0, help="also compare a cold fixed-penalty solve with a cold "
+                    "adaptive one of this period and append the figures to --out")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                  "box_adaptive_bench.jsonl"))
     a = ap.parse_args()
     n, m, N, batch = (int(x) for x in a.shape.split(","))
-    for line in run(n, m, N, batch, a.iters, a.reps, a.warmup):
+    for line in run(n, m, N, batch, a.iters, a.reps, a.warmup, a.adapt_every):
         print(json.dumps(line), flush=True)
+        if a.adapt_every > 0:
+            keep = ("shape", "bounds", "schedule", "rho", "ms_per_iteration", "iters_timed", "reps", "adaptive")
+            with open(a.out, "a") as f:
+                f.write(json.dumps({k: line[k] for k in keep}) + "\n")
 
 
 if __name__ == "__main__":
