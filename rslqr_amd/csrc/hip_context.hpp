@@ -34,6 +34,18 @@ struct PendingEvent {
   hipEvent_t start, stop;
 };
 
+// What the last factorisation left on the primary set (kept records and factors never pipeline), as the plain API's
+// re-solves see it
+struct KeptState {
+  bool rec_complete = false;  // every separator record and factor is there (fast mode + KEEP / KEEP_RECORDS)
+  bool rec_compact = false;   // ... in the compact form of the default schedule (level-0 records = L, the factors of the upper
+                              // separators in the slack of those slots): the re-solve is rb_forward / rb_forward_top / rb_backsub
+  bool fact_valid = false;    // the device holds a complete factorisation (last solve ran with KEEP_FACT)
+  const char* schedule = "none";  // name of the launch sequence the last solve used (ndlqr_hip_schedule)
+  // the records / factors no longer belong to the resident inputs: the re-solves refuse until the next solve
+  void forget_factorisation() { rec_complete = fact_valid = false; }
+};
+
 // A launch sequence captured as a hipGraph: the key it was captured under (replayed while that matches) and what the
 // sequence leaves behind (replays do not re-enter the launch code)
 struct CapturedChain {
@@ -41,9 +53,7 @@ struct CapturedChain {
   unsigned flags = 0;
   hipStream_t stream = nullptr;
   unsigned apply = 0;  // (apply_blk0 << 16 | apply_nblk): the restricted back-substitution of a step
-  bool rec_complete = false;
-  bool rec_compact = false;
-  const char* schedule = "none";
+  KeptState kept;  // (fact_valid is not the chain's to say: replay_chain passes the live one through)
   void reset() {
     if (exec) (void)hipGraphExecDestroy(exec);
     exec = nullptr;
@@ -112,7 +122,7 @@ struct NdlqrHipCtx {
   bool state_dirty = false;  // a solve failed to launch or to complete: counters / failure words are zeroed before the next one
   int fail_base = 0;         // value of the (cumulative) batch-wide failure counter at the last synchronisation
   int* info = nullptr;
-  const char* schedule = "none";  // name of the launch sequence the last solve used (ndlqr_hip_schedule)
+  KeptState kept;  // of the latest solve
   double* kkt_out = nullptr;  // [2 batch] scratch of ndlqr_hip_kkt_residual (allocated on first use)
   // several right-hand sides per problem (ndlqr_hip_solve_multi_rhs): buffers for `multi_cap` right-hand sides, grown on demand
   size_t multi_cap = 0;
@@ -123,10 +133,6 @@ struct NdlqrHipCtx {
   bool no_top = false;      // NDLQR_NO_TOP=1: the last three tree levels as launches of their own (A/B timing of reduced_top_mc)
   int top_levels = 3;       // tree levels inside reduced_top_mc (NDLQR_TOP_LEVELS, 3 .. 5): beyond three a wavefront takes several separators of the first ones in turn
   bool no_mfma = false;     // NDLQR_NO_MFMA=1: keep the scalar Schur kernel for large blocks (A/B timing)
-  // rec_complete, rec_compact and fact_valid describe the primary set only: kept records and factors never pipeline
-  bool rec_complete = false;  // last factorisation left every separator record and factor (fast mode + KEEP / KEEP_RECORDS)
-  bool rec_compact = false;   // ... in the compact form of the default schedule (level-0 records = L, the factors of the upper
-                              // separators in the slack of those slots): the re-solve is rb_forward / rb_forward_top / rb_backsub
   int sep_threads = 0;        // NDLQR_SEP_THREADS: workgroup size of the matrix-core separator (0 = by block size)
   hipEvent_t ev_step[2] = {};  // end of the steps of ndlqr_hip_step_async, alternating (ndlqr_hip_synchronize_previous)
   unsigned step_count = 0;
@@ -155,7 +161,6 @@ struct NdlqrHipCtx {
   bool timing_pending = false;
   double last_ms = 0;
   int last_failures = 0;
-  bool fact_valid = false;  // the device holds a complete factorisation (last solve ran with KEEP_FACT)
   // Adjoint solve and parameter gradients (ndlqr_hip_solve_adjoint / ndlqr_hip_gradients): the adjoint right-hand side
   // and its solution w in buffers of their own, [batch][N][2n+m] (allocated on first use), so that the primal state stays
   // as it is. soln_gen counts the resident solutions (note_solution); adj_gen is the one the adjoint belongs to (0: none).
@@ -172,7 +177,7 @@ struct NdlqrHipCtx {
   // residuals; box_rho: the penalty of every problem [batch]; box_word: running count | problems whose penalty changed |
   // lo > hi | pattern changed (h_box_word: the same four, then the box adjoint's running count). The shifted
   // factorisation is remembered (box_fact) with its penalties -- box_rho, and box_rho_value when box_rho_uniform says
-  // they are all that one value -- and what the plain API's state flags were after it, so that the next constrained
+  // they are all that one value -- and what the plain API's kept state was after it (box_kept), so that the next constrained
   // solve may skip factoring.
   double *box_lo = nullptr, *box_hi = nullptr, *box_v = nullptr, *box_y = nullptr, *box_z = nullptr, *box_qr_save = nullptr;
   double* box_rhs[2] = {};
@@ -186,8 +191,7 @@ struct NdlqrHipCtx {
   bool box_rho_uniform = false;
   double box_rho_value = 0.0;
   unsigned box_flags = 0;      // the flags of that factorisation
-  bool box_rec_complete = false, box_rec_compact = false, box_fact_valid = false;
-  const char* box_schedule = "none";
+  KeptState box_kept;          // ... and what it left
   // Gradients through the box-constrained solve (ndlqr_hip_solve_box_adjoint / ndlqr_hip_bound_gradients,
   // kernels_box_grad.hpp; allocated on first use). box_soln_gen: the solution generation the latest constrained solve
   // left (0: none since the bounds were set); abox_gen: the one the box adjoint belongs to (0: none). The adjoint's own

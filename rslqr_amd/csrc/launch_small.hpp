@@ -108,15 +108,15 @@ static int launch_small(NdlqrHipCtx* c) {
   const int store_l = plan.store_l;
   // the record-based re-solve needs every separator's record and factor: KEEP writes them all,
   // KEEP_RECORDS adds the factors to the lean schedule
-  c->rec_complete = !STRICT && (KEEP || (lean && store_l));
+  c->kept.rec_complete = !STRICT && (KEEP || (lean && store_l));
   if constexpr (!STRICT && !KEEP && ndlqr::P1OnMatrixCores<NX, NU>::value) {
     if (plan.reduced) {
       const bool tree = plan.tree;
       // compact level-0 records + the two-launch back-substitution (kernels_rowbcast.hpp), unless the
       // records have to serve a record-based re-solve (KEEP_RECORDS) or the tree schedule runs
       const bool compact = plan.compact;
-      c->schedule = tree ? "reduced-tree" : (compact ? (store_l ? "reduced-compact-records" : "reduced") : "reduced-records");
-      c->rec_compact = compact && store_l == 2;
+      c->kept.schedule = tree ? "reduced-tree" : (compact ? (store_l ? "reduced-compact-records" : "reduced") : "reduced-records");
+      c->kept.rec_compact = compact && store_l == 2;
       bool fuse2 = false;
       {
         ScopedSlot t(c, SLOT_BOTTOM);
@@ -135,7 +135,7 @@ static int launch_small(NdlqrHipCtx* c) {
         // 0.578 -> 0.569; (12,8) +2.5 %, (13,4) +0.9 %, (9,3) / (10,4) / (15,2) +-0). NDLQR_FUSE2=0 / 1 overrides.
         fuse2 = !launched && !tree && compact && !store_l && d.N >= 16 &&
                 (c->fuse2 > 0 || (c->fuse2 < 0 && NX == 12 && NU == 4));
-        if (fuse2) c->schedule = "reduced-fused2";
+        if (fuse2) c->kept.schedule = "reduced-fused2";
         if (launched) {
         } else if (fuse2) {
           hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream, d,
@@ -188,7 +188,7 @@ static int launch_small(NdlqrHipCtx* c) {
       return NDLQR_OK;
     }
   }
-  c->schedule = lean ? "knot-lean" : (STRICT ? "knot-strict" : "knot-keep");
+  c->kept.schedule = lean ? "knot-lean" : (STRICT ? "knot-strict" : "knot-keep");
   {
     ScopedSlot t(c, SLOT_BOTTOM);
     hipLaunchKernelGGL((ndlqr::bottom_small<NX, NU, STRICT, KEEP, JB>), dim3(d.N >> JB, d.batch), dim3(32 << JB), 0,
@@ -220,7 +220,7 @@ static void launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value && 8 * (2 * NX + NU) <= 256) {
-    if (c->rec_compact) {
+    if (c->kept.rec_compact) {
       // the compact records of the default schedule (round 4): forward pass over the separators with the right-hand-side
       // column alone, then the back-substitution of a full solve. s.red (the accumulator slots, idle here) holds what
       // the eight-knot blocks push to the separators between them: [batch][N / 8][2][NX].
@@ -357,7 +357,7 @@ static int launch_time_shard(NdlqrHipCtx* c, const int phase, const int g, const
       launch_rb_backsub<NX, NU, false>(c, dim3(cnt, d.batch), bs.stream, d, c->AB, c->QR,
                          bs.rhs, bs.rec, bs.ytop, bs.z);
     }
-    c->schedule = "reduced-time-shard";
+    c->kept.schedule = "reduced-time-shard";
     return NDLQR_OK;
   }
 }

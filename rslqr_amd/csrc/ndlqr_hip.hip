@@ -6,6 +6,7 @@
 // Written for wave64 / gfx950 only; built with -ffp-contract=off so that every fused
 // multiply-add in the kernels is an explicit fma() (fast mode) or an explicit mul + add
 // (NDLQR_FLAG_STRICT_FP, which reproduces the reference's default CPU build bit for bit).
+#include <initializer_list>
 #include <mutex>
 #include <utility>
 
@@ -404,8 +405,7 @@ static hipError_t other_stream_waits(NdlqrHipCtx* c) {
 static void note_new_inputs(NdlqrHipCtx* c) {
   rhs_written_cur(c, 0xFu);
   next_solve_on_current_set(c);
-  c->fact_valid = false;
-  c->rec_complete = false;
+  c->kept.forget_factorisation();
   c->inputs_replaced = true;
   c->box_fact = false;
 }
@@ -600,8 +600,8 @@ static void launch_backsub_reduced_generic(NdlqrHipCtx* c, const double* rhs, do
 static int launch_reduced_generic(NdlqrHipCtx* c, const ReducedGenericPlan& p) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
-  c->schedule = p.keep ? "generic-reduced-records" : "generic-reduced";
-  c->rec_complete = p.keep;  // records, slots and W of every separator stay: rhs-only re-solves (launch_rhs_reduced_generic)
+  c->kept.schedule = p.keep ? "generic-reduced-records" : "generic-reduced";
+  c->kept.rec_complete = p.keep;  // records, slots and W of every separator stay: rhs-only re-solves (launch_rhs_reduced_generic)
   for (int l = 0; l < d.K; ++l) {
     ScopedSlot t(c, SLOT_SEP);
     const dim3 grid(d.N >> (l + 1), d.batch);
@@ -712,7 +712,7 @@ static int launch_generic(NdlqrHipCtx* c, bool lean) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   double* rec = lean ? s.rec : nullptr;
-  c->schedule = lean ? "generic-lean" : (STRICT ? "generic-strict" : "generic-keep");
+  c->kept.schedule = lean ? "generic-lean" : (STRICT ? "generic-strict" : "generic-keep");
   {
     ScopedSlot t(c, SLOT_LEAF);
     hipLaunchKernelGGL((ndlqr::leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(128), 0, s.stream, d,
@@ -902,8 +902,8 @@ static int enqueue_solve(NdlqrHipCtx* c) {
   const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
   int err = NDLQR_OK;
   bool done = false;
-  c->rec_complete = false;
-  c->rec_compact = false;
+  c->kept.rec_complete = false;
+  c->kept.rec_compact = false;
   done = try_launch_small(c, strict, &err);
   if (!done) {
     const ReducedGenericPlan rp = plan_reduced_generic(c);
@@ -993,14 +993,11 @@ static int replay_chain(NdlqrHipCtx* c, CapturedChain& g, int (*enqueue)(NdlqrHi
     g.flags = c->flags;
     g.stream = st;
     g.apply = apply;
-    g.rec_complete = c->rec_complete;
-    g.rec_compact = c->rec_compact;
-    g.schedule = c->schedule;
+    g.kept = c->kept;
   }
   HIP_TRY(hipGraphLaunch(g.exec, st));
-  c->rec_complete = g.rec_complete;
-  c->rec_compact = g.rec_compact;
-  c->schedule = g.schedule;
+  g.kept.fact_valid = c->kept.fact_valid;  // (the callers' to set: launch_solve, ndlqr_hip_solve_staged)
+  c->kept = g.kept;
   return NDLQR_OK;
 }
 
@@ -1016,7 +1013,7 @@ static int launch_solve(NdlqrHipCtx* c) {
   if (err) return err;
   HIP_TRY(hipGetLastError());
   note_solution(c);
-  c->fact_valid = solve_leaves_factors(c);
+  c->kept.fact_valid = solve_leaves_factors(c);
   c->inputs_replaced = false;
   c->box_fact = false;  // (the records / factors are those of the unshifted matrix now)
   ++c->factor_count;
@@ -1112,8 +1109,7 @@ int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
   int err = prepare_solve(c, nullptr);  // (allocations, recovery from a failed solve; depth 1: the primary set)
   if (err) return err;
   rhs_written_cur(c, 0xFu);
-  c->fact_valid = false;  // new A, B, Q, R: neither a cached factor array nor cached records match
-  c->rec_complete = false;
+  c->kept.forget_factorisation();  // new A, B, Q, R: neither a cached factor array nor cached records match
   c->box_fact = false;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
@@ -1122,7 +1118,7 @@ int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   note_solution(c);
-  c->fact_valid = solve_leaves_factors(c);
+  c->kept.fact_valid = solve_leaves_factors(c);
   c->inputs_replaced = false;
   c->timing_pending = true;
   c->state_dirty = false;
@@ -1198,8 +1194,7 @@ static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
     HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
     c->timing_pending = true;
     note_solution(c);
-    c->fact_valid = false;
-    c->rec_complete = false;
+    c->kept.forget_factorisation();
   }
   return NDLQR_OK;
 }
@@ -1305,11 +1300,11 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   //  (16,4,256) x 1024 the re-solve takes 2.8 ms against 1.9 for factor + solve, profiles/r04_mpc_steps.txt. The
   //  full-record form of the small shapes -- tree schedule -- re-solves no faster than it factors and keeps factoring.)
   const bool generic_records = !pick_small(c) && c->d.n > 32;
-  if ((c->flags & NDLQR_FLAG_KEEP_RECORDS) && !(c->flags & (NDLQR_FLAG_STRICT_FP | NDLQR_FLAG_KEEP_FACT)) && c->rec_complete &&
-      (c->rec_compact || generic_records) && c->cur == 0 && try_launch_rhs_records(c, s.rhs, s.z)) {
+  if ((c->flags & NDLQR_FLAG_KEEP_RECORDS) && !(c->flags & (NDLQR_FLAG_STRICT_FP | NDLQR_FLAG_KEEP_FACT)) && c->kept.rec_complete &&
+      (c->kept.rec_compact || generic_records) && c->cur == 0 && try_launch_rhs_records(c, s.rhs, s.z)) {
     HIP_TRY(hipGetLastError());
     note_solution(c);
-    c->schedule = generic_records ? "generic-reduced-records (re-solve)" : "reduced-compact-records (re-solve)";
+    c->kept.schedule = generic_records ? "generic-reduced-records (re-solve)" : "reduced-compact-records (re-solve)";
   } else {
     err = launch_solve(c);
     if (err) return err;
@@ -1492,7 +1487,7 @@ static void launch_rhs_sweep(NdlqrHipCtx* c, const double* rhs, double* z) {
 // the record-based re-solve where the kept records have one: right-hand side `rhs`, solution into `z`
 static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
-  if (!c->rec_complete || (c->flags & NDLQR_FLAG_STRICT_FP)) return false;
+  if (!c->kept.rec_complete || (c->flags & NDLQR_FLAG_STRICT_FP)) return false;
   if (!pick_small(c)) {  // runtime-sized separator-only schedule: records + slots + W of every separator
     if (!plan_reduced_generic(c).ok) return false;
     launch_rhs_reduced_generic(c, rhs, z);
@@ -1503,7 +1498,7 @@ static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z)
   if (!inst) return false;
   // (the full-record forms: sweep array of rhs_forward_upper within the default dynamic LDS, backsub_small's K + 4
   //  separators of nx rows in one workgroup; the compact form -- rb_forward / rb_forward_top -- was checked by its plan)
-  if (!c->rec_compact && (d.N < 8 || (size_t)(d.N / 8) * d.n * sizeof(double) > 60 * 1024 || (d.K + 4) * inst->nx > 256))
+  if (!c->kept.rec_compact && (d.N < 8 || (size_t)(d.N / 8) * d.n * sizeof(double) > 60 * 1024 || (d.K + 4) * inst->nx > 256))
     return false;
   inst->rhs(c, rhs, z);
   return true;
@@ -1513,14 +1508,14 @@ static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z)
 // `refusal` when there are records only and this shape / horizon has no record-based re-solve
 static int launch_resolve(NdlqrHipCtx* c, const double* rhs, double* z, const char* refusal) {
   if (try_launch_rhs_records(c, rhs, z)) return NDLQR_OK;
-  if (!c->fact_valid) return refuse(refusal);
+  if (!c->kept.fact_valid) return refuse(refusal);
   if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c, rhs, z); else launch_rhs_sweep<false>(c, rhs, z);
   return NDLQR_OK;
 }
 
 int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
   if (!c) return NDLQR_ERR_INVALID;
-  if (!c->fact_valid && !c->rec_complete)
+  if (!c->kept.fact_valid && !c->kept.rec_complete)
     return refuse("rhs-only solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or "
                   "NDLQR_FLAG_KEEP_RECORDS (cached factorisation)");
   HIP_TRY(hipSetDevice(c->device));
@@ -1555,6 +1550,72 @@ static int ensure_grad_stage(NdlqrHipCtx* c, size_t doubles) {
   return NDLQR_OK;
 }
 
+// K arrays of the caller, cnt[k] doubles each (null: absent), and their way through grad_stage. In this order: classify();
+// ensure_grad_stage for `stage` doubles plus whatever the caller wants behind them; sync_all; place(), which fills dev[] --
+// what the kernels get -- and returns the first free double; copy(st, true) before the launches that read inputs, or
+// copy(st, false) behind those that wrote outputs.
+template <int K>
+struct CallerArrays {
+  double* user[K];
+  size_t cnt[K];
+  bool own[K] = {};  // this device's memory: read or written by the kernels as it is
+  double* dev[K] = {};
+  size_t stage = 0;  // doubles to stage
+  // `who`: the API function, `what`: "an output lies", ... -- the refusal reads "who: what in the memory of another device ..."
+  int classify(const NdlqrHipCtx* c, const char* who, const char* what) {
+    for (int k = 0; k < K; ++k) {
+      if (!user[k]) continue;
+      const Where w = where(user[k], c->device);
+      if (w == Where::OtherDevice)
+        return refuse(std::string(who) + ": " + what + " in the memory of another device than the solver's");
+      own[k] = w == Where::OwnDevice;
+      if (!own[k]) stage += cnt[k];
+    }
+    return NDLQR_OK;
+  }
+  double* place(const NdlqrHipCtx* c) {
+    double* at = c->grad_stage;
+    for (int k = 0; k < K; ++k) {
+      if (!user[k]) continue;
+      dev[k] = own[k] ? user[k] : at;
+      if (!own[k]) at += cnt[k];
+    }
+    return at;
+  }
+  int copy(hipStream_t st, bool in) {
+    for (int k = 0; k < K; ++k)
+      if (user[k] && !own[k])
+        HIP_TRY(hipMemcpyAsync(in ? dev[k] : user[k], in ? user[k] : dev[k], sizeof(double) * cnt[k], hipMemcpyDefault, st));
+    return NDLQR_OK;
+  }
+};
+
+// KERNEL<true> under NDLQR_FLAG_STRICT_FP, KERNEL<false> otherwise: one argument list for both
+#define launch_strict(strict, KERNEL, grid, block, lds, stream, ...)                            \
+  do {                                                                                          \
+    if (strict) hipLaunchKernelGGL(KERNEL<true>, grid, block, lds, stream, __VA_ARGS__);        \
+    else hipLaunchKernelGGL(KERNEL<false>, grid, block, lds, stream, __VA_ARGS__);              \
+  } while (0)
+
+// the device time between the events of the (synchronised) set, for ndlqr_hip_last_solve_ms
+static void note_elapsed(NdlqrHipCtx* c, const BufferSet& s) {
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
+}
+
+// device buffers that are allocated on first use: those of the list that are not there yet
+struct FirstUse {
+  void** p;
+  size_t bytes;
+  template <typename T>
+  FirstUse(T** q, size_t b) : p(reinterpret_cast<void**>(q)), bytes(b) {}
+};
+static int alloc_missing(std::initializer_list<FirstUse> list) {
+  for (const FirstUse& a : list)
+    if (!*a.p) HIP_TRY(hipMalloc(a.p, a.bytes));
+  return NDLQR_OK;
+}
+
 // The re-solves of the kept records write what depends on the right-hand side into them (z_sep / y~: the last n entries
 // of every record) and, on the runtime-sized schedule, into the slots (gL | gR). Every re-solve recomputes those before
 // it reads them; the adjoint solve still leaves them as it found them: saved before, restored after (2 n doubles per
@@ -1578,46 +1639,44 @@ static hipError_t adjoint_scratch(NdlqrHipCtx* c, bool restore) {
 
 int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   if (!c || !g) return NDLQR_ERR_INVALID;
-  if (!c->fact_valid && !c->rec_complete)
+  if (!c->kept.fact_valid && !c->kept.rec_complete)
     return refuse("adjoint solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
                   "factorisation) of the resident inputs");
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_adjoint");
-  if (!strcmp(c->schedule, "reduced-time-shard")) return refuse("adjoint solve: not available on a time-axis shard");
+  if (!strcmp(c->kept.schedule, "reduced-time-shard")) return refuse("adjoint solve: not available on a time-axis shard");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
-  const Where wg = where(g, c->device);
-  if (wg == Where::OtherDevice) return refuse("ndlqr_hip_solve_adjoint: g lies in the memory of another device than the solver's");
+  CallerArrays<1> ga = {{const_cast<double*>(g)}, {((size_t)u.rows * u.N - u.m) * d.batch}};
+  int err = ga.classify(c, "ndlqr_hip_solve_adjoint", "g lies");
+  if (err) return err;
   HIP_TRY(sync_all(c));
   c->cur = 0;  // cached records / factors live in the primary set
   BufferSet& s = c->set[0];
-  const size_t nvars = (size_t)u.rows * u.N - u.m;
-  if (!c->adj_rhs) HIP_TRY(hipMalloc(&c->adj_rhs, bytes_z(d)));
-  if (!c->adj_save) HIP_TRY(hipMalloc(&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n));
+  err = alloc_missing({{&c->adj_rhs, bytes_z(d)}, {&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n}});
+  if (err) return err;
   if (!c->adj_z) {
     HIP_TRY(hipMalloc(&c->adj_z, bytes_z(d)));
     HIP_TRY(hipMemsetAsync(c->adj_z, 0, bytes_z(d), s.stream));  // (entries a re-solve does not write: the pad rows)
   }
-  const double* gd = g;
-  if (wg != Where::OwnDevice) {
-    const int serr = ensure_grad_stage(c, nvars * d.batch);
-    if (serr) return serr;
-    HIP_TRY(hipMemcpyAsync(c->grad_stage, g, sizeof(double) * nvars * d.batch, hipMemcpyDefault, s.stream));
-    gd = c->grad_stage;
-  }
+  err = ensure_grad_stage(c, ga.stage);
+  if (err) return err;
+  ga.place(c);
+  err = ga.copy(s.stream, true);
+  if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, gd, c->adj_rhs);
+  hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)ga.dev[0],
+                     c->adj_rhs);
   HIP_TRY(hipGetLastError());
   HIP_TRY(adjoint_scratch(c, false));
-  const int rerr = launch_resolve(c, c->adj_rhs, c->adj_z,
-                                  "adjoint solve: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
-  if (rerr) return rerr;
+  err = launch_resolve(c, c->adj_rhs, c->adj_z,
+                       "adjoint solve: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
+  if (err) return err;
   HIP_TRY(hipGetLastError());
   HIP_TRY(adjoint_scratch(c, true));
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
+  note_elapsed(c, s);
   c->adj_gen = c->soln_gen;
   return NDLQR_OK;
 }
@@ -1656,22 +1715,19 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
-  double* user[ndlqr::GRAD_COUNT] = {gA, gB, gQ, gR, gq, gr, gd, gx0};
-  bool own[ndlqr::GRAD_COUNT] = {};  // this device's memory: written by the kernels as it is
-  size_t size[ndlqr::GRAD_COUNT] = {};
-  size_t stage = 0, total = 0;
+  CallerArrays<ndlqr::GRAD_COUNT> ga = {{gA, gB, gQ, gR, gq, gr, gd, gx0}, {}};
+  double* const* user = ga.user;
+  size_t total = 0;
   ndlqr::GradOut out = {};
   for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) {
     if (!user[o]) continue;
-    const Where wo = where(user[o], c->device);
-    if (wo == Where::OtherDevice) return refuse("ndlqr_hip_gradients: an output lies in the memory of another device than the solver's");
     const bool summed = (sum_mask >> o) & 1u;
     const size_t per = o == ndlqr::GRAD_x0 ? (size_t)u.n : (size_t)u.N * ndlqr::grad_width(u, o);
-    size[o] = summed ? per : per * d.batch;
-    own[o] = wo == Where::OwnDevice;
-    if (!own[o]) stage += size[o];
+    ga.cnt[o] = summed ? per : per * d.batch;
     if (summed) { out.off[o] = total; total += per; }
   }
+  int err = ga.classify(c, "ndlqr_hip_gradients", "an output lies");
+  if (err) return err;
   out.sum = sum_mask;
   out.total = total;
   // chunk of knots per workgroup: the accumulators of its summed outputs and its z | w blocks within 48 KB of LDS where
@@ -1703,19 +1759,13 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
     nsplit = (d.batch + ppb - 1) / ppb;
   }
   const size_t npart = nsplit > 1 ? (size_t)nsplit * total : 0;
-  {
-    const int serr = ensure_grad_stage(c, stage + npart);
-    if (serr) return serr;
-  }
+  err = ensure_grad_stage(c, ga.stage + npart);
+  if (err) return err;
   HIP_TRY(sync_all(c));
   BufferSet& s = c->set[0];
-  double* at = c->grad_stage;
-  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) {
-    if (!user[o]) continue;
-    out.p[o] = own[o] ? user[o] : at;
-    if (!own[o]) at += size[o];
-  }
-  double* part = npart ? at : nullptr;
+  double* part = ga.place(c);  // (the partial sums behind the staged outputs)
+  if (!npart) part = nullptr;
+  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) out.p[o] = ga.dev[o];
   const double* z = c->set[c->latest].z;
   const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
   if (lds > 64 * 1024)  // (beyond the default limit of dynamic LDS)
@@ -1723,12 +1773,8 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
                                        : reinterpret_cast<const void*>(&ndlqr::grad_assemble<false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  if (strict)
-    hipLaunchKernelGGL(ndlqr::grad_assemble<true>, dim3(nchunks, nsplit, nslice), dim3(256), lds, s.stream, u, d, KC, ppb,
-                       (int)EC, z, (const double*)c->adj_z, out, part);
-  else
-    hipLaunchKernelGGL(ndlqr::grad_assemble<false>, dim3(nchunks, nsplit, nslice), dim3(256), lds, s.stream, u, d, KC, ppb,
-                       (int)EC, z, (const double*)c->adj_z, out, part);
+  launch_strict(strict, ndlqr::grad_assemble, dim3(nchunks, nsplit, nslice), dim3(256), lds, s.stream, u, d, KC, ppb, (int)EC,
+                z, (const double*)c->adj_z, out, part);
   HIP_TRY(hipGetLastError());
   if (part) {
     hipLaunchKernelGGL(ndlqr::grad_sum_splits, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s.stream, out, nsplit,
@@ -1736,12 +1782,10 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o)
-    if (user[o] && !own[o])
-      HIP_TRY(hipMemcpyAsync(user[o], out.p[o], sizeof(double) * size[o], hipMemcpyDefault, s.stream));
+  err = ga.copy(s.stream, false);
+  if (err) return err;
   HIP_TRY(hipStreamSynchronize(s.stream));
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
+  note_elapsed(c, s);
   return NDLQR_OK;
 }
 
@@ -1755,13 +1799,6 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
 // problems next to the running count and, when it is not zero, restores QR, shifts it by the new vector and factors the
 // whole batch again -- one factorisation serves every problem that changed in that round.
 
-template <typename T>
-static int box_alloc(T** p, size_t bytes) {
-  if (*p) return NDLQR_OK;
-  HIP_TRY(hipMalloc(p, bytes));
-  return NDLQR_OK;
-}
-static int fail_if(hipError_t e, const char* what) { return e == hipSuccess ? NDLQR_OK : fail(what, e); }
 
 // Bounds in the caller's layout, [P][N][n] and [P][N][m] with P = batch, or P = 1 (shared): this device's memory is read
 // as it is, host memory is staged through HBM. Checked (lo <= hi for every used entry) before anything is replaced.
@@ -1773,43 +1810,25 @@ int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const do
   HIP_TRY(hipSetDevice(c->device));
   const int P = shared ? 1 : d.batch;
   const size_t nx = (size_t)P * u.N * u.n, nu = (size_t)P * u.N * u.m;
-  const double* src[4] = {xlo, xhi, ulo, uhi};
-  const size_t cnt[4] = {nx, nx, nu, nu};
-  Where w[4] = {Where::OwnDevice, Where::OwnDevice, Where::OwnDevice, Where::OwnDevice};
-  size_t stage = 0;
-  for (int k = 0; k < 4; ++k) {
-    if (!src[k]) continue;
-    w[k] = where(src[k], c->device);
-    if (w[k] == Where::OtherDevice) return refuse("ndlqr_hip_set_bounds: bounds lie in the memory of another device than the solver's");
-    if (w[k] != Where::OwnDevice) stage += cnt[k];
-  }
-  {
-    const int serr = ensure_grad_stage(c, stage);
-    if (serr) return serr;
-  }
+  CallerArrays<4> in = {{const_cast<double*>(xlo), const_cast<double*>(xhi), const_cast<double*>(ulo), const_cast<double*>(uhi)},
+                        {nx, nx, nu, nu}};
+  int err = in.classify(c, "ndlqr_hip_set_bounds", "bounds lie");
+  if (!err) err = ensure_grad_stage(c, in.stage);
+  if (err) return err;
   const size_t nlo = sizeof(double) * (size_t)d.batch * d.N * d.w;  // (room for per-problem bounds, shared or not)
   if (!c->box_mask) {
     HIP_TRY(hipMalloc(&c->box_mask, (size_t)d.batch * d.N * d.w));
     HIP_TRY(hipMemset(c->box_mask, 0, (size_t)d.batch * d.N * d.w));
   }
-  int aerr = box_alloc(&c->box_lo, nlo);
-  if (!aerr) aerr = box_alloc(&c->box_hi, nlo);
-  if (!aerr) aerr = box_alloc(&c->box_word, 4 * sizeof(int));
-  if (aerr) return aerr;
+  err = alloc_missing({{&c->box_lo, nlo}, {&c->box_hi, nlo}, {&c->box_word, 4 * sizeof(int)}});
+  if (err) return err;
   if (!c->h_box_word) HIP_TRY(hipHostMalloc((void**)&c->h_box_word, 5 * sizeof(int), hipHostMallocDefault));
   HIP_TRY(sync_all(c));  // (a solve in flight may still read the bounds)
   BufferSet& s = c->set[0];
-  const double* view[4] = {};
-  double* at = c->grad_stage;
-  for (int k = 0; k < 4; ++k) {
-    if (!src[k]) continue;
-    view[k] = src[k];
-    if (w[k] != Where::OwnDevice) {
-      HIP_TRY(hipMemcpyAsync(at, src[k], sizeof(double) * cnt[k], hipMemcpyDefault, s.stream));
-      view[k] = at;
-      at += cnt[k];
-    }
-  }
+  in.place(c);
+  err = in.copy(s.stream, true);
+  if (err) return err;
+  const double* const* view = in.dev;
   HIP_TRY(hipMemsetAsync(c->box_word, 0, 4 * sizeof(int), s.stream));
   hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 0,
                      c->box_lo, c->box_hi, c->box_mask, c->box_word + 2, c->box_word + 3);
@@ -1844,21 +1863,100 @@ static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd) {
   c->box_fact = false;
   int err = prepare_solve(c, nullptr);  // (KEEP_*: stream-ordered on the primary set)
   if (!err) err = launch_solve(c);
-  if (!err) c->state_dirty = false;
-  if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
-  if (!err) {  // a non-positive pivot of the shifted factorisation (e.g. Q or R <= 0 on an unbounded entry): no iterations
-    int seen = 0;
-    for (const BufferSet& b : c->set)
-      if (b.h_fail && *b.h_fail > seen) seen = *b.h_fail;
-    c->last_failures = seen - c->fail_base;
-    c->fail_base = seen;
-    if (c->last_failures > 0) {
-      refuse("ndlqr_hip_solve_box: " + std::to_string(c->last_failures) + " non-positive pivot(s) in the factorisation of "
-             "Q + rho M, R + rho M");
-      err = *not_spd = NDLQR_ERR_NOT_SPD;
-    }
+  if (err) return err;
+  c->state_dirty = false;
+  HIP_TRY(hipStreamSynchronize(st));
+  // a non-positive pivot of the shifted factorisation (e.g. Q or R <= 0 on an unbounded entry): no iterations
+  int seen = 0;
+  for (const BufferSet& b : c->set)
+    if (b.h_fail && *b.h_fail > seen) seen = *b.h_fail;
+  c->last_failures = seen - c->fail_base;
+  c->fail_base = seen;
+  if (c->last_failures > 0) {
+    refuse("ndlqr_hip_solve_box: " + std::to_string(c->last_failures) + " non-positive pivot(s) in the factorisation of "
+           "Q + rho M, R + rho M");
+    return *not_spd = NDLQR_ERR_NOT_SPD;
   }
-  return err;
+  return NDLQR_OK;
+}
+
+// QR shifted by rho M in place, with the flags of the shifted factorisation instead of the caller's and, once the caller has
+// put it there, its kept state instead of the plain API's: from open() to close(). A scope left without close() (an early
+// return) restores the same. Everything is enqueued on the primary set's stream.
+struct ShiftedQR {
+  NdlqrHipCtx* c;
+  const unsigned user_flags;
+  bool open_ = false, columns_saved = false;
+  explicit ShiftedQR(NdlqrHipCtx* ctx) : c(ctx), user_flags(ctx->flags) {}
+  ShiftedQR(const ShiftedQR&) = delete;
+  ~ShiftedQR() { (void)close(); }
+  int shift(const double* rho) {
+    const ndlqr::Dims& d = c->d;
+    hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, c->set[0].stream, d, rho, (const double*)c->box_lo,
+                       (const double*)c->box_hi, c->box_bstride, c->QR);
+    HIP_TRY(hipGetLastError());
+    return NDLQR_OK;
+  }
+  // QR saved, shifted by the penalties `rho` [batch] on the bounded entries, c->flags = flags
+  int open(const double* rho, unsigned flags) {
+    HIP_TRY(hipMemcpyAsync(c->box_qr_save, c->QR, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
+    open_ = true;
+    const int err = shift(rho);
+    c->flags = flags;
+    return err;
+  }
+  // new penalties: the saved QR again, shifted by them
+  int reshift(const double* rho) {
+    HIP_TRY(hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
+    return shift(rho);
+  }
+  // the right-hand-side columns of the kept records, which the re-solves of an adjoint overwrite: restored by close()
+  int save_record_columns() {
+    HIP_TRY(adjoint_scratch(c, false));
+    columns_saved = true;
+    return NDLQR_OK;
+  }
+  // Record columns and QR restored, the caller's flags back; the kept records / factors belong to the shifted matrix, so the
+  // plain re-solves refuse until the next solve. The first error.
+  int close() {
+    if (!open_) return NDLQR_OK;
+    open_ = false;
+    const hipError_t ce = columns_saved ? adjoint_scratch(c, true) : hipSuccess;
+    const hipError_t qe = hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream);
+    c->flags = user_flags;
+    c->kept.forget_factorisation();
+    if (ce != hipSuccess) return fail("restoring the record columns", ce);
+    return qe != hipSuccess ? fail("restoring QR", qe) : NDLQR_OK;
+  }
+};
+
+// iters / status of a constrained solve or its adjoint (`who`) go to host memory or this device's
+static int refuse_foreign_iters_status(const NdlqrHipCtx* c, const char* who, const int* iters, const int* status) {
+  for (const int* p : {iters, status})
+    if (p && where(p, c->device) == Where::OtherDevice)
+      return refuse(std::string(who) + ": iters / status lie in the memory of another device than the solver's");
+  return NDLQR_OK;
+}
+
+// The per-problem iteration counts and status words behind everything enqueued on st, for the caller (null: not asked
+// for); a problem still running at max_iter (0) reports 2: the last iterate. Synchronises st.
+static int deliver_iters_status(const NdlqrHipCtx* c, hipStream_t st, const int* d_iters, const int* d_status, int* iters,
+                                int* status) {
+  const size_t bytes = sizeof(int) * (size_t)c->d.batch;
+  std::vector<int> h_it((size_t)c->d.batch), h_st((size_t)c->d.batch);
+  HIP_TRY(hipMemcpyAsync(h_it.data(), d_iters, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_st.data(), d_status, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int& v : h_st)
+    if (v == 0) v = 2;
+  int* user[2] = {iters, status};
+  const int* val[2] = {h_it.data(), h_st.data()};
+  for (int k = 0; k < 2; ++k) {
+    if (!user[k]) continue;
+    if (where(user[k], c->device) == Where::OwnDevice) HIP_TRY(hipMemcpy(user[k], val[k], bytes, hipMemcpyHostToDevice));
+    else memcpy(user[k], val[k], bytes);
+  }
+  return NDLQR_OK;
 }
 
 int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
@@ -1870,36 +1968,27 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   if (!c->box_have_bounds) return refuse("ndlqr_hip_solve_box: no bounds (ndlqr_hip_set_bounds first)");
   const ndlqr::Dims& d = c->d;
   HIP_TRY(hipSetDevice(c->device));
-  for (const int* p : {iters, status})
-    if (p && where(p, c->device) == Where::OtherDevice)
-      return refuse("ndlqr_hip_solve_box: iters / status lie in the memory of another device than the solver's");
+  int err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_box", iters, status);
+  if (err) return err;
   const size_t nz = bytes_z(d), nv = sizeof(double) * (size_t)d.batch * d.N * d.w;
   if (!c->box_z) {
     HIP_TRY(hipMalloc(&c->box_z, nz));
     HIP_TRY(hipMemset(c->box_z, 0, nz));  // (entries a re-solve does not write: the pad rows)
   }
-  int aerr = box_alloc(&c->box_v, nv);
-  if (!aerr) aerr = box_alloc(&c->box_y, nv);
-  if (!aerr) aerr = box_alloc(&c->box_qr_save, bytes_QR(d));
-  if (!aerr) aerr = box_alloc(&c->box_rhs[0], nz);
-  if (!aerr) aerr = box_alloc(&c->box_rhs[1], nz);
-  if (!aerr) aerr = box_alloc(&c->box_resid, sizeof(double) * 2 * (size_t)d.batch);
-  if (!aerr) aerr = box_alloc(&c->box_status, sizeof(int) * (size_t)d.batch);
-  if (!aerr) aerr = box_alloc(&c->box_iters, sizeof(int) * (size_t)d.batch);
-  if (!aerr) aerr = box_alloc(&c->box_rho, sizeof(double) * (size_t)d.batch);
-  if (aerr) return aerr;
+  err = alloc_missing({{&c->box_v, nv}, {&c->box_y, nv}, {&c->box_qr_save, bytes_QR(d)}, {&c->box_rhs[0], nz},
+                       {&c->box_rhs[1], nz}, {&c->box_resid, sizeof(double) * 2 * (size_t)d.batch},
+                       {&c->box_status, sizeof(int) * (size_t)d.batch}, {&c->box_iters, sizeof(int) * (size_t)d.batch},
+                       {&c->box_rho, sizeof(double) * (size_t)d.batch}});
+  if (err) return err;
   // 1. everything idle, the primary set current with an up-to-date right-hand side
   HIP_TRY(sync_all(c));
   c->cur = 0;
-  {
-    const int merr = rhs_make_current(c, 0xFu);
-    if (merr) return merr;
-  }
+  err = rhs_make_current(c, 0xFu);
+  if (err) return err;
   BufferSet& s = c->set[0];
   const hipStream_t st = s.stream;
   const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
-  const unsigned user_flags = c->flags;
-  const unsigned box_flags = user_flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
+  const unsigned box_flags = c->flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
   // the remembered factorisation applies to an adaptive warm start whatever its penalties are (the settings' rho is
   // ignored: an MPC loop keeps what it learnt); everywhere else only when they are all the settings' rho
   const bool usable = c->box_fact && c->box_flags == box_flags;
@@ -1908,140 +1997,101 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   bool uniform = keep_rho ? c->box_rho_uniform : true;
   const double uniform_value = keep_rho ? c->box_rho_value : rho;
   HIP_TRY(hipEventRecord(s.ev_start, st));
-  // 2. the penalties; shift QR (restored on every exit below)
+  // 2. the penalties
   if (!reuse) {
     c->box_fact = false;  // (the remembered factorisation belongs to the penalties overwritten here)
     hipLaunchKernelGGL(ndlqr::box_fill_rho, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, rho, c->box_rho);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(c->box_qr_save, c->QR, bytes_QR(d), hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)c->box_rho,
-                     (const double*)c->box_lo, (const double*)c->box_hi, c->box_bstride, c->QR);
-  int err = fail_if(hipGetLastError(), "box_shift_qr");
   bool factored = false;  // the shifted matrix was factored in this call (the resident solution is then overwritten)
   int not_spd = NDLQR_OK;
-  c->flags = box_flags;
-  // 3. factor the shifted matrix, unless the remembered factorisation applies
-  if (!err && reuse) {
-    c->rec_complete = c->box_rec_complete;
-    c->rec_compact = c->box_rec_compact;
-    c->fact_valid = c->box_fact_valid;
-    c->schedule = c->box_schedule;
-  } else if (!err) {
-    factored = true;
-    err = box_factor(c, st, &not_spd);
-  }
-  // 4. the iterations
-  const double* lo = c->box_lo;
-  const double* hi = c->box_hi;
-  const size_t bs = c->box_bstride;
-  ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, rho_min, rho_max};
-  const double* rhov = c->box_rho;
-  int done_iters = 0;
-  if (!err) {
+  ShiftedQR shifted(c);
+  // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
+  const auto iterate = [&]() -> int {
+    // 3. shift QR; factor the shifted matrix, unless the remembered factorisation applies
+    int e = shifted.open(c->box_rho, box_flags);
+    if (e) return e;
+    if (reuse) {
+      c->kept = c->box_kept;
+    } else {
+      factored = true;
+      e = box_factor(c, st, &not_spd);
+      if (e) return e;
+    }
+    // 4. the iterations
+    const double* lo = c->box_lo;
+    const double* hi = c->box_hi;
+    const size_t bs = c->box_bstride;
+    const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, rho_min, rho_max};
+    const double* rhov = c->box_rho;
     const int cold = warm_start && c->box_have_vy ? 0 : 1;
-    if (strict)
-      hipLaunchKernelGGL(ndlqr::box_start<true>, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, lo, hi, bs,
-                         (const double*)s.rhs, c->box_v, c->box_y, c->box_rhs[0], c->box_rhs[1]);
-    else
-      hipLaunchKernelGGL(ndlqr::box_start<false>, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, lo, hi, bs,
-                         (const double*)s.rhs, c->box_v, c->box_y, c->box_rhs[0], c->box_rhs[1]);
-    err = fail_if(hipGetLastError(), "box_start");
+    launch_strict(strict, ndlqr::box_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, lo, hi, bs,
+                  (const double*)s.rhs, c->box_v, c->box_y, c->box_rhs[0], c->box_rhs[1]);
+    HIP_TRY(hipGetLastError());
     c->box_have_vy = true;
     c->h_box_word[0] = d.batch;
     c->h_box_word[1] = 0;
-    if (!err) err = fail_if(hipMemcpyAsync(c->box_word, c->h_box_word, 2 * sizeof(int), hipMemcpyHostToDevice, st), "box running count");
-    if (!err) err = fail_if(hipMemsetAsync(c->box_status, 0, sizeof(int) * (size_t)d.batch, st), "box status");
-  }
-  for (int it = 1; it <= max_iter && !err; ++it) {
-    const double* rc = c->box_rhs[(it - 1) & 1];
-    double* rn = c->box_rhs[it & 1];
-    err = launch_resolve(c, rc, c->box_z, "box-constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
-    if (err) break;
-    const int adapt = adapt_every > 0 && it % adapt_every == 0 && it < max_iter;
-    if (strict)
-      hipLaunchKernelGGL(ndlqr::box_update<true>, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box_z,
-                         lo, hi, bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_rho, c->box_status,
-                         c->box_iters, c->box_resid, c->box_word);
-    else
-      hipLaunchKernelGGL(ndlqr::box_update<false>, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box_z,
-                         lo, hi, bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_rho, c->box_status,
-                         c->box_iters, c->box_resid, c->box_word);
-    err = fail_if(hipGetLastError(), "box_update");
-    done_iters = it;
-    if (!err && (it % check_every == 0 || it == max_iter || adapt)) {
-      // 5. one word: how many problems still run; after an adapting update also how many changed their penalty
-      err = fail_if(hipMemcpyAsync(c->h_box_word, c->box_word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st),
-                    "box running count");
-      if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
-      if (!err && c->h_box_word[0] == 0) break;
-      if (!err && adapt && c->h_box_word[1] != 0) {
-        // 5a. new penalties: the saved QR shifted by the new vector and factored as above (frozen problems keep their
-        // penalty: the same factors again, so their later re-solves reproduce their z)
-        uniform = false;
-        factored = true;
-        err = fail_if(hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(d), hipMemcpyDeviceToDevice, st), "restoring QR");
-        if (!err) {
-          hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, lo, hi, bs, c->QR);
-          err = fail_if(hipGetLastError(), "box_shift_qr");
+    HIP_TRY(hipMemcpyAsync(c->box_word, c->h_box_word, 2 * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(c->box_status, 0, sizeof(int) * (size_t)d.batch, st));
+    for (int it = 1; it <= max_iter; ++it) {
+      const double* rc = c->box_rhs[(it - 1) & 1];
+      double* rn = c->box_rhs[it & 1];
+      e = launch_resolve(c, rc, c->box_z, "box-constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      if (e) return e;
+      const int adapt = adapt_every > 0 && it % adapt_every == 0 && it < max_iter;
+      launch_strict(strict, ndlqr::box_update, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box_z, lo, hi,
+                    bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_rho, c->box_status, c->box_iters,
+                    c->box_resid, c->box_word);
+      HIP_TRY(hipGetLastError());
+      if (it % check_every == 0 || it == max_iter || adapt) {
+        // 5. one word: how many problems still run; after an adapting update also how many changed their penalty
+        HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c->h_box_word[0] == 0) break;
+        if (adapt && c->h_box_word[1] != 0) {
+          // 5a. new penalties: the saved QR shifted by the new vector and factored as above (frozen problems keep their
+          // penalty: the same factors again, so their later re-solves reproduce their z)
+          uniform = false;
+          factored = true;
+          e = shifted.reshift(rhov);
+          if (!e) e = box_factor(c, st, &not_spd);
+          if (e) return e;
+          HIP_TRY(hipMemsetAsync(c->box_word + 1, 0, sizeof(int), st));
         }
-        if (!err) err = box_factor(c, st, &not_spd);
-        if (!err) err = fail_if(hipMemsetAsync(c->box_word + 1, 0, sizeof(int), st), "box changed count");
       }
     }
-  }
-  // 6. deliver, restore QR, bookkeeping
-  if (!err && done_iters > 0) {
+    // 6. deliver
     hipLaunchKernelGGL(ndlqr::box_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, lo, hi, bs, (const double*)c->box_z, c->box_v,
                        s.z);
-    err = fail_if(hipGetLastError(), "box_finish");
-  }
-  const hipError_t re = hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(d), hipMemcpyDeviceToDevice, st);
-  if (!err && re != hipSuccess) err = fail("restoring QR", re);
-  c->flags = user_flags;
+    HIP_TRY(hipGetLastError());
+    return NDLQR_OK;
+  };
+  err = iterate();
+  // 7. restore QR, bookkeeping
+  const KeptState shifted_kept = c->kept;  // (close() forgets it for the plain API)
+  const int cerr = shifted.close();
+  if (!err) err = cerr;
   if (!err) {
     c->box_fact = true;
     c->box_rho_uniform = uniform;
     c->box_rho_value = uniform_value;
     c->box_flags = box_flags;
-    c->box_rec_complete = c->rec_complete;
-    c->box_rec_compact = c->rec_compact;
-    c->box_fact_valid = c->fact_valid;
-    c->box_schedule = c->schedule;
+    c->box_kept = shifted_kept;
   } else {
     c->box_fact = false;
     c->box_have_vy = false;
     if (!not_spd) c->state_dirty = true;  // (a failed launch; a non-positive pivot leaves the device state clean)
     if (factored) c->z_invalid = true;    // (the factorisation solved the shifted matrix with the unshifted right-hand side)
-  }
-  // the kept records / factors belong to the shifted matrix: the plain re-solves refuse until the next solve
-  c->rec_complete = false;
-  c->fact_valid = false;
-  if (err) {
     (void)hipStreamSynchronize(st);
     return err;
   }
   note_solution(c);
   c->box_soln_gen = c->soln_gen;
   HIP_TRY(hipEventRecord(s.ev_stop, st));
-  std::vector<int> h_it((size_t)d.batch), h_st((size_t)d.batch);
-  HIP_TRY(hipMemcpyAsync(h_it.data(), c->box_iters, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h_st.data(), c->box_status, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
   c->timing_pending = true;
-  const int serr = ndlqr_hip_synchronize(c);
-  if (serr) return serr;
-  for (int& v : h_st)
-    if (v == 0) v = 2;  // max_iter reached: the last iterate
-  int* user[2] = {iters, status};
-  const std::vector<int>* val[2] = {&h_it, &h_st};
-  for (int k = 0; k < 2; ++k) {  // (host or this device's memory)
-    if (!user[k]) continue;
-    if (where(user[k], c->device) == Where::OwnDevice)
-      HIP_TRY(hipMemcpy(user[k], val[k]->data(), sizeof(int) * (size_t)d.batch, hipMemcpyHostToDevice));
-    else
-      memcpy(user[k], val[k]->data(), sizeof(int) * (size_t)d.batch);
-  }
-  return NDLQR_OK;
+  err = deliver_iters_status(c, st, c->box_iters, c->box_status, iters, status);
+  if (err) return err;
+  return ndlqr_hip_synchronize(c);
 }
 
 int ndlqr_hip_download_box_penalties(NdlqrHipCtx* c, double* rho) {
@@ -2061,36 +2111,18 @@ int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* m
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
-  double* user[2] = {mu_x, mu_u};
-  const size_t cnt[2] = {(size_t)u.batch * u.N * u.n, (size_t)u.batch * u.N * u.m};
-  bool own[2] = {};
-  size_t stage = 0;
-  for (int k = 0; k < 2; ++k) {
-    if (!user[k]) continue;
-    const Where w = where(user[k], c->device);
-    if (w == Where::OtherDevice)
-      return refuse("ndlqr_hip_download_bound_multipliers: an output lies in the memory of another device than the solver's");
-    own[k] = w == Where::OwnDevice;
-    if (!own[k]) stage += cnt[k];
-  }
-  {
-    const int serr = ensure_grad_stage(c, stage);
-    if (serr) return serr;
-  }
+  CallerArrays<2> out = {{mu_x, mu_u}, {(size_t)u.batch * u.N * u.n, (size_t)u.batch * u.N * u.m}};
+  int err = out.classify(c, "ndlqr_hip_download_bound_multipliers", "an output lies");
+  if (!err) err = ensure_grad_stage(c, out.stage);
+  if (err) return err;
   HIP_TRY(sync_all(c));
   const BufferSet& s = c->set[0];
-  double* out[2] = {};
-  double* at = c->grad_stage;
-  for (int k = 0; k < 2; ++k) {
-    if (!user[k]) continue;
-    out[k] = own[k] ? user[k] : at;
-    if (!own[k]) at += cnt[k];
-  }
+  out.place(c);
   hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box_rho,
-                     (const double*)c->box_y, out[0], out[1]);
+                     (const double*)c->box_y, out.dev[0], out.dev[1]);
   HIP_TRY(hipGetLastError());
-  for (int k = 0; k < 2; ++k)
-    if (user[k] && !own[k]) HIP_TRY(hipMemcpyAsync(user[k], out[k], sizeof(double) * cnt[k], hipMemcpyDefault, s.stream));
+  err = out.copy(s.stream, false);
+  if (err) return err;
   HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }
@@ -2111,159 +2143,104 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
   if (c->box_soln_gen == 0 || c->box_soln_gen != c->soln_gen || !c->box_fact || c->inputs_replaced)
     return refuse("ndlqr_hip_solve_box_adjoint: the resident solution is not that of the latest constrained solve (a solve, "
                   "step, re-solve, new inputs or new bounds came after it)");
-  if (!strcmp(c->box_schedule, "reduced-time-shard")) return refuse("ndlqr_hip_solve_box_adjoint: not available on a time-axis shard");
+  if (!strcmp(c->box_kept.schedule, "reduced-time-shard")) return refuse("ndlqr_hip_solve_box_adjoint: not available on a time-axis shard");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
-  const Where wg = where(g, c->device);
-  if (wg == Where::OtherDevice) return refuse("ndlqr_hip_solve_box_adjoint: g lies in the memory of another device than the solver's");
-  for (const int* p : {iters, status})
-    if (p && where(p, c->device) == Where::OtherDevice)
-      return refuse("ndlqr_hip_solve_box_adjoint: iters / status lie in the memory of another device than the solver's");
+  CallerArrays<1> ga = {{const_cast<double*>(g)}, {((size_t)u.rows * u.N - u.m) * d.batch}};
+  int err = ga.classify(c, "ndlqr_hip_solve_box_adjoint", "g lies");
+  if (!err) err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_box_adjoint", iters, status);
+  if (err) return err;
   const size_t nz = bytes_z(d), nv = sizeof(double) * (size_t)d.batch * d.N * d.w;
-  const size_t nvars = (size_t)u.rows * u.N - u.m;
   if (!c->adj_z) {
     HIP_TRY(hipMalloc(&c->adj_z, nz));
     HIP_TRY(hipMemset(c->adj_z, 0, nz));  // (entries a re-solve does not write: the pad rows)
   }
-  int aerr = box_alloc(&c->adj_rhs, nz);
-  if (!aerr) aerr = box_alloc(&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n);
-  if (!aerr) aerr = box_alloc(&c->abox_code, (size_t)d.batch * d.N * d.w);
-  if (!aerr) aerr = box_alloc(&c->abox_v, nv);
-  if (!aerr) aerr = box_alloc(&c->abox_y, nv);
-  if (!aerr) aerr = box_alloc(&c->abox_rhs[0], nz);
-  if (!aerr) aerr = box_alloc(&c->abox_rhs[1], nz);
-  if (!aerr) aerr = box_alloc(&c->abox_resid, sizeof(double) * 2 * (size_t)d.batch);
-  if (!aerr) aerr = box_alloc(&c->abox_status, sizeof(int) * (size_t)d.batch);
-  if (!aerr) aerr = box_alloc(&c->abox_iters, sizeof(int) * (size_t)d.batch);
-  if (!aerr) aerr = box_alloc(&c->abox_word, sizeof(int));
-  if (!aerr && wg != Where::OwnDevice) aerr = ensure_grad_stage(c, nvars * d.batch);
-  if (aerr) return aerr;
+  err = alloc_missing({{&c->adj_rhs, nz}, {&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n},
+                       {&c->abox_code, (size_t)d.batch * d.N * d.w}, {&c->abox_v, nv}, {&c->abox_y, nv}, {&c->abox_rhs[0], nz},
+                       {&c->abox_rhs[1], nz}, {&c->abox_resid, sizeof(double) * 2 * (size_t)d.batch},
+                       {&c->abox_status, sizeof(int) * (size_t)d.batch}, {&c->abox_iters, sizeof(int) * (size_t)d.batch},
+                       {&c->abox_word, sizeof(int)}});
+  if (!err) err = ensure_grad_stage(c, ga.stage);
+  if (err) return err;
   // 1. everything idle, the primary set current; g packed into the adjoint's resident right-hand side
   HIP_TRY(sync_all(c));
   c->cur = 0;
   BufferSet& s = c->set[0];
   const hipStream_t st = s.stream;
-  const double* gd = g;
-  if (wg != Where::OwnDevice) {
-    HIP_TRY(hipMemcpyAsync(c->grad_stage, g, sizeof(double) * nvars * d.batch, hipMemcpyDefault, st));
-    gd = c->grad_stage;
-  }
+  ga.place(c);
+  err = ga.copy(st, true);
+  if (err) return err;
   c->abox_gen = 0;
   c->adj_gen = 0;
   const bool strict = (c->box_flags & NDLQR_FLAG_STRICT_FP) != 0;
-  const unsigned user_flags = c->flags;
-  const double* rho = c->box_rho;  // (the forward's final penalties: those of the remembered factorisation)
-  const double* lo = c->box_lo;
-  const double* hi = c->box_hi;
-  const size_t bs = c->box_bstride;
   HIP_TRY(hipEventRecord(s.ev_start, st));
-  hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, st, u, d, gd, c->adj_rhs);
-  int err = fail_if(hipGetLastError(), "adjoint_rhs_generic");
-  // 2. shift QR, take up the remembered shifted factorisation, save the right-hand-side columns of the records
-  if (!err) err = fail_if(hipMemcpyAsync(c->box_qr_save, c->QR, bytes_QR(d), hipMemcpyDeviceToDevice, st), "saving QR");
-  bool shifted = false;
-  if (!err) {
-    hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, lo, hi, bs, c->QR);
-    err = fail_if(hipGetLastError(), "box_shift_qr");
-    shifted = true;
-  }
-  c->flags = c->box_flags;
-  c->rec_complete = c->box_rec_complete;
-  c->rec_compact = c->box_rec_compact;
-  c->fact_valid = c->box_fact_valid;
-  c->schedule = c->box_schedule;
-  bool saved = false;
-  if (!err) {
-    err = fail_if(adjoint_scratch(c, false), "saving the record columns");
-    saved = !err;
-  }
-  // 3. codes, v = y = 0, right-hand sides, status
-  ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
-  if (!err) err = fail_if(hipMemsetAsync(c->abox_word, 0, sizeof(int), st), "box adjoint running count");
-  if (!err) {
-    if (strict)
-      hipLaunchKernelGGL(ndlqr::box_adjoint_start<true>, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, lo, hi, bs,
-                         (const double*)c->box_v, (const int*)c->box_status, (const double*)c->adj_rhs, c->abox_code,
-                         c->abox_v, c->abox_y, c->abox_rhs[0], c->abox_rhs[1], c->abox_status, c->abox_iters, c->abox_word);
-    else
-      hipLaunchKernelGGL(ndlqr::box_adjoint_start<false>, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, lo, hi, bs,
-                         (const double*)c->box_v, (const int*)c->box_status, (const double*)c->adj_rhs, c->abox_code,
-                         c->abox_v, c->abox_y, c->abox_rhs[0], c->abox_rhs[1], c->abox_status, c->abox_iters, c->abox_word);
-    err = fail_if(hipGetLastError(), "box_adjoint_start");
-  }
-  // 4. the iterations (none when every problem's forward ended non-finite)
-  if (!err) {
-    err = fail_if(hipMemcpyAsync(&c->h_box_word[4], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st), "box adjoint running count");
-    if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
-  }
-  const bool any = !err && c->h_box_word[4] > 0;
-  for (int it = 1; it <= max_iter && any && !err; ++it) {
-    const double* rc = c->abox_rhs[(it - 1) & 1];
-    double* rn = c->abox_rhs[it & 1];
-    err = launch_resolve(c, rc, c->adj_z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
-    if (err) break;
-    if (strict)
-      hipLaunchKernelGGL(ndlqr::box_adjoint_update<true>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj_z,
-                         (const unsigned char*)c->abox_code, c->abox_v, c->abox_y, (const double*)c->adj_rhs, rc, rn,
-                         rho, c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
-    else
-      hipLaunchKernelGGL(ndlqr::box_adjoint_update<false>, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj_z,
-                         (const unsigned char*)c->abox_code, c->abox_v, c->abox_y, (const double*)c->adj_rhs, rc, rn,
-                         rho, c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
-    err = fail_if(hipGetLastError(), "box_adjoint_update");
-    if (!err && (it % check_every == 0 || it == max_iter)) {
-      err = fail_if(hipMemcpyAsync(&c->h_box_word[4], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st), "box adjoint running count");
-      if (!err) err = fail_if(hipStreamSynchronize(st), "hipStreamSynchronize");
-      if (!err && c->h_box_word[4] == 0) break;
+  ShiftedQR shifted(c);
+  // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
+  const auto iterate = [&]() -> int {
+    const double* rho = c->box_rho;  // (the forward's final penalties: those of the remembered factorisation)
+    hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, st, u, d, (const double*)ga.dev[0],
+                       c->adj_rhs);
+    HIP_TRY(hipGetLastError());
+    // 2. shift QR, take up the remembered shifted factorisation, save the right-hand-side columns of the records
+    int e = shifted.open(rho, c->box_flags);
+    if (e) return e;
+    c->kept = c->box_kept;
+    e = shifted.save_record_columns();
+    if (e) return e;
+    // 3. codes, v = y = 0, right-hand sides, status
+    const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
+    HIP_TRY(hipMemsetAsync(c->abox_word, 0, sizeof(int), st));
+    launch_strict(strict, ndlqr::box_adjoint_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, (const double*)c->box_lo,
+                  (const double*)c->box_hi, c->box_bstride, (const double*)c->box_v, (const int*)c->box_status,
+                  (const double*)c->adj_rhs, c->abox_code, c->abox_v, c->abox_y, c->abox_rhs[0], c->abox_rhs[1], c->abox_status,
+                  c->abox_iters, c->abox_word);
+    HIP_TRY(hipGetLastError());
+    // 4. the iterations (none when every problem's forward ended non-finite)
+    HIP_TRY(hipMemcpyAsync(&c->h_box_word[4], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const bool any = c->h_box_word[4] > 0;
+    for (int it = 1; it <= max_iter && any; ++it) {
+      const double* rc = c->abox_rhs[(it - 1) & 1];
+      double* rn = c->abox_rhs[it & 1];
+      e = launch_resolve(c, rc, c->adj_z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      if (e) return e;
+      launch_strict(strict, ndlqr::box_adjoint_update, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj_z,
+                    (const unsigned char*)c->abox_code, c->abox_v, c->abox_y, (const double*)c->adj_rhs, rc, rn, rho,
+                    c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
+      HIP_TRY(hipGetLastError());
+      if (it % check_every == 0 || it == max_iter) {
+        HIP_TRY(hipMemcpyAsync(&c->h_box_word[4], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c->h_box_word[4] == 0) break;
+      }
     }
-  }
-  if (!err && !any) {  // (no re-solve ran: a defined w all the same -- the re-solve of the packed g)
-    err = launch_resolve(c, c->abox_rhs[0], c->adj_z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
-    if (!err) err = fail_if(hipGetLastError(), "box adjoint re-solve");
-  }
-  // 5. w = [lambda, v], restore the record columns and QR, bookkeeping
-  if (!err) {
+    if (!any) {  // (no re-solve ran: a defined w all the same -- the re-solve of the packed g)
+      e = launch_resolve(c, c->abox_rhs[0], c->adj_z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      if (e) return e;
+      HIP_TRY(hipGetLastError());
+    }
+    // 5. w = [lambda, v]
     hipLaunchKernelGGL(ndlqr::box_adjoint_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, (const unsigned char*)c->abox_code,
                        (const double*)c->abox_v, c->adj_z);
-    err = fail_if(hipGetLastError(), "box_adjoint_finish");
-  }
-  if (saved) {
-    const hipError_t re = adjoint_scratch(c, true);
-    if (!err && re != hipSuccess) err = fail("restoring the record columns", re);
-  }
-  if (shifted) {
-    const hipError_t re = hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(d), hipMemcpyDeviceToDevice, st);
-    if (!err && re != hipSuccess) err = fail("restoring QR", re);
-  }
-  c->flags = user_flags;
-  c->rec_complete = false;  // (as the constrained solve left them: the kept records / factors are the shifted ones)
-  c->fact_valid = false;
+    HIP_TRY(hipGetLastError());
+    return NDLQR_OK;
+  };
+  err = iterate();
+  // 6. restore the record columns and QR, bookkeeping (the kept state as the constrained solve left it)
+  const int cerr = shifted.close();
+  if (!err) err = cerr;
   if (err) {
     c->state_dirty = true;
     (void)hipStreamSynchronize(st);
     return err;
   }
   HIP_TRY(hipEventRecord(s.ev_stop, st));
-  std::vector<int> h_it((size_t)d.batch), h_st((size_t)d.batch);
-  HIP_TRY(hipMemcpyAsync(h_it.data(), c->abox_iters, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h_st.data(), c->abox_status, sizeof(int) * (size_t)d.batch, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
+  err = deliver_iters_status(c, st, c->abox_iters, c->abox_status, iters, status);
+  if (err) return err;
+  note_elapsed(c, s);
   c->adj_gen = c->soln_gen;
   c->abox_gen = c->soln_gen;
-  for (int& v : h_st)
-    if (v == 0) v = 2;  // max_iter reached: the last iterate
-  int* user[2] = {iters, status};
-  const std::vector<int>* val[2] = {&h_it, &h_st};
-  for (int k = 0; k < 2; ++k) {  // (host or this device's memory)
-    if (!user[k]) continue;
-    if (where(user[k], c->device) == Where::OwnDevice)
-      HIP_TRY(hipMemcpy(user[k], val[k]->data(), sizeof(int) * (size_t)d.batch, hipMemcpyHostToDevice));
-    else
-      memcpy(user[k], val[k]->data(), sizeof(int) * (size_t)d.batch);
-  }
   return NDLQR_OK;
 }
 
@@ -2277,22 +2254,11 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
-  double* user[4] = {gxlo, gxhi, gulo, guhi};
   const size_t P = summed ? 1 : (size_t)d.batch;
-  const size_t cnt[4] = {P * u.N * u.n, P * u.N * u.n, P * u.N * u.m, P * u.N * u.m};
-  bool own[4] = {};
-  size_t stage = 0;
-  bool anyout = false;
-  for (int k = 0; k < 4; ++k) {
-    if (!user[k]) continue;
-    anyout = true;
-    const Where w = where(user[k], c->device);
-    if (w == Where::OtherDevice)
-      return refuse("ndlqr_hip_bound_gradients: an output lies in the memory of another device than the solver's");
-    own[k] = w == Where::OwnDevice;
-    if (!own[k]) stage += cnt[k];
-  }
-  if (!anyout) return NDLQR_OK;
+  CallerArrays<4> go = {{gxlo, gxhi, gulo, guhi}, {P * u.N * u.n, P * u.N * u.n, P * u.N * u.m, P * u.N * u.m}};
+  int err = go.classify(c, "ndlqr_hip_bound_gradients", "an output lies");
+  if (err) return err;
+  if (!gxlo && !gxhi && !gulo && !guhi) return NDLQR_OK;
   // batch sums: entries of [N][n+m] one per thread, the batch split into about 2048 / ceil(entries / 256) runs of problems
   // added in order, then the runs in order (grad_assemble's scheme: deterministic, no atomics)
   const size_t E = (size_t)u.N * (u.n + u.m);
@@ -2306,20 +2272,14 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
     nsplit = (d.batch + ppb - 1) / ppb;
   }
   const size_t npart = nsplit > 1 ? (size_t)nsplit * 2 * E : 0;
-  {
-    const int serr = ensure_grad_stage(c, stage + npart);
-    if (serr) return serr;
-  }
+  err = ensure_grad_stage(c, go.stage + npart);
+  if (err) return err;
   HIP_TRY(sync_all(c));
   BufferSet& s = c->set[0];
   ndlqr::BoundOut out = {};
-  double* at = c->grad_stage;
-  for (int k = 0; k < 4; ++k) {
-    if (!user[k]) continue;
-    out.p[k] = own[k] ? user[k] : at;
-    if (!own[k]) at += cnt[k];
-  }
-  double* part = npart ? at : nullptr;
+  double* part = go.place(c);  // (the partial sums behind the staged outputs)
+  if (!npart) part = nullptr;
+  for (int k = 0; k < 4; ++k) out.p[k] = go.dev[k];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   if (!summed) {
     hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box_rho,
@@ -2336,11 +2296,10 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
     }
   }
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  for (int k = 0; k < 4; ++k)
-    if (user[k] && !own[k]) HIP_TRY(hipMemcpyAsync(user[k], out.p[k], sizeof(double) * cnt[k], hipMemcpyDefault, s.stream));
+  err = go.copy(s.stream, false);
+  if (err) return err;
   HIP_TRY(hipStreamSynchronize(s.stream));
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
+  note_elapsed(c, s);
   return NDLQR_OK;
 }
 
@@ -2366,7 +2325,7 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
   c->cur = 0;
   BufferSet& st = c->set[0];
   const SmallInstance* inst = pick_small(c);
-  if (!inst || !c->rec_complete || !c->rec_compact)
+  if (!inst || !c->kept.rec_complete || !c->kept.rec_compact)
     return refuse("multiple right-hand sides need the compact records of a solve with NDLQR_FLAG_KEEP_RECORDS on a "
                   "size-specialised shape (level-per-launch schedule: batch x N / 4 > 2048, or NDLQR_TREE=0)");
   const ndlqr::Dims& d = c->d;
@@ -2555,9 +2514,9 @@ static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count
   return NDLQR_OK;
 }
 
-const char* ndlqr_hip_schedule(const NdlqrHipCtx* c) { return c ? c->schedule : "none"; }
+const char* ndlqr_hip_schedule(const NdlqrHipCtx* c) { return c ? c->kept.schedule : "none"; }
 
-int ndlqr_hip_factors_valid(const NdlqrHipCtx* c) { return c && c->fact_valid ? 1 : 0; }
+int ndlqr_hip_factors_valid(const NdlqrHipCtx* c) { return c && c->kept.fact_valid ? 1 : 0; }
 
 int ndlqr_hip_pack_solutions_device(NdlqrHipCtx* c, double* dst) {
   if (!c || !dst) return NDLQR_ERR_INVALID;
@@ -2614,7 +2573,7 @@ int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
 
 int ndlqr_hip_download_factors(NdlqrHipCtx* c, int p, double* fact) {
   if (!c || !fact || p < 0 || p >= c->d.batch) return NDLQR_ERR_INVALID;
-  if (!c->fact_valid) return refuse("factor download needs NDLQR_FLAG_KEEP_FACT set before the solve");
+  if (!c->kept.fact_valid) return refuse("factor download needs NDLQR_FLAG_KEEP_FACT set before the solve");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
