@@ -25,6 +25,16 @@ int ndlqr_hip_ensure_F(NdlqrHipCtx* c);
     if (e_ != hipSuccess) return ndlqr_hip_fail(#expr, e_);            \
   } while (0)
 
+// LDS of a workgroup on gfx950, and the dynamic LDS a kernel gets without asking for more
+constexpr size_t kLdsMax = 160 * 1024;
+constexpr size_t kLdsDefaultDynamic = 64 * 1024;
+// ... and the asking, before a launch with `lds` bytes of dynamic LDS
+template <class Kernel>
+static inline hipError_t allow_dynamic_lds(Kernel* kernel, size_t lds) {
+  if (lds <= kLdsDefaultDynamic) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // ------------------------------------------------------------------------------ context
 
 enum { SLOT_LEAF = 0, SLOT_SEP, SLOT_SCHUR, SLOT_BOUNDARY, SLOT_APPLY, SLOT_BOTTOM, SLOT_UPPER, SLOT_TOP, SLOT_COUNT };
@@ -34,9 +44,15 @@ struct PendingEvent {
   hipEvent_t start, stop;
 };
 
+// The kernels a solve runs (plan_solve): a size-specialised instance (launch_small.hpp), the
+// runtime-sized separator-only schedule (launch_reduced_generic) or the knot-based runtime-sized one (launch_generic)
+enum class Family { None, Small, GenericReduced, GenericKnot };
+
 // What the last factorisation left on the primary set (kept records and factors never pipeline), as the plain API's
-// re-solves see it
+// re-solves see it: they run the kernels of the family that wrote the records, whatever the flags say by then
 struct KeptState {
+  Family family = Family::None;  // whose records / slots these are
+  bool time_shard = false;       // ... those of one chunk of a time-axis shard (launch_time_shard): no re-solve
   bool rec_complete = false;  // every separator record and factor is there (fast mode + KEEP / KEEP_RECORDS)
   bool rec_compact = false;   // ... in the compact form of the default schedule (level-0 records = L, the factors of the upper
                               // separators in the slack of those slots): the re-solve is rb_forward / rb_forward_top / rb_backsub
@@ -46,14 +62,13 @@ struct KeptState {
   void forget_factorisation() { rec_complete = fact_valid = false; }
 };
 
-// A launch sequence captured as a hipGraph: the key it was captured under (replayed while that matches) and what the
-// sequence leaves behind (replays do not re-enter the launch code)
+// A launch sequence captured as a hipGraph and the key it was captured under (replayed while that matches; the key
+// determines the SolvePlan, and with it what the sequence leaves behind)
 struct CapturedChain {
   hipGraphExec_t exec = nullptr;
   unsigned flags = 0;
   hipStream_t stream = nullptr;
   unsigned apply = 0;  // (apply_blk0 << 16 | apply_nblk): the restricted back-substitution of a step
-  KeptState kept;  // (fact_valid is not the chain's to say: replay_chain passes the live one through)
   void reset() {
     if (exec) (void)hipGraphExecDestroy(exec);
     exec = nullptr;
@@ -134,6 +149,8 @@ struct NdlqrHipCtx {
   int top_levels = 3;       // tree levels inside reduced_top_mc (NDLQR_TOP_LEVELS, 3 .. 5): beyond three a wavefront takes several separators of the first ones in turn
   bool no_mfma = false;     // NDLQR_NO_MFMA=1: keep the scalar Schur kernel for large blocks (A/B timing)
   int sep_threads = 0;        // NDLQR_SEP_THREADS: workgroup size of the matrix-core separator (0 = by block size)
+  int mult_threads = 0;       // NDLQR_MULT_THREADS: workgroup size of backsub_multipliers_compact (0 = by block size)
+  bool no_reduced_generic = false;  // NDLQR_DEV_NO_REDUCED_GENERIC (developer): A/B against the knot-based runtime-sized schedule
   hipEvent_t ev_step[2] = {};  // end of the steps of ndlqr_hip_step_async, alternating (ndlqr_hip_synchronize_previous)
   unsigned step_count = 0;
   hipEvent_t ev_inputs = nullptr;  // orders the other buffer set's stream behind a device-side replacement of the inputs

@@ -1,6 +1,6 @@
-// launch_small.hpp -- internal: launch sequences of the size-specialised kernels, instantiated
-// once per (nstates, ninputs) in its own translation unit (small_instance.hip) so that the
-// instances compile in parallel.
+// launch_small.hpp -- internal: launch sequences of the size-specialised kernels and the table entry
+// (SmallInstance) ndlqr_hip.hip reaches them through, instantiated once per (nstates, ninputs) in its own
+// translation unit (small_instance.hip) so that the instances compile in parallel.
 #pragma once
 #include "hip_context.hpp"
 #include "kernels_leaf.hpp"
@@ -17,17 +17,31 @@
 //       upper levels in registers, one pass)
 constexpr int kBottomLevels = 2;  // tree levels fused with the leaf phase
 
-// What launch_small is going to do for this context: decided once, before the launch sequence is
-// enqueued (and possibly captured), so that ndlqr_hip.hip can allocate what the schedule needs.
+// What launch_small does for a context with these flags: decided once per solve by the instance's `plan` entry (plan_solve
+// in ndlqr_hip.hip), before the launch sequence is enqueued (and possibly captured), so that the host layer can allocate
+// what the schedule needs and knows what it leaves. launch_small only issues the launches this names.
 struct SmallPlan {
+  bool strict, keep;  // NDLQR_FLAG_STRICT_FP, NDLQR_FLAG_KEEP_FACT: the instance of the knot-based kernels
   bool lean;     // solution by back-substitution from the separator records (fast mode, no KEEP)
   int store_l;   // keep the separator factors for a record-based re-solve (KEEP_RECORDS)
   bool reduced;  // separator-only schedule (bottom_reduced_mc + reduced_level_mc)
   bool tree;     // ... with the whole factorisation in one launch (small batches)
   bool compact;  // ... with compact level-0 records and the two-launch back-substitution (kernels_rowbcast.hpp)
   bool rowbcast; // ... and the bottom levels on the row-broadcast core (four separators per wavefront)
+  bool fuse2;    // ... or tree level 2 inside the bottom launch (bottom8_reduced_mc)
+  int level0;    // first tree level with a launch of its own (reduced_level_mc), up to ...
+  int ltop;      // ... the first one inside reduced_top_mc (== K: no such launch), which starts at ...
+  int top_l0;    // ... this level (level 2 may have gone with the bottom launch)
+  bool top_sweeps;  // reduced_top_mc also runs the top-down sweep over the records of level >= 3 (else rb_backsub_top does)
+  size_t top_lds;   // the sweep array of rb_backsub_top
+  const char* schedule;  // ndlqr_hip_schedule
+  bool rec_complete, rec_compact;  // KeptState
   bool needs_F;  // the schedule reads or writes the factor array
 };
+
+// rb_backsub's thread roles (and those of the re-solve on its records) need eight knots of 2 nx + nu rows in a workgroup
+template <int NX, int NU>
+constexpr bool kRbBacksubFits = 8 * (2 * NX + NU) <= 256;
 
 // An MPC step that wants nothing but a knot range (NDLQR_SOLN_ONLY): the last launch of a back-substitution whose workgroups
 // take eight knots each runs those of the range -- grid and Dims::xoff of that launch.
@@ -55,20 +69,23 @@ static void launch_rb_backsub(const NdlqrHipCtx* c, const dim3 grid, hipStream_t
   hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, MULTI, false>), grid, dim3(256), 0, stream, args...);
 }
 
-template <int NX, int NU, bool STRICT, bool KEEP>
-static SmallPlan plan_small(const NdlqrHipCtx* c) {
+template <int NX, int NU>
+static SmallPlan plan_small(const NdlqrHipCtx* c, const bool strict, const bool keep) {
   const ndlqr::Dims& d = c->d;
-  const BufferSet& s = c->set[c->cur];
-  SmallPlan p;
+  const BufferSet& s = c->set[0];  // (the alternate set is allocated with the same optional buffers: ensure_alt)
+  SmallPlan p = {};
+  p.strict = strict;
+  p.keep = keep;
   // fast mode without KEEP: solution by back-substitution from the separator records (backsub_small
   // resolves K + 4 separators of NX rows in one 256-thread workgroup)
-  p.lean = !STRICT && !KEEP && (d.K + 4) * NX <= 256;
+  p.lean = !strict && !keep && (d.K + 4) * NX <= 256;
   p.store_l = (c->flags & NDLQR_FLAG_KEEP_RECORDS) ? 1 : 0;  // factors for a record-based re-solve
-  p.reduced = false;
-  p.tree = false;
-  p.rowbcast = false;
-  p.compact = false;
-  if constexpr (!STRICT && !KEEP && ndlqr::P1OnMatrixCores<NX, NU>::value) {
+  // the record-based re-solve needs every separator's record and factor: KEEP writes them all,
+  // KEEP_RECORDS adds the factors to the lean schedule
+  p.rec_complete = !strict && (keep || (p.lean && p.store_l));
+  p.level0 = p.ltop = p.top_l0 = d.K;
+  p.schedule = p.lean ? "knot-lean" : (strict ? "knot-strict" : "knot-keep");
+  if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value) {
     if (p.lean && s.red) {
       p.reduced = true;
       // tree schedule for small batches (at most half a resident round of bottom wavefronts): three
@@ -80,9 +97,10 @@ static SmallPlan plan_small(const NdlqrHipCtx* c) {
       // same schedule, which then also keeps the factors of the separators of level >= 1 in the slack of the level-0
       // record slots (store_l = 2; the record-based re-solve rb_forward / rb_forward_top works on that: four sweep
       // arrays in the LDS of its one workgroup per problem)
-      p.compact = !p.tree && d.N >= 16 && 8 * (2 * NX + NU) <= 256 &&
-                  sizeof(double) * (size_t)(d.N >> 3) * NX * (p.store_l ? 4 : 1) <= 160 * 1024;
+      p.top_lds = sizeof(double) * (size_t)(d.N >> 3) * NX;
+      p.compact = !p.tree && d.N >= 16 && kRbBacksubFits<NX, NU> && p.top_lds * (p.store_l ? 4 : 1) <= kLdsMax;
       if (p.compact && p.store_l) p.store_l = 2;
+      p.rec_compact = p.compact && p.store_l == 2;
       // row-broadcast bottom kernel (one DPP row holds the rows of S-bar and of [A | B]'): its cost falls
       // with the block size, the matrix-core kernel's does not (16x16 tiles whatever n is). Measured bottom
       // kernel, N = 256 x 1024: (6,3) 0.105 vs 0.170 ms, (8,4) 0.144 vs 0.190, (9,3) 0.202 vs 0.244,
@@ -90,6 +108,26 @@ static SmallPlan plan_small(const NdlqrHipCtx* c) {
       // (10,4) 0.230 vs 0.207, (9,3) 0.203 vs 0.187, (8,4) 0.143 vs 0.152, (6,3) 0.104 vs 0.134 -- so it serves n <= 8
       // (NDLQR_ROWBCAST=0/1 overrides)
       p.rowbcast = p.compact && !p.store_l && NX <= 16 && NX + NU <= 16 && (c->rowbcast == 1 || (c->rowbcast < 0 && NX <= 8));
+      // Levels 0-2 in one launch (bottom8_reduced_mc: two wavefronts per eight knots, the level-2 slot in LDS): 12 % less
+      // HBM traffic and one launch less per step; the level-2 work costs inside the bottom launch about what it costs
+      // outside, so the step gains little -- and only at the (12,4) instance, where it is the default (same box,
+      // profiles/r04_fuse2_ab.txt: (12,4,256) x 1024 0.587 -> 0.579 ms, (12,4,1024) x 512 1.20 -> 1.16, the padded (11,3)
+      // 0.578 -> 0.569; (12,8) +2.5 %, (13,4) +0.9 %, (9,3) / (10,4) / (15,2) +-0). NDLQR_FUSE2=0 / 1 overrides.
+      p.fuse2 = !p.rowbcast && p.compact && !p.store_l && (c->fuse2 > 0 || (c->fuse2 < 0 && NX == 12 && NU == 4));
+      p.schedule = p.tree ? "reduced-tree"
+                   : !p.compact ? "reduced-records"
+                   : p.store_l ? "reduced-compact-records" : (p.fuse2 ? "reduced-fused2" : "reduced");
+      if (!p.tree) {
+        // upper levels: one launch per level while a level has more than four separators per problem, then the
+        // last three levels in one launch (reduced_top_mc; NDLQR_NO_TOP=1: a launch per level to the root)
+        const int top_levels = d.K - c->top_levels >= 3 ? c->top_levels : 3;
+        p.level0 = p.fuse2 ? 3 : 2;
+        p.ltop = (d.K >= 5 && !c->no_top) ? d.K - top_levels : d.K;
+        p.top_l0 = (p.fuse2 && p.ltop < 3) ? 3 : p.ltop;  // (level 2 went with the bottom launch)
+        // ... which also runs the top-down sweep over the records of level >= 3 when the back-substitution is the
+        // two-launch form and its array fits the workgroup's LDS
+        p.top_sweeps = p.ltop < d.K && p.compact && p.top_lds <= 4 * sizeof(ndlqr::ReducedLds<NX, NU, false>);
+      }
     }
   }
   // the separator-only schedule touches F only to park the factors of KEEP_RECORDS under its full-record forms
@@ -98,85 +136,49 @@ static SmallPlan plan_small(const NdlqrHipCtx* c) {
 }
 
 template <int NX, int NU, bool STRICT, bool KEEP>
-static int launch_small(NdlqrHipCtx* c) {
+static int launch_small(NdlqrHipCtx* c, const SmallPlan& plan) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   using Sh = ndlqr::SchurShape<NX, NU>;
   constexpr int JB = kBottomLevels;
-  const SmallPlan plan = plan_small<NX, NU, STRICT, KEEP>(c);
   const bool lean = plan.lean;
   const int store_l = plan.store_l;
-  // the record-based re-solve needs every separator's record and factor: KEEP writes them all,
-  // KEEP_RECORDS adds the factors to the lean schedule
-  c->kept.rec_complete = !STRICT && (KEEP || (lean && store_l));
   if constexpr (!STRICT && !KEEP && ndlqr::P1OnMatrixCores<NX, NU>::value) {
     if (plan.reduced) {
-      const bool tree = plan.tree;
-      // compact level-0 records + the two-launch back-substitution (kernels_rowbcast.hpp), unless the
-      // records have to serve a record-based re-solve (KEEP_RECORDS) or the tree schedule runs
-      const bool compact = plan.compact;
-      c->kept.schedule = tree ? "reduced-tree" : (compact ? (store_l ? "reduced-compact-records" : "reduced") : "reduced-records");
-      c->kept.rec_compact = compact && store_l == 2;
-      bool fuse2 = false;
       {
         ScopedSlot t(c, SLOT_BOTTOM);
-        bool launched = false;
-        if constexpr (NX <= 16 && NX + NU <= 16) {
-          if (plan.rowbcast) {  // one separator per DPP row, four per wavefront
+        if (plan.rowbcast) {  // one separator per DPP row, four per wavefront
+          if constexpr (NX <= 16 && NX + NU <= 16)
             hipLaunchKernelGGL((ndlqr::rb_bottom<NX, NU>), dim3(d.N >> 4, d.batch), dim3(64), 0, s.stream, d, c->AB,
                                c->QR, s.rhs, s.red, s.rec, c->info);
-            launched = true;
-          }
-        }
-        // Levels 0-2 in one launch (bottom8_reduced_mc: two wavefronts per eight knots, the level-2 slot in LDS): 12 % less
-        // HBM traffic and one launch less per step; the level-2 work costs inside the bottom launch about what it costs
-        // outside, so the step gains little -- and only at the (12,4) instance, where it is the default (same box,
-        // profiles/r04_fuse2_ab.txt: (12,4,256) x 1024 0.587 -> 0.579 ms, (12,4,1024) x 512 1.20 -> 1.16, the padded (11,3)
-        // 0.578 -> 0.569; (12,8) +2.5 %, (13,4) +0.9 %, (9,3) / (10,4) / (15,2) +-0). NDLQR_FUSE2=0 / 1 overrides.
-        fuse2 = !launched && !tree && compact && !store_l && d.N >= 16 &&
-                (c->fuse2 > 0 || (c->fuse2 < 0 && NX == 12 && NU == 4));
-        if (fuse2) c->kept.schedule = "reduced-fused2";
-        if (launched) {
-        } else if (fuse2) {
+        } else if (plan.fuse2) {
           hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream, d,
                              c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
-        } else if (tree)
+        } else if (plan.tree)
           hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
                              d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, s.tree_cnt, 0);
-        else if (compact)
+        else if (plan.compact)
           hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
                              d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, nullptr, 1);
         else
           hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
                              d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, nullptr, 0);
       }
-      // upper levels: one launch per level while a level has more than four separators per problem, then the
-      // last three levels in one launch (reduced_top_mc; NDLQR_NO_TOP=1: a launch per level to the root)
-      const int top_levels = d.K - c->top_levels >= 3 ? c->top_levels : 3;
-      const int ltop = (d.K >= 5 && !c->no_top) ? d.K - top_levels : d.K;
-      for (int l = fuse2 ? 3 : 2; l < ltop && !tree; ++l) {
+      for (int l = plan.level0; l < plan.ltop; ++l) {
         ScopedSlot t(c, SLOT_UPPER);
         hipLaunchKernelGGL((ndlqr::reduced_level_mc<NX, NU>), dim3(d.N >> (l + 1), d.batch), dim3(64), 0, s.stream,
                            d, l, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l);
       }
-      // ... which also runs the top-down sweep over the records of level >= 3 when the back-substitution is the
-      // two-launch form and its array fits the workgroup's LDS
-      const bool top_sweeps = !tree && ltop < d.K && compact &&
-                              sizeof(double) * (size_t)(d.N >> 3) * NX <= 4 * sizeof(ndlqr::ReducedLds<NX, NU, false>);
-      if (!tree && ltop < d.K) {
+      if (plan.ltop < d.K) {
         ScopedSlot t(c, SLOT_TOP);  // (a profile slot of its own: one kernel name per slot, like rocprofv3's per-kernel averages)
-        const int l0 = (fuse2 && ltop < 3) ? 3 : ltop;  // (level 2 went with the bottom launch)
-        hipLaunchKernelGGL((ndlqr::reduced_top_mc<NX, NU>), dim3(d.batch), dim3(256), 0, s.stream, d, l0, c->AB,
-                           c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, top_sweeps ? s.ytop : (double*)nullptr);
+        hipLaunchKernelGGL((ndlqr::reduced_top_mc<NX, NU>), dim3(d.batch), dim3(256), 0, s.stream, d, plan.top_l0, c->AB,
+                           c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, plan.top_sweeps ? s.ytop : (double*)nullptr);
       }
       ScopedSlot t(c, SLOT_APPLY);
-      if (compact) {
-        if (!top_sweeps) {
-          const size_t top_lds = sizeof(double) * (size_t)(d.N >> 3) * NX;
-          if (top_lds > 64 * 1024)  // (beyond the default limit of dynamic LDS: horizons of 8192 knots at 12 states)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ndlqr::rb_backsub_top<NX>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)top_lds);
-          hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), top_lds, s.stream, d, s.rec, s.ytop);
+      if (plan.compact) {
+        if (!plan.top_sweeps) {  // (beyond the default limit of dynamic LDS: horizons of 8192 knots at 12 states)
+          (void)allow_dynamic_lds(&ndlqr::rb_backsub_top<NX>, plan.top_lds);
+          hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), plan.top_lds, s.stream, d, s.rec, s.ytop);
         }
         // (an MPC step that asked for nothing but a knot range -- NDLQR_SOLN_ONLY -- runs the workgroups of that range)
         launch_rb_backsub<NX, NU, false>(c, dim3(apply_grid(c, d), d.batch), s.stream,
@@ -188,7 +190,6 @@ static int launch_small(NdlqrHipCtx* c) {
       return NDLQR_OK;
     }
   }
-  c->kept.schedule = lean ? "knot-lean" : (STRICT ? "knot-strict" : "knot-keep");
   {
     ScopedSlot t(c, SLOT_BOTTOM);
     hipLaunchKernelGGL((ndlqr::bottom_small<NX, NU, STRICT, KEEP, JB>), dim3(d.N >> JB, d.batch), dim3(32 << JB), 0,
@@ -219,7 +220,7 @@ template <int NX, int NU>
 static void launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
-  if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value && 8 * (2 * NX + NU) <= 256) {
+  if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value && kRbBacksubFits<NX, NU>) {
     if (c->kept.rec_compact) {
       // the compact records of the default schedule (round 4): forward pass over the separators with the right-hand-side
       // column alone, then the back-substitution of a full solve. s.red (the accumulator slots, idle here) holds what
@@ -232,9 +233,7 @@ static void launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
       {
         ScopedSlot t(c, SLOT_UPPER);
         const size_t lds = sizeof(double) * 4 * (size_t)(d.N >> 3) * NX;
-        if (lds > 64 * 1024)
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ndlqr::rb_forward_top<NX, NU>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)allow_dynamic_lds(&ndlqr::rb_forward_top<NX, NU>, lds);
         hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU>), dim3(d.batch), dim3(256), lds, s.stream, d, c->AB, c->QR,
                            rhs, s.rec, (const double*)s.red, s.ytop);
       }
@@ -269,14 +268,12 @@ static void launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
 template <int NX, int NU>
 static bool launch_multi_rhs(NdlqrHipCtx* c, const int count, const double* rhs, double* zsep, double* fsum, double* ytop,
                              double* z) {
-  if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value && 8 * (2 * NX + NU) <= 256) {
+  if constexpr (ndlqr::P1OnMatrixCores<NX, NU>::value && kRbBacksubFits<NX, NU>) {
     const ndlqr::Dims& d = c->d;
     BufferSet& s = c->set[c->cur];
     const size_t lds = sizeof(double) * 4 * (size_t)(d.N >> 3) * NX;
-    if (lds > 160 * 1024) return false;
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ndlqr::rb_forward_top<NX, NU, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > kLdsMax) return false;
+    (void)allow_dynamic_lds(&ndlqr::rb_forward_top<NX, NU, true>, lds);
     hipLaunchKernelGGL((ndlqr::rb_forward<NX, NU, true>), dim3(d.N / 8, count), dim3(256), 0, s.stream, d, c->AB, c->QR, rhs,
                        s.rec, fsum, d.batch, zsep);
     hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU, true>), dim3(count), dim3(256), lds, s.stream, d, c->AB, c->QR, rhs,
@@ -311,12 +308,10 @@ static int launch_time_shard(NdlqrHipCtx* c, const int phase, const int g, const
     return NDLQR_ERR_INVALID;
   } else {
     const int ltop = d.K - lg;  // levels [0, ltop) lie inside a chunk
-    if (!bs.red || !bs.ytop || ltop < 4 || 8 * (2 * NX + NU) > 256 || (c->flags & ~NDLQR_FLAG_PROFILE)) return NDLQR_ERR_INVALID;
+    if (!bs.red || !bs.ytop || ltop < 4 || !kRbBacksubFits<NX, NU> || (c->flags & ~NDLQR_FLAG_PROFILE)) return NDLQR_ERR_INVALID;
     const size_t top_lds = sizeof(double) * (size_t)(d.N >> 3) * NX;
-    if (top_lds > 160 * 1024) return NDLQR_ERR_INVALID;  // (rb_backsub_top's sweep array has to fit one workgroup's LDS)
-    if (top_lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ndlqr::rb_backsub_top<NX>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)top_lds);
+    if (top_lds > kLdsMax) return NDLQR_ERR_INVALID;  // (rb_backsub_top's sweep array has to fit one workgroup's LDS)
+    (void)allow_dynamic_lds(&ndlqr::rb_backsub_top<NX>, top_lds);
     constexpr size_t SLOT = ndlqr::RedSlot<NX>::SIZE;
     if (phase == 0) {
       // whatever an earlier exchange left in the top slots goes: this rank's chunk writes its halves afresh
@@ -358,6 +353,39 @@ static int launch_time_shard(NdlqrHipCtx* c, const int phase, const int g, const
                          bs.rhs, bs.rec, bs.ytop, bs.z);
     }
     c->kept.schedule = "reduced-time-shard";
+    c->kept.family = Family::Small;
+    c->kept.time_shard = true;
     return NDLQR_OK;
   }
 }
+
+// The entry points of one size-specialised instance, as ndlqr_hip.hip dispatches to them: one object per line of
+// small_instances.def, exported by that line's translation unit (small_instance.hip)
+struct SmallInstance {
+  int nx, nu;
+  int kpb;   // knots per workgroup of its Schur kernels
+  int slot;  // doubles per accumulator slot
+  SmallPlan (*plan)(const NdlqrHipCtx*, bool strict, bool keep);  // what `solve` would do (plan_small)
+  int (*solve)(NdlqrHipCtx*, const SmallPlan&);                   // factor + solve launch sequence (launch_small)
+  void (*rhs)(NdlqrHipCtx*, const double* rhs, double* z);        // record-based re-solve of `rhs` into `z` (launch_rhs_records)
+  int (*tshard)(NdlqrHipCtx*, int phase, int g, int G);           // time-axis sharding: chunk g of G, phase 0 / 1 (launch_time_shard)
+  // several right-hand sides per problem (launch_multi_rhs)
+  bool (*multi)(NdlqrHipCtx*, int count, const double* rhs, double* zsep, double* fsum, double* ytop, double* z);
+};
+
+template <int NX, int NU>
+static int solve_small(NdlqrHipCtx* c, const SmallPlan& p) {
+  if (p.strict) return p.keep ? launch_small<NX, NU, true, true>(c, p) : launch_small<NX, NU, true, false>(c, p);
+  return p.keep ? launch_small<NX, NU, false, true>(c, p) : launch_small<NX, NU, false, false>(c, p);
+}
+
+// (not constexpr: a constant-initialised const object would be emitted for the device as well, where these host
+//  functions do not exist)
+template <int NX, int NU>
+static SmallInstance make_small_instance() {
+  return {NX, NU, ndlqr::SchurShape<NX, NU>::KPB, (int)ndlqr::RedSlot<NX>::SIZE, plan_small<NX, NU>, solve_small<NX, NU>,
+          launch_rhs_records<NX, NU>, launch_time_shard<NX, NU>, launch_multi_rhs<NX, NU>};
+}
+// the name of the instance's object
+#define NDLQR_SMALL_NAME_(NX_, NU_) ndlqr_small_##NX_##_##NU_
+#define NDLQR_SMALL_NAME(NX_, NU_) NDLQR_SMALL_NAME_(NX_, NU_)

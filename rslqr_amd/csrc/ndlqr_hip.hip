@@ -17,9 +17,7 @@
 #include "kernels_grad.hpp"
 #include "kernels_mfma.hpp"
 #include "kernels_reduced_mfma.hpp"
-#ifdef NDLQR_SINGLE_TU  // developer builds (tools/segtime.py): every instance in this translation unit
-#include "launch_small.hpp"
-#endif
+#include "launch_small.hpp"  // (SmallInstance; its templates are instantiated in small_instance.hip)
 
 // ------------------------------------------------------------------------------ errors
 
@@ -158,6 +156,8 @@ NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int bat
   if (getenv("NDLQR_TOP_LEVELS")) c->top_levels = atoi(getenv("NDLQR_TOP_LEVELS"));
   if (c->top_levels < 3 || c->top_levels > 5) c->top_levels = 3;
   if (getenv("NDLQR_SEP_THREADS")) c->sep_threads = atoi(getenv("NDLQR_SEP_THREADS"));
+  if (getenv("NDLQR_MULT_THREADS")) c->mult_threads = atoi(getenv("NDLQR_MULT_THREADS"));
+  c->no_reduced_generic = getenv("NDLQR_DEV_NO_REDUCED_GENERIC") != nullptr;
   BufferSet& s = c->set[0];
   bool ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_inputs, hipEventDisableTiming) == hipSuccess &&
@@ -466,7 +466,7 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
   if (c->d.N % 8 == 0 && c->du.n <= 16)
     hipLaunchKernelGGL(ndlqr::pack_flat_generic<8>, dim3(c->d.N / 8, c->d.batch), dim3(128), 0, s.stream, c->du, c->d, A, B, Q,
                        R, q, r, d, x0, c->AB, c->QR, s.rhs);
-  else if (c->du.n > 16 && sizeof(double) * (size_t)(c->du.n | 1) * c->du.w <= 64 * 1024)  // through LDS, whole lines in and out
+  else if (c->du.n > 16 && sizeof(double) * (size_t)(c->du.n | 1) * c->du.w <= kLdsDefaultDynamic)  // through LDS, whole lines in and out
     hipLaunchKernelGGL(ndlqr::pack_flat_tiled, dim3(c->d.N, c->d.batch), dim3(256), sizeof(double) * (size_t)(c->du.n | 1) * c->du.w,
                        s.stream, c->du, c->d, A, B, Q, R, q, r, d, x0, c->AB, c->QR, s.rhs);
   else
@@ -511,8 +511,7 @@ static ReducedGenericPlan plan_reduced_generic(const NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
   ReducedGenericPlan p = {false, 0, 0, 0, false, false};
   if (c->flags & (NDLQR_FLAG_STRICT_FP | NDLQR_FLAG_KEEP_FACT)) return p;
-  if (c->no_mfma || d.n > 128 || d.N < 2) return p;
-  if (getenv("NDLQR_DEV_NO_REDUCED_GENERIC")) return p;  // (developer: A/B against the knot-based runtime-sized schedule)
+  if (c->no_mfma || c->no_reduced_generic || d.n > 128 || d.N < 2) return p;
   p.keep = (c->flags & NDLQR_FLAG_KEEP_RECORDS) != 0;  // W of every separator kept for rhs-only re-solves
   p.nb = (d.n + 15) / 16;
   const int npad = 16 * p.nb, wpad = (d.w + 3) / 4 * 4;
@@ -525,7 +524,7 @@ static ReducedGenericPlan plan_reduced_generic(const NdlqrHipCtx* c) {
   if (wpad > p.threads) return p;  // one weight / rhs entry per thread
   if (p.nb >= 5 && p.threads != 64 * p.nb) return p;  // (beyond 64 states the second panel array does not fit the LDS)
   p.lds = sizeof(double) * (size_t)ndlqr::reduced_lds_doubles(npad, wpad, p.threads == 64 * p.nb);
-  if (p.lds > 160 * 1024) return p;
+  if (p.lds > kLdsMax) return p;
   p.ok = true;
   return p;
 }
@@ -573,7 +572,7 @@ static void launch_backsub_reduced_generic(NdlqrHipCtx* c, const double* rhs, do
   // (rows of CA | CB eight per wavefront. Four wavefronts per separator leave a CU a quarter full at small blocks: one up to
   //  32 states, two up to 64, four beyond -- profiles/r04_mult_threads_ab.txt: (16,4,256) x 1024 2.30 -> 1.86 ms per solve,
   //  (20,20) 1.32 -> 1.23, (48,16,512) 6.44 -> 6.27, (96,16) best at four; NDLQR_MULT_THREADS overrides)
-  static const int thr_env = getenv("NDLQR_MULT_THREADS") ? atoi(getenv("NDLQR_MULT_THREADS")) : 0;
+  const int thr_env = c->mult_threads;
   const int thr_m = (thr_env == 64 || thr_env == 128 || thr_env == 256) ? thr_env : (d.n <= 32 ? 64 : (d.n <= 64 ? 128 : 256));
   // A step that wants knots [k0, k1] alone (NDLQR_SOLN_ONLY: apply_blk0 / apply_nblk in units of eight knots): of every
   // level the separators whose subtree meets [k0 - 1, k1 + 2] -- a set closed under "needs the multipliers of the
@@ -600,8 +599,6 @@ static void launch_backsub_reduced_generic(NdlqrHipCtx* c, const double* rhs, do
 static int launch_reduced_generic(NdlqrHipCtx* c, const ReducedGenericPlan& p) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
-  c->kept.schedule = p.keep ? "generic-reduced-records" : "generic-reduced";
-  c->kept.rec_complete = p.keep;  // records, slots and W of every separator stay: rhs-only re-solves (launch_rhs_reduced_generic)
   for (int l = 0; l < d.K; ++l) {
     ScopedSlot t(c, SLOT_SEP);
     const dim3 grid(d.N >> (l + 1), d.batch);
@@ -677,10 +674,14 @@ struct GenericSepPlan {
   bool scratch;
   size_t lds;
   int threads;
+  int schur_nb;  // the Schur update beside it: schur_mfma<schur_nb> (1 .. 4), schur_mfma_rt (0) or schur_generic (-1)
 };
 static GenericSepPlan plan_generic_sep(const NdlqrHipCtx* c, const bool strict) {
   const ndlqr::Dims& d = c->d;
   GenericSepPlan p;
+  // block sizes that fill 16x16 MFMA tiles: Schur update on the fp64 matrix cores (fast mode; beyond 64 states the
+  // runtime-sized form)
+  p.schur_nb = (strict || d.n % 16 != 0 || c->no_mfma) ? -1 : (d.n > 64 ? 0 : (d.rows % 16 == 0 ? d.n / 16 : -1));
   p.mfma = !strict && d.n % 16 == 0 && d.w % 4 == 0 && !c->no_mfma;
   p.scratch = false;
   const int ctl = 2 * (d.n / 16) + 1, ctc = ctl < kSepChunkTiles ? ctl : kSepChunkTiles;
@@ -697,22 +698,45 @@ static GenericSepPlan plan_generic_sep(const NdlqrHipCtx* c, const bool strict) 
   if (p.mfma) {
     // (beyond 112 states S-bar / L goes to global memory: the panel chunk and the inverses of the diagonal blocks stay)
     const size_t lds_no_s = lds_mfma - sizeof(double) * (size_t)d.n * (d.n + 1);
-    if (lds_mfma <= 160 * 1024) { p.lds = lds_mfma; return p; }
-    if (lds_no_s <= 160 * 1024) { p.lds = lds_no_s; p.scratch = true; return p; }
+    if (lds_mfma <= kLdsMax) { p.lds = lds_mfma; return p; }
+    if (lds_no_s <= kLdsMax) { p.lds = lds_no_s; p.scratch = true; return p; }
     p.mfma = false;
   }
-  p.scratch = lds_generic > 160 * 1024;
+  p.scratch = lds_generic > kLdsMax;
   p.lds = p.scratch ? 0 : lds_generic;
   p.threads = p.scratch ? 1024 : 256;
   return p;
 }
 
+// Everything a solve decides before it launches, by plan_solve (below) from the block sizes, the flags, the NDLQR_*
+// switches read at creation and the optional buffers of the primary set: which launch sequence runs, what that needs
+// allocated (prepare_solve) and what it leaves behind (launch_solve). The launch functions get it and only issue launches.
+struct SolvePlan {
+  Family family;
+  const SmallInstance* inst;  // Family::Small
+  SmallPlan small;            // ... and what its launch_small does
+  ReducedGenericPlan red;     // Family::GenericReduced (red.ok)
+  GenericSepPlan sep;         // Family::GenericKnot: its separator and Schur kernels
+  bool strict, keep;          // NDLQR_FLAG_STRICT_FP, NDLQR_FLAG_KEEP_FACT
+  bool lean;                  // Family::GenericKnot, fast mode without KEEP: the Schur passes only keep the boundary knots of
+                              // every subtree up to date, the solution comes from the back-substitution over the records
+  bool rec_as_factors;        // NDLQR_FLAG_KEEP_RECORDS where no schedule keeps records (Family::GenericKnot: blocks beyond 128
+                              // states, inputs wider than a workgroup): the factor array is kept instead, the re-solve is the
+                              // factor-based sweep
+  // what has to exist before the launches (and any capture of them)
+  bool needs_F;               // the factor array (ndlqr_hip_ensure_F)
+  size_t sep_scratch_bytes;   // NdlqrHipCtx::sep_scratch (0: not used)
+  bool needs_red_generic;     // the runtime-sized slots (ensure_red_generic)
+  bool may_pipeline;          // nothing but records and the solution stay: may alternate between the two buffer sets
+  KeptState kept;             // what the solve leaves (fact_valid: a complete factor array)
+};
+
 template <bool STRICT>
-static int launch_generic(NdlqrHipCtx* c, bool lean) {
+static int launch_generic(NdlqrHipCtx* c, const SolvePlan& plan) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
+  const bool lean = plan.lean;
   double* rec = lean ? s.rec : nullptr;
-  c->kept.schedule = lean ? "generic-lean" : (STRICT ? "generic-strict" : "generic-keep");
   {
     ScopedSlot t(c, SLOT_LEAF);
     hipLaunchKernelGGL((ndlqr::leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(128), 0, s.stream, d,
@@ -720,18 +744,11 @@ static int launch_generic(NdlqrHipCtx* c, bool lean) {
   }
   // S (n x (n+1)) + right-hand-side panel (n x (2n+1)); on the matrix-core path the panel goes through
   // LDS in chunks of kSepChunkTiles column tiles (+ the inverses of the 16x16 diagonal blocks, pitch 17)
-  const GenericSepPlan sp = plan_generic_sep(c, STRICT);
+  const GenericSepPlan& sp = plan.sep;
   const bool p1mfma = sp.mfma;
   const size_t lds = sp.lds;
   const int sep_threads = sp.threads;
-  double* sep_scratch = nullptr;
-  if (sp.scratch) {
-    sep_scratch = c->sep_scratch;
-    if (!sep_scratch) {
-      g_last_error = "nstates too large for the separator kernel's LDS staging and no global scratch";
-      return NDLQR_ERR_INVALID;
-    }
-  }
+  double* sep_scratch = sp.scratch ? c->sep_scratch : nullptr;  // (allocated by prepare_solve)
   for (int l = 0; l < d.K; ++l) {
     const int nsub = d.N >> (l + 1);
     {
@@ -749,22 +766,20 @@ static int launch_generic(NdlqrHipCtx* c, bool lean) {
       ScopedSlot t(c, lean ? SLOT_BOUNDARY : SLOT_SCHUR);
       const int bnd = lean ? 1 : 0;
       const unsigned gx = lean ? 2u * (unsigned)nsub : (unsigned)d.N;  // knots this pass updates
-      // block sizes that fill 16x16 MFMA tiles: Schur update on the fp64 matrix cores (fast mode)
-      const bool mfma = !STRICT && d.n % 16 == 0 && d.rows % 16 == 0 && d.n <= 64 && !c->no_mfma;
       const size_t flds = sizeof(double) * (size_t)d.n * (d.n + 16);
-      if (mfma && d.n == 64)
+      if (sp.schur_nb == 4)
         hipLaunchKernelGGL((ndlqr::schur_mfma<4>), dim3(gx, d.batch), dim3(256), flds, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
-      else if (mfma && d.n == 48)
+      else if (sp.schur_nb == 3)
         hipLaunchKernelGGL((ndlqr::schur_mfma<3>), dim3(gx, d.batch), dim3(256), flds, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
-      else if (mfma && d.n == 32)
+      else if (sp.schur_nb == 2)
         hipLaunchKernelGGL((ndlqr::schur_mfma<2>), dim3(gx, d.batch), dim3(256), flds, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
-      else if (mfma && d.n == 16)
+      else if (sp.schur_nb == 1)
         hipLaunchKernelGGL((ndlqr::schur_mfma<1>), dim3(gx, d.batch), dim3(256), flds, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
-      else if (!STRICT && d.n % 16 == 0 && d.n > 64 && !c->no_mfma)  // (runtime-sized matrix-core form: blocks beyond 64 states)
+      else if (sp.schur_nb == 0)  // (runtime-sized matrix-core form: blocks beyond 64 states)
         hipLaunchKernelGGL(ndlqr::schur_mfma_rt, dim3(gx, d.batch), dim3(256), 0, s.stream, d, l, c->F, s.z, bnd,
                            (const double*)rec);
       else {
@@ -788,59 +803,24 @@ static int launch_generic(NdlqrHipCtx* c, bool lean) {
 }
 
 // ---- size-specialised instances: one translation unit each (small_instance.hip), listed in
-//      small_instances.def
-#define NDLQR_SMALL_INSTANCE(NX_, NU_)                                              \
-  int ndlqr_small_solve_##NX_##_##NU_(NdlqrHipCtx* c, bool strict, bool keep);       \
-  int ndlqr_small_needs_F_##NX_##_##NU_(const NdlqrHipCtx* c, bool strict, bool keep); \
-  void ndlqr_small_rhs_##NX_##_##NU_(NdlqrHipCtx* c, const double* rhs, double* z);                               \
-  int ndlqr_small_kpb_##NX_##_##NU_(void);                                          \
-  int ndlqr_small_tshard_##NX_##_##NU_(NdlqrHipCtx* c, int phase, int g, int G);      \
-  int ndlqr_small_slot_##NX_##_##NU_(void);                                          \
-  int ndlqr_small_multi_##NX_##_##NU_(NdlqrHipCtx* c, int count, const double* rhs, double* zsep, double* fsum, double* ytop, double* z);
-#include "small_instances.def"
-#undef NDLQR_SMALL_INSTANCE
-
-struct SmallInstance {
-  int nx, nu;
-  int (*solve)(NdlqrHipCtx*, bool, bool);
-  int (*needs_F)(const NdlqrHipCtx*, bool, bool);
-  void (*rhs)(NdlqrHipCtx*, const double*, double*);
-  int (*kpb)(void);
-  int (*tshard)(NdlqrHipCtx*, int, int, int);
-  int (*slot)(void);
-  int (*multi)(NdlqrHipCtx*, int, const double*, double*, double*, double*, double*);
-};
+//      small_instances.def; developer builds with NDLQR_SINGLE_TU (tools/segtime.py) hold every instance here
 #ifdef NDLQR_SINGLE_TU
-#define NDLQR_SMALL_INSTANCE(NX_, NU_)                                                              \
-  int ndlqr_small_solve_##NX_##_##NU_(NdlqrHipCtx* c, bool strict, bool keep) {                     \
-    if (strict) return keep ? launch_small<NX_, NU_, true, true>(c) : launch_small<NX_, NU_, true, false>(c); \
-    return keep ? launch_small<NX_, NU_, false, true>(c) : launch_small<NX_, NU_, false, false>(c);           \
-  }                                                                                                 \
-  int ndlqr_small_needs_F_##NX_##_##NU_(const NdlqrHipCtx* c, bool strict, bool keep) {             \
-    if (strict) return keep ? plan_small<NX_, NU_, true, true>(c).needs_F : plan_small<NX_, NU_, true, false>(c).needs_F; \
-    return keep ? plan_small<NX_, NU_, false, true>(c).needs_F : plan_small<NX_, NU_, false, false>(c).needs_F;           \
-  }                                                                                                 \
-  void ndlqr_small_rhs_##NX_##_##NU_(NdlqrHipCtx* c, const double* rhs, double* z) { launch_rhs_records<NX_, NU_>(c, rhs, z); } \
-  int ndlqr_small_kpb_##NX_##_##NU_(void) { return ndlqr::SchurShape<NX_, NU_>::KPB; }              \
-  int ndlqr_small_tshard_##NX_##_##NU_(NdlqrHipCtx* c, int phase, int g, int G) { return launch_time_shard<NX_, NU_>(c, phase, g, G); } \
-  int ndlqr_small_slot_##NX_##_##NU_(void) { return (int)ndlqr::RedSlot<NX_>::SIZE; }              \
-  int ndlqr_small_multi_##NX_##_##NU_(NdlqrHipCtx* c, int count, const double* rhs, double* zsep, double* fsum, double* ytop, double* z) { return launch_multi_rhs<NX_, NU_>(c, count, rhs, zsep, fsum, ytop, z) ? 1 : 0; }
+#define NDLQR_SMALL_INSTANCE(NX_, NU_) static const SmallInstance NDLQR_SMALL_NAME(NX_, NU_) = make_small_instance<NX_, NU_>();
+#else
+#define NDLQR_SMALL_INSTANCE(NX_, NU_) extern const SmallInstance NDLQR_SMALL_NAME(NX_, NU_);
+#endif
 #include "small_instances.def"
 #undef NDLQR_SMALL_INSTANCE
-#endif
 
-static const SmallInstance kSmallInstances[] = {
-#define NDLQR_SMALL_INSTANCE(NX_, NU_) \
-  {NX_, NU_, ndlqr_small_solve_##NX_##_##NU_, ndlqr_small_needs_F_##NX_##_##NU_, ndlqr_small_rhs_##NX_##_##NU_, \
-   ndlqr_small_kpb_##NX_##_##NU_, ndlqr_small_tshard_##NX_##_##NU_, ndlqr_small_slot_##NX_##_##NU_,            \
-   ndlqr_small_multi_##NX_##_##NU_},
+static const SmallInstance* const kSmallInstances[] = {
+#define NDLQR_SMALL_INSTANCE(NX_, NU_) &NDLQR_SMALL_NAME(NX_, NU_),
 #include "small_instances.def"
 #undef NDLQR_SMALL_INSTANCE
 };
 
 static bool has_small_instance(int nstates, int ninputs) {
-  for (const SmallInstance& s : kSmallInstances)
-    if (s.nx == nstates && s.nu == ninputs) return true;
+  for (const SmallInstance* s : kSmallInstances)
+    if (s->nx == nstates && s->nu == ninputs) return true;
   return false;
 }
 
@@ -848,16 +828,16 @@ static bool has_small_instance(int nstates, int ninputs) {
 // when there is none
 static void pick_pad_instance(int nstates, int ninputs, int* pn, int* pm) {
   long best = -1;
-  for (const SmallInstance& si : kSmallInstances) {
-    if (si.nx < nstates || si.nu < ninputs || si.nx < 6) continue;
-    const long cost = (long)si.nx * si.nx * (si.nx + si.nu);
-    if (best < 0 || cost < best) { best = cost; *pn = si.nx; *pm = si.nu; }
+  for (const SmallInstance* si : kSmallInstances) {
+    if (si->nx < nstates || si->nu < ninputs || si->nx < 6) continue;
+    const long cost = (long)si->nx * si->nx * (si->nx + si->nu);
+    if (best < 0 || cost < best) { best = cost; *pn = si->nx; *pm = si->nu; }
   }
 }
 
 static const SmallInstance* find_small(const ndlqr::Dims& d) {
-  for (const SmallInstance& s : kSmallInstances)
-    if (s.nx == d.n && s.nu == d.m) return &s;
+  for (const SmallInstance* s : kSmallInstances)
+    if (s->nx == d.n && s->nu == d.m) return s;
   return nullptr;
 }
 
@@ -868,78 +848,85 @@ static const SmallInstance* pick_small(const NdlqrHipCtx* c) {
   const SmallInstance* inst = find_small(d);
   // the fused kernels own eight knots per workgroup and two tree levels: shorter horizons run the
   // runtime-sized kernels
-  if (!inst || d.N < inst->kpb() || d.K < 3) return nullptr;
+  if (!inst || d.N < inst->kpb || d.K < 3) return nullptr;
   return inst;
 }
 
-// returns true when (n, m, N) has a size-specialised instance and it was launched
-static bool try_launch_small(NdlqrHipCtx* c, bool strict, int* err) {
-  const SmallInstance* inst = pick_small(c);
-  if (!inst) return false;
-  *err = inst->solve(c, strict, (c->flags & NDLQR_FLAG_KEEP_FACT) != 0);
-  return true;
+// the instance whose records the last factorisation left (nullptr: none, or another family's)
+static const SmallInstance* kept_instance(const NdlqrHipCtx* c) {
+  return c->kept.family == Family::Small ? find_small(c->d) : nullptr;
 }
 
-// does the launch sequence enqueue_solve is about to issue touch the factor array?
-static bool solve_needs_F(const NdlqrHipCtx* c) {
-  const SmallInstance* inst = pick_small(c);
-  if (!inst) return !plan_reduced_generic(c).ok;  // the other runtime-sized kernels work on F
-  return inst->needs_F(c, (c->flags & NDLQR_FLAG_STRICT_FP) != 0, (c->flags & NDLQR_FLAG_KEEP_FACT) != 0) != 0;
-}
-
-// NDLQR_FLAG_KEEP_RECORDS where no schedule keeps records -- the knot-based runtime-sized path: blocks beyond 128 states,
-// inputs wider than a workgroup -- keeps the factor array instead: the right-hand-side re-solve is the factor-based sweep
-static bool records_kept_as_factors(const NdlqrHipCtx* c) {
-  return (c->flags & NDLQR_FLAG_KEEP_RECORDS) && !(c->flags & NDLQR_FLAG_STRICT_FP) && !pick_small(c) &&
-         !plan_reduced_generic(c).ok;
+static SolvePlan plan_solve(const NdlqrHipCtx* c) {
+  const ndlqr::Dims& d = c->d;
+  SolvePlan p = {};
+  p.strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
+  p.keep = (c->flags & NDLQR_FLAG_KEEP_FACT) != 0;
+  p.inst = pick_small(c);
+  if (p.inst) {
+    p.family = Family::Small;
+    p.small = p.inst->plan(c, p.strict, p.keep);
+    p.needs_F = p.small.needs_F;
+    p.kept.schedule = p.small.schedule;
+    p.kept.rec_complete = p.small.rec_complete;
+    p.kept.rec_compact = p.small.rec_compact;
+  } else if ((p.red = plan_reduced_generic(c)).ok) {
+    p.family = Family::GenericReduced;
+    p.needs_red_generic = true;
+    p.kept.schedule = p.red.keep ? "generic-reduced-records" : "generic-reduced";
+    p.kept.rec_complete = p.red.keep;  // records, slots and W of every separator stay: rhs-only re-solves (launch_rhs_reduced_generic)
+  } else {
+    p.family = Family::GenericKnot;
+    p.rec_as_factors = (c->flags & NDLQR_FLAG_KEEP_RECORDS) && !p.strict;
+    p.lean = !p.strict && !p.keep && !p.rec_as_factors;
+    p.needs_F = true;
+    p.sep = plan_generic_sep(c, p.strict);
+    // a block too large for the separator kernel's LDS: S-bar and the panel of every level-0 separator in global memory
+    if (p.sep.scratch)
+      p.sep_scratch_bytes = sizeof(double) * ((size_t)d.n * (d.n + 1) + (size_t)d.n * (2 * d.n + 1)) * (size_t)d.batch *
+                            (d.N / 2 > 0 ? d.N / 2 : 1);
+    p.kept.schedule = p.lean ? "generic-lean" : (p.strict ? "generic-strict" : "generic-keep");
+  }
+  p.kept.family = p.family;
+  // a complete factor array is on the device with KEEP, and on the strict runtime-sized path
+  p.kept.fact_valid = p.keep || p.rec_as_factors || ((c->flags & NDLQR_FLAG_GENERIC) && p.strict);
+  // Two-deep pipeline: solves that leave nothing behind but records and the solution may alternate between two buffer
+  // sets. Everything else -- factor array, kept records, per-kernel events -- stays stream-ordered on the primary set.
+  p.may_pipeline = !p.needs_F && !(c->flags & (NDLQR_FLAG_PROFILE | NDLQR_FLAG_KEEP_RECORDS | NDLQR_FLAG_KEEP_FACT));
+  return p;
 }
 
 // Enqueue leaf/bottom + per-level + apply launches on the context's stream.
-static int enqueue_solve(NdlqrHipCtx* c) {
-  const ndlqr::Dims& d = c->d;
+static int enqueue_solve(NdlqrHipCtx* c, const SolvePlan& plan) {
   BufferSet& s = c->set[c->cur];
   // (the failure counters are cumulative: no memset node; the host subtracts what it has seen)
-  const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
   int err = NDLQR_OK;
-  bool done = false;
-  c->kept.rec_complete = false;
-  c->kept.rec_compact = false;
-  done = try_launch_small(c, strict, &err);
-  if (!done) {
-    const ReducedGenericPlan rp = plan_reduced_generic(c);
-    const bool lean = !strict && !(c->flags & NDLQR_FLAG_KEEP_FACT) && !records_kept_as_factors(c);
-    if (rp.ok) err = launch_reduced_generic(c, rp);
-    else err = strict ? launch_generic<true>(c, false) : launch_generic<false>(c, lean);
+  switch (plan.family) {
+    case Family::Small: err = plan.inst->solve(c, plan.small); break;
+    case Family::GenericReduced: err = launch_reduced_generic(c, plan.red); break;
+    default: err = plan.strict ? launch_generic<true>(c, plan) : launch_generic<false>(c, plan); break;
   }
   // the batch-wide failure count travels to pinned host memory behind the last kernel: the host
   // reads it after the stream synchronisation without another blocking copy
-  if (!err) HIP_TRY(hipMemcpyAsync(s.h_fail, c->info + d.batch, sizeof(int), hipMemcpyDeviceToHost, s.stream));
+  if (!err) HIP_TRY(hipMemcpyAsync(s.h_fail, c->info + c->d.batch, sizeof(int), hipMemcpyDeviceToHost, s.stream));
   return err;
 }
 
-// first half of a solve: allocations, recovery from a failed solve, choice of the buffer set (c->cur on return).
-// *pipelined_out: this solve runs on the two-deep pipeline.
-static int prepare_solve(NdlqrHipCtx* c, bool* pipelined_out) {
+// first half of a solve: its plan (*plan), the allocations that asks for, recovery from a failed solve, choice of the
+// buffer set (c->cur on return).
+static int prepare_solve(NdlqrHipCtx* c, SolvePlan* plan) {
   HIP_TRY(hipSetDevice(c->device));
-  if (solve_needs_F(c)) {  // before any capture starts: allocation is not a stream operation
+  *plan = plan_solve(c);
+  // before any capture starts: allocation is not a stream operation
+  if (plan->needs_F) {
     const int ferr = ndlqr_hip_ensure_F(c);
     if (ferr) return ferr;
   }
-  const bool red_generic = !pick_small(c) && plan_reduced_generic(c).ok;
-  if (!pick_small(c) && !red_generic && !c->sep_scratch) {
-    // knot-based runtime-sized path with a block too large for the separator kernel's LDS (launch_generic): S-bar and
-    // the panel of every level-0 separator in global memory. Before any capture starts: allocation is not a stream operation.
-    const ndlqr::Dims& dd = c->d;
-    const size_t per_sep = (size_t)dd.n * (dd.n + 1) + (size_t)dd.n * (2 * dd.n + 1);
-    if (plan_generic_sep(c, (c->flags & NDLQR_FLAG_STRICT_FP) != 0).scratch) {
-      const size_t bytes = sizeof(double) * per_sep * (size_t)dd.batch * (dd.N / 2 > 0 ? dd.N / 2 : 1);
-      if (hipMalloc(&c->sep_scratch, bytes) != hipSuccess) {
-        c->sep_scratch = nullptr;
-        (void)hipGetLastError();
-        return refuse("global scratch of the large-block separator kernel does not fit on the device (" +
-                      std::to_string(bytes >> 20) + " MiB): use a smaller batch");
-      }
-    }
+  if (plan->sep_scratch_bytes && !c->sep_scratch && hipMalloc(&c->sep_scratch, plan->sep_scratch_bytes) != hipSuccess) {
+    c->sep_scratch = nullptr;
+    (void)hipGetLastError();
+    return refuse("global scratch of the large-block separator kernel does not fit on the device (" +
+                  std::to_string(plan->sep_scratch_bytes >> 20) + " MiB): use a smaller batch");
   }
   if (c->state_dirty) {
     // the previous solve did not launch or complete: its arrival counters may be odd and its failure
@@ -955,35 +942,31 @@ static int prepare_solve(NdlqrHipCtx* c, bool* pipelined_out) {
     c->fail_base = 0;
     c->state_dirty = false;
   }
-  // Two-deep pipeline: solves that leave nothing behind but records and the solution alternate between two
-  // buffer sets, each on its own stream (the other set may still be in flight). Everything else -- factor
-  // array, kept records, per-kernel events, a caller-owned stream -- stays stream-ordered on the primary set.
-  const bool pipelined = c->pipeline >= 2 && c->own_stream && !solve_needs_F(c) &&
-                         !(c->flags & (NDLQR_FLAG_PROFILE | NDLQR_FLAG_KEEP_RECORDS | NDLQR_FLAG_KEEP_FACT));
+  // (each set on its own stream, the other set may still be in flight; a caller-owned stream stays stream-ordered)
+  const bool pipelined = c->pipeline >= 2 && c->own_stream && plan->may_pipeline;
   const bool want_alt = pipelined && (c->solve_count & 1u) && ensure_alt(c);
   if (!pipelined && c->set[1].stream) HIP_TRY(hipStreamSynchronize(c->set[1].stream));
-  if (red_generic) {  // (after ensure_alt: both buffer sets get their slots)
+  if (plan->needs_red_generic) {  // (after ensure_alt: both buffer sets get their slots)
     const int rerr = ensure_red_generic(c);
     if (rerr) return rerr;
   }
   c->cur = want_alt ? 1 : 0;
   ++c->solve_count;
   c->state_dirty = true;  // until this solve is known to have been enqueued completely
-  if (pipelined_out) *pipelined_out = pipelined;
   return NDLQR_OK;
 }
 
 // The launch sequence `enqueue` issues on the current buffer set's stream, replayed as the hipGraph of `g`: a fixed chain
 // of short launches, captured once (launch-bound single solves -- batch 1 -- gain the most) and again whenever the key it
-// was captured under changes. The schedule bookkeeping is then what THIS chain's sequence leaves behind.
-static int replay_chain(NdlqrHipCtx* c, CapturedChain& g, int (*enqueue)(NdlqrHipCtx*)) {
+// was captured under changes (the key determines the plan).
+static int replay_chain(NdlqrHipCtx* c, CapturedChain& g, const SolvePlan& plan, int (*enqueue)(NdlqrHipCtx*, const SolvePlan&)) {
   const hipStream_t st = c->set[c->cur].stream;
   const unsigned apply = ((unsigned)c->apply_blk0 << 16) | (unsigned)c->apply_nblk;  // (restricted back-substitution of a step)
   if (!g.exec || g.flags != c->flags || g.stream != st || g.apply != apply) {
     g.reset();
     hipGraph_t graph = nullptr;
     HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int err = enqueue(c);
+    const int err = enqueue(c, plan);
     hipError_t e = hipStreamEndCapture(st, &graph);
     if (err) { if (graph) (void)hipGraphDestroy(graph); return err; }
     if (e != hipSuccess) return fail("hipStreamEndCapture", e);
@@ -993,27 +976,20 @@ static int replay_chain(NdlqrHipCtx* c, CapturedChain& g, int (*enqueue)(NdlqrHi
     g.flags = c->flags;
     g.stream = st;
     g.apply = apply;
-    g.kept = c->kept;
   }
   HIP_TRY(hipGraphLaunch(g.exec, st));
-  g.kept.fact_valid = c->kept.fact_valid;  // (the callers' to set: launch_solve, ndlqr_hip_solve_staged)
-  c->kept = g.kept;
   return NDLQR_OK;
 }
 
-// a complete factor array is on the device with KEEP, and on the strict runtime-sized path
-static bool solve_leaves_factors(const NdlqrHipCtx* c) {
-  return (c->flags & NDLQR_FLAG_KEEP_FACT) != 0 || records_kept_as_factors(c) ||
-         ((c->flags & NDLQR_FLAG_GENERIC) && (c->flags & NDLQR_FLAG_STRICT_FP));
-}
-
 // second half: the launch sequence on the current buffer set's stream (per-kernel events need eager launches)
-static int launch_solve(NdlqrHipCtx* c) {
-  const int err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_solve(c) : replay_chain(c, c->set[c->cur].graph, enqueue_solve);
+static int launch_solve(NdlqrHipCtx* c, const SolvePlan& plan) {
+  c->kept.rec_complete = c->kept.rec_compact = false;  // (the launches overwrite the records)
+  const int err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_solve(c, plan)
+                                                  : replay_chain(c, c->set[c->cur].graph, plan, enqueue_solve);
   if (err) return err;
   HIP_TRY(hipGetLastError());
   note_solution(c);
-  c->kept.fact_valid = solve_leaves_factors(c);
+  c->kept = plan.kept;
   c->inputs_replaced = false;
   c->box_fact = false;  // (the records / factors are those of the unshifted matrix now)
   ++c->factor_count;
@@ -1022,13 +998,14 @@ static int launch_solve(NdlqrHipCtx* c) {
 
 int ndlqr_hip_solve_async(NdlqrHipCtx* c) {
   if (!c) return NDLQR_ERR_INVALID;
-  int err = prepare_solve(c, nullptr);
+  SolvePlan plan;
+  int err = prepare_solve(c, &plan);
   if (err) return err;
   BufferSet& s = c->set[c->cur];
   err = rhs_make_current(c, 0xFu);  // (this buffer set's copy of the right-hand side may be behind: steps write one set)
   if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  err = launch_solve(c);
+  err = launch_solve(c, plan);
   if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   c->timing_pending = true;
@@ -1068,7 +1045,7 @@ int ndlqr_hip_staged_io(NdlqrHipCtx* c, double** AB, double** QR, double** rhs, 
 }
 
 // the copies around the launch chain, on the context's stream (captured, or eager under NDLQR_FLAG_PROFILE)
-static int enqueue_staged(NdlqrHipCtx* c) {
+static int enqueue_staged(NdlqrHipCtx* c, const SolvePlan& plan) {
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   BufferSet& s = c->set[c->cur];
@@ -1087,7 +1064,7 @@ static int enqueue_staged(NdlqrHipCtx* c) {
     HIP_TRY(hipMemcpyAsync(c->QR, c->h_io + oQR, sizeof(double) * nQR, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(s.rhs, c->h_io + orhs, sizeof(double) * nz, hipMemcpyHostToDevice, st));
   }
-  const int err = enqueue_solve(c);
+  const int err = enqueue_solve(c, plan);
   if (err) return err;
   if (c->padded) {
     hipLaunchKernelGGL(ndlqr::unpad_blocks_generic, dim3(d.N * d.batch), dim3(64), 0, st, u, d, (const double*)s.z,
@@ -1106,19 +1083,20 @@ int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
     const int perr = ndlqr_hip_set_pipeline_depth(c, 1);
     if (perr) return perr;
   }
-  int err = prepare_solve(c, nullptr);  // (allocations, recovery from a failed solve; depth 1: the primary set)
+  SolvePlan plan;
+  int err = prepare_solve(c, &plan);  // (allocations, recovery from a failed solve; depth 1: the primary set)
   if (err) return err;
   rhs_written_cur(c, 0xFu);
   c->kept.forget_factorisation();  // new A, B, Q, R: neither a cached factor array nor cached records match
   c->box_fact = false;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_staged(c) : replay_chain(c, c->staged, enqueue_staged);
+  err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_staged(c, plan) : replay_chain(c, c->staged, plan, enqueue_staged);
   if (err) return err;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   note_solution(c);
-  c->kept.fact_valid = solve_leaves_factors(c);
+  c->kept = plan.kept;
   c->inputs_replaced = false;
   c->timing_pending = true;
   c->state_dirty = false;
@@ -1137,7 +1115,7 @@ static const SmallInstance* time_shard_instance(NdlqrHipCtx* c, int G) {
 
 int ndlqr_hip_time_shard_top_doubles(NdlqrHipCtx* c, int G) {
   const SmallInstance* inst = time_shard_instance(c, G);
-  return inst ? (G - 1) * c->d.batch * inst->slot() : NDLQR_ERR_INVALID;
+  return inst ? (G - 1) * c->d.batch * inst->slot : NDLQR_ERR_INVALID;
 }
 
 static int time_shard_copy_slots(NdlqrHipCtx* c, int G, double* buf, bool to_buf) {
@@ -1145,7 +1123,7 @@ static int time_shard_copy_slots(NdlqrHipCtx* c, int G, double* buf, bool to_buf
   if (!inst || !buf) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
   BufferSet& b = c->set[c->cur];
-  const size_t slot = (size_t)inst->slot();
+  const size_t slot = (size_t)inst->slot;
   const size_t pitch_red = sizeof(double) * (size_t)(d.N >> 2) * slot, width = sizeof(double) * slot;
   HIP_TRY(hipSetDevice(c->device));
   for (int j = 1; j < G; ++j) {
@@ -1250,7 +1228,8 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
                          double* soln) {
   if (!c || !x0 || !soln) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
-  int err = prepare_solve(c, nullptr);
+  SolvePlan plan;
+  int err = prepare_solve(c, &plan);
   if (err) return err;
   BufferSet& s = c->set[c->cur];
   err = ensure_xfer(c);  // (before anything is captured: allocation is not a stream operation)
@@ -1299,14 +1278,14 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   //  against 11.5 ms at (64,16,512) x 256, 4.8 against 6.4 at (48,16,512) x 256; at (32,8) the two are equal and at
   //  (16,4,256) x 1024 the re-solve takes 2.8 ms against 1.9 for factor + solve, profiles/r04_mpc_steps.txt. The
   //  full-record form of the small shapes -- tree schedule -- re-solves no faster than it factors and keeps factoring.)
-  const bool generic_records = !pick_small(c) && c->d.n > 32;
+  const bool generic_records = c->kept.family == Family::GenericReduced && c->d.n > 32;
   if ((c->flags & NDLQR_FLAG_KEEP_RECORDS) && !(c->flags & (NDLQR_FLAG_STRICT_FP | NDLQR_FLAG_KEEP_FACT)) && c->kept.rec_complete &&
       (c->kept.rec_compact || generic_records) && c->cur == 0 && try_launch_rhs_records(c, s.rhs, s.z)) {
     HIP_TRY(hipGetLastError());
     note_solution(c);
     c->kept.schedule = generic_records ? "generic-reduced-records (re-solve)" : "reduced-compact-records (re-solve)";
   } else {
-    err = launch_solve(c);
+    err = launch_solve(c, plan);
     if (err) return err;
   }
   // (the staging has been consumed by the pack kernel: it now takes the packed solutions -- all of them, or the slice
@@ -1330,7 +1309,8 @@ int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   const KnotSlice sel = {knot0, nknots, blocks};
   if (!c || !out || !sel.valid(c->d.N, 15u)) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
-  int err = prepare_solve(c, nullptr);
+  SolvePlan plan;
+  int err = prepare_solve(c, &plan);
   if (err) return err;
   BufferSet& s = c->set[c->cur];
   err = ensure_xfer(c);
@@ -1340,7 +1320,7 @@ int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   hipStream_t st = s.stream;
   HIP_TRY(hipEventRecord(s.ev_start, st));
   const ApplySlice apply_slice(c, sel);
-  err = launch_solve(c);
+  err = launch_solve(c, plan);
   if (err) return err;
   err = deliver(c->du, d, sel, s.z, out, where(out, c->device) == Where::OwnDevice, s.xfer, hipMemcpyDefault, st, d.batch);
   if (err) return err;
@@ -1471,7 +1451,7 @@ static void launch_rhs_sweep(NdlqrHipCtx* c, const double* rhs, double* z) {
     {
       ScopedSlot t(c, SLOT_SEP);
       const size_t lds_staged = sizeof(double) * ((size_t)d.n * (d.n + 1) + d.n);
-      const int staged = lds_staged <= 160 * 1024 ? 1 : 0;
+      const int staged = lds_staged <= kLdsMax ? 1 : 0;
       hipLaunchKernelGGL((ndlqr::rhs_separator_generic<STRICT>), dim3(d.N >> (l + 1), d.batch), dim3(64),
                          staged ? lds_staged : sizeof(double) * (size_t)d.n, s.stream, d, l, c->AB, c->F, z, staged);
     }
@@ -1484,17 +1464,16 @@ static void launch_rhs_sweep(NdlqrHipCtx* c, const double* rhs, double* z) {
   }
 }
 
-// the record-based re-solve where the kept records have one: right-hand side `rhs`, solution into `z`
+// the record-based re-solve where the kept records have one, by the kernels of the family that wrote them: right-hand
+// side `rhs`, solution into `z`
 static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
   const ndlqr::Dims& d = c->d;
   if (!c->kept.rec_complete || (c->flags & NDLQR_FLAG_STRICT_FP)) return false;
-  if (!pick_small(c)) {  // runtime-sized separator-only schedule: records + slots + W of every separator
-    if (!plan_reduced_generic(c).ok) return false;
+  if (c->kept.family == Family::GenericReduced) {  // records + slots + W of every separator
     launch_rhs_reduced_generic(c, rhs, z);
     return true;
   }
-  if (c->flags & NDLQR_FLAG_GENERIC) return false;
-  const SmallInstance* inst = find_small(d);
+  const SmallInstance* inst = kept_instance(c);
   if (!inst) return false;
   // (the full-record forms: sweep array of rhs_forward_upper within the default dynamic LDS, backsub_small's K + 4
   //  separators of nx rows in one workgroup; the compact form -- rb_forward / rb_forward_top -- was checked by its plan)
@@ -1629,7 +1608,7 @@ static hipError_t adjoint_scratch(NdlqrHipCtx* c, bool restore) {
   const size_t rec_pitch = sizeof(double) * (2 * (size_t)d.n * d.n + d.n);
   hipError_t e = restore ? hipMemcpy2DAsync(rec_col, rec_pitch, save, col, col, rows, hipMemcpyDeviceToDevice, s.stream)
                          : hipMemcpy2DAsync(save, col, rec_col, rec_pitch, col, rows, hipMemcpyDeviceToDevice, s.stream);
-  if (e != hipSuccess || pick_small(c) || d.N < 4 || !s.red || s.red_bytes < bytes_red_generic(d)) return e;
+  if (e != hipSuccess || c->kept.family != Family::GenericReduced || d.N < 4) return e;
   double* slot_g = s.red + 4 * (size_t)d.n * d.n;
   const size_t slot_pitch = sizeof(double) * (4 * (size_t)d.n * d.n + 2 * d.n), nslots = (size_t)d.batch * (d.N / 2);
   save += rows * d.n;
@@ -1643,7 +1622,7 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
     return refuse("adjoint solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
                   "factorisation) of the resident inputs");
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_adjoint");
-  if (!strcmp(c->kept.schedule, "reduced-time-shard")) return refuse("adjoint solve: not available on a time-axis shard");
+  if (c->kept.time_shard) return refuse("adjoint solve: not available on a time-axis shard");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
@@ -1737,7 +1716,7 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
     if (user[o] && ((sum_mask >> o) & 1u)) wsum += ndlqr::grad_width(u, o);
   int KC = 8;
   while (KC > 1 && (KC > d.N || sizeof(double) * ((size_t)KC * wsum + 2 * (size_t)(KC + 1) * d.rows) > 48 * 1024)) KC >>= 1;
-  const size_t lds_max = 160 * 1024 / sizeof(double), zw = 2 * (size_t)(KC + 1) * d.rows, nacc = (size_t)KC * wsum;
+  const size_t lds_max = kLdsMax / sizeof(double), zw = 2 * (size_t)(KC + 1) * d.rows, nacc = (size_t)KC * wsum;
   if (zw >= lds_max)
     return refuse("ndlqr_hip_gradients: z and w of two knots of this block size exceed the LDS of a workgroup");
   // where the accumulators of one knot do not fit beside z | w (a batch-summed gA from about 139 states on), they are
@@ -1768,10 +1747,7 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
   for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) out.p[o] = ga.dev[o];
   const double* z = c->set[c->latest].z;
   const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
-  if (lds > 64 * 1024)  // (beyond the default limit of dynamic LDS)
-    HIP_TRY(hipFuncSetAttribute(strict ? reinterpret_cast<const void*>(&ndlqr::grad_assemble<true>)
-                                       : reinterpret_cast<const void*>(&ndlqr::grad_assemble<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(strict ? allow_dynamic_lds(&ndlqr::grad_assemble<true>, lds) : allow_dynamic_lds(&ndlqr::grad_assemble<false>, lds));
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   launch_strict(strict, ndlqr::grad_assemble, dim3(nchunks, nsplit, nslice), dim3(256), lds, s.stream, u, d, KC, ppb, (int)EC,
                 z, (const double*)c->adj_z, out, part);
@@ -1861,8 +1837,9 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
 // the pivot check: *not_spd = NDLQR_ERR_NOT_SPD, which is returned, when a pivot was not positive.
 static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd) {
   c->box_fact = false;
-  int err = prepare_solve(c, nullptr);  // (KEEP_*: stream-ordered on the primary set)
-  if (!err) err = launch_solve(c);
+  SolvePlan plan;
+  int err = prepare_solve(c, &plan);  // (KEEP_*: stream-ordered on the primary set)
+  if (!err) err = launch_solve(c, plan);
   if (err) return err;
   c->state_dirty = false;
   HIP_TRY(hipStreamSynchronize(st));
@@ -2143,7 +2120,7 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
   if (c->box_soln_gen == 0 || c->box_soln_gen != c->soln_gen || !c->box_fact || c->inputs_replaced)
     return refuse("ndlqr_hip_solve_box_adjoint: the resident solution is not that of the latest constrained solve (a solve, "
                   "step, re-solve, new inputs or new bounds came after it)");
-  if (!strcmp(c->box_kept.schedule, "reduced-time-shard")) return refuse("ndlqr_hip_solve_box_adjoint: not available on a time-axis shard");
+  if (c->box_kept.time_shard) return refuse("ndlqr_hip_solve_box_adjoint: not available on a time-axis shard");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
@@ -2324,7 +2301,7 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
   HIP_TRY(sync_all(c));
   c->cur = 0;
   BufferSet& st = c->set[0];
-  const SmallInstance* inst = pick_small(c);
+  const SmallInstance* inst = kept_instance(c);
   if (!inst || !c->kept.rec_complete || !c->kept.rec_compact)
     return refuse("multiple right-hand sides need the compact records of a solve with NDLQR_FLAG_KEEP_RECORDS on a "
                   "size-specialised shape (level-per-launch schedule: batch x N / 4 > 2048, or NDLQR_TREE=0)");

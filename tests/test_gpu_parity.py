@@ -433,6 +433,64 @@ def test_resolve_with_records_only(ndlqr, oracle, n, m, N):
     bs.close()
 
 
+_FLAG_CHANGE_REFS = {}
+
+
+def _flag_change_refs(ndlqr, oracle, n, m, N, batch):
+    """(first, mixed, oracle solutions of first, of mixed): the problems of test_resolve_with_records_only, solved once."""
+    key = (n, m, N, batch)
+    if key not in _FLAG_CHANGE_REFS:
+        first = [synth(ndlqr, n, m, N, 300 + p) for p in range(batch)]
+        other = [synth(ndlqr, n, m, N, 700 + p) for p in range(batch)]
+        mixed = [Problem(n, m, N, f.A, f.B, f.Q, f.R, o.q, o.r, o.d, o.x0) for f, o in zip(first, other)]
+        refs = [[oracle.solve(prob, 1)[0][: prob.nvars] for prob in probs] for probs in (first, mixed)]
+        _FLAG_CHANGE_REFS[key] = (first, mixed, refs[0], refs[1])
+    return _FLAG_CHANGE_REFS[key]
+
+
+# (NDLQR_TREE, flags of the factorisation, its schedule, flags from then on, schedule of a solve under those)
+FLAG_CHANGES = [(None, "records", "reduced-tree", "generic+records", "generic-reduced-records"),
+                ("0", "records", "reduced-compact-records", "generic+records", "generic-reduced-records"),
+                (None, "generic+records", "generic-reduced-records", "records", "reduced-tree")]
+
+
+@pytest.mark.parametrize("tree,flags0,want0,flags1,want1", FLAG_CHANGES, ids=[c[2] + "-then-" + c[3] for c in FLAG_CHANGES])
+def test_resolve_after_flag_change(ndlqr, oracle, monkeypatch, tree, flags0, want0, flags1, want1):
+    """NDLQR_FLAG_GENERIC set or cleared between a KEEP_RECORDS solve and its re-solves: the rhs-only solve and the
+    adjoint run the kernels of the family that wrote the records (KeptState), to the accuracy they have when the flags
+    stay; the next solve runs the new family's schedule."""
+    from test_gpu_gradients import REL_TOL as ADJOINT_REL_TOL, adjoint_problem, rel
+    if tree is not None:
+        monkeypatch.setenv("NDLQR_TREE", tree)
+    n, m, N, batch = 12, 4, 16, 3
+    fl = {"records": ndlqr.FLAG_KEEP_RECORDS, "generic+records": ndlqr.FLAG_GENERIC | ndlqr.FLAG_KEEP_RECORDS}
+    first, mixed, ref_first, ref_mixed = _flag_change_refs(ndlqr, oracle, n, m, N, batch)
+
+    def check(sol, probs, refs):
+        for p, prob in enumerate(probs):
+            assert np.linalg.norm(sol[p] - refs[p]) / np.linalg.norm(refs[p]) <= REL_TOL
+            ok, detail = _kkt_ok(oracle, prob, sol[p])
+            assert ok, detail
+
+    bs = ndlqr.BatchSolver(n, m, N, batch, flags=fl[flags0])
+    bs.initialize_flat(*stack(first))
+    assert bs.solve() == 0 and bs.schedule() == want0, bs.schedule()
+    check(bs.solutions(), first, ref_first)
+    bs.set_flags(fl[flags1])
+    bs.set_rhs_flat(*[np.stack([getattr(p, k) for p in mixed]) for k in ("q", "r", "d", "x0")])
+    assert bs.solve_rhs_only() == 0
+    check(bs.solutions(), mixed, ref_mixed)
+    g = np.random.default_rng(4).standard_normal((batch, bs.nvars))
+    assert bs.solve_adjoint(g) == 0
+    w = bs.adjoint()
+    for p, prob in enumerate(mixed):
+        wr = oracle.solve(adjoint_problem(prob, g[p]), 1)[0][: prob.nvars]
+        assert rel(w[p], wr) <= ADJOINT_REL_TOL, (p, rel(w[p], wr))
+    assert bs.solve() == 0 and bs.schedule() == want1, bs.schedule()
+    check(bs.solutions(), mixed, ref_mixed)
+    bs.close()
+
+
 @pytest.mark.parametrize("n,m,N", [(12, 4, 256), (6, 3, 512)])
 @pytest.mark.parametrize("a_scale,q_scale", [(1.15, 1.0), (1.0, 1e-4), (1.3, 1e-3)])
 def test_harder_problem_families(ndlqr, oracle, n, m, N, a_scale, q_scale):
