@@ -502,6 +502,30 @@ int ndlqr_SolveBatchAdjoint(NdLqrBatchSolver* bs, const double* g);  /* K w = g 
 int ndlqr_CopyBatchAdjoint(NdLqrBatchSolver* bs, double* w);         /* [batch][nvars]; returns nvars */
 int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR,
                          double* gq, double* gr, double* gd, double* gx0);
+/* additive: iterative refinement of a batch solve with a double-double residual, for callers who need more than the
+ * solve paths deliver on ill-conditioned inputs. ndlqr_RefineBatch evaluates r = b - K z of the resident solutions with
+ * every row accumulated in double-double and rounded once, re-solves K delta = r against the kept factorisation, and
+ * stores z + delta (fp64) for every problem whose residual norm ||r||_inf went down -- up to max_steps times (1 .. 8), with
+ * no host read-back between the steps. Step s of a problem is accepted iff its residual norm fell strictly at every step
+ * up to s (false for NaN; a rejection is permanent): a problem's residual never grows, one that cannot be improved keeps its
+ * solution bit for bit, and NaN or inf data take 0 steps.
+ *   Outputs, each [batch] and each may be NULL (host, pinned or the solver's device memory): steps taken; eta = ||r||_inf /
+ *   max_i(|b_i| + sum_j |K_ij| |z_j|) before and after them.
+ *   Reach: wherever ndlqr_SolveBatchRhsOnly works -- a solve with NDLQR_FLAG_KEEP_RECORDS (fast mode) or
+ *   NDLQR_FLAG_KEEP_FACT (any mode). NDLQR_ERR_INVALID without a kept factorisation of the resident inputs (also after a
+ *   constrained solve or the upload of new inputs), after a step that computed a slice alone (NDLQR_SOLN_ONLY), on a
+ *   time-axis shard, for max_steps outside 1 .. 8 and for device memory of another device.
+ *   State: the refined solution is a new resident solution -- ndlqr_CopyBatchSolutions, ndlqr_BatchKktResiduals and the
+ *   device pack see it, and an earlier adjoint is invalidated. The kept records and factors, the inputs, the right-hand side
+ *   and the flags stay bit for bit as found: a later ndlqr_SolveBatchRhsOnly equals one without the refinement.
+ * ndlqr_RefineBatchAdjoint does the same for w of the latest ndlqr_SolveBatchAdjoint against its g; it changes w alone,
+ * needs a valid plain adjoint and refuses the adjoint of a constrained solve.
+ * ndlqr_BatchKktResidualVector delivers r = b - K z, [batch][nvars] in the packing of ndlqr_CopyBatchSolutions, evaluated
+ * in double-double; it needs no kept factorisation and refuses where ndlqr_BatchKktResiduals does.
+ * All three block; ndlqr_BatchSolveTimeMs then reports the device time of the whole call. */
+int ndlqr_RefineBatch(NdLqrBatchSolver* bs, int max_steps, int* steps, double* eta_before, double* eta_after);
+int ndlqr_RefineBatchAdjoint(NdLqrBatchSolver* bs, int max_steps, int* steps, double* eta_before, double* eta_after);
+int ndlqr_BatchKktResidualVector(NdLqrBatchSolver* bs, double* r);
 /* additive: box-constrained batch solve (MPC with actuator and state limits). For every problem of the batch, the resident
  * LQR problem plus the bounds xlo_k <= x_k <= xhi_k (k = 1 .. N-1) and ulo_k <= u_k <= uhi_k (k = 0 .. N-2), solved by
  * scaled ADMM with over-relaxation and a fixed penalty rho (OSQP-style) on the kept factorisation:

@@ -103,6 +103,16 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* ctx, const double* g);
 int ndlqr_hip_download_adjoint(NdlqrHipCtx* ctx, double* w); /* [batch][nvars]: host, pinned or this device's memory */
 int ndlqr_hip_gradients(NdlqrHipCtx* ctx, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR, double* gq,
                         double* gr, double* gd, double* gx0);
+/* Iterative refinement with a double-double residual (ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint,
+ * ndlqr_BatchKktResidualVector). which = 0: the resident solution against the resident right-hand
+ * side; 1: w of the latest plain adjoint against its packed g. max_steps in [1, 8]. steps [batch] (int), eta_before,
+ * eta_after [batch]: each may be NULL; host, pinned or this device's memory. Blocking. ndlqr_hip_refine_phase_ms: device
+ * time of the residual kernels | re-solves | commits of the latest refinement that ran under NDLQR_FLAG_PROFILE (3
+ * doubles). ndlqr_hip_kkt_residual_vector: r = b - K z of the resident solution, [batch][nvars] in the packing of
+ * ndlqr_hip_download_solutions, every row accumulated in double-double (host, pinned or this device's memory). */
+int ndlqr_hip_refine(NdlqrHipCtx* ctx, int which, int max_steps, int* steps, double* eta_before, double* eta_after);
+int ndlqr_hip_refine_phase_ms(NdlqrHipCtx* ctx, double* out3);
+int ndlqr_hip_kkt_residual_vector(NdlqrHipCtx* ctx, double* r);
 /* Box-constrained solve by scaled ADMM on the kept factorisation (ndlqr.h: ndlqr_BatchSetBounds,
  * ndlqr_SolveBatchBoxConstrained, ndlqr_CopyBatchBoundMultipliers). Bounds in the flat layout,
  * [batch][N][n] / [batch][N][m], or [N][..] once for every problem when `shared`; NULL = unbounded; host, pinned or this

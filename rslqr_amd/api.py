@@ -273,6 +273,10 @@ def lib():
     proto("ndlqr_SolveBatchAdjoint", ci, vp, dp)
     proto("ndlqr_CopyBatchAdjoint", ci, vp, dp)
     proto("ndlqr_BatchGradients", ci, vp, C.c_uint, dp, dp, dp, dp, dp, dp, dp, dp)
+    proto("ndlqr_RefineBatch", ci, vp, ci, C.POINTER(ci), dp, dp)
+    proto("ndlqr_RefineBatchAdjoint", ci, vp, ci, C.POINTER(ci), dp, dp)
+    proto("ndlqr_BatchKktResidualVector", ci, vp, dp)
+    proto("ndlqr_hip_refine_phase_ms", ci, vp, dp)
     proto("ndlqr_BatchDeviceContext", vp, vp)
     proto("ndlqr_BatchSetBounds", ci, vp, C.c_uint, dp, dp, dp, dp)
     proto("ndlqr_SolveBatchBoxConstrained", ci, vp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
@@ -621,6 +625,43 @@ class BatchSolver:
         if err:
             raise RuntimeError("ndlqr_BatchGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
+
+    # ---- iterative refinement (include/ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint, ndlqr_BatchKktResidualVector)
+    def _refine(self, name, max_steps):
+        steps = np.zeros(self.batch, dtype=np.int32)
+        before, after = np.zeros(self.batch), np.zeros(self.batch)
+        err = getattr(self.L, name)(self.h, int(max_steps), steps.ctypes.data_as(C.POINTER(C.c_int)), _ptr(before), _ptr(after))
+        if err:
+            raise RuntimeError("%s failed: %d (%s)" % (name, err, self.L.ndlqr_hip_last_error().decode()))
+        return steps, before, after
+
+    def refine(self, max_steps=2):
+        """ndlqr_RefineBatch: up to max_steps (1 .. 8) steps of iterative refinement of the resident solutions with a
+        double-double residual, against the factorisation the last solve kept (FLAG_KEEP_RECORDS or FLAG_KEEP_FACT).
+        Returns (steps, eta_before, eta_after), numpy arrays [batch]: the steps every problem took (a step counts while the
+        residual norm fell at every step so far) and eta = ||r||_inf / max_i(|b_i| + sum_j |K_ij| |z_j|) before and after
+        them. Raises on a refusal (no kept factorisation of the resident solution)."""
+        return self._refine("ndlqr_RefineBatch", max_steps)
+
+    def refine_adjoint(self, max_steps=2):
+        """ndlqr_RefineBatchAdjoint: the same for w of the latest solve_adjoint against its g."""
+        return self._refine("ndlqr_RefineBatchAdjoint", max_steps)
+
+    def kkt_residual_vector(self, out=None):
+        """ndlqr_BatchKktResidualVector: r = b - K z of the resident solutions, [batch, nvars] in the packing of solutions(),
+        every row accumulated in double-double and rounded once; `out`: destination (numpy array or DeviceArray)."""
+        if out is None:
+            out = np.zeros((self.batch, self.nvars))
+        err = self.L.ndlqr_BatchKktResidualVector(self.h, _any_ptr(out, self.batch * self.nvars))
+        if err:
+            raise RuntimeError("ndlqr_BatchKktResidualVector failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def refine_phase_ms(self):
+        """(residual, re-solve, commit) device times in ms of the latest refinement that ran under FLAG_PROFILE."""
+        out = np.zeros(3)
+        self.L.ndlqr_hip_refine_phase_ms(self.ctx, _ptr(out))
+        return tuple(out)
 
     # ---- box-constrained solve (include/ndlqr.h: ndlqr_BatchSetBounds, ndlqr_SolveBatchBoxConstrained)
     def set_bounds(self, xlo=None, xhi=None, ulo=None, uhi=None):

@@ -101,8 +101,9 @@ def _flat(args, n, m, N, b, shared):
     return out
 
 
-def _solve(bs, flat, token, key):
-    """Factor + solve of `flat` on the cached solver; the solver then holds forward `token`."""
+def _solve(bs, flat, token, key, refine=0):
+    """Factor + solve of `flat` on the cached solver (and `refine` steps of iterative refinement at most); the solver then
+    holds forward `token`."""
     torch.cuda.current_stream(flat[0].device).synchronize()  # (the library reads torch memory on its own stream)
     bs.initialize_flat_device(*[t.data_ptr() for t in flat])
     err = bs.solve()
@@ -110,61 +111,94 @@ def _solve(bs, flat, token, key):
         _cache[key][1] = None
         raise RuntimeError("lqr_solve: the factorisation failed (%d non-positive pivots): Q, R or the problem are not "
                            "positive definite" % max(bs.cholesky_failures(), 1))
+    if refine > 0:
+        bs.refine(refine)
     _cache[key][1] = token
+
+
+def _forward(ctx, refine, args):
+    dev, n, m, N, b, shared = _check(args)
+    key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _cache:
+        _cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
+    bs = _cache[key][0]
+    flat = _flat(args, n, m, N, b, shared)
+    token = next(_tokens)
+    _solve(bs, flat, token, key, refine)
+    z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
+    bs.solutions_to_device(z.data_ptr())
+    bs.synchronize()
+    ctx.key, ctx.token, ctx.flat, ctx.shared, ctx.dims = key, token, flat, shared, (n, m, N, b)
+    ctx.refine = refine
+    return z
+
+
+def _backward(ctx, gz, needs_input_grad):
+    n, m, N, b = ctx.dims
+    bs = _cache[ctx.key][0]
+    if _cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's factorisation again
+        _solve(bs, ctx.flat, ctx.token, ctx.key, ctx.refine)
+    gz = gz.detach().to(torch.float64).contiguous()
+    torch.cuda.current_stream(gz.device).synchronize()
+    err = bs.solve_adjoint(_View(gz))
+    if err:
+        raise RuntimeError("lqr_solve backward: adjoint solve failed: %d" % err)
+    if ctx.refine > 0:
+        bs.refine_adjoint(ctx.refine)
+    mask = 0
+    out, views = {}, {}
+    for i, (name, sh, need) in enumerate(zip(GRAD_NAMES, ctx.shared, needs_input_grad)):
+        if not need:
+            continue
+        if sh:
+            mask |= 1 << i
+        out[name] = torch.empty(bs.gradient_shape(name, sh), dtype=torch.float64, device=gz.device)
+        views[name] = _View(out[name])
+    if views:
+        bs.gradients(mask, views)
+    grads = []
+    for name, sh in zip(GRAD_NAMES, ctx.shared):
+        g = out.get(name)
+        if g is not None and name in ("A", "B"):  # flat column-major -> row-major math convention
+            cols = n if name == "A" else m
+            g = g.reshape(*g.shape[:-1], cols, n).transpose(-1, -2)
+        grads.append(g)
+    return tuple(grads)
 
 
 class LqrSolve(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *args):
-        dev, n, m, N, b, shared = _check(args)
-        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
-        if key not in _cache:
-            _cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
-        bs = _cache[key][0]
-        flat = _flat(args, n, m, N, b, shared)
-        token = next(_tokens)
-        _solve(bs, flat, token, key)
-        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
-        bs.solutions_to_device(z.data_ptr())
-        bs.synchronize()
-        ctx.key, ctx.token, ctx.flat, ctx.shared, ctx.dims = key, token, flat, shared, (n, m, N, b)
-        return z
+        return _forward(ctx, 0, args)
 
     @staticmethod
     def backward(ctx, gz):
-        n, m, N, b = ctx.dims
-        bs = _cache[ctx.key][0]
-        if _cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's factorisation again
-            _solve(bs, ctx.flat, ctx.token, ctx.key)
-        gz = gz.detach().to(torch.float64).contiguous()
-        torch.cuda.current_stream(gz.device).synchronize()
-        err = bs.solve_adjoint(_View(gz))
-        if err:
-            raise RuntimeError("lqr_solve backward: adjoint solve failed: %d" % err)
-        mask = 0
-        out, views = {}, {}
-        for i, (name, sh, need) in enumerate(zip(GRAD_NAMES, ctx.shared, ctx.needs_input_grad)):
-            if not need:
-                continue
-            if sh:
-                mask |= 1 << i
-            out[name] = torch.empty(bs.gradient_shape(name, sh), dtype=torch.float64, device=gz.device)
-            views[name] = _View(out[name])
-        if views:
-            bs.gradients(mask, views)
-        grads = []
-        for name, sh in zip(GRAD_NAMES, ctx.shared):
-            g = out.get(name)
-            if g is not None and name in ("A", "B"):  # flat column-major -> row-major math convention
-                cols = n if name == "A" else m
-                g = g.reshape(*g.shape[:-1], cols, n).transpose(-1, -2)
-            grads.append(g)
-        return tuple(grads)
+        return _backward(ctx, gz, ctx.needs_input_grad)
 
 
-def lqr_solve(A, B, Q, R, q, r, d, x0):
-    """z [b, nvars] of the LQR problems (see the module docstring), differentiable in every argument."""
-    return LqrSolve.apply(A, B, Q, R, q, r, d, x0)
+class LqrSolveRefined(torch.autograd.Function):
+    """LqrSolve with `refine` steps of iterative refinement (ndlqr_RefineBatch) behind the forward solve and behind the
+    adjoint solve of the backward (ndlqr_RefineBatchAdjoint)."""
+
+    @staticmethod
+    def forward(ctx, refine, *args):
+        return _forward(ctx, refine, args)
+
+    @staticmethod
+    def backward(ctx, gz):
+        return (None,) + _backward(ctx, gz, ctx.needs_input_grad[1:])
+
+
+def lqr_solve(A, B, Q, R, q, r, d, x0, refine=0):
+    """z [b, nvars] of the LQR problems (see the module docstring), differentiable in every argument. refine > 0: that
+    many steps of iterative refinement with a double-double residual at most (BatchSolver.refine) on the solution, and in
+    the backward on the adjoint before the gradients are assembled; 0: neither."""
+    refine = int(refine)
+    if refine < 0 or refine > 8:
+        raise ValueError("lqr_solve: refine must lie in 0 .. 8, got %d" % refine)
+    if refine == 0:
+        return LqrSolve.apply(A, B, Q, R, q, r, d, x0)
+    return LqrSolveRefined.apply(refine, A, B, Q, R, q, r, d, x0)
 
 
 # ------------------------------------------------------------------------------------------------ box-constrained
@@ -321,4 +355,4 @@ def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=Non
                              A, B, Q, R, q, r, d, x0, xlo, xhi, ulo, uhi)
 
 
-__all__ = ["LqrSolve", "LqrSolveBox", "lqr_solve", "lqr_solve_box", "split_solution"]
+__all__ = ["LqrSolve", "LqrSolveRefined", "LqrSolveBox", "lqr_solve", "lqr_solve_box", "split_solution"]

@@ -359,6 +359,18 @@ int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, do
   if (!bs) return NDLQR_ERR_INVALID;
   return ndlqr_hip_gradients(bs->ctx, sum_mask, gA, gB, gQ, gR, gq, gr, gd, gx0);
 }
+int ndlqr_RefineBatch(NdLqrBatchSolver* bs, int max_steps, int* steps, double* eta_before, double* eta_after) {
+  if (!bs) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_refine(bs->ctx, 0, max_steps, steps, eta_before, eta_after);
+}
+int ndlqr_RefineBatchAdjoint(NdLqrBatchSolver* bs, int max_steps, int* steps, double* eta_before, double* eta_after) {
+  if (!bs) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_refine(bs->ctx, 1, max_steps, steps, eta_before, eta_after);
+}
+int ndlqr_BatchKktResidualVector(NdLqrBatchSolver* bs, double* r) {
+  if (!bs || !r) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_kkt_residual_vector(bs->ctx, r);
+}
 int ndlqr_BatchSetBounds(NdLqrBatchSolver* bs, unsigned flags, const double* xlo, const double* xhi, const double* ulo,
                          const double* uhi) {
   if (!bs || (flags & ~NDLQR_BOUNDS_SHARED)) return NDLQR_ERR_INVALID;

@@ -219,6 +219,14 @@ struct NdlqrHipCtx {
   double *abox_v = nullptr, *abox_y = nullptr, *abox_resid = nullptr;
   double* abox_rhs[2] = {};
   int *abox_status = nullptr, *abox_iters = nullptr, *abox_word = nullptr;
+  // Iterative refinement (ndlqr_hip_refine, kernels_refine.hpp; allocated on first use): the double-double residual and
+  // the correction in buffers of the right-hand side's layout, the norm slots [2][9][batch] (rho, then the scale, as bit
+  // patterns), what the caller gets (steps [batch], eta before | after [2 batch]) and, under NDLQR_FLAG_PROFILE, the
+  // device time of the residual kernels | re-solves | commits of the latest call.
+  double *ref_r = nullptr, *ref_delta = nullptr, *ref_eta = nullptr;
+  unsigned long long* ref_norms = nullptr;
+  int* ref_steps = nullptr;
+  double ref_phase_ms[3] = {};
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // profile
   std::vector<PendingEvent> pending;
