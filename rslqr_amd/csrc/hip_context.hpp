@@ -6,7 +6,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ndlqr.h"
@@ -75,27 +77,6 @@ struct CapturedChain {
   }
 };
 
-// Everything a solve writes, and what orders it. The context holds two such sets: consecutive solves alternate between
-// them, each on its own stream, so that the thinly populated upper-level kernels and the HBM-bound back-substitution of
-// one solve run beside the ALU-bound bottom kernel of the next (only for schedules without cross-solve state: no factor
-// array, no kept records).
-struct BufferSet {
-  double* rec = nullptr;   // [batch][N][2 n^2 + n] separator records f_a | f_bb | z_sep (compact forms use the front of a record and its last n entries)
-  double* red = nullptr;   // accumulators of the separator-only schedules: [batch][N/4][slot] (size-specialised shapes, allocated with the set) or [batch][N/2][4 n^2 + 2 n] (runtime-sized schedule, on its first solve)
-  size_t red_bytes = 0;
-  double* ytop = nullptr;  // [batch][N/8][n] multipliers of the separators of level >= 3 (rb_backsub_top -> rb_backsub)
-  double* z = nullptr;
-  double* rhs = nullptr;   // this set's copy of the right-hand side (ndlqr_hip_step_async replaces it per step)
-  double* xfer = nullptr;  // transfer staging in HBM: flat q | r | d | x0 going up, packed [batch][nvars] coming down (allocated on first use)
-  int* tree_cnt = nullptr; // arrival counters of the separators of level >= 2, [batch][N / 4]; zero between solves (reset by the root's wavefront)
-  int* h_fail = nullptr;   // pinned host word: the batch-wide failure count, copied behind the last kernel of a solve
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  unsigned long long rhs_gen[4] = {};  // generations of this set's copy of the right-hand side (NdlqrHipCtx::rhs_latest)
-  CapturedChain graph;     // the launch sequence of a solve on this set
-  bool ready = false;      // allocated
-};
-
 // A slice of every solution: knots [knot0, knot0 + nknots), of each the blocks of `blocks` (NDLQR_SOLN_*), packed
 // [batch][nknots][width]. nknots == 0: the whole solution vectors, [batch][nvars].
 struct KnotSlice {
@@ -112,45 +93,237 @@ struct KnotSlice {
   size_t doubles(const ndlqr::Dims& u) const { return nknots > 0 ? width(u) * nknots : (size_t)u.rows * u.N - u.m; }
 };
 
-struct NdlqrHipCtx {
-  ndlqr::Dims d = {};   // block sizes of the DEVICE layout (every kernel works on these)
-  ndlqr::Dims du = {};  // the caller's block sizes: the same, or smaller when the problem runs zero-padded into the next
-                        // size-specialised instance ("padded shapes", ndlqr_hip_create); only the boundary functions see it
-  bool padded = false;
-  double* pad_stage = nullptr;  // HBM staging of caller-layout inputs / outputs of a padded shape (grown on demand)
-  size_t pad_stage_cap = 0;     // doubles
-  int device = 0;
-  unsigned flags = 0;
-  bool own_stream = true;  // the primary set's stream is the context's own (ndlqr_hip_set_stream)
-  double* AB = nullptr;
-  double* QR = nullptr;
-  double* F = nullptr;  // complete factor array; allocated by the first solve whose schedule touches it (ndlqr_hip_ensure_F)
+// (internal to the library: no inline member of the owners, the feature structs and the context is an exported symbol)
+#pragma GCC visibility push(hidden)
+
+// ------------------------------------------------------------------------------ owned memory
+// The two owners of the host layer's memory: DevBuf<T> (hipMalloc) and PinnedBuf<T> (hipHostMalloc). Move-only, freed by
+// the destructor; they convert to T*, so kernel argument lists and pointer arithmetic read as with a raw pointer.
+template <class T, bool PINNED>
+class OwnedBuf {
+  T* p_ = nullptr;
+  size_t n_ = 0;  // capacity, elements
+
+ public:
+  OwnedBuf() = default;
+  OwnedBuf(const OwnedBuf&) = delete;
+  OwnedBuf& operator=(const OwnedBuf&) = delete;
+  OwnedBuf(OwnedBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+  OwnedBuf& operator=(OwnedBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; }  // (o frees the old one)
+  ~OwnedBuf() { reset(); }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  size_t count() const { return n_; }
+  void reset() {
+    if (p_) (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+    p_ = nullptr; n_ = 0;
+  }
+  // first-use buffers of a fixed size: allocated when empty, left alone otherwise
+  hipError_t ensure(size_t count) {
+    if (p_) return hipSuccess;
+    const hipError_t e = PINNED ? hipHostMalloc((void**)&p_, sizeof(T) * count, hipHostMallocDefault)
+                                : hipMalloc((void**)&p_, sizeof(T) * count);
+    if (e != hipSuccess) p_ = nullptr;
+    else n_ = count;
+    return e;
+  }
+  // ... zero-filled at that allocation (device memory: on `st`, ordered before whatever that stream runs next)
+  hipError_t ensure_zeroed(size_t count, hipStream_t st = nullptr) {
+    if (p_) return hipSuccess;
+    const hipError_t e = ensure(count);
+    if (e != hipSuccess) return e;
+    if (PINNED) { memset(p_, 0, sizeof(T) * count); return hipSuccess; }
+    return hipMemsetAsync(p_, 0, sizeof(T) * count, st);
+  }
+  // room for `count` elements: freed and allocated again when too small (the old contents go)
+  hipError_t grow(size_t count) {
+    if (count <= n_) return hipSuccess;
+    reset();
+    return ensure(count);
+  }
+};
+template <class T> using DevBuf = OwnedBuf<T, false>;
+template <class T> using PinnedBuf = OwnedBuf<T, true>;
+
+// doubles of the device arrays every feature sizes its buffers by
+static inline size_t doubles_QR(const ndlqr::Dims& d) { return (size_t)d.batch * d.N * d.w; }
+static inline size_t doubles_z(const ndlqr::Dims& d) { return (size_t)d.batch * d.N * d.rows; }
+static inline size_t doubles_F(const ndlqr::Dims& d) { return (size_t)d.batch * d.K * d.N * d.fb; }
+// first error of a list of allocations
+static inline hipError_t first_error(std::initializer_list<hipError_t> list) {
+  for (const hipError_t e : list) if (e != hipSuccess) return e;
+  return hipSuccess;
+}
+
+// Everything a solve writes, and what orders it. The context holds two such sets: consecutive solves alternate between
+// them, each on its own stream, so that the thinly populated upper-level kernels and the HBM-bound back-substitution of
+// one solve run beside the ALU-bound bottom kernel of the next (only for schedules without cross-solve state: no factor
+// array, no kept records).
+struct BufferSet {
+  DevBuf<double> rec;   // [batch][N][2 n^2 + n] separator records f_a | f_bb | z_sep (compact forms use the front of a record and its last n entries)
+  DevBuf<double> red;   // accumulators of the separator-only schedules: [batch][N/4][slot] (size-specialised shapes, allocated with the set) or [batch][N/2][4 n^2 + 2 n] (runtime-sized schedule, on its first solve)
+  DevBuf<double> ytop;  // [batch][N/8][n] multipliers of the separators of level >= 3 (rb_backsub_top -> rb_backsub)
+  DevBuf<double> z;
+  DevBuf<double> rhs;   // this set's copy of the right-hand side (ndlqr_hip_step_async replaces it per step)
+  DevBuf<double> xfer;  // transfer staging in HBM: flat q | r | d | x0 going up, packed [batch][nvars] coming down (allocated on first use)
+  DevBuf<int> tree_cnt; // arrival counters of the separators of level >= 2, [batch][N / 4]; zero between solves (reset by the root's wavefront)
+  PinnedBuf<int> h_fail;  // pinned host word: the batch-wide failure count, copied behind the last kernel of a solve
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  unsigned long long rhs_gen[4] = {};  // generations of this set's copy of the right-hand side (NdlqrHipCtx::rhs_latest)
+  CapturedChain graph;     // the launch sequence of a solve on this set
+  bool ready = false;      // allocated
+  // `u`: the caller's block sizes (caller-layout data: max(flat right-hand side, packed solutions) doubles)
+  hipError_t ensure_xfer(const ndlqr::Dims& u) { return xfer.ensure((size_t)u.batch * u.N * u.rows + (size_t)u.batch * u.n); }
+};
+
+// ------------------------------------------------------------------------------ one struct per feature
+// The state of an optional feature: its buffers with their layout, its bookkeeping, and one ensure() that names the
+// buffers and their sizes once (d: the device layout, st: the stream a zero-fill is ordered on). The entry point that
+// first needs the feature calls it; the buffers go with the context. A new feature adds its struct here, a member to
+// NdlqrHipCtx and the ensure() call to its entry points -- nothing else.
+
+// Developer switches of the environment, read once when the context is created (read_knobs, ndlqr_hip.hip)
+struct DevKnobs {
   int rowbcast = -1;  // bottom levels of the separator-only schedule on the row-broadcast core (rb_bottom): NDLQR_ROWBCAST=1 always, 0 never (bottom_reduced_mc), unset (-1): by block size
   int tree = -1;  // tree schedule (bottom_reduced_mc<TREE>: one launch for the whole factorisation, wavefronts climbing on arrival counters): NDLQR_TREE=1 always, 0 never, unset (-1): when all bottom wavefronts are resident at once (small batches: fewer launches win; large ones: a launch per level is faster)
   int backsub_cols = -1;  // rb_backsub at nstates + ninputs <= 16: the body with [A | B] in registers (rb_backsub_cols, block 128) unless NDLQR_BACKSUB_COLS=0 asks for the LDS-staged one
   int fuse2 = -1;  // tree level 2 inside the bottom launch (bottom8_reduced_mc) instead of as a launch of its own: NDLQR_FUSE2=1 always, 0 never, unset (-1): where it measured faster -- the (12,4) instance (launch_small.hpp)
-  BufferSet set[2];     // the two-deep solve pipeline: [0] the primary set, [1] the alternate (allocated on first use)
-  int cur = 0;          // the set the next launches go to
-  int latest = 0;       // the set holding the most recent solution
-  int pipeline = 2;     // 1: stream-ordered solves; 2 (default, NDLQR_PIPELINE): consecutive solves alternate sets
-  unsigned solve_count = 0;  // solves enqueued so far (parity picks the set)
-  bool state_dirty = false;  // a solve failed to launch or to complete: counters / failure words are zeroed before the next one
-  int fail_base = 0;         // value of the (cumulative) batch-wide failure counter at the last synchronisation
-  int* info = nullptr;
-  KeptState kept;  // of the latest solve
-  double* kkt_out = nullptr;  // [2 batch] scratch of ndlqr_hip_kkt_residual (allocated on first use)
-  // several right-hand sides per problem (ndlqr_hip_solve_multi_rhs): buffers for `multi_cap` right-hand sides, grown on demand
-  size_t multi_cap = 0;
-  double *multi_rhs = nullptr, *multi_z = nullptr, *multi_zsep = nullptr, *multi_fsum = nullptr, *multi_ytop = nullptr,
-         *multi_in = nullptr, *multi_out = nullptr;
-  double* sep_scratch = nullptr;  // S-bar and panel of every level-0 separator in global memory: blocks beyond the LDS of separator_generic (allocated on first use)
-  double* h_stage[2] = {};  // pinned bounce buffers of the downloads into pageable host memory (allocated on first use)
+  int pipeline = 2;         // NDLQR_PIPELINE: the pipeline depth a context starts with (NdlqrHipCtx::pipeline)
   bool no_top = false;      // NDLQR_NO_TOP=1: the last three tree levels as launches of their own (A/B timing of reduced_top_mc)
   int top_levels = 3;       // tree levels inside reduced_top_mc (NDLQR_TOP_LEVELS, 3 .. 5): beyond three a wavefront takes several separators of the first ones in turn
   bool no_mfma = false;     // NDLQR_NO_MFMA=1: keep the scalar Schur kernel for large blocks (A/B timing)
   int sep_threads = 0;        // NDLQR_SEP_THREADS: workgroup size of the matrix-core separator (0 = by block size)
   int mult_threads = 0;       // NDLQR_MULT_THREADS: workgroup size of backsub_multipliers_compact (0 = by block size)
   bool no_reduced_generic = false;  // NDLQR_DEV_NO_REDUCED_GENERIC (developer): A/B against the knot-based runtime-sized schedule
+  bool no_pad = false;        // NDLQR_NO_PAD=1: the caller's block size on the device (A/B, tests)
+  bool alt_priority_set = false;  // NDLQR_ALT_PRIORITY: stream priority of the alternate buffer set (unset: the greatest)
+  int alt_priority = 0;
+};
+
+// Adjoint solve and parameter gradients (ndlqr_hip_solve_adjoint / ndlqr_hip_gradients): the adjoint right-hand side
+// and its solution w in buffers of their own, [batch][N][2n+m], so that the primal state stays as it is. gen: the
+// resident solution (NdlqrHipCtx::soln_gen) the adjoint belongs to (0: none).
+struct AdjointState {
+  DevBuf<double> rhs, z;
+  DevBuf<double> save;  // right-hand-side columns of the kept records / slots, saved around a re-solve that is not the primal's
+  unsigned long long gen = 0;
+  hipError_t ensure_save(const ndlqr::Dims& d) { return save.ensure(2 * (size_t)d.batch * d.N * d.n); }
+  hipError_t ensure(const ndlqr::Dims& d, hipStream_t st) {
+    // (z zeroed: the entries a re-solve does not write, the pad rows)
+    return first_error({rhs.ensure(doubles_z(d)), z.ensure_zeroed(doubles_z(d), st), ensure_save(d)});
+  }
+};
+
+// Box-constrained solve by ADMM (ndlqr_hip_set_bounds / ndlqr_hip_solve_box, kernels_box.hpp). Bounds lo | hi in the
+// device layout [batch][N][n+m] ([N][n+m] when shared: bstride 0) and their bounded pattern; v, y and two ADMM
+// right-hand sides (ping-pong) and the re-solve's z; per problem status, iterations and residuals; rho: the penalty of
+// every problem [batch]; word: running count | problems whose penalty changed | lo > hi | pattern changed (h_word: the
+// same four, then the box adjoint's running count). The shifted factorisation is remembered (fact) with its penalties --
+// rho, and rho_value when rho_uniform says they are all that one value -- and what the plain API's kept state was after
+// it (kept), so that the next constrained solve may skip factoring. soln_gen: the solution generation the latest
+// constrained solve left (0: none since the bounds were set).
+struct BoxState {
+  DevBuf<double> lo, hi, v, y, z, qr_save, rhs[2], resid, rho;
+  DevBuf<unsigned char> mask;
+  DevBuf<int> status, iters, word;
+  PinnedBuf<int> h_word;
+  bool shared = false, have_bounds = false, have_vy = false;
+  size_t bstride = 0;      // doubles between the bounds of consecutive problems (0: shared)
+  bool fact = false;       // the kept records / factors are those of QR + rho M of the current bounds pattern
+  bool rho_uniform = false;
+  double rho_value = 0.0;
+  unsigned flags = 0;      // the flags of that factorisation
+  KeptState kept;          // ... and what it left
+  unsigned long long soln_gen = 0;
+  hipError_t ensure(const ndlqr::Dims& d, hipStream_t st) {
+    const size_t nz = doubles_z(d), nv = doubles_QR(d), nb = (size_t)d.batch;  // (bounds: room for per-problem ones, shared or not)
+    return first_error({mask.ensure_zeroed(nv, st), lo.ensure(nv), hi.ensure(nv), word.ensure(4), h_word.ensure(5),
+                        z.ensure_zeroed(nz, st),  // (entries a re-solve does not write: the pad rows)
+                        v.ensure(nv), y.ensure(nv), qr_save.ensure(nv), rhs[0].ensure(nz), rhs[1].ensure(nz),
+                        resid.ensure(2 * nb), status.ensure(nb), iters.ensure(nb), rho.ensure(nb)});
+  }
+};
+
+// Gradients through the box-constrained solve (ndlqr_hip_solve_box_adjoint / ndlqr_hip_bound_gradients,
+// kernels_box_grad.hpp). gen: the solution generation the box adjoint belongs to (0: none). The adjoint's own entry
+// codes, v, y, ADMM right-hand sides (its resident one is adj.rhs, its solution adj.z), per problem status, iterations
+// and residuals, and its running count: nothing of the forward's iteration state is touched.
+struct BoxAdjointState {
+  DevBuf<unsigned char> code;
+  DevBuf<double> v, y, resid, rhs[2];
+  DevBuf<int> status, iters, word;
+  unsigned long long gen = 0;
+  hipError_t ensure(const ndlqr::Dims& d) {
+    const size_t nz = doubles_z(d), nv = doubles_QR(d), nb = (size_t)d.batch;
+    return first_error({code.ensure(nv), v.ensure(nv), y.ensure(nv), rhs[0].ensure(nz), rhs[1].ensure(nz),
+                        resid.ensure(2 * nb), status.ensure(nb), iters.ensure(nb), word.ensure(1)});
+  }
+};
+
+// Iterative refinement (ndlqr_hip_refine, kernels_refine.hpp): the double-double residual and the correction in buffers
+// of the right-hand side's layout, the norm slots [2][kRefineMaxSteps + 1][batch] (rho, then the scale, as bit patterns),
+// what the caller gets (steps [batch], eta before | after [2 batch]) and, under NDLQR_FLAG_PROFILE, the device time of
+// the residual kernels | re-solves | commits of the latest call.
+constexpr int kRefineMaxSteps = 8;
+struct RefineState {
+  DevBuf<double> r, delta, eta;
+  DevBuf<unsigned long long> norms;
+  DevBuf<int> steps;
+  double phase_ms[3] = {};
+  static size_t norm_count(const ndlqr::Dims& d) { return 2 * (kRefineMaxSteps + 1) * (size_t)d.batch; }
+  hipError_t ensure_r(const ndlqr::Dims& d) { return r.ensure(doubles_z(d)); }  // (ndlqr_hip_kkt_residual_vector: the residual alone)
+  hipError_t ensure(const ndlqr::Dims& d, hipStream_t st) {
+    return first_error({ensure_r(d), norms.ensure(norm_count(d)), steps.ensure((size_t)d.batch), eta.ensure(2 * (size_t)d.batch),
+                        delta.ensure_zeroed(doubles_z(d), st)});  // (entries a re-solve does not write: the pad rows)
+  }
+};
+
+// Several right-hand sides per problem (ndlqr_hip_solve_multi_rhs): buffers for `cap` right-hand sides ([cap] of the
+// right-hand side, the solution, z_sep, the pushed sums and the top multipliers; the caller-layout inputs and packed
+// solutions), grown on demand
+struct MultiRhsState {
+  DevBuf<double> rhs, z, zsep, fsum, ytop, in, out;
+  // (u: the caller's block sizes. Padded shapes: the pad entries of rhs and z are zero and stay zero -- the pack kernel
+  //  never touches them)
+  hipError_t ensure(const ndlqr::Dims& d, const ndlqr::Dims& u, size_t cap, hipStream_t st) {
+    const size_t nz = cap * d.N * d.rows;
+    if (rhs.count() >= nz) return hipSuccess;
+    hipError_t e = first_error({rhs.grow(nz), z.grow(nz), zsep.grow(cap * d.N * d.n), fsum.grow(cap * (d.N / 8) * 2 * d.n),
+                                ytop.grow(cap * (d.N / 8) * d.n), in.grow(cap * ((size_t)u.N * (2 * u.n + u.m) + u.n)),
+                                out.grow(cap * ((size_t)u.rows * u.N - u.m))});
+    if (e == hipSuccess) e = first_error({hipMemsetAsync(rhs, 0, sizeof(double) * nz, st), hipMemsetAsync(z, 0, sizeof(double) * nz, st)});
+    if (e != hipSuccess)
+      for (DevBuf<double>* b : {&rhs, &z, &zsep, &fsum, &ytop, &in, &out}) b->reset();
+    return e;
+  }
+};
+
+struct NdlqrHipCtx {
+  ndlqr::Dims d = {};   // block sizes of the DEVICE layout (every kernel works on these)
+  ndlqr::Dims du = {};  // the caller's block sizes: the same, or smaller when the problem runs zero-padded into the next
+                        // size-specialised instance ("padded shapes", ndlqr_hip_create); only the boundary functions see it
+  bool padded = false;
+  int device = 0;
+  unsigned flags = 0;
+  DevKnobs knobs;
+  bool own_stream = true;  // the primary set's stream is the context's own (ndlqr_hip_set_stream)
+  DevBuf<double> AB, QR;
+  DevBuf<double> F;  // complete factor array; allocated by the first solve whose schedule touches it (ndlqr_hip_ensure_F)
+  DevBuf<int> info;
+  DevBuf<double> pad_stage;    // HBM staging of caller-layout inputs / outputs of a padded shape (grow_pad_stage)
+  DevBuf<double> grad_stage;   // HBM staging of the host outputs / inputs of the gradient and bounds functions and their partial batch sums (grown on demand)
+  DevBuf<double> kkt_out;      // [2 batch] scratch of ndlqr_hip_kkt_residual (allocated on first use)
+  DevBuf<double> sep_scratch;  // S-bar and panel of every level-0 separator in global memory: blocks beyond the LDS of separator_generic (allocated on first use)
+  PinnedBuf<double> h_stage[2];  // bounce buffers of the downloads into pageable host memory (allocated on first use)
+  BufferSet set[2];     // the two-deep solve pipeline: [0] the primary set, [1] the alternate (allocated on first use)
+  int cur = 0;          // the set the next launches go to
+  int latest = 0;       // the set holding the most recent solution
+  int pipeline = 2;     // 1: stream-ordered solves; 2 (default, DevKnobs::pipeline): consecutive solves alternate sets
+  unsigned solve_count = 0;  // solves enqueued so far (parity picks the set)
+  bool state_dirty = false;  // a solve failed to launch or to complete: counters / failure words are zeroed before the next one
+  int fail_base = 0;         // value of the (cumulative) batch-wide failure counter at the last synchronisation
+  KeptState kept;  // of the latest solve
   hipEvent_t ev_step[2] = {};  // end of the steps of ndlqr_hip_step_async, alternating (ndlqr_hip_synchronize_previous)
   unsigned step_count = 0;
   hipEvent_t ev_inputs = nullptr;  // orders the other buffer set's stream behind a device-side replacement of the inputs
@@ -173,67 +346,37 @@ struct NdlqrHipCtx {
   // One-shot solve of a small batch from / into pinned host staging (ndlqr_hip_solve_staged; the drop-in ndlqr_Solve):
   // AB | QR | rhs going up, the solution blocks [batch][N][2n+m] coming down, all in the caller's block size; the whole
   // sequence -- three copies up, the launch chain, the copy down -- is ONE captured graph.
-  double* h_io = nullptr;  // pinned: AB | QR | rhs | z
+  PinnedBuf<double> h_io;  // AB | QR | rhs | z
   CapturedChain staged;
   bool timing_pending = false;
   double last_ms = 0;
   int last_failures = 0;
-  // Adjoint solve and parameter gradients (ndlqr_hip_solve_adjoint / ndlqr_hip_gradients): the adjoint right-hand side
-  // and its solution w in buffers of their own, [batch][N][2n+m] (allocated on first use), so that the primal state stays
-  // as it is. soln_gen counts the resident solutions (note_solution); adj_gen is the one the adjoint belongs to (0: none).
-  double* adj_rhs = nullptr;
-  double* adj_z = nullptr;
-  double* adj_save = nullptr;    // right-hand-side columns of the kept records / slots, saved around the adjoint re-solve
-  double* grad_stage = nullptr;  // HBM staging of the host outputs / inputs and the partial batch sums (grown on demand)
-  size_t grad_stage_cap = 0;     // doubles
-  unsigned long long soln_gen = 0, adj_gen = 0;
-  bool inputs_replaced = false;  // new A, B, Q, R since the last solve
-  // Box-constrained solve by ADMM (ndlqr_hip_set_bounds / ndlqr_hip_solve_box, kernels_box.hpp; buffers allocated on first
-  // use). Bounds lo | hi in the device layout [batch][N][n+m] ([N][n+m] when shared: box_bstride 0) and their bounded
-  // pattern; v, y and two ADMM right-hand sides (ping-pong) and the re-solve's z; per problem status, iterations and
-  // residuals; box_rho: the penalty of every problem [batch]; box_word: running count | problems whose penalty changed |
-  // lo > hi | pattern changed (h_box_word: the same four, then the box adjoint's running count). The shifted
-  // factorisation is remembered (box_fact) with its penalties -- box_rho, and box_rho_value when box_rho_uniform says
-  // they are all that one value -- and what the plain API's kept state was after it (box_kept), so that the next constrained
-  // solve may skip factoring.
-  double *box_lo = nullptr, *box_hi = nullptr, *box_v = nullptr, *box_y = nullptr, *box_z = nullptr, *box_qr_save = nullptr;
-  double* box_rhs[2] = {};
-  double *box_resid = nullptr, *box_rho = nullptr;
-  unsigned char* box_mask = nullptr;
-  int *box_status = nullptr, *box_iters = nullptr, *box_word = nullptr;
-  int* h_box_word = nullptr;   // pinned
-  bool box_shared = false, box_have_bounds = false, box_have_vy = false;
-  size_t box_bstride = 0;      // doubles between the bounds of consecutive problems (0: shared)
-  bool box_fact = false;       // the kept records / factors are those of QR + rho M of the current bounds pattern
-  bool box_rho_uniform = false;
-  double box_rho_value = 0.0;
-  unsigned box_flags = 0;      // the flags of that factorisation
-  KeptState box_kept;          // ... and what it left
-  // Gradients through the box-constrained solve (ndlqr_hip_solve_box_adjoint / ndlqr_hip_bound_gradients,
-  // kernels_box_grad.hpp; allocated on first use). box_soln_gen: the solution generation the latest constrained solve
-  // left (0: none since the bounds were set); abox_gen: the one the box adjoint belongs to (0: none). The adjoint's own
-  // entry codes, v, y, ADMM right-hand sides (its resident one is adj_rhs, its solution adj_z), per problem status,
-  // iterations and residuals, and its running count: nothing of the forward's iteration state is touched.
-  unsigned long long box_soln_gen = 0, abox_gen = 0;
-  unsigned char* abox_code = nullptr;
-  double *abox_v = nullptr, *abox_y = nullptr, *abox_resid = nullptr;
-  double* abox_rhs[2] = {};
-  int *abox_status = nullptr, *abox_iters = nullptr, *abox_word = nullptr;
-  // Iterative refinement (ndlqr_hip_refine, kernels_refine.hpp; allocated on first use): the double-double residual and
-  // the correction in buffers of the right-hand side's layout, the norm slots [2][9][batch] (rho, then the scale, as bit
-  // patterns), what the caller gets (steps [batch], eta before | after [2 batch]) and, under NDLQR_FLAG_PROFILE, the
-  // device time of the residual kernels | re-solves | commits of the latest call.
-  double *ref_r = nullptr, *ref_delta = nullptr, *ref_eta = nullptr;
-  unsigned long long* ref_norms = nullptr;
-  int* ref_steps = nullptr;
-  double ref_phase_ms[3] = {};
+  unsigned long long soln_gen = 0;  // counts the resident solutions (note_solution)
+  bool inputs_replaced = false;     // new A, B, Q, R since the last solve
+  // the optional features, each with its buffers (allocated on first use by its ensure())
+  AdjointState adj;
+  BoxState box;
+  BoxAdjointState abox;
+  RefineState ref;
+  MultiRhsState multi;
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // profile
   std::vector<PendingEvent> pending;
   std::vector<hipEvent_t> event_pool;
   double slot_ms[SLOT_COUNT] = {};
   int slot_launches[SLOT_COUNT] = {};
+  // Room for `doubles` in pad_stage. Growing waits for the current set's stream, which may still read the old array, and
+  // drops the staged graph, which holds its address.
+  hipError_t grow_pad_stage(size_t doubles) {
+    if (doubles <= pad_stage.count()) return hipSuccess;
+    const hipError_t e = pad_stage ? hipStreamSynchronize(set[cur].stream) : hipSuccess;
+    if (e != hipSuccess) return e;
+    staged.reset();
+    return pad_stage.grow(doubles);
+  }
 };
+
+#pragma GCC visibility pop
 
 static inline hipEvent_t take_event(NdlqrHipCtx* c) {
   if (!c->event_pool.empty()) {

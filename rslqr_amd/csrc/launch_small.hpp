@@ -59,9 +59,9 @@ static inline ndlqr::Dims apply_dims(const NdlqrHipCtx* c, const ndlqr::Dims& d)
 // (12,4), (10,4), (9,3), (8,4), (6,3) x 1024 and (12,4,1024) x 512, faster at each -- and,
 // with NDLQR_BACKSUB_COLS=0, the LDS-staged one that the larger instances run.
 template <int NX, int NU, bool MULTI, class... Args>
-static void launch_rb_backsub(const NdlqrHipCtx* c, const dim3 grid, hipStream_t stream, Args... args) {
+static void launch_rb_backsub(const NdlqrHipCtx* c, const dim3 grid, hipStream_t stream, const Args&... args) {
   if constexpr (NX + NU <= 16) {
-    if (c->backsub_cols != 0) {
+    if (c->knobs.backsub_cols != 0) {
       hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, MULTI, true>), grid, dim3(ndlqr::kRbBacksubColsThreads), 0, stream, args...);
       return;
     }
@@ -90,7 +90,7 @@ static SmallPlan plan_small(const NdlqrHipCtx* c, const bool strict, const bool 
       p.reduced = true;
       // tree schedule for small batches (at most half a resident round of bottom wavefronts): three
       // launches instead of K + 1; measured cross-over at batch x N / 4 ~ 4096 wavefronts
-      p.tree = s.tree_cnt && (c->tree == 1 || (c->tree < 0 && (size_t)d.batch * (d.N >> 2) <= 2048));
+      p.tree = s.tree_cnt && (c->knobs.tree == 1 || (c->knobs.tree < 0 && (size_t)d.batch * (d.N >> 2) <= 2048));
       // compact level-0 records (L of S-bar only) and the two-launch back-substitution: the tree schedule keeps the
       // one-kernel back-substitution; rb_backsub's thread roles need 8 (2 nx + nu) <= 256 (and rb_backsub_top's sweep
       // array, N / 8 multipliers, has to fit the LDS of its one workgroup per problem). With KEEP_RECORDS (round 4): the
@@ -107,22 +107,22 @@ static SmallPlan plan_small(const NdlqrHipCtx* c, const bool strict, const bool 
       // (10,4) 0.230 vs 0.271, (12,4) 0.301 vs 0.290 in round 2. Round 3 (paired Cholesky pass that carries the panel):
       // (10,4) 0.230 vs 0.207, (9,3) 0.203 vs 0.187, (8,4) 0.143 vs 0.152, (6,3) 0.104 vs 0.134 -- so it serves n <= 8
       // (NDLQR_ROWBCAST=0/1 overrides)
-      p.rowbcast = p.compact && !p.store_l && NX <= 16 && NX + NU <= 16 && (c->rowbcast == 1 || (c->rowbcast < 0 && NX <= 8));
+      p.rowbcast = p.compact && !p.store_l && NX <= 16 && NX + NU <= 16 && (c->knobs.rowbcast == 1 || (c->knobs.rowbcast < 0 && NX <= 8));
       // Levels 0-2 in one launch (bottom8_reduced_mc: two wavefronts per eight knots, the level-2 slot in LDS): 12 % less
       // HBM traffic and one launch less per step; the level-2 work costs inside the bottom launch about what it costs
       // outside, so the step gains little -- and only at the (12,4) instance, where it is the default (same box,
       // profiles/r04_fuse2_ab.txt: (12,4,256) x 1024 0.587 -> 0.579 ms, (12,4,1024) x 512 1.20 -> 1.16, the padded (11,3)
       // 0.578 -> 0.569; (12,8) +2.5 %, (13,4) +0.9 %, (9,3) / (10,4) / (15,2) +-0). NDLQR_FUSE2=0 / 1 overrides.
-      p.fuse2 = !p.rowbcast && p.compact && !p.store_l && (c->fuse2 > 0 || (c->fuse2 < 0 && NX == 12 && NU == 4));
+      p.fuse2 = !p.rowbcast && p.compact && !p.store_l && (c->knobs.fuse2 > 0 || (c->knobs.fuse2 < 0 && NX == 12 && NU == 4));
       p.schedule = p.tree ? "reduced-tree"
                    : !p.compact ? "reduced-records"
                    : p.store_l ? "reduced-compact-records" : (p.fuse2 ? "reduced-fused2" : "reduced");
       if (!p.tree) {
         // upper levels: one launch per level while a level has more than four separators per problem, then the
         // last three levels in one launch (reduced_top_mc; NDLQR_NO_TOP=1: a launch per level to the root)
-        const int top_levels = d.K - c->top_levels >= 3 ? c->top_levels : 3;
+        const int top_levels = d.K - c->knobs.top_levels >= 3 ? c->knobs.top_levels : 3;
         p.level0 = p.fuse2 ? 3 : 2;
-        p.ltop = (d.K >= 5 && !c->no_top) ? d.K - top_levels : d.K;
+        p.ltop = (d.K >= 5 && !c->knobs.no_top) ? d.K - top_levels : d.K;
         p.top_l0 = (p.fuse2 && p.ltop < 3) ? 3 : p.ltop;  // (level 2 went with the bottom launch)
         // ... which also runs the top-down sweep over the records of level >= 3 when the back-substitution is the
         // two-launch form and its array fits the workgroup's LDS

@@ -6,9 +6,7 @@
 // Written for wave64 / gfx950 only; built with -ffp-contract=off so that every fused
 // multiply-add in the kernels is an explicit fma() (fast mode) or an explicit mul + add
 // (NDLQR_FLAG_STRICT_FP, which reproduces the reference's default CPU build bit for bit).
-#include <initializer_list>
 #include <mutex>
-#include <utility>
 
 #include "hip_context.hpp"
 #include "kernels_generic.hpp"
@@ -63,33 +61,48 @@ static const char* kSlotNames[SLOT_COUNT] = {"leaf", "separator", "schur", "schu
 static bool has_small_instance(int nstates, int ninputs);  // defined with the instance table below
 static void pick_pad_instance(int nstates, int ninputs, int* pn, int* pm);
 
-static size_t bytes_AB(const ndlqr::Dims& d) { return sizeof(double) * (size_t)d.batch * d.N * d.n * d.w; }
-static size_t bytes_QR(const ndlqr::Dims& d) { return sizeof(double) * (size_t)d.batch * d.N * d.w; }
-static size_t bytes_z(const ndlqr::Dims& d) { return sizeof(double) * (size_t)d.batch * d.N * d.rows; }
-static size_t bytes_rec(const ndlqr::Dims& d) { return sizeof(double) * (size_t)d.batch * d.N * (2 * d.n * d.n + d.n); }
-static size_t bytes_F(const ndlqr::Dims& d) { return sizeof(double) * (size_t)d.batch * d.K * d.N * d.fb; }
+static size_t bytes_QR(const ndlqr::Dims& d) { return sizeof(double) * doubles_QR(d); }
+static size_t bytes_z(const ndlqr::Dims& d) { return sizeof(double) * doubles_z(d); }
+static size_t bytes_F(const ndlqr::Dims& d) { return sizeof(double) * doubles_F(d); }
+
+// Every getenv of the context: the developer switches, read once per context
+static DevKnobs read_knobs() {
+  DevKnobs k;
+  const auto num = [](const char* name, int* v) { if (getenv(name)) *v = atoi(getenv(name)); };
+  const auto onoff = [](const char* name, int* v) { if (getenv(name)) *v = atoi(getenv(name)) != 0 ? 1 : 0; };
+  num("NDLQR_PIPELINE", &k.pipeline);
+  onoff("NDLQR_TREE", &k.tree);                  // unset: by batch size
+  onoff("NDLQR_ROWBCAST", &k.rowbcast);          // unset: by block size
+  onoff("NDLQR_FUSE2", &k.fuse2);                // unset: by instance (launch_small)
+  onoff("NDLQR_BACKSUB_COLS", &k.backsub_cols);
+  k.no_mfma = getenv("NDLQR_NO_MFMA") != nullptr;
+  k.no_top = getenv("NDLQR_NO_TOP") != nullptr;
+  num("NDLQR_TOP_LEVELS", &k.top_levels);
+  if (k.top_levels < 3 || k.top_levels > 5) k.top_levels = 3;
+  num("NDLQR_SEP_THREADS", &k.sep_threads);
+  num("NDLQR_MULT_THREADS", &k.mult_threads);
+  k.no_reduced_generic = getenv("NDLQR_DEV_NO_REDUCED_GENERIC") != nullptr;
+  k.no_pad = getenv("NDLQR_NO_PAD") != nullptr;
+  k.alt_priority_set = getenv("NDLQR_ALT_PRIORITY") != nullptr;
+  num("NDLQR_ALT_PRIORITY", &k.alt_priority);
+  return k;
+}
 
 // What both buffer sets allocate alike, on the set's stream (created by the caller): events, records, solution, its copy of
 // the right-hand side, failure word; with `slots` (size-specialised shapes) the accumulator slots, the multipliers of the
 // top separators and the arrival counters (the runtime-sized schedule's slots: ensure_red_generic)
 static bool alloc_set(NdlqrHipCtx* c, BufferSet& s, bool slots) {
   const ndlqr::Dims& d = c->d;
-  bool ok = hipEventCreate(&s.ev_start) == hipSuccess && hipEventCreate(&s.ev_stop) == hipSuccess &&
-            hipMalloc(&s.rec, bytes_rec(d)) == hipSuccess && hipMalloc(&s.z, bytes_z(d)) == hipSuccess &&
-            hipMalloc(&s.rhs, bytes_z(d)) == hipSuccess &&
-            hipHostMalloc((void**)&s.h_fail, sizeof(int), hipHostMallocDefault) == hipSuccess;
-  if (ok) *s.h_fail = 0;
-  if (ok && slots) {
+  hipError_t e = first_error({hipEventCreate(&s.ev_start), hipEventCreate(&s.ev_stop), s.rec.ensure((size_t)d.batch * d.N * (2 * d.n * d.n + d.n)),
+                              s.rhs.ensure(doubles_z(d)), s.h_fail.ensure_zeroed(1)});
+  if (e == hipSuccess && slots) {
     // slot = DL | DR (packed lower triangles) | CA | CB | gL | gR, padded to whole 128-byte lines (RedSlot<NX>::SIZE)
     const size_t slot_doubles = ((size_t)d.n * (d.n + 1) + 2 * (size_t)d.n * d.n + 2 * d.n + 15) / 16 * 16;
-    const size_t red_bytes = sizeof(double) * (size_t)d.batch * (d.N / 4) * slot_doubles;
-    const size_t cnt_bytes = sizeof(int) * (size_t)d.batch * (d.N / 4);
-    ok = hipMalloc(&s.red, red_bytes) == hipSuccess && hipMemsetAsync(s.red, 0, red_bytes, s.stream) == hipSuccess &&
-         hipMalloc(&s.ytop, sizeof(double) * (size_t)d.batch * (d.N / 8) * d.n) == hipSuccess &&
-         hipMalloc(&s.tree_cnt, cnt_bytes) == hipSuccess && hipMemsetAsync(s.tree_cnt, 0, cnt_bytes, s.stream) == hipSuccess;
-    if (ok) s.red_bytes = red_bytes;
+    e = first_error({s.red.ensure_zeroed((size_t)d.batch * (d.N / 4) * slot_doubles, s.stream),
+                     s.ytop.ensure((size_t)d.batch * (d.N / 8) * d.n),
+                     s.tree_cnt.ensure_zeroed((size_t)d.batch * (d.N / 4), s.stream)});
   }
-  return ok && hipMemsetAsync(s.z, 0, bytes_z(d), s.stream) == hipSuccess;
+  return e == hipSuccess && s.z.ensure_zeroed(doubles_z(d), s.stream) == hipSuccess;
 }
 
 NdlqrHipCtx* ndlqr_hip_create(int nstates, int ninputs, int nhorizon, int batch, int device) {
@@ -122,6 +135,8 @@ NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int bat
   if ((e = hipSetDevice(device)) != hipSuccess) { fail("hipSetDevice", e); return nullptr; }
 
   NdlqrHipCtx* c = new NdlqrHipCtx();
+  c->knobs = read_knobs();
+  c->pipeline = c->knobs.pipeline;
   ndlqr::Dims& d = c->d;
   auto set_dims = [&](ndlqr::Dims& x, int n_, int m_) {
     x.n = n_; x.m = m_; x.N = nhorizon; x.batch = batch;
@@ -134,46 +149,31 @@ NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int bat
   // real variables see the same arithmetic plus exact zeros) instead of the runtime-sized kernels, which are 3-4x
   // slower below 16 states. NDLQR_NO_PAD=1 keeps the caller's block size (A/B, tests).
   int pn = nstates, pm = ninputs;
-  if (!has_small_instance(nstates, ninputs) && nhorizon >= 8 && !getenv("NDLQR_NO_PAD") &&
-      !(create_flags & NDLQR_CREATE_NO_PAD))
+  const bool may_pad = !c->knobs.no_pad && !(create_flags & NDLQR_CREATE_NO_PAD);
+  if (!has_small_instance(nstates, ninputs) && nhorizon >= 8 && may_pad)
     pick_pad_instance(nstates, ninputs, &pn, &pm);
   // ... and beyond 128 states (the knot-based kernels: launch_generic) a block that does not fill 16 x 16 tiles is padded
   // to the next one that does: separator_mfma instead of separator_generic, 3-7x faster there (round 4)
-  if (nstates > 128 && (nstates % 16 != 0 || (nstates + ninputs) % 4 != 0) && !getenv("NDLQR_NO_PAD") &&
-      !(create_flags & NDLQR_CREATE_NO_PAD)) {
+  if (nstates > 128 && (nstates % 16 != 0 || (nstates + ninputs) % 4 != 0) && may_pad) {
     pn = (nstates + 15) / 16 * 16;
     pm = ninputs + (4 - (pn + ninputs) % 4) % 4;
   }
   set_dims(d, pn, pm);
   c->padded = pn != nstates || pm != ninputs;
   c->device = device;
-  if (getenv("NDLQR_PIPELINE")) c->pipeline = atoi(getenv("NDLQR_PIPELINE"));
-  if (getenv("NDLQR_TREE")) c->tree = atoi(getenv("NDLQR_TREE")) != 0 ? 1 : 0;  // unset: by batch size
-  if (getenv("NDLQR_ROWBCAST")) c->rowbcast = atoi(getenv("NDLQR_ROWBCAST")) != 0 ? 1 : 0;  // unset: by block size
-  if (getenv("NDLQR_FUSE2")) c->fuse2 = atoi(getenv("NDLQR_FUSE2")) != 0 ? 1 : 0;  // unset: by instance (launch_small)
-  if (getenv("NDLQR_BACKSUB_COLS")) c->backsub_cols = atoi(getenv("NDLQR_BACKSUB_COLS")) != 0 ? 1 : 0;
-  c->no_mfma = getenv("NDLQR_NO_MFMA") != nullptr;
-  c->no_top = getenv("NDLQR_NO_TOP") != nullptr;
-  if (getenv("NDLQR_TOP_LEVELS")) c->top_levels = atoi(getenv("NDLQR_TOP_LEVELS"));
-  if (c->top_levels < 3 || c->top_levels > 5) c->top_levels = 3;
-  if (getenv("NDLQR_SEP_THREADS")) c->sep_threads = atoi(getenv("NDLQR_SEP_THREADS"));
-  if (getenv("NDLQR_MULT_THREADS")) c->mult_threads = atoi(getenv("NDLQR_MULT_THREADS"));
-  c->no_reduced_generic = getenv("NDLQR_DEV_NO_REDUCED_GENERIC") != nullptr;
   BufferSet& s = c->set[0];
   bool ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_inputs, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_step[0], hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_step[1], hipEventDisableTiming) == hipSuccess &&
-            hipMalloc(&c->AB, bytes_AB(d)) == hipSuccess && hipMalloc(&c->QR, bytes_QR(d)) == hipSuccess &&
-            hipMalloc(&c->info, sizeof(int) * ((size_t)batch + 1)) == hipSuccess &&
+            c->AB.ensure((size_t)d.batch * d.N * d.n * d.w) == hipSuccess && c->QR.ensure(doubles_QR(d)) == hipSuccess &&
             alloc_set(c, s, nhorizon >= 8 && has_small_instance(d.n, d.m));
   if (ok && c->padded) {
     hipLaunchKernelGGL(ndlqr::pad_fill_generic, dim3(d.N, d.batch), dim3(128), 0, s.stream, d, c->AB, c->QR, s.rhs);
     ok = hipGetLastError() == hipSuccess;
   }
   // (the factor array F is allocated by the first solve whose schedule touches it: ndlqr_hip_ensure_F)
-  ok = ok && hipMemsetAsync(c->info, 0, sizeof(int) * ((size_t)batch + 1), s.stream) == hipSuccess &&
-       hipStreamSynchronize(s.stream) == hipSuccess;
+  ok = ok && c->info.ensure_zeroed((size_t)batch + 1, s.stream) == hipSuccess && hipStreamSynchronize(s.stream) == hipSuccess;
   if (!ok) {
     fail("device allocation", hipGetLastError());
     ndlqr_hip_destroy(c);
@@ -183,14 +183,12 @@ NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int bat
   return c;
 }
 
-// release buffer set i (the primary set's stream only where the context owns it)
+// release buffer set i (the primary set's stream only where the context owns it): what is not memory by hand, the
+// buffers with the set
 static void free_set(NdlqrHipCtx* c, int i) {
   BufferSet& s = c->set[i];
   if (s.stream) (void)hipStreamSynchronize(s.stream);
   s.graph.reset();
-  (void)hipFree(s.rec); (void)hipFree(s.red); (void)hipFree(s.ytop); (void)hipFree(s.z); (void)hipFree(s.tree_cnt);
-  (void)hipFree(s.rhs); (void)hipFree(s.xfer);
-  if (s.h_fail) (void)hipHostFree(s.h_fail);
   if (s.ev_start) (void)hipEventDestroy(s.ev_start);
   if (s.ev_stop) (void)hipEventDestroy(s.ev_stop);
   if (s.stream && (i == 1 || c->own_stream)) (void)hipStreamDestroy(s.stream);
@@ -202,29 +200,11 @@ void ndlqr_hip_destroy(NdlqrHipCtx* c) {
   (void)hipSetDevice(c->device);
   for (int i = 1; i >= 0; --i) free_set(c, i);
   c->staged.reset();
-  if (c->h_io) (void)hipHostFree(c->h_io);
   for (auto& p : c->pending) { (void)hipEventDestroy(p.start); (void)hipEventDestroy(p.stop); }
   for (auto& ev : c->event_pool) (void)hipEventDestroy(ev);
-  (void)hipFree(c->AB); (void)hipFree(c->QR); (void)hipFree(c->F); (void)hipFree(c->info);
-  (void)hipFree(c->sep_scratch);
-  (void)hipFree(c->multi_rhs); (void)hipFree(c->multi_z); (void)hipFree(c->multi_zsep); (void)hipFree(c->multi_fsum);
-  (void)hipFree(c->multi_ytop); (void)hipFree(c->multi_in); (void)hipFree(c->multi_out);
-  (void)hipFree(c->kkt_out); (void)hipFree(c->pad_stage);
-  (void)hipFree(c->adj_rhs); (void)hipFree(c->adj_z); (void)hipFree(c->adj_save); (void)hipFree(c->grad_stage);
-  (void)hipFree(c->box_lo); (void)hipFree(c->box_hi); (void)hipFree(c->box_v); (void)hipFree(c->box_y); (void)hipFree(c->box_z);
-  (void)hipFree(c->box_qr_save); (void)hipFree(c->box_rhs[0]); (void)hipFree(c->box_rhs[1]); (void)hipFree(c->box_resid);
-  (void)hipFree(c->box_rho);
-  (void)hipFree(c->box_mask); (void)hipFree(c->box_status); (void)hipFree(c->box_iters); (void)hipFree(c->box_word);
-  (void)hipFree(c->abox_code); (void)hipFree(c->abox_v); (void)hipFree(c->abox_y); (void)hipFree(c->abox_resid);
-  (void)hipFree(c->abox_rhs[0]); (void)hipFree(c->abox_rhs[1]); (void)hipFree(c->abox_status); (void)hipFree(c->abox_iters);
-  (void)hipFree(c->abox_word);
-  (void)hipFree(c->ref_r); (void)hipFree(c->ref_delta); (void)hipFree(c->ref_norms); (void)hipFree(c->ref_steps);
-  (void)hipFree(c->ref_eta);
-  if (c->h_box_word) (void)hipHostFree(c->h_box_word);
-  for (double* h : c->h_stage) if (h) (void)hipHostFree(h);
   if (c->ev_inputs) (void)hipEventDestroy(c->ev_inputs);
   for (hipEvent_t ev : c->ev_step) if (ev) (void)hipEventDestroy(ev);
-  delete c;
+  delete c;  // (every buffer goes with its owner)
 }
 
 // ------------------------------------------------------------------------------ two-deep solve pipeline
@@ -267,7 +247,7 @@ static bool ensure_alt(NdlqrHipCtx* c) {
   // before, tools/e2e_probe.py --other-solvers; with its own priority level it keeps it).
   int prio_least = 0, prio_greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  const int alt_prio = getenv("NDLQR_ALT_PRIORITY") ? atoi(getenv("NDLQR_ALT_PRIORITY")) : prio_greatest;
+  const int alt_prio = c->knobs.alt_priority_set ? c->knobs.alt_priority : prio_greatest;
   bool ok = hipStreamCreateWithPriority(&a.stream, hipStreamNonBlocking, alt_prio) == hipSuccess &&
             alloc_set(c, a, p.tree_cnt != nullptr);
   // this set's own copy of the right-hand side (a step of ndlqr_hip_step_async replaces the right-hand side of
@@ -327,9 +307,7 @@ int ndlqr_hip_pipeline_depth(const NdlqrHipCtx* c) { return c ? c->pipeline : 0;
 int ndlqr_hip_ensure_F(NdlqrHipCtx* c) {
   if (c->F) return NDLQR_OK;
   HIP_TRY(hipSetDevice(c->device));
-  hipError_t e = hipMalloc(&c->F, bytes_F(c->d));
-  if (e != hipSuccess) {
-    c->F = nullptr;
+  if (c->F.ensure(doubles_F(c->d)) != hipSuccess) {
     (void)hipGetLastError();
     return refuse("factor array does not fit on the device (" + std::to_string(bytes_F(c->d) >> 20) +
                   " MiB): use the default fast mode without NDLQR_FLAG_KEEP_FACT, or a smaller batch");
@@ -410,17 +388,7 @@ static void note_new_inputs(NdlqrHipCtx* c) {
   next_solve_on_current_set(c);
   c->kept.forget_factorisation();
   c->inputs_replaced = true;
-  c->box_fact = false;
-}
-
-// staging of caller-layout data of a padded shape
-static int ensure_pad_stage(NdlqrHipCtx* c, size_t doubles) {
-  if (doubles <= c->pad_stage_cap) return NDLQR_OK;
-  if (c->pad_stage) { HIP_TRY(hipStreamSynchronize(c->set[c->cur].stream)); (void)hipFree(c->pad_stage); c->pad_stage = nullptr; c->pad_stage_cap = 0; }
-  c->staged.reset();  // (it holds the old address)
-  HIP_TRY(hipMalloc(&c->pad_stage, sizeof(double) * doubles));
-  c->pad_stage_cap = doubles;
-  return NDLQR_OK;
+  c->box.fact = false;
 }
 
 int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB, const double* QR,
@@ -437,8 +405,7 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
   if (c->padded) {  // the caller's layout goes to a staging array in HBM, a kernel files it into the padded arrays
     const ndlqr::Dims& u = c->du;
     const size_t uAB = (size_t)u.N * u.n * u.w * count, uQR = (size_t)u.N * u.w * count, uz = (size_t)u.N * u.rows * count;
-    const int serr = ensure_pad_stage(c, uAB + uQR + uz);
-    if (serr) return serr;
+    HIP_TRY(c->grow_pad_stage(uAB + uQR + uz));
     double* s0 = c->pad_stage;
     HIP_TRY(hipMemcpyAsync(s0, AB, sizeof(double) * uAB, hipMemcpyHostToDevice, s.stream));
     HIP_TRY(hipMemcpyAsync(s0 + uAB, QR, sizeof(double) * uQR, hipMemcpyHostToDevice, s.stream));
@@ -514,7 +481,7 @@ static ReducedGenericPlan plan_reduced_generic(const NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
   ReducedGenericPlan p = {false, 0, 0, 0, false, false};
   if (c->flags & (NDLQR_FLAG_STRICT_FP | NDLQR_FLAG_KEEP_FACT)) return p;
-  if (c->no_mfma || c->no_reduced_generic || d.n > 128 || d.N < 2) return p;
+  if (c->knobs.no_mfma || c->knobs.no_reduced_generic || d.n > 128 || d.N < 2) return p;
   p.keep = (c->flags & NDLQR_FLAG_KEEP_RECORDS) != 0;  // W of every separator kept for rhs-only re-solves
   p.nb = (d.n + 15) / 16;
   const int npad = 16 * p.nb, wpad = (d.w + 3) / 4 * 4;
@@ -532,8 +499,8 @@ static ReducedGenericPlan plan_reduced_generic(const NdlqrHipCtx* c) {
   return p;
 }
 
-static size_t bytes_red_generic(const ndlqr::Dims& d) {
-  return sizeof(double) * (size_t)d.batch * (d.N / 2) * (4 * (size_t)d.n * d.n + 2 * d.n);
+static size_t doubles_red_generic(const ndlqr::Dims& d) {
+  return (size_t)d.batch * (d.N / 2) * (4 * (size_t)d.n * d.n + 2 * d.n);
 }
 
 // slots of the separators of level >= 1 (runtime-sized separator-only schedule); allocated by the first
@@ -541,24 +508,21 @@ static size_t bytes_red_generic(const ndlqr::Dims& d) {
 // every accumulator block. Must run outside stream capture.
 static int ensure_red_generic(NdlqrHipCtx* c) {
   if (c->d.N < 4) return NDLQR_OK;  // a single separator: no slots
-  const size_t need = bytes_red_generic(c->d);
+  const size_t need = doubles_red_generic(c->d);
   for (BufferSet& s : c->set) {
-    if (!s.ready || (s.red && s.red_bytes >= need)) continue;
+    if (!s.ready || s.red.count() >= need) continue;
     // (a context of a size-specialised shape under NDLQR_FLAG_GENERIC comes with the smaller array of ITS schedule)
     HIP_TRY(sync_all(c));
-    if (s.red) { (void)hipFree(s.red); s.red = nullptr; s.red_bytes = 0; }
     s.graph.reset();  // a launch sequence captured on this buffer set holds the old address
-    if (hipMalloc(&s.red, need) != hipSuccess) {
-      s.red = nullptr;
+    if (s.red.grow(need) != hipSuccess) {
       (void)hipGetLastError();
       g_last_error = "accumulator slots of the separator-only schedule do not fit on the device";
       return NDLQR_ERR_INVALID;
     }
-    s.red_bytes = need;
     // (zeros for the size-specialised schedule, should the context go back to it. hipMemset runs on the null
     //  stream and may return before it is done; the solver's streams are non-blocking: wait here, or the
     //  level-0 launch races with it)
-    HIP_TRY(hipMemset(s.red, 0, need));
+    HIP_TRY(hipMemset(s.red, 0, sizeof(double) * need));
     HIP_TRY(hipDeviceSynchronize());
   }
   return NDLQR_OK;
@@ -575,7 +539,7 @@ static void launch_backsub_reduced_generic(NdlqrHipCtx* c, const double* rhs, do
   // (rows of CA | CB eight per wavefront. Four wavefronts per separator leave a CU a quarter full at small blocks: one up to
   //  32 states, two up to 64, four beyond -- profiles/r04_mult_threads_ab.txt: (16,4,256) x 1024 2.30 -> 1.86 ms per solve,
   //  (20,20) 1.32 -> 1.23, (48,16,512) 6.44 -> 6.27, (96,16) best at four; NDLQR_MULT_THREADS overrides)
-  const int thr_env = c->mult_threads;
+  const int thr_env = c->knobs.mult_threads;
   const int thr_m = (thr_env == 64 || thr_env == 128 || thr_env == 256) ? thr_env : (d.n <= 32 ? 64 : (d.n <= 64 ? 128 : 256));
   // A step that wants knots [k0, k1] alone (NDLQR_SOLN_ONLY: apply_blk0 / apply_nblk in units of eight knots): of every
   // level the separators whose subtree meets [k0 - 1, k1 + 2] -- a set closed under "needs the multipliers of the
@@ -684,15 +648,15 @@ static GenericSepPlan plan_generic_sep(const NdlqrHipCtx* c, const bool strict) 
   GenericSepPlan p;
   // block sizes that fill 16x16 MFMA tiles: Schur update on the fp64 matrix cores (fast mode; beyond 64 states the
   // runtime-sized form)
-  p.schur_nb = (strict || d.n % 16 != 0 || c->no_mfma) ? -1 : (d.n > 64 ? 0 : (d.rows % 16 == 0 ? d.n / 16 : -1));
-  p.mfma = !strict && d.n % 16 == 0 && d.w % 4 == 0 && !c->no_mfma;
+  p.schur_nb = (strict || d.n % 16 != 0 || c->knobs.no_mfma) ? -1 : (d.n > 64 ? 0 : (d.rows % 16 == 0 ? d.n / 16 : -1));
+  p.mfma = !strict && d.n % 16 == 0 && d.w % 4 == 0 && !c->knobs.no_mfma;
   p.scratch = false;
   const int ctl = 2 * (d.n / 16) + 1, ctc = ctl < kSepChunkTiles ? ctl : kSepChunkTiles;
   const size_t lds_mfma = sizeof(double) * ((size_t)d.n * (d.n + 1) + (size_t)d.n * (16 * ctc + 1) + (size_t)d.n * 17);
   const size_t lds_generic = sizeof(double) * ((size_t)d.n * (d.n + 1) + (size_t)d.n * (2 * d.n + 1));
   // matrix-core separator: one wavefront per 16x16 tile of the products / updates; 512 threads let two
   // workgroups (67 KB of LDS each at n = 64) share a CU
-  p.threads = c->sep_threads > 0 ? c->sep_threads : (d.n >= 32 ? 512 : 256);
+  p.threads = c->knobs.sep_threads > 0 ? c->knobs.sep_threads : (d.n >= 32 ? 512 : 256);
   if (p.mfma) {  // separator_mfma: a wavefront per tile of a block row of W, at most three panel tiles per wavefront
     const int need = (d.n / 16) > ((d.n / 16) * ctc + 2) / 3 ? (d.n / 16) : ((d.n / 16) * ctc + 2) / 3;
     if (p.threads < 64 * need) p.threads = 64 * need;
@@ -925,8 +889,7 @@ static int prepare_solve(NdlqrHipCtx* c, SolvePlan* plan) {
     const int ferr = ndlqr_hip_ensure_F(c);
     if (ferr) return ferr;
   }
-  if (plan->sep_scratch_bytes && !c->sep_scratch && hipMalloc(&c->sep_scratch, plan->sep_scratch_bytes) != hipSuccess) {
-    c->sep_scratch = nullptr;
+  if (plan->sep_scratch_bytes && c->sep_scratch.ensure(plan->sep_scratch_bytes / sizeof(double)) != hipSuccess) {
     (void)hipGetLastError();
     return refuse("global scratch of the large-block separator kernel does not fit on the device (" +
                   std::to_string(plan->sep_scratch_bytes >> 20) + " MiB): use a smaller batch");
@@ -994,7 +957,7 @@ static int launch_solve(NdlqrHipCtx* c, const SolvePlan& plan) {
   note_solution(c);
   c->kept = plan.kept;
   c->inputs_replaced = false;
-  c->box_fact = false;  // (the records / factors are those of the unshifted matrix now)
+  c->box.fact = false;  // (the records / factors are those of the unshifted matrix now)
   ++c->factor_count;
   return NDLQR_OK;
 }
@@ -1035,10 +998,9 @@ int ndlqr_hip_staged_io(NdlqrHipCtx* c, double** AB, double** QR, double** rhs, 
   size_t oAB, oQR, orhs, oz;
   const size_t total = staged_doubles(c->du, &oAB, &oQR, &orhs, &oz);
   if (!c->h_io) {
-    HIP_TRY(hipHostMalloc((void**)&c->h_io, sizeof(double) * total, hipHostMallocDefault));
+    HIP_TRY(c->h_io.ensure(total));
     if (c->padded) {  // (caller-layout staging in HBM for both directions; allocated outside any capture)
-      const int serr = ensure_pad_stage(c, total);
-      if (serr) return serr;
+      HIP_TRY(c->grow_pad_stage(total));
     }
     const int perr = ndlqr_hip_set_pipeline_depth(c, 1);
     if (perr) return perr;
@@ -1091,7 +1053,7 @@ int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
   if (err) return err;
   rhs_written_cur(c, 0xFu);
   c->kept.forget_factorisation();  // new A, B, Q, R: neither a cached factor array nor cached records match
-  c->box_fact = false;
+  c->box.fact = false;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_staged(c, plan) : replay_chain(c, c->staged, plan, enqueue_staged);
@@ -1145,7 +1107,7 @@ int ndlqr_hip_time_shard_import(NdlqrHipCtx* c, int G, const double* buf) {
 }
 
 static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
-  if (c) c->box_fact = false;  // (the phases overwrite the records)
+  if (c) c->box.fact = false;  // (the phases overwrite the records)
   const SmallInstance* inst = time_shard_instance(c, G);
   if (!inst) {
     g_last_error = "time-axis sharding: needs a size-specialised block size with a matrix-core instance, G a power of two, "
@@ -1181,15 +1143,6 @@ static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
 }
 int ndlqr_hip_time_shard_factor(NdlqrHipCtx* c, int g, int G) { return time_shard_phase(c, 0, g, G); }
 int ndlqr_hip_time_shard_finish(NdlqrHipCtx* c, int g, int G) { return time_shard_phase(c, 1, g, G); }
-
-// transfer staging of the current buffer set: max(flat right-hand side, packed solutions) doubles
-static int ensure_xfer(NdlqrHipCtx* c) {
-  BufferSet& s = c->set[c->cur];
-  if (s.xfer) return NDLQR_OK;
-  const ndlqr::Dims& d = c->du;  // (caller-layout data: flat right-hand side going up, packed solutions coming down)
-  HIP_TRY(hipMalloc(&s.xfer, sizeof(double) * ((size_t)d.batch * d.N * d.rows + (size_t)d.batch * d.n)));
-  return NDLQR_OK;
-}
 
 // Packs the solutions of `count` problems from the blocks [count][N][2n+m] at z into dst: the whole vectors [count][nvars],
 // or the slice `sel` [count][nknots][width]. u: the caller's block sizes, d: the device layout.
@@ -1235,8 +1188,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   int err = prepare_solve(c, &plan);
   if (err) return err;
   BufferSet& s = c->set[c->cur];
-  err = ensure_xfer(c);  // (before anything is captured: allocation is not a stream operation)
-  if (err) return err;
+  HIP_TRY(s.ensure_xfer(c->du));  // (before anything is captured: allocation is not a stream operation)
   // the parts of the right-hand side this step does not replace: this buffer set's copy of them may be behind the other's
   const unsigned written = (q ? 1u : 0u) | (r ? 2u : 0u) | (dd ? 4u : 0u) | 8u;
   err = rhs_make_current(c, ~written & 0xFu);
@@ -1316,8 +1268,7 @@ int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   int err = prepare_solve(c, &plan);
   if (err) return err;
   BufferSet& s = c->set[c->cur];
-  err = ensure_xfer(c);
-  if (err) return err;
+  HIP_TRY(s.ensure_xfer(c->du));
   err = rhs_make_current(c, 0xFu);
   if (err) return err;
   hipStream_t st = s.stream;
@@ -1373,8 +1324,7 @@ int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
     return need_full_solution(c, "ndlqr_hip_download_selection");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
-  const int xerr = ensure_xfer(c);
-  if (xerr) return xerr;
+  HIP_TRY(s.ensure_xfer(c->du));
   const int derr =
       deliver(c->du, c->d, sel, c->set[c->latest].z, out, false, s.xfer, hipMemcpyDeviceToHost, s.stream, c->d.batch);
   if (derr) return derr;
@@ -1425,8 +1375,7 @@ int ndlqr_hip_upload_rhs(NdlqrHipCtx* c, int p0, int count, const double* rhs) {
   const size_t sz = (size_t)d.N * d.rows;
   if (c->padded) {
     const size_t uz = (size_t)c->du.N * c->du.rows * count;
-    const int serr = ensure_pad_stage(c, uz);
-    if (serr) return serr;
+    HIP_TRY(c->grow_pad_stage(uz));
     HIP_TRY(hipMemcpyAsync(c->pad_stage, rhs, sizeof(double) * uz, hipMemcpyHostToDevice, s.stream));
     hipLaunchKernelGGL(ndlqr::pad_inputs_generic, dim3(d.N, count), dim3(128), 0, s.stream, c->du, d, p0,
                        (const double*)nullptr, (const double*)nullptr, (const double*)c->pad_stage, c->AB, c->QR, s.rhs);
@@ -1522,18 +1471,8 @@ int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
 // The caller's arrays: this device's memory is taken as it is, host memory (pinned or pageable) is staged through HBM, and
 // another device's memory is refused (the caller has the wrong device, and a silent copy would hide it).
 
-static int ensure_grad_stage(NdlqrHipCtx* c, size_t doubles) {
-  if (doubles <= c->grad_stage_cap) return NDLQR_OK;
-  (void)hipFree(c->grad_stage);
-  c->grad_stage = nullptr;
-  c->grad_stage_cap = 0;
-  HIP_TRY(hipMalloc(&c->grad_stage, sizeof(double) * doubles));
-  c->grad_stage_cap = doubles;
-  return NDLQR_OK;
-}
-
 // K arrays of the caller, cnt[k] doubles each (null: absent), and their way through grad_stage. In this order: classify();
-// ensure_grad_stage for `stage` doubles plus whatever the caller wants behind them; sync_all; place(), which fills dev[] --
+// grad_stage.grow for `stage` doubles plus whatever the caller wants behind them; sync_all; place(), which fills dev[] --
 // what the kernels get -- and returns the first free double; copy(st, true) before the launches that read inputs, or
 // copy(st, false) behind those that wrote outputs.
 template <int K>
@@ -1585,19 +1524,6 @@ static void note_elapsed(NdlqrHipCtx* c, const BufferSet& s) {
   if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
 }
 
-// device buffers that are allocated on first use: those of the list that are not there yet
-struct FirstUse {
-  void** p;
-  size_t bytes;
-  template <typename T>
-  FirstUse(T** q, size_t b) : p(reinterpret_cast<void**>(q)), bytes(b) {}
-};
-static int alloc_missing(std::initializer_list<FirstUse> list) {
-  for (const FirstUse& a : list)
-    if (!*a.p) HIP_TRY(hipMalloc(a.p, a.bytes));
-  return NDLQR_OK;
-}
-
 // The re-solves of the kept records write what depends on the right-hand side into them (z_sep / y~: the last n entries
 // of every record) and, on the runtime-sized schedule, into the slots (gL | gR). Every re-solve recomputes those before
 // it reads them; the adjoint solve still leaves them as it found them: saved before, restored after (2 n doubles per
@@ -1606,7 +1532,7 @@ static hipError_t adjoint_scratch(NdlqrHipCtx* c, bool restore) {
   const ndlqr::Dims& d = c->d;
   const BufferSet& s = c->set[0];
   const size_t col = sizeof(double) * d.n, rows = (size_t)d.batch * d.N;
-  double* save = c->adj_save;
+  double* save = c->adj.save;
   double* rec_col = s.rec + 2 * (size_t)d.n * d.n;
   const size_t rec_pitch = sizeof(double) * (2 * (size_t)d.n * d.n + d.n);
   hipError_t e = restore ? hipMemcpy2DAsync(rec_col, rec_pitch, save, col, col, rows, hipMemcpyDeviceToDevice, s.stream)
@@ -1635,23 +1561,17 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   HIP_TRY(sync_all(c));
   c->cur = 0;  // cached records / factors live in the primary set
   BufferSet& s = c->set[0];
-  err = alloc_missing({{&c->adj_rhs, bytes_z(d)}, {&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n}});
-  if (err) return err;
-  if (!c->adj_z) {
-    HIP_TRY(hipMalloc(&c->adj_z, bytes_z(d)));
-    HIP_TRY(hipMemsetAsync(c->adj_z, 0, bytes_z(d), s.stream));  // (entries a re-solve does not write: the pad rows)
-  }
-  err = ensure_grad_stage(c, ga.stage);
-  if (err) return err;
+  HIP_TRY(c->adj.ensure(d, s.stream));
+  HIP_TRY(c->grad_stage.grow(ga.stage));
   ga.place(c);
   err = ga.copy(s.stream, true);
   if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)ga.dev[0],
-                     c->adj_rhs);
+                     c->adj.rhs);
   HIP_TRY(hipGetLastError());
   HIP_TRY(adjoint_scratch(c, false));
-  err = launch_resolve(c, c->adj_rhs, c->adj_z,
+  err = launch_resolve(c, c->adj.rhs, c->adj.z,
                        "adjoint solve: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
   if (err) return err;
   HIP_TRY(hipGetLastError());
@@ -1659,14 +1579,14 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   note_elapsed(c, s);
-  c->adj_gen = c->soln_gen;
+  c->adj.gen = c->soln_gen;
   return NDLQR_OK;
 }
 
 // is there an adjoint of the resident solution of the resident inputs?
 static int need_adjoint(const NdlqrHipCtx* c, const char* who) {
   if (c->z_partial || c->z_invalid) return need_full_solution(c, who);
-  if (c->adj_gen == 0 || c->adj_gen != c->soln_gen)
+  if (c->adj.gen == 0 || c->adj.gen != c->soln_gen)
     return refuse(std::string(who) + ": no adjoint of the resident solution (ndlqr_hip_solve_adjoint after the latest solve)");
   if (c->inputs_replaced) return refuse(std::string(who) + ": the inputs were replaced after the factorisation");
   return NDLQR_OK;
@@ -1681,10 +1601,10 @@ int ndlqr_hip_download_adjoint(NdlqrHipCtx* c, double* w) {
   HIP_TRY(hipSetDevice(c->device));
   const Where ww = where(w, c->device);
   if (ww == Where::OtherDevice) return refuse("ndlqr_hip_download_adjoint: w lies in the memory of another device than the solver's");
-  if (ww != Where::OwnDevice) return download_packed(c, c->adj_z, 0, c->d.batch, w);
+  if (ww != Where::OwnDevice) return download_packed(c, c->adj.z, 0, c->d.batch, w);
   const BufferSet& s = c->set[0];
   HIP_TRY(sync_all(c));
-  HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->adj_z, w, s.stream, c->d.batch));
+  HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->adj.z, w, s.stream, c->d.batch));
   HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }
@@ -1741,8 +1661,7 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
     nsplit = (d.batch + ppb - 1) / ppb;
   }
   const size_t npart = nsplit > 1 ? (size_t)nsplit * total : 0;
-  err = ensure_grad_stage(c, ga.stage + npart);
-  if (err) return err;
+  HIP_TRY(c->grad_stage.grow(ga.stage + npart));
   HIP_TRY(sync_all(c));
   BufferSet& s = c->set[0];
   double* part = ga.place(c);  // (the partial sums behind the staged outputs)
@@ -1753,7 +1672,7 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
   HIP_TRY(strict ? allow_dynamic_lds(&ndlqr::grad_assemble<true>, lds) : allow_dynamic_lds(&ndlqr::grad_assemble<false>, lds));
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   launch_strict(strict, ndlqr::grad_assemble, dim3(nchunks, nsplit, nslice), dim3(256), lds, s.stream, u, d, KC, ppb, (int)EC,
-                z, (const double*)c->adj_z, out, part);
+                z, (const double*)c->adj.z, out, part);
   HIP_TRY(hipGetLastError());
   if (part) {
     hipLaunchKernelGGL(ndlqr::grad_sum_splits, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s.stream, out, nsplit,
@@ -1772,8 +1691,8 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
 // Scaled ADMM with a fixed penalty on the kept factorisation (kernels_box.hpp): QR is shifted by
 // rho M in place -- the pointers, and with them the captured launch chain of the primary set, stay valid, and every record
 // re-solve reads the shifted diagonal --, factored once (or not at all while the remembered shifted factorisation still
-// applies), and every iteration is one re-solve into box_z plus one box_update; the host reads the running count every
-// check_every iterations. The penalty is a device vector, box_rho [batch]. With adapt_every > 0
+// applies), and every iteration is one re-solve into box.z plus one box_update; the host reads the running count every
+// check_every iterations. The penalty is a device vector, box.rho [batch]. With adapt_every > 0
 // box_update may move a problem's penalty at every adapt_every-th iteration; the host then reads the count of changed
 // problems next to the running count and, when it is not zero, restores QR, shifts it by the new vector and factors the
 // whole batch again -- one factorisation serves every problem that changed in that round.
@@ -1792,41 +1711,34 @@ int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const do
   CallerArrays<4> in = {{const_cast<double*>(xlo), const_cast<double*>(xhi), const_cast<double*>(ulo), const_cast<double*>(uhi)},
                         {nx, nx, nu, nu}};
   int err = in.classify(c, "ndlqr_hip_set_bounds", "bounds lie");
-  if (!err) err = ensure_grad_stage(c, in.stage);
   if (err) return err;
-  const size_t nlo = sizeof(double) * (size_t)d.batch * d.N * d.w;  // (room for per-problem bounds, shared or not)
-  if (!c->box_mask) {
-    HIP_TRY(hipMalloc(&c->box_mask, (size_t)d.batch * d.N * d.w));
-    HIP_TRY(hipMemset(c->box_mask, 0, (size_t)d.batch * d.N * d.w));
-  }
-  err = alloc_missing({{&c->box_lo, nlo}, {&c->box_hi, nlo}, {&c->box_word, 4 * sizeof(int)}});
-  if (err) return err;
-  if (!c->h_box_word) HIP_TRY(hipHostMalloc((void**)&c->h_box_word, 5 * sizeof(int), hipHostMallocDefault));
-  HIP_TRY(sync_all(c));  // (a solve in flight may still read the bounds)
   BufferSet& s = c->set[0];
+  HIP_TRY(c->grad_stage.grow(in.stage));
+  HIP_TRY(c->box.ensure(d, s.stream));
+  HIP_TRY(sync_all(c));  // (a solve in flight may still read the bounds)
   in.place(c);
   err = in.copy(s.stream, true);
   if (err) return err;
   const double* const* view = in.dev;
-  HIP_TRY(hipMemsetAsync(c->box_word, 0, 4 * sizeof(int), s.stream));
+  HIP_TRY(hipMemsetAsync(c->box.word, 0, 4 * sizeof(int), s.stream));
   hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 0,
-                     c->box_lo, c->box_hi, c->box_mask, c->box_word + 2, c->box_word + 3);
+                     c->box.lo, c->box.hi, c->box.mask, c->box.word + 2, c->box.word + 3);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipMemcpyAsync(c->box.h_word, c->box.word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
-  if (c->h_box_word[2]) return refuse("ndlqr_hip_set_bounds: a lower bound exceeds its upper bound (or is NaN)");
+  if (c->box.h_word[2]) return refuse("ndlqr_hip_set_bounds: a lower bound exceeds its upper bound (or is NaN)");
   // the pattern lives in mask per problem: shared bounds are compared against problem 0's row of it, so a change between
   // shared and per-problem bounds always counts as a new pattern
   hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 1,
-                     c->box_lo, c->box_hi, c->box_mask, c->box_word + 2, c->box_word + 3);
+                     c->box.lo, c->box.hi, c->box.mask, c->box.word + 2, c->box.word + 3);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipMemcpyAsync(c->box.h_word, c->box.word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
-  if (c->h_box_word[3] || (bool)shared != c->box_shared || !c->box_have_bounds) c->box_fact = false;
-  c->box_soln_gen = 0;  // (a box adjoint needs the constrained solution of these bounds)
-  c->box_shared = shared != 0;
-  c->box_bstride = shared ? 0 : (size_t)d.N * d.w;
-  c->box_have_bounds = true;
+  if (c->box.h_word[3] || (bool)shared != c->box.shared || !c->box.have_bounds) c->box.fact = false;
+  c->box.soln_gen = 0;  // (a box adjoint needs the constrained solution of these bounds)
+  c->box.shared = shared != 0;
+  c->box.bstride = shared ? 0 : (size_t)d.N * d.w;
+  c->box.have_bounds = true;
   return NDLQR_OK;
 }
 
@@ -1839,7 +1751,7 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
 // The shifted matrix factored on the primary set as a plain solve does it (the resident solution is overwritten), with
 // the pivot check: *not_spd = NDLQR_ERR_NOT_SPD, which is returned, when a pivot was not positive.
 static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd) {
-  c->box_fact = false;
+  c->box.fact = false;
   SolvePlan plan;
   int err = prepare_solve(c, &plan);  // (KEEP_*: stream-ordered on the primary set)
   if (!err) err = launch_solve(c, plan);
@@ -1872,14 +1784,14 @@ struct ShiftedQR {
   ~ShiftedQR() { (void)close(); }
   int shift(const double* rho) {
     const ndlqr::Dims& d = c->d;
-    hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, c->set[0].stream, d, rho, (const double*)c->box_lo,
-                       (const double*)c->box_hi, c->box_bstride, c->QR);
+    hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, c->set[0].stream, d, rho, (const double*)c->box.lo,
+                       (const double*)c->box.hi, c->box.bstride, c->QR);
     HIP_TRY(hipGetLastError());
     return NDLQR_OK;
   }
   // QR saved, shifted by the penalties `rho` [batch] on the bounded entries, c->flags = flags
   int open(const double* rho, unsigned flags) {
-    HIP_TRY(hipMemcpyAsync(c->box_qr_save, c->QR, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
+    HIP_TRY(hipMemcpyAsync(c->box.qr_save, c->QR, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
     open_ = true;
     const int err = shift(rho);
     c->flags = flags;
@@ -1887,7 +1799,7 @@ struct ShiftedQR {
   }
   // new penalties: the saved QR again, shifted by them
   int reshift(const double* rho) {
-    HIP_TRY(hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
+    HIP_TRY(hipMemcpyAsync(c->QR, c->box.qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
     return shift(rho);
   }
   // the right-hand-side columns of the kept records, which the re-solves of an adjoint overwrite: restored by close()
@@ -1902,7 +1814,7 @@ struct ShiftedQR {
     if (!open_) return NDLQR_OK;
     open_ = false;
     const hipError_t ce = columns_saved ? adjoint_scratch(c, true) : hipSuccess;
-    const hipError_t qe = hipMemcpyAsync(c->QR, c->box_qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream);
+    const hipError_t qe = hipMemcpyAsync(c->QR, c->box.qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream);
     c->flags = user_flags;
     c->kept.forget_factorisation();
     if (ce != hipSuccess) return fail("restoring the record columns", ce);
@@ -1945,21 +1857,12 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   if (!c || !(rho > 0.0) || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 ||
       check_every < 1 || adapt_every < 0 || (adapt_every > 0 && !(rho_min > 0.0 && rho_min <= rho_max)))
     return NDLQR_ERR_INVALID;
-  if (!c->box_have_bounds) return refuse("ndlqr_hip_solve_box: no bounds (ndlqr_hip_set_bounds first)");
+  if (!c->box.have_bounds) return refuse("ndlqr_hip_solve_box: no bounds (ndlqr_hip_set_bounds first)");
   const ndlqr::Dims& d = c->d;
   HIP_TRY(hipSetDevice(c->device));
   int err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_box", iters, status);
   if (err) return err;
-  const size_t nz = bytes_z(d), nv = sizeof(double) * (size_t)d.batch * d.N * d.w;
-  if (!c->box_z) {
-    HIP_TRY(hipMalloc(&c->box_z, nz));
-    HIP_TRY(hipMemset(c->box_z, 0, nz));  // (entries a re-solve does not write: the pad rows)
-  }
-  err = alloc_missing({{&c->box_v, nv}, {&c->box_y, nv}, {&c->box_qr_save, bytes_QR(d)}, {&c->box_rhs[0], nz},
-                       {&c->box_rhs[1], nz}, {&c->box_resid, sizeof(double) * 2 * (size_t)d.batch},
-                       {&c->box_status, sizeof(int) * (size_t)d.batch}, {&c->box_iters, sizeof(int) * (size_t)d.batch},
-                       {&c->box_rho, sizeof(double) * (size_t)d.batch}});
-  if (err) return err;
+  HIP_TRY(c->box.ensure(d, c->set[0].stream));
   // 1. everything idle, the primary set current with an up-to-date right-hand side
   HIP_TRY(sync_all(c));
   c->cur = 0;
@@ -1971,16 +1874,16 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   const unsigned box_flags = c->flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
   // the remembered factorisation applies to an adaptive warm start whatever its penalties are (the settings' rho is
   // ignored: an MPC loop keeps what it learnt); everywhere else only when they are all the settings' rho
-  const bool usable = c->box_fact && c->box_flags == box_flags;
+  const bool usable = c->box.fact && c->box.flags == box_flags;
   const bool keep_rho = usable && adapt_every > 0 && warm_start;
-  const bool reuse = keep_rho || (usable && c->box_rho_uniform && c->box_rho_value == rho);
-  bool uniform = keep_rho ? c->box_rho_uniform : true;
-  const double uniform_value = keep_rho ? c->box_rho_value : rho;
+  const bool reuse = keep_rho || (usable && c->box.rho_uniform && c->box.rho_value == rho);
+  bool uniform = keep_rho ? c->box.rho_uniform : true;
+  const double uniform_value = keep_rho ? c->box.rho_value : rho;
   HIP_TRY(hipEventRecord(s.ev_start, st));
   // 2. the penalties
   if (!reuse) {
-    c->box_fact = false;  // (the remembered factorisation belongs to the penalties overwritten here)
-    hipLaunchKernelGGL(ndlqr::box_fill_rho, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, rho, c->box_rho);
+    c->box.fact = false;  // (the remembered factorisation belongs to the penalties overwritten here)
+    hipLaunchKernelGGL(ndlqr::box_fill_rho, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, rho, c->box.rho);
     HIP_TRY(hipGetLastError());
   }
   bool factored = false;  // the shifted matrix was factored in this call (the resident solution is then overwritten)
@@ -1989,46 +1892,46 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
   const auto iterate = [&]() -> int {
     // 3. shift QR; factor the shifted matrix, unless the remembered factorisation applies
-    int e = shifted.open(c->box_rho, box_flags);
+    int e = shifted.open(c->box.rho, box_flags);
     if (e) return e;
     if (reuse) {
-      c->kept = c->box_kept;
+      c->kept = c->box.kept;
     } else {
       factored = true;
       e = box_factor(c, st, &not_spd);
       if (e) return e;
     }
     // 4. the iterations
-    const double* lo = c->box_lo;
-    const double* hi = c->box_hi;
-    const size_t bs = c->box_bstride;
+    const double* lo = c->box.lo;
+    const double* hi = c->box.hi;
+    const size_t bs = c->box.bstride;
     const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, rho_min, rho_max};
-    const double* rhov = c->box_rho;
-    const int cold = warm_start && c->box_have_vy ? 0 : 1;
+    const double* rhov = c->box.rho;
+    const int cold = warm_start && c->box.have_vy ? 0 : 1;
     launch_strict(strict, ndlqr::box_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, lo, hi, bs,
-                  (const double*)s.rhs, c->box_v, c->box_y, c->box_rhs[0], c->box_rhs[1]);
+                  (const double*)s.rhs, c->box.v, c->box.y, c->box.rhs[0], c->box.rhs[1]);
     HIP_TRY(hipGetLastError());
-    c->box_have_vy = true;
-    c->h_box_word[0] = d.batch;
-    c->h_box_word[1] = 0;
-    HIP_TRY(hipMemcpyAsync(c->box_word, c->h_box_word, 2 * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(c->box_status, 0, sizeof(int) * (size_t)d.batch, st));
+    c->box.have_vy = true;
+    c->box.h_word[0] = d.batch;
+    c->box.h_word[1] = 0;
+    HIP_TRY(hipMemcpyAsync(c->box.word, c->box.h_word, 2 * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(c->box.status, 0, sizeof(int) * (size_t)d.batch, st));
     for (int it = 1; it <= max_iter; ++it) {
-      const double* rc = c->box_rhs[(it - 1) & 1];
-      double* rn = c->box_rhs[it & 1];
-      e = launch_resolve(c, rc, c->box_z, "box-constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      const double* rc = c->box.rhs[(it - 1) & 1];
+      double* rn = c->box.rhs[it & 1];
+      e = launch_resolve(c, rc, c->box.z, "box-constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
       if (e) return e;
       const int adapt = adapt_every > 0 && it % adapt_every == 0 && it < max_iter;
-      launch_strict(strict, ndlqr::box_update, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box_z, lo, hi,
-                    bs, c->box_v, c->box_y, (const double*)s.rhs, rc, rn, c->box_rho, c->box_status, c->box_iters,
-                    c->box_resid, c->box_word);
+      launch_strict(strict, ndlqr::box_update, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box.z, lo, hi,
+                    bs, c->box.v, c->box.y, (const double*)s.rhs, rc, rn, c->box.rho, c->box.status, c->box.iters,
+                    c->box.resid, c->box.word);
       HIP_TRY(hipGetLastError());
       if (it % check_every == 0 || it == max_iter || adapt) {
         // 5. one word: how many problems still run; after an adapting update also how many changed their penalty
-        HIP_TRY(hipMemcpyAsync(c->h_box_word, c->box_word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->box.h_word, c->box.word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (c->h_box_word[0] == 0) break;
-        if (adapt && c->h_box_word[1] != 0) {
+        if (c->box.h_word[0] == 0) break;
+        if (adapt && c->box.h_word[1] != 0) {
           // 5a. new penalties: the saved QR shifted by the new vector and factored as above (frozen problems keep their
           // penalty: the same factors again, so their later re-solves reproduce their z)
           uniform = false;
@@ -2036,12 +1939,12 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
           e = shifted.reshift(rhov);
           if (!e) e = box_factor(c, st, &not_spd);
           if (e) return e;
-          HIP_TRY(hipMemsetAsync(c->box_word + 1, 0, sizeof(int), st));
+          HIP_TRY(hipMemsetAsync(c->box.word + 1, 0, sizeof(int), st));
         }
       }
     }
     // 6. deliver
-    hipLaunchKernelGGL(ndlqr::box_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, lo, hi, bs, (const double*)c->box_z, c->box_v,
+    hipLaunchKernelGGL(ndlqr::box_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, lo, hi, bs, (const double*)c->box.z, c->box.v,
                        s.z);
     HIP_TRY(hipGetLastError());
     return NDLQR_OK;
@@ -2052,54 +1955,54 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   const int cerr = shifted.close();
   if (!err) err = cerr;
   if (!err) {
-    c->box_fact = true;
-    c->box_rho_uniform = uniform;
-    c->box_rho_value = uniform_value;
-    c->box_flags = box_flags;
-    c->box_kept = shifted_kept;
+    c->box.fact = true;
+    c->box.rho_uniform = uniform;
+    c->box.rho_value = uniform_value;
+    c->box.flags = box_flags;
+    c->box.kept = shifted_kept;
   } else {
-    c->box_fact = false;
-    c->box_have_vy = false;
+    c->box.fact = false;
+    c->box.have_vy = false;
     if (!not_spd) c->state_dirty = true;  // (a failed launch; a non-positive pivot leaves the device state clean)
     if (factored) c->z_invalid = true;    // (the factorisation solved the shifted matrix with the unshifted right-hand side)
     (void)hipStreamSynchronize(st);
     return err;
   }
   note_solution(c);
-  c->box_soln_gen = c->soln_gen;
+  c->box.soln_gen = c->soln_gen;
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   c->timing_pending = true;
-  err = deliver_iters_status(c, st, c->box_iters, c->box_status, iters, status);
+  err = deliver_iters_status(c, st, c->box.iters, c->box.status, iters, status);
   if (err) return err;
   return ndlqr_hip_synchronize(c);
 }
 
 int ndlqr_hip_download_box_penalties(NdlqrHipCtx* c, double* rho) {
   if (!c || !rho) return NDLQR_ERR_INVALID;
-  if (!c->box_have_vy || !c->box_rho) return refuse("ndlqr_hip_download_box_penalties: no constrained solve yet");
+  if (!c->box.have_vy || !c->box.rho) return refuse("ndlqr_hip_download_box_penalties: no constrained solve yet");
   HIP_TRY(hipSetDevice(c->device));
   if (where(rho, c->device) == Where::OtherDevice)
     return refuse("ndlqr_hip_download_box_penalties: the output lies in the memory of another device than the solver's");
   HIP_TRY(sync_all(c));
-  HIP_TRY(hipMemcpy(rho, c->box_rho, sizeof(double) * (size_t)c->d.batch, hipMemcpyDefault));
+  HIP_TRY(hipMemcpy(rho, c->box.rho, sizeof(double) * (size_t)c->d.batch, hipMemcpyDefault));
   return NDLQR_OK;
 }
 
 int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* mu_u) {
   if (!c || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
-  if (!c->box_have_vy || !c->box_y) return refuse("ndlqr_hip_download_bound_multipliers: no constrained solve yet");
+  if (!c->box.have_vy || !c->box.y) return refuse("ndlqr_hip_download_bound_multipliers: no constrained solve yet");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
   CallerArrays<2> out = {{mu_x, mu_u}, {(size_t)u.batch * u.N * u.n, (size_t)u.batch * u.N * u.m}};
   int err = out.classify(c, "ndlqr_hip_download_bound_multipliers", "an output lies");
-  if (!err) err = ensure_grad_stage(c, out.stage);
   if (err) return err;
+  HIP_TRY(c->grad_stage.grow(out.stage));
   HIP_TRY(sync_all(c));
   const BufferSet& s = c->set[0];
   out.place(c);
-  hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box_rho,
-                     (const double*)c->box_y, out.dev[0], out.dev[1]);
+  hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
+                     (const double*)c->box.y, out.dev[0], out.dev[1]);
   HIP_TRY(hipGetLastError());
   err = out.copy(s.stream, false);
   if (err) return err;
@@ -2111,7 +2014,7 @@ int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* m
 // The adjoint of the active-set system (kernels_box_grad.hpp) by the ADMM of the forward on its
 // remembered shifted factorisation: QR shifted by the forward's rho on its bounded entries again (restored on every
 // exit), the kept records / factors taken as the forward left them -- nothing is factored --, every iteration one
-// re-solve into adj_z plus one box_adjoint_update. The right-hand-side columns of the kept records and slots are saved and
+// re-solve into adj.z plus one box_adjoint_update. The right-hand-side columns of the kept records and slots are saved and
 // restored around it as for the plain adjoint, so the next warm-started forward finds everything as it was.
 
 int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, double eps_abs, double eps_rel, int max_iter,
@@ -2120,10 +2023,10 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
       check_every < 1)
     return NDLQR_ERR_INVALID;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_box_adjoint");
-  if (c->box_soln_gen == 0 || c->box_soln_gen != c->soln_gen || !c->box_fact || c->inputs_replaced)
+  if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.fact || c->inputs_replaced)
     return refuse("ndlqr_hip_solve_box_adjoint: the resident solution is not that of the latest constrained solve (a solve, "
                   "step, re-solve, new inputs or new bounds came after it)");
-  if (c->box_kept.time_shard) return refuse("ndlqr_hip_solve_box_adjoint: not available on a time-axis shard");
+  if (c->box.kept.time_shard) return refuse("ndlqr_hip_solve_box_adjoint: not available on a time-axis shard");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
@@ -2131,18 +2034,9 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
   int err = ga.classify(c, "ndlqr_hip_solve_box_adjoint", "g lies");
   if (!err) err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_box_adjoint", iters, status);
   if (err) return err;
-  const size_t nz = bytes_z(d), nv = sizeof(double) * (size_t)d.batch * d.N * d.w;
-  if (!c->adj_z) {
-    HIP_TRY(hipMalloc(&c->adj_z, nz));
-    HIP_TRY(hipMemset(c->adj_z, 0, nz));  // (entries a re-solve does not write: the pad rows)
-  }
-  err = alloc_missing({{&c->adj_rhs, nz}, {&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n},
-                       {&c->abox_code, (size_t)d.batch * d.N * d.w}, {&c->abox_v, nv}, {&c->abox_y, nv}, {&c->abox_rhs[0], nz},
-                       {&c->abox_rhs[1], nz}, {&c->abox_resid, sizeof(double) * 2 * (size_t)d.batch},
-                       {&c->abox_status, sizeof(int) * (size_t)d.batch}, {&c->abox_iters, sizeof(int) * (size_t)d.batch},
-                       {&c->abox_word, sizeof(int)}});
-  if (!err) err = ensure_grad_stage(c, ga.stage);
-  if (err) return err;
+  HIP_TRY(c->adj.ensure(d, c->set[0].stream));
+  HIP_TRY(c->abox.ensure(d));
+  HIP_TRY(c->grad_stage.grow(ga.stage));
   // 1. everything idle, the primary set current; g packed into the adjoint's resident right-hand side
   HIP_TRY(sync_all(c));
   c->cur = 0;
@@ -2151,58 +2045,58 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
   ga.place(c);
   err = ga.copy(st, true);
   if (err) return err;
-  c->abox_gen = 0;
-  c->adj_gen = 0;
-  const bool strict = (c->box_flags & NDLQR_FLAG_STRICT_FP) != 0;
+  c->abox.gen = 0;
+  c->adj.gen = 0;
+  const bool strict = (c->box.flags & NDLQR_FLAG_STRICT_FP) != 0;
   HIP_TRY(hipEventRecord(s.ev_start, st));
   ShiftedQR shifted(c);
   // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
   const auto iterate = [&]() -> int {
-    const double* rho = c->box_rho;  // (the forward's final penalties: those of the remembered factorisation)
+    const double* rho = c->box.rho;  // (the forward's final penalties: those of the remembered factorisation)
     hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, st, u, d, (const double*)ga.dev[0],
-                       c->adj_rhs);
+                       c->adj.rhs);
     HIP_TRY(hipGetLastError());
     // 2. shift QR, take up the remembered shifted factorisation, save the right-hand-side columns of the records
-    int e = shifted.open(rho, c->box_flags);
+    int e = shifted.open(rho, c->box.flags);
     if (e) return e;
-    c->kept = c->box_kept;
+    c->kept = c->box.kept;
     e = shifted.save_record_columns();
     if (e) return e;
     // 3. codes, v = y = 0, right-hand sides, status
     const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
-    HIP_TRY(hipMemsetAsync(c->abox_word, 0, sizeof(int), st));
-    launch_strict(strict, ndlqr::box_adjoint_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, (const double*)c->box_lo,
-                  (const double*)c->box_hi, c->box_bstride, (const double*)c->box_v, (const int*)c->box_status,
-                  (const double*)c->adj_rhs, c->abox_code, c->abox_v, c->abox_y, c->abox_rhs[0], c->abox_rhs[1], c->abox_status,
-                  c->abox_iters, c->abox_word);
+    HIP_TRY(hipMemsetAsync(c->abox.word, 0, sizeof(int), st));
+    launch_strict(strict, ndlqr::box_adjoint_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, (const double*)c->box.lo,
+                  (const double*)c->box.hi, c->box.bstride, (const double*)c->box.v, (const int*)c->box.status,
+                  (const double*)c->adj.rhs, c->abox.code, c->abox.v, c->abox.y, c->abox.rhs[0], c->abox.rhs[1], c->abox.status,
+                  c->abox.iters, c->abox.word);
     HIP_TRY(hipGetLastError());
     // 4. the iterations (none when every problem's forward ended non-finite)
-    HIP_TRY(hipMemcpyAsync(&c->h_box_word[4], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&c->box.h_word[4], c->abox.word, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const bool any = c->h_box_word[4] > 0;
+    const bool any = c->box.h_word[4] > 0;
     for (int it = 1; it <= max_iter && any; ++it) {
-      const double* rc = c->abox_rhs[(it - 1) & 1];
-      double* rn = c->abox_rhs[it & 1];
-      e = launch_resolve(c, rc, c->adj_z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      const double* rc = c->abox.rhs[(it - 1) & 1];
+      double* rn = c->abox.rhs[it & 1];
+      e = launch_resolve(c, rc, c->adj.z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
       if (e) return e;
-      launch_strict(strict, ndlqr::box_adjoint_update, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj_z,
-                    (const unsigned char*)c->abox_code, c->abox_v, c->abox_y, (const double*)c->adj_rhs, rc, rn, rho,
-                    c->abox_status, c->abox_iters, c->abox_resid, c->abox_word);
+      launch_strict(strict, ndlqr::box_adjoint_update, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj.z,
+                    (const unsigned char*)c->abox.code, c->abox.v, c->abox.y, (const double*)c->adj.rhs, rc, rn, rho,
+                    c->abox.status, c->abox.iters, c->abox.resid, c->abox.word);
       HIP_TRY(hipGetLastError());
       if (it % check_every == 0 || it == max_iter) {
-        HIP_TRY(hipMemcpyAsync(&c->h_box_word[4], c->abox_word, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&c->box.h_word[4], c->abox.word, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (c->h_box_word[4] == 0) break;
+        if (c->box.h_word[4] == 0) break;
       }
     }
     if (!any) {  // (no re-solve ran: a defined w all the same -- the re-solve of the packed g)
-      e = launch_resolve(c, c->abox_rhs[0], c->adj_z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      e = launch_resolve(c, c->abox.rhs[0], c->adj.z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
       if (e) return e;
       HIP_TRY(hipGetLastError());
     }
     // 5. w = [lambda, v]
-    hipLaunchKernelGGL(ndlqr::box_adjoint_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, (const unsigned char*)c->abox_code,
-                       (const double*)c->abox_v, c->adj_z);
+    hipLaunchKernelGGL(ndlqr::box_adjoint_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, (const unsigned char*)c->abox.code,
+                       (const double*)c->abox.v, c->adj.z);
     HIP_TRY(hipGetLastError());
     return NDLQR_OK;
   };
@@ -2216,11 +2110,11 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
     return err;
   }
   HIP_TRY(hipEventRecord(s.ev_stop, st));
-  err = deliver_iters_status(c, st, c->abox_iters, c->abox_status, iters, status);
+  err = deliver_iters_status(c, st, c->abox.iters, c->abox.status, iters, status);
   if (err) return err;
   note_elapsed(c, s);
-  c->adj_gen = c->soln_gen;
-  c->abox_gen = c->soln_gen;
+  c->adj.gen = c->soln_gen;
+  c->abox.gen = c->soln_gen;
   return NDLQR_OK;
 }
 
@@ -2228,7 +2122,7 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
   if (!c) return NDLQR_ERR_INVALID;
   const int aerr = need_adjoint(c, "ndlqr_hip_bound_gradients");
   if (aerr) return aerr;
-  if (c->abox_gen != c->soln_gen)
+  if (c->abox.gen != c->soln_gen)
     return refuse("ndlqr_hip_bound_gradients: no box adjoint of the resident solution (ndlqr_hip_solve_box_adjoint after the "
                   "latest constrained solve)");
   const ndlqr::Dims& d = c->d;
@@ -2252,8 +2146,7 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
     nsplit = (d.batch + ppb - 1) / ppb;
   }
   const size_t npart = nsplit > 1 ? (size_t)nsplit * 2 * E : 0;
-  err = ensure_grad_stage(c, go.stage + npart);
-  if (err) return err;
+  HIP_TRY(c->grad_stage.grow(go.stage + npart));
   HIP_TRY(sync_all(c));
   BufferSet& s = c->set[0];
   ndlqr::BoundOut out = {};
@@ -2262,13 +2155,13 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
   for (int k = 0; k < 4; ++k) out.p[k] = go.dev[k];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   if (!summed) {
-    hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box_rho,
-                       (const unsigned char*)c->abox_code, (const double*)c->abox_y, out);
+    hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
+                       (const unsigned char*)c->abox.code, (const double*)c->abox.y, out);
     HIP_TRY(hipGetLastError());
   } else {
     hipLaunchKernelGGL(ndlqr::box_bound_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d,
-                       (const double*)c->box_rho, ppb,
-                       (const unsigned char*)c->abox_code, (const double*)c->abox_y, out, part);
+                       (const double*)c->box.rho, ppb,
+                       (const unsigned char*)c->abox.code, (const double*)c->abox.y, out, part);
     HIP_TRY(hipGetLastError());
     if (part) {
       hipLaunchKernelGGL(ndlqr::box_bound_sum_splits, dim3(nblk), dim3(256), 0, s.stream, u, nsplit, (const double*)part, out);
@@ -2292,11 +2185,7 @@ unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* c) { return c ? c->
 // z (+) delta over the old one, and the commit for the problems whose residual norm went down at every step so far. The
 // host reads nothing back between the steps: acceptance is decided on the device from the norm slots.
 
-constexpr int kRefineMaxSteps = 8;
-
-static int ensure_refine_r(NdlqrHipCtx* c) { return alloc_missing({{&c->ref_r, bytes_z(c->d)}}); }
-
-// r = b - K (z (+) delta) into c->ref_r on the current set's stream (norms == nullptr: the vector alone)
+// r = b - K (z (+) delta) into c->ref.r on the current set's stream (norms == nullptr: the vector alone)
 static int launch_residual_dd(NdlqrHipCtx* c, const double* rhs, const double* z, const double* delta,
                               unsigned long long* norms, int nslots, int slot) {
   const ndlqr::Dims& d = c->d;
@@ -2306,7 +2195,7 @@ static int launch_residual_dd(NdlqrHipCtx* c, const double* rhs, const double* z
   HIP_TRY(allow_dynamic_lds(&ndlqr::kkt_residual_dd, lds));
   const int threads = d.rows + d.n <= 64 ? 64 : (d.rows + d.n <= 128 ? 128 : 256);
   hipLaunchKernelGGL(ndlqr::kkt_residual_dd, dim3(d.N, d.batch), dim3(threads), lds, c->set[c->cur].stream, c->du, d,
-                     (const double*)c->AB, (const double*)c->QR, rhs, z, delta, c->ref_r, norms, nslots, slot, staged ? 1 : 0);
+                     (const double*)c->AB, (const double*)c->QR, rhs, z, delta, c->ref.r, norms, nslots, slot, staged ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return NDLQR_OK;
 }
@@ -2328,10 +2217,10 @@ struct RefinePhases {
   }
   // (the stream has been synchronised)
   void collect() {
-    for (int p = 0; p < 3; ++p) c->ref_phase_ms[p] = 0.0;
+    for (int p = 0; p < 3; ++p) c->ref.phase_ms[p] = 0.0;
     for (const Span& sp : spans) {
       float ms = 0.0f;
-      if (hipEventElapsedTime(&ms, sp.start, sp.stop) == hipSuccess) c->ref_phase_ms[sp.phase] += ms;
+      if (hipEventElapsedTime(&ms, sp.start, sp.stop) == hipSuccess) c->ref.phase_ms[sp.phase] += ms;
       c->event_pool.push_back(sp.start);
       c->event_pool.push_back(sp.stop);
     }
@@ -2352,7 +2241,7 @@ int ndlqr_hip_refine(NdlqrHipCtx* c, int which, int max_steps, int* steps, doubl
   if (which) {
     const int aerr = need_adjoint(c, who);
     if (aerr) return aerr;
-    if (c->abox_gen == c->soln_gen) return refuse(std::string(who) + ": the adjoint is that of a constrained solve");
+    if (c->abox.gen == c->soln_gen) return refuse(std::string(who) + ": the adjoint is that of a constrained solve");
   }
   const ndlqr::Dims& d = c->d;
   HIP_TRY(hipSetDevice(c->device));
@@ -2368,59 +2257,53 @@ int ndlqr_hip_refine(NdlqrHipCtx* c, int which, int max_steps, int* steps, doubl
   BufferSet& s = c->set[0];
   const hipStream_t st = s.stream;
   const int nslots = max_steps + 1;
-  const size_t norm_bytes = sizeof(unsigned long long) * 2 * (kRefineMaxSteps + 1) * (size_t)d.batch;
-  err = alloc_missing({{&c->ref_r, bytes_z(d)}, {&c->ref_norms, norm_bytes}, {&c->ref_steps, sizeof(int) * (size_t)d.batch},
-                       {&c->ref_eta, sizeof(double) * 2 * (size_t)d.batch},
-                       {&c->adj_save, sizeof(double) * 2 * (size_t)d.batch * d.N * d.n}});
-  if (err) return err;
-  if (!c->ref_delta) {
-    HIP_TRY(hipMalloc(&c->ref_delta, bytes_z(d)));
-    HIP_TRY(hipMemsetAsync(c->ref_delta, 0, bytes_z(d), st));  // (entries a re-solve does not write: the pad rows)
-  }
-  const double* rhs = which ? c->adj_rhs : s.rhs;
-  double* z = which ? c->adj_z : s.z;
+  const size_t norm_bytes = sizeof(unsigned long long) * RefineState::norm_count(d);
+  HIP_TRY(c->ref.ensure(d, st));
+  HIP_TRY(c->adj.ensure_save(d));
+  const double* rhs = which ? c->adj.rhs : s.rhs;
+  double* z = which ? c->adj.z : s.z;
   RefinePhases phases(c);
   HIP_TRY(hipEventRecord(s.ev_start, st));
-  HIP_TRY(hipMemsetAsync(c->ref_norms, 0, norm_bytes, st));
+  HIP_TRY(hipMemsetAsync(c->ref.norms, 0, norm_bytes, st));
   // 2. the residual of z as found
   phases.open(0);
-  err = launch_residual_dd(c, rhs, z, nullptr, c->ref_norms, nslots, 0);
+  err = launch_residual_dd(c, rhs, z, nullptr, c->ref.norms, nslots, 0);
   phases.close();
   if (err) return err;
   // 3. the steps
   for (int step = 1; step <= max_steps; ++step) {
     phases.open(1);
     HIP_TRY(adjoint_scratch(c, false));
-    err = launch_resolve(c, c->ref_r, c->ref_delta,
+    err = launch_resolve(c, c->ref.r, c->ref.delta,
                          "refinement: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
     if (err) return err;
     HIP_TRY(hipGetLastError());
     HIP_TRY(adjoint_scratch(c, true));
     phases.close();
     phases.open(0);
-    err = launch_residual_dd(c, rhs, z, c->ref_delta, c->ref_norms, nslots, step);
+    err = launch_residual_dd(c, rhs, z, c->ref.delta, c->ref.norms, nslots, step);
     phases.close();
     if (err) return err;
     phases.open(2);
     hipLaunchKernelGGL(ndlqr::refine_commit, dim3((unsigned)((d.N * d.rows + 255) / 256), d.batch), dim3(256), 0, st, d,
-                       (const unsigned long long*)c->ref_norms, step, (const double*)c->ref_delta, z);
+                       (const unsigned long long*)c->ref.norms, step, (const double*)c->ref.delta, z);
     phases.close();
     HIP_TRY(hipGetLastError());
   }
   // 4. what the caller asked for
   hipLaunchKernelGGL(ndlqr::refine_report, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, max_steps,
-                     (const unsigned long long*)c->ref_norms, c->ref_steps, c->ref_eta);
+                     (const unsigned long long*)c->ref.norms, c->ref.steps, c->ref.eta);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   if (!which) note_solution(c);  // (a refined primal is a new resident solution: an earlier adjoint no longer applies)
   for (int k = 0; k < 2; ++k)
     if (ea.user[k]) {
-      if (ea.own[k]) HIP_TRY(hipMemcpyAsync(ea.user[k], c->ref_eta + (size_t)k * d.batch, sizeof(double) * d.batch, hipMemcpyDeviceToDevice, st));
-      else HIP_TRY(hipMemcpyAsync(ea.user[k], c->ref_eta + (size_t)k * d.batch, sizeof(double) * d.batch, hipMemcpyDeviceToHost, st));
+      if (ea.own[k]) HIP_TRY(hipMemcpyAsync(ea.user[k], c->ref.eta + (size_t)k * d.batch, sizeof(double) * d.batch, hipMemcpyDeviceToDevice, st));
+      else HIP_TRY(hipMemcpyAsync(ea.user[k], c->ref.eta + (size_t)k * d.batch, sizeof(double) * d.batch, hipMemcpyDeviceToHost, st));
     }
   if (steps) {
     const bool own = where(steps, c->device) == Where::OwnDevice;
-    HIP_TRY(hipMemcpyAsync(steps, c->ref_steps, sizeof(int) * (size_t)d.batch, own ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(steps, c->ref.steps, sizeof(int) * (size_t)d.batch, own ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));
   note_elapsed(c, s);
@@ -2430,7 +2313,7 @@ int ndlqr_hip_refine(NdlqrHipCtx* c, int which, int max_steps, int* steps, doubl
 
 int ndlqr_hip_refine_phase_ms(NdlqrHipCtx* c, double* out3) {
   if (!c || !out3) return NDLQR_ERR_INVALID;
-  for (int p = 0; p < 3; ++p) out3[p] = c->ref_phase_ms[p];
+  for (int p = 0; p < 3; ++p) out3[p] = c->ref.phase_ms[p];
   return NDLQR_OK;
 }
 
@@ -2442,18 +2325,18 @@ int ndlqr_hip_kkt_residual_vector(NdlqrHipCtx* c, double* r) {
   if (wr == Where::OtherDevice)
     return refuse("ndlqr_hip_kkt_residual_vector: r lies in the memory of another device than the solver's");
   HIP_TRY(sync_all(c));
-  int err = ensure_refine_r(c);
-  if (err) return err;
+  HIP_TRY(c->ref.ensure_r(c->d));
+  int err;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   err = launch_residual_dd(c, s.rhs, c->set[c->latest].z, nullptr, nullptr, 0, 0);
   if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   if (wr != Where::OwnDevice) {
-    err = download_packed(c, c->ref_r, 0, c->d.batch, r);
+    err = download_packed(c, c->ref.r, 0, c->d.batch, r);
     if (err) return err;
   } else {
-    HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->ref_r, r, s.stream, c->d.batch));
+    HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->ref.r, r, s.stream, c->d.batch));
     HIP_TRY(hipStreamSynchronize(s.stream));
   }
   note_elapsed(c, s);
@@ -2486,7 +2369,6 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
                   "size-specialised shape (level-per-launch schedule: batch x N / 4 > 2048, or NDLQR_TREE=0)");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
-  const size_t nvars = (size_t)u.rows * u.N - u.m;
   // sets of right-hand sides per chunk: the chunk's count rides on gridDim.y, and its buffers stay within ~2 GB
   size_t per_set = (size_t)d.batch;
   size_t sets = 65535 / per_set;
@@ -2494,30 +2376,10 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
   while (sets > 1 && sets * per_set * bytes_per > ((size_t)2 << 30)) sets >>= 1;
   if (sets > (size_t)nrhs) sets = (size_t)nrhs;
   if (sets == 0) return NDLQR_ERR_INVALID;
-  const size_t cap = sets * per_set;
-  if (c->multi_cap < cap) {
-    (void)hipFree(c->multi_rhs); (void)hipFree(c->multi_z); (void)hipFree(c->multi_zsep); (void)hipFree(c->multi_fsum);
-    (void)hipFree(c->multi_ytop); (void)hipFree(c->multi_in); (void)hipFree(c->multi_out);
-    c->multi_rhs = c->multi_z = c->multi_zsep = c->multi_fsum = c->multi_ytop = c->multi_in = c->multi_out = nullptr;
-    c->multi_cap = 0;
-    const size_t nz = cap * d.N * d.rows;
-    const size_t nin = cap * ((size_t)u.N * (2 * u.n + u.m) + u.n);
-    bool ok = hipMalloc(&c->multi_rhs, sizeof(double) * nz) == hipSuccess &&
-              hipMalloc(&c->multi_z, sizeof(double) * nz) == hipSuccess &&
-              hipMalloc(&c->multi_zsep, sizeof(double) * cap * d.N * d.n) == hipSuccess &&
-              hipMalloc(&c->multi_fsum, sizeof(double) * cap * (d.N / 8) * 2 * d.n) == hipSuccess &&
-              hipMalloc(&c->multi_ytop, sizeof(double) * cap * (d.N / 8) * d.n) == hipSuccess &&
-              hipMalloc(&c->multi_in, sizeof(double) * nin) == hipSuccess &&
-              hipMalloc(&c->multi_out, sizeof(double) * cap * nvars) == hipSuccess;
-    // (padded shapes: the pad entries of the right-hand side are zero and stay zero -- the pack kernel never touches them)
-    ok = ok && hipMemsetAsync(c->multi_rhs, 0, sizeof(double) * nz, st.stream) == hipSuccess &&
-         hipMemsetAsync(c->multi_z, 0, sizeof(double) * nz, st.stream) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      g_last_error = "buffers of the multiple right-hand sides do not fit on the device";
-      return NDLQR_ERR_INVALID;
-    }
-    c->multi_cap = cap;
+  if (c->multi.ensure(d, u, sets * per_set, st.stream) != hipSuccess) {
+    (void)hipGetLastError();
+    g_last_error = "buffers of the multiple right-hand sides do not fit on the device";
+    return NDLQR_ERR_INVALID;
   }
   double total_ms = 0.0;
   for (size_t s0 = 0; s0 < (size_t)nrhs; s0 += sets) {
@@ -2525,23 +2387,23 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
     ndlqr::Dims uc = u, dc = d;
     uc.batch = dc.batch = (int)count;  // (the pack kernels index problems by their position alone)
     const size_t nq = count * u.N * u.n, nr = count * u.N * u.m, nx = count * u.n;
-    double* in = c->multi_in;
+    double* in = c->multi.in;
     HIP_TRY(hipMemcpyAsync(in, q + s0 * per_set * u.N * u.n, sizeof(double) * nq, hipMemcpyHostToDevice, st.stream));
     HIP_TRY(hipMemcpyAsync(in + nq, r + s0 * per_set * u.N * u.m, sizeof(double) * nr, hipMemcpyHostToDevice, st.stream));
     HIP_TRY(hipMemcpyAsync(in + nq + nr, dd + s0 * per_set * u.N * u.n, sizeof(double) * nq, hipMemcpyHostToDevice, st.stream));
     HIP_TRY(hipMemcpyAsync(in + 2 * nq + nr, x0 + s0 * per_set * u.n, sizeof(double) * nx, hipMemcpyHostToDevice, st.stream));
     hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic, dim3(512), dim3(256), 0, st.stream, uc, dc, (const double*)in,
-                       (const double*)(in + nq), (const double*)(in + nq + nr), (const double*)(in + 2 * nq + nr), c->multi_rhs);
+                       (const double*)(in + nq), (const double*)(in + nq + nr), (const double*)(in + 2 * nq + nr), c->multi.rhs);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.ev_start, st.stream));
     const ApplySlice apply_slice(c, sel);
-    if (!inst->multi(c, (int)count, c->multi_rhs, c->multi_zsep, c->multi_fsum, c->multi_ytop, c->multi_z)) {
+    if (!inst->multi(c, (int)count, c->multi.rhs, c->multi.zsep, c->multi.fsum, c->multi.ytop, c->multi.z)) {
       g_last_error = "multiple right-hand sides: this shape / horizon has no such form";
       return NDLQR_ERR_INVALID;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.ev_stop, st.stream));
-    const int derr = deliver(uc, dc, sel, c->multi_z, soln + s0 * per_set * sel.doubles(u), false, c->multi_out,
+    const int derr = deliver(uc, dc, sel, c->multi.z, soln + s0 * per_set * sel.doubles(u), false, c->multi.out,
                              hipMemcpyDeviceToHost, st.stream, (unsigned)count);
     if (derr) return derr;
     HIP_TRY(hipStreamSynchronize(st.stream));
@@ -2630,8 +2492,7 @@ static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
-  const int xerr = ensure_xfer(c);
-  if (xerr) return xerr;
+  HIP_TRY(s.ensure_xfer(c->du));
   const size_t nvars = (size_t)c->du.rows * d.N - c->du.m, pitch = (size_t)d.rows * d.N;
   hipStream_t st = s.stream;
   HIP_TRY(launch_pack(c->du, d, KnotSlice(), zsrc + p0 * pitch, s.xfer, st, count));
@@ -2648,7 +2509,7 @@ static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count
     return NDLQR_OK;
   }
   for (int i = 0; i < 2; ++i)
-    if (!c->h_stage[i]) HIP_TRY(hipHostMalloc((void**)&c->h_stage[i], sizeof(double) * chunk, hipHostMallocDefault));
+    HIP_TRY(c->h_stage[i].ensure(chunk));
   hipEvent_t done[2] = {take_event(c), take_event(c)};
   const size_t nchunks = (total + chunk - 1) / chunk;
   hipError_t e = hipSuccess;
@@ -2690,7 +2551,7 @@ int ndlqr_hip_kkt_residual(NdlqrHipCtx* c, double* res, double* bnorm) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->kkt_out) HIP_TRY(hipMalloc(&c->kkt_out, sizeof(double) * 2 * (size_t)d.batch));
+  HIP_TRY(c->kkt_out.ensure(2 * (size_t)d.batch));
   double* out = c->kkt_out;
   HIP_TRY(sync_all(c));
   hipLaunchKernelGGL(ndlqr::kkt_residual_generic, dim3(d.batch), dim3(256), 0, s.stream, d, c->AB, c->QR, s.rhs,
@@ -2715,8 +2576,7 @@ int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
   const double* zp = c->set[c->latest].z + p * pitch;
   if (c->padded) {
     const size_t upitch = (size_t)c->du.rows * d.N;
-    const int serr = ensure_pad_stage(c, upitch);
-    if (serr) return serr;
+    HIP_TRY(c->grow_pad_stage(upitch));
     hipLaunchKernelGGL(ndlqr::unpad_blocks_generic, dim3(d.N), dim3(64), 0, s.stream, c->du, d, zp, c->pad_stage);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(z_full, c->pad_stage, sizeof(double) * upitch, hipMemcpyDeviceToHost, s.stream));
@@ -2765,9 +2625,8 @@ int ndlqr_hip_download_factors(NdlqrHipCtx* c, int p, double* fact) {
 // an OpenMP team, test/parallel_test.c:30-239) run side by side on different scratches.
 namespace {
 struct DenseScratch {
-  double* dev = nullptr;
-  double* host = nullptr;
-  size_t cap = 0;  // doubles
+  DevBuf<double> dev;       // both of one capacity, grown on demand
+  PinnedBuf<double> host;
   hipStream_t stream = nullptr;
   int device = -1;  // the device its stream and buffer live on: leased only to calls whose current device is this one
 };
@@ -2795,15 +2654,10 @@ struct DenseLease {
   }
   int ensure(size_t doubles) {
     if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (doubles <= s->cap) return NDLQR_OK;
-    size_t cap = s->cap ? s->cap : 4096;
+    size_t cap = s->host.count() ? s->host.count() : 4096;
     while (cap < doubles) cap *= 2;
-    if (s->dev) { (void)hipFree(s->dev); s->dev = nullptr; }
-    if (s->host) { (void)hipHostFree(s->host); s->host = nullptr; }
-    s->cap = 0;
-    HIP_TRY(hipMalloc(&s->dev, sizeof(double) * cap));
-    HIP_TRY(hipHostMalloc((void**)&s->host, sizeof(double) * cap, hipHostMallocDefault));
-    s->cap = cap;
+    HIP_TRY(s->dev.grow(cap));
+    HIP_TRY(s->host.grow(cap));
     return NDLQR_OK;
   }
 };
