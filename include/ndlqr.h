@@ -603,6 +603,47 @@ int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho);
  *   input upload or ndlqr_BatchSetBounds since --, and any later solve invalidates it (as the plain adjoint). Blocking. */
 int ndlqr_SolveBatchBoxAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrBoxSettings* s, int* iters, int* status);
 int ndlqr_BatchBoundGradients(NdLqrBatchSolver* bs, unsigned flags, double* gxlo, double* gxhi, double* gulo, double* guhi);
+/* additive: active-set polish of the latest constrained solve. ADMM run to a loose tolerance has
+ * usually found the active set A; the constrained solution then solves K z + E_A' mu = b, E_A z = c_A, and
+ * ndlqr_PolishBatchBoxConstrained solves that system directly: it reads A off the iterate (an entry is active at hi when
+ * v == hi and y > 0, or lo == hi; at lo when v == lo and y < 0: exact comparisons), factors Q, R + sigma_p on the entries
+ * of A once (sigma_p = sigma x the largest entry of diag Q, R of problem p), and takes up to max_steps steps of
+ *     r = (b - E_A' mu) - K z  in double-double,   re-solve of r,   z += delta,   mu_A += sigma_p delta_A,   z_A = c_A exactly,
+ * a step counting only while the residual norm fell at every step so far (the rule of ndlqr_RefineBatch). Each problem's
+ * last accepted iterate is then validated -- mu >= 0 at an upper bound, <= 0 at a lower one, lo <= z <= hi on the free
+ * bounded entries, all exact --; where that fails and rounds remain, wrong-signed entries are released, entries outside
+ * their box are fixed at the violated bound, and the batch is shifted and factored again (at most max_rounds times).
+ * steps[p], status[p] (each may be NULL; host, pinned or the solver's device memory): the accepted steps; 1 = polished: the
+ * resident solution is the polished [lambda, x, u] -- every bound holds exactly, active entries sit on their bound bit
+ * for bit --, ndlqr_CopyBatchBoundMultipliers returns the polished mu, and v, y of the next warm start are the polished
+ * point; 2 = not polished (no accepted step, or the set was still invalid after the last round) and 3 = not finite (or the
+ * constrained solve's status was 3): solution, v, y and mu stay bit for bit what the constrained solve left.
+ *   Returns NDLQR_ERR_INVALID unless the resident solution is that of the latest ndlqr_SolveBatchBoxConstrained (no solve,
+ *   step, re-solve, polish, input upload or ndlqr_BatchSetBounds since). A polish counts as a new solution; it replaces the
+ *   remembered ADMM factorisation by its own, so the next constrained solve factors once and ndlqr_SolveBatchBoxAdjoint
+ *   refuses; the plain re-solves, the multi-rhs solves and the plain adjoint refuse until the next ndlqr_SolveBatch, as
+ *   after the constrained solve. The resident A, B, Q, R, q, r, d, x0 are unchanged on every exit. A non-positive pivot
+ *   returns NDLQR_ERR_NOT_SPD with nothing remembered and no resident solution, as for the constrained solve. Strict mode
+ *   is bit-reproducible (DESIGN.md section 3.13 gives the operation order). Blocking; ndlqr_BatchSolveTimeMs then reports
+ *   the device time of the whole call. */
+#define NDLQR_POLISH_DEFAULT_SIGMA 1e8
+typedef struct {
+  double sigma;    /* penalty on active entries relative to the problem's largest diag(Q,R) entry; 0 -> NDLQR_POLISH_DEFAULT_SIGMA */
+  int max_steps;   /* 0 -> 8; at most 32 */
+  int max_rounds;  /* active-set correction rounds, each at most one refactorisation; 0 -> 3 */
+} NdLqrPolishSettings;  /* NULL / zero-initialised = defaults */
+int ndlqr_PolishBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrPolishSettings* s, int* steps, int* status);
+/* additive: the adjoint of the polished solution. After a polish, for g = dL/dz* as for ndlqr_SolveBatchAdjoint,
+ * ndlqr_SolveBatchPolishedAdjoint solves K w + E_A' nu = g, E_A w = 0 on the polish's final active set and its remembered
+ * factorisation by the loop of the polish -- right-hand side g, c = 0, start w = nu = 0, up to max_steps steps under the
+ * same acceptance rule; nothing is factored, no rounds; sigma and max_rounds of the settings are ignored. steps[p],
+ * status[p]: 1 = solved; a problem whose polish status is not 1 reports that status (2 or 3) and gets w = 0, nu = 0; 2 also
+ * when no step was accepted. Afterwards ndlqr_CopyBatchAdjoint and ndlqr_BatchGradients work as after the box adjoint,
+ * and ndlqr_BatchBoundGradients returns nu split by the polish codes (same layouts, same deterministic batch sums).
+ * NDLQR_ERR_INVALID unless the resident solution is that of the latest polish and its factorisation is still remembered
+ * (no solve, step, re-solve, input upload or ndlqr_BatchSetBounds since). g, steps, status: host, pinned or the solver's
+ * device memory. Nothing of the polish changes. Blocking; ndlqr_BatchSolveTimeMs reports the device time of the call. */
+int ndlqr_SolveBatchPolishedAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrPolishSettings* s, int* steps, int* status);
 void* ndlqr_BatchDeviceContext(NdLqrBatchSolver* bs);      /* NdlqrHipCtx* (ndlqr_hip.h) */
 
 /* Seeded synthetic problem generator (host, bit-reproducible). */

@@ -142,6 +142,17 @@ unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* ctx);
 int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* ctx, const double* g, double alpha, double eps_abs, double eps_rel, int max_iter,
                                 int check_every, int* iters, int* status);
 int ndlqr_hip_bound_gradients(NdlqrHipCtx* ctx, int summed, double* gxlo, double* gxhi, double* gulo, double* guhi);
+/* Active-set polish of the latest constrained solve (ndlqr.h: ndlqr_PolishBatchBoxConstrained).
+ * ndlqr_hip_polish_box takes the resolved settings (sigma > 0, 1 <= max_steps <= 32, max_rounds >= 0) and blocks; steps /
+ * status [batch] may be NULL (host, pinned or this device's memory). ndlqr_hip_download_polish_codes: the entry codes of
+ * the latest polish, [batch][N][n+m] bytes into host memory (0 unbounded, 1 free, 2 at the lower bound, 3 at the upper). */
+int ndlqr_hip_polish_box(NdlqrHipCtx* ctx, double sigma, int max_steps, int max_rounds, int* steps, int* status);
+/* ... and its adjoint on the remembered polish factorisation (ndlqr.h: ndlqr_SolveBatchPolishedAdjoint): g as for
+ * ndlqr_hip_solve_adjoint (host, pinned or this device's memory), 1 <= max_steps <= 32; blocks. Afterwards
+ * ndlqr_hip_download_adjoint, ndlqr_hip_gradients and ndlqr_hip_bound_gradients read its w and nu. */
+int ndlqr_hip_solve_polished_adjoint(NdlqrHipCtx* ctx, const double* g, int max_steps, int* steps, int* status);
+/* developer / test hook, not for production use (a blocking copy and a repack on the host): the entry codes */
+int ndlqr_hip_download_polish_codes(NdlqrHipCtx* ctx, unsigned char* codes);
 /* Several right-hand sides per problem against one kept factorisation each (the reference's NdData holds a single
  * right-hand side, src/nddata.h:70-75): nrhs sets of right-hand sides for the whole batch, flat HOST arrays in the layout of
  * ndlqr_BatchSetRhsFlat with a leading [nrhs] -- q, d [nrhs][batch][N][n], r [nrhs][batch][N][m], x0 [nrhs][batch][n] --,

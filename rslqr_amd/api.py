@@ -130,6 +130,11 @@ BOUNDS_SHARED = 1
 _LIB = None
 
 
+class NdLqrPolishSettings(C.Structure):
+    """NdLqrPolishSettings of include/ndlqr.h"""
+    _fields_ = [("sigma", C.c_double), ("max_steps", C.c_int), ("max_rounds", C.c_int)]
+
+
 def library_path():
     return _build.LIB
 
@@ -284,6 +289,9 @@ def lib():
     proto("ndlqr_CopyBatchBoxPenalties", ci, vp, dp)
     proto("ndlqr_SolveBatchBoxAdjoint", ci, vp, dp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_BatchBoundGradients", ci, vp, C.c_uint, dp, dp, dp, dp)
+    proto("ndlqr_PolishBatchBoxConstrained", ci, vp, C.POINTER(NdLqrPolishSettings), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_hip_download_polish_codes", ci, vp, C.POINTER(C.c_ubyte))
+    proto("ndlqr_SolveBatchPolishedAdjoint", ci, vp, dp, C.POINTER(NdLqrPolishSettings), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_hip_factor_count", C.c_ulonglong, vp)
     # shim bits used by the benchmark
     proto("ndlqr_hip_set_stream", ci, vp, vp)
@@ -760,6 +768,50 @@ class BatchSolver:
         err = self.L.ndlqr_BatchBoundGradients(self.h, BOUNDS_SHARED if summed else 0, *ptrs)
         if err:
             raise RuntimeError("ndlqr_BatchBoundGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    # ---- active-set polish (include/ndlqr.h: ndlqr_PolishBatchBoxConstrained)
+    def polish_box(self, sigma=0.0, max_steps=0, max_rounds=0, steps=None, status=None):
+        """ndlqr_PolishBatchBoxConstrained on the latest constrained solve (0 = the library's default for every setting).
+        Returns (steps, status) as numpy int arrays [batch] (or the DeviceArray-like destinations given); status 1 =
+        polished, 2 = not polished (the ADMM solution stays), 3 = not finite. Raises on a nonzero return."""
+        st = NdLqrPolishSettings(sigma, int(max_steps), int(max_rounds))
+        if steps is None:
+            steps = np.zeros(self.batch, dtype=np.int32)
+        if status is None:
+            status = np.zeros(self.batch, dtype=np.int32)
+        as_int = lambda a: C.cast(a.ptr, C.POINTER(C.c_int)) if hasattr(a, "ptr") else a.ctypes.data_as(C.POINTER(C.c_int))
+        err = self.L.ndlqr_PolishBatchBoxConstrained(self.h, C.byref(st), as_int(steps), as_int(status))
+        if err:
+            raise RuntimeError("ndlqr_PolishBatchBoxConstrained failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return steps, status
+
+    def solve_polished_adjoint(self, g, max_steps=0, steps=None, status=None):
+        """ndlqr_SolveBatchPolishedAdjoint: the adjoint of the polished active-set system for g = dL/dz* [batch, nvars]
+        (numpy array or DeviceArray) on the polish's factorisation. Returns (steps, status); status 1 = solved, 2 / 3 = the
+        polish status of a problem that was not polished (its w and nu are 0), or 2 = no step accepted. Raises on a nonzero
+        return. Afterwards adjoint(), gradients() and bound_gradients() read its w and nu."""
+        if not hasattr(g, "ptr"):
+            g = np.ascontiguousarray(g, dtype=np.float64)
+        st = NdLqrPolishSettings(0.0, int(max_steps), 0)
+        if steps is None:
+            steps = np.zeros(self.batch, dtype=np.int32)
+        if status is None:
+            status = np.zeros(self.batch, dtype=np.int32)
+        as_int = lambda a: C.cast(a.ptr, C.POINTER(C.c_int)) if hasattr(a, "ptr") else a.ctypes.data_as(C.POINTER(C.c_int))
+        err = self.L.ndlqr_SolveBatchPolishedAdjoint(self.h, _any_ptr(g, self.batch * self.nvars), C.byref(st), as_int(steps),
+                                                     as_int(status))
+        if err:
+            raise RuntimeError("ndlqr_SolveBatchPolishedAdjoint failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return steps, status
+
+    def polish_codes(self):
+        """developer / test hook: entry codes [batch, N, n+m] of the latest polish (0 unbounded, 1 free, 2 at the lower bound, 3 at the upper)"""
+        out = np.zeros((self.batch, self.N, self.n + self.m), dtype=np.uint8)
+        err = self.L.ndlqr_hip_download_polish_codes(self.ctx, out.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        if err:
+            raise RuntimeError("ndlqr_hip_download_polish_codes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
 
     def factor_count(self):

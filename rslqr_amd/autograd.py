@@ -258,7 +258,7 @@ def _solve_box(bs, flat, bflat, all_shared, settings, token, key):
     err = bs.L.ndlqr_BatchSetBounds(bs.h, BOUNDS_SHARED if all_shared else 0, *ptrs)
     if err:
         raise ValueError("lqr_solve_box: the bounds were refused (%s)" % bs.L.ndlqr_hip_last_error().decode())
-    rho, alpha, eps_abs, eps_rel, max_iter, adapt_every = settings
+    rho, alpha, eps_abs, eps_rel, max_iter, adapt_every, polish = settings
     try:
         _, status = bs.solve_box(rho=rho, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
                                  adapt_every=adapt_every)
@@ -269,6 +269,16 @@ def _solve_box(bs, flat, bflat, all_shared, settings, token, key):
         raise RuntimeError("lqr_solve_box: %d of %d problems did not converge (status %s): raise max_iter, change rho or "
                            "set adapt_every (the per-problem adaptive penalty)"
                            % (bad, status.size, sorted(set(status.tolist()) - {1})))
+    if polish:
+        try:
+            _, status = bs.polish_box()
+        except RuntimeError as e:
+            raise RuntimeError("lqr_solve_box: the polish failed (%s)" % e) from None
+        bad = int((status != 1).sum())
+        if bad:
+            raise RuntimeError("lqr_solve_box: %d of %d problems were not polished (status %s): the active set ADMM left "
+                               "was not corrected within the rounds; tighten eps_abs / eps_rel"
+                               % (bad, status.size, sorted(set(status.tolist()) - {1})))
     _box_cache[key][1] = token
 
 
@@ -301,8 +311,11 @@ class LqrSolveBox(torch.autograd.Function):
             _solve_box(bs, ctx.flat, ctx.bflat, ctx.all_shared, ctx.settings, ctx.token, ctx.key)
         gz = gz.detach().to(torch.float64).contiguous()
         torch.cuda.current_stream(gz.device).synchronize()
-        _, alpha, eps_abs, eps_rel, max_iter, _ = ctx.settings
-        _, status = bs.solve_box_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter)
+        _, alpha, eps_abs, eps_rel, max_iter, _, polish = ctx.settings
+        if polish:
+            _, status = bs.solve_polished_adjoint(_View(gz))
+        else:
+            _, status = bs.solve_box_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter)
         bad = int((status != 1).sum())
         if bad:
             raise RuntimeError("lqr_solve_box backward: the adjoint of %d of %d problems did not converge (status %s)"
@@ -342,7 +355,7 @@ class LqrSolveBox(torch.autograd.Function):
 
 
 def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=None, *, rho=0.0, alpha=0.0, eps_abs=0.0,
-                  eps_rel=0.0, max_iter=0, adapt_every=0):
+                  eps_rel=0.0, max_iter=0, adapt_every=0, polish=False):
     """z* [b, nvars] of the LQR problems of lqr_solve with xlo <= x_k <= xhi (k >= 1) and ulo <= u_k <= uhi, by the
     box-constrained batch solve (ndlqr_SolveBatchBoxConstrained, cold start; 0 = the library's default for every
     setting; adapt_every > 0: the per-problem adaptive penalty, considered every that many iterations, so that rho
@@ -350,8 +363,12 @@ def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=Non
     active-set system (ndlqr_SolveBatchBoxAdjoint) with the same settings, on the penalties the forward ended with. Bounds: None (unbounded), [N, n] / [N, m] shared by every problem
     or [b, N, n] / [b, N, m]; entries may be +-inf. Raises RuntimeError when a problem's forward or adjoint iteration
     does not converge (status != 1). The gradients hold where the active set is locally stable (strict
-    complementarity); at a degenerate active set the bound gradients are one of many."""
-    return LqrSolveBox.apply((float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(adapt_every)),
+    complementarity); at a degenerate active set the bound gradients are one of many.
+    polish=True: the forward is ADMM followed by the active-set polish (ndlqr_PolishBatchBoxConstrained, default
+    settings), so a loose eps_abs / eps_rel such as 1e-3 suffices, and the backward is the polished adjoint
+    (ndlqr_SolveBatchPolishedAdjoint) with the same gradient assembly; raises when a problem's polish status is not 1."""
+    return LqrSolveBox.apply((float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(adapt_every),
+                              bool(polish)),
                              A, B, Q, R, q, r, d, x0, xlo, xhi, ulo, uhi)
 
 

@@ -418,6 +418,23 @@ int ndlqr_BatchBoundGradients(NdLqrBatchSolver* bs, unsigned flags, double* gxlo
   if (!bs || (flags & ~NDLQR_BOUNDS_SHARED)) return NDLQR_ERR_INVALID;
   return ndlqr_hip_bound_gradients(bs->ctx, (flags & NDLQR_BOUNDS_SHARED) ? 1 : 0, gxlo, gxhi, gulo, guhi);
 }
+int ndlqr_PolishBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrPolishSettings* s, int* steps, int* status) {
+  NdLqrPolishSettings z;
+  if (!bs) return NDLQR_ERR_INVALID;
+  memset(&z, 0, sizeof(z));
+  if (s) z = *s;
+  if (!(z.sigma >= 0.0) || z.max_steps < 0 || z.max_rounds < 0) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_polish_box(bs->ctx, z.sigma > 0.0 ? z.sigma : NDLQR_POLISH_DEFAULT_SIGMA, z.max_steps > 0 ? z.max_steps : 8,
+                              z.max_rounds > 0 ? z.max_rounds : 3, steps, status);
+}
+int ndlqr_SolveBatchPolishedAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrPolishSettings* s, int* steps, int* status) {
+  NdLqrPolishSettings z;
+  if (!bs || !g) return NDLQR_ERR_INVALID;
+  memset(&z, 0, sizeof(z));
+  if (s) z = *s;
+  if (z.max_steps < 0) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_solve_polished_adjoint(bs->ctx, g, z.max_steps > 0 ? z.max_steps : 8, steps, status);
+}
 int ndlqr_CopyBatchFactors(NdLqrBatchSolver* bs, int p, double* fact) {
   if (!bs || !fact || p < 0 || p >= bs->batch) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_factors(bs->ctx, p, fact);

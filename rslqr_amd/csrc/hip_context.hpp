@@ -279,6 +279,45 @@ struct RefineState {
   }
 };
 
+// Active-set polish of a constrained solve (ndlqr_hip_polish_box, kernels_box_polish.hpp). Entry codes (bytes) and mu in
+// the layout of the bounds; the accepted iterate z | mu | bt (bt: the right-hand side b - E_A' mu of the residual) and the
+// candidate zc | muc | btc; z0: the resident solution as found (the factorisations overwrite it); r, delta: residual and
+// correction; norms: the slots of one round, [2][kPolishMaxSteps + 1][batch] as RefineState's; sig [batch]; per problem
+// its state (what the caller gets as status), its accepted steps and those of the current round; word: running count |
+// problems whose set changed (h_word: the same). The factorisation of the last round is remembered (fact) with its flags
+// and what it left (kept) for the adjoint on the same system; whatever drops box.fact drops it (forget_shifted).
+// soln_gen: the solution generation the latest polish left (0: none). The adjoint on the same system
+// (ndlqr_hip_solve_polished_adjoint) shares the candidate, residual, correction and norm buffers.
+constexpr int kPolishMaxSteps = 32;
+struct PolishState {
+  DevBuf<unsigned char> code;
+  DevBuf<double> z, mu, bt, zc, muc, btc, z0, r, delta, sig;
+  DevBuf<double> nu, abt, ones;      // the adjoint's multipliers and right-hand side (its w is adj.z); 1.0 [batch]
+  DevBuf<int> astate, asteps, ahere;  // ... its states and steps
+  unsigned long long adj_gen = 0;     // the solution generation the polished adjoint belongs to (0: none)
+  DevBuf<unsigned long long> norms;
+  DevBuf<int> state, steps, here, word;
+  PinnedBuf<int> h_word;
+  bool fact = false;
+  unsigned flags = 0;
+  KeptState kept;
+  unsigned long long soln_gen = 0;
+  static size_t norm_count(const ndlqr::Dims& d) { return 2 * (kPolishMaxSteps + 1) * (size_t)d.batch; }
+  hipError_t ensure(const ndlqr::Dims& d, hipStream_t st) {
+    const size_t nz = doubles_z(d), nv = doubles_QR(d), nb = (size_t)d.batch;
+    return first_error({code.ensure(nv), z.ensure(nz), mu.ensure(nv), bt.ensure(nz), zc.ensure(nz), muc.ensure(nv),
+                        btc.ensure(nz), z0.ensure(nz), r.ensure(nz),
+                        delta.ensure_zeroed(nz, st),  // (entries a re-solve does not write: the pad rows)
+                        sig.ensure(nb), norms.ensure(norm_count(d)), state.ensure(nb), steps.ensure(nb), here.ensure(nb),
+                        word.ensure(2), h_word.ensure(2)});
+  }
+  hipError_t ensure_adjoint(const ndlqr::Dims& d) {
+    const size_t nb = (size_t)d.batch;
+    return first_error({nu.ensure(doubles_QR(d)), abt.ensure(doubles_z(d)), ones.ensure(nb), astate.ensure(nb), asteps.ensure(nb),
+                        ahere.ensure(nb)});
+  }
+};
+
 // Several right-hand sides per problem (ndlqr_hip_solve_multi_rhs): buffers for `cap` right-hand sides ([cap] of the
 // right-hand side, the solution, z_sep, the pushed sums and the top multipliers; the caller-layout inputs and packed
 // solutions), grown on demand
@@ -358,8 +397,11 @@ struct NdlqrHipCtx {
   BoxState box;
   BoxAdjointState abox;
   RefineState ref;
+  PolishState pol;
   MultiRhsState multi;
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
+  // the remembered shifted factorisations (ADMM's and the polish's) no longer match the records / factors
+  void forget_shifted() { box.fact = pol.fact = false; }
   // profile
   std::vector<PendingEvent> pending;
   std::vector<hipEvent_t> event_pool;

@@ -12,6 +12,7 @@
 #include "kernels_generic.hpp"
 #include "kernels_box.hpp"
 #include "kernels_box_grad.hpp"
+#include "kernels_box_polish.hpp"
 #include "kernels_grad.hpp"
 #include "kernels_refine.hpp"
 #include "kernels_mfma.hpp"
@@ -388,7 +389,7 @@ static void note_new_inputs(NdlqrHipCtx* c) {
   next_solve_on_current_set(c);
   c->kept.forget_factorisation();
   c->inputs_replaced = true;
-  c->box.fact = false;
+  c->forget_shifted();
 }
 
 int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB, const double* QR,
@@ -957,7 +958,7 @@ static int launch_solve(NdlqrHipCtx* c, const SolvePlan& plan) {
   note_solution(c);
   c->kept = plan.kept;
   c->inputs_replaced = false;
-  c->box.fact = false;  // (the records / factors are those of the unshifted matrix now)
+  c->forget_shifted();  // (the records / factors are those of the unshifted matrix now)
   ++c->factor_count;
   return NDLQR_OK;
 }
@@ -1053,7 +1054,7 @@ int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
   if (err) return err;
   rhs_written_cur(c, 0xFu);
   c->kept.forget_factorisation();  // new A, B, Q, R: neither a cached factor array nor cached records match
-  c->box.fact = false;
+  c->forget_shifted();
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   err = (c->flags & NDLQR_FLAG_PROFILE) ? enqueue_staged(c, plan) : replay_chain(c, c->staged, plan, enqueue_staged);
@@ -1107,7 +1108,7 @@ int ndlqr_hip_time_shard_import(NdlqrHipCtx* c, int G, const double* buf) {
 }
 
 static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
-  if (c) c->box.fact = false;  // (the phases overwrite the records)
+  if (c) c->forget_shifted();  // (the phases overwrite the records)
   const SmallInstance* inst = time_shard_instance(c, G);
   if (!inst) {
     g_last_error = "time-axis sharding: needs a size-specialised block size with a matrix-core instance, G a power of two, "
@@ -1735,6 +1736,8 @@ int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const do
   HIP_TRY(hipMemcpyAsync(c->box.h_word, c->box.word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   if (c->box.h_word[3] || (bool)shared != c->box.shared || !c->box.have_bounds) c->box.fact = false;
+  c->pol.fact = false;  // (the polish belongs to the bounds it ran with)
+  c->pol.soln_gen = 0;
   c->box.soln_gen = 0;  // (a box adjoint needs the constrained solution of these bounds)
   c->box.shared = shared != 0;
   c->box.bstride = shared ? 0 : (size_t)d.N * d.w;
@@ -1750,8 +1753,10 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs
 
 // The shifted matrix factored on the primary set as a plain solve does it (the resident solution is overwritten), with
 // the pivot check: *not_spd = NDLQR_ERR_NOT_SPD, which is returned, when a pivot was not positive.
-static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd) {
-  c->box.fact = false;
+// (who, what: the entry point and the shifted matrix, for the message)
+static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd, const char* who = "ndlqr_hip_solve_box",
+                      const char* what = "Q + rho M, R + rho M") {
+  c->forget_shifted();
   SolvePlan plan;
   int err = prepare_solve(c, &plan);  // (KEEP_*: stream-ordered on the primary set)
   if (!err) err = launch_solve(c, plan);
@@ -1765,8 +1770,7 @@ static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd) {
   c->last_failures = seen - c->fail_base;
   c->fail_base = seen;
   if (c->last_failures > 0) {
-    refuse("ndlqr_hip_solve_box: " + std::to_string(c->last_failures) + " non-positive pivot(s) in the factorisation of "
-           "Q + rho M, R + rho M");
+    refuse(std::string(who) + ": " + std::to_string(c->last_failures) + " non-positive pivot(s) in the factorisation of " + what);
     return *not_spd = NDLQR_ERR_NOT_SPD;
   }
   return NDLQR_OK;
@@ -1789,18 +1793,27 @@ struct ShiftedQR {
     HIP_TRY(hipGetLastError());
     return NDLQR_OK;
   }
-  // QR saved, shifted by the penalties `rho` [batch] on the bounded entries, c->flags = flags
-  int open(const double* rho, unsigned flags) {
+  // QR saved, c->flags = flags; the caller shifts (the polish: by sigma on its active entries)
+  int open_unshifted(unsigned flags) {
     HIP_TRY(hipMemcpyAsync(c->box.qr_save, c->QR, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
     open_ = true;
-    const int err = shift(rho);
     c->flags = flags;
-    return err;
+    return NDLQR_OK;
+  }
+  // the saved QR again
+  int restore() {
+    HIP_TRY(hipMemcpyAsync(c->QR, c->box.qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
+    return NDLQR_OK;
+  }
+  // QR saved, shifted by the penalties `rho` [batch] on the bounded entries, c->flags = flags
+  int open(const double* rho, unsigned flags) {
+    const int err = open_unshifted(flags);
+    return err ? err : shift(rho);
   }
   // new penalties: the saved QR again, shifted by them
   int reshift(const double* rho) {
-    HIP_TRY(hipMemcpyAsync(c->QR, c->box.qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
-    return shift(rho);
+    const int err = restore();
+    return err ? err : shift(rho);
   }
   // the right-hand-side columns of the kept records, which the re-solves of an adjoint overwrite: restored by close()
   int save_record_columns() {
@@ -1882,7 +1895,7 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   HIP_TRY(hipEventRecord(s.ev_start, st));
   // 2. the penalties
   if (!reuse) {
-    c->box.fact = false;  // (the remembered factorisation belongs to the penalties overwritten here)
+    c->forget_shifted();  // (the remembered factorisation belongs to the penalties overwritten here)
     hipLaunchKernelGGL(ndlqr::box_fill_rho, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, rho, c->box.rho);
     HIP_TRY(hipGetLastError());
   }
@@ -1961,7 +1974,7 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
     c->box.flags = box_flags;
     c->box.kept = shifted_kept;
   } else {
-    c->box.fact = false;
+    c->forget_shifted();
     c->box.have_vy = false;
     if (!not_spd) c->state_dirty = true;  // (a failed launch; a non-positive pivot leaves the device state clean)
     if (factored) c->z_invalid = true;    // (the factorisation solved the shifted matrix with the unshifted right-hand side)
@@ -2001,8 +2014,12 @@ int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* m
   HIP_TRY(sync_all(c));
   const BufferSet& s = c->set[0];
   out.place(c);
-  hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
-                     (const double*)c->box.y, out.dev[0], out.dev[1]);
+  if (c->pol.soln_gen != 0 && c->pol.soln_gen == c->soln_gen)  // (a polished solution: its mu where the polish succeeded)
+    hipLaunchKernelGGL(ndlqr::polish_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
+                       (const double*)c->box.y, (const int*)c->pol.state, (const double*)c->pol.mu, out.dev[0], out.dev[1]);
+  else
+    hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
+                       (const double*)c->box.y, out.dev[0], out.dev[1]);
   HIP_TRY(hipGetLastError());
   err = out.copy(s.stream, false);
   if (err) return err;
@@ -2023,6 +2040,9 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
       check_every < 1)
     return NDLQR_ERR_INVALID;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_box_adjoint");
+  if (c->pol.soln_gen != 0 && c->pol.soln_gen == c->soln_gen)
+    return refuse("ndlqr_hip_solve_box_adjoint: the resident solution was polished (ndlqr_hip_polish_box), which replaced the "
+                  "ADMM factorisation: its adjoint is the polished adjoint (ndlqr_hip_solve_polished_adjoint)");
   if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.fact || c->inputs_replaced)
     return refuse("ndlqr_hip_solve_box_adjoint: the resident solution is not that of the latest constrained solve (a solve, "
                   "step, re-solve, new inputs or new bounds came after it)");
@@ -2122,9 +2142,13 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
   if (!c) return NDLQR_ERR_INVALID;
   const int aerr = need_adjoint(c, "ndlqr_hip_bound_gradients");
   if (aerr) return aerr;
-  if (c->abox.gen != c->soln_gen)
+  const bool polished = c->pol.adj_gen != 0 && c->pol.adj_gen == c->soln_gen;  // (nu split by the polish codes, penalty 1)
+  if (c->abox.gen != c->soln_gen && !polished)
     return refuse("ndlqr_hip_bound_gradients: no box adjoint of the resident solution (ndlqr_hip_solve_box_adjoint after the "
-                  "latest constrained solve)");
+                  "latest constrained solve, or ndlqr_hip_solve_polished_adjoint after the latest polish)");
+  const double* g_rho = polished ? c->pol.ones : c->box.rho;
+  const unsigned char* g_code = polished ? c->pol.code : c->abox.code;
+  const double* g_y = polished ? c->pol.nu : c->abox.y;
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
@@ -2155,13 +2179,11 @@ int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* 
   for (int k = 0; k < 4; ++k) out.p[k] = go.dev[k];
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   if (!summed) {
-    hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
-                       (const unsigned char*)c->abox.code, (const double*)c->abox.y, out);
+    hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, g_rho, g_code, g_y, out);
     HIP_TRY(hipGetLastError());
   } else {
     hipLaunchKernelGGL(ndlqr::box_bound_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d,
-                       (const double*)c->box.rho, ppb,
-                       (const unsigned char*)c->abox.code, (const double*)c->abox.y, out, part);
+                       g_rho, ppb, g_code, g_y, out, part);
     HIP_TRY(hipGetLastError());
     if (part) {
       hipLaunchKernelGGL(ndlqr::box_bound_sum_splits, dim3(nblk), dim3(256), 0, s.stream, u, nsplit, (const double*)part, out);
@@ -2186,8 +2208,9 @@ unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* c) { return c ? c->
 // host reads nothing back between the steps: acceptance is decided on the device from the norm slots.
 
 // r = b - K (z (+) delta) into c->ref.r on the current set's stream (norms == nullptr: the vector alone)
-static int launch_residual_dd(NdlqrHipCtx* c, const double* rhs, const double* z, const double* delta,
-                              unsigned long long* norms, int nslots, int slot) {
+// (QR: the diagonal to use -- the polish passes the saved, unshifted one --, r: the destination)
+static int launch_residual_dd_on(NdlqrHipCtx* c, const double* QR, const double* rhs, const double* z, const double* delta,
+                                 double* r, unsigned long long* norms, int nslots, int slot) {
   const ndlqr::Dims& d = c->d;
   const bool staged = ndlqr::refine_lds_bytes(d, true) + 64 <= kLdsMax;  // (+ the kernel's static words)
   const size_t lds = ndlqr::refine_lds_bytes(d, staged);
@@ -2195,9 +2218,15 @@ static int launch_residual_dd(NdlqrHipCtx* c, const double* rhs, const double* z
   HIP_TRY(allow_dynamic_lds(&ndlqr::kkt_residual_dd, lds));
   const int threads = d.rows + d.n <= 64 ? 64 : (d.rows + d.n <= 128 ? 128 : 256);
   hipLaunchKernelGGL(ndlqr::kkt_residual_dd, dim3(d.N, d.batch), dim3(threads), lds, c->set[c->cur].stream, c->du, d,
-                     (const double*)c->AB, (const double*)c->QR, rhs, z, delta, c->ref.r, norms, nslots, slot, staged ? 1 : 0);
+                     (const double*)c->AB, QR, rhs, z, delta, r, norms, nslots, slot, staged ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return NDLQR_OK;
+}
+
+// r = b - K (z (+) delta) into c->ref.r on the resident QR
+static int launch_residual_dd(NdlqrHipCtx* c, const double* rhs, const double* z, const double* delta,
+                              unsigned long long* norms, int nslots, int slot) {
+  return launch_residual_dd_on(c, c->QR, rhs, z, delta, c->ref.r, norms, nslots, slot);
 }
 
 // per-phase device times of a refinement under NDLQR_FLAG_PROFILE (ndlqr_hip_refine_phase_ms)
@@ -2241,7 +2270,8 @@ int ndlqr_hip_refine(NdlqrHipCtx* c, int which, int max_steps, int* steps, doubl
   if (which) {
     const int aerr = need_adjoint(c, who);
     if (aerr) return aerr;
-    if (c->abox.gen == c->soln_gen) return refuse(std::string(who) + ": the adjoint is that of a constrained solve");
+    if (c->abox.gen == c->soln_gen || c->pol.adj_gen == c->soln_gen)
+      return refuse(std::string(who) + ": the adjoint is that of a constrained solve");
   }
   const ndlqr::Dims& d = c->d;
   HIP_TRY(hipSetDevice(c->device));
@@ -2340,6 +2370,244 @@ int ndlqr_hip_kkt_residual_vector(NdlqrHipCtx* c, double* r) {
     HIP_TRY(hipStreamSynchronize(s.stream));
   }
   note_elapsed(c, s);
+  return NDLQR_OK;
+}
+
+
+// ------------------------------------------------------------------------------ active-set polish
+// ndlqr_hip_polish_box (kernels_box_polish.hpp): the active set read off the latest constrained
+// solve, QR shifted by sigma on its entries inside a ShiftedQR scope and factored as box_factor does, then per round up to
+// max_steps steps of residual (double-double, on the saved unshifted QR) -> re-solve -> polish_update, the validation of
+// every problem's last accepted iterate, and -- while a set changed and rounds remain -- the corrected sets shifted and
+// factored again. Nothing is read back between the launches of a step; one word per step tells whether a problem still
+// runs, two words per round whether a set changed.
+
+// the steps of one round on the current factorisation
+// the accepted iterate and what defines the system of a polish or of its adjoint (lo == nullptr: c = 0)
+struct PolishSystem {
+  const double* res;  // b
+  const double *lo, *hi;
+  double *z, *mu, *bt;
+  int *state, *here;
+};
+static int polish_steps(NdlqrHipCtx* c, hipStream_t st, bool strict, int max_steps, const PolishSystem& y) {
+  const ndlqr::Dims& d = c->d;
+  PolishState& p = c->pol;
+  const int nslots = max_steps + 1;
+  const double* qr = c->box.qr_save;  // (the unshifted diagonal)
+  HIP_TRY(hipMemsetAsync(p.norms, 0, sizeof(unsigned long long) * PolishState::norm_count(d), st));
+  int e = launch_residual_dd_on(c, qr, y.bt, y.z, nullptr, p.r, p.norms, nslots, 0);
+  if (e) return e;
+  for (int step = 1; step <= max_steps + 1; ++step) {
+    const int form = step <= max_steps;
+    if (form) {
+      e = launch_resolve(c, p.r, p.delta, "polish: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      if (e) return e;
+    }
+    launch_strict(strict, ndlqr::polish_update, dim3(d.batch), dim3(256), 0, st, d, step, form,
+                  (const unsigned long long*)p.norms, (const double*)p.sig, y.lo, y.hi, c->box.bstride,
+                  (const unsigned char*)p.code, y.res, (const double*)p.delta, y.z, y.mu, y.bt, p.zc, p.muc, p.btc, y.state,
+                  y.here, p.word);
+    HIP_TRY(hipGetLastError());
+    if (!form) break;
+    e = launch_residual_dd_on(c, qr, p.btc, p.zc, nullptr, p.r, p.norms, nslots, step);
+    if (e) return e;
+    if (step >= 2) {  // one word: how many problems still run
+      HIP_TRY(hipMemcpyAsync(p.h_word, p.word, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (p.h_word[0] == 0) break;
+    }
+  }
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_polish_box(NdlqrHipCtx* c, double sigma, int max_steps, int max_rounds, int* steps, int* status) {
+  if (!c || !(sigma > 0.0) || !(sigma < HUGE_VAL) || max_steps < 1 || max_steps > kPolishMaxSteps || max_rounds < 0)
+    return NDLQR_ERR_INVALID;
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_polish_box");
+  if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.have_vy || c->inputs_replaced)
+    return refuse("ndlqr_hip_polish_box: the resident solution is not that of the latest constrained solve (a solve, step, "
+                  "re-solve, polish, new inputs or new bounds came after it)");
+  if (c->box.kept.time_shard) return refuse("ndlqr_hip_polish_box: not available on a time-axis shard");
+  const ndlqr::Dims& d = c->d;
+  HIP_TRY(hipSetDevice(c->device));
+  int err = refuse_foreign_iters_status(c, "ndlqr_hip_polish_box", steps, status);
+  if (err) return err;
+  HIP_TRY(c->pol.ensure(d, c->set[0].stream));
+  // 1. everything idle, the primary set current with an up-to-date right-hand side
+  HIP_TRY(sync_all(c));
+  c->cur = 0;
+  err = rhs_make_current(c, 0xFu);
+  if (err) return err;
+  BufferSet& s = c->set[0];
+  PolishState& p = c->pol;
+  const hipStream_t st = s.stream;
+  const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
+  const unsigned pol_flags = c->flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
+  const double* lo = c->box.lo;
+  const double* hi = c->box.hi;
+  const size_t bs = c->box.bstride;
+  p.fact = false;
+  HIP_TRY(hipEventRecord(s.ev_start, st));
+  // 2. sigma, codes, the starting iterate (before the first factorisation overwrites the resident solution)
+  hipLaunchKernelGGL(ndlqr::polish_sigma, dim3(d.batch), dim3(256), 0, st, c->du, d, sigma, (const double*)c->QR, p.sig);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(p.word, 0, 2 * sizeof(int), st));
+  hipLaunchKernelGGL(ndlqr::polish_start, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)c->box.rho, lo, hi, bs,
+                     (const double*)c->box.v, (const double*)c->box.y, (const int*)c->box.status, (const double*)s.rhs,
+                     (const double*)s.z, p.z0, p.z, p.code, p.mu, p.bt, p.state, p.steps, p.here, p.word);
+  HIP_TRY(hipGetLastError());
+  bool factored = false;
+  int not_spd = NDLQR_OK;
+  ShiftedQR shifted(c);
+  // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
+  const auto rounds = [&]() -> int {
+    int e = shifted.open_unshifted(pol_flags);
+    if (e) return e;
+    for (int round = 0; round <= max_rounds; ++round) {
+      // 3. shift by sigma on the active entries, factor
+      if (round > 0) {
+        e = shifted.restore();
+        if (e) return e;
+      }
+      hipLaunchKernelGGL(ndlqr::polish_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)p.sig,
+                         (const unsigned char*)p.code, c->QR);
+      HIP_TRY(hipGetLastError());
+      factored = true;
+      e = box_factor(c, st, &not_spd, "ndlqr_hip_polish_box", "Q, R + sigma on the active entries");
+      if (e) return e;
+      // 4. the steps
+      // (word[0]: the problems that run in this round, counted by polish_start / the previous round's validation)
+      e = polish_steps(c, st, strict, max_steps, {s.rhs, lo, hi, p.z, p.mu, p.bt, p.state, p.here});
+      if (e) return e;
+      // 5. validation; the sets that changed
+      HIP_TRY(hipMemsetAsync(p.word, 0, 2 * sizeof(int), st));
+      hipLaunchKernelGGL(ndlqr::polish_validate, dim3(d.batch), dim3(256), 0, st, d, round == max_rounds ? 1 : 0, lo, hi, bs,
+                         (const double*)s.rhs, p.code, p.z, p.mu, p.bt, p.state, p.steps, p.here, p.word);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(p.h_word, p.word, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (p.h_word[1] == 0) break;
+    }
+    // 6. deliver
+    hipLaunchKernelGGL(ndlqr::polish_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)c->box.rho,
+                       (const int*)p.state, (const unsigned char*)p.code, (const double*)p.z, (const double*)p.mu,
+                       (const double*)p.z0, s.z, c->box.v, c->box.y);
+    HIP_TRY(hipGetLastError());
+    return NDLQR_OK;
+  };
+  err = rounds();
+  // 7. restore QR, bookkeeping
+  const KeptState shifted_kept = c->kept;  // (close() forgets it for the plain API)
+  const int cerr = shifted.close();
+  if (!err) err = cerr;
+  if (err) {
+    c->forget_shifted();
+    if (!not_spd) c->state_dirty = true;  // (a failed launch; a non-positive pivot leaves the device state clean)
+    if (factored) c->z_invalid = true;    // (the factorisation overwrote the resident solution)
+    (void)hipStreamSynchronize(st);
+    return err;
+  }
+  note_solution(c);  // (polish_finish wrote the resident solution: whatever belonged to the ADMM solution no longer applies)
+  p.soln_gen = p.adj_gen = 0;
+  HIP_TRY(hipEventRecord(s.ev_stop, st));
+  err = deliver_iters_status(c, st, p.steps, p.state, steps, status);
+  if (err) return err;  // (nothing remembered: the caller never learnt which problems were polished)
+  note_elapsed(c, s);
+  p.fact = true;  // (box_factor dropped the ADMM's)
+  p.flags = pol_flags;
+  p.kept = shifted_kept;
+  p.soln_gen = c->soln_gen;
+  return NDLQR_OK;
+}
+
+// The adjoint of the polished active-set system, K w + E_A' nu = g, E_A w = 0, on the remembered polish factorisation: the
+// loop of the polish with b = the packed g, c = 0, start w = nu = 0, the final codes; nothing is factored, no rounds. The
+// right-hand-side columns of the kept records are saved and restored as for the other adjoints.
+int ndlqr_hip_solve_polished_adjoint(NdlqrHipCtx* c, const double* g, int max_steps, int* steps, int* status) {
+  if (!c || !g || max_steps < 1 || max_steps > kPolishMaxSteps) return NDLQR_ERR_INVALID;
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_polished_adjoint");
+  if (c->pol.soln_gen == 0 || c->pol.soln_gen != c->soln_gen || !c->pol.fact || c->inputs_replaced)
+    return refuse("ndlqr_hip_solve_polished_adjoint: the resident solution is not that of the latest polish, or its "
+                  "factorisation is gone (a solve, step, re-solve, new inputs or new bounds came after it)");
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  CallerArrays<1> ga = {{const_cast<double*>(g)}, {((size_t)u.rows * u.N - u.m) * d.batch}};
+  int err = ga.classify(c, "ndlqr_hip_solve_polished_adjoint", "g lies");
+  if (!err) err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_polished_adjoint", steps, status);
+  if (err) return err;
+  PolishState& p = c->pol;
+  HIP_TRY(c->adj.ensure(d, c->set[0].stream));
+  HIP_TRY(p.ensure_adjoint(d));
+  HIP_TRY(c->grad_stage.grow(ga.stage));
+  HIP_TRY(sync_all(c));
+  c->cur = 0;
+  BufferSet& s = c->set[0];
+  const hipStream_t st = s.stream;
+  ga.place(c);
+  err = ga.copy(st, true);
+  if (err) return err;
+  c->adj.gen = c->abox.gen = p.adj_gen = 0;
+  const bool strict = (p.flags & NDLQR_FLAG_STRICT_FP) != 0;
+  HIP_TRY(hipEventRecord(s.ev_start, st));
+  ShiftedQR shifted(c);
+  const auto run = [&]() -> int {
+    hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, st, u, d, (const double*)ga.dev[0],
+                       c->adj.rhs);
+    HIP_TRY(hipGetLastError());
+    int e = shifted.open_unshifted(p.flags);
+    if (e) return e;
+    hipLaunchKernelGGL(ndlqr::polish_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)p.sig,
+                       (const unsigned char*)p.code, c->QR);
+    HIP_TRY(hipGetLastError());
+    c->kept = p.kept;
+    e = shifted.save_record_columns();
+    if (e) return e;
+    hipLaunchKernelGGL(ndlqr::box_fill_rho, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, 1.0, p.ones);
+    HIP_TRY(hipMemsetAsync(p.word, 0, 2 * sizeof(int), st));
+    hipLaunchKernelGGL(ndlqr::polish_adjoint_start, dim3(d.N, d.batch), dim3(64), 0, st, d, (const int*)p.state,
+                       (const double*)c->adj.rhs, c->adj.z, p.nu, p.abt, p.astate, p.asteps, p.ahere, p.word);
+    HIP_TRY(hipGetLastError());
+    e = polish_steps(c, st, strict, max_steps, {c->adj.rhs, nullptr, nullptr, c->adj.z, p.nu, p.abt, p.astate, p.ahere});
+    if (e) return e;
+    hipLaunchKernelGGL(ndlqr::polish_adjoint_finish, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch,
+                       (const unsigned long long*)p.norms, p.astate, p.asteps, (const int*)p.ahere);
+    HIP_TRY(hipGetLastError());
+    return NDLQR_OK;
+  };
+  err = run();
+  const int cerr = shifted.close();
+  if (!err) err = cerr;
+  if (err) {
+    c->state_dirty = true;
+    (void)hipStreamSynchronize(st);
+    return err;
+  }
+  HIP_TRY(hipEventRecord(s.ev_stop, st));
+  err = deliver_iters_status(c, st, p.asteps, p.astate, steps, status);
+  if (err) return err;
+  note_elapsed(c, s);
+  c->adj.gen = c->soln_gen;
+  p.adj_gen = c->soln_gen;
+  return NDLQR_OK;
+}
+
+// developer / test hook: the entry codes of the latest polish in the caller's block sizes, [batch][N][n+m] bytes (host)
+int ndlqr_hip_download_polish_codes(NdlqrHipCtx* c, unsigned char* codes) {
+  if (!c || !codes) return NDLQR_ERR_INVALID;
+  if (c->pol.soln_gen == 0 || c->pol.soln_gen != c->soln_gen)
+    return refuse("ndlqr_hip_download_polish_codes: the resident solution is not that of a polish");
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(sync_all(c));
+  std::vector<unsigned char> h(doubles_QR(d));
+  HIP_TRY(hipMemcpy(h.data(), c->pol.code, h.size(), hipMemcpyDeviceToHost));
+  for (int b = 0; b < d.batch; ++b)
+    for (int k = 0; k < d.N; ++k)
+      for (int j = 0; j < u.n + u.m; ++j)
+        codes[((size_t)b * u.N + k) * (u.n + u.m) + j] = h[((size_t)b * d.N + k) * d.w + (j < u.n ? j : d.n + (j - u.n))];
   return NDLQR_OK;
 }
 
