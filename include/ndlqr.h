@@ -537,9 +537,10 @@ int ndlqr_BatchKktResidualVector(NdLqrBatchSolver* bs, double* r);
  *   the finite / infinite pattern of the bounds and A, B, Q, R are those of the previous constrained solve: an MPC loop of
  *   ndlqr_BatchSetRhsFlat + this call pays only the iterations -- then iterates one right-hand-side re-solve and one
  *   element-wise update kernel per iteration. iters[p], status[p] (each may be NULL; host or the solver's device memory):
- *   iterations taken; 1 = converged, 2 = max_iter reached, the last iterate is returned (not an error; an infeasible
- *   problem ends so -- there is no infeasibility certificate), 3 = the iterate is not finite (NaN or inf in the problem's
- *   data): stopped, not a solution. A non-positive pivot of the shifted factorisation (Q or R <= 0 on an unbounded entry,
+ *   iterations taken; 1 = converged, 2 = max_iter reached, the last iterate is returned (not an error; without
+ *   infeasibility detection, below, an infeasible problem ends so), 3 = the iterate is not finite (NaN or inf in the
+ *   problem's data): stopped, not a solution, 4 = primal infeasible, a certificate was found (only with
+ *   ndlqr_BatchSetInfeasibilityDetection; the last iterate is returned, as for 2). A non-positive pivot of the shifted factorisation (Q or R <= 0 on an unbounded entry,
  *   as ndlqr_SolveBatch refuses it) returns NDLQR_ERR_NOT_SPD before any iteration; after that, and after any other
  *   error once the factorisation ran, the solution getters refuse until the next solve. A warm start keeps v, y of the
  *   entries bounded now (y of the others is zeroed). Blocking. Converged when, over the bounded entries of the problem,
@@ -583,6 +584,34 @@ int ndlqr_BatchSetBounds(NdLqrBatchSolver* bs, unsigned flags, const double* xlo
 int ndlqr_SolveBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status);
 int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u);
 int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho);
+/* additive: primal infeasibility detection in the box-constrained solve. State bounds make
+ * infeasibility an ordinary event in MPC; without detection such a problem keeps the whole batch iterating to max_iter.
+ *   ndlqr_BatchSetInfeasibilityDetection: every == 0 (the initial state) = off: no call changes a bit of its result.
+ *   every > 0: ndlqr_SolveBatchBoxConstrained tests every running problem at the iterations it >= 2 with it % every == 0;
+ *   eps == 0 -> 1e-4 (OSQP's eps_prim_inf). every < 0, or eps negative or not finite: NDLQR_ERR_INVALID and the previous
+ *   setting stays. The setting belongs to the solver and holds for every later constrained solve.
+ *   The test: with dlam = lambda^it - lambda^(it-1) (the multipliers of two consecutive re-solves) and
+ *   dmu = rho^it y^it - rho^(it-1) y^(it-1) on the bounded entries (in units of mu, so across a change of the adaptive
+ *   penalty too), let
+ *       e_x,k = -dlam_k + A_k' dlam_(k+1) + dmu_x,k,   e_u,k = B_k' dlam_(k+1) + dmu_u,k   (no A', B' term at k = N-1),
+ *       S = sum over the bounded entries of (hi_i max(dmu_i, 0) + lo_i min(dmu_i, 0)) - x0' dlam_0 - sum_k d_k' dlam_(k+1).
+ *   Every (x, u) that satisfies the dynamics and the bounds has e'(x, u) <= S, so e = 0 with S < 0 proves that there is
+ *   none. The problem is certified when ||dmu||_inf > 0, ||e||_inf <= eps ||dmu||_inf, S < -eps ||dmu||_inf, and every
+ *   entry whose dmu_i points to an infinite bound has |dmu_i| <= eps ||dmu||_inf (it then counts 0 in S); a non-finite
+ *   value anywhere means no certificate. A certified problem ends with status 4 and is frozen as a converged one is: it
+ *   leaves the running count, so the batch ends when every problem has a status of 1, 3 or 4, or at max_iter. Its resident
+ *   solution is its last iterate, as for status 2. The problems iterate independently: detection changes nothing for the
+ *   others.
+ *   ndlqr_CopyBatchInfeasibilityCertificate: dlam [batch][N][n], dmu_x [batch][N][n], dmu_u [batch][N][m] in the flat
+ *   layout of ndlqr_CopyBatchBoundMultipliers (each may be NULL, not all; host, pinned or the solver's device memory);
+ *   the rows of every problem whose status is not 4 are zero. NDLQR_ERR_INVALID unless the resident solution is that of
+ *   the latest constrained solve and detection was on for it.
+ *   Downstream, for a status-4 problem: ndlqr_PolishBatchBoxConstrained reports 2 and leaves it bit for bit;
+ *   ndlqr_SolveBatchBoxAdjoint does not iterate it, reports 4 and gives w = 0, nu = 0 (zero gradients);
+ *   ndlqr_SolveBatchPolishedAdjoint follows the polish status; a warm-started next solve starts that problem cold
+ *   (v = y = 0: its y has diverged and is not a starting point). */
+int ndlqr_BatchSetInfeasibilityDetection(NdLqrBatchSolver* bs, int every, double eps);
+int ndlqr_CopyBatchInfeasibilityCertificate(NdLqrBatchSolver* bs, double* dlam, double* dmu_x, double* dmu_u);
 /* additive: gradients through the box-constrained solve (differentiable MPC with actuator and state limits). After
  * ndlqr_SolveBatchBoxConstrained, for a loss L(z*) of the constrained solutions and g = dL/dz* (as for
  * ndlqr_SolveBatchAdjoint), ndlqr_SolveBatchBoxAdjoint solves the adjoint of the active-set system
@@ -590,7 +619,8 @@ int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho);
  * (A: the bounded entries whose projected iterate lies exactly on a bound; E_A picks them) by the same ADMM on the
  * forward's kept shifted factorisation -- the penalties the forward ended with, cold start, nothing factored, nothing
  * adapted. The settings' rho, warm_start, adapt_every, rho_min and rho_max are ignored; alpha, eps_abs, eps_rel, max_iter and check_every (0: the defaults of the forward) apply, and iters / status
- * report as for the forward. A problem whose forward ended as 3 is not iterated and reports 3. Afterwards
+ * report as for the forward. A problem whose forward ended as 3 or 4 is not iterated and reports that status (4: w = 0,
+ * nu = 0). Afterwards
  * ndlqr_CopyBatchAdjoint returns w and ndlqr_BatchGradients dL/d(A, B, Q, R, q, r, d, x0) at the constrained solution,
  * as after ndlqr_SolveBatchAdjoint. ndlqr_BatchBoundGradients returns dL/dc_A = nu: entry i goes to dL/dhi_i when the
  * forward's iterate sits on hi_i (lo_i == hi_i included), to dL/dlo_i when it sits on lo_i, 0 everywhere else; flat

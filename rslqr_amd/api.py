@@ -287,6 +287,8 @@ def lib():
     proto("ndlqr_SolveBatchBoxConstrained", ci, vp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_CopyBatchBoundMultipliers", ci, vp, dp, dp)
     proto("ndlqr_CopyBatchBoxPenalties", ci, vp, dp)
+    proto("ndlqr_BatchSetInfeasibilityDetection", ci, vp, ci, cd)
+    proto("ndlqr_CopyBatchInfeasibilityCertificate", ci, vp, dp, dp, dp)
     proto("ndlqr_SolveBatchBoxAdjoint", ci, vp, dp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_BatchBoundGradients", ci, vp, C.c_uint, dp, dp, dp, dp)
     proto("ndlqr_PolishBatchBoxConstrained", ci, vp, C.POINTER(NdLqrPolishSettings), C.POINTER(ci), C.POINTER(ci))
@@ -696,8 +698,8 @@ class BatchSolver:
                   adapt_every=0, rho_min=0.0, rho_max=0.0):
         """ndlqr_SolveBatchBoxConstrained (0 = the library's default for every setting). adapt_every > 0: the per-problem
         adaptive penalty, considered every that many iterations and kept within [rho_min, rho_max]; 0: fixed rho. Returns
-        (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached. Raises on a nonzero
-        return."""
+        (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached, 3 = not finite, 4 = primal
+        infeasible with a certificate (only after set_box_infeasibility(every > 0)). Raises on a nonzero return."""
         st = NdLqrBoxSettingsFull(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0,
                                   int(adapt_every), rho_min, rho_max)
         iters = np.zeros(self.batch, dtype=np.int32)
@@ -708,6 +710,33 @@ class BatchSolver:
             raise RuntimeError("ndlqr_SolveBatchBoxConstrained failed: %d (%s)"
                                % (err, self.L.ndlqr_hip_last_error().decode()))
         return iters, status
+
+    def set_box_infeasibility(self, every=0, eps=0.0):
+        """ndlqr_BatchSetInfeasibilityDetection: every > 0 lets the constrained solves that follow test every running
+        problem for a primal infeasibility certificate at the iterations it % every == 0 (status 4; eps = 0: 1e-4);
+        every = 0 (the initial state): off. Raises on a refusal (every < 0, eps negative or not finite); the previous
+        setting then stays."""
+        err = self.L.ndlqr_BatchSetInfeasibilityDetection(self.h, int(every), float(eps))
+        if err:
+            raise RuntimeError("ndlqr_BatchSetInfeasibilityDetection failed: %d" % err)
+
+    def infeasibility_certificate(self, dlam=None, dmu_x=None, dmu_u=None):
+        """ndlqr_CopyBatchInfeasibilityCertificate: (dlam [batch, N, n], dmu_x [batch, N, n], dmu_u [batch, N, m]) of the
+        last constrained solve, which ran with detection on: the Farkas certificate of every status-4 problem, zero rows
+        for the others; `dlam`, `dmu_x`, `dmu_u`: destinations (numpy arrays or DeviceArrays). Raises on a refusal."""
+        n, m, N, B = self.n, self.m, self.N, self.batch
+        if dlam is None:
+            dlam = np.zeros((B, N, n))
+        if dmu_x is None:
+            dmu_x = np.zeros((B, N, n))
+        if dmu_u is None:
+            dmu_u = np.zeros((B, N, m))
+        err = self.L.ndlqr_CopyBatchInfeasibilityCertificate(self.h, _any_ptr(dlam, B * N * n), _any_ptr(dmu_x, B * N * n),
+                                                             _any_ptr(dmu_u, B * N * m))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchInfeasibilityCertificate failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return dlam, dmu_x, dmu_u
 
     def box_penalties(self, rho=None):
         """ndlqr_CopyBatchBoxPenalties: rho [batch] of the last constrained solve (what an adaptive solve ended with);
@@ -739,7 +768,8 @@ class BatchSolver:
         """ndlqr_SolveBatchBoxAdjoint: the adjoint of the active-set system of the last constrained solve for g = dL/dz*
         [batch, nvars] (numpy array or DeviceArray), on the forward's kept shifted factorisation (its final penalties, a cold start;
         0 = the library's default for every setting). Returns (iters, status) as numpy int arrays [batch]; status 1 =
-        converged, 2 = max_iter reached, 3 = not finite (or the forward's was). Raises on a nonzero return. Afterwards
+        converged, 2 = max_iter reached, 3 = not finite (or the forward's was), 4 = the forward certified the problem
+        infeasible (not iterated: w = 0, zero gradients). Raises on a nonzero return. Afterwards
         adjoint() and gradients() read its w."""
         if not hasattr(g, "ptr"):
             g = np.ascontiguousarray(g, dtype=np.float64)

@@ -258,28 +258,31 @@ def _solve_box(bs, flat, bflat, all_shared, settings, token, key):
     err = bs.L.ndlqr_BatchSetBounds(bs.h, BOUNDS_SHARED if all_shared else 0, *ptrs)
     if err:
         raise ValueError("lqr_solve_box: the bounds were refused (%s)" % bs.L.ndlqr_hip_last_error().decode())
-    rho, alpha, eps_abs, eps_rel, max_iter, adapt_every, polish = settings
+    rho, alpha, eps_abs, eps_rel, max_iter, adapt_every, polish, infeas_every = settings
+    bs.set_box_infeasibility(infeas_every)  # (the cached solver keeps the setting of whoever used it last)
     try:
         _, status = bs.solve_box(rho=rho, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
                                  adapt_every=adapt_every)
     except RuntimeError as e:
         raise RuntimeError("lqr_solve_box: the constrained solve failed (%s)" % e) from None
-    bad = int((status != 1).sum())
+    infeasible = status == 4  # (only with infeas_every > 0: certified, z is the last iterate, the gradients are zero)
+    bad = int(((status != 1) & ~infeasible).sum())
     if bad:
         raise RuntimeError("lqr_solve_box: %d of %d problems did not converge (status %s): raise max_iter, change rho or "
                            "set adapt_every (the per-problem adaptive penalty)"
-                           % (bad, status.size, sorted(set(status.tolist()) - {1})))
+                           % (bad, status.size, sorted(set(status.tolist()) - {1, 4})))
     if polish:
         try:
             _, status = bs.polish_box()
         except RuntimeError as e:
             raise RuntimeError("lqr_solve_box: the polish failed (%s)" % e) from None
-        bad = int((status != 1).sum())
+        bad = int(((status != 1) & ~infeasible).sum())
         if bad:
             raise RuntimeError("lqr_solve_box: %d of %d problems were not polished (status %s): the active set ADMM left "
                                "was not corrected within the rounds; tighten eps_abs / eps_rel"
-                               % (bad, status.size, sorted(set(status.tolist()) - {1})))
+                               % (bad, status.size, sorted(set(status[~infeasible].tolist()) - {1})))
     _box_cache[key][1] = token
+    return infeasible
 
 
 class LqrSolveBox(torch.autograd.Function):
@@ -295,7 +298,7 @@ class LqrSolveBox(torch.autograd.Function):
         flat = _flat(problem, n, m, N, b, shared)
         all_shared, bflat = _flat_bounds(bounds, bshared, b)
         token = next(_tokens)
-        _solve_box(bs, flat, bflat, all_shared, settings, token, key)
+        ctx.infeasible = _solve_box(bs, flat, bflat, all_shared, settings, token, key)
         z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
         bs.solutions_to_device(z.data_ptr())
         bs.synchronize()
@@ -311,15 +314,15 @@ class LqrSolveBox(torch.autograd.Function):
             _solve_box(bs, ctx.flat, ctx.bflat, ctx.all_shared, ctx.settings, ctx.token, ctx.key)
         gz = gz.detach().to(torch.float64).contiguous()
         torch.cuda.current_stream(gz.device).synchronize()
-        _, alpha, eps_abs, eps_rel, max_iter, _, polish = ctx.settings
+        _, alpha, eps_abs, eps_rel, max_iter, _, polish, _ = ctx.settings
         if polish:
             _, status = bs.solve_polished_adjoint(_View(gz))
         else:
             _, status = bs.solve_box_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter)
-        bad = int((status != 1).sum())
+        bad = int(((status != 1) & ~ctx.infeasible).sum())  # (a certified problem is not iterated: w = 0, nu = 0)
         if bad:
             raise RuntimeError("lqr_solve_box backward: the adjoint of %d of %d problems did not converge (status %s)"
-                               % (bad, status.size, sorted(set(status.tolist()) - {1})))
+                               % (bad, status.size, sorted(set(status[~ctx.infeasible].tolist()) - {1})))
         need, need_b = ctx.needs_input_grad[1:9], ctx.needs_input_grad[9:]
         mask = 0
         out, views = {}, {}
@@ -355,7 +358,7 @@ class LqrSolveBox(torch.autograd.Function):
 
 
 def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=None, *, rho=0.0, alpha=0.0, eps_abs=0.0,
-                  eps_rel=0.0, max_iter=0, adapt_every=0, polish=False):
+                  eps_rel=0.0, max_iter=0, adapt_every=0, polish=False, infeas_every=0):
     """z* [b, nvars] of the LQR problems of lqr_solve with xlo <= x_k <= xhi (k >= 1) and ulo <= u_k <= uhi, by the
     box-constrained batch solve (ndlqr_SolveBatchBoxConstrained, cold start; 0 = the library's default for every
     setting; adapt_every > 0: the per-problem adaptive penalty, considered every that many iterations, so that rho
@@ -366,9 +369,12 @@ def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=Non
     complementarity); at a degenerate active set the bound gradients are one of many.
     polish=True: the forward is ADMM followed by the active-set polish (ndlqr_PolishBatchBoxConstrained, default
     settings), so a loose eps_abs / eps_rel such as 1e-3 suffices, and the backward is the polished adjoint
-    (ndlqr_SolveBatchPolishedAdjoint) with the same gradient assembly; raises when a problem's polish status is not 1."""
+    (ndlqr_SolveBatchPolishedAdjoint) with the same gradient assembly; raises when a problem's polish status is not 1.
+    infeas_every > 0: primal infeasibility detection every that many iterations (ndlqr_BatchSetInfeasibilityDetection,
+    default eps). A problem that is certified infeasible (status 4) does not raise: its z is the last iterate, which solves
+    nothing, and it gets zero gradients in every tensor -- the adjoint does not iterate it (w = 0, nu = 0)."""
     return LqrSolveBox.apply((float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(adapt_every),
-                              bool(polish)),
+                              bool(polish), int(infeas_every)),
                              A, B, Q, R, q, r, d, x0, xlo, xhi, ulo, uhi)
 
 

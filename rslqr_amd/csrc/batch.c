@@ -12,6 +12,7 @@
  * negated as in src/solver.c:188-190.
  */
 #define _GNU_SOURCE
+#include <math.h>
 #include <pthread.h>
 #include <sched.h>
 #include <stdio.h>
@@ -397,6 +398,15 @@ int ndlqr_SolveBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings*
 int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho) {
   if (!bs || !rho) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_box_penalties(bs->ctx, rho);
+}
+int ndlqr_BatchSetInfeasibilityDetection(NdLqrBatchSolver* bs, int every, double eps) {
+  /* (eps < HUGE_VAL is false for a NaN as well) */
+  if (!bs || every < 0 || !(eps >= 0.0 && eps < HUGE_VAL)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_set_box_infeasibility(bs->ctx, every, eps > 0.0 ? eps : 1e-4);
+}
+int ndlqr_CopyBatchInfeasibilityCertificate(NdLqrBatchSolver* bs, double* dlam, double* dmu_x, double* dmu_u) {
+  if (!bs || (!dlam && !dmu_x && !dmu_u)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_infeasibility_certificate(bs->ctx, dlam, dmu_x, dmu_u);
 }
 int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u) {
   if (!bs || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;

@@ -245,6 +245,24 @@ struct BoxState {
   }
 };
 
+// Infeasibility detection of the box-constrained solve (ndlqr_hip_set_box_infeasibility, kernels_box_infeas.hpp;
+// DESIGN.md section 3.14). every, eps: the setting (every == 0: off -- nothing here is allocated or launched). The
+// iteration before a check leaves copies of the re-solve's z, of y and of the penalties (z_prev [batch][N][2n+m], y_prev
+// [batch][N][n+m], rho_prev [batch]); the certificate of every status-4 problem in the device block sizes, zero elsewhere
+// (cert_lam [batch][N][n], cert_mu [batch][N][n+m]). gen: the solution generation of the latest constrained solve that
+// ran with detection on (0: none).
+struct BoxInfeasState {
+  DevBuf<double> z_prev, y_prev, rho_prev, cert_lam, cert_mu;
+  int every = 0;
+  double eps = 1e-4;
+  unsigned long long gen = 0;
+  hipError_t ensure(const ndlqr::Dims& d) {
+    const size_t nv = doubles_QR(d);
+    return first_error({z_prev.ensure(doubles_z(d)), y_prev.ensure(nv), rho_prev.ensure((size_t)d.batch),
+                        cert_lam.ensure((size_t)d.batch * d.N * d.n), cert_mu.ensure(nv)});
+  }
+};
+
 // Gradients through the box-constrained solve (ndlqr_hip_solve_box_adjoint / ndlqr_hip_bound_gradients,
 // kernels_box_grad.hpp). gen: the solution generation the box adjoint belongs to (0: none). The adjoint's own entry
 // codes, v, y, ADMM right-hand sides (its resident one is adj.rhs, its solution adj.z), per problem status, iterations
@@ -395,6 +413,7 @@ struct NdlqrHipCtx {
   // the optional features, each with its buffers (allocated on first use by its ensure())
   AdjointState adj;
   BoxState box;
+  BoxInfeasState infeas;
   BoxAdjointState abox;
   RefineState ref;
   PolishState pol;

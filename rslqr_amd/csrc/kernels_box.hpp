@@ -102,13 +102,16 @@ __device__ __forceinline__ double box_rhs_entry(double res, double v, double y, 
 
 // Start of a solve: both ADMM right-hand sides from the resident one and v, y (zeroed first for a cold start; a warm
 // start zeroes y of the entries the current bounds leave unbounded, which may have been bounded in the previous solve).
+// prev_status (a warm start: the status words of the previous solve, which this launch precedes): a problem that ended
+// as 4 -- certified infeasible, its y has diverged -- starts cold.
 //   grid (N, batch), block 64.
 template <bool STRICT>
-__global__ void box_start(Dims d, const double* __restrict__ rhov, int cold, const double* __restrict__ lo,
-                          const double* __restrict__ hi, size_t bstride, const double* __restrict__ res,
-                          double* __restrict__ v, double* __restrict__ y, double* __restrict__ rhs0,
-                          double* __restrict__ rhs1) {
+__global__ void box_start(Dims d, const double* __restrict__ rhov, int cold_all, const int* __restrict__ prev_status,
+                          const double* __restrict__ lo, const double* __restrict__ hi, size_t bstride,
+                          const double* __restrict__ res, double* __restrict__ v, double* __restrict__ y,
+                          double* __restrict__ rhs0, double* __restrict__ rhs1) {
   const int k = blockIdx.x, b = blockIdx.y;
+  const bool cold = cold_all || prev_status[b] == 4;
   const double rho = rhov[b];
   const size_t oz = ((size_t)b * d.N + k) * d.rows, ov = ((size_t)b * d.N + k) * d.w,
                ob = (size_t)b * bstride + (size_t)k * d.w;

@@ -27,8 +27,8 @@ namespace ndlqr {
 enum : unsigned char { BOX_UNBOUNDED = 0, BOX_SPLIT = 1, BOX_AT_LO = 2, BOX_AT_HI = 3 };
 
 // Start of a box adjoint: the codes from the forward's v (vf) and bounds, v = y = 0, both ADMM right-hand sides from the
-// packed g (res, the adjoint's resident right-hand side); status and iteration count of every problem -- 3 (not iterated)
-// where the forward ended as 3, else 0 and one more in the running count.
+// packed g (res, the adjoint's resident right-hand side); status and iteration count of every problem -- 3 or 4 (not
+// iterated) where the forward ended so, else 0 and one more in the running count.
 //   grid (N, batch), block 64.
 template <bool STRICT>
 __global__ void box_adjoint_start(Dims d, const double* __restrict__ rhov, const double* __restrict__ lo,
@@ -55,7 +55,8 @@ __global__ void box_adjoint_start(Dims d, const double* __restrict__ rhov, const
     rhs1[oz + r] = val;
   }
   if (k == 0 && threadIdx.x == 0) {
-    const int st = fstatus[b] == 3 ? 3 : 0;
+    const int fs = fstatus[b];
+    const int st = (fs == 3 || fs == 4) ? fs : 0;
     status[b] = st;
     iters[b] = 0;
     if (st == 0) atomicAdd(running, 1);
@@ -151,11 +152,16 @@ __global__ __launch_bounds__(256) void box_adjoint_update(Dims d, int it, BoxPar
 }
 
 // End of a box adjoint, in place on the adjoint solution z (the last re-solve): x, u of the bounded entries become v
-// (0 on the fixed ones); lambda and the unbounded entries stay as the re-solve left them.
+// (0 on the fixed ones); lambda and the unbounded entries stay as the re-solve left them. A problem whose forward was
+// certified infeasible (status 4) has no solution to differentiate: w = 0 (its nu = rho y is 0 from the start).
 //   grid (N, batch), block 64.
 static __global__ void box_adjoint_finish(Dims d, const unsigned char* __restrict__ code, const double* __restrict__ v,
-                                          double* __restrict__ z) {
+                                          const int* __restrict__ status, double* __restrict__ z) {
   const int k = blockIdx.x, b = blockIdx.y;
+  if (status[b] == 4) {
+    for (int r = threadIdx.x; r < d.rows; r += blockDim.x) z[((size_t)b * d.N + k) * d.rows + r] = 0.0;
+    return;
+  }
   const size_t oz = ((size_t)b * d.N + k) * d.rows + d.n, ov = ((size_t)b * d.N + k) * d.w;
   for (int j = threadIdx.x; j < d.w; j += blockDim.x)
     if (code[ov + j] != BOX_UNBOUNDED) z[oz + j] = v[ov + j];

@@ -55,7 +55,8 @@ static __global__ __launch_bounds__(256) void polish_sigma(Dims du, Dims d, doub
 // Start of a polish: the resident solution zs saved into z0 and taken as z; codes from the exact comparisons of the ADMM
 // iterate with its bounds -- 3: v == hi && y > 0, or lo == hi; 2: v == lo && y < 0; 1: bounded otherwise --; mu = rho y on
 // the active entries, 0 elsewhere; bt = b - E_A' mu from the resident right-hand side res; state 3 for a problem whose
-// constrained solve ended non-finite, 0 otherwise (counted in *running); no steps yet.
+// constrained solve ended non-finite, 2 (kept as it is) for one that was certified infeasible (status 4), 0 otherwise
+// (counted in *running); no steps yet.
 //   grid (N, batch), block 64.
 static __global__ void polish_start(Dims d, const double* __restrict__ rhov, const double* __restrict__ lo,
                                     const double* __restrict__ hi, size_t bstride, const double* __restrict__ v,
@@ -69,9 +70,10 @@ static __global__ void polish_start(Dims d, const double* __restrict__ rhov, con
   const size_t oz = ((size_t)b * d.N + k) * d.rows, ov = ((size_t)b * d.N + k) * d.w,
                ob = (size_t)b * bstride + (size_t)k * d.w;
   if (k == 0 && threadIdx.x == 0) {
-    const bool nan = box_status[b] == 3;
-    state[b] = nan ? POLISH_NAN : POLISH_RUNNING;
-    if (!nan) atomicAdd(running, 1);
+    const int bst = box_status[b];
+    const bool run = bst != 3 && bst != 4;
+    state[b] = run ? POLISH_RUNNING : bst == 3 ? POLISH_NAN : POLISH_KEPT;
+    if (run) atomicAdd(running, 1);
     steps[b] = 0;
     here[b] = 0;
   }

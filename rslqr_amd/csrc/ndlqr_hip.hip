@@ -12,6 +12,7 @@
 #include "kernels_generic.hpp"
 #include "kernels_box.hpp"
 #include "kernels_box_grad.hpp"
+#include "kernels_box_infeas.hpp"
 #include "kernels_box_polish.hpp"
 #include "kernels_grad.hpp"
 #include "kernels_refine.hpp"
@@ -1697,6 +1698,9 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
 // box_update may move a problem's penalty at every adapt_every-th iteration; the host then reads the count of changed
 // problems next to the running count and, when it is not zero, restores QR, shifts it by the new vector and factors the
 // whole batch again -- one factorisation serves every problem that changed in that round.
+// Infeasibility detection (ndlqr_hip_set_box_infeasibility, kernels_box_infeas.hpp): with a check
+// period set, the iteration before a check leaves copies of z, y and rho behind its box_update, and the check iteration
+// runs box_certify behind its own: a certified problem (status 4) leaves the running count like a converged one.
 
 
 // Bounds in the caller's layout, [P][N][n] and [P][N][m] with P = batch, or P = 1 (shared): this device's memory is read
@@ -1876,6 +1880,9 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   int err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_box", iters, status);
   if (err) return err;
   HIP_TRY(c->box.ensure(d, c->set[0].stream));
+  const int infeas_every = c->infeas.every;
+  if (infeas_every > 0) HIP_TRY(c->infeas.ensure(d));
+  c->infeas.gen = 0;
   // 1. everything idle, the primary set current with an up-to-date right-hand side
   HIP_TRY(sync_all(c));
   c->cur = 0;
@@ -1921,9 +1928,15 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
     const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, rho_min, rho_max};
     const double* rhov = c->box.rho;
     const int cold = warm_start && c->box.have_vy ? 0 : 1;
-    launch_strict(strict, ndlqr::box_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, lo, hi, bs,
-                  (const double*)s.rhs, c->box.v, c->box.y, c->box.rhs[0], c->box.rhs[1]);
+    launch_strict(strict, ndlqr::box_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, (const int*)c->box.status, lo,
+                  hi, bs, (const double*)s.rhs, c->box.v, c->box.y, c->box.rhs[0], c->box.rhs[1]);
     HIP_TRY(hipGetLastError());
+    BoxInfeasState& inf = c->infeas;
+    if (infeas_every > 0) {  // (the certificate rows of the problems that do not end as 4 are zero)
+      HIP_TRY(hipMemsetAsync(inf.cert_lam, 0, sizeof(double) * (size_t)d.batch * d.N * d.n, st));
+      HIP_TRY(hipMemsetAsync(inf.cert_mu, 0, sizeof(double) * doubles_QR(d), st));
+    }
+    const auto is_check = [&](int i) { return infeas_every > 0 && i >= 2 && i <= max_iter && i % infeas_every == 0; };
     c->box.have_vy = true;
     c->box.h_word[0] = d.batch;
     c->box.h_word[1] = 0;
@@ -1939,6 +1952,19 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
                     bs, c->box.v, c->box.y, (const double*)s.rhs, rc, rn, c->box.rho, c->box.status, c->box.iters,
                     c->box.resid, c->box.word);
       HIP_TRY(hipGetLastError());
+      if (is_check(it)) {  // the differences over this iteration: a certificate?
+        hipLaunchKernelGGL(ndlqr::box_certify, dim3(d.batch), dim3(256), ndlqr::certify_lds_bytes(d), st, d, it, inf.eps,
+                           (const double*)c->AB, (const double*)c->box.z, (const double*)inf.z_prev, (const double*)c->box.y,
+                           (const double*)inf.y_prev, (const double*)c->box.rho, (const double*)inf.rho_prev, lo, hi, bs,
+                           (const double*)s.rhs, c->box.rhs[(it - 1) & 1], (const double*)rn, c->box.status, c->box.iters,
+                           c->box.word, inf.cert_lam, inf.cert_mu);
+        HIP_TRY(hipGetLastError());
+      }
+      if (is_check(it + 1)) {  // what the next iteration's check takes its differences against
+        HIP_TRY(hipMemcpyAsync(inf.z_prev, c->box.z, sizeof(double) * doubles_z(d), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(inf.y_prev, c->box.y, sizeof(double) * doubles_QR(d), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(inf.rho_prev, c->box.rho, sizeof(double) * (size_t)d.batch, hipMemcpyDeviceToDevice, st));
+      }
       if (it % check_every == 0 || it == max_iter || adapt) {
         // 5. one word: how many problems still run; after an adapting update also how many changed their penalty
         HIP_TRY(hipMemcpyAsync(c->box.h_word, c->box.word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1983,11 +2009,44 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   }
   note_solution(c);
   c->box.soln_gen = c->soln_gen;
+  if (infeas_every > 0) c->infeas.gen = c->soln_gen;
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   c->timing_pending = true;
   err = deliver_iters_status(c, st, c->box.iters, c->box.status, iters, status);
   if (err) return err;
   return ndlqr_hip_synchronize(c);
+}
+
+int ndlqr_hip_set_box_infeasibility(NdlqrHipCtx* c, int every, double eps) {
+  if (!c || every < 0 || !(eps > 0.0 && eps < HUGE_VAL)) return NDLQR_ERR_INVALID;
+  c->infeas.every = every;
+  c->infeas.eps = eps;
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* c, double* dlam, double* dmu_x, double* dmu_u) {
+  if (!c || (!dlam && !dmu_x && !dmu_u)) return NDLQR_ERR_INVALID;
+  if (c->infeas.gen == 0 || c->infeas.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
+    return refuse("ndlqr_hip_download_infeasibility_certificate: the resident solution is not that of a constrained solve "
+                  "with infeasibility detection on (ndlqr_hip_set_box_infeasibility before the solve)");
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nx = (size_t)u.batch * u.N * u.n;
+  CallerArrays<3> out = {{dlam, dmu_x, dmu_u}, {nx, nx, (size_t)u.batch * u.N * u.m}};
+  int err = out.classify(c, "ndlqr_hip_download_infeasibility_certificate", "an output lies");
+  if (err) return err;
+  HIP_TRY(c->grad_stage.grow(out.stage));
+  HIP_TRY(sync_all(c));
+  const BufferSet& s = c->set[0];
+  out.place(c);
+  hipLaunchKernelGGL(ndlqr::box_certificate_out, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->infeas.cert_lam,
+                     (const double*)c->infeas.cert_mu, out.dev[0], out.dev[1], out.dev[2]);
+  HIP_TRY(hipGetLastError());
+  err = out.copy(s.stream, false);
+  if (err) return err;
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
 }
 
 int ndlqr_hip_download_box_penalties(NdlqrHipCtx* c, double* rho) {
@@ -2116,7 +2175,7 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
     }
     // 5. w = [lambda, v]
     hipLaunchKernelGGL(ndlqr::box_adjoint_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, (const unsigned char*)c->abox.code,
-                       (const double*)c->abox.v, c->adj.z);
+                       (const double*)c->abox.v, (const int*)c->abox.status, c->adj.z);
     HIP_TRY(hipGetLastError());
     return NDLQR_OK;
   };
