@@ -606,12 +606,20 @@ int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho);
  *   layout of ndlqr_CopyBatchBoundMultipliers (each may be NULL, not all; host, pinned or the solver's device memory);
  *   the rows of every problem whose status is not 4 are zero. NDLQR_ERR_INVALID unless the resident solution is that of
  *   the latest constrained solve and detection was on for it.
+ *   ndlqr_CopyBatchInfeasibilityMeasures: the four numbers of every problem's latest check, measures [batch][4] =
+ *   ||e||_inf | ||dmu||_inf | max |dmu_i| over the entries pointing to an infinite bound | S, and the iteration of that
+ *   check, iteration [batch] (either may be NULL, not both; host, pinned or the solver's device memory). They are stored
+ *   before the decision, for certified and running problems alike, a NaN among them as it is; a problem that no check
+ *   examined (frozen before the first one) has iteration 0 and a row of zeros. The same refusals as
+ *   ndlqr_CopyBatchInfeasibilityCertificate. With them a caller sees how far a running problem is from a certificate --
+ *   ||e||_inf / ||dmu||_inf and -S / ||dmu||_inf against eps -- when choosing eps.
  *   Downstream, for a status-4 problem: ndlqr_PolishBatchBoxConstrained reports 2 and leaves it bit for bit;
  *   ndlqr_SolveBatchBoxAdjoint does not iterate it, reports 4 and gives w = 0, nu = 0 (zero gradients);
  *   ndlqr_SolveBatchPolishedAdjoint follows the polish status; a warm-started next solve starts that problem cold
  *   (v = y = 0: its y has diverged and is not a starting point). */
 int ndlqr_BatchSetInfeasibilityDetection(NdLqrBatchSolver* bs, int every, double eps);
 int ndlqr_CopyBatchInfeasibilityCertificate(NdLqrBatchSolver* bs, double* dlam, double* dmu_x, double* dmu_u);
+int ndlqr_CopyBatchInfeasibilityMeasures(NdLqrBatchSolver* bs, double* measures, int* iteration);
 /* additive: gradients through the box-constrained solve (differentiable MPC with actuator and state limits). After
  * ndlqr_SolveBatchBoxConstrained, for a loss L(z*) of the constrained solutions and g = dL/dz* (as for
  * ndlqr_SolveBatchAdjoint), ndlqr_SolveBatchBoxAdjoint solves the adjoint of the active-set system

@@ -136,9 +136,12 @@ int ndlqr_hip_download_box_penalties(NdlqrHipCtx* ctx, double* rho);
  * ndlqr_CopyBatchInfeasibilityCertificate). ndlqr_hip_set_box_infeasibility takes the resolved
  * setting (every >= 0, 0: off; eps > 0 and finite) for the solves that follow. ndlqr_hip_download_infeasibility_certificate:
  * dlam [batch][N][n], dmu_x [batch][N][n], dmu_u [batch][N][m] of the latest constrained solve (each may be NULL; host,
- * pinned or this device's memory); zero rows for every problem that did not end as 4. */
+ * pinned or this device's memory); zero rows for every problem that did not end as 4.
+ * ndlqr_hip_download_infeasibility_measures: measures [batch][4], iteration [batch] of every problem's latest check
+ * (ndlqr.h: ndlqr_CopyBatchInfeasibilityMeasures), with the same refusals and destinations. */
 int ndlqr_hip_set_box_infeasibility(NdlqrHipCtx* ctx, int every, double eps);
 int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* ctx, double* dlam, double* dmu_x, double* dmu_u);
+int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* ctx, double* measures, int* iteration);
 int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* ctx, double* mu_x, double* mu_u);
 unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* ctx);
 /* Gradients through the box-constrained solve (ndlqr.h: ndlqr_SolveBatchBoxAdjoint, ndlqr_BatchBoundGradients;

@@ -289,6 +289,7 @@ def lib():
     proto("ndlqr_CopyBatchBoxPenalties", ci, vp, dp)
     proto("ndlqr_BatchSetInfeasibilityDetection", ci, vp, ci, cd)
     proto("ndlqr_CopyBatchInfeasibilityCertificate", ci, vp, dp, dp, dp)
+    proto("ndlqr_CopyBatchInfeasibilityMeasures", ci, vp, dp, C.POINTER(ci))
     proto("ndlqr_SolveBatchBoxAdjoint", ci, vp, dp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_BatchBoundGradients", ci, vp, C.c_uint, dp, dp, dp, dp)
     proto("ndlqr_PolishBatchBoxConstrained", ci, vp, C.POINTER(NdLqrPolishSettings), C.POINTER(ci), C.POINTER(ci))
@@ -737,6 +738,30 @@ class BatchSolver:
             raise RuntimeError("ndlqr_CopyBatchInfeasibilityCertificate failed: %d (%s)"
                                % (err, self.L.ndlqr_hip_last_error().decode()))
         return dlam, dmu_x, dmu_u
+
+    def infeasibility_measures(self, measures=None, iteration=None):
+        """ndlqr_CopyBatchInfeasibilityMeasures: (measures [batch, 4], iteration [batch]) of the last constrained solve,
+        which ran with detection on: ||e||_inf, ||dmu||_inf, the largest |dmu_i| toward an infinite bound and S as the
+        latest check of every problem found them, and the iteration of that check (0 and a row of zeros: no check examined
+        the problem). `measures`: destination (numpy array or DeviceArray); `iteration`: a C-contiguous int32 numpy array,
+        or anything with `ptr` addressing batch ints of device memory. Raises on a refusal."""
+        B = self.batch
+        if measures is None:
+            measures = np.zeros((B, 4))
+        if iteration is None:
+            iteration = np.zeros(B, dtype=np.int32)
+        if hasattr(iteration, "ptr"):
+            ip = C.cast(C.c_void_p(int(iteration.ptr)), C.POINTER(C.c_int))
+        else:
+            if not (isinstance(iteration, np.ndarray) and iteration.dtype == np.int32 and iteration.flags["C_CONTIGUOUS"]
+                    and iteration.size == B):
+                raise ValueError("expected a C-contiguous int32 array of %d entries" % B)
+            ip = iteration.ctypes.data_as(C.POINTER(C.c_int))
+        err = self.L.ndlqr_CopyBatchInfeasibilityMeasures(self.h, _any_ptr(measures, 4 * B), ip)
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchInfeasibilityMeasures failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return measures, iteration
 
     def box_penalties(self, rho=None):
         """ndlqr_CopyBatchBoxPenalties: rho [batch] of the last constrained solve (what an adaptive solve ended with);

@@ -408,6 +408,10 @@ int ndlqr_CopyBatchInfeasibilityCertificate(NdLqrBatchSolver* bs, double* dlam, 
   if (!bs || (!dlam && !dmu_x && !dmu_u)) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_infeasibility_certificate(bs->ctx, dlam, dmu_x, dmu_u);
 }
+int ndlqr_CopyBatchInfeasibilityMeasures(NdLqrBatchSolver* bs, double* measures, int* iteration) {
+  if (!bs || (!measures && !iteration)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_infeasibility_measures(bs->ctx, measures, iteration);
+}
 int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u) {
   if (!bs || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_bound_multipliers(bs->ctx, mu_x, mu_u);

@@ -249,17 +249,20 @@ struct BoxState {
 // DESIGN.md section 3.14). every, eps: the setting (every == 0: off -- nothing here is allocated or launched). The
 // iteration before a check leaves copies of the re-solve's z, of y and of the penalties (z_prev [batch][N][2n+m], y_prev
 // [batch][N][n+m], rho_prev [batch]); the certificate of every status-4 problem in the device block sizes, zero elsewhere
-// (cert_lam [batch][N][n], cert_mu [batch][N][n+m]). gen: the solution generation of the latest constrained solve that
-// ran with detection on (0: none).
+// (cert_lam [batch][N][n], cert_mu [batch][N][n+m]); the four numbers of every problem's latest check and the iteration
+// it ran at (measures [batch][4], measured_at [batch]; zero for a problem no check examined). gen: the solution
+// generation of the latest constrained solve that ran with detection on (0: none).
 struct BoxInfeasState {
-  DevBuf<double> z_prev, y_prev, rho_prev, cert_lam, cert_mu;
+  DevBuf<double> z_prev, y_prev, rho_prev, cert_lam, cert_mu, measures;
+  DevBuf<int> measured_at;
   int every = 0;
   double eps = 1e-4;
   unsigned long long gen = 0;
   hipError_t ensure(const ndlqr::Dims& d) {
     const size_t nv = doubles_QR(d);
     return first_error({z_prev.ensure(doubles_z(d)), y_prev.ensure(nv), rho_prev.ensure((size_t)d.batch),
-                        cert_lam.ensure((size_t)d.batch * d.N * d.n), cert_mu.ensure(nv)});
+                        cert_lam.ensure((size_t)d.batch * d.N * d.n), cert_mu.ensure(nv),
+                        measures.ensure(4 * (size_t)d.batch), measured_at.ensure((size_t)d.batch)});
   }
 };
 

@@ -35,7 +35,9 @@ static inline size_t certify_lds_bytes(const Dims& d) { return sizeof(double) * 
 // system, and dlam, dmu go to cert_lam [batch][N][n], cert_mu [batch][N][n+m] (device block sizes; zero before the solve).
 // Task t = g w + j of a pass is column j of [A | B] of its g-th knot: one thread forms e of that entry, its terms of S
 // and its maxima; the sums of S stay in a two-term accumulator per thread and are added up in a fixed tree, the maxima
-// likewise with max_nan: the decision is the same from run to run.
+// likewise with max_nan: the decision is the same from run to run. The four numbers the decision is taken from go to
+// measures [batch][4] = ||e||_inf | D | the maximum toward an infinite bound | S, and `it` to measured_at [batch], before
+// it is taken: for every problem the launch examined, whatever becomes of it (a NaN among them is stored as it is).
 //   grid (batch), block 256, dynamic LDS certify_lds_bytes(d).
 static __global__ __launch_bounds__(256) void box_certify(Dims d, int it, double eps, const double* __restrict__ AB,
                                                           const double* __restrict__ z, const double* __restrict__ zp,
@@ -46,7 +48,8 @@ static __global__ __launch_bounds__(256) void box_certify(Dims d, int it, double
                                                           double* __restrict__ rhs_cur, const double* __restrict__ rhs_next,
                                                           int* __restrict__ status, int* __restrict__ iters,
                                                           int* __restrict__ running, double* __restrict__ cert_lam,
-                                                          double* __restrict__ cert_mu) {
+                                                          double* __restrict__ cert_mu, double* __restrict__ measures,
+                                                          int* __restrict__ measured_at) {
 #pragma clang fp contract(off)
   extern __shared__ double certify_lds[];  // dlam of knots k0 .. k0 + G, [G + 1][n]
   __shared__ double red[5][256];           // |e|, |dmu|, |dmu| toward an infinite bound, S hi, S lo
@@ -112,6 +115,8 @@ static __global__ __launch_bounds__(256) void box_certify(Dims d, int it, double
   }
   if (tid == 0) {
     const double E = red[0][0], D = red[1][0], I = red[2][0], sum = red[3][0] + red[4][0];
+    measures[4 * (size_t)b] = E; measures[4 * (size_t)b + 1] = D; measures[4 * (size_t)b + 2] = I; measures[4 * (size_t)b + 3] = sum;
+    measured_at[b] = it;
     // a NaN or an infinity anywhere: no certificate (the comparisons alone would already refuse a NaN)
     const bool finite = isfinite(E) && isfinite(D) && isfinite(I) && isfinite(sum);
     const double tol = eps * D;

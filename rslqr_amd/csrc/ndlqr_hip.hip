@@ -1935,6 +1935,8 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
     if (infeas_every > 0) {  // (the certificate rows of the problems that do not end as 4 are zero)
       HIP_TRY(hipMemsetAsync(inf.cert_lam, 0, sizeof(double) * (size_t)d.batch * d.N * d.n, st));
       HIP_TRY(hipMemsetAsync(inf.cert_mu, 0, sizeof(double) * doubles_QR(d), st));
+      HIP_TRY(hipMemsetAsync(inf.measures, 0, sizeof(double) * 4 * (size_t)d.batch, st));
+      HIP_TRY(hipMemsetAsync(inf.measured_at, 0, sizeof(int) * (size_t)d.batch, st));
     }
     const auto is_check = [&](int i) { return infeas_every > 0 && i >= 2 && i <= max_iter && i % infeas_every == 0; };
     c->box.have_vy = true;
@@ -1957,7 +1959,7 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
                            (const double*)c->AB, (const double*)c->box.z, (const double*)inf.z_prev, (const double*)c->box.y,
                            (const double*)inf.y_prev, (const double*)c->box.rho, (const double*)inf.rho_prev, lo, hi, bs,
                            (const double*)s.rhs, c->box.rhs[(it - 1) & 1], (const double*)rn, c->box.status, c->box.iters,
-                           c->box.word, inf.cert_lam, inf.cert_mu);
+                           c->box.word, inf.cert_lam, inf.cert_mu, inf.measures, inf.measured_at);
         HIP_TRY(hipGetLastError());
       }
       if (is_check(it + 1)) {  // what the next iteration's check takes its differences against
@@ -2046,6 +2048,23 @@ int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* c, double* dlam, d
   err = out.copy(s.stream, false);
   if (err) return err;
   HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* c, double* measures, int* iteration) {
+  if (!c || (!measures && !iteration)) return NDLQR_ERR_INVALID;
+  if (c->infeas.gen == 0 || c->infeas.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
+    return refuse("ndlqr_hip_download_infeasibility_measures: the resident solution is not that of a constrained solve "
+                  "with infeasibility detection on (ndlqr_hip_set_box_infeasibility before the solve)");
+  HIP_TRY(hipSetDevice(c->device));
+  for (const void* p : {(const void*)measures, (const void*)iteration})
+    if (p && where(p, c->device) == Where::OtherDevice)
+      return refuse("ndlqr_hip_download_infeasibility_measures: an output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  // (stored in the caller's layout: plain copies, as ndlqr_hip_download_box_penalties)
+  const size_t nb = (size_t)c->d.batch;
+  if (measures) HIP_TRY(hipMemcpy(measures, c->infeas.measures, sizeof(double) * 4 * nb, hipMemcpyDefault));
+  if (iteration) HIP_TRY(hipMemcpy(iteration, c->infeas.measured_at, sizeof(int) * nb, hipMemcpyDefault));
   return NDLQR_OK;
 }
 

@@ -84,11 +84,13 @@ def farkas_check(prob, bounds, dlam, dmu_x, dmu_u, eps):
     return out
 
 
-def admm_infeas_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs, eps_rel, max_iter, every, eps=1e-4):
+def admm_infeas_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs, eps_rel, max_iter, every, eps=1e-4,
+                          trace=None):
     """box_support.admm_reference (fixed penalty, the operation order of strict mode) with the certificate test at the
     iterations it >= 2, it % every == 0, behind the update and the convergence test of that iteration. Returns
     (status, iters, dlam [N, n], dmu_x [N, n], dmu_u [N, m]): status 1 converged, 2 max_iter, 4 certified at `iters` (the
-    differences are those of that iteration; zeros otherwise)."""
+    differences are those of that iteration; zeros otherwise). trace: a list that takes (it, dlam, dmu_x, dmu_u) of
+    every check."""
     n, m, N = prob.n, prob.m, prob.N
     Mx, Mu = masks(n, m, N, xlo, xhi, ulo, uhi)
     M = np.concatenate([Mx, Mu], axis=1) > 0
@@ -121,6 +123,8 @@ def admm_infeas_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs, 
         if every > 0 and it >= 2 and it % every == 0:
             dlam, dmu = lam - lam_prev, mu - mu_prev
             c = farkas_check(prob, (xlo, xhi, ulo, uhi), dlam, dmu[:, :n], dmu[:, n:], eps)
+            if trace is not None:
+                trace.append((it, dlam, dmu[:, :n], dmu[:, n:]))
             if c["ok"]:
                 return 4, it, dlam, dmu[:, :n], dmu[:, n:]
         lam_prev, mu_prev = lam, mu

@@ -26,13 +26,17 @@ every case within 2000 iterations and ends no barely feasible problem as 4:
 (every test recomputes the reference's run of problem 1 once per case and asserts that it
 certifies). The device solve gets max_iter = 2 x (the reference's certification iteration) + EVERY and has to certify
 within one check interval of the reference: in fast mode its re-solve differs from the oracle's in the last bits, which
-can move a threshold crossing by one check.
+can move a threshold crossing by one check. In strict mode the device iterates are the restatement's bit for bit, so
+strict-knot and strict-generic certify at the reference's iteration exactly, with the reference's differences bit for
+bit and its four numbers (ndlqr_CopyBatchInfeasibilityMeasures) within the bounds of box_infeas_measures_support.py --
+wherever the reference's own margins are not within 1e-6 of 1 at that check and the one before, which the test asserts.
 """
 import functools
 
 import numpy as np
 import pytest
 
+from box_infeas_measures_support import measures_reference
 from box_infeas_support import admm_infeas_reference, barely_feasible_bounds, farkas_check, infeasible_bounds
 from box_support import condensed, split
 from support import Problem
@@ -84,7 +88,9 @@ class Case:
             if p == 1:
                 self.feasible1 = make(barely_feasible_bounds)  # the same problem after relaxing the bound: gap -> -gap
         self.bounds = [np.stack([r[i] for r in rows]) for i in range(4)]
-        self.ref = admm_infeas_reference(self.probs[1], self.solve, *rows[1], self.rho, ALPHA, EPS_ADMM, EPS_ADMM, 2000, EVERY, EPS)
+        self.trace = []
+        self.ref = admm_infeas_reference(self.probs[1], self.solve, *rows[1], self.rho, ALPHA, EPS_ADMM, EPS_ADMM, 2000, EVERY, EPS,
+                                         trace=self.trace)
         print("reference: problem 1 status %d at iteration %d" % self.ref[:2])
         assert self.ref[0] == 4, self.ref[:2]
         self.max_iter = 2 * self.ref[1] + EVERY
@@ -109,6 +115,24 @@ class Case:
         args = dict(rho=self.rho, alpha=ALPHA, eps_abs=EPS_ADMM, eps_rel=EPS_ADMM, max_iter=self.max_iter, check_every=EVERY)
         args.update(kw)
         return bs.solve_box(**args)
+
+    def decisive_margins(self):
+        """The reference's margins E / (eps D), I / (eps D) and S / (-eps D) at its certifying check and at the one before,
+        none of them within 1e-6 of 1: there the fp64 evaluation of the kernel decides as the reference does (its errors,
+        box_infeas_measures_support, are many orders below 1e-6 of these numbers). Returns the certifying check's
+        reference numbers."""
+        b = [a[1] for a in self.bounds]
+        refs = []
+        for it, dlam, dmu_x, dmu_u in self.trace[-2:]:
+            r = measures_reference(self.probs[1], b, dlam, dmu_x, dmu_u)
+            assert r["D"] > 0, (it, r)
+            margins = [r["E"] / (EPS * r["D"]), r["I"] / (EPS * r["D"]), r["S"] / (-EPS * r["D"])]
+            print("reference check at %d: E / (eps D) %.6g, I / (eps D) %.6g, S / (-eps D) %.6g" % (it, *margins))
+            assert all(abs(v - 1.0) > 1e-6 for v in margins), (it, margins)
+            assert max(r["tol_E"] / (EPS * r["D"]), r["tol_S"] / (EPS * r["D"])) < 1e-7, (it, r)
+            refs.append(r)
+        assert self.trace[-1][0] == self.ref[1] and (len(self.trace) < 2 or self.trace[-2][0] == self.ref[1] - EVERY)
+        return refs[-1]
 
     def check_certificate(self, bs, st, eps=EPS):
         """status-4 rows pass the long-double test at 2 eps (the factor covers the kernel's fp64 evaluation of e against
@@ -147,6 +171,19 @@ def test_infeasible_member_is_certified_in_every_family(ndlqr, oracle, monkeypat
     assert abs(int(it[1]) - case.ref[1]) <= EVERY, (it, case.ref[1])
     assert all(st[p] in (1, 2) for p in others(case)), st
     case.check_certificate(bs, st)
+    if case.flags == "strict":
+        # the device iterates are the restatement's bit for bit: the same check certifies, with the same differences, and
+        # the numbers it decided on are the reference's within the bounds of test_gpu_box_infeas_measures.py
+        ref = case.decisive_margins()
+        assert it[1] == case.ref[1], (it, case.ref[1])
+        dlam, dmu_x, dmu_u = bs.infeasibility_certificate()
+        assert np.array_equal(dlam[1], case.ref[2]) and np.array_equal(dmu_x[1], case.ref[3]) and np.array_equal(dmu_u[1], case.ref[4])
+        measures, at = bs.infeasibility_measures()
+        E, D, I, S = measures[1]
+        print("read-out at %d: E %.17g (ref %.17g) D %.17g I %.17g S %.17g (ref %.17g)" % (at[1], E, ref["E"], D, I, S, ref["S"]))
+        assert at[1] == case.ref[1]
+        assert D == ref["D"] and I == ref["I"], (D, ref["D"], I, ref["I"])
+        assert abs(E - ref["E"]) <= ref["tol_E"] and abs(S - ref["S"]) <= ref["tol_S"], (E, S, ref)
     bs.close()
 
 
