@@ -620,6 +620,33 @@ int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho);
 int ndlqr_BatchSetInfeasibilityDetection(NdLqrBatchSolver* bs, int every, double eps);
 int ndlqr_CopyBatchInfeasibilityCertificate(NdLqrBatchSolver* bs, double* dlam, double* dmu_x, double* dmu_u);
 int ndlqr_CopyBatchInfeasibilityMeasures(NdLqrBatchSolver* bs, double* measures, int* iteration);
+/* additive: safeguarded Anderson acceleration of the box-constrained solve. The cost of a
+ * constrained solve is its number of iterations; the ADMM is a fixed-point iteration in w = v + y over a problem's
+ * bounded entries, and type-II Anderson acceleration extrapolates it from the last mem iterations.
+ *   ndlqr_BatchSetBoxAcceleration: mem == 0 (the initial state) = off: no call changes a bit of any result, nothing is
+ *   allocated and no other kernel is launched. mem in 1 .. 16: the memory (5 is the documented choice). safeguard == 0 ->
+ *   1.0, reg == 0 -> 1e-10. mem < 0 or > 16, or safeguard or reg negative or not finite: NDLQR_ERR_INVALID and the
+ *   previous setting stays. The setting belongs to the solver and holds for every later constrained solve (not for
+ *   ndlqr_SolveBatchBoxAdjoint, whose ADMM is not accelerated).
+ *   The rule, per problem and iteration, with t = alpha z + (1 - alpha) v + y the plain successor of w = v + y and
+ *   g = t - (v + y): convergence, NaN and status are evaluated as without acceleration, on v+ = clip(t),
+ *   y+ = (y + zh) - v+, before anything else, and a converged problem freezes with them. If the iteration started from an
+ *   accelerated iterate and |g|_2 > safeguard |g_prev|_2, the step is rejected: v, y go back to the plain v+, y+ that the
+ *   step before saved, the history is cleared, and the next step is plain. Otherwise (t, g) joins a ring of mem + 1
+ *   entries; with c >= 1 columns dG = [g_(i+1) - g_i], dT = [t_(i+1) - t_i], gamma solves
+ *   (dG'dG + reg tr(dG'dG) / c I) gamma = dG'g by Cholesky and w+ = t - dT gamma gives v = clip(w+), y = w+ - v. A pivot
+ *   that is not positive, or a gamma or w+ that is not finite: the plain step, the history cleared. A problem whose
+ *   adaptive penalty moves takes the plain step and clears its history. Warm and cold starts begin with an empty history.
+ *   With ndlqr_BatchSetInfeasibilityDetection on, the iteration before a check and the check iteration take plain steps.
+ *   The ring is scratch of one solve: polish, adjoints, multipliers, penalties and warm starts see v, y, rho and status
+ *   as before. Results are the same from run to run (no floating-point atomics).
+ *   ndlqr_CopyBatchBoxAcceleration: of the latest constrained solve, accepted and rejected [batch] (steps taken
+ *   accelerated; steps rejected by the safeguard), gamma [batch][mem] (the coefficients of every problem's latest
+ *   accelerated step, oldest column first, zero beyond its column count) and columns [batch] (that count). Any may be
+ *   NULL, not all; host, pinned or the solver's device memory. NDLQR_ERR_INVALID unless the resident solution is that of
+ *   the latest constrained solve and acceleration was on for it. */
+int ndlqr_BatchSetBoxAcceleration(NdLqrBatchSolver* bs, int mem, double safeguard, double reg);
+int ndlqr_CopyBatchBoxAcceleration(NdLqrBatchSolver* bs, int* accepted, int* rejected, double* gamma, int* columns);
 /* additive: gradients through the box-constrained solve (differentiable MPC with actuator and state limits). After
  * ndlqr_SolveBatchBoxConstrained, for a loss L(z*) of the constrained solutions and g = dL/dz* (as for
  * ndlqr_SolveBatchAdjoint), ndlqr_SolveBatchBoxAdjoint solves the adjoint of the active-set system

@@ -142,6 +142,13 @@ int ndlqr_hip_download_box_penalties(NdlqrHipCtx* ctx, double* rho);
 int ndlqr_hip_set_box_infeasibility(NdlqrHipCtx* ctx, int every, double eps);
 int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* ctx, double* dlam, double* dmu_x, double* dmu_u);
 int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* ctx, double* measures, int* iteration);
+/* Anderson acceleration of the constrained solve (ndlqr.h: ndlqr_BatchSetBoxAcceleration, ndlqr_CopyBatchBoxAcceleration;
+ * DESIGN.md section 3.15). ndlqr_hip_set_box_acceleration takes the resolved setting (mem 0 .. 16, 0: off; safeguard and
+ * reg > 0 and finite) for the solves that follow. ndlqr_hip_download_box_acceleration: accepted, rejected, columns [batch]
+ * and gamma [batch][mem] of the latest constrained solve, which ran with acceleration on (each may be null, not all;
+ * host, pinned or this device's memory); refuses as ndlqr_hip_download_infeasibility_measures does. */
+int ndlqr_hip_set_box_acceleration(NdlqrHipCtx* ctx, int mem, double safeguard, double reg);
+int ndlqr_hip_download_box_acceleration(NdlqrHipCtx* ctx, int* accepted, int* rejected, double* gamma, int* columns);
 int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* ctx, double* mu_x, double* mu_u);
 unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* ctx);
 /* Gradients through the box-constrained solve (ndlqr.h: ndlqr_SolveBatchBoxAdjoint, ndlqr_BatchBoundGradients;

@@ -290,6 +290,8 @@ def lib():
     proto("ndlqr_BatchSetInfeasibilityDetection", ci, vp, ci, cd)
     proto("ndlqr_CopyBatchInfeasibilityCertificate", ci, vp, dp, dp, dp)
     proto("ndlqr_CopyBatchInfeasibilityMeasures", ci, vp, dp, C.POINTER(ci))
+    proto("ndlqr_BatchSetBoxAcceleration", ci, vp, ci, cd, cd)
+    proto("ndlqr_CopyBatchBoxAcceleration", ci, vp, C.POINTER(ci), C.POINTER(ci), dp, C.POINTER(ci))
     proto("ndlqr_SolveBatchBoxAdjoint", ci, vp, dp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_BatchBoundGradients", ci, vp, C.c_uint, dp, dp, dp, dp)
     proto("ndlqr_PolishBatchBoxConstrained", ci, vp, C.POINTER(NdLqrPolishSettings), C.POINTER(ci), C.POINTER(ci))
@@ -762,6 +764,31 @@ class BatchSolver:
             raise RuntimeError("ndlqr_CopyBatchInfeasibilityMeasures failed: %d (%s)"
                                % (err, self.L.ndlqr_hip_last_error().decode()))
         return measures, iteration
+
+    def set_box_acceleration(self, mem=0, safeguard=0.0, reg=0.0):
+        """ndlqr_BatchSetBoxAcceleration: mem in 1 .. 16 lets the constrained solves that follow take safeguarded
+        Anderson-accelerated steps from the last mem iterations (safeguard = 0: 1.0, reg = 0: 1e-10; 5 is the documented
+        memory); mem = 0 (the initial state): off. Raises on a refusal (mem outside 0 .. 16, safeguard or reg negative or
+        not finite); the previous setting then stays."""
+        err = self.L.ndlqr_BatchSetBoxAcceleration(self.h, int(mem), float(safeguard), float(reg))
+        if err:
+            raise RuntimeError("ndlqr_BatchSetBoxAcceleration failed: %d" % err)
+        self._accel_mem = int(mem)
+
+    def box_acceleration(self):
+        """ndlqr_CopyBatchBoxAcceleration: (accepted [batch], rejected [batch], gamma [batch, mem], columns [batch]) of
+        the last constrained solve, which ran with acceleration on: the steps it took accelerated, the steps its
+        safeguard rejected, and the coefficients and column count of every problem's latest accelerated step. Raises on
+        a refusal."""
+        B, mem = self.batch, getattr(self, "_accel_mem", 0)
+        ints = [np.zeros(B, dtype=np.int32) for _ in range(3)]
+        gamma = np.zeros((B, max(mem, 1)))
+        ip = [a.ctypes.data_as(C.POINTER(C.c_int)) for a in ints]
+        err = self.L.ndlqr_CopyBatchBoxAcceleration(self.h, ip[0], ip[1], _ptr(gamma), ip[2])
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchBoxAcceleration failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return ints[0], ints[1], gamma[:, :mem], ints[2]
 
     def box_penalties(self, rho=None):
         """ndlqr_CopyBatchBoxPenalties: rho [batch] of the last constrained solve (what an adaptive solve ended with);

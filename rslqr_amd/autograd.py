@@ -258,8 +258,9 @@ def _solve_box(bs, flat, bflat, all_shared, settings, token, key):
     err = bs.L.ndlqr_BatchSetBounds(bs.h, BOUNDS_SHARED if all_shared else 0, *ptrs)
     if err:
         raise ValueError("lqr_solve_box: the bounds were refused (%s)" % bs.L.ndlqr_hip_last_error().decode())
-    rho, alpha, eps_abs, eps_rel, max_iter, adapt_every, polish, infeas_every = settings
+    rho, alpha, eps_abs, eps_rel, max_iter, adapt_every, polish, infeas_every, accel_mem = settings
     bs.set_box_infeasibility(infeas_every)  # (the cached solver keeps the setting of whoever used it last)
+    bs.set_box_acceleration(accel_mem)
     try:
         _, status = bs.solve_box(rho=rho, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
                                  adapt_every=adapt_every)
@@ -314,7 +315,7 @@ class LqrSolveBox(torch.autograd.Function):
             _solve_box(bs, ctx.flat, ctx.bflat, ctx.all_shared, ctx.settings, ctx.token, ctx.key)
         gz = gz.detach().to(torch.float64).contiguous()
         torch.cuda.current_stream(gz.device).synchronize()
-        _, alpha, eps_abs, eps_rel, max_iter, _, polish, _ = ctx.settings
+        _, alpha, eps_abs, eps_rel, max_iter, _, polish, _, _ = ctx.settings
         if polish:
             _, status = bs.solve_polished_adjoint(_View(gz))
         else:
@@ -358,7 +359,7 @@ class LqrSolveBox(torch.autograd.Function):
 
 
 def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=None, *, rho=0.0, alpha=0.0, eps_abs=0.0,
-                  eps_rel=0.0, max_iter=0, adapt_every=0, polish=False, infeas_every=0):
+                  eps_rel=0.0, max_iter=0, adapt_every=0, polish=False, infeas_every=0, accel_mem=0):
     """z* [b, nvars] of the LQR problems of lqr_solve with xlo <= x_k <= xhi (k >= 1) and ulo <= u_k <= uhi, by the
     box-constrained batch solve (ndlqr_SolveBatchBoxConstrained, cold start; 0 = the library's default for every
     setting; adapt_every > 0: the per-problem adaptive penalty, considered every that many iterations, so that rho
@@ -372,9 +373,12 @@ def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=Non
     (ndlqr_SolveBatchPolishedAdjoint) with the same gradient assembly; raises when a problem's polish status is not 1.
     infeas_every > 0: primal infeasibility detection every that many iterations (ndlqr_BatchSetInfeasibilityDetection,
     default eps). A problem that is certified infeasible (status 4) does not raise: its z is the last iterate, which solves
-    nothing, and it gets zero gradients in every tensor -- the adjoint does not iterate it (w = 0, nu = 0)."""
+    nothing, and it gets zero gradients in every tensor -- the adjoint does not iterate it (w = 0, nu = 0).
+    accel_mem > 0: the forward's ADMM takes safeguarded Anderson-accelerated steps with that memory
+    (ndlqr_BatchSetBoxAcceleration, default safeguard and weight): fewer iterations to the same convergence test; the
+    backward is unchanged (the adjoint's ADMM is not accelerated)."""
     return LqrSolveBox.apply((float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(adapt_every),
-                              bool(polish), int(infeas_every)),
+                              bool(polish), int(infeas_every), int(accel_mem)),
                              A, B, Q, R, q, r, d, x0, xlo, xhi, ulo, uhi)
 
 

@@ -412,6 +412,16 @@ int ndlqr_CopyBatchInfeasibilityMeasures(NdLqrBatchSolver* bs, double* measures,
   if (!bs || (!measures && !iteration)) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_infeasibility_measures(bs->ctx, measures, iteration);
 }
+int ndlqr_BatchSetBoxAcceleration(NdLqrBatchSolver* bs, int mem, double safeguard, double reg) {
+  /* (x < HUGE_VAL is false for a NaN as well) */
+  if (!bs || mem < 0 || mem > 16 || !(safeguard >= 0.0 && safeguard < HUGE_VAL) || !(reg >= 0.0 && reg < HUGE_VAL))
+    return NDLQR_ERR_INVALID;
+  return ndlqr_hip_set_box_acceleration(bs->ctx, mem, safeguard > 0.0 ? safeguard : 1.0, reg > 0.0 ? reg : 1e-10);
+}
+int ndlqr_CopyBatchBoxAcceleration(NdLqrBatchSolver* bs, int* accepted, int* rejected, double* gamma, int* columns) {
+  if (!bs || (!accepted && !rejected && !gamma && !columns)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_box_acceleration(bs->ctx, accepted, rejected, gamma, columns);
+}
 int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u) {
   if (!bs || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_bound_multipliers(bs->ctx, mu_x, mu_u);

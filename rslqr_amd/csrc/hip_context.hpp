@@ -266,6 +266,26 @@ struct BoxInfeasState {
   }
 };
 
+// Anderson acceleration of the box-constrained solve (ndlqr_hip_set_box_acceleration, kernels_box_accel.hpp; DESIGN.md
+// section 3.15). mem, safeguard, reg: the setting (mem == 0: off -- nothing here is allocated or launched). Scratch of
+// one solve, zeroed or overwritten at its start: the ring of t and of g, ring_t, ring_g [batch][mem+1][N][n+m] (they
+// grow with mem); the plain v+, y+ an accelerated step saves, pv, py [batch][N][n+m]; per problem the Gram matrix
+// gram [batch][17][17], |g_prev| gprev [batch], gamma [batch][mem] of the latest accelerated step and the words
+// meta [6][batch] (ring start, ring fill, accelerated, accepted, rejected, columns). gen: the solution generation of the
+// latest constrained solve that ran accelerated (0: none), mem_solved: its memory -- what the read-out refers to.
+struct BoxAccelState {
+  DevBuf<double> ring_t, ring_g, pv, py, gram, gprev, gamma;
+  DevBuf<int> meta;
+  int mem = 0, mem_solved = 0;
+  double safeguard = 1.0, reg = 1e-10;
+  unsigned long long gen = 0;
+  hipError_t ensure(const ndlqr::Dims& d) {
+    const size_t nv = doubles_QR(d), nb = (size_t)d.batch;
+    return first_error({ring_t.grow((size_t)(mem + 1) * nv), ring_g.grow((size_t)(mem + 1) * nv), pv.ensure(nv), py.ensure(nv),
+                        gram.ensure(nb * 17 * 17), gprev.ensure(nb), gamma.ensure(nb * 16), meta.ensure(6 * nb)});
+  }
+};
+
 // Gradients through the box-constrained solve (ndlqr_hip_solve_box_adjoint / ndlqr_hip_bound_gradients,
 // kernels_box_grad.hpp). gen: the solution generation the box adjoint belongs to (0: none). The adjoint's own entry
 // codes, v, y, ADMM right-hand sides (its resident one is adj.rhs, its solution adj.z), per problem status, iterations
@@ -417,6 +437,7 @@ struct NdlqrHipCtx {
   AdjointState adj;
   BoxState box;
   BoxInfeasState infeas;
+  BoxAccelState accel;
   BoxAdjointState abox;
   RefineState ref;
   PolishState pol;

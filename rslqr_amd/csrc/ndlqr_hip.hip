@@ -12,6 +12,7 @@
 #include "kernels_generic.hpp"
 #include "kernels_box.hpp"
 #include "kernels_box_grad.hpp"
+#include "kernels_box_accel.hpp"
 #include "kernels_box_infeas.hpp"
 #include "kernels_box_polish.hpp"
 #include "kernels_grad.hpp"
@@ -1701,6 +1702,9 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
 // Infeasibility detection (ndlqr_hip_set_box_infeasibility, kernels_box_infeas.hpp): with a check
 // period set, the iteration before a check leaves copies of z, y and rho behind its box_update, and the check iteration
 // runs box_certify behind its own: a certified problem (status 4) leaves the running count like a converged one.
+// Anderson acceleration (ndlqr_hip_set_box_acceleration, kernels_box_accel.hpp): with a memory
+// set, box_update_accel takes the place of box_update in the loop; the iteration before an infeasibility check and the
+// check iteration take plain steps.
 
 
 // Bounds in the caller's layout, [P][N][n] and [P][N][m] with P = batch, or P = 1 (shared): this device's memory is read
@@ -1883,6 +1887,9 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   const int infeas_every = c->infeas.every;
   if (infeas_every > 0) HIP_TRY(c->infeas.ensure(d));
   c->infeas.gen = 0;
+  const int accel_mem = c->accel.mem;
+  if (accel_mem > 0) HIP_TRY(c->accel.ensure(d));
+  c->accel.gen = 0;
   // 1. everything idle, the primary set current with an up-to-date right-hand side
   HIP_TRY(sync_all(c));
   c->cur = 0;
@@ -1939,6 +1946,14 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
       HIP_TRY(hipMemsetAsync(inf.measured_at, 0, sizeof(int) * (size_t)d.batch, st));
     }
     const auto is_check = [&](int i) { return infeas_every > 0 && i >= 2 && i <= max_iter && i % infeas_every == 0; };
+    BoxAccelState& acc = c->accel;
+    const ndlqr::AccelParams AP = {accel_mem, acc.safeguard, acc.reg};
+    const ndlqr::AccelBufs AX = {acc.ring_t, acc.ring_g, acc.pv, acc.py, acc.gram, acc.gprev, acc.gamma, acc.meta};
+    if (accel_mem > 0) {  // an empty history, warm start or cold; the ring, pv, py and gram are written before they are read
+      HIP_TRY(hipMemsetAsync(acc.meta, 0, sizeof(int) * ndlqr::ACCEL_WORDS * (size_t)d.batch, st));
+      HIP_TRY(hipMemsetAsync(acc.gprev, 0, sizeof(double) * (size_t)d.batch, st));
+      HIP_TRY(hipMemsetAsync(acc.gamma, 0, sizeof(double) * (size_t)accel_mem * d.batch, st));
+    }
     c->box.have_vy = true;
     c->box.h_word[0] = d.batch;
     c->box.h_word[1] = 0;
@@ -1950,9 +1965,14 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
       e = launch_resolve(c, rc, c->box.z, "box-constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
       if (e) return e;
       const int adapt = adapt_every > 0 && it % adapt_every == 0 && it < max_iter;
-      launch_strict(strict, ndlqr::box_update, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box.z, lo, hi,
-                    bs, c->box.v, c->box.y, (const double*)s.rhs, rc, rn, c->box.rho, c->box.status, c->box.iters,
-                    c->box.resid, c->box.word);
+      if (accel_mem > 0)
+        launch_strict(strict, ndlqr::box_update_accel, dim3(d.batch), dim3(256), 0, st, d, it, adapt,
+                      is_check(it) || is_check(it + 1) ? 1 : 0, P, AP, (const double*)c->box.z, lo, hi, bs, c->box.v, c->box.y,
+                      (const double*)s.rhs, rc, rn, c->box.rho, c->box.status, c->box.iters, c->box.resid, c->box.word, AX);
+      else
+        launch_strict(strict, ndlqr::box_update, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box.z, lo, hi,
+                      bs, c->box.v, c->box.y, (const double*)s.rhs, rc, rn, c->box.rho, c->box.status, c->box.iters,
+                      c->box.resid, c->box.word);
       HIP_TRY(hipGetLastError());
       if (is_check(it)) {  // the differences over this iteration: a certificate?
         hipLaunchKernelGGL(ndlqr::box_certify, dim3(d.batch), dim3(256), ndlqr::certify_lds_bytes(d), st, d, it, inf.eps,
@@ -2012,6 +2032,10 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   note_solution(c);
   c->box.soln_gen = c->soln_gen;
   if (infeas_every > 0) c->infeas.gen = c->soln_gen;
+  if (accel_mem > 0) {
+    c->accel.gen = c->soln_gen;
+    c->accel.mem_solved = accel_mem;
+  }
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   c->timing_pending = true;
   err = deliver_iters_status(c, st, c->box.iters, c->box.status, iters, status);
@@ -2065,6 +2089,36 @@ int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* c, double* measures, 
   const size_t nb = (size_t)c->d.batch;
   if (measures) HIP_TRY(hipMemcpy(measures, c->infeas.measures, sizeof(double) * 4 * nb, hipMemcpyDefault));
   if (iteration) HIP_TRY(hipMemcpy(iteration, c->infeas.measured_at, sizeof(int) * nb, hipMemcpyDefault));
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_set_box_acceleration(NdlqrHipCtx* c, int mem, double safeguard, double reg) {
+  if (!c || mem < 0 || mem > ndlqr::ACCEL_MEM_MAX || !(safeguard > 0.0 && safeguard < HUGE_VAL) || !(reg > 0.0 && reg < HUGE_VAL))
+    return NDLQR_ERR_INVALID;
+  c->accel.mem = mem;
+  c->accel.gen = 0;  // (the read-out's gamma has the width of the memory it ran with: a solve with this setting first)
+  c->accel.safeguard = safeguard;
+  c->accel.reg = reg;
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_download_box_acceleration(NdlqrHipCtx* c, int* accepted, int* rejected, double* gamma, int* columns) {
+  if (!c || (!accepted && !rejected && !gamma && !columns)) return NDLQR_ERR_INVALID;
+  if (c->accel.gen == 0 || c->accel.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
+    return refuse("ndlqr_hip_download_box_acceleration: the resident solution is not that of a constrained solve with "
+                  "acceleration on (ndlqr_hip_set_box_acceleration before the solve)");
+  HIP_TRY(hipSetDevice(c->device));
+  for (const void* p : {(const void*)accepted, (const void*)rejected, (const void*)gamma, (const void*)columns})
+    if (p && where(p, c->device) == Where::OtherDevice)
+      return refuse("ndlqr_hip_download_box_acceleration: an output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  // (stored in the caller's layout: plain copies, as ndlqr_hip_download_box_penalties)
+  const size_t nb = (size_t)c->d.batch;
+  const int* meta = c->accel.meta;
+  if (accepted) HIP_TRY(hipMemcpy(accepted, meta + ndlqr::ACCEL_ACCEPTED * nb, sizeof(int) * nb, hipMemcpyDefault));
+  if (rejected) HIP_TRY(hipMemcpy(rejected, meta + ndlqr::ACCEL_REJECTED * nb, sizeof(int) * nb, hipMemcpyDefault));
+  if (columns) HIP_TRY(hipMemcpy(columns, meta + ndlqr::ACCEL_COLUMNS * nb, sizeof(int) * nb, hipMemcpyDefault));
+  if (gamma) HIP_TRY(hipMemcpy(gamma, c->accel.gamma, sizeof(double) * nb * c->accel.mem_solved, hipMemcpyDefault));
   return NDLQR_OK;
 }
 
