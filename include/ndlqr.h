@@ -565,7 +565,19 @@ int ndlqr_BatchKktResidualVector(NdLqrBatchSolver* bs, double* r);
  *   loop keeps what it learnt; otherwise every problem starts at the settings' rho. A fixed-rho solve reuses a
  *   remembered factorisation only when all its penalties are that rho. iters and status keep their meaning.
  *   adapt_every < 0 or rho_min > rho_max: NDLQR_ERR_INVALID. ndlqr_CopyBatchBoxPenalties: rho [batch] of the latest
- *   constrained solve (host, pinned or the solver's device memory). */
+ *   constrained solve (host, pinned or the solver's device memory).
+ *   ndlqr_CopyBatchBoxResiduals: the four numbers of the convergence test above as every problem's last update found
+ *   them, resid [batch][4] = r_prim | r_dual | s_prim | s_dual with r_prim = ||z - v||_inf, r_dual = rho ||v - v_prev||_inf,
+ *   s_prim = max(||z||_inf, ||v||_inf), s_dual = rho ||y||_inf over the bounded entries (host, pinned or the solver's device
+ *   memory). A row holds the values of the last update the problem took part in: the iteration at which it was frozen for
+ *   status 1, 3 and 4 (a NaN or an infinity is stored as it is), iteration max_iter for status 2; they are stored before
+ *   the decision, with the penalty the iteration ran with. A problem without a bounded entry converges at iteration 1
+ *   and has a row of zeros. With them a caller whose problem ended as 2 sees how far it was from the tolerance.
+ *   NDLQR_ERR_INVALID unless the resident solution is that of a constrained solve with the current bounds (as
+ *   ndlqr_SolveBatchBoxAdjoint: no solve, step, re-solve or ndlqr_BatchSetBounds since).
+ *   ndlqr_CopyBatchBoxAdjointResiduals: the same four numbers of the latest ndlqr_SolveBatchBoxAdjoint (below), whose
+ *   iteration has the same test; a problem that the box adjoint does not iterate (forward status 3 or 4) has a row of
+ *   zeros. NDLQR_ERR_INVALID unless there is a box adjoint of the resident solution (as ndlqr_BatchBoundGradients). */
 typedef struct {
   double rho;       /* penalty; 0 -> 0.1 */
   double alpha;     /* over-relaxation in (0, 2); 0 -> 1.6 */
@@ -584,6 +596,8 @@ int ndlqr_BatchSetBounds(NdLqrBatchSolver* bs, unsigned flags, const double* xlo
 int ndlqr_SolveBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status);
 int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* mu_u);
 int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho);
+int ndlqr_CopyBatchBoxResiduals(NdLqrBatchSolver* bs, double* resid);
+int ndlqr_CopyBatchBoxAdjointResiduals(NdLqrBatchSolver* bs, double* resid);
 /* additive: primal infeasibility detection in the box-constrained solve. State bounds make
  * infeasibility an ordinary event in MPC; without detection such a problem keeps the whole batch iterating to max_iter.
  *   ndlqr_BatchSetInfeasibilityDetection: every == 0 (the initial state) = off: no call changes a bit of its result.

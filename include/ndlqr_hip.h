@@ -127,11 +127,16 @@ int ndlqr_hip_solve_box(NdlqrHipCtx* ctx, double rho, double alpha, double eps_a
  * every running problem move its rho by a power of two at every adapt_every-th iteration, within [rho_min, rho_max]
  * (resolved: 0 < rho_min <= rho_max), and the batch is factored again whenever one did; adapt_every == 0 is
  * ndlqr_hip_solve_box. ndlqr_hip_download_box_penalties: rho [batch] of the latest constrained solve (host, pinned or
- * this device's memory). */
+ * this device's memory). ndlqr_hip_download_box_residuals, ndlqr_hip_download_box_adjoint_residuals: resid [batch][4] =
+ * r_prim | r_dual | s_prim | s_dual of every problem's last update in the latest constrained solve / box adjoint (ndlqr.h:
+ * ndlqr_CopyBatchBoxResiduals, ndlqr_CopyBatchBoxAdjointResiduals), same destinations; they refuse unless the resident
+ * solution is that of a constrained solve / has a box adjoint. */
 int ndlqr_hip_solve_box_ex(NdlqrHipCtx* ctx, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
                            int check_every, int warm_start, int* iters, int* status, int adapt_every, double rho_min,
                            double rho_max);
 int ndlqr_hip_download_box_penalties(NdlqrHipCtx* ctx, double* rho);
+int ndlqr_hip_download_box_residuals(NdlqrHipCtx* ctx, double* resid);
+int ndlqr_hip_download_box_adjoint_residuals(NdlqrHipCtx* ctx, double* resid);
 /* Infeasibility detection of the constrained solve (ndlqr.h: ndlqr_BatchSetInfeasibilityDetection,
  * ndlqr_CopyBatchInfeasibilityCertificate). ndlqr_hip_set_box_infeasibility takes the resolved
  * setting (every >= 0, 0: off; eps > 0 and finite) for the solves that follow. ndlqr_hip_download_infeasibility_certificate:

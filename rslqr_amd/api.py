@@ -287,6 +287,8 @@ def lib():
     proto("ndlqr_SolveBatchBoxConstrained", ci, vp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_CopyBatchBoundMultipliers", ci, vp, dp, dp)
     proto("ndlqr_CopyBatchBoxPenalties", ci, vp, dp)
+    proto("ndlqr_CopyBatchBoxResiduals", ci, vp, dp)
+    proto("ndlqr_CopyBatchBoxAdjointResiduals", ci, vp, dp)
     proto("ndlqr_BatchSetInfeasibilityDetection", ci, vp, ci, cd)
     proto("ndlqr_CopyBatchInfeasibilityCertificate", ci, vp, dp, dp, dp)
     proto("ndlqr_CopyBatchInfeasibilityMeasures", ci, vp, dp, C.POINTER(ci))
@@ -799,6 +801,25 @@ class BatchSolver:
         if err:
             raise RuntimeError("ndlqr_CopyBatchBoxPenalties failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return rho
+
+    def _residuals(self, name, resid):
+        if resid is None:
+            resid = np.zeros((self.batch, 4))
+        err = getattr(self.L, name)(self.h, _any_ptr(resid, 4 * self.batch))
+        if err:
+            raise RuntimeError("%s failed: %d (%s)" % (name, err, self.L.ndlqr_hip_last_error().decode()))
+        return resid
+
+    def box_residuals(self, resid=None):
+        """ndlqr_CopyBatchBoxResiduals: [batch, 4] = r_prim | r_dual | s_prim | s_dual of the last constrained solve, the
+        numbers of the convergence test as the last update of every problem found them (its freezing iteration, or
+        max_iter for status 2); `resid`: destination (numpy array or DeviceArray). Raises on a refusal."""
+        return self._residuals("ndlqr_CopyBatchBoxResiduals", resid)
+
+    def box_adjoint_residuals(self, resid=None):
+        """ndlqr_CopyBatchBoxAdjointResiduals: the same of the last box adjoint (a row of zeros for a problem it did
+        not iterate)."""
+        return self._residuals("ndlqr_CopyBatchBoxAdjointResiduals", resid)
 
     def bound_multipliers(self, mu_x=None, mu_u=None):
         """ndlqr_CopyBatchBoundMultipliers: (mu_x [batch, N, n], mu_u [batch, N, m]) = rho y of the last constrained solve;

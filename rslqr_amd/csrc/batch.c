@@ -399,6 +399,14 @@ int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho) {
   if (!bs || !rho) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_box_penalties(bs->ctx, rho);
 }
+int ndlqr_CopyBatchBoxResiduals(NdLqrBatchSolver* bs, double* resid) {
+  if (!bs || !resid) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_box_residuals(bs->ctx, resid);
+}
+int ndlqr_CopyBatchBoxAdjointResiduals(NdLqrBatchSolver* bs, double* resid) {
+  if (!bs || !resid) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_box_adjoint_residuals(bs->ctx, resid);
+}
 int ndlqr_BatchSetInfeasibilityDetection(NdLqrBatchSolver* bs, int every, double eps) {
   /* (eps < HUGE_VAL is false for a NaN as well) */
   if (!bs || every < 0 || !(eps >= 0.0 && eps < HUGE_VAL)) return NDLQR_ERR_INVALID;

@@ -217,7 +217,8 @@ struct AdjointState {
 
 // Box-constrained solve by ADMM (ndlqr_hip_set_bounds / ndlqr_hip_solve_box, kernels_box.hpp). Bounds lo | hi in the
 // device layout [batch][N][n+m] ([N][n+m] when shared: bstride 0) and their bounded pattern; v, y and two ADMM
-// right-hand sides (ping-pong) and the re-solve's z; per problem status, iterations and residuals; rho: the penalty of
+// right-hand sides (ping-pong) and the re-solve's z; per problem status, iterations and residuals (resid [batch][4] =
+// r_prim | r_dual | sp | sd of its last update: the read-out of ndlqr_hip_download_box_residuals); rho: the penalty of
 // every problem [batch]; word: running count | problems whose penalty changed | lo > hi | pattern changed (h_word: the
 // same four, then the box adjoint's running count). The shifted factorisation is remembered (fact) with its penalties --
 // rho, and rho_value when rho_uniform says they are all that one value -- and what the plain API's kept state was after
@@ -241,7 +242,7 @@ struct BoxState {
     return first_error({mask.ensure_zeroed(nv, st), lo.ensure(nv), hi.ensure(nv), word.ensure(4), h_word.ensure(5),
                         z.ensure_zeroed(nz, st),  // (entries a re-solve does not write: the pad rows)
                         v.ensure(nv), y.ensure(nv), qr_save.ensure(nv), rhs[0].ensure(nz), rhs[1].ensure(nz),
-                        resid.ensure(2 * nb), status.ensure(nb), iters.ensure(nb), rho.ensure(nb)});
+                        resid.ensure(4 * nb), status.ensure(nb), iters.ensure(nb), rho.ensure(nb)});
   }
 };
 
@@ -298,7 +299,7 @@ struct BoxAdjointState {
   hipError_t ensure(const ndlqr::Dims& d) {
     const size_t nz = doubles_z(d), nv = doubles_QR(d), nb = (size_t)d.batch;
     return first_error({code.ensure(nv), v.ensure(nv), y.ensure(nv), rhs[0].ensure(nz), rhs[1].ensure(nz),
-                        resid.ensure(2 * nb), status.ensure(nb), iters.ensure(nb), word.ensure(1)});
+                        resid.ensure(4 * nb), status.ensure(nb), iters.ensure(nb), word.ensure(1)});
   }
 };
 

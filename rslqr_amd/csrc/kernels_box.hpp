@@ -213,8 +213,10 @@ __global__ __launch_bounds__(256) void box_update(Dims d, int it, int adapt, Box
                         isfinite(red[4][0]);
     const int conv = finite && r_prim <= tol_p && r_dual <= tol_d;
     iters[b] = it;
-    resid[2 * (size_t)b] = r_prim;
-    resid[2 * (size_t)b + 1] = r_dual;
+    resid[4 * (size_t)b] = r_prim;  // the read-out (ndlqr_CopyBatchBoxResiduals): the four numbers of the test below
+    resid[4 * (size_t)b + 1] = r_dual;
+    resid[4 * (size_t)b + 2] = sp;
+    resid[4 * (size_t)b + 3] = sd;
     if (conv || !finite) {
       status[b] = conv ? 1 : 3;
       atomicSub(running, 1);

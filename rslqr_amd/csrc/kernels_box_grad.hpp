@@ -127,14 +127,17 @@ __global__ __launch_bounds__(256) void box_adjoint_update(Dims d, int it, BoxPar
   }
   if (tid == 0) {
     const double r_prim = red[0][0], r_dual = rho * red[1][0];
-    const double tol_p = P.eps_abs + P.eps_rel * max_nan(red[2][0], red[3][0]);
-    const double tol_d = P.eps_abs + P.eps_rel * (rho * red[4][0]);
+    const double sp = max_nan(red[2][0], red[3][0]), sd = rho * red[4][0];
+    const double tol_p = P.eps_abs + P.eps_rel * sp;
+    const double tol_d = P.eps_abs + P.eps_rel * sd;
     const bool finite = isfinite(r_prim) && isfinite(r_dual) && isfinite(red[2][0]) && isfinite(red[3][0]) &&
                         isfinite(red[4][0]);
     const int conv = finite && r_prim <= tol_p && r_dual <= tol_d;
     iters[b] = it;
-    resid[2 * (size_t)b] = r_prim;
-    resid[2 * (size_t)b + 1] = r_dual;
+    resid[4 * (size_t)b] = r_prim;  // the read-out (ndlqr_CopyBatchBoxAdjointResiduals)
+    resid[4 * (size_t)b + 1] = r_dual;
+    resid[4 * (size_t)b + 2] = sp;
+    resid[4 * (size_t)b + 3] = sd;
     if (conv || !finite) {
       status[b] = conv ? 1 : 3;
       atomicSub(running, 1);

@@ -2133,6 +2133,31 @@ int ndlqr_hip_download_box_penalties(NdlqrHipCtx* c, double* rho) {
   return NDLQR_OK;
 }
 
+// resid [batch][4] of a constrained solve or its adjoint (`who`), stored in the caller's layout: a plain copy
+static int download_resid(NdlqrHipCtx* c, const char* who, const double* d_resid, double* resid) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (where(resid, c->device) == Where::OtherDevice)
+    return refuse(std::string(who) + ": the output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  HIP_TRY(hipMemcpy(resid, d_resid, sizeof(double) * 4 * (size_t)c->d.batch, hipMemcpyDefault));
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_download_box_residuals(NdlqrHipCtx* c, double* resid) {
+  if (!c || !resid) return NDLQR_ERR_INVALID;
+  if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.resid)
+    return refuse("ndlqr_hip_download_box_residuals: the resident solution is not that of a constrained solve");
+  return download_resid(c, "ndlqr_hip_download_box_residuals", c->box.resid, resid);
+}
+
+int ndlqr_hip_download_box_adjoint_residuals(NdlqrHipCtx* c, double* resid) {
+  if (!c || !resid) return NDLQR_ERR_INVALID;
+  if (c->abox.gen == 0 || c->abox.gen != c->soln_gen || !c->abox.resid)
+    return refuse("ndlqr_hip_download_box_adjoint_residuals: no box adjoint of the resident solution "
+                  "(ndlqr_hip_solve_box_adjoint after the latest constrained solve)");
+  return download_resid(c, "ndlqr_hip_download_box_adjoint_residuals", c->abox.resid, resid);
+}
+
 int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* mu_u) {
   if (!c || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
   if (!c->box.have_vy || !c->box.y) return refuse("ndlqr_hip_download_bound_multipliers: no constrained solve yet");
@@ -2217,6 +2242,8 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
     // 3. codes, v = y = 0, right-hand sides, status
     const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
     HIP_TRY(hipMemsetAsync(c->abox.word, 0, sizeof(int), st));
+    // (the read-out row of a problem that is not iterated -- forward status 3 or 4 -- is zero)
+    HIP_TRY(hipMemsetAsync(c->abox.resid, 0, sizeof(double) * 4 * (size_t)d.batch, st));
     launch_strict(strict, ndlqr::box_adjoint_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, (const double*)c->box.lo,
                   (const double*)c->box.hi, c->box.bstride, (const double*)c->box.v, (const int*)c->box.status,
                   (const double*)c->adj.rhs, c->abox.code, c->abox.v, c->abox.y, c->abox.rhs[0], c->abox.rhs[1], c->abox.status,

@@ -34,10 +34,11 @@ def penalty_step(rho, r_prim, r_dual, sp, sd, rho_min=RHO_MIN, rho_max=RHO_MAX):
 
 
 def admm_adaptive_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs, eps_rel, max_iter, adapt_every,
-                            rho_min=RHO_MIN, rho_max=RHO_MAX):
+                            rho_min=RHO_MIN, rho_max=RHO_MAX, trace=None):
     """The iteration of DESIGN.md sections 3.9 and 3.11 in the operation order of strict mode; solve(problem) -> z (nvars).
     adapt_every == 0: box_support.admm_reference. Returns (x, u from v as [N, n], [N, m]; mu_x, mu_u; lam of the last
-    solve; iters; status; the final rho; the number of times rho changed)."""
+    solve; iters; status; the final rho; the number of times rho changed). trace: a list that gets one dict per iteration
+    -- it, resid = (r_prim, r_dual, sp, sd) and rho, the penalty the iteration ran with."""
     n, m, N = prob.n, prob.m, prob.N
     Mx, Mu = masks(n, m, N, xlo, xhi, ulo, uhi)
     M = np.concatenate([Mx, Mu], axis=1) > 0
@@ -68,6 +69,8 @@ def admm_adaptive_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs
         finite = all(math.isfinite(a) for a in (r_prim, r_dual, mx(zx), mx(vn), mx(yn)))
         conv = finite and r_prim <= eps_abs + eps_rel * sp and r_dual <= eps_abs + eps_rel * sd
         v, y = vn, yn
+        if trace is not None:
+            trace.append(dict(it=it, resid=(r_prim, r_dual, sp, sd), rho=rho))
         if conv or not finite:
             status = 1 if conv else 3
             break

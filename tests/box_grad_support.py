@@ -145,10 +145,10 @@ def adjoint_problem(prob, g):
     return Problem(n, m, N, prob.A, prob.B, prob.Q, prob.R, -G[:, n:2 * n], r, d, -G[0, :n])
 
 
-def adjoint_admm_reference(prob, solve, codes, g, rho, alpha, eps_abs, eps_rel, max_iter):
+def adjoint_admm_reference(prob, solve, codes, g, rho, alpha, eps_abs, eps_rel, max_iter, trace=None):
     """The box adjoint's iteration in the operation order of strict mode: box_support's
     admm_reference on the adjoint problem with lo = hi = 0 on the fixed entries (codes 2, 3) and the identity as the clip
-    of the free ones (code 1). Returns (w [nvars], nu [N, n+m], iters, status)."""
+    of the free ones (code 1). trace: as for admm_reference. Returns (w [nvars], nu [N, n+m], iters, status)."""
     n, m, N = prob.n, prob.m, prob.N
     ap = adjoint_problem(prob, g)
     M = codes > 0
@@ -175,8 +175,12 @@ def adjoint_admm_reference(prob, solve, codes, g, rho, alpha, eps_abs, eps_rel, 
         mx = lambda a: float(np.abs(a[M]).max()) if M.any() else 0.0
         r_prim = mx(zx - vn)
         r_dual = rho * mx(vn - v)
-        conv = r_prim <= eps_abs + eps_rel * max(mx(zx), mx(vn)) and r_dual <= eps_abs + eps_rel * (rho * mx(yn))
+        sp = max(mx(zx), mx(vn))
+        sd = rho * mx(yn)
+        conv = r_prim <= eps_abs + eps_rel * sp and r_dual <= eps_abs + eps_rel * sd
         v, y = vn, yn
+        if trace is not None:
+            trace.append(dict(it=it, Z=Z.copy(), v=v.copy(), y=y.copy(), resid=(r_prim, r_dual, sp, sd), conv=bool(conv)))
         if conv:
             status = 1
             break

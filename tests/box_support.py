@@ -84,8 +84,11 @@ def masks(n, m, N, xlo, xhi, ulo, uhi):
     return Mx, Mu
 
 
-def admm_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs, eps_rel, max_iter):
+def admm_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs, eps_rel, max_iter, start=None, trace=None):
     """The iteration of DESIGN.md section 3.9 in the operation order of strict mode; solve(problem) -> z (nvars).
+    start: (v, y) [N, n+m] of a warm start (box_start: the entries bounded now keep them, y of the others is zero and
+    their v is not read); None: cold. trace: a list that gets one dict per iteration -- it, Z (the re-solve as blocks),
+    v, y after the update, resid = (r_prim, r_dual, sp, sd) and conv (box_update_support.py reads it).
     Returns (x, u from v as [N, n], [N, m]; mu_x, mu_u; lam of the last solve; iters; status)."""
     n, m, N = prob.n, prob.m, prob.N
     Mx, Mu = masks(n, m, N, xlo, xhi, ulo, uhi)
@@ -97,6 +100,12 @@ def admm_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs, eps_rel
     y = np.zeros((N, n + m))
     oma = 1.0 - alpha
     qt = q.copy()
+    if start is not None:
+        v = np.where(M, start[0], 0.0)
+        y = np.where(M, start[1], 0.0)
+        t = y - v
+        t = rho * t
+        qt = np.where(M, q + t, q)
     status, it = 0, 0
     Z = None
     for it in range(1, max_iter + 1):
@@ -111,8 +120,12 @@ def admm_reference(prob, solve, xlo, xhi, ulo, uhi, rho, alpha, eps_abs, eps_rel
         mx = lambda a: float(np.abs(a[M]).max()) if M.any() else 0.0
         r_prim = mx(zx - vn)
         r_dual = rho * mx(vn - v)
-        conv = r_prim <= eps_abs + eps_rel * max(mx(zx), mx(vn)) and r_dual <= eps_abs + eps_rel * (rho * mx(yn))
+        sp = max(mx(zx), mx(vn))
+        sd = rho * mx(yn)
+        conv = r_prim <= eps_abs + eps_rel * sp and r_dual <= eps_abs + eps_rel * sd
         v, y = vn, yn
+        if trace is not None:
+            trace.append(dict(it=it, Z=Z.copy(), v=v.copy(), y=y.copy(), resid=(r_prim, r_dual, sp, sd), conv=bool(conv)))
         if conv:
             status = 1
             break
