@@ -362,6 +362,23 @@ typedef struct NdLqrBatchSolver NdLqrBatchSolver;
  * ndlqr_hip_last_error() = "global scratch ... does not fit" if the device is too small for the batch). The factor-based
  * rhs-only re-solve reads the factor where it lies beyond ~140 states. */
 
+/* The batch solver takes ANY horizon nhorizon >= 2 (the drop-in ndlqr_NewNdLqrSolver keeps the reference's power of two).
+ * A horizon that is no power of two runs padded to the next one on the device ("Padded horizon"):
+ * decoupled unit knots behind the caller's, which solve to exactly zero, and the caller's last knot as an interior knot
+ * with [A | B] = 0, R = 1, r = 0 -- A, B, R, r, d of the last knot are not part of the problem and are never read. Every
+ * array of the API keeps the caller's shapes ([batch][nhorizon][..], nvars = (2n+m) nhorizon - m); the padding is exact;
+ * a solve costs what the next power of two costs. Carried through: the four initialisers, ndlqr_SolveBatch / ...Async in
+ * every flag mode, ndlqr_BatchSetRhsFlat + ndlqr_SolveBatchRhsOnly, ndlqr_BatchStepAsync, the step selection and the
+ * slice functions (knots below nhorizon), ndlqr_CopyBatchSolution(s)(Device), ndlqr_BatchKktResiduals,
+ * ndlqr_BatchKktResidualVector, ndlqr_SolveBatchAdjoint, ndlqr_CopyBatchAdjoint, ndlqr_BatchGradients,
+ * ndlqr_BatchSetBounds, ndlqr_SolveBatchBoxConstrained (fixed and adaptive penalty), ndlqr_CopyBatchBoundMultipliers,
+ * ndlqr_CopyBatchBoxPenalties, ndlqr_CopyBatchBoxResiduals.
+ * REFUSED at a padded horizon (NDLQR_ERR_INVALID, ndlqr_hip_last_error() names the horizon): ndlqr_SolveBatchMultiRhs(Slices),
+ * ndlqr_RefineBatch(Adjoint), ndlqr_SolveBatchBoxAdjoint, ndlqr_BatchBoundGradients, ndlqr_CopyBatchBoxAdjointResiduals,
+ * ndlqr_PolishBatchBoxConstrained, ndlqr_SolveBatchPolishedAdjoint, ndlqr_BatchSetInfeasibilityDetection (every > 0) and
+ * its two getters, ndlqr_BatchSetBoxAcceleration (mem > 0) and ndlqr_CopyBatchBoxAcceleration, the ndlqr_BatchTimeShard*
+ * functions, ndlqr_CopyBatchFactors, and of ndlqr_hip.h: ndlqr_hip_device_pointers, ndlqr_hip_staged_io,
+ * ndlqr_hip_download_rhs_blocks, ndlqr_hip_download_polish_codes. */
 NdLqrBatchSolver* ndlqr_NewBatchSolver(int nstates, int ninputs, int nhorizon, int batch,
                                        int device);
 int ndlqr_FreeBatchSolver(NdLqrBatchSolver* bs);

@@ -35,7 +35,10 @@ typedef struct NdlqrHipCtx NdlqrHipCtx;
 int ndlqr_hip_device_count(void);
 const char* ndlqr_hip_last_error(void);
 
-/* replaces the allocation half of ndlqr_NewNdLqrSolver (src/solver.c:61-96) for a batch */
+/* replaces the allocation half of ndlqr_NewNdLqrSolver (src/solver.c:61-96) for a batch.
+ * nhorizon: any value >= 2. One that is no power of two runs padded to the next one on the device (the horizon padding is
+ * not optional: NDLQR_CREATE_NO_PAD and NDLQR_NO_PAD govern the block size only); the functions below keep the caller's
+ * horizon in every array they take or fill, or refuse (include/ndlqr.h, at ndlqr_NewBatchSolver, has the list). */
 NdlqrHipCtx* ndlqr_hip_create(int nstates, int ninputs, int nhorizon, int batch, int device);
 /* ... with creation options: NDLQR_CREATE_NO_PAD keeps the caller's block size on the device (a block size without
  * a size-specialised instance otherwise runs zero-padded inside one, with another array layout: raw device pointers

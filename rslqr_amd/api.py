@@ -307,6 +307,8 @@ def lib():
     proto("ndlqr_hip_profile_get", ci, vp, ci, C.c_char_p, ci, dp, C.POINTER(ci))
     proto("ndlqr_hip_profile_reset", ci, vp)
     proto("ndlqr_hip_device_pointers", ci, vp, C.POINTER(vp))
+    proto("ndlqr_hip_staged_io", ci, vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp))
+    proto("ndlqr_hip_download_rhs_blocks", ci, vp, ci, dp)
     proto("ndlqr_hip_upload_inputs", ci, vp, ci, ci, dp, dp, dp)
     proto("ndlqr_hip_factors_valid", ci, vp)
     proto("ndlqr_hip_schedule", C.c_char_p, vp)
@@ -723,7 +725,7 @@ class BatchSolver:
         setting then stays."""
         err = self.L.ndlqr_BatchSetInfeasibilityDetection(self.h, int(every), float(eps))
         if err:
-            raise RuntimeError("ndlqr_BatchSetInfeasibilityDetection failed: %d" % err)
+            raise RuntimeError("ndlqr_BatchSetInfeasibilityDetection failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
 
     def infeasibility_certificate(self, dlam=None, dmu_x=None, dmu_u=None):
         """ndlqr_CopyBatchInfeasibilityCertificate: (dlam [batch, N, n], dmu_x [batch, N, n], dmu_u [batch, N, m]) of the
@@ -774,7 +776,7 @@ class BatchSolver:
         not finite); the previous setting then stays."""
         err = self.L.ndlqr_BatchSetBoxAcceleration(self.h, int(mem), float(safeguard), float(reg))
         if err:
-            raise RuntimeError("ndlqr_BatchSetBoxAcceleration failed: %d" % err)
+            raise RuntimeError("ndlqr_BatchSetBoxAcceleration failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         self._accel_mem = int(mem)
 
     def box_acceleration(self):
@@ -934,6 +936,10 @@ class BatchSolver:
             raise RuntimeError("ndlqr_hip_upload_inputs failed: %d" % err)
 
     def factors(self, p):
+        if self.N & (self.N - 1):
+            # (a padded horizon: the factor array is that of the device's tree, which the library does not hand out)
+            raise RuntimeError("ndlqr_CopyBatchFactors: not available for a padded horizon (horizon %d is no power of two)"
+                               % self.N)
         K = int(np.log2(self.N))
         out = np.zeros(self.N * K * (2 * self.n + self.m) * self.n)
         err = self.L.ndlqr_CopyBatchFactors(self.h, p, _ptr(out))

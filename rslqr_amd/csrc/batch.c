@@ -24,6 +24,9 @@
 
 struct NdLqrBatchSolver {
   int n, m, N, K, batch, nvars, device;
+  int cut; /* the horizon runs padded to the next power of two on the device: the caller's last knot, N - 1, is an
+              interior device knot there and goes up as [A | B] = 0, R = 1 (its A, B, R, r, d are not part of the
+              problem and are never read) */
   NdlqrHipCtx* ctx;
   /* host staging for `chunk` problems */
   int chunk;
@@ -39,8 +42,8 @@ static size_t rhs_doubles(const NdLqrBatchSolver* bs) { return (size_t)bs->N * (
 NdLqrBatchSolver* ndlqr_NewBatchSolver(int nstates, int ninputs, int nhorizon, int batch,
                                        int device) {
   if (nstates <= 0 || ninputs <= 0 || batch <= 0) return NULL;
-  if (nhorizon < 2 || !IsPowerOfTwo(nhorizon)) {
-    fprintf(stderr, "ERROR: horizon must be a power of two >= 2, got %d.\n", nhorizon);
+  if (nhorizon < 2) { /* (any horizon: one that is no power of two runs padded to the next one, ndlqr_hip_create_ex) */
+    fprintf(stderr, "ERROR: horizon must be >= 2, got %d.\n", nhorizon);
     return NULL;
   }
   NdlqrHipCtx* ctx = ndlqr_hip_create(nstates, ninputs, nhorizon, batch, device);
@@ -50,7 +53,9 @@ NdLqrBatchSolver* ndlqr_NewBatchSolver(int nstates, int ninputs, int nhorizon, i
   }
   NdLqrBatchSolver* bs = (NdLqrBatchSolver*)calloc(1, sizeof(*bs));
   if (!bs) { ndlqr_hip_destroy(ctx); return NULL; }
-  bs->n = nstates; bs->m = ninputs; bs->N = nhorizon; bs->K = LogOfTwo(nhorizon);
+  bs->n = nstates; bs->m = ninputs; bs->N = nhorizon;
+  bs->K = 0; while ((1 << bs->K) < nhorizon) ++bs->K; /* levels of the device's tree */
+  bs->cut = !IsPowerOfTwo(nhorizon);
   bs->batch = batch; bs->device = device; bs->ctx = ctx;
   bs->nvars = (2 * nstates + ninputs) * nhorizon - ninputs;
   /* stage at most ~64 MB of packed inputs at a time */
@@ -88,6 +93,12 @@ static void pack_knot(const NdLqrBatchSolver* bs, int slot, int k, const double*
   const int n = bs->n, m = bs->m, w = n + m;
   double* AB = bs->hAB + (size_t)slot * ab_doubles(bs) + (size_t)k * n * w;
   double* QR = bs->hQR + (size_t)slot * qr_doubles(bs) + (size_t)k * w;
+  if (bs->cut && k == bs->N - 1) {
+    memset(AB, 0, sizeof(double) * (size_t)n * w);
+    memcpy(QR, Qk, sizeof(double) * n);
+    for (int j = 0; j < m; ++j) QR[n + j] = 1.0;
+    return;
+  }
   for (int i = 0; i < n; ++i) {
     for (int j = 0; j < n; ++j) AB[i * w + j] = Ak[i + n * j];
     for (int j = 0; j < m; ++j) AB[i * w + n + j] = Bk[i + n * j];

@@ -382,9 +382,10 @@ struct MultiRhsState {
 
 struct NdlqrHipCtx {
   ndlqr::Dims d = {};   // block sizes of the DEVICE layout (every kernel works on these)
-  ndlqr::Dims du = {};  // the caller's block sizes: the same, or smaller when the problem runs zero-padded into the next
-                        // size-specialised instance ("padded shapes", ndlqr_hip_create); only the boundary functions see it
-  bool padded = false;
+  ndlqr::Dims du = {};  // the caller's block sizes and horizon: the same, or smaller when the problem runs zero-padded into
+                        // the next size-specialised instance ("padded shapes", ndlqr_hip_create) or with its horizon padded
+                        // to the next power of two (du.N < d.N, "padded horizon"); only the boundary functions see it
+  bool padded = false;  // d differs from du in a block size or in the horizon
   int device = 0;
   unsigned flags = 0;
   DevKnobs knobs;

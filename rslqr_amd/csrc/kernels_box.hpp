@@ -33,7 +33,9 @@ __device__ __forceinline__ double max_nan(double m, double a) { return (a > m ||
 // Bounds in the caller's layout -- xlo, xhi [P][N][n], ulo, uhi [P][N][m], P = batch or 1 (shared); nullptr: unbounded --
 // into the device layout lo, hi [P][N][n+m]. commit == 0: only check, *bad = 1 when lo > hi (or NaN) for an entry that is
 // used. commit == 1: write lo, hi, and the bounded pattern into mask, *changed = 1 where it differs from what mask held.
-//   grid (N, P), block 64.
+// The caller's arrays have du.N knots, the device's d.N: the tail knots of a padded horizon (k >= du.N) and u of the
+// caller's last knot du.N - 1 are unbounded whatever the bounds say, and the caller's arrays are not read there.
+//   grid (d.N, P), block 64.
 static __global__ void box_bounds(Dims du, Dims d, const double* __restrict__ xlo, const double* __restrict__ xhi,
                                   const double* __restrict__ ulo, const double* __restrict__ uhi, int commit,
                                   double* __restrict__ lo, double* __restrict__ hi, unsigned char* __restrict__ mask,
@@ -44,13 +46,13 @@ static __global__ void box_bounds(Dims du, Dims d, const double* __restrict__ xl
   for (int j = threadIdx.x; j < d.w; j += blockDim.x) {
     double l = -HUGE_VAL, h = HUGE_VAL;
     if (j < d.n) {
-      if (j < du.n && k > 0) {
+      if (j < du.n && k > 0 && k < du.N) {
         if (xlo) l = xlo[xo + j];
         if (xhi) h = xhi[xo + j];
       }
     } else {
       const int i = j - d.n;
-      if (i < du.m && k < d.N - 1) {
+      if (i < du.m && k < du.N - 1) {
         if (ulo) l = ulo[uo + i];
         if (uhi) h = uhi[uo + i];
       }
@@ -279,7 +281,7 @@ static __global__ void box_finish(Dims d, const double* __restrict__ lo, const d
 }
 
 // Multipliers mu = rho[b] y into the caller's flat layout: mu_x [batch][N][n], mu_u [batch][N][m] (either may be nullptr).
-//   grid (N, batch), block 64.
+//   grid (du.N, batch), block 64.
 static __global__ void box_multipliers(Dims du, Dims d, const double* __restrict__ rhov, const double* __restrict__ y,
                                        double* __restrict__ mu_x, double* __restrict__ mu_u) {
   const int k = blockIdx.x, b = blockIdx.y;

@@ -324,7 +324,12 @@ __global__ void schur_generic(Dims d, int l, double* F, double* z, int boundary,
 // KP consecutive knots per workgroup, every thread's KP loads of a round in flight before its first store: with one knot per
 // workgroup and a load or two per thread the launch ran at (bytes in flight) / (memory latency) = 3 TB/s -- 330 us per
 // 1024 x (12,4,256), a third of an iteration of a loop that replaces the whole problem. grid (N / KP, batch).
-template <int KP>
+// HP ("padded horizon", du.N < d.N: ndlqr_hip.hip): the grid covers the device's d.N knots, the caller's arrays have
+// du.N. Per knot of the workgroup: knots >= du.N write nothing (pad_fill_generic's decoupled unit knots stay); knot
+// du.N - 1, the caller's last, becomes an interior device knot with [A | B] = 0, R = 1 and a zero r slot written here --
+// the caller's A, B, R, r of that knot are not loaded (nor is its d: the lambda block of knot du.N stays zero) -- and
+// takes the caller's Q and q only. HP = false is the code as it was.
+template <int KP, bool HP = false>
 static __global__ void pack_flat_generic(Dims du, Dims d, const double* __restrict__ A, const double* __restrict__ B,
                                   const double* __restrict__ Q, const double* __restrict__ R,
                                   const double* __restrict__ q, const double* __restrict__ r,
@@ -332,41 +337,48 @@ static __global__ void pack_flat_generic(Dims du, Dims d, const double* __restri
                                   double* __restrict__ AB, double* __restrict__ QR, double* __restrict__ rhs) {
   const int k0 = blockIdx.x * KP, b = blockIdx.y;
   const int n = du.n, m = du.m, N = du.N;
-  const size_t pk0 = (size_t)b * N + k0;
+  // knots of this workgroup the caller has / whose A, B, R the caller's arrays provide
+  const int nreal = HP ? (N - k0 < KP ? N - k0 : KP) : KP, nfull = HP ? (N - 1 - k0 < KP ? N - 1 - k0 : KP) : KP;
+  if (HP && nreal <= 0) return;
+  const size_t pk0 = (size_t)b * N + k0, dk0 = (size_t)b * d.N + k0;
   for (int e = threadIdx.x; e < n * du.w; e += blockDim.x) {
     const int i = e / du.w, j = e - i * du.w;
     const double* src = j < n ? A + pk0 * n * n + (i + n * j) : B + pk0 * n * m + (i + n * (j - n));
     const size_t sstr = j < n ? (size_t)n * n : (size_t)n * m;
-    double* dst = AB + pk0 * d.n * d.w + (i * d.w + (j < n ? j : d.n + (j - n)));
+    double* dst = AB + dk0 * d.n * d.w + (i * d.w + (j < n ? j : d.n + (j - n)));
     double v[KP];
 #pragma unroll
-    for (int kk = 0; kk < KP; ++kk) v[kk] = src[kk * sstr];
+    for (int kk = 0; kk < KP; ++kk) v[kk] = (!HP || kk < nfull) ? src[kk * sstr] : 0.0;
 #pragma unroll
-    for (int kk = 0; kk < KP; ++kk) dst[(size_t)kk * d.n * d.w] = v[kk];
+    for (int kk = 0; kk < KP; ++kk)
+      if (!HP || kk < nreal) dst[(size_t)kk * d.n * d.w] = v[kk];
   }
   for (int e = threadIdx.x; e < du.w; e += blockDim.x) {
     const double* src = e < n ? Q + pk0 * n + e : R + pk0 * m + (e - n);
     const int sstr = e < n ? n : m;
-    double* dst = QR + pk0 * d.w + (e < n ? e : d.n + (e - n));
+    double* dst = QR + dk0 * d.w + (e < n ? e : d.n + (e - n));
     double v[KP];
 #pragma unroll
-    for (int kk = 0; kk < KP; ++kk) v[kk] = src[kk * sstr];
+    for (int kk = 0; kk < KP; ++kk) v[kk] = (!HP || kk < (e < n ? nreal : nfull)) ? src[kk * sstr] : 1.0;
 #pragma unroll
-    for (int kk = 0; kk < KP; ++kk) dst[kk * d.w] = v[kk];
+    for (int kk = 0; kk < KP; ++kk)
+      if (!HP || kk < nreal) dst[kk * d.w] = v[kk];
   }
   for (int e = threadIdx.x; e < du.rows; e += blockDim.x) {
-    double* dst = rhs + pk0 * d.rows + (e < n ? e : (e < 2 * n ? d.n + (e - n) : 2 * d.n + (e - 2 * n)));
+    double* dst = rhs + dk0 * d.rows + (e < n ? e : (e < 2 * n ? d.n + (e - n) : 2 * d.n + (e - 2 * n)));
     double v[KP];
 #pragma unroll
     for (int kk = 0; kk < KP; ++kk) {
       const int k = k0 + kk;
       const size_t pk = pk0 + kk;
-      if (e < n) v[kk] = k == 0 ? -x0[(size_t)b * n + e] : -dd[(pk - 1) * n + e];
+      if (HP && kk >= nreal) v[kk] = 0.0;
+      else if (e < n) v[kk] = k == 0 ? -x0[(size_t)b * n + e] : -dd[(pk - 1) * n + e];
       else if (e < 2 * n) v[kk] = -q[pk * n + (e - n)];
       else v[kk] = k < N - 1 ? -r[pk * m + (e - 2 * n)] : 0.0;
     }
 #pragma unroll
-    for (int kk = 0; kk < KP; ++kk) dst[kk * d.rows] = v[kk];
+    for (int kk = 0; kk < KP; ++kk)
+      if (!HP || kk < nreal) dst[kk * d.rows] = v[kk];
   }
 }
 
@@ -374,6 +386,8 @@ static __global__ void pack_flat_generic(Dims du, Dims d, const double* __restri
 // lines) and leave row-major through LDS -- column j of [A | B] at pack_tile[P j ..], pitch P = n | 1 (odd: the transposed
 // reads of a wavefront, stride P doubles, fall into distinct banks). The direct form reads with a stride of n doubles
 // between lanes: at (64,16) every lane a line of its own, 2.3 TB/s. grid (N, batch), dynamic LDS P (n + m) doubles.
+// A padded horizon (du.N < d.N, see pack_flat_generic): the grid covers d.N knots; knots >= du.N return, knot du.N - 1
+// gets [A | B] = 0 and R = 1 without loading the caller's.
 static __global__ __launch_bounds__(256) void pack_flat_tiled(Dims du, Dims d, const double* __restrict__ A,
                                                               const double* __restrict__ B, const double* __restrict__ Q,
                                                               const double* __restrict__ R, const double* __restrict__ q,
@@ -383,18 +397,20 @@ static __global__ __launch_bounds__(256) void pack_flat_tiled(Dims du, Dims d, c
   extern __shared__ __attribute__((aligned(16))) double pack_tile[];
   const int k = blockIdx.x, b = blockIdx.y;
   const int n = du.n, m = du.m, N = du.N, P = n | 1;
-  const size_t pk = (size_t)b * N + k;
+  if (k >= N) return;  // (a tail knot of a padded horizon; uniform over the workgroup)
+  const bool cut = N < d.N && k == N - 1;  // the caller's last knot as an interior device knot
+  const size_t pk = (size_t)b * N + k, dk = (size_t)b * d.N + k;
   const double* Ak = A + pk * n * n;
   const double* Bk = B + pk * n * m;
   for (int e = threadIdx.x; e < n * du.w; e += blockDim.x) {  // (B_k follows A_k's columns: column j of [A | B] = entries n j ..)
     const int j = e / n, i = e - j * n;
-    pack_tile[i + P * j] = j < n ? Ak[e] : Bk[e - n * n];
+    pack_tile[i + P * j] = cut ? 0.0 : (j < n ? Ak[e] : Bk[e - n * n]);
   }
   // the vectors meanwhile (independent of the tile)
-  double* qr = QR + pk * d.w;
+  double* qr = QR + dk * d.w;
   for (int e = threadIdx.x; e < du.w; e += blockDim.x)
-    qr[e < n ? e : d.n + (e - n)] = e < n ? Q[pk * n + e] : R[pk * m + (e - n)];
-  double* z = rhs + pk * d.rows;
+    qr[e < n ? e : d.n + (e - n)] = e < n ? Q[pk * n + e] : (cut ? 1.0 : R[pk * m + (e - n)]);
+  double* z = rhs + dk * d.rows;
   for (int e = threadIdx.x; e < du.rows; e += blockDim.x) {
     double v;
     if (e < n) v = k == 0 ? -x0[(size_t)b * n + e] : -dd[(pk - 1) * n + e];
@@ -403,7 +419,7 @@ static __global__ __launch_bounds__(256) void pack_flat_tiled(Dims du, Dims d, c
     z[e < n ? e : (e < 2 * n ? d.n + (e - n) : 2 * d.n + (e - 2 * n))] = v;
   }
   __syncthreads();
-  double* ab = AB + pk * d.n * d.w;
+  double* ab = AB + dk * d.n * d.w;
   for (int e = threadIdx.x; e < n * du.w; e += blockDim.x) {
     const int i = e / du.w, j = e - i * du.w;
     ab[i * d.w + (j < n ? j : d.n + (j - n))] = pack_tile[i + P * j];
@@ -422,20 +438,26 @@ static __global__ void pad_fill_generic(Dims d, double* __restrict__ AB, double*
 
 // Packed inputs in the CALLER's block size (the host layout of ndlqr_hip_upload_inputs, staged in HBM) into the padded
 // device arrays of problems [p0, p0 + count). Null sAB: the right-hand side alone. grid (N, count).
+// A padded horizon (du.N < d.N): the grid covers d.N knots, the staging has du.N; knots >= du.N return, knot du.N - 1 gets
+// [A | B] = 0, R = 1 and a zero r slot without reading the staged ones.
 static __global__ void pad_inputs_generic(Dims du, Dims d, const int p0, const double* __restrict__ sAB,
                                           const double* __restrict__ sQR, const double* __restrict__ srhs,
                                           double* __restrict__ AB, double* __restrict__ QR, double* __restrict__ rhs) {
+  if ((int)blockIdx.x >= du.N) return;
   const size_t sk = (size_t)blockIdx.y * du.N + blockIdx.x, pk = ((size_t)p0 + blockIdx.y) * d.N + blockIdx.x;
   const int n = du.n;
+  const bool cut = du.N < d.N && (int)blockIdx.x == du.N - 1;
   if (sAB) {
     for (int e = threadIdx.x; e < n * du.w; e += blockDim.x) {
       const int i = e / du.w, j = e - i * du.w;
-      AB[pk * d.n * d.w + i * d.w + (j < n ? j : d.n + (j - n))] = sAB[sk * n * du.w + e];
+      AB[pk * d.n * d.w + i * d.w + (j < n ? j : d.n + (j - n))] = cut ? 0.0 : sAB[sk * n * du.w + e];
     }
-    for (int e = threadIdx.x; e < du.w; e += blockDim.x) QR[pk * d.w + (e < n ? e : d.n + (e - n))] = sQR[sk * du.w + e];
+    for (int e = threadIdx.x; e < du.w; e += blockDim.x)
+      QR[pk * d.w + (e < n ? e : d.n + (e - n))] = (cut && e >= n) ? 1.0 : sQR[sk * du.w + e];
   }
   for (int e = threadIdx.x; e < du.rows; e += blockDim.x)
-    rhs[pk * d.rows + (e < n ? e : (e < 2 * n ? d.n + (e - n) : 2 * d.n + (e - 2 * n)))] = srhs[sk * du.rows + e];
+    rhs[pk * d.rows + (e < n ? e : (e < 2 * n ? d.n + (e - n) : 2 * d.n + (e - 2 * n)))] =
+        (cut && e >= 2 * n) ? 0.0 : srhs[sk * du.rows + e];
 }
 
 // One problem's solution blocks [N][2 n + m] (caller's block size, the u slot of the last knot included) out of
@@ -469,6 +491,24 @@ __device__ __forceinline__ void pack_rhs_one(const Dims& du, const Dims& d, cons
   }
 }
 
+// HP ("padded horizon", du.N < d.N): the caller's arrays have du.N knots per problem, the device's d.N. Entry g of part
+// `which` of the caller's arrays into the device right-hand side: r and d of the caller's last knot are not loaded (the
+// r slot there is written as zero, the lambda block of knot du.N stays zero).
+__device__ __forceinline__ void pack_rhs_one_hp(const Dims& du, const Dims& d, const int which, const size_t g,
+                                                const double* __restrict__ p, double* __restrict__ rhs) {
+  const size_t n = du.n, m = du.m, rows = d.rows, N = du.N, np = d.n;
+  const size_t wdt = which == 1 ? m : n;
+  const size_t pk = g / wdt, e = g - pk * wdt;      // (x0: pk is the problem)
+  if (which == 3) { rhs[pk * (size_t)d.N * rows + e] = -p[g]; return; }
+  const size_t b = pk / N, k = pk - b * N, dk = b * (size_t)d.N + k;  // knot k of problem b: device knot dk
+  if (which == 0) rhs[dk * rows + np + e] = -p[g];
+  else if (which == 1) rhs[dk * rows + 2 * np + e] = k < N - 1 ? -p[g] : 0.0;
+  else if (k < N - 1) rhs[(dk + 1) * rows + e] = -p[g];
+}
+
+// HP = false is the kernel as it was; HP = true (a padded horizon) a plain grid-stride loop that decides per entry
+// before it loads.
+template <bool HP = false>
 static __global__ __launch_bounds__(256) void pack_rhs_stream_generic(Dims du, Dims d, const double* __restrict__ q,
                                                                       const double* __restrict__ r,
                                                                       const double* __restrict__ dd,
@@ -484,14 +524,18 @@ static __global__ __launch_bounds__(256) void pack_rhs_stream_generic(Dims du, D
     if (!p) continue;
     const size_t n = cnt[which];
     size_t i = t0;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-      const double a = p[i], b = p[i + stride], c = p[i + 2 * stride], e = p[i + 3 * stride];
-      pack_rhs_one(du, d, which, i, a, rhs);
-      pack_rhs_one(du, d, which, i + stride, b, rhs);
-      pack_rhs_one(du, d, which, i + 2 * stride, c, rhs);
-      pack_rhs_one(du, d, which, i + 3 * stride, e, rhs);
+    if constexpr (HP) {
+      for (; i < n; i += stride) pack_rhs_one_hp(du, d, which, i, p, rhs);
+    } else {
+      for (; i + 3 * stride < n; i += 4 * stride) {
+        const double a = p[i], b = p[i + stride], c = p[i + 2 * stride], e = p[i + 3 * stride];
+        pack_rhs_one(du, d, which, i, a, rhs);
+        pack_rhs_one(du, d, which, i + stride, b, rhs);
+        pack_rhs_one(du, d, which, i + 2 * stride, c, rhs);
+        pack_rhs_one(du, d, which, i + 3 * stride, e, rhs);
+      }
+      for (; i < n; i += stride) pack_rhs_one(du, d, which, i, p[i], rhs);
     }
-    for (; i < n; i += stride) pack_rhs_one(du, d, which, i, p[i], rhs);
   }
 }
 

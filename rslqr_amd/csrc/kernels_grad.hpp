@@ -18,16 +18,18 @@ namespace ndlqr {
 
 // The adjoint right-hand side: g [batch][nvars] in the caller's block sizes (the packing of ndlqr_CopyBatchSolutions)
 // into the device blocks [batch][N][2n+m]; the input slot of the last knot and the pad entries of a padded shape are zero.
-//   grid (N, batch), block 64.
+// The last knot is the caller's, du.N - 1; the tail knots of a padded horizon (k >= du.N) are zero and g is not read there.
+//   grid (d.N, batch), block 64.
 static __global__ void adjoint_rhs_generic(Dims du, Dims d, const double* __restrict__ g, double* __restrict__ rhs) {
   const int k = blockIdx.x, b = blockIdx.y;
   const size_t nvars = (size_t)du.rows * du.N - du.m;
   const double* gk = g + (size_t)b * nvars + (size_t)k * du.rows;
   double* rk = rhs + ((size_t)b * d.N + k) * d.rows;
-  const bool last = k == d.N - 1;
+  const bool last = k == du.N - 1, tail = k >= du.N;
   for (int r = threadIdx.x; r < d.rows; r += blockDim.x) {
     int e = -1;
-    if (r < d.n) e = r < du.n ? r : -1;
+    if (tail) e = -1;
+    else if (r < d.n) e = r < du.n ? r : -1;
     else if (r < 2 * d.n) e = r - d.n < du.n ? du.n + (r - d.n) : -1;
     else e = (r - 2 * d.n < du.m && !last) ? 2 * du.n + (r - 2 * d.n) : -1;
     rk[r] = e >= 0 ? gk[e] : 0.0;
@@ -65,6 +67,9 @@ __host__ __device__ inline int grad_width(const Dims& du, const int o) {
 // writes the per-problem outputs. Each workgroup takes its problems in order and every thread owns the same accumulator
 // entries throughout, so the sums are deterministic. Outputs are written as contiguous runs of the flat layout:
 // consecutive lanes, consecutive elements.
+// A padded horizon (du.N < d.N): the grid and the chunks are the device's (the same workgroups, splits and order of
+// summation as a solver of horizon d.N), the outputs the caller's -- [batch][du.N][width], [du.N][width] summed: a chunk
+// covers its knots below du.N only, the last knot is du.N - 1.
 // STRICT: no contraction, gA / gB as t1 = a b, t2 = c e, s = t1 + t2, out = -s (numpy reproduces them bit for bit).
 template <bool STRICT>
 __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int KC, const int ppb, const int EC,
@@ -73,6 +78,8 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int n = du.n, N = d.N, rows = d.rows, xo = d.n, uo = 2 * d.n;
   const int k0 = blockIdx.x * KC, nk1 = (KC + 1 < N - k0) ? KC + 1 : N - k0;
+  if (k0 >= du.N) return;  // (a chunk in the tail of a padded horizon; uniform over the block)
+  const int KU = KC < du.N - k0 ? KC : du.N - k0;  // the caller's knots of this chunk
   const int p0 = blockIdx.y * ppb, p1 = (p0 + ppb < du.batch) ? p0 + ppb : du.batch;
   double* zs = sm;
   double* ws = zs + (KC + 1) * rows;
@@ -84,7 +91,7 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
     int a = 0;
     for (int o = 0; o < GRAD_COUNT; ++o) {
       aoff[o] = a;
-      if (out.p[o] && (out.sum & (1u << o))) a += o == GRAD_x0 ? (k0 == 0 ? n : 0) : KC * grad_width(du, o);
+      if (out.p[o] && (out.sum & (1u << o))) a += o == GRAD_x0 ? (k0 == 0 ? n : 0) : KU * grad_width(du, o);
     }
     if (blockIdx.z > 0 && a <= s0) return;  // (a further slice with no entries in this chunk; uniform over the block)
     for (int e = tid; e < (a < s1 ? a : s1) - s0; e += blockDim.x) acc[e] = 0.0;  // (the first barrier below orders these)
@@ -103,11 +110,11 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
       const bool summed = (out.sum & (1u << o)) != 0;
       if (!summed && blockIdx.z > 0) continue;
       const int W = grad_width(du, o);
-      const int E = o == GRAD_x0 ? (k0 == 0 ? n : 0) : KC * W;
+      const int E = o == GRAD_x0 ? (k0 == 0 ? n : 0) : KU * W;
       const int e0 = summed && s0 > aoff[o] ? s0 - aoff[o] : 0, e1 = summed && s1 - aoff[o] < E ? s1 - aoff[o] : E;
       for (int e = e0 + tid; e < e1; e += blockDim.x) {
         const int kk = e / W, rr = e - kk * W, k = k0 + kk;
-        const bool last = k == N - 1;
+        const bool last = k == du.N - 1;
         const double* Z = zs + kk * rows;
         const double* Wv = ws + kk * rows;
         double v;
@@ -135,14 +142,14 @@ __global__ __launch_bounds__(256) void grad_assemble(Dims du, Dims d, const int 
           default: v = -Wv[rr]; break;  // x0: lambda of knot 0
         }
         if (summed) acc[aoff[o] + e - s0] += v;
-        else dst[(o == GRAD_x0 ? (size_t)p * n : ((size_t)p * N + k0) * W) + e] = v;
+        else dst[(o == GRAD_x0 ? (size_t)p * n : ((size_t)p * du.N + k0) * W) + e] = v;
       }
     }
   }
   for (int o = 0; o < GRAD_COUNT; ++o) {
     if (!out.p[o] || !(out.sum & (1u << o))) continue;
     const int W = grad_width(du, o);
-    const int E = o == GRAD_x0 ? (k0 == 0 ? n : 0) : KC * W;
+    const int E = o == GRAD_x0 ? (k0 == 0 ? n : 0) : KU * W;
     const int e0 = s0 > aoff[o] ? s0 - aoff[o] : 0, e1 = s1 - aoff[o] < E ? s1 - aoff[o] : E;
     double* dst = part ? part + (size_t)blockIdx.y * out.total + out.off[o] : out.p[o];
     const size_t at = o == GRAD_x0 ? 0 : (size_t)k0 * W;

@@ -43,6 +43,14 @@ static int refuse(const std::string& msg) {
   return NDLQR_ERR_INVALID;
 }
 
+// Padded horizon (ndlqr_hip_create_ex): an entry point that is not carried through refuses here -- it would index the
+// caller's arrays, which have du.N knots, with the device's d.N
+static int need_unpadded_horizon(const NdlqrHipCtx* c, const char* who) {
+  if (c->du.N == c->d.N) return NDLQR_OK;
+  return refuse(std::string(who) + ": not available for a padded horizon (horizon " + std::to_string(c->du.N) +
+                " runs as " + std::to_string(c->d.N) + " knots); use a power-of-two horizon");
+}
+
 // Where a caller's array lives. A pointer the runtime does not know (an ordinary malloc'ed one is "invalid value" to older
 // runtimes) is pageable host memory.
 enum class Where { Pageable, Pinned, OwnDevice, OtherDevice };
@@ -113,7 +121,7 @@ NdlqrHipCtx* ndlqr_hip_create(int nstates, int ninputs, int nhorizon, int batch,
 }
 
 NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int batch, int device, unsigned create_flags) {
-  if (nstates <= 0 || ninputs <= 0 || batch <= 0 || nhorizon < 2 || (nhorizon & (nhorizon - 1))) {
+  if (nstates <= 0 || ninputs <= 0 || batch <= 0 || nhorizon < 2 || nhorizon > (1 << 24)) {
     g_last_error = "invalid dimensions";
     return nullptr;
   }
@@ -141,12 +149,19 @@ NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int bat
   c->knobs = read_knobs();
   c->pipeline = c->knobs.pipeline;
   ndlqr::Dims& d = c->d;
-  auto set_dims = [&](ndlqr::Dims& x, int n_, int m_) {
-    x.n = n_; x.m = m_; x.N = nhorizon; x.batch = batch;
-    x.K = 0; while ((1 << x.K) < nhorizon) ++x.K;
+  // Padded horizon: the device works on the next power of two (the tree, the schedules and the size-specialised kernels
+  // see nothing else); the knots beyond the caller's are decoupled unit knots ([A | B] = 0, Q = R = 1, zero right-hand
+  // side: pad_fill_generic) and the caller's last knot becomes an interior device knot with [A | B] = 0, R = 1 and a zero
+  // r slot (the pack kernels). The tail solves to exactly zero and the caller's solution is a prefix of the device's.
+  int phorizon = 1;
+  while (phorizon < nhorizon) phorizon <<= 1;
+  auto set_dims = [&](ndlqr::Dims& x, int n_, int m_, int N_) {
+    x.n = n_; x.m = m_; x.N = N_; x.batch = batch;
+    x.K = 0; while ((1 << x.K) < phorizon) ++x.K;
     x.rows = 2 * n_ + m_; x.w = n_ + m_; x.fb = x.rows * n_; x.xoff = 0;
   };
-  set_dims(c->du, nstates, ninputs);
+  set_dims(c->du, nstates, ninputs, nhorizon);
+  nhorizon = phorizon;  // (everything below is sized and chosen by the device's horizon)
   // Padded shapes: a block size without a size-specialised instance runs zero-padded inside the cheapest instance
   // that contains it (dummy states and inputs with unit weights and no coupling: they solve to exactly zero and the
   // real variables see the same arithmetic plus exact zeros) instead of the runtime-sized kernels, which are 3-4x
@@ -161,8 +176,8 @@ NdlqrHipCtx* ndlqr_hip_create_ex(int nstates, int ninputs, int nhorizon, int bat
     pn = (nstates + 15) / 16 * 16;
     pm = ninputs + (4 - (pn + ninputs) % 4) % 4;
   }
-  set_dims(d, pn, pm);
-  c->padded = pn != nstates || pm != ninputs;
+  set_dims(d, pn, pm, phorizon);
+  c->padded = pn != nstates || pm != ninputs || c->du.N != d.N;
   c->device = device;
   BufferSet& s = c->set[0];
   bool ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
@@ -436,12 +451,19 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
   HIP_TRY(sync_all(c));  // solves in flight on either slot still read the inputs
   // (eight knots per workgroup while a thread's eight loads -- the same entry of eight consecutive blocks -- stay within what
   //  the caches hold together: at (64,16) the strided reads of eight 40 KB blocks at once took 9.5 instead of 5 ms)
-  if (c->d.N % 8 == 0 && c->du.n <= 16)
+  const bool hp = c->du.N != c->d.N;  // padded horizon: the per-knot guards of the pack kernels
+  if (c->d.N % 8 == 0 && c->du.n <= 16 && hp)
+    hipLaunchKernelGGL((ndlqr::pack_flat_generic<8, true>), dim3(c->d.N / 8, c->d.batch), dim3(128), 0, s.stream, c->du, c->d, A,
+                       B, Q, R, q, r, d, x0, c->AB, c->QR, s.rhs);
+  else if (c->d.N % 8 == 0 && c->du.n <= 16)
     hipLaunchKernelGGL(ndlqr::pack_flat_generic<8>, dim3(c->d.N / 8, c->d.batch), dim3(128), 0, s.stream, c->du, c->d, A, B, Q,
                        R, q, r, d, x0, c->AB, c->QR, s.rhs);
   else if (c->du.n > 16 && sizeof(double) * (size_t)(c->du.n | 1) * c->du.w <= kLdsDefaultDynamic)  // through LDS, whole lines in and out
     hipLaunchKernelGGL(ndlqr::pack_flat_tiled, dim3(c->d.N, c->d.batch), dim3(256), sizeof(double) * (size_t)(c->du.n | 1) * c->du.w,
                        s.stream, c->du, c->d, A, B, Q, R, q, r, d, x0, c->AB, c->QR, s.rhs);
+  else if (hp)
+    hipLaunchKernelGGL((ndlqr::pack_flat_generic<1, true>), dim3(c->d.N, c->d.batch), dim3(128), 0, s.stream, c->du, c->d, A, B,
+                       Q, R, q, r, d, x0, c->AB, c->QR, s.rhs);
   else
     hipLaunchKernelGGL(ndlqr::pack_flat_generic<1>, dim3(c->d.N, c->d.batch), dim3(128), 0, s.stream, c->du, c->d, A, B, Q, R,
                        q, r, d, x0, c->AB, c->QR, s.rhs);
@@ -453,6 +475,7 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
 
 int ndlqr_hip_device_pointers(NdlqrHipCtx* c, void** out5) {
   if (!c || !out5) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_device_pointers")) return herr;
   if (c->padded)
     return refuse("no raw device pointers for a block size that runs zero-padded (the arrays have another layout): "
                   "use ndlqr_hip_pack_flat_device, or NDLQR_NO_PAD=1");
@@ -997,6 +1020,7 @@ static size_t staged_doubles(const ndlqr::Dims& u, size_t* oAB, size_t* oQR, siz
 
 int ndlqr_hip_staged_io(NdlqrHipCtx* c, double** AB, double** QR, double** rhs, double** z) {
   if (!c || !AB || !QR || !rhs || !z) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_staged_io")) return herr;
   HIP_TRY(hipSetDevice(c->device));
   size_t oAB, oQR, orhs, oz;
   const size_t total = staged_doubles(c->du, &oAB, &oQR, &orhs, &oz);
@@ -1082,11 +1106,13 @@ static const SmallInstance* time_shard_instance(NdlqrHipCtx* c, int G) {
 }
 
 int ndlqr_hip_time_shard_top_doubles(NdlqrHipCtx* c, int G) {
+  if (c && need_unpadded_horizon(c, "ndlqr_hip_time_shard_top_doubles")) return NDLQR_ERR_INVALID;
   const SmallInstance* inst = time_shard_instance(c, G);
   return inst ? (G - 1) * c->d.batch * inst->slot : NDLQR_ERR_INVALID;
 }
 
 static int time_shard_copy_slots(NdlqrHipCtx* c, int G, double* buf, bool to_buf) {
+  if (c && need_unpadded_horizon(c, to_buf ? "ndlqr_hip_time_shard_export" : "ndlqr_hip_time_shard_import")) return NDLQR_ERR_INVALID;
   const SmallInstance* inst = time_shard_instance(c, G);
   if (!inst || !buf) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
@@ -1110,6 +1136,7 @@ int ndlqr_hip_time_shard_import(NdlqrHipCtx* c, int G, const double* buf) {
 }
 
 static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
+  if (c && need_unpadded_horizon(c, phase == 0 ? "ndlqr_hip_time_shard_factor" : "ndlqr_hip_time_shard_finish")) return NDLQR_ERR_INVALID;
   if (c) c->forget_shifted();  // (the phases overwrite the records)
   const SmallInstance* inst = time_shard_instance(c, G);
   if (!inst) {
@@ -1222,8 +1249,12 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
     }
     stage += cnt[k];
   }
-  hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic, dim3(512), dim3(256), 0, st, u, d, view[0], view[1], view[2],
-                     view[3], s.rhs);
+  if (u.N != d.N)  // (a padded horizon: the per-entry guards)
+    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<true>, dim3(512), dim3(256), 0, st, u, d, view[0], view[1], view[2],
+                       view[3], s.rhs);
+  else
+    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<false>, dim3(512), dim3(256), 0, st, u, d, view[0], view[1], view[2],
+                       view[3], s.rhs);
   HIP_TRY(hipGetLastError());
   rhs_written_cur(c, written);
   // NDLQR_SOLN_ONLY: nothing but the selected knots is wanted
@@ -1265,7 +1296,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
 // Consecutive calls alternate between the buffer sets like ndlqr_hip_solve_async; complete after ndlqr_hip_synchronize.
 int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
   const KnotSlice sel = {knot0, nknots, blocks};
-  if (!c || !out || !sel.valid(c->d.N, 15u)) return NDLQR_ERR_INVALID;
+  if (!c || !out || !sel.valid(c->du.N, 15u)) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
   SolvePlan plan;
   int err = prepare_solve(c, &plan);
@@ -1313,7 +1344,7 @@ int ndlqr_hip_set_step_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   if (!c) return NDLQR_ERR_INVALID;
   if (nknots == 0) { c->sel = KnotSlice(); return NDLQR_OK; }
   const KnotSlice sel = {knot0, nknots, blocks};
-  if (!sel.valid(c->d.N, 15u)) return NDLQR_ERR_INVALID;
+  if (!sel.valid(c->du.N, 15u)) return NDLQR_ERR_INVALID;
   c->sel = sel;
   return NDLQR_OK;
 }
@@ -1321,7 +1352,7 @@ int ndlqr_hip_set_step_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
 // the same slice of the most recent solve, synchronously: out = [batch][nknots][width] doubles
 int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
   const KnotSlice sel = {knot0, nknots, blocks};
-  if (!c || !out || !sel.valid(c->d.N, 7u)) return NDLQR_ERR_INVALID;
+  if (!c || !out || !sel.valid(c->du.N, 7u)) return NDLQR_ERR_INVALID;
   BufferSet& s = c->set[c->cur];
   if (c->z_invalid || (c->z_partial && (knot0 < 8 * c->z_blk0 || knot0 + nknots > 8 * (c->z_blk0 + c->z_nblk))))
     return need_full_solution(c, "ndlqr_hip_download_selection");
@@ -2045,6 +2076,8 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
 
 int ndlqr_hip_set_box_infeasibility(NdlqrHipCtx* c, int every, double eps) {
   if (!c || every < 0 || !(eps > 0.0 && eps < HUGE_VAL)) return NDLQR_ERR_INVALID;
+  if (every > 0)  // (switching it off is always possible)
+    if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_set_box_infeasibility")) return herr;
   c->infeas.every = every;
   c->infeas.eps = eps;
   return NDLQR_OK;
@@ -2052,6 +2085,7 @@ int ndlqr_hip_set_box_infeasibility(NdlqrHipCtx* c, int every, double eps) {
 
 int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* c, double* dlam, double* dmu_x, double* dmu_u) {
   if (!c || (!dlam && !dmu_x && !dmu_u)) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_infeasibility_certificate")) return herr;
   if (c->infeas.gen == 0 || c->infeas.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
     return refuse("ndlqr_hip_download_infeasibility_certificate: the resident solution is not that of a constrained solve "
                   "with infeasibility detection on (ndlqr_hip_set_box_infeasibility before the solve)");
@@ -2077,6 +2111,7 @@ int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* c, double* dlam, d
 
 int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* c, double* measures, int* iteration) {
   if (!c || (!measures && !iteration)) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_infeasibility_measures")) return herr;
   if (c->infeas.gen == 0 || c->infeas.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
     return refuse("ndlqr_hip_download_infeasibility_measures: the resident solution is not that of a constrained solve "
                   "with infeasibility detection on (ndlqr_hip_set_box_infeasibility before the solve)");
@@ -2095,6 +2130,8 @@ int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* c, double* measures, 
 int ndlqr_hip_set_box_acceleration(NdlqrHipCtx* c, int mem, double safeguard, double reg) {
   if (!c || mem < 0 || mem > ndlqr::ACCEL_MEM_MAX || !(safeguard > 0.0 && safeguard < HUGE_VAL) || !(reg > 0.0 && reg < HUGE_VAL))
     return NDLQR_ERR_INVALID;
+  if (mem > 0)  // (switching it off is always possible)
+    if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_set_box_acceleration")) return herr;
   c->accel.mem = mem;
   c->accel.gen = 0;  // (the read-out's gamma has the width of the memory it ran with: a solve with this setting first)
   c->accel.safeguard = safeguard;
@@ -2104,6 +2141,7 @@ int ndlqr_hip_set_box_acceleration(NdlqrHipCtx* c, int mem, double safeguard, do
 
 int ndlqr_hip_download_box_acceleration(NdlqrHipCtx* c, int* accepted, int* rejected, double* gamma, int* columns) {
   if (!c || (!accepted && !rejected && !gamma && !columns)) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_box_acceleration")) return herr;
   if (c->accel.gen == 0 || c->accel.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
     return refuse("ndlqr_hip_download_box_acceleration: the resident solution is not that of a constrained solve with "
                   "acceleration on (ndlqr_hip_set_box_acceleration before the solve)");
@@ -2152,6 +2190,7 @@ int ndlqr_hip_download_box_residuals(NdlqrHipCtx* c, double* resid) {
 
 int ndlqr_hip_download_box_adjoint_residuals(NdlqrHipCtx* c, double* resid) {
   if (!c || !resid) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_box_adjoint_residuals")) return herr;
   if (c->abox.gen == 0 || c->abox.gen != c->soln_gen || !c->abox.resid)
     return refuse("ndlqr_hip_download_box_adjoint_residuals: no box adjoint of the resident solution "
                   "(ndlqr_hip_solve_box_adjoint after the latest constrained solve)");
@@ -2175,7 +2214,7 @@ int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* m
     hipLaunchKernelGGL(ndlqr::polish_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
                        (const double*)c->box.y, (const int*)c->pol.state, (const double*)c->pol.mu, out.dev[0], out.dev[1]);
   else
-    hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
+    hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(u.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
                        (const double*)c->box.y, out.dev[0], out.dev[1]);
   HIP_TRY(hipGetLastError());
   err = out.copy(s.stream, false);
@@ -2196,6 +2235,7 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
   if (!c || !g || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 ||
       check_every < 1)
     return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_solve_box_adjoint")) return herr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_box_adjoint");
   if (c->pol.soln_gen != 0 && c->pol.soln_gen == c->soln_gen)
     return refuse("ndlqr_hip_solve_box_adjoint: the resident solution was polished (ndlqr_hip_polish_box), which replaced the "
@@ -2299,6 +2339,7 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
 
 int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* gxhi, double* gulo, double* guhi) {
   if (!c) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_bound_gradients")) return herr;
   const int aerr = need_adjoint(c, "ndlqr_hip_bound_gradients");
   if (aerr) return aerr;
   const bool polished = c->pol.adj_gen != 0 && c->pol.adj_gen == c->soln_gen;  // (nu split by the polish codes, penalty 1)
@@ -2418,6 +2459,7 @@ struct RefinePhases {
 
 int ndlqr_hip_refine(NdlqrHipCtx* c, int which, int max_steps, int* steps, double* eta_before, double* eta_after) {
   if (!c || which < 0 || which > 1 || max_steps < 1 || max_steps > kRefineMaxSteps) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_refine")) return herr;
   const char* who = which ? "ndlqr_hip_refine (adjoint)" : "ndlqr_hip_refine";
   if (!c->kept.fact_valid && !c->kept.rec_complete)
     return refuse(std::string(who) + ": needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
@@ -2583,6 +2625,7 @@ static int polish_steps(NdlqrHipCtx* c, hipStream_t st, bool strict, int max_ste
 int ndlqr_hip_polish_box(NdlqrHipCtx* c, double sigma, int max_steps, int max_rounds, int* steps, int* status) {
   if (!c || !(sigma > 0.0) || !(sigma < HUGE_VAL) || max_steps < 1 || max_steps > kPolishMaxSteps || max_rounds < 0)
     return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_polish_box")) return herr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_polish_box");
   if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.have_vy || c->inputs_replaced)
     return refuse("ndlqr_hip_polish_box: the resident solution is not that of the latest constrained solve (a solve, step, "
@@ -2685,6 +2728,7 @@ int ndlqr_hip_polish_box(NdlqrHipCtx* c, double sigma, int max_steps, int max_ro
 // right-hand-side columns of the kept records are saved and restored as for the other adjoints.
 int ndlqr_hip_solve_polished_adjoint(NdlqrHipCtx* c, const double* g, int max_steps, int* steps, int* status) {
   if (!c || !g || max_steps < 1 || max_steps > kPolishMaxSteps) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_solve_polished_adjoint")) return herr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_polished_adjoint");
   if (c->pol.soln_gen == 0 || c->pol.soln_gen != c->soln_gen || !c->pol.fact || c->inputs_replaced)
     return refuse("ndlqr_hip_solve_polished_adjoint: the resident solution is not that of the latest polish, or its "
@@ -2755,6 +2799,7 @@ int ndlqr_hip_solve_polished_adjoint(NdlqrHipCtx* c, const double* g, int max_st
 // developer / test hook: the entry codes of the latest polish in the caller's block sizes, [batch][N][n+m] bytes (host)
 int ndlqr_hip_download_polish_codes(NdlqrHipCtx* c, unsigned char* codes) {
   if (!c || !codes) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_polish_codes")) return herr;
   if (c->pol.soln_gen == 0 || c->pol.soln_gen != c->soln_gen)
     return refuse("ndlqr_hip_download_polish_codes: the resident solution is not that of a polish");
   const ndlqr::Dims& d = c->d;
@@ -2785,6 +2830,7 @@ int ndlqr_hip_download_polish_codes(NdlqrHipCtx* c, unsigned char* codes) {
 static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const double* r, const double* dd, const double* x0,
                            const KnotSlice& sel, double* soln) {
   if (!c || nrhs <= 0 || !q || !r || !dd || !x0 || !soln) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, sel.nknots > 0 ? "ndlqr_hip_solve_multi_rhs_slices" : "ndlqr_hip_solve_multi_rhs")) return herr;
   if (sel.nknots > 0 && !sel.valid(c->d.N, 15u)) return NDLQR_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
@@ -2819,7 +2865,7 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
     HIP_TRY(hipMemcpyAsync(in + nq, r + s0 * per_set * u.N * u.m, sizeof(double) * nr, hipMemcpyHostToDevice, st.stream));
     HIP_TRY(hipMemcpyAsync(in + nq + nr, dd + s0 * per_set * u.N * u.n, sizeof(double) * nq, hipMemcpyHostToDevice, st.stream));
     HIP_TRY(hipMemcpyAsync(in + 2 * nq + nr, x0 + s0 * per_set * u.n, sizeof(double) * nx, hipMemcpyHostToDevice, st.stream));
-    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic, dim3(512), dim3(256), 0, st.stream, uc, dc, (const double*)in,
+    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<false>, dim3(512), dim3(256), 0, st.stream, uc, dc, (const double*)in,
                        (const double*)(in + nq), (const double*)(in + nq + nr), (const double*)(in + 2 * nq + nr), c->multi.rhs);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.ev_start, st.stream));
@@ -2920,7 +2966,7 @@ static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
   HIP_TRY(s.ensure_xfer(c->du));
-  const size_t nvars = (size_t)c->du.rows * d.N - c->du.m, pitch = (size_t)d.rows * d.N;
+  const size_t nvars = (size_t)c->du.rows * c->du.N - c->du.m, pitch = (size_t)d.rows * d.N;
   hipStream_t st = s.stream;
   HIP_TRY(launch_pack(c->du, d, KnotSlice(), zsrc + p0 * pitch, s.xfer, st, count));
   const size_t total = nvars * count;
@@ -2994,6 +3040,7 @@ int ndlqr_hip_kkt_residual(NdlqrHipCtx* c, double* res, double* bnorm) {
 
 int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
   if (!c || !z_full || p < 0 || p >= c->d.batch) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_rhs_blocks")) return herr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_download_rhs_blocks");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
@@ -3016,6 +3063,7 @@ int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
 
 int ndlqr_hip_download_factors(NdlqrHipCtx* c, int p, double* fact) {
   if (!c || !fact || p < 0 || p >= c->d.batch) return NDLQR_ERR_INVALID;
+  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_factors")) return herr;
   if (!c->kept.fact_valid) return refuse("factor download needs NDLQR_FLAG_KEEP_FACT set before the solve");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
