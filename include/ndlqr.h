@@ -393,6 +393,29 @@ int ndlqr_InitializeBatchFlat(NdLqrBatchSolver* bs, const double* A, const doubl
 int ndlqr_InitializeBatchFlatDevice(NdLqrBatchSolver* bs, const double* dA, const double* dB,
                                     const double* dQ, const double* dR, const double* dq,
                                     const double* dr, const double* dd, const double* dx0);
+/* Dense cost matrices and a state-input cross term: per knot the cost
+ *   1/2 x'Q x + x'H u + 1/2 u'R u + q'x + r'u,   Q [batch][N][n*n], R [batch][N][m*m], H [batch][N][n*m]
+ * column-major like A and B; H may be NULL (no cross term). Only the LOWER triangles of Q and R are read. Needs R_k > 0 and
+ * Q_k - H_k R_k^-1 H_k' > 0 (the dense form of Q > 0, R > 0); H, R of the last knot are not part of the problem and, like
+ * its A, B, r, d, are never read. Host or device pointers (this device's). The problem is reduced on the device to a
+ * unit-cost problem of the same shape, which the solver's kernels solve as they are; every result comes back in the
+ * caller's variables. A pivot of the reduction that is not positive is reported like one of the solver's own: the next
+ * ndlqr_SolveBatch returns NDLQR_ERR_NOT_SPD and ndlqr_BatchCholeskyFailures counts it.
+ * The solver is in dense-cost mode (ndlqr_BatchCostIsDense) until one of the diagonal initialisers above or below is
+ * called. CARRIED THROUGH in that mode: ndlqr_SolveBatch and ndlqr_SolveBatchAsync + ndlqr_BatchSynchronize in every flag
+ * mode, ndlqr_CopyBatchSolution(s)(Device), ndlqr_BatchSetRhsFlat + ndlqr_SolveBatchRhsOnly, ndlqr_SolveBatchAdjoint +
+ * ndlqr_CopyBatchAdjoint, ndlqr_BatchCholeskyFailures, ndlqr_BatchSolveTimeMs, any horizon >= 2.
+ * REFUSED (NDLQR_ERR_INVALID, ndlqr_hip_last_error() opens with the name of the function of ndlqr_hip.h behind the call):
+ * ndlqr_BatchStepAsync, ndlqr_BatchSetStepSelection (a non-empty one), ndlqr_SolveBatchSlicesAsync,
+ * ndlqr_CopyBatchSolutionSlices, ndlqr_SolveBatchMultiRhs(Slices), ndlqr_BatchGradients (rslqr_amd.autograd.lqr_solve_dense
+ * assembles the dense-cost gradients from z and w), ndlqr_RefineBatch(Adjoint), ndlqr_BatchKktResiduals,
+ * ndlqr_BatchKktResidualVector (their rows are those of the reduced system), ndlqr_BatchSetBounds and every function of the
+ * box-constrained solve, the ndlqr_BatchTimeShard* functions, ndlqr_CopyBatchFactors, and of ndlqr_hip.h
+ * ndlqr_hip_device_pointers, ndlqr_hip_staged_io / ndlqr_hip_solve_staged, ndlqr_hip_download_rhs_blocks. */
+int ndlqr_InitializeBatchFlatDense(NdLqrBatchSolver* bs, const double* A, const double* B, const double* Q,
+                                   const double* H, const double* R, const double* q, const double* r,
+                                   const double* d, const double* x0);
+int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs); /* 1: dense-cost mode, 0: not */
 /* Seeded synthetic problems, problem p seeded with seed0 + p; generated on the
  * host, packed and uploaded. */
 int ndlqr_InitializeBatchSynthetic(NdLqrBatchSolver* bs, uint64_t seed0);

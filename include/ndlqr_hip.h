@@ -66,6 +66,40 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* ctx, int p0, int count, const double* A
 int ndlqr_hip_pack_flat_device(NdlqrHipCtx* ctx, const double* A, const double* B, const double* Q,
                                const double* R, const double* q, const double* r, const double* d,
                                const double* x0);
+/* Dense cost matrices and state-input cross terms (ndlqr.h: ndlqr_InitializeBatchFlatDense). The
+ * dense-cost problem -- Q [batch][N][n*n], R [batch][N][m*m], H [batch][N][n*m] (may be NULL: zero), column-major like A and
+ * B, of which only the LOWER triangles of Q and R are read; the other arrays as for ndlqr_hip_pack_flat_device -- is reduced
+ * on the device to a unit-cost problem of the same shape (kernels_cost.hpp), which goes through ndlqr_hip_pack_flat_device
+ * like a caller's. Every array: host, pinned or this device's memory. A, B, H, R, r, d of the last knot are never loaded.
+ * The context is in dense-cost mode from then on, until ndlqr_hip_upload_inputs or ndlqr_hip_pack_flat_device is called.
+ * A pivot that is not positive in R_k or in Q_k - H_k R_k^-1 H_k' counts like one of the solver's own Cholesky: the next
+ * synchronisation reports it (ndlqr_hip_cholesky_failures). Block sizes whose working set per knot in cost_transform
+ * -- 3 n^2 + 2 n m + m^2 doubles and the padding -- exceeds the LDS of a workgroup are refused by name.
+ * CARRIED THROUGH in dense-cost mode, every result in the caller's variables: ndlqr_hip_solve_async /
+ * ndlqr_hip_synchronize in every flag mode, ndlqr_hip_download_solutions, ndlqr_hip_pack_solutions_device,
+ * ndlqr_hip_set_rhs_dense + ndlqr_hip_solve_rhs_async, ndlqr_hip_solve_adjoint + ndlqr_hip_download_adjoint,
+ * ndlqr_hip_cholesky_failures, ndlqr_hip_last_solve_ms, any horizon >= 2.
+ * REFUSED in dense-cost mode (NDLQR_ERR_INVALID; ndlqr_hip_last_error() opens with the function's name): ndlqr_hip_step_async,
+ * ndlqr_hip_solve_slices_async, ndlqr_hip_set_step_selection (a non-empty one), ndlqr_hip_download_selection,
+ * ndlqr_hip_solve_multi_rhs(_slices), ndlqr_hip_gradients, ndlqr_hip_refine, ndlqr_hip_kkt_residual,
+ * ndlqr_hip_kkt_residual_vector (their rows are those of the reduced system), ndlqr_hip_set_bounds and everything on the box
+ * solve (ndlqr_hip_solve_box(_ex), ndlqr_hip_solve_box_adjoint, ndlqr_hip_bound_gradients, ndlqr_hip_polish_box,
+ * ndlqr_hip_solve_polished_adjoint, ndlqr_hip_set_box_infeasibility / ndlqr_hip_set_box_acceleration when switching on, and
+ * the box downloads), the ndlqr_hip_time_shard_* functions, ndlqr_hip_download_factors, ndlqr_hip_download_rhs_blocks,
+ * ndlqr_hip_device_pointers, ndlqr_hip_staged_io and ndlqr_hip_solve_staged.
+ * ndlqr_hip_set_rhs_dense: a new flat right-hand side q, r, d, x0 in the caller's variables (same memories).
+ * ndlqr_hip_download_cost_reduction (read-out for the tests): the records L [batch][N][n*n], LR [batch][N][m*m], G
+ * [batch][N][m*n] (column-major; the triangles with zeros above; LR = 1, G = 0 at the last knot) and the reduced problem in
+ * the flat layout, At, Bt, qt, rt, dt [batch][N][..], x0t [batch][n], into HOST memory; any pointer may be NULL. */
+int ndlqr_hip_init_dense(NdlqrHipCtx* ctx, const double* A, const double* B, const double* Q, const double* H,
+                         const double* R, const double* q, const double* r, const double* d, const double* x0);
+int ndlqr_hip_cost_is_dense(const NdlqrHipCtx* ctx);
+/* Under NDLQR_FLAG_PROFILE: device time (HIP events, ms) of the latest cost_factor + cost_transform | cost_apply_t (S') |
+ * cost_apply (S), 3 doubles; a profiled call waits for its kernels. Without the flag nothing is recorded. */
+int ndlqr_hip_cost_phase_ms(NdlqrHipCtx* ctx, double* out3);
+int ndlqr_hip_set_rhs_dense(NdlqrHipCtx* ctx, const double* q, const double* r, const double* d, const double* x0);
+int ndlqr_hip_download_cost_reduction(NdlqrHipCtx* ctx, double* L, double* LR, double* G, double* At, double* Bt,
+                                      double* qt, double* rt, double* dt, double* x0t);
 /* Device pointers for zero-copy producers (order: AB, QR, rhs, F, z). Allocates the factor array and
  * sets the pipeline depth to 1, so that z is THE solution buffer from then on. */
 int ndlqr_hip_device_pointers(NdlqrHipCtx* ctx, void** out5);

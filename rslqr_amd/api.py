@@ -243,6 +243,10 @@ def lib():
     proto("ndlqr_InitializeBatch", ci, vp, C.POINTER(pp), ci)
     proto("ndlqr_InitializeBatchFlat", ci, vp, dp, dp, dp, dp, dp, dp, dp, dp)
     proto("ndlqr_InitializeBatchSynthetic", ci, vp, cu64)
+    proto("ndlqr_InitializeBatchFlatDense", ci, vp, dp, dp, dp, dp, dp, dp, dp, dp, dp)
+    proto("ndlqr_BatchCostIsDense", ci, vp)
+    proto("ndlqr_hip_download_cost_reduction", ci, vp, dp, dp, dp, dp, dp, dp, dp, dp, dp)
+    proto("ndlqr_hip_cost_phase_ms", ci, vp, dp)
     proto("ndlqr_InitializeBatchFlatDevice", ci, vp, vp, vp, vp, vp, vp, vp, vp, vp)
     proto("ndlqr_SolveBatch", ci, vp)
     proto("ndlqr_BatchSetRhsFlat", ci, vp, dp, dp, dp, dp)
@@ -448,6 +452,57 @@ class BatchSolver:
         err = self.L.ndlqr_InitializeBatchFlatDevice(self.h, *[C.c_void_p(int(p)) for p in device_ptrs])
         if err:
             raise RuntimeError("ndlqr_InitializeBatchFlatDevice failed: %d" % err)
+
+    def initialize_flat_dense(self, A, B, Q, H, R, q, r, d, x0):
+        """ndlqr_InitializeBatchFlatDense: dense cost matrices Q [batch, N, n*n], R [batch, N, m*m] and the state-input
+        cross term H [batch, N, n*m] (None: no cross term), column-major per knot like A and B; only the lower triangles of
+        Q and R are read. The other arrays as for initialize_flat. Each array is a numpy array or device memory (anything
+        with `ptr` and `size`, such as a DeviceArray). The solver is in dense-cost mode afterwards (cost_is_dense()): solve,
+        solutions, set_rhs_flat + solve_rhs_only, solve_adjoint + adjoint work in the caller's variables; what has no
+        dense-cost form refuses (include/ndlqr.h has the list)."""
+        n, m, N, bt = self.n, self.m, self.N, self.batch
+        sizes = dict(A=bt * N * n * n, B=bt * N * n * m, Q=bt * N * n * n, H=bt * N * n * m, R=bt * N * m * m,
+                     q=bt * N * n, r=bt * N * m, d=bt * N * n, x0=bt * n)
+        ptrs, keep = [], []
+        for name, a in zip(("A", "B", "Q", "H", "R", "q", "r", "d", "x0"), (A, B, Q, H, R, q, r, d, x0)):
+            if a is None:
+                if name != "H":
+                    raise ValueError("%s is missing (only H may be None)" % name)
+                ptrs.append(None)
+                continue
+            if not hasattr(a, "ptr"):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != sizes[name]:
+                    raise ValueError("bad size for %s" % name)
+                keep.append(a)
+            ptrs.append(_any_ptr(a, sizes[name]))
+        err = self.L.ndlqr_InitializeBatchFlatDense(self.h, *ptrs)
+        if err:
+            raise RuntimeError("ndlqr_InitializeBatchFlatDense failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+
+    def cost_is_dense(self):
+        """ndlqr_BatchCostIsDense: True between initialize_flat_dense and the next diagonal initialiser."""
+        return bool(self.L.ndlqr_BatchCostIsDense(self.h))
+
+    def cost_phase_ms(self):
+        """(factor + transform, S', S): device times in ms of the latest launches of the reduction's kernels under FLAG_PROFILE."""
+        out = np.zeros(3)
+        self.L.ndlqr_hip_cost_phase_ms(self.ctx, _ptr(out))
+        return tuple(out)
+
+    def cost_reduction(self):
+        """ndlqr_hip_download_cost_reduction (read-out for the tests): dict of numpy arrays -- the records L [batch, N, n*n],
+        LR [batch, N, m*m], G [batch, N, m*n] (column-major per knot) and the reduced unit-cost problem At, Bt, qt, rt, dt,
+        x0t in the flat layout of initialize_flat. Raises outside dense-cost mode."""
+        n, m, N, bt = self.n, self.m, self.N, self.batch
+        out = dict(L=np.zeros((bt, N, n * n)), LR=np.zeros((bt, N, m * m)), G=np.zeros((bt, N, m * n)),
+                   At=np.zeros((bt, N, n * n)), Bt=np.zeros((bt, N, n * m)), qt=np.zeros((bt, N, n)), rt=np.zeros((bt, N, m)),
+                   dt=np.zeros((bt, N, n)), x0t=np.zeros((bt, n)))
+        err = self.L.ndlqr_hip_download_cost_reduction(self.ctx, *[_ptr(out[k]) for k in
+                                                                   ("L", "LR", "G", "At", "Bt", "qt", "rt", "dt", "x0t")])
+        if err:
+            raise RuntimeError("ndlqr_hip_download_cost_reduction failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
 
     def initialize_synthetic(self, seed0):
         err = self.L.ndlqr_InitializeBatchSynthetic(self.h, seed0)

@@ -14,6 +14,9 @@ Streams: the library runs on streams of its own. Before it reads torch memory, t
 every call into the library returns only after its writes are complete. That is the whole contract: the tensors this
 module returns may be used on any stream at once.
 
+``lqr_solve_dense`` takes dense cost matrices Q, R and a state-input cross term H (ndlqr_InitializeBatchFlatDense); its
+backward is one adjoint solve, the gradients are assembled in torch from z and w.
+
 ``lqr_solve_box`` adds bounds on x and u (ndlqr_SolveBatchBoxConstrained); its backward is the adjoint of the
 active-set system (ndlqr_SolveBatchBoxAdjoint) plus the gradients with respect to the bounds (ndlqr_BatchBoundGradients).
 
@@ -383,3 +386,120 @@ def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=Non
 
 
 __all__ = ["LqrSolve", "LqrSolveRefined", "LqrSolveBox", "lqr_solve", "lqr_solve_box", "split_solution"]
+
+
+# ------------------------------------------------------------------------------------------------ dense cost matrices
+# A cache of its own again: a solver in dense-cost mode serves no diagonal forward in between.
+_DENSE_ARGS = ("A", "B", "Q", "H", "R", "q", "r", "d", "x0")
+_dense_cache = {}            # (n, m, N, b, device index) -> [BatchSolver, token of the forward it holds]
+
+
+def _dense_solve(bs, flat, token, key):
+    torch.cuda.current_stream(flat[0].device).synchronize()  # (the library reads torch memory on its own stream)
+    bs.initialize_flat_dense(*[_View(t) for t in flat])
+    err = bs.solve()
+    if err or bs.cholesky_failures() > 0:
+        _dense_cache[key][1] = None
+        raise RuntimeError("lqr_solve_dense: the factorisation failed (%d non-positive pivots): R or Q - H R^-1 H' are not "
+                           "positive definite" % max(bs.cholesky_failures(), 1))
+    _dense_cache[key][1] = token
+
+
+class LqrSolveDense(torch.autograd.Function):
+    """Forward: ndlqr_InitializeBatchFlatDense + solve with NDLQR_FLAG_KEEP_RECORDS. Backward: one adjoint solve
+    (ndlqr_SolveBatchAdjoint); the nine gradients are outer products per knot of z and w, both in the caller's variables,
+    assembled here in torch with the signs and per-knot conventions of kernels_grad.hpp (zero for A, B, H, R, r, d of the
+    last knot). The C-level ndlqr_BatchGradients has no dense-cost form and stays refused."""
+
+    @staticmethod
+    def forward(ctx, A, B, Q, H, R, q, r, d, x0):
+        b, N, n, m = B.shape
+        dev = A.device
+        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
+        if key not in _dense_cache:
+            _dense_cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
+        bs = _dense_cache[key][0]
+        # the flat layout: matrices column-major per knot (the transpose, stored row-major)
+        flat = [(t.detach().transpose(-1, -2) if t.dim() == 4 else t.detach()).contiguous().reshape(b, -1)
+                for t in (A, B, Q, H, R, q, r, d, x0)]
+        token = next(_tokens)
+        _dense_solve(bs, flat, token, key)
+        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
+        bs.solutions_to_device(z.data_ptr())
+        bs.synchronize()
+        ctx.key, ctx.token, ctx.flat, ctx.dims = key, token, flat, (n, m, N, b)
+        ctx.save_for_backward(z)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        n, m, N, b = ctx.dims
+        (z,) = ctx.saved_tensors
+        bs = _dense_cache[ctx.key][0]
+        if _dense_cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's again
+            _dense_solve(bs, ctx.flat, ctx.token, ctx.key)
+        gz = gz.detach().to(torch.float64).contiguous()
+        torch.cuda.current_stream(gz.device).synchronize()
+        err = bs.solve_adjoint(_View(gz))
+        if err:
+            raise RuntimeError("lqr_solve_dense backward: adjoint solve failed: %d" % err)
+        w = torch.empty_like(z)
+        bs.adjoint(_View(w))
+        zl, zx, zu = split_solution(z, n, m, N)
+        wl, wx, wu = split_solution(w, n, m, N)
+        outer = lambda a, c: a.unsqueeze(-1) * c.unsqueeze(-2)
+        pad = lambda t: torch.nn.functional.pad(t, (0, 0) * (t.dim() - 2) + (0, 1))  # a zero last knot
+        zx1, wx1 = zx[:, :N - 1], wx[:, :N - 1]
+        gA = pad(-(outer(wl[:, 1:], zx1) + outer(zl[:, 1:], wx1)))
+        gB = pad(-(outer(wl[:, 1:], zu) + outer(zl[:, 1:], wu)))
+        gQ = -0.5 * (outer(wx, zx) + outer(zx, wx))
+        gH = pad(-(outer(wx1, zu) + outer(zx1, wu)))
+        gR = pad(-0.5 * (outer(wu, zu) + outer(zu, wu)))
+        gq = -wx
+        gr = pad(-wu)
+        gd = pad(-wl[:, 1:])
+        gx0 = -wl[:, 0]
+        grads = (gA, gB, gQ, gH, gR, gq, gr, gd, gx0)
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
+
+
+def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
+    """z [b, nvars] of LQR problems with dense cost matrices and a state-input cross term, differentiable in every argument:
+        A [b, N, n, n]   B [b, N, n, m]   Q [b, N, n, n]   H [b, N, n, m]   R [b, N, m, m]   q, d [b, N, n]   r [b, N, m]   x0 [b, n]
+    in the row-major math convention; per knot the cost is 1/2 x'Q x + x'H u + 1/2 u'R u + q'x + r'u. Any argument may leave
+    out the batch dimension (shared: its gradient is the batch sum). Q and R are read as symmetric matrices through their
+    lower triangles, and dL/dQ, dL/dR come back symmetric: the gradient in the space of symmetric matrices. Needs R_k > 0
+    and Q_k - H_k R_k^-1 H_k' > 0. H, R of the last knot are not part of the problem (zero gradient), like its A, B, r, d."""
+    args = (A, B, Q, H, R, q, r, d, x0)
+    dev = None
+    for name, t in zip(_DENSE_ARGS, args):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("lqr_solve_dense: %s must be a torch.Tensor" % name)
+        if t.dtype != torch.float64:
+            raise TypeError("lqr_solve_dense: %s must be float64, got %s" % (name, t.dtype))
+        if t.device.type != "cuda":
+            raise ValueError("lqr_solve_dense: %s must live on a ROCm device, got %s" % (name, t.device))
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            raise ValueError("lqr_solve_dense: every argument must be on one device (%s is on %s, A on %s)" % (name, t.device, dev))
+    if A.dim() not in (3, 4) or A.shape[-1] != A.shape[-2] or B.dim() not in (3, 4) or B.shape[-3:-1] != A.shape[-3:-1]:
+        raise ValueError("lqr_solve_dense: A must be [b, N, n, n] and B [b, N, n, m] (b optional), got %s and %s"
+                         % (tuple(A.shape), tuple(B.shape)))
+    N, n, m = B.shape[-3:]
+    per = dict(A=(N, n, n), B=(N, n, m), Q=(N, n, n), H=(N, n, m), R=(N, m, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,))
+    batch = set()
+    for name, t in zip(_DENSE_ARGS, args):
+        if tuple(t.shape) == per[name]:
+            continue
+        if t.dim() == len(per[name]) + 1 and tuple(t.shape[1:]) == per[name]:
+            batch.add(t.shape[0])
+        else:
+            raise ValueError("lqr_solve_dense: %s must be [b, %s] or %s, got %s"
+                             % (name, ", ".join(str(x) for x in per[name]), list(per[name]), tuple(t.shape)))
+    if len(batch) > 1:
+        raise ValueError("lqr_solve_dense: batch dimensions disagree: %s" % sorted(batch))
+    b = batch.pop() if batch else 1
+    # (a shared argument is expanded here, outside the Function: autograd sums its gradient over the batch)
+    full = [t if t.dim() == len(per[name]) + 1 else t.unsqueeze(0).expand(b, *t.shape) for name, t in zip(_DENSE_ARGS, args)]
+    return LqrSolveDense.apply(*full)

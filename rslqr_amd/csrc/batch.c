@@ -177,6 +177,14 @@ int ndlqr_InitializeBatchFlatDevice(NdLqrBatchSolver* bs, const double* dA, cons
   return ndlqr_hip_pack_flat_device(bs->ctx, dA, dB, dQ, dR, dq, dr, dd, dx0);
 }
 
+int ndlqr_InitializeBatchFlatDense(NdLqrBatchSolver* bs, const double* A, const double* B, const double* Q,
+                                   const double* H, const double* R, const double* q, const double* r,
+                                   const double* d, const double* x0) {
+  if (!bs) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_init_dense(bs->ctx, A, B, Q, H, R, q, r, d, x0);
+}
+int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs) { return bs ? ndlqr_hip_cost_is_dense(bs->ctx) : 0; }
+
 /* Synthetic problems of one staging chunk are generated and packed side by side on host threads
  * (one splitmix64 stream per problem, so the result does not depend on the thread count): the
  * (64,16,512) x 256 family is 37 s of Box-Muller draws on one core. */
@@ -248,6 +256,7 @@ int ndlqr_InitializeBatchSynthetic(NdLqrBatchSolver* bs, uint64_t seed0) {
 int ndlqr_BatchSetRhsFlat(NdLqrBatchSolver* bs, const double* q, const double* r, const double* d,
                           const double* x0) {
   if (!bs || !q || !r || !d || !x0) return NDLQR_ERR_INVALID;
+  if (ndlqr_hip_cost_is_dense(bs->ctx)) return ndlqr_hip_set_rhs_dense(bs->ctx, q, r, d, x0); /* (through S' on the device) */
   const size_t n = (size_t)bs->n, m = (size_t)bs->m, N = (size_t)bs->N;
   int slot = 0, p0 = 0;
   for (int p = 0; p < bs->batch; ++p) {

@@ -380,6 +380,25 @@ struct MultiRhsState {
   }
 };
 
+// Dense cost matrices by reduction to a unit-cost problem (ndlqr_hip_init_dense, kernels_cost.hpp; DESIGN.md section
+// 3.16). dense: the resident problem is the reduction of a dense-cost one -- the mode every diagonal initialiser leaves.
+// All in the CALLER's block sizes and horizon (u): rec [batch][N][n^2 + m^2 + m n], the records L | L_R | G of every knot,
+// resident while the mode lasts; the reduced problem in the flat layout the pack kernels read -- At [batch][N][n^2], Bt
+// [batch][N][n m], qt, dt [batch][N][n], rt [batch][N][m], x0t [batch][n] and ones [batch][N][n+m] (Q~ | R~ = 1); stage
+// [batch][nvars], the packed vector S' goes through on its way into the adjoint solve.
+struct CostState {
+  bool dense = false;
+  DevBuf<double> rec, At, Bt, qt, rt, dt, x0t, ones, stage;
+  double phase_ms[3] = {};  // under NDLQR_FLAG_PROFILE: device time of the latest cost_factor + cost_transform | cost_apply_t | cost_apply
+  static size_t record_doubles(const ndlqr::Dims& u) { return (size_t)u.n * u.n + (size_t)u.m * u.m + (size_t)u.m * u.n; }
+  hipError_t ensure(const ndlqr::Dims& u) {
+    const size_t kn = (size_t)u.batch * u.N;
+    return first_error({rec.ensure(kn * record_doubles(u)), At.ensure(kn * u.n * u.n), Bt.ensure(kn * u.n * u.m),
+                        qt.ensure(kn * u.n), rt.ensure(kn * u.m), dt.ensure(kn * u.n), x0t.ensure((size_t)u.batch * u.n),
+                        ones.ensure(kn * u.w), stage.ensure((size_t)u.batch * ((size_t)u.rows * u.N - u.m))});
+  }
+};
+
 struct NdlqrHipCtx {
   ndlqr::Dims d = {};   // block sizes of the DEVICE layout (every kernel works on these)
   ndlqr::Dims du = {};  // the caller's block sizes and horizon: the same, or smaller when the problem runs zero-padded into
@@ -444,6 +463,7 @@ struct NdlqrHipCtx {
   RefineState ref;
   PolishState pol;
   MultiRhsState multi;
+  CostState cost;
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // the remembered shifted factorisations (ADMM's and the polish's) no longer match the records / factors
   void forget_shifted() { box.fact = pol.fact = false; }

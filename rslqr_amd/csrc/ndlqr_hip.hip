@@ -15,6 +15,7 @@
 #include "kernels_box_accel.hpp"
 #include "kernels_box_infeas.hpp"
 #include "kernels_box_polish.hpp"
+#include "kernels_cost.hpp"
 #include "kernels_grad.hpp"
 #include "kernels_refine.hpp"
 #include "kernels_mfma.hpp"
@@ -49,6 +50,58 @@ static int need_unpadded_horizon(const NdlqrHipCtx* c, const char* who) {
   if (c->du.N == c->d.N) return NDLQR_OK;
   return refuse(std::string(who) + ": not available for a padded horizon (horizon " + std::to_string(c->du.N) +
                 " runs as " + std::to_string(c->d.N) + " knots); use a power-of-two horizon");
+}
+
+// Dense-cost mode (ndlqr_hip_init_dense): the resident problem is the unit-cost reduction of the
+// caller's. An entry point that is not carried through refuses here -- the rows, records and arrays it would work on are
+// those of the reduced system
+static int need_diagonal_cost(const NdlqrHipCtx* c, const char* who) {
+  if (!c->cost.dense) return NDLQR_OK;
+  return refuse(std::string(who) + ": not available in dense-cost mode (the resident problem is the unit-cost reduction "
+                "ndlqr_InitializeBatchFlatDense left); use a diagonal initialiser");
+}
+
+// one launch of a kernel of kernels_cost.hpp: a wavefront per (knot, problem) of `count` problems
+template <class... Params, class... Args>
+static hipError_t launch_cost(void (*kernel)(Params...), size_t lds_doubles, const ndlqr::Dims& u, unsigned count, hipStream_t st,
+                              Args... args) {
+  const size_t lds = sizeof(double) * lds_doubles;
+  const hipError_t e = allow_dynamic_lds(kernel, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(u.N, count), dim3(64), lds, st, static_cast<Params>(args)...);
+  return hipGetLastError();
+}
+// Under NDLQR_FLAG_PROFILE: HIP events around the launches of one phase of the reduction (CostState::phase_ms[which]);
+// stop() waits for them, so a profiled call is synchronous. Without the flag nothing is recorded.
+struct CostPhase {
+  NdlqrHipCtx* c;
+  hipStream_t st;
+  int which;
+  hipEvent_t a = nullptr, b = nullptr;
+  CostPhase(NdlqrHipCtx* ctx, hipStream_t stream, int phase) : c(ctx), st(stream), which(phase) {
+    if (!(c->flags & NDLQR_FLAG_PROFILE)) return;
+    a = take_event(c); b = take_event(c);
+    (void)hipEventRecord(a, st);
+  }
+  void stop() {
+    if (!a) return;
+    float ms = 0.0f;
+    if (hipEventRecord(b, st) == hipSuccess && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess)
+      c->cost.phase_ms[which] = ms;
+    c->event_pool.push_back(a);
+    c->event_pool.push_back(b);
+    a = b = nullptr;
+  }
+};
+// dense-cost mode: `vec`, the packed [count][nvars] vectors of problems [p0, p0 + count) in the reduced variables, becomes
+// the same in the caller's (S, in place)
+static hipError_t cost_map_back(NdlqrHipCtx* c, double* vec, int p0, unsigned count, hipStream_t st) {
+  const ndlqr::Dims& u = c->du;
+  CostPhase phase(c, st, 2);
+  const hipError_t e = launch_cost(ndlqr::cost_apply, ndlqr::cost_apply_lds(u.n, u.m), u, count, st, u.n, u.m, u.N,
+                                   c->cost.rec + (size_t)p0 * u.N * CostState::record_doubles(u), vec);
+  phase.stop();
+  return e;
 }
 
 // Where a caller's array lives. A pointer the runtime does not know (an ordinary malloc'ed one is "invalid value" to older
@@ -439,6 +492,7 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
   }
   HIP_TRY(hipStreamSynchronize(s.stream));  // the host staging buffers are reused by the caller
   note_new_inputs(c);
+  c->cost.dense = false;
   return NDLQR_OK;
 }
 
@@ -469,6 +523,7 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
                        q, r, d, x0, c->AB, c->QR, s.rhs);
   HIP_TRY(hipGetLastError());
   note_new_inputs(c);              // (the whole batch: nothing of the older copies is needed any more)
+  c->cost.dense = false;           // (ndlqr_hip_init_dense, which gets here with the reduced arrays, sets it again)
   HIP_TRY(other_stream_waits(c));  // the next solve may run on the other buffer set's stream
   return NDLQR_OK;
 }
@@ -476,6 +531,7 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
 int ndlqr_hip_device_pointers(NdlqrHipCtx* c, void** out5) {
   if (!c || !out5) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_device_pointers")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_device_pointers")) return cerr;
   if (c->padded)
     return refuse("no raw device pointers for a block size that runs zero-padded (the arrays have another layout): "
                   "use ndlqr_hip_pack_flat_device, or NDLQR_NO_PAD=1");
@@ -1021,6 +1077,7 @@ static size_t staged_doubles(const ndlqr::Dims& u, size_t* oAB, size_t* oQR, siz
 int ndlqr_hip_staged_io(NdlqrHipCtx* c, double** AB, double** QR, double** rhs, double** z) {
   if (!c || !AB || !QR || !rhs || !z) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_staged_io")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_staged_io")) return cerr;
   HIP_TRY(hipSetDevice(c->device));
   size_t oAB, oQR, orhs, oz;
   const size_t total = staged_doubles(c->du, &oAB, &oQR, &orhs, &oz);
@@ -1071,6 +1128,7 @@ static int enqueue_staged(NdlqrHipCtx* c, const SolvePlan& plan) {
 
 int ndlqr_hip_solve_staged(NdlqrHipCtx* c) {
   if (!c || !c->h_io) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_staged")) return cerr;
   if (c->pipeline != 1) {
     const int perr = ndlqr_hip_set_pipeline_depth(c, 1);
     if (perr) return perr;
@@ -1107,12 +1165,14 @@ static const SmallInstance* time_shard_instance(NdlqrHipCtx* c, int G) {
 
 int ndlqr_hip_time_shard_top_doubles(NdlqrHipCtx* c, int G) {
   if (c && need_unpadded_horizon(c, "ndlqr_hip_time_shard_top_doubles")) return NDLQR_ERR_INVALID;
+  if (c && need_diagonal_cost(c, "ndlqr_hip_time_shard_top_doubles")) return NDLQR_ERR_INVALID;
   const SmallInstance* inst = time_shard_instance(c, G);
   return inst ? (G - 1) * c->d.batch * inst->slot : NDLQR_ERR_INVALID;
 }
 
 static int time_shard_copy_slots(NdlqrHipCtx* c, int G, double* buf, bool to_buf) {
   if (c && need_unpadded_horizon(c, to_buf ? "ndlqr_hip_time_shard_export" : "ndlqr_hip_time_shard_import")) return NDLQR_ERR_INVALID;
+  if (c && need_diagonal_cost(c, to_buf ? "ndlqr_hip_time_shard_export" : "ndlqr_hip_time_shard_import")) return NDLQR_ERR_INVALID;
   const SmallInstance* inst = time_shard_instance(c, G);
   if (!inst || !buf) return NDLQR_ERR_INVALID;
   const ndlqr::Dims& d = c->d;
@@ -1137,6 +1197,7 @@ int ndlqr_hip_time_shard_import(NdlqrHipCtx* c, int G, const double* buf) {
 
 static int time_shard_phase(NdlqrHipCtx* c, int phase, int g, int G) {
   if (c && need_unpadded_horizon(c, phase == 0 ? "ndlqr_hip_time_shard_factor" : "ndlqr_hip_time_shard_finish")) return NDLQR_ERR_INVALID;
+  if (c && need_diagonal_cost(c, phase == 0 ? "ndlqr_hip_time_shard_factor" : "ndlqr_hip_time_shard_finish")) return NDLQR_ERR_INVALID;
   if (c) c->forget_shifted();  // (the phases overwrite the records)
   const SmallInstance* inst = time_shard_instance(c, G);
   if (!inst) {
@@ -1213,6 +1274,7 @@ static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z)
 int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const double* dd, const double* x0,
                          double* soln) {
   if (!c || !x0 || !soln) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_step_async")) return cerr;
   const ndlqr::Dims& d = c->d;
   SolvePlan plan;
   int err = prepare_solve(c, &plan);
@@ -1297,6 +1359,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
 int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
   const KnotSlice sel = {knot0, nknots, blocks};
   if (!c || !out || !sel.valid(c->du.N, 15u)) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_slices_async")) return cerr;
   const ndlqr::Dims& d = c->d;
   SolvePlan plan;
   int err = prepare_solve(c, &plan);
@@ -1343,6 +1406,7 @@ int ndlqr_hip_synchronize_previous(NdlqrHipCtx* c) {
 int ndlqr_hip_set_step_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks) {
   if (!c) return NDLQR_ERR_INVALID;
   if (nknots == 0) { c->sel = KnotSlice(); return NDLQR_OK; }
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_set_step_selection")) return cerr;
   const KnotSlice sel = {knot0, nknots, blocks};
   if (!sel.valid(c->du.N, 15u)) return NDLQR_ERR_INVALID;
   c->sel = sel;
@@ -1353,6 +1417,7 @@ int ndlqr_hip_set_step_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
 int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
   const KnotSlice sel = {knot0, nknots, blocks};
   if (!c || !out || !sel.valid(c->du.N, 7u)) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_selection")) return cerr;
   BufferSet& s = c->set[c->cur];
   if (c->z_invalid || (c->z_partial && (knot0 < 8 * c->z_blk0 || knot0 + nknots > 8 * (c->z_blk0 + c->z_nblk))))
     return need_full_solution(c, "ndlqr_hip_download_selection");
@@ -1545,6 +1610,136 @@ struct CallerArrays {
   }
 };
 
+// ------------------------------------------------------------------------------ dense cost matrices
+// Layered ABOVE the plain entry points: the dense-cost problem is reduced on the device to a unit-cost problem of the same
+// shape (kernels_cost.hpp), whose flat arrays -- device-resident, in the caller's layout -- go to ndlqr_hip_pack_flat_device
+// and the right-hand-side pack kernel like any caller's. The solve kernels, their schedules and captured graphs never
+// learn of it; solutions and adjoints are mapped back where they are packed for the caller (cost_map_back).
+
+// S' of the flat right-hand side at q, r, d, x0 (device) into the reduced flat arrays, on `st`
+static hipError_t cost_reduce_rhs(NdlqrHipCtx* c, const double* q, const double* r, const double* d, const double* x0,
+                                  hipStream_t st) {
+  const ndlqr::Dims& u = c->du;
+  CostState& k = c->cost;
+  CostPhase phase(c, st, 1);
+  const hipError_t e = launch_cost(ndlqr::cost_apply_t, ndlqr::cost_apply_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N,
+                                   k.rec.get(), q, r, d, x0, nullptr, k.qt.get(), k.rt.get(), k.dt.get(), k.x0t.get(), nullptr);
+  phase.stop();
+  return e;
+}
+
+int ndlqr_hip_init_dense(NdlqrHipCtx* c, const double* A, const double* B, const double* Q, const double* H, const double* R,
+                         const double* q, const double* r, const double* d, const double* x0) {
+  if (!c || !A || !B || !Q || !R || !q || !r || !d || !x0) return NDLQR_ERR_INVALID;
+  const ndlqr::Dims& u = c->du;
+  const size_t lds = sizeof(double) * ndlqr::cost_transform_lds(u.n, u.m);
+  if (lds > kLdsMax)
+    return refuse("ndlqr_hip_init_dense: cost_transform stages " + std::to_string(lds) + " bytes per knot at (" +
+                  std::to_string(u.n) + "," + std::to_string(u.m) + "), beyond the " + std::to_string(kLdsMax) +
+                  " bytes of LDS of a workgroup");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t kn = (size_t)u.batch * u.N, n = (size_t)u.n, m = (size_t)u.m;
+  CallerArrays<9> ca = {{const_cast<double*>(A), const_cast<double*>(B), const_cast<double*>(Q), const_cast<double*>(H),
+                         const_cast<double*>(R), const_cast<double*>(q), const_cast<double*>(r), const_cast<double*>(d),
+                         const_cast<double*>(x0)},
+                        {kn * n * n, kn * n * m, kn * n * n, kn * n * m, kn * m * m, kn * n, kn * m, kn * n, (size_t)u.batch * n}};
+  int err = ca.classify(c, "ndlqr_hip_init_dense", "an input lies");
+  if (err) return err;
+  HIP_TRY(sync_all(c));  // solves in flight still read the inputs (and the staging)
+  CostState& k = c->cost;
+  const bool fresh = !k.ones;
+  HIP_TRY(k.ensure(u));
+  HIP_TRY(c->grad_stage.grow(ca.stage));
+  ca.place(c);
+  const hipStream_t st = c->set[c->cur].stream;
+  err = ca.copy(st, true);
+  if (err) return err;
+  if (fresh) {
+    hipLaunchKernelGGL(ndlqr::cost_fill, dim3(256), dim3(256), 0, st, k.ones.get(), kn * (n + m), 1.0);
+    HIP_TRY(hipGetLastError());
+  }
+  {
+    CostPhase phase(c, st, 0);
+    HIP_TRY(launch_cost(ndlqr::cost_factor, ndlqr::cost_factor_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, u.batch, ca.dev[2],
+                        ca.dev[3], ca.dev[4], k.rec.get(), c->info.get()));
+    HIP_TRY(launch_cost(ndlqr::cost_transform, ndlqr::cost_transform_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, ca.dev[0],
+                        ca.dev[1], k.rec.get(), k.At.get(), k.Bt.get()));
+    phase.stop();
+  }
+  HIP_TRY(cost_reduce_rhs(c, ca.dev[5], ca.dev[6], ca.dev[7], ca.dev[8], st));
+  // (waits for the stream first: the caller's arrays and the staging are free again when this returns)
+  err = ndlqr_hip_pack_flat_device(c, k.At, k.Bt, k.ones, k.ones + kn * n, k.qt, k.rt, k.dt, k.x0t);
+  if (err) return err;
+  k.dense = true;
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_cost_is_dense(const NdlqrHipCtx* c) { return c && c->cost.dense ? 1 : 0; }
+int ndlqr_hip_cost_phase_ms(NdlqrHipCtx* c, double* out3) {
+  if (!c || !out3) return NDLQR_ERR_INVALID;
+  for (int i = 0; i < 3; ++i) out3[i] = c->cost.phase_ms[i];
+  return NDLQR_OK;
+}
+
+// ndlqr_BatchSetRhsFlat in dense-cost mode: flat q, r, d, x0 in the caller's variables (host, pinned or this device's
+// memory) -> S' -> the resident right-hand side of the reduced problem
+int ndlqr_hip_set_rhs_dense(NdlqrHipCtx* c, const double* q, const double* r, const double* d, const double* x0) {
+  if (!c || !q || !r || !d || !x0) return NDLQR_ERR_INVALID;
+  if (!c->cost.dense) return refuse("ndlqr_hip_set_rhs_dense: the solver is not in dense-cost mode");
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t kn = (size_t)u.batch * u.N;
+  CallerArrays<4> ca = {{const_cast<double*>(q), const_cast<double*>(r), const_cast<double*>(d), const_cast<double*>(x0)},
+                        {kn * u.n, kn * u.m, kn * u.n, (size_t)u.batch * u.n}};
+  int err = ca.classify(c, "ndlqr_hip_set_rhs_dense", "an input lies");
+  if (err) return err;
+  HIP_TRY(sync_all(c));
+  HIP_TRY(c->grad_stage.grow(ca.stage));
+  ca.place(c);
+  BufferSet& s = c->set[c->cur];
+  err = ca.copy(s.stream, true);
+  if (err) return err;
+  HIP_TRY(cost_reduce_rhs(c, ca.dev[0], ca.dev[1], ca.dev[2], ca.dev[3], s.stream));
+  const CostState& k = c->cost;
+  if (u.N != c->d.N)
+    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<true>, dim3(512), dim3(256), 0, s.stream, u, c->d, (const double*)k.qt,
+                       (const double*)k.rt, (const double*)k.dt, (const double*)k.x0t, s.rhs.get());
+  else
+    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<false>, dim3(512), dim3(256), 0, s.stream, u, c->d, (const double*)k.qt,
+                       (const double*)k.rt, (const double*)k.dt, (const double*)k.x0t, s.rhs.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  rhs_written_cur(c, 0xFu);
+  next_solve_on_current_set(c);
+  return NDLQR_OK;
+}
+
+// Read-out for the tests: the records and the reduced problem in the caller's flat layout, each [batch][N][..] (x0t
+// [batch][n]) into HOST memory; any pointer may be null. L [n*n], LR [m*m], G [m*n] column-major.
+int ndlqr_hip_download_cost_reduction(NdlqrHipCtx* c, double* L, double* LR, double* G, double* At, double* Bt, double* qt,
+                                      double* rt, double* dt, double* x0t) {
+  if (!c) return NDLQR_ERR_INVALID;
+  if (!c->cost.dense) return refuse("ndlqr_hip_download_cost_reduction: the solver is not in dense-cost mode");
+  const ndlqr::Dims& u = c->du;
+  const CostState& k = c->cost;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(sync_all(c));
+  const size_t kn = (size_t)u.batch * u.N, n = (size_t)u.n, m = (size_t)u.m, recd = CostState::record_doubles(u);
+  double* const part[3] = {L, LR, G};
+  const size_t width[3] = {n * n, m * m, m * n};
+  size_t off = 0;
+  for (int i = 0; i < 3; off += width[i], ++i)
+    if (part[i])
+      HIP_TRY(hipMemcpy2D(part[i], sizeof(double) * width[i], k.rec + off, sizeof(double) * recd, sizeof(double) * width[i], kn,
+                          hipMemcpyDeviceToHost));
+  double* const dst[6] = {At, Bt, qt, rt, dt, x0t};
+  const double* const src[6] = {k.At, k.Bt, k.qt, k.rt, k.dt, k.x0t};
+  const size_t cnt[6] = {kn * n * n, kn * n * m, kn * n, kn * m, kn * n, (size_t)u.batch * n};
+  for (int i = 0; i < 6; ++i)
+    if (dst[i]) HIP_TRY(hipMemcpy(dst[i], src[i], sizeof(double) * cnt[i], hipMemcpyDeviceToHost));
+  return NDLQR_OK;
+}
+
 // KERNEL<true> under NDLQR_FLAG_STRICT_FP, KERNEL<false> otherwise: one argument list for both
 #define launch_strict(strict, KERNEL, grid, block, lds, stream, ...)                            \
   do {                                                                                          \
@@ -1589,6 +1784,18 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
+  if (c->cost.dense) {  // g~ = S' g in the staging vector, which then is the adjoint's g
+    const size_t count = ((size_t)u.rows * u.N - u.m) * d.batch;
+    if (where(g, c->device) == Where::OtherDevice)
+      return refuse("ndlqr_hip_solve_adjoint: g lies in the memory of another device than the solver's");
+    HIP_TRY(sync_all(c));
+    const hipStream_t st = c->set[0].stream;
+    HIP_TRY(hipMemcpyAsync(c->cost.stage, g, sizeof(double) * count, hipMemcpyDefault, st));
+    HIP_TRY(launch_cost(ndlqr::cost_apply_t, ndlqr::cost_apply_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, c->cost.rec.get(),
+                        nullptr, nullptr, nullptr, nullptr, c->cost.stage.get(), nullptr, nullptr, nullptr, nullptr,
+                        c->cost.stage.get()));
+    g = c->cost.stage;
+  }
   CallerArrays<1> ga = {{const_cast<double*>(g)}, {((size_t)u.rows * u.N - u.m) * d.batch}};
   int err = ga.classify(c, "ndlqr_hip_solve_adjoint", "g lies");
   if (err) return err;
@@ -1639,6 +1846,7 @@ int ndlqr_hip_download_adjoint(NdlqrHipCtx* c, double* w) {
   const BufferSet& s = c->set[0];
   HIP_TRY(sync_all(c));
   HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->adj.z, w, s.stream, c->d.batch));
+  if (c->cost.dense) HIP_TRY(cost_map_back(c, w, 0, c->d.batch, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }
@@ -1646,6 +1854,7 @@ int ndlqr_hip_download_adjoint(NdlqrHipCtx* c, double* w) {
 int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR, double* gq,
                         double* gr, double* gd, double* gx0) {
   if (!c || (sum_mask & ~0xFFu)) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_gradients")) return cerr;
   const int aerr = need_adjoint(c, "ndlqr_hip_gradients");
   if (aerr) return aerr;
   const ndlqr::Dims& d = c->d;
@@ -1743,6 +1952,7 @@ int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* g
 int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const double* xhi, const double* ulo,
                          const double* uhi) {
   if (!c) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_set_bounds")) return cerr;
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
   HIP_TRY(hipSetDevice(c->device));
@@ -1909,6 +2119,7 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
   if (!c || !(rho > 0.0) || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 ||
       check_every < 1 || adapt_every < 0 || (adapt_every > 0 && !(rho_min > 0.0 && rho_min <= rho_max)))
     return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_box")) return cerr;
   if (!c->box.have_bounds) return refuse("ndlqr_hip_solve_box: no bounds (ndlqr_hip_set_bounds first)");
   const ndlqr::Dims& d = c->d;
   HIP_TRY(hipSetDevice(c->device));
@@ -2076,8 +2287,10 @@ int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_
 
 int ndlqr_hip_set_box_infeasibility(NdlqrHipCtx* c, int every, double eps) {
   if (!c || every < 0 || !(eps > 0.0 && eps < HUGE_VAL)) return NDLQR_ERR_INVALID;
-  if (every > 0)  // (switching it off is always possible)
+  if (every > 0) {  // (switching it off is always possible)
     if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_set_box_infeasibility")) return herr;
+    if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_set_box_infeasibility")) return cerr;
+  }
   c->infeas.every = every;
   c->infeas.eps = eps;
   return NDLQR_OK;
@@ -2086,6 +2299,7 @@ int ndlqr_hip_set_box_infeasibility(NdlqrHipCtx* c, int every, double eps) {
 int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* c, double* dlam, double* dmu_x, double* dmu_u) {
   if (!c || (!dlam && !dmu_x && !dmu_u)) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_infeasibility_certificate")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_infeasibility_certificate")) return cerr;
   if (c->infeas.gen == 0 || c->infeas.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
     return refuse("ndlqr_hip_download_infeasibility_certificate: the resident solution is not that of a constrained solve "
                   "with infeasibility detection on (ndlqr_hip_set_box_infeasibility before the solve)");
@@ -2112,6 +2326,7 @@ int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* c, double* dlam, d
 int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* c, double* measures, int* iteration) {
   if (!c || (!measures && !iteration)) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_infeasibility_measures")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_infeasibility_measures")) return cerr;
   if (c->infeas.gen == 0 || c->infeas.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
     return refuse("ndlqr_hip_download_infeasibility_measures: the resident solution is not that of a constrained solve "
                   "with infeasibility detection on (ndlqr_hip_set_box_infeasibility before the solve)");
@@ -2130,8 +2345,10 @@ int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* c, double* measures, 
 int ndlqr_hip_set_box_acceleration(NdlqrHipCtx* c, int mem, double safeguard, double reg) {
   if (!c || mem < 0 || mem > ndlqr::ACCEL_MEM_MAX || !(safeguard > 0.0 && safeguard < HUGE_VAL) || !(reg > 0.0 && reg < HUGE_VAL))
     return NDLQR_ERR_INVALID;
-  if (mem > 0)  // (switching it off is always possible)
+  if (mem > 0) {  // (switching it off is always possible)
     if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_set_box_acceleration")) return herr;
+    if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_set_box_acceleration")) return cerr;
+  }
   c->accel.mem = mem;
   c->accel.gen = 0;  // (the read-out's gamma has the width of the memory it ran with: a solve with this setting first)
   c->accel.safeguard = safeguard;
@@ -2142,6 +2359,7 @@ int ndlqr_hip_set_box_acceleration(NdlqrHipCtx* c, int mem, double safeguard, do
 int ndlqr_hip_download_box_acceleration(NdlqrHipCtx* c, int* accepted, int* rejected, double* gamma, int* columns) {
   if (!c || (!accepted && !rejected && !gamma && !columns)) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_box_acceleration")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_box_acceleration")) return cerr;
   if (c->accel.gen == 0 || c->accel.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
     return refuse("ndlqr_hip_download_box_acceleration: the resident solution is not that of a constrained solve with "
                   "acceleration on (ndlqr_hip_set_box_acceleration before the solve)");
@@ -2162,6 +2380,7 @@ int ndlqr_hip_download_box_acceleration(NdlqrHipCtx* c, int* accepted, int* reje
 
 int ndlqr_hip_download_box_penalties(NdlqrHipCtx* c, double* rho) {
   if (!c || !rho) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_box_penalties")) return cerr;
   if (!c->box.have_vy || !c->box.rho) return refuse("ndlqr_hip_download_box_penalties: no constrained solve yet");
   HIP_TRY(hipSetDevice(c->device));
   if (where(rho, c->device) == Where::OtherDevice)
@@ -2191,6 +2410,7 @@ int ndlqr_hip_download_box_residuals(NdlqrHipCtx* c, double* resid) {
 int ndlqr_hip_download_box_adjoint_residuals(NdlqrHipCtx* c, double* resid) {
   if (!c || !resid) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_box_adjoint_residuals")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_box_adjoint_residuals")) return cerr;
   if (c->abox.gen == 0 || c->abox.gen != c->soln_gen || !c->abox.resid)
     return refuse("ndlqr_hip_download_box_adjoint_residuals: no box adjoint of the resident solution "
                   "(ndlqr_hip_solve_box_adjoint after the latest constrained solve)");
@@ -2199,6 +2419,7 @@ int ndlqr_hip_download_box_adjoint_residuals(NdlqrHipCtx* c, double* resid) {
 
 int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* mu_u) {
   if (!c || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_bound_multipliers")) return cerr;
   if (!c->box.have_vy || !c->box.y) return refuse("ndlqr_hip_download_bound_multipliers: no constrained solve yet");
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
@@ -2236,6 +2457,7 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
       check_every < 1)
     return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_solve_box_adjoint")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_box_adjoint")) return cerr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_box_adjoint");
   if (c->pol.soln_gen != 0 && c->pol.soln_gen == c->soln_gen)
     return refuse("ndlqr_hip_solve_box_adjoint: the resident solution was polished (ndlqr_hip_polish_box), which replaced the "
@@ -2340,6 +2562,7 @@ int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, d
 int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* gxhi, double* gulo, double* guhi) {
   if (!c) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_bound_gradients")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_bound_gradients")) return cerr;
   const int aerr = need_adjoint(c, "ndlqr_hip_bound_gradients");
   if (aerr) return aerr;
   const bool polished = c->pol.adj_gen != 0 && c->pol.adj_gen == c->soln_gen;  // (nu split by the polish codes, penalty 1)
@@ -2460,6 +2683,7 @@ struct RefinePhases {
 int ndlqr_hip_refine(NdlqrHipCtx* c, int which, int max_steps, int* steps, double* eta_before, double* eta_after) {
   if (!c || which < 0 || which > 1 || max_steps < 1 || max_steps > kRefineMaxSteps) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_refine")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_refine")) return cerr;
   const char* who = which ? "ndlqr_hip_refine (adjoint)" : "ndlqr_hip_refine";
   if (!c->kept.fact_valid && !c->kept.rec_complete)
     return refuse(std::string(who) + ": needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
@@ -2550,6 +2774,7 @@ int ndlqr_hip_refine_phase_ms(NdlqrHipCtx* c, double* out3) {
 
 int ndlqr_hip_kkt_residual_vector(NdlqrHipCtx* c, double* r) {
   if (!c || !r) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_kkt_residual_vector")) return cerr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_kkt_residual_vector");
   HIP_TRY(hipSetDevice(c->device));
   const Where wr = where(r, c->device);
@@ -2626,6 +2851,7 @@ int ndlqr_hip_polish_box(NdlqrHipCtx* c, double sigma, int max_steps, int max_ro
   if (!c || !(sigma > 0.0) || !(sigma < HUGE_VAL) || max_steps < 1 || max_steps > kPolishMaxSteps || max_rounds < 0)
     return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_polish_box")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_polish_box")) return cerr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_polish_box");
   if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.have_vy || c->inputs_replaced)
     return refuse("ndlqr_hip_polish_box: the resident solution is not that of the latest constrained solve (a solve, step, "
@@ -2729,6 +2955,7 @@ int ndlqr_hip_polish_box(NdlqrHipCtx* c, double sigma, int max_steps, int max_ro
 int ndlqr_hip_solve_polished_adjoint(NdlqrHipCtx* c, const double* g, int max_steps, int* steps, int* status) {
   if (!c || !g || max_steps < 1 || max_steps > kPolishMaxSteps) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_solve_polished_adjoint")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_polished_adjoint")) return cerr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_polished_adjoint");
   if (c->pol.soln_gen == 0 || c->pol.soln_gen != c->soln_gen || !c->pol.fact || c->inputs_replaced)
     return refuse("ndlqr_hip_solve_polished_adjoint: the resident solution is not that of the latest polish, or its "
@@ -2800,6 +3027,7 @@ int ndlqr_hip_solve_polished_adjoint(NdlqrHipCtx* c, const double* g, int max_st
 int ndlqr_hip_download_polish_codes(NdlqrHipCtx* c, unsigned char* codes) {
   if (!c || !codes) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_polish_codes")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_polish_codes")) return cerr;
   if (c->pol.soln_gen == 0 || c->pol.soln_gen != c->soln_gen)
     return refuse("ndlqr_hip_download_polish_codes: the resident solution is not that of a polish");
   const ndlqr::Dims& d = c->d;
@@ -2831,6 +3059,7 @@ static int solve_multi_rhs(NdlqrHipCtx* c, int nrhs, const double* q, const doub
                            const KnotSlice& sel, double* soln) {
   if (!c || nrhs <= 0 || !q || !r || !dd || !x0 || !soln) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, sel.nknots > 0 ? "ndlqr_hip_solve_multi_rhs_slices" : "ndlqr_hip_solve_multi_rhs")) return herr;
+  if (const int cerr = need_diagonal_cost(c, sel.nknots > 0 ? "ndlqr_hip_solve_multi_rhs_slices" : "ndlqr_hip_solve_multi_rhs")) return cerr;
   if (sel.nknots > 0 && !sel.valid(c->d.N, 15u)) return NDLQR_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(sync_all(c));
@@ -2969,6 +3198,7 @@ static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count
   const size_t nvars = (size_t)c->du.rows * c->du.N - c->du.m, pitch = (size_t)d.rows * d.N;
   hipStream_t st = s.stream;
   HIP_TRY(launch_pack(c->du, d, KnotSlice(), zsrc + p0 * pitch, s.xfer, st, count));
+  if (c->cost.dense) HIP_TRY(cost_map_back(c, s.xfer, p0, count, st));  // the reduced variables -> the caller's, in the staging
   const size_t total = nvars * count;
   if (where(soln, c->device) == Where::Pinned) {
     HIP_TRY(hipMemcpyAsync(soln, s.xfer, sizeof(double) * total, hipMemcpyDeviceToHost, st));
@@ -3015,11 +3245,13 @@ int ndlqr_hip_pack_solutions_device(NdlqrHipCtx* c, double* dst) {
   HIP_TRY(hipSetDevice(c->device));
   // on the stream of the latest solve: ordered behind it, asynchronous for the caller
   HIP_TRY(launch_pack(c->du, d, KnotSlice(), c->set[c->latest].z, dst, c->set[c->latest].stream, d.batch));
+  if (c->cost.dense) HIP_TRY(cost_map_back(c, dst, 0, d.batch, c->set[c->latest].stream));
   return NDLQR_OK;
 }
 
 int ndlqr_hip_kkt_residual(NdlqrHipCtx* c, double* res, double* bnorm) {
   if (!c || !res) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_kkt_residual")) return cerr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_kkt_residual");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
@@ -3041,6 +3273,7 @@ int ndlqr_hip_kkt_residual(NdlqrHipCtx* c, double* res, double* bnorm) {
 int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
   if (!c || !z_full || p < 0 || p >= c->d.batch) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_rhs_blocks")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_rhs_blocks")) return cerr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_download_rhs_blocks");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
@@ -3064,6 +3297,7 @@ int ndlqr_hip_download_rhs_blocks(NdlqrHipCtx* c, int p, double* z_full) {
 int ndlqr_hip_download_factors(NdlqrHipCtx* c, int p, double* fact) {
   if (!c || !fact || p < 0 || p >= c->d.batch) return NDLQR_ERR_INVALID;
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_factors")) return herr;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_factors")) return cerr;
   if (!c->kept.fact_valid) return refuse("factor download needs NDLQR_FLAG_KEEP_FACT set before the solve");
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
