@@ -131,21 +131,169 @@ __global__ void box_start(Dims d, const double* __restrict__ rhov, int cold_all,
   }
 }
 
-// One ADMM update of every running problem (status[b] == 0) after re-solve `it` (1-based): z [batch][N][2n+m] is the
-// re-solve's solution with the right-hand side rhs_cur; v, y are updated in place, the next right-hand side -- from the
-// resident one, res -- goes to rhs_next. Per problem, over its bounded entries: r_prim = max |z - v+|, r_dual = rho max |v+ - v|; converged when
-//     r_prim <= eps_abs + eps_rel max(max |z|, max |v+|)   and   r_dual <= eps_abs + eps_rel rho max |y+|.
-// A converged problem is frozen: status 1, and rhs_next takes a copy of rhs_cur, so later re-solves reproduce its z. A
-// problem whose maxima are not finite (NaN / inf in its iterate; the reductions keep a NaN) is frozen as status 3.
-// The running count drops by one with an ordinary global atomic. Max-reductions in LDS: deterministic.
-// adapt != 0: a problem that keeps running may move its penalty by a power of two, decided by
-// thread 0 from the same maxima -- with sp = max(max |z|, max |v+|) and sd = rho max |y+|, all of r_prim, r_dual, sp, sd
-// finite and > 0:
+// ---- The update core shared by box_update, box_update_accel (kernels_box_accel.hpp) and box_adjoint_update
+// (kernels_box_grad.hpp). One workgroup of 256 threads per problem; entry e of [N][w] belongs to thread e mod 256 in every
+// pass (e = tid; e += blockDim.x), so a thread re-reads only what it wrote itself and no pass waits for global stores.
+
+// offset of entry e of [N][w] (x or u entry j of knot k, e = k w + j) in a problem's [N][rows] block
+__device__ __forceinline__ size_t box_entry_offset(const Dims& d, unsigned e) {
+  const unsigned k = e / (unsigned)d.w, j = e - k * (unsigned)d.w;
+  return (size_t)k * d.rows + d.n + j;
+}
+
+// Problem b's part of the arrays every update kernel works on.
+struct BoxViews {
+  unsigned nw;  // entries of [N][w]
+  const double *zb, *rs, *rc;
+  double *vb, *yb, *rn;
+  __device__ __forceinline__ BoxViews(const Dims& d, int b, const double* z, double* v, double* y, const double* res,
+                                      const double* rhs_cur, double* rhs_next)
+      : nw((unsigned)(d.N * d.w)), zb(z + (size_t)b * d.N * d.rows), rs(res + (size_t)b * d.N * d.rows),
+        rc(rhs_cur + (size_t)b * d.N * d.rows), vb(v + (size_t)b * nw), yb(y + (size_t)b * nw),
+        rn(rhs_next + (size_t)b * d.N * d.rows) {}
+};
+
+// Problem b's bounds in a forward kernel, and the predicate "entry e is bounded" its tails take.
+struct BoxBounds {
+  const double *lb, *hb;
+  __device__ __forceinline__ BoxBounds(const double* lo, const double* hi, size_t bstride, int b)
+      : lb(lo + (size_t)b * bstride), hb(hi + (size_t)b * bstride) {}
+  __device__ __forceinline__ bool operator()(unsigned e) const { return box_bounded(lb[e], hb[e]); }
+};
+
+// The five running maxima of a problem over its bounded entries: |z - v+|, |v+ - v|, |z|, |v+|, |y+|. They keep a NaN.
+struct BoxMaxima {
+  double rp = 0.0, rd = 0.0, zm = 0.0, vm = 0.0, ym = 0.0;
+  __device__ __forceinline__ void note(double zi, double v0, double vn, double yn) {
+    rp = max_nan(rp, fabs(zi - vn));
+    rd = max_nan(rd, fabs(vn - v0));
+    zm = max_nan(zm, fabs(zi));
+    vm = max_nan(vm, fabs(vn));
+    ym = max_nan(ym, fabs(yn));
+  }
+  // over the workgroup into red[q][0], by a tree in LDS: deterministic. Ends in a barrier.
+  __device__ __forceinline__ void reduce(double (&red)[5][256], int tid) const {
+    red[0][tid] = rp; red[1][tid] = rd; red[2][tid] = zm; red[3][tid] = vm; red[4][tid] = ym;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s)
+        for (int q = 0; q < 5; ++q) red[q][tid] = max_nan(red[q][tid], red[q][tid + s]);
+      __syncthreads();
+    }
+  }
+};
+
+// zh = alpha z + (1 - alpha) v
+template <bool STRICT>
+__device__ __forceinline__ double box_relaxed(const BoxParams& P, double zi, double v0) {
+  if constexpr (STRICT) {
+    const double a = P.alpha * zi;
+    const double c = P.oma * v0;
+    return a + c;
+  } else {
+    return fma(P.alpha, zi, P.oma * v0);
+  }
+}
+
+struct BoxStep {
+  double t, vn, yn;  // zh + y, v+, y+
+};
+
+// The step of one bounded entry from its z, v, y: t = zh + y, v+ = clip ? min(max(t, lo), hi) : t, y+ = (y + zh) - v+.
+// Arithmetic only. Each kernel loads z before v and y, stores v+, y+, writes the next right-hand side entry
+// (box_rhs_entry) and lets the maxima take note, in that order.
+template <bool STRICT>
+__device__ __forceinline__ BoxStep box_step(const BoxParams& P, double zi, double v0, double y0, bool clip, double lo,
+                                            double hi) {
+  const double zh = box_relaxed<STRICT>(P, zi, v0);
+  const double t = zh + y0;
+  const double vn = clip ? fmin(fmax(t, lo), hi) : t;
+  const double yn = (y0 + zh) - vn;
+  return {t, vn, yn};
+}
+
+struct BoxVerdict {
+  double r_prim, r_dual, sp, sd;
+  bool frozen;
+};
+
+// Thread 0's judgement of problem b after re-solve `it` (1-based), from the reduced maxima: r_prim = max |z - v+|,
+// r_dual = rho max |v+ - v|, sp = max(max |z|, max |v+|), sd = rho max |y+|; converged when
+//     r_prim <= eps_abs + eps_rel sp   and   r_dual <= eps_abs + eps_rel sd.
+// A converged problem is frozen as status 1; one whose maxima are not finite (a NaN or an infinity in z, v+ or y+, from
+// the problem data or a failed pivot) as status 3. A frozen problem leaves the running count by an ordinary global
+// atomic. iters[b] = it, and the four numbers go to resid[b] (the read-outs ndlqr_CopyBatchBoxResiduals and
+// ndlqr_CopyBatchBoxAdjointResiduals) whether or not the problem goes on.
+__device__ __forceinline__ BoxVerdict box_judge(const BoxParams& P, double rho, const double (&red)[5][256], int b, int it,
+                                                int* status, int* iters, double* resid, int* running) {
+  const double r_prim = red[0][0], r_dual = rho * red[1][0];
+  const double sp = max_nan(red[2][0], red[3][0]), sd = rho * red[4][0];
+  const double tol_p = P.eps_abs + P.eps_rel * sp;
+  const double tol_d = P.eps_abs + P.eps_rel * sd;
+  const bool finite = isfinite(r_prim) && isfinite(r_dual) && isfinite(red[2][0]) && isfinite(red[3][0]) &&
+                      isfinite(red[4][0]);
+  const int conv = finite && r_prim <= tol_p && r_dual <= tol_d;
+  iters[b] = it;
+  resid[4 * (size_t)b] = r_prim;
+  resid[4 * (size_t)b + 1] = r_dual;
+  resid[4 * (size_t)b + 2] = sp;
+  resid[4 * (size_t)b + 3] = sd;
+  if (conv || !finite) {
+    status[b] = conv ? 1 : 3;
+    atomicSub(running, 1);
+  }
+  return {r_prim, r_dual, sp, sd, conv || !finite};
+}
+
+// The adaptive penalty of a problem that goes on, decided by thread 0 from the verdict's four
+// numbers when all of them are finite and > 0:
 //     k = (ilogb(r_prim / sp) - ilogb(r_dual / sd)) / 2 (toward zero) clamped to [-6, 6],
-//     rho+ = ldexp(rho, k) clamped to [rho_min, rho_max];
-// when rho+ != rho: y <- y (rho / rho+) on the bounded entries (mu = rho y is kept), rho[b] = rho+, rhs_next rewritten
-// from rho+ and that y in a second pass, and running[1] counts the problem (the host refactors). Exact or correctly
-// rounded operations only: numpy reproduces the decision bit for bit. A frozen problem never changes its penalty.
+//     rho+ = ldexp(rho, k) clamped to [rho_min, rho_max].
+// Exact or correctly rounded operations only: numpy reproduces the decision bit for bit. True when rho+ != rho: then
+// *rho_next = rho[b] = rho+ and running[1] counts the problem (the host refactors).
+__device__ __forceinline__ bool box_adapt_penalty(const BoxParams& P, double rho, const BoxVerdict& J, int b, double* rhov,
+                                                  int* running, double* rho_next) {
+  if (!(isfinite(J.sd) && J.r_prim > 0.0 && J.r_dual > 0.0 && J.sp > 0.0 && J.sd > 0.0)) return false;
+  int k = (ilogb(J.r_prim / J.sp) - ilogb(J.r_dual / J.sd)) / 2;
+  k = k < -6 ? -6 : k > 6 ? 6 : k;
+  if (k == 0) return false;
+  const double rn = fmin(fmax(ldexp(rho, k), P.rho_min), P.rho_max);
+  if (rn == rho) return false;
+  *rho_next = rn;
+  rhov[b] = rn;
+  atomicAdd(running + 1, 1);
+  return true;
+}
+
+// Tail of a problem whose penalty moved from rho to rho_new: y <- y (rho / rho_new) on the entries that count (mu = rho y
+// is kept) and the next right-hand side rewritten from rho_new and that y. Reads the v+, y+ this thread stored.
+template <bool STRICT, class Counts>
+__device__ __forceinline__ void box_tail_new_penalty(const Dims& d, const BoxViews& V, double rho, double rho_new, int tid,
+                                                     Counts counts) {
+  const double s = rho / rho_new;
+  for (unsigned e = tid; e < V.nw; e += blockDim.x) {
+    if (!counts(e)) continue;
+    const size_t oz = box_entry_offset(d, e);
+    const double ys = V.yb[e] * s;
+    V.yb[e] = ys;
+    V.rn[oz] = box_rhs_entry<STRICT>(V.rs[oz], V.vb[e], ys, rho_new);
+  }
+}
+
+// Tail of a frozen problem: the next right-hand side is the current one, so later re-solves reproduce its z.
+template <class Counts>
+__device__ __forceinline__ void box_tail_frozen(const Dims& d, const BoxViews& V, int tid, Counts counts) {
+  for (unsigned e = tid; e < V.nw; e += blockDim.x) {
+    if (!counts(e)) continue;
+    const size_t oz = box_entry_offset(d, e);
+    V.rn[oz] = V.rc[oz];
+  }
+}
+
+// One ADMM update of every running problem (status[b] == 0) after re-solve `it`: z [batch][N][2n+m] is the re-solve's
+// solution with the right-hand side rhs_cur; v, y are updated in place over the bounded entries (box_step with the clip
+// to [lo, hi]), the next right-hand side -- from the resident one, res -- goes to rhs_next; then box_judge. adapt != 0: a
+// problem that goes on may move its penalty (box_adapt_penalty, box_tail_new_penalty). A frozen problem never does.
 //   grid (batch), block 256.
 template <bool STRICT>
 __global__ __launch_bounds__(256) void box_update(Dims d, int it, int adapt, BoxParams P, const double* __restrict__ z,
@@ -161,104 +309,28 @@ __global__ __launch_bounds__(256) void box_update(Dims d, int it, int adapt, Box
   const int b = blockIdx.x, tid = threadIdx.x;
   if (status[b] != 0) return;  // frozen (uniform over the workgroup)
   const double rho = rhov[b];
-  const int w = d.w, n = d.n, rows = d.rows;
-  const unsigned nw = (unsigned)(d.N * w);
-  const double* lb = lo + (size_t)b * bstride;
-  const double* hb = hi + (size_t)b * bstride;
-  double* vb = v + (size_t)b * nw;
-  double* yb = y + (size_t)b * nw;
-  const double* zb = z + (size_t)b * d.N * rows;
-  const double* rs = res + (size_t)b * d.N * rows;
-  const double* rc = rhs_cur + (size_t)b * d.N * rows;
-  double* rn = rhs_next + (size_t)b * d.N * rows;
-  double rp = 0.0, rd = 0.0, zm = 0.0, vm = 0.0, ym = 0.0;
-  for (unsigned e = tid; e < nw; e += blockDim.x) {
-    const double l = lb[e], h = hb[e];
+  const BoxViews V(d, b, z, v, y, res, rhs_cur, rhs_next);
+  const BoxBounds bounded(lo, hi, bstride, b);
+  BoxMaxima M;
+  for (unsigned e = tid; e < V.nw; e += blockDim.x) {
+    const double l = bounded.lb[e], h = bounded.hb[e];
     if (!box_bounded(l, h)) continue;
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-    const size_t oz = (size_t)k * rows + n + j;
-    const double zi = zb[oz], v0 = vb[e], y0 = yb[e];
-    double zh;
-    if constexpr (STRICT) {
-      const double a = P.alpha * zi;
-      const double c = P.oma * v0;
-      zh = a + c;
-    } else {
-      zh = fma(P.alpha, zi, P.oma * v0);
-    }
-    const double t = zh + y0;
-    const double vn = fmin(fmax(t, l), h);
-    const double yn = (y0 + zh) - vn;
-    vb[e] = vn;
-    yb[e] = yn;
-    rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, rho);
-    rp = max_nan(rp, fabs(zi - vn));
-    rd = max_nan(rd, fabs(vn - v0));
-    zm = max_nan(zm, fabs(zi));
-    vm = max_nan(vm, fabs(vn));
-    ym = max_nan(ym, fabs(yn));
+    const size_t oz = box_entry_offset(d, e);
+    const double zi = V.zb[oz], v0 = V.vb[e], y0 = V.yb[e];
+    const BoxStep s = box_step<STRICT>(P, zi, v0, y0, true, l, h);
+    V.vb[e] = s.vn;
+    V.yb[e] = s.yn;
+    V.rn[oz] = box_rhs_entry<STRICT>(V.rs[oz], s.vn, s.yn, rho);
+    M.note(zi, v0, s.vn, s.yn);
   }
-  red[0][tid] = rp; red[1][tid] = rd; red[2][tid] = zm; red[3][tid] = vm; red[4][tid] = ym;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s)
-      for (int q = 0; q < 5; ++q) red[q][tid] = max_nan(red[q][tid], red[q][tid + s]);
-    __syncthreads();
-  }
+  M.reduce(red, tid);
   if (tid == 0) {
-    const double r_prim = red[0][0], r_dual = rho * red[1][0];
-    const double sp = max_nan(red[2][0], red[3][0]), sd = rho * red[4][0];
-    const double tol_p = P.eps_abs + P.eps_rel * sp;
-    const double tol_d = P.eps_abs + P.eps_rel * sd;
-    // a NaN or an infinity in z, v+ or y+ (from the problem data or a failed pivot) ends the problem as status 3
-    const bool finite = isfinite(r_prim) && isfinite(r_dual) && isfinite(red[2][0]) && isfinite(red[3][0]) &&
-                        isfinite(red[4][0]);
-    const int conv = finite && r_prim <= tol_p && r_dual <= tol_d;
-    iters[b] = it;
-    resid[4 * (size_t)b] = r_prim;  // the read-out (ndlqr_CopyBatchBoxResiduals): the four numbers of the test below
-    resid[4 * (size_t)b + 1] = r_dual;
-    resid[4 * (size_t)b + 2] = sp;
-    resid[4 * (size_t)b + 3] = sd;
-    if (conv || !finite) {
-      status[b] = conv ? 1 : 3;
-      atomicSub(running, 1);
-    }
-    int mode = conv || !finite;
-    if (adapt && !mode && isfinite(sd) && r_prim > 0.0 && r_dual > 0.0 && sp > 0.0 && sd > 0.0) {
-      int k = (ilogb(r_prim / sp) - ilogb(r_dual / sd)) / 2;
-      k = k < -6 ? -6 : k > 6 ? 6 : k;
-      if (k != 0) {
-        const double rho_next = fmin(fmax(ldexp(rho, k), P.rho_min), P.rho_max);
-        if (rho_next != rho) {
-          rho_s = rho_next;
-          rhov[b] = rho_next;
-          atomicAdd(running + 1, 1);
-          mode = 2;
-        }
-      }
-    }
-    conv_s = mode;
+    const BoxVerdict J = box_judge(P, rho, red, b, it, status, iters, resid, running);
+    conv_s = J.frozen ? 1 : adapt && box_adapt_penalty(P, rho, J, b, rhov, running, &rho_s) ? 2 : 0;
   }
   __syncthreads();
-  if (!conv_s) return;
-  if (conv_s == 2) {  // a new penalty: y rescaled, the next right-hand side from it (same entry -> thread map as above)
-    const double rho_new = rho_s, s = rho / rho_new;
-    for (unsigned e = tid; e < nw; e += blockDim.x) {
-      if (!box_bounded(lb[e], hb[e])) continue;
-      const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-      const size_t oz = (size_t)k * rows + n + j;
-      const double ys = yb[e] * s;
-      yb[e] = ys;
-      rn[oz] = box_rhs_entry<STRICT>(rs[oz], vb[e], ys, rho_new);
-    }
-    return;
-  }
-  for (unsigned e = tid; e < nw; e += blockDim.x) {  // frozen: the next right-hand side is the current one
-    if (!box_bounded(lb[e], hb[e])) continue;
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-    const size_t oz = (size_t)k * rows + n + j;
-    rn[oz] = rc[oz];
-  }
+  if (conv_s == 2) box_tail_new_penalty<STRICT>(d, V, rho, rho_s, tid, bounded);
+  else if (conv_s == 1) box_tail_frozen(d, V, tid, bounded);
 }
 
 // End of a solve: the resident solution blocks zs get lambda from the last re-solve z and x, u from v (bounded entries)

@@ -59,9 +59,9 @@ __device__ __forceinline__ double accel_wave_sum(double x) {
   return x;
 }
 
-// One ADMM update of every running problem, as box_update (same arguments, same convergence test, NaN rule, status,
-// residuals, running count and adaptive penalty, all evaluated on the plain v+, y+ before anything else), then per
-// problem that keeps running with its penalty:
+// One ADMM update of every running problem: box_update's arguments and its calls of the shared core of kernels_box.hpp
+// (box_step with the clip to [lo, hi], box_judge, box_adapt_penalty and the two tails), so everything is judged on the
+// plain v+, y+ before anything else; then per problem that keeps running with its penalty:
 //   - started from an accelerated iterate and |g| > safeguard |g_prev|: v, y <- pv, py, the next right-hand side from
 //     them, the history cleared, a rejection counted; |g_prev| stays;
 //   - otherwise (t, g) is pushed; with c >= 1 columns and plain_only == 0 thread 0 solves for gamma by Cholesky; a
@@ -70,7 +70,7 @@ __device__ __forceinline__ double accel_wave_sum(double x) {
 // A problem whose penalty moves takes the plain v+, y+ (y rescaled) and clears its history: w changes scale with rho.
 // plain_only (the iteration before an infeasibility check and the check iteration): the history is recorded, the step
 // is the plain one. Sums: per thread in entry order, per wavefront by accel_wave_sum, the four wavefronts in order by
-// thread 0 -- no floating-point atomics. Maxima: the LDS tree of box_update.
+// thread 0 -- no floating-point atomics.
 //   grid (batch), block 256.
 template <bool STRICT>
 __global__ __launch_bounds__(256) void box_update_accel(Dims d, int it, int adapt, int plain_only, BoxParams P, AccelParams A,
@@ -91,16 +91,9 @@ __global__ __launch_bounds__(256) void box_update_accel(Dims d, int it, int adap
   const int b = blockIdx.x, tid = threadIdx.x, batch = gridDim.x;
   if (status[b] != 0) return;  // frozen (uniform over the workgroup)
   const double rho = rhov[b];
-  const int w = d.w, n = d.n, rows = d.rows;
-  const unsigned nw = (unsigned)(d.N * w);
-  const double* lb = lo + (size_t)b * bstride;
-  const double* hb = hi + (size_t)b * bstride;
-  double* vb = v + (size_t)b * nw;
-  double* yb = y + (size_t)b * nw;
-  const double* zb = z + (size_t)b * d.N * rows;
-  const double* rs = res + (size_t)b * d.N * rows;
-  const double* rc = rhs_cur + (size_t)b * d.N * rows;
-  double* rn = rhs_next + (size_t)b * d.N * rows;
+  const BoxViews V(d, b, z, v, y, res, rhs_cur, rhs_next);
+  const unsigned nw = V.nw;
+  const BoxBounds bounded(lo, hi, bstride, b);
   // the ring as this iteration's push leaves it: a full ring drops its oldest entry, the new one takes slot snew
   const int R = A.mem + 1;
   const int fill = X.meta[ACCEL_FILL * batch + b];
@@ -113,37 +106,22 @@ __global__ __launch_bounds__(256) void box_update_accel(Dims d, int it, int adap
   double* Gr = X.ring_g + (size_t)b * R * nw;
   double* pvb = X.pv + (size_t)b * nw;
   double* pyb = X.py + (size_t)b * nw;
-  double rp = 0.0, rd = 0.0, zm = 0.0, vm = 0.0, ym = 0.0;
+  BoxMaxima M;
   double acc_a[OLD], acc_b[OLD], a_new = 0.0, b_new = 0.0, gg = 0.0;
 #pragma unroll
   for (int k = 0; k < OLD; ++k) acc_a[k] = acc_b[k] = 0.0;
   for (unsigned e = tid; e < nw; e += blockDim.x) {
-    const double l = lb[e], h = hb[e];
+    const double l = bounded.lb[e], h = bounded.hb[e];
     if (!box_bounded(l, h)) continue;
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-    const size_t oz = (size_t)k * rows + n + j;
-    const double zi = zb[oz], v0 = vb[e], y0 = yb[e];
-    double zh;
-    if constexpr (STRICT) {
-      const double a = P.alpha * zi;
-      const double c = P.oma * v0;
-      zh = a + c;
-    } else {
-      zh = fma(P.alpha, zi, P.oma * v0);
-    }
-    const double t = zh + y0;
-    const double vn = fmin(fmax(t, l), h);
-    const double yn = (y0 + zh) - vn;
-    vb[e] = vn;
-    yb[e] = yn;
-    rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, rho);
-    rp = max_nan(rp, fabs(zi - vn));
-    rd = max_nan(rd, fabs(vn - v0));
-    zm = max_nan(zm, fabs(zi));
-    vm = max_nan(vm, fabs(vn));
-    ym = max_nan(ym, fabs(yn));
+    const size_t oz = box_entry_offset(d, e);
+    const double zi = V.zb[oz], v0 = V.vb[e], y0 = V.yb[e];
+    const BoxStep st = box_step<STRICT>(P, zi, v0, y0, true, l, h);
+    V.vb[e] = st.vn;
+    V.yb[e] = st.yn;
+    V.rn[oz] = box_rhs_entry<STRICT>(V.rs[oz], st.vn, st.yn, rho);
+    M.note(zi, v0, st.vn, st.yn);
     // the residual of the fixed-point map, the push, and this entry's terms of the new row of dG'dG and of dG'g
-    const double g = t - (v0 + y0);
+    const double t = st.t, g = t - (v0 + y0);
     gg = accel_mad<STRICT>(g, g, gg);
     if (fp > 0) {
       int s = slast;
@@ -166,7 +144,6 @@ __global__ __launch_bounds__(256) void box_update_accel(Dims d, int it, int adap
     Tr[(size_t)snew * nw + e] = t;
     Gr[(size_t)snew * nw + e] = g;
   }
-  red[0][tid] = rp; red[1][tid] = rd; red[2][tid] = zm; red[3][tid] = vm; red[4][tid] = ym;
   {
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
@@ -179,43 +156,10 @@ __global__ __launch_bounds__(256) void box_update_accel(Dims d, int it, int adap
     const double sa = accel_wave_sum(a_new), sb = accel_wave_sum(b_new), sg = accel_wave_sum(gg);
     if (lane == 0) { sums[2 * OLD][wave] = sa; sums[2 * OLD + 1][wave] = sb; sums[2 * OLD + 2][wave] = sg; }
   }
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s)
-      for (int q = 0; q < 5; ++q) red[q][tid] = max_nan(red[q][tid], red[q][tid + s]);
-    __syncthreads();
-  }
+  M.reduce(red, tid);
   if (tid == 0) {
-    const double r_prim = red[0][0], r_dual = rho * red[1][0];
-    const double sp = max_nan(red[2][0], red[3][0]), sd = rho * red[4][0];
-    const double tol_p = P.eps_abs + P.eps_rel * sp;
-    const double tol_d = P.eps_abs + P.eps_rel * sd;
-    const bool finite = isfinite(r_prim) && isfinite(r_dual) && isfinite(red[2][0]) && isfinite(red[3][0]) &&
-                        isfinite(red[4][0]);
-    const int conv = finite && r_prim <= tol_p && r_dual <= tol_d;
-    iters[b] = it;
-    resid[4 * (size_t)b] = r_prim;  // the read-out (ndlqr_CopyBatchBoxResiduals): the four numbers of the test below
-    resid[4 * (size_t)b + 1] = r_dual;
-    resid[4 * (size_t)b + 2] = sp;
-    resid[4 * (size_t)b + 3] = sd;
-    if (conv || !finite) {
-      status[b] = conv ? 1 : 3;
-      atomicSub(running, 1);
-    }
-    int mode = conv || !finite;
-    if (adapt && !mode && isfinite(sd) && r_prim > 0.0 && r_dual > 0.0 && sp > 0.0 && sd > 0.0) {
-      int k = (ilogb(r_prim / sp) - ilogb(r_dual / sd)) / 2;
-      k = k < -6 ? -6 : k > 6 ? 6 : k;
-      if (k != 0) {
-        const double rho_next = fmin(fmax(ldexp(rho, k), P.rho_min), P.rho_max);
-        if (rho_next != rho) {
-          rho_s = rho_next;
-          rhov[b] = rho_next;
-          atomicAdd(running + 1, 1);
-          mode = 2;
-        }
-      }
-    }
+    const BoxVerdict J = box_judge(P, rho, red, b, it, status, iters, resid, running);
+    int mode = J.frozen ? 1 : adapt && box_adapt_penalty(P, rho, J, b, rhov, running, &rho_s) ? 2 : 0;
     int* meta = X.meta + b;  // word q at meta[q * batch]
     if (mode == 2) {
       meta[ACCEL_FILL * batch] = 0;
@@ -291,12 +235,11 @@ __global__ __launch_bounds__(256) void box_update_accel(Dims d, int it, int adap
     const int c = fp;
     int bad = 0;
     for (unsigned e = tid; e < nw; e += blockDim.x) {
-      const double l = lb[e], h = hb[e];
+      const double l = bounded.lb[e], h = bounded.hb[e];
       if (!box_bounded(l, h)) continue;
-      const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-      const size_t oz = (size_t)k * rows + n + j;
-      pvb[e] = vb[e];
-      pyb[e] = yb[e];
+      const size_t oz = box_entry_offset(d, e);
+      pvb[e] = V.vb[e];
+      pyb[e] = V.yb[e];
       int s = start;
       double tl = Tr[(size_t)s * nw + e], corr = 0.0;
 #pragma unroll
@@ -312,9 +255,9 @@ __global__ __launch_bounds__(256) void box_update_accel(Dims d, int it, int adap
       if (!isfinite(wn)) bad = 1;
       const double vn = fmin(fmax(wn, l), h);
       const double yn = wn - vn;
-      vb[e] = vn;
-      yb[e] = yn;
-      rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, rho);
+      V.vb[e] = vn;
+      V.yb[e] = yn;
+      V.rn[oz] = box_rhs_entry<STRICT>(V.rs[oz], vn, yn, rho);
     }
     bad = __syncthreads_or(bad);
     if (tid == 0) {
@@ -332,34 +275,17 @@ __global__ __launch_bounds__(256) void box_update_accel(Dims d, int it, int adap
   }
   if (mode == 3 || mode == 4) {  // rejected (or w+ not finite): the saved plain v+, y+ again
     for (unsigned e = tid; e < nw; e += blockDim.x) {
-      if (!box_bounded(lb[e], hb[e])) continue;
-      const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-      const size_t oz = (size_t)k * rows + n + j;
+      if (!bounded(e)) continue;
+      const size_t oz = box_entry_offset(d, e);
       const double vs = pvb[e], ys = pyb[e];
-      vb[e] = vs;
-      yb[e] = ys;
-      rn[oz] = box_rhs_entry<STRICT>(rs[oz], vs, ys, rho);
+      V.vb[e] = vs;
+      V.yb[e] = ys;
+      V.rn[oz] = box_rhs_entry<STRICT>(V.rs[oz], vs, ys, rho);
     }
     return;
   }
-  if (mode == 2) {  // a new penalty: y rescaled, the next right-hand side from it (same entry -> thread map as above)
-    const double rho_new = rho_s, s = rho / rho_new;
-    for (unsigned e = tid; e < nw; e += blockDim.x) {
-      if (!box_bounded(lb[e], hb[e])) continue;
-      const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-      const size_t oz = (size_t)k * rows + n + j;
-      const double ys = yb[e] * s;
-      yb[e] = ys;
-      rn[oz] = box_rhs_entry<STRICT>(rs[oz], vb[e], ys, rho_new);
-    }
-    return;
-  }
-  for (unsigned e = tid; e < nw; e += blockDim.x) {  // frozen: the next right-hand side is the current one
-    if (!box_bounded(lb[e], hb[e])) continue;
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-    const size_t oz = (size_t)k * rows + n + j;
-    rn[oz] = rc[oz];
-  }
+  if (mode == 2) box_tail_new_penalty<STRICT>(d, V, rho, rho_s, tid, bounded);
+  else box_tail_frozen(d, V, tid, bounded);
 }
 
 }  // namespace ndlqr

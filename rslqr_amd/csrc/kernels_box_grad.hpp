@@ -63,9 +63,10 @@ __global__ void box_adjoint_start(Dims d, const double* __restrict__ rhov, const
   }
 }
 
-// One ADMM update of the box adjoint for every running problem after re-solve `it`: box_update (kernels_box.hpp) with
-// lo = hi = 0 on the fixed entries and the identity for the clip of the split ones -- same convergence test, freezing,
-// NaN handling and running count. v holds the split entries' projected iterate, y the fixed entries' scaled dual.
+// One ADMM update of the box adjoint for every running problem after re-solve `it`: the shared core of kernels_box.hpp
+// (box_step, box_judge, box_tail_frozen) over the entries whose code is not BOX_UNBOUNDED, with its own clip: to [0, 0]
+// on the fixed entries, the identity -- not a clip to +-inf, which would drop a NaN -- on the split ones. v holds the
+// split entries' projected iterate, y the fixed entries' scaled dual; rho is the forward's final penalty (no adapting).
 //   grid (batch), block 256.
 template <bool STRICT>
 __global__ __launch_bounds__(256) void box_adjoint_update(Dims d, int it, BoxParams P, const double* __restrict__ z,
@@ -79,79 +80,26 @@ __global__ __launch_bounds__(256) void box_adjoint_update(Dims d, int it, BoxPar
   __shared__ int conv_s;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (status[b] != 0) return;  // frozen (uniform over the workgroup)
-  const double rho = rhov[b];  // (the forward's final penalty of this problem: the adjoint does not adapt)
-  const int w = d.w, n = d.n, rows = d.rows;
-  const unsigned nw = (unsigned)(d.N * w);
-  const unsigned char* cb = code + (size_t)b * nw;
-  double* vb = v + (size_t)b * nw;
-  double* yb = y + (size_t)b * nw;
-  const double* zb = z + (size_t)b * d.N * rows;
-  const double* rs = res + (size_t)b * d.N * rows;
-  const double* rc = rhs_cur + (size_t)b * d.N * rows;
-  double* rn = rhs_next + (size_t)b * d.N * rows;
-  double rp = 0.0, rd = 0.0, zm = 0.0, vm = 0.0, ym = 0.0;
-  for (unsigned e = tid; e < nw; e += blockDim.x) {
+  const double rho = rhov[b];
+  const BoxViews V(d, b, z, v, y, res, rhs_cur, rhs_next);
+  const unsigned char* cb = code + (size_t)b * V.nw;
+  BoxMaxima M;
+  for (unsigned e = tid; e < V.nw; e += blockDim.x) {
     const unsigned char c = cb[e];
     if (c == BOX_UNBOUNDED) continue;
     const bool fixed = c != BOX_SPLIT;
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-    const size_t oz = (size_t)k * rows + n + j;
-    const double zi = zb[oz];
-    const double v0 = fixed ? 0.0 : vb[e], y0 = fixed ? yb[e] : 0.0;
-    double zh;
-    if constexpr (STRICT) {
-      const double a = P.alpha * zi;
-      const double cc = P.oma * v0;
-      zh = a + cc;
-    } else {
-      zh = fma(P.alpha, zi, P.oma * v0);
-    }
-    const double t = zh + y0;
-    const double vn = fixed ? fmin(fmax(t, 0.0), 0.0) : t;
-    const double yn = (y0 + zh) - vn;
-    if (fixed) yb[e] = yn;
-    else vb[e] = vn;  // (yn is +0 exactly: y of a split entry is never stored)
-    rn[oz] = box_rhs_entry<STRICT>(rs[oz], vn, yn, rho);
-    rp = max_nan(rp, fabs(zi - vn));
-    rd = max_nan(rd, fabs(vn - v0));
-    zm = max_nan(zm, fabs(zi));
-    vm = max_nan(vm, fabs(vn));
-    ym = max_nan(ym, fabs(yn));
+    const size_t oz = box_entry_offset(d, e);
+    const double zi = V.zb[oz], v0 = fixed ? 0.0 : V.vb[e], y0 = fixed ? V.yb[e] : 0.0;
+    const BoxStep s = box_step<STRICT>(P, zi, v0, y0, fixed, 0.0, 0.0);
+    if (fixed) V.yb[e] = s.yn;
+    else V.vb[e] = s.vn;  // (yn is +0 exactly: y of a split entry is never stored)
+    V.rn[oz] = box_rhs_entry<STRICT>(V.rs[oz], s.vn, s.yn, rho);
+    M.note(zi, v0, s.vn, s.yn);
   }
-  red[0][tid] = rp; red[1][tid] = rd; red[2][tid] = zm; red[3][tid] = vm; red[4][tid] = ym;
+  M.reduce(red, tid);
+  if (tid == 0) conv_s = box_judge(P, rho, red, b, it, status, iters, resid, running).frozen;
   __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s)
-      for (int q = 0; q < 5; ++q) red[q][tid] = max_nan(red[q][tid], red[q][tid + s]);
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const double r_prim = red[0][0], r_dual = rho * red[1][0];
-    const double sp = max_nan(red[2][0], red[3][0]), sd = rho * red[4][0];
-    const double tol_p = P.eps_abs + P.eps_rel * sp;
-    const double tol_d = P.eps_abs + P.eps_rel * sd;
-    const bool finite = isfinite(r_prim) && isfinite(r_dual) && isfinite(red[2][0]) && isfinite(red[3][0]) &&
-                        isfinite(red[4][0]);
-    const int conv = finite && r_prim <= tol_p && r_dual <= tol_d;
-    iters[b] = it;
-    resid[4 * (size_t)b] = r_prim;  // the read-out (ndlqr_CopyBatchBoxAdjointResiduals)
-    resid[4 * (size_t)b + 1] = r_dual;
-    resid[4 * (size_t)b + 2] = sp;
-    resid[4 * (size_t)b + 3] = sd;
-    if (conv || !finite) {
-      status[b] = conv ? 1 : 3;
-      atomicSub(running, 1);
-    }
-    conv_s = conv || !finite;
-  }
-  __syncthreads();
-  if (!conv_s) return;
-  for (unsigned e = tid; e < nw; e += blockDim.x) {  // frozen: the next right-hand side is the current one
-    if (cb[e] == BOX_UNBOUNDED) continue;
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-    const size_t oz = (size_t)k * rows + n + j;
-    rn[oz] = rc[oz];
-  }
+  if (conv_s) box_tail_frozen(d, V, tid, [=](unsigned e) { return cb[e] != BOX_UNBOUNDED; });
 }
 
 // End of a box adjoint, in place on the adjoint solution z (the last re-solve): x, u of the bounded entries become v

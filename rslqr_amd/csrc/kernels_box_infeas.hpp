@@ -131,11 +131,10 @@ static __global__ __launch_bounds__(256) void box_certify(Dims d, int it, double
   __syncthreads();
   if (!found_s) return;
   for (unsigned e = tid; e < (unsigned)(N * w); e += blockDim.x) {
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
     const bool bounded = box_bounded(lb[e], hb[e]);
     cert_mu[ov + e] = bounded ? rho * y[ov + e] - rho_prev * yp[ov + e] : 0.0;
     if (bounded) {
-      const size_t at = oz + (size_t)k * rows + n + j;
+      const size_t at = oz + box_entry_offset(d, e);
       rhs_cur[at] = rhs_next[at];
     }
   }

@@ -212,7 +212,7 @@ static __global__ __launch_bounds__(256) void polish_validate(Dims d, int final,
   const int b = blockIdx.x, tid = threadIdx.x;
   const int st = state[b];
   if (st != POLISH_RUNNING && st != POLISH_STOPPED) return;  // (uniform over the workgroup)
-  const int rows = d.rows, n = d.n, w = d.w;
+  const int rows = d.rows, w = d.w;
   const unsigned nw = (unsigned)(d.N * w);
   const size_t oz = (size_t)b * d.N * rows, ov = (size_t)b * nw;
   const double* lb = lo + (size_t)b * bstride;
@@ -223,8 +223,7 @@ static __global__ __launch_bounds__(256) void polish_validate(Dims d, int final,
   for (unsigned e = tid; e < nw; e += blockDim.x) {
     const unsigned char cd = code[ov + e];
     if (cd == 0) continue;
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-    const double l = lb[e], h = hb[e], m = mu[ov + e], zi = z[oz + (size_t)k * rows + n + j];
+    const double l = lb[e], h = hb[e], m = mu[ov + e], zi = z[oz + box_entry_offset(d, e)];
     if (cd == 3) bad |= (l < h && m < 0.0);
     else if (cd == 2) bad |= (m > 0.0);
     else bad |= (zi > h || zi < l);
@@ -244,8 +243,7 @@ static __global__ __launch_bounds__(256) void polish_validate(Dims d, int final,
   for (unsigned e = tid; e < nw; e += blockDim.x) {
     const unsigned char cd = code[ov + e];
     if (cd == 0) continue;
-    const unsigned k = e / (unsigned)w, j = e - k * (unsigned)w;
-    const size_t at = oz + (size_t)k * rows + n + j;
+    const size_t at = oz + box_entry_offset(d, e);
     const double l = lb[e], h = hb[e], m = mu[ov + e], zi = z[at];
     unsigned char nc = cd;
     if ((cd == 3 && l < h && m < 0.0) || (cd == 2 && m > 0.0)) nc = 1;
