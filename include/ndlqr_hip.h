@@ -4,7 +4,9 @@
  * Plain pointers and sizes only. This is the device boundary that SURVEY.md (section 1) inserts
  * between the reference's L2 driver (src/solve.c) and its L1/L0 numerics
  * (src/nested_dissection.c, src/linalg_custom.c): everything behind these calls runs on
- * gfx950. Implemented in rslqr_amd/csrc/ndlqr_hip.hip.
+ * gfx950. Implemented in rslqr_amd/csrc: the context, the solve pipeline and the downloads in ndlqr_hip.hip, each
+ * optional feature in a unit of its own (hip_grad.hip: adjoint and gradients, hip_box.hip: bounds, ADMM, polish,
+ * hip_refine.hip, hip_cost.hip: dense costs, hip_dense.hip: the Matrix* helpers).
  *
  * Device data model (all fp64):
  *   inputs  AB  [batch][N][n][n+m]   row i of knot k = [A_k(i,:) | B_k(i,:)]   (A,B row-major)

@@ -4,7 +4,7 @@
  * New relative to the reference (which solves one problem per ndlqr_Solve call and
  * parallelises inside it, src/solve.c:50-183): a batch axis of independent problems is the
  * unit of GPU parallelism. This file only packs caller data into the device input layout of
- * ndlqr_hip.h and drives the shim; all numerics are in ndlqr_hip.hip.
+ * ndlqr_hip.h and drives the shim; all numerics are in the HIP units (ndlqr_hip.hip, hip_*.hip).
  *
  * Packing = the data movement of ndlqr_InitializeWithLQRProblem (src/solver.c:122-194) without
  * materialising the zero-padded `data` array: A_k, B_k go in row-major (which is exactly the

@@ -1,5 +1,6 @@
 // hip_context.hpp -- internal: the device context behind NdlqrHipCtx* and the launch-profiling
-// helper, shared by ndlqr_hip.hip and the per-size translation units (small_instance.hip).
+// helper, shared by every unit of the HIP host layer: the core (ndlqr_hip.hip), the feature units (hip_*.hip; what they
+// share beyond the context: hip_host.hpp) and the per-instance units (small_instance.hip, reduced_instance.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,9 +19,11 @@
 
 // records the message for ndlqr_hip_last_error(), prints it, returns NDLQR_ERR_NO_DEVICE (or
 // NDLQR_ERR_INVALID for a rejected launch configuration / argument)
+#pragma GCC visibility push(hidden)
 int ndlqr_hip_fail(const char* what, hipError_t e);
 struct NdlqrHipCtx;
 int ndlqr_hip_ensure_F(NdlqrHipCtx* c);
+#pragma GCC visibility pop
 #define HIP_TRY(expr)                                                  \
   do {                                                                 \
     hipError_t e_ = (expr);                                            \
@@ -180,8 +183,9 @@ struct BufferSet {
 // ------------------------------------------------------------------------------ one struct per feature
 // The state of an optional feature: its buffers with their layout, its bookkeeping, and one ensure() that names the
 // buffers and their sizes once (d: the device layout, st: the stream a zero-fill is ordered on). The entry point that
-// first needs the feature calls it; the buffers go with the context. A new feature adds its struct here, a member to
-// NdlqrHipCtx and the ensure() call to its entry points -- nothing else.
+// first needs the feature calls it; the buffers go with the context. A new feature adds its struct here with a member in
+// NdlqrHipCtx, its kernels_<feature>.hpp, its unit hip_<feature>.hip with the entry points (which call ensure()) and one
+// line in HIP_UNITS of rslqr_amd/build.py -- nothing else, and nothing in the core unit ("Units").
 
 // Developer switches of the environment, read once when the context is created (read_knobs, ndlqr_hip.hip)
 struct DevKnobs {

@@ -22,7 +22,7 @@
 
 #include "kernels_box.hpp"
 #include "kernels_common.hpp"
-#include "kernels_refine.hpp"
+#include "kernels_dd.hpp"
 
 namespace ndlqr {
 

@@ -67,6 +67,16 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// accumulator tile of v_mfma_f64_16x16x4_f64 (fragment layout: kernels_mfma.hpp)
+typedef double mfma_acc_t __attribute__((ext_vector_type(4)));
+
+// Four k-steps of a tile product: acc += A B with the operand fragments already in registers.
+__device__ __forceinline__ mfma_acc_t mfma4(const double (&a)[4], const double (&b)[4], mfma_acc_t acc) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b[q], acc, 0, 0, 0);
+  return acc;
+}
+
 // Developer instrumentation (tools/segtime.py; never defined in the shipped build): cycles spent
 // between consecutive marks, summed over lane 0 of every wavefront, per segment id.
 #ifdef NDLQR_SEGTIME

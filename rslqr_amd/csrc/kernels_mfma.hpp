@@ -15,8 +15,6 @@
 
 namespace ndlqr {
 
-typedef double mfma_acc_t __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------- shared phases
 // Geometry of a separator workgroup: S-bar / L / W in LDS with row pitch ns = n + 1, ONE chunk of the
 // right-hand-side panel with row pitch xs, the inverses of the 16x16 diagonal blocks of L (pitch 17).
@@ -25,13 +23,6 @@ struct SepGeom {
   int lane, wave, nwave, li, lk;
 };
 constexpr int kSepMaxPanelTiles = 3;  // panel tiles a wavefront may own: tiles * CT <= 3 nwave (checked on the host)
-
-// Four k-steps of a tile product: acc += A B with the operand fragments already in registers.
-__device__ __forceinline__ mfma_acc_t mfma4(const double (&a)[4], const double (&b)[4], mfma_acc_t acc) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b[q], acc, 0, 0, 0);
-  return acc;
-}
 
 // acc += sum_{kb = kb0}^{kb1 - 1} A_kb B_kb (16 x 16 blocks, four k-steps each); load(kb, a, b) fetches the
 // operand fragments of block kb from LDS. The fragments of block kb + 1 are requested before the products

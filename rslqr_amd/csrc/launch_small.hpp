@@ -1,5 +1,5 @@
 // launch_small.hpp -- internal: launch sequences of the size-specialised kernels and the table entry
-// (SmallInstance) ndlqr_hip.hip reaches them through, instantiated once per (nstates, ninputs) in its own
+// (SmallInstance) the core unit, ndlqr_hip.hip, reaches them through, instantiated once per (nstates, ninputs) in its own
 // translation unit (small_instance.hip) so that the instances compile in parallel.
 #pragma once
 #include "hip_context.hpp"

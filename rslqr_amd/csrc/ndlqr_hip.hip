@@ -1,25 +1,20 @@
-// ndlqr_hip.hip -- gfx950 (MI355X, CDNA4) implementation of the device boundary in
-// include/ndlqr_hip.h: context/memory management, launch sequence, D2H converters and the
-// dense Matrix* helpers. Kernels live in kernels_generic.hpp (any n, m) and kernels_small.hpp
-// (size-specialised, one knot row per lane).
+// ndlqr_hip.hip -- gfx950 (MI355X, CDNA4) implementation of the device boundary in include/ndlqr_hip.h, the core
+// unit: errors, context and memory management, the two-deep pipeline, uploads and packing, the SolvePlan and the launch
+// sequences of the three kernel families, staged solve, time shard, steps and slices, rhs-only and multi-rhs re-solves,
+// synchronisation, profile and downloads. Its kernels: kernels_generic.hpp, kernels_mfma.hpp (any n, m), the re-solve
+// and back-substitution of kernels_reduced_solve.hpp; the size-specialised family is instantiated per block size in
+// small_instance.hip (launch_small.hpp) and the separators of the runtime-sized separator-only family per tile count
+// in reduced_instance.hip (launch_reduced.hpp). The optional features have a unit each (hip_grad.hip, hip_box.hip,
+// hip_refine.hip, hip_cost.hip, hip_dense.hip); hip_host.hpp declares what they share with this one.
 //
 // Written for wave64 / gfx950 only; built with -ffp-contract=off so that every fused
 // multiply-add in the kernels is an explicit fma() (fast mode) or an explicit mul + add
 // (NDLQR_FLAG_STRICT_FP, which reproduces the reference's default CPU build bit for bit).
-#include <mutex>
-
-#include "hip_context.hpp"
+#include "hip_host.hpp"
 #include "kernels_generic.hpp"
-#include "kernels_box.hpp"
-#include "kernels_box_grad.hpp"
-#include "kernels_box_accel.hpp"
-#include "kernels_box_infeas.hpp"
-#include "kernels_box_polish.hpp"
-#include "kernels_cost.hpp"
-#include "kernels_grad.hpp"
-#include "kernels_refine.hpp"
 #include "kernels_mfma.hpp"
-#include "kernels_reduced_mfma.hpp"
+#include "launch_reduced.hpp"        // (ReducedInstance; its templates are instantiated in reduced_instance.hip)
+#include "kernels_reduced_solve.hpp"
 #include "launch_small.hpp"  // (SmallInstance; its templates are instantiated in small_instance.hip)
 
 // ------------------------------------------------------------------------------ errors
@@ -36,9 +31,9 @@ int ndlqr_hip_fail(const char* what, hipError_t e) {
   if (e == hipErrorInvalidConfiguration || e == hipErrorInvalidValue) return NDLQR_ERR_INVALID;
   return NDLQR_ERR_NO_DEVICE;
 }
-static int fail(const char* what, hipError_t e) { return ndlqr_hip_fail(what, e); }
+int fail(const char* what, hipError_t e) { return ndlqr_hip_fail(what, e); }
 // records the message for ndlqr_hip_last_error(), prints it, returns NDLQR_ERR_INVALID
-static int refuse(const std::string& msg) {
+int refuse(const std::string& msg) {
   g_last_error = msg;
   fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
   return NDLQR_ERR_INVALID;
@@ -46,7 +41,7 @@ static int refuse(const std::string& msg) {
 
 // Padded horizon (ndlqr_hip_create_ex): an entry point that is not carried through refuses here -- it would index the
 // caller's arrays, which have du.N knots, with the device's d.N
-static int need_unpadded_horizon(const NdlqrHipCtx* c, const char* who) {
+int need_unpadded_horizon(const NdlqrHipCtx* c, const char* who) {
   if (c->du.N == c->d.N) return NDLQR_OK;
   return refuse(std::string(who) + ": not available for a padded horizon (horizon " + std::to_string(c->du.N) +
                 " runs as " + std::to_string(c->d.N) + " knots); use a power-of-two horizon");
@@ -55,59 +50,13 @@ static int need_unpadded_horizon(const NdlqrHipCtx* c, const char* who) {
 // Dense-cost mode (ndlqr_hip_init_dense): the resident problem is the unit-cost reduction of the
 // caller's. An entry point that is not carried through refuses here -- the rows, records and arrays it would work on are
 // those of the reduced system
-static int need_diagonal_cost(const NdlqrHipCtx* c, const char* who) {
+int need_diagonal_cost(const NdlqrHipCtx* c, const char* who) {
   if (!c->cost.dense) return NDLQR_OK;
   return refuse(std::string(who) + ": not available in dense-cost mode (the resident problem is the unit-cost reduction "
                 "ndlqr_InitializeBatchFlatDense left); use a diagonal initialiser");
 }
 
-// one launch of a kernel of kernels_cost.hpp: a wavefront per (knot, problem) of `count` problems
-template <class... Params, class... Args>
-static hipError_t launch_cost(void (*kernel)(Params...), size_t lds_doubles, const ndlqr::Dims& u, unsigned count, hipStream_t st,
-                              Args... args) {
-  const size_t lds = sizeof(double) * lds_doubles;
-  const hipError_t e = allow_dynamic_lds(kernel, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kernel, dim3(u.N, count), dim3(64), lds, st, static_cast<Params>(args)...);
-  return hipGetLastError();
-}
-// Under NDLQR_FLAG_PROFILE: HIP events around the launches of one phase of the reduction (CostState::phase_ms[which]);
-// stop() waits for them, so a profiled call is synchronous. Without the flag nothing is recorded.
-struct CostPhase {
-  NdlqrHipCtx* c;
-  hipStream_t st;
-  int which;
-  hipEvent_t a = nullptr, b = nullptr;
-  CostPhase(NdlqrHipCtx* ctx, hipStream_t stream, int phase) : c(ctx), st(stream), which(phase) {
-    if (!(c->flags & NDLQR_FLAG_PROFILE)) return;
-    a = take_event(c); b = take_event(c);
-    (void)hipEventRecord(a, st);
-  }
-  void stop() {
-    if (!a) return;
-    float ms = 0.0f;
-    if (hipEventRecord(b, st) == hipSuccess && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess)
-      c->cost.phase_ms[which] = ms;
-    c->event_pool.push_back(a);
-    c->event_pool.push_back(b);
-    a = b = nullptr;
-  }
-};
-// dense-cost mode: `vec`, the packed [count][nvars] vectors of problems [p0, p0 + count) in the reduced variables, becomes
-// the same in the caller's (S, in place)
-static hipError_t cost_map_back(NdlqrHipCtx* c, double* vec, int p0, unsigned count, hipStream_t st) {
-  const ndlqr::Dims& u = c->du;
-  CostPhase phase(c, st, 2);
-  const hipError_t e = launch_cost(ndlqr::cost_apply, ndlqr::cost_apply_lds(u.n, u.m), u, count, st, u.n, u.m, u.N,
-                                   c->cost.rec + (size_t)p0 * u.N * CostState::record_doubles(u), vec);
-  phase.stop();
-  return e;
-}
-
-// Where a caller's array lives. A pointer the runtime does not know (an ordinary malloc'ed one is "invalid value" to older
-// runtimes) is pageable host memory.
-enum class Where { Pageable, Pinned, OwnDevice, OtherDevice };
-static Where where(const void* p, int device) {
+Where where(const void* p, int device) {
   hipPointerAttribute_t a;
   if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return Where::Pageable; }
   if (a.type == hipMemoryTypeDevice) return a.device == device ? Where::OwnDevice : Where::OtherDevice;
@@ -122,10 +71,45 @@ int ndlqr_hip_device_count(void) {
 
 static const char* kSlotNames[SLOT_COUNT] = {"leaf", "separator", "schur", "schur_boundary", "apply", "bottom", "upper", "top"};
 
-static bool has_small_instance(int nstates, int ninputs);  // defined with the instance table below
-static void pick_pad_instance(int nstates, int ninputs, int* pn, int* pm);
+// ---- size-specialised instances: one translation unit each (small_instance.hip), listed in
+//      small_instances.def; developer builds with NDLQR_SINGLE_TU (tools/segtime.py) hold every instance here
+#ifdef NDLQR_SINGLE_TU
+#define NDLQR_SMALL_INSTANCE(NX_, NU_) static const SmallInstance NDLQR_SMALL_NAME(NX_, NU_) = make_small_instance<NX_, NU_>();
+#else
+#define NDLQR_SMALL_INSTANCE(NX_, NU_) extern const SmallInstance NDLQR_SMALL_NAME(NX_, NU_);
+#endif
+#include "small_instances.def"
+#undef NDLQR_SMALL_INSTANCE
 
-static size_t bytes_QR(const ndlqr::Dims& d) { return sizeof(double) * doubles_QR(d); }
+static const SmallInstance* const kSmallInstances[] = {
+#define NDLQR_SMALL_INSTANCE(NX_, NU_) &NDLQR_SMALL_NAME(NX_, NU_),
+#include "small_instances.def"
+#undef NDLQR_SMALL_INSTANCE
+};
+
+static bool has_small_instance(int nstates, int ninputs) {
+  for (const SmallInstance* s : kSmallInstances)
+    if (s->nx == nstates && s->nu == ninputs) return true;
+  return false;
+}
+
+// cheapest instance (with a matrix-core path: six states or more) that contains the block size; *pn, *pm untouched
+// when there is none
+static void pick_pad_instance(int nstates, int ninputs, int* pn, int* pm) {
+  long best = -1;
+  for (const SmallInstance* si : kSmallInstances) {
+    if (si->nx < nstates || si->nu < ninputs || si->nx < 6) continue;
+    const long cost = (long)si->nx * si->nx * (si->nx + si->nu);
+    if (best < 0 || cost < best) { best = cost; *pn = si->nx; *pm = si->nu; }
+  }
+}
+
+static const SmallInstance* find_small(const ndlqr::Dims& d) {
+  for (const SmallInstance* s : kSmallInstances)
+    if (s->nx == d.n && s->nu == d.m) return s;
+  return nullptr;
+}
+
 static size_t bytes_z(const ndlqr::Dims& d) { return sizeof(double) * doubles_z(d); }
 static size_t bytes_F(const ndlqr::Dims& d) { return sizeof(double) * doubles_F(d); }
 
@@ -282,7 +266,7 @@ void ndlqr_hip_destroy(NdlqrHipCtx* c) {
 
 // the current buffer set holds the most recent solution -- all of it, or (a step with NDLQR_SOLN_ONLY) the knots of the
 // workgroups its back-substitution ran
-static void note_solution(NdlqrHipCtx* c) {
+void note_solution(NdlqrHipCtx* c) {
   ++c->soln_gen;  // (an adjoint of an earlier solution no longer applies)
   c->latest = c->cur;
   c->z_partial = c->apply_nblk > 0;
@@ -298,7 +282,7 @@ static void next_solve_on_current_set(NdlqrHipCtx* c) {
   if ((c->solve_count & 1u) != (unsigned)c->cur) ++c->solve_count;
 }
 // consumers of the whole solution vector refuse a slice
-static int need_full_solution(const NdlqrHipCtx* c, const char* who) {
+int need_full_solution(const NdlqrHipCtx* c, const char* who) {
   if (c->z_invalid)
     return refuse(std::string(who) + ": the last constrained solve failed; there is no resident solution until the next solve");
   if (!c->z_partial) return NDLQR_OK;
@@ -339,14 +323,12 @@ static bool ensure_alt(NdlqrHipCtx* c) {
 }
 
 // every solve in flight on either set has finished
-static hipError_t sync_all(NdlqrHipCtx* c) {
+hipError_t sync_all(NdlqrHipCtx* c) {
   hipError_t e = hipSuccess;
   for (const BufferSet& s : c->set)
     if (s.stream) { const hipError_t e2 = hipStreamSynchronize(s.stream); if (e == hipSuccess) e = e2; }
   return e;
 }
-
-static int rhs_make_current(NdlqrHipCtx* c, unsigned need);  // below
 
 int ndlqr_hip_set_pipeline_depth(NdlqrHipCtx* c, int depth) {
   if (!c || depth < 1) return NDLQR_ERR_INVALID;
@@ -422,11 +404,16 @@ static void rhs_written_cur(NdlqrHipCtx* c, unsigned mask) {
   for (int p = 0; p < 4; ++p)
     if (mask & (1u << p)) c->set[c->cur].rhs_gen[p] = ++c->rhs_latest[p];
 }
+// everything is idle and the current set's whole right-hand side has just been rewritten
+void note_new_rhs(NdlqrHipCtx* c) {
+  rhs_written_cur(c, 0xFu);
+  next_solve_on_current_set(c);
+}
 // rhs_make_current: the current set's copy is brought up to date in the parts of `need` before a solve reads it. Only a
 // change of flow gets here with something to do (full MPC steps followed by x0-only steps, a plain solve behind steps,
 // the first solve on the other set after an upload): everything in flight is waited for, the stale parts are copied
 // from the other set on this set's stream, and the other set's stream waits for that copy before it may rewrite its own.
-static int rhs_make_current(NdlqrHipCtx* c, unsigned need) {
+int rhs_make_current(NdlqrHipCtx* c, unsigned need) {
   BufferSet& s = c->set[c->cur];
   const BufferSet& o = c->set[1 - c->cur];
   unsigned stale = 0;
@@ -551,14 +538,6 @@ constexpr int kSepChunkTiles = 3;  // column tiles of the right-hand-side panel 
 
 // Separator-only schedule for blocks that fill 16x16 matrix-core tiles (kernels_reduced_mfma.hpp): workgroup
 // size and LDS of separator_reduced_mfma, or false when the shape does not qualify (-> generic-lean).
-struct ReducedGenericPlan {
-  bool ok;
-  int threads;
-  size_t lds;
-  int nb;    // 16 x 16 tiles per block row
-  bool pad;  // the block does not fill them
-  bool keep; // NDLQR_FLAG_KEEP_RECORDS
-};
 static ReducedGenericPlan plan_reduced_generic(const NdlqrHipCtx* c) {
   const ndlqr::Dims& d = c->d;
   ReducedGenericPlan p = {false, 0, 0, 0, false, false};
@@ -569,13 +548,11 @@ static ReducedGenericPlan plan_reduced_generic(const NdlqrHipCtx* c) {
   const int npad = 16 * p.nb, wpad = (d.w + 3) / 4 * 4;
   p.pad = npad != d.n || wpad != d.w;  // blocks that do not fill their tiles: zero-padded in LDS (PAD instances)
   // one wavefront per 16x16 block where the weights fit its lanes: many small workgroups fill the chip better than
-  // a four-wavefront workgroup whose phases are mostly serial at this size
-  // a wavefront per 16-column tile where the weights fit the lanes ("two rounds", kernels_reduced_mfma.hpp: small
-  // workgroups, three or more of them per CU), else twice that
-  p.threads = wpad <= 64 * p.nb ? 64 * p.nb : (p.nb >= 3 ? 512 : 256);
-  if (wpad > p.threads) return p;  // one weight / rhs entry per thread
-  if (p.nb >= 5 && p.threads != 64 * p.nb) return p;  // (beyond 64 states the second panel array does not fit the LDS)
-  p.lds = sizeof(double) * (size_t)ndlqr::reduced_lds_doubles(npad, wpad, p.threads == 64 * p.nb);
+  // a four-wavefront workgroup whose phases are mostly serial at this size; else the wider form, where there is one
+  // (kReducedThreads, launch_reduced.hpp)
+  p.threads = wpad <= kReducedThreads[p.nb][0] ? kReducedThreads[p.nb][0] : kReducedThreads[p.nb][1];
+  if (wpad > p.threads) return p;  // one weight / rhs entry per thread (0: no wider form beyond 64 states)
+  p.lds = sizeof(double) * (size_t)ndlqr::reduced_lds_doubles(npad, wpad, p.threads == kReducedThreads[p.nb][0]);
   if (p.lds > kLdsMax) return p;
   p.ok = true;
   return p;
@@ -645,54 +622,27 @@ static void launch_backsub_reduced_generic(NdlqrHipCtx* c, const double* rhs, do
                      lds, s.stream, d0, c->AB, c->QR, rhs, s.rec, z);
 }
 
+// ---- the separator launch of every tile count: one translation unit each (reduced_instance.hip); developer builds with
+//      NDLQR_SINGLE_TU (tools/segtime.py) hold every instance here
+#ifdef NDLQR_SINGLE_TU
+#define NDLQR_REDUCED_INSTANCE(NB_) static const ReducedInstance NDLQR_REDUCED_NAME(NB_) = make_reduced_instance<NB_>();
+#else
+#define NDLQR_REDUCED_INSTANCE(NB_) extern const ReducedInstance NDLQR_REDUCED_NAME(NB_) __attribute__((visibility("hidden")));
+#endif
+NDLQR_REDUCED_INSTANCES
+#undef NDLQR_REDUCED_INSTANCE
+static const ReducedInstance* const kReducedInstances[kReducedMaxNB + 1] = {nullptr,
+#define NDLQR_REDUCED_INSTANCE(NB_) &NDLQR_REDUCED_NAME(NB_),
+    NDLQR_REDUCED_INSTANCES
+#undef NDLQR_REDUCED_INSTANCE
+};
+
 static int launch_reduced_generic(NdlqrHipCtx* c, const ReducedGenericPlan& p) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   for (int l = 0; l < d.K; ++l) {
     ScopedSlot t(c, SLOT_SEP);
-    const dim3 grid(d.N >> (l + 1), d.batch);
-#define NDLQR_LAUNCH_SEP2(NB_, NT_, L0_, PAD_)                                                                     \
-  hipLaunchKernelGGL((ndlqr::separator_reduced_mfma<NB_, NT_, L0_, PAD_>), grid, dim3(NT_), p.lds, s.stream, d, l, \
-                     c->AB, c->QR, s.rhs, s.red, s.rec, c->info)
-#define NDLQR_LAUNCH_SEP(NB_, NT_)                                          \
-  do {                                                                      \
-    if (l == 0 && p.pad) NDLQR_LAUNCH_SEP2(NB_, NT_, true, true);           \
-    else if (l == 0) NDLQR_LAUNCH_SEP2(NB_, NT_, true, false);              \
-    else if (p.pad) NDLQR_LAUNCH_SEP2(NB_, NT_, false, true);               \
-    else NDLQR_LAUNCH_SEP2(NB_, NT_, false, false);                         \
-  } while (0)
-    switch (p.nb) {
-      case 1:
-        if (p.threads == 64) NDLQR_LAUNCH_SEP(1, 64);
-        else NDLQR_LAUNCH_SEP(1, 256);
-        break;
-      case 2:
-        if (p.threads == 128) NDLQR_LAUNCH_SEP(2, 128);
-        else NDLQR_LAUNCH_SEP(2, 256);
-        break;
-      case 3:
-        if (p.threads == 192) NDLQR_LAUNCH_SEP(3, 192);
-        else NDLQR_LAUNCH_SEP(3, 512);
-        break;
-      case 4:
-        if (p.threads == 256) NDLQR_LAUNCH_SEP(4, 256);
-        else NDLQR_LAUNCH_SEP(4, 512);
-        break;
-      case 5:  // (beyond 64 states: one workgroup per CU, the form with one wavefront per tile column only)
-        NDLQR_LAUNCH_SEP(5, 320);
-        break;
-      case 6:
-        NDLQR_LAUNCH_SEP(6, 384);
-        break;
-      case 7:
-        NDLQR_LAUNCH_SEP(7, 448);
-        break;
-      default:
-        NDLQR_LAUNCH_SEP(8, 512);
-        break;
-    }
-#undef NDLQR_LAUNCH_SEP2
-#undef NDLQR_LAUNCH_SEP
+    kReducedInstances[p.nb]->separator(c, p, l);
   }
   launch_backsub_reduced_generic(c, s.rhs, s.z);
   return NDLQR_OK;
@@ -849,45 +799,6 @@ static int launch_generic(NdlqrHipCtx* c, const SolvePlan& plan) {
                        c->AB, c->QR, s.rhs, s.z);
   }
   return NDLQR_OK;
-}
-
-// ---- size-specialised instances: one translation unit each (small_instance.hip), listed in
-//      small_instances.def; developer builds with NDLQR_SINGLE_TU (tools/segtime.py) hold every instance here
-#ifdef NDLQR_SINGLE_TU
-#define NDLQR_SMALL_INSTANCE(NX_, NU_) static const SmallInstance NDLQR_SMALL_NAME(NX_, NU_) = make_small_instance<NX_, NU_>();
-#else
-#define NDLQR_SMALL_INSTANCE(NX_, NU_) extern const SmallInstance NDLQR_SMALL_NAME(NX_, NU_);
-#endif
-#include "small_instances.def"
-#undef NDLQR_SMALL_INSTANCE
-
-static const SmallInstance* const kSmallInstances[] = {
-#define NDLQR_SMALL_INSTANCE(NX_, NU_) &NDLQR_SMALL_NAME(NX_, NU_),
-#include "small_instances.def"
-#undef NDLQR_SMALL_INSTANCE
-};
-
-static bool has_small_instance(int nstates, int ninputs) {
-  for (const SmallInstance* s : kSmallInstances)
-    if (s->nx == nstates && s->nu == ninputs) return true;
-  return false;
-}
-
-// cheapest instance (with a matrix-core path: six states or more) that contains the block size; *pn, *pm untouched
-// when there is none
-static void pick_pad_instance(int nstates, int ninputs, int* pn, int* pm) {
-  long best = -1;
-  for (const SmallInstance* si : kSmallInstances) {
-    if (si->nx < nstates || si->nu < ninputs || si->nx < 6) continue;
-    const long cost = (long)si->nx * si->nx * (si->nx + si->nu);
-    if (best < 0 || cost < best) { best = cost; *pn = si->nx; *pm = si->nu; }
-  }
-}
-
-static const SmallInstance* find_small(const ndlqr::Dims& d) {
-  for (const SmallInstance* s : kSmallInstances)
-    if (s->nx == d.n && s->nu == d.m) return s;
-  return nullptr;
 }
 
 // the size-specialised instance that serves this context (nullptr: runtime-sized kernels)
@@ -1237,8 +1148,8 @@ int ndlqr_hip_time_shard_finish(NdlqrHipCtx* c, int g, int G) { return time_shar
 
 // Packs the solutions of `count` problems from the blocks [count][N][2n+m] at z into dst: the whole vectors [count][nvars],
 // or the slice `sel` [count][nknots][width]. u: the caller's block sizes, d: the device layout.
-static hipError_t launch_pack(const ndlqr::Dims& u, const ndlqr::Dims& d, const KnotSlice& sel, const double* z, double* dst,
-                              hipStream_t st, unsigned count) {
+hipError_t launch_pack(const ndlqr::Dims& u, const ndlqr::Dims& d, const KnotSlice& sel, const double* z, double* dst,
+                       hipStream_t st, unsigned count) {
   if (sel.nknots > 0)
     hipLaunchKernelGGL(ndlqr::pack_selection_generic, dim3(sel.nknots, count), dim3(64), 0, st, u, d, sel.knot0, sel.nknots,
                        sel.blocks & 7u, z, dst);
@@ -1256,6 +1167,61 @@ static int deliver(const ndlqr::Dims& u, const ndlqr::Dims& d, const KnotSlice& 
   return NDLQR_OK;
 }
 
+// the factor-array sweep of a re-solve: right-hand side `rhs`, solution into `z`
+template <bool STRICT>
+static void launch_rhs_sweep(NdlqrHipCtx* c, const double* rhs, double* z) {
+  const ndlqr::Dims& d = c->d;
+  BufferSet& s = c->set[c->cur];
+  {
+    ScopedSlot t(c, SLOT_LEAF);
+    hipLaunchKernelGGL((ndlqr::rhs_leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(64), 0, s.stream, d, c->QR,
+                       rhs, z);
+  }
+  for (int l = 0; l < d.K; ++l) {
+    {
+      ScopedSlot t(c, SLOT_SEP);
+      const size_t lds_staged = sizeof(double) * ((size_t)d.n * (d.n + 1) + d.n);
+      const int staged = lds_staged <= kLdsMax ? 1 : 0;
+      hipLaunchKernelGGL((ndlqr::rhs_separator_generic<STRICT>), dim3(d.N >> (l + 1), d.batch), dim3(64),
+                         staged ? lds_staged : sizeof(double) * (size_t)d.n, s.stream, d, l, c->AB, c->F, z, staged);
+    }
+    {
+      ScopedSlot t(c, SLOT_SCHUR);
+      const int work = d.N * d.rows;
+      hipLaunchKernelGGL((ndlqr::rhs_update_generic<STRICT>), dim3((work + 255) / 256, d.batch), dim3(256), 0,
+                         s.stream, d, l, c->F, z);
+    }
+  }
+}
+
+// the record-based re-solve where the kept records have one, by the kernels of the family that wrote them: right-hand
+// side `rhs`, solution into `z`
+static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
+  const ndlqr::Dims& d = c->d;
+  if (!c->kept.rec_complete || (c->flags & NDLQR_FLAG_STRICT_FP)) return false;
+  if (c->kept.family == Family::GenericReduced) {  // records + slots + W of every separator
+    launch_rhs_reduced_generic(c, rhs, z);
+    return true;
+  }
+  const SmallInstance* inst = kept_instance(c);
+  if (!inst) return false;
+  // (the full-record forms: sweep array of rhs_forward_upper within the default dynamic LDS, backsub_small's K + 4
+  //  separators of nx rows in one workgroup; the compact form -- rb_forward / rb_forward_top -- was checked by its plan)
+  if (!c->kept.rec_compact && (d.N < 8 || (size_t)(d.N / 8) * d.n * sizeof(double) > 60 * 1024 || (d.K + 4) * inst->nx > 256))
+    return false;
+  inst->rhs(c, rhs, z);
+  return true;
+}
+
+// the re-solve on what the last factorisation kept: the records where they have one, else the factor array; refused with
+// `refusal` when there are records only and this shape / horizon has no record-based re-solve
+int launch_resolve(NdlqrHipCtx* c, const double* rhs, double* z, const char* refusal) {
+  if (try_launch_rhs_records(c, rhs, z)) return NDLQR_OK;
+  if (!c->kept.fact_valid) return refuse(refusal);
+  if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c, rhs, z); else launch_rhs_sweep<false>(c, rhs, z);
+  return NDLQR_OK;
+}
+
 // While in scope, the last launch of the back-substitution runs only the workgroups (eight knots each) that hold the knots
 // of `sel` (launch_small.hpp: apply_grid / apply_dims; schedules without that launch compute everything); an empty slice,
 // or `on` false, leaves it whole.
@@ -1269,7 +1235,16 @@ struct ApplySlice {
   ~ApplySlice() { c->apply_blk0 = c->apply_nblk = 0; }
 };
 
-static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z);  // below
+// the flat q, r, d, x0 (this device's memory, or a device-side view of pinned memory; null: a part that is not replaced)
+// packed into the current set's right-hand side, on its stream
+hipError_t launch_pack_rhs(NdlqrHipCtx* c, const double* q, const double* r, const double* d, const double* x0) {
+  BufferSet& s = c->set[c->cur];
+  if (c->du.N != c->d.N)  // (a padded horizon: the per-entry guards)
+    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<true>, dim3(512), dim3(256), 0, s.stream, c->du, c->d, q, r, d, x0, s.rhs.get());
+  else
+    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<false>, dim3(512), dim3(256), 0, s.stream, c->du, c->d, q, r, d, x0, s.rhs.get());
+  return hipGetLastError();
+}
 
 int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const double* dd, const double* x0,
                          double* soln) {
@@ -1311,13 +1286,7 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
     }
     stage += cnt[k];
   }
-  if (u.N != d.N)  // (a padded horizon: the per-entry guards)
-    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<true>, dim3(512), dim3(256), 0, st, u, d, view[0], view[1], view[2],
-                       view[3], s.rhs);
-  else
-    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<false>, dim3(512), dim3(256), 0, st, u, d, view[0], view[1], view[2],
-                       view[3], s.rhs);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_pack_rhs(c, view[0], view[1], view[2], view[3]));
   rhs_written_cur(c, written);
   // NDLQR_SOLN_ONLY: nothing but the selected knots is wanted
   const ApplySlice apply_slice(c, c->sel, (c->sel.blocks & NDLQR_SOLN_ONLY) != 0);
@@ -1483,63 +1452,7 @@ int ndlqr_hip_upload_rhs(NdlqrHipCtx* c, int p0, int count, const double* rhs) {
     HIP_TRY(hipMemcpyAsync(s.rhs + p0 * sz, rhs, sizeof(double) * sz * count, hipMemcpyHostToDevice, s.stream));
   }
   HIP_TRY(hipStreamSynchronize(s.stream));
-  rhs_written_cur(c, 0xFu);
-  next_solve_on_current_set(c);
-  return NDLQR_OK;
-}
-
-// the factor-array sweep of a re-solve: right-hand side `rhs`, solution into `z`
-template <bool STRICT>
-static void launch_rhs_sweep(NdlqrHipCtx* c, const double* rhs, double* z) {
-  const ndlqr::Dims& d = c->d;
-  BufferSet& s = c->set[c->cur];
-  {
-    ScopedSlot t(c, SLOT_LEAF);
-    hipLaunchKernelGGL((ndlqr::rhs_leaf_generic<STRICT>), dim3(d.N, d.batch), dim3(64), 0, s.stream, d, c->QR,
-                       rhs, z);
-  }
-  for (int l = 0; l < d.K; ++l) {
-    {
-      ScopedSlot t(c, SLOT_SEP);
-      const size_t lds_staged = sizeof(double) * ((size_t)d.n * (d.n + 1) + d.n);
-      const int staged = lds_staged <= kLdsMax ? 1 : 0;
-      hipLaunchKernelGGL((ndlqr::rhs_separator_generic<STRICT>), dim3(d.N >> (l + 1), d.batch), dim3(64),
-                         staged ? lds_staged : sizeof(double) * (size_t)d.n, s.stream, d, l, c->AB, c->F, z, staged);
-    }
-    {
-      ScopedSlot t(c, SLOT_SCHUR);
-      const int work = d.N * d.rows;
-      hipLaunchKernelGGL((ndlqr::rhs_update_generic<STRICT>), dim3((work + 255) / 256, d.batch), dim3(256), 0,
-                         s.stream, d, l, c->F, z);
-    }
-  }
-}
-
-// the record-based re-solve where the kept records have one, by the kernels of the family that wrote them: right-hand
-// side `rhs`, solution into `z`
-static bool try_launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
-  const ndlqr::Dims& d = c->d;
-  if (!c->kept.rec_complete || (c->flags & NDLQR_FLAG_STRICT_FP)) return false;
-  if (c->kept.family == Family::GenericReduced) {  // records + slots + W of every separator
-    launch_rhs_reduced_generic(c, rhs, z);
-    return true;
-  }
-  const SmallInstance* inst = kept_instance(c);
-  if (!inst) return false;
-  // (the full-record forms: sweep array of rhs_forward_upper within the default dynamic LDS, backsub_small's K + 4
-  //  separators of nx rows in one workgroup; the compact form -- rb_forward / rb_forward_top -- was checked by its plan)
-  if (!c->kept.rec_compact && (d.N < 8 || (size_t)(d.N / 8) * d.n * sizeof(double) > 60 * 1024 || (d.K + 4) * inst->nx > 256))
-    return false;
-  inst->rhs(c, rhs, z);
-  return true;
-}
-
-// the re-solve on what the last factorisation kept: the records where they have one, else the factor array; refused with
-// `refusal` when there are records only and this shape / horizon has no record-based re-solve
-static int launch_resolve(NdlqrHipCtx* c, const double* rhs, double* z, const char* refusal) {
-  if (try_launch_rhs_records(c, rhs, z)) return NDLQR_OK;
-  if (!c->kept.fact_valid) return refuse(refusal);
-  if (c->flags & NDLQR_FLAG_STRICT_FP) launch_rhs_sweep<true>(c, rhs, z); else launch_rhs_sweep<false>(c, rhs, z);
+  note_new_rhs(c);
   return NDLQR_OK;
 }
 
@@ -1566,189 +1479,10 @@ int ndlqr_hip_solve_rhs_async(NdlqrHipCtx* c) {
   return NDLQR_OK;
 }
 
-// ------------------------------------------------------------------------------ adjoint solve, parameter gradients
-// The caller's arrays: this device's memory is taken as it is, host memory (pinned or pageable) is staged through HBM, and
-// another device's memory is refused (the caller has the wrong device, and a silent copy would hide it).
-
-// K arrays of the caller, cnt[k] doubles each (null: absent), and their way through grad_stage. In this order: classify();
-// grad_stage.grow for `stage` doubles plus whatever the caller wants behind them; sync_all; place(), which fills dev[] --
-// what the kernels get -- and returns the first free double; copy(st, true) before the launches that read inputs, or
-// copy(st, false) behind those that wrote outputs.
-template <int K>
-struct CallerArrays {
-  double* user[K];
-  size_t cnt[K];
-  bool own[K] = {};  // this device's memory: read or written by the kernels as it is
-  double* dev[K] = {};
-  size_t stage = 0;  // doubles to stage
-  // `who`: the API function, `what`: "an output lies", ... -- the refusal reads "who: what in the memory of another device ..."
-  int classify(const NdlqrHipCtx* c, const char* who, const char* what) {
-    for (int k = 0; k < K; ++k) {
-      if (!user[k]) continue;
-      const Where w = where(user[k], c->device);
-      if (w == Where::OtherDevice)
-        return refuse(std::string(who) + ": " + what + " in the memory of another device than the solver's");
-      own[k] = w == Where::OwnDevice;
-      if (!own[k]) stage += cnt[k];
-    }
-    return NDLQR_OK;
-  }
-  double* place(const NdlqrHipCtx* c) {
-    double* at = c->grad_stage;
-    for (int k = 0; k < K; ++k) {
-      if (!user[k]) continue;
-      dev[k] = own[k] ? user[k] : at;
-      if (!own[k]) at += cnt[k];
-    }
-    return at;
-  }
-  int copy(hipStream_t st, bool in) {
-    for (int k = 0; k < K; ++k)
-      if (user[k] && !own[k])
-        HIP_TRY(hipMemcpyAsync(in ? dev[k] : user[k], in ? user[k] : dev[k], sizeof(double) * cnt[k], hipMemcpyDefault, st));
-    return NDLQR_OK;
-  }
-};
-
-// ------------------------------------------------------------------------------ dense cost matrices
-// Layered ABOVE the plain entry points: the dense-cost problem is reduced on the device to a unit-cost problem of the same
-// shape (kernels_cost.hpp), whose flat arrays -- device-resident, in the caller's layout -- go to ndlqr_hip_pack_flat_device
-// and the right-hand-side pack kernel like any caller's. The solve kernels, their schedules and captured graphs never
-// learn of it; solutions and adjoints are mapped back where they are packed for the caller (cost_map_back).
-
-// S' of the flat right-hand side at q, r, d, x0 (device) into the reduced flat arrays, on `st`
-static hipError_t cost_reduce_rhs(NdlqrHipCtx* c, const double* q, const double* r, const double* d, const double* x0,
-                                  hipStream_t st) {
-  const ndlqr::Dims& u = c->du;
-  CostState& k = c->cost;
-  CostPhase phase(c, st, 1);
-  const hipError_t e = launch_cost(ndlqr::cost_apply_t, ndlqr::cost_apply_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N,
-                                   k.rec.get(), q, r, d, x0, nullptr, k.qt.get(), k.rt.get(), k.dt.get(), k.x0t.get(), nullptr);
-  phase.stop();
-  return e;
-}
-
-int ndlqr_hip_init_dense(NdlqrHipCtx* c, const double* A, const double* B, const double* Q, const double* H, const double* R,
-                         const double* q, const double* r, const double* d, const double* x0) {
-  if (!c || !A || !B || !Q || !R || !q || !r || !d || !x0) return NDLQR_ERR_INVALID;
-  const ndlqr::Dims& u = c->du;
-  const size_t lds = sizeof(double) * ndlqr::cost_transform_lds(u.n, u.m);
-  if (lds > kLdsMax)
-    return refuse("ndlqr_hip_init_dense: cost_transform stages " + std::to_string(lds) + " bytes per knot at (" +
-                  std::to_string(u.n) + "," + std::to_string(u.m) + "), beyond the " + std::to_string(kLdsMax) +
-                  " bytes of LDS of a workgroup");
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t kn = (size_t)u.batch * u.N, n = (size_t)u.n, m = (size_t)u.m;
-  CallerArrays<9> ca = {{const_cast<double*>(A), const_cast<double*>(B), const_cast<double*>(Q), const_cast<double*>(H),
-                         const_cast<double*>(R), const_cast<double*>(q), const_cast<double*>(r), const_cast<double*>(d),
-                         const_cast<double*>(x0)},
-                        {kn * n * n, kn * n * m, kn * n * n, kn * n * m, kn * m * m, kn * n, kn * m, kn * n, (size_t)u.batch * n}};
-  int err = ca.classify(c, "ndlqr_hip_init_dense", "an input lies");
-  if (err) return err;
-  HIP_TRY(sync_all(c));  // solves in flight still read the inputs (and the staging)
-  CostState& k = c->cost;
-  const bool fresh = !k.ones;
-  HIP_TRY(k.ensure(u));
-  HIP_TRY(c->grad_stage.grow(ca.stage));
-  ca.place(c);
-  const hipStream_t st = c->set[c->cur].stream;
-  err = ca.copy(st, true);
-  if (err) return err;
-  if (fresh) {
-    hipLaunchKernelGGL(ndlqr::cost_fill, dim3(256), dim3(256), 0, st, k.ones.get(), kn * (n + m), 1.0);
-    HIP_TRY(hipGetLastError());
-  }
-  {
-    CostPhase phase(c, st, 0);
-    HIP_TRY(launch_cost(ndlqr::cost_factor, ndlqr::cost_factor_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, u.batch, ca.dev[2],
-                        ca.dev[3], ca.dev[4], k.rec.get(), c->info.get()));
-    HIP_TRY(launch_cost(ndlqr::cost_transform, ndlqr::cost_transform_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, ca.dev[0],
-                        ca.dev[1], k.rec.get(), k.At.get(), k.Bt.get()));
-    phase.stop();
-  }
-  HIP_TRY(cost_reduce_rhs(c, ca.dev[5], ca.dev[6], ca.dev[7], ca.dev[8], st));
-  // (waits for the stream first: the caller's arrays and the staging are free again when this returns)
-  err = ndlqr_hip_pack_flat_device(c, k.At, k.Bt, k.ones, k.ones + kn * n, k.qt, k.rt, k.dt, k.x0t);
-  if (err) return err;
-  k.dense = true;
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_cost_is_dense(const NdlqrHipCtx* c) { return c && c->cost.dense ? 1 : 0; }
-int ndlqr_hip_cost_phase_ms(NdlqrHipCtx* c, double* out3) {
-  if (!c || !out3) return NDLQR_ERR_INVALID;
-  for (int i = 0; i < 3; ++i) out3[i] = c->cost.phase_ms[i];
-  return NDLQR_OK;
-}
-
-// ndlqr_BatchSetRhsFlat in dense-cost mode: flat q, r, d, x0 in the caller's variables (host, pinned or this device's
-// memory) -> S' -> the resident right-hand side of the reduced problem
-int ndlqr_hip_set_rhs_dense(NdlqrHipCtx* c, const double* q, const double* r, const double* d, const double* x0) {
-  if (!c || !q || !r || !d || !x0) return NDLQR_ERR_INVALID;
-  if (!c->cost.dense) return refuse("ndlqr_hip_set_rhs_dense: the solver is not in dense-cost mode");
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t kn = (size_t)u.batch * u.N;
-  CallerArrays<4> ca = {{const_cast<double*>(q), const_cast<double*>(r), const_cast<double*>(d), const_cast<double*>(x0)},
-                        {kn * u.n, kn * u.m, kn * u.n, (size_t)u.batch * u.n}};
-  int err = ca.classify(c, "ndlqr_hip_set_rhs_dense", "an input lies");
-  if (err) return err;
-  HIP_TRY(sync_all(c));
-  HIP_TRY(c->grad_stage.grow(ca.stage));
-  ca.place(c);
-  BufferSet& s = c->set[c->cur];
-  err = ca.copy(s.stream, true);
-  if (err) return err;
-  HIP_TRY(cost_reduce_rhs(c, ca.dev[0], ca.dev[1], ca.dev[2], ca.dev[3], s.stream));
-  const CostState& k = c->cost;
-  if (u.N != c->d.N)
-    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<true>, dim3(512), dim3(256), 0, s.stream, u, c->d, (const double*)k.qt,
-                       (const double*)k.rt, (const double*)k.dt, (const double*)k.x0t, s.rhs.get());
-  else
-    hipLaunchKernelGGL(ndlqr::pack_rhs_stream_generic<false>, dim3(512), dim3(256), 0, s.stream, u, c->d, (const double*)k.qt,
-                       (const double*)k.rt, (const double*)k.dt, (const double*)k.x0t, s.rhs.get());
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  rhs_written_cur(c, 0xFu);
-  next_solve_on_current_set(c);
-  return NDLQR_OK;
-}
-
-// Read-out for the tests: the records and the reduced problem in the caller's flat layout, each [batch][N][..] (x0t
-// [batch][n]) into HOST memory; any pointer may be null. L [n*n], LR [m*m], G [m*n] column-major.
-int ndlqr_hip_download_cost_reduction(NdlqrHipCtx* c, double* L, double* LR, double* G, double* At, double* Bt, double* qt,
-                                      double* rt, double* dt, double* x0t) {
-  if (!c) return NDLQR_ERR_INVALID;
-  if (!c->cost.dense) return refuse("ndlqr_hip_download_cost_reduction: the solver is not in dense-cost mode");
-  const ndlqr::Dims& u = c->du;
-  const CostState& k = c->cost;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(sync_all(c));
-  const size_t kn = (size_t)u.batch * u.N, n = (size_t)u.n, m = (size_t)u.m, recd = CostState::record_doubles(u);
-  double* const part[3] = {L, LR, G};
-  const size_t width[3] = {n * n, m * m, m * n};
-  size_t off = 0;
-  for (int i = 0; i < 3; off += width[i], ++i)
-    if (part[i])
-      HIP_TRY(hipMemcpy2D(part[i], sizeof(double) * width[i], k.rec + off, sizeof(double) * recd, sizeof(double) * width[i], kn,
-                          hipMemcpyDeviceToHost));
-  double* const dst[6] = {At, Bt, qt, rt, dt, x0t};
-  const double* const src[6] = {k.At, k.Bt, k.qt, k.rt, k.dt, k.x0t};
-  const size_t cnt[6] = {kn * n * n, kn * n * m, kn * n, kn * m, kn * n, (size_t)u.batch * n};
-  for (int i = 0; i < 6; ++i)
-    if (dst[i]) HIP_TRY(hipMemcpy(dst[i], src[i], sizeof(double) * cnt[i], hipMemcpyDeviceToHost));
-  return NDLQR_OK;
-}
-
-// KERNEL<true> under NDLQR_FLAG_STRICT_FP, KERNEL<false> otherwise: one argument list for both
-#define launch_strict(strict, KERNEL, grid, block, lds, stream, ...)                            \
-  do {                                                                                          \
-    if (strict) hipLaunchKernelGGL(KERNEL<true>, grid, block, lds, stream, __VA_ARGS__);        \
-    else hipLaunchKernelGGL(KERNEL<false>, grid, block, lds, stream, __VA_ARGS__);              \
-  } while (0)
+// ------------------------------------------------------------------------------ services of the feature units (hip_host.hpp)
 
 // the device time between the events of the (synchronised) set, for ndlqr_hip_last_solve_ms
-static void note_elapsed(NdlqrHipCtx* c, const BufferSet& s) {
+void note_elapsed(NdlqrHipCtx* c, const BufferSet& s) {
   float ms = 0.0f;
   if (hipEventElapsedTime(&ms, s.ev_start, s.ev_stop) == hipSuccess) c->last_ms = ms;
 }
@@ -1757,7 +1491,7 @@ static void note_elapsed(NdlqrHipCtx* c, const BufferSet& s) {
 // of every record) and, on the runtime-sized schedule, into the slots (gL | gR). Every re-solve recomputes those before
 // it reads them; the adjoint solve still leaves them as it found them: saved before, restored after (2 n doubles per
 // knot instead of the whole records).
-static hipError_t adjoint_scratch(NdlqrHipCtx* c, bool restore) {
+hipError_t adjoint_scratch(NdlqrHipCtx* c, bool restore) {
   const ndlqr::Dims& d = c->d;
   const BufferSet& s = c->set[0];
   const size_t col = sizeof(double) * d.n, rows = (size_t)d.batch * d.N;
@@ -1774,58 +1508,8 @@ static hipError_t adjoint_scratch(NdlqrHipCtx* c, bool restore) {
                  : hipMemcpy2DAsync(save, 2 * col, slot_g, slot_pitch, 2 * col, nslots, hipMemcpyDeviceToDevice, s.stream);
 }
 
-int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
-  if (!c || !g) return NDLQR_ERR_INVALID;
-  if (!c->kept.fact_valid && !c->kept.rec_complete)
-    return refuse("adjoint solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
-                  "factorisation) of the resident inputs");
-  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_adjoint");
-  if (c->kept.time_shard) return refuse("adjoint solve: not available on a time-axis shard");
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->cost.dense) {  // g~ = S' g in the staging vector, which then is the adjoint's g
-    const size_t count = ((size_t)u.rows * u.N - u.m) * d.batch;
-    if (where(g, c->device) == Where::OtherDevice)
-      return refuse("ndlqr_hip_solve_adjoint: g lies in the memory of another device than the solver's");
-    HIP_TRY(sync_all(c));
-    const hipStream_t st = c->set[0].stream;
-    HIP_TRY(hipMemcpyAsync(c->cost.stage, g, sizeof(double) * count, hipMemcpyDefault, st));
-    HIP_TRY(launch_cost(ndlqr::cost_apply_t, ndlqr::cost_apply_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, c->cost.rec.get(),
-                        nullptr, nullptr, nullptr, nullptr, c->cost.stage.get(), nullptr, nullptr, nullptr, nullptr,
-                        c->cost.stage.get()));
-    g = c->cost.stage;
-  }
-  CallerArrays<1> ga = {{const_cast<double*>(g)}, {((size_t)u.rows * u.N - u.m) * d.batch}};
-  int err = ga.classify(c, "ndlqr_hip_solve_adjoint", "g lies");
-  if (err) return err;
-  HIP_TRY(sync_all(c));
-  c->cur = 0;  // cached records / factors live in the primary set
-  BufferSet& s = c->set[0];
-  HIP_TRY(c->adj.ensure(d, s.stream));
-  HIP_TRY(c->grad_stage.grow(ga.stage));
-  ga.place(c);
-  err = ga.copy(s.stream, true);
-  if (err) return err;
-  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)ga.dev[0],
-                     c->adj.rhs);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(adjoint_scratch(c, false));
-  err = launch_resolve(c, c->adj.rhs, c->adj.z,
-                       "adjoint solve: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
-  if (err) return err;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(adjoint_scratch(c, true));
-  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  note_elapsed(c, s);
-  c->adj.gen = c->soln_gen;
-  return NDLQR_OK;
-}
-
 // is there an adjoint of the resident solution of the resident inputs?
-static int need_adjoint(const NdlqrHipCtx* c, const char* who) {
+int need_adjoint(const NdlqrHipCtx* c, const char* who) {
   if (c->z_partial || c->z_invalid) return need_full_solution(c, who);
   if (c->adj.gen == 0 || c->adj.gen != c->soln_gen)
     return refuse(std::string(who) + ": no adjoint of the resident solution (ndlqr_hip_solve_adjoint after the latest solve)");
@@ -1833,178 +1517,10 @@ static int need_adjoint(const NdlqrHipCtx* c, const char* who) {
   return NDLQR_OK;
 }
 
-static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count, double* soln);  // below
-
-int ndlqr_hip_download_adjoint(NdlqrHipCtx* c, double* w) {
-  if (!c || !w) return NDLQR_ERR_INVALID;
-  const int aerr = need_adjoint(c, "ndlqr_hip_download_adjoint");
-  if (aerr) return aerr;
-  HIP_TRY(hipSetDevice(c->device));
-  const Where ww = where(w, c->device);
-  if (ww == Where::OtherDevice) return refuse("ndlqr_hip_download_adjoint: w lies in the memory of another device than the solver's");
-  if (ww != Where::OwnDevice) return download_packed(c, c->adj.z, 0, c->d.batch, w);
-  const BufferSet& s = c->set[0];
-  HIP_TRY(sync_all(c));
-  HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->adj.z, w, s.stream, c->d.batch));
-  if (c->cost.dense) HIP_TRY(cost_map_back(c, w, 0, c->d.batch, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_gradients(NdlqrHipCtx* c, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR, double* gq,
-                        double* gr, double* gd, double* gx0) {
-  if (!c || (sum_mask & ~0xFFu)) return NDLQR_ERR_INVALID;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_gradients")) return cerr;
-  const int aerr = need_adjoint(c, "ndlqr_hip_gradients");
-  if (aerr) return aerr;
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  CallerArrays<ndlqr::GRAD_COUNT> ga = {{gA, gB, gQ, gR, gq, gr, gd, gx0}, {}};
-  double* const* user = ga.user;
-  size_t total = 0;
-  ndlqr::GradOut out = {};
-  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) {
-    if (!user[o]) continue;
-    const bool summed = (sum_mask >> o) & 1u;
-    const size_t per = o == ndlqr::GRAD_x0 ? (size_t)u.n : (size_t)u.N * ndlqr::grad_width(u, o);
-    ga.cnt[o] = summed ? per : per * d.batch;
-    if (summed) { out.off[o] = total; total += per; }
-  }
-  int err = ga.classify(c, "ndlqr_hip_gradients", "an output lies");
-  if (err) return err;
-  out.sum = sum_mask;
-  out.total = total;
-  // chunk of knots per workgroup: the accumulators of its summed outputs and its z | w blocks within 48 KB of LDS where
-  // they fit (one knot of the batch-summed gA at 128 states is 128 KB)
-  int wsum = 0;
-  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o)
-    if (user[o] && ((sum_mask >> o) & 1u)) wsum += ndlqr::grad_width(u, o);
-  int KC = 8;
-  while (KC > 1 && (KC > d.N || sizeof(double) * ((size_t)KC * wsum + 2 * (size_t)(KC + 1) * d.rows) > 48 * 1024)) KC >>= 1;
-  const size_t lds_max = kLdsMax / sizeof(double), zw = 2 * (size_t)(KC + 1) * d.rows, nacc = (size_t)KC * wsum;
-  if (zw >= lds_max)
-    return refuse("ndlqr_hip_gradients: z and w of two knots of this block size exceed the LDS of a workgroup");
-  // where the accumulators of one knot do not fit beside z | w (a batch-summed gA from about 139 states on), they are
-  // spread over nslice workgroups of EC entries each (a third grid dimension); one slice otherwise
-  int nslice = (int)((nacc + (lds_max - zw) - 1) / (lds_max - zw));
-  if (nslice < 1) nslice = 1;
-  const size_t EC = (nacc + nslice - 1) / nslice;
-  const size_t lds = sizeof(double) * (EC + zw);
-  const int nchunks = d.N / KC;
-  // problems per workgroup row: one without batch sums; with them, about 2048 workgroups in all (the split sums meet in
-  // a second, ordered pass)
-  int ppb = 1, nsplit = d.batch;
-  if (total > 0) {
-    nsplit = 2048 / (nchunks * nslice);
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > d.batch) nsplit = d.batch;
-    while (nsplit > 1 && (size_t)nsplit * total > ((size_t)64 << 20)) nsplit >>= 1;  // partial sums within 512 MB
-    ppb = (d.batch + nsplit - 1) / nsplit;
-    nsplit = (d.batch + ppb - 1) / ppb;
-  }
-  const size_t npart = nsplit > 1 ? (size_t)nsplit * total : 0;
-  HIP_TRY(c->grad_stage.grow(ga.stage + npart));
-  HIP_TRY(sync_all(c));
-  BufferSet& s = c->set[0];
-  double* part = ga.place(c);  // (the partial sums behind the staged outputs)
-  if (!npart) part = nullptr;
-  for (int o = 0; o < ndlqr::GRAD_COUNT; ++o) out.p[o] = ga.dev[o];
-  const double* z = c->set[c->latest].z;
-  const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
-  HIP_TRY(strict ? allow_dynamic_lds(&ndlqr::grad_assemble<true>, lds) : allow_dynamic_lds(&ndlqr::grad_assemble<false>, lds));
-  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  launch_strict(strict, ndlqr::grad_assemble, dim3(nchunks, nsplit, nslice), dim3(256), lds, s.stream, u, d, KC, ppb, (int)EC,
-                z, (const double*)c->adj.z, out, part);
-  HIP_TRY(hipGetLastError());
-  if (part) {
-    hipLaunchKernelGGL(ndlqr::grad_sum_splits, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s.stream, out, nsplit,
-                       (const double*)part);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  err = ga.copy(s.stream, false);
-  if (err) return err;
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  note_elapsed(c, s);
-  return NDLQR_OK;
-}
-
-// ------------------------------------------------------------------------------ box-constrained solve (ADMM)
-// Scaled ADMM with a fixed penalty on the kept factorisation (kernels_box.hpp): QR is shifted by
-// rho M in place -- the pointers, and with them the captured launch chain of the primary set, stay valid, and every record
-// re-solve reads the shifted diagonal --, factored once (or not at all while the remembered shifted factorisation still
-// applies), and every iteration is one re-solve into box.z plus one box_update; the host reads the running count every
-// check_every iterations. The penalty is a device vector, box.rho [batch]. With adapt_every > 0
-// box_update may move a problem's penalty at every adapt_every-th iteration; the host then reads the count of changed
-// problems next to the running count and, when it is not zero, restores QR, shifts it by the new vector and factors the
-// whole batch again -- one factorisation serves every problem that changed in that round.
-// Infeasibility detection (ndlqr_hip_set_box_infeasibility, kernels_box_infeas.hpp): with a check
-// period set, the iteration before a check leaves copies of z, y and rho behind its box_update, and the check iteration
-// runs box_certify behind its own: a certified problem (status 4) leaves the running count like a converged one.
-// Anderson acceleration (ndlqr_hip_set_box_acceleration, kernels_box_accel.hpp): with a memory
-// set, box_update_accel takes the place of box_update in the loop; the iteration before an infeasibility check and the
-// check iteration take plain steps.
-
-
-// Bounds in the caller's layout, [P][N][n] and [P][N][m] with P = batch, or P = 1 (shared): this device's memory is read
-// as it is, host memory is staged through HBM. Checked (lo <= hi for every used entry) before anything is replaced.
-int ndlqr_hip_set_bounds(NdlqrHipCtx* c, int shared, const double* xlo, const double* xhi, const double* ulo,
-                         const double* uhi) {
-  if (!c) return NDLQR_ERR_INVALID;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_set_bounds")) return cerr;
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  const int P = shared ? 1 : d.batch;
-  const size_t nx = (size_t)P * u.N * u.n, nu = (size_t)P * u.N * u.m;
-  CallerArrays<4> in = {{const_cast<double*>(xlo), const_cast<double*>(xhi), const_cast<double*>(ulo), const_cast<double*>(uhi)},
-                        {nx, nx, nu, nu}};
-  int err = in.classify(c, "ndlqr_hip_set_bounds", "bounds lie");
-  if (err) return err;
-  BufferSet& s = c->set[0];
-  HIP_TRY(c->grad_stage.grow(in.stage));
-  HIP_TRY(c->box.ensure(d, s.stream));
-  HIP_TRY(sync_all(c));  // (a solve in flight may still read the bounds)
-  in.place(c);
-  err = in.copy(s.stream, true);
-  if (err) return err;
-  const double* const* view = in.dev;
-  HIP_TRY(hipMemsetAsync(c->box.word, 0, 4 * sizeof(int), s.stream));
-  hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 0,
-                     c->box.lo, c->box.hi, c->box.mask, c->box.word + 2, c->box.word + 3);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(c->box.h_word, c->box.word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  if (c->box.h_word[2]) return refuse("ndlqr_hip_set_bounds: a lower bound exceeds its upper bound (or is NaN)");
-  // the pattern lives in mask per problem: shared bounds are compared against problem 0's row of it, so a change between
-  // shared and per-problem bounds always counts as a new pattern
-  hipLaunchKernelGGL(ndlqr::box_bounds, dim3(d.N, P), dim3(64), 0, s.stream, u, d, view[0], view[1], view[2], view[3], 1,
-                     c->box.lo, c->box.hi, c->box.mask, c->box.word + 2, c->box.word + 3);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(c->box.h_word, c->box.word, 4 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  if (c->box.h_word[3] || (bool)shared != c->box.shared || !c->box.have_bounds) c->box.fact = false;
-  c->pol.fact = false;  // (the polish belongs to the bounds it ran with)
-  c->pol.soln_gen = 0;
-  c->box.soln_gen = 0;  // (a box adjoint needs the constrained solution of these bounds)
-  c->box.shared = shared != 0;
-  c->box.bstride = shared ? 0 : (size_t)d.N * d.w;
-  c->box.have_bounds = true;
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_solve_box(NdlqrHipCtx* c, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
-                        int check_every, int warm_start, int* iters, int* status) {
-  return ndlqr_hip_solve_box_ex(c, rho, alpha, eps_abs, eps_rel, max_iter, check_every, warm_start, iters, status, 0, 1e-6,
-                                1e6);
-}
-
-// The shifted matrix factored on the primary set as a plain solve does it (the resident solution is overwritten), with
+// What is resident factored on the primary set as a plain solve does it (the resident solution is overwritten), with
 // the pivot check: *not_spd = NDLQR_ERR_NOT_SPD, which is returned, when a pivot was not positive.
-// (who, what: the entry point and the shifted matrix, for the message)
-static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd, const char* who = "ndlqr_hip_solve_box",
-                      const char* what = "Q + rho M, R + rho M") {
+// (who, what: the entry point and the matrix, for the message)
+int factor_resident(NdlqrHipCtx* c, hipStream_t st, int* not_spd, const char* who, const char* what) {
   c->forget_shifted();
   SolvePlan plan;
   int err = prepare_solve(c, &plan);  // (KEEP_*: stream-ordered on the primary set)
@@ -2012,7 +1528,7 @@ static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd, const char* 
   if (err) return err;
   c->state_dirty = false;
   HIP_TRY(hipStreamSynchronize(st));
-  // a non-positive pivot of the shifted factorisation (e.g. Q or R <= 0 on an unbounded entry): no iterations
+  // a non-positive pivot (of a shifted factorisation: e.g. Q or R <= 0 on an unbounded entry)
   int seen = 0;
   for (const BufferSet& b : c->set)
     if (b.h_fail && *b.h_fail > seen) seen = *b.h_fail;
@@ -2025,67 +1541,8 @@ static int box_factor(NdlqrHipCtx* c, hipStream_t st, int* not_spd, const char* 
   return NDLQR_OK;
 }
 
-// QR shifted by rho M in place, with the flags of the shifted factorisation instead of the caller's and, once the caller has
-// put it there, its kept state instead of the plain API's: from open() to close(). A scope left without close() (an early
-// return) restores the same. Everything is enqueued on the primary set's stream.
-struct ShiftedQR {
-  NdlqrHipCtx* c;
-  const unsigned user_flags;
-  bool open_ = false, columns_saved = false;
-  explicit ShiftedQR(NdlqrHipCtx* ctx) : c(ctx), user_flags(ctx->flags) {}
-  ShiftedQR(const ShiftedQR&) = delete;
-  ~ShiftedQR() { (void)close(); }
-  int shift(const double* rho) {
-    const ndlqr::Dims& d = c->d;
-    hipLaunchKernelGGL(ndlqr::box_shift_qr, dim3(d.N, d.batch), dim3(64), 0, c->set[0].stream, d, rho, (const double*)c->box.lo,
-                       (const double*)c->box.hi, c->box.bstride, c->QR);
-    HIP_TRY(hipGetLastError());
-    return NDLQR_OK;
-  }
-  // QR saved, c->flags = flags; the caller shifts (the polish: by sigma on its active entries)
-  int open_unshifted(unsigned flags) {
-    HIP_TRY(hipMemcpyAsync(c->box.qr_save, c->QR, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
-    open_ = true;
-    c->flags = flags;
-    return NDLQR_OK;
-  }
-  // the saved QR again
-  int restore() {
-    HIP_TRY(hipMemcpyAsync(c->QR, c->box.qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream));
-    return NDLQR_OK;
-  }
-  // QR saved, shifted by the penalties `rho` [batch] on the bounded entries, c->flags = flags
-  int open(const double* rho, unsigned flags) {
-    const int err = open_unshifted(flags);
-    return err ? err : shift(rho);
-  }
-  // new penalties: the saved QR again, shifted by them
-  int reshift(const double* rho) {
-    const int err = restore();
-    return err ? err : shift(rho);
-  }
-  // the right-hand-side columns of the kept records, which the re-solves of an adjoint overwrite: restored by close()
-  int save_record_columns() {
-    HIP_TRY(adjoint_scratch(c, false));
-    columns_saved = true;
-    return NDLQR_OK;
-  }
-  // Record columns and QR restored, the caller's flags back; the kept records / factors belong to the shifted matrix, so the
-  // plain re-solves refuse until the next solve. The first error.
-  int close() {
-    if (!open_) return NDLQR_OK;
-    open_ = false;
-    const hipError_t ce = columns_saved ? adjoint_scratch(c, true) : hipSuccess;
-    const hipError_t qe = hipMemcpyAsync(c->QR, c->box.qr_save, bytes_QR(c->d), hipMemcpyDeviceToDevice, c->set[0].stream);
-    c->flags = user_flags;
-    c->kept.forget_factorisation();
-    if (ce != hipSuccess) return fail("restoring the record columns", ce);
-    return qe != hipSuccess ? fail("restoring QR", qe) : NDLQR_OK;
-  }
-};
-
 // iters / status of a constrained solve or its adjoint (`who`) go to host memory or this device's
-static int refuse_foreign_iters_status(const NdlqrHipCtx* c, const char* who, const int* iters, const int* status) {
+int refuse_foreign_iters_status(const NdlqrHipCtx* c, const char* who, const int* iters, const int* status) {
   for (const int* p : {iters, status})
     if (p && where(p, c->device) == Where::OtherDevice)
       return refuse(std::string(who) + ": iters / status lie in the memory of another device than the solver's");
@@ -2094,8 +1551,8 @@ static int refuse_foreign_iters_status(const NdlqrHipCtx* c, const char* who, co
 
 // The per-problem iteration counts and status words behind everything enqueued on st, for the caller (null: not asked
 // for); a problem still running at max_iter (0) reports 2: the last iterate. Synchronises st.
-static int deliver_iters_status(const NdlqrHipCtx* c, hipStream_t st, const int* d_iters, const int* d_status, int* iters,
-                                int* status) {
+int deliver_iters_status(const NdlqrHipCtx* c, hipStream_t st, const int* d_iters, const int* d_status, int* iters,
+                         int* status) {
   const size_t bytes = sizeof(int) * (size_t)c->d.batch;
   std::vector<int> h_it((size_t)c->d.batch), h_st((size_t)c->d.batch);
   HIP_TRY(hipMemcpyAsync(h_it.data(), d_iters, bytes, hipMemcpyDeviceToHost, st));
@@ -2113,936 +1570,7 @@ static int deliver_iters_status(const NdlqrHipCtx* c, hipStream_t st, const int*
   return NDLQR_OK;
 }
 
-int ndlqr_hip_solve_box_ex(NdlqrHipCtx* c, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
-                           int check_every, int warm_start, int* iters, int* status, int adapt_every, double rho_min,
-                           double rho_max) {
-  if (!c || !(rho > 0.0) || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 ||
-      check_every < 1 || adapt_every < 0 || (adapt_every > 0 && !(rho_min > 0.0 && rho_min <= rho_max)))
-    return NDLQR_ERR_INVALID;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_box")) return cerr;
-  if (!c->box.have_bounds) return refuse("ndlqr_hip_solve_box: no bounds (ndlqr_hip_set_bounds first)");
-  const ndlqr::Dims& d = c->d;
-  HIP_TRY(hipSetDevice(c->device));
-  int err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_box", iters, status);
-  if (err) return err;
-  HIP_TRY(c->box.ensure(d, c->set[0].stream));
-  const int infeas_every = c->infeas.every;
-  if (infeas_every > 0) HIP_TRY(c->infeas.ensure(d));
-  c->infeas.gen = 0;
-  const int accel_mem = c->accel.mem;
-  if (accel_mem > 0) HIP_TRY(c->accel.ensure(d));
-  c->accel.gen = 0;
-  // 1. everything idle, the primary set current with an up-to-date right-hand side
-  HIP_TRY(sync_all(c));
-  c->cur = 0;
-  err = rhs_make_current(c, 0xFu);
-  if (err) return err;
-  BufferSet& s = c->set[0];
-  const hipStream_t st = s.stream;
-  const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
-  const unsigned box_flags = c->flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
-  // the remembered factorisation applies to an adaptive warm start whatever its penalties are (the settings' rho is
-  // ignored: an MPC loop keeps what it learnt); everywhere else only when they are all the settings' rho
-  const bool usable = c->box.fact && c->box.flags == box_flags;
-  const bool keep_rho = usable && adapt_every > 0 && warm_start;
-  const bool reuse = keep_rho || (usable && c->box.rho_uniform && c->box.rho_value == rho);
-  bool uniform = keep_rho ? c->box.rho_uniform : true;
-  const double uniform_value = keep_rho ? c->box.rho_value : rho;
-  HIP_TRY(hipEventRecord(s.ev_start, st));
-  // 2. the penalties
-  if (!reuse) {
-    c->forget_shifted();  // (the remembered factorisation belongs to the penalties overwritten here)
-    hipLaunchKernelGGL(ndlqr::box_fill_rho, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, rho, c->box.rho);
-    HIP_TRY(hipGetLastError());
-  }
-  bool factored = false;  // the shifted matrix was factored in this call (the resident solution is then overwritten)
-  int not_spd = NDLQR_OK;
-  ShiftedQR shifted(c);
-  // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
-  const auto iterate = [&]() -> int {
-    // 3. shift QR; factor the shifted matrix, unless the remembered factorisation applies
-    int e = shifted.open(c->box.rho, box_flags);
-    if (e) return e;
-    if (reuse) {
-      c->kept = c->box.kept;
-    } else {
-      factored = true;
-      e = box_factor(c, st, &not_spd);
-      if (e) return e;
-    }
-    // 4. the iterations
-    const double* lo = c->box.lo;
-    const double* hi = c->box.hi;
-    const size_t bs = c->box.bstride;
-    const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, rho_min, rho_max};
-    const double* rhov = c->box.rho;
-    const int cold = warm_start && c->box.have_vy ? 0 : 1;
-    launch_strict(strict, ndlqr::box_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rhov, cold, (const int*)c->box.status, lo,
-                  hi, bs, (const double*)s.rhs, c->box.v, c->box.y, c->box.rhs[0], c->box.rhs[1]);
-    HIP_TRY(hipGetLastError());
-    BoxInfeasState& inf = c->infeas;
-    if (infeas_every > 0) {  // (the certificate rows of the problems that do not end as 4 are zero)
-      HIP_TRY(hipMemsetAsync(inf.cert_lam, 0, sizeof(double) * (size_t)d.batch * d.N * d.n, st));
-      HIP_TRY(hipMemsetAsync(inf.cert_mu, 0, sizeof(double) * doubles_QR(d), st));
-      HIP_TRY(hipMemsetAsync(inf.measures, 0, sizeof(double) * 4 * (size_t)d.batch, st));
-      HIP_TRY(hipMemsetAsync(inf.measured_at, 0, sizeof(int) * (size_t)d.batch, st));
-    }
-    const auto is_check = [&](int i) { return infeas_every > 0 && i >= 2 && i <= max_iter && i % infeas_every == 0; };
-    BoxAccelState& acc = c->accel;
-    const ndlqr::AccelParams AP = {accel_mem, acc.safeguard, acc.reg};
-    const ndlqr::AccelBufs AX = {acc.ring_t, acc.ring_g, acc.pv, acc.py, acc.gram, acc.gprev, acc.gamma, acc.meta};
-    if (accel_mem > 0) {  // an empty history, warm start or cold; the ring, pv, py and gram are written before they are read
-      HIP_TRY(hipMemsetAsync(acc.meta, 0, sizeof(int) * ndlqr::ACCEL_WORDS * (size_t)d.batch, st));
-      HIP_TRY(hipMemsetAsync(acc.gprev, 0, sizeof(double) * (size_t)d.batch, st));
-      HIP_TRY(hipMemsetAsync(acc.gamma, 0, sizeof(double) * (size_t)accel_mem * d.batch, st));
-    }
-    c->box.have_vy = true;
-    c->box.h_word[0] = d.batch;
-    c->box.h_word[1] = 0;
-    HIP_TRY(hipMemcpyAsync(c->box.word, c->box.h_word, 2 * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(c->box.status, 0, sizeof(int) * (size_t)d.batch, st));
-    for (int it = 1; it <= max_iter; ++it) {
-      const double* rc = c->box.rhs[(it - 1) & 1];
-      double* rn = c->box.rhs[it & 1];
-      e = launch_resolve(c, rc, c->box.z, "box-constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
-      if (e) return e;
-      const int adapt = adapt_every > 0 && it % adapt_every == 0 && it < max_iter;
-      if (accel_mem > 0)
-        launch_strict(strict, ndlqr::box_update_accel, dim3(d.batch), dim3(256), 0, st, d, it, adapt,
-                      is_check(it) || is_check(it + 1) ? 1 : 0, P, AP, (const double*)c->box.z, lo, hi, bs, c->box.v, c->box.y,
-                      (const double*)s.rhs, rc, rn, c->box.rho, c->box.status, c->box.iters, c->box.resid, c->box.word, AX);
-      else
-        launch_strict(strict, ndlqr::box_update, dim3(d.batch), dim3(256), 0, st, d, it, adapt, P, (const double*)c->box.z, lo, hi,
-                      bs, c->box.v, c->box.y, (const double*)s.rhs, rc, rn, c->box.rho, c->box.status, c->box.iters,
-                      c->box.resid, c->box.word);
-      HIP_TRY(hipGetLastError());
-      if (is_check(it)) {  // the differences over this iteration: a certificate?
-        hipLaunchKernelGGL(ndlqr::box_certify, dim3(d.batch), dim3(256), ndlqr::certify_lds_bytes(d), st, d, it, inf.eps,
-                           (const double*)c->AB, (const double*)c->box.z, (const double*)inf.z_prev, (const double*)c->box.y,
-                           (const double*)inf.y_prev, (const double*)c->box.rho, (const double*)inf.rho_prev, lo, hi, bs,
-                           (const double*)s.rhs, c->box.rhs[(it - 1) & 1], (const double*)rn, c->box.status, c->box.iters,
-                           c->box.word, inf.cert_lam, inf.cert_mu, inf.measures, inf.measured_at);
-        HIP_TRY(hipGetLastError());
-      }
-      if (is_check(it + 1)) {  // what the next iteration's check takes its differences against
-        HIP_TRY(hipMemcpyAsync(inf.z_prev, c->box.z, sizeof(double) * doubles_z(d), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(inf.y_prev, c->box.y, sizeof(double) * doubles_QR(d), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(inf.rho_prev, c->box.rho, sizeof(double) * (size_t)d.batch, hipMemcpyDeviceToDevice, st));
-      }
-      if (it % check_every == 0 || it == max_iter || adapt) {
-        // 5. one word: how many problems still run; after an adapting update also how many changed their penalty
-        HIP_TRY(hipMemcpyAsync(c->box.h_word, c->box.word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c->box.h_word[0] == 0) break;
-        if (adapt && c->box.h_word[1] != 0) {
-          // 5a. new penalties: the saved QR shifted by the new vector and factored as above (frozen problems keep their
-          // penalty: the same factors again, so their later re-solves reproduce their z)
-          uniform = false;
-          factored = true;
-          e = shifted.reshift(rhov);
-          if (!e) e = box_factor(c, st, &not_spd);
-          if (e) return e;
-          HIP_TRY(hipMemsetAsync(c->box.word + 1, 0, sizeof(int), st));
-        }
-      }
-    }
-    // 6. deliver
-    hipLaunchKernelGGL(ndlqr::box_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, lo, hi, bs, (const double*)c->box.z, c->box.v,
-                       s.z);
-    HIP_TRY(hipGetLastError());
-    return NDLQR_OK;
-  };
-  err = iterate();
-  // 7. restore QR, bookkeeping
-  const KeptState shifted_kept = c->kept;  // (close() forgets it for the plain API)
-  const int cerr = shifted.close();
-  if (!err) err = cerr;
-  if (!err) {
-    c->box.fact = true;
-    c->box.rho_uniform = uniform;
-    c->box.rho_value = uniform_value;
-    c->box.flags = box_flags;
-    c->box.kept = shifted_kept;
-  } else {
-    c->forget_shifted();
-    c->box.have_vy = false;
-    if (!not_spd) c->state_dirty = true;  // (a failed launch; a non-positive pivot leaves the device state clean)
-    if (factored) c->z_invalid = true;    // (the factorisation solved the shifted matrix with the unshifted right-hand side)
-    (void)hipStreamSynchronize(st);
-    return err;
-  }
-  note_solution(c);
-  c->box.soln_gen = c->soln_gen;
-  if (infeas_every > 0) c->infeas.gen = c->soln_gen;
-  if (accel_mem > 0) {
-    c->accel.gen = c->soln_gen;
-    c->accel.mem_solved = accel_mem;
-  }
-  HIP_TRY(hipEventRecord(s.ev_stop, st));
-  c->timing_pending = true;
-  err = deliver_iters_status(c, st, c->box.iters, c->box.status, iters, status);
-  if (err) return err;
-  return ndlqr_hip_synchronize(c);
-}
-
-int ndlqr_hip_set_box_infeasibility(NdlqrHipCtx* c, int every, double eps) {
-  if (!c || every < 0 || !(eps > 0.0 && eps < HUGE_VAL)) return NDLQR_ERR_INVALID;
-  if (every > 0) {  // (switching it off is always possible)
-    if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_set_box_infeasibility")) return herr;
-    if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_set_box_infeasibility")) return cerr;
-  }
-  c->infeas.every = every;
-  c->infeas.eps = eps;
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_download_infeasibility_certificate(NdlqrHipCtx* c, double* dlam, double* dmu_x, double* dmu_u) {
-  if (!c || (!dlam && !dmu_x && !dmu_u)) return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_infeasibility_certificate")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_infeasibility_certificate")) return cerr;
-  if (c->infeas.gen == 0 || c->infeas.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
-    return refuse("ndlqr_hip_download_infeasibility_certificate: the resident solution is not that of a constrained solve "
-                  "with infeasibility detection on (ndlqr_hip_set_box_infeasibility before the solve)");
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t nx = (size_t)u.batch * u.N * u.n;
-  CallerArrays<3> out = {{dlam, dmu_x, dmu_u}, {nx, nx, (size_t)u.batch * u.N * u.m}};
-  int err = out.classify(c, "ndlqr_hip_download_infeasibility_certificate", "an output lies");
-  if (err) return err;
-  HIP_TRY(c->grad_stage.grow(out.stage));
-  HIP_TRY(sync_all(c));
-  const BufferSet& s = c->set[0];
-  out.place(c);
-  hipLaunchKernelGGL(ndlqr::box_certificate_out, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->infeas.cert_lam,
-                     (const double*)c->infeas.cert_mu, out.dev[0], out.dev[1], out.dev[2]);
-  HIP_TRY(hipGetLastError());
-  err = out.copy(s.stream, false);
-  if (err) return err;
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_download_infeasibility_measures(NdlqrHipCtx* c, double* measures, int* iteration) {
-  if (!c || (!measures && !iteration)) return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_infeasibility_measures")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_infeasibility_measures")) return cerr;
-  if (c->infeas.gen == 0 || c->infeas.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
-    return refuse("ndlqr_hip_download_infeasibility_measures: the resident solution is not that of a constrained solve "
-                  "with infeasibility detection on (ndlqr_hip_set_box_infeasibility before the solve)");
-  HIP_TRY(hipSetDevice(c->device));
-  for (const void* p : {(const void*)measures, (const void*)iteration})
-    if (p && where(p, c->device) == Where::OtherDevice)
-      return refuse("ndlqr_hip_download_infeasibility_measures: an output lies in the memory of another device than the solver's");
-  HIP_TRY(sync_all(c));
-  // (stored in the caller's layout: plain copies, as ndlqr_hip_download_box_penalties)
-  const size_t nb = (size_t)c->d.batch;
-  if (measures) HIP_TRY(hipMemcpy(measures, c->infeas.measures, sizeof(double) * 4 * nb, hipMemcpyDefault));
-  if (iteration) HIP_TRY(hipMemcpy(iteration, c->infeas.measured_at, sizeof(int) * nb, hipMemcpyDefault));
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_set_box_acceleration(NdlqrHipCtx* c, int mem, double safeguard, double reg) {
-  if (!c || mem < 0 || mem > ndlqr::ACCEL_MEM_MAX || !(safeguard > 0.0 && safeguard < HUGE_VAL) || !(reg > 0.0 && reg < HUGE_VAL))
-    return NDLQR_ERR_INVALID;
-  if (mem > 0) {  // (switching it off is always possible)
-    if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_set_box_acceleration")) return herr;
-    if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_set_box_acceleration")) return cerr;
-  }
-  c->accel.mem = mem;
-  c->accel.gen = 0;  // (the read-out's gamma has the width of the memory it ran with: a solve with this setting first)
-  c->accel.safeguard = safeguard;
-  c->accel.reg = reg;
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_download_box_acceleration(NdlqrHipCtx* c, int* accepted, int* rejected, double* gamma, int* columns) {
-  if (!c || (!accepted && !rejected && !gamma && !columns)) return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_box_acceleration")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_box_acceleration")) return cerr;
-  if (c->accel.gen == 0 || c->accel.gen != c->soln_gen || c->box.soln_gen != c->soln_gen)
-    return refuse("ndlqr_hip_download_box_acceleration: the resident solution is not that of a constrained solve with "
-                  "acceleration on (ndlqr_hip_set_box_acceleration before the solve)");
-  HIP_TRY(hipSetDevice(c->device));
-  for (const void* p : {(const void*)accepted, (const void*)rejected, (const void*)gamma, (const void*)columns})
-    if (p && where(p, c->device) == Where::OtherDevice)
-      return refuse("ndlqr_hip_download_box_acceleration: an output lies in the memory of another device than the solver's");
-  HIP_TRY(sync_all(c));
-  // (stored in the caller's layout: plain copies, as ndlqr_hip_download_box_penalties)
-  const size_t nb = (size_t)c->d.batch;
-  const int* meta = c->accel.meta;
-  if (accepted) HIP_TRY(hipMemcpy(accepted, meta + ndlqr::ACCEL_ACCEPTED * nb, sizeof(int) * nb, hipMemcpyDefault));
-  if (rejected) HIP_TRY(hipMemcpy(rejected, meta + ndlqr::ACCEL_REJECTED * nb, sizeof(int) * nb, hipMemcpyDefault));
-  if (columns) HIP_TRY(hipMemcpy(columns, meta + ndlqr::ACCEL_COLUMNS * nb, sizeof(int) * nb, hipMemcpyDefault));
-  if (gamma) HIP_TRY(hipMemcpy(gamma, c->accel.gamma, sizeof(double) * nb * c->accel.mem_solved, hipMemcpyDefault));
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_download_box_penalties(NdlqrHipCtx* c, double* rho) {
-  if (!c || !rho) return NDLQR_ERR_INVALID;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_box_penalties")) return cerr;
-  if (!c->box.have_vy || !c->box.rho) return refuse("ndlqr_hip_download_box_penalties: no constrained solve yet");
-  HIP_TRY(hipSetDevice(c->device));
-  if (where(rho, c->device) == Where::OtherDevice)
-    return refuse("ndlqr_hip_download_box_penalties: the output lies in the memory of another device than the solver's");
-  HIP_TRY(sync_all(c));
-  HIP_TRY(hipMemcpy(rho, c->box.rho, sizeof(double) * (size_t)c->d.batch, hipMemcpyDefault));
-  return NDLQR_OK;
-}
-
-// resid [batch][4] of a constrained solve or its adjoint (`who`), stored in the caller's layout: a plain copy
-static int download_resid(NdlqrHipCtx* c, const char* who, const double* d_resid, double* resid) {
-  HIP_TRY(hipSetDevice(c->device));
-  if (where(resid, c->device) == Where::OtherDevice)
-    return refuse(std::string(who) + ": the output lies in the memory of another device than the solver's");
-  HIP_TRY(sync_all(c));
-  HIP_TRY(hipMemcpy(resid, d_resid, sizeof(double) * 4 * (size_t)c->d.batch, hipMemcpyDefault));
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_download_box_residuals(NdlqrHipCtx* c, double* resid) {
-  if (!c || !resid) return NDLQR_ERR_INVALID;
-  if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.resid)
-    return refuse("ndlqr_hip_download_box_residuals: the resident solution is not that of a constrained solve");
-  return download_resid(c, "ndlqr_hip_download_box_residuals", c->box.resid, resid);
-}
-
-int ndlqr_hip_download_box_adjoint_residuals(NdlqrHipCtx* c, double* resid) {
-  if (!c || !resid) return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_box_adjoint_residuals")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_box_adjoint_residuals")) return cerr;
-  if (c->abox.gen == 0 || c->abox.gen != c->soln_gen || !c->abox.resid)
-    return refuse("ndlqr_hip_download_box_adjoint_residuals: no box adjoint of the resident solution "
-                  "(ndlqr_hip_solve_box_adjoint after the latest constrained solve)");
-  return download_resid(c, "ndlqr_hip_download_box_adjoint_residuals", c->abox.resid, resid);
-}
-
-int ndlqr_hip_download_bound_multipliers(NdlqrHipCtx* c, double* mu_x, double* mu_u) {
-  if (!c || (!mu_x && !mu_u)) return NDLQR_ERR_INVALID;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_bound_multipliers")) return cerr;
-  if (!c->box.have_vy || !c->box.y) return refuse("ndlqr_hip_download_bound_multipliers: no constrained solve yet");
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  CallerArrays<2> out = {{mu_x, mu_u}, {(size_t)u.batch * u.N * u.n, (size_t)u.batch * u.N * u.m}};
-  int err = out.classify(c, "ndlqr_hip_download_bound_multipliers", "an output lies");
-  if (err) return err;
-  HIP_TRY(c->grad_stage.grow(out.stage));
-  HIP_TRY(sync_all(c));
-  const BufferSet& s = c->set[0];
-  out.place(c);
-  if (c->pol.soln_gen != 0 && c->pol.soln_gen == c->soln_gen)  // (a polished solution: its mu where the polish succeeded)
-    hipLaunchKernelGGL(ndlqr::polish_multipliers, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
-                       (const double*)c->box.y, (const int*)c->pol.state, (const double*)c->pol.mu, out.dev[0], out.dev[1]);
-  else
-    hipLaunchKernelGGL(ndlqr::box_multipliers, dim3(u.N, d.batch), dim3(64), 0, s.stream, u, d, (const double*)c->box.rho,
-                       (const double*)c->box.y, out.dev[0], out.dev[1]);
-  HIP_TRY(hipGetLastError());
-  err = out.copy(s.stream, false);
-  if (err) return err;
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return NDLQR_OK;
-}
-
-// ------------------------------------------------------------------------------ gradients through the box-constrained solve
-// The adjoint of the active-set system (kernels_box_grad.hpp) by the ADMM of the forward on its
-// remembered shifted factorisation: QR shifted by the forward's rho on its bounded entries again (restored on every
-// exit), the kept records / factors taken as the forward left them -- nothing is factored --, every iteration one
-// re-solve into adj.z plus one box_adjoint_update. The right-hand-side columns of the kept records and slots are saved and
-// restored around it as for the plain adjoint, so the next warm-started forward finds everything as it was.
-
-int ndlqr_hip_solve_box_adjoint(NdlqrHipCtx* c, const double* g, double alpha, double eps_abs, double eps_rel, int max_iter,
-                                int check_every, int* iters, int* status) {
-  if (!c || !g || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 ||
-      check_every < 1)
-    return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_solve_box_adjoint")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_box_adjoint")) return cerr;
-  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_box_adjoint");
-  if (c->pol.soln_gen != 0 && c->pol.soln_gen == c->soln_gen)
-    return refuse("ndlqr_hip_solve_box_adjoint: the resident solution was polished (ndlqr_hip_polish_box), which replaced the "
-                  "ADMM factorisation: its adjoint is the polished adjoint (ndlqr_hip_solve_polished_adjoint)");
-  if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.fact || c->inputs_replaced)
-    return refuse("ndlqr_hip_solve_box_adjoint: the resident solution is not that of the latest constrained solve (a solve, "
-                  "step, re-solve, new inputs or new bounds came after it)");
-  if (c->box.kept.time_shard) return refuse("ndlqr_hip_solve_box_adjoint: not available on a time-axis shard");
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  CallerArrays<1> ga = {{const_cast<double*>(g)}, {((size_t)u.rows * u.N - u.m) * d.batch}};
-  int err = ga.classify(c, "ndlqr_hip_solve_box_adjoint", "g lies");
-  if (!err) err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_box_adjoint", iters, status);
-  if (err) return err;
-  HIP_TRY(c->adj.ensure(d, c->set[0].stream));
-  HIP_TRY(c->abox.ensure(d));
-  HIP_TRY(c->grad_stage.grow(ga.stage));
-  // 1. everything idle, the primary set current; g packed into the adjoint's resident right-hand side
-  HIP_TRY(sync_all(c));
-  c->cur = 0;
-  BufferSet& s = c->set[0];
-  const hipStream_t st = s.stream;
-  ga.place(c);
-  err = ga.copy(st, true);
-  if (err) return err;
-  c->abox.gen = 0;
-  c->adj.gen = 0;
-  const bool strict = (c->box.flags & NDLQR_FLAG_STRICT_FP) != 0;
-  HIP_TRY(hipEventRecord(s.ev_start, st));
-  ShiftedQR shifted(c);
-  // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
-  const auto iterate = [&]() -> int {
-    const double* rho = c->box.rho;  // (the forward's final penalties: those of the remembered factorisation)
-    hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, st, u, d, (const double*)ga.dev[0],
-                       c->adj.rhs);
-    HIP_TRY(hipGetLastError());
-    // 2. shift QR, take up the remembered shifted factorisation, save the right-hand-side columns of the records
-    int e = shifted.open(rho, c->box.flags);
-    if (e) return e;
-    c->kept = c->box.kept;
-    e = shifted.save_record_columns();
-    if (e) return e;
-    // 3. codes, v = y = 0, right-hand sides, status
-    const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
-    HIP_TRY(hipMemsetAsync(c->abox.word, 0, sizeof(int), st));
-    // (the read-out row of a problem that is not iterated -- forward status 3 or 4 -- is zero)
-    HIP_TRY(hipMemsetAsync(c->abox.resid, 0, sizeof(double) * 4 * (size_t)d.batch, st));
-    launch_strict(strict, ndlqr::box_adjoint_start, dim3(d.N, d.batch), dim3(64), 0, st, d, rho, (const double*)c->box.lo,
-                  (const double*)c->box.hi, c->box.bstride, (const double*)c->box.v, (const int*)c->box.status,
-                  (const double*)c->adj.rhs, c->abox.code, c->abox.v, c->abox.y, c->abox.rhs[0], c->abox.rhs[1], c->abox.status,
-                  c->abox.iters, c->abox.word);
-    HIP_TRY(hipGetLastError());
-    // 4. the iterations (none when every problem's forward ended non-finite)
-    HIP_TRY(hipMemcpyAsync(&c->box.h_word[4], c->abox.word, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const bool any = c->box.h_word[4] > 0;
-    for (int it = 1; it <= max_iter && any; ++it) {
-      const double* rc = c->abox.rhs[(it - 1) & 1];
-      double* rn = c->abox.rhs[it & 1];
-      e = launch_resolve(c, rc, c->adj.z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
-      if (e) return e;
-      launch_strict(strict, ndlqr::box_adjoint_update, dim3(d.batch), dim3(256), 0, st, d, it, P, (const double*)c->adj.z,
-                    (const unsigned char*)c->abox.code, c->abox.v, c->abox.y, (const double*)c->adj.rhs, rc, rn, rho,
-                    c->abox.status, c->abox.iters, c->abox.resid, c->abox.word);
-      HIP_TRY(hipGetLastError());
-      if (it % check_every == 0 || it == max_iter) {
-        HIP_TRY(hipMemcpyAsync(&c->box.h_word[4], c->abox.word, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c->box.h_word[4] == 0) break;
-      }
-    }
-    if (!any) {  // (no re-solve ran: a defined w all the same -- the re-solve of the packed g)
-      e = launch_resolve(c, c->abox.rhs[0], c->adj.z, "box adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
-      if (e) return e;
-      HIP_TRY(hipGetLastError());
-    }
-    // 5. w = [lambda, v]
-    hipLaunchKernelGGL(ndlqr::box_adjoint_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, (const unsigned char*)c->abox.code,
-                       (const double*)c->abox.v, (const int*)c->abox.status, c->adj.z);
-    HIP_TRY(hipGetLastError());
-    return NDLQR_OK;
-  };
-  err = iterate();
-  // 6. restore the record columns and QR, bookkeeping (the kept state as the constrained solve left it)
-  const int cerr = shifted.close();
-  if (!err) err = cerr;
-  if (err) {
-    c->state_dirty = true;
-    (void)hipStreamSynchronize(st);
-    return err;
-  }
-  HIP_TRY(hipEventRecord(s.ev_stop, st));
-  err = deliver_iters_status(c, st, c->abox.iters, c->abox.status, iters, status);
-  if (err) return err;
-  note_elapsed(c, s);
-  c->adj.gen = c->soln_gen;
-  c->abox.gen = c->soln_gen;
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_bound_gradients(NdlqrHipCtx* c, int summed, double* gxlo, double* gxhi, double* gulo, double* guhi) {
-  if (!c) return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_bound_gradients")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_bound_gradients")) return cerr;
-  const int aerr = need_adjoint(c, "ndlqr_hip_bound_gradients");
-  if (aerr) return aerr;
-  const bool polished = c->pol.adj_gen != 0 && c->pol.adj_gen == c->soln_gen;  // (nu split by the polish codes, penalty 1)
-  if (c->abox.gen != c->soln_gen && !polished)
-    return refuse("ndlqr_hip_bound_gradients: no box adjoint of the resident solution (ndlqr_hip_solve_box_adjoint after the "
-                  "latest constrained solve, or ndlqr_hip_solve_polished_adjoint after the latest polish)");
-  const double* g_rho = polished ? c->pol.ones : c->box.rho;
-  const unsigned char* g_code = polished ? c->pol.code : c->abox.code;
-  const double* g_y = polished ? c->pol.nu : c->abox.y;
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t P = summed ? 1 : (size_t)d.batch;
-  CallerArrays<4> go = {{gxlo, gxhi, gulo, guhi}, {P * u.N * u.n, P * u.N * u.n, P * u.N * u.m, P * u.N * u.m}};
-  int err = go.classify(c, "ndlqr_hip_bound_gradients", "an output lies");
-  if (err) return err;
-  if (!gxlo && !gxhi && !gulo && !guhi) return NDLQR_OK;
-  // batch sums: entries of [N][n+m] one per thread, the batch split into about 2048 / ceil(entries / 256) runs of problems
-  // added in order, then the runs in order (grad_assemble's scheme: deterministic, no atomics)
-  const size_t E = (size_t)u.N * (u.n + u.m);
-  const unsigned nblk = (unsigned)((E + 255) / 256);
-  int nsplit = 1, ppb = d.batch;
-  if (summed) {
-    nsplit = (int)(2048 / nblk);
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > d.batch) nsplit = d.batch;
-    ppb = (d.batch + nsplit - 1) / nsplit;
-    nsplit = (d.batch + ppb - 1) / ppb;
-  }
-  const size_t npart = nsplit > 1 ? (size_t)nsplit * 2 * E : 0;
-  HIP_TRY(c->grad_stage.grow(go.stage + npart));
-  HIP_TRY(sync_all(c));
-  BufferSet& s = c->set[0];
-  ndlqr::BoundOut out = {};
-  double* part = go.place(c);  // (the partial sums behind the staged outputs)
-  if (!npart) part = nullptr;
-  for (int k = 0; k < 4; ++k) out.p[k] = go.dev[k];
-  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  if (!summed) {
-    hipLaunchKernelGGL(ndlqr::box_bound_grads, dim3(d.N, d.batch), dim3(64), 0, s.stream, u, d, g_rho, g_code, g_y, out);
-    HIP_TRY(hipGetLastError());
-  } else {
-    hipLaunchKernelGGL(ndlqr::box_bound_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d,
-                       g_rho, ppb, g_code, g_y, out, part);
-    HIP_TRY(hipGetLastError());
-    if (part) {
-      hipLaunchKernelGGL(ndlqr::box_bound_sum_splits, dim3(nblk), dim3(256), 0, s.stream, u, nsplit, (const double*)part, out);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  err = go.copy(s.stream, false);
-  if (err) return err;
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  note_elapsed(c, s);
-  return NDLQR_OK;
-}
-
 unsigned long long ndlqr_hip_factor_count(const NdlqrHipCtx* c) { return c ? c->factor_count : 0; }
-
-// ------------------------------------------------------------------------------ iterative refinement
-// ndlqr_hip_refine (kernels_refine.hpp): the residual of the resident solution (which == 0) or of the
-// latest plain adjoint (which == 1) in double-double, then max_steps times: the re-solve of that residual against the kept
-// factorisation into delta (record columns / slots saved and restored around it, as for the adjoint solve), the residual of
-// z (+) delta over the old one, and the commit for the problems whose residual norm went down at every step so far. The
-// host reads nothing back between the steps: acceptance is decided on the device from the norm slots.
-
-// r = b - K (z (+) delta) into c->ref.r on the current set's stream (norms == nullptr: the vector alone)
-// (QR: the diagonal to use -- the polish passes the saved, unshifted one --, r: the destination)
-static int launch_residual_dd_on(NdlqrHipCtx* c, const double* QR, const double* rhs, const double* z, const double* delta,
-                                 double* r, unsigned long long* norms, int nslots, int slot) {
-  const ndlqr::Dims& d = c->d;
-  const bool staged = ndlqr::refine_lds_bytes(d, true) + 64 <= kLdsMax;  // (+ the kernel's static words)
-  const size_t lds = ndlqr::refine_lds_bytes(d, staged);
-  if (lds + 64 > kLdsMax) return refuse("double-double residual: two knots of this block size exceed the LDS of a workgroup");
-  HIP_TRY(allow_dynamic_lds(&ndlqr::kkt_residual_dd, lds));
-  const int threads = d.rows + d.n <= 64 ? 64 : (d.rows + d.n <= 128 ? 128 : 256);
-  hipLaunchKernelGGL(ndlqr::kkt_residual_dd, dim3(d.N, d.batch), dim3(threads), lds, c->set[c->cur].stream, c->du, d,
-                     (const double*)c->AB, QR, rhs, z, delta, r, norms, nslots, slot, staged ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  return NDLQR_OK;
-}
-
-// r = b - K (z (+) delta) into c->ref.r on the resident QR
-static int launch_residual_dd(NdlqrHipCtx* c, const double* rhs, const double* z, const double* delta,
-                              unsigned long long* norms, int nslots, int slot) {
-  return launch_residual_dd_on(c, c->QR, rhs, z, delta, c->ref.r, norms, nslots, slot);
-}
-
-// per-phase device times of a refinement under NDLQR_FLAG_PROFILE (ndlqr_hip_refine_phase_ms)
-struct RefinePhases {
-  NdlqrHipCtx* c;
-  bool on;
-  struct Span { int phase; hipEvent_t start, stop; };
-  std::vector<Span> spans;
-  explicit RefinePhases(NdlqrHipCtx* ctx) : c(ctx), on((ctx->flags & NDLQR_FLAG_PROFILE) != 0) {}
-  void open(int phase) {
-    if (!on) return;
-    spans.push_back({phase, take_event(c), take_event(c)});
-    (void)hipEventRecord(spans.back().start, c->set[0].stream);
-  }
-  void close() {
-    if (on) (void)hipEventRecord(spans.back().stop, c->set[0].stream);
-  }
-  // (the stream has been synchronised)
-  void collect() {
-    for (int p = 0; p < 3; ++p) c->ref.phase_ms[p] = 0.0;
-    for (const Span& sp : spans) {
-      float ms = 0.0f;
-      if (hipEventElapsedTime(&ms, sp.start, sp.stop) == hipSuccess) c->ref.phase_ms[sp.phase] += ms;
-      c->event_pool.push_back(sp.start);
-      c->event_pool.push_back(sp.stop);
-    }
-    spans.clear();
-  }
-};
-
-int ndlqr_hip_refine(NdlqrHipCtx* c, int which, int max_steps, int* steps, double* eta_before, double* eta_after) {
-  if (!c || which < 0 || which > 1 || max_steps < 1 || max_steps > kRefineMaxSteps) return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_refine")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_refine")) return cerr;
-  const char* who = which ? "ndlqr_hip_refine (adjoint)" : "ndlqr_hip_refine";
-  if (!c->kept.fact_valid && !c->kept.rec_complete)
-    return refuse(std::string(who) + ": needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
-                  "factorisation) of the resident inputs");
-  if (c->z_partial || c->z_invalid) return need_full_solution(c, who);
-  if (c->kept.time_shard) return refuse(std::string(who) + ": not available on a time-axis shard");
-  if (c->inputs_replaced) return refuse(std::string(who) + ": the inputs were replaced after the factorisation");
-  if (c->latest != 0) return refuse(std::string(who) + ": the resident solution is not on the primary buffer set");
-  if (which) {
-    const int aerr = need_adjoint(c, who);
-    if (aerr) return aerr;
-    if (c->abox.gen == c->soln_gen || c->pol.adj_gen == c->soln_gen)
-      return refuse(std::string(who) + ": the adjoint is that of a constrained solve");
-  }
-  const ndlqr::Dims& d = c->d;
-  HIP_TRY(hipSetDevice(c->device));
-  CallerArrays<2> ea = {{eta_before, eta_after}, {(size_t)d.batch, (size_t)d.batch}};
-  int err = ea.classify(c, who, "an output lies");
-  if (!err) err = refuse_foreign_iters_status(c, who, steps, nullptr);
-  if (err) return err;
-  // 1. everything idle, the primary set current with an up-to-date right-hand side
-  HIP_TRY(sync_all(c));
-  c->cur = 0;
-  err = rhs_make_current(c, 0xFu);
-  if (err) return err;
-  BufferSet& s = c->set[0];
-  const hipStream_t st = s.stream;
-  const int nslots = max_steps + 1;
-  const size_t norm_bytes = sizeof(unsigned long long) * RefineState::norm_count(d);
-  HIP_TRY(c->ref.ensure(d, st));
-  HIP_TRY(c->adj.ensure_save(d));
-  const double* rhs = which ? c->adj.rhs : s.rhs;
-  double* z = which ? c->adj.z : s.z;
-  RefinePhases phases(c);
-  HIP_TRY(hipEventRecord(s.ev_start, st));
-  HIP_TRY(hipMemsetAsync(c->ref.norms, 0, norm_bytes, st));
-  // 2. the residual of z as found
-  phases.open(0);
-  err = launch_residual_dd(c, rhs, z, nullptr, c->ref.norms, nslots, 0);
-  phases.close();
-  if (err) return err;
-  // 3. the steps
-  for (int step = 1; step <= max_steps; ++step) {
-    phases.open(1);
-    HIP_TRY(adjoint_scratch(c, false));
-    err = launch_resolve(c, c->ref.r, c->ref.delta,
-                         "refinement: this configuration needs NDLQR_FLAG_KEEP_FACT (like the rhs-only solve)");
-    if (err) return err;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(adjoint_scratch(c, true));
-    phases.close();
-    phases.open(0);
-    err = launch_residual_dd(c, rhs, z, c->ref.delta, c->ref.norms, nslots, step);
-    phases.close();
-    if (err) return err;
-    phases.open(2);
-    hipLaunchKernelGGL(ndlqr::refine_commit, dim3((unsigned)((d.N * d.rows + 255) / 256), d.batch), dim3(256), 0, st, d,
-                       (const unsigned long long*)c->ref.norms, step, (const double*)c->ref.delta, z);
-    phases.close();
-    HIP_TRY(hipGetLastError());
-  }
-  // 4. what the caller asked for
-  hipLaunchKernelGGL(ndlqr::refine_report, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, max_steps,
-                     (const unsigned long long*)c->ref.norms, c->ref.steps, c->ref.eta);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(s.ev_stop, st));
-  if (!which) note_solution(c);  // (a refined primal is a new resident solution: an earlier adjoint no longer applies)
-  for (int k = 0; k < 2; ++k)
-    if (ea.user[k]) {
-      if (ea.own[k]) HIP_TRY(hipMemcpyAsync(ea.user[k], c->ref.eta + (size_t)k * d.batch, sizeof(double) * d.batch, hipMemcpyDeviceToDevice, st));
-      else HIP_TRY(hipMemcpyAsync(ea.user[k], c->ref.eta + (size_t)k * d.batch, sizeof(double) * d.batch, hipMemcpyDeviceToHost, st));
-    }
-  if (steps) {
-    const bool own = where(steps, c->device) == Where::OwnDevice;
-    HIP_TRY(hipMemcpyAsync(steps, c->ref.steps, sizeof(int) * (size_t)d.batch, own ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  note_elapsed(c, s);
-  phases.collect();
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_refine_phase_ms(NdlqrHipCtx* c, double* out3) {
-  if (!c || !out3) return NDLQR_ERR_INVALID;
-  for (int p = 0; p < 3; ++p) out3[p] = c->ref.phase_ms[p];
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_kkt_residual_vector(NdlqrHipCtx* c, double* r) {
-  if (!c || !r) return NDLQR_ERR_INVALID;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_kkt_residual_vector")) return cerr;
-  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_kkt_residual_vector");
-  HIP_TRY(hipSetDevice(c->device));
-  const Where wr = where(r, c->device);
-  if (wr == Where::OtherDevice)
-    return refuse("ndlqr_hip_kkt_residual_vector: r lies in the memory of another device than the solver's");
-  HIP_TRY(sync_all(c));
-  HIP_TRY(c->ref.ensure_r(c->d));
-  int err;
-  BufferSet& s = c->set[c->cur];
-  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  err = launch_residual_dd(c, s.rhs, c->set[c->latest].z, nullptr, nullptr, 0, 0);
-  if (err) return err;
-  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  if (wr != Where::OwnDevice) {
-    err = download_packed(c, c->ref.r, 0, c->d.batch, r);
-    if (err) return err;
-  } else {
-    HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->ref.r, r, s.stream, c->d.batch));
-    HIP_TRY(hipStreamSynchronize(s.stream));
-  }
-  note_elapsed(c, s);
-  return NDLQR_OK;
-}
-
-
-// ------------------------------------------------------------------------------ active-set polish
-// ndlqr_hip_polish_box (kernels_box_polish.hpp): the active set read off the latest constrained
-// solve, QR shifted by sigma on its entries inside a ShiftedQR scope and factored as box_factor does, then per round up to
-// max_steps steps of residual (double-double, on the saved unshifted QR) -> re-solve -> polish_update, the validation of
-// every problem's last accepted iterate, and -- while a set changed and rounds remain -- the corrected sets shifted and
-// factored again. Nothing is read back between the launches of a step; one word per step tells whether a problem still
-// runs, two words per round whether a set changed.
-
-// the steps of one round on the current factorisation
-// the accepted iterate and what defines the system of a polish or of its adjoint (lo == nullptr: c = 0)
-struct PolishSystem {
-  const double* res;  // b
-  const double *lo, *hi;
-  double *z, *mu, *bt;
-  int *state, *here;
-};
-static int polish_steps(NdlqrHipCtx* c, hipStream_t st, bool strict, int max_steps, const PolishSystem& y) {
-  const ndlqr::Dims& d = c->d;
-  PolishState& p = c->pol;
-  const int nslots = max_steps + 1;
-  const double* qr = c->box.qr_save;  // (the unshifted diagonal)
-  HIP_TRY(hipMemsetAsync(p.norms, 0, sizeof(unsigned long long) * PolishState::norm_count(d), st));
-  int e = launch_residual_dd_on(c, qr, y.bt, y.z, nullptr, p.r, p.norms, nslots, 0);
-  if (e) return e;
-  for (int step = 1; step <= max_steps + 1; ++step) {
-    const int form = step <= max_steps;
-    if (form) {
-      e = launch_resolve(c, p.r, p.delta, "polish: this configuration needs NDLQR_FLAG_KEEP_FACT");
-      if (e) return e;
-    }
-    launch_strict(strict, ndlqr::polish_update, dim3(d.batch), dim3(256), 0, st, d, step, form,
-                  (const unsigned long long*)p.norms, (const double*)p.sig, y.lo, y.hi, c->box.bstride,
-                  (const unsigned char*)p.code, y.res, (const double*)p.delta, y.z, y.mu, y.bt, p.zc, p.muc, p.btc, y.state,
-                  y.here, p.word);
-    HIP_TRY(hipGetLastError());
-    if (!form) break;
-    e = launch_residual_dd_on(c, qr, p.btc, p.zc, nullptr, p.r, p.norms, nslots, step);
-    if (e) return e;
-    if (step >= 2) {  // one word: how many problems still run
-      HIP_TRY(hipMemcpyAsync(p.h_word, p.word, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (p.h_word[0] == 0) break;
-    }
-  }
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_polish_box(NdlqrHipCtx* c, double sigma, int max_steps, int max_rounds, int* steps, int* status) {
-  if (!c || !(sigma > 0.0) || !(sigma < HUGE_VAL) || max_steps < 1 || max_steps > kPolishMaxSteps || max_rounds < 0)
-    return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_polish_box")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_polish_box")) return cerr;
-  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_polish_box");
-  if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.have_vy || c->inputs_replaced)
-    return refuse("ndlqr_hip_polish_box: the resident solution is not that of the latest constrained solve (a solve, step, "
-                  "re-solve, polish, new inputs or new bounds came after it)");
-  if (c->box.kept.time_shard) return refuse("ndlqr_hip_polish_box: not available on a time-axis shard");
-  const ndlqr::Dims& d = c->d;
-  HIP_TRY(hipSetDevice(c->device));
-  int err = refuse_foreign_iters_status(c, "ndlqr_hip_polish_box", steps, status);
-  if (err) return err;
-  HIP_TRY(c->pol.ensure(d, c->set[0].stream));
-  // 1. everything idle, the primary set current with an up-to-date right-hand side
-  HIP_TRY(sync_all(c));
-  c->cur = 0;
-  err = rhs_make_current(c, 0xFu);
-  if (err) return err;
-  BufferSet& s = c->set[0];
-  PolishState& p = c->pol;
-  const hipStream_t st = s.stream;
-  const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
-  const unsigned pol_flags = c->flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
-  const double* lo = c->box.lo;
-  const double* hi = c->box.hi;
-  const size_t bs = c->box.bstride;
-  p.fact = false;
-  HIP_TRY(hipEventRecord(s.ev_start, st));
-  // 2. sigma, codes, the starting iterate (before the first factorisation overwrites the resident solution)
-  hipLaunchKernelGGL(ndlqr::polish_sigma, dim3(d.batch), dim3(256), 0, st, c->du, d, sigma, (const double*)c->QR, p.sig);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemsetAsync(p.word, 0, 2 * sizeof(int), st));
-  hipLaunchKernelGGL(ndlqr::polish_start, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)c->box.rho, lo, hi, bs,
-                     (const double*)c->box.v, (const double*)c->box.y, (const int*)c->box.status, (const double*)s.rhs,
-                     (const double*)s.z, p.z0, p.z, p.code, p.mu, p.bt, p.state, p.steps, p.here, p.word);
-  HIP_TRY(hipGetLastError());
-  bool factored = false;
-  int not_spd = NDLQR_OK;
-  ShiftedQR shifted(c);
-  // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
-  const auto rounds = [&]() -> int {
-    int e = shifted.open_unshifted(pol_flags);
-    if (e) return e;
-    for (int round = 0; round <= max_rounds; ++round) {
-      // 3. shift by sigma on the active entries, factor
-      if (round > 0) {
-        e = shifted.restore();
-        if (e) return e;
-      }
-      hipLaunchKernelGGL(ndlqr::polish_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)p.sig,
-                         (const unsigned char*)p.code, c->QR);
-      HIP_TRY(hipGetLastError());
-      factored = true;
-      e = box_factor(c, st, &not_spd, "ndlqr_hip_polish_box", "Q, R + sigma on the active entries");
-      if (e) return e;
-      // 4. the steps
-      // (word[0]: the problems that run in this round, counted by polish_start / the previous round's validation)
-      e = polish_steps(c, st, strict, max_steps, {s.rhs, lo, hi, p.z, p.mu, p.bt, p.state, p.here});
-      if (e) return e;
-      // 5. validation; the sets that changed
-      HIP_TRY(hipMemsetAsync(p.word, 0, 2 * sizeof(int), st));
-      hipLaunchKernelGGL(ndlqr::polish_validate, dim3(d.batch), dim3(256), 0, st, d, round == max_rounds ? 1 : 0, lo, hi, bs,
-                         (const double*)s.rhs, p.code, p.z, p.mu, p.bt, p.state, p.steps, p.here, p.word);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(p.h_word, p.word, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (p.h_word[1] == 0) break;
-    }
-    // 6. deliver
-    hipLaunchKernelGGL(ndlqr::polish_finish, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)c->box.rho,
-                       (const int*)p.state, (const unsigned char*)p.code, (const double*)p.z, (const double*)p.mu,
-                       (const double*)p.z0, s.z, c->box.v, c->box.y);
-    HIP_TRY(hipGetLastError());
-    return NDLQR_OK;
-  };
-  err = rounds();
-  // 7. restore QR, bookkeeping
-  const KeptState shifted_kept = c->kept;  // (close() forgets it for the plain API)
-  const int cerr = shifted.close();
-  if (!err) err = cerr;
-  if (err) {
-    c->forget_shifted();
-    if (!not_spd) c->state_dirty = true;  // (a failed launch; a non-positive pivot leaves the device state clean)
-    if (factored) c->z_invalid = true;    // (the factorisation overwrote the resident solution)
-    (void)hipStreamSynchronize(st);
-    return err;
-  }
-  note_solution(c);  // (polish_finish wrote the resident solution: whatever belonged to the ADMM solution no longer applies)
-  p.soln_gen = p.adj_gen = 0;
-  HIP_TRY(hipEventRecord(s.ev_stop, st));
-  err = deliver_iters_status(c, st, p.steps, p.state, steps, status);
-  if (err) return err;  // (nothing remembered: the caller never learnt which problems were polished)
-  note_elapsed(c, s);
-  p.fact = true;  // (box_factor dropped the ADMM's)
-  p.flags = pol_flags;
-  p.kept = shifted_kept;
-  p.soln_gen = c->soln_gen;
-  return NDLQR_OK;
-}
-
-// The adjoint of the polished active-set system, K w + E_A' nu = g, E_A w = 0, on the remembered polish factorisation: the
-// loop of the polish with b = the packed g, c = 0, start w = nu = 0, the final codes; nothing is factored, no rounds. The
-// right-hand-side columns of the kept records are saved and restored as for the other adjoints.
-int ndlqr_hip_solve_polished_adjoint(NdlqrHipCtx* c, const double* g, int max_steps, int* steps, int* status) {
-  if (!c || !g || max_steps < 1 || max_steps > kPolishMaxSteps) return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_solve_polished_adjoint")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_polished_adjoint")) return cerr;
-  if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_solve_polished_adjoint");
-  if (c->pol.soln_gen == 0 || c->pol.soln_gen != c->soln_gen || !c->pol.fact || c->inputs_replaced)
-    return refuse("ndlqr_hip_solve_polished_adjoint: the resident solution is not that of the latest polish, or its "
-                  "factorisation is gone (a solve, step, re-solve, new inputs or new bounds came after it)");
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  CallerArrays<1> ga = {{const_cast<double*>(g)}, {((size_t)u.rows * u.N - u.m) * d.batch}};
-  int err = ga.classify(c, "ndlqr_hip_solve_polished_adjoint", "g lies");
-  if (!err) err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_polished_adjoint", steps, status);
-  if (err) return err;
-  PolishState& p = c->pol;
-  HIP_TRY(c->adj.ensure(d, c->set[0].stream));
-  HIP_TRY(p.ensure_adjoint(d));
-  HIP_TRY(c->grad_stage.grow(ga.stage));
-  HIP_TRY(sync_all(c));
-  c->cur = 0;
-  BufferSet& s = c->set[0];
-  const hipStream_t st = s.stream;
-  ga.place(c);
-  err = ga.copy(st, true);
-  if (err) return err;
-  c->adj.gen = c->abox.gen = p.adj_gen = 0;
-  const bool strict = (p.flags & NDLQR_FLAG_STRICT_FP) != 0;
-  HIP_TRY(hipEventRecord(s.ev_start, st));
-  ShiftedQR shifted(c);
-  const auto run = [&]() -> int {
-    hipLaunchKernelGGL(ndlqr::adjoint_rhs_generic, dim3(d.N, d.batch), dim3(64), 0, st, u, d, (const double*)ga.dev[0],
-                       c->adj.rhs);
-    HIP_TRY(hipGetLastError());
-    int e = shifted.open_unshifted(p.flags);
-    if (e) return e;
-    hipLaunchKernelGGL(ndlqr::polish_shift_qr, dim3(d.N, d.batch), dim3(64), 0, st, d, (const double*)p.sig,
-                       (const unsigned char*)p.code, c->QR);
-    HIP_TRY(hipGetLastError());
-    c->kept = p.kept;
-    e = shifted.save_record_columns();
-    if (e) return e;
-    hipLaunchKernelGGL(ndlqr::box_fill_rho, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch, 1.0, p.ones);
-    HIP_TRY(hipMemsetAsync(p.word, 0, 2 * sizeof(int), st));
-    hipLaunchKernelGGL(ndlqr::polish_adjoint_start, dim3(d.N, d.batch), dim3(64), 0, st, d, (const int*)p.state,
-                       (const double*)c->adj.rhs, c->adj.z, p.nu, p.abt, p.astate, p.asteps, p.ahere, p.word);
-    HIP_TRY(hipGetLastError());
-    e = polish_steps(c, st, strict, max_steps, {c->adj.rhs, nullptr, nullptr, c->adj.z, p.nu, p.abt, p.astate, p.ahere});
-    if (e) return e;
-    hipLaunchKernelGGL(ndlqr::polish_adjoint_finish, dim3((d.batch + 255) / 256), dim3(256), 0, st, d.batch,
-                       (const unsigned long long*)p.norms, p.astate, p.asteps, (const int*)p.ahere);
-    HIP_TRY(hipGetLastError());
-    return NDLQR_OK;
-  };
-  err = run();
-  const int cerr = shifted.close();
-  if (!err) err = cerr;
-  if (err) {
-    c->state_dirty = true;
-    (void)hipStreamSynchronize(st);
-    return err;
-  }
-  HIP_TRY(hipEventRecord(s.ev_stop, st));
-  err = deliver_iters_status(c, st, p.asteps, p.astate, steps, status);
-  if (err) return err;
-  note_elapsed(c, s);
-  c->adj.gen = c->soln_gen;
-  p.adj_gen = c->soln_gen;
-  return NDLQR_OK;
-}
-
-// developer / test hook: the entry codes of the latest polish in the caller's block sizes, [batch][N][n+m] bytes (host)
-int ndlqr_hip_download_polish_codes(NdlqrHipCtx* c, unsigned char* codes) {
-  if (!c || !codes) return NDLQR_ERR_INVALID;
-  if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_download_polish_codes")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_download_polish_codes")) return cerr;
-  if (c->pol.soln_gen == 0 || c->pol.soln_gen != c->soln_gen)
-    return refuse("ndlqr_hip_download_polish_codes: the resident solution is not that of a polish");
-  const ndlqr::Dims& d = c->d;
-  const ndlqr::Dims& u = c->du;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(sync_all(c));
-  std::vector<unsigned char> h(doubles_QR(d));
-  HIP_TRY(hipMemcpy(h.data(), c->pol.code, h.size(), hipMemcpyDeviceToHost));
-  for (int b = 0; b < d.batch; ++b)
-    for (int k = 0; k < d.N; ++k)
-      for (int j = 0; j < u.n + u.m; ++j)
-        codes[((size_t)b * u.N + k) * (u.n + u.m) + j] = h[((size_t)b * d.N + k) * d.w + (j < u.n ? j : d.n + (j - u.n))];
-  return NDLQR_OK;
-}
-
 
 // Several right-hand sides per problem against ONE kept factorisation each (SURVEY.md 8(f)-2 "multiple right-hand
 // sides"; the reference's NdData holds a single one, src/nddata.h:70-75): nrhs x batch right-hand sides, flat host arrays
@@ -3189,7 +1717,7 @@ int ndlqr_hip_download_solutions(NdlqrHipCtx* c, int p0, int count, double* soln
   return download_packed(c, c->set[c->latest].z, p0, count, soln);
 }
 // ... of the blocks [batch][N][2n+m] at zsrc (the latest solution, or the adjoint solution)
-static int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count, double* soln) {
+int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count, double* soln) {
   const ndlqr::Dims& d = c->d;
   BufferSet& s = c->set[c->cur];
   HIP_TRY(hipSetDevice(c->device));
@@ -3323,144 +1851,6 @@ int ndlqr_hip_download_factors(NdlqrHipCtx* c, int p, double* fact) {
       }
     }
   return NDLQR_OK;
-}
-
-// ------------------------------------------------------------------------------ dense helpers
-
-// Host matrices in, host matrices out (the reference's Matrix* layer, src/linalg.c:55-190). One call = one
-// packed H2D copy of the operands, one kernel, one D2H copy of the result, all on the stream of a pooled
-// scratch (a device buffer + a pinned staging buffer, grown on demand): no allocation and no blocking
-// null-stream copy per call, and calls from different host threads (the reference's tests call these from
-// an OpenMP team, test/parallel_test.c:30-239) run side by side on different scratches.
-namespace {
-struct DenseScratch {
-  DevBuf<double> dev;       // both of one capacity, grown on demand
-  PinnedBuf<double> host;
-  hipStream_t stream = nullptr;
-  int device = -1;  // the device its stream and buffer live on: leased only to calls whose current device is this one
-};
-std::mutex g_dense_mu;
-std::vector<DenseScratch*> g_dense_pool;  // idle scratches; never freed (bounded by the peak concurrency)
-
-struct DenseLease {
-  DenseScratch* s = nullptr;
-  DenseLease() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    std::lock_guard<std::mutex> lock(g_dense_mu);
-    for (size_t i = g_dense_pool.size(); i-- > 0;)
-      if (g_dense_pool[i]->device == dev) {
-        s = g_dense_pool[i];
-        g_dense_pool.erase(g_dense_pool.begin() + (long)i);
-        return;
-      }
-    s = new DenseScratch();
-    s->device = dev;
-  }
-  ~DenseLease() {
-    std::lock_guard<std::mutex> lock(g_dense_mu);
-    g_dense_pool.push_back(s);
-  }
-  int ensure(size_t doubles) {
-    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    size_t cap = s->host.count() ? s->host.count() : 4096;
-    while (cap < doubles) cap *= 2;
-    HIP_TRY(s->dev.grow(cap));
-    HIP_TRY(s->host.grow(cap));
-    return NDLQR_OK;
-  }
-};
-}  // namespace
-
-static int dense_ready() {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-    g_last_error = "no HIP device for the dense Matrix* helpers (no CPU fallback)";
-    fprintf(stderr, "ndlqr_hip: %s\n", g_last_error.c_str());
-    return NDLQR_ERR_NO_DEVICE;
-  }
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_gemm(int tA, int tB, int m, int n, int k, double alpha, const double* A, int lda,
-                   const double* B, int ldb, double beta, double* C, int ldc) {
-  if (dense_ready()) return NDLQR_ERR_NO_DEVICE;
-  if (m <= 0 || n <= 0 || k < 0 || !A || !B || !C) return NDLQR_ERR_INVALID;
-  // stored shapes: A is (Ar x Ac) with leading dimension lda, ...; the last column ends after its rows
-  const int Ar = tA ? k : m, Ac = tA ? m : k, Br = tB ? n : k, Bc = tB ? k : n;
-  if (k > 0 && (lda < Ar || ldb < Br)) return NDLQR_ERR_INVALID;
-  if (ldc < m) return NDLQR_ERR_INVALID;
-  const size_t nA = k > 0 ? (size_t)lda * (Ac - 1) + Ar : 0, nB = k > 0 ? (size_t)ldb * (Bc - 1) + Br : 0,
-               nC = (size_t)ldc * (n - 1) + m;
-  DenseLease L;
-  const int err = L.ensure(nA + nB + nC);
-  if (err) return err;
-  DenseScratch* s = L.s;
-  memcpy(s->host, A, sizeof(double) * nA);
-  memcpy(s->host + nA, B, sizeof(double) * nB);
-  memcpy(s->host + nA + nB, C, sizeof(double) * nC);
-  HIP_TRY(hipMemcpyAsync(s->dev, s->host, sizeof(double) * (nA + nB + nC), hipMemcpyHostToDevice, s->stream));
-  const int total = m * n;
-  hipLaunchKernelGGL(ndlqr::dense_gemm, dim3((total + 255) / 256), dim3(256), 0, s->stream, tA, tB, m, n, k, alpha,
-                     s->dev, lda, s->dev + nA, ldb, beta, s->dev + nA + nB, ldc);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(s->host + nA + nB, s->dev + nA + nB, sizeof(double) * nC, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  memcpy(C, s->host + nA + nB, sizeof(double) * nC);
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_potrf_lower(int n, double* A, int lda) {
-  if (dense_ready()) return NDLQR_ERR_NO_DEVICE;
-  if (n <= 0 || !A) return NDLQR_ERR_INVALID;
-  if (lda < n) return NDLQR_ERR_INVALID;
-  const size_t nA = (size_t)lda * (n - 1) + n;
-  DenseLease L;
-  const int err = L.ensure(nA + 1);  // + one slot for the failure word
-  if (err) return err;
-  DenseScratch* s = L.s;
-  memcpy(s->host, A, sizeof(double) * nA);
-  s->host[nA] = 0.0;  // (all-zero bits: the int the kernel writes into starts at 0)
-  HIP_TRY(hipMemcpyAsync(s->dev, s->host, sizeof(double) * (nA + 1), hipMemcpyHostToDevice, s->stream));
-  hipLaunchKernelGGL(ndlqr::dense_potrf, dim3(1), dim3(256), 0, s->stream, n, s->dev, lda,
-                     reinterpret_cast<int*>(s->dev + nA));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(s->host, s->dev, sizeof(double) * (nA + 1), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  memcpy(A, s->host, sizeof(double) * nA);
-  int info = 0;
-  memcpy(&info, s->host + nA, sizeof(int));
-  return info ? -1 : 0;
-}
-
-// which: 0 = L L' x = b (both substitutions), 1 = L x = b, 2 = L' x = b
-static int dense_tri_solve(int which, int n, int nrhs, const double* Lm, int ldl, double* B, int ldb) {
-  if (dense_ready()) return NDLQR_ERR_NO_DEVICE;
-  if (n <= 0 || nrhs <= 0 || !Lm || !B) return NDLQR_ERR_INVALID;
-  if (ldl < n || ldb < n) return NDLQR_ERR_INVALID;
-  const size_t nL = (size_t)ldl * (n - 1) + n, nB = (size_t)ldb * (nrhs - 1) + n;
-  DenseLease L;
-  const int err = L.ensure(nL + nB);
-  if (err) return err;
-  DenseScratch* s = L.s;
-  memcpy(s->host, Lm, sizeof(double) * nL);
-  memcpy(s->host + nL, B, sizeof(double) * nB);
-  HIP_TRY(hipMemcpyAsync(s->dev, s->host, sizeof(double) * (nL + nB), hipMemcpyHostToDevice, s->stream));
-  hipLaunchKernelGGL(ndlqr::dense_potrs, dim3((nrhs + 63) / 64), dim3(64), 0, s->stream, n, nrhs, s->dev, ldl,
-                     s->dev + nL, ldb, which);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(s->host + nL, s->dev + nL, sizeof(double) * nB, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  memcpy(B, s->host + nL, sizeof(double) * nB);
-  return NDLQR_OK;
-}
-
-int ndlqr_hip_potrs_lower(int n, int nrhs, const double* L, int ldl, double* B, int ldb) {
-  return dense_tri_solve(0, n, nrhs, L, ldl, B, ldb);
-}
-
-int ndlqr_hip_trsv_lower(int n, int nrhs, const double* L, int ldl, double* B, int ldb, int transposed) {
-  return dense_tri_solve(transposed ? 2 : 1, n, nrhs, L, ldl, B, ldb);
 }
 
 // developer hook (tools/debug_compare.py; not part of include/*.h): raw copy of an internal array,

@@ -5,6 +5,8 @@ test/solver_test.c) -- plus: every symbol declared in include/*.h is exported, a
 fails loudly (no CPU fallback) when no HIP device is present."""
 import ctypes as C
 import os
+import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -27,6 +29,21 @@ def test_every_declared_symbol_is_exported(ndlqr, L):
     missing = [s for s in names if not hasattr(L, s)]
     assert not missing, missing
     assert b"gfx950" in L.ndlqr_Version()
+
+
+def test_no_internal_symbol_is_exported(ndlqr):
+    """Every dynamic symbol with a C name is public API, a developer hook or a per-instance dispatch object: the
+    units of the HIP host layer share their internals through hidden declarations, not through the export table."""
+    import rslqr_amd.build as build
+    ndlqr.lib()  # (built if need be)
+    out = subprocess.run(["nm", "-D", "--defined-only", build.LIB], capture_output=True, text=True, check=True).stdout
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert len(names) > 100
+    declared = set(ndlqr.exported_symbols())
+    allowed = re.compile(r"ndlqr_hip_debug_\w+|ndlqr_small_\d+_\d+|ndlqr_reduced_\d+")
+    leaked = sorted(s for s in names if not s.startswith("_Z") and not s.startswith("__hip")
+                    and s not in declared and not allowed.fullmatch(s))
+    assert not leaked, leaked
 
 
 def test_build_tree(ndlqr, L):  # test/binarytree_test.c:4-21

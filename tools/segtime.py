@@ -48,12 +48,14 @@ def build():
     objs = [os.path.join(b.OBJDIR, s + ".o") for s in b.C_SOURCES]
     o = os.path.join(b.OBJDIR, "ndlqr_hip_seg.o")
     hipcc = b._hipcc()
-    # one translation unit with every instance (the counters are one __device__ array per unit)
+    # the core as one translation unit with every instance of both families (the counters are one __device__ array per
+    # unit); the feature units, which hold no instrumented kernel, are linked as the library's build left them
     subprocess.run([hipcc, "--offload-arch=" + b.ARCH, "-std=c++17", "-O3", "-ffp-contract=off", "-fPIC",
                     "-DNDLQR_SEGTIME", "-DNDLQR_SINGLE_TU", "-I" + b.INCLUDE, "-I" + b.CSRC, "-c",
                     os.path.join(b.CSRC, b.HIP_MAIN), "-o", o], check=True)
-    subprocess.run([hipcc, "--offload-arch=" + b.ARCH, "-shared", "-fPIC", "-o", SEGLIB] + objs + [o, "-lm"],
-                   check=True)
+    features = b.hip_objects(skip=(b.HIP_MAIN, b.HIP_INSTANCE, b.HIP_REDUCED))
+    subprocess.run([hipcc, "--offload-arch=" + b.ARCH, "-shared", "-fPIC", "-o", SEGLIB] + objs + [o] + features +
+                   ["-lm", "-lpthread"], check=True)
     print("built", SEGLIB)
 
 
