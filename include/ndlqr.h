@@ -416,6 +416,38 @@ int ndlqr_InitializeBatchFlatDense(NdLqrBatchSolver* bs, const double* A, const 
                                    const double* H, const double* R, const double* q, const double* r,
                                    const double* d, const double* x0);
 int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs); /* 1: dense-cost mode, 0: not */
+/* General linear inequality constraints: per knot p >= 1 rows
+ *   lo_k <= C_k x_k + D_k u_k <= hi_k,   C [batch][N][p*n], D [batch][N][p*m] column-major per knot like A and B,
+ * lo, hi [P][N][p] with P = batch, or P = 1 with NDLQR_BOUNDS_SHARED in `flags`. Entries of lo, hi may be +-inf (a row with
+ * both infinite is unbounded); D of the last knot is never loaded. The nine arrays before p are those of
+ * ndlqr_InitializeBatchFlatDense (a diagonal cost is passed as a dense one); host or device pointers (this device's).
+ *   ndlqr_InitializeBatchFlatConstrained puts the solver into dense-cost mode exactly as the dense initialiser does --
+ *   ndlqr_SolveBatch, ndlqr_BatchSetRhsFlat + ndlqr_SolveBatchRhsOnly and ndlqr_SolveBatchAdjoint work as there and give the
+ *   UNCONSTRAINED answers -- and retains A, B, Q, H, R, the right-hand side, C and D on the device (constrained mode,
+ *   ndlqr_BatchIsConstrained). Every other initialiser leaves constrained mode.
+ *   ndlqr_BatchSetConstraintBounds: new bounds without touching C, D or the factorisation; lo > hi or a NaN is refused
+ *   before anything is replaced; a change of WHICH rows are bounded drops the remembered factorisation.
+ *   ndlqr_SolveBatchLinConstrained: scaled ADMM on the rows (section 3.9 carried to w = C x + D u) with the fixed penalty
+ *   s->rho; the settings rho, alpha, eps_abs, eps_rel, max_iter, check_every, warm_start are those of
+ *   ndlqr_SolveBatchBoxConstrained with the same defaults (0, or s == NULL). The cost shifted by rho C'MC, rho C'MD, rho D'MD
+ *   (M: the bounded rows) is reduced and factored once -- or not at all while rho, the flags, the inputs and the bounded
+ *   pattern stay as they were (ndlqr_BatchSetRhsFlat keeps them) --, every iteration is one re-solve and one update
+ *   kernel. iters / status [batch] (may be NULL): status 1 converged, 2 max_iter reached, 3 not finite. The solution that
+ *   ndlqr_CopyBatchSolution(s) delivers afterwards is [lambda, x, u] of the last re-solve: the dynamics hold exactly, the
+ *   rows hold to within r_prim. A plain solve afterwards gives what it gave before, bit for bit.
+ *   ndlqr_CopyBatchConstraintMultipliers: mu = rho y, [batch][N][p] (mu > 0 at an upper, < 0 at a lower bound).
+ *   ndlqr_CopyBatchConstraintResiduals: [batch][4] = r_prim | r_dual | sp | sd of every problem's last update, with the
+ *   meaning of ndlqr_CopyBatchBoxResiduals: r_prim = max |w - v|, r_dual = rho max |[C D]'(v - v_prev)|,
+ *   sp = max(max |w|, max |v|), sd = rho max |[C D]' y|.
+ * REFUSED by name (NDLQR_ERR_INVALID, ndlqr_hip_last_error()): s->adapt_every > 0 (adaptive penalty); everything of the box
+ * solve -- acceleration, infeasibility detection, polish, box adjoint and bound gradients -- as in dense-cost mode;
+ * ndlqr_BatchStepAsync. There is no adjoint through the constrained solve yet. */
+int ndlqr_InitializeBatchFlatConstrained(NdLqrBatchSolver* bs, const double* A, const double* B, const double* Q,
+                                         const double* H, const double* R, const double* q, const double* r,
+                                         const double* d, const double* x0, int p, const double* C, const double* D,
+                                         const double* lo, const double* hi, unsigned flags);
+int ndlqr_BatchIsConstrained(const NdLqrBatchSolver* bs); /* 1: constrained mode, 0: not */
+int ndlqr_BatchSetConstraintBounds(NdLqrBatchSolver* bs, const double* lo, const double* hi, unsigned flags);
 /* Seeded synthetic problems, problem p seeded with seed0 + p; generated on the
  * host, packed and uploaded. */
 int ndlqr_InitializeBatchSynthetic(NdLqrBatchSolver* bs, uint64_t seed0);
@@ -638,6 +670,10 @@ int ndlqr_CopyBatchBoundMultipliers(NdLqrBatchSolver* bs, double* mu_x, double* 
 int ndlqr_CopyBatchBoxPenalties(NdLqrBatchSolver* bs, double* rho);
 int ndlqr_CopyBatchBoxResiduals(NdLqrBatchSolver* bs, double* resid);
 int ndlqr_CopyBatchBoxAdjointResiduals(NdLqrBatchSolver* bs, double* resid);
+/* the constrained solve of ndlqr_InitializeBatchFlatConstrained (above) and its read-outs */
+int ndlqr_SolveBatchLinConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status);
+int ndlqr_CopyBatchConstraintMultipliers(NdLqrBatchSolver* bs, double* mu);
+int ndlqr_CopyBatchConstraintResiduals(NdLqrBatchSolver* bs, double* resid);
 /* additive: primal infeasibility detection in the box-constrained solve. State bounds make
  * infeasibility an ordinary event in MPC; without detection such a problem keeps the whole batch iterating to max_iter.
  *   ndlqr_BatchSetInfeasibilityDetection: every == 0 (the initial state) = off: no call changes a bit of its result.

@@ -6,7 +6,7 @@
  * (src/nested_dissection.c, src/linalg_custom.c): everything behind these calls runs on
  * gfx950. Implemented in rslqr_amd/csrc: the context, the solve pipeline and the downloads in ndlqr_hip.hip, each
  * optional feature in a unit of its own (hip_grad.hip: adjoint and gradients, hip_box.hip: bounds, ADMM, polish,
- * hip_refine.hip, hip_cost.hip: dense costs, hip_dense.hip: the Matrix* helpers).
+ * hip_refine.hip, hip_cost.hip: dense costs, hip_lin.hip: linear inequality constraints, hip_dense.hip: the Matrix* helpers).
  *
  * Device data model (all fp64):
  *   inputs  AB  [batch][N][n][n+m]   row i of knot k = [A_k(i,:) | B_k(i,:)]   (A,B row-major)
@@ -102,6 +102,35 @@ int ndlqr_hip_cost_phase_ms(NdlqrHipCtx* ctx, double* out3);
 int ndlqr_hip_set_rhs_dense(NdlqrHipCtx* ctx, const double* q, const double* r, const double* d, const double* x0);
 int ndlqr_hip_download_cost_reduction(NdlqrHipCtx* ctx, double* L, double* LR, double* G, double* At, double* Bt,
                                       double* qt, double* rt, double* dt, double* x0t);
+/* General linear inequality constraints lo_k <= C_k x_k + D_k u_k <= hi_k (ndlqr.h: ndlqr_InitializeBatchFlatConstrained;
+ * DESIGN.md section 3.17). ndlqr_hip_init_constrained takes the nine arrays of ndlqr_hip_init_dense and p >= 1 rows per
+ * knot, C [batch][N][p*n], D [batch][N][p*m] (column-major per knot; D of the last knot is never loaded), lo, hi [P][N][p]
+ * with P = batch, or 1 when `shared`; entries of lo, hi may be +-inf. Host or this device's memory. It retains A, B, Q, H,
+ * R, the right-hand side, C and D on the device and leaves the context in dense-cost mode exactly as ndlqr_hip_init_dense
+ * does -- constrained mode (ndlqr_hip_is_constrained) is dense-cost mode with constraints; ndlqr_hip_init_dense,
+ * ndlqr_hip_pack_flat_device and ndlqr_hip_upload_inputs leave it.
+ * ndlqr_hip_set_constraint_bounds: new lo, hi; refuses lo > hi or NaN before anything is replaced; a new bounded pattern
+ * drops the remembered shifted factorisation.
+ * ndlqr_hip_solve_constrained: scaled ADMM with the fixed penalty rho (arguments and statuses of ndlqr_hip_solve_box;
+ * adapt_every > 0, the adaptive penalty, is refused); the
+ * resident solution afterwards is [lambda, x, u] of the last re-solve in the caller's variables.
+ * ndlqr_hip_download_constraint_multipliers: mu = rho y [batch][N][p]; ndlqr_hip_download_constraint_residuals: [batch][4]
+ * as ndlqr_hip_download_box_residuals. ndlqr_hip_download_constraint_reduction (read-out for the tests, HOST memory, any
+ * pointer may be NULL): the shifted costs Qs [batch][N][n*n], Hs [batch][N][n*m], Rs [batch][N][m*m], the shifted records and
+ * reduced problem as ndlqr_hip_download_cost_reduction gives the plain ones, and the iterates v, y [batch][N][p].
+ * Every refusal opens ndlqr_hip_last_error() with the function's name. */
+int ndlqr_hip_init_constrained(NdlqrHipCtx* ctx, const double* A, const double* B, const double* Q, const double* H,
+                               const double* R, const double* q, const double* r, const double* d, const double* x0, int p,
+                               const double* C, const double* D, const double* lo, const double* hi, int shared);
+int ndlqr_hip_is_constrained(const NdlqrHipCtx* ctx);
+int ndlqr_hip_set_constraint_bounds(NdlqrHipCtx* ctx, const double* lo, const double* hi, int shared);
+int ndlqr_hip_solve_constrained(NdlqrHipCtx* ctx, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
+                                int check_every, int warm_start, int adapt_every, int* iters, int* status);
+int ndlqr_hip_download_constraint_multipliers(NdlqrHipCtx* ctx, double* mu);
+int ndlqr_hip_download_constraint_residuals(NdlqrHipCtx* ctx, double* resid);
+int ndlqr_hip_download_constraint_reduction(NdlqrHipCtx* ctx, double* Qs, double* Hs, double* Rs, double* L, double* LR,
+                                            double* G, double* At, double* Bt, double* qt, double* rt, double* dt, double* x0t,
+                                            double* v, double* y);
 /* Device pointers for zero-copy producers (order: AB, QR, rhs, F, z). Allocates the factor array and
  * sets the pipeline depth to 1, so that z is THE solution buffer from then on. */
 int ndlqr_hip_device_pointers(NdlqrHipCtx* ctx, void** out5);

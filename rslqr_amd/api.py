@@ -247,6 +247,13 @@ def lib():
     proto("ndlqr_BatchCostIsDense", ci, vp)
     proto("ndlqr_hip_download_cost_reduction", ci, vp, dp, dp, dp, dp, dp, dp, dp, dp, dp)
     proto("ndlqr_hip_cost_phase_ms", ci, vp, dp)
+    proto("ndlqr_InitializeBatchFlatConstrained", ci, vp, dp, dp, dp, dp, dp, dp, dp, dp, dp, ci, dp, dp, dp, dp, C.c_uint)
+    proto("ndlqr_BatchIsConstrained", ci, vp)
+    proto("ndlqr_BatchSetConstraintBounds", ci, vp, dp, dp, C.c_uint)
+    proto("ndlqr_SolveBatchLinConstrained", ci, vp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_CopyBatchConstraintMultipliers", ci, vp, dp)
+    proto("ndlqr_CopyBatchConstraintResiduals", ci, vp, dp)
+    proto("ndlqr_hip_download_constraint_reduction", ci, vp, *([dp] * 14))
     proto("ndlqr_InitializeBatchFlatDevice", ci, vp, vp, vp, vp, vp, vp, vp, vp, vp)
     proto("ndlqr_SolveBatch", ci, vp)
     proto("ndlqr_BatchSetRhsFlat", ci, vp, dp, dp, dp, dp)
@@ -502,6 +509,117 @@ class BatchSolver:
                                                                    ("L", "LR", "G", "At", "Bt", "qt", "rt", "dt", "x0t")])
         if err:
             raise RuntimeError("ndlqr_hip_download_cost_reduction failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    # ---- linear inequality constraints (include/ndlqr.h: ndlqr_InitializeBatchFlatConstrained)
+    def _constraint_bounds(self, lo, hi, p=None):
+        """(lo, hi, shared, keep-alive list) for the C calls: numpy bounds of shape (p,), (N, p) -- shared -- or
+        (batch, N, p); a DeviceArray holds batch * N * p doubles."""
+        N, B = self.N, self.batch
+        p = self._rows if p is None else p
+        host = [a if hasattr(a, "ptr") else np.asarray(a, dtype=np.float64) for a in (lo, hi)]
+        shared = all(not hasattr(a, "ptr") and a.ndim <= 2 for a in host)
+        ptrs, keep = [], []
+        for a in host:
+            if not hasattr(a, "ptr"):
+                if a.shape not in ((p,), (N, p), (B, N, p)):
+                    raise ValueError("bounds of shape %s: expected (%d,), (%d, %d) or (%d, %d, %d)" % (a.shape, p, N, p, B, N, p))
+                a = np.ascontiguousarray(np.broadcast_to(a, (N, p) if shared else (B, N, p)))
+                keep.append(a)
+            ptrs.append(_any_ptr(a, (1 if shared else B) * N * p))
+        return ptrs[0], ptrs[1], shared, keep
+
+    def initialize_flat_constrained(self, A, B, Q, H, R, q, r, d, x0, C_, D_, lo, hi):
+        """ndlqr_InitializeBatchFlatConstrained: the nine arrays of initialize_flat_dense, then the constraint rows
+        lo <= C x + D u <= hi per knot: C_ [batch, N, p*n], D_ [batch, N, p*m] column-major per knot (p is taken from C_'s
+        size) and lo, hi of shape (p,), (N, p) -- one set for every problem -- or (batch, N, p); entries may be +-inf.
+        Arrays are numpy arrays or device memory (`ptr`, `size`). Afterwards the solver is in constrained mode
+        (is_constrained()): dense-cost mode with solve_constrained() available."""
+        n, m, N, bt = self.n, self.m, self.N, self.batch
+        csize = C_.size
+        if csize % (bt * N * n):
+            raise ValueError("bad size for C")
+        p = csize // (bt * N * n)
+        sizes = dict(A=bt * N * n * n, B=bt * N * n * m, Q=bt * N * n * n, H=bt * N * n * m, R=bt * N * m * m,
+                     q=bt * N * n, r=bt * N * m, d=bt * N * n, x0=bt * n, C=bt * N * p * n, D=bt * N * p * m)
+        ptrs, keep = [], []
+        for name, a in zip(("A", "B", "Q", "H", "R", "q", "r", "d", "x0", "C", "D"), (A, B, Q, H, R, q, r, d, x0, C_, D_)):
+            if a is None:
+                if name != "H":
+                    raise ValueError("%s is missing (only H may be None)" % name)
+                ptrs.append(None)
+                continue
+            if not hasattr(a, "ptr"):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != sizes[name]:
+                    raise ValueError("bad size for %s" % name)
+                keep.append(a)
+            ptrs.append(_any_ptr(a, sizes[name]))
+        plo, phi, shared, keep2 = self._constraint_bounds(lo, hi, p)
+        err = self.L.ndlqr_InitializeBatchFlatConstrained(self.h, *ptrs[:9], p, ptrs[9], ptrs[10], plo, phi,
+                                                          BOUNDS_SHARED if shared else 0)
+        if err:
+            raise RuntimeError("ndlqr_InitializeBatchFlatConstrained failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._rows = p  # (only now: a refused call leaves the context, and the shapes checked here, as they were)
+
+    def is_constrained(self):
+        """ndlqr_BatchIsConstrained: True between initialize_flat_constrained and the next other initialiser."""
+        return bool(self.L.ndlqr_BatchIsConstrained(self.h))
+
+    def set_constraint_bounds(self, lo, hi):
+        """ndlqr_BatchSetConstraintBounds: new lo, hi (shapes as for initialize_flat_constrained). Raises on a refusal
+        (lo > hi, NaN, not in constrained mode); the previous bounds then stay."""
+        if not getattr(self, "_rows", 0):
+            raise RuntimeError("ndlqr_BatchSetConstraintBounds: initialize_flat_constrained first")
+        plo, phi, shared, keep = self._constraint_bounds(lo, hi)
+        err = self.L.ndlqr_BatchSetConstraintBounds(self.h, plo, phi, BOUNDS_SHARED if shared else 0)
+        if err:
+            raise RuntimeError("ndlqr_BatchSetConstraintBounds failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+
+    def solve_constrained(self, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0, warm_start=False,
+                          adapt_every=0):
+        """ndlqr_SolveBatchLinConstrained (0 = the library's default of the box solve for every setting; adapt_every > 0 is
+        refused). Returns (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached, 3 = not
+        finite. solutions() afterwards gives [lambda, x, u] of the last re-solve. Raises on a nonzero return."""
+        st = NdLqrBoxSettingsFull(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0,
+                                  int(adapt_every), 0.0, 0.0)
+        iters = np.zeros(self.batch, dtype=np.int32)
+        status = np.zeros(self.batch, dtype=np.int32)
+        err = self.L.ndlqr_SolveBatchLinConstrained(self.h, C.byref(st), iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                                    status.ctypes.data_as(C.POINTER(C.c_int)))
+        if err:
+            raise RuntimeError("ndlqr_SolveBatchLinConstrained failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return iters, status
+
+    def constraint_multipliers(self):
+        """ndlqr_CopyBatchConstraintMultipliers: mu = rho y, [batch, N, p]."""
+        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)))
+        err = self.L.ndlqr_CopyBatchConstraintMultipliers(self.h, _ptr(out))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchConstraintMultipliers failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def constraint_residuals(self):
+        """ndlqr_CopyBatchConstraintResiduals: [batch, 4] = r_prim | r_dual | s_prim | s_dual of the last constrained solve."""
+        out = np.zeros((self.batch, 4))
+        err = self.L.ndlqr_CopyBatchConstraintResiduals(self.h, _ptr(out))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchConstraintResiduals failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def constraint_reduction(self):
+        """ndlqr_hip_download_constraint_reduction (read-out for the tests): dict of numpy arrays -- the shifted costs Qs, Hs,
+        Rs, the shifted records L, LR, G and reduced problem At .. x0t (as cost_reduction gives the plain ones), and the
+        iterates v, y [batch, N, p] of the latest constrained solve."""
+        n, m, N, bt, p = self.n, self.m, self.N, self.batch, getattr(self, "_rows", 1)
+        out = dict(Qs=np.zeros((bt, N, n * n)), Hs=np.zeros((bt, N, n * m)), Rs=np.zeros((bt, N, m * m)),
+                   L=np.zeros((bt, N, n * n)), LR=np.zeros((bt, N, m * m)), G=np.zeros((bt, N, m * n)),
+                   At=np.zeros((bt, N, n * n)), Bt=np.zeros((bt, N, n * m)), qt=np.zeros((bt, N, n)), rt=np.zeros((bt, N, m)),
+                   dt=np.zeros((bt, N, n)), x0t=np.zeros((bt, n)), v=np.zeros((bt, N, p)), y=np.zeros((bt, N, p)))
+        err = self.L.ndlqr_hip_download_constraint_reduction(self.ctx, *[_ptr(out[k]) for k in (
+            "Qs", "Hs", "Rs", "L", "LR", "G", "At", "Bt", "qt", "rt", "dt", "x0t", "v", "y")])
+        if err:
+            raise RuntimeError("ndlqr_hip_download_constraint_reduction failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
 
     def initialize_synthetic(self, seed0):

@@ -185,6 +185,41 @@ int ndlqr_InitializeBatchFlatDense(NdLqrBatchSolver* bs, const double* A, const 
 }
 int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs) { return bs ? ndlqr_hip_cost_is_dense(bs->ctx) : 0; }
 
+int ndlqr_InitializeBatchFlatConstrained(NdLqrBatchSolver* bs, const double* A, const double* B, const double* Q,
+                                         const double* H, const double* R, const double* q, const double* r,
+                                         const double* d, const double* x0, int p, const double* C, const double* D,
+                                         const double* lo, const double* hi, unsigned flags) {
+  if (!bs || (flags & ~NDLQR_BOUNDS_SHARED)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_init_constrained(bs->ctx, A, B, Q, H, R, q, r, d, x0, p, C, D, lo, hi, (flags & NDLQR_BOUNDS_SHARED) ? 1 : 0);
+}
+int ndlqr_BatchIsConstrained(const NdLqrBatchSolver* bs) { return bs ? ndlqr_hip_is_constrained(bs->ctx) : 0; }
+int ndlqr_BatchSetConstraintBounds(NdLqrBatchSolver* bs, const double* lo, const double* hi, unsigned flags) {
+  if (!bs || (flags & ~NDLQR_BOUNDS_SHARED)) return NDLQR_ERR_INVALID;
+  /* (lo <= hi is checked on the device, where the bounds may already live) */
+  return ndlqr_hip_set_constraint_bounds(bs->ctx, lo, hi, (flags & NDLQR_BOUNDS_SHARED) ? 1 : 0);
+}
+int ndlqr_SolveBatchLinConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status) {
+  NdLqrBoxSettings z;
+  if (!bs) return NDLQR_ERR_INVALID;
+  memset(&z, 0, sizeof(z));
+  if (s) z = *s;
+  if (z.rho < 0.0 || z.alpha < 0.0 || z.alpha >= 2.0 || z.eps_abs < 0.0 || z.eps_rel < 0.0 || z.max_iter < 0 ||
+      z.check_every < 0 || z.adapt_every < 0)
+    return NDLQR_ERR_INVALID;
+  return ndlqr_hip_solve_constrained(bs->ctx, z.rho > 0.0 ? z.rho : 0.1, z.alpha > 0.0 ? z.alpha : 1.6,
+                                     z.eps_abs > 0.0 ? z.eps_abs : 1e-6, z.eps_rel > 0.0 ? z.eps_rel : 1e-6,
+                                     z.max_iter > 0 ? z.max_iter : 4000, z.check_every > 0 ? z.check_every : 10,
+                                     z.warm_start != 0, z.adapt_every, iters, status);
+}
+int ndlqr_CopyBatchConstraintMultipliers(NdLqrBatchSolver* bs, double* mu) {
+  if (!bs || !mu) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_multipliers(bs->ctx, mu);
+}
+int ndlqr_CopyBatchConstraintResiduals(NdLqrBatchSolver* bs, double* resid) {
+  if (!bs || !resid) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_residuals(bs->ctx, resid);
+}
+
 /* Synthetic problems of one staging chunk are generated and packed side by side on host threads
  * (one splitmix64 stream per problem, so the result does not depend on the thread count): the
  * (64,16,512) x 256 family is 37 s of Box-Muller draws on one core. */

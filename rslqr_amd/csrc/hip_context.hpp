@@ -392,7 +392,9 @@ struct MultiRhsState {
 // [batch][nvars], the packed vector S' goes through on its way into the adjoint solve.
 struct CostState {
   bool dense = false;
+  unsigned long long mapped_gen = 0;  // the resident solution of this generation is already in the caller's variables (a constrained solve's): the delivery does not map it back
   DevBuf<double> rec, At, Bt, qt, rt, dt, x0t, ones, stage;
+  bool mapped(unsigned long long gen) const { return mapped_gen != 0 && mapped_gen == gen; }
   double phase_ms[3] = {};  // under NDLQR_FLAG_PROFILE: device time of the latest cost_factor + cost_transform | cost_apply_t | cost_apply
   static size_t record_doubles(const ndlqr::Dims& u) { return (size_t)u.n * u.n + (size_t)u.m * u.m + (size_t)u.m * u.n; }
   hipError_t ensure(const ndlqr::Dims& u) {
@@ -400,6 +402,49 @@ struct CostState {
     return first_error({rec.ensure(kn * record_doubles(u)), At.ensure(kn * u.n * u.n), Bt.ensure(kn * u.n * u.m),
                         qt.ensure(kn * u.n), rt.ensure(kn * u.m), dt.ensure(kn * u.n), x0t.ensure((size_t)u.batch * u.n),
                         ones.ensure(kn * u.w), stage.ensure((size_t)u.batch * ((size_t)u.rows * u.N - u.m))});
+  }
+};
+
+// General linear inequality constraints lo <= C x + D u <= hi by ADMM on the dense-cost reduction
+// (ndlqr_hip_init_constrained / ndlqr_hip_solve_constrained, kernels_lin.hpp). active: the
+// resident problem came from the constrained initialiser -- a dense-cost mode with constraints; every other initialiser
+// leaves it. All in the CALLER's block sizes and horizon (u), p rows per knot. Retained inputs in the flat layout: A, B,
+// Q, H (has_H), R and the caller's right-hand side q, r, d, x0 (rhs_new: replaced since the shifted S' last ran); C
+// [batch][N][p n], D [batch][N][p m]; lo, hi, mask [P][N][p] (bstride 0: shared). The shifted problem: costs Qs, Hs, Rs,
+// records rec, and the reduced flat arrays At .. x0t (CostState keeps the plain ones). Iteration state: v, y [batch][N][p],
+// the re-solve's z~ and two right-hand sides in the device layout, per problem status, iters, resid [4]; word: the
+// running count | lo > hi | pattern changed. The shifted reduction and factorisation are remembered (fact) with rho_value,
+// the flags and what the factorisation left (kept). soln_gen: the solution generation the latest constrained solve left.
+struct LinState {
+  bool active = false, has_H = false, shared = false, have_vy = false, rhs_new = true, fact = false;
+  int p = 0;
+  size_t bstride = 0;
+  double rho_value = 0.0;
+  unsigned flags = 0;
+  KeptState kept;
+  unsigned long long soln_gen = 0;
+  size_t lds_asked[5] = {};  // dynamic LDS already asked for lin_shift_cost | lin_start | lin_update<true> | <false> | lin_finish
+  DevBuf<double> A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, Qs, Hs, Rs, rec, At, Bt, qt, rt, dt, x0t, v, y, z, rhs[2], resid;
+  DevBuf<unsigned char> mask;
+  DevBuf<int> status, iters, word;
+  PinnedBuf<int> h_word;
+  // the buffers that depend on p are allocated again when p changes
+  hipError_t ensure(const ndlqr::Dims& u, const ndlqr::Dims& dd, int rows_per_knot, hipStream_t st) {
+    const size_t kn = (size_t)u.batch * u.N, n = (size_t)u.n, m = (size_t)u.m, nb = (size_t)u.batch;
+    if (rows_per_knot != p)
+      for (DevBuf<double>* b : {&C, &D, &lo, &hi, &v, &y}) b->reset();
+    if (rows_per_knot != p) mask.reset();
+    p = rows_per_knot;
+    const size_t np = kn * (size_t)p;
+    return first_error({A.ensure(kn * n * n), B.ensure(kn * n * m), Q.ensure(kn * n * n), H.ensure(kn * n * m), R.ensure(kn * m * m),
+                        q.ensure(kn * n), r.ensure(kn * m), d.ensure(kn * n), x0.ensure(nb * n), C.ensure(np * n), D.ensure(np * m),
+                        lo.ensure(np), hi.ensure(np), mask.ensure_zeroed(np, st), Qs.ensure(kn * n * n), Hs.ensure(kn * n * m),
+                        Rs.ensure(kn * m * m), rec.ensure(kn * (n * n + m * m + m * n)), At.ensure(kn * n * n),
+                        Bt.ensure(kn * n * m), qt.ensure(kn * n), rt.ensure(kn * m), dt.ensure(kn * n), x0t.ensure(nb * n),
+                        v.ensure(np), y.ensure(np),
+                        z.ensure_zeroed(doubles_z(dd), st),  // (entries a re-solve does not write: the pad rows)
+                        rhs[0].ensure(doubles_z(dd)), rhs[1].ensure(doubles_z(dd)), resid.ensure(4 * nb),
+                        status.ensure(nb), iters.ensure(nb), word.ensure(3), h_word.ensure(3)});
   }
 };
 
@@ -468,9 +513,10 @@ struct NdlqrHipCtx {
   PolishState pol;
   MultiRhsState multi;
   CostState cost;
+  LinState lin;
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // the remembered shifted factorisations (ADMM's and the polish's) no longer match the records / factors
-  void forget_shifted() { box.fact = pol.fact = false; }
+  void forget_shifted() { box.fact = pol.fact = lin.fact = false; }
   // profile
   std::vector<PendingEvent> pending;
   std::vector<hipEvent_t> event_pool;

@@ -58,18 +58,36 @@ hipError_t cost_reduce_vector(NdlqrHipCtx* c, double* vec, hipStream_t st) {
                      nullptr, nullptr, nullptr, nullptr, vec, nullptr, nullptr, nullptr, nullptr, vec);
 }
 
-// S' of the flat right-hand side at q, r, d, x0 (device) into the reduced flat arrays, on `st`
-static hipError_t cost_reduce_rhs(NdlqrHipCtx* c, const double* q, const double* r, const double* d, const double* x0,
-                                  hipStream_t st) {
+// S' (records `rec`) of the flat right-hand side at q, r, d, x0 (device) into the flat arrays qt, rt, dt, x0t, on `st`
+hipError_t cost_reduce_rhs_to(NdlqrHipCtx* c, const double* rec, const double* q, const double* r, const double* d,
+                              const double* x0, double* qt, double* rt, double* dt, double* x0t, hipStream_t st) {
   const ndlqr::Dims& u = c->du;
-  CostState& k = c->cost;
   CostPhase phase(c, st, 1);
-  const hipError_t e = launch_cost(ndlqr::cost_apply_t, ndlqr::cost_apply_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N,
-                                   k.rec.get(), q, r, d, x0, nullptr, k.qt.get(), k.rt.get(), k.dt.get(), k.x0t.get(), nullptr);
+  const hipError_t e = launch_cost(ndlqr::cost_apply_t, ndlqr::cost_apply_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, rec, q, r,
+                                   d, x0, nullptr, qt, rt, dt, x0t, nullptr);
   phase.stop();
   return e;
 }
-
+// ... into the reduced flat arrays of the plain problem
+static hipError_t cost_reduce_rhs(NdlqrHipCtx* c, const double* q, const double* r, const double* d, const double* x0,
+                                  hipStream_t st) {
+  CostState& k = c->cost;
+  return cost_reduce_rhs_to(c, k.rec, q, r, d, x0, k.qt, k.rt, k.dt, k.x0t, st);
+}
+// The reduction of the dense costs Q, H (null: zero), R and of A, B (device, the caller's flat layout): the records into
+// `rec`, A~, B~ into At, Bt, on `st`
+hipError_t cost_reduce_problem(NdlqrHipCtx* c, const double* A, const double* B, const double* Q, const double* H,
+                               const double* R, double* rec, double* At, double* Bt, hipStream_t st) {
+  const ndlqr::Dims& u = c->du;
+  CostPhase phase(c, st, 0);
+  hipError_t e = launch_cost(ndlqr::cost_factor, ndlqr::cost_factor_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, u.batch, Q, H, R,
+                             rec, c->info.get());
+  if (e == hipSuccess)
+    e = launch_cost(ndlqr::cost_transform, ndlqr::cost_transform_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, A, B,
+                    (const double*)rec, At, Bt);
+  phase.stop();
+  return e;
+}
 int ndlqr_hip_init_dense(NdlqrHipCtx* c, const double* A, const double* B, const double* Q, const double* H, const double* R,
                          const double* q, const double* r, const double* d, const double* x0) {
   if (!c || !A || !B || !Q || !R || !q || !r || !d || !x0) return NDLQR_ERR_INVALID;
@@ -100,14 +118,7 @@ int ndlqr_hip_init_dense(NdlqrHipCtx* c, const double* A, const double* B, const
     hipLaunchKernelGGL(ndlqr::cost_fill, dim3(256), dim3(256), 0, st, k.ones.get(), kn * (n + m), 1.0);
     HIP_TRY(hipGetLastError());
   }
-  {
-    CostPhase phase(c, st, 0);
-    HIP_TRY(launch_cost(ndlqr::cost_factor, ndlqr::cost_factor_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, u.batch, ca.dev[2],
-                        ca.dev[3], ca.dev[4], k.rec.get(), c->info.get()));
-    HIP_TRY(launch_cost(ndlqr::cost_transform, ndlqr::cost_transform_lds(u.n, u.m), u, u.batch, st, u.n, u.m, u.N, ca.dev[0],
-                        ca.dev[1], k.rec.get(), k.At.get(), k.Bt.get()));
-    phase.stop();
-  }
+  HIP_TRY(cost_reduce_problem(c, ca.dev[0], ca.dev[1], ca.dev[2], ca.dev[3], ca.dev[4], k.rec, k.At, k.Bt, st));
   HIP_TRY(cost_reduce_rhs(c, ca.dev[5], ca.dev[6], ca.dev[7], ca.dev[8], st));
   // (waits for the stream first: the caller's arrays and the staging are free again when this returns)
   err = ndlqr_hip_pack_flat_device(c, k.At, k.Bt, k.ones, k.ones + kn * n, k.qt, k.rt, k.dt, k.x0t);
@@ -142,6 +153,12 @@ int ndlqr_hip_set_rhs_dense(NdlqrHipCtx* c, const double* q, const double* r, co
   err = ca.copy(s.stream, true);
   if (err) return err;
   HIP_TRY(cost_reduce_rhs(c, ca.dev[0], ca.dev[1], ca.dev[2], ca.dev[3], s.stream));
+  if (c->lin.active) {  // constrained mode retains the caller's right-hand side: the shifted S' of the next constrained solve reads it
+    double* const keep[4] = {c->lin.q, c->lin.r, c->lin.d, c->lin.x0};
+    for (int i = 0; i < 4; ++i)
+      HIP_TRY(hipMemcpyAsync(keep[i], ca.dev[i], sizeof(double) * ca.cnt[i], hipMemcpyDeviceToDevice, s.stream));
+    c->lin.rhs_new = true;
+  }
   const CostState& k = c->cost;
   HIP_TRY(launch_pack_rhs(c, k.qt, k.rt, k.dt, k.x0t));
   HIP_TRY(hipStreamSynchronize(s.stream));

@@ -11,6 +11,9 @@ hipError_t launch_adjoint_rhs(NdlqrHipCtx* c, const double* g, hipStream_t st) {
 
 int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   if (!c || !g) return NDLQR_ERR_INVALID;
+  if (c->lin.soln_gen != 0 && c->lin.soln_gen == c->soln_gen)
+    return refuse("ndlqr_hip_solve_adjoint: the resident solution is that of a solve with linear inequality constraints "
+                  "(ndlqr_hip_solve_constrained), which has no adjoint yet; a plain solve gives the unconstrained one");
   if (!c->kept.fact_valid && !c->kept.rec_complete)
     return refuse("adjoint solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
                   "factorisation) of the resident inputs");

@@ -123,6 +123,12 @@ int launch_residual_dd_on(NdlqrHipCtx* c, const double* QR, const double* rhs, c
 hipError_t cost_map_back(NdlqrHipCtx* c, double* vec, int p0, unsigned count, hipStream_t st);
 // ... and the packed [batch][nvars] vector `vec` in the caller's variables becomes S' vec (in place): the adjoint's g
 hipError_t cost_reduce_vector(NdlqrHipCtx* c, double* vec, hipStream_t st);
+// ... S' (records `rec`) of the flat right-hand side q, r, d, x0 (device) into the flat arrays qt, rt, dt, x0t
+hipError_t cost_reduce_rhs_to(NdlqrHipCtx* c, const double* rec, const double* q, const double* r, const double* d,
+                              const double* x0, double* qt, double* rt, double* dt, double* x0t, hipStream_t st);
+// ... the reduction of the dense costs Q, H (null: zero), R and of A, B (device, flat): records into rec, A~, B~ into At, Bt
+hipError_t cost_reduce_problem(NdlqrHipCtx* c, const double* A, const double* B, const double* Q, const double* H,
+                               const double* R, double* rec, double* At, double* Bt, hipStream_t st);
 // hip_grad.hip: the caller's packed g [batch][nvars] (this device's memory) into the adjoint's resident right-hand side
 hipError_t launch_adjoint_rhs(NdlqrHipCtx* c, const double* g, hipStream_t st);
 

@@ -1,0 +1,351 @@
+// hip_lin.hip -- general linear inequality constraints lo <= C x + D u <= hi (ndlqr_hip_init_constrained,
+// ndlqr_hip_set_constraint_bounds, ndlqr_hip_solve_constrained and their read-outs): the host
+// side, the kernels of kernels_lin.hpp. The reduction kernels it needs belong to hip_cost.hip (cost_reduce_problem,
+// cost_reduce_rhs_to).
+#include "hip_host.hpp"
+#include "kernels_lin.hpp"
+
+// ------------------------------------------------------------------------------ constrained mode
+// A dense-cost mode with constraints: ndlqr_hip_init_constrained retains the caller's A, B, Q, H, R, q, r, d, x0 and C, D
+// on the device and then runs ndlqr_hip_init_dense on the retained copies, so the plain API sees exactly what the dense
+// initialiser leaves. A constrained solve shifts the retained costs by rho C'MC, rho C'MD, rho D'MD, reduces the shifted
+// problem into buffers of its own (LinState: records, A~, B~, right-hand side), puts it in force (ShiftedReduction),
+// factors it once and iterates: one re-solve into lin.z plus one lin_update per iteration; the host reads the running
+// count every check_every iterations. On the way out the plain reduced problem of CostState is packed again.
+
+// (the kernels hold static LDS next to the dynamic: ask well below the default limit. `asked`: what this context has
+//  asked for this kernel already -- one of LinState::lds_asked --, so that a solve does not ask again)
+template <class Kernel>
+static hipError_t allow_lin_lds(Kernel* kernel, size_t lds, size_t& asked) {
+  if (lds <= 32 * 1024 || lds <= asked) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e == hipSuccess) asked = lds;
+  return e;
+}
+static size_t lin_update_lds_bytes(const ndlqr::Dims& u, int p) { return sizeof(double) * 4 * ndlqr::lin_wave_lds(u.n, u.m, p); }
+
+// Bounds lo, hi [P][N][p] of the caller (P = batch, or 1 when shared): checked (lo <= hi, no NaN) before anything is
+// replaced; with `commit` then copied to the device and their bounded pattern compared with the one in force.
+static int lin_take_bounds(NdlqrHipCtx* c, const char* who, const double* lo, const double* hi, int shared, bool commit) {
+  const ndlqr::Dims& u = c->du;
+  LinState& k = c->lin;
+  const int P = shared ? 1 : u.batch;
+  const size_t cnt = (size_t)P * u.N * k.p;
+  CallerArrays<2> in = {{const_cast<double*>(lo), const_cast<double*>(hi)}, {cnt, cnt}};
+  int err = in.classify(c, who, "bounds lie");
+  if (err) return err;
+  BufferSet& s = c->set[0];
+  HIP_TRY(c->grad_stage.grow(in.stage));
+  HIP_TRY(sync_all(c));
+  in.place(c);
+  err = in.copy(s.stream, true);
+  if (err) return err;
+  HIP_TRY(hipMemsetAsync(k.word, 0, 3 * sizeof(int), s.stream));
+  for (int pass = 0; pass < (commit ? 2 : 1); ++pass) {
+    hipLaunchKernelGGL(ndlqr::lin_bounds, dim3(u.N, P), dim3(64), 0, s.stream, u.N, k.p, (const double*)in.dev[0],
+                       (const double*)in.dev[1], pass, k.lo.get(), k.hi.get(), k.mask.get(), k.word + 1, k.word + 2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(k.h_word, k.word, 3 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    if (k.h_word[1]) return refuse(std::string(who) + ": a lower bound exceeds its upper bound (or is NaN)");
+  }
+  if (!commit) return NDLQR_OK;
+  // (the pattern lives in mask per problem: a change between shared and per-problem bounds always counts as a new one)
+  if (k.h_word[2] || (shared != 0) != k.shared) k.fact = false;
+  k.shared = shared != 0;
+  k.bstride = shared ? 0 : (size_t)u.N * k.p;
+  k.soln_gen = 0;
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_init_constrained(NdlqrHipCtx* c, const double* A, const double* B, const double* Q, const double* H,
+                               const double* R, const double* q, const double* r, const double* d, const double* x0, int p,
+                               const double* C, const double* D, const double* lo, const double* hi, int shared) {
+  if (!c) return NDLQR_ERR_INVALID;
+  if (p < 1) return refuse("ndlqr_hip_init_constrained: p = " + std::to_string(p) + " rows per knot (p >= 1)");
+  if (!A || !B || !Q || !R || !q || !r || !d || !x0 || !C || !D || !lo || !hi) return NDLQR_ERR_INVALID;
+  const ndlqr::Dims& u = c->du;
+  const size_t lds = lin_update_lds_bytes(u, p) + sizeof(double) * 5 * 256 + 16;
+  if (lds > kLdsMax)
+    return refuse("ndlqr_hip_init_constrained: lin_update stages " + std::to_string(lds) + " bytes per workgroup at (" +
+                  std::to_string(u.n) + "," + std::to_string(u.m) + ") with " + std::to_string(p) + " rows, beyond the " +
+                  std::to_string(kLdsMax) + " bytes of LDS of a workgroup");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t kn = (size_t)u.batch * u.N, n = (size_t)u.n, m = (size_t)u.m;
+  CallerArrays<11> ca = {{const_cast<double*>(A), const_cast<double*>(B), const_cast<double*>(Q), const_cast<double*>(H),
+                          const_cast<double*>(R), const_cast<double*>(q), const_cast<double*>(r), const_cast<double*>(d),
+                          const_cast<double*>(x0), const_cast<double*>(C), const_cast<double*>(D)},
+                         {kn * n * n, kn * n * m, kn * n * n, kn * n * m, kn * m * m, kn * n, kn * m, kn * n, (size_t)u.batch * n,
+                          kn * p * n, kn * p * m}};
+  int err = ca.classify(c, "ndlqr_hip_init_constrained", "an input lies");
+  if (err) return err;
+  HIP_TRY(sync_all(c));  // solves in flight still read what is replaced here
+  LinState& k = c->lin;
+  const hipStream_t st = c->set[0].stream;
+  // (from here on the retained state is being replaced: a refusal or failure below leaves constrained mode -- the plain
+  //  dense-cost mode, if the context was in one, stays valid)
+  k.active = false;
+  k.fact = false;
+  HIP_TRY(k.ensure(u, c->d, p, st));
+  err = lin_take_bounds(c, "ndlqr_hip_init_constrained", lo, hi, shared, false);
+  if (err) return err;
+  // the retained copies (host memory: straight into them; the caller's arrays are free again when this returns)
+  double* const keep[11] = {k.A, k.B, k.Q, k.H, k.R, k.q, k.r, k.d, k.x0, k.C, k.D};
+  for (int i = 0; i < 11; ++i)
+    if (ca.user[i]) HIP_TRY(hipMemcpyAsync(keep[i], ca.user[i], sizeof(double) * ca.cnt[i], hipMemcpyDefault, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  k.has_H = H != nullptr;
+  k.fact = false;
+  k.have_vy = false;
+  k.rhs_new = true;
+  k.soln_gen = 0;
+  // the context enters dense-cost mode exactly as the dense initialiser leaves it
+  err = ndlqr_hip_init_dense(c, k.A, k.B, k.Q, k.has_H ? k.H.get() : nullptr, k.R, k.q, k.r, k.d, k.x0);
+  if (err) return err;
+  HIP_TRY(hipMemsetAsync(k.mask, 0, kn * p, st));  // (no pattern in force: the first solve factors whatever the bounds are)
+  err = lin_take_bounds(c, "ndlqr_hip_init_constrained", lo, hi, shared, true);
+  if (err) return err;
+  k.fact = false;
+  k.active = true;
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_is_constrained(const NdlqrHipCtx* c) { return c && c->lin.active ? 1 : 0; }
+
+static int need_constrained(const NdlqrHipCtx* c, const char* who) {
+  if (c->lin.active && c->cost.dense) return NDLQR_OK;
+  return refuse(std::string(who) + ": the solver is not in constrained mode (ndlqr_InitializeBatchFlatConstrained first; "
+                "every other initialiser leaves it)");
+}
+
+int ndlqr_hip_set_constraint_bounds(NdlqrHipCtx* c, const double* lo, const double* hi, int shared) {
+  if (!c || !lo || !hi) return NDLQR_ERR_INVALID;
+  if (const int merr = need_constrained(c, "ndlqr_hip_set_constraint_bounds")) return merr;
+  HIP_TRY(hipSetDevice(c->device));
+  return lin_take_bounds(c, "ndlqr_hip_set_constraint_bounds", lo, hi, shared, true);
+}
+
+// The shifted reduced problem in force instead of the plain one, with the flags of the shifted factorisation instead of
+// the caller's: from open() to close(). A scope left without close() (an early return) restores the same: the plain
+// reduced problem of CostState packed again, the caller's flags, and the kept factorisation -- which belongs to the
+// shifted problem -- forgotten for the plain API.
+struct ShiftedReduction {
+  NdlqrHipCtx* c;
+  const unsigned user_flags;
+  bool open_ = false;
+  explicit ShiftedReduction(NdlqrHipCtx* ctx) : c(ctx), user_flags(ctx->flags) {}
+  ShiftedReduction(const ShiftedReduction&) = delete;
+  ~ShiftedReduction() { (void)close(); }
+  // (ndlqr_hip_pack_flat_device is an initialiser: it leaves both modes, which last through this scope)
+  int pack(const double* At, const double* Bt, const double* qt, const double* rt, const double* dt, const double* x0t) {
+    const size_t kn = (size_t)c->du.batch * c->du.N;
+    const int err = ndlqr_hip_pack_flat_device(c, At, Bt, c->cost.ones, c->cost.ones + kn * c->du.n, qt, rt, dt, x0t);
+    c->cost.dense = true;
+    c->lin.active = true;
+    return err;
+  }
+  int open(unsigned flags) {
+    open_ = true;
+    c->flags = flags;
+    const LinState& k = c->lin;
+    return pack(k.At, k.Bt, k.qt, k.rt, k.dt, k.x0t);
+  }
+  int close() {
+    if (!open_) return NDLQR_OK;
+    open_ = false;
+    const CostState& k = c->cost;
+    const int err = pack(k.At, k.Bt, k.qt, k.rt, k.dt, k.x0t);
+    c->flags = user_flags;
+    c->kept.forget_factorisation();
+    return err;
+  }
+};
+
+int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
+                                int check_every, int warm_start, int adapt_every, int* iters, int* status) {
+  if (!c || adapt_every < 0 || !(rho > 0.0 && rho < HUGE_VAL) || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) ||
+      max_iter < 1 || check_every < 1)
+    return NDLQR_ERR_INVALID;
+  if (adapt_every > 0)
+    return refuse("ndlqr_hip_solve_constrained: the adaptive penalty (adapt_every > 0) is not available for linear inequality "
+                  "constraints");
+  if (const int merr = need_constrained(c, "ndlqr_hip_solve_constrained")) return merr;
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  LinState& k = c->lin;
+  HIP_TRY(hipSetDevice(c->device));
+  int err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_constrained", iters, status);
+  if (err) return err;
+  // 1. everything idle, the primary set current
+  HIP_TRY(sync_all(c));
+  c->cur = 0;
+  BufferSet& s = c->set[0];
+  const hipStream_t st = s.stream;
+  const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
+  const unsigned lin_flags = c->flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
+  const bool reuse = k.fact && k.flags == lin_flags && k.rho_value == rho;
+  const int p = k.p;
+  const size_t lds = lin_update_lds_bytes(u, p);
+  HIP_TRY(hipEventRecord(s.ev_start, st));
+  bool factored = false;
+  int not_spd = NDLQR_OK;
+  ShiftedReduction shifted(c);
+  const double* Hk = k.has_H ? k.H.get() : nullptr;
+  // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
+  const auto iterate = [&]() -> int {
+    // 2. the shifted costs and their reduction, unless the remembered ones apply; S^' of the right-hand side when either is new
+    if (!reuse) {
+      const size_t slds = sizeof(double) * ndlqr::lin_shift_lds(u.n, u.m, p);
+      HIP_TRY(allow_lin_lds(ndlqr::lin_shift_cost, slds, k.lds_asked[0]));
+      hipLaunchKernelGGL(ndlqr::lin_shift_cost, dim3(u.N, u.batch), dim3(64), slds, st, u.n, u.m, u.N, p, rho,
+                         (const double*)k.Q, Hk, (const double*)k.R, (const double*)k.C, (const double*)k.D, (const double*)k.lo,
+                         (const double*)k.hi, k.bstride, k.Qs.get(), k.Hs.get(), k.Rs.get());
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(cost_reduce_problem(c, k.A, k.B, k.Qs, k.Hs, k.Rs, k.rec, k.At, k.Bt, st));
+    }
+    if (!reuse || k.rhs_new) HIP_TRY(cost_reduce_rhs_to(c, k.rec, k.q, k.r, k.d, k.x0, k.qt, k.rt, k.dt, k.x0t, st));
+    // 3. the shifted reduced problem in force; factored, unless the remembered factorisation applies
+    int e = shifted.open(lin_flags);
+    if (e) return e;
+    if (reuse) {
+      c->kept = k.kept;
+    } else {
+      factored = true;
+      e = factor_resident(c, st, &not_spd, "ndlqr_hip_solve_constrained", "the reduction of Q + rho C'MC, H + rho C'MD, R + rho D'MD");
+      if (e) return e;
+    }
+    // 4. the iterations
+    const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
+    const int cold = warm_start && k.have_vy ? 0 : 1;
+    HIP_TRY(allow_lin_lds(ndlqr::lin_start, lds, k.lds_asked[1]));
+    if (strict) HIP_TRY(allow_lin_lds(ndlqr::lin_update<true>, lds, k.lds_asked[2]));
+    else HIP_TRY(allow_lin_lds(ndlqr::lin_update<false>, lds, k.lds_asked[3]));
+    hipLaunchKernelGGL(ndlqr::lin_start, dim3(u.batch), dim3(256), lds, st, u, d, p, cold, rho,
+                  (const double*)k.rec, (const double*)k.C, (const double*)k.D, (const double*)k.lo, (const double*)k.hi,
+                  k.bstride, (const double*)s.rhs, k.v.get(), k.y.get(), k.rhs[0].get(), k.rhs[1].get());
+    HIP_TRY(hipGetLastError());
+    k.have_vy = true;
+    k.h_word[0] = u.batch;
+    HIP_TRY(hipMemcpyAsync(k.word, k.h_word, sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(k.status, 0, sizeof(int) * (size_t)u.batch, st));
+    for (int it = 1; it <= max_iter; ++it) {
+      const double* rc = k.rhs[(it - 1) & 1];
+      double* rn = k.rhs[it & 1];
+      e = launch_resolve(c, rc, k.z, "constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      if (e) return e;
+      launch_strict(strict, ndlqr::lin_update, dim3(u.batch), dim3(256), lds, st, u, d, p, it, P, (const double*)k.z,
+                    (const double*)k.rec, (const double*)k.C, (const double*)k.D, (const double*)k.lo, (const double*)k.hi,
+                    k.bstride, k.v.get(), k.y.get(), (const double*)s.rhs, rc, rn, rho, k.status.get(),
+                    k.iters.get(), k.resid.get(), k.word.get());
+      HIP_TRY(hipGetLastError());
+      if (it % check_every == 0 || it == max_iter) {
+        // 5. one word: how many problems still run
+        HIP_TRY(hipMemcpyAsync(k.h_word, k.word, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (k.h_word[0] == 0) break;
+      }
+    }
+    // 6. deliver: S^ z~ of the last re-solve, in the caller's variables
+    const size_t flds = sizeof(double) * ndlqr::lin_wave_lds(u.n, u.m, p);
+    HIP_TRY(allow_lin_lds(ndlqr::lin_finish, flds, k.lds_asked[4]));
+    hipLaunchKernelGGL(ndlqr::lin_finish, dim3(d.N, d.batch), dim3(64), flds, st, u, d, p, (const double*)k.rec,
+                       (const double*)k.z, s.z.get());
+    HIP_TRY(hipGetLastError());
+    return NDLQR_OK;
+  };
+  err = iterate();
+  // 7. the plain reduced problem again, bookkeeping
+  const KeptState shifted_kept = c->kept;  // (close() forgets it for the plain API)
+  const int cerr = shifted.close();
+  if (!err) err = cerr;
+  if (err) {
+    k.fact = false;
+    k.have_vy = false;
+    if (!not_spd) c->state_dirty = true;  // (a failed launch; a non-positive pivot leaves the device state clean)
+    if (factored) c->z_invalid = true;    // (the factorisation overwrote the resident solution)
+    (void)hipStreamSynchronize(st);
+    return err;
+  }
+  k.fact = true;  // (the initialiser inside the scope dropped it)
+  k.rho_value = rho;
+  k.flags = lin_flags;
+  k.kept = shifted_kept;
+  k.rhs_new = false;
+  note_solution(c);
+  k.soln_gen = c->soln_gen;
+  c->cost.mapped_gen = c->soln_gen;  // (the delivery must not apply the plain records to it)
+  HIP_TRY(hipEventRecord(s.ev_stop, st));
+  c->timing_pending = true;
+  err = deliver_iters_status(c, st, k.iters, k.status, iters, status);
+  if (err) return err;
+  return ndlqr_hip_synchronize(c);
+}
+
+// mu = rho y [batch][N][p], into host memory or this device's
+int ndlqr_hip_download_constraint_multipliers(NdlqrHipCtx* c, double* mu) {
+  if (!c || !mu) return NDLQR_ERR_INVALID;
+  if (const int merr = need_constrained(c, "ndlqr_hip_download_constraint_multipliers")) return merr;
+  if (!c->lin.have_vy) return refuse("ndlqr_hip_download_constraint_multipliers: no constrained solve yet");
+  const ndlqr::Dims& u = c->du;
+  LinState& k = c->lin;
+  HIP_TRY(hipSetDevice(c->device));
+  const int per = u.N * k.p;
+  CallerArrays<1> out = {{mu}, {(size_t)u.batch * per}};
+  int err = out.classify(c, "ndlqr_hip_download_constraint_multipliers", "the output lies");
+  if (err) return err;
+  HIP_TRY(c->grad_stage.grow(out.stage));
+  HIP_TRY(sync_all(c));
+  const BufferSet& s = c->set[0];
+  out.place(c);
+  hipLaunchKernelGGL(ndlqr::lin_multipliers, dim3((per + 255) / 256, u.batch), dim3(256), 0, s.stream, per, k.rho_value,
+                     (const double*)k.y, out.dev[0]);
+  HIP_TRY(hipGetLastError());
+  err = out.copy(s.stream, false);
+  if (err) return err;
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
+}
+
+// resid [batch][4] = r_prim | r_dual | sp | sd of every problem's last update, as ndlqr_hip_download_box_residuals
+int ndlqr_hip_download_constraint_residuals(NdlqrHipCtx* c, double* resid) {
+  if (!c || !resid) return NDLQR_ERR_INVALID;
+  if (const int merr = need_constrained(c, "ndlqr_hip_download_constraint_residuals")) return merr;
+  if (c->lin.soln_gen == 0 || c->lin.soln_gen != c->soln_gen)
+    return refuse("ndlqr_hip_download_constraint_residuals: the resident solution is not that of a constrained solve");
+  HIP_TRY(hipSetDevice(c->device));
+  if (where(resid, c->device) == Where::OtherDevice)
+    return refuse("ndlqr_hip_download_constraint_residuals: the output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  HIP_TRY(hipMemcpy(resid, c->lin.resid, sizeof(double) * 4 * (size_t)c->du.batch, hipMemcpyDefault));
+  return NDLQR_OK;
+}
+
+// Read-out for the tests, the counterpart of ndlqr_hip_download_cost_reduction: the shifted costs, the shifted records and
+// the shifted reduced problem of the latest constrained solve in the caller's flat layout, and its iterates v, y
+// [batch][N][p], into HOST memory; any pointer may be null.
+int ndlqr_hip_download_constraint_reduction(NdlqrHipCtx* c, double* Qs, double* Hs, double* Rs, double* L, double* LR, double* G,
+                                            double* At, double* Bt, double* qt, double* rt, double* dt, double* x0t, double* v,
+                                            double* y) {
+  if (!c) return NDLQR_ERR_INVALID;
+  if (const int merr = need_constrained(c, "ndlqr_hip_download_constraint_reduction")) return merr;
+  if (!c->lin.have_vy) return refuse("ndlqr_hip_download_constraint_reduction: no constrained solve yet");
+  const ndlqr::Dims& u = c->du;
+  const LinState& k = c->lin;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(sync_all(c));
+  const size_t kn = (size_t)u.batch * u.N, n = (size_t)u.n, m = (size_t)u.m, recd = n * n + m * m + m * n;
+  double* const part[3] = {L, LR, G};
+  const size_t width[3] = {n * n, m * m, m * n};
+  size_t off = 0;
+  for (int i = 0; i < 3; off += width[i], ++i)
+    if (part[i])
+      HIP_TRY(hipMemcpy2D(part[i], sizeof(double) * width[i], k.rec + off, sizeof(double) * recd, sizeof(double) * width[i], kn,
+                          hipMemcpyDeviceToHost));
+  double* const dst[11] = {Qs, Hs, Rs, At, Bt, qt, rt, dt, x0t, v, y};
+  const double* const src[11] = {k.Qs, k.Hs, k.Rs, k.At, k.Bt, k.qt, k.rt, k.dt, k.x0t, k.v, k.y};
+  const size_t cnt[11] = {kn * n * n, kn * n * m, kn * m * m, kn * n * n, kn * n * m, kn * n, kn * m, kn * n, (size_t)u.batch * n,
+                          kn * k.p, kn * k.p};
+  for (int i = 0; i < 11; ++i)
+    if (dst[i]) HIP_TRY(hipMemcpy(dst[i], src[i], sizeof(double) * cnt[i], hipMemcpyDeviceToHost));
+  return NDLQR_OK;
+}

@@ -14,19 +14,18 @@
 //     cost_apply_t     S' on a right-hand side: flat (q, r, d, x0) -> flat (q~, r~, d~, x0~), or a packed [count][nvars]
 //                      vector in [lambda x u] order in place (the adjoint's g)
 //     cost_apply       S on a packed [count][nvars] solution, in place
+// The per-knot pieces -- record layout, triangular solves, the bodies of S and S' -- live in kernels_cost_knot.hpp, which
+// kernels_lin.hpp shares.
 // A, B, H, R, r, d of the caller's last knot are never loaded (every such load sits behind the wave-uniform test of the
 // knot): whatever they hold, a NaN included, reaches no output. The last knot's record is L | 1 | 0.
 // A Cholesky pivot that is not positive counts in the problem's info word like the solver's own (flag_failure) and is
 // taken as 1: finite input gives finite output, nothing is written out of range.
 #pragma once
 #include "kernels_common.hpp"
+#include "kernels_cost_knot.hpp"
 
 namespace ndlqr {
 
-// doubles of one knot's record: L [n][n] | L_R [m][m] | G [m][n], each column-major, the triangles with zeros above
-__host__ __device__ inline size_t cost_record_doubles(int n, int m) { return (size_t)n * n + (size_t)m * m + (size_t)m * n; }
-// leading dimension of a triangular factor staged in LDS: odd, so that walking a row is as conflict-free as walking a column
-__host__ __device__ inline int cost_ld(int k) { return k | 1; }
 // dynamic LDS (doubles) of the four kernels
 __host__ __device__ inline size_t cost_factor_lds(int n, int m) { return (size_t)n * n + (size_t)m * m + (size_t)n * m; }
 __host__ __device__ inline size_t cost_transform_lds(int n, int m) {
@@ -60,43 +59,6 @@ __device__ inline int cost_chol_lds(double* a, const int ld, const int k, const 
     wave_lds_sync();
   }
   return bad;
-}
-
-// v <- L^-1 v (k entries in LDS, L lower with leading dimension ld) by one wavefront: the dependent chain, a column per step
-__device__ inline void cost_trsv_lower(const double* L, const int ld, const int k, double* v, const int lane) {
-  for (int j = 0; j < k; ++j) {
-    const double xj = v[j] / L[j + ld * j];
-    if (lane == 0) v[j] = xj;
-    for (int i = j + 1 + lane; i < k; i += 64) v[i] = fma(-L[i + ld * j], xj, v[i]);
-    wave_lds_sync();
-  }
-}
-// v <- L^-T v
-__device__ inline void cost_trsv_lower_t(const double* L, const int ld, const int k, double* v, const int lane) {
-  for (int j = k - 1; j >= 0; --j) {
-    const double xj = v[j] / L[j + ld * j];
-    if (lane == 0) v[j] = xj;
-    for (int i = lane; i < j; i += 64) v[i] = fma(-L[j + ld * i], xj, v[i]);
-    wave_lds_sync();
-  }
-}
-
-// a knot's record into LDS: L (leading dimension cost_ld(n)), and with `rest` L_R (cost_ld(m)) and G [m][n]
-__device__ inline void cost_stage_record(const double* __restrict__ rk, const int n, const int m, const bool rest, double* sL,
-                                         double* sLR, double* sG, const int lane) {
-  const int ldn = cost_ld(n), ldm = cost_ld(m);
-  for (int idx = lane; idx < n * n; idx += 64) {
-    const int j = idx / n;
-    sL[idx - j * n + ldn * j] = rk[idx];
-  }
-  if (!rest) return;
-  rk += (size_t)n * n;
-  for (int idx = lane; idx < m * m; idx += 64) {
-    const int j = idx / m;
-    sLR[idx - j * m + ldm * j] = rk[idx];
-  }
-  rk += (size_t)m * m;
-  for (int idx = lane; idx < m * n; idx += 64) sG[idx] = rk[idx];
 }
 
 // grid (N, batch), block 64, dynamic LDS cost_factor_lds(n, m) doubles. Q [batch][N][n*n], R [batch][N][m*m], H
@@ -281,23 +243,8 @@ static __global__ __launch_bounds__(64) void cost_apply_t(const int n, const int
   if (!last)
     for (int i = lane; i < m; i += 64) su[i] = iu[i];
   wave_lds_sync();
-  for (int i = lane; i < n; i += 64) {
-    double s = 0.0;
-    for (int c = i; c < n; ++c) s = fma(sL[c + ldn * i], sl[c], s);
-    ol[i] = s;
-    if (!last) {
-      double t = sx[i];
-      for (int c = 0; c < m; ++c) t = fma(-sG[c + m * i], su[c], t);
-      sx[i] = t;
-    }
-  }
-  wave_lds_sync();
-  cost_trsv_lower(sL, ldn, n, sx, lane);
-  for (int i = lane; i < n; i += 64) ox[i] = sx[i];
-  if (!last) {
-    cost_trsv_lower(sLR, ldm, m, su, lane);
-    for (int i = lane; i < m; i += 64) ou[i] = su[i];
-  } else if (!g) {
+  cost_knot_St<true, true>(n, m, last, sL, sLR, sG, sl, sx, su, ol, ox, ou, lane);
+  if (last && !g) {
     for (int i = lane; i < m; i += 64) ou[i] = 0.0;
     for (int i = lane; i < n; i += 64) dt[kb * n + i] = 0.0;
   }
@@ -327,20 +274,7 @@ static __global__ __launch_bounds__(64) void cost_apply(const int n, const int m
   if (!last)
     for (int i = lane; i < m; i += 64) su[i] = zu[i];
   wave_lds_sync();
-  for (int i = lane; i < n; i += 64) {
-    double s = 0.0;
-    for (int c = 0; c <= i; ++c) s = fma(sL[i + ldn * c], sl[c], s);
-    zl[i] = s;
-  }
-  cost_trsv_lower_t(sL, ldn, n, sx, lane);
-  for (int i = lane; i < n; i += 64) zx[i] = sx[i];
-  if (last) return;
-  cost_trsv_lower_t(sLR, ldm, m, su, lane);
-  for (int j = lane; j < m; j += 64) {
-    double s = su[j];
-    for (int i = 0; i < n; ++i) s = fma(-sG[j + m * i], sx[i], s);
-    zu[j] = s;
-  }
+  cost_knot_S<true>(n, m, last, sL, sLR, sG, sl, sx, su, zl, zx, zu, lane);
 }
 
 }  // namespace ndlqr

@@ -1,0 +1,353 @@
+// kernels_lin.hpp -- internal: general linear inequality constraints lo_k <= C_k x_k + D_k u_k <= hi_k by scaled ADMM on
+// the dense-cost reduction (ndlqr_hip_init_constrained, ndlqr_hip_solve_constrained).
+//
+// Section 3.9 carried to the rows w = C x + D u: v (projected copy of w) and y (scaled dual) are [batch][N][p] in the
+// CALLER's horizon, like the bounds lo, hi ([N][p] once when shared). A row is bounded (M = 1) when one of its bounds is
+// finite. ADMM on such rows shifts the cost by rho C'MC, rho C'MD, rho D'MD -- dense: lin_shift_cost forms the shifted
+// costs, the kernels of kernels_cost.hpp reduce them to a unit-cost problem (the SHIFTED records L | L_R | G and A~, B~),
+// which is factored once. One iteration is a re-solve in the reduced variables followed by lin_update, which per knot
+//     applies S^ to the knot's z~ (x, u in the caller's variables),      forms w = C x + D u,
+//     steps the bounded rows (box_step of the shared update core),        stores v+, y+,
+//     forms rho [C'; D'] M (y+ - v+),   applies S^',   writes the next reduced right-hand side res~ - S^'[...],
+// and then judges the problem (box_judge) from
+//     r_prim = max |w - v+|,  r_dual = rho max |G'(v+ - v)|,  sp = max(max |w|, max |v+|),  sd = rho max |G' y+|   (G = [C D]).
+// The caller's block sizes are `u` (n, m, N of the flat arrays, the records and C, D), the device layout of z~ and of the
+// right-hand sides is `d` (a zero-padded block size and / or a padded horizon): row i of lambda | x | u of knot k sits at
+// k d.rows + (i | d.n + i | 2 d.n + i). Pad entries and the knots k >= u.N are never written: they keep the resident
+// right-hand side lin_start copied. D of the caller's last knot is never loaded (its rows are w = C x).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kernels_box_core.hpp"
+#include "kernels_cost_knot.hpp"
+
+namespace ndlqr {
+
+// doubles of LDS one wavefront of lin_update / lin_start / lin_finish stages for its knot: the record, C [p][n], D [p][m]
+// (column-major, as the caller gives them) and the vectors lambda | x | u~ | u | three row vectors
+__host__ __device__ inline size_t lin_wave_lds(int n, int m, int p) {
+  return (size_t)n * cost_ld(n) + (size_t)m * cost_ld(m) + (size_t)m * n + (size_t)p * n + (size_t)p * m + 2 * (size_t)n +
+         2 * (size_t)m + 3 * (size_t)p;
+}
+__host__ __device__ inline size_t lin_shift_lds(int n, int m, int p) { return (size_t)p * n + (size_t)p * m + p; }
+
+// Bounds in the caller's layout lo, hi [P][N][p] (P = batch or 1). commit == 0: only check, *bad = 1 when lo > hi (or
+// NaN). commit == 1: copy them to dlo, dhi and the bounded pattern into mask, *changed = 1 where it differs.
+//   grid (N, P), block 64.
+static __global__ void lin_bounds(int N, int p, const double* __restrict__ lo, const double* __restrict__ hi, int commit,
+                                  double* __restrict__ dlo, double* __restrict__ dhi, unsigned char* __restrict__ mask,
+                                  int* __restrict__ bad, int* __restrict__ changed) {
+  const size_t o = ((size_t)blockIdx.y * N + blockIdx.x) * p;
+  for (int r = threadIdx.x; r < p; r += blockDim.x) {
+    const double l = lo[o + r], h = hi[o + r];
+    if (!commit) {
+      if (!(l <= h)) *bad = 1;
+      continue;
+    }
+    dlo[o + r] = l;
+    dhi[o + r] = h;
+    const unsigned char b = box_bounded(l, h) ? 1 : 0;
+    if (mask[o + r] != b) {
+      mask[o + r] = b;
+      *changed = 1;
+    }
+  }
+}
+
+// Q^ = Q + rho C'MC, H^ = H + rho C'MD, R^ = R + rho D'MD of every knot (the last: Q^ alone; H^ = 0, R^ = 1 are written
+// and nothing of the caller's H, R, D is loaded there). One wavefront per (knot, problem); C, D and the row weights
+// rho M go through LDS, the costs come in and leave as they lie. Q, R are read in their lower triangles (as cost_factor
+// does) and leave symmetric. H may be null (zero).
+//   grid (N, batch), block 64, dynamic LDS lin_shift_lds(n, m, p) doubles.
+static __global__ __launch_bounds__(64) void lin_shift_cost(const int n, const int m, const int N, const int p,
+                                                            const double rho, const double* __restrict__ Q,
+                                                            const double* __restrict__ H, const double* __restrict__ R,
+                                                            const double* __restrict__ C, const double* __restrict__ D,
+                                                            const double* __restrict__ lo, const double* __restrict__ hi,
+                                                            const size_t bstride, double* __restrict__ Qs,
+                                                            double* __restrict__ Hs, double* __restrict__ Rs) {
+  extern __shared__ __attribute__((aligned(16))) double lin_lds[];
+  const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const bool last = k == N - 1;
+  const size_t kb = (size_t)b * N + k;
+  double* sC = lin_lds;
+  double* sD = sC + (size_t)p * n;
+  double* sw = sD + (size_t)p * m;
+  {
+    const double* Ck = C + kb * p * n;
+    for (int idx = lane; idx < p * n; idx += 64) sC[idx] = Ck[idx];
+    if (!last) {
+      const double* Dk = D + kb * p * m;
+      for (int idx = lane; idx < p * m; idx += 64) sD[idx] = Dk[idx];
+    }
+    const size_t ob = (size_t)b * bstride + (size_t)k * p;
+    for (int r = lane; r < p; r += 64) sw[r] = box_bounded(lo[ob + r], hi[ob + r]) ? rho : 0.0;
+  }
+  wave_lds_sync();
+  {
+    const double* Qk = Q + kb * n * n;
+    double* Qo = Qs + kb * n * n;
+    for (int idx = lane; idx < n * n; idx += 64) {
+      const int j = idx / n, i = idx - j * n;
+      double s = 0.0;
+      for (int r = 0; r < p; ++r) s = fma(sC[r + p * i] * sw[r], sC[r + p * j], s);
+      Qo[idx] = (i >= j ? Qk[idx] : Qk[j + n * i]) + s;
+    }
+  }
+  double* Ho = Hs + kb * n * m;
+  double* Ro = Rs + kb * m * m;
+  if (last) {
+    for (int idx = lane; idx < n * m; idx += 64) Ho[idx] = 0.0;
+    for (int idx = lane; idx < m * m; idx += 64) Ro[idx] = (idx / m == idx % m) ? 1.0 : 0.0;
+    return;
+  }
+  const double* Hk = H ? H + kb * n * m : nullptr;
+  for (int idx = lane; idx < n * m; idx += 64) {
+    const int j = idx / n, i = idx - j * n;
+    double s = 0.0;
+    for (int r = 0; r < p; ++r) s = fma(sC[r + p * i] * sw[r], sD[r + p * j], s);
+    Ho[idx] = (Hk ? Hk[idx] : 0.0) + s;
+  }
+  const double* Rk = R + kb * m * m;
+  for (int idx = lane; idx < m * m; idx += 64) {
+    const int j = idx / m, i = idx - j * m;
+    double s = 0.0;
+    for (int r = 0; r < p; ++r) s = fma(sD[r + p * i] * sw[r], sD[r + p * j], s);
+    Ro[idx] = (i >= j ? Rk[idx] : Rk[j + m * i]) + s;
+  }
+}
+
+// One wavefront's LDS for its knot (lin_wave_lds doubles at `base`).
+struct LinKnotLds {
+  double *sL, *sLR, *sG, *sC, *sD, *sl, *sx, *su, *ux, *t0, *t1, *t2;
+  __device__ __forceinline__ LinKnotLds(double* base, int n, int m, int p) {
+    sL = base;
+    sLR = sL + (size_t)n * cost_ld(n);
+    sG = sLR + (size_t)m * cost_ld(m);
+    sC = sG + (size_t)m * n;
+    sD = sC + (size_t)p * n;
+    sl = sD + (size_t)p * m;  // lambda~ (lin_finish) | the x rows of the perturbation (n entries, as sx)
+    sx = sl + n;
+    su = sx + n;
+    ux = su + m;  // u in the caller's variables
+    t0 = ux + m;  // rho M (y - v) | M (v+ - v) | M y+ of the knot's rows
+    t1 = t0 + p;
+    t2 = t1 + p;
+  }
+};
+
+// the knot's shifted record and C, D into LDS (D and the rest of the record: !last)
+__device__ __forceinline__ void lin_stage_knot(const LinKnotLds& S, const Dims& u, const int p, const bool last,
+                                               const double* __restrict__ rk, const double* __restrict__ Ck,
+                                               const double* __restrict__ Dk, const int lane) {
+  cost_stage_record(rk, u.n, u.m, !last, S.sL, S.sLR, S.sG, lane);
+  for (int idx = lane; idx < p * u.n; idx += 64) S.sC[idx] = Ck[idx];
+  if (!last)
+    for (int idx = lane; idx < p * u.m; idx += 64) S.sD[idx] = Dk[idx];
+}
+
+// With rho M (y - v) of the knot's rows in S.t0 (and the record, C, D staged): the x and u rows of the next reduced
+// right-hand side, rn = rs - S^'[C' t0; D' t0]. E != nullptr (lin_update): S.t1, S.t2 hold M (v+ - v) and M y+, and the
+// maxima of |G' t1|, |G' t2| over the knot's entries are taken into E->rd, E->ym on the way. rn2: a second destination
+// (lin_start writes both ping-pong buffers) or null. Begins and ends with the wavefront's LDS in order.
+__device__ __forceinline__ void lin_next_rhs(const LinKnotLds& S, const Dims& u, const Dims& d, const int p, const bool last,
+                                             const double* __restrict__ rs, double* __restrict__ rn, double* __restrict__ rn2,
+                                             BoxMaxima* E, const int lane) {
+  const int n = u.n, m = u.m;
+  wave_lds_sync();
+  for (int j = lane; j < n + (last ? 0 : m); j += 64) {
+    const double* col = j < n ? S.sC + (size_t)p * j : S.sD + (size_t)p * (j - n);
+    double a = 0.0, bb = 0.0, cc = 0.0;
+    for (int r = 0; r < p; ++r) {
+      a = fma(col[r], S.t0[r], a);
+      if (E) {
+        bb = fma(col[r], S.t1[r], bb);
+        cc = fma(col[r], S.t2[r], cc);
+      }
+    }
+    if (E) {
+      E->rd = max_nan(E->rd, fabs(bb));
+      E->ym = max_nan(E->ym, fabs(cc));
+    }
+    if (j < n) S.sx[j] = a;
+    else S.su[j - n] = a;
+  }
+  wave_lds_sync();
+  cost_knot_St<false, false>(n, m, last, S.sL, S.sLR, S.sG, nullptr, S.sx, S.su, nullptr, nullptr, nullptr, lane);
+  wave_lds_sync();
+  for (int i = lane; i < n; i += 64) {
+    const double val = rs[d.n + i] - S.sx[i];
+    rn[d.n + i] = val;
+    if (rn2) rn2[d.n + i] = val;
+  }
+  if (!last)
+    for (int j = lane; j < m; j += 64) {
+      const double val = rs[2 * d.n + j] - S.su[j];
+      rn[2 * d.n + j] = val;
+      if (rn2) rn2[2 * d.n + j] = val;
+    }
+  wave_lds_sync();
+}
+
+// rho (y - v) of one bounded row (a rounded difference, then a rounded product: the same in both modes)
+__device__ __forceinline__ double lin_row_weight(double rho, double v, double y) {
+  const double t = y - v;
+  return rho * t;
+}
+
+// Start of a solve: both ADMM right-hand sides from the resident (shifted, reduced) one `res`. cold: v = y = 0 and the
+// right-hand sides are copies of res. Otherwise (warm start) y of the rows the current bounds leave unbounded is zeroed
+// and the right-hand sides are res~ - S^'[rho G'M(y - v)]. v and the SCALED dual y are taken as the previous solve left
+// them whatever its penalty was -- as box_start does: a warm start with another rho starts from mu = rho y, not from the
+// previous mu; the iteration converges from any start.
+//   grid (batch), block 256, dynamic LDS 4 lin_wave_lds(n, m, p) doubles.
+static __global__ __launch_bounds__(256) void lin_start(Dims u, Dims d, int p, int cold, const double rho,
+                                                 const double* __restrict__ rec, const double* __restrict__ C,
+                                                 const double* __restrict__ D, const double* __restrict__ lo,
+                                                 const double* __restrict__ hi, size_t bstride, const double* __restrict__ res,
+                                                 double* __restrict__ v, double* __restrict__ y, double* __restrict__ rhs0,
+                                                 double* __restrict__ rhs1) {
+  extern __shared__ __attribute__((aligned(16))) double lin_lds[];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const size_t oz = (size_t)b * d.N * d.rows;
+  for (unsigned e = tid; e < (unsigned)(d.N * d.rows); e += blockDim.x) {
+    const double val = res[oz + e];
+    rhs0[oz + e] = val;
+    rhs1[oz + e] = val;
+  }
+  double* vb = v + (size_t)b * u.N * p;
+  double* yb = y + (size_t)b * u.N * p;
+  if (cold) {
+    for (unsigned e = tid; e < (unsigned)(u.N * p); e += blockDim.x) { vb[e] = 0.0; yb[e] = 0.0; }
+    return;
+  }
+  __syncthreads();  // (the copies above precede this workgroup's overwrites of the x and u rows)
+  const LinKnotLds S(lin_lds + (size_t)wave * lin_wave_lds(u.n, u.m, p), u.n, u.m, p);
+  const size_t recd = cost_record_doubles(u.n, u.m);
+  for (int k = wave; k < u.N; k += 4) {
+    const bool last = k == u.N - 1;
+    const size_t kb = (size_t)b * u.N + k;
+    lin_stage_knot(S, u, p, last, rec + kb * recd, C + kb * p * u.n, D + kb * p * u.m, lane);
+    const size_t ob = (size_t)b * bstride + (size_t)k * p;
+    for (int r = lane; r < p; r += 64) {
+      const bool bounded = box_bounded(lo[ob + r], hi[ob + r]);
+      if (!bounded) yb[(size_t)k * p + r] = 0.0;
+      S.t0[r] = bounded ? lin_row_weight(rho, vb[(size_t)k * p + r], yb[(size_t)k * p + r]) : 0.0;
+    }
+    const size_t ok = oz + (size_t)k * d.rows;
+    lin_next_rhs(S, u, d, p, last, res + ok, rhs0 + ok, rhs1 + ok, nullptr, lane);
+  }
+}
+
+// One ADMM update of every running problem (status[b] == 0) after re-solve `it`; see the head of this file. z: the
+// re-solve's solution z~ [batch][N][2n+m] (device layout) with the right-hand side rhs_cur; rec, C, D, v, y in the
+// caller's block sizes. The four wavefronts take the knots k < u.N round-robin; then the maxima are reduced and thread 0
+// judges (box_judge). A frozen problem's next right-hand side is its current one.
+//   grid (batch), block 256, dynamic LDS 4 lin_wave_lds(n, m, p) doubles.
+template <bool STRICT>
+__global__ __launch_bounds__(256) void lin_update(Dims u, Dims d, int p, int it, BoxParams P, const double* __restrict__ z,
+                                                  const double* __restrict__ rec, const double* __restrict__ C,
+                                                  const double* __restrict__ D, const double* __restrict__ lo,
+                                                  const double* __restrict__ hi, size_t bstride, double* __restrict__ v,
+                                                  double* __restrict__ y, const double* __restrict__ res,
+                                                  const double* __restrict__ rhs_cur, double* __restrict__ rhs_next,
+                                                  const double rho, int* __restrict__ status,
+                                                  int* __restrict__ iters, double* __restrict__ resid,
+                                                  int* __restrict__ running) {
+  extern __shared__ __attribute__((aligned(16))) double lin_lds[];
+  __shared__ double red[5][256];
+  __shared__ int conv_s;
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (status[b] != 0) return;  // frozen (uniform over the workgroup)
+  const int n = u.n, m = u.m;
+  const size_t oz = (size_t)b * d.N * d.rows;
+  double* vb = v + (size_t)b * u.N * p;
+  double* yb = y + (size_t)b * u.N * p;
+  const LinKnotLds S(lin_lds + (size_t)wave * lin_wave_lds(n, m, p), n, m, p);
+  const size_t recd = cost_record_doubles(n, m);
+  BoxMaxima M;
+  for (int k = wave; k < u.N; k += 4) {
+    const bool last = k == u.N - 1;
+    const size_t kb = (size_t)b * u.N + k, ok = oz + (size_t)k * d.rows;
+    lin_stage_knot(S, u, p, last, rec + kb * recd, C + kb * p * n, D + kb * p * m, lane);
+    for (int i = lane; i < n; i += 64) S.sx[i] = z[ok + d.n + i];
+    if (!last)
+      for (int j = lane; j < m; j += 64) S.su[j] = z[ok + 2 * d.n + j];
+    wave_lds_sync();
+    // x -> S.sx, u -> S.ux
+    cost_knot_S<false>(n, m, last, S.sL, S.sLR, S.sG, nullptr, S.sx, S.su, nullptr, S.sx, S.ux, lane);
+    wave_lds_sync();
+    const size_t ob = (size_t)b * bstride + (size_t)k * p;
+    for (int r = lane; r < p; r += 64) {
+      double w = 0.0;
+      for (int j = 0; j < n; ++j) w = fma(S.sC[r + p * j], S.sx[j], w);
+      if (!last)
+        for (int j = 0; j < m; ++j) w = fma(S.sD[r + p * j], S.ux[j], w);
+      const double l = lo[ob + r], h = hi[ob + r];
+      double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+      if (box_bounded(l, h)) {
+        const size_t e = (size_t)k * p + r;
+        const double v0 = vb[e], y0 = yb[e];
+        const BoxStep s = box_step<STRICT>(P, w, v0, y0, true, l, h);
+        vb[e] = s.vn;
+        yb[e] = s.yn;
+        M.rp = max_nan(M.rp, fabs(w - s.vn));
+        M.zm = max_nan(M.zm, fabs(w));
+        M.vm = max_nan(M.vm, fabs(s.vn));
+        t0 = lin_row_weight(rho, s.vn, s.yn);
+        t1 = s.vn - v0;
+        t2 = s.yn;
+      }
+      S.t0[r] = t0;
+      S.t1[r] = t1;
+      S.t2[r] = t2;
+    }
+    lin_next_rhs(S, u, d, p, last, res + ok, rhs_next + ok, nullptr, &M, lane);
+  }
+  M.reduce(red, tid);
+  if (tid == 0) conv_s = box_judge(P, rho, red, b, it, status, iters, resid, running).frozen ? 1 : 0;
+  __syncthreads();
+  if (conv_s == 1)
+    for (unsigned e = tid; e < (unsigned)(u.N * (n + m)); e += blockDim.x) {
+      const unsigned k = e / (unsigned)(n + m), j = e - k * (unsigned)(n + m);
+      if ((int)k == u.N - 1 && (int)j >= n) continue;
+      const size_t o = oz + (size_t)k * d.rows + ((int)j < n ? d.n + j : 2 * d.n + (j - n));
+      rhs_next[o] = rhs_cur[o];
+    }
+}
+
+// End of a solve: the resident solution blocks zs get S^ z~ of the last re-solve -- lambda, x, u in the caller's variables
+// under the shifted records -- and the pad entries and the knots k >= u.N as the re-solve left them.
+//   grid (d.N, batch), block 64, dynamic LDS lin_wave_lds(n, m, p) doubles.
+static __global__ __launch_bounds__(64) void lin_finish(Dims u, Dims d, int p, const double* __restrict__ rec,
+                                                        const double* __restrict__ z, double* __restrict__ zs) {
+  extern __shared__ __attribute__((aligned(16))) double lin_lds[];
+  const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const int n = u.n, m = u.m;
+  const size_t ok = ((size_t)b * d.N + k) * d.rows;
+  const bool real = k < u.N, last = k == u.N - 1;
+  for (int r = lane; r < d.rows; r += 64) {
+    const int blk = r < d.n ? 0 : (r < 2 * d.n ? 1 : 2), i = r - blk * d.n;
+    const bool mapped = real && (blk < 2 ? i < n : (i < m && !last));
+    if (!mapped) zs[ok + r] = z[ok + r];
+  }
+  if (!real) return;
+  const LinKnotLds S(lin_lds, n, m, p);
+  cost_stage_record(rec + ((size_t)b * u.N + k) * cost_record_doubles(n, m), n, m, !last, S.sL, S.sLR, S.sG, lane);
+  for (int i = lane; i < n; i += 64) { S.sl[i] = z[ok + i]; S.sx[i] = z[ok + d.n + i]; }
+  if (!last)
+    for (int j = lane; j < m; j += 64) S.su[j] = z[ok + 2 * d.n + j];
+  wave_lds_sync();
+  cost_knot_S<true>(n, m, last, S.sL, S.sLR, S.sG, S.sl, S.sx, S.su, zs + ok, zs + ok + d.n, zs + ok + 2 * d.n, lane);
+}
+
+// mu = rho y, elementwise over [batch][N][p].
+//   grid ceil(N p / 256), batch; block 256.
+static __global__ void lin_multipliers(int per_problem, const double rho, const double* __restrict__ y,
+                                       double* __restrict__ mu) {
+  const int b = blockIdx.y;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < per_problem) mu[(size_t)b * per_problem + e] = rho * y[(size_t)b * per_problem + e];
+}
+
+}  // namespace ndlqr

@@ -480,6 +480,7 @@ int ndlqr_hip_upload_inputs(NdlqrHipCtx* c, int p0, int count, const double* AB,
   HIP_TRY(hipStreamSynchronize(s.stream));  // the host staging buffers are reused by the caller
   note_new_inputs(c);
   c->cost.dense = false;
+  c->lin.active = false;
   return NDLQR_OK;
 }
 
@@ -511,6 +512,7 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* c, const double* A, const double* B,
   HIP_TRY(hipGetLastError());
   note_new_inputs(c);              // (the whole batch: nothing of the older copies is needed any more)
   c->cost.dense = false;           // (ndlqr_hip_init_dense, which gets here with the reduced arrays, sets it again)
+  c->lin.active = false;           // (... and ndlqr_hip_init_constrained this one)
   HIP_TRY(other_stream_waits(c));  // the next solve may run on the other buffer set's stream
   return NDLQR_OK;
 }
@@ -1726,7 +1728,8 @@ int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count, doubl
   const size_t nvars = (size_t)c->du.rows * c->du.N - c->du.m, pitch = (size_t)d.rows * d.N;
   hipStream_t st = s.stream;
   HIP_TRY(launch_pack(c->du, d, KnotSlice(), zsrc + p0 * pitch, s.xfer, st, count));
-  if (c->cost.dense) HIP_TRY(cost_map_back(c, s.xfer, p0, count, st));  // the reduced variables -> the caller's, in the staging
+  // the reduced variables -> the caller's, in the staging (a constrained solve's solution is in the caller's already)
+  if (c->cost.dense && !(zsrc == c->set[c->latest].z && c->cost.mapped(c->soln_gen))) HIP_TRY(cost_map_back(c, s.xfer, p0, count, st));
   const size_t total = nvars * count;
   if (where(soln, c->device) == Where::Pinned) {
     HIP_TRY(hipMemcpyAsync(soln, s.xfer, sizeof(double) * total, hipMemcpyDeviceToHost, st));
@@ -1773,7 +1776,7 @@ int ndlqr_hip_pack_solutions_device(NdlqrHipCtx* c, double* dst) {
   HIP_TRY(hipSetDevice(c->device));
   // on the stream of the latest solve: ordered behind it, asynchronous for the caller
   HIP_TRY(launch_pack(c->du, d, KnotSlice(), c->set[c->latest].z, dst, c->set[c->latest].stream, d.batch));
-  if (c->cost.dense) HIP_TRY(cost_map_back(c, dst, 0, d.batch, c->set[c->latest].stream));
+  if (c->cost.dense && !c->cost.mapped(c->soln_gen)) HIP_TRY(cost_map_back(c, dst, 0, d.batch, c->set[c->latest].stream));
   return NDLQR_OK;
 }
 
