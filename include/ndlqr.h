@@ -441,7 +441,8 @@ int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs); /* 1: dense-cost mode, 0
  *   sp = max(max |w|, max |v|), sd = rho max |[C D]' y|.
  * REFUSED by name (NDLQR_ERR_INVALID, ndlqr_hip_last_error()): s->adapt_every > 0 (adaptive penalty); everything of the box
  * solve -- acceleration, infeasibility detection, polish, box adjoint and bound gradients -- as in dense-cost mode;
- * ndlqr_BatchStepAsync. There is no adjoint through the constrained solve yet. */
+ * ndlqr_BatchStepAsync. ndlqr_SolveBatchAdjoint refuses after a constrained solve: its adjoint is
+ * ndlqr_SolveBatchLinAdjoint (below). */
 int ndlqr_InitializeBatchFlatConstrained(NdLqrBatchSolver* bs, const double* A, const double* B, const double* Q,
                                          const double* H, const double* R, const double* q, const double* r,
                                          const double* d, const double* x0, int p, const double* C, const double* D,
@@ -758,6 +759,39 @@ int ndlqr_CopyBatchBoxAcceleration(NdLqrBatchSolver* bs, int* accepted, int* rej
  *   input upload or ndlqr_BatchSetBounds since --, and any later solve invalidates it (as the plain adjoint). Blocking. */
 int ndlqr_SolveBatchBoxAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrBoxSettings* s, int* iters, int* status);
 int ndlqr_BatchBoundGradients(NdLqrBatchSolver* bs, unsigned flags, double* gxlo, double* gxhi, double* gulo, double* guhi);
+/* additive: gradients through the solve with linear inequality constraints (differentiable MPC
+ * with rate limits, polytopic state sets, state-dependent input limits, and any box on a dense-cost problem). After
+ * ndlqr_SolveBatchLinConstrained, for a loss L(z*) of the constrained solutions and g = dL/dz* [batch][nvars] (as for
+ * ndlqr_SolveBatchAdjoint), ndlqr_SolveBatchLinAdjoint solves the adjoint of the active-set system
+ *     K w + G_A' nu = g,   G_A w = 0        (G = [C D]; the last knot: C alone)
+ * (A: the bounded rows whose projected iterate lies exactly on a bound) by the same ADMM on the forward's remembered
+ * shifted reduction and factorisation -- its rho, its bounded pattern, a cold start, nothing factored. The settings' rho,
+ * warm_start and adapt_every are ignored; alpha, eps_abs, eps_rel, max_iter and check_every (0: the defaults of the
+ * forward) apply, and iters / status report as for the forward. A problem whose forward ended as 3 is not iterated and
+ * reports 3 (w = 0, nu = 0, zero constraint gradients). Afterwards
+ *   ndlqr_CopyBatchAdjoint returns w in the caller's variables, from which dL/d(A, B, Q, H, R, q, r, d, x0) follow as the
+ *   outer products of z* and w (rslqr_amd.autograd assembles them; ndlqr_BatchGradients stays refused in dense-cost mode);
+ *   ndlqr_BatchConstraintGradients returns dL/dC [P][N][p*n] and dL/dD [P][N][p*m] (column-major per knot like C, D): row r
+ *   of knot k is -(mu_r w_x' + nu_r x_k') and -(mu_r w_u' + nu_r u_k'), exactly zero outside A and for D of the last knot;
+ *   and dL/dlo, dL/dhi [P][N][p]: nu_r goes to dL/dhi when the forward's iterate sits on hi (lo == hi included), to dL/dlo
+ *   when it sits on lo, 0 everywhere else. P = batch, or 1 with NDLQR_BOUNDS_SHARED in `flags`: summed over the batch,
+ *   deterministically (two calls give the same bits). A NULL output is not computed;
+ *   ndlqr_CopyBatchConstraintAdjointMultipliers: nu [batch][N][p], with mu's sign convention;
+ *   ndlqr_CopyBatchConstraintAdjointResiduals: [batch][4] of the adjoint's last updates, as ndlqr_CopyBatchConstraintResiduals
+ *   (a row of zeros for a problem that was not iterated);
+ *   ndlqr_CopyBatchConstraintCodes: one byte per row [batch][N][p]: 0 unbounded, 1 bounded and inactive, 2 active at lo,
+ *   3 active at hi.
+ * Outputs: host, pinned or the solver's device memory. Where the active rows are degenerate, nu is one of many.
+ *   Nothing of the forward changes: resident solution, v and y (the next warm start), mu, its residuals, the remembered
+ *   factorisation (ndlqr_hip_factor_count does not move). The adjoint refuses by name (NDLQR_ERR_INVALID,
+ *   ndlqr_hip_last_error()) unless the resident solution is that of the latest constrained solve -- no solve, new inputs,
+ *   ndlqr_BatchSetRhsFlat or ndlqr_BatchSetConstraintBounds since --, and the four read-outs unless the latest
+ *   constrained adjoint belongs to the resident solution (a plain ndlqr_SolveBatchAdjoint never feeds them). Blocking. */
+int ndlqr_SolveBatchLinAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrBoxSettings* s, int* iters, int* status);
+int ndlqr_BatchConstraintGradients(NdLqrBatchSolver* bs, double* gC, double* gD, double* glo, double* ghi, unsigned flags);
+int ndlqr_CopyBatchConstraintAdjointMultipliers(NdLqrBatchSolver* bs, double* nu);
+int ndlqr_CopyBatchConstraintAdjointResiduals(NdLqrBatchSolver* bs, double* resid);
+int ndlqr_CopyBatchConstraintCodes(NdLqrBatchSolver* bs, unsigned char* codes);
 /* additive: active-set polish of the latest constrained solve. ADMM run to a loose tolerance has
  * usually found the active set A; the constrained solution then solves K z + E_A' mu = b, E_A z = c_A, and
  * ndlqr_PolishBatchBoxConstrained solves that system directly: it reads A off the iterate (an entry is active at hi when

@@ -131,6 +131,25 @@ int ndlqr_hip_download_constraint_residuals(NdlqrHipCtx* ctx, double* resid);
 int ndlqr_hip_download_constraint_reduction(NdlqrHipCtx* ctx, double* Qs, double* Hs, double* Rs, double* L, double* LR,
                                             double* G, double* At, double* Bt, double* qt, double* rt, double* dt, double* x0t,
                                             double* v, double* y);
+/* Gradients through the solve with linear inequality constraints (ndlqr.h: ndlqr_SolveBatchLinAdjoint,
+ * ndlqr_BatchConstraintGradients). ndlqr_hip_solve_constrained_adjoint: the adjoint of the
+ * active-set system for g = dL/dz* [batch][nvars] by the forward's ADMM on its remembered shifted reduction and
+ * factorisation (its rho, a cold start, nothing factored); refuses unless the resident solution is that of the latest
+ * ndlqr_hip_solve_constrained with its right-hand side and bounds. Afterwards ndlqr_hip_download_adjoint returns w.
+ * ndlqr_hip_constraint_gradients: dL/dC [P][N][p*n], dL/dD [P][N][p*m] (column-major per knot), dL/dlo, dL/dhi [P][N][p]
+ * with P = batch, or 1 when `summed` (deterministic batch sums); each may be NULL.
+ * ndlqr_hip_download_constraint_adjoint_multipliers: nu [batch][N][p].
+ * ndlqr_hip_download_constraint_adjoint_residuals: [batch][4] of the adjoint's last updates.
+ * ndlqr_hip_download_constraint_codes: the row codes [batch][N][p] bytes (0 unbounded, 1 free, 2 at lo, 3 at hi) and,
+ * for the tests, the adjoint's own v [batch][N][p] into HOST memory (either may be NULL).
+ * The gradients and the three read-outs refuse unless the latest constrained adjoint is that of the resident solution.
+ * Outputs: host or this device's memory. */
+int ndlqr_hip_solve_constrained_adjoint(NdlqrHipCtx* ctx, const double* g, double alpha, double eps_abs, double eps_rel,
+                                        int max_iter, int check_every, int* iters, int* status);
+int ndlqr_hip_constraint_gradients(NdlqrHipCtx* ctx, int summed, double* gC, double* gD, double* glo, double* ghi);
+int ndlqr_hip_download_constraint_adjoint_multipliers(NdlqrHipCtx* ctx, double* nu);
+int ndlqr_hip_download_constraint_adjoint_residuals(NdlqrHipCtx* ctx, double* resid);
+int ndlqr_hip_download_constraint_codes(NdlqrHipCtx* ctx, unsigned char* codes, double* v);
 /* Device pointers for zero-copy producers (order: AB, QR, rhs, F, z). Allocates the factor array and
  * sets the pipeline depth to 1, so that z is THE solution buffer from then on. */
 int ndlqr_hip_device_pointers(NdlqrHipCtx* ctx, void** out5);

@@ -254,6 +254,12 @@ def lib():
     proto("ndlqr_CopyBatchConstraintMultipliers", ci, vp, dp)
     proto("ndlqr_CopyBatchConstraintResiduals", ci, vp, dp)
     proto("ndlqr_hip_download_constraint_reduction", ci, vp, *([dp] * 14))
+    proto("ndlqr_SolveBatchLinAdjoint", ci, vp, dp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_BatchConstraintGradients", ci, vp, dp, dp, dp, dp, C.c_uint)
+    proto("ndlqr_CopyBatchConstraintAdjointMultipliers", ci, vp, dp)
+    proto("ndlqr_CopyBatchConstraintAdjointResiduals", ci, vp, dp)
+    proto("ndlqr_CopyBatchConstraintCodes", ci, vp, C.c_void_p)
+    proto("ndlqr_hip_download_constraint_codes", ci, vp, C.c_void_p, dp)
     proto("ndlqr_InitializeBatchFlatDevice", ci, vp, vp, vp, vp, vp, vp, vp, vp, vp)
     proto("ndlqr_SolveBatch", ci, vp)
     proto("ndlqr_BatchSetRhsFlat", ci, vp, dp, dp, dp, dp)
@@ -620,6 +626,79 @@ class BatchSolver:
             "Qs", "Hs", "Rs", "L", "LR", "G", "At", "Bt", "qt", "rt", "dt", "x0t", "v", "y")])
         if err:
             raise RuntimeError("ndlqr_hip_download_constraint_reduction failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    # ---- gradients through the solve with linear inequality constraints (include/ndlqr.h: ndlqr_SolveBatchLinAdjoint,
+    # ndlqr_BatchConstraintGradients)
+    def solve_constrained_adjoint(self, g, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0):
+        """ndlqr_SolveBatchLinAdjoint: the adjoint of the active-set system of the last solve_constrained for g = dL/dz*
+        [batch, nvars] (numpy array or DeviceArray), on the forward's remembered shifted factorisation (its rho, a cold
+        start; 0 = the library's default for every setting). Returns (iters, status) as numpy int arrays [batch]; status 1 =
+        converged, 2 = max_iter reached, 3 = not finite (or the forward's was: not iterated, w = 0, zero gradients).
+        Raises on a nonzero return. Afterwards adjoint() gives w in the caller's variables and constraint_gradients(),
+        constraint_adjoint_multipliers(), constraint_adjoint_residuals() and constraint_codes() read the rest."""
+        if not hasattr(g, "ptr"):
+            g = np.ascontiguousarray(g, dtype=np.float64)
+        st = NdLqrBoxSettingsFull(0.0, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 0)
+        iters = np.zeros(self.batch, dtype=np.int32)
+        status = np.zeros(self.batch, dtype=np.int32)
+        err = self.L.ndlqr_SolveBatchLinAdjoint(self.h, _any_ptr(g, self.batch * self.nvars), C.byref(st),
+                                                iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                                status.ctypes.data_as(C.POINTER(C.c_int)))
+        if err:
+            raise RuntimeError("ndlqr_SolveBatchLinAdjoint failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return iters, status
+
+    def constraint_gradients(self, summed=False, out=None):
+        """ndlqr_BatchConstraintGradients: dict with keys C, D, lo, hi -> dL/d(C, D, lo, hi) of the last constrained
+        adjoint: C [batch, N, p*n] and D [batch, N, p*m] column-major per knot like the inputs, lo, hi [batch, N, p]; or
+        without the batch dimension, summed over the batch (NDLQR_BOUNDS_SHARED; two calls give the same bits). `out`:
+        dict of destinations (numpy arrays or DeviceArrays); only those keys are computed. Default: numpy arrays for all
+        four."""
+        n, m, N, B, p = self.n, self.m, self.N, self.batch, getattr(self, "_rows", 1)
+        shape = {k: ((N, w) if summed else (B, N, w)) for k, w in (("C", p * n), ("D", p * m), ("lo", p), ("hi", p))}
+        if out is None:
+            out = {k: np.zeros(sh) for k, sh in shape.items()}
+        unknown = set(out) - set(shape)
+        if unknown:
+            raise ValueError("unknown constraint gradient names: %s" % sorted(unknown))
+        ptrs = [None if out.get(k) is None else _any_ptr(out[k], int(np.prod(shape[k]))) for k in ("C", "D", "lo", "hi")]
+        err = self.L.ndlqr_BatchConstraintGradients(self.h, *ptrs, BOUNDS_SHARED if summed else 0)
+        if err:
+            raise RuntimeError("ndlqr_BatchConstraintGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def constraint_adjoint_multipliers(self):
+        """ndlqr_CopyBatchConstraintAdjointMultipliers: nu = rho y of the last constrained adjoint, [batch, N, p] (zero
+        outside the active set)."""
+        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)))
+        err = self.L.ndlqr_CopyBatchConstraintAdjointMultipliers(self.h, _ptr(out))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchConstraintAdjointMultipliers failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def constraint_adjoint_residuals(self, resid=None):
+        """ndlqr_CopyBatchConstraintAdjointResiduals: [batch, 4] = r_prim | r_dual | s_prim | s_dual of the last constrained
+        adjoint (a row of zeros for a problem it did not iterate)."""
+        return self._residuals("ndlqr_CopyBatchConstraintAdjointResiduals", resid)
+
+    def constraint_codes(self):
+        """ndlqr_CopyBatchConstraintCodes: uint8 [batch, N, p] of the last constrained adjoint -- 0 unbounded, 1 bounded
+        and inactive, 2 active at lo, 3 active at hi."""
+        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)), dtype=np.uint8)
+        err = self.L.ndlqr_CopyBatchConstraintCodes(self.h, out.ctypes.data_as(C.c_void_p))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchConstraintCodes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def constraint_adjoint_iterate(self):
+        """ndlqr_hip_download_constraint_codes (read-out for the tests): the constrained adjoint's own projected iterate
+        v [batch, N, p] (0 on the fixed and the unbounded rows)."""
+        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)))
+        err = self.L.ndlqr_hip_download_constraint_codes(self.ctx, None, _ptr(out))
+        if err:
+            raise RuntimeError("ndlqr_hip_download_constraint_codes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
 
     def initialize_synthetic(self, seed0):

@@ -17,6 +17,10 @@ module returns may be used on any stream at once.
 ``lqr_solve_dense`` takes dense cost matrices Q, R and a state-input cross term H (ndlqr_InitializeBatchFlatDense); its
 backward is one adjoint solve, the gradients are assembled in torch from z and w.
 
+``lqr_solve_constrained`` adds rows lo <= C x + D u <= hi to the dense-cost problem (ndlqr_SolveBatchLinConstrained); its
+backward is the adjoint of the active-set system (ndlqr_SolveBatchLinAdjoint), the nine problem gradients assembled as for
+``lqr_solve_dense`` and the four row gradients from ndlqr_BatchConstraintGradients.
+
 ``lqr_solve_box`` adds bounds on x and u (ndlqr_SolveBatchBoxConstrained); its backward is the adjoint of the
 active-set system (ndlqr_SolveBatchBoxAdjoint) plus the gradients with respect to the bounds (ndlqr_BatchBoundGradients).
 
@@ -386,6 +390,7 @@ def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=Non
 
 
 __all__ = ["LqrSolve", "LqrSolveRefined", "LqrSolveBox", "lqr_solve", "lqr_solve_box", "split_solution"]
+# (lqr_solve_dense and lqr_solve_constrained, below, are imported by name)
 
 
 # ------------------------------------------------------------------------------------------------ dense cost matrices
@@ -403,6 +408,28 @@ def _dense_solve(bs, flat, token, key):
         raise RuntimeError("lqr_solve_dense: the factorisation failed (%d non-positive pivots): R or Q - H R^-1 H' are not "
                            "positive definite" % max(bs.cholesky_failures(), 1))
     _dense_cache[key][1] = token
+
+
+def _dense_gradients(z, w, n, m, N):
+    """dL/d(A, B, Q, H, R, q, r, d, x0) [b, ...] in the math convention from the solutions z and the adjoint solutions w
+    [b, nvars], both in the caller's variables: the outer products per knot with the signs and per-knot conventions of
+    kernels_grad.hpp (zero for A, B, H, R, r, d of the last knot; Q and R as symmetric matrices). They hold for the plain
+    dense-cost solve and, with w of the active-set system, for the constrained one (G_A w = 0 drops the constraint term)."""
+    zl, zx, zu = split_solution(z, n, m, N)
+    wl, wx, wu = split_solution(w, n, m, N)
+    outer = lambda a, c: a.unsqueeze(-1) * c.unsqueeze(-2)
+    pad = lambda t: torch.nn.functional.pad(t, (0, 0) * (t.dim() - 2) + (0, 1))  # a zero last knot
+    zx1, wx1 = zx[:, :N - 1], wx[:, :N - 1]
+    gA = pad(-(outer(wl[:, 1:], zx1) + outer(zl[:, 1:], wx1)))
+    gB = pad(-(outer(wl[:, 1:], zu) + outer(zl[:, 1:], wu)))
+    gQ = -0.5 * (outer(wx, zx) + outer(zx, wx))
+    gH = pad(-(outer(wx1, zu) + outer(zx1, wu)))
+    gR = pad(-0.5 * (outer(wu, zu) + outer(zu, wu)))
+    gq = -wx
+    gr = pad(-wu)
+    gd = pad(-wl[:, 1:])
+    gx0 = -wl[:, 0]
+    return (gA, gB, gQ, gH, gR, gq, gr, gd, gx0)
 
 
 class LqrSolveDense(torch.autograd.Function):
@@ -445,21 +472,7 @@ class LqrSolveDense(torch.autograd.Function):
             raise RuntimeError("lqr_solve_dense backward: adjoint solve failed: %d" % err)
         w = torch.empty_like(z)
         bs.adjoint(_View(w))
-        zl, zx, zu = split_solution(z, n, m, N)
-        wl, wx, wu = split_solution(w, n, m, N)
-        outer = lambda a, c: a.unsqueeze(-1) * c.unsqueeze(-2)
-        pad = lambda t: torch.nn.functional.pad(t, (0, 0) * (t.dim() - 2) + (0, 1))  # a zero last knot
-        zx1, wx1 = zx[:, :N - 1], wx[:, :N - 1]
-        gA = pad(-(outer(wl[:, 1:], zx1) + outer(zl[:, 1:], wx1)))
-        gB = pad(-(outer(wl[:, 1:], zu) + outer(zl[:, 1:], wu)))
-        gQ = -0.5 * (outer(wx, zx) + outer(zx, wx))
-        gH = pad(-(outer(wx1, zu) + outer(zx1, wu)))
-        gR = pad(-0.5 * (outer(wu, zu) + outer(zu, wu)))
-        gq = -wx
-        gr = pad(-wu)
-        gd = pad(-wl[:, 1:])
-        gx0 = -wl[:, 0]
-        grads = (gA, gB, gQ, gH, gR, gq, gr, gd, gx0)
+        grads = _dense_gradients(z, w, n, m, N)
         return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
 
 
@@ -503,3 +516,154 @@ def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
     # (a shared argument is expanded here, outside the Function: autograd sums its gradient over the batch)
     full = [t if t.dim() == len(per[name]) + 1 else t.unsqueeze(0).expand(b, *t.shape) for name, t in zip(_DENSE_ARGS, args)]
     return LqrSolveDense.apply(*full)
+
+
+# ------------------------------------------------------------------------------------------------ linear inequality constraints
+# A cache of its own once more: a solver in constrained mode retains its problem on the device.
+_ROW_ARGS = ("C", "D", "lo", "hi")
+_lin_cache = {}              # (n, m, N, p, b, device index) -> [BatchSolver, token of the forward it holds]
+
+
+def _lin_solve(bs, flat, settings, token, key):
+    """Initialise + constrained solve (cold) of `flat` on the cached solver; it then holds `token`."""
+    torch.cuda.current_stream(flat[0].device).synchronize()  # (the library reads torch memory on its own stream)
+    _lin_cache[key][1] = None
+    rho, alpha, eps_abs, eps_rel, max_iter, check_every = settings
+    try:
+        bs.initialize_flat_constrained(*[_View(t) for t in flat])
+        _, status = bs.solve_constrained(rho=rho, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
+                                         check_every=check_every)
+    except RuntimeError as e:
+        raise RuntimeError("lqr_solve_constrained: the constrained solve failed (%s)" % e) from None
+    bad = int((status != 1).sum())
+    if bad:
+        raise RuntimeError("lqr_solve_constrained: %d of %d problems did not converge (status %s): raise max_iter or change rho"
+                           % (bad, status.size, sorted(set(status.tolist()) - {1})))
+    _lin_cache[key][1] = token
+
+
+class LqrSolveConstrained(torch.autograd.Function):
+    """Forward: ndlqr_InitializeBatchFlatConstrained + ndlqr_SolveBatchLinConstrained (cold). Backward: the adjoint of the
+    active-set system (ndlqr_SolveBatchLinAdjoint, the forward's alpha, tolerances and max_iter); the nine problem
+    gradients from z* and w (_dense_gradients), dL/d(C, D, lo, hi) from ndlqr_BatchConstraintGradients -- batch-summed on
+    the device when every row argument is shared (row_shared), else per problem."""
+
+    @staticmethod
+    def forward(ctx, settings, row_shared, A, B, Q, H, R, q, r, d, x0, C_, D_, lo, hi):
+        b, N, n, m = B.shape
+        p = C_.shape[-2]
+        dev = A.device
+        key = (n, m, N, p, b, dev.index if dev.index is not None else torch.cuda.current_device())
+        if key not in _lin_cache:
+            _lin_cache[key] = [BatchSolver(n, m, N, b, device=key[5], flags=FLAG_KEEP_RECORDS), None]
+        bs = _lin_cache[key][0]
+        expand = lambda t, sh: t.unsqueeze(0).expand(b, *t.shape) if sh else t
+        rows = [expand(t.detach(), sh) for t, sh in zip((C_, D_, lo, hi), row_shared)]
+        # the flat layout: matrices column-major per knot (the transpose, stored row-major)
+        flat = [(t.detach().transpose(-1, -2) if t.dim() == 4 else t.detach()).contiguous().reshape(b, -1)
+                for t in (A, B, Q, H, R, q, r, d, x0, rows[0], rows[1])] + [t.contiguous().reshape(b, -1) for t in rows[2:]]
+        token = next(_tokens)
+        _lin_solve(bs, flat, settings, token, key)
+        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
+        bs.solutions_to_device(z.data_ptr())
+        bs.synchronize()
+        ctx.key, ctx.token, ctx.flat, ctx.dims, ctx.settings, ctx.row_shared = key, token, flat, (n, m, N, p, b), settings, row_shared
+        ctx.save_for_backward(z)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        n, m, N, p, b = ctx.dims
+        (z,) = ctx.saved_tensors
+        bs = _lin_cache[ctx.key][0]
+        if _lin_cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's forward again
+            _lin_solve(bs, ctx.flat, ctx.settings, ctx.token, ctx.key)
+        gz = gz.detach().to(torch.float64).contiguous()
+        torch.cuda.current_stream(gz.device).synchronize()
+        _, alpha, eps_abs, eps_rel, max_iter, check_every = ctx.settings
+        try:
+            _, status = bs.solve_constrained_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
+                                                     check_every=check_every)
+        except RuntimeError as e:
+            raise RuntimeError("lqr_solve_constrained backward: the adjoint failed (%s)" % e) from None
+        bad = int((status != 1).sum())
+        if bad:
+            raise RuntimeError("lqr_solve_constrained backward: the adjoint of %d of %d problems did not converge (status %s)"
+                               % (bad, status.size, sorted(set(status.tolist()) - {1})))
+        w = torch.empty_like(z)
+        bs.adjoint(_View(w))
+        need = ctx.needs_input_grad[2:]
+        grads = [g if nd else None for g, nd in zip(_dense_gradients(z, w, n, m, N), need[:9])]
+        need_rows = need[9:]
+        wanted = [k for k, nd in zip(_ROW_ARGS, need_rows) if nd]
+        summed = bool(wanted) and all(sh for k, sh in zip(_ROW_ARGS, ctx.row_shared) if k in wanted)
+        width = dict(C=p * n, D=p * m, lo=p, hi=p)
+        out = {k: torch.empty(((N, width[k]) if summed else (b, N, width[k])), dtype=torch.float64, device=gz.device) for k in wanted}
+        if out:
+            bs.constraint_gradients(summed, {k: _View(v) for k, v in out.items()})
+        for k, sh in zip(_ROW_ARGS, ctx.row_shared):
+            g = out.get(k)
+            if g is not None:
+                if sh and not summed:
+                    g = g.sum(0)
+                if k in ("C", "D"):  # flat column-major -> row-major math convention
+                    g = g.reshape(*g.shape[:-1], n if k == "C" else m, p).transpose(-1, -2)
+            grads.append(g)
+        return (None, None) + tuple(grads)
+
+
+def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0,
+                          max_iter=0, check_every=0):
+    """z* [b, nvars] of the dense-cost LQR problems of lqr_solve_dense subject to, per knot, p rows
+        lo_k <= C_k x_k + D_k u_k <= hi_k,     C [b, N, p, n]   D [b, N, p, m]   lo, hi [b, N, p]
+    (entries of lo, hi may be +-inf; D of the last knot is not part of the problem), by the solve with linear inequality
+    constraints (ndlqr_SolveBatchLinConstrained, cold start; 0 = the library's default for every setting), differentiable
+    in all thirteen tensors. Any argument may leave out the batch dimension (shared: its gradient is the batch sum -- for
+    C, D, lo, hi computed on the device when all of them that need a gradient are shared). The backward is the adjoint
+    of the active-set system (ndlqr_SolveBatchLinAdjoint) with the same alpha, tolerances, max_iter and check_every on the
+    forward's factorisation. Raises RuntimeError when a problem's forward or adjoint iteration does not converge (status
+    != 1). The gradients hold where the active set is locally stable (strict complementarity, independent active rows);
+    dL/dC and dL/dD are exactly zero on the rows that are not active."""
+    args = (A, B, Q, H, R, q, r, d, x0, C, D, lo, hi)
+    names = _DENSE_ARGS + _ROW_ARGS
+    dev = None
+    for name, t in zip(names, args):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("lqr_solve_constrained: %s must be a torch.Tensor" % name)
+        if t.dtype != torch.float64:
+            raise TypeError("lqr_solve_constrained: %s must be float64, got %s" % (name, t.dtype))
+        if t.device.type != "cuda":
+            raise ValueError("lqr_solve_constrained: %s must live on a ROCm device, got %s" % (name, t.device))
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            raise ValueError("lqr_solve_constrained: every argument must be on one device (%s is on %s, A on %s)"
+                             % (name, t.device, dev))
+    if A.dim() not in (3, 4) or A.shape[-1] != A.shape[-2] or B.dim() not in (3, 4) or B.shape[-3:-1] != A.shape[-3:-1]:
+        raise ValueError("lqr_solve_constrained: A must be [b, N, n, n] and B [b, N, n, m] (b optional), got %s and %s"
+                         % (tuple(A.shape), tuple(B.shape)))
+    N, n, m = B.shape[-3:]
+    if C.dim() not in (3, 4) or C.shape[-3] != N or C.shape[-1] != n or C.shape[-2] < 1:
+        raise ValueError("lqr_solve_constrained: C must be [b, N, p, n] or [N, p, n] with p >= 1, got %s" % (tuple(C.shape),))
+    p = C.shape[-2]
+    per = dict(A=(N, n, n), B=(N, n, m), Q=(N, n, n), H=(N, n, m), R=(N, m, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,),
+               C=(N, p, n), D=(N, p, m), lo=(N, p), hi=(N, p))
+    batch = set()
+    shared = {}
+    for name, t in zip(names, args):
+        if tuple(t.shape) == per[name]:
+            shared[name] = True
+        elif t.dim() == len(per[name]) + 1 and tuple(t.shape[1:]) == per[name]:
+            shared[name] = False
+            batch.add(t.shape[0])
+        else:
+            raise ValueError("lqr_solve_constrained: %s must be [b, %s] or %s, got %s"
+                             % (name, ", ".join(str(x) for x in per[name]), list(per[name]), tuple(t.shape)))
+    if len(batch) > 1:
+        raise ValueError("lqr_solve_constrained: batch dimensions disagree: %s" % sorted(batch))
+    b = batch.pop() if batch else 1
+    # (a shared problem argument is expanded here, outside the Function: autograd sums its gradient over the batch; the row
+    #  arguments go in as they are, so that the library can sum theirs)
+    full = [t if not shared[name] else t.unsqueeze(0).expand(b, *t.shape) for name, t in zip(_DENSE_ARGS, args[:9])]
+    settings = (float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(check_every))
+    return LqrSolveConstrained.apply(settings, tuple(shared[k] for k in _ROW_ARGS), *full, C, D, lo, hi)

@@ -219,6 +219,33 @@ int ndlqr_CopyBatchConstraintResiduals(NdLqrBatchSolver* bs, double* resid) {
   if (!bs || !resid) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_constraint_residuals(bs->ctx, resid);
 }
+int ndlqr_SolveBatchLinAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrBoxSettings* s, int* iters, int* status) {
+  NdLqrBoxSettings z;
+  if (!bs) return NDLQR_ERR_INVALID;
+  memset(&z, 0, sizeof(z));
+  if (s) z = *s;
+  /* (rho, warm_start and adapt_every are the forward's: ignored here. 0: the default; anything else goes on as it is, and
+   *  what is out of range is refused by name) */
+  return ndlqr_hip_solve_constrained_adjoint(bs->ctx, g, z.alpha != 0.0 ? z.alpha : 1.6, z.eps_abs != 0.0 ? z.eps_abs : 1e-6,
+                                             z.eps_rel != 0.0 ? z.eps_rel : 1e-6, z.max_iter != 0 ? z.max_iter : 4000,
+                                             z.check_every != 0 ? z.check_every : 10, iters, status);
+}
+int ndlqr_BatchConstraintGradients(NdLqrBatchSolver* bs, double* gC, double* gD, double* glo, double* ghi, unsigned flags) {
+  if (!bs || (flags & ~NDLQR_BOUNDS_SHARED)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_constraint_gradients(bs->ctx, (flags & NDLQR_BOUNDS_SHARED) ? 1 : 0, gC, gD, glo, ghi);
+}
+int ndlqr_CopyBatchConstraintAdjointMultipliers(NdLqrBatchSolver* bs, double* nu) {
+  if (!bs || !nu) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_adjoint_multipliers(bs->ctx, nu);
+}
+int ndlqr_CopyBatchConstraintAdjointResiduals(NdLqrBatchSolver* bs, double* resid) {
+  if (!bs || !resid) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_adjoint_residuals(bs->ctx, resid);
+}
+int ndlqr_CopyBatchConstraintCodes(NdLqrBatchSolver* bs, unsigned char* codes) {
+  if (!bs || !codes) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_codes(bs->ctx, codes, NULL);
+}
 
 /* Synthetic problems of one staging chunk are generated and packed side by side on host threads
  * (one splitmix64 stream per problem, so the result does not depend on the thread count): the

@@ -448,6 +448,32 @@ struct LinState {
   }
 };
 
+// Gradients through the solve with linear inequality constraints (ndlqr_hip_solve_constrained_adjoint /
+// ndlqr_hip_constraint_gradients, kernels_lin_grad.hpp). gen: the solution generation the
+// constrained adjoint belongs to (0: none). The adjoint's own row codes, v, y [batch][N][p], ADMM right-hand sides (its
+// resident one is adj.rhs, its re-solves go to lin.z, its solution to adj.z), per problem status, iterations and
+// residuals, and its running count (word, h_word): nothing of the forward's iteration state is touched. lds_asked: as
+// LinState's, for lin_adjoint_start | lin_adjoint_update<true> | <false> | lin_adjoint_finish.
+struct LinAdjointState {
+  DevBuf<unsigned char> code;
+  DevBuf<double> v, y, resid, rhs[2];
+  DevBuf<int> status, iters, word;
+  PinnedBuf<int> h_word;
+  int p = 0;
+  size_t lds_asked[4] = {};
+  unsigned long long gen = 0;
+  // the buffers that depend on p are allocated again when p changes
+  hipError_t ensure(const ndlqr::Dims& u, const ndlqr::Dims& dd, int rows_per_knot) {
+    if (rows_per_knot != p) {
+      code.reset(); v.reset(); y.reset();
+    }
+    p = rows_per_knot;
+    const size_t np = (size_t)u.batch * u.N * p, nz = doubles_z(dd), nb = (size_t)u.batch;
+    return first_error({code.ensure(np), v.ensure(np), y.ensure(np), rhs[0].ensure(nz), rhs[1].ensure(nz), resid.ensure(4 * nb),
+                        status.ensure(nb), iters.ensure(nb), word.ensure(1), h_word.ensure(1)});
+  }
+};
+
 struct NdlqrHipCtx {
   ndlqr::Dims d = {};   // block sizes of the DEVICE layout (every kernel works on these)
   ndlqr::Dims du = {};  // the caller's block sizes and horizon: the same, or smaller when the problem runs zero-padded into
@@ -514,9 +540,14 @@ struct NdlqrHipCtx {
   MultiRhsState multi;
   CostState cost;
   LinState lin;
+  LinAdjointState alin;
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // the remembered shifted factorisations (ADMM's and the polish's) no longer match the records / factors
   void forget_shifted() { box.fact = pol.fact = lin.fact = false; }
+  // adj.z holds w of the constrained adjoint of the resident solution, in the caller's variables already
+  bool lin_adjoint_resident() const {
+    return alin.gen != 0 && alin.gen == soln_gen && adj.gen == soln_gen && lin.soln_gen == soln_gen && !lin.rhs_new;
+  }
   // profile
   std::vector<PendingEvent> pending;
   std::vector<hipEvent_t> event_pool;

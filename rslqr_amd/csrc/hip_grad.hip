@@ -13,7 +13,8 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   if (!c || !g) return NDLQR_ERR_INVALID;
   if (c->lin.soln_gen != 0 && c->lin.soln_gen == c->soln_gen)
     return refuse("ndlqr_hip_solve_adjoint: the resident solution is that of a solve with linear inequality constraints "
-                  "(ndlqr_hip_solve_constrained), which has no adjoint yet; a plain solve gives the unconstrained one");
+                  "(ndlqr_hip_solve_constrained), whose adjoint is ndlqr_hip_solve_constrained_adjoint; a plain solve gives "
+                  "the unconstrained one");
   if (!c->kept.fact_valid && !c->kept.rec_complete)
     return refuse("adjoint solve needs a previous solve with NDLQR_FLAG_KEEP_FACT or NDLQR_FLAG_KEEP_RECORDS (cached "
                   "factorisation) of the resident inputs");
@@ -60,7 +61,9 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
 
 int ndlqr_hip_download_adjoint(NdlqrHipCtx* c, double* w) {
   if (!c || !w) return NDLQR_ERR_INVALID;
-  const int aerr = need_adjoint(c, "ndlqr_hip_download_adjoint");
+  // (w of a constrained adjoint: the scope of the shifted reduction repacked the inputs, which is no replacement)
+  const bool lin_adj = c->lin_adjoint_resident() && !c->z_partial && !c->z_invalid;
+  const int aerr = lin_adj ? NDLQR_OK : need_adjoint(c, "ndlqr_hip_download_adjoint");
   if (aerr) return aerr;
   HIP_TRY(hipSetDevice(c->device));
   const Where ww = where(w, c->device);
@@ -69,7 +72,7 @@ int ndlqr_hip_download_adjoint(NdlqrHipCtx* c, double* w) {
   const BufferSet& s = c->set[0];
   HIP_TRY(sync_all(c));
   HIP_TRY(launch_pack(c->du, c->d, KnotSlice(), c->adj.z, w, s.stream, c->d.batch));
-  if (c->cost.dense) HIP_TRY(cost_map_back(c, w, 0, c->d.batch, s.stream));
+  if (c->cost.dense && !lin_adj) HIP_TRY(cost_map_back(c, w, 0, c->d.batch, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }

@@ -1,9 +1,10 @@
 // hip_lin.hip -- general linear inequality constraints lo <= C x + D u <= hi (ndlqr_hip_init_constrained,
-// ndlqr_hip_set_constraint_bounds, ndlqr_hip_solve_constrained and their read-outs): the host
-// side, the kernels of kernels_lin.hpp. The reduction kernels it needs belong to hip_cost.hip (cost_reduce_problem,
+// ndlqr_hip_set_constraint_bounds, ndlqr_hip_solve_constrained and their read-outs) and the
+// gradients through that solve (ndlqr_hip_solve_constrained_adjoint, ndlqr_hip_constraint_gradients; section 3.18): the
+// host side, the kernels of kernels_lin.hpp and kernels_lin_grad.hpp. The reduction kernels it needs belong to hip_cost.hip (cost_reduce_problem,
 // cost_reduce_rhs_to).
 #include "hip_host.hpp"
-#include "kernels_lin.hpp"
+#include "kernels_lin_grad.hpp"
 
 // ------------------------------------------------------------------------------ constrained mode
 // A dense-cost mode with constraints: ndlqr_hip_init_constrained retains the caller's A, B, Q, H, R, q, r, d, x0 and C, D
@@ -55,6 +56,7 @@ static int lin_take_bounds(NdlqrHipCtx* c, const char* who, const double* lo, co
   k.shared = shared != 0;
   k.bstride = shared ? 0 : (size_t)u.N * k.p;
   k.soln_gen = 0;
+  c->alin.gen = 0;
   return NDLQR_OK;
 }
 
@@ -86,6 +88,7 @@ int ndlqr_hip_init_constrained(NdlqrHipCtx* c, const double* A, const double* B,
   //  dense-cost mode, if the context was in one, stays valid)
   k.active = false;
   k.fact = false;
+  c->alin.gen = 0;
   HIP_TRY(k.ensure(u, c->d, p, st));
   err = lin_take_bounds(c, "ndlqr_hip_init_constrained", lo, hi, shared, false);
   if (err) return err;
@@ -347,5 +350,262 @@ int ndlqr_hip_download_constraint_reduction(NdlqrHipCtx* c, double* Qs, double* 
                           kn * k.p, kn * k.p};
   for (int i = 0; i < 11; ++i)
     if (dst[i]) HIP_TRY(hipMemcpy(dst[i], src[i], sizeof(double) * cnt[i], hipMemcpyDeviceToHost));
+  return NDLQR_OK;
+}
+
+// ------------------------------------------------------------------------------ gradients through the constrained solve
+// The adjoint of the active-set system K w + G_A' nu = g, G_A w = 0 (kernels_lin_grad.hpp) by the
+// ADMM of the forward on its remembered shifted reduction and factorisation: the shifted reduced problem in force again
+// (ShiftedReduction, restored on every exit), the kept records / factors taken as the forward left them -- nothing is
+// factored --, every iteration one re-solve into lin.z plus one lin_adjoint_update, the host reading the running count
+// every check_every iterations. The right-hand-side columns of the kept records are saved and restored around it as for
+// the plain adjoint. Afterwards the forward's bookkeeping is put back as its own epilogue leaves it.
+
+// is the resident solution that of the latest constrained solve, with its factorisation, right-hand side and bounds?
+static int need_constrained_solution(const NdlqrHipCtx* c, const char* who) {
+  if (const int merr = need_constrained(c, who)) return merr;
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, who);
+  const LinState& k = c->lin;
+  if (k.soln_gen == 0 || k.soln_gen != c->soln_gen || !k.fact || !k.have_vy || k.rhs_new)
+    return refuse(std::string(who) + ": the resident solution is not that of the latest constrained solve "
+                  "(ndlqr_hip_solve_constrained first; a solve, new inputs, a new right-hand side or new bounds came after it)");
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_solve_constrained_adjoint(NdlqrHipCtx* c, const double* g, double alpha, double eps_abs, double eps_rel,
+                                        int max_iter, int check_every, int* iters, int* status) {
+  if (!c) return NDLQR_ERR_INVALID;
+  if (!g || !(alpha > 0.0 && alpha < 2.0) || !(eps_abs >= 0.0) || !(eps_rel >= 0.0) || max_iter < 1 || check_every < 1)
+    return refuse("ndlqr_hip_solve_constrained_adjoint: bad argument (g, 0 < alpha < 2, eps_abs >= 0, eps_rel >= 0, "
+                  "max_iter >= 1, check_every >= 1)");
+  if (const int serr = need_constrained_solution(c, "ndlqr_hip_solve_constrained_adjoint")) return serr;
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  LinState& k = c->lin;
+  LinAdjointState& a = c->alin;
+  if (k.kept.time_shard) return refuse("ndlqr_hip_solve_constrained_adjoint: not available on a time-axis shard");
+  HIP_TRY(hipSetDevice(c->device));
+  CallerArrays<1> ga = {{const_cast<double*>(g)}, {((size_t)u.rows * u.N - u.m) * d.batch}};
+  int err = ga.classify(c, "ndlqr_hip_solve_constrained_adjoint", "g lies");
+  if (!err) err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_constrained_adjoint", iters, status);
+  if (err) return err;
+  HIP_TRY(c->adj.ensure(d, c->set[0].stream));
+  HIP_TRY(a.ensure(u, d, k.p));
+  HIP_TRY(c->grad_stage.grow(ga.stage));
+  // 1. everything idle, the primary set current; g packed into the adjoint's resident right-hand side
+  HIP_TRY(sync_all(c));
+  c->cur = 0;
+  BufferSet& s = c->set[0];
+  const hipStream_t st = s.stream;
+  ga.place(c);
+  err = ga.copy(st, true);
+  if (err) return err;
+  a.gen = 0;
+  c->adj.gen = 0;
+  const bool strict = (k.flags & NDLQR_FLAG_STRICT_FP) != 0;
+  const int p = k.p;
+  const double rho = k.rho_value;
+  const size_t lds = lin_update_lds_bytes(u, p), flds = sizeof(double) * ndlqr::lin_wave_lds(u.n, u.m, p);
+  // what the scope's initialiser drops and the forward's epilogue had left
+  const KeptState fwd_kept = k.kept;
+  const unsigned fwd_flags = k.flags;
+  const bool fwd_inputs_replaced = c->inputs_replaced;
+  HIP_TRY(hipEventRecord(s.ev_start, st));
+  ShiftedReduction shifted(c);
+  // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
+  const auto iterate = [&]() -> int {
+    HIP_TRY(launch_adjoint_rhs(c, ga.dev[0], st));
+    // 2. the shifted reduced problem in force, the remembered factorisation taken up, its record columns saved
+    int e = shifted.open(fwd_flags);
+    if (e) return e;
+    c->kept = fwd_kept;
+    HIP_TRY(adjoint_scratch(c, false));
+    // 3. codes, v = y = 0, S^' g and both right-hand sides, status
+    const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
+    HIP_TRY(allow_lin_lds(ndlqr::lin_adjoint_start, flds, a.lds_asked[0]));
+    if (strict) HIP_TRY(allow_lin_lds(ndlqr::lin_adjoint_update<true>, lds, a.lds_asked[1]));
+    else HIP_TRY(allow_lin_lds(ndlqr::lin_adjoint_update<false>, lds, a.lds_asked[2]));
+    HIP_TRY(allow_lin_lds(ndlqr::lin_adjoint_finish, flds, a.lds_asked[3]));
+    HIP_TRY(hipMemsetAsync(a.word, 0, sizeof(int), st));
+    // (the read-out row of a problem that is not iterated -- forward status 3 -- is zero)
+    HIP_TRY(hipMemsetAsync(a.resid, 0, sizeof(double) * 4 * (size_t)u.batch, st));
+    hipLaunchKernelGGL(ndlqr::lin_adjoint_start, dim3(d.N, d.batch), dim3(64), flds, st, u, d, p, (const double*)k.rec,
+                       (const double*)k.lo, (const double*)k.hi, k.bstride, (const double*)k.v, (const int*)k.status,
+                       c->adj.rhs.get(), a.code.get(), a.v.get(), a.y.get(), a.rhs[0].get(), a.rhs[1].get(), a.status.get(),
+                       a.iters.get(), a.word.get());
+    HIP_TRY(hipGetLastError());
+    // 4. the iterations (none when every problem's forward ended non-finite)
+    HIP_TRY(hipMemcpyAsync(a.h_word, a.word, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const bool any = a.h_word[0] > 0;
+    for (int it = 1; it <= max_iter && any; ++it) {
+      const double* rc = a.rhs[(it - 1) & 1];
+      double* rn = a.rhs[it & 1];
+      e = launch_resolve(c, rc, k.z, "constrained adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      if (e) return e;
+      launch_strict(strict, ndlqr::lin_adjoint_update, dim3(u.batch), dim3(256), lds, st, u, d, p, it, P, (const double*)k.z,
+                    (const double*)k.rec, (const double*)k.C, (const double*)k.D, (const unsigned char*)a.code, a.v.get(),
+                    a.y.get(), (const double*)c->adj.rhs, rc, rn, rho, a.status.get(), a.iters.get(), a.resid.get(),
+                    a.word.get());
+      HIP_TRY(hipGetLastError());
+      if (it % check_every == 0 || it == max_iter) {
+        HIP_TRY(hipMemcpyAsync(a.h_word, a.word, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (a.h_word[0] == 0) break;
+      }
+    }
+    if (!any) {  // (no re-solve ran: lin.z defined all the same -- the re-solve of S^' g)
+      e = launch_resolve(c, a.rhs[0], k.z, "constrained adjoint: this configuration needs NDLQR_FLAG_KEEP_FACT");
+      if (e) return e;
+    }
+    // 5. w = S^ w~ of the last re-solve, in the caller's variables
+    hipLaunchKernelGGL(ndlqr::lin_adjoint_finish, dim3(d.N, d.batch), dim3(64), flds, st, u, d, p, (const double*)k.rec,
+                       (const double*)k.z, (const int*)a.status, c->adj.z.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(adjoint_scratch(c, true));
+    return NDLQR_OK;
+  };
+  err = iterate();
+  // 6. the plain reduced problem again; the forward's bookkeeping as its epilogue left it
+  const int cerr = shifted.close();
+  if (!err) err = cerr;
+  if (err) {
+    k.fact = false;
+    c->state_dirty = true;
+    (void)hipStreamSynchronize(st);
+    return err;
+  }
+  k.fact = true;  // (the initialiser inside the scope dropped it; rho_value, flags and kept were never touched)
+  k.kept = fwd_kept;
+  k.flags = fwd_flags;
+  c->inputs_replaced = fwd_inputs_replaced;
+  HIP_TRY(hipEventRecord(s.ev_stop, st));
+  err = deliver_iters_status(c, st, a.iters, a.status, iters, status);
+  if (err) return err;
+  note_elapsed(c, s);
+  c->adj.gen = c->soln_gen;
+  a.gen = c->soln_gen;
+  return NDLQR_OK;
+}
+
+// is there a constrained adjoint of the resident solution?
+static int need_constrained_adjoint(const NdlqrHipCtx* c, const char* who) {
+  if (const int merr = need_constrained(c, who)) return merr;
+  if (c->z_partial || c->z_invalid) return need_full_solution(c, who);
+  if (!c->lin_adjoint_resident())
+    return refuse(std::string(who) + ": no constrained adjoint of the resident solution (ndlqr_hip_solve_constrained_adjoint "
+                  "after the latest constrained solve)");
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_constraint_gradients(NdlqrHipCtx* c, int summed, double* gC, double* gD, double* glo, double* ghi) {
+  if (!c) return NDLQR_ERR_INVALID;
+  if (const int aerr = need_constrained_adjoint(c, "ndlqr_hip_constraint_gradients")) return aerr;
+  const ndlqr::Dims& d = c->d;
+  const ndlqr::Dims& u = c->du;
+  const LinState& k = c->lin;
+  const LinAdjointState& a = c->alin;
+  const int p = k.p;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t P = summed ? 1 : (size_t)u.batch, kn = P * u.N;
+  CallerArrays<4> go = {{gC, gD, glo, ghi}, {kn * p * u.n, kn * p * u.m, kn * p, kn * p}};
+  int err = go.classify(c, "ndlqr_hip_constraint_gradients", "an output lies");
+  if (err) return err;
+  if (!gC && !gD && !glo && !ghi) return NDLQR_OK;
+  // batch sums: entries of [N][W] one per thread, the batch split into about 2048 / ceil(entries / 256) runs of problems
+  // added in order, then the runs in order (ndlqr_hip_bound_gradients' scheme: deterministic, no atomics)
+  const size_t E = (size_t)u.N * ndlqr::lin_grad_width(u.n, u.m, p);
+  const unsigned nblk = (unsigned)((E + 255) / 256);
+  int nsplit = 1, ppb = u.batch;
+  if (summed) {
+    nsplit = (int)(2048 / nblk);
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > u.batch) nsplit = u.batch;
+    ppb = (u.batch + nsplit - 1) / nsplit;
+    nsplit = (u.batch + ppb - 1) / ppb;
+  }
+  const size_t npart = nsplit > 1 ? (size_t)nsplit * E : 0;
+  HIP_TRY(c->grad_stage.grow(go.stage + npart));
+  HIP_TRY(sync_all(c));
+  BufferSet& s = c->set[0];
+  ndlqr::LinGradOut out = {};
+  double* part = go.place(c);  // (the partial sums behind the staged outputs)
+  if (!npart) part = nullptr;
+  for (int i = 0; i < 4; ++i) out.p[i] = go.dev[i];
+  const bool strict = (k.flags & NDLQR_FLAG_STRICT_FP) != 0;
+  const double* z = c->set[c->latest].z;
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  if (!summed) {
+    launch_strict(strict, ndlqr::lin_constraint_grads, dim3(u.N, u.batch), dim3(64), 0, s.stream, u, d, p, k.rho_value,
+                  (const unsigned char*)a.code, (const double*)k.y, (const double*)a.y, (const int*)a.status, z,
+                  (const double*)c->adj.z, out);
+    HIP_TRY(hipGetLastError());
+  } else {
+    launch_strict(strict, ndlqr::lin_constraint_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d, p, k.rho_value, ppb,
+                  (const unsigned char*)a.code, (const double*)k.y, (const double*)a.y, (const int*)a.status, z,
+                  (const double*)c->adj.z, out, part);
+    HIP_TRY(hipGetLastError());
+    if (part) {
+      hipLaunchKernelGGL(ndlqr::lin_grad_sum_splits, dim3(nblk), dim3(256), 0, s.stream, u, p, nsplit, (const double*)part, out);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
+  err = go.copy(s.stream, false);
+  if (err) return err;
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  note_elapsed(c, s);
+  return NDLQR_OK;
+}
+
+// nu = rho y of the latest constrained adjoint [batch][N][p] (0 outside the active set), into host memory or this device's
+int ndlqr_hip_download_constraint_adjoint_multipliers(NdlqrHipCtx* c, double* nu) {
+  if (!c || !nu) return NDLQR_ERR_INVALID;
+  if (const int aerr = need_constrained_adjoint(c, "ndlqr_hip_download_constraint_adjoint_multipliers")) return aerr;
+  const ndlqr::Dims& u = c->du;
+  const LinAdjointState& a = c->alin;
+  HIP_TRY(hipSetDevice(c->device));
+  const int per = u.N * c->lin.p;
+  CallerArrays<1> out = {{nu}, {(size_t)u.batch * per}};
+  int err = out.classify(c, "ndlqr_hip_download_constraint_adjoint_multipliers", "the output lies");
+  if (err) return err;
+  HIP_TRY(c->grad_stage.grow(out.stage));
+  HIP_TRY(sync_all(c));
+  const BufferSet& s = c->set[0];
+  out.place(c);
+  hipLaunchKernelGGL(ndlqr::lin_adjoint_multipliers, dim3((per + 255) / 256, u.batch), dim3(256), 0, s.stream, per,
+                     c->lin.rho_value, (const unsigned char*)a.code, (const double*)a.y, out.dev[0]);
+  HIP_TRY(hipGetLastError());
+  err = out.copy(s.stream, false);
+  if (err) return err;
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
+}
+
+// resid [batch][4] of every problem's last adjoint update (a row of zeros for a problem that was not iterated)
+int ndlqr_hip_download_constraint_adjoint_residuals(NdlqrHipCtx* c, double* resid) {
+  if (!c || !resid) return NDLQR_ERR_INVALID;
+  if (const int aerr = need_constrained_adjoint(c, "ndlqr_hip_download_constraint_adjoint_residuals")) return aerr;
+  HIP_TRY(hipSetDevice(c->device));
+  if (where(resid, c->device) == Where::OtherDevice)
+    return refuse("ndlqr_hip_download_constraint_adjoint_residuals: the output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  HIP_TRY(hipMemcpy(resid, c->alin.resid, sizeof(double) * 4 * (size_t)c->du.batch, hipMemcpyDefault));
+  return NDLQR_OK;
+}
+
+// the row codes [batch][N][p] bytes of the latest constrained adjoint (0 unbounded, 1 free, 2 fixed at the lower bound,
+// 3 at the upper), into host memory or this device's; v: the adjoint's own projected iterate (read-out for the tests,
+// HOST memory, may be null)
+int ndlqr_hip_download_constraint_codes(NdlqrHipCtx* c, unsigned char* codes, double* v) {
+  if (!c || (!codes && !v)) return NDLQR_ERR_INVALID;
+  if (const int aerr = need_constrained_adjoint(c, "ndlqr_hip_download_constraint_codes")) return aerr;
+  HIP_TRY(hipSetDevice(c->device));
+  if (codes && where(codes, c->device) == Where::OtherDevice)
+    return refuse("ndlqr_hip_download_constraint_codes: the output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  const size_t np = (size_t)c->du.batch * c->du.N * c->lin.p;
+  if (codes) HIP_TRY(hipMemcpy(codes, c->alin.code, np, hipMemcpyDefault));
+  if (v) HIP_TRY(hipMemcpy(v, c->alin.v, sizeof(double) * np, hipMemcpyDeviceToHost));
   return NDLQR_OK;
 }

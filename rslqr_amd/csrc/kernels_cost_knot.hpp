@@ -1,7 +1,7 @@
 // kernels_cost_knot.hpp -- the per-knot pieces of the dense-cost reduction that more than one
 // kernel header uses: the record layout, the triangular solves of one wavefront in LDS, and the bodies of S and S' on
-// one knot's staged record. kernels_cost.hpp (cost_apply, cost_apply_t) and kernels_lin.hpp (lin_update, lin_finish) call
-// them; no __global__ kernel lives here.
+// one knot's staged record. kernels_cost.hpp (cost_apply, cost_apply_t), kernels_lin.hpp (lin_update, lin_finish) and
+// kernels_lin_grad.hpp (lin_adjoint_start) call them; no __global__ kernel lives here.
 #pragma once
 #include "kernels_common.hpp"
 

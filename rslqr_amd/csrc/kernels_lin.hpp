@@ -239,10 +239,91 @@ static __global__ __launch_bounds__(256) void lin_start(Dims u, Dims d, int p, i
   }
 }
 
+// What an update knows of the rows of problem b: row r of knot k -> is it in the splitting (bounded), and the
+// clip of its step. The forward's rows: the bounds as they lie; the clip is always on.
+struct LinBoundRows {
+  const double *lo, *hi;
+  size_t ob;  // the problem's offset in the bounds
+  __device__ __forceinline__ LinBoundRows(const double* lo_, const double* hi_, size_t bstride, int b)
+      : lo(lo_), hi(hi_), ob((size_t)b * bstride) {}
+  __device__ __forceinline__ bool operator()(int k, int p, int r, bool& clip, double& l, double& h) const {
+    const size_t o = ob + (size_t)k * p;
+    l = lo[o + r];
+    h = hi[o + r];
+    clip = true;
+    return box_bounded(l, h);
+  }
+};
+
+// One knot of an ADMM update, by one wavefront: the body lin_update and lin_adjoint_update (kernels_lin_grad.hpp) share.
+// Stages the knot's shifted record and C, D, applies S^ to the knot's z~, forms w = C x + D u a row per lane, steps the
+// rows `rows` puts in the splitting (box_step), stores v+, y+, and writes the knot's next right-hand side with the maxima
+// on the same pass (lin_next_rhs). oz: the problem's offset in z, res and rhs_next; vb, yb: the problem's v and y.
+template <bool STRICT, class Rows>
+__device__ __forceinline__ void lin_update_knot(const LinKnotLds& S, const Dims& u, const Dims& d, const int p, const int k,
+                                                const int b, const BoxParams& P, const double rho,
+                                                const double* __restrict__ z, const double* __restrict__ rec,
+                                                const double* __restrict__ C, const double* __restrict__ D, const Rows& rows,
+                                                double* __restrict__ vb, double* __restrict__ yb,
+                                                const double* __restrict__ res, double* __restrict__ rhs_next, const size_t oz,
+                                                BoxMaxima& M, const int lane) {
+  const int n = u.n, m = u.m;
+  const size_t recd = cost_record_doubles(n, m);
+  const bool last = k == u.N - 1;
+  const size_t kb = (size_t)b * u.N + k, ok = oz + (size_t)k * d.rows;
+  lin_stage_knot(S, u, p, last, rec + kb * recd, C + kb * p * n, D + kb * p * m, lane);
+  for (int i = lane; i < n; i += 64) S.sx[i] = z[ok + d.n + i];
+  if (!last)
+    for (int j = lane; j < m; j += 64) S.su[j] = z[ok + 2 * d.n + j];
+  wave_lds_sync();
+  // x -> S.sx, u -> S.ux
+  cost_knot_S<false>(n, m, last, S.sL, S.sLR, S.sG, nullptr, S.sx, S.su, nullptr, S.sx, S.ux, lane);
+  wave_lds_sync();
+  for (int r = lane; r < p; r += 64) {
+    double w = 0.0;
+    for (int j = 0; j < n; ++j) w = fma(S.sC[r + p * j], S.sx[j], w);
+    if (!last)
+      for (int j = 0; j < m; ++j) w = fma(S.sD[r + p * j], S.ux[j], w);
+    bool clip;
+    double l, h;
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+    if (rows(k, p, r, clip, l, h)) {
+      const size_t e = (size_t)k * p + r;
+      const double v0 = vb[e], y0 = yb[e];
+      const BoxStep s = box_step<STRICT>(P, w, v0, y0, clip, l, h);
+      vb[e] = s.vn;
+      yb[e] = s.yn;
+      M.rp = max_nan(M.rp, fabs(w - s.vn));
+      M.zm = max_nan(M.zm, fabs(w));
+      M.vm = max_nan(M.vm, fabs(s.vn));
+      t0 = lin_row_weight(rho, s.vn, s.yn);
+      t1 = s.vn - v0;
+      t2 = s.yn;
+    }
+    S.t0[r] = t0;
+    S.t1[r] = t1;
+    S.t2[r] = t2;
+  }
+  lin_next_rhs(S, u, d, p, last, res + ok, rhs_next + ok, nullptr, &M, lane);
+}
+
+// a frozen problem's next right-hand side is its current one (the x and u rows of the knots k < u.N)
+__device__ __forceinline__ void lin_tail_frozen(const Dims& u, const Dims& d, const size_t oz,
+                                                const double* __restrict__ rhs_cur, double* __restrict__ rhs_next,
+                                                const int tid) {
+  const int n = u.n, m = u.m;
+  for (unsigned e = tid; e < (unsigned)(u.N * (n + m)); e += blockDim.x) {
+    const unsigned k = e / (unsigned)(n + m), j = e - k * (unsigned)(n + m);
+    if ((int)k == u.N - 1 && (int)j >= n) continue;
+    const size_t o = oz + (size_t)k * d.rows + ((int)j < n ? d.n + j : 2 * d.n + (j - n));
+    rhs_next[o] = rhs_cur[o];
+  }
+}
+
 // One ADMM update of every running problem (status[b] == 0) after re-solve `it`; see the head of this file. z: the
 // re-solve's solution z~ [batch][N][2n+m] (device layout) with the right-hand side rhs_cur; rec, C, D, v, y in the
-// caller's block sizes. The four wavefronts take the knots k < u.N round-robin; then the maxima are reduced and thread 0
-// judges (box_judge). A frozen problem's next right-hand side is its current one.
+// caller's block sizes. The four wavefronts take the knots k < u.N round-robin (lin_update_knot); then the maxima are
+// reduced and thread 0 judges (box_judge). A frozen problem's next right-hand side is its current one.
 //   grid (batch), block 256, dynamic LDS 4 lin_wave_lds(n, m, p) doubles.
 template <bool STRICT>
 __global__ __launch_bounds__(256) void lin_update(Dims u, Dims d, int p, int it, BoxParams P, const double* __restrict__ z,
@@ -259,70 +340,26 @@ __global__ __launch_bounds__(256) void lin_update(Dims u, Dims d, int p, int it,
   __shared__ int conv_s;
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   if (status[b] != 0) return;  // frozen (uniform over the workgroup)
-  const int n = u.n, m = u.m;
   const size_t oz = (size_t)b * d.N * d.rows;
   double* vb = v + (size_t)b * u.N * p;
   double* yb = y + (size_t)b * u.N * p;
-  const LinKnotLds S(lin_lds + (size_t)wave * lin_wave_lds(n, m, p), n, m, p);
-  const size_t recd = cost_record_doubles(n, m);
+  const LinKnotLds S(lin_lds + (size_t)wave * lin_wave_lds(u.n, u.m, p), u.n, u.m, p);
+  const LinBoundRows rows(lo, hi, bstride, b);
   BoxMaxima M;
-  for (int k = wave; k < u.N; k += 4) {
-    const bool last = k == u.N - 1;
-    const size_t kb = (size_t)b * u.N + k, ok = oz + (size_t)k * d.rows;
-    lin_stage_knot(S, u, p, last, rec + kb * recd, C + kb * p * n, D + kb * p * m, lane);
-    for (int i = lane; i < n; i += 64) S.sx[i] = z[ok + d.n + i];
-    if (!last)
-      for (int j = lane; j < m; j += 64) S.su[j] = z[ok + 2 * d.n + j];
-    wave_lds_sync();
-    // x -> S.sx, u -> S.ux
-    cost_knot_S<false>(n, m, last, S.sL, S.sLR, S.sG, nullptr, S.sx, S.su, nullptr, S.sx, S.ux, lane);
-    wave_lds_sync();
-    const size_t ob = (size_t)b * bstride + (size_t)k * p;
-    for (int r = lane; r < p; r += 64) {
-      double w = 0.0;
-      for (int j = 0; j < n; ++j) w = fma(S.sC[r + p * j], S.sx[j], w);
-      if (!last)
-        for (int j = 0; j < m; ++j) w = fma(S.sD[r + p * j], S.ux[j], w);
-      const double l = lo[ob + r], h = hi[ob + r];
-      double t0 = 0.0, t1 = 0.0, t2 = 0.0;
-      if (box_bounded(l, h)) {
-        const size_t e = (size_t)k * p + r;
-        const double v0 = vb[e], y0 = yb[e];
-        const BoxStep s = box_step<STRICT>(P, w, v0, y0, true, l, h);
-        vb[e] = s.vn;
-        yb[e] = s.yn;
-        M.rp = max_nan(M.rp, fabs(w - s.vn));
-        M.zm = max_nan(M.zm, fabs(w));
-        M.vm = max_nan(M.vm, fabs(s.vn));
-        t0 = lin_row_weight(rho, s.vn, s.yn);
-        t1 = s.vn - v0;
-        t2 = s.yn;
-      }
-      S.t0[r] = t0;
-      S.t1[r] = t1;
-      S.t2[r] = t2;
-    }
-    lin_next_rhs(S, u, d, p, last, res + ok, rhs_next + ok, nullptr, &M, lane);
-  }
+  for (int k = wave; k < u.N; k += 4)
+    lin_update_knot<STRICT>(S, u, d, p, k, b, P, rho, z, rec, C, D, rows, vb, yb, res, rhs_next, oz, M, lane);
   M.reduce(red, tid);
   if (tid == 0) conv_s = box_judge(P, rho, red, b, it, status, iters, resid, running).frozen ? 1 : 0;
   __syncthreads();
-  if (conv_s == 1)
-    for (unsigned e = tid; e < (unsigned)(u.N * (n + m)); e += blockDim.x) {
-      const unsigned k = e / (unsigned)(n + m), j = e - k * (unsigned)(n + m);
-      if ((int)k == u.N - 1 && (int)j >= n) continue;
-      const size_t o = oz + (size_t)k * d.rows + ((int)j < n ? d.n + j : 2 * d.n + (j - n));
-      rhs_next[o] = rhs_cur[o];
-    }
+  if (conv_s == 1) lin_tail_frozen(u, d, oz, rhs_cur, rhs_next, tid);
 }
 
-// End of a solve: the resident solution blocks zs get S^ z~ of the last re-solve -- lambda, x, u in the caller's variables
-// under the shifted records -- and the pad entries and the knots k >= u.N as the re-solve left them.
-//   grid (d.N, batch), block 64, dynamic LDS lin_wave_lds(n, m, p) doubles.
-static __global__ __launch_bounds__(64) void lin_finish(Dims u, Dims d, int p, const double* __restrict__ rec,
-                                                        const double* __restrict__ z, double* __restrict__ zs) {
-  extern __shared__ __attribute__((aligned(16))) double lin_lds[];
-  const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+// Knot k of problem b of a delivery, by one wavefront: zs gets S^ z~ -- lambda, x, u in the caller's variables under the
+// shifted records -- and the pad entries and the knots k >= u.N as z~ holds them. The body of lin_finish and
+// lin_adjoint_finish (kernels_lin_grad.hpp). lds: lin_wave_lds(n, m, p) doubles.
+__device__ __forceinline__ void lin_deliver_knot(double* lds, const Dims& u, const Dims& d, const int p, const int k,
+                                                 const int b, const double* __restrict__ rec, const double* __restrict__ z,
+                                                 double* __restrict__ zs, const int lane) {
   const int n = u.n, m = u.m;
   const size_t ok = ((size_t)b * d.N + k) * d.rows;
   const bool real = k < u.N, last = k == u.N - 1;
@@ -332,13 +369,21 @@ static __global__ __launch_bounds__(64) void lin_finish(Dims u, Dims d, int p, c
     if (!mapped) zs[ok + r] = z[ok + r];
   }
   if (!real) return;
-  const LinKnotLds S(lin_lds, n, m, p);
+  const LinKnotLds S(lds, n, m, p);
   cost_stage_record(rec + ((size_t)b * u.N + k) * cost_record_doubles(n, m), n, m, !last, S.sL, S.sLR, S.sG, lane);
   for (int i = lane; i < n; i += 64) { S.sl[i] = z[ok + i]; S.sx[i] = z[ok + d.n + i]; }
   if (!last)
     for (int j = lane; j < m; j += 64) S.su[j] = z[ok + 2 * d.n + j];
   wave_lds_sync();
   cost_knot_S<true>(n, m, last, S.sL, S.sLR, S.sG, S.sl, S.sx, S.su, zs + ok, zs + ok + d.n, zs + ok + 2 * d.n, lane);
+}
+
+// End of a solve: the resident solution blocks zs get S^ z~ of the last re-solve (lin_deliver_knot).
+//   grid (d.N, batch), block 64, dynamic LDS lin_wave_lds(n, m, p) doubles.
+static __global__ __launch_bounds__(64) void lin_finish(Dims u, Dims d, int p, const double* __restrict__ rec,
+                                                        const double* __restrict__ z, double* __restrict__ zs) {
+  extern __shared__ __attribute__((aligned(16))) double lin_lds[];
+  lin_deliver_knot(lin_lds, u, d, p, blockIdx.x, blockIdx.y, rec, z, zs, threadIdx.x);
 }
 
 // mu = rho y, elementwise over [batch][N][p].

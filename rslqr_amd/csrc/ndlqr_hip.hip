@@ -1729,7 +1729,9 @@ int download_packed(NdlqrHipCtx* c, const double* zsrc, int p0, int count, doubl
   hipStream_t st = s.stream;
   HIP_TRY(launch_pack(c->du, d, KnotSlice(), zsrc + p0 * pitch, s.xfer, st, count));
   // the reduced variables -> the caller's, in the staging (a constrained solve's solution is in the caller's already)
-  if (c->cost.dense && !(zsrc == c->set[c->latest].z && c->cost.mapped(c->soln_gen))) HIP_TRY(cost_map_back(c, s.xfer, p0, count, st));
+  // (... and so is w of a constrained adjoint)
+  const bool in_callers = (zsrc == c->set[c->latest].z && c->cost.mapped(c->soln_gen)) || (zsrc == c->adj.z && c->lin_adjoint_resident());
+  if (c->cost.dense && !in_callers) HIP_TRY(cost_map_back(c, s.xfer, p0, count, st));
   const size_t total = nvars * count;
   if (where(soln, c->device) == Where::Pinned) {
     HIP_TRY(hipMemcpyAsync(soln, s.xfer, sizeof(double) * total, hipMemcpyDeviceToHost, st));
