@@ -435,11 +435,23 @@ int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs); /* 1: dense-cost mode, 0
  *   kernel. iters / status [batch] (may be NULL): status 1 converged, 2 max_iter reached, 3 not finite. The solution that
  *   ndlqr_CopyBatchSolution(s) delivers afterwards is [lambda, x, u] of the last re-solve: the dynamics hold exactly, the
  *   rows hold to within r_prim. A plain solve afterwards gives what it gave before, bit for bit.
+ *   ndlqr_BatchSetConstraintPenaltyAdaptation: every > 0 gives the constrained solves that follow
+ *   the per-problem adaptive penalty of the box solve (section 3.11): at the iterations it % every == 0, it < max_iter,
+ *   every running problem may move its penalty by a power of two within [rho_min, rho_max] (0: the library's 1e-6 and
+ *   1e6) from its own residuals, keeping mu = rho y; the whole batch is then shifted, reduced and factored again, at most
+ *   once per such iteration. every = 0, the initial state: off. Negative values or rho_min > rho_max return
+ *   NDLQR_ERR_INVALID and the previous setting stays. The setting belongs to the solver: allowed in any mode, kept
+ *   across initialisers. With it on, s->rho is the start of a cold solve; a solve with warm_start on a remembered
+ *   factorisation starts from the penalties the previous one ended with, factors nothing and ignores s->rho. A solve
+ *   with adaptation off reuses a remembered factorisation only while all its penalties are s->rho.
+ *   ndlqr_CopyBatchConstraintPenalties: rho [batch] of the latest constrained solve (host or this device's memory);
+ *   refused by name before a constrained solve.
  *   ndlqr_CopyBatchConstraintMultipliers: mu = rho y, [batch][N][p] (mu > 0 at an upper, < 0 at a lower bound).
  *   ndlqr_CopyBatchConstraintResiduals: [batch][4] = r_prim | r_dual | sp | sd of every problem's last update, with the
  *   meaning of ndlqr_CopyBatchBoxResiduals: r_prim = max |w - v|, r_dual = rho max |[C D]'(v - v_prev)|,
  *   sp = max(max |w|, max |v|), sd = rho max |[C D]' y|.
- * REFUSED by name (NDLQR_ERR_INVALID, ndlqr_hip_last_error()): s->adapt_every > 0 (adaptive penalty); everything of the box
+ * REFUSED by name (NDLQR_ERR_INVALID, ndlqr_hip_last_error()): s->adapt_every > 0 (that field, with rho_min and rho_max, is
+ * the box solve's: ndlqr_BatchSetConstraintPenaltyAdaptation is this solve's switch); everything of the box
  * solve -- acceleration, infeasibility detection, polish, box adjoint and bound gradients -- as in dense-cost mode;
  * ndlqr_BatchStepAsync. ndlqr_SolveBatchAdjoint refuses after a constrained solve: its adjoint is
  * ndlqr_SolveBatchLinAdjoint (below). */
@@ -673,6 +685,8 @@ int ndlqr_CopyBatchBoxResiduals(NdLqrBatchSolver* bs, double* resid);
 int ndlqr_CopyBatchBoxAdjointResiduals(NdLqrBatchSolver* bs, double* resid);
 /* the constrained solve of ndlqr_InitializeBatchFlatConstrained (above) and its read-outs */
 int ndlqr_SolveBatchLinConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status);
+int ndlqr_BatchSetConstraintPenaltyAdaptation(NdLqrBatchSolver* bs, int every, double rho_min, double rho_max);
+int ndlqr_CopyBatchConstraintPenalties(NdLqrBatchSolver* bs, double* rho);
 int ndlqr_CopyBatchConstraintMultipliers(NdLqrBatchSolver* bs, double* mu);
 int ndlqr_CopyBatchConstraintResiduals(NdLqrBatchSolver* bs, double* resid);
 /* additive: primal infeasibility detection in the box-constrained solve. State bounds make

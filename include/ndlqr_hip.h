@@ -111,10 +111,15 @@ int ndlqr_hip_download_cost_reduction(NdlqrHipCtx* ctx, double* L, double* LR, d
  * ndlqr_hip_pack_flat_device and ndlqr_hip_upload_inputs leave it.
  * ndlqr_hip_set_constraint_bounds: new lo, hi; refuses lo > hi or NaN before anything is replaced; a new bounded pattern
  * drops the remembered shifted factorisation.
- * ndlqr_hip_solve_constrained: scaled ADMM with the fixed penalty rho (arguments and statuses of ndlqr_hip_solve_box;
- * adapt_every > 0, the adaptive penalty, is refused); the
+ * ndlqr_hip_solve_constrained: scaled ADMM with the penalty rho (arguments and statuses of ndlqr_hip_solve_box;
+ * adapt_every > 0 is refused: the argument is the box settings', the adaptive penalty of this solve is switched on by
+ * ndlqr_hip_set_constraint_adaptation); the
  * resident solution afterwards is [lambda, x, u] of the last re-solve in the caller's variables.
- * ndlqr_hip_download_constraint_multipliers: mu = rho y [batch][N][p]; ndlqr_hip_download_constraint_residuals: [batch][4]
+ * ndlqr_hip_set_constraint_adaptation: every > 0 lets the solves that follow move every running
+ * problem's penalty at the iterations it % every == 0, it < max_iter, within [rho_min, rho_max] (0 < rho_min <= rho_max);
+ * every = 0: off. Any mode; no initialiser resets it. ndlqr_hip_download_constraint_penalties: rho [batch] of the latest
+ * constrained solve.
+ * ndlqr_hip_download_constraint_multipliers: mu = rho[b] y [batch][N][p]; ndlqr_hip_download_constraint_residuals: [batch][4]
  * as ndlqr_hip_download_box_residuals. ndlqr_hip_download_constraint_reduction (read-out for the tests, HOST memory, any
  * pointer may be NULL): the shifted costs Qs [batch][N][n*n], Hs [batch][N][n*m], Rs [batch][N][m*m], the shifted records and
  * reduced problem as ndlqr_hip_download_cost_reduction gives the plain ones, and the iterates v, y [batch][N][p].
@@ -126,6 +131,8 @@ int ndlqr_hip_is_constrained(const NdlqrHipCtx* ctx);
 int ndlqr_hip_set_constraint_bounds(NdlqrHipCtx* ctx, const double* lo, const double* hi, int shared);
 int ndlqr_hip_solve_constrained(NdlqrHipCtx* ctx, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
                                 int check_every, int warm_start, int adapt_every, int* iters, int* status);
+int ndlqr_hip_set_constraint_adaptation(NdlqrHipCtx* ctx, int every, double rho_min, double rho_max);
+int ndlqr_hip_download_constraint_penalties(NdlqrHipCtx* ctx, double* rho);
 int ndlqr_hip_download_constraint_multipliers(NdlqrHipCtx* ctx, double* mu);
 int ndlqr_hip_download_constraint_residuals(NdlqrHipCtx* ctx, double* resid);
 int ndlqr_hip_download_constraint_reduction(NdlqrHipCtx* ctx, double* Qs, double* Hs, double* Rs, double* L, double* LR,
@@ -134,7 +141,7 @@ int ndlqr_hip_download_constraint_reduction(NdlqrHipCtx* ctx, double* Qs, double
 /* Gradients through the solve with linear inequality constraints (ndlqr.h: ndlqr_SolveBatchLinAdjoint,
  * ndlqr_BatchConstraintGradients). ndlqr_hip_solve_constrained_adjoint: the adjoint of the
  * active-set system for g = dL/dz* [batch][nvars] by the forward's ADMM on its remembered shifted reduction and
- * factorisation (its rho, a cold start, nothing factored); refuses unless the resident solution is that of the latest
+ * factorisation (its penalties rho [batch] as it ended with them, a cold start, nothing factored, nothing adapted); refuses unless the resident solution is that of the latest
  * ndlqr_hip_solve_constrained with its right-hand side and bounds. Afterwards ndlqr_hip_download_adjoint returns w.
  * ndlqr_hip_constraint_gradients: dL/dC [P][N][p*n], dL/dD [P][N][p*m] (column-major per knot), dL/dlo, dL/dhi [P][N][p]
  * with P = batch, or 1 when `summed` (deterministic batch sums); each may be NULL.

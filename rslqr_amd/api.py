@@ -251,6 +251,8 @@ def lib():
     proto("ndlqr_BatchIsConstrained", ci, vp)
     proto("ndlqr_BatchSetConstraintBounds", ci, vp, dp, dp, C.c_uint)
     proto("ndlqr_SolveBatchLinConstrained", ci, vp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_BatchSetConstraintPenaltyAdaptation", ci, vp, ci, C.c_double, C.c_double)
+    proto("ndlqr_CopyBatchConstraintPenalties", ci, vp, dp)
     proto("ndlqr_CopyBatchConstraintMultipliers", ci, vp, dp)
     proto("ndlqr_CopyBatchConstraintResiduals", ci, vp, dp)
     proto("ndlqr_hip_download_constraint_reduction", ci, vp, *([dp] * 14))
@@ -585,7 +587,7 @@ class BatchSolver:
     def solve_constrained(self, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0, warm_start=False,
                           adapt_every=0):
         """ndlqr_SolveBatchLinConstrained (0 = the library's default of the box solve for every setting; adapt_every > 0 is
-        refused). Returns (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached, 3 = not
+        refused: the adaptive penalty of this solve is switched on by set_constraint_adaptation). Returns (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached, 3 = not
         finite. solutions() afterwards gives [lambda, x, u] of the last re-solve. Raises on a nonzero return."""
         st = NdLqrBoxSettingsFull(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0,
                                   int(adapt_every), 0.0, 0.0)
@@ -596,6 +598,26 @@ class BatchSolver:
         if err:
             raise RuntimeError("ndlqr_SolveBatchLinConstrained failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return iters, status
+
+    def set_constraint_adaptation(self, every=0, rho_min=0.0, rho_max=0.0):
+        """ndlqr_BatchSetConstraintPenaltyAdaptation: every > 0 gives the solve_constrained() calls that follow the
+        per-problem adaptive penalty, considered every that many iterations within [rho_min, rho_max] (0: the library's
+        1e-6 and 1e6); every = 0 (the initial state): off. Raises on a refusal (a negative argument, rho_min > rho_max);
+        the previous setting then stays."""
+        err = self.L.ndlqr_BatchSetConstraintPenaltyAdaptation(self.h, int(every), float(rho_min), float(rho_max))
+        if err:
+            raise RuntimeError("ndlqr_BatchSetConstraintPenaltyAdaptation failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+
+    def constraint_penalties(self, rho=None):
+        """ndlqr_CopyBatchConstraintPenalties: rho [batch] of the last solve_constrained (what an adaptive solve ended
+        with); `rho`: destination (numpy array or DeviceArray)."""
+        if rho is None:
+            rho = np.zeros(self.batch)
+        err = self.L.ndlqr_CopyBatchConstraintPenalties(self.h, _any_ptr(rho, self.batch))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchConstraintPenalties failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return rho
 
     def constraint_multipliers(self):
         """ndlqr_CopyBatchConstraintMultipliers: mu = rho y, [batch, N, p]."""

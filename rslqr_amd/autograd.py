@@ -528,8 +528,9 @@ def _lin_solve(bs, flat, settings, token, key):
     """Initialise + constrained solve (cold) of `flat` on the cached solver; it then holds `token`."""
     torch.cuda.current_stream(flat[0].device).synchronize()  # (the library reads torch memory on its own stream)
     _lin_cache[key][1] = None
-    rho, alpha, eps_abs, eps_rel, max_iter, check_every = settings
+    rho, alpha, eps_abs, eps_rel, max_iter, check_every, adapt_every = settings
     try:
+        bs.set_constraint_adaptation(adapt_every)
         bs.initialize_flat_constrained(*[_View(t) for t in flat])
         _, status = bs.solve_constrained(rho=rho, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
                                          check_every=check_every)
@@ -580,7 +581,7 @@ class LqrSolveConstrained(torch.autograd.Function):
             _lin_solve(bs, ctx.flat, ctx.settings, ctx.token, ctx.key)
         gz = gz.detach().to(torch.float64).contiguous()
         torch.cuda.current_stream(gz.device).synchronize()
-        _, alpha, eps_abs, eps_rel, max_iter, check_every = ctx.settings
+        _, alpha, eps_abs, eps_rel, max_iter, check_every, _ = ctx.settings
         try:
             _, status = bs.solve_constrained_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
                                                      check_every=check_every)
@@ -613,15 +614,16 @@ class LqrSolveConstrained(torch.autograd.Function):
 
 
 def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0,
-                          max_iter=0, check_every=0):
+                          max_iter=0, check_every=0, adapt_every=0):
     """z* [b, nvars] of the dense-cost LQR problems of lqr_solve_dense subject to, per knot, p rows
         lo_k <= C_k x_k + D_k u_k <= hi_k,     C [b, N, p, n]   D [b, N, p, m]   lo, hi [b, N, p]
     (entries of lo, hi may be +-inf; D of the last knot is not part of the problem), by the solve with linear inequality
-    constraints (ndlqr_SolveBatchLinConstrained, cold start; 0 = the library's default for every setting), differentiable
-    in all thirteen tensors. Any argument may leave out the batch dimension (shared: its gradient is the batch sum -- for
+    constraints (ndlqr_SolveBatchLinConstrained, cold start; 0 = the library's default for every setting; adapt_every > 0:
+    the per-problem adaptive penalty of ndlqr_BatchSetConstraintPenaltyAdaptation, considered every that many iterations,
+    0: off), differentiable in all thirteen tensors. Any argument may leave out the batch dimension (shared: its gradient is the batch sum -- for
     C, D, lo, hi computed on the device when all of them that need a gradient are shared). The backward is the adjoint
     of the active-set system (ndlqr_SolveBatchLinAdjoint) with the same alpha, tolerances, max_iter and check_every on the
-    forward's factorisation. Raises RuntimeError when a problem's forward or adjoint iteration does not converge (status
+    forward's factorisation and final penalties. Raises RuntimeError when a problem's forward or adjoint iteration does not converge (status
     != 1). The gradients hold where the active set is locally stable (strict complementarity, independent active rows);
     dL/dC and dL/dD are exactly zero on the rows that are not active."""
     args = (A, B, Q, H, R, q, r, d, x0, C, D, lo, hi)
@@ -665,5 +667,5 @@ def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, 
     # (a shared problem argument is expanded here, outside the Function: autograd sums its gradient over the batch; the row
     #  arguments go in as they are, so that the library can sum theirs)
     full = [t if not shared[name] else t.unsqueeze(0).expand(b, *t.shape) for name, t in zip(_DENSE_ARGS, args[:9])]
-    settings = (float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(check_every))
+    settings = (float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(check_every), int(adapt_every))
     return LqrSolveConstrained.apply(settings, tuple(shared[k] for k in _ROW_ARGS), *full, C, D, lo, hi)

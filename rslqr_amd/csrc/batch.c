@@ -211,6 +211,19 @@ int ndlqr_SolveBatchLinConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings*
                                      z.max_iter > 0 ? z.max_iter : 4000, z.check_every > 0 ? z.check_every : 10,
                                      z.warm_start != 0, z.adapt_every, iters, status);
 }
+int ndlqr_BatchSetConstraintPenaltyAdaptation(NdLqrBatchSolver* bs, int every, double rho_min, double rho_max) {
+  /* (x < HUGE_VAL is false for a NaN as well) */
+  if (!bs || every < 0 || !(rho_min >= 0.0 && rho_min < HUGE_VAL) || !(rho_max >= 0.0 && rho_max < HUGE_VAL))
+    return NDLQR_ERR_INVALID;
+  rho_min = rho_min > 0.0 ? rho_min : 1e-6;
+  rho_max = rho_max > 0.0 ? rho_max : 1e6;
+  if (!(rho_min <= rho_max)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_set_constraint_adaptation(bs->ctx, every, rho_min, rho_max);
+}
+int ndlqr_CopyBatchConstraintPenalties(NdLqrBatchSolver* bs, double* rho) {
+  if (!bs || !rho) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_penalties(bs->ctx, rho);
+}
 int ndlqr_CopyBatchConstraintMultipliers(NdLqrBatchSolver* bs, double* mu) {
   if (!bs || !mu) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_constraint_multipliers(bs->ctx, mu);

@@ -413,20 +413,25 @@ struct CostState {
 // [batch][N][p n], D [batch][N][p m]; lo, hi, mask [P][N][p] (bstride 0: shared). The shifted problem: costs Qs, Hs, Rs,
 // records rec, and the reduced flat arrays At .. x0t (CostState keeps the plain ones). Iteration state: v, y [batch][N][p],
 // the re-solve's z~ and two right-hand sides in the device layout, per problem status, iters, resid [4]; word: the
-// running count | lo > hi | pattern changed. The shifted reduction and factorisation are remembered (fact) with rho_value,
-// the flags and what the factorisation left (kept). soln_gen: the solution generation the latest constrained solve left.
+// running count | lo > hi | pattern changed (within a solve word[1] counts the problems whose penalty moved at an adapt
+// iteration, moved [batch] marks them: section 3.19). The shifted reduction and factorisation are remembered (fact) with
+// the penalties rho [batch] -- rho_value when rho_uniform says they are all that one value --, the flags and what the
+// factorisation left (kept). soln_gen: the solution generation the latest constrained solve left. adapt_every, rho_min,
+// rho_max: the setting of ndlqr_hip_set_constraint_adaptation, the solver's and not the problem's: no initialiser resets it.
 struct LinState {
   bool active = false, has_H = false, shared = false, have_vy = false, rhs_new = true, fact = false;
+  bool rho_uniform = false;
   int p = 0;
+  int adapt_every = 0;
   size_t bstride = 0;
-  double rho_value = 0.0;
+  double rho_value = 0.0, rho_min = 1e-6, rho_max = 1e6;
   unsigned flags = 0;
   KeptState kept;
   unsigned long long soln_gen = 0;
   size_t lds_asked[5] = {};  // dynamic LDS already asked for lin_shift_cost | lin_start | lin_update<true> | <false> | lin_finish
-  DevBuf<double> A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, Qs, Hs, Rs, rec, At, Bt, qt, rt, dt, x0t, v, y, z, rhs[2], resid;
+  DevBuf<double> A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, Qs, Hs, Rs, rec, At, Bt, qt, rt, dt, x0t, v, y, z, rhs[2], resid, rho;
   DevBuf<unsigned char> mask;
-  DevBuf<int> status, iters, word;
+  DevBuf<int> status, iters, word, moved;
   PinnedBuf<int> h_word;
   // the buffers that depend on p are allocated again when p changes
   hipError_t ensure(const ndlqr::Dims& u, const ndlqr::Dims& dd, int rows_per_knot, hipStream_t st) {
@@ -444,7 +449,8 @@ struct LinState {
                         v.ensure(np), y.ensure(np),
                         z.ensure_zeroed(doubles_z(dd), st),  // (entries a re-solve does not write: the pad rows)
                         rhs[0].ensure(doubles_z(dd)), rhs[1].ensure(doubles_z(dd)), resid.ensure(4 * nb),
-                        status.ensure(nb), iters.ensure(nb), word.ensure(3), h_word.ensure(3)});
+                        rho.ensure(nb), status.ensure(nb), iters.ensure(nb), word.ensure(3), h_word.ensure(3),
+                        moved.ensure_zeroed(nb, st)});
   }
 };
 

@@ -13,6 +13,11 @@
 // problem into buffers of its own (LinState: records, A~, B~, right-hand side), puts it in force (ShiftedReduction),
 // factors it once and iterates: one re-solve into lin.z plus one lin_update per iteration; the host reads the running
 // count every check_every iterations. On the way out the plain reduced problem of CostState is packed again.
+// The penalty is a device vector, lin.rho [batch]. With ndlqr_hip_set_constraint_adaptation(every > 0) (DESIGN.md section
+// 3.19) lin_update may move a problem's penalty at every every-th iteration; the host then reads the count of moved
+// problems with the running count and, when it is not zero, shifts, reduces, packs and factors the whole batch again and
+// lets lin_start rewrite the right-hand sides of the moved problems -- one factorisation serves every problem that moved
+// in that round, and the deterministic kernels give every other problem its old records and factors back.
 
 // (the kernels hold static LDS next to the dynamic: ask well below the default limit. `asked`: what this context has
 //  asked for this kernel already -- one of LinState::lds_asked --, so that a solve does not ask again)
@@ -150,6 +155,10 @@ struct ShiftedReduction {
   int open(unsigned flags) {
     open_ = true;
     c->flags = flags;
+    return repack();
+  }
+  // the shifted reduced problem packed (again: LinState's arrays were written anew for new penalties)
+  int repack() {
     const LinState& k = c->lin;
     return pack(k.At, k.Bt, k.qt, k.rt, k.dt, k.x0t);
   }
@@ -170,8 +179,8 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
       max_iter < 1 || check_every < 1)
     return NDLQR_ERR_INVALID;
   if (adapt_every > 0)
-    return refuse("ndlqr_hip_solve_constrained: the adaptive penalty (adapt_every > 0) is not available for linear inequality "
-                  "constraints");
+    return refuse("ndlqr_hip_solve_constrained: the adaptive penalty (adapt_every > 0) of the settings is the box solve's; "
+                  "ndlqr_hip_set_constraint_adaptation (ndlqr_BatchSetConstraintPenaltyAdaptation) switches it on here");
   if (const int merr = need_constrained(c, "ndlqr_hip_solve_constrained")) return merr;
   const ndlqr::Dims& d = c->d;
   const ndlqr::Dims& u = c->du;
@@ -186,7 +195,14 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
   const hipStream_t st = s.stream;
   const bool strict = (c->flags & NDLQR_FLAG_STRICT_FP) != 0;
   const unsigned lin_flags = c->flags | (strict ? NDLQR_FLAG_KEEP_FACT : NDLQR_FLAG_KEEP_RECORDS);
-  const bool reuse = k.fact && k.flags == lin_flags && k.rho_value == rho;
+  // the remembered factorisation applies to an adaptive warm start whatever its penalties are (the settings' rho is
+  // ignored, as in the box solve); everywhere else only when they are all the settings' rho
+  const int every = k.adapt_every;
+  const bool usable = k.fact && k.flags == lin_flags;
+  const bool keep_rho = usable && every > 0 && warm_start;
+  const bool reuse = keep_rho || (usable && k.rho_uniform && k.rho_value == rho);
+  bool uniform = keep_rho ? k.rho_uniform : true;
+  const double uniform_value = keep_rho ? k.rho_value : rho;
   const int p = k.p;
   const size_t lds = lin_update_lds_bytes(u, p);
   HIP_TRY(hipEventRecord(s.ev_start, st));
@@ -194,17 +210,34 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
   int not_spd = NDLQR_OK;
   ShiftedReduction shifted(c);
   const double* Hk = k.has_H ? k.H.get() : nullptr;
+  const double* rhov = k.rho;
+  // the costs shifted by the penalties as they stand, and their reduction
+  const auto shift_and_reduce = [&]() -> int {
+    const size_t slds = sizeof(double) * ndlqr::lin_shift_lds(u.n, u.m, p);
+    HIP_TRY(allow_lin_lds(ndlqr::lin_shift_cost, slds, k.lds_asked[0]));
+    hipLaunchKernelGGL(ndlqr::lin_shift_cost, dim3(u.N, u.batch), dim3(64), slds, st, u.n, u.m, u.N, p, rhov,
+                       (const double*)k.Q, Hk, (const double*)k.R, (const double*)k.C, (const double*)k.D, (const double*)k.lo,
+                       (const double*)k.hi, k.bstride, k.Qs.get(), k.Hs.get(), k.Rs.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(cost_reduce_problem(c, k.A, k.B, k.Qs, k.Hs, k.Rs, k.rec, k.At, k.Bt, st));
+    return NDLQR_OK;
+  };
+  const auto start = [&](int mode) -> int {
+    hipLaunchKernelGGL(ndlqr::lin_start, dim3(u.batch), dim3(256), lds, st, u, d, p, mode, rhov, (const double*)k.rec,
+                       (const double*)k.C, (const double*)k.D, (const double*)k.lo, (const double*)k.hi, k.bstride,
+                       (const double*)s.rhs, k.v.get(), k.y.get(), k.rhs[0].get(), k.rhs[1].get(), k.moved.get());
+    HIP_TRY(hipGetLastError());
+    return NDLQR_OK;
+  };
+  const char* const what = "the reduction of Q + rho C'MC, H + rho C'MD, R + rho D'MD";
   // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
   const auto iterate = [&]() -> int {
-    // 2. the shifted costs and their reduction, unless the remembered ones apply; S^' of the right-hand side when either is new
+    // 2. the penalties, the shifted costs and their reduction, unless the remembered ones apply; S^' of the right-hand
+    // side when either is new
     if (!reuse) {
-      const size_t slds = sizeof(double) * ndlqr::lin_shift_lds(u.n, u.m, p);
-      HIP_TRY(allow_lin_lds(ndlqr::lin_shift_cost, slds, k.lds_asked[0]));
-      hipLaunchKernelGGL(ndlqr::lin_shift_cost, dim3(u.N, u.batch), dim3(64), slds, st, u.n, u.m, u.N, p, rho,
-                         (const double*)k.Q, Hk, (const double*)k.R, (const double*)k.C, (const double*)k.D, (const double*)k.lo,
-                         (const double*)k.hi, k.bstride, k.Qs.get(), k.Hs.get(), k.Rs.get());
+      hipLaunchKernelGGL(ndlqr::lin_fill_rho, dim3((u.batch + 255) / 256), dim3(256), 0, st, u.batch, rho, k.rho.get());
       HIP_TRY(hipGetLastError());
-      HIP_TRY(cost_reduce_problem(c, k.A, k.B, k.Qs, k.Hs, k.Rs, k.rec, k.At, k.Bt, st));
+      if (const int se = shift_and_reduce()) return se;
     }
     if (!reuse || k.rhs_new) HIP_TRY(cost_reduce_rhs_to(c, k.rec, k.q, k.r, k.d, k.x0, k.qt, k.rt, k.dt, k.x0t, st));
     // 3. the shifted reduced problem in force; factored, unless the remembered factorisation applies
@@ -214,38 +247,51 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
       c->kept = k.kept;
     } else {
       factored = true;
-      e = factor_resident(c, st, &not_spd, "ndlqr_hip_solve_constrained", "the reduction of Q + rho C'MC, H + rho C'MD, R + rho D'MD");
+      e = factor_resident(c, st, &not_spd, "ndlqr_hip_solve_constrained", what);
       if (e) return e;
     }
     // 4. the iterations
-    const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, 0.0, 0.0};
-    const int cold = warm_start && k.have_vy ? 0 : 1;
+    const ndlqr::BoxParams P = {alpha, 1.0 - alpha, eps_abs, eps_rel, k.rho_min, k.rho_max};
     HIP_TRY(allow_lin_lds(ndlqr::lin_start, lds, k.lds_asked[1]));
     if (strict) HIP_TRY(allow_lin_lds(ndlqr::lin_update<true>, lds, k.lds_asked[2]));
     else HIP_TRY(allow_lin_lds(ndlqr::lin_update<false>, lds, k.lds_asked[3]));
-    hipLaunchKernelGGL(ndlqr::lin_start, dim3(u.batch), dim3(256), lds, st, u, d, p, cold, rho,
-                  (const double*)k.rec, (const double*)k.C, (const double*)k.D, (const double*)k.lo, (const double*)k.hi,
-                  k.bstride, (const double*)s.rhs, k.v.get(), k.y.get(), k.rhs[0].get(), k.rhs[1].get());
-    HIP_TRY(hipGetLastError());
+    e = start(warm_start && k.have_vy ? ndlqr::LIN_START_WARM : ndlqr::LIN_START_COLD);
+    if (e) return e;
     k.have_vy = true;
     k.h_word[0] = u.batch;
-    HIP_TRY(hipMemcpyAsync(k.word, k.h_word, sizeof(int), hipMemcpyHostToDevice, st));
+    k.h_word[1] = 0;
+    HIP_TRY(hipMemcpyAsync(k.word, k.h_word, 2 * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(k.status, 0, sizeof(int) * (size_t)u.batch, st));
+    HIP_TRY(hipMemsetAsync(k.moved, 0, sizeof(int) * (size_t)u.batch, st));
     for (int it = 1; it <= max_iter; ++it) {
       const double* rc = k.rhs[(it - 1) & 1];
       double* rn = k.rhs[it & 1];
       e = launch_resolve(c, rc, k.z, "constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
       if (e) return e;
-      launch_strict(strict, ndlqr::lin_update, dim3(u.batch), dim3(256), lds, st, u, d, p, it, P, (const double*)k.z,
+      const int adapt = every > 0 && it % every == 0 && it < max_iter;
+      launch_strict(strict, ndlqr::lin_update, dim3(u.batch), dim3(256), lds, st, u, d, p, it, adapt, P, (const double*)k.z,
                     (const double*)k.rec, (const double*)k.C, (const double*)k.D, (const double*)k.lo, (const double*)k.hi,
-                    k.bstride, k.v.get(), k.y.get(), (const double*)s.rhs, rc, rn, rho, k.status.get(),
-                    k.iters.get(), k.resid.get(), k.word.get());
+                    k.bstride, k.v.get(), k.y.get(), (const double*)s.rhs, rc, rn, k.rho.get(), k.status.get(),
+                    k.iters.get(), k.resid.get(), k.word.get(), k.moved.get());
       HIP_TRY(hipGetLastError());
-      if (it % check_every == 0 || it == max_iter) {
-        // 5. one word: how many problems still run
-        HIP_TRY(hipMemcpyAsync(k.h_word, k.word, sizeof(int), hipMemcpyDeviceToHost, st));
+      if (it % check_every == 0 || it == max_iter || adapt) {
+        // 5. one word: how many problems still run; after an adapting update also how many moved their penalty
+        HIP_TRY(hipMemcpyAsync(k.h_word, k.word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (k.h_word[0] == 0) break;
+        if (adapt && k.h_word[1] != 0) {
+          // 5a. new penalties: the whole batch shifted, reduced, packed and factored as above (a problem that did not move
+          // gets its records, its res~ and its factors back bit for bit), then both right-hand sides of the moved problems
+          uniform = false;
+          factored = true;
+          if (const int se = shift_and_reduce()) return se;
+          HIP_TRY(cost_reduce_rhs_to(c, k.rec, k.q, k.r, k.d, k.x0, k.qt, k.rt, k.dt, k.x0t, st));
+          e = shifted.repack();
+          if (!e) e = factor_resident(c, st, &not_spd, "ndlqr_hip_solve_constrained", what);
+          if (!e) e = start(ndlqr::LIN_START_MOVED);
+          if (e) return e;
+          HIP_TRY(hipMemsetAsync(k.word + 1, 0, sizeof(int), st));
+        }
       }
     }
     // 6. deliver: S^ z~ of the last re-solve, in the caller's variables
@@ -270,7 +316,8 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
     return err;
   }
   k.fact = true;  // (the initialiser inside the scope dropped it)
-  k.rho_value = rho;
+  k.rho_uniform = uniform;
+  k.rho_value = uniform_value;
   k.flags = lin_flags;
   k.kept = shifted_kept;
   k.rhs_new = false;
@@ -284,7 +331,30 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
   return ndlqr_hip_synchronize(c);
 }
 
-// mu = rho y [batch][N][p], into host memory or this device's
+int ndlqr_hip_set_constraint_adaptation(NdlqrHipCtx* c, int every, double rho_min, double rho_max) {
+  if (!c) return NDLQR_ERR_INVALID;
+  if (every < 0 || !(rho_min > 0.0 && rho_min <= rho_max && rho_max < HUGE_VAL))
+    return refuse("ndlqr_hip_set_constraint_adaptation: bad argument (every >= 0, 0 < rho_min <= rho_max, finite)");
+  c->lin.adapt_every = every;
+  c->lin.rho_min = rho_min;
+  c->lin.rho_max = rho_max;
+  return NDLQR_OK;
+}
+
+// rho [batch] of the latest constrained solve, into host memory or this device's
+int ndlqr_hip_download_constraint_penalties(NdlqrHipCtx* c, double* rho) {
+  if (!c || !rho) return NDLQR_ERR_INVALID;
+  if (const int merr = need_constrained(c, "ndlqr_hip_download_constraint_penalties")) return merr;
+  if (!c->lin.have_vy) return refuse("ndlqr_hip_download_constraint_penalties: no constrained solve yet");
+  HIP_TRY(hipSetDevice(c->device));
+  if (where(rho, c->device) == Where::OtherDevice)
+    return refuse("ndlqr_hip_download_constraint_penalties: the output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  HIP_TRY(hipMemcpy(rho, c->lin.rho, sizeof(double) * (size_t)c->du.batch, hipMemcpyDefault));
+  return NDLQR_OK;
+}
+
+// mu = rho[b] y [batch][N][p], into host memory or this device's
 int ndlqr_hip_download_constraint_multipliers(NdlqrHipCtx* c, double* mu) {
   if (!c || !mu) return NDLQR_ERR_INVALID;
   if (const int merr = need_constrained(c, "ndlqr_hip_download_constraint_multipliers")) return merr;
@@ -300,8 +370,8 @@ int ndlqr_hip_download_constraint_multipliers(NdlqrHipCtx* c, double* mu) {
   HIP_TRY(sync_all(c));
   const BufferSet& s = c->set[0];
   out.place(c);
-  hipLaunchKernelGGL(ndlqr::lin_multipliers, dim3((per + 255) / 256, u.batch), dim3(256), 0, s.stream, per, k.rho_value,
-                     (const double*)k.y, out.dev[0]);
+  hipLaunchKernelGGL(ndlqr::lin_multipliers, dim3((per + 255) / 256, u.batch), dim3(256), 0, s.stream, per,
+                     (const double*)k.rho, (const double*)k.y, out.dev[0]);
   HIP_TRY(hipGetLastError());
   err = out.copy(s.stream, false);
   if (err) return err;
@@ -404,7 +474,7 @@ int ndlqr_hip_solve_constrained_adjoint(NdlqrHipCtx* c, const double* g, double 
   c->adj.gen = 0;
   const bool strict = (k.flags & NDLQR_FLAG_STRICT_FP) != 0;
   const int p = k.p;
-  const double rho = k.rho_value;
+  const double* rhov = k.rho;  // (the vector the forward ended with: nothing here moves it)
   const size_t lds = lin_update_lds_bytes(u, p), flds = sizeof(double) * ndlqr::lin_wave_lds(u.n, u.m, p);
   // what the scope's initialiser drops and the forward's epilogue had left
   const KeptState fwd_kept = k.kept;
@@ -445,7 +515,7 @@ int ndlqr_hip_solve_constrained_adjoint(NdlqrHipCtx* c, const double* g, double 
       if (e) return e;
       launch_strict(strict, ndlqr::lin_adjoint_update, dim3(u.batch), dim3(256), lds, st, u, d, p, it, P, (const double*)k.z,
                     (const double*)k.rec, (const double*)k.C, (const double*)k.D, (const unsigned char*)a.code, a.v.get(),
-                    a.y.get(), (const double*)c->adj.rhs, rc, rn, rho, a.status.get(), a.iters.get(), a.resid.get(),
+                    a.y.get(), (const double*)c->adj.rhs, rc, rn, rhov, a.status.get(), a.iters.get(), a.resid.get(),
                     a.word.get());
       HIP_TRY(hipGetLastError());
       if (it % check_every == 0 || it == max_iter) {
@@ -475,7 +545,7 @@ int ndlqr_hip_solve_constrained_adjoint(NdlqrHipCtx* c, const double* g, double 
     (void)hipStreamSynchronize(st);
     return err;
   }
-  k.fact = true;  // (the initialiser inside the scope dropped it; rho_value, flags and kept were never touched)
+  k.fact = true;  // (the initialiser inside the scope dropped it; the penalties, flags and kept were never touched)
   k.kept = fwd_kept;
   k.flags = fwd_flags;
   c->inputs_replaced = fwd_inputs_replaced;
@@ -536,12 +606,12 @@ int ndlqr_hip_constraint_gradients(NdlqrHipCtx* c, int summed, double* gC, doubl
   const double* z = c->set[c->latest].z;
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   if (!summed) {
-    launch_strict(strict, ndlqr::lin_constraint_grads, dim3(u.N, u.batch), dim3(64), 0, s.stream, u, d, p, k.rho_value,
+    launch_strict(strict, ndlqr::lin_constraint_grads, dim3(u.N, u.batch), dim3(64), 0, s.stream, u, d, p, (const double*)k.rho,
                   (const unsigned char*)a.code, (const double*)k.y, (const double*)a.y, (const int*)a.status, z,
                   (const double*)c->adj.z, out);
     HIP_TRY(hipGetLastError());
   } else {
-    launch_strict(strict, ndlqr::lin_constraint_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d, p, k.rho_value, ppb,
+    launch_strict(strict, ndlqr::lin_constraint_grads_sum, dim3(nblk, nsplit), dim3(256), 0, s.stream, u, d, p, (const double*)k.rho, ppb,
                   (const unsigned char*)a.code, (const double*)k.y, (const double*)a.y, (const int*)a.status, z,
                   (const double*)c->adj.z, out, part);
     HIP_TRY(hipGetLastError());
@@ -574,7 +644,7 @@ int ndlqr_hip_download_constraint_adjoint_multipliers(NdlqrHipCtx* c, double* nu
   const BufferSet& s = c->set[0];
   out.place(c);
   hipLaunchKernelGGL(ndlqr::lin_adjoint_multipliers, dim3((per + 255) / 256, u.batch), dim3(256), 0, s.stream, per,
-                     c->lin.rho_value, (const unsigned char*)a.code, (const double*)a.y, out.dev[0]);
+                     (const double*)c->lin.rho, (const unsigned char*)a.code, (const double*)a.y, out.dev[0]);
   HIP_TRY(hipGetLastError());
   err = out.copy(s.stream, false);
   if (err) return err;

@@ -123,28 +123,8 @@ __global__ void box_start(Dims d, const double* __restrict__ rhov, int cold_all,
 }
 
 // ---- The update core shared by box_update, box_update_accel (kernels_box_accel.hpp), box_adjoint_update
-// (kernels_box_grad.hpp) and lin_update (kernels_lin.hpp): kernels_box_core.hpp. What follows here are the tails of the
-// box kernels.
-
-// The adaptive penalty of a problem that goes on, decided by thread 0 from the verdict's four
-// numbers when all of them are finite and > 0:
-//     k = (ilogb(r_prim / sp) - ilogb(r_dual / sd)) / 2 (toward zero) clamped to [-6, 6],
-//     rho+ = ldexp(rho, k) clamped to [rho_min, rho_max].
-// Exact or correctly rounded operations only: numpy reproduces the decision bit for bit. True when rho+ != rho: then
-// *rho_next = rho[b] = rho+ and running[1] counts the problem (the host refactors).
-__device__ __forceinline__ bool box_adapt_penalty(const BoxParams& P, double rho, const BoxVerdict& J, int b, double* rhov,
-                                                  int* running, double* rho_next) {
-  if (!(isfinite(J.sd) && J.r_prim > 0.0 && J.r_dual > 0.0 && J.sp > 0.0 && J.sd > 0.0)) return false;
-  int k = (ilogb(J.r_prim / J.sp) - ilogb(J.r_dual / J.sd)) / 2;
-  k = k < -6 ? -6 : k > 6 ? 6 : k;
-  if (k == 0) return false;
-  const double rn = fmin(fmax(ldexp(rho, k), P.rho_min), P.rho_max);
-  if (rn == rho) return false;
-  *rho_next = rn;
-  rhov[b] = rn;
-  atomicAdd(running + 1, 1);
-  return true;
-}
+// (kernels_box_grad.hpp) and lin_update (kernels_lin.hpp): kernels_box_core.hpp, box_adapt_penalty included. What follows
+// here are the tails of the box kernels.
 
 // Tail of a problem whose penalty moved from rho to rho_new: y <- y (rho / rho_new) on the entries that count (mu = rho y
 // is kept) and the next right-hand side rewritten from rho_new and that y. Reads the v+, y+ this thread stored.

@@ -1,6 +1,7 @@
 // kernels_box_core.hpp -- internal: the ADMM update core of the constrained solves (DESIGN.md sections 3.9, 3.17): the
-// parameters, the step of one constrained entry, the running maxima of a problem and its judgement. No __global__ kernel
-// lives here; kernels_box.hpp and its companions (hip_box.hip) and kernels_lin.hpp (hip_lin.hip) include it.
+// parameters, the step of one constrained entry, the running maxima of a problem, its judgement and the decision of the
+// adaptive penalty (sections 3.11, 3.19). No __global__ kernel lives here; kernels_box.hpp and its companions
+// (hip_box.hip) and kernels_lin.hpp (hip_lin.hip) include it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +12,7 @@ namespace ndlqr {
 struct BoxParams {
   double alpha, oma;  // oma = 1 - alpha
   double eps_abs, eps_rel;
-  double rho_min, rho_max;  // clamp of the adaptive penalty (read only when box_update adapts)
+  double rho_min, rho_max;  // clamp of the adaptive penalty (read only when box_update / lin_update adapts)
 };
 
 __device__ __forceinline__ bool box_bounded(double lo, double hi) { return lo > -HUGE_VAL || hi < HUGE_VAL; }
@@ -130,6 +131,26 @@ __device__ __forceinline__ BoxVerdict box_judge(const BoxParams& P, double rho, 
     atomicSub(running, 1);
   }
   return {r_prim, r_dual, sp, sd, conv || !finite};
+}
+
+// The adaptive penalty of a problem that goes on (DESIGN.md sections 3.11 and 3.19), decided by thread 0 of box_update,
+// box_update_accel or lin_update from the verdict's four numbers when all of them are finite and > 0:
+//     k = (ilogb(r_prim / sp) - ilogb(r_dual / sd)) / 2 (toward zero) clamped to [-6, 6],
+//     rho+ = ldexp(rho, k) clamped to [rho_min, rho_max].
+// Exact or correctly rounded operations only: numpy reproduces the decision bit for bit. True when rho+ != rho: then
+// *rho_next = rho[b] = rho+ and running[1] counts the problem (the host refactors).
+__device__ __forceinline__ bool box_adapt_penalty(const BoxParams& P, double rho, const BoxVerdict& J, int b, double* rhov,
+                                                  int* running, double* rho_next) {
+  if (!(isfinite(J.sd) && J.r_prim > 0.0 && J.r_dual > 0.0 && J.sp > 0.0 && J.sd > 0.0)) return false;
+  int k = (ilogb(J.r_prim / J.sp) - ilogb(J.r_dual / J.sd)) / 2;
+  k = k < -6 ? -6 : k > 6 ? 6 : k;
+  if (k == 0) return false;
+  const double rn = fmin(fmax(ldexp(rho, k), P.rho_min), P.rho_max);
+  if (rn == rho) return false;
+  *rho_next = rn;
+  rhov[b] = rn;
+  atomicAdd(running + 1, 1);
+  return true;
 }
 
 }  // namespace ndlqr

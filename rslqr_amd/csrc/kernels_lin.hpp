@@ -15,6 +15,9 @@
 // right-hand sides is `d` (a zero-padded block size and / or a padded horizon): row i of lambda | x | u of knot k sits at
 // k d.rows + (i | d.n + i | 2 d.n + i). Pad entries and the knots k >= u.N are never written: they keep the resident
 // right-hand side lin_start copied. D of the caller's last knot is never loaded (its rows are w = C x).
+// The penalty is per problem, rho[batch] (a fixed-penalty solve fills it with one value; lin_update may move it by powers
+// of two at an adapt iteration, after which the host shifts, reduces and factors again and lin_start, in its restart
+// mode, rewrites the right-hand sides of the problems that moved: DESIGN.md section 3.19).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,13 +57,21 @@ static __global__ void lin_bounds(int N, int p, const double* __restrict__ lo, c
   }
 }
 
-// Q^ = Q + rho C'MC, H^ = H + rho C'MD, R^ = R + rho D'MD of every knot (the last: Q^ alone; H^ = 0, R^ = 1 are written
+// rho[b] = value for every problem.
+//   grid ceil(batch / 256), block 256.
+static __global__ void lin_fill_rho(int batch, double value, double* __restrict__ rho) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < batch) rho[b] = value;
+}
+
+// Q^ = Q + rho[b] C'MC, H^ = H + rho[b] C'MD, R^ = R + rho[b] D'MD of every knot (the last: Q^ alone; H^ = 0, R^ = 1 are written
 // and nothing of the caller's H, R, D is loaded there). One wavefront per (knot, problem); C, D and the row weights
 // rho M go through LDS, the costs come in and leave as they lie. Q, R are read in their lower triangles (as cost_factor
 // does) and leave symmetric. H may be null (zero).
 //   grid (N, batch), block 64, dynamic LDS lin_shift_lds(n, m, p) doubles.
 static __global__ __launch_bounds__(64) void lin_shift_cost(const int n, const int m, const int N, const int p,
-                                                            const double rho, const double* __restrict__ Q,
+                                                            const double* __restrict__ rhov,
+                                                            const double* __restrict__ Q,
                                                             const double* __restrict__ H, const double* __restrict__ R,
                                                             const double* __restrict__ C, const double* __restrict__ D,
                                                             const double* __restrict__ lo, const double* __restrict__ hi,
@@ -69,6 +80,7 @@ static __global__ __launch_bounds__(64) void lin_shift_cost(const int n, const i
   extern __shared__ __attribute__((aligned(16))) double lin_lds[];
   const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
   const bool last = k == N - 1;
+  const double rho = rhov[b];
   const size_t kb = (size_t)b * N + k;
   double* sC = lin_lds;
   double* sD = sC + (size_t)p * n;
@@ -195,20 +207,28 @@ __device__ __forceinline__ double lin_row_weight(double rho, double v, double y)
   return rho * t;
 }
 
-// Start of a solve: both ADMM right-hand sides from the resident (shifted, reduced) one `res`. cold: v = y = 0 and the
-// right-hand sides are copies of res. Otherwise (warm start) y of the rows the current bounds leave unbounded is zeroed
+enum : int { LIN_START_WARM = 0, LIN_START_COLD = 1, LIN_START_MOVED = 2 };
+
+// Start of a solve: both ADMM right-hand sides from the resident (shifted, reduced) one `res`. LIN_START_COLD: v = y = 0
+// and the right-hand sides are copies of res. LIN_START_WARM: y of the rows the current bounds leave unbounded is zeroed
 // and the right-hand sides are res~ - S^'[rho G'M(y - v)]. v and the SCALED dual y are taken as the previous solve left
 // them whatever its penalty was -- as box_start does: a warm start with another rho starts from mu = rho y, not from the
 // previous mu; the iteration converges from any start.
+// LIN_START_MOVED, within a solve, after the shifted problem was reduced and factored again for new penalties: what
+// LIN_START_WARM does -- pad entries and the knots k >= u.N included --, from the new res and the new records, for the
+// problems marked in `moved` alone, whose marks it clears; y is zeroed nowhere. A problem that is not marked keeps both
+// buffers: a frozen one's hold the right-hand side of its last re-solve, which its final (v, y) would not give again.
 //   grid (batch), block 256, dynamic LDS 4 lin_wave_lds(n, m, p) doubles.
-static __global__ __launch_bounds__(256) void lin_start(Dims u, Dims d, int p, int cold, const double rho,
+static __global__ __launch_bounds__(256) void lin_start(Dims u, Dims d, int p, int mode, const double* __restrict__ rhov,
                                                  const double* __restrict__ rec, const double* __restrict__ C,
                                                  const double* __restrict__ D, const double* __restrict__ lo,
                                                  const double* __restrict__ hi, size_t bstride, const double* __restrict__ res,
                                                  double* __restrict__ v, double* __restrict__ y, double* __restrict__ rhs0,
-                                                 double* __restrict__ rhs1) {
+                                                 double* __restrict__ rhs1, int* __restrict__ moved) {
   extern __shared__ __attribute__((aligned(16))) double lin_lds[];
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (mode == LIN_START_MOVED && moved[b] == 0) return;  // (uniform over the workgroup)
+  const double rho = rhov[b];
   const size_t oz = (size_t)b * d.N * d.rows;
   for (unsigned e = tid; e < (unsigned)(d.N * d.rows); e += blockDim.x) {
     const double val = res[oz + e];
@@ -217,11 +237,12 @@ static __global__ __launch_bounds__(256) void lin_start(Dims u, Dims d, int p, i
   }
   double* vb = v + (size_t)b * u.N * p;
   double* yb = y + (size_t)b * u.N * p;
-  if (cold) {
+  if (mode == LIN_START_COLD) {
     for (unsigned e = tid; e < (unsigned)(u.N * p); e += blockDim.x) { vb[e] = 0.0; yb[e] = 0.0; }
     return;
   }
-  __syncthreads();  // (the copies above precede this workgroup's overwrites of the x and u rows)
+  __syncthreads();  // (the copies above precede this workgroup's overwrites of the x and u rows; every thread has read the mark)
+  if (mode == LIN_START_MOVED && tid == 0) moved[b] = 0;
   const LinKnotLds S(lin_lds + (size_t)wave * lin_wave_lds(u.n, u.m, p), u.n, u.m, p);
   const size_t recd = cost_record_doubles(u.n, u.m);
   for (int k = wave; k < u.N; k += 4) {
@@ -231,7 +252,7 @@ static __global__ __launch_bounds__(256) void lin_start(Dims u, Dims d, int p, i
     const size_t ob = (size_t)b * bstride + (size_t)k * p;
     for (int r = lane; r < p; r += 64) {
       const bool bounded = box_bounded(lo[ob + r], hi[ob + r]);
-      if (!bounded) yb[(size_t)k * p + r] = 0.0;
+      if (!bounded && mode == LIN_START_WARM) yb[(size_t)k * p + r] = 0.0;
       S.t0[r] = bounded ? lin_row_weight(rho, vb[(size_t)k * p + r], yb[(size_t)k * p + r]) : 0.0;
     }
     const size_t ok = oz + (size_t)k * d.rows;
@@ -320,26 +341,45 @@ __device__ __forceinline__ void lin_tail_frozen(const Dims& u, const Dims& d, co
   }
 }
 
+// Tail of a problem whose penalty moved: y <- y (rho / rho+) on its bounded rows. Row r of knot k belongs to the lane
+// that stored its y+ in lin_update_knot, so every lane re-reads only what it wrote itself.
+__device__ __forceinline__ void lin_tail_new_penalty(const Dims& u, const int p, const LinBoundRows& rows,
+                                                     double* __restrict__ yb, const double s, const int wave, const int lane) {
+  for (int k = wave; k < u.N; k += 4)
+    for (int r = lane; r < p; r += 64) {
+      bool clip;
+      double l, h;
+      if (rows(k, p, r, clip, l, h)) yb[(size_t)k * p + r] *= s;
+    }
+}
+
 // One ADMM update of every running problem (status[b] == 0) after re-solve `it`; see the head of this file. z: the
 // re-solve's solution z~ [batch][N][2n+m] (device layout) with the right-hand side rhs_cur; rec, C, D, v, y in the
 // caller's block sizes. The four wavefronts take the knots k < u.N round-robin (lin_update_knot); then the maxima are
-// reduced and thread 0 judges (box_judge). A frozen problem's next right-hand side is its current one.
+// reduced and thread 0 judges (box_judge). A frozen problem's next right-hand side is its current one. adapt != 0: a
+// problem that goes on may move its penalty (box_adapt_penalty): then rho[b] = rho+, y of its bounded rows is multiplied
+// by rho / rho+ (mu = rho y is kept), moved[b] = 1 and running[1] counts it. Its next right-hand side is NOT the one of
+// rho+ -- res~ and S^' belong to the shifted records of rho+, which the host has yet to make: lin_start(LIN_START_MOVED)
+// writes it after them. A frozen problem never moves.
 //   grid (batch), block 256, dynamic LDS 4 lin_wave_lds(n, m, p) doubles.
 template <bool STRICT>
-__global__ __launch_bounds__(256) void lin_update(Dims u, Dims d, int p, int it, BoxParams P, const double* __restrict__ z,
+__global__ __launch_bounds__(256) void lin_update(Dims u, Dims d, int p, int it, int adapt, BoxParams P,
+                                                  const double* __restrict__ z,
                                                   const double* __restrict__ rec, const double* __restrict__ C,
                                                   const double* __restrict__ D, const double* __restrict__ lo,
                                                   const double* __restrict__ hi, size_t bstride, double* __restrict__ v,
                                                   double* __restrict__ y, const double* __restrict__ res,
                                                   const double* __restrict__ rhs_cur, double* __restrict__ rhs_next,
-                                                  const double rho, int* __restrict__ status,
+                                                  double* __restrict__ rhov, int* __restrict__ status,
                                                   int* __restrict__ iters, double* __restrict__ resid,
-                                                  int* __restrict__ running) {
+                                                  int* __restrict__ running, int* __restrict__ moved) {
   extern __shared__ __attribute__((aligned(16))) double lin_lds[];
   __shared__ double red[5][256];
-  __shared__ int conv_s;
+  __shared__ double rho_s;  // the new penalty when conv_s == 2
+  __shared__ int conv_s;    // 0: goes on, 1: frozen, 2: goes on with a new penalty
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   if (status[b] != 0) return;  // frozen (uniform over the workgroup)
+  const double rho = rhov[b];
   const size_t oz = (size_t)b * d.N * d.rows;
   double* vb = v + (size_t)b * u.N * p;
   double* yb = y + (size_t)b * u.N * p;
@@ -349,9 +389,14 @@ __global__ __launch_bounds__(256) void lin_update(Dims u, Dims d, int p, int it,
   for (int k = wave; k < u.N; k += 4)
     lin_update_knot<STRICT>(S, u, d, p, k, b, P, rho, z, rec, C, D, rows, vb, yb, res, rhs_next, oz, M, lane);
   M.reduce(red, tid);
-  if (tid == 0) conv_s = box_judge(P, rho, red, b, it, status, iters, resid, running).frozen ? 1 : 0;
+  if (tid == 0) {
+    const BoxVerdict J = box_judge(P, rho, red, b, it, status, iters, resid, running);
+    conv_s = J.frozen ? 1 : adapt && box_adapt_penalty(P, rho, J, b, rhov, running, &rho_s) ? 2 : 0;
+    if (conv_s == 2) moved[b] = 1;
+  }
   __syncthreads();
   if (conv_s == 1) lin_tail_frozen(u, d, oz, rhs_cur, rhs_next, tid);
+  else if (conv_s == 2) lin_tail_new_penalty(u, p, rows, yb, rho / rho_s, wave, lane);
 }
 
 // Knot k of problem b of a delivery, by one wavefront: zs gets S^ z~ -- lambda, x, u in the caller's variables under the
@@ -386,11 +431,12 @@ static __global__ __launch_bounds__(64) void lin_finish(Dims u, Dims d, int p, c
   lin_deliver_knot(lin_lds, u, d, p, blockIdx.x, blockIdx.y, rec, z, zs, threadIdx.x);
 }
 
-// mu = rho y, elementwise over [batch][N][p].
+// mu = rho[b] y, elementwise over [batch][N][p].
 //   grid ceil(N p / 256), batch; block 256.
-static __global__ void lin_multipliers(int per_problem, const double rho, const double* __restrict__ y,
+static __global__ void lin_multipliers(int per_problem, const double* __restrict__ rhov, const double* __restrict__ y,
                                        double* __restrict__ mu) {
   const int b = blockIdx.y;
+  const double rho = rhov[b];
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < per_problem) mu[(size_t)b * per_problem + e] = rho * y[(size_t)b * per_problem + e];
 }

@@ -5,7 +5,7 @@
 // bound) and G = [C D], the adjoint of a loss L(z*) with g = dL/dz* is the equality-constrained system
 //     K w + G_A' nu = g,   G_A w = 0,
 // solved as section 3.10 solves the box case: by the ADMM of kernels_lin.hpp on the forward's remembered SHIFTED
-// reduction and factorisation (same rho, same M), right-hand side S^' g, lo = hi = 0 on A. The rows of M \ A carry the
+// reduction and factorisation (same rho[batch] -- the vector the forward ended with, which nothing here moves --, same M), right-hand side S^' g, lo = hi = 0 on A. The rows of M \ A carry the
 // rho shift of that factorisation, so they stay in the splitting as free rows: bounded, but their clip is the identity
 // (y stays 0). Every row gets a byte code from the forward's v once -- the codes of box_adjoint_start:
 //     LIN_UNBOUNDED 0   not in M: no part of the iteration
@@ -99,7 +99,7 @@ struct LinCodeRows {
 
 // One ADMM update of the constrained adjoint for every running problem after re-solve `it`: lin_update with the codes in
 // place of the bounds (lin_update_knot over LinCodeRows; box_judge; lin_tail_frozen). v, y, res, the right-hand sides,
-// status, iters, resid and the running count are the adjoint's own; rho is the forward's.
+// status, iters, resid and the running count are the adjoint's own; rho [batch] is the forward's.
 //   grid (batch), block 256, dynamic LDS 4 lin_wave_lds(n, m, p) doubles.
 template <bool STRICT>
 __global__ __launch_bounds__(256) void lin_adjoint_update(Dims u, Dims d, int p, int it, BoxParams P,
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void lin_adjoint_update(Dims u, Dims d, int p,
                                                           const unsigned char* __restrict__ code, double* __restrict__ v,
                                                           double* __restrict__ y, const double* __restrict__ res,
                                                           const double* __restrict__ rhs_cur, double* __restrict__ rhs_next,
-                                                          const double rho, int* __restrict__ status,
+                                                          const double* __restrict__ rhov, int* __restrict__ status,
                                                           int* __restrict__ iters, double* __restrict__ resid,
                                                           int* __restrict__ running) {
   extern __shared__ __attribute__((aligned(16))) double lin_lds[];
@@ -116,6 +116,7 @@ __global__ __launch_bounds__(256) void lin_adjoint_update(Dims u, Dims d, int p,
   __shared__ int conv_s;
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   if (status[b] != 0) return;  // frozen (uniform over the workgroup)
+  const double rho = rhov[b];
   const size_t oz = (size_t)b * d.N * d.rows;
   double* vb = v + (size_t)b * u.N * p;
   double* yb = y + (size_t)b * u.N * p;
@@ -170,7 +171,7 @@ __device__ __forceinline__ double lin_row_grad(double mu, double wj, double nu, 
 // the caller's variables; yf, ya: the forward's and the adjoint's scaled duals. Exactly 0 on the rows outside the active
 // set, for D of the last knot and for a problem the adjoint did not solve (status 3).
 template <bool STRICT>
-__device__ __forceinline__ double lin_grad_entry(const Dims& u, const Dims& d, const int p, const double rho,
+__device__ __forceinline__ double lin_grad_entry(const Dims& u, const Dims& d, const int p, const double* __restrict__ rhov,
                                                  const unsigned char* __restrict__ code, const double* __restrict__ yf,
                                                  const double* __restrict__ ya, const int* __restrict__ status,
                                                  const double* __restrict__ z, const double* __restrict__ w, const int b,
@@ -193,6 +194,7 @@ __device__ __forceinline__ double lin_grad_entry(const Dims& u, const Dims& d, c
   const size_t ev = ((size_t)b * u.N + k) * p + r;
   const unsigned char c = code[ev];
   if (c < LIN_AT_LO) return 0.0;
+  const double rho = rhov[b];
   const double nu = rho * ya[ev];
   if (*which >= 2) return (*which == 3 ? c == LIN_AT_HI : c == LIN_AT_LO) ? nu : 0.0;
   const double mu = rho * yf[ev];
@@ -210,14 +212,15 @@ __device__ __forceinline__ void lin_grad_put(const Dims& u, const int p, const L
 // Per-problem constraint gradients.
 //   grid (N, batch), block 64.
 template <bool STRICT>
-__global__ void lin_constraint_grads(Dims u, Dims d, int p, const double rho, const unsigned char* __restrict__ code,
+__global__ void lin_constraint_grads(Dims u, Dims d, int p, const double* __restrict__ rhov,
+                                     const unsigned char* __restrict__ code,
                                      const double* __restrict__ yf, const double* __restrict__ ya,
                                      const int* __restrict__ status, const double* __restrict__ z,
                                      const double* __restrict__ w, LinGradOut out) {
   const int k = blockIdx.x, b = blockIdx.y, W = lin_grad_width(u.n, u.m, p);
   for (int e = threadIdx.x; e < W; e += blockDim.x) {
     int which, at;
-    const double val = lin_grad_entry<STRICT>(u, d, p, rho, code, yf, ya, status, z, w, b, k, e, &which, &at);
+    const double val = lin_grad_entry<STRICT>(u, d, p, rhov, code, yf, ya, status, z, w, b, k, e, &which, &at);
     lin_grad_put(u, p, out, (size_t)b, k, which, at, val);
   }
 }
@@ -227,7 +230,8 @@ __global__ void lin_constraint_grads(Dims u, Dims d, int p, const double rho, co
 // lin_grad_sum_splits adds up in order (the scheme of box_bound_grads_sum: deterministic, no atomics).
 //   grid (ceil(N W / 256), nsplit), block 256.
 template <bool STRICT>
-__global__ __launch_bounds__(256) void lin_constraint_grads_sum(Dims u, Dims d, int p, const double rho, int ppb,
+__global__ __launch_bounds__(256) void lin_constraint_grads_sum(Dims u, Dims d, int p, const double* __restrict__ rhov,
+                                                                int ppb,
                                                                 const unsigned char* __restrict__ code,
                                                                 const double* __restrict__ yf, const double* __restrict__ ya,
                                                                 const int* __restrict__ status, const double* __restrict__ z,
@@ -241,7 +245,7 @@ __global__ __launch_bounds__(256) void lin_constraint_grads_sum(Dims u, Dims d, 
   const int p0 = blockIdx.y * ppb, p1 = (p0 + ppb < u.batch) ? p0 + ppb : u.batch;
   double sum = 0.0;
   int which = 0, at = 0;
-  for (int b = p0; b < p1; ++b) sum += lin_grad_entry<STRICT>(u, d, p, rho, code, yf, ya, status, z, w, b, k, e, &which, &at);
+  for (int b = p0; b < p1; ++b) sum += lin_grad_entry<STRICT>(u, d, p, rhov, code, yf, ya, status, z, w, b, k, e, &which, &at);
   if (part) part[(size_t)blockIdx.y * E + g] = sum;
   else lin_grad_put(u, p, out, 0, k, which, at, sum);
 }
@@ -262,10 +266,12 @@ static __global__ __launch_bounds__(256) void lin_grad_sum_splits(Dims u, int p,
   lin_grad_put(u, p, out, 0, k, which, at, sum);
 }
 
-// nu = rho y of the adjoint on the fixed rows, 0 elsewhere, elementwise over [batch][N][p].
+// nu = rho[b] y of the adjoint on the fixed rows, 0 elsewhere, elementwise over [batch][N][p].
 //   grid ceil(N p / 256), batch; block 256.
-static __global__ void lin_adjoint_multipliers(int per_problem, const double rho, const unsigned char* __restrict__ code,
-                                               const double* __restrict__ y, double* __restrict__ nu) {
+static __global__ void lin_adjoint_multipliers(int per_problem, const double* __restrict__ rhov,
+                                               const unsigned char* __restrict__ code, const double* __restrict__ y,
+                                               double* __restrict__ nu) {
+  const double rho = rhov[blockIdx.y];
   const size_t o = (size_t)blockIdx.y * per_problem + blockIdx.x * blockDim.x + threadIdx.x;
   if ((int)(blockIdx.x * blockDim.x + threadIdx.x) < per_problem) nu[o] = code[o] >= LIN_AT_LO ? rho * y[o] : 0.0;
 }

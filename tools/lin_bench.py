@@ -22,6 +22,15 @@ run replaces. Device times between the HIP events of a blocking call (solve_ms()
     through ndlqr_BatchSetRhsFlat + the rhs-only re-solve + the delivery's S, HIP events of FLAG_PROFILE).
 
     python tools/lin_bench.py [--reps 20] [--warmup 3] [--out profiles/lin_bench.jsonl]
+
+With --adapt-every K it measures the per-problem adaptive penalty instead and writes
+profiles/lin_adaptive_bench.jsonl: at the same shape and rows, cold solves from rho = 1 (+ k 2^-30 in repetition k, so that none reuses a factorisation) to eps 1e-6 within --max-iter
+iterations, with the fixed penalty and with the penalty considered every K iterations, in one process on one context; per
+variant the iterations over the batch (min / median / max), the statuses, the factorisations of one solve, ms per solve
+(median device time over --reps) and ms per iteration (ms per solve / the largest iteration count, which is what the batch
+runs), and for the adaptive variant the smallest and largest final penalty.
+
+    python tools/lin_bench.py --adapt-every 25 [--reps 3] [--max-iter 1000] [--out profiles/lin_adaptive_bench.jsonl]
 """
 import argparse
 import json
@@ -68,12 +77,55 @@ def rows(p, rng):
     return flat(C), flat(D), np.full(p, 0.5)
 
 
+def adaptive_main(a):
+    _, dense = problems()
+    rng = np.random.default_rng(11)
+    names = ("A", "B", "Q", "H", "R", "q", "r", "d", "x0")
+    lines = []
+    for p in (4, 8):
+        C, D, hi = rows(p, rng)
+        bs = R.BatchSolver(N_, M_, HOR, BATCH)
+        bs.initialize_flat_constrained(*[dense[k] for k in names], C, D, -hi, hi)
+        line = dict(shape=[N_, M_, HOR], batch=BATCH, p=p, reps=a.reps, rho=1.0, alpha=1.6, eps=1e-6, max_iter=a.max_iter,
+                    adapt_every=a.adapt_every)
+        for name, every in (("fixed", 0), ("adaptive", a.adapt_every)):
+            bs.set_constraint_adaptation(every)
+            ms, out = [], None
+            for k in range(a.warmup + a.reps):
+                fc = bs.factor_count()
+                # (a penalty the remembered factorisation does not have: every solve shifts, reduces and factors)
+                iters, status = bs.solve_constrained(rho=1.0 + (k + 1) * 2.0 ** -30, alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_iter=a.max_iter)
+                ms.append(bs.solve_ms())
+                rho = bs.constraint_penalties()
+                out = dict(iters=[int(iters.min()), int(np.median(iters)), int(iters.max())],
+                           status={str(k): int((status == k).sum()) for k in sorted(set(status.tolist()))},
+                           factorisations=int(bs.factor_count() - fc), rho=[float(rho.min()), float(rho.max())])
+            t = np.array(ms[a.warmup:])
+            out.update(solve_ms=float(np.median(t)), solve_spread=float((t.max() - t.min()) / np.median(t)),
+                       ms_per_iteration=float(np.median(t)) / out["iters"][2])
+            line[name] = out
+        bs.close()
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+    with open(a.out, "w") as f:
+        for ln in lines:
+            f.write(json.dumps(ln) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lin_bench.jsonl"))
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--adapt-every", type=int, default=0)
+    ap.add_argument("--max-iter", type=int, default=1000)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    adaptive = a.adapt_every > 0
+    a.reps = a.reps if a.reps is not None else (3 if adaptive else 20)
+    a.warmup = a.warmup if a.warmup is not None else (1 if adaptive else 3)
+    a.out = a.out or os.path.join(ROOT, "profiles", "lin_adaptive_bench.jsonl" if adaptive else "lin_bench.jsonl")
+    if adaptive:
+        return adaptive_main(a)
     diag, dense = problems()
     rng = np.random.default_rng(11)
     names = ("A", "B", "Q", "H", "R", "q", "r", "d", "x0")
