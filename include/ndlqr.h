@@ -432,7 +432,8 @@ int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs); /* 1: dense-cost mode, 0
  *   ndlqr_SolveBatchBoxConstrained with the same defaults (0, or s == NULL). The cost shifted by rho C'MC, rho C'MD, rho D'MD
  *   (M: the bounded rows) is reduced and factored once -- or not at all while rho, the flags, the inputs and the bounded
  *   pattern stay as they were (ndlqr_BatchSetRhsFlat keeps them) --, every iteration is one re-solve and one update
- *   kernel. iters / status [batch] (may be NULL): status 1 converged, 2 max_iter reached, 3 not finite. The solution that
+ *   kernel. iters / status [batch] (may be NULL): status 1 converged, 2 max_iter reached, 3 not finite, 4 certified
+ *   infeasible (only with ndlqr_BatchSetConstraintInfeasibilityDetection, below). The solution that
  *   ndlqr_CopyBatchSolution(s) delivers afterwards is [lambda, x, u] of the last re-solve: the dynamics hold exactly, the
  *   rows hold to within r_prim. A plain solve afterwards gives what it gave before, bit for bit.
  *   ndlqr_BatchSetConstraintPenaltyAdaptation: every > 0 gives the constrained solves that follow
@@ -446,13 +447,34 @@ int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs); /* 1: dense-cost mode, 0
  *   with adaptation off reuses a remembered factorisation only while all its penalties are s->rho.
  *   ndlqr_CopyBatchConstraintPenalties: rho [batch] of the latest constrained solve (host or this device's memory);
  *   refused by name before a constrained solve.
+ *   ndlqr_BatchSetConstraintInfeasibilityDetection: every > 0 lets the constrained solves that
+ *   follow test every running problem, at the iterations it >= 2 with it % every == 0 and it <= max_iter, for a Farkas
+ *   certificate that the dynamics and the rows have no common point: with dlam, dmu the differences of the multipliers
+ *   (in the caller's variables) and of mu = rho y over that iteration, D = max |dmu|,
+ *     e_x,k = -dlam_k + A_k' dlam_(k+1) + C_k' dmu_k,  e_u,k = B_k' dlam_(k+1) + D_k' dmu_k  (last knot: -dlam + C' dmu only),
+ *     S = sum over bounded rows (hi max(dmu, 0) + lo min(dmu, 0)) - x0' dlam_0 - sum_k d_k' dlam_(k+1),
+ *   a problem is certified when D > 0, max |e| <= eps D, S < -eps D, every dmu pointing to an infinite bound is at most
+ *   eps D, and all of them are finite (a NaN never certifies). It then ends as status 4 with iters = that iteration, frozen
+ *   like a converged one; its delivered solution is its last iterate (the dynamics hold, the rows do not), the batch ends
+ *   when every problem is 1, 3 or 4. every = 0, the initial state: off -- nothing is allocated, copied or launched. eps = 0:
+ *   1e-4. every < 0, or eps negative or not finite, returns NDLQR_ERR_INVALID and the previous setting stays. The setting
+ *   belongs to the solver: allowed in any mode and for any horizon, kept across initialisers; it is this solve's own --
+ *   ndlqr_BatchSetInfeasibilityDetection stays the box solve's. A warm-started solve starts a problem that ended as 4
+ *   cold; ndlqr_SolveBatchLinAdjoint does not iterate it (w = 0, nu = 0, every gradient of it zero).
+ *   ndlqr_CopyBatchConstraintInfeasibilityCertificate: dlam [batch][N][n], dmu [batch][N][p] of the problems that ended as
+ *   4, zero rows for the others; either may be NULL, not both. ndlqr_CopyBatchConstraintInfeasibilityMeasures: measures
+ *   [batch][4] = max |e| | D | the largest |dmu| toward an infinite bound | S of every problem's latest check and
+ *   iteration [batch], the iteration it ran at (0: never examined); either may be NULL, not both. Host or this device's
+ *   memory. Both refuse by name unless the resident solution is that of the latest constrained solve and detection was on
+ *   for it, and outside constrained mode.
  *   ndlqr_CopyBatchConstraintMultipliers: mu = rho y, [batch][N][p] (mu > 0 at an upper, < 0 at a lower bound).
  *   ndlqr_CopyBatchConstraintResiduals: [batch][4] = r_prim | r_dual | sp | sd of every problem's last update, with the
  *   meaning of ndlqr_CopyBatchBoxResiduals: r_prim = max |w - v|, r_dual = rho max |[C D]'(v - v_prev)|,
  *   sp = max(max |w|, max |v|), sd = rho max |[C D]' y|.
  * REFUSED by name (NDLQR_ERR_INVALID, ndlqr_hip_last_error()): s->adapt_every > 0 (that field, with rho_min and rho_max, is
  * the box solve's: ndlqr_BatchSetConstraintPenaltyAdaptation is this solve's switch); everything of the box
- * solve -- acceleration, infeasibility detection, polish, box adjoint and bound gradients -- as in dense-cost mode;
+ * solve -- acceleration, its infeasibility detection (ndlqr_BatchSetInfeasibilityDetection and its two read-outs: this
+ * solve has ndlqr_BatchSetConstraintInfeasibilityDetection), polish, box adjoint and bound gradients -- as in dense-cost mode;
  * ndlqr_BatchStepAsync. ndlqr_SolveBatchAdjoint refuses after a constrained solve: its adjoint is
  * ndlqr_SolveBatchLinAdjoint (below). */
 int ndlqr_InitializeBatchFlatConstrained(NdLqrBatchSolver* bs, const double* A, const double* B, const double* Q,
@@ -687,6 +709,9 @@ int ndlqr_CopyBatchBoxAdjointResiduals(NdLqrBatchSolver* bs, double* resid);
 int ndlqr_SolveBatchLinConstrained(NdLqrBatchSolver* bs, const NdLqrBoxSettings* s, int* iters, int* status);
 int ndlqr_BatchSetConstraintPenaltyAdaptation(NdLqrBatchSolver* bs, int every, double rho_min, double rho_max);
 int ndlqr_CopyBatchConstraintPenalties(NdLqrBatchSolver* bs, double* rho);
+int ndlqr_BatchSetConstraintInfeasibilityDetection(NdLqrBatchSolver* bs, int every, double eps);
+int ndlqr_CopyBatchConstraintInfeasibilityCertificate(NdLqrBatchSolver* bs, double* dlam, double* dmu);
+int ndlqr_CopyBatchConstraintInfeasibilityMeasures(NdLqrBatchSolver* bs, double* measures, int* iteration);
 int ndlqr_CopyBatchConstraintMultipliers(NdLqrBatchSolver* bs, double* mu);
 int ndlqr_CopyBatchConstraintResiduals(NdLqrBatchSolver* bs, double* resid);
 /* additive: primal infeasibility detection in the box-constrained solve. State bounds make

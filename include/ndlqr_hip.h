@@ -133,6 +133,16 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* ctx, double rho, double alpha, doub
                                 int check_every, int warm_start, int adapt_every, int* iters, int* status);
 int ndlqr_hip_set_constraint_adaptation(NdlqrHipCtx* ctx, int every, double rho_min, double rho_max);
 int ndlqr_hip_download_constraint_penalties(NdlqrHipCtx* ctx, double* rho);
+/* Infeasibility detection of that solve (ndlqr.h: ndlqr_BatchSetConstraintInfeasibilityDetection):
+ * every > 0 lets the constrained solves that follow test every running problem for a Farkas certificate at the iterations
+ * it >= 2, it % every == 0 (status 4); eps > 0 and finite. every = 0: off. Any mode, any horizon; no initialiser resets it.
+ * The read-outs -- dlam [batch][N][n] and dmu [batch][N][p] (either may be NULL; zero rows for a problem that is not 4),
+ * measures [batch][4] = ||e||_inf | D | the maximum toward an infinite bound | S and the iteration [batch] of every
+ * problem's latest check -- go to host memory or this device's and refuse by name unless the resident solution is that
+ * of the latest constrained solve and detection was on for it. */
+int ndlqr_hip_set_constraint_infeasibility(NdlqrHipCtx* ctx, int every, double eps);
+int ndlqr_hip_download_constraint_infeasibility_certificate(NdlqrHipCtx* ctx, double* dlam, double* dmu);
+int ndlqr_hip_download_constraint_infeasibility_measures(NdlqrHipCtx* ctx, double* measures, int* iteration);
 int ndlqr_hip_download_constraint_multipliers(NdlqrHipCtx* ctx, double* mu);
 int ndlqr_hip_download_constraint_residuals(NdlqrHipCtx* ctx, double* resid);
 int ndlqr_hip_download_constraint_reduction(NdlqrHipCtx* ctx, double* Qs, double* Hs, double* Rs, double* L, double* LR,

@@ -253,6 +253,9 @@ def lib():
     proto("ndlqr_SolveBatchLinConstrained", ci, vp, C.POINTER(NdLqrBoxSettingsFull), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_BatchSetConstraintPenaltyAdaptation", ci, vp, ci, C.c_double, C.c_double)
     proto("ndlqr_CopyBatchConstraintPenalties", ci, vp, dp)
+    proto("ndlqr_BatchSetConstraintInfeasibilityDetection", ci, vp, ci, cd)
+    proto("ndlqr_CopyBatchConstraintInfeasibilityCertificate", ci, vp, dp, dp)
+    proto("ndlqr_CopyBatchConstraintInfeasibilityMeasures", ci, vp, dp, C.POINTER(ci))
     proto("ndlqr_CopyBatchConstraintMultipliers", ci, vp, dp)
     proto("ndlqr_CopyBatchConstraintResiduals", ci, vp, dp)
     proto("ndlqr_hip_download_constraint_reduction", ci, vp, *([dp] * 14))
@@ -588,7 +591,7 @@ class BatchSolver:
                           adapt_every=0):
         """ndlqr_SolveBatchLinConstrained (0 = the library's default of the box solve for every setting; adapt_every > 0 is
         refused: the adaptive penalty of this solve is switched on by set_constraint_adaptation). Returns (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached, 3 = not
-        finite. solutions() afterwards gives [lambda, x, u] of the last re-solve. Raises on a nonzero return."""
+        finite, 4 = certified infeasible (only after set_constraint_infeasibility(every > 0)). solutions() afterwards gives [lambda, x, u] of the last re-solve. Raises on a nonzero return."""
         st = NdLqrBoxSettingsFull(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0,
                                   int(adapt_every), 0.0, 0.0)
         iters = np.zeros(self.batch, dtype=np.int32)
@@ -618,6 +621,54 @@ class BatchSolver:
         if err:
             raise RuntimeError("ndlqr_CopyBatchConstraintPenalties failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return rho
+
+    def set_constraint_infeasibility(self, every=0, eps=0.0):
+        """ndlqr_BatchSetConstraintInfeasibilityDetection: every > 0 lets the solve_constrained() calls that follow test
+        every running problem for a primal infeasibility certificate at the iterations it >= 2, it % every == 0 (status 4;
+        eps = 0: 1e-4); every = 0 (the initial state): off. Raises on a refusal (every < 0, eps negative or not finite);
+        the previous setting then stays."""
+        err = self.L.ndlqr_BatchSetConstraintInfeasibilityDetection(self.h, int(every), float(eps))
+        if err:
+            raise RuntimeError("ndlqr_BatchSetConstraintInfeasibilityDetection failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+
+    def constraint_infeasibility_certificate(self, dlam=None, dmu=None):
+        """ndlqr_CopyBatchConstraintInfeasibilityCertificate: (dlam [batch, N, n], dmu [batch, N, p]) of the last
+        solve_constrained, which ran with detection on: the Farkas certificate of every status-4 problem, zero rows for
+        the others; `dlam`, `dmu`: destinations (numpy arrays or DeviceArrays). Raises on a refusal."""
+        n, N, B, p = self.n, self.N, self.batch, getattr(self, "_rows", 1)
+        if dlam is None:
+            dlam = np.zeros((B, N, n))
+        if dmu is None:
+            dmu = np.zeros((B, N, p))
+        err = self.L.ndlqr_CopyBatchConstraintInfeasibilityCertificate(self.h, _any_ptr(dlam, B * N * n), _any_ptr(dmu, B * N * p))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchConstraintInfeasibilityCertificate failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return dlam, dmu
+
+    def constraint_infeasibility_measures(self, measures=None, iteration=None):
+        """ndlqr_CopyBatchConstraintInfeasibilityMeasures: (measures [batch, 4], iteration [batch]) of the last
+        solve_constrained, which ran with detection on: ||e||_inf, ||dmu||_inf, the largest |dmu_i| toward an infinite
+        bound and S as the latest check of every problem found them, and the iteration of that check (0 and a row of
+        zeros: no check examined the problem). Arguments as for infeasibility_measures. Raises on a refusal."""
+        B = self.batch
+        if measures is None:
+            measures = np.zeros((B, 4))
+        if iteration is None:
+            iteration = np.zeros(B, dtype=np.int32)
+        if hasattr(iteration, "ptr"):
+            ip = C.cast(C.c_void_p(int(iteration.ptr)), C.POINTER(C.c_int))
+        else:
+            if not (isinstance(iteration, np.ndarray) and iteration.dtype == np.int32 and iteration.flags["C_CONTIGUOUS"]
+                    and iteration.size == B):
+                raise ValueError("expected a C-contiguous int32 array of %d entries" % B)
+            ip = iteration.ctypes.data_as(C.POINTER(C.c_int))
+        err = self.L.ndlqr_CopyBatchConstraintInfeasibilityMeasures(self.h, _any_ptr(measures, 4 * B), ip)
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchConstraintInfeasibilityMeasures failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return measures, iteration
 
     def constraint_multipliers(self):
         """ndlqr_CopyBatchConstraintMultipliers: mu = rho y, [batch, N, p]."""
@@ -656,7 +707,8 @@ class BatchSolver:
         """ndlqr_SolveBatchLinAdjoint: the adjoint of the active-set system of the last solve_constrained for g = dL/dz*
         [batch, nvars] (numpy array or DeviceArray), on the forward's remembered shifted factorisation (its rho, a cold
         start; 0 = the library's default for every setting). Returns (iters, status) as numpy int arrays [batch]; status 1 =
-        converged, 2 = max_iter reached, 3 = not finite (or the forward's was: not iterated, w = 0, zero gradients).
+        converged, 2 = max_iter reached, 3 = not finite (or the forward's was, or the forward certified the problem infeasible:
+        not iterated, w = 0, zero gradients).
         Raises on a nonzero return. Afterwards adjoint() gives w in the caller's variables and constraint_gradients(),
         constraint_adjoint_multipliers(), constraint_adjoint_residuals() and constraint_codes() read the rest."""
         if not hasattr(g, "ptr"):

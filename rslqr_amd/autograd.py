@@ -525,22 +525,26 @@ _lin_cache = {}              # (n, m, N, p, b, device index) -> [BatchSolver, to
 
 
 def _lin_solve(bs, flat, settings, token, key):
-    """Initialise + constrained solve (cold) of `flat` on the cached solver; it then holds `token`."""
+    """Initialise + constrained solve (cold) of `flat` on the cached solver; it then holds `token`. Returns the mask of
+    the problems certified infeasible (status 4: only with infeas_every > 0)."""
     torch.cuda.current_stream(flat[0].device).synchronize()  # (the library reads torch memory on its own stream)
     _lin_cache[key][1] = None
-    rho, alpha, eps_abs, eps_rel, max_iter, check_every, adapt_every = settings
+    rho, alpha, eps_abs, eps_rel, max_iter, check_every, adapt_every, infeas_every, infeas_eps = settings
     try:
         bs.set_constraint_adaptation(adapt_every)
+        bs.set_constraint_infeasibility(infeas_every, infeas_eps)  # (the cached solver keeps the setting of whoever used it last)
         bs.initialize_flat_constrained(*[_View(t) for t in flat])
         _, status = bs.solve_constrained(rho=rho, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
                                          check_every=check_every)
     except RuntimeError as e:
         raise RuntimeError("lqr_solve_constrained: the constrained solve failed (%s)" % e) from None
-    bad = int((status != 1).sum())
+    infeasible = status == 4  # (certified: z is the last iterate, the gradients are zero)
+    bad = int(((status != 1) & ~infeasible).sum())
     if bad:
         raise RuntimeError("lqr_solve_constrained: %d of %d problems did not converge (status %s): raise max_iter or change rho"
-                           % (bad, status.size, sorted(set(status.tolist()) - {1})))
+                           % (bad, status.size, sorted(set(status[~infeasible].tolist()) - {1})))
     _lin_cache[key][1] = token
+    return infeasible
 
 
 class LqrSolveConstrained(torch.autograd.Function):
@@ -564,7 +568,7 @@ class LqrSolveConstrained(torch.autograd.Function):
         flat = [(t.detach().transpose(-1, -2) if t.dim() == 4 else t.detach()).contiguous().reshape(b, -1)
                 for t in (A, B, Q, H, R, q, r, d, x0, rows[0], rows[1])] + [t.contiguous().reshape(b, -1) for t in rows[2:]]
         token = next(_tokens)
-        _lin_solve(bs, flat, settings, token, key)
+        ctx.infeasible = _lin_solve(bs, flat, settings, token, key)
         z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
         bs.solutions_to_device(z.data_ptr())
         bs.synchronize()
@@ -581,16 +585,16 @@ class LqrSolveConstrained(torch.autograd.Function):
             _lin_solve(bs, ctx.flat, ctx.settings, ctx.token, ctx.key)
         gz = gz.detach().to(torch.float64).contiguous()
         torch.cuda.current_stream(gz.device).synchronize()
-        _, alpha, eps_abs, eps_rel, max_iter, check_every, _ = ctx.settings
+        _, alpha, eps_abs, eps_rel, max_iter, check_every = ctx.settings[:6]
         try:
             _, status = bs.solve_constrained_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
                                                      check_every=check_every)
         except RuntimeError as e:
             raise RuntimeError("lqr_solve_constrained backward: the adjoint failed (%s)" % e) from None
-        bad = int((status != 1).sum())
+        bad = int(((status != 1) & ~ctx.infeasible).sum())  # (a certified problem is not iterated: w = 0, nu = 0)
         if bad:
             raise RuntimeError("lqr_solve_constrained backward: the adjoint of %d of %d problems did not converge (status %s)"
-                               % (bad, status.size, sorted(set(status.tolist()) - {1})))
+                               % (bad, status.size, sorted(set(status[~ctx.infeasible].tolist()) - {1})))
         w = torch.empty_like(z)
         bs.adjoint(_View(w))
         need = ctx.needs_input_grad[2:]
@@ -614,13 +618,15 @@ class LqrSolveConstrained(torch.autograd.Function):
 
 
 def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0,
-                          max_iter=0, check_every=0, adapt_every=0):
+                          max_iter=0, check_every=0, adapt_every=0, infeas_every=0, infeas_eps=0.0):
     """z* [b, nvars] of the dense-cost LQR problems of lqr_solve_dense subject to, per knot, p rows
         lo_k <= C_k x_k + D_k u_k <= hi_k,     C [b, N, p, n]   D [b, N, p, m]   lo, hi [b, N, p]
     (entries of lo, hi may be +-inf; D of the last knot is not part of the problem), by the solve with linear inequality
     constraints (ndlqr_SolveBatchLinConstrained, cold start; 0 = the library's default for every setting; adapt_every > 0:
     the per-problem adaptive penalty of ndlqr_BatchSetConstraintPenaltyAdaptation, considered every that many iterations,
-    0: off), differentiable in all thirteen tensors. Any argument may leave out the batch dimension (shared: its gradient is the batch sum -- for
+    0: off; infeas_every > 0: infeasibility detection every that many iterations with the tolerance infeas_eps, 0: 1e-4
+    (ndlqr_BatchSetConstraintInfeasibilityDetection) -- a problem certified infeasible (status 4) does not raise: its z is
+    the last iterate and every gradient of it is zero), differentiable in all thirteen tensors. Any argument may leave out the batch dimension (shared: its gradient is the batch sum -- for
     C, D, lo, hi computed on the device when all of them that need a gradient are shared). The backward is the adjoint
     of the active-set system (ndlqr_SolveBatchLinAdjoint) with the same alpha, tolerances, max_iter and check_every on the
     forward's factorisation and final penalties. Raises RuntimeError when a problem's forward or adjoint iteration does not converge (status
@@ -667,5 +673,6 @@ def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, 
     # (a shared problem argument is expanded here, outside the Function: autograd sums its gradient over the batch; the row
     #  arguments go in as they are, so that the library can sum theirs)
     full = [t if not shared[name] else t.unsqueeze(0).expand(b, *t.shape) for name, t in zip(_DENSE_ARGS, args[:9])]
-    settings = (float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(check_every), int(adapt_every))
+    settings = (float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(check_every), int(adapt_every),
+                int(infeas_every), float(infeas_eps))
     return LqrSolveConstrained.apply(settings, tuple(shared[k] for k in _ROW_ARGS), *full, C, D, lo, hi)

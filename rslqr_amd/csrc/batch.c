@@ -224,6 +224,19 @@ int ndlqr_CopyBatchConstraintPenalties(NdLqrBatchSolver* bs, double* rho) {
   if (!bs || !rho) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_constraint_penalties(bs->ctx, rho);
 }
+int ndlqr_BatchSetConstraintInfeasibilityDetection(NdLqrBatchSolver* bs, int every, double eps) {
+  /* (eps < HUGE_VAL is false for a NaN as well) */
+  if (!bs || every < 0 || !(eps >= 0.0 && eps < HUGE_VAL)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_set_constraint_infeasibility(bs->ctx, every, eps > 0.0 ? eps : 1e-4);
+}
+int ndlqr_CopyBatchConstraintInfeasibilityCertificate(NdLqrBatchSolver* bs, double* dlam, double* dmu) {
+  if (!bs || (!dlam && !dmu)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_infeasibility_certificate(bs->ctx, dlam, dmu);
+}
+int ndlqr_CopyBatchConstraintInfeasibilityMeasures(NdLqrBatchSolver* bs, double* measures, int* iteration) {
+  if (!bs || (!measures && !iteration)) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_infeasibility_measures(bs->ctx, measures, iteration);
+}
 int ndlqr_CopyBatchConstraintMultipliers(NdLqrBatchSolver* bs, double* mu) {
   if (!bs || !mu) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_constraint_multipliers(bs->ctx, mu);

@@ -480,6 +480,34 @@ struct LinAdjointState {
   }
 };
 
+// Infeasibility detection of the solve with linear inequality constraints (ndlqr_hip_set_constraint_infeasibility,
+// kernels_lin_infeas.hpp). every, eps: the setting, the solver's and not the problem's (every == 0:
+// off -- nothing here is allocated or launched). All in the CALLER's block sizes and horizon (u): lam_prev, lam_cur
+// [batch][N][n], the multipliers of the re-solve before a check and of the check's in the caller's variables; mu_prev
+// [batch][N][p] = rho y after the update before a check; the certificate of every status-4 problem, zero elsewhere
+// (cert_lam [batch][N][n], cert_mu [batch][N][p]); the four numbers of every problem's latest check and the iteration it
+// ran at (measures [batch][4], measured_at [batch]; zero for a problem no check examined). All of it is zeroed at the
+// start of every solve with detection on. gen: the solution generation of the latest constrained solve that ran with
+// detection on (0: none). lds_asked: as LinState's, for lin_lambda_out | lin_certify.
+struct LinInfeasState {
+  DevBuf<double> lam_prev, lam_cur, mu_prev, cert_lam, cert_mu, measures;
+  DevBuf<int> measured_at;
+  int every = 0, p = 0;
+  double eps = 1e-4;
+  size_t lds_asked[2] = {};
+  unsigned long long gen = 0;
+  // the buffers that depend on p are allocated again when p changes
+  hipError_t ensure(const ndlqr::Dims& u, int rows_per_knot) {
+    if (rows_per_knot != p) {
+      mu_prev.reset(); cert_mu.reset();
+    }
+    p = rows_per_knot;
+    const size_t nl = (size_t)u.batch * u.N * u.n, np = (size_t)u.batch * u.N * p, nb = (size_t)u.batch;
+    return first_error({lam_prev.ensure(nl), lam_cur.ensure(nl), mu_prev.ensure(np), cert_lam.ensure(nl), cert_mu.ensure(np),
+                        measures.ensure(4 * nb), measured_at.ensure(nb)});
+  }
+};
+
 struct NdlqrHipCtx {
   ndlqr::Dims d = {};   // block sizes of the DEVICE layout (every kernel works on these)
   ndlqr::Dims du = {};  // the caller's block sizes and horizon: the same, or smaller when the problem runs zero-padded into
@@ -547,6 +575,7 @@ struct NdlqrHipCtx {
   CostState cost;
   LinState lin;
   LinAdjointState alin;
+  LinInfeasState lin_infeas;
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // the remembered shifted factorisations (ADMM's and the polish's) no longer match the records / factors
   void forget_shifted() { box.fact = pol.fact = lin.fact = false; }

@@ -2,9 +2,11 @@
 // ndlqr_hip_set_constraint_bounds, ndlqr_hip_solve_constrained and their read-outs) and the
 // gradients through that solve (ndlqr_hip_solve_constrained_adjoint, ndlqr_hip_constraint_gradients; section 3.18): the
 // host side, the kernels of kernels_lin.hpp and kernels_lin_grad.hpp. The reduction kernels it needs belong to hip_cost.hip (cost_reduce_problem,
-// cost_reduce_rhs_to).
+// cost_reduce_rhs_to). Infeasibility detection of that solve (ndlqr_hip_set_constraint_infeasibility and its two read-outs;
+// section 3.20, kernels_lin_infeas.hpp) lives in its loop and at the end of this file.
 #include "hip_host.hpp"
 #include "kernels_lin_grad.hpp"
+#include "kernels_lin_infeas.hpp"
 
 // ------------------------------------------------------------------------------ constrained mode
 // A dense-cost mode with constraints: ndlqr_hip_init_constrained retains the caller's A, B, Q, H, R, q, r, d, x0 and C, D
@@ -18,6 +20,11 @@
 // problems with the running count and, when it is not zero, shifts, reduces, packs and factors the whole batch again and
 // lets lin_start rewrite the right-hand sides of the moved problems -- one factorisation serves every problem that moved
 // in that round, and the deterministic kernels give every other problem its old records and factors back.
+// Infeasibility detection (ndlqr_hip_set_constraint_infeasibility(every > 0)): the iteration before a
+// check leaves lambda of its re-solve in the caller's variables (lin_lambda_out) and mu = rho y (lin_multipliers) behind
+// lin_update and before any refactorisation; the check iteration forms its own lambda the same way and lin_certify judges
+// the differences. A certified problem is frozen as status 4 and leaves the running count the host reads anyway. With
+// every == 0 nothing of this is allocated, copied or launched.
 
 // (the kernels hold static LDS next to the dynamic: ask well below the default limit. `asked`: what this context has
 //  asked for this kernel already -- one of LinState::lds_asked --, so that a solve does not ask again)
@@ -188,6 +195,17 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
   HIP_TRY(hipSetDevice(c->device));
   int err = refuse_foreign_iters_status(c, "ndlqr_hip_solve_constrained", iters, status);
   if (err) return err;
+  LinInfeasState& inf = c->lin_infeas;
+  const int infeas_every = inf.every;
+  const size_t lam_lds = sizeof(double) * ndlqr::lin_lambda_lds(u.n), cert_lds = ndlqr::lin_certify_lds_bytes(u, k.p);
+  if (infeas_every > 0) {
+    if (cert_lds + sizeof(double) * 5 * 256 + 16 > kLdsMax)
+      return refuse("ndlqr_hip_solve_constrained: lin_certify stages " + std::to_string(cert_lds) + " bytes per workgroup at (" +
+                    std::to_string(u.n) + "," + std::to_string(u.m) + ") with " + std::to_string(k.p) +
+                    " rows, beyond the LDS of a workgroup (ndlqr_hip_set_constraint_infeasibility(0) switches detection off)");
+    HIP_TRY(inf.ensure(u, k.p));
+  }
+  inf.gen = 0;
   // 1. everything idle, the primary set current
   HIP_TRY(sync_all(c));
   c->cur = 0;
@@ -225,10 +243,12 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
   const auto start = [&](int mode) -> int {
     hipLaunchKernelGGL(ndlqr::lin_start, dim3(u.batch), dim3(256), lds, st, u, d, p, mode, rhov, (const double*)k.rec,
                        (const double*)k.C, (const double*)k.D, (const double*)k.lo, (const double*)k.hi, k.bstride,
-                       (const double*)s.rhs, k.v.get(), k.y.get(), k.rhs[0].get(), k.rhs[1].get(), k.moved.get());
+                       (const double*)s.rhs, (const int*)k.status, k.v.get(), k.y.get(), k.rhs[0].get(), k.rhs[1].get(),
+                       k.moved.get());
     HIP_TRY(hipGetLastError());
     return NDLQR_OK;
   };
+  const auto is_check = [&](int i) { return infeas_every > 0 && i >= 2 && i <= max_iter && i % infeas_every == 0; };
   const char* const what = "the reduction of Q + rho C'MC, H + rho C'MD, R + rho D'MD";
   // (a lambda for its early returns: every one of them arrives at close() and the bookkeeping behind it)
   const auto iterate = [&]() -> int {
@@ -263,6 +283,15 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
     HIP_TRY(hipMemcpyAsync(k.word, k.h_word, 2 * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(k.status, 0, sizeof(int) * (size_t)u.batch, st));
     HIP_TRY(hipMemsetAsync(k.moved, 0, sizeof(int) * (size_t)u.batch, st));
+    const size_t nlam = (size_t)u.batch * u.N * u.n, nmu = (size_t)u.batch * u.N * p;
+    if (infeas_every > 0) {  // (the certificate rows of the problems that do not end as 4 are zero)
+      HIP_TRY(allow_lin_lds(ndlqr::lin_lambda_out, lam_lds, inf.lds_asked[0]));
+      HIP_TRY(allow_lin_lds(ndlqr::lin_certify, cert_lds, inf.lds_asked[1]));
+      for (DevBuf<double>* buf : {&inf.lam_prev, &inf.lam_cur, &inf.cert_lam}) HIP_TRY(hipMemsetAsync(*buf, 0, sizeof(double) * nlam, st));
+      for (DevBuf<double>* buf : {&inf.mu_prev, &inf.cert_mu}) HIP_TRY(hipMemsetAsync(*buf, 0, sizeof(double) * nmu, st));
+      HIP_TRY(hipMemsetAsync(inf.measures, 0, sizeof(double) * 4 * (size_t)u.batch, st));
+      HIP_TRY(hipMemsetAsync(inf.measured_at, 0, sizeof(int) * (size_t)u.batch, st));
+    }
     for (int it = 1; it <= max_iter; ++it) {
       const double* rc = k.rhs[(it - 1) & 1];
       double* rn = k.rhs[it & 1];
@@ -274,11 +303,36 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
                     k.bstride, k.v.get(), k.y.get(), (const double*)s.rhs, rc, rn, k.rho.get(), k.status.get(),
                     k.iters.get(), k.resid.get(), k.word.get(), k.moved.get());
       HIP_TRY(hipGetLastError());
+      const bool check = is_check(it), before_check = is_check(it + 1);
+      if (check || before_check) {
+        // 4a. lambda of this re-solve in the caller's variables, under the records it used (a refactorisation comes later)
+        hipLaunchKernelGGL(ndlqr::lin_lambda_out, dim3(u.N, u.batch), dim3(64), lam_lds, st, u, d, (const double*)k.rec,
+                           (const double*)k.z, check ? inf.lam_cur.get() : inf.lam_prev.get());
+        HIP_TRY(hipGetLastError());
+      }
+      if (check) {  // the differences over this iteration: a certificate?
+        hipLaunchKernelGGL(ndlqr::lin_certify, dim3(u.batch), dim3(256), cert_lds, st, u, d, p, it, inf.eps, (const double*)k.A,
+                           (const double*)k.B, (const double*)k.C, (const double*)k.D, (const double*)k.d, (const double*)k.x0,
+                           (const double*)k.lo, (const double*)k.hi, k.bstride, (const double*)inf.lam_cur,
+                           (const double*)inf.lam_prev, (const double*)k.y, (const double*)inf.mu_prev, (const double*)k.rho,
+                           k.rhs[(it - 1) & 1].get(), (const double*)rn, k.status.get(), k.iters.get(), k.word.get(),
+                           inf.cert_lam.get(), inf.cert_mu.get(), inf.measures.get(), inf.measured_at.get());
+        HIP_TRY(hipGetLastError());
+      }
+      if (before_check) {  // what the next iteration's check takes its differences against
+        if (check) HIP_TRY(hipMemcpyAsync(inf.lam_prev, inf.lam_cur, sizeof(double) * nlam, hipMemcpyDeviceToDevice, st));
+        const int per = u.N * p;
+        hipLaunchKernelGGL(ndlqr::lin_multipliers, dim3((per + 255) / 256, u.batch), dim3(256), 0, st, per, (const double*)k.rho,
+                           (const double*)k.y, inf.mu_prev.get());
+        HIP_TRY(hipGetLastError());
+      }
       if (it % check_every == 0 || it == max_iter || adapt) {
         // 5. one word: how many problems still run; after an adapting update also how many moved their penalty
         HIP_TRY(hipMemcpyAsync(k.h_word, k.word, (adapt ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (k.h_word[0] == 0) break;
+        // (a problem that moved its penalty goes on -- unless the check behind the same update certified it: its move
+        //  stands, and 5a. runs for it as for any other)
+        if (k.h_word[0] == 0 && !(adapt && k.h_word[1] != 0)) break;
         if (adapt && k.h_word[1] != 0) {
           // 5a. new penalties: the whole batch shifted, reduced, packed and factored as above (a problem that did not move
           // gets its records, its res~ and its factors back bit for bit), then both right-hand sides of the moved problems
@@ -291,6 +345,13 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
           if (!e) e = start(ndlqr::LIN_START_MOVED);
           if (e) return e;
           HIP_TRY(hipMemsetAsync(k.word + 1, 0, sizeof(int), st));
+          if (k.h_word[0] == 0) {
+            // (the batch ended with that certificate: one more re-solve, so that z~ belongs to the records in force --
+            //  every other problem is frozen and gets its z~ back bit for bit)
+            e = launch_resolve(c, rn, k.z, "constrained solve: this configuration needs NDLQR_FLAG_KEEP_FACT");
+            if (e) return e;
+            break;
+          }
         }
       }
     }
@@ -323,6 +384,7 @@ int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double
   k.rhs_new = false;
   note_solution(c);
   k.soln_gen = c->soln_gen;
+  if (infeas_every > 0) inf.gen = c->soln_gen;
   c->cost.mapped_gen = c->soln_gen;  // (the delivery must not apply the plain records to it)
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   c->timing_pending = true;
@@ -338,6 +400,60 @@ int ndlqr_hip_set_constraint_adaptation(NdlqrHipCtx* c, int every, double rho_mi
   c->lin.adapt_every = every;
   c->lin.rho_min = rho_min;
   c->lin.rho_max = rho_max;
+  return NDLQR_OK;
+}
+
+int ndlqr_hip_set_constraint_infeasibility(NdlqrHipCtx* c, int every, double eps) {
+  if (!c) return NDLQR_ERR_INVALID;
+  if (every < 0 || !(eps > 0.0 && eps < HUGE_VAL))
+    return refuse("ndlqr_hip_set_constraint_infeasibility: bad argument (every >= 0, eps > 0 and finite)");
+  c->lin_infeas.every = every;
+  c->lin_infeas.eps = eps;
+  return NDLQR_OK;
+}
+
+// is the resident solution that of the latest constrained solve, and did that solve run with detection on?
+static int need_constraint_infeasibility(const NdlqrHipCtx* c, const char* who) {
+  if (const int merr = need_constrained(c, who)) return merr;
+  const unsigned long long gen = c->lin_infeas.gen;
+  if (gen == 0 || gen != c->soln_gen || c->lin.soln_gen != c->soln_gen)
+    return refuse(std::string(who) + ": the resident solution is not that of a constrained solve with infeasibility detection "
+                  "on (ndlqr_hip_set_constraint_infeasibility before ndlqr_hip_solve_constrained)");
+  return NDLQR_OK;
+}
+
+// dlam [batch][N][n], dmu [batch][N][p] of every status-4 problem of the latest constrained solve (zero rows elsewhere),
+// into host memory or this device's; either may be null. (Stored in the caller's layout: plain copies.)
+int ndlqr_hip_download_constraint_infeasibility_certificate(NdlqrHipCtx* c, double* dlam, double* dmu) {
+  if (!c || (!dlam && !dmu)) return NDLQR_ERR_INVALID;
+  const char* const who = "ndlqr_hip_download_constraint_infeasibility_certificate";
+  if (const int serr = need_constraint_infeasibility(c, who)) return serr;
+  const ndlqr::Dims& u = c->du;
+  HIP_TRY(hipSetDevice(c->device));
+  for (const void* o : {(const void*)dlam, (const void*)dmu})
+    if (o && where(o, c->device) == Where::OtherDevice)
+      return refuse(std::string(who) + ": an output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  const size_t kn = (size_t)u.batch * u.N;
+  if (dlam) HIP_TRY(hipMemcpy(dlam, c->lin_infeas.cert_lam, sizeof(double) * kn * u.n, hipMemcpyDefault));
+  if (dmu) HIP_TRY(hipMemcpy(dmu, c->lin_infeas.cert_mu, sizeof(double) * kn * c->lin.p, hipMemcpyDefault));
+  return NDLQR_OK;
+}
+
+// measures [batch][4] = ||e||_inf | D | the maximum toward an infinite bound | S of every problem's latest check and the
+// iteration it ran at (zero for a problem no check examined), as ndlqr_hip_download_infeasibility_measures
+int ndlqr_hip_download_constraint_infeasibility_measures(NdlqrHipCtx* c, double* measures, int* iteration) {
+  if (!c || (!measures && !iteration)) return NDLQR_ERR_INVALID;
+  const char* const who = "ndlqr_hip_download_constraint_infeasibility_measures";
+  if (const int serr = need_constraint_infeasibility(c, who)) return serr;
+  HIP_TRY(hipSetDevice(c->device));
+  for (const void* o : {(const void*)measures, (const void*)iteration})
+    if (o && where(o, c->device) == Where::OtherDevice)
+      return refuse(std::string(who) + ": an output lies in the memory of another device than the solver's");
+  HIP_TRY(sync_all(c));
+  const size_t nb = (size_t)c->du.batch;
+  if (measures) HIP_TRY(hipMemcpy(measures, c->lin_infeas.measures, sizeof(double) * 4 * nb, hipMemcpyDefault));
+  if (iteration) HIP_TRY(hipMemcpy(iteration, c->lin_infeas.measured_at, sizeof(int) * nb, hipMemcpyDefault));
   return NDLQR_OK;
 }
 

@@ -213,7 +213,8 @@ enum : int { LIN_START_WARM = 0, LIN_START_COLD = 1, LIN_START_MOVED = 2 };
 // and the right-hand sides are copies of res. LIN_START_WARM: y of the rows the current bounds leave unbounded is zeroed
 // and the right-hand sides are res~ - S^'[rho G'M(y - v)]. v and the SCALED dual y are taken as the previous solve left
 // them whatever its penalty was -- as box_start does: a warm start with another rho starts from mu = rho y, not from the
-// previous mu; the iteration converges from any start.
+// previous mu; the iteration converges from any start. A problem the previous solve left as 4 (prev_status: certified
+// infeasible, its y has diverged) starts cold, as in box_start.
 // LIN_START_MOVED, within a solve, after the shifted problem was reduced and factored again for new penalties: what
 // LIN_START_WARM does -- pad entries and the knots k >= u.N included --, from the new res and the new records, for the
 // problems marked in `moved` alone, whose marks it clears; y is zeroed nowhere. A problem that is not marked keeps both
@@ -223,8 +224,9 @@ static __global__ __launch_bounds__(256) void lin_start(Dims u, Dims d, int p, i
                                                  const double* __restrict__ rec, const double* __restrict__ C,
                                                  const double* __restrict__ D, const double* __restrict__ lo,
                                                  const double* __restrict__ hi, size_t bstride, const double* __restrict__ res,
-                                                 double* __restrict__ v, double* __restrict__ y, double* __restrict__ rhs0,
-                                                 double* __restrict__ rhs1, int* __restrict__ moved) {
+                                                 const int* __restrict__ prev_status, double* __restrict__ v,
+                                                 double* __restrict__ y, double* __restrict__ rhs0, double* __restrict__ rhs1,
+                                                 int* __restrict__ moved) {
   extern __shared__ __attribute__((aligned(16))) double lin_lds[];
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   if (mode == LIN_START_MOVED && moved[b] == 0) return;  // (uniform over the workgroup)
@@ -237,7 +239,7 @@ static __global__ __launch_bounds__(256) void lin_start(Dims u, Dims d, int p, i
   }
   double* vb = v + (size_t)b * u.N * p;
   double* yb = y + (size_t)b * u.N * p;
-  if (mode == LIN_START_COLD) {
+  if (mode == LIN_START_COLD || (mode == LIN_START_WARM && prev_status[b] == 4)) {  // (uniform over the workgroup)
     for (unsigned e = tid; e < (unsigned)(u.N * p); e += blockDim.x) { vb[e] = 0.0; yb[e] = 0.0; }
     return;
   }

@@ -27,8 +27,8 @@ enum : unsigned char { LIN_UNBOUNDED = 0, LIN_FREE = 1, LIN_AT_LO = 2, LIN_AT_HI
 // Start of a constrained adjoint. Per knot: the codes from the forward's v (vf) and the bounds, v = y = 0, and S^' (the
 // SHIFTED records rec) on the knot's rows of the adjoint's resident right-hand side `res` -- the packed g on entry, S^' g
 // on exit, in place -- which both ADMM right-hand sides receive; the pad entries and the knots k >= u.N are copied. Status
-// and iteration count of every problem: 3 (not iterated) where the forward ended so, else 0 and one more in the running
-// count.
+// and iteration count of every problem: 3 (not iterated) where the forward ended so or as 4 (certified infeasible), else
+// 0 and one more in the running count.
 //   grid (d.N, batch), block 64, dynamic LDS lin_wave_lds(n, m, p) doubles.
 static __global__ __launch_bounds__(64) void lin_adjoint_start(Dims u, Dims d, int p, const double* __restrict__ rec,
                                                                const double* __restrict__ lo, const double* __restrict__ hi,
@@ -42,7 +42,7 @@ static __global__ __launch_bounds__(64) void lin_adjoint_start(Dims u, Dims d, i
   const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
   const int n = u.n, m = u.m;
   if (k == 0 && lane == 0) {
-    const int st = fstatus[b] == 3 ? 3 : 0;
+    const int st = (fstatus[b] == 3 || fstatus[b] == 4) ? 3 : 0;  // (certified infeasible: nothing to differentiate)
     status[b] = st;
     iters[b] = 0;
     if (st == 0) atomicAdd(running, 1);
