@@ -364,6 +364,10 @@ int ndlqr_hip_cholesky_failures(NdlqrHipCtx* ctx);
  * "generic-reduced-records", "generic-lean",
  * "generic-strict", "generic-keep" (DESIGN.md section 3). */
 const char* ndlqr_hip_schedule(const NdlqrHipCtx* ctx);
+/* 1 when the last solve wrote compact records (the Cholesky factor alone, packed) for the level-1 separators as well
+ * as for level 0 ("reduced" / "reduced-fused2" at the instances where that is the default; NDLQR_COMPACT1=1/0), else 0:
+ * the schedule name does not tell. */
+int ndlqr_hip_compact_level1(const NdlqrHipCtx* ctx);
 
 /* Per-kernel profile (NDLQR_FLAG_PROFILE): HIP-event durations accumulated since the last
  * reset, one slot per kernel kind. Returns number of slots / fills name, total ms, launches. */

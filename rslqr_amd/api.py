@@ -334,6 +334,8 @@ def lib():
     proto("ndlqr_hip_upload_inputs", ci, vp, ci, ci, dp, dp, dp)
     proto("ndlqr_hip_factors_valid", ci, vp)
     proto("ndlqr_hip_schedule", C.c_char_p, vp)
+    if hasattr(L, "ndlqr_hip_compact_level1"):  # (an older build loaded through NDLQR_LIBRARY for an A/B has none)
+        proto("ndlqr_hip_compact_level1", C.c_int, vp)
     proto("ndlqr_hip_set_pipeline_depth", ci, vp, ci)
     proto("ndlqr_hip_pipeline_depth", ci, vp)
     proto("ndlqr_hip_pack_solutions_device", ci, vp, vp)
@@ -1289,6 +1291,10 @@ class BatchSolver:
     def schedule(self):
         """Name of the launch sequence the last solve used."""
         return self.L.ndlqr_hip_schedule(self.ctx).decode()
+
+    def compact_level1(self):
+        """True when the last solve kept only the packed Cholesky factor of the level-1 separators (NDLQR_COMPACT1)."""
+        return hasattr(self.L, "ndlqr_hip_compact_level1") and bool(self.L.ndlqr_hip_compact_level1(self.ctx))
 
     def set_pipeline_depth(self, depth):
         """1: stream-ordered solves; 2: consecutive asynchronous solves alternate between two buffer sets."""

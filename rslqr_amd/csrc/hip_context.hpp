@@ -63,6 +63,7 @@ struct KeptState {
                               // separators in the slack of those slots): the re-solve is rb_forward / rb_forward_top / rb_backsub
   bool fact_valid = false;    // the device holds a complete factorisation (last solve ran with KEEP_FACT)
   const char* schedule = "none";  // name of the launch sequence the last solve used (ndlqr_hip_schedule)
+  bool rec1_compact = false;      // ... and it left compact level-1 records (SmallPlan::compact1; ndlqr_hip_compact_level1)
   // the records / factors no longer belong to the resident inputs: the re-solves refuse until the next solve
   void forget_factorisation() { rec_complete = fact_valid = false; }
 };
@@ -193,6 +194,7 @@ struct DevKnobs {
   int tree = -1;  // tree schedule (bottom_reduced_mc<TREE>: one launch for the whole factorisation, wavefronts climbing on arrival counters): NDLQR_TREE=1 always, 0 never, unset (-1): when all bottom wavefronts are resident at once (small batches: fewer launches win; large ones: a launch per level is faster)
   int backsub_cols = -1;  // rb_backsub at nstates + ninputs <= 16: the body with [A | B] in registers (rb_backsub_cols, block 128) unless NDLQR_BACKSUB_COLS=0 asks for the LDS-staged one
   int fuse2 = -1;  // tree level 2 inside the bottom launch (bottom8_reduced_mc) instead of as a launch of its own: NDLQR_FUSE2=1 always, 0 never, unset (-1): where it measured faster -- the (12,4) instance (launch_small.hpp)
+  int compact1 = -1;  // compact records (L alone, packed) for the level-1 separators too, substituted with by rb_backsub_cols: NDLQR_COMPACT1=1 wherever the kernels exist, 0 never, unset (-1): where it measured faster (launch_small.hpp)
   int pipeline = 2;         // NDLQR_PIPELINE: the pipeline depth a context starts with (NdlqrHipCtx::pipeline)
   bool no_top = false;      // NDLQR_NO_TOP=1: the last three tree levels as launches of their own (A/B timing of reduced_top_mc)
   int top_levels = 3;       // tree levels inside reduced_top_mc (NDLQR_TOP_LEVELS, 3 .. 5): beyond three a wavefront takes several separators of the first ones in turn

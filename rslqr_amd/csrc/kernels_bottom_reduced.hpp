@@ -762,14 +762,15 @@ __device__ __forceinline__ void reduced_eliminate_tail_mc(const Dims& d, const i
 // second read of [A | B] are gone; m's own pushes to the separators k0 - 1 and k0 + 7 follow the groups' plain stores
 // as atomic adds (the groups' stores are acknowledged before the barrier), like those of a level launch.
 //   grid (N / 8, batch), block 128; N >= 16 (a level-3 separator exists); compact level-0 records.
-template <int NX, int NU, bool TREE, bool REDIRECT>
+template <int NX, int NU, bool TREE, bool REDIRECT, bool C1 = false>
 __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, const int b, const int lane,
                                                 const double* __restrict__ AB, const double* __restrict__ QR,
                                                 const double* __restrict__ rhs, double* red, double* __restrict__ rec,
                                                 double* F, int* __restrict__ info, const int store_l, const int compact0,
                                                 ReducedLds<NX, NU>& lds, double* slotA, double* slotB,
                                                 const bool with_m = false, acc4_t* c_m = nullptr);  // (below)
-template <int NX, int NU>
+// C1: compact records for the level-1 separators too (bottom_group_mc); m keeps its full record.
+template <int NX, int NU, bool C1 = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void bottom8_reduced_mc(
     Dims d, const double* __restrict__ AB, const double* __restrict__ QR, const double* __restrict__ rhs, double* red,
     double* __restrict__ rec, int* __restrict__ info) {
@@ -783,7 +784,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void b
   for (int e = threadIdx.x; e < RedSlot<NX>::SIZE; e += 128) mslot[e] = 0.0;
   __syncthreads();
   acc4_t c_m = {0.0, 0.0, 0.0, 0.0};  // leaf tile of m (the first wavefront: it has [A_m | B_m] staged)
-  bottom_group_mc<NX, NU, false, true>(d, kw + 4 * wave, b, lane, AB, QR, rhs, red, rec, nullptr, info, 0, 1, lds[wave],
+  bottom_group_mc<NX, NU, false, true, C1>(d, kw + 4 * wave, b, lane, AB, QR, rhs, red, rec, nullptr, info, 0, 1, lds[wave],
                                        wave == 1 ? mslot : nullptr, wave == 0 ? mslot : nullptr, wave == 0, &c_m);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's plain stores to k0 - 1 / k0 + 7 are acknowledged
   __syncthreads();
@@ -859,7 +860,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 // The four knots k0 .. k0 + 3 of problem b by one wavefront: leaf phase + tree levels 0 and 1 (body of bottom_reduced_mc
 // and of bottom8_reduced_mc). slotA / slotB: where the group's pushes to the separators k0 - 1 / k0 + 3 go instead of
 // their slots in `red` (bottom8_reduced_mc: the level-2 separator between its two groups lives in LDS); null: `red`.
-template <int NX, int NU, bool TREE, bool REDIRECT>
+template <int NX, int NU, bool TREE, bool REDIRECT, bool C1>
 __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, const int b, const int lane,
                                                 const double* __restrict__ AB, const double* __restrict__ QR,
                                                 const double* __restrict__ rhs, double* red, double* __restrict__ rec,
@@ -1079,6 +1080,28 @@ __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, con
     if (slotA) sa.p = slotA;
     if (slotB) sb.p = slotB;
   }
+  if constexpr (C1) {
+    // compact record for t as well: the Y-only pass of the level-0 pair with both halves on c_t (DPP rows 2-3 repeat rows
+    // 0-1: no unit vectors, no W tile, no X = W'Y); the record is L_t, packed, at the start of t's slot, and the Gram
+    // products read Y from the LDS tiles like the level-0 hooks. rb_backsub_cols<C1> substitutes with L_t.
+    static_assert(!TREE, "the tree schedule keeps full records");
+    if (chol_pair_y_mc<NX>(lane, c_t, c_t, lds.buf, wcol, myrec + REC, myrec + REC) && lane == 0) flag_failure(info, d, b);
+    SEG(34);
+    using PY = McPairYLayout<NX>;
+    double y0[KSN], y1[KSN];
+    acc4_t Z0 = {0.0, 0.0, 0.0, 0.0}, Z1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < KSN; ++q) {
+      y0[q] = lds.buf[PY::tile(0, 0) + (4 * q + lk) * PY::YP + li];
+      y1[q] = lds.buf[PY::tile(0, 1) + (4 * q + lk) * PY::YP + li];
+      Z0[q] = y0[q]; Z1[q] = y1[q];
+    }
+    acc4_t g00, g01, g11;
+    gram_mc<NX, true, true, false, true>(y0, y1, Z0, Z1, g00, g01, unused, g11);
+    push_mc<NX>(lane, hasA, hasB, leftchild, sa, sb, g00, g01, g11, park_a, cb_t, park_b11, StorePlain(), StorePlain());
+    SEG(36);
+    return;
+  }
   if (chol_wy_mc<NX>(lane, c_t, lds.buf, wcol, lstore_of<NX>(store_l, F, rec, d, b, 1, k0 + 1)) && lane == 0)
     flag_failure(info, d, b);
   tail_wy_mc<NX>(lane, lds.buf, X0, X1,
@@ -1102,15 +1125,16 @@ __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, con
 
 // COMPACT: the instantiation of the default schedule (compact level-0 records: `compact0` is taken as 1 and the
 // full-record path is not compiled in -- 104 instead of 126 VGPRs at (12,4), no spills at (13,4) and (15,2)).
-template <int NX, int NU, bool TREE, bool COMPACT = false>
+// C1 (with COMPACT): compact level-1 records as well.
+template <int NX, int NU, bool TREE, bool COMPACT = false, bool C1 = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void bottom_reduced_mc(
     Dims d, const double* __restrict__ AB, const double* __restrict__ QR, const double* __restrict__ rhs,
     double* red, double* __restrict__ rec, double* F, int* __restrict__ info, const int store_l, int* cnt,
     const int compact0) {
-  static_assert(!(TREE && COMPACT), "the tree schedule keeps full records");
+  static_assert(!(TREE && COMPACT) && (COMPACT || !C1), "the tree schedule keeps full records");
   __shared__ ReducedLds<NX, NU> lds;
   const int lane = threadIdx.x, b = blockIdx.y, N = d.N, k0 = (blockIdx.x + d.xoff) * 4;
-  bottom_group_mc<NX, NU, TREE, false>(d, k0, b, lane, AB, QR, rhs, red, rec, F, info, store_l, COMPACT ? 1 : compact0, lds,
+  bottom_group_mc<NX, NU, TREE, false, C1>(d, k0, b, lane, AB, QR, rhs, red, rec, F, info, store_l, COMPACT ? 1 : compact0, lds,
                                        nullptr, nullptr);
 
   if constexpr (TREE) {

@@ -791,35 +791,64 @@ __device__ __forceinline__ double rb_rcp(const double x) {
 //   products cross LDS once (lds.prod, in the bytes of the records of level 1 / 2, which are spent by then) and lane r
 //   adds up row r -- a transposed sum; fp64 DPP on gfx950 has row_newbcast alone, a butterfly of 32-bit moves and
 //   selects costs twice the instructions. The four substitutions run where the sums land. Three workgroup barriers.
+//
+// C1 (compact level-1 records: the records of first + 1 and first + 5 hold L_t, packed, like those of level 0). The
+//   eight knots are a block-tridiagonal system of their own between y(first - 1), y(first + 3) and y(first + 7), and every
+//   step of it is the level-0 step above -- v(s) = [A_s | B_s] z-hat(s) - r_a y(s-1) - wv(s+1), y(s) = L^-T L^-1 v(s) --
+//   run in the rows where the columns of knot s lie, with the factor of that separator:
+//     round 1, wavefront 0: u(s) for s = first + 0, 2, 4, 6 with y(first + 1) = y(first + 5) = 0;
+//     round 2, wavefront 1 (rows 0 and 2): y(t) = L_t^-T L_t^-1 v(t) for t = first + 1, first + 5, v(t) formed from
+//              u(t - 1) and u(t + 1) -- S-bar_t is the Schur complement of exactly that elimination;
+//     round 3, wavefront 0: round 1 again with y(t) in place: the multipliers of the level-0 separators.
+//   Five workgroup barriers instead of three; nothing is loaded that the kernel did not load before. A wavefront fetches
+//   its factors from LDS once, scaled to a unit diagonal (L = L~ D: y = L~^-T D^-2 L~^-1 v), so that a substitution step
+//   is one DPP FMA; wavefront 0 uses its four factors in rounds 1 and 3.
 constexpr int kRbBacksubColsThreads = 128;
 
-template <int NX, int NU>
-struct alignas(16) RbBacksubColsLds {
+template <int NX, bool C1>
+struct RbBacksubColsC1 {};
+template <int NX>
+struct RbBacksubColsC1<NX, true> {
+  double wu[4][NX];  // round 2: what wv holds for the odd knots, of the even knots, with u in the place of y
+};
+
+template <int NX, int NU, bool C1 = false>
+struct alignas(16) RbBacksubColsLds : RbBacksubColsC1<NX, C1> {
   static constexpr int NN = NX * NX, REC = 2 * NN + NX, R0 = NX * (NX + 1) / 2;
   static constexpr int R0P = (R0 + 1) / 2 * 2, RECP = REC + (REC & 1);
   static constexpr int TS = 17;  // row pitch of the products: odd, the sixteen lanes of a row read sixteen banks
-  double rec0[4][R0P];    // level-0 separators first + 0, 2, 4, 6: Cholesky factor of S-bar, packed lower triangle
+  static constexpr int NL = C1 ? 6 : 4, NF = C1 ? 1 : 3;  // packed factors / full records of a workgroup
+  // level-0 separators first + 0, 2, 4, 6 (C1: then the level-1 separators first + 1, first + 5): Cholesky factor of
+  // S-bar, packed lower triangle
+  double rec0[NL][R0P];
   union {
-    double rec1[3][RECP];  // separators first + 1, first + 3, first + 5: f_a | f_bb | z_sep
-    double prod[4][NX * TS];  // [even knot][row r][column c]: [A | B](r, c) z-hat(c)
+    double rec1[NF][RECP];  // separators first + 1, first + 3, first + 5 (C1: first + 3 alone): f_a | f_bb | z_sep
+    double prod[4][NX * TS];  // [row of the wavefront][row r][column c]: [A | B](r, c) z-hat(c)
   };
   double ys[9][NX];       // [0..6]: separators first .. first + 6; [7]: first - 1; [8]: first + 7
   double wv[4][NX];       // z(s+1).lambda + (cost(s+1) - A_{s+1}' y_{s+1}) / Q_{s+1} of the four odd knots
 };
 
-// e / SZ for e < 4 SZ (which of up to four records a staged word belongs to): three compares instead of a multiply-high
-template <int SZ>
-__device__ __forceinline__ int rec_of(const int e) { return (e >= SZ) + (e >= 2 * SZ) + (e >= 3 * SZ); }
+// e / SZ for e < NR SZ (which of up to NR records a staged word belongs to): compares instead of a multiply-high
+template <int SZ, int NR = 4>
+__device__ __forceinline__ int rec_of(const int e) {
+  int q = 0;
+#pragma unroll
+  for (int r = 1; r < NR; ++r) q += e >= r * SZ;
+  return q;
+}
 
-template <int NX, int NU, bool MULTI>
+template <int NX, int NU, bool MULTI, bool C1 = false>
 __device__ __forceinline__ void rb_backsub_cols(const Dims& d, const double* __restrict__ AB, const double* __restrict__ QR,
                                                 const double* __restrict__ rhs, const double* __restrict__ recs,
                                                 const double* __restrict__ ytop, double* __restrict__ z,
                                                 const int nprob, const double* __restrict__ zsep) {
-  using Lds = RbBacksubColsLds<NX, NU>;
+  using Lds = RbBacksubColsLds<NX, NU, C1>;
   constexpr int W = NX + NU, ROWS = 2 * NX + NU, NN = NX * NX, REC = 2 * NN + NX, KPB = 8, R0 = Lds::R0, TS = Lds::TS;
   constexpr int NT = kRbBacksubColsThreads;  // two wavefronts (four measured slower at every instance: DESIGN.md section 7)
-  static_assert(W <= 16 && NT == 128 && 3 * NX <= NT, "thread roles fit the workgroup");
+  constexpr int NL = Lds::NL, NF = Lds::NF;
+  static_assert(W <= 16 && NT == 128 && 4 * NX <= NT, "thread roles fit the workgroup");
+  static_assert(!(C1 && MULTI), "the kept records (multi-rhs) are never compact at level 1");
   __shared__ Lds lds;
   const int N = d.N, b = blockIdx.y, first = (blockIdx.x + d.xoff) * KPB;
   const int bp = MULTI ? b % nprob : b;  // the problem whose inputs and records this right-hand side is solved against
@@ -840,19 +869,20 @@ __device__ __forceinline__ void rb_backsub_cols(const Dims& d, const double* __r
     const double* rc0 = recs + ((size_t)bp * N + first) * REC;
     constexpr bool WIDE = NX % 2 == 0 && R0 % 2 == 0;
     constexpr int G = WIDE ? 2 : 1;                                             // doubles per record load
-    constexpr int N0 = 4 * R0 / G, I0 = (N0 + NT - 1) / NT, N1 = 3 * REC / G, I1 = (N1 + NT - 1) / NT;
+    constexpr int N0 = NL * R0 / G, I0 = (N0 + NT - 1) / NT, N1 = NF * REC / G, I1 = (N1 + NT - 1) / NT;
     double t0[I0][G], t1[I1][G];
 #pragma unroll
     for (int it = 0; it < I0; ++it) {
-      const int e = t + NT * it, ec = e < N0 ? e : N0 - 1, q = rec_of<R0 / G>(ec), w_ = ec - q * (R0 / G);
-      const double* src = rc0 + (size_t)(2 * q) * REC + G * w_;
+      const int e = t + NT * it, ec = e < N0 ? e : N0 - 1, q = rec_of<R0 / G, NL>(ec), w_ = ec - q * (R0 / G);
+      const int ko = (!C1 || q < 4) ? 2 * q : 4 * q - 15;  // knots 0, 2, 4, 6, then (C1) 1 and 5
+      const double* src = rc0 + (size_t)ko * REC + G * w_;
       if constexpr (WIDE) { const double2 v = *reinterpret_cast<const double2*>(src); t0[it][0] = v.x; t0[it][1] = v.y; }
       else t0[it][0] = *src;
     }
 #pragma unroll
     for (int it = 0; it < I1; ++it) {
-      const int e = t + NT * it, ec = e < N1 ? e : N1 - 1, q = rec_of<REC / G>(ec), w_ = ec - q * (REC / G);
-      const double* src = rc0 + (size_t)(2 * q + 1) * REC + G * w_;
+      const int e = t + NT * it, ec = e < N1 ? e : N1 - 1, q = rec_of<REC / G, NF>(ec), w_ = ec - q * (REC / G);
+      const double* src = rc0 + (size_t)(C1 ? 3 : 2 * q + 1) * REC + G * w_;
       if constexpr (WIDE) { const double2 v = *reinterpret_cast<const double2*>(src); t1[it][0] = v.x; t1[it][1] = v.y; }
       else t1[it][0] = *src;
     }
@@ -868,13 +898,13 @@ __device__ __forceinline__ void rb_backsub_cols(const Dims& d, const double* __r
     }
 #pragma unroll
     for (int it = 0; it < I0; ++it) {
-      const int e = t + NT * it, ec = e < N0 ? e : N0 - 1, q = rec_of<R0 / G>(ec), w_ = ec - q * (R0 / G);
+      const int e = t + NT * it, ec = e < N0 ? e : N0 - 1, q = rec_of<R0 / G, NL>(ec), w_ = ec - q * (R0 / G);
 #pragma unroll
       for (int h = 0; h < G; ++h) lds.rec0[q][G * w_ + h] = t0[it][h];
     }
 #pragma unroll
     for (int it = 0; it < I1; ++it) {
-      const int e = t + NT * it, ec = e < N1 ? e : N1 - 1, q = rec_of<REC / G>(ec), w_ = ec - q * (REC / G);
+      const int e = t + NT * it, ec = e < N1 ? e : N1 - 1, q = rec_of<REC / G, NF>(ec), w_ = ec - q * (REC / G);
       // (MULTI: the records carry the z_sep of whatever right-hand side was solved last; this one's come from zsep.
       //  WIDE: 2 NN is even, no word holds both an entry of f_bb and one of z_sep)
       if (!MULTI || G * w_ < 2 * NN) {
@@ -883,6 +913,9 @@ __device__ __forceinline__ void rb_backsub_cols(const Dims& d, const double* __r
       }
     }
     if (t < 2 * NX) lds.ys[t < NX ? 7 : 8][t < NX ? t : t - NX] = ty;
+    if constexpr (C1) {  // round 1 runs with y(first + 1) = y(first + 5) = 0
+      if (t >= 2 * NX && t < 4 * NX) lds.ys[t < 3 * NX ? 1 : 5][t < 3 * NX ? t - 2 * NX : t - 3 * NX] = 0.0;
+    }
     if constexpr (MULTI) {
       if (t < 3 * NX) lds.rec1[t / NX][2 * NN + t % NX] = tz;
     }
@@ -897,6 +930,108 @@ __device__ __forceinline__ void rb_backsub_cols(const Dims& d, const double* __r
     for (int r = 0; r < NX; ++r) s = fma(a[r], y[r], s);
     return s;
   };
+  if constexpr (C1) {
+    // ---- compact level-1 records: three rounds of the level-0 step (see above)
+    // row c and column c of the unit-diagonal factor L~ = L D^-1 of the separator of this lane's DPP row, from the packed
+    // L at Lp; returns 1 / L(c, c)^2. (The loads are not clamped: row c read to entry NX - 1 and column c read from row 0
+    // stay inside the NX (NX + 1) / 2 doubles of the factor; the selects drop what is not of the triangle.)
+    auto load_l = [&](const double* Lp, double (&lrow)[NX], double (&lcol)[NX]) {
+      const double* rowp = Lp + cx * (cx + 1) / 2;
+      double dinv = rb_rcp(rowp[cx]);
+      dpp_fence(dinv);
+      sfor<NX>([&](auto ec) {
+        constexpr int e = decltype(ec)::value;
+        const double de = row_bc<e>(dinv);  // 1 / L(e, e)
+        const double lo = rowp[e] * de;                       // L~(c, e), e < c
+        const double up = Lp[e * (e + 1) / 2 + cx] * dinv;    // L~(e, c), e > c
+        lrow[e] = (e < c && c < NX) ? lo : 0.0;
+        lcol[e] = (e > c && c < NX) ? up : 0.0;
+      });
+      return dinv * dinv;
+    };
+    // v = [A_s | B_s] z-hat(s) - r_a y_{s-1} - wvp for the knot of this row, then y = L^-T L^-1 v. (All 64 lanes run it
+    // -- DPP needs them active --, lanes c >= NX idle.)
+    auto sep_step = [&](const double (&lrow)[NX], const double (&lcol)[NX], const double d2, const double* wvp) {
+      const double ya = (i > 0 && c < NX) ? lds.ys[k > 0 ? k - 1 : 7][cx] : 0.0;
+      const double zh = (i == 0 && c < NX) ? -tl : (tg + ya) * qinv;
+      if (c < W) {
+#pragma unroll
+        for (int r = 0; r < NX; ++r) lds.prod[j][r * TS + c] = a[r] * zh;
+      }
+      wave_lds_sync();
+      const double* pr = lds.prod[j] + cx * TS;
+      double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+      for (int m = 0; m + 1 < W; m += 2) { v0 += pr[m]; v1 += pr[m + 1]; }
+      if constexpr (W % 2) v0 += pr[W - 1];
+      double x = (v0 + v1) - wvp[cx];
+      sfor<NX - 1>([&](auto cc) {  // forward, unit diagonal: entry c is final when step c starts
+        constexpr int e = decltype(cc)::value;
+        dpp_fence(x);
+        fnmac_bc<e>(x, x, lrow[e]);
+      });
+      x = x * d2;
+      sfor<NX - 1>([&](auto cc) {  // backward, descending
+        constexpr int e = NX - 1 - decltype(cc)::value;
+        dpp_fence(x);
+        fnmac_bc<e>(x, x, lcol[e]);
+      });
+      return x;
+    };
+    double lrow[NX], lcol[NX];
+    double d2;
+    if (odd) {
+      // wavefront 1: the level-2 separator from its record; the dots of knots first + 3 and first + 7, whose multipliers
+      // are known then; wv for round 1 (y_t = 0: knots first + 1 and first + 5 add no dot)
+      const bool left = first > 0, right = first + KPB < N;
+      if (j == 1 && c < NX) {
+        const double* rc = lds.rec1[0];
+        double s = rc[2 * NN + c];
+        if (left) {
+#pragma unroll
+          for (int e = 0; e < NX; ++e) s = fma(-rc[c * NX + e], lds.ys[7][e], s);
+        }
+        if (right) {
+#pragma unroll
+          for (int e = 0; e < NX; ++e) s = fma(-rc[NN + c * NX + e], lds.ys[8][e], s);
+        }
+        lds.ys[3][c] = s;
+      }
+      wave_lds_sync();
+      if ((j & 1) && i < N - 1) dot = ab_dot(lds.ys[k < 7 ? k : 8]);
+      if (c < NX) lds.wv[j][c] = tl + (tg - dot) * qinv;
+      d2 = load_l(lds.rec0[4 + (j >> 1)], lrow, lcol);  // L_t (rows 1 and 3 run along on it; their results are dropped)
+    } else {
+      d2 = load_l(lds.rec0[j], lrow, lcol);
+    }
+    __syncthreads();
+    if (!odd) {  // round 1: u of the four level-0 separators, and what knots first + 2 and first + 6 add to v(t)
+      const double x = sep_step(lrow, lcol, d2, lds.wv[j]);
+      if (c < NX) lds.ys[k][c] = x;
+      wave_lds_sync();
+      const double du = ab_dot(lds.ys[k]);
+      if (c < NX) lds.wu[j][c] = tl + (tg - du) * qinv;
+    }
+    __syncthreads();
+    if (odd) {  // round 2: y_t in rows 0 and 2
+      const double x = sep_step(lrow, lcol, d2, lds.wu[(j + 1) & 3]);
+      if ((j & 1) == 0) {
+        if (c < NX) lds.ys[k][c] = x;
+      }
+      wave_lds_sync();
+      if ((j & 1) == 0) {
+        dot = ab_dot(lds.ys[k]);
+        if (c < NX) lds.wv[j][c] = tl + (tg - dot) * qinv;
+      }
+    }
+    __syncthreads();
+    if (!odd) {  // round 3: the level-0 separators with y_t in place
+      const double x = sep_step(lrow, lcol, d2, lds.wv[j]);
+      if (c < NX) lds.ys[k][c] = x;
+      wave_lds_sync();
+      dot = ab_dot(lds.ys[k]);
+    }
+  } else {
   if (odd) {
     // ---- wavefront 1: multipliers of the local separators of level 2, then 1
     auto resolve = [&](const int q, const bool hasA, const int slotA, const bool hasB, const int slotB) {
@@ -955,6 +1090,7 @@ __device__ __forceinline__ void rb_backsub_cols(const Dims& d, const double* __r
     wave_lds_sync();
     dot = ab_dot(lds.ys[k]);  // (an even knot is never the last one)
   }
+  }
   __syncthreads();
 
   // ---- solution rows: lambda(c), then x(c) / u(c)
@@ -969,12 +1105,14 @@ __device__ __forceinline__ void rb_backsub_cols(const Dims& d, const double* __r
 }
 
 // COLS: rb_backsub_cols (NX + NU <= 16 only), block kRbBacksubColsThreads; else rb_backsub_staged, block 256
-template <int NX, int NU, bool MULTI = false, bool COLS = false>
+// C1 (COLS only): the records of the level-1 separators are compact too (rb_backsub_cols)
+template <int NX, int NU, bool MULTI = false, bool COLS = false, bool C1 = false>
 __global__ __launch_bounds__(COLS ? kRbBacksubColsThreads : 256) void rb_backsub(
     Dims d, const double* __restrict__ AB, const double* __restrict__ QR, const double* __restrict__ rhs,
     const double* __restrict__ recs, const double* __restrict__ ytop, double* __restrict__ z, const int nprob = 0,
     const double* __restrict__ zsep = nullptr) {
-  if constexpr (COLS) rb_backsub_cols<NX, NU, MULTI>(d, AB, QR, rhs, recs, ytop, z, nprob, zsep);
+  static_assert(COLS || !C1, "the staged body reads full level-1 records");
+  if constexpr (COLS) rb_backsub_cols<NX, NU, MULTI, C1>(d, AB, QR, rhs, recs, ytop, z, nprob, zsep);
   else rb_backsub_staged<NX, NU, MULTI>(d, AB, QR, rhs, recs, ytop, z, nprob, zsep);
 }
 

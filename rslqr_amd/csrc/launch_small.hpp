@@ -29,6 +29,7 @@ struct SmallPlan {
   bool compact;  // ... with compact level-0 records and the two-launch back-substitution (kernels_rowbcast.hpp)
   bool rowbcast; // ... and the bottom levels on the row-broadcast core (four separators per wavefront)
   bool fuse2;    // ... or tree level 2 inside the bottom launch (bottom8_reduced_mc)
+  bool compact1; // ... and compact records for the level-1 separators as well (rb_backsub_cols substitutes with L_t)
   int level0;    // first tree level with a launch of its own (reduced_level_mc), up to ...
   int ltop;      // ... the first one inside reduced_top_mc (== K: no such launch), which starts at ...
   int top_l0;    // ... this level (level 2 may have gone with the bottom launch)
@@ -58,9 +59,21 @@ static inline ndlqr::Dims apply_dims(const NdlqrHipCtx* c, const ndlqr::Dims& d)
 // section 3.4): the one that keeps [A | B] in registers -- the default: same-box A/B against the staged body at
 // (12,4), (10,4), (9,3), (8,4), (6,3) x 1024 and (12,4,1024) x 512, faster at each -- and,
 // with NDLQR_BACKSUB_COLS=0, the LDS-staged one that the larger instances run.
+// compact1: the level-1 records are compact too (a full solve of a plan with SmallPlan::compact1 alone).
+template <int NX, int NU>
+constexpr bool kCompact1Fits = ndlqr::P1OnMatrixCores<NX, NU>::value && NX >= 9 && NX + NU <= 16;
+
 template <int NX, int NU, bool MULTI, class... Args>
-static void launch_rb_backsub(const NdlqrHipCtx* c, const dim3 grid, hipStream_t stream, const Args&... args) {
+static void launch_rb_backsub(const NdlqrHipCtx* c, const dim3 grid, hipStream_t stream, const bool compact1,
+                              const Args&... args) {
   if constexpr (NX + NU <= 16) {
+    if constexpr (kCompact1Fits<NX, NU> && !MULTI) {
+      if (compact1) {
+        hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, false, true, true>), grid, dim3(ndlqr::kRbBacksubColsThreads), 0, stream,
+                           args...);
+        return;
+      }
+    }
     if (c->knobs.backsub_cols != 0) {
       hipLaunchKernelGGL((ndlqr::rb_backsub<NX, NU, MULTI, true>), grid, dim3(ndlqr::kRbBacksubColsThreads), 0, stream, args...);
       return;
@@ -114,6 +127,17 @@ static SmallPlan plan_small(const NdlqrHipCtx* c, const bool strict, const bool 
       // profiles/r04_fuse2_ab.txt: (12,4,256) x 1024 0.587 -> 0.579 ms, (12,4,1024) x 512 1.20 -> 1.16, the padded (11,3)
       // 0.578 -> 0.569; (12,8) +2.5 %, (13,4) +0.9 %, (9,3) / (10,4) / (15,2) +-0). NDLQR_FUSE2=0 / 1 overrides.
       p.fuse2 = !p.rowbcast && p.compact && !p.store_l && (c->knobs.fuse2 > 0 || (c->knobs.fuse2 < 0 && NX == 12 && NU == 4));
+      // Compact level-1 records: the bottom launch drops W = L^-1, X = W'Y and three quarters of the record stores of
+      // its level-1 separators, rb_backsub_cols reads 78 instead of 300 doubles for each and substitutes three times in
+      // turn instead of once. Only with the matrix-core bottom kernel and the column back-substitution (n >= 9,
+      // n + m <= 16). The default where the slowest of five runs was below the parent's fastest on the same box
+      // (profiles/compact1_ab.txt): the (12,4) instance on its default schedule (fused level 2) -- (12,4,256) x 1024
+      // 0.537-0.548 -> 0.527-0.533 ms, (12,4,1024) x 512 1.146-1.162 -> 1.072-1.078, the padded (11,3) 0.535-0.539 ->
+      // 0.518-0.522 -- and (10,4): 0.473-0.475 -> 0.448-0.456; (9,3) 0.389-0.391 -> 0.383-0.389 touches the parent's range
+      // and stays off. NDLQR_COMPACT1=0 / 1 overrides.
+      p.compact1 = kCompact1Fits<NX, NU> && p.compact && !p.store_l && !p.rowbcast && c->knobs.backsub_cols != 0 &&
+                   (c->knobs.compact1 > 0 ||
+                    (c->knobs.compact1 < 0 && ((NX == 12 && NU == 4 && p.fuse2) || (NX == 10 && NU == 4))));
       p.schedule = p.tree ? "reduced-tree"
                    : !p.compact ? "reduced-records"
                    : p.store_l ? "reduced-compact-records" : (p.fuse2 ? "reduced-fused2" : "reduced");
@@ -152,15 +176,33 @@ static int launch_small(NdlqrHipCtx* c, const SmallPlan& plan) {
             hipLaunchKernelGGL((ndlqr::rb_bottom<NX, NU>), dim3(d.N >> 4, d.batch), dim3(64), 0, s.stream, d, c->AB,
                                c->QR, s.rhs, s.red, s.rec, c->info);
         } else if (plan.fuse2) {
-          hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream, d,
-                             c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
+          bool done = false;
+          if constexpr (kCompact1Fits<NX, NU>) {
+            if (plan.compact1) {
+              hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU, true>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream, d,
+                                 c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
+              done = true;
+            }
+          }
+          if (!done)
+            hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream, d,
+                               c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
         } else if (plan.tree)
           hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
                              d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, s.tree_cnt, 0);
-        else if (plan.compact)
-          hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
-                             d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, nullptr, 1);
-        else
+        else if (plan.compact) {
+          bool done = false;
+          if constexpr (kCompact1Fits<NX, NU>) {
+            if (plan.compact1) {
+              hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false, true, true>), dim3(d.N >> 2, d.batch), dim3(64), 0,
+                                 s.stream, d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, nullptr, 1);
+              done = true;
+            }
+          }
+          if (!done)
+            hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false, true>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
+                               d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, nullptr, 1);
+        } else
           hipLaunchKernelGGL((ndlqr::bottom_reduced_mc<NX, NU, false>), dim3(d.N >> 2, d.batch), dim3(64), 0, s.stream,
                              d, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, nullptr, 0);
       }
@@ -181,7 +223,7 @@ static int launch_small(NdlqrHipCtx* c, const SmallPlan& plan) {
           hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), plan.top_lds, s.stream, d, s.rec, s.ytop);
         }
         // (an MPC step that asked for nothing but a knot range -- NDLQR_SOLN_ONLY -- runs the workgroups of that range)
-        launch_rb_backsub<NX, NU, false>(c, dim3(apply_grid(c, d), d.batch), s.stream,
+        launch_rb_backsub<NX, NU, false>(c, dim3(apply_grid(c, d), d.batch), s.stream, plan.compact1,
                            apply_dims(c, d), c->AB, c->QR, s.rhs, s.rec, s.ytop, s.z);
       } else {
         hipLaunchKernelGGL((ndlqr::backsub_small<NX, NU>), dim3(apply_grid(c, d), d.batch), dim3(256), 0, s.stream, apply_dims(c, d), c->AB,
@@ -238,7 +280,7 @@ static void launch_rhs_records(NdlqrHipCtx* c, const double* rhs, double* z) {
                            rhs, s.rec, (const double*)s.red, s.ytop);
       }
       ScopedSlot t(c, SLOT_APPLY);
-      launch_rb_backsub<NX, NU, false>(c, dim3(apply_grid(c, d), d.batch), s.stream,
+      launch_rb_backsub<NX, NU, false>(c, dim3(apply_grid(c, d), d.batch), s.stream, false,
                          apply_dims(c, d), c->AB, c->QR, rhs, s.rec, s.ytop, z);
       return;
     }
@@ -279,7 +321,7 @@ static bool launch_multi_rhs(NdlqrHipCtx* c, const int count, const double* rhs,
     hipLaunchKernelGGL((ndlqr::rb_forward_top<NX, NU, true>), dim3(count), dim3(256), lds, s.stream, d, c->AB, c->QR, rhs,
                        s.rec, (const double*)fsum, ytop, d.batch, zsep);
     // (a knot range alone: ndlqr_hip_solve_multi_rhs_slices)
-    launch_rb_backsub<NX, NU, true>(c, dim3(apply_grid(c, d), count), s.stream,
+    launch_rb_backsub<NX, NU, true>(c, dim3(apply_grid(c, d), count), s.stream, false,
                        apply_dims(c, d), c->AB, c->QR, rhs, (const double*)s.rec, (const double*)ytop, z, d.batch,
                        (const double*)zsep);
     return true;
@@ -349,7 +391,7 @@ static int launch_time_shard(NdlqrHipCtx* c, const int phase, const int g, const
       hipLaunchKernelGGL((ndlqr::rb_backsub_top<NX>), dim3(d.batch), dim3(256), top_lds, bs.stream, d, bs.rec, bs.ytop);
       const int cnt = (d.N >> 3) / G;
       d.xoff = g * cnt;
-      launch_rb_backsub<NX, NU, false>(c, dim3(cnt, d.batch), bs.stream, d, c->AB, c->QR,
+      launch_rb_backsub<NX, NU, false>(c, dim3(cnt, d.batch), bs.stream, false, d, c->AB, c->QR,
                          bs.rhs, bs.rec, bs.ytop, bs.z);
     }
     c->kept.schedule = "reduced-time-shard";

@@ -16,10 +16,11 @@ HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (MI355X_MICROARCH.md; ~6300 a
 FP64_PEAK_TFLOPS = 78.6   # dense fp64: matrix-core rate = vector rate on gfx950 (same guide)
 
 
-def record_doubles(n, level, compact_level0=False):
+def record_doubles(n, level, compact_level0=False, compact_level1=False):
     """Separator record f_a | f_bb | z_sep (2 n^2 + n). With the compact level-0 records of the
-    row-broadcast schedule a level-0 separator keeps only the packed inverse factor (n (n+1) / 2)."""
-    if compact_level0 and level == 0:
+    row-broadcast schedule a level-0 separator keeps only the packed inverse factor (n (n+1) / 2);
+    with compact level-1 records (NDLQR_COMPACT1) a level-1 separator keeps its packed factor alone too."""
+    if (compact_level0 and level == 0) or (compact_level1 and level == 1):
         return n * (n + 1) // 2
     return 2 * n * n + n
 
@@ -51,25 +52,28 @@ def compulsory_bytes(n, m, N):
     return 8 * (inputs_doubles(n, m, N) + N * (2 * n + m))
 
 
-def reduced_model(n, m, N, compact_level0=False, fused2=False):
+def reduced_model(n, m, N, compact_level0=False, fused2=False, compact_level1=False):
     """Separator-only ("reduced") schedule of the size-specialised shapes: bottom kernel (leaf phase +
     tree levels 0, 1), one launch per upper level, back-substitution. Returns
     {slot: {"bytes": per solve, "flops": per solve, "launches": per solve}}.
     fused2 (round 4, bottom8_reduced_mc): the bottom launch also eliminates the level-2 separators, whose slots live in
     LDS -- per eight knots it stores the two groups' shares of the outer separators, adds the level-2 separator's
-    (two symmetric blocks + two vectors each, one coupling block) and writes the level-2 record."""
+    (two symmetric blocks + two vectors each, one coupling block) and writes the level-2 record.
+    compact_level1: the N / 4 level-1 separators keep their packed factor alone (written by the bottom launch, read by the
+    back-substitution); every level above keeps the full record."""
     K = int(math.log2(N))
     if fused2 and N >= 16:
-        base = reduced_model(n, m, N, compact_level0, False)
+        base = reduced_model(n, m, N, compact_level0, False, compact_level1)
         w, rows = n + m, 2 * n + m
         tri = n * (n + 1) // 2
-        rec0, rec = record_doubles(n, 0, compact_level0), record_doubles(n, 1)
+        rec0, rec = record_doubles(n, 0, compact_level0), record_doubles(n, 2)
+        rec1 = record_doubles(n, 1, compact_level0, compact_level1)
         fs = separator_flops(n, w)
         push = 2 * tri + n * n + 2 * n
         slot = 2 * tri + 2 * n * n + 2 * n
         per_sep = slot + n * w + w + n + rows + 2 * n + rec + push   # an upper-level separator in a launch of its own
         nsep2 = N // 8
-        base["bottom"] = {"bytes": 8 * (inputs_doubles(n, m, N) + (N // 2) * rec0 + (N // 4 + nsep2) * rec +
+        base["bottom"] = {"bytes": 8 * (inputs_doubles(n, m, N) + (N // 2) * rec0 + (N // 4) * rec1 + nsep2 * rec +
                                        nsep2 * (4 * (tri + n) + n * n)),
                           "flops": (3 * N // 4 + nsep2) * fs, "launches": 1}
         if "upper" in base:
@@ -87,12 +91,13 @@ def reduced_model(n, m, N, compact_level0=False, fused2=False):
     push = 2 * tri + n * n + 2 * n      # what one four-knot group / one upper separator pushes to its neighbours
     slot = 2 * tri + 2 * n * n + 2 * n  # DL | DR | CA | CB | gL | gR of one separator of level >= 2
     rec0 = record_doubles(n, 0, compact_level0)
-    rec = record_doubles(n, 1)
+    rec = record_doubles(n, 2)
+    rec1 = record_doubles(n, 1, compact_level0, compact_level1)
     fs = separator_flops(n, w)
     nsep_upper = max(N // 4 - 1, 0)
-    bottom_b = inputs_doubles(n, m, N) + (N // 2) * rec0 + (N // 4) * rec + (N // 4) * push
+    bottom_b = inputs_doubles(n, m, N) + (N // 2) * rec0 + (N // 4) * rec1 + (N // 4) * push
     upper_b = nsep_upper * (slot + n * w + w + n + rows + 2 * n + rec + push)
-    recs_read = (N // 2) * rec0 + (N // 4) * rec + nsep_upper * rec
+    recs_read = (N // 2) * rec0 + (N // 4) * rec1 + nsep_upper * rec
     # back-substitution: every record once, the inputs again, the solution; the compact form adds the
     # multipliers of the top of the tree (written by rb_backsub_top, two read per eight knots)
     apply_b = recs_read + inputs_doubles(n, m, N) + N * rows + ((N // 8) * n + (N // 8) * 2 * n if compact_level0 else 0)
@@ -198,13 +203,17 @@ def generic_reduced_model(n, m, N):
     }
 
 
-def model_for(schedule, n, m, N):
+def model_for(schedule, n, m, N, compact1=False):
     """Per-slot model of the named launch sequence (ndlqr_hip_schedule), or None when this file has no
-    model for it (strict / KEEP schedules stream the whole factor array: model (B) is their roofline)."""
+    model for it (strict / KEEP schedules stream the whole factor array: model (B) is their roofline).
+    compact1: the solve kept compact level-1 records (BatchSolver.compact_level1(); "reduced" and "reduced-fused2"
+    only). The name alone does not tell, and without the argument the model is that of full level-1 records: 1.8 KB per
+    four knots more than such a solve moves at (12,4), so the fractions it yields for `bottom` and `apply` are upper
+    bounds."""
     if schedule == "reduced":  # compact level-0 records, two-launch back-substitution
-        return reduced_model(n, m, N, compact_level0=True)
+        return reduced_model(n, m, N, compact_level0=True, compact_level1=compact1)
     if schedule == "reduced-fused2":  # ... with tree level 2 inside the bottom launch (NDLQR_FUSE2=1)
-        return reduced_model(n, m, N, compact_level0=True, fused2=True)
+        return reduced_model(n, m, N, compact_level0=True, fused2=True, compact_level1=compact1)
     if schedule in ("reduced-tree", "reduced-records"):
         return reduced_model(n, m, N)
     if schedule == "knot-lean":
