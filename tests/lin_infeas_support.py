@@ -8,6 +8,7 @@ Problems are the dicts of cost_support (math convention); rows C [N, p, n], D [N
   bounds of the tests are made of: the largest sum of absolute terms of an entry of e, and the sum of absolute terms of S.
 - admm_infeas(): lin_support.admm (fixed rho, the operation order of strict mode) with the test behind the update and the
   convergence test of iteration `it`.
+- check_kept_lambda(): a check as a function of the two iterates two cold solves deliver, through a solver handed in.
 - family_a() -- "travelling": the m input rows |u| <= ubar plus one dense row c'x_knot <= level, with level `gap` below
   (infeasible) or above (the barely feasible twin) the SMALLEST value c'x_knot takes over the input box, from the condensed
   dynamics x_k = c_k + G_k U: c'c_k - ||c'G_k||_1 ubar. (A level below the largest reachable value would exclude nothing.)
@@ -135,6 +136,41 @@ def admm_infeas(p, C, D, lo, hi, rho=RHO, alpha=ALPHA, eps_abs=EPS_ABS, eps_rel=
                 return dict(status=4, iters=it, z=z, v=v, y=y, dlam=dlam, dmu=dmu)
         lam_prev, mu_prev = lam, mu
     return dict(status=2, iters=max_iter, z=z, v=v, y=y, **zero)
+
+
+def check_kept_lambda(bs, inst, it, every, eps, settings, label=()):
+    """The body of test_kept_lambda_is_the_delivered_one (test_gpu_lin_infeas.py), shared with test_gpu_lin_shapes.py. bs:
+    a solver in constrained mode with the batch `inst` (dicts p, C, D, lo, hi), detection off. Two cold solves stopped at
+    it - 1 and it deliver the iterates whose differences a check at `it` judges; a third with a check every `every`
+    iterations (it % every == 0, no other check before it) leaves the measures: D and the infinite-side maximum bit for
+    bit, ||e||_inf within (n + p + 2) eps x the largest sum of absolute terms of an entry, S within
+    4 eps^2 sum |terms| + eps |S|. Every solve must end as status 2 at its max_iter. Returns the checks per problem."""
+    ld, eps64 = np.longdouble, np.finfo(float).eps
+    n, m, N = cs.dims(inst[0]["p"])
+    stop = []
+    for mi in (it - 1, it):
+        iters, status = bs.solve_constrained(max_iter=mi, **settings)
+        assert (iters == mi).all() and (status == 2).all()
+        stop.append((np.stack([cs.split(z, n, m, N)[0] for z in bs.solutions()]), bs.constraint_multipliers()))
+    bs.set_constraint_infeasibility(every, eps)
+    iters, status = bs.solve_constrained(max_iter=it, **settings)
+    assert (iters == it).all() and (status == 2).all()
+    meas, at = bs.constraint_infeasibility_measures()
+    bs.set_constraint_infeasibility(0)
+    assert (at == it).all()
+    p_rows = inst[0]["C"].shape[1]
+    out = []
+    for i, c in enumerate(inst):
+        dlam, dmu = stop[1][0][i] - stop[0][0][i], stop[1][1][i] - stop[0][1][i]
+        chk = farkas_check_rows(c["p"], c["C"], c["D"], c["lo"], c["hi"], dlam, dmu, eps)
+        print(*label, "problem", i, "device", ["%.17e" % x for x in meas[i]], "from the iterates",
+              ["%.17e" % float(chk[k]) for k in ("e_inf", "dmu_inf", "inf_max", "S")])
+        assert meas[i][1] == float(chk["dmu_inf"]) and chk["dmu_inf"] > 0
+        assert meas[i][2] == float(chk["inf_max"])
+        assert abs(ld(meas[i][0]) - chk["e_inf"]) <= (n + p_rows + 2) * eps64 * chk["e_scale"]
+        assert abs(ld(meas[i][3]) - chk["S"]) <= 4 * eps64 * eps64 * chk["S_scale"] + eps64 * abs(chk["S"])
+        out.append(chk)
+    return out
 
 
 def condensed(p):

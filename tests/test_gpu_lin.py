@@ -70,27 +70,26 @@ def fields(z, n, m, N):
 
 
 # ---------------------------------------------------------------------------- 1: shifted costs and records, entry by entry
-@pytest.mark.parametrize("n,m,N", CASES)
-def test_shifted_reduction_per_entry(ndlqr, n, m, N):
-    cases = ls.case(n, m, N)
+def restated_reduction(cases, dtype):
+    """the shifted costs Qs, Hs, Rs and the reduction of the shifted problem of every case, restated in `dtype`, in the
+    layout of constraint_reduction()"""
+    reds, costs = [], []
+    for c in cases:
+        ps = ls.shifted_problem(c["p"], c["C"], c["D"], c["lo"], c["hi"], ls.RHO, dtype)
+        reds.append(cs.reduce(ps, dtype))
+        costs.append(ps)
+    out = cs.reduction_flat(reds)
+    for k, name in (("Q", "Qs"), ("H", "Hs"), ("R", "Rs")):
+        a = np.stack([p[k] for p in costs])
+        out[name] = a.transpose(0, 1, 3, 2).reshape(a.shape[0], a.shape[1], -1)
+    return out
 
-    def restated(dtype):
-        reds, costs = [], []
-        for c in cases:
-            ps = ls.shifted_problem(c["p"], c["C"], c["D"], c["lo"], c["hi"], ls.RHO, dtype)
-            reds.append(cs.reduce(ps, dtype))
-            costs.append(ps)
-        out = cs.reduction_flat(reds)
-        for k, name in (("Q", "Qs"), ("H", "Hs"), ("R", "Rs")):
-            a = np.stack([p[k] for p in costs])
-            out[name] = a.transpose(0, 1, 3, 2).reshape(a.shape[0], a.shape[1], -1)
-        return out
 
-    exact, f64 = restated(np.longdouble), restated(np.float64)
-    bs = constrained_solver(ndlqr, cases)
-    bs.solve_constrained(max_iter=1, **SET)
-    got = bs.constraint_reduction()
-    bs.close()
+def check_shifted_reduction(got, cases, label):
+    """the rule of test 1: per array, the largest error against the longdouble restatement within 8 x the float64
+    restatement's own, at least 16 eps of the array's largest entry"""
+    N = cases[0]["C"].shape[0]
+    exact, f64 = restated_reduction(cases, np.longdouble), restated_reduction(cases, np.float64)
     for k in RED_NAMES:
         # (H, R of the last knot are not part of the problem: the device writes 0 and 1 there)
         cut = slice(0, N - 1) if k in ("Hs", "Rs") else slice(0, N)
@@ -98,9 +97,19 @@ def test_shifted_reduction_per_entry(ndlqr, n, m, N):
         own = float(np.abs(f - e).max())
         bar = max(8 * own, 16 * EPS * float(np.abs(e).max()))
         err = float(np.abs(g - e).max())
-        print("shifted", (n, m, N), k, "device %.3e numpy %.3e ratio to bar %.3f" % (err, own, err / bar))
+        print("shifted", label, k, "device %.3e numpy %.3e ratio to bar %.3f" % (err, own, err / bar))
         assert g.shape == e.shape and np.isfinite(g).all()
         assert err <= bar, (k, err, bar)
+
+
+@pytest.mark.parametrize("n,m,N", CASES)
+def test_shifted_reduction_per_entry(ndlqr, n, m, N):
+    cases = ls.case(n, m, N)
+    bs = constrained_solver(ndlqr, cases)
+    bs.solve_constrained(max_iter=1, **SET)
+    got = bs.constraint_reduction()
+    bs.close()
+    check_shifted_reduction(got, cases, (n, m, N))
 
 
 # ---------------------------------------------------------------------------- 2: the first iterations

@@ -215,30 +215,10 @@ def test_kept_lambda_is_the_delivered_one(ndlqr, fam, n, m, N):
     infinite-side maximum bit for bit, ||e||_inf within (n + p + 2) eps x the largest sum of absolute terms of an entry
     (its fma chain), S within 4 eps^2 sum |terms| + eps |S| (the two-term accumulator, rounded once)."""
     inst = li.instance(n, m, N, fam)
-    it = 2 * li.EVERY
     for flags in modes(ndlqr, n, m, N):
         bs = constrained_solver(ndlqr, inst, flags)
-        stop = []
-        for mi in (it - 1, it):
-            iters, status = bs.solve_constrained(max_iter=mi, **SET)
-            assert (iters == mi).all() and (status == 2).all()
-            stop.append((np.stack([cs.split(z, n, m, N)[0] for z in bs.solutions()]), bs.constraint_multipliers()))
-        bs.set_constraint_infeasibility(li.EVERY, li.EPS)
-        iters, status = bs.solve_constrained(max_iter=it, **SET)
-        assert (iters == it).all() and (status == 2).all()
-        meas, at = bs.constraint_infeasibility_measures()
+        li.check_kept_lambda(bs, inst, 2 * li.EVERY, li.EVERY, li.EPS, SET, ("kept lambda", (n, m, N), "flags", flags))
         bs.close()
-        assert (at == it).all()
-        p_rows = inst[0]["C"].shape[1]
-        for i, c in enumerate(inst):
-            dlam, dmu = stop[1][0][i] - stop[0][0][i], stop[1][1][i] - stop[0][1][i]
-            chk = li.farkas_check_rows(c["p"], c["C"], c["D"], c["lo"], c["hi"], dlam, dmu, li.EPS)
-            print("kept lambda", (n, m, N), "flags", flags, "problem", i, "device", ["%.17e" % x for x in meas[i]], "from the iterates",
-                  ["%.17e" % float(chk[k]) for k in ("e_inf", "dmu_inf", "inf_max", "S")])
-            assert meas[i][1] == float(chk["dmu_inf"]) and chk["dmu_inf"] > 0
-            assert meas[i][2] == float(chk["inf_max"])
-            assert abs(LD(meas[i][0]) - chk["e_inf"]) <= (n + p_rows + 2) * EPS * chk["e_scale"]
-            assert abs(LD(meas[i][3]) - chk["S"]) <= 4 * EPS * EPS * chk["S_scale"] + EPS * abs(chk["S"])
 
 
 # ---------------------------------------------------------------------------- 6: warm start after status 4
