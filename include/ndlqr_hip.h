@@ -368,6 +368,9 @@ const char* ndlqr_hip_schedule(const NdlqrHipCtx* ctx);
  * as for level 0 ("reduced" / "reduced-fused2" at the instances where that is the default; NDLQR_COMPACT1=1/0), else 0:
  * the schedule name does not tell. */
 int ndlqr_hip_compact_level1(const NdlqrHipCtx* ctx);
+/* 1 when the fused bottom launch of the last solve took the two level-1 separators of a workgroup through one Cholesky
+ * pass ("reduced-fused2" with compact level-1 records: the default of the (12,4) instance; NDLQR_PAIR1=1/0), else 0. The records are the same either way. */
+int ndlqr_hip_level1_paired(const NdlqrHipCtx* ctx);
 
 /* Per-kernel profile (NDLQR_FLAG_PROFILE): HIP-event durations accumulated since the last
  * reset, one slot per kernel kind. Returns number of slots / fills name, total ms, launches. */

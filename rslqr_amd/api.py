@@ -336,6 +336,8 @@ def lib():
     proto("ndlqr_hip_schedule", C.c_char_p, vp)
     if hasattr(L, "ndlqr_hip_compact_level1"):  # (an older build loaded through NDLQR_LIBRARY for an A/B has none)
         proto("ndlqr_hip_compact_level1", C.c_int, vp)
+    if hasattr(L, "ndlqr_hip_level1_paired"):
+        proto("ndlqr_hip_level1_paired", C.c_int, vp)
     proto("ndlqr_hip_set_pipeline_depth", ci, vp, ci)
     proto("ndlqr_hip_pipeline_depth", ci, vp)
     proto("ndlqr_hip_pack_solutions_device", ci, vp, vp)
@@ -1295,6 +1297,11 @@ class BatchSolver:
     def compact_level1(self):
         """True when the last solve kept only the packed Cholesky factor of the level-1 separators (NDLQR_COMPACT1)."""
         return hasattr(self.L, "ndlqr_hip_compact_level1") and bool(self.L.ndlqr_hip_compact_level1(self.ctx))
+
+    def level1_paired(self):
+        """True when the fused bottom launch of the last solve ran one Cholesky pass for the two level-1 separators of a
+        workgroup (NDLQR_PAIR1)."""
+        return hasattr(self.L, "ndlqr_hip_level1_paired") and bool(self.L.ndlqr_hip_level1_paired(self.ctx))
 
     def set_pipeline_depth(self, depth):
         """1: stream-ordered solves; 2: consecutive asynchronous solves alternate between two buffer sets."""

@@ -5,7 +5,8 @@
 //   bottom_reduced_mc   leaf phase + tree levels 0 and 1, one wavefront per four consecutive knots (bottom_group_mc)
 //                       (TREE: the wavefront climbs on through the upper levels on arrival counters)
 //   bottom8_reduced_mc  the same for eight knots per two-wavefront workgroup with tree level 2 behind it, the level-2
-//                       slot in LDS (opt-in: NDLQR_FUSE2=1)
+//                       slot in LDS (opt-in: NDLQR_FUSE2=1); <.., P1>: one Cholesky pass for the level-1 separators of
+//                       both wavefronts' groups (NDLQR_PAIR1)
 //   reduced_level_mc    one upper level, one wavefront per separator (reduced_separator_mc)
 //   reduced_top_mc      the last three levels + the top-down sweep of the back-substitution, one workgroup per problem
 //   the separator core  chol_pair_y_mc / chol_wy_mc (the Cholesky pass on the vector ALU, one row of S-bar per lane of
@@ -325,6 +326,89 @@ __device__ __forceinline__ bool chol_pair_y_mc(const int lane_in, const acc4_t& 
     }
   }
   // the record: row li of L (entries 0 .. li) by lane li of DPP rows 0 (A) and 2 (B)
+  if ((lk & 1) == 0 && li < NX) {
+    double* lr = (lk == 0 ? lrecA : lrecB) + li * (li + 1) / 2;
+#pragma unroll
+    for (int c = 0; c < NX; ++c)
+      if (c <= li) lr[c] = acc[c];
+  }
+  wave_lds_sync();
+  return bad;
+}
+
+// The same pass for the level-1 separators t0, t1 of the TWO four-knot groups of a workgroup (bottom8_reduced_mc<.., P1>):
+// with compact level-1 records the pass of one t has both halves of the wavefront on the same tile (chol_pair_y_mc(c_t, c_t)
+// above), and the two t of a workgroup are as independent of each other as s0 and s2 of one group. Every wavefront leaves
+// its t in its own buffer (pair1_exchange_mc) -- the [S-bar | b~] tile at SCR, the negated coupling tiles at TA | TB
+// (pitch TP), the rhs column b~ once more in column NX of TA, so that lane h <= NX finds its panel column at TA + h --
+// and behind a workgroup barrier ONE wavefront runs the pass: lanes 0..31 on bufA, lanes 32..63 on bufB. Each half
+// leaves Y0 = L^-1 [r_a | b~], Y1 = L^-1 r_bb at tile(0, 0) / tile(0, 1) of the buffer it read, where the group's own
+// wavefront finds them behind the next barrier. Lane for lane the arithmetic of chol_pair_y_mc's rows 0-1.
+template <int NX>
+struct McPair1Layout {
+  static constexpr int SP = McPitch<NX>::SP, TP = 17;
+  static constexpr int SCR = 0, TA = 16 * SP, TB = TA + 16 * TP, SIZE = TB + 16 * TP;
+};
+template <int NX>
+__device__ __forceinline__ void pair1_exchange_mc(const int lane_in, const acc4_t& c_t, const acc4_t& ca_t,
+                                                  const acc4_t& cb_t, double* buf) {
+  using X = McPair1Layout<NX>;
+  int lane = lane_in;
+  asm volatile("" : "+v"(lane));
+  const int li = lane & 15, lk = lane >> 4;
+  wave_lds_sync();  // (the operands of the level-0 hooks are in registers)
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    buf[X::SCR + (lk + 4 * g) * X::SP + li] = c_t[g];
+    buf[X::TA + (lk + 4 * g) * X::TP + li] = li == NX ? c_t[g] : -ca_t[g];
+    buf[X::TB + (lk + 4 * g) * X::TP + li] = -cb_t[g];
+  }
+}
+template <int NX>
+__device__ __forceinline__ bool chol_pair1_y_mc(const int lane_in, double* bufA, double* bufB, double* lrecA,
+                                                double* lrecB) {
+  using P = McPairYLayout<NX>;
+  using X = McPair1Layout<NX>;
+  constexpr int SP = P::SP, YP = P::YP, KS = P::KS;
+  static_assert(2 * P::TILE <= X::SIZE, "the Y tiles of one separator lie inside what its wavefront wrote");
+  int lane = lane_in;
+  asm volatile("" : "+v"(lane));
+  const int li = lane & 15, lk = lane >> 4, h = lane & 31;
+  const int ri = li < NX ? li : NX - 1;
+  double* buf = lk < 2 ? bufA : bufB;
+  const double* tile = buf + X::SCR;
+  double acc[NX], w[NX];
+  if constexpr (NX % 2 == 0) {
+#pragma unroll
+    for (int j = 0; j < NX; j += 2) {
+      const double2 t = *reinterpret_cast<const double2*>(&tile[ri * SP + j]);
+      acc[j] = t.x; acc[j + 1] = t.y;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < NX; ++j) acc[j] = tile[ri * SP + j];
+  }
+  {
+    const bool is_b = h > NX && h <= 2 * NX;
+    const double* src = buf + (h <= NX ? X::TA + h : X::TB + (is_b ? h - NX - 1 : 0));  // (no column: finite don't-cares)
+#pragma unroll
+    for (int k = 0; k < NX; ++k) w[k] = src[k * X::TP];
+  }
+  const bool bad = rb_chol_inv<NX, false>(li, acc, w);
+  wave_lds_sync();  // (every lane has its row of S-bar and its panel column: the Y tiles may overwrite them)
+  {
+    double* ydst = buf + (h <= NX ? P::tile(0, 0) + h : P::tile(0, 1) + (h <= 2 * NX ? h - NX - 1 : YP - 1));
+#pragma unroll
+    for (int k = 0; k < NX; ++k) ydst[k * YP] = w[k];
+    if constexpr (4 * KS > NX) {  // rows NX .. 4 KS - 1 of the tiles are read by the last k-step: zero
+#pragma unroll
+      for (int e0 = 0; e0 < (4 * KS - NX) * YP; e0 += 16) {
+        const int e = e0 + li;
+        if (e < (4 * KS - NX) * YP) buf[P::tile(0, lk & 1) + NX * YP + e] = 0.0;
+      }
+    }
+  }
+  // the records: row li of L (entries 0 .. li) by lane li of DPP rows 0 (t0) and 2 (t1)
   if ((lk & 1) == 0 && li < NX) {
     double* lr = (lk == 0 ? lrecA : lrecB) + li * (li + 1) / 2;
 #pragma unroll
@@ -752,6 +836,38 @@ __device__ __forceinline__ void reduced_eliminate_tail_mc(const Dims& d, const i
   }
 }
 
+// What a four-knot group hands to the workgroup's paired level-1 pass (bottom8_reduced_mc<.., P1>): the tile of its t with
+// the Schur contributions of s0 and s2 in it, the two couplings of t, and what s0 / s2 parked for the group's neighbours.
+struct Pair1Hand { acc4_t c_t, ca_t, cb_t, park_a, park_b11; };
+// The tail of a group's t behind the paired pass (bottom8_reduced_mc<.., P1>): the Gram products of the Y tiles the pass
+// left in this wavefront's buffer and the pushes of the whole group to the separators k0 - 1 (A) and k0 + 3 (B) -- what
+// bottom_group_mc<.., C1> does behind its own pass, with the same operands in the same order.
+template <int NX, int NU>
+__device__ __forceinline__ void pair1_tail_mc(const Dims& d, const int k0, const int b, const int lane_in, double* red,
+                                              const double* buf, const Pair1Hand& hd, double* slotA, double* slotB) {
+  using PY = McPairYLayout<NX>;
+  constexpr int KSN = (NX + 3) / 4;
+  int lane = lane_in;
+  asm volatile("" : "+v"(lane));
+  const int li = lane & 15, lk = lane >> 4;
+  const bool hasA = k0 > 0, hasB = k0 + 4 < d.N, leftchild = (k0 & 4) == 0;
+  RedSlot<NX> sa = red_slot<NX>(red, d, b, hasA ? k0 - 1 : 3);
+  RedSlot<NX> sb = red_slot<NX>(red, d, b, hasB ? k0 + 3 : 3);
+  if (slotA) sa.p = slotA;
+  if (slotB) sb.p = slotB;
+  double y0[KSN], y1[KSN];
+  acc4_t Z0 = {0.0, 0.0, 0.0, 0.0}, Z1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < KSN; ++q) {
+    y0[q] = buf[PY::tile(0, 0) + (4 * q + lk) * PY::YP + li];
+    y1[q] = buf[PY::tile(0, 1) + (4 * q + lk) * PY::YP + li];
+    Z0[q] = y0[q]; Z1[q] = y1[q];
+  }
+  acc4_t g00, g01, g11, unused;
+  gram_mc<NX, true, true, false, true>(y0, y1, Z0, Z1, g00, g01, unused, g11);
+  push_mc<NX>(lane, hasA, hasB, leftchild, sa, sb, g00, g01, g11, hd.park_a, hd.cb_t, hd.park_b11, StorePlain(), StorePlain());
+}
+
 // Leaf phase + tree levels 0, 1 AND 2 in one launch: a workgroup of two wavefronts per EIGHT knots (round 4). Each wavefront
 // runs the four-knot group of bottom_reduced_mc; what the two groups push to the level-2 separator m = k0 + 3 between
 // them -- DL | gL | CA from the left group, DR | gR | CB from the right one -- goes to a slot in LDS instead of `red`, and
@@ -762,15 +878,18 @@ __device__ __forceinline__ void reduced_eliminate_tail_mc(const Dims& d, const i
 // second read of [A | B] are gone; m's own pushes to the separators k0 - 1 and k0 + 7 follow the groups' plain stores
 // as atomic adds (the groups' stores are acknowledged before the barrier), like those of a level launch.
 //   grid (N / 8, batch), block 128; N >= 16 (a level-3 separator exists); compact level-0 records.
-template <int NX, int NU, bool TREE, bool REDIRECT, bool C1 = false>
+template <int NX, int NU, bool TREE, bool REDIRECT, bool C1 = false, bool P1 = false>
 __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, const int b, const int lane,
                                                 const double* __restrict__ AB, const double* __restrict__ QR,
                                                 const double* __restrict__ rhs, double* red, double* __restrict__ rec,
                                                 double* F, int* __restrict__ info, const int store_l, const int compact0,
                                                 ReducedLds<NX, NU>& lds, double* slotA, double* slotB,
-                                                const bool with_m = false, acc4_t* c_m = nullptr);  // (below)
+                                                const bool with_m = false, acc4_t* c_m = nullptr,
+                                                Pair1Hand* hand = nullptr);  // (below)
 // C1: compact records for the level-1 separators too (bottom_group_mc); m keeps its full record.
-template <int NX, int NU, bool C1 = false>
+// P1 (with C1): ONE Cholesky pass for the level-1 separators of both groups (chol_pair1_y_mc), on the first wavefront,
+// between two more workgroup barriers: five passes per eight knots become four.
+template <int NX, int NU, bool C1 = false, bool P1 = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void bottom8_reduced_mc(
     Dims d, const double* __restrict__ AB, const double* __restrict__ QR, const double* __restrict__ rhs, double* red,
     double* __restrict__ rec, int* __restrict__ info) {
@@ -784,8 +903,27 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void b
   for (int e = threadIdx.x; e < RedSlot<NX>::SIZE; e += 128) mslot[e] = 0.0;
   __syncthreads();
   acc4_t c_m = {0.0, 0.0, 0.0, 0.0};  // leaf tile of m (the first wavefront: it has [A_m | B_m] staged)
+  if constexpr (P1) {
+    static_assert(C1, "the paired pass is the Y-only pass of compact level-1 records");
+    static_assert(McPair1Layout<NX>::SIZE <= ReducedLds<NX, NU>::NBUF, "tile and couplings of t fit the wavefront's buffer");
+    Pair1Hand hd;
+    bottom_group_mc<NX, NU, false, true, true, true>(d, kw + 4 * wave, b, lane, AB, QR, rhs, red, rec, nullptr, info, 0, 1,
+                                                     lds[wave], nullptr, nullptr, wave == 0, &c_m, &hd);
+    pair1_exchange_mc<NX>(lane, hd.c_t, hd.ca_t, hd.cb_t, lds[wave].buf);
+    __syncthreads();
+    if (wave == 0) {  // t0 = kw + 1 in DPP rows 0-1, t1 = kw + 5 in rows 2-3; the second wavefront waits at the barrier
+      double* rec_t0 = rec + ((size_t)b * d.N + kw + 1) * (2 * NX * NX + NX);
+      if (chol_pair1_y_mc<NX>(lane, lds[0].buf, lds[1].buf, rec_t0, rec_t0 + 4 * (2 * NX * NX + NX)) &&
+          (lane == 0 || lane == 32))
+        flag_failure(info, d, b);
+    }
+    __syncthreads();
+    pair1_tail_mc<NX, NU>(d, kw + 4 * wave, b, lane, red, lds[wave].buf, hd, wave == 1 ? mslot : nullptr,
+                          wave == 0 ? mslot : nullptr);
+  } else {
   bottom_group_mc<NX, NU, false, true, C1>(d, kw + 4 * wave, b, lane, AB, QR, rhs, red, rec, nullptr, info, 0, 1, lds[wave],
                                        wave == 1 ? mslot : nullptr, wave == 0 ? mslot : nullptr, wave == 0, &c_m);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's plain stores to k0 - 1 / k0 + 7 are acknowledged
   __syncthreads();
   asm volatile("" : "+v"(lane));
@@ -860,13 +998,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 // The four knots k0 .. k0 + 3 of problem b by one wavefront: leaf phase + tree levels 0 and 1 (body of bottom_reduced_mc
 // and of bottom8_reduced_mc). slotA / slotB: where the group's pushes to the separators k0 - 1 / k0 + 3 go instead of
 // their slots in `red` (bottom8_reduced_mc: the level-2 separator between its two groups lives in LDS); null: `red`.
-template <int NX, int NU, bool TREE, bool REDIRECT, bool C1>
+// P1 (with C1, bottom8_reduced_mc alone): the group ends behind its level-0 separators and hands t to the workgroup
+// (Pair1Hand); the pass of t, its Gram products and the pushes follow in the kernel body, between its barriers.
+template <int NX, int NU, bool TREE, bool REDIRECT, bool C1, bool P1>
 __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, const int b, const int lane,
                                                 const double* __restrict__ AB, const double* __restrict__ QR,
                                                 const double* __restrict__ rhs, double* red, double* __restrict__ rec,
                                                 double* F, int* __restrict__ info, const int store_l, const int compact0,
                                                 ReducedLds<NX, NU>& lds, double* slotA, double* slotB,
-                                                const bool with_m, acc4_t* c_m) {
+                                                const bool with_m, acc4_t* c_m, Pair1Hand* hand) {
+  static_assert(!P1 || (C1 && REDIRECT && !TREE), "the paired level-1 pass: the fused bottom launch with compact level-1 records");
   constexpr int W = NX + NU, ROWS = 2 * NX + NU, NN = NX * NX, KSN = (NX + 3) / 4;
   constexpr int REC = 2 * NN + NX;
   // row pitch of the staged [A | B]: even W padded by two doubles so that the 16 rows an operand
@@ -1049,6 +1190,10 @@ __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, con
   factor_tail_mc<NX>(lane, c_s2, ra2, rb2, lds.buf + Pair::W_B, X0, X1, hook_s2);
   store_record_mc<NX>(myrec + 2 * REC, lane, true, hasB, X0, X1);
   SEG(35);
+  }
+  if constexpr (P1) {
+    hand->c_t = c_t; hand->ca_t = ca_t; hand->cb_t = cb_t; hand->park_a = park_a; hand->park_b11 = park_b11;
+    return;
   }
   // ---- t = k0 + 1 (level 1): r_a = -CA[t] = -Y_bb'Y_a of s0, r_bb = -CB[t] = -Y_a'Y_bb of s2: the two coupling tiles
   //      go from the accumulators through LDS (over the dead tiles of the pair) to one panel column per lane

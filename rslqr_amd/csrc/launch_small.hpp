@@ -30,6 +30,7 @@ struct SmallPlan {
   bool rowbcast; // ... and the bottom levels on the row-broadcast core (four separators per wavefront)
   bool fuse2;    // ... or tree level 2 inside the bottom launch (bottom8_reduced_mc)
   bool compact1; // ... and compact records for the level-1 separators as well (rb_backsub_cols substitutes with L_t)
+  bool pair1;    // ... whose two Cholesky passes per workgroup of the fused bottom launch run as one (bottom8_reduced_mc<.., P1>)
   int level0;    // first tree level with a launch of its own (reduced_level_mc), up to ...
   int ltop;      // ... the first one inside reduced_top_mc (== K: no such launch), which starts at ...
   int top_l0;    // ... this level (level 2 may have gone with the bottom launch)
@@ -62,6 +63,10 @@ static inline ndlqr::Dims apply_dims(const NdlqrHipCtx* c, const ndlqr::Dims& d)
 // compact1: the level-1 records are compact too (a full solve of a plan with SmallPlan::compact1 alone).
 template <int NX, int NU>
 constexpr bool kCompact1Fits = ndlqr::P1OnMatrixCores<NX, NU>::value && NX >= 9 && NX + NU <= 16;
+
+// pair1: the paired level-1 pass of the fused bottom launch leaves a wavefront's tile and couplings of t in its buffer
+template <int NX, int NU>
+constexpr bool kPair1Fits = kCompact1Fits<NX, NU> && ndlqr::McPair1Layout<NX>::SIZE <= ndlqr::ReducedLds<NX, NU>::NBUF;
 
 template <int NX, int NU, bool MULTI, class... Args>
 static void launch_rb_backsub(const NdlqrHipCtx* c, const dim3 grid, hipStream_t stream, const bool compact1,
@@ -138,6 +143,19 @@ static SmallPlan plan_small(const NdlqrHipCtx* c, const bool strict, const bool 
       p.compact1 = kCompact1Fits<NX, NU> && p.compact && !p.store_l && !p.rowbcast && c->knobs.backsub_cols != 0 &&
                    (c->knobs.compact1 > 0 ||
                     (c->knobs.compact1 < 0 && ((NX == 12 && NU == 4 && p.fuse2) || (NX == 10 && NU == 4))));
+      // Paired level-1 pass: with compact level-1 records the pass of one t has both halves of its wavefront on the same
+      // tile, so the fused bottom launch can take the t of its two groups through ONE pass on its first wavefront (two more
+      // workgroup barriers, the tiles exchanged through LDS): four Cholesky passes per eight knots instead of five, the
+      // same records and, bit for bit, the same solutions. Only where the fused launch runs with compact level-1
+      // records. The default where the slowest of five runs was below the parent's fastest on the same box
+      // (profiles/pair1_ab.txt): the (12,4) instance -- (12,4,256) x 1024 0.5391-0.5444 -> 0.5248-0.5347 ms,
+      // (12,4,1024) x 512 1.0643-1.0761 -> 1.0399-1.0492, the padded (11,3) 0.5169-0.5236 -> 0.5044-0.5106. With
+      // NDLQR_FUSE2=1 it also cleared the rule against the present defaults of (10,4), 0.4530-0.4598 -> 0.4447-0.4464 (the
+      // fused launch without pairing: 0.4533-0.4593, +-0 as in round 4), and of (9,3) with NDLQR_COMPACT1=1 too,
+      // 0.3905-0.3961 -> 0.3804-0.3842; those instances keep their schedule ("reduced", which
+      // tests/test_compact1_records.py holds them to) and pair on request. NDLQR_PAIR1=0 / 1 overrides.
+      p.pair1 = kPair1Fits<NX, NU> && p.fuse2 && p.compact1 &&
+                (c->knobs.pair1 > 0 || (c->knobs.pair1 < 0 && NX == 12 && NU == 4));
       p.schedule = p.tree ? "reduced-tree"
                    : !p.compact ? "reduced-records"
                    : p.store_l ? "reduced-compact-records" : (p.fuse2 ? "reduced-fused2" : "reduced");
@@ -177,8 +195,15 @@ static int launch_small(NdlqrHipCtx* c, const SmallPlan& plan) {
                                c->QR, s.rhs, s.red, s.rec, c->info);
         } else if (plan.fuse2) {
           bool done = false;
+          if constexpr (kPair1Fits<NX, NU>) {
+            if (plan.pair1) {
+              hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU, true, true>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream,
+                                 d, c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
+              done = true;
+            }
+          }
           if constexpr (kCompact1Fits<NX, NU>) {
-            if (plan.compact1) {
+            if (!done && plan.compact1) {
               hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU, true>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream, d,
                                  c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
               done = true;
