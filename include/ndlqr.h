@@ -28,7 +28,7 @@ extern "C" {
 #define NDLQR_OK 0
 #define NDLQR_ERR_INVALID (-1)   /* reference convention: -1 on NULL / bad argument */
 #define NDLQR_ERR_NO_DEVICE (-2) /* additive: no usable HIP device / HIP runtime error */
-#define NDLQR_ERR_NOT_SPD (-3)   /* additive: a Cholesky pivot was <= 0 on the device */
+#define NDLQR_ERR_NOT_SPD (-3)   /* additive: a Cholesky pivot or a weight was not positive and finite on the device */
 
 /* ------------------------------------------------------------------ matrix.h:71-75 */
 typedef struct {
@@ -576,6 +576,11 @@ int ndlqr_CopyBatchSolutions(NdLqrBatchSolver* bs, double* soln);          /* ba
 int ndlqr_CopyBatchSolutionsDevice(NdLqrBatchSolver* bs, double* dsoln);
 int ndlqr_CopyBatchFactors(NdLqrBatchSolver* bs, int p, double* fact);     /* reference layout */
 int ndlqr_BatchCholeskyFailures(NdLqrBatchSolver* bs);
+/* Which members failed: counts[b], b = 0 .. batch - 1, is the number of times the device flagged problem b. The words
+ * are cumulative since the solver was created (ndlqr_hip.h: ndlqr_hip_download_failure_counts), so the failures of one
+ * solve are the difference between the counts after and before it; their sum over the batch grows by what
+ * ndlqr_BatchCholeskyFailures reports for that solve. Waits for everything in flight. */
+int ndlqr_CopyBatchCholeskyFailureCounts(NdLqrBatchSolver* bs, int* counts);
 /* KKT residual ||K z - b||_2 and ||b||_2 of every problem's resident solution against its raw
  * data, evaluated on the device (batch doubles each; bnorm may be NULL). */
 int ndlqr_BatchKktResiduals(NdLqrBatchSolver* bs, double* res, double* bnorm);

@@ -359,6 +359,13 @@ int ndlqr_hip_pack_solutions_device(NdlqrHipCtx* ctx, double* dst);
  * reference's KKT system (src/solver.c:122-194). batch doubles each. */
 int ndlqr_hip_kkt_residual(NdlqrHipCtx* ctx, double* res, double* bnorm);
 int ndlqr_hip_cholesky_failures(NdlqrHipCtx* ctx);
+/* The per-problem failure words, counts[0 .. batch): how often a kernel flagged problem b (a weight that is not
+ * positive where the weights are staged, a Cholesky pivot that is not positive and finite). The words are the device's
+ * own: CUMULATIVE since the context was created, or since the recovery of a solve that did not launch or complete zeroed
+ * them -- take the difference between two calls for the count of the solves between them. One problem may be flagged
+ * several times by one solve (at the separator that meets the bad data and at its ancestors). Waits for everything in
+ * flight; does not change what ndlqr_hip_cholesky_failures reports. */
+int ndlqr_hip_download_failure_counts(NdlqrHipCtx* ctx, int* counts);
 /* Name of the launch sequence the last solve used (for reports): "reduced", "reduced-fused2" (the (12,4) instance; NDLQR_FUSE2=1/0), "reduced-tree",
  * "reduced-records", "knot-lean", "knot-strict", "knot-keep", "generic-reduced",
  * "generic-reduced-records", "generic-lean",

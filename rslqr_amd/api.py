@@ -295,6 +295,7 @@ def lib():
     proto("ndlqr_CopyBatchSolutionsDevice", ci, vp, vp)
     proto("ndlqr_CopyBatchFactors", ci, vp, ci, dp)
     proto("ndlqr_BatchCholeskyFailures", ci, vp)
+    proto("ndlqr_CopyBatchCholeskyFailureCounts", ci, vp, C.POINTER(ci))
     proto("ndlqr_BatchKktResiduals", ci, vp, dp, dp)
     proto("ndlqr_BatchSolveTimeMs", cd, vp)
     proto("ndlqr_SolveBatchAdjoint", ci, vp, dp)
@@ -1279,6 +1280,16 @@ class BatchSolver:
 
     def cholesky_failures(self):
         return self.L.ndlqr_BatchCholeskyFailures(self.h)
+
+    def cholesky_failure_counts(self):
+        """int32 [batch]: how often the device flagged each problem. The words are the device's own, cumulative since the
+        solver was created (or since the recovery of a solve that did not complete zeroed them): the failures of one solve
+        are the difference between two calls."""
+        out = np.zeros(self.batch, dtype=np.int32)
+        err = self.L.ndlqr_CopyBatchCholeskyFailureCounts(self.h, out.ctypes.data_as(C.POINTER(C.c_int)))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchCholeskyFailureCounts failed: %d" % err)
+        return out
 
     def profile(self):
         """{kernel name: (total ms, launches)} accumulated since the last reset."""

@@ -435,6 +435,10 @@ double ndlqr_BatchSolveTimeMs(const NdLqrBatchSolver* bs) {
 int ndlqr_BatchCholeskyFailures(NdLqrBatchSolver* bs) {
   return bs ? ndlqr_hip_cholesky_failures(bs->ctx) : NDLQR_ERR_INVALID;
 }
+int ndlqr_CopyBatchCholeskyFailureCounts(NdLqrBatchSolver* bs, int* counts) {
+  if (!bs || !counts) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_failure_counts(bs->ctx, counts);
+}
 int ndlqr_BatchKktResiduals(NdLqrBatchSolver* bs, double* res, double* bnorm) {
   if (!bs || !res) return NDLQR_ERR_INVALID;
   return ndlqr_hip_kkt_residual(bs->ctx, res, bnorm);

@@ -1062,7 +1062,7 @@ __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, con
     for (int it = 0; it < IQ; ++it) {
       const int e = lane + 64 * it, ec = e < NQ ? e : NQ - 1, kn = ec / W, c = ec - kn * W;
       rq[ec] = 1.0 / qv[it];
-      if (e < NQ && !(qv[it] > 0.0) && !(k0 + kn == N - 1 && c >= NX)) flag_failure(info, d, b);  // terminal R is unused
+      if (e < NQ && !positive_finite(qv[it]) && !(k0 + kn == N - 1 && c >= NX)) flag_failure(info, d, b);  // terminal R is unused
     }
 #pragma unroll
     for (int it = 0; it < IR; ++it) { const int e = lane + 64 * it; rh[e < NR ? e : NR - 1] = rv[it]; }

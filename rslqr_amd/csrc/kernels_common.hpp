@@ -26,6 +26,11 @@ __device__ __forceinline__ double mad(double a, double b, double acc) {
   }
 }
 
+// A weight or a pivot the factorisation can use: positive and finite. NaN fails both comparisons; +inf -- a weight whose
+// reciprocal is 0, a pivot whose root scales its row to 0 or NaN -- passes `v > 0.0` alone and would leave a wrong or
+// non-finite solution unreported (rb_chol_inv, kernels_dpp.hpp, bounds its pivots the same way through 1 / sqrt).
+__device__ __forceinline__ bool positive_finite(const double v) { return (v > 0.0) & (v < HUGE_VAL); }
+
 // A Cholesky pivot was not positive: count it for problem b and in the batch total (slot
 // info[batch], the only word the host reads back after every solve).
 __device__ __forceinline__ void flag_failure(int* info, const Dims& d, int b) {

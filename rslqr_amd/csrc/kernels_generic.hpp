@@ -137,7 +137,7 @@ __global__ void separator_generic(Dims d, int l, const double* __restrict__ AB, 
   //      product from the remaining lower triangle (wavefront per column c, lane per row i >= c).
   for (int j = 0; j < n; ++j) {
     const double pivot = S[j * ns + j];
-    if (!(pivot > 0.0)) {  // uniform: every thread reads the same LDS word
+    if (!positive_finite(pivot)) {  // uniform: every thread reads the same LDS word (+inf: its root makes the row NaN)
       if (threadIdx.x == 0) flag_failure(info, d, b);
       break;
     }

@@ -25,7 +25,7 @@ __global__ void leaf_generic(Dims d, const double* __restrict__ AB, const double
 
   // pivot check (clap_CholeskyFactorize fails on a pivot <= 0, linalg_custom.c:99-102)
   for (int i = threadIdx.x; i < n + (last ? 0 : m); i += blockDim.x)
-    if (!(qr[i] > 0.0)) flag_failure(info, d, b);
+    if (!positive_finite(qr[i])) flag_failure(info, d, b);
 
   // Fast mode: one reciprocal per weight instead of sqrt + two divisions per factor element
   // (L * L == q up to rounding; strict mode keeps the reference's operations)

@@ -385,7 +385,7 @@ __global__ __launch_bounds__(NTHR, reduced_min_waves(NB, NTHR)) void separator_r
     // the weights of knot s pass through exactly this separator (those of the last knot: Q through separator
     // N - 2, its R is not part of the problem): a non-positive one fails the Cholesky of Q_k / R_k in the reference
     // (src/nested_dissection.c:24-59) -- counted here, S-bar itself may well stay positive definite
-    if ((tid < w && !(qv > 0.0)) || (s == N - 2 && tid < nl && !(q1v > 0.0))) flag_failure(info, d, b);
+    if ((tid < w && !positive_finite(qv)) || (s == N - 2 && tid < nl && !positive_finite(q1v))) flag_failure(info, d, b);
   }
   __syncthreads();
   SEG(50);

@@ -237,7 +237,7 @@ __global__ __launch_bounds__(64, 2) void rb_bottom(Dims d, const double* __restr
     for (int it = 0; it < IQ; ++it) {
       const int e = lane + 64 * it, ec = e < NQ ? e : NQ - 1, kn = ec / W, c = ec - kn * W;
       (&lds.rq[0][0])[ec] = 1.0 / qv[it];
-      if (e < NQ && !(qv[it] > 0.0) && !(kw + kn == N - 1 && c >= NX)) flag_failure(info, d, b);  // terminal R is unused
+      if (e < NQ && !positive_finite(qv[it]) && !(kw + kn == N - 1 && c >= NX)) flag_failure(info, d, b);  // terminal R is unused
     }
 #pragma unroll
     for (int it = 0; it < IR; ++it) { const int e = lane + 64 * it; (&lds.rh[0][0])[e < NR ? e : NR - 1] = rv[it]; }

@@ -104,7 +104,9 @@ __device__ __forceinline__ bool factor_solve(const int lane, double (&acc)[NX], 
     for (int k = 0; k < j; ++k) v = mad<STRICT>(-acc[k], readlane_f64(acc[k], j), v);
     if constexpr (KEEPL) { if (gi >= j) acc[j] = v; } else { acc[j] = v; }
     const double pivot = readlane_f64(acc[j], j);
-    bad |= !(pivot > 0.0);  // no short-circuit: keeps the pivot loop one basic block
+    // no short-circuit: keeps the pivot loop one basic block. An infinite pivot (rsqrt gives 0, sqrt inf: its row of the
+    // right-hand sides becomes inf * 0 or inf / inf) is none
+    bad |= !positive_finite(pivot);
     if constexpr (STRICT) {
       const double root = sqrt(pivot);
       if constexpr (KEEPL) { if (gi >= j) acc[j] = acc[j] / root; } else { acc[j] = acc[j] / root; }
@@ -1203,7 +1205,7 @@ __global__ __launch_bounds__(32 << JB, (KEEP && !STRICT) ? 2 : 3) void bottom_sm
     if (!lam) {
       const double qv = qv_in;
       if constexpr (STRICT) sc = qv / sqrt(qv); else rq = 1.0 / qv;
-      if (has_knot && !(qv > 0.0) && !(last && r >= 2 * NX)) flag_failure(info, d, b);
+      if (has_knot && !positive_finite(qv) && !(last && r >= 2 * NX)) flag_failure(info, d, b);
     }
     auto scale = [&](double v) -> double {
       if constexpr (STRICT) return (v / sc) / sc; else return v * rq;

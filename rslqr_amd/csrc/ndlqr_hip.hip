@@ -1694,6 +1694,18 @@ int ndlqr_hip_synchronize(NdlqrHipCtx* c) {
 
 double ndlqr_hip_last_solve_ms(NdlqrHipCtx* c) { return c ? c->last_ms : -1.0; }
 int ndlqr_hip_cholesky_failures(NdlqrHipCtx* c) { return c ? c->last_failures : NDLQR_ERR_INVALID; }
+// info[0 .. batch): the per-problem words as the device holds them (cumulative; zeroed at creation and by the recovery
+// of prepare_solve). Waits for everything in flight; touches neither last_failures nor fail_base.
+int ndlqr_hip_download_failure_counts(NdlqrHipCtx* c, int* counts) {
+  if (!c || !counts) return NDLQR_ERR_INVALID;
+  HIP_TRY(hipSetDevice(c->device));
+  {
+    const hipError_t se = sync_all(c);
+    if (se != hipSuccess) { c->state_dirty = true; return fail("hipStreamSynchronize", se); }
+  }
+  HIP_TRY(hipMemcpy(counts, c->info.get(), sizeof(int) * (size_t)c->d.batch, hipMemcpyDeviceToHost));
+  return NDLQR_OK;
+}
 
 int ndlqr_hip_profile_slots(NdlqrHipCtx* c) { return c ? (int)SLOT_COUNT : 0; }
 int ndlqr_hip_profile_get(NdlqrHipCtx* c, int slot, char* name, int name_cap, double* total_ms, int* launches) {

@@ -10,8 +10,12 @@ In the environment it is given (NDLQR_COMPACT1, NDLQR_TREE=0) it runs, at batch 
   kept     a solver with KEEP_RECORDS in the same environment: schedule name, full solve, rhs-only re-solve, and one
            multi-rhs call whose first right-hand side is the problems' own
   (python tests/compact1_support.py nonspd: a non-positive R entry at knot 3 -- the construction of
-   test_non_spd_block_is_reported, N = 16 -- and at knot 1, whose input cost enters a level-1 block: return code and failure
-   count of each)
+   test_non_spd_block_is_reported, N = 16 -- and at knot 1: return code and failure count of each. Both are flagged by the
+   check of the weights where the bottom launch stages them (kernels_bottom_reduced.hpp:1065), not by a Cholesky pass: with
+   every other weight positive the separator blocks stay positive definite.
+   python tests/compact1_support.py nonspd n m N batch flags: failure_support.run_case in this environment -- NaN / Inf in
+   A_k and B_k of every separator, which only the Cholesky passes can flag, the level-1 pass on compact records
+   included -- as JSON: schedule name, compact, paired, the violations found)
   weak     (12,4,32) only: the weak-input-cost family (R x 1e-4), its solution, and the refined solution (refine(2) on a
            KEEP_RECORDS solve of the same problems) in the same process
 """
@@ -21,6 +25,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 
@@ -61,6 +66,11 @@ def non_spd():
 
 
 def main():
+    if sys.argv[1] == "nonspd" and len(sys.argv) > 2:
+        import failure_support as fs
+        n, m, N, batch = (int(a) for a in sys.argv[2:6])
+        print(json.dumps(fs.run_case(R, n, m, N, batch, sys.argv[6])))
+        return None
     if sys.argv[1] == "nonspd":
         return non_spd()
     n, m, N = (int(a) for a in sys.argv[1:4])

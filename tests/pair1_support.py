@@ -10,8 +10,14 @@ NDLQR_FUSE2=1 NDLQR_COMPACT1=1) it runs, at batch 3, the problems of tests/compa
            last tile
   kept     a solver with KEEP_RECORDS in the same environment: schedule name, paired or not, full solve, rhs-only re-solve
   weak     (12,4,32) only: the weak-input-cost family (R x 1e-4), its solution, and the refined solution
-  (python tests/pair1_support.py nonspd: (12,4,16), a non-positive R entry at knot 1 -- it enters t0 of the first
-   workgroup, lanes 0-31 of the paired pass -- and at knot 5 -- t1, lanes 32-63: return code and failure count of each)
+  (python tests/pair1_support.py nonspd: (12,4,16), a non-positive R entry at knot 1 -- a weight of the knots of t0 of
+   the first workgroup -- and at knot 5 -- of t1: return code and failure count of each. What flags them is the check of
+   the weights where the bottom launch stages them (kernels_bottom_reduced.hpp:1065): with every other weight positive
+   S-bar of t0 / t1 stays positive definite and the flag of the paired pass (lanes 0 and 32, :916-918) does not fire.
+   python tests/pair1_support.py nonspd n m N batch flags: failure_support.run_case in this environment -- NaN / Inf in
+   A_k and B_k of every separator, which only the Cholesky passes can flag, t0 and t1 of the paired pass included, the
+   weights, the unused data of the last knot and the isolated infinite pivot -- as JSON: schedule name, compact, paired,
+   the violations found)
 """
 import json
 import os
@@ -26,6 +32,7 @@ import numpy as np  # noqa: E402
 import rslqr_amd as R  # noqa: E402
 
 import compact1_support as cs  # noqa: E402
+import failure_support as fs  # noqa: E402
 
 
 def state(bs):
@@ -76,6 +83,10 @@ def weak_family(n, m, N):
 
 
 def main():
+    if sys.argv[1] == "nonspd" and len(sys.argv) > 2:
+        n, m, N, batch = (int(a) for a in sys.argv[2:6])
+        print(json.dumps(fs.run_case(R, n, m, N, batch, sys.argv[6])))
+        return None
     if sys.argv[1] == "nonspd":
         return non_spd()
     n, m, N = (int(a) for a in sys.argv[1:4])

@@ -135,9 +135,31 @@ def test_weak_input_costs():
     assert (e_on <= WEAK_MARGIN * e_off.max()).all(), (e_on, e_off)
 
 
+# (n, m, N, batch, flags, schedule, whether the switch decides about compact level-1 records)
+FAILURE_CASES = [(12, 4, 16, 5, "none", "reduced-fused2", True),
+                 (10, 4, 16, 5, "none", "reduced", True),
+                 (9, 3, 16, 5, "none", "reduced", True),
+                 (12, 4, 16, 5, "records", "reduced-compact-records", False)]
+
+
+@pytest.mark.parametrize("knob", ["1", "0"])
+@pytest.mark.parametrize("n,m,N,batch,flags,want,switched", FAILURE_CASES)
+def test_failures_are_reported_per_problem(knob, n, m, N, batch, flags, want, switched):
+    """tests/failure_support.py (run_case) with the knob on and off: a NaN or +Inf in A_k or B_k reaches no check of the
+    weights, so what reports it is the flag of a Cholesky pass -- for odd k = 1 (mod 4) that of the level-1 pass, on compact
+    records (knob on) or with the full record (knob off) -- and the per-problem words name the member: every separator,
+    both bad members of a batch of 5, at least one flag per contaminated separator, the healthy members bit-equal to a
+    healthy solve. A solver with KEEP_RECORDS keeps full level-1 records whatever the knob says and reports the same."""
+    out = child(knob, "nonspd", n, m, N, batch, flags)
+    print(knob, n, m, N, flags, out["schedule"], "solves", out["solves"], "isolated infinity", out.get("isolated"))
+    assert out["schedule"] == want and out["compact1"] is (switched and knob == "1"), out
+    assert not out["violations"], "%d violations, the first: %s" % (len(out["violations"]), out["violations"][:6])
+
+
 def test_non_spd_block_is_reported():
-    """A non-positive R entry -- at knot 3 as in test_gpu_parity.test_non_spd_block_is_reported, and at knot 1, whose input
-    cost enters a level-1 block -- makes the knob-on solve return NDLQR_ERR_NOT_SPD and count the failure."""
+    """A non-positive R entry -- at knot 3 as in test_gpu_parity.test_non_spd_block_is_reported, and at knot 1 -- makes the
+    knob-on solve return NDLQR_ERR_NOT_SPD and count the failure. (What counts it is the check of the weights where the
+    bottom launch stages them, not a Cholesky pass: test_failures_are_reported_per_problem holds those.)"""
     for case in child("1", "nonspd"):
         assert case["compact1"] is True
         assert case["rc"] == -3 and case["failures"] >= 1, case

@@ -33,7 +33,7 @@ def forced(n):
 
 @functools.lru_cache(maxsize=None)
 def child(knob, *args):
-    n = args[0] if isinstance(args[0], int) else 12
+    n = next((a for a in args if isinstance(a, int)), 12)  # (the block size: the first number)
     env = dict(os.environ, NDLQR_PAIR1=knob, NDLQR_TREE="0", **forced(n))
     r = subprocess.run([sys.executable, os.path.abspath(ps.__file__)] + [str(a) for a in args], env=env, capture_output=True,
                        text=True, timeout=300)
@@ -114,6 +114,26 @@ def test_non_spd_block_is_reported(case):
     got = child("1", "nonspd")[case]
     assert got["knot"] == (1, 5)[case] and got["paired"] is True
     assert got["rc"] == -3 and got["failures"] >= 1, got
+
+
+# (n, m, N, batch, flags, schedule, compact level-1 records and -- with the knob on -- the paired pass)
+FAILURE_CASES = [(12, 4, 16, 5, "none", "reduced-fused2", True),
+                 (10, 4, 16, 5, "none", "reduced-fused2", True),
+                 (12, 4, 16, 5, "records", "reduced-compact-records", False)]
+
+
+@pytest.mark.parametrize("knob", ["1", "0"])
+@pytest.mark.parametrize("n,m,N,batch,flags,want,compact1", FAILURE_CASES)
+def test_failures_are_reported_per_problem(knob, n, m, N, batch, flags, want, compact1):
+    """tests/failure_support.py (run_case) with the knob on and off: a NaN or +Inf in A_k or B_k reaches no check of the
+    weights, so what reports it is the flag of a Cholesky pass -- for k = 1, 0, 2 (mod 8) that of t0, lane 0 of the paired
+    pass, for k = 5, 4, 6 that of t1, lane 32 -- and the per-problem words name the member: every separator, both bad
+    members of a batch of 5, the count of flags at least one per contaminated separator, the healthy members bit-equal to
+    a healthy solve. A solver with KEEP_RECORDS in the same environment does not pair and reports the same."""
+    out = child(knob, "nonspd", n, m, N, batch, flags)
+    print(knob, n, m, N, flags, out["schedule"], "solves", out["solves"], "isolated infinity", out.get("isolated"))
+    assert out["schedule"] == want and out["compact1"] is compact1 and out["paired"] is (compact1 and knob == "1"), out
+    assert not out["violations"], "%d violations, the first: %s" % (len(out["violations"]), out["violations"][:6])
 
 
 # The paired pass is, lane for lane, the arithmetic of the pass it replaces, so the two errors are expected to be equal.
