@@ -235,6 +235,18 @@ def lib():
     proto("MatrixCholeskySolve", ci, mp, mp)
     proto("MatrixSymmetricMultiply", None, mp, mp, mp, cd, cd)
     proto("MatrixAddition", ci, mp, mp, cd)
+    proto("MatrixCholeskyFactorizeWithInfo", ci, mp, C.POINTER(CholeskyInfo))
+    proto("MatrixCholeskySolveWithInfo", ci, mp, mp, C.POINTER(CholeskyInfo))
+    proto("MatrixCopyDiagonal", None, mp, mp)
+    proto("clap_MatrixAddition", ci, mp, mp, cd)
+    proto("clap_MatrixScale", ci, mp, cd)
+    proto("clap_MatrixMultiply", ci, mp, mp, mp, C.c_bool, C.c_bool, cd, cd)
+    proto("clap_MatrixTransposeMultiply", ci, mp, mp, mp)
+    proto("clap_SymmetricMatrixMultiply", ci, mp, mp, mp, cd, cd)
+    proto("clap_AddDiagonal", ci, mp, cd)
+    proto("clap_CholeskyFactorize", ci, mp)
+    proto("clap_CholeskySolve", ci, mp, mp)
+    proto("clap_LowerTriBackSub", ci, mp, mp, C.c_bool)
     # batch
     proto("ndlqr_NewBatchSolver", vp, ci, ci, ci, ci, ci)
     proto("ndlqr_FreeBatchSolver", ci, vp)
@@ -345,6 +357,7 @@ def lib():
     proto("ndlqr_hip_gemm", ci, ci, ci, ci, ci, ci, cd, dp, ci, dp, ci, cd, dp, ci)
     proto("ndlqr_hip_potrf_lower", ci, ci, dp, ci)
     proto("ndlqr_hip_potrs_lower", ci, ci, ci, dp, ci, dp, ci)
+    proto("ndlqr_hip_trsv_lower", ci, ci, ci, dp, ci, dp, ci, ci)
     _LIB = L
     return L
 

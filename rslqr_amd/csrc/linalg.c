@@ -104,10 +104,11 @@ int clap_MatrixAddition(Matrix* A, Matrix* B, double alpha) { return MatrixAddit
 
 int clap_MatrixScale(Matrix* A, double alpha) {
   if (!A) return -1;
-  /* A <- 0 * (A * 1) + alpha * A as a (count x 1) product: the arithmetic stays on the device */
+  /* A <- A * alpha as a (count x 1) product with k = 0, which is exactly C * beta: one multiplication per entry like
+   * the reference's A *= alpha (a k = 1 product would add (0 * A) * 1 on top: +0 for -0, NaN for inf). The two
+   * operands of the empty product are not read. The arithmetic stays on the device. */
   const int count = MatrixNumElements(A);
-  double one = 1.0;
-  return ndlqr_hip_gemm(0, 0, count, 1, 1, 0.0, A->data, count, &one, 1, alpha, A->data, count);
+  return ndlqr_hip_gemm(0, 0, count, 1, 0, 0.0, A->data, count, A->data, 1, alpha, A->data, count);
 }
 
 int clap_MatrixMultiply(Matrix* A, Matrix* B, Matrix* C, bool tA, bool tB, double alpha, double beta) {
