@@ -404,11 +404,12 @@ int ndlqr_InitializeBatchFlatDevice(NdLqrBatchSolver* bs, const double* dA, cons
  * The solver is in dense-cost mode (ndlqr_BatchCostIsDense) until one of the diagonal initialisers above or below is
  * called. CARRIED THROUGH in that mode: ndlqr_SolveBatch and ndlqr_SolveBatchAsync + ndlqr_BatchSynchronize in every flag
  * mode, ndlqr_CopyBatchSolution(s)(Device), ndlqr_BatchSetRhsFlat + ndlqr_SolveBatchRhsOnly, ndlqr_SolveBatchAdjoint +
- * ndlqr_CopyBatchAdjoint, ndlqr_BatchCholeskyFailures, ndlqr_BatchSolveTimeMs, any horizon >= 2.
+ * ndlqr_CopyBatchAdjoint + ndlqr_BatchGradientsDense (the nine dense-cost gradients, assembled on the device),
+ * ndlqr_BatchCholeskyFailures, ndlqr_BatchSolveTimeMs, any horizon >= 2.
  * REFUSED (NDLQR_ERR_INVALID, ndlqr_hip_last_error() opens with the name of the function of ndlqr_hip.h behind the call):
  * ndlqr_BatchStepAsync, ndlqr_BatchSetStepSelection (a non-empty one), ndlqr_SolveBatchSlicesAsync,
- * ndlqr_CopyBatchSolutionSlices, ndlqr_SolveBatchMultiRhs(Slices), ndlqr_BatchGradients (rslqr_amd.autograd.lqr_solve_dense
- * assembles the dense-cost gradients from z and w), ndlqr_RefineBatch(Adjoint), ndlqr_BatchKktResiduals,
+ * ndlqr_CopyBatchSolutionSlices, ndlqr_SolveBatchMultiRhs(Slices), ndlqr_BatchGradients (the dense-cost gradients are
+ * ndlqr_BatchGradientsDense's), ndlqr_RefineBatch(Adjoint), ndlqr_BatchKktResiduals,
  * ndlqr_BatchKktResidualVector (their rows are those of the reduced system), ndlqr_BatchSetBounds and every function of the
  * box-constrained solve, the ndlqr_BatchTimeShard* functions, ndlqr_CopyBatchFactors, and of ndlqr_hip.h
  * ndlqr_hip_device_pointers, ndlqr_hip_staged_io / ndlqr_hip_solve_staged, ndlqr_hip_download_rhs_blocks. */
@@ -614,6 +615,44 @@ int ndlqr_SolveBatchAdjoint(NdLqrBatchSolver* bs, const double* g);  /* K w = g 
 int ndlqr_CopyBatchAdjoint(NdLqrBatchSolver* bs, double* w);         /* [batch][nvars]; returns nvars */
 int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR,
                          double* gq, double* gr, double* gd, double* gx0);
+/* additive: the parameter gradients of dense-cost mode. ndlqr_BatchGradientsDense assembles
+ * dL/d(A, B, Q, H, R, q, r, d, x0) on the device from exactly the z and w that ndlqr_CopyBatchSolutions and
+ * ndlqr_CopyBatchAdjoint would deliver at that moment (both in the caller's variables), in the flat layout of
+ * ndlqr_InitializeBatchFlatDense: gA, gQ [batch][N][n*n], gB, gH [batch][N][n*m], gR [batch][N][m*m], column-major per knot
+ * ((i, j) at i + rows*j); gq, gd [batch][N][n], gr [batch][N][m], gx0 [batch][n]. With lam+ = lambda_(k+1), per knot
+ *     gA(i,j) = -(w_lam+[i] z_x[j] + z_lam+[i] w_x[j])      gB(i,j) = -(w_lam+[i] z_u[j] + z_lam+[i] w_u[j])
+ *     gH(i,j) = -(w_x[i] z_u[j] + z_x[i] w_u[j])
+ *     gQ(i,j) = -1/2 (w_x[i] z_x[j] + z_x[i] w_x[j])        gR(i,j) = -1/2 (w_u[i] z_u[j] + z_u[i] w_u[j])
+ *     gq = -w_x     gr = -w_u     gd = -w_lam+     gx0 = -w_lam0
+ * A, B, H, R, r, d of the last knot are exactly zero. Both triangles of gQ and gR are written and (i,j), (j,i) carry the
+ * same bits in every mode: the gradient in the space of symmetric matrices. With NDLQR_FLAG_STRICT_FP every matrix entry is
+ * t1 = a*b (the w factor first), t2 = c*e, s = t1 + t2, -s (-0.5*s for Q, R) without contraction: bit-reproducible from z
+ * and w; otherwise A, B and H are one fused multiply-add each.
+ *   Reach: dense-cost mode after ndlqr_SolveBatchAdjoint (this includes constrained mode after a plain solve and adjoint:
+ *   the unconstrained answers), and constrained mode after ndlqr_SolveBatchLinAdjoint of the resident constrained solution,
+ *   where w is that of the active-set system and the same formulas hold; there a problem the adjoint did not iterate
+ *   (status 3) gets exact zeros in every per-problem output and is left out of the batch sums, as in
+ *   ndlqr_BatchConstraintGradients. Any horizon >= 2, every block size dense-cost mode accepts.
+ *   Outputs and sum_mask (NDLQR_GRADD_*) as for ndlqr_BatchGradients: NULL = not computed; host, pinned or the solver's
+ *   device memory; bit o: output o summed over the batch, deterministically (two calls give the same bits).
+ *   Returns NDLQR_ERR_INVALID (ndlqr_hip_last_error() opens with ndlqr_hip_gradients_dense) outside dense-cost mode -- there
+ *   ndlqr_BatchGradients is the call --, without an adjoint of the resident solution (any solve, re-solve, new inputs,
+ *   ndlqr_BatchSetRhsFlat or ndlqr_BatchSetConstraintBounds since it was taken), for a partial or invalid solution, for mask
+ *   bits beyond the ninth and for an output in the memory of another device.
+ *   Nothing else moves: the resident solution and adjoint, the kept and remembered factorisations, v, y, mu and the warm
+ *   start stay as they are, and nothing is factored. Blocking; ndlqr_BatchSolveTimeMs then reports the device time of the
+ *   gradient kernels (the packing of z and w included). */
+#define NDLQR_GRADD_A 1u
+#define NDLQR_GRADD_B 2u
+#define NDLQR_GRADD_Q 4u
+#define NDLQR_GRADD_H 8u
+#define NDLQR_GRADD_R 16u
+#define NDLQR_GRADD_q 32u
+#define NDLQR_GRADD_r 64u
+#define NDLQR_GRADD_d 128u
+#define NDLQR_GRADD_x0 256u
+int ndlqr_BatchGradientsDense(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gH,
+                              double* gR, double* gq, double* gr, double* gd, double* gx0);
 /* additive: iterative refinement of a batch solve with a double-double residual, for callers who need more than the
  * solve paths deliver on ill-conditioned inputs. ndlqr_RefineBatch evaluates r = b - K z of the resident solutions with
  * every row accumulated in double-double and rounded once, re-solves K delta = r against the kept factorisation, and
@@ -814,7 +853,8 @@ int ndlqr_BatchBoundGradients(NdLqrBatchSolver* bs, unsigned flags, double* gxlo
  * forward) apply, and iters / status report as for the forward. A problem whose forward ended as 3 is not iterated and
  * reports 3 (w = 0, nu = 0, zero constraint gradients). Afterwards
  *   ndlqr_CopyBatchAdjoint returns w in the caller's variables, from which dL/d(A, B, Q, H, R, q, r, d, x0) follow as the
- *   outer products of z* and w (rslqr_amd.autograd assembles them; ndlqr_BatchGradients stays refused in dense-cost mode);
+ *   outer products of z* and w (ndlqr_BatchGradientsDense assembles them on the device; ndlqr_BatchGradients stays refused
+ *   in dense-cost mode);
  *   ndlqr_BatchConstraintGradients returns dL/dC [P][N][p*n] and dL/dD [P][N][p*m] (column-major per knot like C, D): row r
  *   of knot k is -(mu_r w_x' + nu_r x_k') and -(mu_r w_u' + nu_r u_k'), exactly zero outside A and for D of the last knot;
  *   and dL/dlo, dL/dhi [P][N][p]: nu_r goes to dL/dhi when the forward's iterate sits on hi (lo == hi included), to dL/dlo

@@ -207,6 +207,14 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* ctx, const double* g);
 int ndlqr_hip_download_adjoint(NdlqrHipCtx* ctx, double* w); /* [batch][nvars]: host, pinned or this device's memory */
 int ndlqr_hip_gradients(NdlqrHipCtx* ctx, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gR, double* gq,
                         double* gr, double* gd, double* gx0);
+/* ... in dense-cost mode (ndlqr.h: ndlqr_BatchGradientsDense): the nine gradients from packed
+ * copies of z and w in the caller's variables, after ndlqr_hip_solve_adjoint or -- the resident solution that of a
+ * constrained solve -- ndlqr_hip_solve_constrained_adjoint. Every refusal opens with the function's name. Blocking.
+ * ndlqr_hip_gradients_dense_constants: out2[0] the workgroups the split of a batch sum aims at, out2[1] the knots of a
+ * chunk at most (for the tests, which size a batch by them). */
+int ndlqr_hip_gradients_dense(NdlqrHipCtx* ctx, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gH, double* gR,
+                              double* gq, double* gr, double* gd, double* gx0);
+int ndlqr_hip_gradients_dense_constants(int* out2);
 /* Iterative refinement with a double-double residual (ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint,
  * ndlqr_BatchKktResidualVector). which = 0: the resident solution against the resident right-hand
  * side; 1: w of the latest plain adjoint against its packed g. max_steps in [1, 8]. steps [batch] (int), eta_before,

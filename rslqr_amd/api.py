@@ -22,6 +22,9 @@ SOLN_LAMBDA, SOLN_STATE, SOLN_INPUT, SOLN_ONLY = 1, 2, 4, 8
 # ndlqr_BatchGradients: bit o of sum_mask sums output o over the batch; GRAD_NAMES in the order of the bits / arguments
 GRAD_A, GRAD_B, GRAD_Q, GRAD_R, GRAD_q, GRAD_r, GRAD_d, GRAD_x0 = 1, 2, 4, 8, 16, 32, 64, 128
 GRAD_NAMES = ("A", "B", "Q", "R", "q", "r", "d", "x0")
+# ndlqr_BatchGradientsDense: the same for the nine outputs of dense-cost mode, in the order of the dense initialiser
+GRADD_A, GRADD_B, GRADD_Q, GRADD_H, GRADD_R, GRADD_q, GRADD_r, GRADD_d, GRADD_x0 = 1, 2, 4, 8, 16, 32, 64, 128, 256
+GRAD_DENSE_NAMES = ("A", "B", "Q", "H", "R", "q", "r", "d", "x0")
 
 ERR_INVALID = -1
 ERR_NO_DEVICE = -2
@@ -313,6 +316,8 @@ def lib():
     proto("ndlqr_SolveBatchAdjoint", ci, vp, dp)
     proto("ndlqr_CopyBatchAdjoint", ci, vp, dp)
     proto("ndlqr_BatchGradients", ci, vp, C.c_uint, dp, dp, dp, dp, dp, dp, dp, dp)
+    proto("ndlqr_BatchGradientsDense", ci, vp, C.c_uint, dp, dp, dp, dp, dp, dp, dp, dp, dp)
+    proto("ndlqr_hip_gradients_dense_constants", ci, C.POINTER(C.c_int))
     proto("ndlqr_RefineBatch", ci, vp, ci, C.POINTER(ci), dp, dp)
     proto("ndlqr_RefineBatchAdjoint", ci, vp, ci, C.POINTER(ci), dp, dp)
     proto("ndlqr_BatchKktResidualVector", ci, vp, dp)
@@ -985,6 +990,35 @@ class BatchSolver:
         err = self.L.ndlqr_BatchGradients(self.h, sum_mask, *ptrs)
         if err:
             raise RuntimeError("ndlqr_BatchGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def dense_gradient_shape(self, name, summed=False):
+        """Shape of gradient `name` (GRAD_DENSE_NAMES) in the flat layout of initialize_flat_dense, per problem or summed
+        over the batch."""
+        n, m, N = self.n, self.m, self.N
+        per = dict(A=(N, n * n), B=(N, n * m), Q=(N, n * n), H=(N, n * m), R=(N, m * m), q=(N, n), r=(N, m), d=(N, n),
+                   x0=(n,))[name]
+        return per if summed else (self.batch,) + per
+
+    def gradients_dense(self, sum_mask=0, out=None):
+        """ndlqr_BatchGradientsDense: dict name -> dL/d(name) for the names of GRAD_DENSE_NAMES in dense-cost mode, after
+        solve_adjoint or -- on a constrained solution -- solve_constrained_adjoint, in the flat layout of
+        initialize_flat_dense (matrices column-major per knot); those whose bit is in sum_mask (GRADD_*) summed over the
+        batch. `out`: dict of destinations (numpy arrays or DeviceArrays); only those names are computed. Default: numpy
+        arrays for all nine."""
+        if out is None:
+            out = {k: np.zeros(self.dense_gradient_shape(k, bool(sum_mask & (1 << i)))) for i, k in enumerate(GRAD_DENSE_NAMES)}
+        unknown = set(out) - set(GRAD_DENSE_NAMES)
+        if unknown:
+            raise ValueError("unknown gradient names: %s" % sorted(unknown))
+        ptrs = []
+        for i, k in enumerate(GRAD_DENSE_NAMES):
+            a = out.get(k)
+            ptrs.append(None if a is None else
+                        _any_ptr(a, int(np.prod(self.dense_gradient_shape(k, bool(sum_mask & (1 << i)))))))
+        err = self.L.ndlqr_BatchGradientsDense(self.h, sum_mask, *ptrs)
+        if err:
+            raise RuntimeError("ndlqr_BatchGradientsDense failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
 
     # ---- iterative refinement (include/ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint, ndlqr_BatchKktResidualVector)

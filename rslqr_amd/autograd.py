@@ -15,10 +15,11 @@ every call into the library returns only after its writes are complete. That is 
 module returns may be used on any stream at once.
 
 ``lqr_solve_dense`` takes dense cost matrices Q, R and a state-input cross term H (ndlqr_InitializeBatchFlatDense); its
-backward is one adjoint solve, the gradients are assembled in torch from z and w.
+backward is one adjoint solve and the gradient kernel of dense-cost mode (ndlqr_BatchGradientsDense), which writes the
+gradients that are asked for straight into torch tensors -- batch-summed on the device for a shared argument.
 
 ``lqr_solve_constrained`` adds rows lo <= C x + D u <= hi to the dense-cost problem (ndlqr_SolveBatchLinConstrained); its
-backward is the adjoint of the active-set system (ndlqr_SolveBatchLinAdjoint), the nine problem gradients assembled as for
+backward is the adjoint of the active-set system (ndlqr_SolveBatchLinAdjoint), the nine problem gradients from ndlqr_BatchGradientsDense as for
 ``lqr_solve_dense`` and the four row gradients from ndlqr_BatchConstraintGradients.
 
 ``lqr_solve_box`` adds bounds on x and u (ndlqr_SolveBatchBoxConstrained); its backward is the adjoint of the
@@ -31,7 +32,7 @@ import itertools
 
 import torch
 
-from .api import BatchSolver, FLAG_KEEP_RECORDS, GRAD_NAMES
+from .api import BatchSolver, FLAG_KEEP_RECORDS, GRAD_DENSE_NAMES, GRAD_NAMES
 
 _ARGS = ("A", "B", "Q", "R", "q", "r", "d", "x0")
 _cache = {}                  # (n, m, N, b, device index) -> [BatchSolver, token of the forward it holds]
@@ -414,7 +415,9 @@ def _dense_gradients(z, w, n, m, N):
     """dL/d(A, B, Q, H, R, q, r, d, x0) [b, ...] in the math convention from the solutions z and the adjoint solutions w
     [b, nvars], both in the caller's variables: the outer products per knot with the signs and per-knot conventions of
     kernels_grad.hpp (zero for A, B, H, R, r, d of the last knot; Q and R as symmetric matrices). They hold for the plain
-    dense-cost solve and, with w of the active-set system, for the constrained one (G_A w = 0 drops the constraint term)."""
+    dense-cost solve and, with w of the active-set system, for the constrained one (G_A w = 0 drops the constraint term).
+    The independent restatement of ndlqr_BatchGradientsDense in torch: the tests and tools/grad_dense_bench.py compare
+    against it; no backward calls it."""
     zl, zx, zu = split_solution(z, n, m, N)
     wl, wx, wu = split_solution(w, n, m, N)
     outer = lambda a, c: a.unsqueeze(-1) * c.unsqueeze(-2)
@@ -432,36 +435,73 @@ def _dense_gradients(z, w, n, m, N):
     return (gA, gB, gQ, gH, gR, gq, gr, gd, gx0)
 
 
+def _flat_dense(args, shared, b):
+    """The flat layout of ndlqr_InitializeBatchFlatDense, contiguous on the device: matrices column-major per knot (the
+    transpose, stored row-major); an argument without its batch dimension (`shared`) expanded to the batch."""
+    out = []
+    for t, sh in zip(args, shared):
+        t = t.detach()
+        if sh:
+            t = t.unsqueeze(0)
+        if t.dim() == 4:
+            t = t.transpose(-1, -2)
+        out.append(t.expand(b, *t.shape[1:]).contiguous().reshape(b, -1))
+    return out
+
+
+def _dense_backward_gradients(bs, shared, needs, dims, device):
+    """dL/d(A, B, Q, H, R, q, r, d, x0) from the resident solution and adjoint (ndlqr_BatchGradientsDense), only those
+    `needs` asks for, written by the kernel into torch tensors; a `shared` argument's is the batch sum computed on the
+    device. Math convention: the matrices row-major."""
+    n, m, N, b = dims
+    mask = 0
+    out, views = {}, {}
+    for i, (name, sh, need) in enumerate(zip(GRAD_DENSE_NAMES, shared, needs)):
+        if not need:
+            continue
+        if sh:
+            mask |= 1 << i
+        out[name] = torch.empty(bs.dense_gradient_shape(name, sh), dtype=torch.float64, device=device)
+        views[name] = _View(out[name])
+    if views:
+        torch.cuda.current_stream(device).synchronize()
+        bs.gradients_dense(mask, views)
+    rows = dict(A=n, B=n, Q=n, H=n, R=m)
+    grads = []
+    for name in GRAD_DENSE_NAMES:
+        g = out.get(name)
+        if g is not None and name in rows:  # flat column-major -> row-major math convention
+            g = g.reshape(*g.shape[:-1], g.shape[-1] // rows[name], rows[name]).transpose(-1, -2)
+        grads.append(g)
+    return grads
+
+
 class LqrSolveDense(torch.autograd.Function):
     """Forward: ndlqr_InitializeBatchFlatDense + solve with NDLQR_FLAG_KEEP_RECORDS. Backward: one adjoint solve
-    (ndlqr_SolveBatchAdjoint); the nine gradients are outer products per knot of z and w, both in the caller's variables,
-    assembled here in torch with the signs and per-knot conventions of kernels_grad.hpp (zero for A, B, H, R, r, d of the
-    last knot). The C-level ndlqr_BatchGradients has no dense-cost form and stays refused."""
+    (ndlqr_SolveBatchAdjoint) and ndlqr_BatchGradientsDense: the gradients that are asked for, outer products per knot of
+    z and w in the caller's variables (zero for A, B, H, R, r, d of the last knot), written by the kernel into torch
+    tensors. shared: per argument, whether it came without its batch dimension -- its gradient is the batch sum, computed
+    on the device. dims: (n, m, N, b)."""
 
     @staticmethod
-    def forward(ctx, A, B, Q, H, R, q, r, d, x0):
-        b, N, n, m = B.shape
+    def forward(ctx, shared, dims, A, B, Q, H, R, q, r, d, x0):
+        n, m, N, b = dims
         dev = A.device
         key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
         if key not in _dense_cache:
             _dense_cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
         bs = _dense_cache[key][0]
-        # the flat layout: matrices column-major per knot (the transpose, stored row-major)
-        flat = [(t.detach().transpose(-1, -2) if t.dim() == 4 else t.detach()).contiguous().reshape(b, -1)
-                for t in (A, B, Q, H, R, q, r, d, x0)]
+        flat = _flat_dense((A, B, Q, H, R, q, r, d, x0), shared, b)
         token = next(_tokens)
         _dense_solve(bs, flat, token, key)
         z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
         bs.solutions_to_device(z.data_ptr())
         bs.synchronize()
-        ctx.key, ctx.token, ctx.flat, ctx.dims = key, token, flat, (n, m, N, b)
-        ctx.save_for_backward(z)
+        ctx.key, ctx.token, ctx.flat, ctx.dims, ctx.shared = key, token, flat, (n, m, N, b), shared
         return z
 
     @staticmethod
     def backward(ctx, gz):
-        n, m, N, b = ctx.dims
-        (z,) = ctx.saved_tensors
         bs = _dense_cache[ctx.key][0]
         if _dense_cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's again
             _dense_solve(bs, ctx.flat, ctx.token, ctx.key)
@@ -470,10 +510,7 @@ class LqrSolveDense(torch.autograd.Function):
         err = bs.solve_adjoint(_View(gz))
         if err:
             raise RuntimeError("lqr_solve_dense backward: adjoint solve failed: %d" % err)
-        w = torch.empty_like(z)
-        bs.adjoint(_View(w))
-        grads = _dense_gradients(z, w, n, m, N)
-        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
+        return (None, None) + tuple(_dense_backward_gradients(bs, ctx.shared, ctx.needs_input_grad[2:], ctx.dims, gz.device))
 
 
 def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
@@ -502,8 +539,10 @@ def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
     N, n, m = B.shape[-3:]
     per = dict(A=(N, n, n), B=(N, n, m), Q=(N, n, n), H=(N, n, m), R=(N, m, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,))
     batch = set()
+    shared = []
     for name, t in zip(_DENSE_ARGS, args):
-        if tuple(t.shape) == per[name]:
+        shared.append(tuple(t.shape) == per[name])
+        if shared[-1]:
             continue
         if t.dim() == len(per[name]) + 1 and tuple(t.shape[1:]) == per[name]:
             batch.add(t.shape[0])
@@ -513,9 +552,8 @@ def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
     if len(batch) > 1:
         raise ValueError("lqr_solve_dense: batch dimensions disagree: %s" % sorted(batch))
     b = batch.pop() if batch else 1
-    # (a shared argument is expanded here, outside the Function: autograd sums its gradient over the batch)
-    full = [t if t.dim() == len(per[name]) + 1 else t.unsqueeze(0).expand(b, *t.shape) for name, t in zip(_DENSE_ARGS, args)]
-    return LqrSolveDense.apply(*full)
+    # (a shared argument goes in as it is: the library sums its gradient over the batch)
+    return LqrSolveDense.apply(tuple(shared), (n, m, N, b), *args)
 
 
 # ------------------------------------------------------------------------------------------------ linear inequality constraints
@@ -550,12 +588,13 @@ def _lin_solve(bs, flat, settings, token, key):
 class LqrSolveConstrained(torch.autograd.Function):
     """Forward: ndlqr_InitializeBatchFlatConstrained + ndlqr_SolveBatchLinConstrained (cold). Backward: the adjoint of the
     active-set system (ndlqr_SolveBatchLinAdjoint, the forward's alpha, tolerances and max_iter); the nine problem
-    gradients from z* and w (_dense_gradients), dL/d(C, D, lo, hi) from ndlqr_BatchConstraintGradients -- batch-summed on
-    the device when every row argument is shared (row_shared), else per problem."""
+    gradients from z* and w by ndlqr_BatchGradientsDense, those that are asked for, batch-summed on the device for an
+    argument that is shared (shared, in the order of the nine), dL/d(C, D, lo, hi) from ndlqr_BatchConstraintGradients --
+    batch-summed on the device when every row argument is shared (row_shared), else per problem. dims: (n, m, N, b)."""
 
     @staticmethod
-    def forward(ctx, settings, row_shared, A, B, Q, H, R, q, r, d, x0, C_, D_, lo, hi):
-        b, N, n, m = B.shape
+    def forward(ctx, settings, row_shared, shared, dims, A, B, Q, H, R, q, r, d, x0, C_, D_, lo, hi):
+        n, m, N, b = dims
         p = C_.shape[-2]
         dev = A.device
         key = (n, m, N, p, b, dev.index if dev.index is not None else torch.cuda.current_device())
@@ -564,22 +603,19 @@ class LqrSolveConstrained(torch.autograd.Function):
         bs = _lin_cache[key][0]
         expand = lambda t, sh: t.unsqueeze(0).expand(b, *t.shape) if sh else t
         rows = [expand(t.detach(), sh) for t, sh in zip((C_, D_, lo, hi), row_shared)]
-        # the flat layout: matrices column-major per knot (the transpose, stored row-major)
-        flat = [(t.detach().transpose(-1, -2) if t.dim() == 4 else t.detach()).contiguous().reshape(b, -1)
-                for t in (A, B, Q, H, R, q, r, d, x0, rows[0], rows[1])] + [t.contiguous().reshape(b, -1) for t in rows[2:]]
+        flat = _flat_dense((A, B, Q, H, R, q, r, d, x0), shared, b) + _flat_dense(rows, (False,) * 4, b)
         token = next(_tokens)
         ctx.infeasible = _lin_solve(bs, flat, settings, token, key)
         z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
         bs.solutions_to_device(z.data_ptr())
         bs.synchronize()
         ctx.key, ctx.token, ctx.flat, ctx.dims, ctx.settings, ctx.row_shared = key, token, flat, (n, m, N, p, b), settings, row_shared
-        ctx.save_for_backward(z)
+        ctx.shared = shared
         return z
 
     @staticmethod
     def backward(ctx, gz):
         n, m, N, p, b = ctx.dims
-        (z,) = ctx.saved_tensors
         bs = _lin_cache[ctx.key][0]
         if _lin_cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's forward again
             _lin_solve(bs, ctx.flat, ctx.settings, ctx.token, ctx.key)
@@ -595,10 +631,8 @@ class LqrSolveConstrained(torch.autograd.Function):
         if bad:
             raise RuntimeError("lqr_solve_constrained backward: the adjoint of %d of %d problems did not converge (status %s)"
                                % (bad, status.size, sorted(set(status[~ctx.infeasible].tolist()) - {1})))
-        w = torch.empty_like(z)
-        bs.adjoint(_View(w))
-        need = ctx.needs_input_grad[2:]
-        grads = [g if nd else None for g, nd in zip(_dense_gradients(z, w, n, m, N), need[:9])]
+        need = ctx.needs_input_grad[4:]
+        grads = _dense_backward_gradients(bs, ctx.shared, need[:9], (n, m, N, b), gz.device)
         need_rows = need[9:]
         wanted = [k for k, nd in zip(_ROW_ARGS, need_rows) if nd]
         summed = bool(wanted) and all(sh for k, sh in zip(_ROW_ARGS, ctx.row_shared) if k in wanted)
@@ -614,7 +648,7 @@ class LqrSolveConstrained(torch.autograd.Function):
                 if k in ("C", "D"):  # flat column-major -> row-major math convention
                     g = g.reshape(*g.shape[:-1], n if k == "C" else m, p).transpose(-1, -2)
             grads.append(g)
-        return (None, None) + tuple(grads)
+        return (None, None, None, None) + tuple(grads)
 
 
 def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0,
@@ -670,9 +704,8 @@ def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, 
     if len(batch) > 1:
         raise ValueError("lqr_solve_constrained: batch dimensions disagree: %s" % sorted(batch))
     b = batch.pop() if batch else 1
-    # (a shared problem argument is expanded here, outside the Function: autograd sums its gradient over the batch; the row
-    #  arguments go in as they are, so that the library can sum theirs)
-    full = [t if not shared[name] else t.unsqueeze(0).expand(b, *t.shape) for name, t in zip(_DENSE_ARGS, args[:9])]
+    # (every argument goes in as it is: the library sums the gradient of a shared one over the batch)
     settings = (float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(check_every), int(adapt_every),
                 int(infeas_every), float(infeas_eps))
-    return LqrSolveConstrained.apply(settings, tuple(shared[k] for k in _ROW_ARGS), *full, C, D, lo, hi)
+    return LqrSolveConstrained.apply(settings, tuple(shared[k] for k in _ROW_ARGS), tuple(shared[k] for k in _DENSE_ARGS),
+                                     (n, m, N, b), *args)

@@ -472,6 +472,11 @@ int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, do
   if (!bs) return NDLQR_ERR_INVALID;
   return ndlqr_hip_gradients(bs->ctx, sum_mask, gA, gB, gQ, gR, gq, gr, gd, gx0);
 }
+int ndlqr_BatchGradientsDense(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gH,
+                              double* gR, double* gq, double* gr, double* gd, double* gx0) {
+  if (!bs) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_gradients_dense(bs->ctx, sum_mask, gA, gB, gQ, gH, gR, gq, gr, gd, gx0);
+}
 int ndlqr_RefineBatch(NdLqrBatchSolver* bs, int max_steps, int* steps, double* eta_before, double* eta_after) {
   if (!bs) return NDLQR_ERR_INVALID;
   return ndlqr_hip_refine(bs->ctx, 0, max_steps, steps, eta_before, eta_after);

@@ -211,11 +211,13 @@ struct DevKnobs {
 
 // Adjoint solve and parameter gradients (ndlqr_hip_solve_adjoint / ndlqr_hip_gradients): the adjoint right-hand side
 // and its solution w in buffers of their own, [batch][N][2n+m], so that the primal state stays as it is. gen: the
-// resident solution (NdlqrHipCtx::soln_gen) the adjoint belongs to (0: none).
+// resident solution (NdlqrHipCtx::soln_gen) the adjoint belongs to (0: none); rhs_stamp: NdlqrHipCtx::rhs_stamp() when
+// the plain or the constrained adjoint solve ended (ndlqr_hip_gradients_dense refuses a right-hand side replaced since).
 struct AdjointState {
   DevBuf<double> rhs, z;
   DevBuf<double> save;  // right-hand-side columns of the kept records / slots, saved around a re-solve that is not the primal's
   unsigned long long gen = 0;
+  unsigned long long rhs_stamp = 0;
   hipError_t ensure_save(const ndlqr::Dims& d) { return save.ensure(2 * (size_t)d.batch * d.N * d.n); }
   hipError_t ensure(const ndlqr::Dims& d, hipStream_t st) {
     // (z zeroed: the entries a re-solve does not write, the pad rows)
@@ -587,6 +589,8 @@ struct NdlqrHipCtx {
   bool lin_adjoint_resident() const {
     return alin.gen != 0 && alin.gen == soln_gen && adj.gen == soln_gen && lin.soln_gen == soln_gen && !lin.rhs_new;
   }
+  // grows with every write of a part of the right-hand side (rhs_latest)
+  unsigned long long rhs_stamp() const { return rhs_latest[0] + rhs_latest[1] + rhs_latest[2] + rhs_latest[3]; }
   // profile
   std::vector<PendingEvent> pending;
   std::vector<hipEvent_t> event_pool;

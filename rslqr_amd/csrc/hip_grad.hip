@@ -56,6 +56,7 @@ int ndlqr_hip_solve_adjoint(NdlqrHipCtx* c, const double* g) {
   HIP_TRY(hipStreamSynchronize(s.stream));
   note_elapsed(c, s);
   c->adj.gen = c->soln_gen;
+  c->adj.rhs_stamp = c->rhs_stamp();
   return NDLQR_OK;
 }
 

@@ -670,6 +670,7 @@ int ndlqr_hip_solve_constrained_adjoint(NdlqrHipCtx* c, const double* g, double 
   if (err) return err;
   note_elapsed(c, s);
   c->adj.gen = c->soln_gen;
+  c->adj.rhs_stamp = c->rhs_stamp();
   a.gen = c->soln_gen;
   return NDLQR_OK;
 }
