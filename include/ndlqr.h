@@ -653,6 +653,36 @@ int ndlqr_BatchGradients(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, do
 #define NDLQR_GRADD_x0 256u
 int ndlqr_BatchGradientsDense(NdLqrBatchSolver* bs, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gH,
                               double* gR, double* gq, double* gr, double* gd, double* gx0);
+/* additive: feedback gains and cost-to-go matrices -- what an MPC loop applies between two solves
+ * (u = u_0 + K_0 (x - x_0)), what a TVLQR tracking controller needs of every knot, and what an iLQR / SQP outer loop rolls
+ * its line search out with. With P_(N-1) = Q_(N-1), p_(N-1) = q_(N-1), for k = N-2 .. 0 (the reference's Riccati recursion):
+ *     g = P_(k+1) d_k + p_(k+1)
+ *     M = [A_k | B_k]' P_(k+1) [A_k | B_k] + [[Q_k, H_k], [H_k', R_k]]      (Qxx | Qxu ; Qux | Quu)
+ *     v = [q_k ; r_k] + [A_k | B_k]' g                                      (Qx ; Qu)
+ *     Quu = L L',  W = L^-1 Qux,  w = L^-1 Qu
+ *     K_k = -L^-T W     kff_k = -L^-T w     P_k = Qxx - W' W     p_k = Qx - W' w
+ * so that u_k = K_k x_k + kff_k and lambda_k = P_k x_k + p_k on the optimal trajectory, in the signs of the solution vector
+ * [lambda x u]. It delivers gains, not solutions: the time-parallel factorisation stays the only solver.
+ *   Outputs for the knots [knot0, knot0 + nknots): K [batch][nknots][m*n], kff [batch][nknots][m], P [batch][nknots][n*n],
+ *   p [batch][nknots][n]; matrices column-major per knot (K(j,i) at j + m*i). Any of them may be NULL (not computed), not
+ *   all four; failures [batch] ints, may be NULL. Host, pinned or the solver's device memory. P is bit-symmetric. If knot
+ *   N-1 is in the range its K, kff are exact zeros, its P = diag Q_(N-1) (dense-cost mode: Q_(N-1) as L L' of its factor)
+ *   and p = q_(N-1).
+ *   Reads the resident inputs and the latest right-hand side (ndlqr_BatchSetRhsFlat and the steps of ndlqr_BatchStepAsync
+ *   included); in dense-cost mode it runs on the reduced problem and maps the result back, so the outputs are those of the
+ *   caller's Q, H, R. Needs no solve before it and no flag; works in every flag mode (the same bits in all of them), at any
+ *   horizon >= 2 and on every block size whose working set fits the LDS of a workgroup. Blocking.
+ *   Returns NDLQR_OK; NDLQR_ERR_NOT_SPD if a pivot of some Quu was not > 0 (NaN included): the pivot is taken as 1 and
+ *   counted in failures[problem], NOT in the solver's failure counts; all outputs are delivered, finite for finite input,
+ *   and every healthy problem's are those of a healthy batch, bit for bit. NDLQR_ERR_INVALID (ndlqr_hip_last_error() opens
+ *   with ndlqr_hip_feedback_gains) for a knot range outside [0, N), all outputs NULL, constrained (linear-inequality) mode
+ *   -- the resident problem there is the rho-shifted one --, a time-axis shard, a block size beyond the LDS and an output in
+ *   the memory of another device.
+ *   Nothing else moves: the resident solution and what is known about it, the kept and remembered factorisations, the
+ *   failure counts, the box / constraint / polish state stay as they are. ndlqr_BatchSolveTimeMs then reports the device
+ *   time of the call's kernels. */
+int ndlqr_BatchFeedbackGains(NdLqrBatchSolver* bs, int knot0, int nknots, double* K, double* kff, double* P, double* p,
+                             int* failures);
 /* additive: iterative refinement of a batch solve with a double-double residual, for callers who need more than the
  * solve paths deliver on ill-conditioned inputs. ndlqr_RefineBatch evaluates r = b - K z of the resident solutions with
  * every row accumulated in double-double and rounded once, re-solves K delta = r against the kept factorisation, and

@@ -215,6 +215,15 @@ int ndlqr_hip_gradients(NdlqrHipCtx* ctx, unsigned sum_mask, double* gA, double*
 int ndlqr_hip_gradients_dense(NdlqrHipCtx* ctx, unsigned sum_mask, double* gA, double* gB, double* gQ, double* gH, double* gR,
                               double* gq, double* gr, double* gd, double* gx0);
 int ndlqr_hip_gradients_dense_constants(int* out2);
+/* Feedback gains and cost-to-go matrices of the resident problems (ndlqr.h: ndlqr_BatchFeedbackGains has the contract;
+ * DESIGN.md section 3.22): the backward recursion of one workgroup per problem on the device inputs and the latest
+ * right-hand side, for the knots [knot0, knot0 + nknots). K [batch][nknots][m*n], kff [batch][nknots][m],
+ * P [batch][nknots][n*n], p [batch][nknots][n], fails [batch] (int): each may be NULL (not all of the four doubles); host,
+ * pinned or this device's memory. Every refusal opens with the function's name. Blocking.
+ * ndlqr_hip_feedback_gains_lds: the bytes of LDS its sweep needs at (n, m), with the second input buffer or without it
+ * (for the tests and tools, which pick shapes by it). */
+int ndlqr_hip_feedback_gains(NdlqrHipCtx* ctx, int knot0, int nknots, double* K, double* kff, double* P, double* p, int* fails);
+size_t ndlqr_hip_feedback_gains_lds(int n, int m, int second);
 /* Iterative refinement with a double-double residual (ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint,
  * ndlqr_BatchKktResidualVector). which = 0: the resident solution against the resident right-hand
  * side; 1: w of the latest plain adjoint against its packed g. max_steps in [1, 8]. steps [batch] (int), eta_before,

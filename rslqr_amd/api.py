@@ -318,6 +318,8 @@ def lib():
     proto("ndlqr_BatchGradients", ci, vp, C.c_uint, dp, dp, dp, dp, dp, dp, dp, dp)
     proto("ndlqr_BatchGradientsDense", ci, vp, C.c_uint, dp, dp, dp, dp, dp, dp, dp, dp, dp)
     proto("ndlqr_hip_gradients_dense_constants", ci, C.POINTER(C.c_int))
+    proto("ndlqr_BatchFeedbackGains", ci, vp, ci, ci, dp, dp, dp, dp, C.POINTER(ci))
+    proto("ndlqr_hip_feedback_gains_lds", C.c_size_t, ci, ci, ci)
     proto("ndlqr_RefineBatch", ci, vp, ci, C.POINTER(ci), dp, dp)
     proto("ndlqr_RefineBatchAdjoint", ci, vp, ci, C.POINTER(ci), dp, dp)
     proto("ndlqr_BatchKktResidualVector", ci, vp, dp)
@@ -413,6 +415,12 @@ class DeviceArray:
 
 def device_count():
     return lib().ndlqr_hip_device_count()
+
+
+def feedback_gains_lds(n, m, second=False):
+    """Bytes of LDS the sweep of BatchSolver.feedback_gains needs at block size (n, m), with the second input buffer or
+    without it (ndlqr_hip_feedback_gains_lds); a shape that needs more than 160 KB without it is refused."""
+    return int(lib().ndlqr_hip_feedback_gains_lds(n, m, 1 if second else 0))
 
 
 def _ptr(a):
@@ -1020,6 +1028,40 @@ class BatchSolver:
         if err:
             raise RuntimeError("ndlqr_BatchGradientsDense failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
+
+    # ---- feedback gains and cost-to-go matrices (include/ndlqr.h: ndlqr_BatchFeedbackGains)
+    def feedback_gains(self, knot0=0, nknots=None, want=("K", "k", "P", "p"), out=None):
+        """ndlqr_BatchFeedbackGains: u_k = K_k x_k + k_k and lambda_k = P_k x_k + p_k of the resident problems and the
+        latest right-hand side, for the knots [knot0, knot0 + nknots) (nknots=None: to the end of the horizon). Returns a
+        dict of numpy arrays in the math convention -- K [batch, nknots, m, n], k [batch, nknots, m], P [batch, nknots, n, n],
+        p [batch, nknots, n], those named in `want` -- plus "failures", int32 [batch]. With `out`, a dict of pinned_empty
+        arrays or DeviceArrays in the flat shapes of the C API (K [batch, nknots, m*n] column-major per knot, P
+        [batch, nknots, n*n]), those are filled and returned instead (`want` is ignored). Raises RuntimeError with the
+        library's message on a refusal. A pivot that was not positive does not raise: the dict comes back with
+        failures[problem] > 0 for the problems concerned (their outputs are finite, not meaningful); MPC use:
+        feedback_gains(0, 1, want=("K",))["K"][:, 0]."""
+        n, m, bt = self.n, self.m, self.batch
+        if nknots is None:
+            nknots = self.N - knot0
+        flat = dict(K=(bt, nknots, m * n), k=(bt, nknots, m), P=(bt, nknots, n * n), p=(bt, nknots, n))
+        names = tuple(out) if out is not None else tuple(want)
+        unknown = set(names) - set(flat)
+        if unknown:
+            raise ValueError("unknown output names: %s" % sorted(unknown))
+        flat = {k: tuple(max(s, 0) for s in v) for k, v in flat.items()}  # (an empty range is the library's to refuse)
+        res = dict(out) if out is not None else {k: np.zeros(flat[k]) for k in names}
+        ptrs = [None if res.get(k) is None else _any_ptr(res[k], int(np.prod(flat[k]))) for k in ("K", "k", "P", "p")]
+        failures = np.zeros(bt, dtype=np.int32)
+        err = self.L.ndlqr_BatchFeedbackGains(self.h, int(knot0), int(nknots), *ptrs, failures.ctypes.data_as(C.POINTER(C.c_int)))
+        if err not in (0, ERR_NOT_SPD):
+            raise RuntimeError("ndlqr_BatchFeedbackGains failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        if out is None:
+            for k in ("K", "P"):
+                if k in res:
+                    rows = m if k == "K" else n
+                    res[k] = np.ascontiguousarray(res[k].reshape(bt, nknots, n, rows).transpose(0, 1, 3, 2))
+        res["failures"] = failures
+        return res
 
     # ---- iterative refinement (include/ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint, ndlqr_BatchKktResidualVector)
     def _refine(self, name, max_steps):

@@ -477,6 +477,11 @@ int ndlqr_BatchGradientsDense(NdLqrBatchSolver* bs, unsigned sum_mask, double* g
   if (!bs) return NDLQR_ERR_INVALID;
   return ndlqr_hip_gradients_dense(bs->ctx, sum_mask, gA, gB, gQ, gH, gR, gq, gr, gd, gx0);
 }
+int ndlqr_BatchFeedbackGains(NdLqrBatchSolver* bs, int knot0, int nknots, double* K, double* kff, double* P, double* p,
+                             int* failures) {
+  if (!bs) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_feedback_gains(bs->ctx, knot0, nknots, K, kff, P, p, failures);
+}
 int ndlqr_RefineBatch(NdLqrBatchSolver* bs, int max_steps, int* steps, double* eta_before, double* eta_after) {
   if (!bs) return NDLQR_ERR_INVALID;
   return ndlqr_hip_refine(bs->ctx, 0, max_steps, steps, eta_before, eta_after);
