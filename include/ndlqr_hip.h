@@ -395,6 +395,10 @@ int ndlqr_hip_compact_level1(const NdlqrHipCtx* ctx);
 /* 1 when the fused bottom launch of the last solve took the two level-1 separators of a workgroup through one Cholesky
  * pass ("reduced-fused2" with compact level-1 records: the default of the (12,4) instance; NDLQR_PAIR1=1/0), else 0. The records are the same either way. */
 int ndlqr_hip_level1_paired(const NdlqrHipCtx* ctx);
+/* 1 when that paired launch ran in its 16 KB LDS layout (ten workgroups per CU instead of eight; the level-2 separator's
+ * slots are stored once, without atomic adds; NDLQR_BOTTOM_LDS16=1/0, unset: by instance), else 0 -- "not applied". The
+ * records and the solutions are the same either way. */
+int ndlqr_hip_bottom_lds16(const NdlqrHipCtx* ctx);
 
 /* Per-kernel profile (NDLQR_FLAG_PROFILE): HIP-event durations accumulated since the last
  * reset, one slot per kernel kind. Returns number of slots / fills name, total ms, launches. */

@@ -358,6 +358,8 @@ def lib():
         proto("ndlqr_hip_compact_level1", C.c_int, vp)
     if hasattr(L, "ndlqr_hip_level1_paired"):
         proto("ndlqr_hip_level1_paired", C.c_int, vp)
+    if hasattr(L, "ndlqr_hip_bottom_lds16"):
+        proto("ndlqr_hip_bottom_lds16", C.c_int, vp)
     proto("ndlqr_hip_set_pipeline_depth", ci, vp, ci)
     proto("ndlqr_hip_pipeline_depth", ci, vp)
     proto("ndlqr_hip_pack_solutions_device", ci, vp, vp)
@@ -1402,6 +1404,11 @@ class BatchSolver:
         """True when the fused bottom launch of the last solve ran one Cholesky pass for the two level-1 separators of a
         workgroup (NDLQR_PAIR1)."""
         return hasattr(self.L, "ndlqr_hip_level1_paired") and bool(self.L.ndlqr_hip_level1_paired(self.ctx))
+
+    def bottom_lds16(self):
+        """True when that paired launch of the last solve ran in its 16 KB LDS layout (NDLQR_BOTTOM_LDS16); False: not
+        applied."""
+        return hasattr(self.L, "ndlqr_hip_bottom_lds16") and bool(self.L.ndlqr_hip_bottom_lds16(self.ctx))
 
     def set_pipeline_depth(self, depth):
         """1: stream-ordered solves; 2: consecutive asynchronous solves alternate between two buffer sets."""

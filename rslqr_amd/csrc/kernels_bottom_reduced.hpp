@@ -6,7 +6,8 @@
 //                       (TREE: the wavefront climbs on through the upper levels on arrival counters)
 //   bottom8_reduced_mc  the same for eight knots per two-wavefront workgroup with tree level 2 behind it, the level-2
 //                       slot in LDS (opt-in: NDLQR_FUSE2=1); <.., P1>: one Cholesky pass for the level-1 separators of
-//                       both wavefronts' groups (NDLQR_PAIR1)
+//                       both wavefronts' groups (NDLQR_PAIR1); <.., P1, L16>: that launch in 16 KB of LDS, ten workgroups per
+//                       CU, the level >= 3 slots stored once (bottom8_lds16_mc; NDLQR_BOTTOM_LDS16)
 //   reduced_level_mc    one upper level, one wavefront per separator (reduced_separator_mc)
 //   reduced_top_mc      the last three levels + the top-down sweep of the back-substitution, one workgroup per problem
 //   the separator core  chol_pair_y_mc / chol_wy_mc (the Cholesky pass on the vector ALU, one row of S-bar per lane of
@@ -624,6 +625,31 @@ struct alignas(16) ReducedLds {
 #endif
 };
 
+// LDS of one wavefront of bottom8_reduced_mc<.., P1, L16> (the paired fused bottom launch in at most 16 KB per workgroup:
+// ten workgroups per CU = five wavefronts per SIMD, where ReducedLds allows eight = four). The buffer is as large as the
+// largest tile layout that lives in it (McPair1Layout: 832 doubles) and no larger: [A | B] of the four knots is staged at
+// the widest pitch that still fits -- W + 2 like ReducedLds where it does, else W + 1 (the (12,4) instance: 48 rows at
+// pitch 17 = 816 doubles instead of 864 at pitch 18; the odd pitch is staged with 8-byte stores and keeps the 16 rows of an
+// operand fragment in distinct banks). The level-2 slot of the workgroup has no array of its own: it lies over the first
+// wavefront's LDS behind the Y tiles of the paired pass (MSLOT), which is dead while the slot is live -- from the groups'
+// pushes (pair1_tail_mc, which reads the Y tiles at [0, 2 TILE) of either buffer) to the assembly of m's tile
+// (reduced_eliminate_pass_mc, which has the slot in registers before its pass overwrites the buffer).
+template <int NX, int NU>
+struct alignas(16) Bottom8Lds16 {
+  static constexpr int W = NX + NU, ROWS = 2 * NX + NU;
+  static constexpr int NTILE = McPair1Layout<NX>::SIZE > McPairYLayout<NX>::SIZE
+                                   ? (McPair1Layout<NX>::SIZE > McWyLayout<NX>::SIZE ? McPair1Layout<NX>::SIZE : McWyLayout<NX>::SIZE)
+                                   : (McPairYLayout<NX>::SIZE > McWyLayout<NX>::SIZE ? McPairYLayout<NX>::SIZE : McWyLayout<NX>::SIZE);
+  static constexpr int WP = (W % 2 == 0) ? (4 * NX * (W + 2) <= NTILE ? W + 2 : W + 1) : W;
+  static constexpr int NBUF = 4 * NX * WP > NTILE ? 4 * NX * WP : NTILE;
+  static constexpr int NRQ = 4 * W, NRH = 4 * ROWS;
+  static constexpr int MSLOT = 2 * McPairYLayout<NX>::TILE;  // offset of the level-2 slot in the first wavefront's LDS
+  static_assert(MSLOT % 2 == 0 && MSLOT + RedSlot<NX>::SIZE <= NBUF + NRQ + NRH, "the level-2 slot fits behind the Y tiles");
+  double buf[NBUF];
+  double rq[NRQ];
+  double rh[NRH];
+};
+
 // One separator of an upper level (l >= 2) of the separator-only schedule on the matrix-core core
 // (see reduced_level): subtree [base, base + 2^(l+1)) of problem b, by one wavefront.
 // TREE: called from the tree schedule -- the slot was written by wavefronts of this launch, possibly
@@ -878,21 +904,31 @@ __device__ __forceinline__ void pair1_tail_mc(const Dims& d, const int k0, const
 // second read of [A | B] are gone; m's own pushes to the separators k0 - 1 and k0 + 7 follow the groups' plain stores
 // as atomic adds (the groups' stores are acknowledged before the barrier), like those of a level launch.
 //   grid (N / 8, batch), block 128; N >= 16 (a level-3 separator exists); compact level-0 records.
-template <int NX, int NU, bool TREE, bool REDIRECT, bool C1 = false, bool P1 = false>
+template <int NX, int NU, bool TREE, bool REDIRECT, bool C1 = false, bool P1 = false, class LdsT>
 __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, const int b, const int lane,
                                                 const double* __restrict__ AB, const double* __restrict__ QR,
                                                 const double* __restrict__ rhs, double* red, double* __restrict__ rec,
                                                 double* F, int* __restrict__ info, const int store_l, const int compact0,
-                                                ReducedLds<NX, NU>& lds, double* slotA, double* slotB,
+                                                LdsT& lds, double* slotA, double* slotB,
                                                 const bool with_m = false, acc4_t* c_m = nullptr,
                                                 Pair1Hand* hand = nullptr);  // (below)
 // C1: compact records for the level-1 separators too (bottom_group_mc); m keeps its full record.
 // P1 (with C1): ONE Cholesky pass for the level-1 separators of both groups (chol_pair1_y_mc), on the first wavefront,
 // between two more workgroup barriers: five passes per eight knots become four.
-template <int NX, int NU, bool C1 = false, bool P1 = false>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void bottom8_reduced_mc(
+// L16 (with P1): the same launch in at most 16 KB of LDS per workgroup (bottom8_lds16_mc below; NDLQR_BOTTOM_LDS16).
+template <int NX, int NU>
+__device__ __forceinline__ void bottom8_lds16_mc(const Dims& d, const double* __restrict__ AB, const double* __restrict__ QR,
+                                                 const double* __restrict__ rhs, double* red, double* __restrict__ rec,
+                                                 int* __restrict__ info);
+template <int NX, int NU, bool C1 = false, bool P1 = false, bool L16 = false>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(L16 ? 5 : 4))) void bottom8_reduced_mc(
     Dims d, const double* __restrict__ AB, const double* __restrict__ QR, const double* __restrict__ rhs, double* red,
     double* __restrict__ rec, int* __restrict__ info) {
+  if constexpr (L16) {
+    static_assert(P1, "the 16 KB layout is that of the paired pass");
+    bottom8_lds16_mc<NX, NU>(d, AB, QR, rhs, red, rec, info);
+    return;
+  }
   __shared__ ReducedLds<NX, NU> lds[2];
   __shared__ __attribute__((aligned(16))) double mslot[RedSlot<NX>::SIZE];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), b = blockIdx.y;
@@ -931,6 +967,145 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void b
   __syncthreads();
   // (the tail is shared: the first wavefront forms the Gram products and pushes, the second X = W'Y and the record)
   reduced_eliminate_tail_mc<NX, NU>(d, kw, b, lane, wave == 0, red, rec, lds[0].buf);
+}
+
+// The tail of a group's t in bottom8_reduced_mc<.., P1, L16>: pair1_tail_mc with the group's outer side -- what the first
+// wavefront would store to the slot of separator kw - 1 (DR | gR) and the second to that of kw + 7 (DL | gL) -- kept in LDS
+// instead (`park`: the accumulator tiles lane-major, component g of lane l at [64 g + l], A | B | the gL row), where the
+// tail of m finds it and stores its own contribution WITH it: one plain store per slot element where the launch otherwise
+// stores and then adds atomically, behind a wait for the stores' acknowledgement. The sums are the same numbers: a + b.
+// The inner side goes to the level-2 slot in LDS like before; the coupling block of that slot which faces a neighbour
+// that does not exist is written as zeros (it is read and multiplied by zero: see bottom8_lds16_mc).
+struct McParkLayout {
+  static constexpr int A = 0, B = 256, GL = 512, SIZE = 528;
+};
+template <int NX, int NU>
+__device__ __forceinline__ void pair1_tail_park_mc(const Dims& d, const int k0, const int b, const int lane_in,
+                                                   const double* buf, const Pair1Hand& hd, const bool left, double* mslot,
+                                                   double* park) {
+  using PY = McPairYLayout<NX>;
+  using PK = McParkLayout;
+  constexpr int KSN = (NX + 3) / 4;
+  int lane = lane_in;
+  asm volatile("" : "+v"(lane));
+  const int li = lane & 15, lk = lane >> 4;
+  const bool hasA = k0 > 0, hasB = k0 + 4 < d.N;
+  const RedSlot<NX> sm = {mslot};
+  double y0[KSN], y1[KSN];
+  acc4_t Z0 = {0.0, 0.0, 0.0, 0.0}, Z1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < KSN; ++q) {
+    y0[q] = buf[PY::tile(0, 0) + (4 * q + lk) * PY::YP + li];
+    y1[q] = buf[PY::tile(0, 1) + (4 * q + lk) * PY::YP + li];
+    Z0[q] = y0[q]; Z1[q] = y1[q];
+  }
+  acc4_t g00, g01, g11, unused;
+  gram_mc<NX, true, true, false, true>(y0, y1, Z0, Z1, g00, g01, unused, g11);
+  if (left) {  // (uniform per wavefront) the group kw .. kw + 3: A side parked, B side = DL | gL | CA of m
+#pragma unroll
+    for (int g = 0; g < 4; ++g) park[PK::A + 64 * g + lane] = g00[g] + hd.park_a[g];
+    if (li < NX) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int r = lk + 4 * g;
+        if (!rows_none<NX>(g) && (rows_all<NX>(g) || r < NX)) {
+          if (li <= r) sm.DL()[r * (r + 1) / 2 + li] = g11[g] + hd.park_b11[g];
+          sm.CA()[li * NX + r] = hasA ? g01[g] : 0.0;
+        }
+      }
+      if (lk == NX % 4) sm.gL()[li] = g01[NX / 4] + hd.cb_t[NX / 4];
+    }
+  } else {  // the group kw + 4 .. kw + 7: A side = DR | gR | CB of m, B side parked
+    if (li <= NX) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int r = lk + 4 * g;
+        if (!rows_none<NX>(g) && (rows_all<NX>(g) || r < NX) && (li <= r || li == NX))
+          (li < NX ? sm.DR() + r * (r + 1) / 2 + li : sm.gR() + r)[0] = g00[g] + hd.park_a[g];
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) park[PK::B + 64 * g + lane] = g11[g] + hd.park_b11[g];
+    if (li < NX) {
+      if (lk == NX % 4) park[PK::GL + li] = g01[NX / 4] + hd.cb_t[NX / 4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int r = lk + 4 * g;
+        if (!rows_none<NX>(g) && (rows_all<NX>(g) || r < NX)) sm.CB()[r * NX + li] = hasB ? g01[g] : 0.0;
+      }
+    }
+  }
+}
+// ... and the Gram half of the tail of m (reduced_eliminate_tail_mc<gram>) that stores the sums.
+template <int NX, int NU>
+__device__ __forceinline__ void reduced_eliminate_gram_park_mc(const Dims& d, const int base, const int b, const int lane,
+                                                               double* red, const double* buf, const double* park) {
+  using P = McWyLayout<NX>;
+  using PK = McParkLayout;
+  constexpr int KS = P::KS;
+  const int N = d.N, T = 8, s = base + 3;
+  const bool hasA = base > 0, hasB = base + T < N, leftchild = (base & T) == 0;
+  const int li = lane & 15, lk = lane >> 4;
+  double y0[KS], y1[KS];
+  acc4_t Z0 = {0.0, 0.0, 0.0, 0.0}, Z1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < KS; ++q) {
+    y0[q] = buf[P::Y0 + (4 * q + lk) * P::YP + li];
+    y1[q] = buf[P::Y1 + (4 * q + lk) * P::YP + li];
+    Z0[q] = y0[q]; Z1[q] = y1[q];
+  }
+  acc4_t pa, pb11, pb01 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int g = 0; g < 4; ++g) { pa[g] = park[PK::A + 64 * g + lane]; pb11[g] = park[PK::B + 64 * g + lane]; }
+  pb01[NX / 4] = park[PK::GL + li];  // (read by the lanes lk == NX % 4, li < NX, which wrote it)
+  const RedSlot<NX> sa = red_slot<NX>(red, d, b, hasA ? base - 1 : s);
+  const RedSlot<NX> sb = red_slot<NX>(red, d, b, hasB ? base + T - 1 : s);
+  acc4_t g00, g01, g11, unused;
+  gram_mc<NX, true, true, false, true>(y0, y1, Z0, Z1, g00, g01, unused, g11);
+  push_mc<NX>(lane, hasA, hasB, leftchild, sa, sb, g00, g01, g11, pa, pb01, pb11, StorePlain(), StorePlain());
+}
+
+// bottom8_reduced_mc<.., P1, L16>: the paired launch above on Bottom8Lds16 -- the same arithmetic in the same order between
+// the same barriers, with the level-2 slot laid over the first wavefront's dead LDS and the groups' outer sides parked in
+// the second wavefront's. No zeroing loop and no barrier behind it: the one part of the slot that no group has a value
+// for -- the coupling to a neighbour that does not exist, CA in the first workgroup of a problem, CB in the last, read and
+// multiplied by zero -- is stored as zeros by the wavefront that stores it otherwise. No atomic add and no wait for
+// store acknowledgements: the level >= 3 slots kw - 1 and kw + 7 get one plain store per element, from the tail of m.
+template <int NX, int NU>
+__device__ __forceinline__ void bottom8_lds16_mc(const Dims& d, const double* __restrict__ AB, const double* __restrict__ QR,
+                                                 const double* __restrict__ rhs, double* red, double* __restrict__ rec,
+                                                 int* __restrict__ info) {
+  using L = Bottom8Lds16<NX, NU>;
+  __shared__ L lds[2];
+  static_assert(sizeof(L) * 2 <= 16384, "ten workgroups per CU");
+  static_assert(McPair1Layout<NX>::SIZE <= L::NBUF, "tile and couplings of t fit the wavefront's buffer");
+  static_assert(L::MSLOT + McParkLayout::SIZE <= L::NBUF + L::NRQ + L::NRH, "the parked tiles fit behind the Y tiles");
+  double* mslot = reinterpret_cast<double*>(&lds[0]) + L::MSLOT;  // live from the groups' tails to the assembly of m's tile
+  double* park = reinterpret_cast<double*>(&lds[1]) + L::MSLOT;   // ... to the tail of m (whose pass uses lds[0].buf alone)
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), b = blockIdx.y;
+  const int kw = (blockIdx.x + d.xoff) * 8;
+  int lane = threadIdx.x & 63;
+  acc4_t c_m = {0.0, 0.0, 0.0, 0.0};
+  Pair1Hand hd;
+  bottom_group_mc<NX, NU, false, true, true, true>(d, kw + 4 * wave, b, lane, AB, QR, rhs, red, rec, nullptr, info, 0, 1,
+                                                   lds[wave], nullptr, nullptr, wave == 0, &c_m, &hd);
+  pair1_exchange_mc<NX>(lane, hd.c_t, hd.ca_t, hd.cb_t, lds[wave].buf);
+  __syncthreads();
+  if (wave == 0) {
+    double* rec_t0 = rec + ((size_t)b * d.N + kw + 1) * (2 * NX * NX + NX);
+    if (chol_pair1_y_mc<NX>(lane, lds[0].buf, lds[1].buf, rec_t0, rec_t0 + 4 * (2 * NX * NX + NX)) &&
+        (lane == 0 || lane == 32))
+      flag_failure(info, d, b);
+  }
+  __syncthreads();
+  pair1_tail_park_mc<NX, NU>(d, kw + 4 * wave, b, lane, lds[wave].buf, hd, wave == 0, mslot, park);
+  __syncthreads();  // (no store of this launch to the slots kw - 1 / kw + 7 so far: nothing to wait for)
+  asm volatile("" : "+v"(lane));
+  if (wave == 0) reduced_eliminate_pass_mc<NX, NU>(d, kw, b, lane, c_m, mslot, info, lds[0].buf);
+  __syncthreads();
+  // (the tail is shared: the first wavefront forms the Gram products and stores the slots, the second X = W'Y and the record)
+  if (wave == 0) reduced_eliminate_gram_park_mc<NX, NU>(d, kw, b, lane, red, lds[0].buf, park);
+  else reduced_eliminate_tail_mc<NX, NU>(d, kw, b, lane, false, red, rec, lds[0].buf);
 }
 
 // The top of the tree in ONE launch: the last three levels (4 + 2 + 1 separators per problem), one workgroup of four
@@ -1000,19 +1175,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 // their slots in `red` (bottom8_reduced_mc: the level-2 separator between its two groups lives in LDS); null: `red`.
 // P1 (with C1, bottom8_reduced_mc alone): the group ends behind its level-0 separators and hands t to the workgroup
 // (Pair1Hand); the pass of t, its Gram products and the pushes follow in the kernel body, between its barriers.
-template <int NX, int NU, bool TREE, bool REDIRECT, bool C1, bool P1>
+template <int NX, int NU, bool TREE, bool REDIRECT, bool C1, bool P1, class LdsT>
 __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, const int b, const int lane,
                                                 const double* __restrict__ AB, const double* __restrict__ QR,
                                                 const double* __restrict__ rhs, double* red, double* __restrict__ rec,
                                                 double* F, int* __restrict__ info, const int store_l, const int compact0,
-                                                ReducedLds<NX, NU>& lds, double* slotA, double* slotB,
+                                                LdsT& lds, double* slotA, double* slotB,
                                                 const bool with_m, acc4_t* c_m, Pair1Hand* hand) {
   static_assert(!P1 || (C1 && REDIRECT && !TREE), "the paired level-1 pass: the fused bottom launch with compact level-1 records");
   constexpr int W = NX + NU, ROWS = 2 * NX + NU, NN = NX * NX, KSN = (NX + 3) / 4;
   constexpr int REC = 2 * NN + NX;
   // row pitch of the staged [A | B]: even W padded by two doubles so that the 16 rows an operand
   // fragment touches fall into distinct LDS banks
-  constexpr int WP = ReducedLds<NX, NU>::WP;
+  constexpr int WP = LdsT::WP;  // (Bottom8Lds16: W + 1 where W + 2 does not fit its buffer)
   // the staged [A | B] is dead once the leaf tiles and coupling fragments are in registers: the
   // core's scratch lies over it
   double* abs_ = lds.buf;            // [A | B] of the four knots
@@ -1048,7 +1223,12 @@ __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, con
 #pragma unroll
       for (int it = 0; it < IA; ++it) {  // unconditional stores on the clamped index: see reduced_separator_mc
         const int e = lane + 64 * it, ec = e < NA ? e : NA - 1, row = ec / (W / 2), c2 = ec - row * (W / 2);
-        reinterpret_cast<double2*>(&abs_[row * WP])[c2] = t[it];
+        if constexpr (WP % 2 == 0) {
+          reinterpret_cast<double2*>(&abs_[row * WP])[c2] = t[it];
+        } else {  // (odd pitch: the rows are 8-byte aligned)
+          abs_[row * WP + 2 * c2] = t[it].x;
+          abs_[row * WP + 2 * c2 + 1] = t[it].y;
+        }
       }
     } else {
       constexpr int NA = 4 * NX * W, IA = (NA + 63) / 64;
@@ -1201,7 +1381,7 @@ __device__ __forceinline__ void bottom_group_mc(const Dims& d, const int k0, con
   double wcol[NX];
   {
     constexpr int TP = 17;
-    static_assert(2 * 16 * TP <= ReducedLds<NX, NU>::NBUF, "both coupling tiles fit the buffer");
+    static_assert(2 * 16 * TP <= LdsT::NBUF, "both coupling tiles fit the buffer");
     double* ta = lds.buf;
     double* tb = lds.buf + 16 * TP;
     wave_lds_sync();  // (the operands of the level-0 tails are in registers)

@@ -31,6 +31,7 @@ struct SmallPlan {
   bool fuse2;    // ... or tree level 2 inside the bottom launch (bottom8_reduced_mc)
   bool compact1; // ... and compact records for the level-1 separators as well (rb_backsub_cols substitutes with L_t)
   bool pair1;    // ... whose two Cholesky passes per workgroup of the fused bottom launch run as one (bottom8_reduced_mc<.., P1>)
+  bool lds16;    // ... in at most 16 KB of LDS per workgroup: ten workgroups per CU (bottom8_reduced_mc<.., P1, L16>)
   int level0;    // first tree level with a launch of its own (reduced_level_mc), up to ...
   int ltop;      // ... the first one inside reduced_top_mc (== K: no such launch), which starts at ...
   int top_l0;    // ... this level (level 2 may have gone with the bottom launch)
@@ -156,6 +157,16 @@ static SmallPlan plan_small(const NdlqrHipCtx* c, const bool strict, const bool 
       // tests/test_compact1_records.py holds them to) and pair on request. NDLQR_PAIR1=0 / 1 overrides.
       p.pair1 = kPair1Fits<NX, NU> && p.fuse2 && p.compact1 &&
                 (c->knobs.pair1 > 0 || (c->knobs.pair1 < 0 && NX == 12 && NU == 4));
+      // The paired launch in 16 KB of LDS (bottom8_reduced_mc<.., P1, L16>, Bottom8Lds16): ten workgroups per CU instead of
+      // eight (five wavefronts per SIMD at <= 90 VGPRs), no zeroing of the level-2 slot, and the level >= 3 slots next to a
+      // workgroup stored once instead of stored, acknowledged and added to atomically. Same records, bit-equal solutions.
+      // The default wherever the paired launch runs -- at each of its three instances the slowest of five runs was below
+      // the parent's fastest on the same box (profiles/lds16_ab.txt): (12,4,256) x 1024 0.5187-0.5336 -> 0.4965-0.5075 ms
+      // pipelined (bottom launch 0.283 -> 0.260: 0.270 from the occupancy alone), (12,4,1024) x 512 1.0640-1.0675 ->
+      // 1.0170-1.0239, the padded (11,3) 0.5132-0.5164 -> 0.4897-0.4942; with NDLQR_FUSE2=1 NDLQR_COMPACT1=1 NDLQR_PAIR1=1
+      // on both sides (10,4) 0.4476-0.4500 -> 0.4195-0.4250 and (9,3) 0.3809-0.3882 -> 0.3690-0.3763.
+      // NDLQR_BOTTOM_LDS16=0 keeps the 20 KB launch.
+      p.lds16 = p.pair1 && c->knobs.bottom_lds16 != 0;
       p.schedule = p.tree ? "reduced-tree"
                    : !p.compact ? "reduced-records"
                    : p.store_l ? "reduced-compact-records" : (p.fuse2 ? "reduced-fused2" : "reduced");
@@ -196,7 +207,11 @@ static int launch_small(NdlqrHipCtx* c, const SmallPlan& plan) {
         } else if (plan.fuse2) {
           bool done = false;
           if constexpr (kPair1Fits<NX, NU>) {
-            if (plan.pair1) {
+            if (plan.lds16) {
+              hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU, true, true, true>), dim3(d.N >> 3, d.batch), dim3(128), 0,
+                                 s.stream, d, c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
+              done = true;
+            } else if (plan.pair1) {
               hipLaunchKernelGGL((ndlqr::bottom8_reduced_mc<NX, NU, true, true>), dim3(d.N >> 3, d.batch), dim3(128), 0, s.stream,
                                  d, c->AB, c->QR, s.rhs, s.red, s.rec, c->info);
               done = true;

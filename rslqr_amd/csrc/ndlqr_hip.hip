@@ -125,6 +125,7 @@ static DevKnobs read_knobs() {
   onoff("NDLQR_BACKSUB_COLS", &k.backsub_cols);
   onoff("NDLQR_COMPACT1", &k.compact1);          // unset: by instance (launch_small)
   onoff("NDLQR_PAIR1", &k.pair1);                // unset: by instance (launch_small)
+  onoff("NDLQR_BOTTOM_LDS16", &k.bottom_lds16);  // unset: by instance (launch_small)
   k.no_mfma = getenv("NDLQR_NO_MFMA") != nullptr;
   k.no_top = getenv("NDLQR_NO_TOP") != nullptr;
   num("NDLQR_TOP_LEVELS", &k.top_levels);
@@ -836,6 +837,7 @@ static SolvePlan plan_solve(const NdlqrHipCtx* c) {
     p.kept.rec_compact = p.small.rec_compact;
     p.kept.rec1_compact = p.small.compact1;
     p.kept.level1_paired = p.small.pair1;
+    p.kept.bottom_lds16 = p.small.lds16;
   } else if ((p.red = plan_reduced_generic(c)).ok) {
     p.family = Family::GenericReduced;
     p.needs_red_generic = true;
@@ -1788,6 +1790,7 @@ const char* ndlqr_hip_schedule(const NdlqrHipCtx* c) { return c ? c->kept.schedu
 int ndlqr_hip_compact_level1(const NdlqrHipCtx* c) { return c && c->kept.rec1_compact ? 1 : 0; }
 
 int ndlqr_hip_level1_paired(const NdlqrHipCtx* c) { return c && c->kept.level1_paired ? 1 : 0; }
+int ndlqr_hip_bottom_lds16(const NdlqrHipCtx* c) { return c && c->kept.bottom_lds16 ? 1 : 0; }
 
 int ndlqr_hip_factors_valid(const NdlqrHipCtx* c) { return c && c->kept.fact_valid ? 1 : 0; }
 
