@@ -475,7 +475,8 @@ int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs); /* 1: dense-cost mode, 0
  * REFUSED by name (NDLQR_ERR_INVALID, ndlqr_hip_last_error()): s->adapt_every > 0 (that field, with rho_min and rho_max, is
  * the box solve's: ndlqr_BatchSetConstraintPenaltyAdaptation is this solve's switch); everything of the box
  * solve -- acceleration, its infeasibility detection (ndlqr_BatchSetInfeasibilityDetection and its two read-outs: this
- * solve has ndlqr_BatchSetConstraintInfeasibilityDetection), polish, box adjoint and bound gradients -- as in dense-cost mode;
+ * solve has ndlqr_BatchSetConstraintInfeasibilityDetection), its polish (this solve has ndlqr_PolishBatchLinConstrained,
+ * below), box adjoint and bound gradients -- as in dense-cost mode;
  * ndlqr_BatchStepAsync. ndlqr_SolveBatchAdjoint refuses after a constrained solve: its adjoint is
  * ndlqr_SolveBatchLinAdjoint (below). */
 int ndlqr_InitializeBatchFlatConstrained(NdLqrBatchSolver* bs, const double* A, const double* B, const double* Q,
@@ -947,6 +948,43 @@ int ndlqr_PolishBatchBoxConstrained(NdLqrBatchSolver* bs, const NdLqrPolishSetti
  * (no solve, step, re-solve, input upload or ndlqr_BatchSetBounds since). g, steps, status: host, pinned or the solver's
  * device memory. Nothing of the polish changes. Blocking; ndlqr_BatchSolveTimeMs reports the device time of the call. */
 int ndlqr_SolveBatchPolishedAdjoint(NdLqrBatchSolver* bs, const double* g, const NdLqrPolishSettings* s, int* steps, int* status);
+/* additive: active-set polish of the latest solve with linear inequality constraints: section
+ * 3.13's polish carried from entries to rows. With G_k = [C_k D_k] (C alone at the last knot), A the active rows and c
+ * the bound each is active at, the constrained solution solves K z + G_A' mu = b, G_A z = c_A in the caller's variables.
+ * ndlqr_PolishBatchLinConstrained reads A off the iterate of the latest ndlqr_SolveBatchLinConstrained (a row is active
+ * at hi when v == hi and y > 0, or lo == hi; at lo when v == lo and y < 0: exact comparisons; mu = rho_p y there), shifts
+ * the costs by sigma_p G_A' G_A (sigma_p = sigma x the largest entry of diag Q, R of problem p / the largest squared norm
+ * of its bounded rows of [C D]), reduces and factors them once per round, and takes up to max_steps steps of
+ *     r_z = b - K z - G_A' mu,  r_c = c_A - G_A z,   K^ delta = r_z + sigma_p G_A' r_c,   z += delta,
+ *     mu_A += sigma_p (G_A delta - r_c),
+ * a step counting only while max(|r_z|, |r_c|) fell at every step so far (the rule of ndlqr_RefineBatch). Each problem's
+ * last accepted iterate is then validated -- mu >= 0 at an upper bound, <= 0 at a lower one, lo <= C x + D u <= hi on the
+ * inactive bounded rows, all exact --; where that fails and rounds remain, wrong-signed rows are released, violated rows
+ * are fixed at the violated bound, and the batch is shifted, reduced and factored again (at most max_rounds times).
+ * steps[p], status[p] (each may be NULL; host, pinned or the solver's device memory): the accepted steps; 1 = polished: the
+ * resident solution is the polished [lambda, x, u], ndlqr_CopyBatchConstraintMultipliers returns the polished mu, and v
+ * (the rows clipped to their bounds) and y = mu / rho_p of the next warm start are the polished point; 2 = not polished
+ * (no accepted step, the set still invalid after the last round, or the constrained solve certified the problem
+ * infeasible) and 3 = not finite (or the constrained solve's status was 3): solution, v, y and mu stay bit for bit what
+ * the constrained solve left. UNLIKE the box polish an active row cannot be put onto its bound by assignment: the active
+ * rows hold to the floor of the residual (the final |r_c|), not bit for bit.
+ *   Returns NDLQR_ERR_INVALID (by name, ndlqr_hip_last_error()) unless the resident solution is that of the latest
+ *   ndlqr_SolveBatchLinConstrained (no solve, polish, input upload, ndlqr_BatchSetRhsFlat or
+ *   ndlqr_BatchSetConstraintBounds since), outside constrained mode, for steps / status in another device's memory, and
+ *   when a kernel would stage more than the LDS of a workgroup (the message has the bytes). A polish counts as a new
+ *   solution; it takes over the shifted-cost, record and reduced-problem buffers of the constrained solve and drops its
+ *   factorisation: ndlqr_hip_factor_count moves by one per round, the next ndlqr_SolveBatchLinConstrained reduces and
+ *   factors once (with warm_start from the polished v, y), and ndlqr_SolveBatchLinAdjoint and
+ *   ndlqr_BatchConstraintGradients refuse until then. A plain ndlqr_SolveBatch afterwards gives the bits it gave before.
+ *   A non-positive pivot returns NDLQR_ERR_NOT_SPD with nothing remembered and the solutions of the constrained solve back
+ *   in place. The residual (rows accumulated in double-double, rounded once) is the same bits in strict and default mode. NULL / zero settings: max_steps 8, max_rounds 3,
+ *   sigma NDLQR_LIN_POLISH_DEFAULT_SIGMA. Blocking; ndlqr_BatchSolveTimeMs then reports the device time of the whole call.
+ * ndlqr_CopyBatchConstraintPolishCodes: the row codes of the latest polish, uint8 [batch][N][p] (0 unbounded, 1 bounded
+ * and inactive, 2 active at lo, 3 active at hi; host or the solver's device memory); refused by name unless the resident
+ * solution is that of a polish. */
+#define NDLQR_LIN_POLISH_DEFAULT_SIGMA 1e8
+int ndlqr_PolishBatchLinConstrained(NdLqrBatchSolver* bs, const NdLqrPolishSettings* s, int* steps, int* status);
+int ndlqr_CopyBatchConstraintPolishCodes(NdLqrBatchSolver* bs, unsigned char* codes);
 void* ndlqr_BatchDeviceContext(NdLqrBatchSolver* bs);      /* NdlqrHipCtx* (ndlqr_hip.h) */
 
 /* Seeded synthetic problem generator (host, bit-reproducible). */

@@ -6,7 +6,7 @@
  * (src/nested_dissection.c, src/linalg_custom.c): everything behind these calls runs on
  * gfx950. Implemented in rslqr_amd/csrc: the context, the solve pipeline and the downloads in ndlqr_hip.hip, each
  * optional feature in a unit of its own (hip_grad.hip: adjoint and gradients, hip_box.hip: bounds, ADMM, polish,
- * hip_refine.hip, hip_cost.hip: dense costs, hip_lin.hip: linear inequality constraints, hip_dense.hip: the Matrix* helpers).
+ * hip_refine.hip, hip_cost.hip: dense costs, hip_lin.hip: linear inequality constraints, hip_lin_polish.hip: their active-set polish, hip_dense.hip: the Matrix* helpers).
  *
  * Device data model (all fp64):
  *   inputs  AB  [batch][N][n][n+m]   row i of knot k = [A_k(i,:) | B_k(i,:)]   (A,B row-major)
@@ -167,6 +167,29 @@ int ndlqr_hip_constraint_gradients(NdlqrHipCtx* ctx, int summed, double* gC, dou
 int ndlqr_hip_download_constraint_adjoint_multipliers(NdlqrHipCtx* ctx, double* nu);
 int ndlqr_hip_download_constraint_adjoint_residuals(NdlqrHipCtx* ctx, double* resid);
 int ndlqr_hip_download_constraint_codes(NdlqrHipCtx* ctx, unsigned char* codes, double* v);
+/* Active-set polish of the latest solve with linear inequality constraints (ndlqr.h: ndlqr_PolishBatchLinConstrained;
+ * DESIGN.md section 3.23). ndlqr_hip_polish_constrained takes the resolved settings (sigma > 0, 1 <= max_steps <= 32,
+ * max_rounds >= 0) and blocks; steps / status [batch] may be NULL (host, pinned or this device's memory).
+ * ndlqr_hip_download_constraint_polish_codes: the row codes of the latest polish, [batch][N][p] bytes (0 unbounded, 1
+ * bounded and inactive, 2 active at lo, 3 active at hi), into host memory or this device's. */
+int ndlqr_hip_polish_constrained(NdlqrHipCtx* ctx, double sigma, int max_steps, int max_rounds, int* steps, int* status);
+int ndlqr_hip_download_constraint_polish_codes(NdlqrHipCtx* ctx, unsigned char* codes);
+/* developer / test hooks, not for production use (HOST memory, blocking copies and repacks on the host; any output may be
+ * NULL). ndlqr_hip_constraint_polish_residual: the residual kernel of the polish alone, in constrained mode, on given z
+ * [batch][nvars] (packed, the caller's variables), mu [batch][N][p], row codes [batch][N][p] bytes and sigma_p [batch]: r
+ * [batch][nvars] = r_z + sigma_p G_A' r_c, rc [batch][N][p] = c_A - G_A z, norms [2][batch] = max(|r_z|, |r_c|) | |r_c|;
+ * poison_pad != 0 puts NaN instead of zero into the pad entries and pad knots of the device's copy of z.
+ * It overwrites the state a polish left (its read-outs refuse afterwards).
+ * ndlqr_hip_download_constraint_polish_state: of the latest polish the candidate zc [batch][nvars], muc [batch][N][p] of
+ * its last formed step, the norm slots of its last round [2][max_steps + 1][batch] (the front of a buffer of
+ * 2 x 33 x batch doubles, which `norms` must hold), sigma_p [batch] and the number of its factorisations. */
+int ndlqr_hip_constraint_polish_residual(NdlqrHipCtx* ctx, const double* z, const double* mu, const unsigned char* codes,
+                                         const double* sig, int poison_pad, double* r, double* rc, double* norms);
+int ndlqr_hip_download_constraint_polish_state(NdlqrHipCtx* ctx, double* zc, double* muc, double* norms, double* sig,
+                                               int* rounds);
+/* Under NDLQR_FLAG_PROFILE: the device time of the latest polish spent in lin_polish_residual | lin_polish_apply_t + the
+ * re-solve | lin_polish_update (out3, ms), and how many of each were added up (launches3, may be NULL). */
+int ndlqr_hip_constraint_polish_phase_ms(NdlqrHipCtx* ctx, double* out3, int* launches3);
 /* Device pointers for zero-copy producers (order: AB, QR, rhs, F, z). Allocates the factor array and
  * sets the pipeline depth to 1, so that z is THE solution buffer from then on. */
 int ndlqr_hip_device_pointers(NdlqrHipCtx* ctx, void** out5);

@@ -341,6 +341,12 @@ def lib():
     proto("ndlqr_PolishBatchBoxConstrained", ci, vp, C.POINTER(NdLqrPolishSettings), C.POINTER(ci), C.POINTER(ci))
     proto("ndlqr_hip_download_polish_codes", ci, vp, C.POINTER(C.c_ubyte))
     proto("ndlqr_SolveBatchPolishedAdjoint", ci, vp, dp, C.POINTER(NdLqrPolishSettings), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_PolishBatchLinConstrained", ci, vp, C.POINTER(NdLqrPolishSettings), C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_CopyBatchConstraintPolishCodes", ci, vp, vp)
+    proto("ndlqr_hip_polish_constrained", ci, vp, cd, ci, ci, C.POINTER(ci), C.POINTER(ci))
+    proto("ndlqr_hip_constraint_polish_residual", ci, vp, dp, dp, C.POINTER(C.c_ubyte), dp, ci, dp, dp, dp)
+    proto("ndlqr_hip_constraint_polish_phase_ms", ci, vp, dp, C.POINTER(ci))
+    proto("ndlqr_hip_download_constraint_polish_state", ci, vp, dp, dp, dp, dp, C.POINTER(ci))
     proto("ndlqr_hip_factor_count", C.c_ulonglong, vp)
     # shim bits used by the benchmark
     proto("ndlqr_hip_set_stream", ci, vp, vp)
@@ -797,6 +803,76 @@ class BatchSolver:
         err = self.L.ndlqr_CopyBatchConstraintCodes(self.h, out.ctypes.data_as(C.c_void_p))
         if err:
             raise RuntimeError("ndlqr_CopyBatchConstraintCodes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    # ---- active-set polish of the solve with linear inequality constraints (include/ndlqr.h:
+    # ndlqr_PolishBatchLinConstrained)
+    def polish_constrained(self, sigma=0.0, max_steps=0, max_rounds=0, steps=None, status=None):
+        """ndlqr_PolishBatchLinConstrained on the latest solve_constrained (0 = the library's default for every setting).
+        steps / status: int32 destinations [batch] (numpy arrays or device memory with `ptr`); default: new numpy arrays.
+        Returns (steps, status): the accepted steps, and 1 = polished, 2 = not polished (the ADMM solution, v, y stay), 3 =
+        not finite. Raises on a nonzero return."""
+        st = NdLqrPolishSettings(sigma, int(max_steps), int(max_rounds))
+        if steps is None:
+            steps = np.zeros(self.batch, dtype=np.int32)
+        if status is None:
+            status = np.zeros(self.batch, dtype=np.int32)
+        as_int = lambda a: (C.cast(C.c_void_p(int(a.ptr)), C.POINTER(C.c_int)) if hasattr(a, "ptr")
+                            else a.ctypes.data_as(C.POINTER(C.c_int)))
+        err = self.L.ndlqr_PolishBatchLinConstrained(self.h, C.byref(st), as_int(steps), as_int(status))
+        if err:
+            raise RuntimeError("ndlqr_PolishBatchLinConstrained failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        return steps, status
+
+    def constraint_polish_codes(self):
+        """ndlqr_CopyBatchConstraintPolishCodes: uint8 [batch, N, p] of the latest polish_constrained -- 0 unbounded, 1
+        bounded and inactive, 2 active at lo, 3 active at hi."""
+        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)), dtype=np.uint8)
+        err = self.L.ndlqr_CopyBatchConstraintPolishCodes(self.h, out.ctypes.data_as(C.c_void_p))
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchConstraintPolishCodes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def constraint_polish_residual(self, z, mu, codes, sig, poison_pad=False):
+        """ndlqr_hip_constraint_polish_residual (test hook): the residual kernel of the polish alone on z [batch, nvars], mu,
+        codes [batch, N, p] and sigma_p [batch]; poison_pad: the pad entries and pad knots of the device's z hold NaN
+        instead of zero. Returns (r [batch, nvars], rc [batch, N, p], norms [2, batch])."""
+        p = getattr(self, "_rows", 1)
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        sig = np.ascontiguousarray(sig, dtype=np.float64)
+        assert z.shape == (self.batch, self.nvars) and mu.shape == codes.shape == (self.batch, self.N, p) and sig.shape == (self.batch,)
+        r, rc, norms = np.zeros_like(z), np.zeros_like(mu), np.zeros((2, self.batch))
+        err = self.L.ndlqr_hip_constraint_polish_residual(self.ctx, _ptr(z), _ptr(mu), codes.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                          _ptr(sig), 1 if poison_pad else 0, _ptr(r), _ptr(rc), _ptr(norms))
+        if err:
+            raise RuntimeError("ndlqr_hip_constraint_polish_residual failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return r, rc, norms
+
+    def constraint_polish_phase_ms(self):
+        """ndlqr_hip_constraint_polish_phase_ms: under FLAG_PROFILE, (ms [3], launches [3]) of the latest polish_constrained --
+        residuals | S' + re-solves | updates."""
+        ms, cnt = np.zeros(3), np.zeros(3, dtype=np.int32)
+        self.L.ndlqr_hip_constraint_polish_phase_ms(self.ctx, _ptr(ms), cnt.ctypes.data_as(C.POINTER(C.c_int)))
+        return ms, cnt
+
+    def constraint_polish_state(self, max_steps=8):
+        """ndlqr_hip_download_constraint_polish_state (test hook): dict of the latest polish_constrained -- zc [batch, nvars]
+        and muc [batch, N, p], the candidate of its last formed step; norms [2, max_steps + 1, batch], the slots of its last
+        round (max_steps: that of the call); sig [batch]; rounds, its factorisations."""
+        p = getattr(self, "_rows", 1)
+        out = dict(zc=np.zeros((self.batch, self.nvars)), muc=np.zeros((self.batch, self.N, p)), sig=np.zeros(self.batch))
+        norms = np.zeros(2 * 33 * self.batch)
+        rounds = C.c_int(0)
+        err = self.L.ndlqr_hip_download_constraint_polish_state(self.ctx, _ptr(out["zc"]), _ptr(out["muc"]), _ptr(norms),
+                                                                _ptr(out["sig"]), C.byref(rounds))
+        if err:
+            raise RuntimeError("ndlqr_hip_download_constraint_polish_state failed: %d (%s)"
+                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        out["norms"] = norms[: 2 * (max_steps + 1) * self.batch].reshape(2, max_steps + 1, self.batch).copy()
+        out["rounds"] = rounds.value
         return out
 
     def constraint_adjoint_iterate(self):

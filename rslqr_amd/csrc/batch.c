@@ -589,6 +589,19 @@ int ndlqr_SolveBatchPolishedAdjoint(NdLqrBatchSolver* bs, const double* g, const
   if (z.max_steps < 0) return NDLQR_ERR_INVALID;
   return ndlqr_hip_solve_polished_adjoint(bs->ctx, g, z.max_steps > 0 ? z.max_steps : 8, steps, status);
 }
+int ndlqr_PolishBatchLinConstrained(NdLqrBatchSolver* bs, const NdLqrPolishSettings* s, int* steps, int* status) {
+  NdLqrPolishSettings z;
+  if (!bs) return NDLQR_ERR_INVALID;
+  memset(&z, 0, sizeof(z));
+  if (s) z = *s;
+  if (!(z.sigma >= 0.0) || z.max_steps < 0 || z.max_rounds < 0) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_polish_constrained(bs->ctx, z.sigma > 0.0 ? z.sigma : NDLQR_LIN_POLISH_DEFAULT_SIGMA,
+                                      z.max_steps > 0 ? z.max_steps : 8, z.max_rounds > 0 ? z.max_rounds : 3, steps, status);
+}
+int ndlqr_CopyBatchConstraintPolishCodes(NdLqrBatchSolver* bs, unsigned char* codes) {
+  if (!bs || !codes) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_download_constraint_polish_codes(bs->ctx, codes);
+}
 int ndlqr_CopyBatchFactors(NdLqrBatchSolver* bs, int p, double* fact) {
   if (!bs || !fact || p < 0 || p >= bs->batch) return NDLQR_ERR_INVALID;
   return ndlqr_hip_download_factors(bs->ctx, p, fact);

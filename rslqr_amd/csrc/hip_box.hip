@@ -693,8 +693,11 @@ static int polish_steps(NdlqrHipCtx* c, hipStream_t st, bool strict, int max_ste
 int ndlqr_hip_polish_box(NdlqrHipCtx* c, double sigma, int max_steps, int max_rounds, int* steps, int* status) {
   if (!c || !(sigma > 0.0) || !(sigma < HUGE_VAL) || max_steps < 1 || max_steps > kPolishMaxSteps || max_rounds < 0)
     return NDLQR_ERR_INVALID;
+  if (c->cost.dense)
+    return refuse("ndlqr_hip_polish_box: not available in dense-cost mode, constrained mode included: bounds on a dense-cost "
+                  "problem are rows of ndlqr_InitializeBatchFlatConstrained, and the polish of that solve is "
+                  "ndlqr_hip_polish_constrained (ndlqr_PolishBatchLinConstrained)");
   if (const int herr = need_unpadded_horizon(c, "ndlqr_hip_polish_box")) return herr;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_polish_box")) return cerr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, "ndlqr_hip_polish_box");
   if (c->box.soln_gen == 0 || c->box.soln_gen != c->soln_gen || !c->box.have_vy || c->inputs_replaced)
     return refuse("ndlqr_hip_polish_box: the resident solution is not that of the latest constrained solve (a solve, step, "

@@ -516,6 +516,45 @@ struct LinInfeasState {
   }
 };
 
+// Active-set polish of the solve with linear inequality constraints (ndlqr_hip_polish_constrained,
+// kernels_lin_polish.hpp). Per row, in the CALLER's horizon [batch][N][p]: the codes (bytes), the
+// accepted multipliers mu, the candidate muc and rc, the constraint residual of the iterate evaluated last. In the device
+// layout [batch][d.N][2 d.n + d.m]: the accepted iterate z and the candidate zc in the caller's variables, z0 (the resident
+// solution as found: the factorisations overwrite it), r (the right-hand side of the correction in the caller's
+// variables), rt (S^' r) and delta (the re-solve's reduced correction). norms: the slots of one round,
+// [2][kPolishMaxSteps + 1][batch] bit patterns -- max(|r_z|, |r_c|), then |r_c| --; sig [batch]; per problem its state (what
+// the caller gets as status), its accepted steps and those of the current round; word: running count | problems whose set
+// changed (h_word: the same, pinned). The shifted costs, records and reduced problem are LinState's: a polish drops the
+// ADMM factorisation. soln_gen: the solution generation the latest polish left (0: none); rounds: its factorisations.
+// lds_asked: as LinState's, for lin_polish_shift_cost | lin_polish_residual | lin_polish_apply_t | lin_polish_update<true> |
+// <false>.
+struct LinPolishState {
+  DevBuf<unsigned char> code;
+  DevBuf<double> mu, muc, rc, z, zc, z0, r, rt, delta, sig;
+  DevBuf<unsigned long long> norms;
+  DevBuf<int> state, steps, here, word;
+  PinnedBuf<int> h_word;
+  int p = 0, rounds = 0;
+  size_t lds_asked[5] = {};
+  unsigned long long soln_gen = 0;
+  double phase_ms[3] = {};  // under NDLQR_FLAG_PROFILE: device time of the latest polish's residuals | S^' + re-solves | updates
+  int phase_spans[3] = {};  // ... and how many spans each adds up
+  static size_t norm_count(const ndlqr::Dims& d) { return 2 * (kPolishMaxSteps + 1) * (size_t)d.batch; }
+  // the buffers that depend on p are allocated again when p changes
+  hipError_t ensure(const ndlqr::Dims& u, const ndlqr::Dims& dd, int rows_per_knot, hipStream_t st) {
+    if (rows_per_knot != p) {
+      code.reset(); mu.reset(); muc.reset(); rc.reset();
+    }
+    p = rows_per_knot;
+    const size_t np = (size_t)u.batch * u.N * p, nz = doubles_z(dd), nb = (size_t)u.batch;
+    return first_error({code.ensure(np), mu.ensure(np), muc.ensure(np), rc.ensure(np), z.ensure(nz), zc.ensure(nz), z0.ensure(nz),
+                        r.ensure_zeroed(nz, st), rt.ensure_zeroed(nz, st),
+                        delta.ensure_zeroed(nz, st),  // (entries a re-solve does not write: the pad rows)
+                        sig.ensure(nb), norms.ensure(norm_count(dd)), state.ensure(nb), steps.ensure(nb), here.ensure(nb),
+                        word.ensure(2), h_word.ensure(2)});
+  }
+};
+
 struct NdlqrHipCtx {
   ndlqr::Dims d = {};   // block sizes of the DEVICE layout (every kernel works on these)
   ndlqr::Dims du = {};  // the caller's block sizes and horizon: the same, or smaller when the problem runs zero-padded into
@@ -584,6 +623,7 @@ struct NdlqrHipCtx {
   LinState lin;
   LinAdjointState alin;
   LinInfeasState lin_infeas;
+  LinPolishState lin_pol;
   unsigned long long factor_count = 0;  // factorisations launched (ndlqr_hip_factor_count)
   // the remembered shifted factorisations (ADMM's and the polish's) no longer match the records / factors
   void forget_shifted() { box.fact = pol.fact = lin.fact = false; }
@@ -591,6 +631,8 @@ struct NdlqrHipCtx {
   bool lin_adjoint_resident() const {
     return alin.gen != 0 && alin.gen == soln_gen && adj.gen == soln_gen && lin.soln_gen == soln_gen && !lin.rhs_new;
   }
+  // the resident solution is that of the latest polish of a solve with linear inequality constraints
+  bool lin_polished() const { return lin_pol.soln_gen != 0 && lin_pol.soln_gen == soln_gen; }
   // grows with every write of a part of the right-hand side (rhs_latest)
   unsigned long long rhs_stamp() const { return rhs_latest[0] + rhs_latest[1] + rhs_latest[2] + rhs_latest[3]; }
   // profile

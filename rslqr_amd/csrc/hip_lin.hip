@@ -4,7 +4,7 @@
 // host side, the kernels of kernels_lin.hpp and kernels_lin_grad.hpp. The reduction kernels it needs belong to hip_cost.hip (cost_reduce_problem,
 // cost_reduce_rhs_to). Infeasibility detection of that solve (ndlqr_hip_set_constraint_infeasibility and its two read-outs;
 // section 3.20, kernels_lin_infeas.hpp) lives in its loop and at the end of this file.
-#include "hip_host.hpp"
+#include "hip_lin_host.hpp"
 #include "kernels_lin_grad.hpp"
 #include "kernels_lin_infeas.hpp"
 
@@ -26,15 +26,6 @@
 // the differences. A certified problem is frozen as status 4 and leaves the running count the host reads anyway. With
 // every == 0 nothing of this is allocated, copied or launched.
 
-// (the kernels hold static LDS next to the dynamic: ask well below the default limit. `asked`: what this context has
-//  asked for this kernel already -- one of LinState::lds_asked --, so that a solve does not ask again)
-template <class Kernel>
-static hipError_t allow_lin_lds(Kernel* kernel, size_t lds, size_t& asked) {
-  if (lds <= 32 * 1024 || lds <= asked) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e == hipSuccess) asked = lds;
-  return e;
-}
 static size_t lin_update_lds_bytes(const ndlqr::Dims& u, int p) { return sizeof(double) * 4 * ndlqr::lin_wave_lds(u.n, u.m, p); }
 
 // Bounds lo, hi [P][N][p] of the caller (P = batch, or 1 when shared): checked (lo <= hi, no NaN) before anything is
@@ -127,58 +118,12 @@ int ndlqr_hip_init_constrained(NdlqrHipCtx* c, const double* A, const double* B,
 
 int ndlqr_hip_is_constrained(const NdlqrHipCtx* c) { return c && c->lin.active ? 1 : 0; }
 
-static int need_constrained(const NdlqrHipCtx* c, const char* who) {
-  if (c->lin.active && c->cost.dense) return NDLQR_OK;
-  return refuse(std::string(who) + ": the solver is not in constrained mode (ndlqr_InitializeBatchFlatConstrained first; "
-                "every other initialiser leaves it)");
-}
-
 int ndlqr_hip_set_constraint_bounds(NdlqrHipCtx* c, const double* lo, const double* hi, int shared) {
   if (!c || !lo || !hi) return NDLQR_ERR_INVALID;
   if (const int merr = need_constrained(c, "ndlqr_hip_set_constraint_bounds")) return merr;
   HIP_TRY(hipSetDevice(c->device));
   return lin_take_bounds(c, "ndlqr_hip_set_constraint_bounds", lo, hi, shared, true);
 }
-
-// The shifted reduced problem in force instead of the plain one, with the flags of the shifted factorisation instead of
-// the caller's: from open() to close(). A scope left without close() (an early return) restores the same: the plain
-// reduced problem of CostState packed again, the caller's flags, and the kept factorisation -- which belongs to the
-// shifted problem -- forgotten for the plain API.
-struct ShiftedReduction {
-  NdlqrHipCtx* c;
-  const unsigned user_flags;
-  bool open_ = false;
-  explicit ShiftedReduction(NdlqrHipCtx* ctx) : c(ctx), user_flags(ctx->flags) {}
-  ShiftedReduction(const ShiftedReduction&) = delete;
-  ~ShiftedReduction() { (void)close(); }
-  // (ndlqr_hip_pack_flat_device is an initialiser: it leaves both modes, which last through this scope)
-  int pack(const double* At, const double* Bt, const double* qt, const double* rt, const double* dt, const double* x0t) {
-    const size_t kn = (size_t)c->du.batch * c->du.N;
-    const int err = ndlqr_hip_pack_flat_device(c, At, Bt, c->cost.ones, c->cost.ones + kn * c->du.n, qt, rt, dt, x0t);
-    c->cost.dense = true;
-    c->lin.active = true;
-    return err;
-  }
-  int open(unsigned flags) {
-    open_ = true;
-    c->flags = flags;
-    return repack();
-  }
-  // the shifted reduced problem packed (again: LinState's arrays were written anew for new penalties)
-  int repack() {
-    const LinState& k = c->lin;
-    return pack(k.At, k.Bt, k.qt, k.rt, k.dt, k.x0t);
-  }
-  int close() {
-    if (!open_) return NDLQR_OK;
-    open_ = false;
-    const CostState& k = c->cost;
-    const int err = pack(k.At, k.Bt, k.qt, k.rt, k.dt, k.x0t);
-    c->flags = user_flags;
-    c->kept.forget_factorisation();
-    return err;
-  }
-};
 
 int ndlqr_hip_solve_constrained(NdlqrHipCtx* c, double rho, double alpha, double eps_abs, double eps_rel, int max_iter,
                                 int check_every, int warm_start, int adapt_every, int* iters, int* status) {
@@ -486,9 +431,13 @@ int ndlqr_hip_download_constraint_multipliers(NdlqrHipCtx* c, double* mu) {
   HIP_TRY(sync_all(c));
   const BufferSet& s = c->set[0];
   out.place(c);
-  hipLaunchKernelGGL(ndlqr::lin_multipliers, dim3((per + 255) / 256, u.batch), dim3(256), 0, s.stream, per,
-                     (const double*)k.rho, (const double*)k.y, out.dev[0]);
-  HIP_TRY(hipGetLastError());
+  if (c->lin_polished()) {  // (a polished solution: its mu where the polish succeeded)
+    HIP_TRY(launch_lin_polish_multipliers(c, out.dev[0], s.stream));
+  } else {
+    hipLaunchKernelGGL(ndlqr::lin_multipliers, dim3((per + 255) / 256, u.batch), dim3(256), 0, s.stream, per,
+                       (const double*)k.rho, (const double*)k.y, out.dev[0]);
+    HIP_TRY(hipGetLastError());
+  }
   err = out.copy(s.stream, false);
   if (err) return err;
   HIP_TRY(hipStreamSynchronize(s.stream));
@@ -552,6 +501,9 @@ static int need_constrained_solution(const NdlqrHipCtx* c, const char* who) {
   if (const int merr = need_constrained(c, who)) return merr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, who);
   const LinState& k = c->lin;
+  if (c->lin_polished())
+    return refuse(std::string(who) + ": the resident solution was polished (ndlqr_hip_polish_constrained), which replaced the "
+                  "ADMM factorisation and v, y: refused until the next ndlqr_hip_solve_constrained");
   if (k.soln_gen == 0 || k.soln_gen != c->soln_gen || !k.fact || !k.have_vy || k.rhs_new)
     return refuse(std::string(who) + ": the resident solution is not that of the latest constrained solve "
                   "(ndlqr_hip_solve_constrained first; a solve, new inputs, a new right-hand side or new bounds came after it)");
@@ -679,6 +631,9 @@ int ndlqr_hip_solve_constrained_adjoint(NdlqrHipCtx* c, const double* g, double 
 static int need_constrained_adjoint(const NdlqrHipCtx* c, const char* who) {
   if (const int merr = need_constrained(c, who)) return merr;
   if (c->z_partial || c->z_invalid) return need_full_solution(c, who);
+  if (c->lin_polished())
+    return refuse(std::string(who) + ": the resident solution was polished (ndlqr_hip_polish_constrained), which replaced the "
+                  "ADMM factorisation and v, y: refused until the next ndlqr_hip_solve_constrained");
   if (!c->lin_adjoint_resident())
     return refuse(std::string(who) + ": no constrained adjoint of the resident solution (ndlqr_hip_solve_constrained_adjoint "
                   "after the latest constrained solve)");

@@ -23,6 +23,7 @@
 
 #include "kernels_box_core.hpp"
 #include "kernels_cost_knot.hpp"
+#include "kernels_lin_shift.hpp"
 
 namespace ndlqr {
 
@@ -32,7 +33,6 @@ __host__ __device__ inline size_t lin_wave_lds(int n, int m, int p) {
   return (size_t)n * cost_ld(n) + (size_t)m * cost_ld(m) + (size_t)m * n + (size_t)p * n + (size_t)p * m + 2 * (size_t)n +
          2 * (size_t)m + 3 * (size_t)p;
 }
-__host__ __device__ inline size_t lin_shift_lds(int n, int m, int p) { return (size_t)p * n + (size_t)p * m + p; }
 
 // Bounds in the caller's layout lo, hi [P][N][p] (P = batch or 1). commit == 0: only check, *bad = 1 when lo > hi (or
 // NaN). commit == 1: copy them to dlo, dhi and the bounded pattern into mask, *changed = 1 where it differs.
@@ -64,6 +64,13 @@ static __global__ void lin_fill_rho(int batch, double value, double* __restrict_
   if (b < batch) rho[b] = value;
 }
 
+// the row weights of the ADMM: the penalty on the bounded rows
+struct LinPenaltyWeight {
+  const double *lo, *hi;  // the knot's bounds
+  double rho;
+  __device__ __forceinline__ double operator()(int r) const { return box_bounded(lo[r], hi[r]) ? rho : 0.0; }
+};
+
 // Q^ = Q + rho[b] C'MC, H^ = H + rho[b] C'MD, R^ = R + rho[b] D'MD of every knot (the last: Q^ alone; H^ = 0, R^ = 1 are written
 // and nothing of the caller's H, R, D is loaded there). One wavefront per (knot, problem); C, D and the row weights
 // rho M go through LDS, the costs come in and leave as they lie. Q, R are read in their lower triangles (as cost_factor
@@ -78,55 +85,9 @@ static __global__ __launch_bounds__(64) void lin_shift_cost(const int n, const i
                                                             const size_t bstride, double* __restrict__ Qs,
                                                             double* __restrict__ Hs, double* __restrict__ Rs) {
   extern __shared__ __attribute__((aligned(16))) double lin_lds[];
-  const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
-  const bool last = k == N - 1;
-  const double rho = rhov[b];
-  const size_t kb = (size_t)b * N + k;
-  double* sC = lin_lds;
-  double* sD = sC + (size_t)p * n;
-  double* sw = sD + (size_t)p * m;
-  {
-    const double* Ck = C + kb * p * n;
-    for (int idx = lane; idx < p * n; idx += 64) sC[idx] = Ck[idx];
-    if (!last) {
-      const double* Dk = D + kb * p * m;
-      for (int idx = lane; idx < p * m; idx += 64) sD[idx] = Dk[idx];
-    }
-    const size_t ob = (size_t)b * bstride + (size_t)k * p;
-    for (int r = lane; r < p; r += 64) sw[r] = box_bounded(lo[ob + r], hi[ob + r]) ? rho : 0.0;
-  }
-  wave_lds_sync();
-  {
-    const double* Qk = Q + kb * n * n;
-    double* Qo = Qs + kb * n * n;
-    for (int idx = lane; idx < n * n; idx += 64) {
-      const int j = idx / n, i = idx - j * n;
-      double s = 0.0;
-      for (int r = 0; r < p; ++r) s = fma(sC[r + p * i] * sw[r], sC[r + p * j], s);
-      Qo[idx] = (i >= j ? Qk[idx] : Qk[j + n * i]) + s;
-    }
-  }
-  double* Ho = Hs + kb * n * m;
-  double* Ro = Rs + kb * m * m;
-  if (last) {
-    for (int idx = lane; idx < n * m; idx += 64) Ho[idx] = 0.0;
-    for (int idx = lane; idx < m * m; idx += 64) Ro[idx] = (idx / m == idx % m) ? 1.0 : 0.0;
-    return;
-  }
-  const double* Hk = H ? H + kb * n * m : nullptr;
-  for (int idx = lane; idx < n * m; idx += 64) {
-    const int j = idx / n, i = idx - j * n;
-    double s = 0.0;
-    for (int r = 0; r < p; ++r) s = fma(sC[r + p * i] * sw[r], sD[r + p * j], s);
-    Ho[idx] = (Hk ? Hk[idx] : 0.0) + s;
-  }
-  const double* Rk = R + kb * m * m;
-  for (int idx = lane; idx < m * m; idx += 64) {
-    const int j = idx / m, i = idx - j * m;
-    double s = 0.0;
-    for (int r = 0; r < p; ++r) s = fma(sD[r + p * i] * sw[r], sD[r + p * j], s);
-    Ro[idx] = (i >= j ? Rk[idx] : Rk[j + m * i]) + s;
-  }
+  const int k = blockIdx.x, b = blockIdx.y;
+  const LinPenaltyWeight weight = {lo + (size_t)b * bstride + (size_t)k * p, hi + (size_t)b * bstride + (size_t)k * p, rhov[b]};
+  lin_shift_cost_knot(lin_lds, n, m, N, p, k, b, weight, Q, H, R, C, D, Qs, Hs, Rs, threadIdx.x);
 }
 
 // One wavefront's LDS for its knot (lin_wave_lds doubles at `base`).
