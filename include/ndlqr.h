@@ -412,7 +412,9 @@ int ndlqr_InitializeBatchFlatDevice(NdLqrBatchSolver* bs, const double* dA, cons
  * ndlqr_BatchGradientsDense's), ndlqr_RefineBatch(Adjoint), ndlqr_BatchKktResiduals,
  * ndlqr_BatchKktResidualVector (their rows are those of the reduced system), ndlqr_BatchSetBounds and every function of the
  * box-constrained solve, the ndlqr_BatchTimeShard* functions, ndlqr_CopyBatchFactors, and of ndlqr_hip.h
- * ndlqr_hip_device_pointers, ndlqr_hip_staged_io / ndlqr_hip_solve_staged, ndlqr_hip_download_rhs_blocks. */
+ * ndlqr_hip_device_pointers, ndlqr_hip_staged_io / ndlqr_hip_solve_staged, ndlqr_hip_download_rhs_blocks.
+ * (The step and the slices of this mode come under names of their own: ndlqr_BatchStepAsyncDense,
+ * ndlqr_SolveBatchSlicesAsyncDense, ndlqr_CopyBatchSolutionSlicesDense, below.) */
 int ndlqr_InitializeBatchFlatDense(NdLqrBatchSolver* bs, const double* A, const double* B, const double* Q,
                                    const double* H, const double* R, const double* q, const double* r,
                                    const double* d, const double* x0);
@@ -554,6 +556,21 @@ int ndlqr_BatchSetStepSelection(NdLqrBatchSolver* bs, int knot0, int nknots, uns
  * ndlqr_BatchSynchronize), and like a step with NDLQR_SOLN_ONLY it leaves nothing but that slice behind. */
 int ndlqr_SolveBatchSlicesAsync(NdLqrBatchSolver* bs, int knot0, int nknots, unsigned blocks, double* out);
 int ndlqr_CopyBatchSolutionSlices(NdLqrBatchSolver* bs, int knot0, int nknots, unsigned blocks, double* out);
+/* The MPC step and the slices of a DENSE-COST problem (ndlqr_InitializeBatchFlatDense), everything in the caller's
+ * variables. ndlqr_BatchStepAsyncDense is ndlqr_BatchStepAsync for that mode: the right-hand side up, factor + solve (the
+ * re-solve on kept records under NDLQR_FLAG_KEEP_RECORDS), the solutions down, asynchronously, two steps in flight, the
+ * same memories (pinned, pageable -- which blocks --, the solver's device), ndlqr_BatchSynchronize(Previous) as for the
+ * plain step. x0 and out are required; q and r are replaced TOGETHER or not at all (the reduced q needs both); d may be
+ * NULL. What comes down is an argument, not the selection of ndlqr_BatchSetStepSelection: knots [knot0, knot0 + nknots),
+ * blocks = NDLQR_SOLN_* -> out [batch][nknots][width] (u of the last knot: zero), or with nknots == 0 every solution
+ * [batch][nvars]. An x0-only step for (0, 1, NDLQR_SOLN_INPUT | NDLQR_SOLN_ONLY) touches one knot per problem on the way up
+ * and one on the way down. ndlqr_SolveBatchSlicesAsyncDense / ndlqr_CopyBatchSolutionSlicesDense: the dense-cost forms of
+ * the two slice functions above. Each of the three refuses by name (NDLQR_ERR_INVALID; ndlqr_hip_last_error() opens with
+ * the name of the function of ndlqr_hip.h behind it) outside dense-cost mode, in constrained mode, and for q without r. */
+int ndlqr_BatchStepAsyncDense(NdLqrBatchSolver* bs, const double* q, const double* r, const double* d, const double* x0,
+                              int knot0, int nknots, unsigned blocks, double* out);
+int ndlqr_SolveBatchSlicesAsyncDense(NdLqrBatchSolver* bs, int knot0, int nknots, unsigned blocks, double* out);
+int ndlqr_CopyBatchSolutionSlicesDense(NdLqrBatchSolver* bs, int knot0, int nknots, unsigned blocks, double* out);
 /* Time-axis sharding: one problem (or a small batch) over G ranks, rank g on knots [g N / G, (g + 1) N / G) -- for jobs
  * with fewer problems than GPUs (details and limits: ndlqr_hip.h). Per solve, on every rank:
  * Factor -> ExportTop(buf) -> sum buf over the ranks -> ImportTop(buf) -> Finish -> ndlqr_BatchSynchronize. */

@@ -88,7 +88,9 @@ int ndlqr_hip_pack_flat_device(NdlqrHipCtx* ctx, const double* A, const double* 
  * solve (ndlqr_hip_solve_box(_ex), ndlqr_hip_solve_box_adjoint, ndlqr_hip_bound_gradients, ndlqr_hip_polish_box,
  * ndlqr_hip_solve_polished_adjoint, ndlqr_hip_set_box_infeasibility / ndlqr_hip_set_box_acceleration when switching on, and
  * the box downloads), the ndlqr_hip_time_shard_* functions, ndlqr_hip_download_factors, ndlqr_hip_download_rhs_blocks,
- * ndlqr_hip_device_pointers, ndlqr_hip_staged_io and ndlqr_hip_solve_staged.
+ * ndlqr_hip_device_pointers, ndlqr_hip_staged_io and ndlqr_hip_solve_staged. (The step and the slices have dense-cost
+ * forms under names of their own: ndlqr_hip_step_dense_async, ndlqr_hip_solve_slices_dense_async,
+ * ndlqr_hip_download_selection_dense.)
  * ndlqr_hip_set_rhs_dense: a new flat right-hand side q, r, d, x0 in the caller's variables (same memories).
  * ndlqr_hip_download_cost_reduction (read-out for the tests): the records L [batch][N][n*n], LR [batch][N][m*m], G
  * [batch][N][m*n] (column-major; the triangles with zeros above; LR = 1, G = 0 at the last knot) and the reduced problem in
@@ -356,6 +358,29 @@ int ndlqr_hip_set_step_selection(NdlqrHipCtx* ctx, int knot0, int nknots, unsign
 /* Factor + solve of the resident problems delivering a slice alone (ndlqr.h: ndlqr_SolveBatchSlicesAsync). */
 int ndlqr_hip_solve_slices_async(NdlqrHipCtx* ctx, int knot0, int nknots, unsigned blocks, double* out);
 int ndlqr_hip_download_selection(NdlqrHipCtx* ctx, int knot0, int nknots, unsigned blocks, double* out);
+/* The same three for a DENSE-COST problem (ndlqr_hip_init_dense; DESIGN.md section 3.16, "The asynchronous step"), all in
+ * the caller's variables. ndlqr_hip_step_dense_async is ndlqr_hip_step_async with S' on the way up and S on the way down,
+ * each by one kernel between the caller's arrays and the device layout on the step's stream (cost_pack_rhs,
+ * cost_deliver_slice): x0 and `out` are required, q and r are replaced together or not at all (q~ = L^-1 (q - G' r) needs
+ * both), d may be NULL; an x0-only step touches one knot per problem. The slice is an argument: knots
+ * [knot0, knot0 + nknots), blocks = NDLQR_SOLN_* (with NDLQR_SOLN_ONLY nothing but those knots is computed), out
+ * [batch][nknots][width]; nknots == 0: the whole vectors [batch][nvars]. u is computed from both reduced blocks whether or
+ * not the state block is selected; u of the last knot comes out as zero. Memories, the two steps in flight,
+ * ndlqr_hip_synchronize / ndlqr_hip_synchronize_previous and the re-solve under NDLQR_FLAG_KEEP_RECORDS are those of the
+ * plain step. ndlqr_hip_solve_slices_dense_async / ndlqr_hip_download_selection_dense: the twins of the two slice functions.
+ * All three refuse by name (NDLQR_ERR_INVALID, the message opens with the function's name) outside dense-cost mode, in
+ * constrained mode (ndlqr_hip_init_constrained), on a time-axis shard, for another device's memory and for a slice that is
+ * none. ndlqr_hip_download_cost_reduction keeps reporting the reduced right-hand side of the latest initialiser /
+ * ndlqr_hip_set_rhs_dense: steps write the device right-hand side directly. */
+int ndlqr_hip_step_dense_async(NdlqrHipCtx* ctx, const double* q, const double* r, const double* d, const double* x0,
+                               int knot0, int nknots, unsigned blocks, double* out);
+int ndlqr_hip_solve_slices_dense_async(NdlqrHipCtx* ctx, int knot0, int nknots, unsigned blocks, double* out);
+int ndlqr_hip_download_selection_dense(NdlqrHipCtx* ctx, int knot0, int nknots, unsigned blocks, double* out);
+/* Read-out for the tests, every mode: the latest right-hand side as it lies on the device -- [batch][N'][2 n' + m'] in the
+ * device's block sizes and horizon, pad rows and tail knots included, ndlqr_hip_rhs_raw_doubles of them -- into HOST
+ * memory. Waits for everything in flight and brings the current buffer set's copy up to date first. */
+int ndlqr_hip_download_rhs_raw(NdlqrHipCtx* ctx, double* out);
+size_t ndlqr_hip_rhs_raw_doubles(const NdlqrHipCtx* ctx);
 /* Time-axis sharding: ONE problem (or a small batch) solved by G ranks, each working on a chunk of
  * N / G consecutive knots of the horizon -- for jobs with fewer problems than GPUs; the batch axis stays the sharding
  * unit otherwise. Every rank holds the whole problem's inputs (upload as usual) and runs, for its chunk g:

@@ -292,6 +292,11 @@ def lib():
     proto("ndlqr_BatchSetStepSelection", ci, vp, ci, ci, C.c_uint)
     proto("ndlqr_CopyBatchSolutionSlices", ci, vp, ci, ci, C.c_uint, dp)
     proto("ndlqr_SolveBatchSlicesAsync", ci, vp, ci, ci, C.c_uint, dp)
+    proto("ndlqr_BatchStepAsyncDense", ci, vp, dp, dp, dp, dp, ci, ci, C.c_uint, dp)
+    proto("ndlqr_SolveBatchSlicesAsyncDense", ci, vp, ci, ci, C.c_uint, dp)
+    proto("ndlqr_CopyBatchSolutionSlicesDense", ci, vp, ci, ci, C.c_uint, dp)
+    proto("ndlqr_hip_download_rhs_raw", ci, vp, dp)
+    proto("ndlqr_hip_rhs_raw_doubles", C.c_size_t, vp)
     proto("ndlqr_BatchTimeShardTopDoubles", ci, vp, ci)
     proto("ndlqr_BatchTimeShardFactor", ci, vp, ci, ci)
     proto("ndlqr_BatchTimeShardExportTop", ci, vp, ci, vp)
@@ -550,7 +555,9 @@ class BatchSolver:
     def cost_reduction(self):
         """ndlqr_hip_download_cost_reduction (read-out for the tests): dict of numpy arrays -- the records L [batch, N, n*n],
         LR [batch, N, m*m], G [batch, N, m*n] (column-major per knot) and the reduced unit-cost problem At, Bt, qt, rt, dt,
-        x0t in the flat layout of initialize_flat. Raises outside dense-cost mode."""
+        x0t in the flat layout of initialize_flat. Raises outside dense-cost mode. qt, rt, dt, x0t are those of the latest
+        initialize_flat_dense / set_rhs_flat: the steps of step_dense_async reduce straight into the device right-hand side
+        (rhs_raw() shows it) and bypass these arrays."""
         n, m, N, bt = self.n, self.m, self.N, self.batch
         out = dict(L=np.zeros((bt, N, n * n)), LR=np.zeros((bt, N, m * m)), G=np.zeros((bt, N, m * n)),
                    At=np.zeros((bt, N, n * n)), Bt=np.zeros((bt, N, n * m)), qt=np.zeros((bt, N, n)), rt=np.zeros((bt, N, m)),
@@ -979,6 +986,60 @@ class BatchSolver:
         ptr = lambda a: None if a is None else (C.cast(C.c_void_p(a.ptr), dp) if isinstance(a, DeviceArray) else _ptr(a))
         self._step_refs = self._step_refs[-1:] + [(q, r, d, x0, soln)]
         return self.L.ndlqr_BatchStepAsync(self.h, ptr(q), ptr(r), ptr(d), ptr(x0), ptr(soln))
+
+    # ---- the step and the slices in dense-cost mode (include/ndlqr.h: ndlqr_BatchStepAsyncDense)
+    def step_dense_async(self, q, r, d, x0, out, selection=None):
+        """ndlqr_BatchStepAsyncDense: step_async for a dense-cost problem, in the caller's variables. q and r come together
+        or are both None (unchanged), d may be None, x0 and out are required. selection = (knot0, nknots, blocks) delivers
+        that slice, [batch, nknots, width] (with SOLN_ONLY in blocks nothing else is computed); None: every solution
+        [batch, nvars]. Arrays as for step_async: pinned_empty() ones, DeviceArray objects, or pageable numpy arrays (the
+        call then blocks); the solver holds references to those of the two steps that can be in flight. Returns the error
+        code; ValueError for arrays of the wrong size, q without r, or a refusal of the library (its message)."""
+        n, m, N, bt = self.n, self.m, self.N, self.batch
+        if (q is None) != (r is None):
+            raise ValueError("step_dense_async: q and r are replaced together or not at all")
+        if x0 is None or out is None:
+            raise ValueError("step_dense_async: x0 and out are required")
+        k0, nk, blocks = (0, 0, 7) if selection is None else selection
+        out_size = bt * self.nvars if nk == 0 else bt * nk * self.slice_width(blocks)
+        ptrs = [None if a is None else _any_ptr(a, size) for a, size in
+                ((q, bt * N * n), (r, bt * N * m), (d, bt * N * n), (x0, bt * n), (out, out_size))]
+        self._step_refs = self._step_refs[-1:] + [(q, r, d, x0, out)]
+        err = self.L.ndlqr_BatchStepAsyncDense(self.h, *ptrs[:4], k0, nk, blocks, ptrs[4])
+        if err == ERR_INVALID:
+            raise ValueError("ndlqr_BatchStepAsyncDense: %s" % self.L.ndlqr_hip_last_error().decode())
+        return err
+
+    def solve_slices_dense_async(self, knot0, nknots, blocks, out):
+        """ndlqr_SolveBatchSlicesAsyncDense: solve_slices_async for a dense-cost problem -- the slice in the caller's
+        variables into `out` ([batch, nknots, width]); complete after synchronize()."""
+        ptr = _any_ptr(out, self.batch * max(nknots, 0) * self.slice_width(blocks))
+        self._step_refs = self._step_refs[-1:] + [(out,)]
+        err = self.L.ndlqr_SolveBatchSlicesAsyncDense(self.h, knot0, nknots, blocks, ptr)
+        if err == ERR_INVALID:
+            raise ValueError("ndlqr_SolveBatchSlicesAsyncDense: %s" % self.L.ndlqr_hip_last_error().decode())
+        return err
+
+    def solution_slices_dense(self, knot0, nknots, blocks, out=None):
+        """ndlqr_CopyBatchSolutionSlicesDense: [batch, nknots, width] of the latest solve of a dense-cost problem, in the
+        caller's variables."""
+        if out is None:
+            out = np.zeros((self.batch, max(nknots, 0), self.slice_width(blocks)))
+        ptr = _any_ptr(out, self.batch * max(nknots, 0) * self.slice_width(blocks))
+        err = self.L.ndlqr_CopyBatchSolutionSlicesDense(self.h, knot0, nknots, blocks, ptr)
+        if err:
+            raise RuntimeError("ndlqr_CopyBatchSolutionSlicesDense failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
+
+    def rhs_raw(self):
+        """ndlqr_hip_download_rhs_raw (read-out for the tests): the latest right-hand side as it lies on the device,
+        [batch, doubles per problem] in the device's block sizes and horizon, pad rows and tail knots included. Waits for
+        everything in flight. Every mode."""
+        out = np.zeros((self.batch, int(self.L.ndlqr_hip_rhs_raw_doubles(self.ctx)) // self.batch))
+        err = self.L.ndlqr_hip_download_rhs_raw(self.ctx, _ptr(out))
+        if err:
+            raise RuntimeError("ndlqr_hip_download_rhs_raw failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        return out
 
     # ---- time-axis sharding (one problem over G ranks; include/ndlqr_hip.h)
     def time_shard_top_doubles(self, G):

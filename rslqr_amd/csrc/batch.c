@@ -400,6 +400,16 @@ int ndlqr_SolveBatchSlicesAsync(NdLqrBatchSolver* bs, int knot0, int nknots, uns
 int ndlqr_CopyBatchSolutionSlices(NdLqrBatchSolver* bs, int knot0, int nknots, unsigned blocks, double* out) {
   return bs ? ndlqr_hip_download_selection(bs->ctx, knot0, nknots, blocks, out) : NDLQR_ERR_INVALID;
 }
+int ndlqr_BatchStepAsyncDense(NdLqrBatchSolver* bs, const double* q, const double* r, const double* d, const double* x0,
+                              int knot0, int nknots, unsigned blocks, double* out) {
+  return bs ? ndlqr_hip_step_dense_async(bs->ctx, q, r, d, x0, knot0, nknots, blocks, out) : NDLQR_ERR_INVALID;
+}
+int ndlqr_SolveBatchSlicesAsyncDense(NdLqrBatchSolver* bs, int knot0, int nknots, unsigned blocks, double* out) {
+  return bs ? ndlqr_hip_solve_slices_dense_async(bs->ctx, knot0, nknots, blocks, out) : NDLQR_ERR_INVALID;
+}
+int ndlqr_CopyBatchSolutionSlicesDense(NdLqrBatchSolver* bs, int knot0, int nknots, unsigned blocks, double* out) {
+  return bs ? ndlqr_hip_download_selection_dense(bs->ctx, knot0, nknots, blocks, out) : NDLQR_ERR_INVALID;
+}
 int ndlqr_BatchTimeShardTopDoubles(NdLqrBatchSolver* bs, int G) {
   return bs ? ndlqr_hip_time_shard_top_doubles(bs->ctx, G) : NDLQR_ERR_INVALID;
 }

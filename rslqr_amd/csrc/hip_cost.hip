@@ -44,12 +44,41 @@ struct CostPhase {
 // dense-cost mode: `vec`, the packed [count][nvars] vectors of problems [p0, p0 + count) in the reduced variables, becomes
 // the same in the caller's (S, in place)
 hipError_t cost_map_back(NdlqrHipCtx* c, double* vec, int p0, unsigned count, hipStream_t st) {
-  const ndlqr::Dims& u = c->du;
   CostPhase phase(c, st, 2);
-  const hipError_t e = launch_cost(ndlqr::cost_apply, ndlqr::cost_apply_lds(u.n, u.m), u, count, st, u.n, u.m, u.N,
-                                   c->cost.rec + (size_t)p0 * u.N * CostState::record_doubles(u), vec);
+  const hipError_t e = cost_apply_on(c, vec, p0, count, st);
   phase.stop();
   return e;
+}
+// ... the launch alone, for the asynchronous step: no phase timing, nothing waits
+hipError_t cost_apply_on(NdlqrHipCtx* c, double* vec, int p0, unsigned count, hipStream_t st) {
+  const ndlqr::Dims& u = c->du;
+  return launch_cost(ndlqr::cost_apply, ndlqr::cost_apply_lds(u.n, u.m), u, count, st, u.n, u.m, u.N,
+                     c->cost.rec + (size_t)p0 * u.N * CostState::record_doubles(u), vec);
+}
+// The asynchronous step's way up: S' of the parts `parts` (bits q 1, r 2 -- together --, d 4, x0 8) of the caller's flat
+// q, r, d, x0 (device-readable) straight into the device right-hand side `rhs` of one buffer set, on `st`. One knot per
+// problem where x0 alone is replaced.
+hipError_t cost_pack_rhs_on(NdlqrHipCtx* c, unsigned parts, const double* q, const double* r, const double* d, const double* x0,
+                            double* rhs, hipStream_t st) {
+  const ndlqr::Dims& u = c->du;
+  const size_t lds = sizeof(double) * ndlqr::cost_apply_lds(u.n, u.m);
+  const hipError_t e = allow_dynamic_lds(ndlqr::cost_pack_rhs, lds);
+  if (e != hipSuccess) return e;
+  const unsigned knots = (parts & 7u) ? (unsigned)u.N : 1u;
+  hipLaunchKernelGGL(ndlqr::cost_pack_rhs, dim3(knots, u.batch), dim3(64), lds, st, u, c->d, parts, (const double*)c->cost.rec.get(),
+                     q, r, d, x0, rhs);
+  return hipGetLastError();
+}
+// ... and its way down: S of the slice `sel` (non-empty) of the reduced solutions z (device layout) into dst
+// [batch][nknots][width] (this device's memory), on `st`
+hipError_t cost_deliver_slice_on(NdlqrHipCtx* c, const KnotSlice& sel, const double* z, double* dst, hipStream_t st) {
+  const ndlqr::Dims& u = c->du;
+  const size_t lds = sizeof(double) * ndlqr::cost_apply_lds(u.n, u.m);
+  const hipError_t e = allow_dynamic_lds(ndlqr::cost_deliver_slice, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ndlqr::cost_deliver_slice, dim3(sel.nknots, u.batch), dim3(64), lds, st, u, c->d, sel.knot0, sel.nknots,
+                     sel.blocks & 7u, (const double*)c->cost.rec.get(), z, dst);
+  return hipGetLastError();
 }
 // ... and the packed [batch][nvars] vector `vec` in the caller's variables becomes S' vec (in place): the adjoint's g
 hipError_t cost_reduce_vector(NdlqrHipCtx* c, double* vec, hipStream_t st) {

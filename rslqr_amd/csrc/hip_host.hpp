@@ -121,6 +121,15 @@ int launch_residual_dd_on(NdlqrHipCtx* c, const double* QR, const double* rhs, c
 // hip_cost.hip, dense-cost mode: `vec`, the packed [count][nvars] vectors of problems [p0, p0 + count) in the reduced
 // variables, becomes the same in the caller's (S, in place)
 hipError_t cost_map_back(NdlqrHipCtx* c, double* vec, int p0, unsigned count, hipStream_t st);
+// ... the same launch without the phase timing of NDLQR_FLAG_PROFILE (which waits): what an asynchronous step uses
+hipError_t cost_apply_on(NdlqrHipCtx* c, double* vec, int p0, unsigned count, hipStream_t st);
+// ... the asynchronous step's way up: S' of the parts `parts` (bits q 1, r 2 -- together --, d 4, x0 8) of the caller's flat
+// q, r, d, x0 (device-readable; a part not replaced may be null) straight into the device right-hand side `rhs`
+hipError_t cost_pack_rhs_on(NdlqrHipCtx* c, unsigned parts, const double* q, const double* r, const double* d, const double* x0,
+                            double* rhs, hipStream_t st);
+// ... and its way down: S of the non-empty slice `sel` of the reduced solutions z (device layout) into dst
+// [batch][nknots][width] (this device's memory)
+hipError_t cost_deliver_slice_on(NdlqrHipCtx* c, const KnotSlice& sel, const double* z, double* dst, hipStream_t st);
 // ... and the packed [batch][nvars] vector `vec` in the caller's variables becomes S' vec (in place): the adjoint's g
 hipError_t cost_reduce_vector(NdlqrHipCtx* c, double* vec, hipStream_t st);
 // ... S' (records `rec`) of the flat right-hand side q, r, d, x0 (device) into the flat arrays qt, rt, dt, x0t

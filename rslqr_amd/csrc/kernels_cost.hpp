@@ -14,6 +14,10 @@
 //     cost_apply_t     S' on a right-hand side: flat (q, r, d, x0) -> flat (q~, r~, d~, x0~), or a packed [count][nvars]
 //                      vector in [lambda x u] order in place (the adjoint's g)
 //     cost_apply       S on a packed [count][nvars] solution, in place
+// and the two of the asynchronous step (ndlqr_hip_step_dense_async), which work between the caller's arrays and the device
+// layout directly:
+//     cost_pack_rhs       S' on the flat (q, r, d, x0), or a part of them -> the device right-hand side of a buffer set
+//     cost_deliver_slice  S on the z blocks of a knot range -> the packed slice [count][nknots][width]
 // The per-knot pieces -- record layout, triangular solves, the bodies of S and S' -- live in kernels_cost_knot.hpp, which
 // kernels_lin.hpp shares.
 // A, B, H, R, r, d of the caller's last knot are never loaded (every such load sits behind the wave-uniform test of the
@@ -275,6 +279,96 @@ static __global__ __launch_bounds__(64) void cost_apply(const int n, const int m
     for (int i = lane; i < m; i += 64) su[i] = zu[i];
   wave_lds_sync();
   cost_knot_S<true>(n, m, last, sL, sLR, sG, sl, sx, su, zl, zx, zu, lane);
+}
+
+// The part mask of cost_pack_rhs, the bits of copy_rhs_parts_generic: q and r (the x and u rows of every knot; always
+// together, q~_k = L_k^-1 (q_k - G_k' r_k) needs both), d (the lambda rows of the knots >= 1), x0 (the lambda rows of knot 0)
+constexpr unsigned COST_PART_QR = 3u, COST_PART_D = 4u, COST_PART_X0 = 8u;
+
+// S' on the caller's flat right-hand side, packed in the same pass: the parts of `parts` of q, d [batch][du.N][n], r
+// [batch][du.N][m], x0 [batch][n] (this device's memory or a device-side view of pinned memory; a part that is not
+// replaced may be null) -> the entries of the device right-hand side rhs [batch][d.N][d.rows] that pack_rhs_one /
+// pack_rhs_one_hp write of S' b: negated, lambda | x | u rows at 0 | d.n | 2 d.n, the u rows of the caller's last knot
+// zero. Nothing else of rhs -- the pad rows, the tail knots of a padded horizon, the parts not in `parts` -- is touched,
+// and nothing goes through arrays that exist once per solver: two steps in flight on two streams share nothing.
+// grid (du.N, batch), or (1, batch) where `parts` is x0 alone; block 64, dynamic LDS cost_apply_lds(n, m) doubles. The
+// arithmetic is cost_knot_St's, so the bits are those of cost_apply_t followed by the pack kernel.
+static __global__ __launch_bounds__(64) void cost_pack_rhs(const Dims du, const Dims d, const unsigned parts,
+                                                           const double* __restrict__ rec, const double* q, const double* r,
+                                                           const double* dd, const double* x0, double* __restrict__ rhs) {
+  extern __shared__ __attribute__((aligned(16))) double cost_lds[];
+  const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const int n = du.n, m = du.m, N = du.N;
+  const bool last = k == N - 1;
+  const bool qr = (parts & COST_PART_QR) != 0, lam = (parts & (k == 0 ? COST_PART_X0 : COST_PART_D)) != 0;
+  if (!qr && !lam) return;  // (wave-uniform)
+  const size_t kb = (size_t)b * N + k;
+  const int ldn = cost_ld(n), ldm = cost_ld(m);
+  double* sL = cost_lds;
+  double* sLR = sL + (size_t)n * ldn;
+  double* sG = sLR + (size_t)m * ldm;
+  double* sl = sG + (size_t)m * n;
+  double* sx = sl + n;
+  double* su = sx + n;
+  double* so = su + m;  // L' sl
+  // (a knot whose x and u rows stay runs as a last knot on a zero x block: L and the lambda rows alone)
+  const bool tail = last || !qr;
+  cost_stage_record(rec + kb * cost_record_doubles(n, m), n, m, !tail, sL, sLR, sG, lane);
+  const double* il = k == 0 ? x0 + (size_t)b * n : dd + (kb - 1) * n;
+  for (int i = lane; i < n; i += 64) {
+    sl[i] = lam ? il[i] : 0.0;
+    sx[i] = qr ? q[kb * n + i] : 0.0;
+  }
+  if (!tail)
+    for (int i = lane; i < m; i += 64) su[i] = r[kb * m + i];
+  wave_lds_sync();
+  cost_knot_St<true, false>(n, m, tail, sL, sLR, sG, sl, sx, su, so, nullptr, nullptr, lane);
+  wave_lds_sync();
+  double* out = rhs + ((size_t)b * d.N + k) * d.rows;
+  if (lam)
+    for (int i = lane; i < n; i += 64) out[i] = -so[i];
+  if (qr) {
+    for (int i = lane; i < n; i += 64) out[d.n + i] = -sx[i];
+    for (int i = lane; i < m; i += 64) out[2 * d.n + i] = last ? 0.0 : -su[i];
+  }
+}
+
+// S on a slice of the solutions, packed in the same pass: the z blocks of the knots [knot0, knot0 + nknots) of z
+// [batch][d.N][d.rows] (the reduced variables, lambda | x | u at 0 | d.n | 2 d.n) through that knot's record into dst
+// [batch][nknots][width], of each knot the blocks of `blocks` (bit 0: lambda, 1: state, 2: input) in the order of
+// pack_selection_generic. u = L_R^-T nu - G L^-T xi is computed from both whether or not the state block is selected; u
+// of the caller's last knot comes out as exact zero. grid (nknots, batch), block 64, dynamic LDS cost_apply_lds(n, m)
+// doubles. The arithmetic is cost_knot_S's, so the bits are those of cost_apply on the packed vector.
+static __global__ __launch_bounds__(64) void cost_deliver_slice(const Dims du, const Dims d, const int knot0, const int nknots,
+                                                                const unsigned blocks, const double* __restrict__ rec,
+                                                                const double* __restrict__ z, double* __restrict__ dst) {
+  extern __shared__ __attribute__((aligned(16))) double cost_lds[];
+  const int kk = blockIdx.x, k = knot0 + kk, b = blockIdx.y, lane = threadIdx.x;
+  const int n = du.n, m = du.m, N = du.N;
+  const bool last = k == N - 1;
+  const size_t kb = (size_t)b * N + k;
+  const int ldn = cost_ld(n), ldm = cost_ld(m);
+  double* sL = cost_lds;
+  double* sLR = sL + (size_t)n * ldn;
+  double* sG = sLR + (size_t)m * ldm;
+  double* sl = sG + (size_t)m * n;
+  double* sx = sl + n;
+  double* su = sx + n;
+  double* so = su + m;  // L sl
+  const int nl = (blocks & 1u) ? n : 0, nxs = (blocks & 2u) ? n : 0, nu = (blocks & 4u) ? m : 0;
+  const bool rest = !last && nu > 0;  // (the state block alone needs L only)
+  cost_stage_record(rec + kb * cost_record_doubles(n, m), n, m, rest, sL, sLR, sG, lane);
+  const double* zk = z + ((size_t)b * d.N + k) * d.rows;
+  for (int i = lane; i < n; i += 64) { sl[i] = zk[i]; sx[i] = zk[d.n + i]; }
+  if (rest)
+    for (int i = lane; i < m; i += 64) su[i] = zk[2 * d.n + i];
+  wave_lds_sync();
+  cost_knot_S<true>(n, m, !rest, sL, sLR, sG, sl, sx, su, so, sx, su, lane);
+  wave_lds_sync();
+  double* out = dst + ((size_t)b * nknots + kk) * (nl + nxs + nu);
+  for (int i = lane; i < nl; i += 64) out[i] = so[i];
+  for (int i = lane; i < nxs; i += 64) out[nl + i] = sx[i];
+  for (int i = lane; i < nu; i += 64) out[nl + nxs + i] = last ? 0.0 : su[i];
 }
 
 }  // namespace ndlqr

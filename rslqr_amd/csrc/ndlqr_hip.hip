@@ -1254,10 +1254,51 @@ hipError_t launch_pack_rhs(NdlqrHipCtx* c, const double* q, const double* r, con
   return hipGetLastError();
 }
 
-int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const double* dd, const double* x0,
-                         double* soln) {
-  if (!c || !x0 || !soln) return NDLQR_ERR_INVALID;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_step_async")) return cerr;
+// ... in dense-cost mode: the slice `sel` of the reduced solutions at z through S (cost_deliver_slice), or the whole vectors
+// packed and mapped back where they land (pack_solutions_generic + cost_apply) -- no CostPhase: a step never waits
+static int deliver_dense(NdlqrHipCtx* c, const KnotSlice& sel, const double* z, double* dst, bool own, double* stage,
+                         hipMemcpyKind kind, hipStream_t st) {
+  double* tgt = own ? dst : stage;
+  if (sel.nknots > 0) {
+    HIP_TRY(cost_deliver_slice_on(c, sel, z, tgt, st));
+  } else {
+    HIP_TRY(launch_pack(c->du, c->d, sel, z, tgt, st, c->d.batch));
+    HIP_TRY(cost_apply_on(c, tgt, 0, c->d.batch, st));
+  }
+  if (!own) HIP_TRY(hipMemcpyAsync(dst, stage, sizeof(double) * sel.doubles(c->du) * c->d.batch, kind, st));
+  return NDLQR_OK;
+}
+
+// what the dense-cost twins of the step and slice functions refuse, `who` opening the message
+static int need_dense_step(const NdlqrHipCtx* c, const char* who) {
+  if (!c->cost.dense)
+    return refuse(std::string(who) + ": the solver is not in dense-cost mode (ndlqr_InitializeBatchFlatDense); a "
+                  "diagonal-cost problem takes the plain function");
+  if (c->lin.active)
+    return refuse(std::string(who) + ": not available in constrained mode (ndlqr_InitializeBatchFlatConstrained)");
+  if (c->kept.time_shard) return refuse(std::string(who) + ": not available on a time-axis shard");
+  return NDLQR_OK;
+}
+// ... and a slice that is none (`allowed`: KnotSlice::valid)
+static int need_dense_slice(const NdlqrHipCtx* c, const char* who, const KnotSlice& sel, unsigned allowed) {
+  if (sel.valid(c->du.N, allowed)) return NDLQR_OK;
+  return refuse(std::string(who) + ": knots [" + std::to_string(sel.knot0) + ", " + std::to_string(sel.knot0 + sel.nknots) +
+                "), blocks " + std::to_string(sel.blocks) + " is not a slice of a horizon of " + std::to_string(c->du.N) + " knots");
+}
+// ... and an array in another device's memory
+static int need_own_memory(const NdlqrHipCtx* c, const char* who, std::initializer_list<const void*> arrays) {
+  for (const void* p : arrays)
+    if (p && where(p, c->device) == Where::OtherDevice)
+      return refuse(std::string(who) + ": an array lies in the memory of another device than the solver's");
+  return NDLQR_OK;
+}
+
+// One step: the parts q, r, dd, x0 (null: not replaced) of the right-hand side up, factor + solve (or the re-solve on
+// kept records), `sel` of the solutions down into `soln`, all on the stream of the step's buffer set. dense: the arrays
+// are in the caller's variables of a dense-cost problem -- S' on the way up and S on the way down, by the two kernels
+// that work between the caller's arrays and the device layout (kernels_cost.hpp); everything else is the same step.
+static int step_on_set(NdlqrHipCtx* c, const double* q, const double* r, const double* dd, const double* x0,
+                       const KnotSlice& sel, double* soln, bool dense) {
   const ndlqr::Dims& d = c->d;
   SolvePlan plan;
   int err = prepare_solve(c, &plan);
@@ -1294,10 +1335,11 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
     }
     stage += cnt[k];
   }
-  HIP_TRY(launch_pack_rhs(c, view[0], view[1], view[2], view[3]));
+  if (dense) HIP_TRY(cost_pack_rhs_on(c, written, view[0], view[1], view[2], view[3], s.rhs, st));
+  else HIP_TRY(launch_pack_rhs(c, view[0], view[1], view[2], view[3]));
   rhs_written_cur(c, written);
   // NDLQR_SOLN_ONLY: nothing but the selected knots is wanted
-  const ApplySlice apply_slice(c, c->sel, (c->sel.blocks & NDLQR_SOLN_ONLY) != 0);
+  const ApplySlice apply_slice(c, sel, (sel.blocks & NDLQR_SOLN_ONLY) != 0);
   // A step never changes A, B, Q, R. Under NDLQR_FLAG_KEEP_RECORDS the first step (or a solve before it) leaves the
   // compact records of the default schedule, and every further step is the right-hand-side re-solve on them (rb_forward,
   // rb_forward_top, rb_backsub: 0.46 instead of 0.59 ms per (12,4,256) x 1024) -- until new inputs are uploaded, which
@@ -1318,7 +1360,9 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   }
   // (the staging has been consumed by the pack kernel: it now takes the packed solutions -- all of them, or the slice
   //  chosen with ndlqr_hip_set_step_selection)
-  err = deliver(u, d, c->sel, s.z, soln, where(soln, c->device) == Where::OwnDevice, s.xfer, hipMemcpyDefault, st, d.batch);
+  const bool own = where(soln, c->device) == Where::OwnDevice;
+  err = dense ? deliver_dense(c, sel, s.z, soln, own, s.xfer, hipMemcpyDefault, st)
+              : deliver(u, d, sel, s.z, soln, own, s.xfer, hipMemcpyDefault, st, d.batch);
   if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   HIP_TRY(hipEventRecord(c->ev_step[c->step_count & 1u], st));
@@ -1329,14 +1373,38 @@ int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const
   return NDLQR_OK;
 }
 
+int ndlqr_hip_step_async(NdlqrHipCtx* c, const double* q, const double* r, const double* dd, const double* x0,
+                         double* soln) {
+  if (!c || !x0 || !soln) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_step_async")) return cerr;
+  return step_on_set(c, q, r, dd, x0, c->sel, soln, false);
+}
+
+// The step of a dense-cost problem (ndlqr.h: ndlqr_BatchStepAsyncDense): q, r, d, x0 in the caller's variables, q and r
+// together or neither; the slice is an argument (nknots == 0: the whole vectors), not the selection of the plain step.
+int ndlqr_hip_step_dense_async(NdlqrHipCtx* c, const double* q, const double* r, const double* dd, const double* x0, int knot0,
+                               int nknots, unsigned blocks, double* out) {
+  static const char* const who = "ndlqr_hip_step_dense_async";
+  if (!c) return NDLQR_ERR_INVALID;
+  if (const int merr = need_dense_step(c, who)) return merr;
+  if (!x0 || !out) return refuse(std::string(who) + ": x0 and the output are required");
+  if ((q == nullptr) != (r == nullptr))
+    return refuse(std::string(who) + ": q and r are replaced together or not at all (the reduced q needs both: q~ = L^-1 (q - G' r))");
+  KnotSlice sel;  // (the whole vectors)
+  if (nknots != 0) {
+    sel = KnotSlice{knot0, nknots, blocks};
+    if (const int serr = need_dense_slice(c, who, sel, 15u)) return serr;
+  }
+  if (const int oerr = need_own_memory(c, who, {q, r, dd, x0, out})) return oerr;
+  return step_on_set(c, q, r, dd, x0, sel, out, true);
+}
+
 // Factor + solve of the resident problems, of which knots [knot0, knot0 + nknots) -- blocks `blocks` -- are computed by the
 // last launch and written to `out` ([batch][nknots][width]; host, pinned or this device's memory), asynchronously: the
 // solve of a loop that replaces A, B, Q, R as well (ndlqr_hip_pack_flat_device / uploads) and consumes u of knot 0.
 // Consecutive calls alternate between the buffer sets like ndlqr_hip_solve_async; complete after ndlqr_hip_synchronize.
-int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
-  const KnotSlice sel = {knot0, nknots, blocks};
-  if (!c || !out || !sel.valid(c->du.N, 15u)) return NDLQR_ERR_INVALID;
-  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_slices_async")) return cerr;
+// (dense: the slice goes through S on its way out)
+static int solve_slices_on_set(NdlqrHipCtx* c, const KnotSlice& sel, double* out, bool dense) {
   const ndlqr::Dims& d = c->d;
   SolvePlan plan;
   int err = prepare_solve(c, &plan);
@@ -1350,12 +1418,34 @@ int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   const ApplySlice apply_slice(c, sel);
   err = launch_solve(c, plan);
   if (err) return err;
-  err = deliver(c->du, d, sel, s.z, out, where(out, c->device) == Where::OwnDevice, s.xfer, hipMemcpyDefault, st, d.batch);
+  const bool own = where(out, c->device) == Where::OwnDevice;
+  err = dense ? deliver_dense(c, sel, s.z, out, own, s.xfer, hipMemcpyDefault, st)
+              : deliver(c->du, d, sel, s.z, out, own, s.xfer, hipMemcpyDefault, st, d.batch);
   if (err) return err;
   HIP_TRY(hipEventRecord(s.ev_stop, st));
   c->timing_pending = true;
   c->state_dirty = false;
   return NDLQR_OK;
+}
+int ndlqr_hip_solve_slices_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
+  const KnotSlice sel = {knot0, nknots, blocks};
+  if (!c || !out || !sel.valid(c->du.N, 15u)) return NDLQR_ERR_INVALID;
+  if (const int cerr = need_diagonal_cost(c, "ndlqr_hip_solve_slices_async")) return cerr;
+  return solve_slices_on_set(c, sel, out, false);
+}
+// everything the dense-cost twins of the two slice functions refuse by name
+static int need_dense_slice_call(const NdlqrHipCtx* c, const char* who, const KnotSlice& sel, unsigned allowed, const double* out) {
+  if (const int merr = need_dense_step(c, who)) return merr;
+  if (!out) return refuse(std::string(who) + ": the output is required");
+  if (const int serr = need_dense_slice(c, who, sel, allowed)) return serr;
+  return need_own_memory(c, who, {out});
+}
+// ... of a dense-cost problem (ndlqr.h: ndlqr_SolveBatchSlicesAsyncDense)
+int ndlqr_hip_solve_slices_dense_async(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
+  const KnotSlice sel = {knot0, nknots, blocks};
+  if (!c) return NDLQR_ERR_INVALID;
+  if (const int serr = need_dense_slice_call(c, "ndlqr_hip_solve_slices_dense_async", sel, 15u, out)) return serr;
+  return solve_slices_on_set(c, sel, out, true);
 }
 
 // the step before the most recent one is complete (its `soln` may be read) -- whichever stream it ran on
@@ -1404,6 +1494,40 @@ int ndlqr_hip_download_selection(NdlqrHipCtx* c, int knot0, int nknots, unsigned
   const int derr =
       deliver(c->du, c->d, sel, c->set[c->latest].z, out, false, s.xfer, hipMemcpyDeviceToHost, s.stream, c->d.batch);
   if (derr) return derr;
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
+}
+// ... of a dense-cost problem (ndlqr.h: ndlqr_CopyBatchSolutionSlicesDense): the slice in the caller's variables
+int ndlqr_hip_download_selection_dense(NdlqrHipCtx* c, int knot0, int nknots, unsigned blocks, double* out) {
+  static const char* const who = "ndlqr_hip_download_selection_dense";
+  const KnotSlice sel = {knot0, nknots, blocks};
+  if (!c) return NDLQR_ERR_INVALID;
+  if (const int serr = need_dense_slice_call(c, who, sel, 7u, out)) return serr;
+  BufferSet& s = c->set[c->cur];
+  if (c->z_invalid || (c->z_partial && (knot0 < 8 * c->z_blk0 || knot0 + nknots > 8 * (c->z_blk0 + c->z_nblk))))
+    return need_full_solution(c, who);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(sync_all(c));
+  HIP_TRY(s.ensure_xfer(c->du));
+  const bool own = where(out, c->device) == Where::OwnDevice;
+  const int derr = deliver_dense(c, sel, c->set[c->latest].z, out, own, s.xfer, hipMemcpyDefault, s.stream);
+  if (derr) return derr;
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return NDLQR_OK;
+}
+
+// Read-out for the tests: the latest right-hand side as it lies on the device, [batch][d.N][d.rows] doubles in the device's
+// block sizes and horizon (ndlqr_hip_rhs_raw_doubles of them), into HOST memory -- the pad rows and the tail knots of a
+// padded horizon included. Waits for everything in flight and brings the current buffer set's copy up to date first.
+// Every mode.
+size_t ndlqr_hip_rhs_raw_doubles(const NdlqrHipCtx* c) { return c ? doubles_z(c->d) : 0; }
+int ndlqr_hip_download_rhs_raw(NdlqrHipCtx* c, double* out) {
+  if (!c || !out) return NDLQR_ERR_INVALID;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(sync_all(c));
+  if (const int merr = rhs_make_current(c, 0xFu)) return merr;
+  BufferSet& s = c->set[c->cur];
+  HIP_TRY(hipMemcpyAsync(out, s.rhs.get(), bytes_z(c->d), hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   return NDLQR_OK;
 }
