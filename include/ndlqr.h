@@ -372,7 +372,7 @@ typedef struct NdLqrBatchSolver NdLqrBatchSolver;
  * slice functions (knots below nhorizon), ndlqr_CopyBatchSolution(s)(Device), ndlqr_BatchKktResiduals,
  * ndlqr_BatchKktResidualVector, ndlqr_SolveBatchAdjoint, ndlqr_CopyBatchAdjoint, ndlqr_BatchGradients,
  * ndlqr_BatchSetBounds, ndlqr_SolveBatchBoxConstrained (fixed and adaptive penalty), ndlqr_CopyBatchBoundMultipliers,
- * ndlqr_CopyBatchBoxPenalties, ndlqr_CopyBatchBoxResiduals.
+ * ndlqr_CopyBatchBoxPenalties, ndlqr_CopyBatchBoxResiduals, ndlqr_BatchObjective.
  * REFUSED at a padded horizon (NDLQR_ERR_INVALID, ndlqr_hip_last_error() names the horizon): ndlqr_SolveBatchMultiRhs(Slices),
  * ndlqr_RefineBatch(Adjoint), ndlqr_SolveBatchBoxAdjoint, ndlqr_BatchBoundGradients, ndlqr_CopyBatchBoxAdjointResiduals,
  * ndlqr_PolishBatchBoxConstrained, ndlqr_SolveBatchPolishedAdjoint, ndlqr_BatchSetInfeasibilityDetection (every > 0) and
@@ -405,7 +405,8 @@ int ndlqr_InitializeBatchFlatDevice(NdLqrBatchSolver* bs, const double* dA, cons
  * called. CARRIED THROUGH in that mode: ndlqr_SolveBatch and ndlqr_SolveBatchAsync + ndlqr_BatchSynchronize in every flag
  * mode, ndlqr_CopyBatchSolution(s)(Device), ndlqr_BatchSetRhsFlat + ndlqr_SolveBatchRhsOnly, ndlqr_SolveBatchAdjoint +
  * ndlqr_CopyBatchAdjoint + ndlqr_BatchGradientsDense (the nine dense-cost gradients, assembled on the device),
- * ndlqr_BatchCholeskyFailures, ndlqr_BatchSolveTimeMs, any horizon >= 2.
+ * ndlqr_BatchCholeskyFailures, ndlqr_BatchSolveTimeMs, ndlqr_BatchObjective (the caller's Q, H, R: the unit-cost
+ * objective of the reduced problem is the caller's), any horizon >= 2.
  * REFUSED (NDLQR_ERR_INVALID, ndlqr_hip_last_error() opens with the name of the function of ndlqr_hip.h behind the call):
  * ndlqr_BatchStepAsync, ndlqr_BatchSetStepSelection (a non-empty one), ndlqr_SolveBatchSlicesAsync,
  * ndlqr_CopyBatchSolutionSlices, ndlqr_SolveBatchMultiRhs(Slices), ndlqr_BatchGradients (the dense-cost gradients are
@@ -474,6 +475,8 @@ int ndlqr_BatchCostIsDense(const NdLqrBatchSolver* bs); /* 1: dense-cost mode, 0
  *   ndlqr_CopyBatchConstraintResiduals: [batch][4] = r_prim | r_dual | sp | sd of every problem's last update, with the
  *   meaning of ndlqr_CopyBatchBoxResiduals: r_prim = max |w - v|, r_dual = rho max |[C D]'(v - v_prev)|,
  *   sp = max(max |w|, max |v|), sd = rho max |[C D]' y|.
+ *   ndlqr_BatchObjective is carried through: after a constrained solve or its polish the caller's unshifted cost at the
+ *   delivered iterate (from the retained Q, H, R, q, r), after a plain solve the unconstrained optimal value.
  * REFUSED by name (NDLQR_ERR_INVALID, ndlqr_hip_last_error()): s->adapt_every > 0 (that field, with rho_min and rho_max, is
  * the box solve's: ndlqr_BatchSetConstraintPenaltyAdaptation is this solve's switch); everything of the box
  * solve -- acceleration, its infeasibility detection (ndlqr_BatchSetInfeasibilityDetection and its two read-outs: this
@@ -701,6 +704,28 @@ int ndlqr_BatchGradientsDense(NdLqrBatchSolver* bs, unsigned sum_mask, double* g
  *   time of the call's kernels. */
 int ndlqr_BatchFeedbackGains(NdLqrBatchSolver* bs, int knot0, int nknots, double* K, double* kff, double* P, double* p,
                              int* failures);
+/* additive: the value of the cost every problem minimised, at its resident solution -- what a line
+ * search or a trust-region ratio of an iLQR / SQP outer loop divides by, what compares an ADMM iterate with its polish,
+ * and the loss of a differentiable MPC layer (rslqr_amd.autograd.lqr_value):
+ *     J = sum_{k<N} l_k,   l_k = 1/2 x_k'Q_k x_k + x_k'H_k u_k + 1/2 u_k'R_k u_k + q_k'x_k + r_k'u_k
+ * with the last knot contributing 1/2 x'Q x + q'x alone (its H, R, r are never read) and no constant term.
+ *   Outputs: J [batch]; stage [batch][nhorizon] = l_k, may be NULL. Host, pinned or the solver's device memory. Every
+ *   product's rounding error is captured and every sum runs in double-double; J and every l_k are rounded once, and the
+ *   bits depend on the solution and the inputs alone -- not on the flag mode, the memory of the outputs or whether stage was
+ *   asked for.
+ *   Evaluates the solution that ndlqr_CopyBatchSolutions would deliver against the right-hand side that produced it
+ *   (ndlqr_BatchSetRhsFlat + ndlqr_SolveBatchRhsOnly and the steps of ndlqr_BatchStepAsync(Dense) on either buffer set
+ *   included), with the caller's costs: in dense-cost mode the caller's Q, H, R; after ndlqr_SolveBatchBoxConstrained,
+ *   ndlqr_SolveBatchLinConstrained or their polish the UNSHIFTED cost at the delivered iterate. A right-hand side replaced
+ *   without a solve behind it is evaluated as it stands, at the old solution. Works in every flag mode, at any horizon
+ *   >= 2 and every block size. Blocking.
+ *   NDLQR_ERR_INVALID (ndlqr_hip_last_error() opens with ndlqr_hip_objective) for J NULL, before the first solve, after a
+ *   failed constrained solve or a step that computed a slice alone (NDLQR_SOLN_ONLY) -- until the next full solve --, on a
+ *   time-axis shard and for an output in the memory of another device.
+ *   Nothing else moves: the resident solution and what is known about it, the kept and remembered factorisations, the
+ *   adjoint, the failure counts, the box / constraint / polish state stay as they are. ndlqr_BatchSolveTimeMs then reports
+ *   the device time of the call's kernels. */
+int ndlqr_BatchObjective(NdLqrBatchSolver* bs, double* J, double* stage);
 /* additive: iterative refinement of a batch solve with a double-double residual, for callers who need more than the
  * solve paths deliver on ill-conditioned inputs. ndlqr_RefineBatch evaluates r = b - K z of the resident solutions with
  * every row accumulated in double-double and rounded once, re-solves K delta = r against the kept factorisation, and

@@ -249,6 +249,19 @@ int ndlqr_hip_gradients_dense_constants(int* out2);
  * (for the tests and tools, which pick shapes by it). */
 int ndlqr_hip_feedback_gains(NdlqrHipCtx* ctx, int knot0, int nknots, double* K, double* kff, double* P, double* p, int* fails);
 size_t ndlqr_hip_feedback_gains_lds(int n, int m, int second);
+/* The objective value of every problem at its resident solution and its stage costs (ndlqr.h: ndlqr_BatchObjective has the
+ * contract). J [batch]; stage [batch][N], may be NULL; host, pinned or this device's memory (the
+ * kernel writes this device's memory, host memory is staged, another device's is refused). Blocking: everything in flight
+ * is waited for, the kernels run on the stream of the buffer set that holds the latest solution and read the right-hand
+ * side of that set -- the one that produced it. A read-out: z, what is known about it, the kept and remembered
+ * factorisations, the adjoint, the failure words and the box / constraint / polish state stay as they are; only
+ * ndlqr_hip_last_solve_ms moves. NDLQR_ERR_INVALID, the message opening with ndlqr_hip_objective: J NULL, no full valid
+ * resident solution (none yet, a failed constrained solve, a NDLQR_SOLN_ONLY step), a time-axis shard, an output in
+ * another device's memory, a block size whose chunk does not fit the LDS of a workgroup (the bytes are named).
+ * ndlqr_hip_objective_constants: out2[0] the knots of a workgroup's chunk, out2[1] the workgroup size (for the tests,
+ * which size a horizon by them). */
+int ndlqr_hip_objective(NdlqrHipCtx* ctx, double* J, double* stage);
+int ndlqr_hip_objective_constants(int* out2);
 /* Iterative refinement with a double-double residual (ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint,
  * ndlqr_BatchKktResidualVector). which = 0: the resident solution against the resident right-hand
  * side; 1: w of the latest plain adjoint against its packed g. max_steps in [1, 8]. steps [batch] (int), eta_before,

@@ -325,6 +325,8 @@ def lib():
     proto("ndlqr_hip_gradients_dense_constants", ci, C.POINTER(C.c_int))
     proto("ndlqr_BatchFeedbackGains", ci, vp, ci, ci, dp, dp, dp, dp, C.POINTER(ci))
     proto("ndlqr_hip_feedback_gains_lds", C.c_size_t, ci, ci, ci)
+    proto("ndlqr_BatchObjective", ci, vp, dp, dp)
+    proto("ndlqr_hip_objective_constants", ci, C.POINTER(C.c_int))
     proto("ndlqr_RefineBatch", ci, vp, ci, C.POINTER(ci), dp, dp)
     proto("ndlqr_RefineBatchAdjoint", ci, vp, ci, C.POINTER(ci), dp, dp)
     proto("ndlqr_BatchKktResidualVector", ci, vp, dp)
@@ -434,6 +436,15 @@ def feedback_gains_lds(n, m, second=False):
     """Bytes of LDS the sweep of BatchSolver.feedback_gains needs at block size (n, m), with the second input buffer or
     without it (ndlqr_hip_feedback_gains_lds); a shape that needs more than 160 KB without it is refused."""
     return int(lib().ndlqr_hip_feedback_gains_lds(n, m, 1 if second else 0))
+
+
+def objective_constants():
+    """(knots of a workgroup's chunk, workgroup size) of the kernels behind BatchSolver.objective
+    (ndlqr_hip_objective_constants): the tests size a horizon by them."""
+    out = (C.c_int * 2)()
+    if lib().ndlqr_hip_objective_constants(out):
+        raise RuntimeError("ndlqr_hip_objective_constants failed")
+    return int(out[0]), int(out[1])
 
 
 def _ptr(a):
@@ -1200,6 +1211,31 @@ class BatchSolver:
                     rows = m if k == "K" else n
                     res[k] = np.ascontiguousarray(res[k].reshape(bt, nknots, n, rows).transpose(0, 1, 3, 2))
         res["failures"] = failures
+        return res
+
+    # ---- objective values and stage costs (include/ndlqr.h: ndlqr_BatchObjective)
+    def objective(self, stage=False, out=None):
+        """ndlqr_BatchObjective: the value of the cost every problem minimised at its resident solution -- with the caller's
+        costs (dense-cost mode: the caller's Q, H, R; after a constrained solve or polish: the unshifted cost at the
+        delivered iterate) and the right-hand side that produced the solution. Returns {"J": [batch]} and, with
+        stage=True, "stage": [batch, N], the stage costs l_k (J is their sum; the last knot has no input terms), as numpy
+        arrays. With `out`, a dict of numpy arrays (pinned_empty ones included) or DeviceArrays under those names, those
+        are filled and returned instead (`stage` is ignored: "stage" is computed when it is in `out`; "J" is required).
+        Accumulated in double-double and rounded once; the bits do not depend on the flag mode, the memory of the outputs
+        or whether the stage costs were asked for. Raises RuntimeError with the library's message on a refusal (no full
+        resident solution, a time-axis shard)."""
+        shapes = dict(J=(self.batch,), stage=(self.batch, self.N))
+        if out is not None:
+            unknown = set(out) - set(shapes)
+            if unknown:
+                raise ValueError("unknown output names: %s" % sorted(unknown))
+            res = dict(out)
+        else:
+            res = {k: np.zeros(shapes[k]) for k in (("J", "stage") if stage else ("J",))}
+        ptrs = [None if res.get(k) is None else _any_ptr(res[k], int(np.prod(shapes[k]))) for k in ("J", "stage")]
+        err = self.L.ndlqr_BatchObjective(self.h, *ptrs)
+        if err:
+            raise RuntimeError("ndlqr_BatchObjective failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return res
 
     # ---- iterative refinement (include/ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint, ndlqr_BatchKktResidualVector)

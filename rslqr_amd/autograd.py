@@ -513,28 +513,23 @@ class LqrSolveDense(torch.autograd.Function):
         return (None, None) + tuple(_dense_backward_gradients(bs, ctx.shared, ctx.needs_input_grad[2:], ctx.dims, gz.device))
 
 
-def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
-    """z [b, nvars] of LQR problems with dense cost matrices and a state-input cross term, differentiable in every argument:
-        A [b, N, n, n]   B [b, N, n, m]   Q [b, N, n, n]   H [b, N, n, m]   R [b, N, m, m]   q, d [b, N, n]   r [b, N, m]   x0 [b, n]
-    in the row-major math convention; per knot the cost is 1/2 x'Q x + x'H u + 1/2 u'R u + q'x + r'u. Any argument may leave
-    out the batch dimension (shared: its gradient is the batch sum). Q and R are read as symmetric matrices through their
-    lower triangles, and dL/dQ, dL/dR come back symmetric: the gradient in the space of symmetric matrices. Needs R_k > 0
-    and Q_k - H_k R_k^-1 H_k' > 0. H, R of the last knot are not part of the problem (zero gradient), like its A, B, r, d."""
-    args = (A, B, Q, H, R, q, r, d, x0)
+def _check_dense(who, args):
+    """The argument checks of lqr_solve_dense (and lqr_value_dense: `who` opens the messages): (shared flags, (n, m, N, b))."""
     dev = None
     for name, t in zip(_DENSE_ARGS, args):
         if not isinstance(t, torch.Tensor):
-            raise TypeError("lqr_solve_dense: %s must be a torch.Tensor" % name)
+            raise TypeError(who + ": %s must be a torch.Tensor" % name)
         if t.dtype != torch.float64:
-            raise TypeError("lqr_solve_dense: %s must be float64, got %s" % (name, t.dtype))
+            raise TypeError(who + ": %s must be float64, got %s" % (name, t.dtype))
         if t.device.type != "cuda":
-            raise ValueError("lqr_solve_dense: %s must live on a ROCm device, got %s" % (name, t.device))
+            raise ValueError(who + ": %s must live on a ROCm device, got %s" % (name, t.device))
         if dev is None:
             dev = t.device
         elif t.device != dev:
-            raise ValueError("lqr_solve_dense: every argument must be on one device (%s is on %s, A on %s)" % (name, t.device, dev))
+            raise ValueError(who + ": every argument must be on one device (%s is on %s, A on %s)" % (name, t.device, dev))
+    A, B = args[0], args[1]
     if A.dim() not in (3, 4) or A.shape[-1] != A.shape[-2] or B.dim() not in (3, 4) or B.shape[-3:-1] != A.shape[-3:-1]:
-        raise ValueError("lqr_solve_dense: A must be [b, N, n, n] and B [b, N, n, m] (b optional), got %s and %s"
+        raise ValueError(who + ": A must be [b, N, n, n] and B [b, N, n, m] (b optional), got %s and %s"
                          % (tuple(A.shape), tuple(B.shape)))
     N, n, m = B.shape[-3:]
     per = dict(A=(N, n, n), B=(N, n, m), Q=(N, n, n), H=(N, n, m), R=(N, m, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,))
@@ -547,13 +542,25 @@ def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
         if t.dim() == len(per[name]) + 1 and tuple(t.shape[1:]) == per[name]:
             batch.add(t.shape[0])
         else:
-            raise ValueError("lqr_solve_dense: %s must be [b, %s] or %s, got %s"
+            raise ValueError(who + ": %s must be [b, %s] or %s, got %s"
                              % (name, ", ".join(str(x) for x in per[name]), list(per[name]), tuple(t.shape)))
     if len(batch) > 1:
-        raise ValueError("lqr_solve_dense: batch dimensions disagree: %s" % sorted(batch))
+        raise ValueError(who + ": batch dimensions disagree: %s" % sorted(batch))
     b = batch.pop() if batch else 1
+    return tuple(shared), (n, m, N, b)
+
+
+def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
+    """z [b, nvars] of LQR problems with dense cost matrices and a state-input cross term, differentiable in every argument:
+        A [b, N, n, n]   B [b, N, n, m]   Q [b, N, n, n]   H [b, N, n, m]   R [b, N, m, m]   q, d [b, N, n]   r [b, N, m]   x0 [b, n]
+    in the row-major math convention; per knot the cost is 1/2 x'Q x + x'H u + 1/2 u'R u + q'x + r'u. Any argument may leave
+    out the batch dimension (shared: its gradient is the batch sum). Q and R are read as symmetric matrices through their
+    lower triangles, and dL/dQ, dL/dR come back symmetric: the gradient in the space of symmetric matrices. Needs R_k > 0
+    and Q_k - H_k R_k^-1 H_k' > 0. H, R of the last knot are not part of the problem (zero gradient), like its A, B, r, d."""
+    args = (A, B, Q, H, R, q, r, d, x0)
+    shared, dims = _check_dense("lqr_solve_dense", args)
     # (a shared argument goes in as it is: the library sums its gradient over the batch)
-    return LqrSolveDense.apply(tuple(shared), (n, m, N, b), *args)
+    return LqrSolveDense.apply(shared, dims, *args)
 
 
 # ------------------------------------------------------------------------------------------------ linear inequality constraints
@@ -709,3 +716,109 @@ def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, 
                 int(infeas_every), float(infeas_eps))
     return LqrSolveConstrained.apply(settings, tuple(shared[k] for k in _ROW_ARGS), tuple(shared[k] for k in _DENSE_ARGS),
                                      (n, m, N, b), *args)
+
+
+# ------------------------------------------------------------------------------------------------ the optimal value
+# J* = min J as a function of the problem (ndlqr_BatchObjective behind a plain solve). By the envelope theorem its
+# gradient is the partial derivative of the Lagrangian at the solution -- no adjoint solve, no kept factorisation. The
+# Lagrangian that fits the KKT rows of the library (kkt_residual_generic: Q x + q - lambda_k + A' lambda_(k+1) = 0,
+# R u + r + B' lambda_(k+1) = 0) is
+#     L = J - lambda_0'(x_0 - x_init) + sum_k lambda_(k+1)'(A_k x_k + B_k u_k + d_k - x_(k+1)).
+
+def value_gradients(z, n, m, N, dense):
+    """dJ*/d(A, B, Q, R, q, r, d, x0) -- dense: (A, B, Q, H, R, q, r, d, x0) -- per problem, [b, ...] in the math convention,
+    from the solutions z [b, nvars]: dJ/dx0 = lambda_0, dJ/dd_k = lambda_(k+1), dJ/dA_k = lambda_(k+1) x_k',
+    dJ/dB_k = lambda_(k+1) u_k', dJ/dq = x, dJ/dr = u; diagonal costs dJ/dQ = x*x / 2, dJ/dR = u*u / 2; dense costs
+    dJ/dQ = x x' / 2, dJ/dH = x u', dJ/dR = u u' / 2 (symmetric, the convention of lqr_solve_dense). Exactly zero for A, B,
+    H, R, r, d of the last knot, which are never read. Torch operations on any device."""
+    lam, x, u = split_solution(z, n, m, N)
+    outer = lambda a, c: a.unsqueeze(-1) * c.unsqueeze(-2)
+    pad = lambda t: torch.nn.functional.pad(t, (0, 0) * (t.dim() - 2) + (0, 1))  # a zero last knot
+    x1, l1 = x[:, :N - 1], lam[:, 1:]
+    gA, gB = pad(outer(l1, x1)), pad(outer(l1, u))
+    gq, gr, gd, gx0 = x.clone(), pad(u), pad(l1), lam[:, 0].clone()
+    if dense:
+        return (gA, gB, 0.5 * outer(x, x), pad(outer(x1, u)), pad(0.5 * outer(u, u)), gq, gr, gd, gx0)
+    return (gA, gB, 0.5 * x * x, pad(0.5 * u * u), gq, gr, gd, gx0)
+
+
+def _value_backward(ctx, gJ, dense, needs):
+    n, m, N, b = ctx.dims
+    (z,) = ctx.saved_tensors
+    grads = []
+    for g, sh, need in zip(value_gradients(z, n, m, N, dense), ctx.shared, needs):
+        if not need:
+            grads.append(None)
+            continue
+        g = g * gJ.reshape((b,) + (1,) * (g.dim() - 1))
+        grads.append(g.sum(0) if sh else g)
+    return tuple(grads)
+
+
+class LqrValue(torch.autograd.Function):
+    """Forward: a plain solve on lqr_solve's cached solver, then ndlqr_BatchObjective into a torch tensor. Backward: the
+    envelope theorem on the saved solution (value_gradients), in torch."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        dev, n, m, N, b, shared = _check(args)
+        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
+        if key not in _cache:
+            _cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
+        bs = _cache[key][0]
+        _solve(bs, _flat(args, n, m, N, b, shared), next(_tokens), key)
+        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
+        J = torch.empty((b,), dtype=torch.float64, device=dev)
+        bs.solutions_to_device(z.data_ptr())
+        bs.synchronize()
+        bs.objective(out={"J": _View(J)})
+        ctx.save_for_backward(z)
+        ctx.shared, ctx.dims = shared, (n, m, N, b)
+        return J
+
+    @staticmethod
+    def backward(ctx, gJ):
+        return _value_backward(ctx, gJ, False, ctx.needs_input_grad)
+
+
+class LqrValueDense(torch.autograd.Function):
+    """LqrValue for dense costs, on lqr_solve_dense's cached solver. shared, dims: as LqrSolveDense's."""
+
+    @staticmethod
+    def forward(ctx, shared, dims, *args):
+        n, m, N, b = dims
+        dev = args[0].device
+        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
+        if key not in _dense_cache:
+            _dense_cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
+        bs = _dense_cache[key][0]
+        _dense_solve(bs, _flat_dense(args, shared, b), next(_tokens), key)
+        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
+        J = torch.empty((b,), dtype=torch.float64, device=dev)
+        bs.solutions_to_device(z.data_ptr())
+        bs.synchronize()
+        bs.objective(out={"J": _View(J)})
+        ctx.save_for_backward(z)
+        ctx.shared, ctx.dims = shared, dims
+        return J
+
+    @staticmethod
+    def backward(ctx, gJ):
+        return (None, None) + _value_backward(ctx, gJ, True, ctx.needs_input_grad[2:])
+
+
+def lqr_value(A, B, Q, R, q, r, d, x0):
+    """J* [b]: the optimal value of the LQR problems of lqr_solve (same shapes, same sharing rules: an argument without its
+    batch dimension is shared and its gradient is the batch sum), differentiable in every argument. The forward is a plain
+    solve and ndlqr_BatchObjective (double-double, rounded once); the backward needs no adjoint solve: by the envelope
+    theorem dJ*/dtheta is the partial derivative of the Lagrangian at the solution (value_gradients). Gradients are zero
+    for A, B, R, r, d of the last knot, which are not part of the problem."""
+    return LqrValue.apply(A, B, Q, R, q, r, d, x0)
+
+
+def lqr_value_dense(A, B, Q, H, R, q, r, d, x0):
+    """J* [b] of the dense-cost problems of lqr_solve_dense (same shapes and sharing rules), differentiable in every
+    argument as lqr_value is; dJ*/dQ and dJ*/dR come back symmetric, the convention of lqr_solve_dense."""
+    args = (A, B, Q, H, R, q, r, d, x0)
+    shared, dims = _check_dense("lqr_value_dense", args)
+    return LqrValueDense.apply(shared, dims, *args)

@@ -29,7 +29,7 @@ C_SOURCES = ["containers.c", "synth.c", "json.c", "batch.c", "solver.c", "linalg
 HIP_MAIN = "ndlqr_hip.hip"            # the core: context, pipeline, the three families' launch sequences
 # one unit per feature; a new feature adds its line here
 HIP_UNITS = [HIP_MAIN, "hip_grad.hip", "hip_box.hip", "hip_refine.hip", "hip_cost.hip", "hip_lin.hip", "hip_lin_polish.hip", "hip_dense.hip",
-             "hip_grad_dense.hip", "hip_gain.hip"]
+             "hip_grad_dense.hip", "hip_gain.hip", "hip_objective.hip"]
 HIP_INSTANCE = "small_instance.hip"   # compiled once per line of small_instances.def
 HIP_REDUCED = "reduced_instance.hip"  # compiled once per tile count of the runtime-sized separator-only family
 REDUCED_NB = range(1, 9)

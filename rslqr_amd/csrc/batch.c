@@ -492,6 +492,10 @@ int ndlqr_BatchFeedbackGains(NdLqrBatchSolver* bs, int knot0, int nknots, double
   if (!bs) return NDLQR_ERR_INVALID;
   return ndlqr_hip_feedback_gains(bs->ctx, knot0, nknots, K, kff, P, p, failures);
 }
+int ndlqr_BatchObjective(NdLqrBatchSolver* bs, double* J, double* stage) {
+  if (!bs) return NDLQR_ERR_INVALID;
+  return ndlqr_hip_objective(bs->ctx, J, stage);
+}
 int ndlqr_RefineBatch(NdLqrBatchSolver* bs, int max_steps, int* steps, double* eta_before, double* eta_after) {
   if (!bs) return NDLQR_ERR_INVALID;
   return ndlqr_hip_refine(bs->ctx, 0, max_steps, steps, eta_before, eta_after);
