@@ -428,6 +428,16 @@ class DeviceArray:
         return out
 
 
+def _call(L, name, *args, detail=True, ok=(0,)):
+    """L.name(*args), checked: RuntimeError "name failed: code (the library's last error)" -- without the parenthesis for
+    detail=False, the text of the early calls -- unless the return code is one of `ok`. Returns the code."""
+    err = getattr(L, name)(*args)
+    if err not in ok:
+        raise RuntimeError("%s failed: %d (%s)" % (name, err, L.ndlqr_hip_last_error().decode()) if detail
+                           else "%s failed: %d" % (name, err))
+    return err
+
+
 def device_count():
     return lib().ndlqr_hip_device_count()
 
@@ -463,15 +473,66 @@ def _any_ptr(a, size):
     return _ptr(a)
 
 
+def _doubles(a):
+    """`a` itself if it is device memory (has `ptr`), else as a C-contiguous float64 numpy array."""
+    return a if hasattr(a, "ptr") else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _int_ptr(a, size):
+    """int* of a numpy array (int32, C-contiguous) or of device memory -- anything with `ptr` -- holding `size` ints."""
+    if hasattr(a, "ptr"):
+        return C.cast(C.c_void_p(int(a.ptr)), C.POINTER(C.c_int))
+    if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags["C_CONTIGUOUS"] and a.size == size):
+        raise ValueError("expected a C-contiguous int32 array of %d entries" % size)
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _stage(names, arrays, sizes, optional=("H",)):
+    """(pointers, keep-alive list) of the caller's arrays for an initialiser: a numpy array (anything ascontiguousarray
+    takes) of sizes[name] doubles, device memory (`ptr`, `size`), or None for the names in `optional`."""
+    ptrs, keep = [], []
+    for name, a in zip(names, arrays):
+        if a is None:
+            if name not in optional:
+                raise ValueError("%s is missing (only %s may be None)" % (name, " and ".join(optional)))
+            ptrs.append(None)
+            continue
+        if not hasattr(a, "ptr"):
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != sizes[name]:
+                raise ValueError("bad size for %s" % name)
+            keep.append(a)
+        ptrs.append(_any_ptr(a, sizes[name]))
+    return ptrs, keep
+
+
+def _stage_bounds(bounds, N, B):
+    """(pointers, shared, keep-alive list) for the (bound, width, may be None) of `bounds`: a numpy bound of shape
+    (width,), (N, width) -- shared -- or (B, N, width), or device memory of B * N * width doubles. The bounds are shared
+    only if every given one is a host array with ndim <= 2."""
+    host = [a if (a is None and may_be_none) or hasattr(a, "ptr") else np.asarray(a, dtype=np.float64)
+            for a, _, may_be_none in bounds]
+    shared = all(a is None or (not hasattr(a, "ptr") and a.ndim <= 2) for a in host)
+    ptrs, keep = [], []
+    for a, (_, k, _) in zip(host, bounds):
+        if a is None:
+            ptrs.append(None)
+            continue
+        if not hasattr(a, "ptr"):
+            if a.shape not in ((k,), (N, k), (B, N, k)):
+                raise ValueError("bounds of shape %s: expected (%d,), (%d, %d) or (%d, %d, %d)" % (a.shape, k, N, k, B, N, k))
+            a = np.ascontiguousarray(np.broadcast_to(a, (N, k) if shared else (B, N, k)))
+            keep.append(a)
+        ptrs.append(_any_ptr(a, (1 if shared else B) * N * k))
+    return ptrs, shared, keep
+
+
 def generate_synthetic(n, m, N, seed):
     """ndlqr_GenerateSyntheticFlat -> dict of numpy arrays (A [N,n*n] col-major, ...)."""
     out = dict(A=np.zeros((N, n * n)), B=np.zeros((N, n * m)), Q=np.zeros((N, n)),
                R=np.zeros((N, m)), q=np.zeros((N, n)), r=np.zeros((N, m)), d=np.zeros((N, n)),
                x0=np.zeros(n))
-    err = lib().ndlqr_GenerateSyntheticFlat(n, m, N, seed, *[_ptr(out[k]) for k in
-                                                               ("A", "B", "Q", "R", "q", "r", "d", "x0")])
-    if err:
-        raise RuntimeError("ndlqr_GenerateSyntheticFlat failed: %d" % err)
+    _call(lib(), "ndlqr_GenerateSyntheticFlat", n, m, N, seed, *[_ptr(a) for a in out.values()], detail=False)
     return out
 
 
@@ -488,6 +549,8 @@ class BatchSolver:
         self.nvars = self.L.ndlqr_BatchNumVars(self.h)
         self._sel = None          # (knot0, nknots, blocks) of set_step_selection
         self._step_refs = []      # host arrays of the steps in flight (kept alive until they are synchronised)
+        self._rows = 0            # constraint rows per knot of initialize_flat_constrained
+        self._accel_mem = 0       # memory of set_box_acceleration
         if flags:
             self.set_flags(flags)
 
@@ -506,6 +569,65 @@ class BatchSolver:
     def ctx(self):
         return self.L.ndlqr_BatchDeviceContext(self.h)
 
+    # ---- what the methods below share: the checked call, and one helper per family of calls that differ in the C symbol
+    def _call(self, name, *args, **how):
+        """_call on the solver's library: every method that raises on a refusal goes through here."""
+        return _call(self.L, name, *args, **how)
+
+    def _copy_out(self, name, shape, dtype=np.float64, dest=None, via_ctx=False):
+        """The read-outs of one array: `name`(handle, or device context for via_ctx, destination). The destination is
+        `dest` (float64: a numpy array or DeviceArray of prod(shape) doubles), or a new numpy array. Returns it."""
+        if dest is None:
+            dest = np.zeros(shape, dtype=dtype)
+        ptr = _any_ptr(dest, int(np.prod(shape))) if dtype is np.float64 else dest.ctypes.data_as(C.POINTER(C.c_ubyte))
+        self._call(name, self.ctx if via_ctx else self.h, ptr)
+        return dest
+
+    def _admm_solve(self, name, settings, g=None):
+        """The ADMM solves: `name`(handle, [g,] settings, iters, status) with g [batch, nvars] for an adjoint. Returns
+        (iters, status), int32 [batch]."""
+        st = NdLqrBoxSettingsFull(*settings)
+        iters = np.zeros(self.batch, dtype=np.int32)
+        status = np.zeros(self.batch, dtype=np.int32)
+        lead = () if g is None else (_any_ptr(g, self.batch * self.nvars),)
+        self._call(name, self.h, *lead, C.byref(st), _int_ptr(iters, self.batch), _int_ptr(status, self.batch))
+        return iters, status
+
+    def _polish(self, name, settings, steps, status, g=None):
+        """The polish calls: `name`(handle, [g,] settings, steps, status); steps, status: int32 destinations [batch] (numpy
+        arrays or device memory with `ptr`), None: new numpy arrays. Returns (steps, status)."""
+        st = NdLqrPolishSettings(*settings)
+        if steps is None:
+            steps = np.zeros(self.batch, dtype=np.int32)
+        if status is None:
+            status = np.zeros(self.batch, dtype=np.int32)
+        lead = () if g is None else (_any_ptr(g, self.batch * self.nvars),)
+        self._call(name, self.h, *lead, C.byref(st), _int_ptr(steps, self.batch), _int_ptr(status, self.batch))
+        return steps, status
+
+    def _measures(self, name, measures, iteration):
+        """The infeasibility measures: `name`(handle, measures [batch, 4], iteration [batch] of int32)."""
+        if measures is None:
+            measures = np.zeros((self.batch, 4))
+        if iteration is None:
+            iteration = np.zeros(self.batch, dtype=np.int32)
+        ip = _int_ptr(iteration, self.batch)
+        self._call(name, self.h, _any_ptr(measures, 4 * self.batch), ip)
+        return measures, iteration
+
+    def _named_gradients(self, name, shapes, out, flag, flag_first, what):
+        """The gradient read-outs: `name`(handle, [flag,] one pointer per key of `shapes` in its order, [flag]); out: dict
+        of destinations under those keys (numpy arrays or DeviceArrays; a key left out is not computed), None: new numpy
+        arrays for all of them. `what` names the keys in the message about unknown ones. Returns out."""
+        if out is None:
+            out = {k: np.zeros(sh) for k, sh in shapes.items()}
+        unknown = set(out) - set(shapes)
+        if unknown:
+            raise ValueError("unknown %s names: %s" % (what, sorted(unknown)))
+        ptrs = [None if out.get(k) is None else _any_ptr(out[k], int(np.prod(sh))) for k, sh in shapes.items()]
+        self._call(name, self.h, *([flag] + ptrs if flag_first else ptrs + [flag]))
+        return out
+
     def initialize_flat(self, A, B, Q, R, q, r, d, x0):
         n, m, N, bt = self.n, self.m, self.N, self.batch
         shapes = dict(A=(bt, N, n * n), B=(bt, N, n * m), Q=(bt, N, n), R=(bt, N, m),
@@ -516,15 +638,11 @@ class BatchSolver:
             if a.size != int(np.prod(shapes[name])):
                 raise ValueError("bad size for %s" % name)
             arrs.append(a)
-        err = self.L.ndlqr_InitializeBatchFlat(self.h, *[_ptr(a) for a in arrs])
-        if err:
-            raise RuntimeError("ndlqr_InitializeBatchFlat failed: %d" % err)
+        self._call("ndlqr_InitializeBatchFlat", self.h, *[_ptr(a) for a in arrs], detail=False)
 
     def initialize_flat_device(self, *device_ptrs):
         """Eight device pointers (ints), flat reference layout: A, B, Q, R, q, r, d, x0."""
-        err = self.L.ndlqr_InitializeBatchFlatDevice(self.h, *[C.c_void_p(int(p)) for p in device_ptrs])
-        if err:
-            raise RuntimeError("ndlqr_InitializeBatchFlatDevice failed: %d" % err)
+        self._call("ndlqr_InitializeBatchFlatDevice", self.h, *[C.c_void_p(int(p)) for p in device_ptrs], detail=False)
 
     def initialize_flat_dense(self, A, B, Q, H, R, q, r, d, x0):
         """ndlqr_InitializeBatchFlatDense: dense cost matrices Q [batch, N, n*n], R [batch, N, m*m] and the state-input
@@ -536,22 +654,8 @@ class BatchSolver:
         n, m, N, bt = self.n, self.m, self.N, self.batch
         sizes = dict(A=bt * N * n * n, B=bt * N * n * m, Q=bt * N * n * n, H=bt * N * n * m, R=bt * N * m * m,
                      q=bt * N * n, r=bt * N * m, d=bt * N * n, x0=bt * n)
-        ptrs, keep = [], []
-        for name, a in zip(("A", "B", "Q", "H", "R", "q", "r", "d", "x0"), (A, B, Q, H, R, q, r, d, x0)):
-            if a is None:
-                if name != "H":
-                    raise ValueError("%s is missing (only H may be None)" % name)
-                ptrs.append(None)
-                continue
-            if not hasattr(a, "ptr"):
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.size != sizes[name]:
-                    raise ValueError("bad size for %s" % name)
-                keep.append(a)
-            ptrs.append(_any_ptr(a, sizes[name]))
-        err = self.L.ndlqr_InitializeBatchFlatDense(self.h, *ptrs)
-        if err:
-            raise RuntimeError("ndlqr_InitializeBatchFlatDense failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        ptrs, keep = _stage(GRAD_DENSE_NAMES, (A, B, Q, H, R, q, r, d, x0), sizes)
+        self._call("ndlqr_InitializeBatchFlatDense", self.h, *ptrs)
 
     def cost_is_dense(self):
         """ndlqr_BatchCostIsDense: True between initialize_flat_dense and the next diagonal initialiser."""
@@ -573,30 +677,10 @@ class BatchSolver:
         out = dict(L=np.zeros((bt, N, n * n)), LR=np.zeros((bt, N, m * m)), G=np.zeros((bt, N, m * n)),
                    At=np.zeros((bt, N, n * n)), Bt=np.zeros((bt, N, n * m)), qt=np.zeros((bt, N, n)), rt=np.zeros((bt, N, m)),
                    dt=np.zeros((bt, N, n)), x0t=np.zeros((bt, n)))
-        err = self.L.ndlqr_hip_download_cost_reduction(self.ctx, *[_ptr(out[k]) for k in
-                                                                   ("L", "LR", "G", "At", "Bt", "qt", "rt", "dt", "x0t")])
-        if err:
-            raise RuntimeError("ndlqr_hip_download_cost_reduction failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_hip_download_cost_reduction", self.ctx, *[_ptr(a) for a in out.values()])
         return out
 
     # ---- linear inequality constraints (include/ndlqr.h: ndlqr_InitializeBatchFlatConstrained)
-    def _constraint_bounds(self, lo, hi, p=None):
-        """(lo, hi, shared, keep-alive list) for the C calls: numpy bounds of shape (p,), (N, p) -- shared -- or
-        (batch, N, p); a DeviceArray holds batch * N * p doubles."""
-        N, B = self.N, self.batch
-        p = self._rows if p is None else p
-        host = [a if hasattr(a, "ptr") else np.asarray(a, dtype=np.float64) for a in (lo, hi)]
-        shared = all(not hasattr(a, "ptr") and a.ndim <= 2 for a in host)
-        ptrs, keep = [], []
-        for a in host:
-            if not hasattr(a, "ptr"):
-                if a.shape not in ((p,), (N, p), (B, N, p)):
-                    raise ValueError("bounds of shape %s: expected (%d,), (%d, %d) or (%d, %d, %d)" % (a.shape, p, N, p, B, N, p))
-                a = np.ascontiguousarray(np.broadcast_to(a, (N, p) if shared else (B, N, p)))
-                keep.append(a)
-            ptrs.append(_any_ptr(a, (1 if shared else B) * N * p))
-        return ptrs[0], ptrs[1], shared, keep
-
     def initialize_flat_constrained(self, A, B, Q, H, R, q, r, d, x0, C_, D_, lo, hi):
         """ndlqr_InitializeBatchFlatConstrained: the nine arrays of initialize_flat_dense, then the constraint rows
         lo <= C x + D u <= hi per knot: C_ [batch, N, p*n], D_ [batch, N, p*m] column-major per knot (p is taken from C_'s
@@ -610,24 +694,9 @@ class BatchSolver:
         p = csize // (bt * N * n)
         sizes = dict(A=bt * N * n * n, B=bt * N * n * m, Q=bt * N * n * n, H=bt * N * n * m, R=bt * N * m * m,
                      q=bt * N * n, r=bt * N * m, d=bt * N * n, x0=bt * n, C=bt * N * p * n, D=bt * N * p * m)
-        ptrs, keep = [], []
-        for name, a in zip(("A", "B", "Q", "H", "R", "q", "r", "d", "x0", "C", "D"), (A, B, Q, H, R, q, r, d, x0, C_, D_)):
-            if a is None:
-                if name != "H":
-                    raise ValueError("%s is missing (only H may be None)" % name)
-                ptrs.append(None)
-                continue
-            if not hasattr(a, "ptr"):
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.size != sizes[name]:
-                    raise ValueError("bad size for %s" % name)
-                keep.append(a)
-            ptrs.append(_any_ptr(a, sizes[name]))
-        plo, phi, shared, keep2 = self._constraint_bounds(lo, hi, p)
-        err = self.L.ndlqr_InitializeBatchFlatConstrained(self.h, *ptrs[:9], p, ptrs[9], ptrs[10], plo, phi,
-                                                          BOUNDS_SHARED if shared else 0)
-        if err:
-            raise RuntimeError("ndlqr_InitializeBatchFlatConstrained failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        ptrs, keep = _stage(GRAD_DENSE_NAMES + ("C", "D"), (A, B, Q, H, R, q, r, d, x0, C_, D_), sizes)
+        bounds, shared, keep2 = _stage_bounds([(lo, p, False), (hi, p, False)], N, bt)
+        self._call("ndlqr_InitializeBatchFlatConstrained", self.h, *ptrs[:9], p, *ptrs[9:], *bounds, BOUNDS_SHARED if shared else 0)
         self._rows = p  # (only now: a refused call leaves the context, and the shapes checked here, as they were)
 
     def is_constrained(self):
@@ -637,71 +706,48 @@ class BatchSolver:
     def set_constraint_bounds(self, lo, hi):
         """ndlqr_BatchSetConstraintBounds: new lo, hi (shapes as for initialize_flat_constrained). Raises on a refusal
         (lo > hi, NaN, not in constrained mode); the previous bounds then stay."""
-        if not getattr(self, "_rows", 0):
+        if not self._rows:
             raise RuntimeError("ndlqr_BatchSetConstraintBounds: initialize_flat_constrained first")
-        plo, phi, shared, keep = self._constraint_bounds(lo, hi)
-        err = self.L.ndlqr_BatchSetConstraintBounds(self.h, plo, phi, BOUNDS_SHARED if shared else 0)
-        if err:
-            raise RuntimeError("ndlqr_BatchSetConstraintBounds failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        bounds, shared, keep = _stage_bounds([(lo, self._rows, False), (hi, self._rows, False)], self.N, self.batch)
+        self._call("ndlqr_BatchSetConstraintBounds", self.h, *bounds, BOUNDS_SHARED if shared else 0)
 
     def solve_constrained(self, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0, warm_start=False,
                           adapt_every=0):
         """ndlqr_SolveBatchLinConstrained (0 = the library's default of the box solve for every setting; adapt_every > 0 is
         refused: the adaptive penalty of this solve is switched on by set_constraint_adaptation). Returns (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached, 3 = not
         finite, 4 = certified infeasible (only after set_constraint_infeasibility(every > 0)). solutions() afterwards gives [lambda, x, u] of the last re-solve. Raises on a nonzero return."""
-        st = NdLqrBoxSettingsFull(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0,
-                                  int(adapt_every), 0.0, 0.0)
-        iters = np.zeros(self.batch, dtype=np.int32)
-        status = np.zeros(self.batch, dtype=np.int32)
-        err = self.L.ndlqr_SolveBatchLinConstrained(self.h, C.byref(st), iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                                    status.ctypes.data_as(C.POINTER(C.c_int)))
-        if err:
-            raise RuntimeError("ndlqr_SolveBatchLinConstrained failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return iters, status
+        return self._admm_solve("ndlqr_SolveBatchLinConstrained", (rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every),
+                                                                   1 if warm_start else 0, int(adapt_every), 0.0, 0.0))
 
     def set_constraint_adaptation(self, every=0, rho_min=0.0, rho_max=0.0):
         """ndlqr_BatchSetConstraintPenaltyAdaptation: every > 0 gives the solve_constrained() calls that follow the
         per-problem adaptive penalty, considered every that many iterations within [rho_min, rho_max] (0: the library's
         1e-6 and 1e6); every = 0 (the initial state): off. Raises on a refusal (a negative argument, rho_min > rho_max);
         the previous setting then stays."""
-        err = self.L.ndlqr_BatchSetConstraintPenaltyAdaptation(self.h, int(every), float(rho_min), float(rho_max))
-        if err:
-            raise RuntimeError("ndlqr_BatchSetConstraintPenaltyAdaptation failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_BatchSetConstraintPenaltyAdaptation", self.h, int(every), float(rho_min), float(rho_max))
 
     def constraint_penalties(self, rho=None):
         """ndlqr_CopyBatchConstraintPenalties: rho [batch] of the last solve_constrained (what an adaptive solve ended
         with); `rho`: destination (numpy array or DeviceArray)."""
-        if rho is None:
-            rho = np.zeros(self.batch)
-        err = self.L.ndlqr_CopyBatchConstraintPenalties(self.h, _any_ptr(rho, self.batch))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchConstraintPenalties failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return rho
+        return self._copy_out("ndlqr_CopyBatchConstraintPenalties", (self.batch,), dest=rho)
 
     def set_constraint_infeasibility(self, every=0, eps=0.0):
         """ndlqr_BatchSetConstraintInfeasibilityDetection: every > 0 lets the solve_constrained() calls that follow test
         every running problem for a primal infeasibility certificate at the iterations it >= 2, it % every == 0 (status 4;
         eps = 0: 1e-4); every = 0 (the initial state): off. Raises on a refusal (every < 0, eps negative or not finite);
         the previous setting then stays."""
-        err = self.L.ndlqr_BatchSetConstraintInfeasibilityDetection(self.h, int(every), float(eps))
-        if err:
-            raise RuntimeError("ndlqr_BatchSetConstraintInfeasibilityDetection failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_BatchSetConstraintInfeasibilityDetection", self.h, int(every), float(eps))
 
     def constraint_infeasibility_certificate(self, dlam=None, dmu=None):
         """ndlqr_CopyBatchConstraintInfeasibilityCertificate: (dlam [batch, N, n], dmu [batch, N, p]) of the last
         solve_constrained, which ran with detection on: the Farkas certificate of every status-4 problem, zero rows for
         the others; `dlam`, `dmu`: destinations (numpy arrays or DeviceArrays). Raises on a refusal."""
-        n, N, B, p = self.n, self.N, self.batch, getattr(self, "_rows", 1)
+        n, N, B, p = self.n, self.N, self.batch, self._rows or 1
         if dlam is None:
             dlam = np.zeros((B, N, n))
         if dmu is None:
             dmu = np.zeros((B, N, p))
-        err = self.L.ndlqr_CopyBatchConstraintInfeasibilityCertificate(self.h, _any_ptr(dlam, B * N * n), _any_ptr(dmu, B * N * p))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchConstraintInfeasibilityCertificate failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_CopyBatchConstraintInfeasibilityCertificate", self.h, _any_ptr(dlam, B * N * n), _any_ptr(dmu, B * N * p))
         return dlam, dmu
 
     def constraint_infeasibility_measures(self, measures=None, iteration=None):
@@ -709,53 +755,26 @@ class BatchSolver:
         solve_constrained, which ran with detection on: ||e||_inf, ||dmu||_inf, the largest |dmu_i| toward an infinite
         bound and S as the latest check of every problem found them, and the iteration of that check (0 and a row of
         zeros: no check examined the problem). Arguments as for infeasibility_measures. Raises on a refusal."""
-        B = self.batch
-        if measures is None:
-            measures = np.zeros((B, 4))
-        if iteration is None:
-            iteration = np.zeros(B, dtype=np.int32)
-        if hasattr(iteration, "ptr"):
-            ip = C.cast(C.c_void_p(int(iteration.ptr)), C.POINTER(C.c_int))
-        else:
-            if not (isinstance(iteration, np.ndarray) and iteration.dtype == np.int32 and iteration.flags["C_CONTIGUOUS"]
-                    and iteration.size == B):
-                raise ValueError("expected a C-contiguous int32 array of %d entries" % B)
-            ip = iteration.ctypes.data_as(C.POINTER(C.c_int))
-        err = self.L.ndlqr_CopyBatchConstraintInfeasibilityMeasures(self.h, _any_ptr(measures, 4 * B), ip)
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchConstraintInfeasibilityMeasures failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
-        return measures, iteration
+        return self._measures("ndlqr_CopyBatchConstraintInfeasibilityMeasures", measures, iteration)
 
     def constraint_multipliers(self):
         """ndlqr_CopyBatchConstraintMultipliers: mu = rho y, [batch, N, p]."""
-        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)))
-        err = self.L.ndlqr_CopyBatchConstraintMultipliers(self.h, _ptr(out))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchConstraintMultipliers failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        return self._copy_out("ndlqr_CopyBatchConstraintMultipliers", (self.batch, self.N, self._rows or 1))
 
     def constraint_residuals(self):
         """ndlqr_CopyBatchConstraintResiduals: [batch, 4] = r_prim | r_dual | s_prim | s_dual of the last constrained solve."""
-        out = np.zeros((self.batch, 4))
-        err = self.L.ndlqr_CopyBatchConstraintResiduals(self.h, _ptr(out))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchConstraintResiduals failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        return self._copy_out("ndlqr_CopyBatchConstraintResiduals", (self.batch, 4))
 
     def constraint_reduction(self):
         """ndlqr_hip_download_constraint_reduction (read-out for the tests): dict of numpy arrays -- the shifted costs Qs, Hs,
         Rs, the shifted records L, LR, G and reduced problem At .. x0t (as cost_reduction gives the plain ones), and the
         iterates v, y [batch, N, p] of the latest constrained solve."""
-        n, m, N, bt, p = self.n, self.m, self.N, self.batch, getattr(self, "_rows", 1)
+        n, m, N, bt, p = self.n, self.m, self.N, self.batch, self._rows or 1
         out = dict(Qs=np.zeros((bt, N, n * n)), Hs=np.zeros((bt, N, n * m)), Rs=np.zeros((bt, N, m * m)),
                    L=np.zeros((bt, N, n * n)), LR=np.zeros((bt, N, m * m)), G=np.zeros((bt, N, m * n)),
                    At=np.zeros((bt, N, n * n)), Bt=np.zeros((bt, N, n * m)), qt=np.zeros((bt, N, n)), rt=np.zeros((bt, N, m)),
                    dt=np.zeros((bt, N, n)), x0t=np.zeros((bt, n)), v=np.zeros((bt, N, p)), y=np.zeros((bt, N, p)))
-        err = self.L.ndlqr_hip_download_constraint_reduction(self.ctx, *[_ptr(out[k]) for k in (
-            "Qs", "Hs", "Rs", "L", "LR", "G", "At", "Bt", "qt", "rt", "dt", "x0t", "v", "y")])
-        if err:
-            raise RuntimeError("ndlqr_hip_download_constraint_reduction failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_hip_download_constraint_reduction", self.ctx, *[_ptr(a) for a in out.values()])
         return out
 
     # ---- gradients through the solve with linear inequality constraints (include/ndlqr.h: ndlqr_SolveBatchLinAdjoint,
@@ -768,17 +787,8 @@ class BatchSolver:
         not iterated, w = 0, zero gradients).
         Raises on a nonzero return. Afterwards adjoint() gives w in the caller's variables and constraint_gradients(),
         constraint_adjoint_multipliers(), constraint_adjoint_residuals() and constraint_codes() read the rest."""
-        if not hasattr(g, "ptr"):
-            g = np.ascontiguousarray(g, dtype=np.float64)
-        st = NdLqrBoxSettingsFull(0.0, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 0)
-        iters = np.zeros(self.batch, dtype=np.int32)
-        status = np.zeros(self.batch, dtype=np.int32)
-        err = self.L.ndlqr_SolveBatchLinAdjoint(self.h, _any_ptr(g, self.batch * self.nvars), C.byref(st),
-                                                iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                                status.ctypes.data_as(C.POINTER(C.c_int)))
-        if err:
-            raise RuntimeError("ndlqr_SolveBatchLinAdjoint failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return iters, status
+        return self._admm_solve("ndlqr_SolveBatchLinAdjoint", (0.0, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 0),
+                                _doubles(g))
 
     def constraint_gradients(self, summed=False, out=None):
         """ndlqr_BatchConstraintGradients: dict with keys C, D, lo, hi -> dL/d(C, D, lo, hi) of the last constrained
@@ -786,42 +796,25 @@ class BatchSolver:
         without the batch dimension, summed over the batch (NDLQR_BOUNDS_SHARED; two calls give the same bits). `out`:
         dict of destinations (numpy arrays or DeviceArrays); only those keys are computed. Default: numpy arrays for all
         four."""
-        n, m, N, B, p = self.n, self.m, self.N, self.batch, getattr(self, "_rows", 1)
-        shape = {k: ((N, w) if summed else (B, N, w)) for k, w in (("C", p * n), ("D", p * m), ("lo", p), ("hi", p))}
-        if out is None:
-            out = {k: np.zeros(sh) for k, sh in shape.items()}
-        unknown = set(out) - set(shape)
-        if unknown:
-            raise ValueError("unknown constraint gradient names: %s" % sorted(unknown))
-        ptrs = [None if out.get(k) is None else _any_ptr(out[k], int(np.prod(shape[k]))) for k in ("C", "D", "lo", "hi")]
-        err = self.L.ndlqr_BatchConstraintGradients(self.h, *ptrs, BOUNDS_SHARED if summed else 0)
-        if err:
-            raise RuntimeError("ndlqr_BatchConstraintGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        n, m, N, B, p = self.n, self.m, self.N, self.batch, self._rows or 1
+        shapes = {k: ((N, w) if summed else (B, N, w)) for k, w in (("C", p * n), ("D", p * m), ("lo", p), ("hi", p))}
+        return self._named_gradients("ndlqr_BatchConstraintGradients", shapes, out, BOUNDS_SHARED if summed else 0, False,
+                                     "constraint gradient")
 
     def constraint_adjoint_multipliers(self):
         """ndlqr_CopyBatchConstraintAdjointMultipliers: nu = rho y of the last constrained adjoint, [batch, N, p] (zero
         outside the active set)."""
-        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)))
-        err = self.L.ndlqr_CopyBatchConstraintAdjointMultipliers(self.h, _ptr(out))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchConstraintAdjointMultipliers failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        return self._copy_out("ndlqr_CopyBatchConstraintAdjointMultipliers", (self.batch, self.N, self._rows or 1))
 
     def constraint_adjoint_residuals(self, resid=None):
         """ndlqr_CopyBatchConstraintAdjointResiduals: [batch, 4] = r_prim | r_dual | s_prim | s_dual of the last constrained
         adjoint (a row of zeros for a problem it did not iterate)."""
-        return self._residuals("ndlqr_CopyBatchConstraintAdjointResiduals", resid)
+        return self._copy_out("ndlqr_CopyBatchConstraintAdjointResiduals", (self.batch, 4), dest=resid)
 
     def constraint_codes(self):
         """ndlqr_CopyBatchConstraintCodes: uint8 [batch, N, p] of the last constrained adjoint -- 0 unbounded, 1 bounded
         and inactive, 2 active at lo, 3 active at hi."""
-        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)), dtype=np.uint8)
-        err = self.L.ndlqr_CopyBatchConstraintCodes(self.h, out.ctypes.data_as(C.c_void_p))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchConstraintCodes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        return self._copy_out("ndlqr_CopyBatchConstraintCodes", (self.batch, self.N, self._rows or 1), np.uint8)
 
     # ---- active-set polish of the solve with linear inequality constraints (include/ndlqr.h:
     # ndlqr_PolishBatchLinConstrained; DESIGN.md section 3.23)
@@ -830,43 +823,26 @@ class BatchSolver:
         steps / status: int32 destinations [batch] (numpy arrays or device memory with `ptr`); default: new numpy arrays.
         Returns (steps, status): the accepted steps, and 1 = polished, 2 = not polished (the ADMM solution, v, y stay), 3 =
         not finite. Raises on a nonzero return."""
-        st = NdLqrPolishSettings(sigma, int(max_steps), int(max_rounds))
-        if steps is None:
-            steps = np.zeros(self.batch, dtype=np.int32)
-        if status is None:
-            status = np.zeros(self.batch, dtype=np.int32)
-        as_int = lambda a: (C.cast(C.c_void_p(int(a.ptr)), C.POINTER(C.c_int)) if hasattr(a, "ptr")
-                            else a.ctypes.data_as(C.POINTER(C.c_int)))
-        err = self.L.ndlqr_PolishBatchLinConstrained(self.h, C.byref(st), as_int(steps), as_int(status))
-        if err:
-            raise RuntimeError("ndlqr_PolishBatchLinConstrained failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
-        return steps, status
+        return self._polish("ndlqr_PolishBatchLinConstrained", (sigma, int(max_steps), int(max_rounds)), steps, status)
 
     def constraint_polish_codes(self):
         """ndlqr_CopyBatchConstraintPolishCodes: uint8 [batch, N, p] of the latest polish_constrained -- 0 unbounded, 1
         bounded and inactive, 2 active at lo, 3 active at hi."""
-        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)), dtype=np.uint8)
-        err = self.L.ndlqr_CopyBatchConstraintPolishCodes(self.h, out.ctypes.data_as(C.c_void_p))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchConstraintPolishCodes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        return self._copy_out("ndlqr_CopyBatchConstraintPolishCodes", (self.batch, self.N, self._rows or 1), np.uint8)
 
     def constraint_polish_residual(self, z, mu, codes, sig, poison_pad=False):
         """ndlqr_hip_constraint_polish_residual (test hook): the residual kernel of the polish alone on z [batch, nvars], mu,
         codes [batch, N, p] and sigma_p [batch]; poison_pad: the pad entries and pad knots of the device's z hold NaN
         instead of zero. Returns (r [batch, nvars], rc [batch, N, p], norms [2, batch])."""
-        p = getattr(self, "_rows", 1)
+        p = self._rows or 1
         z = np.ascontiguousarray(z, dtype=np.float64)
         mu = np.ascontiguousarray(mu, dtype=np.float64)
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
         sig = np.ascontiguousarray(sig, dtype=np.float64)
         assert z.shape == (self.batch, self.nvars) and mu.shape == codes.shape == (self.batch, self.N, p) and sig.shape == (self.batch,)
         r, rc, norms = np.zeros_like(z), np.zeros_like(mu), np.zeros((2, self.batch))
-        err = self.L.ndlqr_hip_constraint_polish_residual(self.ctx, _ptr(z), _ptr(mu), codes.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                                                          _ptr(sig), 1 if poison_pad else 0, _ptr(r), _ptr(rc), _ptr(norms))
-        if err:
-            raise RuntimeError("ndlqr_hip_constraint_polish_residual failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_hip_constraint_polish_residual", self.ctx, _ptr(z), _ptr(mu), codes.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                   _ptr(sig), 1 if poison_pad else 0, _ptr(r), _ptr(rc), _ptr(norms))
         return r, rc, norms
 
     def constraint_polish_phase_ms(self):
@@ -880,15 +856,12 @@ class BatchSolver:
         """ndlqr_hip_download_constraint_polish_state (test hook): dict of the latest polish_constrained -- zc [batch, nvars]
         and muc [batch, N, p], the candidate of its last formed step; norms [2, max_steps + 1, batch], the slots of its last
         round (max_steps: that of the call); sig [batch]; rounds, its factorisations."""
-        p = getattr(self, "_rows", 1)
+        p = self._rows or 1
         out = dict(zc=np.zeros((self.batch, self.nvars)), muc=np.zeros((self.batch, self.N, p)), sig=np.zeros(self.batch))
         norms = np.zeros(2 * 33 * self.batch)
         rounds = C.c_int(0)
-        err = self.L.ndlqr_hip_download_constraint_polish_state(self.ctx, _ptr(out["zc"]), _ptr(out["muc"]), _ptr(norms),
-                                                                _ptr(out["sig"]), C.byref(rounds))
-        if err:
-            raise RuntimeError("ndlqr_hip_download_constraint_polish_state failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_hip_download_constraint_polish_state", self.ctx, _ptr(out["zc"]), _ptr(out["muc"]), _ptr(norms),
+                   _ptr(out["sig"]), C.byref(rounds))
         out["norms"] = norms[: 2 * (max_steps + 1) * self.batch].reshape(2, max_steps + 1, self.batch).copy()
         out["rounds"] = rounds.value
         return out
@@ -896,25 +869,19 @@ class BatchSolver:
     def constraint_adjoint_iterate(self):
         """ndlqr_hip_download_constraint_codes (read-out for the tests): the constrained adjoint's own projected iterate
         v [batch, N, p] (0 on the fixed and the unbounded rows)."""
-        out = np.zeros((self.batch, self.N, getattr(self, "_rows", 1)))
-        err = self.L.ndlqr_hip_download_constraint_codes(self.ctx, None, _ptr(out))
-        if err:
-            raise RuntimeError("ndlqr_hip_download_constraint_codes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        out = np.zeros((self.batch, self.N, self._rows or 1))
+        self._call("ndlqr_hip_download_constraint_codes", self.ctx, None, _ptr(out))
         return out
 
     def initialize_synthetic(self, seed0):
-        err = self.L.ndlqr_InitializeBatchSynthetic(self.h, seed0)
-        if err:
-            raise RuntimeError("ndlqr_InitializeBatchSynthetic failed: %d" % err)
+        self._call("ndlqr_InitializeBatchSynthetic", self.h, seed0, detail=False)
 
     def solve(self):
         return self.L.ndlqr_SolveBatch(self.h)
 
     def set_rhs_flat(self, q, r, d, x0):
         arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (q, r, d, x0)]
-        err = self.L.ndlqr_BatchSetRhsFlat(self.h, *[_ptr(a) for a in arrs])
-        if err:
-            raise RuntimeError("ndlqr_BatchSetRhsFlat failed: %d" % err)
+        self._call("ndlqr_BatchSetRhsFlat", self.h, *[_ptr(a) for a in arrs], detail=False)
 
     def solve_rhs_only(self):
         """Solution sweep against the cached factorisation (needs FLAG_KEEP_FACT, or FLAG_KEEP_RECORDS
@@ -941,7 +908,7 @@ class BatchSolver:
             if out is None:
                 out = np.empty((nrhs, self.batch, self.nvars))
             err = self.L.ndlqr_SolveBatchMultiRhs(self.h, nrhs, *[_ptr(a) for a in arrs], _ptr(out))
-        if err:
+        if err:  # (not through _call: the message names the plain call for both)
             raise RuntimeError("ndlqr_SolveBatchMultiRhs failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
         return out
 
@@ -977,9 +944,7 @@ class BatchSolver:
         if out is None:
             out = np.zeros((self.batch, nknots, self.slice_width(blocks)))
         assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and out.size == self.batch * nknots * self.slice_width(blocks)
-        err = self.L.ndlqr_CopyBatchSolutionSlices(self.h, knot0, nknots, blocks, _ptr(out))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchSolutionSlices failed: %d" % err)
+        self._call("ndlqr_CopyBatchSolutionSlices", self.h, knot0, nknots, blocks, _ptr(out), detail=False)
         return out
 
     def step_async(self, q, r, d, x0, soln):
@@ -1037,20 +1002,15 @@ class BatchSolver:
         if out is None:
             out = np.zeros((self.batch, max(nknots, 0), self.slice_width(blocks)))
         ptr = _any_ptr(out, self.batch * max(nknots, 0) * self.slice_width(blocks))
-        err = self.L.ndlqr_CopyBatchSolutionSlicesDense(self.h, knot0, nknots, blocks, ptr)
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchSolutionSlicesDense failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_CopyBatchSolutionSlicesDense", self.h, knot0, nknots, blocks, ptr)
         return out
 
     def rhs_raw(self):
         """ndlqr_hip_download_rhs_raw (read-out for the tests): the latest right-hand side as it lies on the device,
         [batch, doubles per problem] in the device's block sizes and horizon, pad rows and tail knots included. Waits for
         everything in flight. Every mode."""
-        out = np.zeros((self.batch, int(self.L.ndlqr_hip_rhs_raw_doubles(self.ctx)) // self.batch))
-        err = self.L.ndlqr_hip_download_rhs_raw(self.ctx, _ptr(out))
-        if err:
-            raise RuntimeError("ndlqr_hip_download_rhs_raw failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        shape = (self.batch, int(self.L.ndlqr_hip_rhs_raw_doubles(self.ctx)) // self.batch)
+        return self._copy_out("ndlqr_hip_download_rhs_raw", shape, via_ctx=True)
 
     # ---- time-axis sharding (one problem over G ranks; include/ndlqr_hip.h)
     def time_shard_top_doubles(self, G):
@@ -1082,18 +1042,14 @@ class BatchSolver:
 
     def solution(self, p):
         out = np.zeros(self.nvars)
-        got = self.L.ndlqr_CopyBatchSolution(self.h, p, _ptr(out))
-        if got != self.nvars:
-            raise RuntimeError("ndlqr_CopyBatchSolution failed: %d" % got)
+        self._call("ndlqr_CopyBatchSolution", self.h, p, _ptr(out), detail=False, ok=(self.nvars,))
         return out
 
     def kkt_residuals(self):
         """(res, bnorm): ||K z - b||_2 and ||b||_2 of every problem, evaluated on the device."""
         res = np.zeros(self.batch)
         bn = np.zeros(self.batch)
-        err = self.L.ndlqr_BatchKktResiduals(self.h, _ptr(res), _ptr(bn))
-        if err:
-            raise RuntimeError("ndlqr_BatchKktResiduals failed: %d" % err)
+        self._call("ndlqr_BatchKktResiduals", self.h, _ptr(res), _ptr(bn), detail=False)
         return res, bn
 
     def solutions(self, out=None):
@@ -1101,9 +1057,7 @@ class BatchSolver:
         if out is None:
             out = np.zeros((self.batch, self.nvars))
         assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and out.size == self.batch * self.nvars
-        got = self.L.ndlqr_CopyBatchSolutions(self.h, _ptr(out))
-        if got != self.nvars:
-            raise RuntimeError("ndlqr_CopyBatchSolutions failed: %d" % got)
+        self._call("ndlqr_CopyBatchSolutions", self.h, _ptr(out), detail=False, ok=(self.nvars,))
         return out
 
     # ---- adjoint solve and parameter gradients (include/ndlqr.h: ndlqr_SolveBatchAdjoint, ndlqr_BatchGradients)
@@ -1111,17 +1065,13 @@ class BatchSolver:
         """ndlqr_SolveBatchAdjoint: K w = g for g = dL/dz [batch, nvars] (numpy array or DeviceArray) against the
         factorisation the last solve kept (FLAG_KEEP_RECORDS or FLAG_KEEP_FACT). Returns the C return code (0, or -1 when
         there is no kept factorisation of the resident solution)."""
-        if not hasattr(g, "ptr"):
-            g = np.ascontiguousarray(g, dtype=np.float64)
-        return self.L.ndlqr_SolveBatchAdjoint(self.h, _any_ptr(g, self.batch * self.nvars))
+        return self.L.ndlqr_SolveBatchAdjoint(self.h, _any_ptr(_doubles(g), self.batch * self.nvars))
 
     def adjoint(self, out=None):
         """ndlqr_CopyBatchAdjoint: the adjoint solution w [batch, nvars] into `out` (numpy array or DeviceArray)."""
         if out is None:
             out = np.zeros((self.batch, self.nvars))
-        got = self.L.ndlqr_CopyBatchAdjoint(self.h, _any_ptr(out, self.batch * self.nvars))
-        if got != self.nvars:
-            raise RuntimeError("ndlqr_CopyBatchAdjoint failed: %d (%s)" % (got, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_CopyBatchAdjoint", self.h, _any_ptr(out, self.batch * self.nvars), ok=(self.nvars,))
         return out
 
     def gradient_shape(self, name, summed=False):
@@ -1135,20 +1085,8 @@ class BatchSolver:
         initialize_flat (A, B column-major per knot); those whose bit is in sum_mask (GRAD_*) summed over the batch.
         `out`: dict of destinations (numpy arrays or DeviceArrays); only those names are computed. Default: numpy arrays
         for all eight."""
-        if out is None:
-            out = {k: np.zeros(self.gradient_shape(k, bool(sum_mask & (1 << i)))) for i, k in enumerate(GRAD_NAMES)}
-        unknown = set(out) - set(GRAD_NAMES)
-        if unknown:
-            raise ValueError("unknown gradient names: %s" % sorted(unknown))
-        ptrs = []
-        for i, k in enumerate(GRAD_NAMES):
-            a = out.get(k)
-            ptrs.append(None if a is None else
-                        _any_ptr(a, int(np.prod(self.gradient_shape(k, bool(sum_mask & (1 << i)))))))
-        err = self.L.ndlqr_BatchGradients(self.h, sum_mask, *ptrs)
-        if err:
-            raise RuntimeError("ndlqr_BatchGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        shapes = {k: self.gradient_shape(k, bool(sum_mask & (1 << i))) for i, k in enumerate(GRAD_NAMES)}
+        return self._named_gradients("ndlqr_BatchGradients", shapes, out, sum_mask, True, "gradient")
 
     def dense_gradient_shape(self, name, summed=False):
         """Shape of gradient `name` (GRAD_DENSE_NAMES) in the flat layout of initialize_flat_dense, per problem or summed
@@ -1164,20 +1102,8 @@ class BatchSolver:
         initialize_flat_dense (matrices column-major per knot); those whose bit is in sum_mask (GRADD_*) summed over the
         batch. `out`: dict of destinations (numpy arrays or DeviceArrays); only those names are computed. Default: numpy
         arrays for all nine."""
-        if out is None:
-            out = {k: np.zeros(self.dense_gradient_shape(k, bool(sum_mask & (1 << i)))) for i, k in enumerate(GRAD_DENSE_NAMES)}
-        unknown = set(out) - set(GRAD_DENSE_NAMES)
-        if unknown:
-            raise ValueError("unknown gradient names: %s" % sorted(unknown))
-        ptrs = []
-        for i, k in enumerate(GRAD_DENSE_NAMES):
-            a = out.get(k)
-            ptrs.append(None if a is None else
-                        _any_ptr(a, int(np.prod(self.dense_gradient_shape(k, bool(sum_mask & (1 << i)))))))
-        err = self.L.ndlqr_BatchGradientsDense(self.h, sum_mask, *ptrs)
-        if err:
-            raise RuntimeError("ndlqr_BatchGradientsDense failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        shapes = {k: self.dense_gradient_shape(k, bool(sum_mask & (1 << i))) for i, k in enumerate(GRAD_DENSE_NAMES)}
+        return self._named_gradients("ndlqr_BatchGradientsDense", shapes, out, sum_mask, True, "gradient")
 
     # ---- feedback gains and cost-to-go matrices (include/ndlqr.h: ndlqr_BatchFeedbackGains)
     def feedback_gains(self, knot0=0, nknots=None, want=("K", "k", "P", "p"), out=None):
@@ -1202,9 +1128,7 @@ class BatchSolver:
         res = dict(out) if out is not None else {k: np.zeros(flat[k]) for k in names}
         ptrs = [None if res.get(k) is None else _any_ptr(res[k], int(np.prod(flat[k]))) for k in ("K", "k", "P", "p")]
         failures = np.zeros(bt, dtype=np.int32)
-        err = self.L.ndlqr_BatchFeedbackGains(self.h, int(knot0), int(nknots), *ptrs, failures.ctypes.data_as(C.POINTER(C.c_int)))
-        if err not in (0, ERR_NOT_SPD):
-            raise RuntimeError("ndlqr_BatchFeedbackGains failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_BatchFeedbackGains", self.h, int(knot0), int(nknots), *ptrs, _int_ptr(failures, bt), ok=(0, ERR_NOT_SPD))
         if out is None:
             for k in ("K", "P"):
                 if k in res:
@@ -1233,18 +1157,14 @@ class BatchSolver:
         else:
             res = {k: np.zeros(shapes[k]) for k in (("J", "stage") if stage else ("J",))}
         ptrs = [None if res.get(k) is None else _any_ptr(res[k], int(np.prod(shapes[k]))) for k in ("J", "stage")]
-        err = self.L.ndlqr_BatchObjective(self.h, *ptrs)
-        if err:
-            raise RuntimeError("ndlqr_BatchObjective failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_BatchObjective", self.h, *ptrs)
         return res
 
     # ---- iterative refinement (include/ndlqr.h: ndlqr_RefineBatch, ndlqr_RefineBatchAdjoint, ndlqr_BatchKktResidualVector)
     def _refine(self, name, max_steps):
         steps = np.zeros(self.batch, dtype=np.int32)
         before, after = np.zeros(self.batch), np.zeros(self.batch)
-        err = getattr(self.L, name)(self.h, int(max_steps), steps.ctypes.data_as(C.POINTER(C.c_int)), _ptr(before), _ptr(after))
-        if err:
-            raise RuntimeError("%s failed: %d (%s)" % (name, err, self.L.ndlqr_hip_last_error().decode()))
+        self._call(name, self.h, int(max_steps), _int_ptr(steps, self.batch), _ptr(before), _ptr(after))
         return steps, before, after
 
     def refine(self, max_steps=2):
@@ -1262,12 +1182,7 @@ class BatchSolver:
     def kkt_residual_vector(self, out=None):
         """ndlqr_BatchKktResidualVector: r = b - K z of the resident solutions, [batch, nvars] in the packing of solutions(),
         every row accumulated in double-double and rounded once; `out`: destination (numpy array or DeviceArray)."""
-        if out is None:
-            out = np.zeros((self.batch, self.nvars))
-        err = self.L.ndlqr_BatchKktResidualVector(self.h, _any_ptr(out, self.batch * self.nvars))
-        if err:
-            raise RuntimeError("ndlqr_BatchKktResidualVector failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        return self._copy_out("ndlqr_BatchKktResidualVector", (self.batch, self.nvars), dest=out)
 
     def refine_phase_ms(self):
         """(residual, re-solve, commit) device times in ms of the latest refinement that ran under FLAG_PROFILE."""
@@ -1280,21 +1195,9 @@ class BatchSolver:
         """ndlqr_BatchSetBounds. Each bound is None (unbounded), a numpy array of shape (n,) / (m,), (N, n) / (N, m) --
         one set for every problem, sent as NDLQR_BOUNDS_SHARED -- or (batch, N, n) / (batch, N, m), or a DeviceArray of
         batch * N * n (m) doubles. Entries may be +-inf. Raises on a refusal (lo > hi)."""
-        n, m, N, B = self.n, self.m, self.N, self.batch
-        given = [(a, k) for a, k in ((xlo, n), (xhi, n), (ulo, m), (uhi, m))]
-        host = [(a if a is None or hasattr(a, "ptr") else np.asarray(a, dtype=np.float64)) for a, _ in given]
-        shared = all(a is None or (not hasattr(a, "ptr") and a.ndim <= 2) for a in host)
-        ptrs, keep = [], []
-        for a, (_, k) in zip(host, given):
-            if a is not None and not hasattr(a, "ptr"):
-                if a.shape not in ((k,), (N, k), (B, N, k)):
-                    raise ValueError("bounds of shape %s: expected (%d,), (%d, %d) or (%d, %d, %d)" % (a.shape, k, N, k, B, N, k))
-                a = np.ascontiguousarray(np.broadcast_to(a, (N, k) if shared else (B, N, k)))
-                keep.append(a)
-            ptrs.append(None if a is None else _any_ptr(a, (1 if shared else B) * N * k))
-        err = self.L.ndlqr_BatchSetBounds(self.h, BOUNDS_SHARED if shared else 0, *ptrs)
-        if err:
-            raise RuntimeError("ndlqr_BatchSetBounds failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        n, m = self.n, self.m
+        ptrs, shared, keep = _stage_bounds([(xlo, n, True), (xhi, n, True), (ulo, m, True), (uhi, m, True)], self.N, self.batch)
+        self._call("ndlqr_BatchSetBounds", self.h, BOUNDS_SHARED if shared else 0, *ptrs)
 
     def solve_box(self, rho=0.0, alpha=0.0, eps_abs=0.0, eps_rel=0.0, max_iter=0, check_every=0, warm_start=False,
                   adapt_every=0, rho_min=0.0, rho_max=0.0):
@@ -1302,25 +1205,15 @@ class BatchSolver:
         adaptive penalty, considered every that many iterations and kept within [rho_min, rho_max]; 0: fixed rho. Returns
         (iters, status) as numpy int arrays [batch]; status 1 = converged, 2 = max_iter reached, 3 = not finite, 4 = primal
         infeasible with a certificate (only after set_box_infeasibility(every > 0)). Raises on a nonzero return."""
-        st = NdLqrBoxSettingsFull(rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 1 if warm_start else 0,
-                                  int(adapt_every), rho_min, rho_max)
-        iters = np.zeros(self.batch, dtype=np.int32)
-        status = np.zeros(self.batch, dtype=np.int32)
-        err = self.L.ndlqr_SolveBatchBoxConstrained(self.h, C.byref(st), iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                                    status.ctypes.data_as(C.POINTER(C.c_int)))
-        if err:
-            raise RuntimeError("ndlqr_SolveBatchBoxConstrained failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
-        return iters, status
+        return self._admm_solve("ndlqr_SolveBatchBoxConstrained", (rho, alpha, eps_abs, eps_rel, int(max_iter), int(check_every),
+                                                                   1 if warm_start else 0, int(adapt_every), rho_min, rho_max))
 
     def set_box_infeasibility(self, every=0, eps=0.0):
         """ndlqr_BatchSetInfeasibilityDetection: every > 0 lets the constrained solves that follow test every running
         problem for a primal infeasibility certificate at the iterations it % every == 0 (status 4; eps = 0: 1e-4);
         every = 0 (the initial state): off. Raises on a refusal (every < 0, eps negative or not finite); the previous
         setting then stays."""
-        err = self.L.ndlqr_BatchSetInfeasibilityDetection(self.h, int(every), float(eps))
-        if err:
-            raise RuntimeError("ndlqr_BatchSetInfeasibilityDetection failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_BatchSetInfeasibilityDetection", self.h, int(every), float(eps))
 
     def infeasibility_certificate(self, dlam=None, dmu_x=None, dmu_u=None):
         """ndlqr_CopyBatchInfeasibilityCertificate: (dlam [batch, N, n], dmu_x [batch, N, n], dmu_u [batch, N, m]) of the
@@ -1333,11 +1226,8 @@ class BatchSolver:
             dmu_x = np.zeros((B, N, n))
         if dmu_u is None:
             dmu_u = np.zeros((B, N, m))
-        err = self.L.ndlqr_CopyBatchInfeasibilityCertificate(self.h, _any_ptr(dlam, B * N * n), _any_ptr(dmu_x, B * N * n),
-                                                             _any_ptr(dmu_u, B * N * m))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchInfeasibilityCertificate failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_CopyBatchInfeasibilityCertificate", self.h, _any_ptr(dlam, B * N * n), _any_ptr(dmu_x, B * N * n),
+                   _any_ptr(dmu_u, B * N * m))
         return dlam, dmu_x, dmu_u
 
     def infeasibility_measures(self, measures=None, iteration=None):
@@ -1346,32 +1236,14 @@ class BatchSolver:
         latest check of every problem found them, and the iteration of that check (0 and a row of zeros: no check examined
         the problem). `measures`: destination (numpy array or DeviceArray); `iteration`: a C-contiguous int32 numpy array,
         or anything with `ptr` addressing batch ints of device memory. Raises on a refusal."""
-        B = self.batch
-        if measures is None:
-            measures = np.zeros((B, 4))
-        if iteration is None:
-            iteration = np.zeros(B, dtype=np.int32)
-        if hasattr(iteration, "ptr"):
-            ip = C.cast(C.c_void_p(int(iteration.ptr)), C.POINTER(C.c_int))
-        else:
-            if not (isinstance(iteration, np.ndarray) and iteration.dtype == np.int32 and iteration.flags["C_CONTIGUOUS"]
-                    and iteration.size == B):
-                raise ValueError("expected a C-contiguous int32 array of %d entries" % B)
-            ip = iteration.ctypes.data_as(C.POINTER(C.c_int))
-        err = self.L.ndlqr_CopyBatchInfeasibilityMeasures(self.h, _any_ptr(measures, 4 * B), ip)
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchInfeasibilityMeasures failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
-        return measures, iteration
+        return self._measures("ndlqr_CopyBatchInfeasibilityMeasures", measures, iteration)
 
     def set_box_acceleration(self, mem=0, safeguard=0.0, reg=0.0):
         """ndlqr_BatchSetBoxAcceleration: mem in 1 .. 16 lets the constrained solves that follow take safeguarded
         Anderson-accelerated steps from the last mem iterations (safeguard = 0: 1.0, reg = 0: 1e-10; 5 is the documented
         memory); mem = 0 (the initial state): off. Raises on a refusal (mem outside 0 .. 16, safeguard or reg negative or
         not finite); the previous setting then stays."""
-        err = self.L.ndlqr_BatchSetBoxAcceleration(self.h, int(mem), float(safeguard), float(reg))
-        if err:
-            raise RuntimeError("ndlqr_BatchSetBoxAcceleration failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_BatchSetBoxAcceleration", self.h, int(mem), float(safeguard), float(reg))
         self._accel_mem = int(mem)
 
     def box_acceleration(self):
@@ -1379,44 +1251,28 @@ class BatchSolver:
         the last constrained solve, which ran with acceleration on: the steps it took accelerated, the steps its
         safeguard rejected, and the coefficients and column count of every problem's latest accelerated step. Raises on
         a refusal."""
-        B, mem = self.batch, getattr(self, "_accel_mem", 0)
+        B, mem = self.batch, self._accel_mem
         ints = [np.zeros(B, dtype=np.int32) for _ in range(3)]
         gamma = np.zeros((B, max(mem, 1)))
-        ip = [a.ctypes.data_as(C.POINTER(C.c_int)) for a in ints]
-        err = self.L.ndlqr_CopyBatchBoxAcceleration(self.h, ip[0], ip[1], _ptr(gamma), ip[2])
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchBoxAcceleration failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        ip = [_int_ptr(a, B) for a in ints]
+        self._call("ndlqr_CopyBatchBoxAcceleration", self.h, ip[0], ip[1], _ptr(gamma), ip[2])
         return ints[0], ints[1], gamma[:, :mem], ints[2]
 
     def box_penalties(self, rho=None):
         """ndlqr_CopyBatchBoxPenalties: rho [batch] of the last constrained solve (what an adaptive solve ended with);
         `rho`: destination (numpy array or DeviceArray)."""
-        if rho is None:
-            rho = np.zeros(self.batch)
-        err = self.L.ndlqr_CopyBatchBoxPenalties(self.h, _any_ptr(rho, self.batch))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchBoxPenalties failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return rho
-
-    def _residuals(self, name, resid):
-        if resid is None:
-            resid = np.zeros((self.batch, 4))
-        err = getattr(self.L, name)(self.h, _any_ptr(resid, 4 * self.batch))
-        if err:
-            raise RuntimeError("%s failed: %d (%s)" % (name, err, self.L.ndlqr_hip_last_error().decode()))
-        return resid
+        return self._copy_out("ndlqr_CopyBatchBoxPenalties", (self.batch,), dest=rho)
 
     def box_residuals(self, resid=None):
         """ndlqr_CopyBatchBoxResiduals: [batch, 4] = r_prim | r_dual | s_prim | s_dual of the last constrained solve, the
         numbers of the convergence test as the last update of every problem found them (its freezing iteration, or
         max_iter for status 2); `resid`: destination (numpy array or DeviceArray). Raises on a refusal."""
-        return self._residuals("ndlqr_CopyBatchBoxResiduals", resid)
+        return self._copy_out("ndlqr_CopyBatchBoxResiduals", (self.batch, 4), dest=resid)
 
     def box_adjoint_residuals(self, resid=None):
         """ndlqr_CopyBatchBoxAdjointResiduals: the same of the last box adjoint (a row of zeros for a problem it did
         not iterate)."""
-        return self._residuals("ndlqr_CopyBatchBoxAdjointResiduals", resid)
+        return self._copy_out("ndlqr_CopyBatchBoxAdjointResiduals", (self.batch, 4), dest=resid)
 
     def bound_multipliers(self, mu_x=None, mu_u=None):
         """ndlqr_CopyBatchBoundMultipliers: (mu_x [batch, N, n], mu_u [batch, N, m]) = rho y of the last constrained solve;
@@ -1426,10 +1282,7 @@ class BatchSolver:
             mu_x = np.zeros((B, N, n))
         if mu_u is None:
             mu_u = np.zeros((B, N, m))
-        err = self.L.ndlqr_CopyBatchBoundMultipliers(self.h, _any_ptr(mu_x, B * N * n), _any_ptr(mu_u, B * N * m))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchBoundMultipliers failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
+        self._call("ndlqr_CopyBatchBoundMultipliers", self.h, _any_ptr(mu_x, B * N * n), _any_ptr(mu_u, B * N * m))
         return mu_x, mu_u
 
     # ---- gradients through the box-constrained solve (include/ndlqr.h: ndlqr_SolveBatchBoxAdjoint,
@@ -1441,78 +1294,34 @@ class BatchSolver:
         converged, 2 = max_iter reached, 3 = not finite (or the forward's was), 4 = the forward certified the problem
         infeasible (not iterated: w = 0, zero gradients). Raises on a nonzero return. Afterwards
         adjoint() and gradients() read its w."""
-        if not hasattr(g, "ptr"):
-            g = np.ascontiguousarray(g, dtype=np.float64)
-        st = NdLqrBoxSettingsFull(0.0, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 0)
-        iters = np.zeros(self.batch, dtype=np.int32)
-        status = np.zeros(self.batch, dtype=np.int32)
-        err = self.L.ndlqr_SolveBatchBoxAdjoint(self.h, _any_ptr(g, self.batch * self.nvars), C.byref(st),
-                                                iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                                status.ctypes.data_as(C.POINTER(C.c_int)))
-        if err:
-            raise RuntimeError("ndlqr_SolveBatchBoxAdjoint failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return iters, status
+        return self._admm_solve("ndlqr_SolveBatchBoxAdjoint", (0.0, alpha, eps_abs, eps_rel, int(max_iter), int(check_every), 0),
+                                _doubles(g))
 
     def bound_gradients(self, summed=False, out=None):
         """ndlqr_BatchBoundGradients: dict with keys xlo, xhi, ulo, uhi -> dL/d(bound) of the last box adjoint, [batch, N, n]
         / [batch, N, m], or [N, n] / [N, m] summed over the batch (NDLQR_BOUNDS_SHARED). `out`: dict of destinations
         (numpy arrays or DeviceArrays); only those keys are computed. Default: numpy arrays for all four."""
         n, m, N, B = self.n, self.m, self.N, self.batch
-        shape = {k: ((N, w) if summed else (B, N, w)) for k, w in (("xlo", n), ("xhi", n), ("ulo", m), ("uhi", m))}
-        if out is None:
-            out = {k: np.zeros(sh) for k, sh in shape.items()}
-        unknown = set(out) - set(shape)
-        if unknown:
-            raise ValueError("unknown bound names: %s" % sorted(unknown))
-        ptrs = [None if out.get(k) is None else _any_ptr(out[k], int(np.prod(shape[k]))) for k in ("xlo", "xhi", "ulo", "uhi")]
-        err = self.L.ndlqr_BatchBoundGradients(self.h, BOUNDS_SHARED if summed else 0, *ptrs)
-        if err:
-            raise RuntimeError("ndlqr_BatchBoundGradients failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        shapes = {k: ((N, w) if summed else (B, N, w)) for k, w in (("xlo", n), ("xhi", n), ("ulo", m), ("uhi", m))}
+        return self._named_gradients("ndlqr_BatchBoundGradients", shapes, out, BOUNDS_SHARED if summed else 0, True, "bound")
 
     # ---- active-set polish (include/ndlqr.h: ndlqr_PolishBatchBoxConstrained)
     def polish_box(self, sigma=0.0, max_steps=0, max_rounds=0, steps=None, status=None):
         """ndlqr_PolishBatchBoxConstrained on the latest constrained solve (0 = the library's default for every setting).
         Returns (steps, status) as numpy int arrays [batch] (or the DeviceArray-like destinations given); status 1 =
         polished, 2 = not polished (the ADMM solution stays), 3 = not finite. Raises on a nonzero return."""
-        st = NdLqrPolishSettings(sigma, int(max_steps), int(max_rounds))
-        if steps is None:
-            steps = np.zeros(self.batch, dtype=np.int32)
-        if status is None:
-            status = np.zeros(self.batch, dtype=np.int32)
-        as_int = lambda a: C.cast(a.ptr, C.POINTER(C.c_int)) if hasattr(a, "ptr") else a.ctypes.data_as(C.POINTER(C.c_int))
-        err = self.L.ndlqr_PolishBatchBoxConstrained(self.h, C.byref(st), as_int(steps), as_int(status))
-        if err:
-            raise RuntimeError("ndlqr_PolishBatchBoxConstrained failed: %d (%s)"
-                               % (err, self.L.ndlqr_hip_last_error().decode()))
-        return steps, status
+        return self._polish("ndlqr_PolishBatchBoxConstrained", (sigma, int(max_steps), int(max_rounds)), steps, status)
 
     def solve_polished_adjoint(self, g, max_steps=0, steps=None, status=None):
         """ndlqr_SolveBatchPolishedAdjoint: the adjoint of the polished active-set system for g = dL/dz* [batch, nvars]
         (numpy array or DeviceArray) on the polish's factorisation. Returns (steps, status); status 1 = solved, 2 / 3 = the
         polish status of a problem that was not polished (its w and nu are 0), or 2 = no step accepted. Raises on a nonzero
         return. Afterwards adjoint(), gradients() and bound_gradients() read its w and nu."""
-        if not hasattr(g, "ptr"):
-            g = np.ascontiguousarray(g, dtype=np.float64)
-        st = NdLqrPolishSettings(0.0, int(max_steps), 0)
-        if steps is None:
-            steps = np.zeros(self.batch, dtype=np.int32)
-        if status is None:
-            status = np.zeros(self.batch, dtype=np.int32)
-        as_int = lambda a: C.cast(a.ptr, C.POINTER(C.c_int)) if hasattr(a, "ptr") else a.ctypes.data_as(C.POINTER(C.c_int))
-        err = self.L.ndlqr_SolveBatchPolishedAdjoint(self.h, _any_ptr(g, self.batch * self.nvars), C.byref(st), as_int(steps),
-                                                     as_int(status))
-        if err:
-            raise RuntimeError("ndlqr_SolveBatchPolishedAdjoint failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return steps, status
+        return self._polish("ndlqr_SolveBatchPolishedAdjoint", (0.0, int(max_steps), 0), steps, status, _doubles(g))
 
     def polish_codes(self):
         """developer / test hook: entry codes [batch, N, n+m] of the latest polish (0 unbounded, 1 free, 2 at the lower bound, 3 at the upper)"""
-        out = np.zeros((self.batch, self.N, self.n + self.m), dtype=np.uint8)
-        err = self.L.ndlqr_hip_download_polish_codes(self.ctx, out.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        if err:
-            raise RuntimeError("ndlqr_hip_download_polish_codes failed: %d (%s)" % (err, self.L.ndlqr_hip_last_error().decode()))
-        return out
+        return self._copy_out("ndlqr_hip_download_polish_codes", (self.batch, self.N, self.n + self.m), np.uint8, via_ctx=True)
 
     def factor_count(self):
         """factorisations this solver has launched (ndlqr_hip_factor_count; tests of the kept shifted factorisation)"""
@@ -1520,15 +1329,11 @@ class BatchSolver:
 
     def solutions_to_device(self, device_ptr):
         """[batch][nvars] packed solutions into device memory (asynchronous on the solver's stream)."""
-        got = self.L.ndlqr_CopyBatchSolutionsDevice(self.h, C.c_void_p(int(device_ptr)))
-        if got != self.nvars:
-            raise RuntimeError("ndlqr_CopyBatchSolutionsDevice failed: %d" % got)
+        self._call("ndlqr_CopyBatchSolutionsDevice", self.h, C.c_void_p(int(device_ptr)), detail=False, ok=(self.nvars,))
 
     def upload_packed(self, AB, QR, rhs):
         """Raw H2D of inputs already in the device layout of include/ndlqr_hip.h (whole batch)."""
-        err = self.L.ndlqr_hip_upload_inputs(self.ctx, 0, self.batch, _ptr(AB), _ptr(QR), _ptr(rhs))
-        if err:
-            raise RuntimeError("ndlqr_hip_upload_inputs failed: %d" % err)
+        self._call("ndlqr_hip_upload_inputs", self.ctx, 0, self.batch, _ptr(AB), _ptr(QR), _ptr(rhs), detail=False)
 
     def factors(self, p):
         if self.N & (self.N - 1):
@@ -1537,9 +1342,7 @@ class BatchSolver:
                                % self.N)
         K = int(np.log2(self.N))
         out = np.zeros(self.N * K * (2 * self.n + self.m) * self.n)
-        err = self.L.ndlqr_CopyBatchFactors(self.h, p, _ptr(out))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchFactors failed: %d" % err)
+        self._call("ndlqr_CopyBatchFactors", self.h, p, _ptr(out), detail=False)
         return out
 
     def cholesky_failures(self):
@@ -1550,9 +1353,7 @@ class BatchSolver:
         solver was created (or since the recovery of a solve that did not complete zeroed them): the failures of one solve
         are the difference between two calls."""
         out = np.zeros(self.batch, dtype=np.int32)
-        err = self.L.ndlqr_CopyBatchCholeskyFailureCounts(self.h, out.ctypes.data_as(C.POINTER(C.c_int)))
-        if err:
-            raise RuntimeError("ndlqr_CopyBatchCholeskyFailureCounts failed: %d" % err)
+        self._call("ndlqr_CopyBatchCholeskyFailureCounts", self.h, _int_ptr(out, self.batch), detail=False)
         return out
 
     def profile(self):

@@ -33,10 +33,15 @@ def test_the_new_getters_are_exported_and_refuse_a_null_solver(ndlqr):
         # (no device here, so no solver: every call is refused; test_gpu_box_update.py sends them to a real one)
         assert fn(None, dp) == ndlqr.api.ERR_INVALID, name
     assert (buf == 0).all()
-    # a row is four doubles: what BatchSolver.box_residuals() allocates for a batch of 3
-    import inspect
-    src = inspect.getsource(ndlqr.api.BatchSolver._residuals)
-    assert "np.zeros((self.batch, 4))" in src and "4 * self.batch" in src
+    # a row is four doubles: what BatchSolver.box_residuals() allocates for a batch of 3, and asks of a destination
+    import types
+    bs = ndlqr.api.BatchSolver.__new__(ndlqr.api.BatchSolver)
+    bs.batch, bs.h, bs.L = 3, None, types.SimpleNamespace(ndlqr_CopyBatchBoxResiduals=lambda h, p: 0)
+    given = np.zeros(4 * 3)
+    assert bs.box_residuals().shape == (3, 4) and bs.box_residuals(given) is given
+    for bad in (np.zeros(4 * 3 - 1), np.zeros(4 * 3 + 1)):
+        with pytest.raises(ValueError, match="expected a C-contiguous float64 array of 12 doubles"):
+            bs.box_residuals(bad)
 
 
 # ------------------------------------------------------------------------------------------------ 2. the restatement is the old one
