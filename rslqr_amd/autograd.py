@@ -25,6 +25,10 @@ backward is the adjoint of the active-set system (ndlqr_SolveBatchLinAdjoint), t
 ``lqr_solve_box`` adds bounds on x and u (ndlqr_SolveBatchBoxConstrained); its backward is the adjoint of the
 active-set system (ndlqr_SolveBatchBoxAdjoint) plus the gradients with respect to the bounds (ndlqr_BatchBoundGradients).
 
+``lqr_value`` and ``lqr_value_dense`` return the optimal values J* [b] of the problems of ``lqr_solve`` and of
+``lqr_solve_dense`` (ndlqr_BatchObjective behind a plain solve on the same cached solvers); their backward needs no adjoint
+solve: by the envelope theorem it is the partial derivative of the Lagrangian at the saved solution, in torch.
+
 Process start-up: torch ships its own HIP runtime next to the system one this library links. Initialise torch's device
 (any CUDA tensor) before the library's first device call in a process; the other order may leave torch without a device.
 """
@@ -34,8 +38,21 @@ import torch
 
 from .api import BatchSolver, FLAG_KEEP_RECORDS, GRAD_DENSE_NAMES, GRAD_NAMES
 
+# (what `from rslqr_amd.autograd import *` gives; lqr_solve_dense, lqr_solve_constrained, lqr_value, lqr_value_dense and
+# their Function classes are public too and are imported by name)
+__all__ = ["LqrSolve", "LqrSolveRefined", "LqrSolveBox", "lqr_solve", "lqr_solve_box", "split_solution"]
+
 _ARGS = ("A", "B", "Q", "R", "q", "r", "d", "x0")
-_cache = {}                  # (n, m, N, b, device index) -> [BatchSolver, token of the forward it holds]
+_BOUNDS = ("xlo", "xhi", "ulo", "uhi")
+_DENSE_ARGS = ("A", "B", "Q", "H", "R", "q", "r", "d", "x0")
+_ROW_ARGS = ("C", "D", "lo", "hi")
+# Four caches, key -> [BatchSolver, token of the forward it holds]. The box solve has one of its own, so that lqr_solve and
+# lqr_solve_box do not evict each other's solvers; a solver in dense-cost mode serves no diagonal forward in between; a
+# solver in constrained mode retains its problem on the device.
+_cache = {}                  # (n, m, N, b, device index)
+_box_cache = {}              # (n, m, N, b, device index)
+_dense_cache = {}            # (n, m, N, b, device index)
+_lin_cache = {}              # (n, m, N, p, b, device index)
 _tokens = itertools.count(1)
 
 
@@ -53,62 +70,155 @@ def split_solution(z, n, m, N):
     return full[..., :n], full[..., n:2 * n], full[..., :N - 1, 2 * n:]
 
 
-def _check(args):
+# ------------------------------------------------------------------------------------------------ what every entry point shares
+def _require_float64(who, name, t, or_none=""):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a torch.Tensor%s" % (who, name, or_none))
+    if t.dtype != torch.float64:
+        raise TypeError("%s: %s must be float64, got %s" % (who, name, t.dtype))
+
+
+def _check(who, names, args, shapes):
+    """The argument checks of every entry point (`who` opens the messages): float64 tensors on one ROCm device, each of
+    its shape in `shapes(who, *args)` -- a dict per name, which checks A, B (and C), the arguments that decide the sizes --
+    or with a batch dimension in front. Returns (device, per argument whether it is shared, (n, m, N, b))."""
     dev = None
-    for name, t in zip(_ARGS, args):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("lqr_solve: %s must be a torch.Tensor" % name)
-        if t.dtype != torch.float64:
-            raise TypeError("lqr_solve: %s must be float64, got %s" % (name, t.dtype))
+    for name, t in zip(names, args):
+        _require_float64(who, name, t)
         if t.device.type != "cuda":
-            raise ValueError("lqr_solve: %s must live on a ROCm device, got %s" % (name, t.device))
+            raise ValueError("%s: %s must live on a ROCm device, got %s" % (who, name, t.device))
         if dev is None:
             dev = t.device
         elif t.device != dev:
-            raise ValueError("lqr_solve: every argument must be on one device (%s is on %s, A on %s)" % (name, t.device, dev))
-    A, B = args[0], args[1]
-    if A.dim() not in (3, 4) or A.shape[-1] != A.shape[-2]:
-        raise ValueError("lqr_solve: A must be [b, N, n, n] or [N, n, n], got %s" % (tuple(A.shape),))
-    N, n = A.shape[-3], A.shape[-1]
-    if B.dim() not in (3, 4) or B.shape[-3] != N or B.shape[-2] != n:
-        raise ValueError("lqr_solve: B must be [b, N, n, m] or [N, n, m], got %s" % (tuple(B.shape),))
-    m = B.shape[-1]
-    per = dict(A=(N, n, n), B=(N, n, m), Q=(N, n), R=(N, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,))
+            raise ValueError("%s: every argument must be on one device (%s is on %s, A on %s)" % (who, name, t.device, dev))
+    per = shapes(who, *args)
     batch = set()
     shared = []
-    for name, t in zip(_ARGS, args):
+    for name, t in zip(names, args):
         shape = per[name]
         if tuple(t.shape) == shape:
             shared.append(True)
         elif t.dim() == len(shape) + 1 and tuple(t.shape[1:]) == shape:
             shared.append(False)
             batch.add(t.shape[0])
-        elif name in ("Q", "R") and t.dim() >= 3 and t.shape[-1] == t.shape[-2] == shape[-1]:
-            raise ValueError("lqr_solve: %s must hold the diagonals, [b, N, %d] or [N, %d]; got the matrices %s"
-                             % (name, shape[-1], shape[-1], tuple(t.shape)))
+        elif name in ("Q", "R") and len(shape) == 2 and t.dim() >= 3 and t.shape[-1] == t.shape[-2] == shape[-1]:
+            raise ValueError("%s: %s must hold the diagonals, [b, N, %d] or [N, %d]; got the matrices %s"
+                             % (who, name, shape[-1], shape[-1], tuple(t.shape)))
         else:
-            raise ValueError("lqr_solve: %s must be [b, %s] or %s, got %s"
-                             % (name, ", ".join(str(x) for x in shape), list(shape), tuple(t.shape)))
+            raise ValueError("%s: %s must be [b, %s] or %s, got %s"
+                             % (who, name, ", ".join(str(x) for x in shape), list(shape), tuple(t.shape)))
     if len(batch) > 1:
-        raise ValueError("lqr_solve: batch dimensions disagree: %s" % sorted(batch))
-    b = batch.pop() if batch else 1
-    return dev, n, m, N, b, shared
+        raise ValueError("%s: batch dimensions disagree: %s" % (who, sorted(batch)))
+    N, n, m = per["B"]
+    return dev, tuple(shared), (n, m, N, batch.pop() if batch else 1)
 
 
-def _flat(args, n, m, N, b, shared):
-    """The flat layout of ndlqr_InitializeBatchFlat, contiguous on the device: A, B column-major (A^T stored row-major)."""
+def _diagonal_shapes(who, A, B, *rest):
+    if A.dim() not in (3, 4) or A.shape[-1] != A.shape[-2]:
+        raise ValueError("%s: A must be [b, N, n, n] or [N, n, n], got %s" % (who, tuple(A.shape)))
+    N, n = A.shape[-3], A.shape[-1]
+    if B.dim() not in (3, 4) or B.shape[-3] != N or B.shape[-2] != n:
+        raise ValueError("%s: B must be [b, N, n, m] or [N, n, m], got %s" % (who, tuple(B.shape)))
+    m = B.shape[-1]
+    return dict(A=(N, n, n), B=(N, n, m), Q=(N, n), R=(N, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,))
+
+
+def _dense_shapes(who, A, B, *rest):
+    if A.dim() not in (3, 4) or A.shape[-1] != A.shape[-2] or B.dim() not in (3, 4) or B.shape[-3:-1] != A.shape[-3:-1]:
+        raise ValueError("%s: A must be [b, N, n, n] and B [b, N, n, m] (b optional), got %s and %s"
+                         % (who, tuple(A.shape), tuple(B.shape)))
+    N, n, m = B.shape[-3:]
+    return dict(A=(N, n, n), B=(N, n, m), Q=(N, n, n), H=(N, n, m), R=(N, m, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,))
+
+
+def _row_shapes(who, *args):
+    per = _dense_shapes(who, *args)
+    C = args[9]
+    N, n, m = per["B"]
+    if C.dim() not in (3, 4) or C.shape[-3] != N or C.shape[-1] != n or C.shape[-2] < 1:
+        raise ValueError("%s: C must be [b, N, p, n] or [N, p, n] with p >= 1, got %s" % (who, tuple(C.shape)))
+    p = C.shape[-2]
+    return dict(per, C=(N, p, n), D=(N, p, m), lo=(N, p), hi=(N, p))
+
+
+def _flat(args, shared, b):
+    """The flat layout of ndlqr_InitializeBatchFlat and ndlqr_InitializeBatchFlatDense, contiguous on the device: matrices
+    column-major per knot (the transpose, stored row-major); an argument without its batch dimension (`shared`) expanded
+    to the batch."""
     out = []
-    for name, t, sh in zip(_ARGS, args, shared):
+    for t, sh in zip(args, shared):
         t = t.detach()
         if sh:
             t = t.unsqueeze(0)
-        if name in ("A", "B"):
+        if t.dim() == 4:
             t = t.transpose(-1, -2)
-        t = t.expand(b, *t.shape[1:]).contiguous().reshape(b, -1)
-        out.append(t)
+        out.append(t.expand(b, *t.shape[1:]).contiguous().reshape(b, -1))
     return out
 
 
+def _solver(cache, dev, dims, p=()):
+    """(key, solver) of `cache` for problems of dims = (n, m, N, b) -- and p rows -- on `dev`: made with
+    NDLQR_FLAG_KEEP_RECORDS on that device when the cache has none."""
+    n, m, N, b = dims
+    key = (n, m, N) + tuple(p) + (b, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in cache:
+        cache[key] = [BatchSolver(n, m, N, b, device=key[-1], flags=FLAG_KEEP_RECORDS), None]
+    return key, cache[key][0]
+
+
+def _solution(bs, dev):
+    """The resident solution z [b, nvars] in a new torch tensor."""
+    z = torch.empty((bs.batch, bs.nvars), dtype=torch.float64, device=dev)
+    bs.solutions_to_device(z.data_ptr())
+    bs.synchronize()
+    return z
+
+
+def _resume(cache, ctx, gz, resolve):
+    """What every backward starts with: (the node's solver, gz contiguous in float64, torch's stream synchronised). If the
+    solver has served another forward since, `resolve(solver)` redoes this node's first."""
+    bs, token = cache[ctx.key]
+    if token != ctx.token:
+        resolve(bs)
+    gz = gz.detach().to(torch.float64).contiguous()
+    torch.cuda.current_stream(gz.device).synchronize()
+    return bs, gz
+
+
+def _require_converged(status, infeasible, message):
+    """RuntimeError message % (how many, of how many, their statuses) unless every problem that is not certified
+    `infeasible` ended with status 1."""
+    bad = int(((status != 1) & ~infeasible).sum())
+    if bad:
+        raise RuntimeError(message % (bad, status.size, sorted(set(status[~infeasible].tolist()) - {1})))
+
+
+def _named_gradients(names, shared, needs, shape_of, compute, rows, device):
+    """The gradients of `names`, those that `needs` asks for, written by the library (`compute(sum mask, views)`) into new
+    torch tensors of `shape_of(name, summed)`; a `shared` argument's is the batch sum computed on the device. A list in
+    the order of `names`, None where none is needed. rows: name -> rows of the matrices, which come back row-major (the
+    math convention). Torch's stream needs no synchronisation here: _resume drained it before the adjoint solve, and
+    nothing but allocations has gone through torch since."""
+    mask = 0
+    out = {}
+    for i, (name, sh, need) in enumerate(zip(names, shared, needs)):
+        if not need:
+            continue
+        if sh:
+            mask |= 1 << i
+        out[name] = torch.empty(shape_of(name, sh), dtype=torch.float64, device=device)
+    if out:
+        compute(mask, {name: _View(g) for name, g in out.items()})
+    grads = []
+    for name in names:
+        g = out.get(name)
+        if g is not None and name in rows:  # flat column-major -> row-major math convention
+            g = g.reshape(*g.shape[:-1], g.shape[-1] // rows[name], rows[name]).transpose(-1, -2)
+        grads.append(g)
+    return grads
+
+
+# ------------------------------------------------------------------------------------------------ diagonal costs
 def _solve(bs, flat, token, key, refine=0):
     """Factor + solve of `flat` on the cached solver (and `refine` steps of iterative refinement at most); the solver then
     holds forward `token`."""
@@ -125,53 +235,25 @@ def _solve(bs, flat, token, key, refine=0):
 
 
 def _forward(ctx, refine, args):
-    dev, n, m, N, b, shared = _check(args)
-    key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
-    if key not in _cache:
-        _cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
-    bs = _cache[key][0]
-    flat = _flat(args, n, m, N, b, shared)
+    dev, shared, dims = _check("lqr_solve", _ARGS, args, _diagonal_shapes)
+    key, bs = _solver(_cache, dev, dims)
+    flat = _flat(args, shared, dims[3])
     token = next(_tokens)
     _solve(bs, flat, token, key, refine)
-    z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
-    bs.solutions_to_device(z.data_ptr())
-    bs.synchronize()
-    ctx.key, ctx.token, ctx.flat, ctx.shared, ctx.dims = key, token, flat, shared, (n, m, N, b)
-    ctx.refine = refine
-    return z
+    ctx.key, ctx.token, ctx.flat, ctx.shared, ctx.dims, ctx.refine = key, token, flat, shared, dims, refine
+    return _solution(bs, dev)
 
 
 def _backward(ctx, gz, needs_input_grad):
-    n, m, N, b = ctx.dims
-    bs = _cache[ctx.key][0]
-    if _cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's factorisation again
-        _solve(bs, ctx.flat, ctx.token, ctx.key, ctx.refine)
-    gz = gz.detach().to(torch.float64).contiguous()
-    torch.cuda.current_stream(gz.device).synchronize()
+    bs, gz = _resume(_cache, ctx, gz, lambda bs: _solve(bs, ctx.flat, ctx.token, ctx.key, ctx.refine))
     err = bs.solve_adjoint(_View(gz))
     if err:
         raise RuntimeError("lqr_solve backward: adjoint solve failed: %d" % err)
     if ctx.refine > 0:
         bs.refine_adjoint(ctx.refine)
-    mask = 0
-    out, views = {}, {}
-    for i, (name, sh, need) in enumerate(zip(GRAD_NAMES, ctx.shared, needs_input_grad)):
-        if not need:
-            continue
-        if sh:
-            mask |= 1 << i
-        out[name] = torch.empty(bs.gradient_shape(name, sh), dtype=torch.float64, device=gz.device)
-        views[name] = _View(out[name])
-    if views:
-        bs.gradients(mask, views)
-    grads = []
-    for name, sh in zip(GRAD_NAMES, ctx.shared):
-        g = out.get(name)
-        if g is not None and name in ("A", "B"):  # flat column-major -> row-major math convention
-            cols = n if name == "A" else m
-            g = g.reshape(*g.shape[:-1], cols, n).transpose(-1, -2)
-        grads.append(g)
-    return tuple(grads)
+    n = ctx.dims[0]
+    return tuple(_named_gradients(GRAD_NAMES, ctx.shared, needs_input_grad, bs.gradient_shape, bs.gradients, dict(A=n, B=n),
+                                  gz.device))
 
 
 class LqrSolve(torch.autograd.Function):
@@ -210,11 +292,6 @@ def lqr_solve(A, B, Q, R, q, r, d, x0, refine=0):
 
 
 # ------------------------------------------------------------------------------------------------ box-constrained
-# A cache of its own, so that lqr_solve and lqr_solve_box do not evict each other's solvers.
-_BOUNDS = ("xlo", "xhi", "ulo", "uhi")
-_box_cache = {}              # (n, m, N, b, device index) -> [BatchSolver, token of the forward it holds]
-
-
 def _check_bounds(bounds, dev, n, m, N, b):
     """Each bound None, [N, n|m] (shared by every problem) or [b, N, n|m]; returns the per-bound shared flags."""
     shared = []
@@ -222,10 +299,7 @@ def _check_bounds(bounds, dev, n, m, N, b):
         if t is None:
             shared.append(None)
             continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("lqr_solve_box: %s must be a torch.Tensor or None" % name)
-        if t.dtype != torch.float64:
-            raise TypeError("lqr_solve_box: %s must be float64, got %s" % (name, t.dtype))
+        _require_float64("lqr_solve_box", name, t, " or None")
         if t.device != dev:
             raise ValueError("lqr_solve_box: %s must be on the problem's device %s, got %s" % (name, dev, t.device))
         k = n if name[0] == "x" else m
@@ -262,6 +336,7 @@ def _solve_box(bs, flat, bflat, all_shared, settings, token, key):
     torch.cuda.current_stream(flat[0].device).synchronize()  # (the library reads torch memory on its own stream)
     _box_cache[key][1] = None
     bs.initialize_flat_device(*[t.data_ptr() for t in flat])
+    # (through the library itself: BatchSolver.set_bounds has no way to say that bounds in device memory are shared)
     ptrs = [None if t is None else _any_ptr(_View(t), t.numel()) for t in bflat]
     err = bs.L.ndlqr_BatchSetBounds(bs.h, BOUNDS_SHARED if all_shared else 0, *ptrs)
     if err:
@@ -275,21 +350,15 @@ def _solve_box(bs, flat, bflat, all_shared, settings, token, key):
     except RuntimeError as e:
         raise RuntimeError("lqr_solve_box: the constrained solve failed (%s)" % e) from None
     infeasible = status == 4  # (only with infeas_every > 0: certified, z is the last iterate, the gradients are zero)
-    bad = int(((status != 1) & ~infeasible).sum())
-    if bad:
-        raise RuntimeError("lqr_solve_box: %d of %d problems did not converge (status %s): raise max_iter, change rho or "
-                           "set adapt_every (the per-problem adaptive penalty)"
-                           % (bad, status.size, sorted(set(status.tolist()) - {1, 4})))
+    _require_converged(status, infeasible, "lqr_solve_box: %d of %d problems did not converge (status %s): raise max_iter, "
+                       "change rho or set adapt_every (the per-problem adaptive penalty)")
     if polish:
         try:
             _, status = bs.polish_box()
         except RuntimeError as e:
             raise RuntimeError("lqr_solve_box: the polish failed (%s)" % e) from None
-        bad = int(((status != 1) & ~infeasible).sum())
-        if bad:
-            raise RuntimeError("lqr_solve_box: %d of %d problems were not polished (status %s): the active set ADMM left "
-                               "was not corrected within the rounds; tighten eps_abs / eps_rel"
-                               % (bad, status.size, sorted(set(status[~infeasible].tolist()) - {1})))
+        _require_converged(status, infeasible, "lqr_solve_box: %d of %d problems were not polished (status %s): the active "
+                           "set ADMM left was not corrected within the rounds; tighten eps_abs / eps_rel")
     _box_cache[key][1] = token
     return infeasible
 
@@ -298,59 +367,33 @@ class LqrSolveBox(torch.autograd.Function):
     @staticmethod
     def forward(ctx, settings, *args):
         problem, bounds = args[:8], args[8:]
-        dev, n, m, N, b, shared = _check(problem)
+        dev, shared, dims = _check("lqr_solve", _ARGS, problem, _diagonal_shapes)
+        n, m, N, b = dims
         bshared = _check_bounds(bounds, dev, n, m, N, b)
-        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
-        if key not in _box_cache:
-            _box_cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
-        bs = _box_cache[key][0]
-        flat = _flat(problem, n, m, N, b, shared)
+        key, bs = _solver(_box_cache, dev, dims)
+        flat = _flat(problem, shared, b)
         all_shared, bflat = _flat_bounds(bounds, bshared, b)
         token = next(_tokens)
         ctx.infeasible = _solve_box(bs, flat, bflat, all_shared, settings, token, key)
-        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
-        bs.solutions_to_device(z.data_ptr())
-        bs.synchronize()
-        ctx.key, ctx.token, ctx.flat, ctx.shared, ctx.dims = key, token, flat, shared, (n, m, N, b)
+        ctx.key, ctx.token, ctx.flat, ctx.shared, ctx.dims = key, token, flat, shared, dims
         ctx.bflat, ctx.bshared, ctx.all_shared, ctx.settings = bflat, bshared, all_shared, settings
-        return z
+        return _solution(bs, dev)
 
     @staticmethod
     def backward(ctx, gz):
         n, m, N, b = ctx.dims
-        bs = _box_cache[ctx.key][0]
-        if _box_cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's forward again
-            _solve_box(bs, ctx.flat, ctx.bflat, ctx.all_shared, ctx.settings, ctx.token, ctx.key)
-        gz = gz.detach().to(torch.float64).contiguous()
-        torch.cuda.current_stream(gz.device).synchronize()
+        bs, gz = _resume(_box_cache, ctx, gz, lambda bs: _solve_box(bs, ctx.flat, ctx.bflat, ctx.all_shared, ctx.settings,
+                                                                     ctx.token, ctx.key))
         _, alpha, eps_abs, eps_rel, max_iter, _, polish, _, _ = ctx.settings
         if polish:
             _, status = bs.solve_polished_adjoint(_View(gz))
         else:
             _, status = bs.solve_box_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter)
-        bad = int(((status != 1) & ~ctx.infeasible).sum())  # (a certified problem is not iterated: w = 0, nu = 0)
-        if bad:
-            raise RuntimeError("lqr_solve_box backward: the adjoint of %d of %d problems did not converge (status %s)"
-                               % (bad, status.size, sorted(set(status[~ctx.infeasible].tolist()) - {1})))
+        # (a certified problem is not iterated: w = 0, nu = 0)
+        _require_converged(status, ctx.infeasible, "lqr_solve_box backward: the adjoint of %d of %d problems did not converge "
+                           "(status %s)")
         need, need_b = ctx.needs_input_grad[1:9], ctx.needs_input_grad[9:]
-        mask = 0
-        out, views = {}, {}
-        for i, (name, sh, nd) in enumerate(zip(GRAD_NAMES, ctx.shared, need)):
-            if not nd:
-                continue
-            if sh:
-                mask |= 1 << i
-            out[name] = torch.empty(bs.gradient_shape(name, sh), dtype=torch.float64, device=gz.device)
-            views[name] = _View(out[name])
-        if views:
-            bs.gradients(mask, views)
-        grads = []
-        for name in GRAD_NAMES:
-            g = out.get(name)
-            if g is not None and name in ("A", "B"):  # flat column-major -> row-major math convention
-                cols = n if name == "A" else m
-                g = g.reshape(*g.shape[:-1], cols, n).transpose(-1, -2)
-            grads.append(g)
+        grads = _named_gradients(GRAD_NAMES, ctx.shared, need, bs.gradient_shape, bs.gradients, dict(A=n, B=n), gz.device)
         bout = {}
         for name, t, nd in zip(_BOUNDS, ctx.bflat, need_b):
             if nd and t is not None:
@@ -390,16 +433,7 @@ def lqr_solve_box(A, B, Q, R, q, r, d, x0, xlo=None, xhi=None, ulo=None, uhi=Non
                              A, B, Q, R, q, r, d, x0, xlo, xhi, ulo, uhi)
 
 
-__all__ = ["LqrSolve", "LqrSolveRefined", "LqrSolveBox", "lqr_solve", "lqr_solve_box", "split_solution"]
-# (lqr_solve_dense and lqr_solve_constrained, below, are imported by name)
-
-
 # ------------------------------------------------------------------------------------------------ dense cost matrices
-# A cache of its own again: a solver in dense-cost mode serves no diagonal forward in between.
-_DENSE_ARGS = ("A", "B", "Q", "H", "R", "q", "r", "d", "x0")
-_dense_cache = {}            # (n, m, N, b, device index) -> [BatchSolver, token of the forward it holds]
-
-
 def _dense_solve(bs, flat, token, key):
     torch.cuda.current_stream(flat[0].device).synchronize()  # (the library reads torch memory on its own stream)
     bs.initialize_flat_dense(*[_View(t) for t in flat])
@@ -416,8 +450,8 @@ def _dense_gradients(z, w, n, m, N):
     [b, nvars], both in the caller's variables: the outer products per knot with the signs and per-knot conventions of
     kernels_grad.hpp (zero for A, B, H, R, r, d of the last knot; Q and R as symmetric matrices). They hold for the plain
     dense-cost solve and, with w of the active-set system, for the constrained one (G_A w = 0 drops the constraint term).
-    The independent restatement of ndlqr_BatchGradientsDense in torch: the tests and tools/grad_dense_bench.py compare
-    against it; no backward calls it."""
+    The independent restatement of ndlqr_BatchGradientsDense in torch: tools/grad_dense_bench.py times the kernel against
+    it; no backward and no test calls it."""
     zl, zx, zu = split_solution(z, n, m, N)
     wl, wx, wu = split_solution(w, n, m, N)
     outer = lambda a, c: a.unsqueeze(-1) * c.unsqueeze(-2)
@@ -435,45 +469,11 @@ def _dense_gradients(z, w, n, m, N):
     return (gA, gB, gQ, gH, gR, gq, gr, gd, gx0)
 
 
-def _flat_dense(args, shared, b):
-    """The flat layout of ndlqr_InitializeBatchFlatDense, contiguous on the device: matrices column-major per knot (the
-    transpose, stored row-major); an argument without its batch dimension (`shared`) expanded to the batch."""
-    out = []
-    for t, sh in zip(args, shared):
-        t = t.detach()
-        if sh:
-            t = t.unsqueeze(0)
-        if t.dim() == 4:
-            t = t.transpose(-1, -2)
-        out.append(t.expand(b, *t.shape[1:]).contiguous().reshape(b, -1))
-    return out
-
-
-def _dense_backward_gradients(bs, shared, needs, dims, device):
-    """dL/d(A, B, Q, H, R, q, r, d, x0) from the resident solution and adjoint (ndlqr_BatchGradientsDense), only those
-    `needs` asks for, written by the kernel into torch tensors; a `shared` argument's is the batch sum computed on the
-    device. Math convention: the matrices row-major."""
-    n, m, N, b = dims
-    mask = 0
-    out, views = {}, {}
-    for i, (name, sh, need) in enumerate(zip(GRAD_DENSE_NAMES, shared, needs)):
-        if not need:
-            continue
-        if sh:
-            mask |= 1 << i
-        out[name] = torch.empty(bs.dense_gradient_shape(name, sh), dtype=torch.float64, device=device)
-        views[name] = _View(out[name])
-    if views:
-        torch.cuda.current_stream(device).synchronize()
-        bs.gradients_dense(mask, views)
-    rows = dict(A=n, B=n, Q=n, H=n, R=m)
-    grads = []
-    for name in GRAD_DENSE_NAMES:
-        g = out.get(name)
-        if g is not None and name in rows:  # flat column-major -> row-major math convention
-            g = g.reshape(*g.shape[:-1], g.shape[-1] // rows[name], rows[name]).transpose(-1, -2)
-        grads.append(g)
-    return grads
+def _dense_named_gradients(bs, shared, needs, dims, device):
+    """dL/d(A, B, Q, H, R, q, r, d, x0) from the resident solution and adjoint (ndlqr_BatchGradientsDense)."""
+    n, m = dims[:2]
+    return _named_gradients(GRAD_DENSE_NAMES, shared, needs, bs.dense_gradient_shape, bs.gradients_dense,
+                            dict(A=n, B=n, Q=n, H=n, R=m), device)
 
 
 class LqrSolveDense(torch.autograd.Function):
@@ -485,69 +485,20 @@ class LqrSolveDense(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, shared, dims, A, B, Q, H, R, q, r, d, x0):
-        n, m, N, b = dims
-        dev = A.device
-        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
-        if key not in _dense_cache:
-            _dense_cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
-        bs = _dense_cache[key][0]
-        flat = _flat_dense((A, B, Q, H, R, q, r, d, x0), shared, b)
+        key, bs = _solver(_dense_cache, A.device, dims)
+        flat = _flat((A, B, Q, H, R, q, r, d, x0), shared, dims[3])
         token = next(_tokens)
         _dense_solve(bs, flat, token, key)
-        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
-        bs.solutions_to_device(z.data_ptr())
-        bs.synchronize()
-        ctx.key, ctx.token, ctx.flat, ctx.dims, ctx.shared = key, token, flat, (n, m, N, b), shared
-        return z
+        ctx.key, ctx.token, ctx.flat, ctx.dims, ctx.shared = key, token, flat, tuple(dims), shared
+        return _solution(bs, A.device)
 
     @staticmethod
     def backward(ctx, gz):
-        bs = _dense_cache[ctx.key][0]
-        if _dense_cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's again
-            _dense_solve(bs, ctx.flat, ctx.token, ctx.key)
-        gz = gz.detach().to(torch.float64).contiguous()
-        torch.cuda.current_stream(gz.device).synchronize()
+        bs, gz = _resume(_dense_cache, ctx, gz, lambda bs: _dense_solve(bs, ctx.flat, ctx.token, ctx.key))
         err = bs.solve_adjoint(_View(gz))
         if err:
             raise RuntimeError("lqr_solve_dense backward: adjoint solve failed: %d" % err)
-        return (None, None) + tuple(_dense_backward_gradients(bs, ctx.shared, ctx.needs_input_grad[2:], ctx.dims, gz.device))
-
-
-def _check_dense(who, args):
-    """The argument checks of lqr_solve_dense (and lqr_value_dense: `who` opens the messages): (shared flags, (n, m, N, b))."""
-    dev = None
-    for name, t in zip(_DENSE_ARGS, args):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(who + ": %s must be a torch.Tensor" % name)
-        if t.dtype != torch.float64:
-            raise TypeError(who + ": %s must be float64, got %s" % (name, t.dtype))
-        if t.device.type != "cuda":
-            raise ValueError(who + ": %s must live on a ROCm device, got %s" % (name, t.device))
-        if dev is None:
-            dev = t.device
-        elif t.device != dev:
-            raise ValueError(who + ": every argument must be on one device (%s is on %s, A on %s)" % (name, t.device, dev))
-    A, B = args[0], args[1]
-    if A.dim() not in (3, 4) or A.shape[-1] != A.shape[-2] or B.dim() not in (3, 4) or B.shape[-3:-1] != A.shape[-3:-1]:
-        raise ValueError(who + ": A must be [b, N, n, n] and B [b, N, n, m] (b optional), got %s and %s"
-                         % (tuple(A.shape), tuple(B.shape)))
-    N, n, m = B.shape[-3:]
-    per = dict(A=(N, n, n), B=(N, n, m), Q=(N, n, n), H=(N, n, m), R=(N, m, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,))
-    batch = set()
-    shared = []
-    for name, t in zip(_DENSE_ARGS, args):
-        shared.append(tuple(t.shape) == per[name])
-        if shared[-1]:
-            continue
-        if t.dim() == len(per[name]) + 1 and tuple(t.shape[1:]) == per[name]:
-            batch.add(t.shape[0])
-        else:
-            raise ValueError(who + ": %s must be [b, %s] or %s, got %s"
-                             % (name, ", ".join(str(x) for x in per[name]), list(per[name]), tuple(t.shape)))
-    if len(batch) > 1:
-        raise ValueError(who + ": batch dimensions disagree: %s" % sorted(batch))
-    b = batch.pop() if batch else 1
-    return tuple(shared), (n, m, N, b)
+        return (None, None) + tuple(_dense_named_gradients(bs, ctx.shared, ctx.needs_input_grad[2:], ctx.dims, gz.device))
 
 
 def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
@@ -558,17 +509,12 @@ def lqr_solve_dense(A, B, Q, H, R, q, r, d, x0):
     lower triangles, and dL/dQ, dL/dR come back symmetric: the gradient in the space of symmetric matrices. Needs R_k > 0
     and Q_k - H_k R_k^-1 H_k' > 0. H, R of the last knot are not part of the problem (zero gradient), like its A, B, r, d."""
     args = (A, B, Q, H, R, q, r, d, x0)
-    shared, dims = _check_dense("lqr_solve_dense", args)
+    _, shared, dims = _check("lqr_solve_dense", _DENSE_ARGS, args, _dense_shapes)
     # (a shared argument goes in as it is: the library sums its gradient over the batch)
     return LqrSolveDense.apply(shared, dims, *args)
 
 
 # ------------------------------------------------------------------------------------------------ linear inequality constraints
-# A cache of its own once more: a solver in constrained mode retains its problem on the device.
-_ROW_ARGS = ("C", "D", "lo", "hi")
-_lin_cache = {}              # (n, m, N, p, b, device index) -> [BatchSolver, token of the forward it holds]
-
-
 def _lin_solve(bs, flat, settings, token, key):
     """Initialise + constrained solve (cold) of `flat` on the cached solver; it then holds `token`. Returns the mask of
     the problems certified infeasible (status 4: only with infeas_every > 0)."""
@@ -584,10 +530,8 @@ def _lin_solve(bs, flat, settings, token, key):
     except RuntimeError as e:
         raise RuntimeError("lqr_solve_constrained: the constrained solve failed (%s)" % e) from None
     infeasible = status == 4  # (certified: z is the last iterate, the gradients are zero)
-    bad = int(((status != 1) & ~infeasible).sum())
-    if bad:
-        raise RuntimeError("lqr_solve_constrained: %d of %d problems did not converge (status %s): raise max_iter or change rho"
-                           % (bad, status.size, sorted(set(status[~infeasible].tolist()) - {1})))
+    _require_converged(status, infeasible, "lqr_solve_constrained: %d of %d problems did not converge (status %s): raise "
+                       "max_iter or change rho")
     _lin_cache[key][1] = token
     return infeasible
 
@@ -603,43 +547,29 @@ class LqrSolveConstrained(torch.autograd.Function):
     def forward(ctx, settings, row_shared, shared, dims, A, B, Q, H, R, q, r, d, x0, C_, D_, lo, hi):
         n, m, N, b = dims
         p = C_.shape[-2]
-        dev = A.device
-        key = (n, m, N, p, b, dev.index if dev.index is not None else torch.cuda.current_device())
-        if key not in _lin_cache:
-            _lin_cache[key] = [BatchSolver(n, m, N, b, device=key[5], flags=FLAG_KEEP_RECORDS), None]
-        bs = _lin_cache[key][0]
-        expand = lambda t, sh: t.unsqueeze(0).expand(b, *t.shape) if sh else t
-        rows = [expand(t.detach(), sh) for t, sh in zip((C_, D_, lo, hi), row_shared)]
-        flat = _flat_dense((A, B, Q, H, R, q, r, d, x0), shared, b) + _flat_dense(rows, (False,) * 4, b)
+        key, bs = _solver(_lin_cache, A.device, dims, (p,))
+        flat = _flat((A, B, Q, H, R, q, r, d, x0, C_, D_, lo, hi), tuple(shared) + tuple(row_shared), b)
         token = next(_tokens)
         ctx.infeasible = _lin_solve(bs, flat, settings, token, key)
-        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
-        bs.solutions_to_device(z.data_ptr())
-        bs.synchronize()
         ctx.key, ctx.token, ctx.flat, ctx.dims, ctx.settings, ctx.row_shared = key, token, flat, (n, m, N, p, b), settings, row_shared
         ctx.shared = shared
-        return z
+        return _solution(bs, A.device)
 
     @staticmethod
     def backward(ctx, gz):
         n, m, N, p, b = ctx.dims
-        bs = _lin_cache[ctx.key][0]
-        if _lin_cache[ctx.key][1] != ctx.token:  # the solver has served another forward since: this node's forward again
-            _lin_solve(bs, ctx.flat, ctx.settings, ctx.token, ctx.key)
-        gz = gz.detach().to(torch.float64).contiguous()
-        torch.cuda.current_stream(gz.device).synchronize()
+        bs, gz = _resume(_lin_cache, ctx, gz, lambda bs: _lin_solve(bs, ctx.flat, ctx.settings, ctx.token, ctx.key))
         _, alpha, eps_abs, eps_rel, max_iter, check_every = ctx.settings[:6]
         try:
             _, status = bs.solve_constrained_adjoint(_View(gz), alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_iter=max_iter,
                                                      check_every=check_every)
         except RuntimeError as e:
             raise RuntimeError("lqr_solve_constrained backward: the adjoint failed (%s)" % e) from None
-        bad = int(((status != 1) & ~ctx.infeasible).sum())  # (a certified problem is not iterated: w = 0, nu = 0)
-        if bad:
-            raise RuntimeError("lqr_solve_constrained backward: the adjoint of %d of %d problems did not converge (status %s)"
-                               % (bad, status.size, sorted(set(status[~ctx.infeasible].tolist()) - {1})))
+        # (a certified problem is not iterated: w = 0, nu = 0)
+        _require_converged(status, ctx.infeasible, "lqr_solve_constrained backward: the adjoint of %d of %d problems did not "
+                           "converge (status %s)")
         need = ctx.needs_input_grad[4:]
-        grads = _dense_backward_gradients(bs, ctx.shared, need[:9], (n, m, N, b), gz.device)
+        grads = _dense_named_gradients(bs, ctx.shared, need[:9], (n, m, N, b), gz.device)
         need_rows = need[9:]
         wanted = [k for k, nd in zip(_ROW_ARGS, need_rows) if nd]
         summed = bool(wanted) and all(sh for k, sh in zip(_ROW_ARGS, ctx.row_shared) if k in wanted)
@@ -674,48 +604,11 @@ def lqr_solve_constrained(A, B, Q, H, R, q, r, d, x0, C, D, lo, hi, *, rho=0.0, 
     != 1). The gradients hold where the active set is locally stable (strict complementarity, independent active rows);
     dL/dC and dL/dD are exactly zero on the rows that are not active."""
     args = (A, B, Q, H, R, q, r, d, x0, C, D, lo, hi)
-    names = _DENSE_ARGS + _ROW_ARGS
-    dev = None
-    for name, t in zip(names, args):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("lqr_solve_constrained: %s must be a torch.Tensor" % name)
-        if t.dtype != torch.float64:
-            raise TypeError("lqr_solve_constrained: %s must be float64, got %s" % (name, t.dtype))
-        if t.device.type != "cuda":
-            raise ValueError("lqr_solve_constrained: %s must live on a ROCm device, got %s" % (name, t.device))
-        if dev is None:
-            dev = t.device
-        elif t.device != dev:
-            raise ValueError("lqr_solve_constrained: every argument must be on one device (%s is on %s, A on %s)"
-                             % (name, t.device, dev))
-    if A.dim() not in (3, 4) or A.shape[-1] != A.shape[-2] or B.dim() not in (3, 4) or B.shape[-3:-1] != A.shape[-3:-1]:
-        raise ValueError("lqr_solve_constrained: A must be [b, N, n, n] and B [b, N, n, m] (b optional), got %s and %s"
-                         % (tuple(A.shape), tuple(B.shape)))
-    N, n, m = B.shape[-3:]
-    if C.dim() not in (3, 4) or C.shape[-3] != N or C.shape[-1] != n or C.shape[-2] < 1:
-        raise ValueError("lqr_solve_constrained: C must be [b, N, p, n] or [N, p, n] with p >= 1, got %s" % (tuple(C.shape),))
-    p = C.shape[-2]
-    per = dict(A=(N, n, n), B=(N, n, m), Q=(N, n, n), H=(N, n, m), R=(N, m, m), q=(N, n), r=(N, m), d=(N, n), x0=(n,),
-               C=(N, p, n), D=(N, p, m), lo=(N, p), hi=(N, p))
-    batch = set()
-    shared = {}
-    for name, t in zip(names, args):
-        if tuple(t.shape) == per[name]:
-            shared[name] = True
-        elif t.dim() == len(per[name]) + 1 and tuple(t.shape[1:]) == per[name]:
-            shared[name] = False
-            batch.add(t.shape[0])
-        else:
-            raise ValueError("lqr_solve_constrained: %s must be [b, %s] or %s, got %s"
-                             % (name, ", ".join(str(x) for x in per[name]), list(per[name]), tuple(t.shape)))
-    if len(batch) > 1:
-        raise ValueError("lqr_solve_constrained: batch dimensions disagree: %s" % sorted(batch))
-    b = batch.pop() if batch else 1
+    _, shared, dims = _check("lqr_solve_constrained", _DENSE_ARGS + _ROW_ARGS, args, _row_shapes)
     # (every argument goes in as it is: the library sums the gradient of a shared one over the batch)
     settings = (float(rho), float(alpha), float(eps_abs), float(eps_rel), int(max_iter), int(check_every), int(adapt_every),
                 int(infeas_every), float(infeas_eps))
-    return LqrSolveConstrained.apply(settings, tuple(shared[k] for k in _ROW_ARGS), tuple(shared[k] for k in _DENSE_ARGS),
-                                     (n, m, N, b), *args)
+    return LqrSolveConstrained.apply(settings, shared[9:], shared[:9], dims, *args)
 
 
 # ------------------------------------------------------------------------------------------------ the optimal value
@@ -742,6 +635,16 @@ def value_gradients(z, n, m, N, dense):
     return (gA, gB, 0.5 * x * x, pad(0.5 * u * u), gq, gr, gd, gx0)
 
 
+def _value_forward(ctx, bs, dev, shared, dims):
+    """J* [b] of the solution the solver holds (ndlqr_BatchObjective); the solution is saved for the backward."""
+    z = _solution(bs, dev)
+    J = torch.empty((bs.batch,), dtype=torch.float64, device=dev)
+    bs.objective(out={"J": _View(J)})
+    ctx.save_for_backward(z)
+    ctx.shared, ctx.dims = shared, dims
+    return J
+
+
 def _value_backward(ctx, gJ, dense, needs):
     n, m, N, b = ctx.dims
     (z,) = ctx.saved_tensors
@@ -761,20 +664,10 @@ class LqrValue(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, *args):
-        dev, n, m, N, b, shared = _check(args)
-        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
-        if key not in _cache:
-            _cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
-        bs = _cache[key][0]
-        _solve(bs, _flat(args, n, m, N, b, shared), next(_tokens), key)
-        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
-        J = torch.empty((b,), dtype=torch.float64, device=dev)
-        bs.solutions_to_device(z.data_ptr())
-        bs.synchronize()
-        bs.objective(out={"J": _View(J)})
-        ctx.save_for_backward(z)
-        ctx.shared, ctx.dims = shared, (n, m, N, b)
-        return J
+        dev, shared, dims = _check("lqr_solve", _ARGS, args, _diagonal_shapes)
+        key, bs = _solver(_cache, dev, dims)
+        _solve(bs, _flat(args, shared, dims[3]), next(_tokens), key)
+        return _value_forward(ctx, bs, dev, shared, dims)
 
     @staticmethod
     def backward(ctx, gJ):
@@ -786,21 +679,10 @@ class LqrValueDense(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, shared, dims, *args):
-        n, m, N, b = dims
         dev = args[0].device
-        key = (n, m, N, b, dev.index if dev.index is not None else torch.cuda.current_device())
-        if key not in _dense_cache:
-            _dense_cache[key] = [BatchSolver(n, m, N, b, device=key[4], flags=FLAG_KEEP_RECORDS), None]
-        bs = _dense_cache[key][0]
-        _dense_solve(bs, _flat_dense(args, shared, b), next(_tokens), key)
-        z = torch.empty((b, bs.nvars), dtype=torch.float64, device=dev)
-        J = torch.empty((b,), dtype=torch.float64, device=dev)
-        bs.solutions_to_device(z.data_ptr())
-        bs.synchronize()
-        bs.objective(out={"J": _View(J)})
-        ctx.save_for_backward(z)
-        ctx.shared, ctx.dims = shared, dims
-        return J
+        key, bs = _solver(_dense_cache, dev, dims)
+        _dense_solve(bs, _flat(args, shared, dims[3]), next(_tokens), key)
+        return _value_forward(ctx, bs, dev, shared, dims)
 
     @staticmethod
     def backward(ctx, gJ):
@@ -820,5 +702,5 @@ def lqr_value_dense(A, B, Q, H, R, q, r, d, x0):
     """J* [b] of the dense-cost problems of lqr_solve_dense (same shapes and sharing rules), differentiable in every
     argument as lqr_value is; dJ*/dQ and dJ*/dR come back symmetric, the convention of lqr_solve_dense."""
     args = (A, B, Q, H, R, q, r, d, x0)
-    shared, dims = _check_dense("lqr_value_dense", args)
+    _, shared, dims = _check("lqr_value_dense", _DENSE_ARGS, args, _dense_shapes)
     return LqrValueDense.apply(shared, dims, *args)
