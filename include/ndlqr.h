@@ -598,7 +598,8 @@ int ndlqr_CopyBatchSolutions(NdLqrBatchSolver* bs, double* soln);          /* ba
 int ndlqr_CopyBatchSolutionsDevice(NdLqrBatchSolver* bs, double* dsoln);
 int ndlqr_CopyBatchFactors(NdLqrBatchSolver* bs, int p, double* fact);     /* reference layout */
 int ndlqr_BatchCholeskyFailures(NdLqrBatchSolver* bs);
-/* Which members failed: counts[b], b = 0 .. batch - 1, is the number of times the device flagged problem b. The words
+/* Which members failed: counts[b], b = 0 .. batch - 1, is the number of times the device flagged problem b (a block of
+ * the top chain, one launch that stands for several tree levels, adds one count per level it stands for). The words
  * are cumulative since the solver was created (ndlqr_hip.h: ndlqr_hip_download_failure_counts), so the failures of one
  * solve are the difference between the counts after and before it; their sum over the batch grows by what
  * ndlqr_BatchCholeskyFailures reports for that solve. Waits for everything in flight. */

@@ -441,7 +441,8 @@ int ndlqr_hip_cholesky_failures(NdlqrHipCtx* ctx);
  * positive where the weights are staged, a Cholesky pivot that is not positive and finite). The words are the device's
  * own: CUMULATIVE since the context was created, or since the recovery of a solve that did not launch or complete zeroed
  * them -- take the difference between two calls for the count of the solves between them. One problem may be flagged
- * several times by one solve (at the separator that meets the bad data and at its ancestors). Waits for everything in
+ * several times by one solve (at the separator that meets the bad data and at its ancestors; a block of the top chain,
+ * which stands for several tree levels in one launch, adds one count per level it stands for). Waits for everything in
  * flight; does not change what ndlqr_hip_cholesky_failures reports. */
 int ndlqr_hip_download_failure_counts(NdlqrHipCtx* ctx, int* counts);
 /* Name of the launch sequence the last solve used (for reports): "reduced", "reduced-fused2" (the (12,4) instance; NDLQR_FUSE2=1/0), "reduced-tree",
@@ -460,6 +461,10 @@ int ndlqr_hip_level1_paired(const NdlqrHipCtx* ctx);
  * slots are stored once, without atomic adds; NDLQR_BOTTOM_LDS16=1/0, unset: by instance), else 0 -- "not applied". The
  * records and the solutions are the same either way. */
 int ndlqr_hip_bottom_lds16(const NdlqrHipCtx* ctx);
+/* 1 when the last solve eliminated the separators of its top tree levels (level >= max(3, K - 5)) as one block-tridiagonal
+ * chain per problem in a single launch ("reduced" / "reduced-fused2" without kept records; NDLQR_TOP_CHAIN=1/0, unset: by
+ * instance), else 0: the schedule name does not tell. The solutions agree to rounding, not bit for bit. */
+int ndlqr_hip_top_chain(const NdlqrHipCtx* ctx);
 
 /* Per-kernel profile (NDLQR_FLAG_PROFILE): HIP-event durations accumulated since the last
  * reset, one slot per kernel kind. Returns number of slots / fills name, total ms, launches. */

@@ -373,6 +373,8 @@ def lib():
         proto("ndlqr_hip_level1_paired", C.c_int, vp)
     if hasattr(L, "ndlqr_hip_bottom_lds16"):
         proto("ndlqr_hip_bottom_lds16", C.c_int, vp)
+    if hasattr(L, "ndlqr_hip_top_chain"):
+        proto("ndlqr_hip_top_chain", C.c_int, vp)
     proto("ndlqr_hip_set_pipeline_depth", ci, vp, ci)
     proto("ndlqr_hip_pipeline_depth", ci, vp)
     proto("ndlqr_hip_pack_solutions_device", ci, vp, vp)
@@ -534,6 +536,12 @@ def generate_synthetic(n, m, N, seed):
                x0=np.zeros(n))
     _call(lib(), "ndlqr_GenerateSyntheticFlat", n, m, N, seed, *[_ptr(a) for a in out.values()], detail=False)
     return out
+
+
+def top_chain(solver):
+    """True when the last solve of the BatchSolver `solver` eliminated the separators of its top tree levels as one
+    block-tridiagonal chain per problem (ndlqr_hip_top_chain; NDLQR_TOP_CHAIN). The schedule name is the same either way."""
+    return hasattr(solver.L, "ndlqr_hip_top_chain") and bool(solver.L.ndlqr_hip_top_chain(solver.ctx))
 
 
 class BatchSolver:

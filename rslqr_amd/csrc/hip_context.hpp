@@ -66,6 +66,7 @@ struct KeptState {
   bool rec1_compact = false;      // ... and it left compact level-1 records (SmallPlan::compact1; ndlqr_hip_compact_level1)
   bool level1_paired = false;     // ... through the paired level-1 pass (SmallPlan::pair1; ndlqr_hip_level1_paired): the records are the same
   bool bottom_lds16 = false;      // ... in the 16 KB LDS layout of that launch (SmallPlan::lds16; ndlqr_hip_bottom_lds16)
+  bool top_chain = false;         // ... with the separators of the top levels as one block-tridiagonal chain (SmallPlan::chain; ndlqr_hip_top_chain)
   // the records / factors no longer belong to the resident inputs: the re-solves refuse until the next solve
   void forget_factorisation() { rec_complete = fact_valid = false; }
 };
@@ -199,8 +200,10 @@ struct DevKnobs {
   int compact1 = -1;  // compact records (L alone, packed) for the level-1 separators too, substituted with by rb_backsub_cols: NDLQR_COMPACT1=1 wherever the kernels exist, 0 never, unset (-1): where it measured faster (launch_small.hpp)
   int pair1 = -1;  // one Cholesky pass for the two level-1 separators of a workgroup of the fused bottom launch (bottom8_reduced_mc<.., P1>): NDLQR_PAIR1=1 wherever fuse2 and compact1 hold, 0 never, unset (-1): where it measured faster -- the (12,4) instance (launch_small.hpp)
   int bottom_lds16 = -1;  // the paired fused bottom launch in at most 16 KB of LDS per workgroup, ten workgroups per CU (bottom8_reduced_mc<.., P1, L16>): NDLQR_BOTTOM_LDS16=1 wherever pair1 holds, 0 never, unset (-1): where it measured faster (launch_small.hpp)
+  int top_chain = -1;  // the top levels of the separator-only schedule as one block-tridiagonal chain per problem (reduced_chain_top) instead of reduced_level_mc / reduced_top_mc: NDLQR_TOP_CHAIN=1 wherever the kernel exists and the schedule keeps no records, 0 never, unset (-1): where it measured faster -- horizons of 256 knots at six instances (launch_small.hpp)
   int pipeline = 2;         // NDLQR_PIPELINE: the pipeline depth a context starts with (NdlqrHipCtx::pipeline)
   bool no_top = false;      // NDLQR_NO_TOP=1: the last three tree levels as launches of their own (A/B timing of reduced_top_mc)
+  bool top_levels_set = false;  // ... NDLQR_TOP_LEVELS was given (the chain stands back for an A/B of reduced_top_mc)
   int top_levels = 3;       // tree levels inside reduced_top_mc (NDLQR_TOP_LEVELS, 3 .. 5): beyond three a wavefront takes several separators of the first ones in turn
   bool no_mfma = false;     // NDLQR_NO_MFMA=1: keep the scalar Schur kernel for large blocks (A/B timing)
   int sep_threads = 0;        // NDLQR_SEP_THREADS: workgroup size of the matrix-core separator (0 = by block size)

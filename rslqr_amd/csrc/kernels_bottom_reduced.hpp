@@ -1121,7 +1121,8 @@ __device__ __forceinline__ void bottom8_lds16_mc(const Dims& d, const double* __
 template <int NX>
 __device__ __forceinline__ void backsub_top_body(const Dims& d, const int b, const int t,
                                                  const double* __restrict__ recs, double* __restrict__ ytop,
-                                                 double* ytop_lds, const int bp = -1, const double* zsep = nullptr);
+                                                 double* ytop_lds, const int bp = -1, const double* zsep = nullptr,
+                                                 const int ltop = 0, const int nt = 256);
 template <int NX, int NU>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void reduced_top_mc(Dims d, const int l0, const double* __restrict__ AB,
                                                       const double* __restrict__ QR, const double* __restrict__ rhs,

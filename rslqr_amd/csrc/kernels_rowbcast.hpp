@@ -476,16 +476,19 @@ __global__ __launch_bounds__(64, 2) void rb_bottom(Dims d, const double* __restr
 //  level -- the workgroup of a problem's last three levels goes straight on to that problem's top-down sweep)
 // (bp, zsep: multiple right-hand sides per problem, rb_forward_top<.., MULTI> -- the records are those of problem bp, the
 //  z_sep of this right-hand side live in zsep[b][N][NX])
+// (ltop, nt: the levels ltop - 1 .. 3 alone, those above already in ytop_lds, by a workgroup of nt threads --
+//  reduced_chain_top, kernels_chain_top.hpp; ltop = 0: from the root, K - 1)
 template <int NX>
 __device__ __forceinline__ void backsub_top_body(const Dims& d, const int b, const int t,
                                                  const double* __restrict__ recs, double* __restrict__ ytop,
-                                                 double* ytop_lds, const int bp, const double* zsep) {
+                                                 double* ytop_lds, const int bp, const double* zsep, const int ltop,
+                                                 const int nt) {
   constexpr int NN = NX * NX, REC = 2 * NN + NX;
   const int N = d.N, K = d.K;
   const int br = bp >= 0 ? bp : b;
-  for (int L = K - 1; L >= 3; --L) {
+  for (int L = (ltop > 0 ? ltop : K) - 1; L >= 3; --L) {
     const int T = 2 << L, nsep = N >> (L + 1);
-    for (int it = t; it < nsep * NX; it += 256) {
+    for (int it = t; it < nsep * NX; it += nt) {
       const int q = it / NX, r = it - q * NX;
       const int base = q * T, s = base + (T >> 1) - 1;
       const double* rc = recs + ((size_t)br * N + s) * REC;
@@ -509,7 +512,7 @@ __device__ __forceinline__ void backsub_top_body(const Dims& d, const int b, con
     __syncthreads();
   }
   double* out = ytop + (size_t)b * (N >> 3) * NX;
-  for (int e = t; e < ((N >> 3) - 1) * NX; e += 256) out[e] = ytop_lds[e];
+  for (int e = t; e < ((N >> 3) - 1) * NX; e += nt) out[e] = ytop_lds[e];
 }
 
 template <int NX>

@@ -7,6 +7,7 @@
 #include "kernels_small.hpp"
 #include "kernels_bottom_reduced.hpp"
 #include "kernels_rowbcast.hpp"
+#include "kernels_chain_top.hpp"
 
 // Size-specialised launch sequences.
 //   separator-only ("reduced"): bottom kernel (leaf phase + levels 0, 1) -> one launch per upper level
@@ -35,6 +36,7 @@ struct SmallPlan {
   int level0;    // first tree level with a launch of its own (reduced_level_mc), up to ...
   int ltop;      // ... the first one inside reduced_top_mc (== K: no such launch), which starts at ...
   int top_l0;    // ... this level (level 2 may have gone with the bottom launch)
+  bool chain;       // the levels from ltop up as one block-tridiagonal chain per problem (reduced_chain_top) instead of reduced_top_mc
   bool top_sweeps;  // reduced_top_mc also runs the top-down sweep over the records of level >= 3 (else rb_backsub_top does)
   size_t top_lds;   // the sweep array of rb_backsub_top
   const char* schedule;  // ndlqr_hip_schedule
@@ -68,6 +70,11 @@ constexpr bool kCompact1Fits = ndlqr::P1OnMatrixCores<NX, NU>::value && NX >= 9 
 // pair1: the paired level-1 pass of the fused bottom launch leaves a wavefront's tile and couplings of t in its buffer
 template <int NX, int NU>
 constexpr bool kPair1Fits = kCompact1Fits<NX, NU> && ndlqr::McPair1Layout<NX>::SIZE <= ndlqr::ReducedLds<NX, NU>::NBUF;
+
+// top chain (reduced_chain_top): the instances where it measured faster than the launches it replaces (plan_small)
+template <int NX, int NU>
+constexpr bool kChainTopMeasured = (NX == 12 && NU == 4) || (NX == 10 && NU == 4) || (NX == 9 && NU == 3) ||
+                                   (NX == 8 && NU == 4) || (NX == 6 && NU == 3) || (NX == 13 && NU == 4);
 
 template <int NX, int NU, bool MULTI, class... Args>
 static void launch_rb_backsub(const NdlqrHipCtx* c, const dim3 grid, hipStream_t stream, const bool compact1,
@@ -180,6 +187,27 @@ static SmallPlan plan_small(const NdlqrHipCtx* c, const bool strict, const bool 
         // ... which also runs the top-down sweep over the records of level >= 3 when the back-substitution is the
         // two-launch form and its array fits the workgroup's LDS
         p.top_sweeps = p.ltop < d.K && p.compact && p.top_lds <= 4 * sizeof(ndlqr::ReducedLds<NX, NU, false>);
+        // The separators of level >= max(3, K - 5) as one block-tridiagonal chain per problem (reduced_chain_top,
+        // kernels_chain_top.hpp: at most 31 blocks, four problems per wavefront, one launch) in place of the level launches
+        // above that level and of reduced_top_mc; the levels below it keep reduced_level_mc, and the chain's launch runs the
+        // top-down sweep over their records. Only where no records of those levels are kept (the chain's scratch lies in
+        // their slots) and the sweep arrays of a workgroup's four problems fit its LDS. NDLQR_NO_TOP / NDLQR_TOP_LEVELS
+        // (A/B of reduced_top_mc) keep the tree. The default where the slowest of five runs was below
+        // the parent's fastest on the same box (profiles/chain_top_ab.txt): horizons of 256 knots at (12,4) 0.4911-0.4998
+        // -> 0.4636-0.4686 ms, the padded (11,3) 0.4786-0.4868 -> 0.4499-0.4554, (10,4) 0.4486-0.4506 -> 0.4202-0.4245, (9,3)
+        // 0.3858-0.3881 -> 0.3726-0.3777, (8,4) 0.3114-0.3195 -> 0.2951-0.3044, (6,3) 0.2217-0.2251 -> 0.2068-0.2088, (13,4)
+        // 0.7004-0.7134 -> 0.6651-0.6748 (x 1024). (12,4,1024) x 512, two level launches under a 31-block chain, touches the
+        // parent's range (0.9893-0.9995 -> 0.9762-0.9938) and stays on request, like every horizon that was not measured.
+        // NDLQR_TOP_CHAIN=0 / 1 overrides.
+        if constexpr (ndlqr::kChainTopFits<NX, NU>) {
+          p.chain = p.compact && !p.store_l && d.K >= 4 && !c->knobs.no_top && !c->knobs.top_levels_set &&
+                    sizeof(ndlqr::ChainTopLds<NX>) + 4 * p.top_lds <= kLdsMax &&
+                    (c->knobs.top_chain > 0 || (c->knobs.top_chain < 0 && d.K == 8 && kChainTopMeasured<NX, NU>));
+          if (p.chain) {
+            p.ltop = p.top_l0 = d.K - ndlqr::kChainTopMaxLevels > 3 ? d.K - ndlqr::kChainTopMaxLevels : 3;
+            p.top_sweeps = true;
+          }
+        }
       }
     }
   }
@@ -251,7 +279,18 @@ static int launch_small(NdlqrHipCtx* c, const SmallPlan& plan) {
         hipLaunchKernelGGL((ndlqr::reduced_level_mc<NX, NU>), dim3(d.N >> (l + 1), d.batch), dim3(64), 0, s.stream,
                            d, l, c->AB, c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l);
       }
-      if (plan.ltop < d.K) {
+      bool chained = false;
+      if constexpr (ndlqr::kChainTopFits<NX, NU>) {
+        if (plan.chain) {
+          ScopedSlot t(c, SLOT_TOP);
+          const size_t lds = 4 * plan.top_lds;
+          (void)allow_dynamic_lds(&ndlqr::reduced_chain_top<NX, NU>, lds);
+          hipLaunchKernelGGL((ndlqr::reduced_chain_top<NX, NU>), dim3((d.batch + 3) / 4), dim3(ndlqr::kChainTopThreads), lds,
+                             s.stream, d, plan.ltop, c->AB, c->QR, s.rhs, s.red, s.rec, c->info, s.ytop);
+          chained = true;
+        }
+      }
+      if (!chained && plan.ltop < d.K) {
         ScopedSlot t(c, SLOT_TOP);  // (a profile slot of its own: one kernel name per slot, like rocprofv3's per-kernel averages)
         hipLaunchKernelGGL((ndlqr::reduced_top_mc<NX, NU>), dim3(d.batch), dim3(256), 0, s.stream, d, plan.top_l0, c->AB,
                            c->QR, s.rhs, s.red, s.rec, c->F, c->info, store_l, plan.top_sweeps ? s.ytop : (double*)nullptr);

@@ -126,8 +126,10 @@ static DevKnobs read_knobs() {
   onoff("NDLQR_COMPACT1", &k.compact1);          // unset: by instance (launch_small)
   onoff("NDLQR_PAIR1", &k.pair1);                // unset: by instance (launch_small)
   onoff("NDLQR_BOTTOM_LDS16", &k.bottom_lds16);  // unset: by instance (launch_small)
+  onoff("NDLQR_TOP_CHAIN", &k.top_chain);        // unset: by instance (launch_small)
   k.no_mfma = getenv("NDLQR_NO_MFMA") != nullptr;
   k.no_top = getenv("NDLQR_NO_TOP") != nullptr;
+  k.top_levels_set = getenv("NDLQR_TOP_LEVELS") != nullptr;
   num("NDLQR_TOP_LEVELS", &k.top_levels);
   if (k.top_levels < 3 || k.top_levels > 5) k.top_levels = 3;
   num("NDLQR_SEP_THREADS", &k.sep_threads);
@@ -838,6 +840,7 @@ static SolvePlan plan_solve(const NdlqrHipCtx* c) {
     p.kept.rec1_compact = p.small.compact1;
     p.kept.level1_paired = p.small.pair1;
     p.kept.bottom_lds16 = p.small.lds16;
+    p.kept.top_chain = p.small.chain;
   } else if ((p.red = plan_reduced_generic(c)).ok) {
     p.family = Family::GenericReduced;
     p.needs_red_generic = true;
@@ -1915,6 +1918,7 @@ int ndlqr_hip_compact_level1(const NdlqrHipCtx* c) { return c && c->kept.rec1_co
 
 int ndlqr_hip_level1_paired(const NdlqrHipCtx* c) { return c && c->kept.level1_paired ? 1 : 0; }
 int ndlqr_hip_bottom_lds16(const NdlqrHipCtx* c) { return c && c->kept.bottom_lds16 ? 1 : 0; }
+int ndlqr_hip_top_chain(const NdlqrHipCtx* c) { return c && c->kept.top_chain ? 1 : 0; }
 
 int ndlqr_hip_factors_valid(const NdlqrHipCtx* c) { return c && c->kept.fact_valid ? 1 : 0; }
 

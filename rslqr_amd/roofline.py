@@ -123,6 +123,49 @@ def reduced_model(n, m, N, compact_level0=False, fused2=False, compact_level1=Fa
     return out
 
 
+def chain_block_flops(n, w):
+    """Useful flops of one block of the top chain (reduced_chain_top): S-bar and the rhs column, Cholesky, the forward
+    substitution of the n + 1 panel columns, the update of the next block (Y'Y symmetric in exact arithmetic, computed in
+    full, and Y'v), and in the backward sweep Y y and one triangular solve."""
+    leaf = 2 * n * n * w + 2 * n * w
+    return leaf + n ** 3 / 3.0 + n * n * (n + 1) + 2 * n * n * (n + 1) + 2 * n * n + n * n
+
+
+def chain_top_model(base, n, m, N, fused2):
+    """`base` (reduced_model with compact level-0 records) with the separators of level >= l0 = max(3, K - 5) eliminated as
+    one block-tridiagonal chain per problem in one launch (profile slot "top"): per block the used part of its slot with
+    ONE coupling block, the inputs of its two knots, and its scratch (L | Y | v in the record slot) written once and read
+    once; the levels below l0 keep their launches ("upper"), and the top-down sweep over their records runs behind the
+    chain."""
+    K = int(math.log2(N))
+    if K < 4:
+        return base
+    w, rows = n + m, 2 * n + m
+    tri = n * (n + 1) // 2
+    rec = record_doubles(n, 2)
+    l0 = max(3, K - 5)
+    blocks = (1 << (K - l0)) - 1
+    slot = 2 * tri + 2 * n * n + 2 * n
+    push = 2 * tri + n * n + 2 * n
+    per_sep = slot + n * w + w + n + rows + 2 * n + rec + push      # a separator in a level launch (reduced_model)
+    per_block = (2 * tri + n * n + 2 * n) + n * w + w + n + rows + 2 * n + 2 * rec
+    level0 = 3 if fused2 else 2
+    left = sum(N >> (l + 1) for l in range(level0, l0))
+    swept = sum(N >> (l + 1) for l in range(3, l0))
+    out = dict(base)
+    if "top" not in out:  # (K = 4: the sweep was rb_backsub_top's, inside "apply")
+        sweep_b = (N // 8 - 1) * rec + (N // 8) * n
+        out["apply"] = {"bytes": out["apply"]["bytes"] - 8 * sweep_b, "flops": out["apply"]["flops"] - (N // 8 - 1) * 4 * n * n,
+                        "launches": 1}
+    out["top"] = {"bytes": 8 * (blocks * per_block + swept * rec + (N // 8) * n),
+                  "flops": blocks * chain_block_flops(n, w) + swept * 4 * n * n, "launches": 1}
+    if left > 0:
+        out["upper"] = {"bytes": 8 * left * per_sep, "flops": left * separator_flops(n, w), "launches": l0 - level0}
+    else:
+        out.pop("upper", None)
+    return out
+
+
 def knot_lean_model(n, m, N):
     """Knot-based lean schedule (bottom_small + level_small + backsub_small): the bottom kernel hands
     the first / last knot of every four-knot group over (E, one live outer column, rhs)."""
@@ -203,17 +246,21 @@ def generic_reduced_model(n, m, N):
     }
 
 
-def model_for(schedule, n, m, N, compact1=False):
+def model_for(schedule, n, m, N, compact1=False, chain=False):
     """Per-slot model of the named launch sequence (ndlqr_hip_schedule), or None when this file has no
     model for it (strict / KEEP schedules stream the whole factor array: model (B) is their roofline).
     compact1: the solve kept compact level-1 records (BatchSolver.compact_level1(); "reduced" and "reduced-fused2"
     only). The name alone does not tell, and without the argument the model is that of full level-1 records: 1.8 KB per
     four knots more than such a solve moves at (12,4), so the fractions it yields for `bottom` and `apply` are upper
-    bounds."""
+    bounds.
+    chain: the solve ran its top levels as one block-tridiagonal chain (BatchSolver.top_chain(); the same two schedules):
+    the `upper` and `top` slots carry the level launches that are left and the chain's bytes and flops."""
     if schedule == "reduced":  # compact level-0 records, two-launch back-substitution
-        return reduced_model(n, m, N, compact_level0=True, compact_level1=compact1)
+        base = reduced_model(n, m, N, compact_level0=True, compact_level1=compact1)
+        return chain_top_model(base, n, m, N, False) if chain else base
     if schedule == "reduced-fused2":  # ... with tree level 2 inside the bottom launch (NDLQR_FUSE2=1)
-        return reduced_model(n, m, N, compact_level0=True, fused2=True, compact_level1=compact1)
+        base = reduced_model(n, m, N, compact_level0=True, fused2=True, compact_level1=compact1)
+        return chain_top_model(base, n, m, N, True) if chain else base
     if schedule in ("reduced-tree", "reduced-records"):
         return reduced_model(n, m, N)
     if schedule == "knot-lean":
